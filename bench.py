@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: spawns one rank per GPU itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (ranks from the environment)
+  python bench.py ... --dump-outputs DIR      (also writes what the last timed step returned to DIR/*.npy: see dump_outputs)
 
 A "step" is one pass of the hot path over one batch: `--batch` (default 32) independent
 NORMAL_CLONEs of a 2048x2048 ROI per GPU (mask stage + fused pre-process + Poisson solve + float-table
@@ -69,7 +70,16 @@ def parse_args(argv=None):
     ap.add_argument("--reference-table", action="store_true",
                     help="instead of the flagship line: the reference's own published table (PDF p3) -- end-to-end latency of the drop-in "
                          "call at source patches 154x100, 300x194, 592x592, 2400x1552, its protocol (1 warm-up + 50 rounds), the CPU port beside it")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the batch's cloned destinations) to DIR/*.npy "
+                         "in float32 / float64: a fixed, seeded sample of pixel positions of every image, the positions, and every image's "
+                         "per-channel sums over all its pixels (at most 64 MB in all) -- two builds run with the same arguments compare file for file")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.reference_table:
+        ap.error("--dump-outputs applies to the flagship line, not to --reference-table")
+    return args
 
 
 def synth(roi, rank):
@@ -505,6 +515,38 @@ def c5_projection_leg(capi, reps=8):
                     "communication one -- NOT a measured 8-GPU number"}
 
 
+DUMP_BUDGET = 48 << 20      # --dump-outputs: bytes of array data, all ranks together (64 MB at most, .npy headers included)
+
+
+def dump_outputs(out_dir, read_image, n, shape, rank, world, seed=20251015):
+    """--dump-outputs: what the timed path returned in its last step -- the n destinations, cloned in place -- as .npy files two builds
+    can compare output for output.  A fixed, seeded sample of pixel positions (the same for every image, every rank and every run with
+    the same arguments; all of them when the batch fits the budget) stands for the images; the per-channel sums cover every pixel.
+      clone_samples    float32 (n, S, 3)  the images' B, G, R values at the sampled positions
+      sample_yx        float64 (S, 2)     the positions (row, column) in the destination image
+      clone_channel_sums float64 (n, 3)   per-channel sum of every pixel of each image (exact)
+    With N > 1 ranks every rank writes its own images, the names suffixed _rank<r>, within budget / N."""
+    import numpy as np
+    H, W = shape[:2]
+    S = max(1, min(H * W, (DUMP_BUDGET // world - n * 3 * 8) // (n * 3 * 4 + 2 * 8)))
+    flat = np.sort(np.random.default_rng(seed).choice(H * W, size=S, replace=False))
+    ys, xs = np.divmod(flat, W)
+    samples = np.empty((n, S, 3), np.float32)
+    sums = np.empty((n, 3), np.float64)
+    for k in range(n):
+        img = read_image(k)
+        samples[k] = img[ys, xs, :]
+        sums[k] = img.reshape(-1, 3).sum(axis=0, dtype=np.float64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {"clone_samples" + sfx: samples, "sample_yx" + sfx: np.stack([ys, xs], axis=1).astype(np.float64),
+              "clone_channel_sums" + sfx: sums}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "images": n, "pixels_sampled_per_image": int(S), "pixels_per_image": int(H * W)}
+
+
 def launch_ranks(args):
     """--gpus N > 1 without a launcher: one fresh child process per rank, started BEFORE this process touches HIP
     (it never does: the library is only loaded by the children).  Rank 0's JSON line is forwarded."""
@@ -603,6 +645,11 @@ def main():
     t_rank = []
     elapsed = timed_region(comm, sync_all, lambda: [step() for _ in range(args.steps)], t_rank)
     per_rank_ms = [round(t * 1e3, 3) for t in comm.gather(t_rank[0])]          # this rank's own elapsed time, every rank's on rank 0
+    # what the last timed step returned, read back before any later leg runs the step again with other settings
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, lambda k: inst.from_device(jobs[k]["b"], jobs[k]["bs"] + (3,)), args.batch, jobs[0]["bs"],
+                              comm.rank, comm.world)
     group_cycles = max(i.info().sweeps for i in pool.instances)
     devices = comm.gather(float(inst.info().device))
     # the same timed step with float32 storage throughout (field between the level-0 launches, right-hand side, level 1): what the
@@ -1049,6 +1096,8 @@ def main():
         "mixed_sizes": mixed_sizes,
         "c5_projected_at_8": c5_projected,
     }
+    if dumped:
+        line["dump_outputs"] = dumped
     if comm.rank == 0 and args.gpus == 1 and args.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(dst, patch, mask, cx, cy, out_float, out_exact, args.cpu_seconds)
     elif comm.rank == 0:
