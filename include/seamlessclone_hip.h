@@ -13,7 +13,8 @@
  * Images are 8-bit, BGR interleaved (CV_8UC3) for face/body and single channel (CV_8UC1)
  * for mask, `step` = bytes per row.  All sc_hip_* entry points are additions: solver
  * options, a device-resident run for callers whose images already live in HBM, run
- * statistics, and stage-level hooks used by the parity tests.
+ * statistics and a batch driver.  The stage-level hooks used by the parity tests are in
+ * seamlessclone_hip_testing.h, which integrators do not need.
  *
  * Threading: one instance <-> one HIP stream <-> one host thread at a time (reference:
  * one instance per stream, not re-entrant).  No process-global state.
@@ -116,7 +117,7 @@ typedef struct sc_solver_opts {
     int   mg_direct_max;     /* multigrid bottom kernel: the first level whose sides are both at most this many unknowns is solved
                                 directly (fast diagonalisation); the LDS-resident levels above it cycle.  0 = default
                                 (SC_MG_DIRECT_MAX_DEFAULT); at most 128.  Same fixed point, slightly different iterates        */
-    int   legacy_paths;      /* read only with SC_FLAG_LEGACY_PATHS: SC_LEGACY_* bits, the superseded launch forms to run instead of
+    int   legacy_paths;      /* read only with SC_FLAG_LEGACY_PATHS (seamlessclone_hip_testing.h): SC_LEGACY_* bits, the superseded launch forms to run instead of
                                 the defaults (A/B measurements and cross-checks of kernels whose decision is made)              */
 } sc_solver_opts;
 #define SC_MG_DIRECT_MAX_DEFAULT 128
@@ -144,28 +145,7 @@ typedef struct sc_solver_opts {
                                             eigenvalue tables are stored and combined in float32
                                             (seamlessClone_imp.cpp:596-599, :1651-1653) -- see DESIGN.md sec. 5,
                                             "float-table correction"                                            */
-#define SC_FLAG_LEGACY_PATHS   (1 << 6)  /* run the superseded launch forms named in sc_solver_opts.legacy_paths (round 5: one switch for the
-                                            A/B scaffolding of decisions that are made; rounds 2-4 had a public flag for each):           */
-#define SC_LEGACY_SEPARATE_RESTRICT 1    /*   float-table correction: the hat-weighted cell sums of the field come from a pass of their own
-                                            over it (k_lm_restrict); default: the level-0 multigrid launch that writes the field leaves them
-                                            behind.  Same cells, another order of the additions (differences at float rounding level)     */
-#define SC_LEGACY_BOTTOM_F32   2         /*   multigrid: the bottom kernel's direct solve as float32 SIMD inner products with every operand
-                                            staged in LDS (k_mg_bottom, rounds 1-3) on the hierarchy of those rounds.  Default since round 4
-                                            where the bottom's first level has at most 96 unknowns per side: four products on the matrix
-                                            cores in float32 (v_mfma_f32_32x32x2_f32: k_mg_bottom_mm).  Same arithmetic up to the order of
-                                            the additions                                                                               */
-#define SC_LEGACY_SEPARATE_TAIL 4        /*   multigrid: the level above the bottom and the bottom as the three launches of rounds 1-3
-                                            (pre-smoothing + residual + restriction, direct solve, prolongation + post-smoothing).  Default
-                                            since round 4 where that level has at most 127 unknowns per side: ONE launch, the level in
-                                            registers (k_mg_tail).  Same arithmetic per point                                            */
-#define SC_FLAG_KEEP_FIELD     (1 << 7)  /* sc_hip_run*: keep the solution field on the device (sc_hip_field_store,
-                                            _residual, _finish after a run): the last multigrid cycle writes the field
-                                            and a post-process launch reads it.  Default: that cycle writes the output
-                                            bytes itself and no final field exists (those hooks then fail with
-                                            SC_ERR_BAD_ARG); the float-table node correction it adds is the one of the
-                                            iterate one cycle earlier (difference at most 0.05 grey levels in the worst case the stop rule admits,
-                                            0.001-0.003 measured; ROIs where
-                                            that bound does not hold take this flag's path by themselves)        */
+/* bits 6, 7 and 14 are taken by seamlessclone_hip_testing.h (SC_FLAG_LEGACY_PATHS, SC_FLAG_KEEP_FIELD, SC_FLAG_POISON_ARENA): do not reuse them */
 
 #define SC_FLAG_FFT_FP64       (1 << 8)  /* SC_METHOD_FFT: the transforms in double instead of float32 (tables, LDS and the planes
                                             between the launches); at most 4096 unknowns per side.  No transform rounding is left:
@@ -210,11 +190,6 @@ typedef struct sc_solver_opts {
                                             thread cloning into a disjoint ROI of the same image would lose its result).  Default: the result
                                             comes back as the compact ROI through pinned staging and is spliced into the caller's rows -- only
                                             ROI bytes of the caller's image are ever written, as in the reference (seamlessClone_imp.cpp:470-483) */
-
-#define SC_FLAG_POISON_ARENA   (1 << 14) /* testing: every device block the arena hands out -- or hands out AGAIN -- WITHOUT zeroing it (fields,
-                                            level planes, image staging: "written before they are read") is filled with 0xFF bytes first -- NaN as float32 and
-                                            float16 -- which is what RECYCLED device memory may hold (fresh memory reads as zero and hides a
-                                            read of something never written).  Results must not change (tests/test_gpu_round5.py)            */
 
 /* ---- statistics of the last run */
 typedef struct sc_run_info {
@@ -303,44 +278,6 @@ SC_API int   sc_hip_device_pci_bus_id(int gpu_id, char *buf, int len);
 SC_API void *sc_hip_host_alloc(void *instance, size_t bytes);
 SC_API void  sc_hip_host_free(void *instance, void *hptr);
 
-/* ---- stage-level hooks (parity tests drive each kernel through these) ------------------- */
-
-/* mask stage only (seamlessClone_imp.cpp:978-1071): geo = {x0,y0,W,H,ltx,lty}; M_out
- * receives the 3x eroded ROI mask, dense W*H bytes (may be NULL). */
-SC_API int sc_hip_mask_stage(void *instance, const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
-                      int centerX, int centerY, int geo[6], uint8_t *M_out, size_t M_capacity);
-
-/* mask stage + fused pre-process (seamlessClone_imp.cpp:1920-2018): downloads the dst-ROI
- * field B and the un-folded RHS lap, planar [3][H][W] float32, channel = BGR index. */
-SC_API int sc_hip_build_rhs(void *instance,
-                     const uint8_t *face, int face_cols, int face_rows, int face_step,
-                     const uint8_t *body, int body_cols, int body_rows, int body_step,
-                     const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
-                     int centerX, int centerY, int geo[6], float *B_out, float *lap_out, size_t plane_capacity);
-
-/* solver-only hooks on caller-supplied fields, planar [C][H][W] float32 (ring included). */
-SC_API int sc_hip_field_load(void *instance, int W, int H, int C, const float *U, const float *lap);
-SC_API int sc_hip_field_sweep(void *instance, int method, int sweeps, float omega, int sweeps_per_launch);
-SC_API int sc_hip_field_residual(void *instance, double out[2] /* sum r^2, sum lap^2 */);
-SC_API int sc_hip_field_solve(void *instance);                      /* run the configured solver on the loaded field */
-SC_API int sc_hip_field_shape(void *instance, int whc[3]);   /* W, H, C of the fields currently on the device */
-SC_API int sc_hip_field_store(void *instance, float *U_out, size_t capacity_floats);
-
-/* post-process alone (seamlessClone_imp.cpp:2078-2103 and the host splice :470-483) on the field currently on the
- * device (sc_hip_field_load, or what a solve left): clamp to [0,255], truncate, interleave the interior of the
- * 3-channel field into the host image `body` with the ROI origin at (ltx, lty). */
-SC_API int sc_hip_field_finish(void *instance, uint8_t *body, int body_cols, int body_rows, int body_step, int ltx, int lty);
-/* float-table correction alone on the field currently on the device: the result becomes
- * result + correction, i.e. the exact solution of the 5-point system turns into what the reference's float32
- * eigenvalue tables give (seamlessClone_imp.cpp:596-599, :1651-1653). */
-SC_API int sc_hip_field_lowmode(void *instance);
-
-/* microbenchmark hook used by bench.py: runs `launches` launches of the sweep kernel
- * (method, sweeps_per_launch) on the loaded field and returns the mean launch time measured
- * with hipEvents on the instance stream. */
-SC_API int sc_hip_field_time_sweeps(void *instance, int method, int launches, int sweeps_per_launch, float omega,
-                             float *ms_per_launch);
-
 /* ---- native batch driver: K instances (HIP streams) on one GPU, one host thread each ----------
  * Clones are independent; several in flight hide one another's latency-bound phases.  Jobs are
  * pulled from a shared counter, each runs exactly once, sc_hip_pool_run returns when all are done. */
@@ -379,38 +316,22 @@ SC_API int   sc_hip_pool_run(void *pool, sc_batch_job *jobs, int n, int device_r
 #define SC_POOL_GROUP_AUTO 0
 SC_API int   sc_hip_pool_set_group(void *pool, int group);
 
-/* isolated timing of the fused level-0 multigrid cycle kernel on the state left by the last
- * MULTIGRID run (values are discarded; bench.py roofline) */
-SC_API int sc_hip_time_cycle0(void *instance, int launches, float *ms_per_launch);
-/* ... and of the other three level-0 launches a fast-path solve is made of, each under a second symbol of its own:
- * form 0 = the full cycle (as sc_hip_time_cycle0), 1 = the full cycle before the judged one (16-bit field in, float out, leaves the
- * float-table correction's cell shares), 2 = the judged cycle (two sweeps, output bytes), 3 = the first launch of a solve (two
- * sweeps from the float16 initial field, no prolongation).  SC_ERR_BAD_ARG unless the last run was a default multigrid solve. */
-SC_API int sc_hip_time_cycle0_form(void *instance, int form, int launches, float *ms_per_launch);
-/* measurement: the launch-bound part of a multigrid cycle (levels 2 .. bottom .. 2 of the hierarchy the last multigrid run left,
- * `*launches` dependent launches) `reps` times as plain launches and as replays of ONE captured HIP graph: ms per pass of each */
-SC_API int sc_hip_time_coarse_chain(void *instance, int reps, float *ms_eager, float *ms_graph, int *launches);
-/* measurement: the shader clock at the eleven phase boundaries of ONE k_mg_tail launch (the level above the bottom and the bottom in one
- * launch, SC_FLAG_SEPARATE_TAIL) on the hierarchy the last multigrid run left: entry | right-hand side loaded | pre-smoothing | residual +
- * restriction | the four products of the direct solve | prolongation | post-smoothing | stores issued.  SC_ERR_BAD_ARG unless that
- * hierarchy runs its bottom this way. */
-SC_API int sc_hip_time_tail_phases(void *instance, unsigned long long *cycles11);
-
 /* Host-only (needs no GPU): how sc_hip_run_device_batch / the pool would partition a batch whose members have these ROI sizes
  * (wh[2i], wh[2i+1]: width and height, ring included) under `opts` (NULL: the defaults), at most `cap` members per group (<= 0: no
  * limit): group_of[i] = the member's group, kind_of[i] (may be NULL) = 0 alone, 1 a same-size group, 2 a size class (different
  * sizes, the same solve: csrc/sc_ragged.cpp; the member's bytes are those of its solo run), 3 a size class on another hierarchy than
  * the member's solo run takes (a small ROI, or the leftover of a class moved onto the next deeper one: within one grey level of the
  * solo run).  Returns the number of groups, or SC_ERR_BAD_ARG. */
+SC_API int sc_hip_plan_groups(const int *wh, int n, int cap, const sc_solver_opts *opts, int *group_of, int *kind_of);
+/* ... and how sc_hip_pool_run would: a pool of `streams` workers with group size `group` (SC_POOL_GROUP_AUTO allowed), jobs handed
+ * to the planner largest first */
+SC_API int sc_hip_plan_groups_pool(const int *wh, int n, int group, int streams, const sc_solver_opts *opts, int *group_of, int *kind_of);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a
  * class it runs the general hierarchy and comes out within one grey level of its solo run instead of with its bytes), conditional
  * (1: the float tables' lowest modes are off by more than 4 % at this size; such members form classes of their own, in which the
  * judged cycle's measured update decides the output's form for the whole group) } */
-/* ... and how sc_hip_pool_run would: a pool of `streams` workers with group size `group` (SC_POOL_GROUP_AUTO allowed), jobs handed
- * to the planner largest first */
-SC_API int sc_hip_plan_groups_pool(const int *wh, int n, int group, int streams, const sc_solver_opts *opts, int *group_of, int *kind_of);
 SC_API int sc_hip_plan_size(int W, int H, const sc_solver_opts *opts, int out[12]);
 /* Host-only: plans and per-size host tables (the float-table correction's ratio table, its part maps) are pure functions of the ROI
  * size and memoised process-wide on first use -- 5-20 us of host arithmetic per NEW size, paid inside the first batch call that meets
@@ -419,18 +340,12 @@ SC_API int sc_hip_plan_size(int W, int H, const sc_solver_opts *opts, int out[12
  * sc_hip_plan_cache_clear forgets everything memoised (tests and measurements). */
 SC_API int sc_hip_plan_prepare(const int *wh, int n, const sc_solver_opts *opts);
 SC_API void sc_hip_plan_cache_clear(void);
-SC_API int sc_hip_plan_groups(const int *wh, int n, int cap, const sc_solver_opts *opts, int *group_of, int *kind_of);
 
 /* Host-only (needs no GPU): 1 when the reference's float32 eigenvalue tables are singular for an ROI of w x h unknowns --
  * (float)(2 cos(PI/(n+1))) is exactly 2.0f in both directions (n >= ~12 870), so the reference's denominator
  * filter_X[0] + filter_Y[0] - 4 (seamlessClone_imp.cpp:1651-1653) is zero and its result undefined.  For such ROIs the
  * default path and SC_METHOD_DST return the exact system's solution (as SC_FLAG_EXACT_TABLES does). */
 SC_API int sc_hip_reference_tables_singular(int w, int h);
-
-/* host-only self test (needs no GPU): the parked-thread row copier of the host path and the tridiagonal
- * eigen-solver behind the direct bottom solve (residual of T V = V L for level operators with an irregular
- * last interval).  Returns 0, or the number of the check that failed. */
-SC_API int sc_hip_selftest_host(void);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,110 @@
+/*
+ * seamlessclone_hip_testing.h -- the test and measurement surface of libseamlessclone_hip.so (MI355X / gfx950).
+ *
+ * Not part of the drop-in boundary: an integrator includes seamlessclone_hip.h only.  What is declared here serves the
+ * parity tests, bench.py and the tools: the flags that run superseded launch forms or debugging aids, the stage-level
+ * hooks that drive one kernel at a time, the microbenchmarks and the host-only self test.  The symbols come from the
+ * same library.
+ */
+#ifndef SEAMLESSCLONE_HIP_TESTING_H
+#define SEAMLESSCLONE_HIP_TESTING_H
+
+#include "seamlessclone_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- sc_solver_opts.flags bits for tests and measurements (the drop-in header leaves bits 6, 7 and 14 to them) */
+#define SC_FLAG_LEGACY_PATHS   (1 << 6)  /* run the superseded launch forms named in sc_solver_opts.legacy_paths (round 5: one switch for the
+                                            A/B scaffolding of decisions that are made; rounds 2-4 had a public flag for each):           */
+#define SC_LEGACY_SEPARATE_RESTRICT 1    /*   float-table correction: the hat-weighted cell sums of the field come from a pass of their own
+                                            over it (k_lm_restrict); default: the level-0 multigrid launch that writes the field leaves them
+                                            behind.  Same cells, another order of the additions (differences at float rounding level)     */
+#define SC_LEGACY_BOTTOM_F32   2         /*   multigrid: the bottom kernel's direct solve as float32 SIMD inner products with every operand
+                                            staged in LDS (k_mg_bottom, rounds 1-3) on the hierarchy of those rounds.  Default since round 4
+                                            where the bottom's first level has at most 96 unknowns per side: four products on the matrix
+                                            cores in float32 (v_mfma_f32_32x32x2_f32: k_mg_bottom_mm).  Same arithmetic up to the order of
+                                            the additions                                                                               */
+#define SC_LEGACY_SEPARATE_TAIL 4        /*   multigrid: the level above the bottom and the bottom as the three launches of rounds 1-3
+                                            (pre-smoothing + residual + restriction, direct solve, prolongation + post-smoothing).  Default
+                                            since round 4 where that level has at most 127 unknowns per side: ONE launch, the level in
+                                            registers (k_mg_tail).  Same arithmetic per point                                            */
+#define SC_FLAG_KEEP_FIELD     (1 << 7)  /* sc_hip_run*: keep the solution field on the device (sc_hip_field_store,
+                                            _residual, _finish after a run): the last multigrid cycle writes the field
+                                            and a post-process launch reads it.  Default: that cycle writes the output
+                                            bytes itself and no final field exists (those hooks then fail with
+                                            SC_ERR_BAD_ARG); the float-table node correction it adds is the one of the
+                                            iterate one cycle earlier (difference at most 0.05 grey levels in the worst case the stop rule admits,
+                                            0.001-0.003 measured; ROIs where
+                                            that bound does not hold take this flag's path by themselves)        */
+
+#define SC_FLAG_POISON_ARENA   (1 << 14) /* testing: every device block the arena hands out -- or hands out AGAIN -- WITHOUT zeroing it (fields,
+                                            level planes, image staging: "written before they are read") is filled with 0xFF bytes first -- NaN as float32 and
+                                            float16 -- which is what RECYCLED device memory may hold (fresh memory reads as zero and hides a
+                                            read of something never written).  Results must not change (tests/test_gpu_round5.py)            */
+
+/* ---- stage-level hooks (parity tests drive each kernel through these) ------------------- */
+
+/* mask stage only (seamlessClone_imp.cpp:978-1071): geo = {x0,y0,W,H,ltx,lty}; M_out
+ * receives the 3x eroded ROI mask, dense W*H bytes (may be NULL). */
+SC_API int sc_hip_mask_stage(void *instance, const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
+                      int centerX, int centerY, int geo[6], uint8_t *M_out, size_t M_capacity);
+
+/* mask stage + fused pre-process (seamlessClone_imp.cpp:1920-2018): downloads the dst-ROI
+ * field B and the un-folded RHS lap, planar [3][H][W] float32, channel = BGR index. */
+SC_API int sc_hip_build_rhs(void *instance,
+                     const uint8_t *face, int face_cols, int face_rows, int face_step,
+                     const uint8_t *body, int body_cols, int body_rows, int body_step,
+                     const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
+                     int centerX, int centerY, int geo[6], float *B_out, float *lap_out, size_t plane_capacity);
+
+/* solver-only hooks on caller-supplied fields, planar [C][H][W] float32 (ring included). */
+SC_API int sc_hip_field_load(void *instance, int W, int H, int C, const float *U, const float *lap);
+SC_API int sc_hip_field_sweep(void *instance, int method, int sweeps, float omega, int sweeps_per_launch);
+SC_API int sc_hip_field_residual(void *instance, double out[2] /* sum r^2, sum lap^2 */);
+SC_API int sc_hip_field_solve(void *instance);                      /* run the configured solver on the loaded field */
+SC_API int sc_hip_field_shape(void *instance, int whc[3]);   /* W, H, C of the fields currently on the device */
+SC_API int sc_hip_field_store(void *instance, float *U_out, size_t capacity_floats);
+
+/* post-process alone (seamlessClone_imp.cpp:2078-2103 and the host splice :470-483) on the field currently on the
+ * device (sc_hip_field_load, or what a solve left): clamp to [0,255], truncate, interleave the interior of the
+ * 3-channel field into the host image `body` with the ROI origin at (ltx, lty). */
+SC_API int sc_hip_field_finish(void *instance, uint8_t *body, int body_cols, int body_rows, int body_step, int ltx, int lty);
+/* float-table correction alone on the field currently on the device: the result becomes
+ * result + correction, i.e. the exact solution of the 5-point system turns into what the reference's float32
+ * eigenvalue tables give (seamlessClone_imp.cpp:596-599, :1651-1653). */
+SC_API int sc_hip_field_lowmode(void *instance);
+
+/* microbenchmark hook used by bench.py: runs `launches` launches of the sweep kernel
+ * (method, sweeps_per_launch) on the loaded field and returns the mean launch time measured
+ * with hipEvents on the instance stream. */
+SC_API int sc_hip_field_time_sweeps(void *instance, int method, int launches, int sweeps_per_launch, float omega,
+                             float *ms_per_launch);
+
+/* isolated timing of the fused level-0 multigrid cycle kernel on the state left by the last
+ * MULTIGRID run (values are discarded; bench.py roofline) */
+SC_API int sc_hip_time_cycle0(void *instance, int launches, float *ms_per_launch);
+/* ... and of the other three level-0 launches a fast-path solve is made of, each under a second symbol of its own:
+ * form 0 = the full cycle (as sc_hip_time_cycle0), 1 = the full cycle before the judged one (16-bit field in, float out, leaves the
+ * float-table correction's cell shares), 2 = the judged cycle (two sweeps, output bytes), 3 = the first launch of a solve (two
+ * sweeps from the float16 initial field, no prolongation).  SC_ERR_BAD_ARG unless the last run was a default multigrid solve. */
+SC_API int sc_hip_time_cycle0_form(void *instance, int form, int launches, float *ms_per_launch);
+/* measurement: the launch-bound part of a multigrid cycle (levels 2 .. bottom .. 2 of the hierarchy the last multigrid run left,
+ * `*launches` dependent launches) `reps` times as plain launches and as replays of ONE captured HIP graph: ms per pass of each */
+SC_API int sc_hip_time_coarse_chain(void *instance, int reps, float *ms_eager, float *ms_graph, int *launches);
+/* measurement: the shader clock at the eleven phase boundaries of ONE k_mg_tail launch (the level above the bottom and the bottom in one
+ * launch, the default; SC_LEGACY_SEPARATE_TAIL runs three) on the hierarchy the last multigrid run left: entry | right-hand side loaded | pre-smoothing | residual +
+ * restriction | the four products of the direct solve | prolongation | post-smoothing | stores issued.  SC_ERR_BAD_ARG unless that
+ * hierarchy runs its bottom this way. */
+SC_API int sc_hip_time_tail_phases(void *instance, unsigned long long *cycles11);
+
+/* host-only self test (needs no GPU): the parked-thread row copier of the host path and the tridiagonal
+ * eigen-solver behind the direct bottom solve (residual of T V = V L for level operators with an irregular
+ * last interval).  Returns 0, or the number of the check that failed. */
+SC_API int sc_hip_selftest_host(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SEAMLESSCLONE_HIP_TESTING_H */

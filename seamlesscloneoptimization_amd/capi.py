@@ -16,6 +16,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.path.join(_PKG, "libseamlessclone_hip.so")
 HEADER_PATH = os.path.join(_ROOT, "include", "seamlessclone_hip.h")
+TESTING_HEADER_PATH = os.path.join(_ROOT, "include", "seamlessclone_hip_testing.h")      # test and measurement hooks, same library
 
 SC_OK = 0
 SC_ERR_BAD_ARG = -1
@@ -109,9 +110,10 @@ _IMG = [C.c_void_p, C.c_int, C.c_int, C.c_int]
 _lib = None
 
 
-def declared_symbols() -> list[str]:
-    """Every function name the public header declares (used by the CPU-side ABI test)."""
-    txt = open(HEADER_PATH).read()
+def declared_symbols(header: str | None = None) -> list[str]:
+    """Every function name `header` declares; by default both headers, the drop-in one and the testing one (used by the CPU-side
+    ABI test)."""
+    txt = "".join(open(h).read() for h in ([header] if header else [HEADER_PATH, TESTING_HEADER_PATH]))
     return sorted(set(re.findall(r"SC_API[^;(]*?\b((?:my_seamlessclone_api_imp_|sc_hip_)\w+)\s*\(", txt)))
 
 
@@ -431,43 +433,27 @@ class Instance:
                                                     float(omega), C.byref(ms)))
         return float(ms.value)
 
+    def time_cycle0(self, launches: int = 100) -> float:
+        ms = C.c_float(0)
+        self._check(self.L.sc_hip_time_cycle0(self.h, int(launches), C.byref(ms)))
+        return float(ms.value)
 
-def _time_cycle0(self, launches: int = 100) -> float:
-    ms = C.c_float(0)
-    self._check(self.L.sc_hip_time_cycle0(self.h, int(launches), C.byref(ms)))
-    return float(ms.value)
+    def time_cycle0_form(self, form: int, launches: int = 100) -> float:
+        ms = C.c_float(0)
+        self._check(self.L.sc_hip_time_cycle0_form(self.h, int(form), int(launches), C.byref(ms)))
+        return float(ms.value)
 
+    def time_coarse_chain(self, reps: int = 50):
+        """(ms per pass as plain launches, ms per pass as HIP-graph replays, dependent launches per pass)"""
+        a, b, n = C.c_float(0), C.c_float(0), C.c_int(0)
+        self._check(self.L.sc_hip_time_coarse_chain(self.h, int(reps), C.byref(a), C.byref(b), C.byref(n)))
+        return float(a.value), float(b.value), int(n.value)
 
-Instance.time_cycle0 = _time_cycle0
-
-
-def _time_cycle0_form(self, form: int, launches: int = 100) -> float:
-    ms = C.c_float(0)
-    self._check(self.L.sc_hip_time_cycle0_form(self.h, int(form), int(launches), C.byref(ms)))
-    return float(ms.value)
-
-
-Instance.time_cycle0_form = _time_cycle0_form
-
-
-def _time_coarse_chain(self, reps: int = 50):
-    """(ms per pass as plain launches, ms per pass as HIP-graph replays, dependent launches per pass)"""
-    a, b, n = C.c_float(0), C.c_float(0), C.c_int(0)
-    self._check(self.L.sc_hip_time_coarse_chain(self.h, int(reps), C.byref(a), C.byref(b), C.byref(n)))
-    return float(a.value), float(b.value), int(n.value)
-
-
-Instance.time_coarse_chain = _time_coarse_chain
-
-
-def _time_tail_phases(self):
-    """shader-clock differences between the eleven phase boundaries of one k_mg_tail launch (ten numbers)"""
-    buf = (C.c_ulonglong * 11)()
-    self._check(self.L.sc_hip_time_tail_phases(self.h, buf))
-    return [int(buf[i + 1]) - int(buf[i]) for i in range(10)]
-
-
-Instance.time_tail_phases = _time_tail_phases
+    def time_tail_phases(self):
+        """shader-clock differences between the eleven phase boundaries of one k_mg_tail launch (ten numbers)"""
+        buf = (C.c_ulonglong * 11)()
+        self._check(self.L.sc_hip_time_tail_phases(self.h, buf))
+        return [int(buf[i + 1]) - int(buf[i]) for i in range(10)]
 
 
 class _Borrowed(Instance):
@@ -596,13 +582,13 @@ def plan_groups(sizes, cap: int = 0, opts: "SolverOpts | None" = None):
 
 
 def source_fingerprint() -> str:
-    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, *.cpp, *.h and the public header).  Profiles under
+    """sha256 (16 hex digits) over the library's sources (csrc/*.hip, *.cpp, *.h and both headers).  Profiles under
     profiles/ record it; bench.py refuses to quote counter figures captured from other sources (traffic_stale)."""
     import glob
     import hashlib
     h = hashlib.sha256()
     files = sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hip")) + glob.glob(os.path.join(_PKG, "csrc", "*.cpp")) +
-                   glob.glob(os.path.join(_PKG, "csrc", "*.h")) + [HEADER_PATH])
+                   glob.glob(os.path.join(_PKG, "csrc", "*.h")) + [HEADER_PATH, TESTING_HEADER_PATH])
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())

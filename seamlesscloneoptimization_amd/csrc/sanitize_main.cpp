@@ -10,7 +10,7 @@
 //   3. the pool's hand-out of jobs against stub instances (sc_pool.cpp compiled with its instance calls renamed to the stubs
 //      below): groups formed, every job run exactly once, per-job codes copied back, several batches on one pool.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
-#include "../../include/seamlessclone_hip.h"
+#include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>

@@ -1,0 +1,353 @@
+// sc_batch.cpp -- the batch path: n device-resident clones on one instance (sc_hip_run_device_batch), partitioned into same-size
+// groups and size classes (sc_ragged.cpp), and the host-only planner exports (sc_hip_plan_*) that show how a batch would be split.
+#include "sc_instance.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace sc;
+
+// ---- n device-resident clones through ONE set of launches ------------------------------------------------------
+// The solver treats the channels of a field as independent planes, so n clones whose ROIs have the same size are one
+// field of 3n channels: every multigrid launch is n times larger (the coarse levels stop being launch-latency bound,
+// the level-1 grid fills whole rounds of workgroup slots) and there are 27 solver launches for the group instead of
+// 27 n.  Masks, positions and images are per clone (bounding box, erode, pre- and post-process each go out as one launch
+// for the group, blockIdx.z = member); the stop rule sees the largest correction of the group.
+// Round 5: the members of a call are PARTITIONED by ROI size -- every sub-group of two or more same-size members shares one
+// set of launches, the rest run alone -- instead of the whole call falling back to one clone at a time as soon as one member
+// differs (a batch of real clones has a mask box per face / frame).  A failing member, the reference's warm-up option and
+// OpenCV's grey-mask semantics still run one after the other through sc_hip_run_device.
+namespace {
+
+constexpr int GROUP_RS = 32;      // ints between the rectangles of a group's scans: one 128-byte line each (eight rectangles in one line: 162 us for the group's scan instead of 20)
+
+struct RagScope {      // leaves the size-class mode on every way out
+    Instance *I;
+    ~RagScope() { rag_end(I); }
+};
+
+// members idx[0..n) of `jobs` as one field of 3n channels: all with the same ROI size (plans == nullptr), or a SIZE CLASS (sc_ragged.cpp:
+// plans[k] = member idx[k]'s plan; the fields take the class's largest width and height).  guess: the predicted rectangles the
+// members were launched on (nullptr: their boxes are the device's), d_r: the device rectangles of ALL members of the call
+int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &idx, const std::vector<Geo> &geo, const int *guess, int *d_r,
+                      const std::vector<SizePlan> *plans)
+{
+    const int n = (int)idx.size();
+    Geo g0 = geo[idx[0]];
+    if (plans) for (int k = 1; k < n; ++k) { g0.W = std::max(g0.W, geo[idx[k]].W); g0.H = std::max(g0.H, geo[idx[k]].H); }
+    int rc;
+    I->mpitch = round_up(g0.W, 64);
+    const size_t mplane = (size_t)I->mpitch * g0.H;
+    if ((rc = ensure(I, I->d_M, mplane * n, false))) return rc;
+    if ((rc = setup_fields(I, g0.W, g0.H, 3 * n))) return rc;
+    RagScope scope{ I };
+    std::vector<MaskJob> mj(n);
+    std::vector<ImageJob> ij(n);
+    for (int k = 0; k < n; ++k) {
+        const int i = idx[k];
+        const sc_batch_job &j = jobs[i];
+        mj[k] = MaskJob{};
+        mj[k].mask = j.mask; mj[k].mw = j.mask_cols; mj[k].mh = j.mask_rows; mj[k].mstep = j.mask_step;
+        mj[k].rect = d_r + GROUP_RS * i;
+        mj[k].g = geo[i]; mj[k].M = (uint8_t *)I->d_M.p + mplane * k; mj[k].mpitch = I->mpitch;
+        ij[k].face_org = j.face + (size_t)geo[i].y0 * j.face_step + 3 * geo[i].x0; ij[k].fstep = j.face_step;
+        ij[k].body_org = j.body + (size_t)geo[i].lty * j.body_step + 3 * geo[i].ltx; ij[k].bstep = j.body_step;
+        ij[k].M = (const uint8_t *)I->d_M.p + mplane * k;
+        ij[k].d_rect = guess ? d_r + GROUP_RS * i : nullptr;
+        if (guess) { ij[k].rx0 = guess[4 * i]; ij[k].rx1 = guess[4 * i + 1]; ij[k].ry0 = guess[4 * i + 2]; ij[k].ry1 = guess[4 * i + 3]; }
+        if (plans) { ij[k].W = geo[i].W; ij[k].H = geo[i].H; }
+    }
+    // (a size class: the members' table goes up FIRST -- 9 us of host time, a 3-us copy in front of the erode -- so that the other
+    //  streams' builds, which wait for it, run beside the erode and the pre-process)
+    if (plans && (rc = rag_begin_table(I, *plans))) return rc;
+    bool builds_done = false;
+    launch_mask_erode3_group(mj.data(), n, I->stream);
+    I->erode_done = false;
+    int solve_rc = SC_OK;
+    for (;;) {
+        I->result_in_U1 = false;
+        I->f_half = mg_reads_half_rhs(I);
+        I->u_half = I->f_half && !(I->opts.flags & SC_FLAG_FLOAT_U0);
+        launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half);
+        SC_HIP(I, hipGetLastError());
+        // a size class: the launches that build its per-call state (rag_begin_builds: 12 us of host time) go in HERE, while the device
+        // erodes and pre-processes -- neither reads the table (member sizes travel in the ImageJobs); with all of rag_begin in front of
+        // the erode the device idled for as long (16 x 320^2: the first level-0 launch started 119 us into the call, now ~80)
+        if (plans && !builds_done) {
+            if ((rc = rag_begin_builds(I))) return rc;
+            builds_done = true;
+        }
+        // --- one solve for the group, results spliced per clone
+        I->info.sweep_launches = 0;
+        I->guard = RectGuard();
+        I->spec_post.group = ij;
+        I->spec_post.ev_solved = nullptr;
+        I->spec_post.armed = true; I->spec_post.done = false;     // the solver enqueues the splices behind the cycle it expects to accept
+        solve_rc = solve(I);
+        I->spec_post.armed = false;
+        I->force_float_field = false;
+        if (solve_rc != SC_RETRY_FLOAT_FIELD) break;
+        I->force_float_field = true;       // a member's 16-bit field saturated: no member was written, the group again on float fields
+        I->info.field_retry = 1;
+    }
+    const bool spliced = I->spec_post.done;
+    I->spec_post.group.clear();
+    if (solve_rc != SC_OK && solve_rc != SC_ERR_NOT_CONVERGED) return solve_rc;
+    if (!spliced) {
+        LmNodes lm;
+        if ((rc = output_nodes(I, lm))) return rc;
+        launch_postprocess_group(result(I), ij.data(), n, I->stream, lm);
+    }
+    for (int k = 0; k < n; ++k) jobs[idx[k]].rc = solve_rc;
+    SC_HIP(I, hipGetLastError());
+    fill_info_geo(I, g0);
+    I->info.group_members = n; I->info.group_ragged = plans ? 1 : 0;
+    return solve_rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
+{
+    if (!jobs || n <= 0) return SC_ERR_BAD_ARG;
+    Instance *I;
+    int rc = begin_call(p, I);
+    if (rc) return rc;
+    auto worse = [](int worst, int rc) { return (rc != SC_OK && (worst == SC_OK || worst == SC_ERR_NOT_CONVERGED)) ? rc : worst; };
+    auto alone = [&](int i) -> int {
+        sc_batch_job &j = jobs[i];
+        j.rc = sc_hip_run_device(p, j.face, j.face_cols, j.face_rows, j.face_step, j.body, j.body_cols, j.body_rows, j.body_step,
+                                 j.mask, j.mask_cols, j.mask_rows, j.mask_step, j.centerX, j.centerY, false);
+        return j.rc;
+    };
+    auto one_by_one = [&]() -> int {
+        int worst = SC_OK;
+        for (int i = 0; i < n; ++i) worst = worse(worst, alone(i));
+        return worst;
+    };
+    {   // refresh the destinations that ask for it: one launch per 16 (k_copy_group); odd alignments take the runtime's copy
+        CopyJobs cj{};
+        int cn = 0;
+        auto flush = [&]() { if (cn) { launch_copy_group(cj, cn, I->stream); cn = 0; } };
+        for (int i = 0; i < n; ++i) {
+            const sc_batch_job &j = jobs[i];
+            if (!j.body_restore) continue;
+            const size_t bytes = (size_t)j.body_step * j.body_rows;
+            if ((((uintptr_t)j.body | (uintptr_t)j.body_restore) & 15) != 0) {
+                SC_HIP(I, hipMemcpyAsync(j.body, j.body_restore, bytes, hipMemcpyDeviceToDevice, I->stream));
+                continue;
+            }
+            cj.dst[cn] = j.body; cj.src[cn] = j.body_restore; cj.bytes[cn] = bytes;
+            if (++cn == CopyJobs::MAX) flush();
+        }
+        flush();
+        SC_HIP(I, hipGetLastError());
+    }
+    if (n == 1 || I->opts.reference_warmup || (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK)) return one_by_one();
+    // members whose images do not even validate run alone (and report their own error); the others are candidates for a group
+    std::vector<char> usable(n, 1);
+    int nusable = 0;
+    for (int i = 0; i < n; ++i) {
+        const sc_batch_job &j = jobs[i];
+        if (validate_images(I, j.face, j.face_cols, j.face_rows, j.face_step, j.body, j.body_cols, j.body_rows, j.body_step,
+                            j.mask, j.mask_cols, j.mask_rows, j.mask_step) != SC_OK) usable[i] = 0;
+        else ++nusable;
+    }
+    I->err.clear();
+    if (nusable < 2) return one_by_one();
+    I->stage_marks = false;
+    // --- bounding boxes of all masks, one read-back
+    constexpr int RS = GROUP_RS;
+    if ((rc = ensure(I, I->d_rects, (size_t)n * RS * sizeof(int)))) return rc;
+    if ((rc = ensure_pinned(I, I->h_rects, (size_t)n * 2 * RS * sizeof(int)))) return rc;
+    // (the fold launch writes every usable member's rectangle to d_r AND into the pinned h_out: no seeds to upload, nothing to read back)
+    int *h_out = (int *)I->h_rects.p + RS * n, *d_r = (int *)I->d_rects.p;
+    {
+        std::vector<MaskJob> mj;
+        mj.reserve(n);
+        for (int i = 0; i < n; ++i) {
+            if (!usable[i]) continue;
+            MaskJob m{};
+            m.mask = jobs[i].mask; m.mw = jobs[i].mask_cols; m.mh = jobs[i].mask_rows; m.mstep = jobs[i].mask_step;
+            m.rect = d_r + RS * i; m.rect_host = h_out + RS * i;
+            mj.push_back(m);
+        }
+        if ((rc = ensure(I, I->d_bbox_parts, sizeof(int) * mask_bbox_group_parts(mj.data(), (int)mj.size())))) return rc;
+        launch_mask_bbox_group(mj.data(), (int)mj.size(), I->stream, (int *)I->d_bbox_parts.p);
+    }
+    SC_HIP(I, hipGetLastError());
+    if (!I->ev_rects) SC_HIP(I, hipEventCreateWithFlags(&I->ev_rects, hipEventDisableTiming));
+    SC_HIP(I, hipEventRecord(I->ev_rects, I->stream));
+    // Like a single clone (predict_rect), the members are launched on PREDICTED bounding boxes -- the interior of every mask,
+    // which is what a mask that touches its four inner borders gives -- while the scans' answers are in flight: no host
+    // wait in front of the erodes.  Every member's splice carries its guess and writes nothing unless the device found
+    // that box; the host compares when the answers are in (they are by the time the solver has waited for its stop rule)
+    // and repeats the members that were guessed wrong, one by one on their true boxes.
+    std::vector<Geo> geo(n);
+    std::vector<int> guess(4 * (size_t)n);
+    bool speculative = !(I->opts.flags & SC_FLAG_NO_SPECULATE) && I->group_spec_cooldown == 0;
+    if (I->group_spec_cooldown > 0) --I->group_spec_cooldown;
+    std::vector<char> grouped(n, 0);          // the member's geometry is known (or predicted) and fits its destination
+    if (speculative) {
+        for (int i = 0; i < n; ++i) {
+            if (!usable[i]) continue;
+            int *r = &guess[4 * i];
+            r[0] = 1; r[1] = jobs[i].mask_cols - 2; r[2] = 1; r[3] = jobs[i].mask_rows - 2;
+            // (a member whose guess does not fit -- a mask narrower than three pixels, a box that leaves the destination -- runs alone on its true box)
+            grouped[i] = jobs[i].mask_cols >= 3 && jobs[i].mask_rows >= 3 && geo_from_rect(I, r, jobs[i].centerX, jobs[i].centerY, geo[i]) == SC_OK &&
+                         check_roi(I, geo[i], jobs[i].body_cols, jobs[i].body_rows) == SC_OK;
+        }
+    } else {
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        for (int i = 0; i < n; ++i) {
+            if (!usable[i]) continue;
+            grouped[i] = geo_from_rect(I, h_out + RS * i, jobs[i].centerX, jobs[i].centerY, geo[i]) == SC_OK &&
+                         check_roi(I, geo[i], jobs[i].body_cols, jobs[i].body_rows) == SC_OK;
+        }
+    }
+    I->err.clear();
+    // --- partition (first-come order inside a sub-group and between them): same-size members share one set of launches as they
+    //     are, members of one size class (sc_ragged.cpp: different sizes, the same solve) through the per-member table
+    std::vector<int> cand;
+    std::vector<SizePlan> plans;
+    bool one_size = true;
+    for (int i = 0; i < n; ++i) {
+        if (!grouped[i]) continue;
+        if (!cand.empty() && (geo[i].W != geo[cand[0]].W || geo[i].H != geo[cand[0]].H)) one_size = false;
+        cand.push_back(i);
+    }
+    std::vector<std::vector<int>> parts;          // indices into cand / plans
+    if (one_size && cand.size() >= 2) {
+        // every member has the same ROI size (a benchmark's batch, a tiled image): one field of 3n channels as in rounds 2-4, and
+        // nothing to plan -- sixteen memo look-ups per call and thirty-two in the pool were 0.5 % of the 2048^2 step
+        parts.emplace_back(cand.size());
+        for (size_t k = 0; k < cand.size(); ++k) parts[0][k] = (int)k;
+        plans.resize(cand.size());
+    } else {
+        plans.resize(cand.size());
+        for (size_t k = 0; k < cand.size(); ++k) plan_size(I->opts, geo[cand[k]].W, geo[cand[k]].H, plans[k]);
+        plan_groups(plans, n, parts);
+    }
+    int worst = SC_OK;
+    sc_run_info keep{};
+    bool have_group = false;
+    std::vector<int> singles;
+    for (int i = 0; i < n; ++i) if (!grouped[i]) singles.push_back(i);
+    for (const auto &pq : parts) {
+        if (pq.size() < 2) { singles.push_back(cand[pq[0]]); grouped[cand[pq[0]]] = 0; continue; }
+        std::vector<int> q(pq.size());
+        std::vector<SizePlan> qp;
+        bool uniform = true;
+        for (size_t k = 0; k < pq.size(); ++k) {
+            q[k] = cand[pq[k]];
+            uniform = uniform && geo[q[k]].W == geo[q[0]].W && geo[q[k]].H == geo[q[0]].H;
+        }
+        if (!uniform) for (int k : pq) qp.push_back(plans[k]);
+        rc = run_group_members(I, jobs, q, geo, speculative ? guess.data() : nullptr, d_r, uniform ? nullptr : &qp);
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;          // a HIP error: nothing more can be trusted on this stream
+        worst = worse(worst, rc);
+        keep = I->info; have_group = true;
+    }
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    I->info.ms_h2d = I->info.ms_mask = I->info.ms_pre = I->info.ms_solve = I->info.ms_post = I->info.ms_d2h = I->info.ms_device_total = 0.f;
+    if (have_group) keep = I->info;
+    if (speculative && have_group) {
+        SC_HIP(I, hipEventSynchronize(I->ev_rects));       // long since passed when the solver has waited for its stop rule
+        for (int i = 0; i < n; ++i)
+            if (grouped[i] && memcmp(&guess[4 * i], h_out + RS * i, 4 * sizeof(int)) != 0) {
+                I->group_spec_cooldown = 8;
+                singles.push_back(i);                          // its destination was not touched: repeat it alone on its true box
+            }
+    }
+    for (int i : singles) worst = worse(worst, alone(i));
+    if (have_group) I->info = keep;                            // the statistics of the (last) group, not of a straggler
+    return worst;
+}
+
+int sc_hip_plan_size(int W, int H, const sc_solver_opts *opts, int out[12])
+{
+    if (!out) return SC_ERR_BAD_ARG;
+    sc_solver_opts o;
+    if (opts) o = *opts; else sc_hip_default_opts(&o);
+    SizePlan p;
+    plan_size(o, W, H, p);
+    const int v[12] = { p.ok ? 1 : 0, p.nl, p.tail, p.npx, p.npy, p.Kxp, p.Kyp, p.nxt, p.nrs, (p.t && p.tail > 0) ? p.t->g[p.tail].x.nc * 1000 + p.t->g[p.tail].y.nc : 0,
+                        p.solo_differs ? 1 : 0, p.conditional ? 1 : 0 };
+    memcpy(out, v, sizeof(v));
+    return SC_OK;
+}
+
+int sc_hip_plan_groups(const int *wh, int n, int cap, const sc_solver_opts *opts, int *group_of, int *kind_of)
+{
+    if (!wh || n < 1 || !group_of) return SC_ERR_BAD_ARG;
+    sc_solver_opts o;
+    if (opts) o = *opts; else sc_hip_default_opts(&o);
+    std::vector<SizePlan> plans(n);
+    for (int i = 0; i < n; ++i) plan_size(o, wh[2 * i], wh[2 * i + 1], plans[i]);
+    std::vector<std::vector<int>> groups;
+    plan_groups(plans, cap > 0 ? cap : n, groups);
+    for (size_t g = 0; g < groups.size(); ++g) {
+        bool uniform = true;
+        for (int i : groups[g]) uniform = uniform && plans[i].W == plans[groups[g][0]].W && plans[i].H == plans[groups[g][0]].H;
+        for (int i : groups[g]) {
+            group_of[i] = (int)g;
+            if (kind_of) kind_of[i] = groups[g].size() < 2 ? 0 : uniform ? 1 : plans[i].solo_differs ? 3 : 2;
+        }
+    }
+    return (int)groups.size();
+}
+
+int sc_hip_plan_groups_pool(const int *wh, int n, int group, int streams, const sc_solver_opts *opts, int *group_of, int *kind_of)
+{
+    if (!wh || n < 1 || !group_of || group < 0 || group > 64 || streams < 1) return SC_ERR_BAD_ARG;
+    sc_solver_opts o;
+    if (opts) o = *opts; else sc_hip_default_opts(&o);
+    // as sc_hip_pool_run: largest first, then the planner under the pool's caps
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return (long)(wh[2 * x] + 2) * (wh[2 * x + 1] + 2) > (long)(wh[2 * y] + 2) * (wh[2 * y + 1] + 2); });
+    std::vector<SizePlan> plans(n);
+    for (int i = 0; i < n; ++i) plan_size(o, wh[2 * order[i]], wh[2 * order[i] + 1], plans[i]);
+    int cap, cap_max;
+    long budget;
+    pool_group_caps(group, n, streams, cap, cap_max, budget);
+    std::vector<std::vector<int>> groups;
+    plan_groups(plans, cap, groups, cap_max, budget);
+    for (size_t g = 0; g < groups.size(); ++g) {
+        bool uniform = true;
+        for (int i : groups[g]) uniform = uniform && plans[i].W == plans[groups[g][0]].W && plans[i].H == plans[groups[g][0]].H;
+        for (int i : groups[g]) {
+            group_of[order[i]] = (int)g;
+            if (kind_of) kind_of[order[i]] = groups[g].size() < 2 ? 0 : uniform ? 1 : plans[i].solo_differs ? 3 : 2;
+        }
+    }
+    return (int)groups.size();
+}
+
+int sc_hip_plan_prepare(const int *wh, int n, const sc_solver_opts *opts)
+{
+    if (!wh || n < 1) return SC_ERR_BAD_ARG;
+    sc_solver_opts o;
+    if (opts) o = *opts; else sc_hip_default_opts(&o);
+    int eligible = 0;
+    for (int i = 0; i < n; ++i) {
+        SizePlan p;
+        if (plan_size(o, wh[2 * i], wh[2 * i + 1], p)) ++eligible;
+    }
+    return eligible;
+}
+
+void sc_hip_plan_cache_clear(void) { plan_cache_clear(); }
+
+int sc_hip_reference_tables_singular(int w, int h)
+{
+    if (w < 1 || h < 1) return 0;
+    const double PIf = (double)3.14159265358979323846f;           // seamlessClone_imp.h:17
+    const float fx0 = (float)(2.0 * std::cos(PIf / (w + 1.0))), fy0 = (float)(2.0 * std::cos(PIf / (h + 1.0)));
+    return ((fx0 + fy0) - 4.0f < 0.0f) ? 0 : 1;
+}
+
+} // extern "C"

@@ -5,7 +5,7 @@
 #include <stddef.h>
 #include <string>
 #include <vector>
-#include "../../include/seamlessclone_hip.h"
+#include "../../include/seamlessclone_hip_testing.h"
 
 namespace sc {
 

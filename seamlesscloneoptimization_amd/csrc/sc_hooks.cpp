@@ -1,0 +1,366 @@
+// sc_hooks.cpp -- the test and measurement hooks of include/seamlessclone_hip_testing.h: the host-only self test, the stage hooks
+// (mask stage, right-hand side), the solver hooks on caller-supplied fields and the kernel timings bench.py reads.  No clone path
+// calls into this file.
+#include "sc_instance.h"
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+using namespace sc;
+
+// A multigrid clone leaves its right-hand side as float16 inside F's buffer; the diagnostic hooks below read
+// float.  Expand through the field that does not hold the result and copy back (not on any hot path).
+static int float_rhs(Instance *I)
+{
+    if (!I->f_half) return SC_OK;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    Field scratch = I->result_in_U1 ? I->U0 : I->U1;
+    const size_t n = I->F.plane * (size_t)I->F.C;
+    launch_half_to_float(I->F.p, scratch.p, n, I->stream);
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipMemcpyAsync(I->F.p, scratch.p, n * sizeof(float), hipMemcpyDeviceToDevice, I->stream));
+    I->f_half = false;
+    return SC_OK;
+}
+
+extern "C" {
+
+int sc_hip_selftest_host(void)
+{
+    // 1: row copier -- strided copy of an awkward shape through the parked helpers, twice (reuse of the pool)
+    {
+        RowCopier rc(5);
+        const int rows = 1237, rb = 3001, sp = 3100, dp = 3072;
+        std::vector<uint8_t> src((size_t)rows * sp), dst((size_t)rows * dp, 0);
+        for (size_t i = 0; i < src.size(); ++i) src[i] = (uint8_t)(i * 2654435761u >> 24);
+        for (int rep = 0; rep < 2; ++rep) {
+            std::fill(dst.begin(), dst.end(), 0);
+            const int per = 17, parts = (rows + per - 1) / per;
+            rc.parallel(parts, [&](int i) {
+                for (int y = i * per; y < std::min(rows, (i + 1) * per); ++y) memcpy(&dst[(size_t)y * dp], &src[(size_t)y * sp], rb);
+            });
+            for (int y = 0; y < rows; ++y) {
+                if (memcmp(&dst[(size_t)y * dp], &src[(size_t)y * sp], rb) != 0) return 1;
+                for (int x = rb; x < dp; ++x) if (dst[(size_t)y * dp + x]) return 1;
+            }
+        }
+        int hits = 0;
+        rc.parallel(1, [&](int) { ++hits; });              // single part runs inline
+        rc.parallel(0, [&](int) { ++hits; });
+        if (hits != 1) return 1;
+    }
+    // 2: eigen-decomposition of the 1-D level operators (the QL reference), 4: the closed form the device builds from against it
+    if (!(sc::fd_selftest_error() < 1e-11)) return 2;
+    if (!(sc::fd_closed_selftest_error() < 1e-10)) return 4;
+    // 3: which parts of a level-0 launch make up each cell row of the float-table correction (sc_lowmode.hip)
+    if (sc::lowmode_part_map_selftest() != 0) return 3;
+    // 5: the pruned search for the correction's largest ratio (plan_size) against the full table's maximum, over sizes of every kind
+    //    (square, elongated, the 2100s and 3000s where one size in ten crosses the 4 % line)
+    {
+        std::vector<float> R(256 * 256);
+        const int ws[] = { 46, 98, 154, 300, 511, 640, 1000, 1027, 1100, 1555, 2046, 2051, 2105, 2118, 2135, 2400, 3118, 3328, 3468, 4096, 6000, 9000 };
+        for (int w : ws)
+            for (int dh = -7; dh <= 7; ++dh) {
+                for (int h : { w + 3 * dh, w / 3 + dh + 40 }) {
+                    if (h < 4) continue;
+                    const int Kx = sc::lowmode_count(w), Ky = sc::lowmode_count(h), Kxp = (Kx + 31) / 32 * 32;
+                    double pruned = -1.0, full = -2.0;
+                    const bool a = sc::lowmode_ratio(w, h, Kx, Ky, Kxp, nullptr, pruned), b = sc::lowmode_ratio(w, h, Kx, Ky, Kxp, R.data(), full);
+                    if (a != b || pruned != full) return 5;
+                }
+            }
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- stage-level hooks
+
+int sc_hip_mask_stage(void *p, const uint8_t *mask, int mc, int mr, int ms, int cx, int cy, int geo[6], uint8_t *M_out,
+                      size_t M_capacity)
+{
+    Instance *I = get(p);
+    if (!I || !mask || !geo) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    if (mc <= 0 || mr <= 0 || ms < mc) return SC_ERR_BAD_SIZE;
+    int rc;
+    const int dms = round_up(mc, 256);
+    if ((rc = ensure(I, I->d_mask, (size_t)dms * mr))) return rc;
+    if ((rc = upload_rows(I, I->h_mask, I->d_mask.p, dms, mask, ms, mc, mr))) return rc;
+    Geo g;
+    if ((rc = device_bbox(I, (const uint8_t *)I->d_mask.p, mc, mr, dms, cx, cy, g))) return rc;
+    fill_info_geo(I, g);
+    geo[0] = g.x0; geo[1] = g.y0; geo[2] = g.W; geo[3] = g.H; geo[4] = g.ltx; geo[5] = g.lty;
+    I->mpitch = round_up(g.W, 64);
+    if ((rc = ensure(I, I->d_M, (size_t)I->mpitch * g.H, false))) return rc;
+    erode_mask(I, (const uint8_t *)I->d_mask.p, dms, mr, g);
+    SC_HIP(I, hipGetLastError());
+    if (M_out) {
+        if (M_capacity < (size_t)g.W * g.H) return SC_ERR_BAD_SIZE;
+        if ((rc = download_rows(I, I->h_out, M_out, g.W, I->d_M.p, I->mpitch, g.W, g.H))) return rc;
+    }
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+// planar float field -> dense [C][H][W] host array.  The planes of a field are contiguous (plane = pitch * H), so the
+// whole field is C * H rows at one pitch.
+static int download_field(Instance *I, const Field &f, float *out)
+{
+    return download_rows(I, I->h_out, (uint8_t *)out, (size_t)f.W * sizeof(float), f.p, (size_t)f.pitch * sizeof(float),
+                         (size_t)f.W * sizeof(float), f.C * f.H);
+}
+
+int sc_hip_build_rhs(void *p, const uint8_t *face, int fc, int fr, int fs, const uint8_t *body, int bc, int br, int bs,
+                     const uint8_t *mask, int mc, int mr, int ms, int cx, int cy, int geo[6], float *B_out,
+                     float *lap_out, size_t plane_capacity)
+{
+    Instance *I = get(p);
+    if (!I || !geo) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    int rc = validate_images(I, face, fc, fr, fs, body, bc, br, bs, mask, mc, mr, ms);
+    if (rc) return rc;
+    if ((rc = sc_hip_mask_stage(p, mask, mc, mr, ms, cx, cy, geo, nullptr, 0))) return rc;
+    Geo g{ geo[0], geo[1], geo[2], geo[3], geo[4], geo[5] };
+    if ((rc = check_roi(I, g, bc, br))) return rc;
+    if (plane_capacity < (size_t)g.W * g.H) return SC_ERR_BAD_SIZE;
+    const int dfs = round_up(3 * g.W, 256);
+    if ((rc = ensure(I, I->d_face, (size_t)dfs * g.H))) return rc;
+    if ((rc = ensure(I, I->d_body_roi, (size_t)dfs * g.H))) return rc;
+    if ((rc = upload_rows(I, I->h_face, I->d_face.p, dfs, face + (size_t)g.y0 * fs + 3 * g.x0, fs, 3 * (size_t)g.W, g.H))) return rc;
+    if ((rc = upload_rows(I, I->h_body, I->d_body_roi.p, dfs, body + (size_t)g.lty * bs + 3 * g.ltx, bs, 3 * (size_t)g.W, g.H))) return rc;
+    if ((rc = setup_fields(I, g.W, g.H, 3))) return rc;
+    launch_preprocess((const uint8_t *)I->d_body_roi.p, dfs, (const uint8_t *)I->d_face.p, dfs,
+                      (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F, I->stream, false, false, (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0);
+    SC_HIP(I, hipGetLastError());
+    if (B_out && (rc = download_field(I, I->U0, B_out))) return rc;
+    if (lap_out && (rc = download_field(I, I->F, lap_out))) return rc;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_field_load(void *p, int W, int H, int C, const float *U, const float *lap)
+{
+    Instance *I = get(p);
+    if (I) field_moved(I);
+    if (I) I->out_direct = false;
+    if (!I || !U || !lap) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    if (W < 1 || H < 1 || C < 1 || C > 16) return SC_ERR_BAD_SIZE;
+    int rc;
+    if ((rc = setup_fields(I, W, H, C))) return rc;
+    // deterministic pads
+    SC_HIP(I, hipMemsetAsync(I->d_U0.p, 0, I->U0.bytes(), I->stream));
+    SC_HIP(I, hipMemsetAsync(I->d_U1.p, 0, I->U1.bytes(), I->stream));
+    SC_HIP(I, hipMemsetAsync(I->d_F.p, 0, I->F.bytes(), I->stream));
+    const size_t wb = (size_t)W * sizeof(float), pb = (size_t)I->U0.pitch * sizeof(float);
+    // a field's planes are contiguous: C * H rows at one pitch, one packed upload each (separate staging buffers)
+    if ((rc = upload_rows(I, I->h_face, I->U0.p, pb, (const uint8_t *)U, wb, wb, C * H))) return rc;
+    if ((rc = upload_rows(I, I->h_body, I->F.p, pb, (const uint8_t *)lap, wb, wb, C * H))) return rc;
+    SC_HIP(I, hipMemcpyAsync(I->U1.p, I->U0.p, pb * (size_t)(C * H - 1) + wb, hipMemcpyDeviceToDevice, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_field_sweep(void *p, int method, int sweeps, float omega, int spl)
+{
+    Instance *I = get(p);
+    if (I && I->out_direct) { I->err = "the last clone kept no solution field (set SC_FLAG_KEEP_FIELD to keep it)"; return SC_ERR_BAD_ARG; }
+    if (I && I->f_half) { int frc = float_rhs(I); if (frc) return frc; }
+    if (!I || !I->F.p) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    I->info.sweep_launches = 0;
+    int rc = run_sweeps(I, method, sweeps, omega, spl);
+    if (rc) return rc;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_field_residual(void *p, double out[2])
+{
+    Instance *I = get(p);
+    if (I && I->out_direct) { I->err = "the last clone kept no solution field (set SC_FLAG_KEEP_FIELD to keep it)"; return SC_ERR_BAD_ARG; }
+    if (I && I->f_half) { int frc = float_rhs(I); if (frc) return frc; }
+    if (!I || !I->F.p || !out) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    return eval_residual(I, out);
+}
+
+int sc_hip_field_solve(void *p)
+{
+    Instance *I = get(p);
+    if (I && I->f_half) { int frc = float_rhs(I); if (frc) return frc; }
+    if (!I || !I->F.p) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    I->info.sweep_launches = 0;
+    int rc = solve(I);
+    hipError_t e = hipStreamSynchronize(I->stream);
+    if (e != hipSuccess) return hip_fail(I, e, "hipStreamSynchronize");
+    return rc;
+}
+
+int sc_hip_field_shape(void *p, int whc[3])
+{
+    Instance *I = get(p);
+    if (!I || !I->F.p || !whc) return SC_ERR_BAD_ARG;
+    whc[0] = I->F.W; whc[1] = I->F.H; whc[2] = I->F.C;
+    return SC_OK;
+}
+
+int sc_hip_field_store(void *p, float *U_out, size_t capacity_floats)
+{
+    Instance *I = get(p);
+    if (I && I->out_direct) { I->err = "the last clone kept no solution field (set SC_FLAG_KEEP_FIELD to keep it)"; return SC_ERR_BAD_ARG; }
+    if (!I || !I->F.p || !U_out) return SC_ERR_BAD_ARG;
+    if (capacity_floats < (size_t)I->F.W * I->F.H * I->F.C) { I->err = "field_store: buffer too small"; return SC_ERR_BAD_SIZE; }
+    SC_HIP(I, hipSetDevice(I->gpu));
+    int rc = download_field(I, result(I), U_out);
+    if (rc) return rc;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_field_finish(void *p, uint8_t *body, int bc, int br, int bs, int ltx, int lty)
+{
+    Instance *I = get(p);
+    if (I && I->out_direct) { I->err = "the last clone kept no solution field (set SC_FLAG_KEEP_FIELD to keep it)"; return SC_ERR_BAD_ARG; }
+    if (!I || !I->F.p || !body) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    const Field &U = result(I);
+    if (U.C != 3) { I->err = "field_finish: needs a 3-channel field"; return SC_ERR_BAD_SIZE; }
+    if (bc <= 0 || br <= 0 || bs < 3 * bc) return SC_ERR_BAD_SIZE;
+    Geo g{ 0, 0, U.W, U.H, ltx, lty };
+    int rc;
+    if ((rc = check_roi(I, g, bc, br))) return rc;
+    const int dfs = round_up(3 * g.W, 256);
+    if ((rc = ensure(I, I->d_body_roi, (size_t)dfs * g.H))) return rc;
+    uint8_t *roi = body + (size_t)lty * bs + 3 * ltx;
+    if ((rc = upload_rows(I, I->h_body, I->d_body_roi.p, dfs, roi, bs, 3 * (size_t)g.W, g.H))) return rc;
+    launch_postprocess(U, (uint8_t *)I->d_body_roi.p, dfs, I->stream);
+    SC_HIP(I, hipGetLastError());
+    return download_rows(I, I->h_out, roi, bs, I->d_body_roi.p, dfs, 3 * (size_t)g.W, g.H);
+}
+
+int sc_hip_field_lowmode(void *p)
+{
+    Instance *I = get(p);
+    if (I && I->out_direct) { I->err = "the last clone kept no solution field (set SC_FLAG_KEEP_FIELD to keep it)"; return SC_ERR_BAD_ARG; }
+    if (I && I->f_half) { int frc = float_rhs(I); if (frc) return frc; }
+    if (!I || !I->F.p) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    Field &U = result(I), &O = I->result_in_U1 ? I->U0 : I->U1;
+    // the partner buffer receives the interior; give it the ring as well so it is a complete field
+    SC_HIP(I, hipMemcpyAsync(O.p, U.p, U.bytes(), hipMemcpyDeviceToDevice, I->stream));
+    int rc = lowmode_correct(I, U, O);
+    if (rc) return rc;
+    I->result_in_U1 = !I->result_in_U1;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_field_time_sweeps(void *p, int method, int launches, int spl, float omega, float *ms_per_launch)
+{
+    Instance *I = get(p);
+    if (I) field_moved(I);
+    if (I && I->f_half) { int frc = float_rhs(I); if (frc) return frc; }
+    if (!I || !I->F.p || !ms_per_launch || launches < 1) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    int d = fused_depth(method, spl);
+    if (method == SC_METHOD_JACOBI && (d == 5 || d == 7)) d -= 1;   // instantiated depths: 1-4, 6, 8
+    const int per = d > 0 ? d : 1;                      // sweeps one "launch group" performs
+    I->bench_tag = true;                                // same code under a second symbol (see k_jacobi)
+    int rc = run_sweeps(I, method, per, omega, spl);    // warm-up
+    if (rc) { I->bench_tag = false; return rc; }
+    I->info.sweep_launches = 0;
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    rc = run_sweeps(I, method, launches * per, omega, spl);
+    I->bench_tag = false;
+    if (rc) return rc;
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    const int n = I->info.sweep_launches > 0 ? I->info.sweep_launches : 1;
+    *ms_per_launch = ev_ms(I->ev_k0, I->ev_k1) / (float)n;
+    return SC_OK;
+}
+
+// Isolated timing of the level-0 cycle kernel (prolongation + 4 red-black sweeps + residual +
+// restriction) on the fields and hierarchy the last MULTIGRID run left on the device.  The values
+// it produces are discarded; only the launch duration matters (bench.py roofline).
+int sc_hip_time_cycle0(void *p, int launches, float *ms_per_launch)
+{
+    Instance *I = get(p);
+    if (I) field_moved(I);
+    if (!I || !ms_per_launch || launches < 1) return SC_ERR_BAD_ARG;
+    if (!I->F.p || I->mg.size() < 2 || !I->mg_partial.p) { I->err = "time_cycle0: run a multigrid clone first"; return SC_ERR_BAD_ARG; }
+    SC_HIP(I, hipSetDevice(I->gpu));
+    const bool comp = mg_composes_level1(I);          // time the form the clone itself runs
+    auto once = [&]() {
+        if (comp)
+            launch_cycle0_composed(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g, 4,
+                                   (float *)I->mg_partial.p, I->stream, true, I->f_half, false, I->mg[2].U, I->mg[1].g, nullptr, I->mg_l1_half,
+                                   (I->mg_l1_half && I->mg_q16_last) ? 3 : 0);
+        else
+            launch_cycle0(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g, 4, true,
+                          (float *)I->mg_partial.p, I->stream, true, I->f_half);
+        I->result_in_U1 = !I->result_in_U1;
+    };
+    once();
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    for (int i = 0; i < launches; ++i) once();
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    *ms_per_launch = ev_ms(I->ev_k0, I->ev_k1) / (float)launches;
+    return SC_OK;
+}
+
+int sc_hip_time_cycle0_form(void *p, int form, int launches, float *ms_per_launch)
+{
+    if (form == 0) return sc_hip_time_cycle0(p, launches, ms_per_launch);
+    Instance *I = get(p);
+    if (I) field_moved(I);
+    if (!I || !ms_per_launch || launches < 1 || form < 1 || form > 3) return SC_ERR_BAD_ARG;
+    if (!I->F.p || I->mg.size() < 3 || !I->mg_partial.p || !mg_composes_level1(I) || !I->mg_l1_half || !I->mg_q16_last || !I->f_half) {
+        I->err = "time_cycle0_form: run a default multigrid clone first";
+        return SC_ERR_BAD_ARG;
+    }
+    SC_HIP(I, hipSetDevice(I->gpu));
+    float4 *bands = form == 1 ? lowmode_bands_buffer(I, 4) : nullptr;
+    LmNodes lm;
+    if (form == 2 && I->lm.CN.p && !I->lm.singular) { lm.CN = (const float *)I->lm.CN.p; lm.ny = I->lm.ny; lm.npitch = I->lm.npitch; }
+    auto once = [&]() {
+        // values are discarded: every form reads the fields in the format it expects (whatever bits they hold) and writes the partner
+        launch_cycle0_twin(form, result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g,
+                           (float *)I->mg_partial.p, I->stream, I->mg[2].U, I->mg[1].g, bands, lm);
+    };
+    once();
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    for (int i = 0; i < launches; ++i) once();
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    lowmode_bands_written(I, nullptr);
+    *ms_per_launch = ev_ms(I->ev_k0, I->ev_k1) / (float)launches;
+    return SC_OK;
+}
+
+int sc_hip_time_coarse_chain(void *p, int reps, float *ms_eager, float *ms_graph, int *launches)
+{
+    Instance *I = get(p);
+    if (!I || reps < 1 || !ms_eager || !ms_graph || !launches) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    return mg_time_coarse_chain(I, reps, ms_eager, ms_graph, launches);
+}
+
+int sc_hip_time_tail_phases(void *p, unsigned long long *cycles11)
+{
+    Instance *I = get(p);
+    if (!I || !cycles11) return SC_ERR_BAD_ARG;
+    SC_HIP(I, hipSetDevice(I->gpu));
+    return mg_time_tail_phases(I, cycles11);
+}
+
+} // extern "C"

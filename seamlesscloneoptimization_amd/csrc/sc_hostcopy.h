@@ -1,7 +1,7 @@
 // sc_hostcopy.h -- persistent helper threads for the host side of the drop-in call (gfx950 library, host code).
 //
 // Pageable caller images are packed row by row into pinned staging before they cross PCIe, and the result is
-// spliced back row by row (sc_api.cpp).  One core copies ~14 GB/s, so a 2048^2 call (29 MB in, 12 MB out) needs
+// spliced back row by row (copy_rows, sc_arena.cpp).  One core copies ~14 GB/s, so a 2048^2 call (29 MB in, 12 MB out) needs
 // several; creating std::threads per copy cost more than the copy itself.  RowCopier keeps a few helpers parked on
 // a condition variable and hands them row ranges.
 #pragma once

@@ -175,7 +175,7 @@ struct Instance {
              std::vector<ImageJob> group; } spec_post;     // group: one destination per member (channels 3i..3i+2) of a group of clones
     // Speculative geometry: a clone may be launched on a predicted bounding box (the previous one for the same
     // mask size, else the whole mask interior) while the bbox kernel's answer is still in flight; `guard` makes
-    // the post-process a no-op on a wrong guess and the host then repeats the clone (sc_api.cpp).
+    // the post-process a no-op on a wrong guess and the host then repeats the clone (sc_api.cpp, sc_batch.cpp).
     RectGuard guard;
     int last_mc = -1, last_mr = -1, last_rect[4] = { 0, 0, 0, 0 };
     int spec_cooldown = 0;
@@ -225,7 +225,7 @@ struct Instance {
     hipEvent_t tm[8]{};   // stage marks of the current run: ev[k], or the previous mark where a stage is empty (no record call)
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
     size_t arena_bytes = 0;
-    std::vector<DevBuf> retired;           // device blocks that growth replaced: freed when the instance goes, or once they add up to 1 GB (ensure, sc_api.cpp)
+    std::vector<DevBuf> retired;           // device blocks that growth replaced: freed when the instance goes, or once they add up to 1 GB (ensure, sc_arena.cpp)
     size_t retired_bytes = 0;
     // Small device buffers are pieces of a few SLABS (16 MB, then doubling) instead of hipMalloc blocks of their own: an instance owns
     // ~40 grow-only buffers, and a caller whose ROI sizes wander re-sizes several of them in one call -- each a hipMalloc of 30-100 us
@@ -255,6 +255,23 @@ int ensure_pinned(Instance *I, DevBuf &b, size_t bytes);
 double fd_selftest_error();   // sc_multigrid.cpp
 double fd_closed_selftest_error();
 int setup_fields(Instance *I, int W, int H, int C);
+
+// ---- what the entry points share (sc_api.cpp, sc_batch.cpp, sc_hooks.cpp) --------------------------------------------------------
+// sc_api.cpp
+Instance *get(void *p);                                   // the instance behind a handle, nullptr if it is none
+int begin_call(void *p, Instance *&I);                    // a clone entry's prologue: get, clear the error and per-call statistics, set the device
+int validate_images(Instance *I, const void *face, int fc, int fr, int fs, const void *body, int bc, int br,
+                    int bs, const void *mask, int mc, int mr, int ms);
+int geo_from_rect(Instance *I, const int r[4], int cx, int cy, Geo &g);
+int check_roi(Instance *I, const Geo &g, int bc, int br);
+int device_bbox(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, int cx, int cy, Geo &g);   // waits for the device's rectangle
+void erode_mask(Instance *I, const uint8_t *d_mask, int ms, int mr, const Geo &g);                    // ROI g of the mask into I->d_M
+void fill_info_geo(Instance *I, const Geo &g);
+float ev_ms(hipEvent_t a, hipEvent_t b);
+// sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
+void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
+int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);
+int download_rows(Instance *I, DevBuf &stage, uint8_t *h, size_t hpitch, const void *d, size_t dpitch, size_t row_bytes, int rows);
 
 // solver drivers (sc_solver.cpp) -- operate on I->U0/U1/F, leave the answer in result(I)
 int solve(Instance *I);

@@ -1,7 +1,7 @@
 // sc_ragged.cpp -- size classes: clones of DIFFERENT ROI sizes through one set of solver launches (round 5).
 //
 // The reference has no batch mode at all (one clone per call, seamlessClone_imp.cu:239-263); its use case -- a mask box per face,
-// per frame -- produces batches in which no two ROIs have the same size.  sc_hip_run_device_batch (sc_api.cpp) solves n same-size
+// per frame -- produces batches in which no two ROIs have the same size.  sc_hip_run_device_batch (sc_batch.cpp) solves n same-size
 // clones as one field of 3n channels; a SIZE CLASS extends that to members whose sizes differ but whose solves are the same
 // program: the same hierarchy depth, the same level held by k_mg_tail with the level below it solved directly at the same operand
 // padding, the same mode-block counts of the float-table correction.  Such members share strides (the class's largest width and

@@ -14,7 +14,7 @@
 #include <sstream>
 #include <string>
 #include <vector>
-#include "../../include/seamlessclone_hip.h"
+#include "../../include/seamlessclone_hip_testing.h"
 
 struct Mat8 {
     int rows = 0, cols = 0, ch = 0;

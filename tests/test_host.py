@@ -60,6 +60,30 @@ def test_ctypes_structs_match_the_header_layout(tmp_path):
             assert int(out[f"{cname}.{fname}"]) == getattr(cls, fname).offset, (cname, fname)
 
 
+def test_testing_surface_is_a_header_of_its_own(tmp_path):
+    """The drop-in header holds what an integrator uses; the test and measurement hooks and the flags only tests set are in
+    seamlessclone_hip_testing.h.  C99 against each header alone, names declared once, and together exactly what the library exports."""
+    import re
+    from seamlesscloneoptimization_amd import capi
+    flags = ("SC_FLAG_POISON_ARENA", "SC_FLAG_LEGACY_PATHS", "SC_FLAG_KEEP_FIELD")
+    for header, sees_flags in (("seamlessclone_hip.h", False), ("seamlessclone_hip_testing.h", True)):
+        checks = "".join(f"#if {'!' if sees_flags else ''}defined({f})\n#error {f}\n#endif\n" for f in flags)
+        src = tmp_path / (header + ".c")
+        src.write_text(f'#include "{header}"\n{checks}int main(void) {{ sc_solver_opts o; sc_hip_default_opts(&o); return o.flags; }}\n')
+        r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
+                            "-o", str(tmp_path / (header + ".o"))], capture_output=True, text=True)
+        assert r.returncode == 0, (header, r.stderr)
+    public, testing = set(capi.declared_symbols(capi.HEADER_PATH)), set(capi.declared_symbols(capi.TESTING_HEADER_PATH))
+    assert not public & testing, public & testing
+    hooks = {"sc_hip_mask_stage", "sc_hip_build_rhs", "sc_hip_selftest_host"}
+    hooks |= {"sc_hip_field_" + n for n in ("load", "sweep", "residual", "solve", "shape", "store", "finish", "lowmode", "time_sweeps")}
+    hooks |= {"sc_hip_time_" + n for n in ("cycle0", "cycle0_form", "coarse_chain", "tail_phases")}
+    assert len(hooks) == 16 and hooks <= testing, hooks - testing
+    nm = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = {l.split()[-1] for l in nm.splitlines() if re.fullmatch(r"(?:my_seamlessclone_api_imp_|sc_hip_)\w+", l.split()[-1])}
+    assert exported == public | testing, (exported - (public | testing), (public | testing) - exported)
+
+
 def test_library_is_gfx950_only():
     from seamlesscloneoptimization_amd import capi
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o",
