@@ -46,8 +46,17 @@ extern "C" {
 #define SC_ERR_HIP           -5   /* HIP runtime error; see sc_hip_last_error()            */
 #define SC_ERR_NOT_CONVERGED -6   /* tol not reached within max_sweeps; result still written */
 
-/* OpenCV clone flags (only NORMAL_CLONE exists in the reference: seamlessClone_imp.cu:301) */
-#define SC_NORMAL_CLONE 1
+/* OpenCV clone flags (cv::NORMAL_CLONE, cv::MIXED_CLONE, cv::MONOCHROME_TRANSFER, same values).  The reference hard-codes
+ * NORMAL_CLONE (seamlessClone_imp.cu:301); the other two are additions, selected per instance with sc_hip_set_clone_mode.
+ * Inside the mask the blended gradient field is
+ *   NORMAL       the patch's (gx, gy)
+ *   MIXED        per channel and pixel, the patch's (gx, gy) where |gx - gy| of the patch exceeds the destination's, else the destination's
+ *   MONOCHROME   the (gx, gy) of the patch's grey image, (1868 B + 9617 G + 4899 R + 8192) >> 14, in all three channels
+ * and the destination's (gx, gy) outside it (OpenCV 3.4.5 Cloning::normalClone).  PARITY UNPINNED for MIXED and MONOCHROME:
+ * checked against a restatement of that arithmetic, not against OpenCV or a fixture of the reference. */
+#define SC_NORMAL_CLONE        1
+#define SC_MIXED_CLONE         2
+#define SC_MONOCHROME_TRANSFER 3
 
 /* ---- solver selection */
 enum sc_method {
@@ -253,6 +262,12 @@ SC_API int  sc_hip_set_solver(void *instance, const sc_solver_opts *opts);
 SC_API int  sc_hip_get_solver(void *instance, sc_solver_opts *opts);
 SC_API int  sc_hip_get_info(void *instance, sc_run_info *info);
 SC_API const char *sc_hip_last_error(void *instance);
+/* Clone mode of the instance's next runs (single, device-resident and batch): SC_NORMAL_CLONE (the default), SC_MIXED_CLONE or
+ * SC_MONOCHROME_TRANSFER; anything else is SC_ERR_BAD_ARG.  sc_hip_set_solver leaves it alone.  A mode other than NORMAL together
+ * with SC_FLAG_OPENCV_GREY_MASK is not supported: such a run (each job of such a batch) returns SC_ERR_BAD_ARG.
+ * sc_hip_get_clone_mode returns the mode, or SC_ERR_BAD_ARG for a bad instance. */
+SC_API int  sc_hip_set_clone_mode(void *instance, int mode);
+SC_API int  sc_hip_get_clone_mode(void *instance);
 
 /* Same as run(), but face/body/mask are DEVICE pointers on the instance's GPU (inputs
  * resident in HBM); body is updated in place on the device.  Asynchronous on the instance
@@ -307,6 +322,7 @@ SC_API void  sc_hip_pool_destroy(void *pool);
 SC_API int   sc_hip_pool_size(void *pool);
 SC_API void *sc_hip_pool_instance(void *pool, int k);          /* instance k, e.g. for sc_hip_get_info */
 SC_API int   sc_hip_pool_set_solver(void *pool, const sc_solver_opts *opts);
+SC_API int   sc_hip_pool_set_clone_mode(void *pool, int mode);  /* sc_hip_set_clone_mode on every instance of the pool (between batches) */
 SC_API int   sc_hip_pool_run(void *pool, sc_batch_job *jobs, int n, int device_resident);
 /* device-resident batches: every worker takes up to `group` jobs at a time -- the batch's jobs bucketed by ROI size: same-size
  * jobs and jobs of one size class -- and runs them through sc_hip_run_device_batch (default 1 = one clone per set of launches; at most 64).

@@ -26,6 +26,12 @@ SC_ERR_ROI_OOB = -4
 SC_ERR_HIP = -5
 SC_ERR_NOT_CONVERGED = -6
 
+# clone modes: OpenCV's flag values (cv2.NORMAL_CLONE, cv2.MIXED_CLONE, cv2.MONOCHROME_TRANSFER); Instance.set_clone_mode
+SC_NORMAL_CLONE = 1
+SC_MIXED_CLONE = 2
+SC_MONOCHROME_TRANSFER = 3
+CLONE_MODES = (SC_NORMAL_CLONE, SC_MIXED_CLONE, SC_MONOCHROME_TRANSFER)
+
 SC_METHOD_JACOBI = 0
 SC_METHOD_RBGS = 1
 SC_METHOD_SOR = 2
@@ -152,6 +158,12 @@ def load():
     L.sc_hip_get_info.restype = C.c_int
     L.sc_hip_last_error.argtypes = [C.c_void_p]
     L.sc_hip_last_error.restype = C.c_char_p
+    L.sc_hip_set_clone_mode.argtypes = [C.c_void_p, C.c_int]
+    L.sc_hip_set_clone_mode.restype = C.c_int
+    L.sc_hip_get_clone_mode.argtypes = [C.c_void_p]
+    L.sc_hip_get_clone_mode.restype = C.c_int
+    L.sc_hip_pool_set_clone_mode.argtypes = [C.c_void_p, C.c_int]
+    L.sc_hip_pool_set_clone_mode.restype = C.c_int
     L.sc_hip_run_device.argtypes = [C.c_void_p] + _IMG * 3 + [C.c_int, C.c_int, C.c_bool]
     L.sc_hip_run_device.restype = C.c_int
     L.sc_hip_malloc.argtypes = [C.c_void_p, C.c_size_t]
@@ -298,6 +310,14 @@ class Instance:
         o = SolverOpts()
         self._check(self.L.sc_hip_get_solver(self.h, C.byref(o)))
         return o
+
+    def set_clone_mode(self, mode: int) -> None:
+        """SC_NORMAL_CLONE (default), SC_MIXED_CLONE or SC_MONOCHROME_TRANSFER for the next runs; set_solver leaves it alone."""
+        self._check(self.L.sc_hip_set_clone_mode(self.h, int(mode)))
+
+    @property
+    def clone_mode(self) -> int:
+        return self._check(self.L.sc_hip_get_clone_mode(self.h), allow=CLONE_MODES)
 
     def info(self) -> RunInfo:
         i = RunInfo()
@@ -470,7 +490,7 @@ class Pool:
     """The library's native batch driver (csrc/sc_pool.cpp): K instances = K HIP streams on one GPU,
     one C++ worker thread each, jobs pulled from a shared counter."""
 
-    def __init__(self, gpu_id: int = 0, streams: int = 4, group: int = 1, **solver):
+    def __init__(self, gpu_id: int = 0, streams: int = 4, group: int = 1, clone_mode: int = SC_NORMAL_CLONE, **solver):
         self.L = load()
         self.h = self.L.sc_hip_pool_create(int(gpu_id), int(streams))
         if not self.h:
@@ -488,6 +508,8 @@ class Pool:
             rc = self.L.sc_hip_pool_set_solver(self.h, C.byref(o))
             if rc != SC_OK:
                 raise SeamlessCloneError(rc, "bad solver options")
+        if clone_mode != SC_NORMAL_CLONE:
+            self.set_clone_mode(clone_mode)
 
     @staticmethod
     def make_jobs(n: int):
@@ -503,6 +525,12 @@ class Pool:
         rc = self.L.sc_hip_pool_set_solver(self.h, C.byref(o))
         if rc != SC_OK:
             raise SeamlessCloneError(rc, "bad solver options")
+
+    def set_clone_mode(self, mode: int) -> None:
+        """The same clone mode on every instance of the pool (between batches)."""
+        rc = self.L.sc_hip_pool_set_clone_mode(self.h, int(mode))
+        if rc != SC_OK:
+            raise SeamlessCloneError(rc, f"bad clone mode {mode}")
 
     def run(self, jobs, device_resident: bool):
         rc = self.L.sc_hip_pool_run(self.h, jobs, len(jobs), 1 if device_resident else 0)

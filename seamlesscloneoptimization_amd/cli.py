@@ -25,6 +25,9 @@ def main(argv=None) -> int:
                     help="auto (default): direct FFT solve (double) up to 720 unknowns per side (also elongated ROIs of at most 450 000 unknowns or at most 140 across), mg above; fft: the reference's default back-end (FFT-based direct solve, float32); mg: multigrid + float-table correction (the reference's arithmetic); dst: the reference's direct DST "
                          "solve on the fp64 matrix cores; sor / rbgs / jacobi: sweeps to a 2e-5 residual")
     ap.add_argument("--exact-tables", action="store_true", help="mg: return the exact solution of the 5-point system instead")
+    ap.add_argument("--clone", default="normal", choices=["normal", "mixed", "monochrome"],
+                    help="clone mode, as cv::seamlessClone's flags: normal (NORMAL_CLONE, the reference's), mixed (MIXED_CLONE), "
+                         "monochrome (MONOCHROME_TRANSFER)")
     ap.add_argument("--dump-rhs", metavar="DIR",
                     help="write the reference's SCDEBUG intermediates (seamlessClone_imp.cpp:2110-2117): DIR/ucMask0.yml (eroded ROI mask) and "
                          "DIR/g{0,1,2}.yml (right-hand side with the Dirichlet ring folded in, planes in the reference's R,G,B order) -- "
@@ -45,6 +48,7 @@ def main(argv=None) -> int:
         if a.method not in ("auto", "mg", "dst", "fft"):
             opts.update(tol=2e-5, max_sweeps=1000000, check_every=64)
         inst.set_solver(**opts)
+        inst.set_clone_mode({"normal": capi.SC_NORMAL_CLONE, "mixed": capi.SC_MIXED_CLONE, "monochrome": capi.SC_MONOCHROME_TRANSFER}[a.clone])
         body = np.array(dst, np.uint8, copy=True, order="C")
         inst.run(np.ascontiguousarray(src), body, np.ascontiguousarray(mask), a.centerX, a.centerY, sync=False)
         body2 = np.array(dst, np.uint8, copy=True, order="C")      # timed run after the warm-up, as the reference does

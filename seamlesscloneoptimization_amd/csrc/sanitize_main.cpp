@@ -20,7 +20,7 @@
 
 // ---- stub instances for the pool (sc_pool.cpp is compiled with -Dmy_seamlessclone_api_imp_create_instance=stub_create ...)
 namespace {
-struct StubInst { int gpu; std::atomic<long> calls{ 0 }; sc_solver_opts opts; };
+struct StubInst { int gpu; std::atomic<long> calls{ 0 }; sc_solver_opts opts; int clone_mode = SC_NORMAL_CLONE; };
 std::atomic<long> g_jobs_run{ 0 };
 }
 extern "C" {
@@ -29,6 +29,12 @@ void stub_destroy(void *p) { delete (StubInst *)p; }
 void stub_sync(void *) {}
 int stub_set_solver(void *p, const sc_solver_opts *o) { ((StubInst *)p)->opts = *o; return SC_OK; }
 int stub_get_solver(void *p, sc_solver_opts *o) { *o = ((StubInst *)p)->opts; return SC_OK; }
+int stub_set_clone_mode(void *p, int mode)
+{
+    if (mode < SC_NORMAL_CLONE || mode > SC_MONOCHROME_TRANSFER) return SC_ERR_BAD_ARG;
+    ((StubInst *)p)->clone_mode = mode;
+    return SC_OK;
+}
 int stub_memcpy_d2d_async(void *, void *, const void *, size_t) { return SC_OK; }
 int stub_run_device(void *p, const uint8_t *, int, int, int, uint8_t *body, int, int, int, const uint8_t *, int, int, int, int, int, bool)
 {
@@ -101,6 +107,10 @@ int main()
             void *pool = sc_hip_pool_create(0, streams);
             if (!pool) return fail("pool_create (stub instances)");
             if (sc_hip_pool_set_group(pool, group) != SC_OK) return fail("pool_set_group");
+            if (sc_hip_pool_set_clone_mode(pool, 0) != SC_ERR_BAD_ARG) return fail("pool_set_clone_mode took mode 0");
+            if (sc_hip_pool_set_clone_mode(pool, SC_MIXED_CLONE) != SC_OK) return fail("pool_set_clone_mode");
+            for (int k = 0; k < sc_hip_pool_size(pool); ++k)
+                if (((StubInst *)sc_hip_pool_instance(pool, k))->clone_mode != SC_MIXED_CLONE) return fail("pool_set_clone_mode missed an instance");
             for (int batch = 0; batch < 5; ++batch) {
                 const int n = 1 + 37 * batch;
                 std::vector<uint8_t> bodies(n, 0);

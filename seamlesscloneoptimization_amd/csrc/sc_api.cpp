@@ -45,6 +45,10 @@ int validate_images(Instance *I, const void *face, int fc, int fr, int fs, const
     if (fc <= 0 || fr <= 0 || bc <= 0 || br <= 0 || mc <= 0 || mr <= 0) { I->err = "empty image"; return SC_ERR_BAD_SIZE; }
     if (fc != mc || fr != mr) { I->err = "face and mask sizes differ"; return SC_ERR_BAD_SIZE; }
     if (fs < 3 * fc || bs < 3 * bc || ms < mc) { I->err = "row step smaller than the row"; return SC_ERR_BAD_SIZE; }
+    if (I->clone_mode != SC_NORMAL_CLONE && (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK)) {
+        I->err = "SC_FLAG_OPENCV_GREY_MASK supports SC_NORMAL_CLONE only";
+        return SC_ERR_BAD_ARG;
+    }
     return SC_OK;
 }
 
@@ -197,7 +201,7 @@ static int device_clone(Instance *I, const uint8_t *d_mask, int ms, int mr, cons
         if (I->scan_pending) I->pending_scan.M_out = (uint8_t *)I->d_M.p;      // the launch's tiles erode the mask themselves and leave it here
         const bool had_scan = I->scan_pending;
         launch_preprocess(body_org, bstep, face_org, fstep, (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F,
-                          I->stream, I->f_half, I->u_half, grey, I->scan_pending ? &I->pending_scan : nullptr);
+                          I->stream, I->f_half, I->u_half, grey, I->scan_pending ? &I->pending_scan : nullptr, I->clone_mode);
         I->scan_pending = false;
         if (pass == passes - 1 && (rc = tmark(I, 5))) return rc;
         if (had_scan) {
@@ -421,6 +425,24 @@ int sc_hip_set_solver(void *p, const sc_solver_opts *o)
     if (o->mg_direct_max < 0) { I->err = "mg_direct_max must be >= 0"; return SC_ERR_BAD_ARG; }
     I->opts = *o;
     return SC_OK;
+}
+
+int sc_hip_set_clone_mode(void *p, int mode)
+{
+    Instance *I = get(p);
+    if (!I) return SC_ERR_BAD_ARG;
+    if (mode != SC_NORMAL_CLONE && mode != SC_MIXED_CLONE && mode != SC_MONOCHROME_TRANSFER) {
+        I->err = "clone mode must be SC_NORMAL_CLONE, SC_MIXED_CLONE or SC_MONOCHROME_TRANSFER";
+        return SC_ERR_BAD_ARG;
+    }
+    I->clone_mode = mode;
+    return SC_OK;
+}
+
+int sc_hip_get_clone_mode(void *p)
+{
+    Instance *I = get(p);
+    return I ? I->clone_mode : SC_ERR_BAD_ARG;
 }
 
 int sc_hip_get_solver(void *p, sc_solver_opts *o)

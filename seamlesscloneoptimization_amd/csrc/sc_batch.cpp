@@ -69,7 +69,7 @@ int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &i
         I->result_in_U1 = false;
         I->f_half = mg_reads_half_rhs(I);
         I->u_half = I->f_half && !(I->opts.flags & SC_FLAG_FLOAT_U0);
-        launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half);
+        launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half, I->clone_mode);
         SC_HIP(I, hipGetLastError());
         // a size class: the launches that build its per-call state (rag_begin_builds: 12 us of host time) go in HERE, while the device
         // erodes and pre-processes -- neither reads the table (member sizes travel in the ImageJobs); with all of rag_begin in front of

@@ -67,7 +67,7 @@ void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);
 struct BboxTask { const uint8_t *mask = nullptr; int mw = 0, mh = 0, mstep = 0; BboxFold fold; int scan_rows = 0; Geo g{}; size_t mask_bytes = 0; uint8_t *M_out = nullptr; };     // M_out: where the tiles leave the eroded mask (the buffer the launch's M argument names)
 void launch_preprocess(const uint8_t *body_org, int bstep, const uint8_t *face_org, int fstep,
                        const uint8_t *M, int mpitch, Field U0, Field U1, Field F, hipStream_t s, bool f_half = false, bool u_half = false, bool grey = false,
-                       const BboxTask *scan = nullptr);
+                       const BboxTask *scan = nullptr, int mode = SC_NORMAL_CLONE);     // mode: SC_NORMAL_CLONE / SC_MIXED_CLONE / SC_MONOCHROME_TRANSFER
 // bounding box the host assumed when it launched a clone before the device's answer was back (d_rect == nullptr: none)
 struct RectGuard { const int *d_rect = nullptr; int x0 = 0, x1 = 0, y0 = 0, y1 = 0; };
 // "Do not write": a device word the launches of one solve may set to that solve's generation number (a 16-bit fixed-point store
@@ -119,7 +119,7 @@ __device__ __forceinline__ float lm_bilinear(const LmNodes &lm, int c, int x, in
 #endif
 void launch_postprocess(Field U, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), LmNodes lm = LmNodes(), AbortFlag ab = AbortFlag());
 // the same for a group (fields of 3n channels), one launch per 16 members
-void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half);
+void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode);
 void launch_postprocess_group(Field U, const ImageJob *jobs, int n, hipStream_t s, LmNodes lm = LmNodes(), AbortFlag ab = AbortFlag());
 // splice of output bytes a multigrid launch left planar in Q's memory (launch_cycle0_out): interleave into the destination
 void launch_splice_planar(Field Q, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), AbortFlag ab = AbortFlag());

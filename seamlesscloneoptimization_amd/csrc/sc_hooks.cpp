@@ -132,7 +132,8 @@ int sc_hip_build_rhs(void *p, const uint8_t *face, int fc, int fr, int fs, const
     if ((rc = upload_rows(I, I->h_body, I->d_body_roi.p, dfs, body + (size_t)g.lty * bs + 3 * g.ltx, bs, 3 * (size_t)g.W, g.H))) return rc;
     if ((rc = setup_fields(I, g.W, g.H, 3))) return rc;
     launch_preprocess((const uint8_t *)I->d_body_roi.p, dfs, (const uint8_t *)I->d_face.p, dfs,
-                      (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F, I->stream, false, false, (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0);
+                      (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F, I->stream, false, false, (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0,
+                      nullptr, I->clone_mode);
     SC_HIP(I, hipGetLastError());
     if (B_out && (rc = download_field(I, I->U0, B_out))) return rc;
     if (lap_out && (rc = download_field(I, I->F, lap_out))) return rc;

@@ -139,6 +139,7 @@ struct Instance {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool aux_pending = false;              // work on aux that `stream` has not waited for yet
     sc_solver_opts opts{};
+    int clone_mode = SC_NORMAL_CLONE;      // sc_hip_set_clone_mode; apart from opts: sc_hip_set_solver does not touch it
     sc_run_info info{};
     std::string err;
 

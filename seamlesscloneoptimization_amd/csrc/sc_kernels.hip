@@ -490,7 +490,13 @@ __device__ __forceinline__ void p4_window(const unsigned *row, int word0, int sh
 // row, vertical AND of seven of them, ring of three) on the tile's 16 + 1 rows and 32 + 1 words, through LDS -- writes it to M (a
 // repeated pass or a retry reads it there) and takes its own words from LDS.  One launch less in front of a single clone's solve
 // (the erode alone: 8.8 us at 2048^2, 10 at 1000^2).
-template <bool HF, bool HU, bool GREY = false, bool ER = false>
+// MODE (SC_NORMAL_CLONE / SC_MIXED_CLONE / SC_MONOCHROME_TRANSFER): how the field is blended inside the mask (OpenCV 3.4.5
+// Cloning::normalClone).  MIXED: per channel, the patch's pair (gx, gy) where |pgx - pgy| > |dgx - dgy|, else the destination's;
+// gx - gy at pixel (u, v) is I(u+1, v) - I(u, v+1), so the tests at x+j-1 and at (x+j, y-1) read the diagonal pixels (x+j-1, y+1)
+// and (x+j+1, y-1) -- the row above needs the fifth word then, like the centre row.  MONOCHROME: the patch's gradients are those
+// of its grey image, cvtColor(BGR2GRAY)'s integer formula for 8-bit data, formed once per pixel for all three channels.  Every
+// gradient stays an integer in [-255, 255], the right-hand side one in [-1020, 1020].  Not combined with GREY.
+template <bool HF, bool HU, bool GREY = false, bool ER = false, int MODE = SC_NORMAL_CLONE>
 __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ body, int bstep,
                                                  const uint8_t *__restrict__ face, int fstep,
                                                  const uint8_t *__restrict__ M, int mpitch,
@@ -559,13 +565,28 @@ __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ bod
     if (y >= H) break;
     const int ry = ly + 1;
     // windows: staged column 0 is pixel tx0-1, so pixel x-1 sits at byte org + 12 lx of the row
-    unsigned bc[5], bu[4], bd[4], pc[5], pu[4], pd[4];
+    constexpr bool MIXED = MODE == SC_MIXED_CLONE, MONO = MODE == SC_MONOCHROME_TRANSFER;
+    constexpr int NU = MIXED ? 5 : 4;          // MIXED reads pixel x+4 of the row above
+    unsigned bc[5], bu[NU], bd[4], pc[5], pu[NU], pd[4];
     p4_window<5>(sb[ry], (ob[ry] >> 2) + 3 * lx, ob[ry] & 3, bc);
-    p4_window<4>(sb[ry - 1], (ob[ry - 1] >> 2) + 3 * lx, ob[ry - 1] & 3, bu);
+    p4_window<NU>(sb[ry - 1], (ob[ry - 1] >> 2) + 3 * lx, ob[ry - 1] & 3, bu);
     p4_window<4>(sb[ry + 1], (ob[ry + 1] >> 2) + 3 * lx, ob[ry + 1] & 3, bd);
     p4_window<5>(sp[ry], (op[ry] >> 2) + 3 * lx, op[ry] & 3, pc);
-    p4_window<4>(sp[ry - 1], (op[ry - 1] >> 2) + 3 * lx, op[ry - 1] & 3, pu);
+    p4_window<NU>(sp[ry - 1], (op[ry - 1] >> 2) + 3 * lx, op[ry - 1] & 3, pu);
     p4_window<4>(sp[ry + 1], (op[ry + 1] >> 2) + 3 * lx, op[ry + 1] & 3, pd);
+    // MONOCHROME: grey values of the patch's window pixels -- centre row x-1 .. x+4, rows above / below x .. x+3
+    float yc[6], yu[4], yd[4];
+    if constexpr (MONO) {
+        auto grey = [](const unsigned *w, int k) {      // pixel k of a window: (1868 B + 9617 G + 4899 R + 8192) >> 14
+            const unsigned b = (w[(3 * k) >> 2] >> (8 * ((3 * k) & 3))) & 0xffu, g = (w[(3 * k + 1) >> 2] >> (8 * ((3 * k + 1) & 3))) & 0xffu,
+                           r = (w[(3 * k + 2) >> 2] >> (8 * ((3 * k + 2) & 3))) & 0xffu;
+            return (float)((1868u * b + 9617u * g + 4899u * r + 8192u) >> 14);
+        };
+#pragma unroll
+        for (int k = 0; k < 6; ++k) yc[k] = grey(pc, k);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { yu[k] = grey(pu, k + 1); yd[k] = grey(pd, k + 1); }
+    }
     // eroded mask: pixels x .. x+3 of rows y and y-1 (aligned words: x % 4 == 0) and pixel x-1 of row y
     const bool yin = (y >= 1) && (y <= H - 2);
     unsigned mw = 0, muw = 0, mlb = 0;
@@ -588,7 +609,8 @@ __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ bod
             float lap = 0.0f;
             if (yin && x + j >= 1 && x + j <= W - 2) {
                 const float bl = P4_BYTE(bc, b - 3), br = P4_BYTE(bc, b + 3), bup = P4_BYTE(bu, b), bdn = P4_BYTE(bd, b);
-                const float pcc = P4_BYTE(pc, b), pl = P4_BYTE(pc, b - 3), pr = P4_BYTE(pc, b + 3), pup = P4_BYTE(pu, b), pdn = P4_BYTE(pd, b);
+                const float pcc = MONO ? yc[j + 1] : P4_BYTE(pc, b), pl = MONO ? yc[j] : P4_BYTE(pc, b - 3), pr = MONO ? yc[j + 2] : P4_BYTE(pc, b + 3),
+                            pup = MONO ? yu[j] : P4_BYTE(pu, b), pdn = MONO ? yd[j] : P4_BYTE(pd, b);
                 const unsigned mb = (mw >> (8 * j)) & 0xffu, mlbyte = (j == 0 ? mlb : ((mw >> (8 * (j - 1))) & 0xffu)), mub = (muw >> (8 * j)) & 0xffu;
                 if (GREY) {
                     const float k = 1.0f / 255.0f;
@@ -600,9 +622,15 @@ __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ bod
                     const float gyu = (bcc - bup) * wui + (pcc - pup) * wum;
                     lap = (gx - gxl) + (gy - gyu);
                 } else {
-                const bool m = mb != 0u;
-                const bool ml = mlbyte != 0u;
-                const bool mu = mub != 0u;
+                bool m = mb != 0u;
+                bool ml = mlbyte != 0u;
+                bool mu = mub != 0u;
+                if constexpr (MIXED) {      // |gx - gy| of the patch against the destination's, at x+j, x+j-1 and (x+j, y-1)
+                    const float pdl = P4_BYTE(pd, b - 3), bdl = P4_BYTE(bd, b - 3), pur = P4_BYTE(pu, b + 3), bur = P4_BYTE(bu, b + 3);
+                    m = m && fabsf(pr - pdn) > fabsf(br - bdn);
+                    ml = ml && fabsf(pcc - pdl) > fabsf(bcc - bdl);
+                    mu = mu && fabsf(pur - pcc) > fabsf(bur - bcc);
+                }
                 const float gx = m ? (pr - pcc) : (br - bcc);
                 const float gxl = ml ? (pcc - pl) : (bcc - bl);
                 const float gy = m ? (pdn - pcc) : (bdn - bcc);
@@ -635,7 +663,7 @@ __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ bod
 // 4).  A clone launched on a PREDICTED box needs the scan's answer only at its very end (the output launches' RectGuard, the
 // host's comparison), so the scan has no business on the critical path in front of the erode: it rides in this launch, which
 // depends on nothing the scan produces.  mask_bbox_block's last workgroup folds the parts as before.
-template <bool HF, bool HU, bool GREY = false, bool BB = false>
+template <bool HF, bool HU, bool GREY = false, bool BB = false, int MODE = SC_NORMAL_CLONE>
 __global__ __launch_bounds__(256) void k_preprocess(const uint8_t *__restrict__ body, int bstep,
                                                      const uint8_t *__restrict__ face, int fstep,
                                                      const uint8_t *__restrict__ M, int mpitch,
@@ -647,12 +675,12 @@ __global__ __launch_bounds__(256) void k_preprocess(const uint8_t *__restrict__ 
         return;
     }
     // (a launch that carries the scan is a clone on a predicted box: its tiles erode the mask themselves, bb.g / bb.mask_bytes)
-    if constexpr (BB) preprocess_block<HF, HU, GREY, true>(body, bstep, face, fstep, M, mpitch, U0, F, 0, (int)blockIdx.y - bb.scan_rows, &bb);
-    else preprocess_block<HF, HU, GREY>(body, bstep, face, fstep, M, mpitch, U0, F, 0, (int)blockIdx.y);
+    if constexpr (BB) preprocess_block<HF, HU, GREY, true, MODE>(body, bstep, face, fstep, M, mpitch, U0, F, 0, (int)blockIdx.y - bb.scan_rows, &bb);
+    else preprocess_block<HF, HU, GREY, false, MODE>(body, bstep, face, fstep, M, mpitch, U0, F, 0, (int)blockIdx.y);
 }
 
 // a group of clones in one launch: blockIdx.z = member, which owns channels 3z..3z+2 of the group's fields
-template <bool HF, bool HU>
+template <bool HF, bool HU, int MODE = SC_NORMAL_CLONE>
 __global__ __launch_bounds__(256) void k_preprocess_group(ImageJobs t, int mpitch, Field U0, Field F)
 {
     const ImageJob &j = t.j[blockIdx.z];
@@ -660,10 +688,11 @@ __global__ __launch_bounds__(256) void k_preprocess_group(ImageJobs t, int mpitc
         if ((int)blockIdx.x * P4_TW >= j.W || (int)blockIdx.y * P4_TH >= j.H) return;
         U0.W = F.W = j.W; U0.H = F.H = j.H;
     }
-    preprocess_block<HF, HU>(j.body_org, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
+    preprocess_block<HF, HU, false, false, MODE>(j.body_org, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
 }
 
-void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half)
+template <int MODE>
+static void launch_preprocess_group_mode(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half)
 {
     for (int i0 = 0; i0 < n; i0 += ImageJobs::MAX) {
         ImageJobs t{};
@@ -673,15 +702,38 @@ void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, 
         u.p = u_half ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(U0.p) + (size_t)3 * i0 * U0.plane) : U0.p + (size_t)3 * i0 * U0.plane;
         f.p = f_half ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(F.p) + (size_t)3 * i0 * F.plane) : F.p + (size_t)3 * i0 * F.plane;
         dim3 g4((U0.W + P4_TW - 1) / P4_TW, (U0.H + P4_TH - 1) / P4_TH, cnt);
-        if (f_half && u_half) hipLaunchKernelGGL((k_preprocess_group<true, true>), g4, dim3(256), 0, s, t, mpitch, u, f);
-        else if (f_half) hipLaunchKernelGGL((k_preprocess_group<true, false>), g4, dim3(256), 0, s, t, mpitch, u, f);
-        else hipLaunchKernelGGL((k_preprocess_group<false, false>), g4, dim3(256), 0, s, t, mpitch, u, f);
+        if (f_half && u_half) hipLaunchKernelGGL((k_preprocess_group<true, true, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
+        else if (f_half) hipLaunchKernelGGL((k_preprocess_group<true, false, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
+        else hipLaunchKernelGGL((k_preprocess_group<false, false, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
     }
+}
+
+void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode)
+{
+    if (mode == SC_MIXED_CLONE) launch_preprocess_group_mode<SC_MIXED_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half);
+    else if (mode == SC_MONOCHROME_TRANSFER) launch_preprocess_group_mode<SC_MONOCHROME_TRANSFER>(jobs, n, mpitch, U0, F, s, f_half, u_half);
+    else launch_preprocess_group_mode<SC_NORMAL_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half);
+}
+
+// the launch of one clone's tiles (and of its bounding-box scan: bb.scan_rows > 0) under clone mode MODE
+template <int MODE>
+static void launch_preprocess_mode(dim3 g4, const uint8_t *body_org, int bstep, const uint8_t *face_org, int fstep, const uint8_t *M, int mpitch,
+                                   Field U0, Field U1, Field F, hipStream_t s, bool f_half, bool u_half, const BboxTask &bb)
+{
+    if (bb.scan_rows > 0) {
+        if (f_half && u_half) hipLaunchKernelGGL((k_preprocess<true, true, false, true, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+        else if (f_half) hipLaunchKernelGGL((k_preprocess<true, false, false, true, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+        else hipLaunchKernelGGL((k_preprocess<false, false, false, true, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+        return;
+    }
+    if (f_half && u_half) hipLaunchKernelGGL((k_preprocess<true, true, false, false, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+    else if (f_half) hipLaunchKernelGGL((k_preprocess<true, false, false, false, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+    else hipLaunchKernelGGL((k_preprocess<false, false, false, false, MODE>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
 }
 
 void launch_preprocess(const uint8_t *body_org, int bstep, const uint8_t *face_org, int fstep,
                        const uint8_t *M, int mpitch, Field U0, Field U1, Field F, hipStream_t s, bool f_half, bool u_half, bool grey,
-                       const BboxTask *scan)
+                       const BboxTask *scan, int mode)
 {
     dim3 g4((U0.W + P4_TW - 1) / P4_TW, (U0.H + P4_TH - 1) / P4_TH);
     BboxTask bb{};
@@ -692,15 +744,12 @@ void launch_preprocess(const uint8_t *body_org, int bstep, const uint8_t *face_o
         bb.fold.nblocks = bb.fold.nbx * ((bb.mh + 4 * BB_ROWS - 1) / (4 * BB_ROWS));
         bb.scan_rows = (bb.fold.nblocks + (int)g4.x - 1) / (int)g4.x;
         g4.y += (unsigned)bb.scan_rows;
-        if (f_half && u_half) hipLaunchKernelGGL((k_preprocess<true, true, false, true>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-        else if (f_half) hipLaunchKernelGGL((k_preprocess<true, false, false, true>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-        else hipLaunchKernelGGL((k_preprocess<false, false, false, true>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-        return;
     }
+    // (grey masks are blended NORMAL only: the host refuses the other modes with SC_FLAG_OPENCV_GREY_MASK)
     if (grey) hipLaunchKernelGGL((k_preprocess<false, false, true>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-    else if (f_half && u_half) hipLaunchKernelGGL((k_preprocess<true, true>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-    else if (f_half) hipLaunchKernelGGL((k_preprocess<true, false>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
-    else hipLaunchKernelGGL((k_preprocess<false, false>), g4, dim3(256), 0, s, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, bb);
+    else if (mode == SC_MIXED_CLONE) launch_preprocess_mode<SC_MIXED_CLONE>(g4, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, s, f_half, u_half, bb);
+    else if (mode == SC_MONOCHROME_TRANSFER) launch_preprocess_mode<SC_MONOCHROME_TRANSFER>(g4, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, s, f_half, u_half, bb);
+    else launch_preprocess_mode<SC_NORMAL_CLONE>(g4, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, s, f_half, u_half, bb);
 }
 
 // Device-to-device refresh of the destinations of a group of clones (sc_batch_job.body_restore) in ONE launch: sixteen separate

@@ -170,6 +170,17 @@ int sc_hip_pool_set_solver(void *p, const sc_solver_opts *opts)
     return SC_OK;
 }
 
+int sc_hip_pool_set_clone_mode(void *p, int mode)
+{
+    Pool *P = get_pool(p);
+    if (!P) return SC_ERR_BAD_ARG;
+    for (void *i : P->inst) {
+        const int rc = sc_hip_set_clone_mode(i, mode);
+        if (rc != SC_OK) return rc;
+    }
+    return SC_OK;
+}
+
 // Runs all jobs (any order, each exactly once) and returns when every one has completed on the GPU.
 // Return value: SC_OK, or the first failing job's code (each job's own code is in jobs[i].rc).
 int sc_hip_pool_set_group(void *p, int group)

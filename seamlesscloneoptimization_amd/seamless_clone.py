@@ -9,6 +9,7 @@ Same method names and argument meaning:
                                                        a copy, SeamlessClone.cpp:217, and the
                                                        clone writes into it, seamlessClone_imp.cpp:470)
     sync(), destroy(), mat2py(a), py2mat(a), loadImageInCpp_Demo(path)
+Additions: setSolver(**opts), setCloneMode(mode), info(); seamlessClone(src, dst, mask, p, flags) shaped like cv2.seamlessClone.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ class SeamlessClone:
         self.centerX = self.centerY = 0
         self.gpu_id = 0
         self._opts = {}
+        self._clone_mode = capi.SC_NORMAL_CLONE
 
     # -- reference surface --------------------------------------------------------------
     def loadMatsInSeamlessClone(self, oface, obody, omask, centerX, centerY, gpu_id):
@@ -40,6 +42,8 @@ class SeamlessClone:
             self.instance_ptr = capi.Instance(self.gpu_id)
             if self._opts:
                 self.instance_ptr.set_solver(**self._opts)
+            if self._clone_mode != capi.SC_NORMAL_CLONE:
+                self.instance_ptr.set_clone_mode(self._clone_mode)
         self.instance_ptr.run(self.face, self.body, self.mask, self.centerX, self.centerY, sync=self.bSync)
         self.blendedMat = self.body       # header copy: aliases the caller's buffer (imp.cpp:470)
         return self.mat2py(self.blendedMat)
@@ -87,19 +91,30 @@ class SeamlessClone:
         if self.instance_ptr is not None:
             self.instance_ptr.set_solver(**kw)
 
+    def setCloneMode(self, mode):
+        """cv2.NORMAL_CLONE (1, default), cv2.MIXED_CLONE (2) or cv2.MONOCHROME_TRANSFER (3) for the next seamlessClone()."""
+        if mode not in capi.CLONE_MODES:
+            raise ValueError("clone mode must be NORMAL_CLONE (1), MIXED_CLONE (2) or MONOCHROME_TRANSFER (3), not %r" % (mode,))
+        self._clone_mode = int(mode)
+        if self.instance_ptr is not None:
+            self.instance_ptr.set_clone_mode(mode)
+
     def info(self):
         return self.instance_ptr.info() if self.instance_ptr is not None else None
 
 
-def seamlessClone(src, dst, mask, p, flags=capi.SC_OK + 1, gpu_id=0, **solver):
-    """cv2.seamlessClone-shaped convenience: returns a NEW blended image, dst untouched."""
-    if flags != 1:
-        raise ValueError("only NORMAL_CLONE (1) is implemented, as in the reference")
+def seamlessClone(src, dst, mask, p, flags=capi.SC_NORMAL_CLONE, gpu_id=0, **solver):
+    """cv2.seamlessClone-shaped convenience: returns a NEW blended image, dst untouched.  flags: cv2.NORMAL_CLONE (1),
+    cv2.MIXED_CLONE (2) or cv2.MONOCHROME_TRANSFER (3)."""
+    if flags not in capi.CLONE_MODES:
+        raise ValueError("flags must be NORMAL_CLONE (1), MIXED_CLONE (2) or MONOCHROME_TRANSFER (3), not %r" % (flags,))
     out = np.array(dst, np.uint8, copy=True, order="C")
     inst = capi.Instance(gpu_id)
     try:
         if solver:
             inst.set_solver(**solver)
+        if flags != capi.SC_NORMAL_CLONE:
+            inst.set_clone_mode(flags)
         inst.run(np.ascontiguousarray(src), out, np.ascontiguousarray(mask), int(p[0]), int(p[1]), sync=True)
     finally:
         inst.destroy()
