@@ -269,6 +269,41 @@ SC_API const char *sc_hip_last_error(void *instance);
 SC_API int  sc_hip_set_clone_mode(void *instance, int mode);
 SC_API int  sc_hip_get_clone_mode(void *instance);
 
+/* ---- whole-image gradient edits: OpenCV 3.4.5's other "Seamless Cloning" functions.  The domain is the whole image: the unknowns
+ * are rows 1..rows-2 and columns 1..cols-2, dst's one-pixel frame is src's, and the change made inside the mask spreads, decaying,
+ * into the rest of the image.  The mask (8-bit, one channel, the image's size; never written) is eroded by a 7 x 7 minimum filter
+ * that ignores pixels outside the image and weights the patch field by M / 255 and src's own gradient by (255 - M) / 255, grey
+ * masks included.  Inside it, per channel, the gradient P = (gx, gy) of src becomes
+ *   COLOR_CHANGE         (P m) k, k = blue_mul, green_mul, red_mul for channels 0, 1, 2
+ *   ILLUMINATION_CHANGE  (Q alpha^beta) |Q|^-beta with Q = P m (0 where that is NaN)
+ *   TEXTURE_FLATTENING   P m at Canny edges of src (L1 gradient, aperture kernel_size, thresholds swapped when low > high), else 0
+ * and the Poisson problem is solved with the instance's solver options (method, flags); the clone mode, reference_warmup and
+ * SC_FLAG_OPENCV_GREY_MASK do not apply.  An empty mask is valid: dst = src within the solve's rounding.  PARITY UNPINNED: checked
+ * against a restatement of that arithmetic (tests/photo_edits_np.py), not against OpenCV.
+ * SC_ERR_BAD_ARG: a bad op, a NULL pointer, a non-finite parameter the op uses, kernel_size not 3, 5 or 7.  SC_ERR_BAD_SIZE: an image
+ * smaller than 3 x 3 or a row step smaller than its row.  Only the cols * 3 bytes of each dst row are written; dst may equal src.
+ * sc_run_info: x0 = y0 = ltx = lty = 0, W x H = the image, the method, field_retry, and (host call, or bSync) the stage times:
+ * ms_mask = erode + Canny.  Single images only: the batch and pool paths do not run edits. */
+#define SC_EDIT_COLOR_CHANGE        1   /* cv::colorChange        */
+#define SC_EDIT_ILLUMINATION_CHANGE 2   /* cv::illuminationChange */
+#define SC_EDIT_TEXTURE_FLATTENING  3   /* cv::textureFlattening  */
+typedef struct sc_edit_params {
+    int   op;
+    float red_mul, green_mul, blue_mul;     /* COLOR_CHANGE                   */
+    float alpha, beta;                      /* ILLUMINATION_CHANGE            */
+    float low_threshold, high_threshold;    /* TEXTURE_FLATTENING             */
+    int   kernel_size;                      /* TEXTURE_FLATTENING: 3, 5 or 7  */
+} sc_edit_params;
+SC_API void sc_hip_default_edit_params(sc_edit_params *p, int op);   /* OpenCV's defaults */
+SC_API int  sc_hip_edit(void *instance, const sc_edit_params *p,
+                        const uint8_t *src, int cols, int rows, int src_step,
+                        const uint8_t *mask, int mask_step,
+                        uint8_t *dst, int dst_step);                 /* host images; dst may equal src */
+SC_API int  sc_hip_edit_device(void *instance, const sc_edit_params *p,
+                        const uint8_t *d_src, int cols, int rows, int src_step,
+                        const uint8_t *d_mask, int mask_step,
+                        uint8_t *d_dst, int dst_step, bool bSync);
+
 /* Same as run(), but face/body/mask are DEVICE pointers on the instance's GPU (inputs
  * resident in HBM); body is updated in place on the device.  Asynchronous on the instance
  * stream unless bSync. */

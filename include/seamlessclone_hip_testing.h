@@ -59,6 +59,18 @@ SC_API int sc_hip_build_rhs(void *instance,
                      const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
                      int centerX, int centerY, int geo[6], float *B_out, float *lap_out, size_t plane_capacity);
 
+/* whole-image edit (sc_hip_edit) up to its right-hand side: M_out receives the eroded mask (dense cols * rows bytes), lap_out the
+ * un-folded right-hand side, planar [3][rows][cols] float32 (0 on the frame).  Either may be NULL. */
+SC_API int sc_hip_edit_rhs(void *instance, const sc_edit_params *p, const uint8_t *src, int cols, int rows, int src_step,
+                           const uint8_t *mask, int mask_step, uint8_t *M_out, float *lap_out, size_t plane_capacity);
+/* the Canny detector of SC_EDIT_TEXTURE_FLATTENING on a host image: classes_out = the map after non-maximum suppression (0 none,
+ * 1 weak, 2 strong), edges_out = the edge map after hysteresis (255 edge, 0 not), dense cols * rows bytes each (either may be NULL);
+ * counts[0] = hysteresis launches, counts[1] = mailbox reads (may be NULL).  sc_hip_edit_counts: the same two counts of the last
+ * edit (0 unless it was a texture flattening). */
+SC_API int sc_hip_canny(void *instance, const uint8_t *src, int cols, int rows, int src_step, float low_threshold,
+                        float high_threshold, int kernel_size, uint8_t *classes_out, uint8_t *edges_out, int counts[2]);
+SC_API int sc_hip_edit_counts(void *instance, int counts[2]);
+
 /* solver-only hooks on caller-supplied fields, planar [C][H][W] float32 (ring included). */
 SC_API int sc_hip_field_load(void *instance, int W, int H, int C, const float *U, const float *lap);
 SC_API int sc_hip_field_sweep(void *instance, int method, int sweeps, float omega, int sweeps_per_launch);

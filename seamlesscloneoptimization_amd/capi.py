@@ -32,6 +32,12 @@ SC_MIXED_CLONE = 2
 SC_MONOCHROME_TRANSFER = 3
 CLONE_MODES = (SC_NORMAL_CLONE, SC_MIXED_CLONE, SC_MONOCHROME_TRANSFER)
 
+# whole-image gradient edits (sc_hip_edit): cv::colorChange, cv::illuminationChange, cv::textureFlattening; Instance.edit
+SC_EDIT_COLOR_CHANGE = 1
+SC_EDIT_ILLUMINATION_CHANGE = 2
+SC_EDIT_TEXTURE_FLATTENING = 3
+EDIT_OPS = (SC_EDIT_COLOR_CHANGE, SC_EDIT_ILLUMINATION_CHANGE, SC_EDIT_TEXTURE_FLATTENING)
+
 SC_METHOD_JACOBI = 0
 SC_METHOD_RBGS = 1
 SC_METHOD_SOR = 2
@@ -99,6 +105,12 @@ class BatchJob(C.Structure):
                 ("body", C.c_void_p), ("body_cols", C.c_int), ("body_rows", C.c_int), ("body_step", C.c_int),
                 ("mask", C.c_void_p), ("mask_cols", C.c_int), ("mask_rows", C.c_int), ("mask_step", C.c_int),
                 ("centerX", C.c_int), ("centerY", C.c_int), ("body_restore", C.c_void_p), ("rc", C.c_int)]
+
+
+class EditParams(C.Structure):
+    _fields_ = [("op", C.c_int), ("red_mul", C.c_float), ("green_mul", C.c_float), ("blue_mul", C.c_float),
+                ("alpha", C.c_float), ("beta", C.c_float), ("low_threshold", C.c_float), ("high_threshold", C.c_float),
+                ("kernel_size", C.c_int)]
 
 
 class SeamlessCloneError(RuntimeError):
@@ -244,6 +256,18 @@ def load():
     L.sc_hip_plan_cache_clear.argtypes = []
     L.sc_hip_plan_cache_clear.restype = None
     L.sc_hip_plan_size.restype = C.c_int
+    L.sc_hip_default_edit_params.argtypes = [C.POINTER(EditParams), C.c_int]
+    L.sc_hip_default_edit_params.restype = None
+    L.sc_hip_edit.argtypes = [C.c_void_p, C.POINTER(EditParams)] + _IMG + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.sc_hip_edit.restype = C.c_int
+    L.sc_hip_edit_device.argtypes = [C.c_void_p, C.POINTER(EditParams)] + _IMG + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_bool]
+    L.sc_hip_edit_device.restype = C.c_int
+    L.sc_hip_edit_rhs.argtypes = [C.c_void_p, C.POINTER(EditParams)] + _IMG + [C.c_void_p, C.c_int, u8p, f32p, C.c_size_t]
+    L.sc_hip_edit_rhs.restype = C.c_int
+    L.sc_hip_canny.argtypes = [C.c_void_p] + _IMG + [C.c_float, C.c_float, C.c_int, u8p, u8p, i32p]
+    L.sc_hip_canny.restype = C.c_int
+    L.sc_hip_edit_counts.argtypes = [C.c_void_p, i32p]
+    L.sc_hip_edit_counts.restype = C.c_int
     _lib = L
     return L
 
@@ -334,6 +358,64 @@ class Instance:
         f, b, m = _img(face), _img(body), _img(mask)
         rc = self.L.my_seamlessclone_api_imp_run(self.h, *f, *b, *m, int(cx), int(cy), self.gpu_id, bool(sync))
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    # ---- whole-image edits
+    def edit_params(self, op: int, **kw) -> EditParams:
+        """OpenCV's defaults for `op` (sc_hip_default_edit_params), with the fields named in kw replaced."""
+        p = EditParams()
+        self.L.sc_hip_default_edit_params(C.byref(p), int(op))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+    def edit(self, params: EditParams, src, mask, dst=None, allow_not_converged=False):
+        """sc_hip_edit on host images: src H x W x 3, mask H x W (uint8).  dst: an array of src's shape to write (may be src
+        itself), default a new one.  Returns dst."""
+        if dst is None:
+            dst = np.empty_like(src)
+        s, m, d = _img(src), _img(mask), _img(dst)
+        if m[1:3] != s[1:3] or d[1:3] != s[1:3]:
+            raise ValueError("src, mask and dst must have one size")
+        rc = self.L.sc_hip_edit(self.h, C.byref(params), *s, m[0], m[3], d[0], d[3])
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return dst
+
+    def edit_device(self, params: EditParams, d_src, shape, d_mask, d_dst, src_step=None, mask_step=None, dst_step=None,
+                    sync=True, allow_not_converged=False):
+        """sc_hip_edit_device: device images of shape (rows, cols); steps default to dense rows."""
+        rows, cols = shape[0], shape[1]
+        rc = self.L.sc_hip_edit_device(self.h, C.byref(params), d_src, cols, rows, src_step or 3 * cols, d_mask,
+                                       mask_step or cols, d_dst, dst_step or 3 * cols, bool(sync))
+        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    def edit_rhs(self, params: EditParams, src, mask):
+        """(eroded mask H x W, un-folded right-hand side [3][H][W]) of an edit (test hook)."""
+        s, m = _img(src), _img(mask)
+        W, H = s[1], s[2]
+        M = np.zeros((H, W), np.uint8)
+        lap = np.zeros((3, H, W), np.float32)
+        self._check(self.L.sc_hip_edit_rhs(self.h, C.byref(params), *s, m[0], m[3], M.ctypes.data_as(u8p), lap.ctypes.data_as(f32p),
+                                           W * H))
+        return M, lap
+
+    def canny(self, src, low, high, kernel_size=3):
+        """(class map before hysteresis: 0 / 1 weak / 2 strong, edge map 0 / 255, (hysteresis launches, mailbox reads))."""
+        s = _img(src)
+        W, H = s[1], s[2]
+        cls = np.zeros((H, W), np.uint8)
+        edges = np.zeros((H, W), np.uint8)
+        counts = np.zeros(2, np.int32)
+        self._check(self.L.sc_hip_canny(self.h, *s, float(low), float(high), int(kernel_size), cls.ctypes.data_as(u8p),
+                                        edges.ctypes.data_as(u8p), counts.ctypes.data_as(i32p)))
+        return cls, edges, (int(counts[0]), int(counts[1]))
+
+    def edit_counts(self):
+        """(hysteresis launches, mailbox reads) of the last edit."""
+        counts = np.zeros(2, np.int32)
+        self._check(self.L.sc_hip_edit_counts(self.h, counts.ctypes.data_as(i32p)))
+        return int(counts[0]), int(counts[1])
 
     # ---- device-resident images
     def malloc(self, nbytes):

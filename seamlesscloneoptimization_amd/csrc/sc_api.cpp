@@ -340,7 +340,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     if (I->aux2) (void)hipStreamSynchronize(I->aux2);
     for (DevBuf &b : I->retired) dev_release(b);                    // blocks that growth replaced (ensure)
     for (Instance::Slab &sl : I->slabs) if (sl.base) (void)hipFree(sl.base);
-    DevBuf *bufs[] = { &I->d_face, &I->d_body_roi, &I->d_out, &I->d_mask, &I->d_in, &I->d_M, &I->d_U0, &I->d_U1, &I->d_F };
+    DevBuf *bufs[] = { &I->d_face, &I->d_body_roi, &I->d_out, &I->d_mask, &I->d_in, &I->d_M, &I->d_edge, &I->d_U0, &I->d_U1, &I->d_F };
     for (DevBuf *b : bufs) dev_release(*b);
     for (DevBuf &b : I->mg_bufs) dev_release(b);
     dev_release(I->mg_partial);
@@ -382,7 +382,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     if (I->h_maxcorr) (void)hipHostFree(I->h_maxcorr);
     if (I->h_rect) (void)hipHostFree(I->h_rect);
     if (I->h_red) (void)hipHostFree(I->h_red);
-    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in }) if (b->p) (void)hipHostFree(b->p);
+    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in, &I->h_hyst }) if (b->p) (void)hipHostFree(b->p);
     for (int i = 0; i < 8; ++i) if (I->ev[i]) (void)hipEventDestroy(I->ev[i]);
     for (int i = 0; i < 8; ++i) if (I->ev_chunk[i]) (void)hipEventDestroy(I->ev_chunk[i]);
     if (I->ev_k0) (void)hipEventDestroy(I->ev_k0);

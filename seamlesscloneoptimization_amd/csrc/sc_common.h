@@ -57,6 +57,15 @@ int  mask_bbox_blocks(int mw, int mh);                               // workgrou
 void launch_mask_bbox(const uint8_t *mask, int mw, int mh, int mstep, BboxFold fold, hipStream_t s);
 void launch_mask_erode3(const uint8_t *mask, int mstep, int mask_rows, Geo g, uint8_t *M, int mpitch, hipStream_t s);
 void launch_mask_erode_min7(const uint8_t *mask, int mstep, Geo g, uint8_t *M, int mpitch, hipStream_t s);   // OpenCV's grey-mask erode (SC_FLAG_OPENCV_GREY_MASK)
+// the whole-image edits (sc_edit.hip): 7 x 7 minimum filter that ignores pixels outside the image; Canny's class map (0 / 1 weak /
+// 2 strong) and one hysteresis launch (stores `round` into *mailbox when a tile's edge pixel changed); the edit's pre-process (op:
+// SC_EDIT_*, k = per-channel factors B, G, R, ab = alpha^beta, nbeta = -beta; E: the class map after hysteresis); src's frame into dst
+void launch_edit_erode(const uint8_t *mask, int mstep, int W, int H, uint8_t *M, int mpitch, hipStream_t s);
+void launch_canny_nms(const uint8_t *src, int sstep, int W, int H, int lo, int hi, int aperture, uint8_t *C, int cpitch, hipStream_t s);
+void launch_canny_hyst(uint8_t *C, int cpitch, int W, int H, unsigned *mailbox, unsigned round, hipStream_t s);
+void launch_edit_frame(const uint8_t *src, int sstep, uint8_t *dst, int dstep, int W, int H, hipStream_t s);
+void launch_edit_preprocess(int op, const float k[3], float ab, float nbeta, const uint8_t *src, int sstep, const uint8_t *M, int mpitch,
+                            const uint8_t *E, Field U0, Field F, hipStream_t s);
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

@@ -1,0 +1,238 @@
+// sc_edit_api.cpp -- the whole-image gradient edits of the C ABI (sc_hip_edit, sc_hip_edit_device: cv::colorChange,
+// cv::illuminationChange, cv::textureFlattening) and the stages the test hooks drive (edit_stage, canny_stage).
+//
+// One edit: erode of the whole mask -> [Canny: class map, hysteresis launches] -> edit pre-process (float right-hand side,
+// U0 = src) -> the instance's solve -> post-process into dst's interior [+ the frame of src when dst is another image].  The
+// domain is the whole image (x0 = y0 = ltx = lty = 0): no bounding box, no speculation, no clone mode.  Kernels: sc_edit.hip.
+#include "sc_instance.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace sc;
+
+namespace sc {
+
+int edit_validate(Instance *I, const sc_edit_params *p, const void *src, int cols, int rows, int ss, const void *mask, int ms,
+                  const void *dst, int ds)
+{
+    if (!p || !src || !mask || !dst) { I->err = "null pointer"; return SC_ERR_BAD_ARG; }
+    if (p->op != SC_EDIT_COLOR_CHANGE && p->op != SC_EDIT_ILLUMINATION_CHANGE && p->op != SC_EDIT_TEXTURE_FLATTENING) {
+        I->err = "op must be SC_EDIT_COLOR_CHANGE, SC_EDIT_ILLUMINATION_CHANGE or SC_EDIT_TEXTURE_FLATTENING";
+        return SC_ERR_BAD_ARG;
+    }
+    const float used[] = { p->red_mul, p->green_mul, p->blue_mul, p->alpha, p->beta, p->low_threshold, p->high_threshold };
+    const int first = p->op == SC_EDIT_COLOR_CHANGE ? 0 : p->op == SC_EDIT_ILLUMINATION_CHANGE ? 3 : 5;
+    const int last = p->op == SC_EDIT_COLOR_CHANGE ? 3 : p->op == SC_EDIT_ILLUMINATION_CHANGE ? 5 : 7;
+    for (int i = first; i < last; ++i)
+        if (!std::isfinite(used[i])) { I->err = "non-finite edit parameter"; return SC_ERR_BAD_ARG; }
+    if (p->op == SC_EDIT_TEXTURE_FLATTENING && p->kernel_size != 3 && p->kernel_size != 5 && p->kernel_size != 7) {
+        I->err = "kernel_size must be 3, 5 or 7";
+        return SC_ERR_BAD_ARG;
+    }
+    if (cols < 3 || rows < 3) { I->err = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
+    if (ss < 3 * cols || ds < 3 * cols || ms < cols) { I->err = "row step smaller than the row"; return SC_ERR_BAD_SIZE; }
+    return SC_OK;
+}
+
+// cv::Canny's thresholds: swapped when low > high, then floored (L1 gradient).  Clamped into [-1, 2^20]: magnitudes lie in
+// [0, 65536], so the comparisons come out the same and the values fit an int.
+static void canny_thresholds(float low, float high, int &lo, int &hi)
+{
+    if (low > high) std::swap(low, high);
+    const double l = std::floor((double)low), h = std::floor((double)high);
+    lo = (int)std::min(std::max(l, -1.0), 1048576.0);
+    hi = (int)std::min(std::max(h, -1.0), 1048576.0);
+}
+
+// Canny of the whole image into I->d_edge (pitch I->mpitch): the class map, then hysteresis launches until one of them changed
+// no tile's edge pixel (k_canny_hyst).  The host reads the pinned mailbox after every HYST_BATCH launches: one wait per batch
+// instead of one per launch; the launches after the map is final change nothing.  C_out: the class map before hysteresis
+// (test hook; synchronises).
+int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float low, float high, int aperture, uint8_t *C_out)
+{
+    int lo, hi, rc;
+    canny_thresholds(low, high, lo, hi);
+    if ((rc = ensure(I, I->d_edge, (size_t)I->mpitch * H, false))) return rc;
+    if ((rc = ensure_pinned(I, I->h_hyst, 64))) return rc;
+    uint8_t *E = (uint8_t *)I->d_edge.p;
+    launch_canny_nms(d_src, ss, W, H, lo, hi, aperture, E, I->mpitch, I->stream);
+    SC_HIP(I, hipGetLastError());
+    if (C_out && (rc = download_rows(I, I->h_out, C_out, W, E, I->mpitch, W, H))) return rc;
+    constexpr int HYST_BATCH = 4;
+    volatile unsigned *box = (volatile unsigned *)I->h_hyst.p;
+    // Each launch that reports an edge change has turned at least one weak pixel strong, so the loop ends; the cap is that bound.
+    const long long max_launches = (long long)W * H + HYST_BATCH + 1;
+    unsigned round = 0;
+    I->hyst_launches = 0; I->hyst_reads = 0;
+    for (;;) {
+        SC_HIP(I, hipStreamSynchronize(I->stream));      // nothing of this instance reads or writes the mailbox while it is reset
+        *box = 0u;
+        for (int k = 0; k < HYST_BATCH; ++k) launch_canny_hyst(E, I->mpitch, W, H, (unsigned *)I->h_hyst.p, ++round, I->stream);
+        SC_HIP(I, hipGetLastError());
+        I->hyst_launches += HYST_BATCH;
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        ++I->hyst_reads;
+        if (*box != round) break;                         // the batch's last launch changed no edge pixel: the map is final
+        if (I->hyst_launches > max_launches) { I->err = "hysteresis did not settle"; return SC_ERR_HIP; }
+    }
+    return SC_OK;
+}
+
+// Erode (and for texture flattening Canny) + the edit's pre-process on device images: leaves d_M, d_edge and the fields.
+int edit_stage(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int W, int H, int ss, const uint8_t *d_mask, int ms)
+{
+    int rc;
+    I->mpitch = round_up(W, 64);
+    if ((rc = ensure(I, I->d_M, (size_t)I->mpitch * H, false))) return rc;
+    launch_edit_erode(d_mask, ms, W, H, (uint8_t *)I->d_M.p, I->mpitch, I->stream);
+    SC_HIP(I, hipGetLastError());
+    if (p->op == SC_EDIT_TEXTURE_FLATTENING &&
+        (rc = canny_stage(I, d_src, W, H, ss, p->low_threshold, p->high_threshold, p->kernel_size, nullptr))) return rc;
+    return SC_OK;
+}
+
+void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int ss)
+{
+    const float k[3] = { p->blue_mul, p->green_mul, p->red_mul };      // channel 0 is B
+    const float ab = powf(p->alpha, p->beta);
+    launch_edit_preprocess(p->op, k, ab, -p->beta, d_src, ss, (const uint8_t *)I->d_M.p, I->mpitch,
+                           p->op == SC_EDIT_TEXTURE_FLATTENING ? (const uint8_t *)I->d_edge.p : nullptr, I->U0, I->F, I->stream);
+}
+
+} // namespace sc
+
+namespace {
+
+void mark(Instance *I, int k)
+{
+    if (I->stage_marks) (void)hipEventRecord(I->ev[k], I->stream);
+}
+
+// The whole edit on device images.  Marks: 0 start, 4 mask + Canny done, 5 pre-process done, 6 solve done, 7 output done.
+int edit_device(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int W, int H, int ss, const uint8_t *d_mask, int ms,
+                uint8_t *d_dst, int ds)
+{
+    int rc;
+    Geo g{ 0, 0, W, H, 0, 0 };
+    fill_info_geo(I, g);
+    I->hyst_launches = I->hyst_reads = 0;
+    if ((rc = setup_fields(I, W, H, 3))) return rc;
+    mark(I, 0);
+    if ((rc = edit_stage(I, p, d_src, W, H, ss, d_mask, ms))) return rc;
+    mark(I, 4);
+    I->guard = RectGuard();
+    I->spec_post.group.clear();
+    I->edit_call = true;          // a float right-hand side (mg_reads_half_rhs)
+    int solve_rc = SC_OK;
+    for (;;) {
+        if (solve_rc == SC_RETRY_FLOAT_FIELD) {      // the 16-bit field saturated, nothing was written: again on float fields
+            I->force_float_field = true;
+            I->info.field_retry = 1;
+        }
+        I->result_in_U1 = false;
+        I->f_half = mg_reads_half_rhs(I);
+        I->u_half = false;
+        edit_preprocess(I, p, d_src, ss);
+        SC_HIP(I, hipGetLastError());
+        mark(I, 5);
+        I->info.sweep_launches = 0;
+        I->spec_post.body_org = d_dst; I->spec_post.bstep = ds;
+        I->spec_post.ev_solved = nullptr;
+        I->spec_post.armed = true; I->spec_post.done = false;
+        solve_rc = solve(I);
+        I->spec_post.armed = false;
+        I->force_float_field = false;
+        if (solve_rc == SC_RETRY_FLOAT_FIELD) continue;
+        break;
+    }
+    I->edit_call = false;
+    if (solve_rc != SC_OK && solve_rc != SC_ERR_NOT_CONVERGED) return solve_rc;
+    mark(I, 6);                   // (a solver that wrote the output itself: ms_post is the frame copy only, ms_solve includes the rest)
+    if (!I->spec_post.done) {
+        LmNodes lm;
+        if ((rc = output_nodes(I, lm))) return rc;
+        launch_postprocess(result(I), d_dst, ds, I->stream, RectGuard(), lm);
+    }
+    if (d_dst != d_src) launch_edit_frame(d_src, ss, d_dst, ds, W, H, I->stream);
+    SC_HIP(I, hipGetLastError());
+    mark(I, 7);
+    return solve_rc;
+}
+
+void edit_timing(Instance *I)
+{
+    I->info.ms_mask = ev_ms(I->ev[0], I->ev[4]);
+    I->info.ms_pre = ev_ms(I->ev[4], I->ev[5]);
+    I->info.ms_solve = ev_ms(I->ev[5], I->ev[6]);
+    I->info.ms_post = ev_ms(I->ev[6], I->ev[7]);
+    I->info.ms_device_total = I->info.ms_mask + I->info.ms_pre + I->info.ms_solve + I->info.ms_post;
+}
+
+} // namespace
+
+extern "C" {
+
+void sc_hip_default_edit_params(sc_edit_params *p, int op)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->op = op;
+    p->red_mul = p->green_mul = p->blue_mul = 1.0f;
+    p->alpha = 0.2f; p->beta = 0.4f;
+    p->low_threshold = 30.0f; p->high_threshold = 45.0f;
+    p->kernel_size = 3;
+}
+
+int sc_hip_edit_device(void *inst, const sc_edit_params *p, const uint8_t *d_src, int cols, int rows, int ss,
+                       const uint8_t *d_mask, int ms, uint8_t *d_dst, int ds, bool bSync)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    if ((rc = edit_validate(I, p, d_src, cols, rows, ss, d_mask, ms, d_dst, ds))) return rc;
+    I->stage_marks = bSync;
+    I->marks_ends_only = false;
+    I->info.ms_h2d = I->info.ms_d2h = 0.f;
+    rc = edit_device(I, p, d_src, cols, rows, ss, d_mask, ms, d_dst, ds);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    if (bSync) {
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        edit_timing(I);
+        I->info.ms_call = ev_ms(I->ev[0], I->ev[7]);
+    } else {
+        I->info.ms_mask = I->info.ms_pre = I->info.ms_solve = I->info.ms_post = I->info.ms_device_total = I->info.ms_call = 0.f;
+    }
+    return rc;
+}
+
+int sc_hip_edit(void *inst, const sc_edit_params *p, const uint8_t *src, int cols, int rows, int ss, const uint8_t *mask, int ms,
+                uint8_t *dst, int ds)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    if ((rc = edit_validate(I, p, src, cols, rows, ss, mask, ms, dst, ds))) return rc;
+    I->stage_marks = true;         // a host-image call is synchronous: its timeline is always read
+    I->marks_ends_only = false;
+    const int dps = round_up(3 * cols, 256), dms = round_up(cols, 256);
+    if ((rc = ensure(I, I->d_face, (size_t)dps * rows + 64, false))) return rc;
+    if ((rc = ensure(I, I->d_out, (size_t)dps * rows + 64, false))) return rc;
+    if ((rc = ensure(I, I->d_mask, (size_t)dms * rows + 64, false))) return rc;
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    if ((rc = upload_rows(I, I->h_face, I->d_face.p, dps, src, ss, 3 * (size_t)cols, rows))) return rc;
+    if ((rc = upload_rows(I, I->h_mask, I->d_mask.p, dms, mask, ms, cols, rows))) return rc;
+    rc = edit_device(I, p, (const uint8_t *)I->d_face.p, cols, rows, dps, (const uint8_t *)I->d_mask.p, dms, (uint8_t *)I->d_out.p, dps);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    const int rc_solve = rc;
+    if ((rc = download_rows(I, I->h_out, dst, ds, I->d_out.p, dps, 3 * (size_t)cols, rows))) return rc;      // only cols * 3 bytes of a row
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    edit_timing(I);
+    I->info.ms_h2d = ev_ms(I->ev_k0, I->ev[0]);
+    I->info.ms_d2h = ev_ms(I->ev[7], I->ev_k1);
+    I->info.ms_call = ev_ms(I->ev_k0, I->ev_k1);
+    return rc_solve;
+}
+
+} // extern "C"

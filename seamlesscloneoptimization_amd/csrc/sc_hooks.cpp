@@ -3,6 +3,7 @@
 // calls into this file.
 #include "sc_instance.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -138,6 +139,73 @@ int sc_hip_build_rhs(void *p, const uint8_t *face, int fc, int fr, int fs, const
     if (B_out && (rc = download_field(I, I->U0, B_out))) return rc;
     if (lap_out && (rc = download_field(I, I->F, lap_out))) return rc;
     SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+// the image and the mask of an edit hook to the device (d_face, d_mask at their padded pitches)
+static int edit_upload(Instance *I, const uint8_t *src, int cols, int rows, int ss, const uint8_t *mask, int ms, int &dps, int &dms)
+{
+    int rc;
+    dps = round_up(3 * cols, 256);
+    dms = round_up(cols, 256);
+    if ((rc = ensure(I, I->d_face, (size_t)dps * rows + 64, false))) return rc;
+    if ((rc = upload_rows(I, I->h_face, I->d_face.p, dps, src, ss, 3 * (size_t)cols, rows))) return rc;
+    if (mask) {
+        if ((rc = ensure(I, I->d_mask, (size_t)dms * rows + 64, false))) return rc;
+        if ((rc = upload_rows(I, I->h_mask, I->d_mask.p, dms, mask, ms, cols, rows))) return rc;
+    }
+    return SC_OK;
+}
+
+int sc_hip_edit_rhs(void *p, const sc_edit_params *ep, const uint8_t *src, int cols, int rows, int ss, const uint8_t *mask, int ms,
+                    uint8_t *M_out, float *lap_out, size_t plane_capacity)
+{
+    Instance *I = get(p);
+    if (!I) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    int rc = edit_validate(I, ep, src, cols, rows, ss, mask, ms, src, 3 * cols);
+    if (rc) return rc;
+    if (plane_capacity < (size_t)cols * rows) return SC_ERR_BAD_SIZE;
+    int dps, dms;
+    if ((rc = edit_upload(I, src, cols, rows, ss, mask, ms, dps, dms))) return rc;
+    if ((rc = setup_fields(I, cols, rows, 3))) return rc;
+    if ((rc = edit_stage(I, ep, (const uint8_t *)I->d_face.p, cols, rows, dps, (const uint8_t *)I->d_mask.p, dms))) return rc;
+    edit_preprocess(I, ep, (const uint8_t *)I->d_face.p, dps);
+    SC_HIP(I, hipGetLastError());
+    if (M_out && (rc = download_rows(I, I->h_out, M_out, cols, I->d_M.p, I->mpitch, cols, rows))) return rc;
+    if (lap_out && (rc = download_field(I, I->F, lap_out))) return rc;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_canny(void *p, const uint8_t *src, int cols, int rows, int ss, float low, float high, int aperture, uint8_t *classes_out,
+                 uint8_t *edges_out, int counts[2])
+{
+    Instance *I = get(p);
+    if (!I || !src) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    if (!std::isfinite(low) || !std::isfinite(high) || (aperture != 3 && aperture != 5 && aperture != 7)) return SC_ERR_BAD_ARG;
+    if (cols < 1 || rows < 1 || ss < 3 * cols) return SC_ERR_BAD_SIZE;
+    int rc, dps, dms;
+    if ((rc = edit_upload(I, src, cols, rows, ss, nullptr, 0, dps, dms))) return rc;
+    I->mpitch = round_up(cols, 64);
+    if ((rc = canny_stage(I, (const uint8_t *)I->d_face.p, cols, rows, dps, low, high, aperture, classes_out))) return rc;
+    if (edges_out) {
+        if ((rc = download_rows(I, I->h_out, edges_out, cols, I->d_edge.p, I->mpitch, cols, rows))) return rc;
+        for (size_t i = 0; i < (size_t)cols * rows; ++i) edges_out[i] = edges_out[i] == 2 ? 255 : 0;
+    }
+    if (counts) { counts[0] = I->hyst_launches; counts[1] = I->hyst_reads; }
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_edit_counts(void *p, int counts[2])
+{
+    Instance *I = get(p);
+    if (!I || !counts) return SC_ERR_BAD_ARG;
+    counts[0] = I->hyst_launches; counts[1] = I->hyst_reads;
     return SC_OK;
 }
 

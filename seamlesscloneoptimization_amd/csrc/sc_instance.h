@@ -140,6 +140,7 @@ struct Instance {
     bool aux_pending = false;              // work on aux that `stream` has not waited for yet
     sc_solver_opts opts{};
     int clone_mode = SC_NORMAL_CLONE;      // sc_hip_set_clone_mode; apart from opts: sc_hip_set_solver does not touch it
+    bool edit_call = false;                // an edit (sc_edit_api.cpp) is solving: its right-hand side is float (mg_reads_half_rhs)
     sc_run_info info{};
     std::string err;
 
@@ -154,6 +155,9 @@ struct Instance {
     // ROI mask after 3x erode
     DevBuf d_M;
     int mpitch = 0;
+    // edits (sc_edit_api.cpp): Canny's class map (pitch mpitch), the hysteresis mailbox (pinned), the last edit's hysteresis counts
+    DevBuf d_edge, h_hyst;
+    int hyst_launches = 0, hyst_reads = 0;
     // fields
     DevBuf d_U0, d_U1, d_F;
     Field U0, U1, F;      // current views into the buffers above
@@ -269,6 +273,12 @@ int device_bbox(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, int 
 void erode_mask(Instance *I, const uint8_t *d_mask, int ms, int mr, const Geo &g);                    // ROI g of the mask into I->d_M
 void fill_info_geo(Instance *I, const Geo &g);
 float ev_ms(hipEvent_t a, hipEvent_t b);
+// sc_edit_api.cpp: the whole-image edits' stages (the test hooks drive them too)
+int edit_validate(Instance *I, const sc_edit_params *p, const void *src, int cols, int rows, int ss, const void *mask, int ms,
+                  const void *dst, int ds);
+int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float low, float high, int aperture, uint8_t *C_out);
+int edit_stage(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int W, int H, int ss, const uint8_t *d_mask, int ms);
+void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int ss);     // into I->U0, I->F (setup_fields first)
 // sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
 void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
 int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);

@@ -9,7 +9,8 @@ Same method names and argument meaning:
                                                        a copy, SeamlessClone.cpp:217, and the
                                                        clone writes into it, seamlessClone_imp.cpp:470)
     sync(), destroy(), mat2py(a), py2mat(a), loadImageInCpp_Demo(path)
-Additions: setSolver(**opts), setCloneMode(mode), info(); seamlessClone(src, dst, mask, p, flags) shaped like cv2.seamlessClone.
+Additions: setSolver(**opts), setCloneMode(mode), info(); seamlessClone(src, dst, mask, p, flags) shaped like cv2.seamlessClone;
+colorChange, illuminationChange and textureFlattening shaped like their cv2 namesakes.
 """
 from __future__ import annotations
 
@@ -119,3 +120,49 @@ def seamlessClone(src, dst, mask, p, flags=capi.SC_NORMAL_CLONE, gpu_id=0, **sol
     finally:
         inst.destroy()
     return out
+
+
+def _edit_mask(mask, shape):
+    """H x W or H x W x 3 uint8 -> H x W; three channels through cvtColor(BGR2GRAY)'s integer formula for 8-bit data."""
+    m = np.asarray(mask, np.uint8)
+    if m.ndim == 3 and m.shape[2] == 1:
+        m = m[:, :, 0]
+    if m.ndim == 3:
+        if m.shape[2] != 3:
+            raise ValueError("mask must have one or three channels")
+        i = m.astype(np.int64)
+        m = ((1868 * i[..., 0] + 9617 * i[..., 1] + 4899 * i[..., 2] + 8192) >> 14).astype(np.uint8)
+    if m.shape != tuple(shape[:2]):
+        raise ValueError("mask must have the image's size")
+    return np.ascontiguousarray(m)
+
+
+def _edit(op, src, mask, gpu_id, solver, **params):
+    s = np.ascontiguousarray(src, np.uint8)
+    if s.ndim != 3 or s.shape[2] != 3:
+        raise ValueError("src must be H x W x 3 uint8")
+    m = _edit_mask(mask, s.shape)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.edit(inst.edit_params(op, **params), s, m)
+    finally:
+        inst.destroy()
+
+
+def colorChange(src, mask, red_mul=1.0, green_mul=1.0, blue_mul=1.0, gpu_id=0, **solver):
+    """cv2.colorChange-shaped: returns a NEW image, src untouched.  The mask is H x W or H x W x 3."""
+    return _edit(capi.SC_EDIT_COLOR_CHANGE, src, mask, gpu_id, solver, red_mul=float(red_mul), green_mul=float(green_mul),
+                 blue_mul=float(blue_mul))
+
+
+def illuminationChange(src, mask, alpha=0.2, beta=0.4, gpu_id=0, **solver):
+    """cv2.illuminationChange-shaped: returns a NEW image, src untouched."""
+    return _edit(capi.SC_EDIT_ILLUMINATION_CHANGE, src, mask, gpu_id, solver, alpha=float(alpha), beta=float(beta))
+
+
+def textureFlattening(src, mask, low_threshold=30, high_threshold=45, kernel_size=3, gpu_id=0, **solver):
+    """cv2.textureFlattening-shaped: returns a NEW image, src untouched.  kernel_size: 3, 5 or 7."""
+    return _edit(capi.SC_EDIT_TEXTURE_FLATTENING, src, mask, gpu_id, solver, low_threshold=float(low_threshold),
+                 high_threshold=float(high_threshold), kernel_size=int(kernel_size))
