@@ -283,7 +283,7 @@ SC_API int  sc_hip_get_clone_mode(void *instance);
  * SC_ERR_BAD_ARG: a bad op, a NULL pointer, a non-finite parameter the op uses, kernel_size not 3, 5 or 7.  SC_ERR_BAD_SIZE: an image
  * smaller than 3 x 3 or a row step smaller than its row.  Only the cols * 3 bytes of each dst row are written; dst may equal src.
  * sc_run_info: x0 = y0 = ltx = lty = 0, W x H = the image, the method, field_retry, and (host call, or bSync) the stage times:
- * ms_mask = erode + Canny.  Single images only: the batch and pool paths do not run edits. */
+ * ms_mask = erode + Canny.  Many images at once: sc_hip_edit_device_batch and sc_hip_pool_edit below. */
 #define SC_EDIT_COLOR_CHANGE        1   /* cv::colorChange        */
 #define SC_EDIT_ILLUMINATION_CHANGE 2   /* cv::illuminationChange */
 #define SC_EDIT_TEXTURE_FLATTENING  3   /* cv::textureFlattening  */
@@ -377,6 +377,40 @@ SC_API int sc_hip_plan_groups(const int *wh, int n, int cap, const sc_solver_opt
 /* ... and how sc_hip_pool_run would: a pool of `streams` workers with group size `group` (SC_POOL_GROUP_AUTO allowed), jobs handed
  * to the planner largest first */
 SC_API int sc_hip_plan_groups_pool(const int *wh, int n, int group, int streams, const sc_solver_opts *opts, int *group_of, int *kind_of);
+
+/* ---- batches of whole-image edits ---------------------------------------------------------------------------------------------
+ * ONE op and ONE parameter set per call: every job of a call shares *p; each job has its own image, mask and destination (one mask
+ * shared by every job is allowed).  Each job means what sc_hip_edit_device means on it, with the instance's solver options: the
+ * whole image is the domain, dst's frame is src's, the caller's mask is never written.
+ * Aliasing: a job's dst may equal its own src; no job's dst may overlap another job's src, mask or dst; jobs may read one src or mask.
+ * Partitioning: jobs with the same cols x rows are solved as ONE field of 3n channels (erode, Canny, pre- and post-process one launch
+ * per 16 members, one set of solver launches for the group); a job whose size no other job shares runs alone through the
+ * single-image path.  Group members get the multigrid answer (SC_METHOD_AUTO resolves to it for a group), and the stop rule sees the
+ * group's largest correction: a member equals its solo SC_METHOD_MULTIGRID run byte for byte when the cycle counts agree, and is within
+ * one grey level of it otherwise.
+ * Errors: a job that does not validate (the codes of sc_hip_edit_device) gets its own code in rc and is skipped, the others run; a group
+ * that fails other than with SC_ERR_HIP runs its members alone.  The return value is the worst code (SC_ERR_NOT_CONVERGED only when
+ * nothing worse happened).  A HIP error ends the call: every job that validated then reads SC_ERR_HIP, the ones already run included
+ * (their work was on the failed stream).  A saturated 16-bit field repeats the whole group on float fields (sc_run_info.field_retry).
+ * Asynchronous like sc_hip_run_device_batch (sync the instance before reading destinations), except that TEXTURE_FLATTENING waits on
+ * the host once per batch of hysteresis launches, for the whole group at once.  sc_run_info afterwards: the last group's (group_members,
+ * W x H = the image), or the last job's when no group was formed; no stage times. */
+typedef struct sc_edit_job {
+    const uint8_t *src;  int cols, rows, src_step;   /* 8-bit BGR */
+    const uint8_t *mask; int mask_step;              /* 8-bit, one channel, cols x rows */
+    uint8_t *dst;        int dst_step;               /* may equal src (in place) */
+    int rc;                                          /* out: SC_OK or SC_ERR_* of this job */
+} sc_edit_job;
+SC_API int sc_hip_edit_device_batch(void *instance, const sc_edit_params *p, sc_edit_job *jobs, int n);
+/* The pool's form.  device_resident: the jobs are bucketed by image size and cut into chunks of sc_hip_pool_set_group's size
+ * (SC_POOL_GROUP_AUTO: the clone batches' rule, the image standing in for the ROI), largest images first; every worker takes a chunk at
+ * a time through sc_hip_edit_device_batch (a chunk of one through sc_hip_edit_device).  Host images (device_resident = 0): one
+ * sc_hip_edit per job on the worker's instance.  Returns when every job has completed: SC_OK, or the first failing job's code. */
+SC_API int sc_hip_pool_edit(void *pool, const sc_edit_params *p, sc_edit_job *jobs, int n, int device_resident);
+/* Host-only (needs no GPU): the chunks sc_hip_pool_edit would form for device-resident edits of these image sizes (wh[2i], wh[2i+1]) on
+ * a pool of `streams` workers with group size `group` (SC_POOL_GROUP_AUTO allowed): group_of[i] = the job's chunk.  Returns the number
+ * of chunks, or SC_ERR_BAD_ARG. */
+SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int streams, int *group_of);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -113,6 +113,12 @@ class EditParams(C.Structure):
                 ("kernel_size", C.c_int)]
 
 
+class EditJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("cols", C.c_int), ("rows", C.c_int), ("src_step", C.c_int),
+                ("mask", C.c_void_p), ("mask_step", C.c_int),
+                ("dst", C.c_void_p), ("dst_step", C.c_int), ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -262,6 +268,12 @@ def load():
     L.sc_hip_edit.restype = C.c_int
     L.sc_hip_edit_device.argtypes = [C.c_void_p, C.POINTER(EditParams)] + _IMG + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_bool]
     L.sc_hip_edit_device.restype = C.c_int
+    L.sc_hip_edit_device_batch.argtypes = [C.c_void_p, C.POINTER(EditParams), C.POINTER(EditJob), C.c_int]
+    L.sc_hip_edit_device_batch.restype = C.c_int
+    L.sc_hip_pool_edit.argtypes = [C.c_void_p, C.POINTER(EditParams), C.POINTER(EditJob), C.c_int, C.c_int]
+    L.sc_hip_pool_edit.restype = C.c_int
+    L.sc_hip_plan_edit_groups_pool.argtypes = [i32p, C.c_int, C.c_int, C.c_int, i32p]
+    L.sc_hip_plan_edit_groups_pool.restype = C.c_int
     L.sc_hip_edit_rhs.argtypes = [C.c_void_p, C.POINTER(EditParams)] + _IMG + [C.c_void_p, C.c_int, u8p, f32p, C.c_size_t]
     L.sc_hip_edit_rhs.restype = C.c_int
     L.sc_hip_canny.argtypes = [C.c_void_p] + _IMG + [C.c_float, C.c_float, C.c_int, u8p, u8p, i32p]
@@ -389,6 +401,21 @@ class Instance:
         rc = self.L.sc_hip_edit_device(self.h, C.byref(params), d_src, cols, rows, src_step or 3 * cols, d_mask,
                                        mask_step or cols, d_dst, dst_step or 3 * cols, bool(sync))
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_edit_jobs(n: int):
+        return (EditJob * n)()
+
+    def edit_device_batch(self, params: EditParams, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_edit_device_batch: jobs is an EditJob array (make_edit_jobs) of device images, one op and parameter set for all.
+        Jobs of one image size are solved as one field of 3n channels; per-job codes in jobs[i].rc.  Returns the worst code:
+        SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
+        rc = self.L.sc_hip_edit_device_batch(self.h, C.byref(params), jobs, len(jobs))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
     def edit_rhs(self, params: EditParams, src, mask):
         """(eroded mask H x W, un-folded right-hand side [3][H][W]) of an edit (test hook)."""
@@ -630,6 +657,26 @@ class Pool:
             j.centerX, j.centerY, j.body_restore = int(cx), int(cy), None
         self.run(jobs, device_resident=False)
 
+    def edit(self, params: EditParams, jobs, device_resident: bool):
+        """sc_hip_pool_edit: an EditJob array (Instance.make_edit_jobs), one op and parameter set for all.  Device-resident jobs go
+        in chunks of one image size through sc_hip_edit_device_batch, host images one sc_hip_edit per job."""
+        rc = self.L.sc_hip_pool_edit(self.h, C.byref(params), jobs, len(jobs), 1 if device_resident else 0)
+        if rc not in (SC_OK, SC_ERR_NOT_CONVERGED):
+            raise SeamlessCloneError(rc, "an edit job failed (see jobs[i].rc)")
+
+    def edit_host(self, params: EditParams, items):
+        """items: (src, mask, dst) numpy tuples (H x W x 3, H x W, H x W x 3 uint8; dst may be src); dst is written."""
+        jobs = Instance.make_edit_jobs(len(items))
+        for j, (src, mask, dst) in zip(jobs, items):
+            s, m, d = _img(src), _img(mask), _img(dst)
+            if m[1:3] != s[1:3] or d[1:3] != s[1:3]:
+                raise ValueError("src, mask and dst must have one size")
+            (j.src, j.cols, j.rows, j.src_step) = s
+            j.mask, j.mask_step = m[0], m[3]
+            j.dst, j.dst_step = d[0], d[3]
+        self.edit(params, jobs, device_resident=False)
+        return jobs
+
     def close(self):
         if getattr(self, "h", None):
             self.L.sc_hip_pool_destroy(self.h)
@@ -664,6 +711,18 @@ def plan_groups_pool(sizes, group: int = 0, streams: int = 2, opts: "SolverOpts 
 
 
 SC_POOL_GROUP_AUTO = 0
+
+
+def plan_edit_groups_pool(sizes, group: int = 0, streams: int = 2):
+    """Host-only: the chunks a Pool(streams, group) forms for device-resident edits of images of these sizes [(W, H), ...]:
+    group_of per job (group 0 = SC_POOL_GROUP_AUTO)."""
+    wh = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(-1, 2))
+    n = wh.shape[0]
+    g = np.zeros(n, np.int32)
+    rc = load().sc_hip_plan_edit_groups_pool(wh.ctypes.data_as(i32p), n, int(group), int(streams), g.ctypes.data_as(i32p))
+    if rc < 0:
+        raise SeamlessCloneError(rc, "sc_hip_plan_edit_groups_pool")
+    return g.tolist()
 
 
 def plan_prepare(sizes, opts: "SolverOpts | None" = None) -> int:

@@ -8,7 +8,9 @@
 //   1. sc_hip_selftest_host: the row copier across its helper threads, both eigen-solvers, the part maps;
 //   2. the planner from several threads at once (plan cache hits, misses and evictions), against a single-threaded reference;
 //   3. the pool's hand-out of jobs against stub instances (sc_pool.cpp compiled with its instance calls renamed to the stubs
-//      below): groups formed, every job run exactly once, per-job codes copied back, several batches on one pool.
+//      below): groups formed, every job run exactly once, per-job codes copied back, several batches on one pool;
+//   4. the same for batches of whole-image edits (sc_hip_pool_edit): chunks of one image size, every job exactly once, codes back,
+//      and a chunk whose batch call fails with SC_ERR_HIP (after writing SC_OK into its members) reported as failed, job and pool.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
@@ -46,6 +48,28 @@ int stub_run_device(void *p, const uint8_t *, int, int, int, uint8_t *body, int,
 int stub_run(void *p, const uint8_t *f, int fc, int fr, int fs, uint8_t *body, int bc, int br, int bs, const uint8_t *m, int mc, int mr, int ms, int cx, int cy, int, bool)
 {
     return stub_run_device(p, f, fc, fr, fs, body, bc, br, bs, m, mc, mr, ms, cx, cy, false);
+}
+std::atomic<long> g_edit_mixed{ 0 };      // an edit chunk with more than one image size
+int stub_edit_device(void *p, const sc_edit_params *, const uint8_t *, int, int, int, const uint8_t *, int, uint8_t *dst, int, bool)
+{
+    ((StubInst *)p)->calls++;
+    g_jobs_run++;
+    *(volatile uint8_t *)dst += 1;
+    return SC_OK;
+}
+int stub_edit(void *p, const sc_edit_params *e, const uint8_t *s, int c, int r, int ss, const uint8_t *m, int ms, uint8_t *dst, int ds)
+{
+    return stub_edit_device(p, e, s, c, r, ss, m, ms, dst, ds, false);
+}
+constexpr int FAILING_COLS = 777;          // a chunk of this width: the batch call writes SC_OK into every member, then fails with a HIP error
+int stub_edit_device_batch(void *p, const sc_edit_params *, sc_edit_job *jobs, int n)
+{
+    ((StubInst *)p)->calls++;
+    for (int i = 0; i < n; ++i) {
+        if (jobs[i].cols != jobs[0].cols || jobs[i].rows != jobs[0].rows) g_edit_mixed++;
+        g_jobs_run++; *(volatile uint8_t *)jobs[i].dst += 1; jobs[i].rc = SC_OK;
+    }
+    return jobs[0].cols == FAILING_COLS ? SC_ERR_HIP : SC_OK;
 }
 int stub_run_device_batch(void *p, sc_batch_job *jobs, int n)
 {
@@ -136,6 +160,65 @@ int main()
             }
             sc_hip_pool_destroy(pool);
         }
+    // 4: edit batches through the pool
+    for (int streams : { 1, 3 })
+        for (int group : { 1, 4, SC_POOL_GROUP_AUTO }) {
+            void *pool = sc_hip_pool_create(0, streams);
+            if (!pool) return fail("pool_create (stub instances)");
+            if (sc_hip_pool_set_group(pool, group) != SC_OK) return fail("pool_set_group");
+            sc_edit_params ep;
+            sc_hip_default_edit_params(&ep, SC_EDIT_COLOR_CHANGE);
+            for (int batch = 0; batch < 4; ++batch) {
+                const int n = 1 + 29 * batch;
+                std::vector<uint8_t> dsts(n, 0);
+                std::vector<sc_edit_job> jobs(n);
+                std::vector<int> wh(2 * n), group_of(n);
+                for (int i = 0; i < n; ++i) {
+                    memset(&jobs[i], 0, sizeof(jobs[i]));
+                    const int w = (i % 3 == 0) ? 640 : (i % 7 == 0) ? 1000 + i : 320, h = (i % 3 == 0) ? 360 : 200;
+                    jobs[i].src = jobs[i].mask = &dsts[i]; jobs[i].dst = &dsts[i];
+                    jobs[i].cols = w; jobs[i].rows = h; jobs[i].src_step = jobs[i].dst_step = 3 * w; jobs[i].mask_step = w;
+                    jobs[i].rc = -12345;
+                    wh[2 * i] = w; wh[2 * i + 1] = h;
+                }
+                const int chunks = sc_hip_plan_edit_groups_pool(wh.data(), n, group, streams, group_of.data());
+                if (chunks < 1 || chunks > n) return fail("plan_edit_groups_pool");
+                for (int i = 0; i < n; ++i)
+                    for (int k = 0; k < n; ++k)
+                        if (group_of[i] == group_of[k] && (wh[2 * i] != wh[2 * k] || wh[2 * i + 1] != wh[2 * k + 1])) return fail("an edit chunk mixes sizes");
+                const long before = g_jobs_run.load();
+                for (int device_resident : { 1, 0 }) {
+                    if (sc_hip_pool_edit(pool, &ep, jobs.data(), n, device_resident) != SC_OK) return fail("pool_edit");
+                    for (int i = 0; i < n; ++i) if (jobs[i].rc != SC_OK) return fail("an edit job's code was not copied back");
+                }
+                if (g_jobs_run.load() - before != 2L * n) return fail("edit jobs run != jobs given");
+                for (int i = 0; i < n; ++i) if (dsts[i] != 2) return fail("an edit job was handed out twice or never");
+            }
+            sc_hip_pool_destroy(pool);
+        }
+    if (g_edit_mixed.load()) return fail("the pool handed one edit batch call several image sizes");
+    // 4b: a batch call that fails with a HIP error after its members' codes read SC_OK
+    {
+        void *pool = sc_hip_pool_create(0, 2);
+        if (!pool) return fail("pool_create (stub instances)");
+        if (sc_hip_pool_set_group(pool, 4) != SC_OK) return fail("pool_set_group");
+        sc_edit_params ep;
+        sc_hip_default_edit_params(&ep, SC_EDIT_COLOR_CHANGE);
+        const int n = 11;
+        std::vector<uint8_t> dsts(n, 0);
+        std::vector<sc_edit_job> jobs(n);
+        for (int i = 0; i < n; ++i) {
+            memset(&jobs[i], 0, sizeof(jobs[i]));
+            const int w = (i % 3 == 0) ? FAILING_COLS : 320;
+            jobs[i].src = jobs[i].mask = &dsts[i]; jobs[i].dst = &dsts[i];
+            jobs[i].cols = w; jobs[i].rows = 200; jobs[i].src_step = jobs[i].dst_step = 3 * w; jobs[i].mask_step = w;
+            jobs[i].rc = -12345;
+        }
+        if (sc_hip_pool_edit(pool, &ep, jobs.data(), n, 1) != SC_ERR_HIP) return fail("pool_edit hid a failed batch call");
+        for (int i = 0; i < n; ++i)
+            if (jobs[i].rc != (jobs[i].cols == FAILING_COLS ? SC_ERR_HIP : SC_OK)) return fail("a job of a failed batch call reads as done");
+        sc_hip_pool_destroy(pool);
+    }
     printf("sanitize_main: clean\n");
     return 0;
 }

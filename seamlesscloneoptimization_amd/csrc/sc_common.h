@@ -66,6 +66,17 @@ void launch_canny_hyst(uint8_t *C, int cpitch, int W, int H, unsigned *mailbox, 
 void launch_edit_frame(const uint8_t *src, int sstep, uint8_t *dst, int dstep, int W, int H, hipStream_t s);
 void launch_edit_preprocess(int op, const float k[3], float ab, float nbeta, const uint8_t *src, int sstep, const uint8_t *M, int mpitch,
                             const uint8_t *E, Field U0, Field F, hipStream_t s);
+// ... their group forms (sc_edit_batch.cpp: same-size images as one field of 3n channels): member k's eroded mask and class map are
+// plane k of M / C (planes mplane / cplane bytes apart, pitch mpitch), its fields channels 3k..3k+2; one launch per 16 members (the
+// table goes by value), the hysteresis one launch for all of them with one mailbox
+struct EditJob { const uint8_t *src; int sstep; const uint8_t *mask; int mstep; uint8_t *dst; int dstep; };
+struct EditJobs { enum { MAX = 16 }; EditJob j[MAX]; };
+void launch_edit_erode_group(const EditJob *jobs, int n, int W, int H, uint8_t *M, int mpitch, size_t mplane, hipStream_t s);
+void launch_canny_nms_group(const EditJob *jobs, int n, int W, int H, int lo, int hi, int aperture, uint8_t *C, int cpitch, size_t cplane, hipStream_t s);
+void launch_canny_hyst_group(uint8_t *C, int cpitch, size_t cplane, int n, int W, int H, unsigned *mailbox, unsigned round, hipStream_t s);
+void launch_edit_preprocess_group(int op, const float k[3], float ab, float nbeta, const EditJob *jobs, int n, const uint8_t *M, int mpitch,
+                                  size_t mplane, const uint8_t *E, Field U0, Field F, hipStream_t s);
+void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream_t s);     // members whose dst is not their src
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

@@ -8,6 +8,7 @@
 // illuminationChange.
 #include "sc_common.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 
 namespace sc {
@@ -16,7 +17,7 @@ namespace sc {
 // cv::erode of the whole mask with a 3 x 3 rectangle, three iterations = a 7 x 7 minimum filter.  Pixels outside the image are
 // ignored (morphologyDefaultBorderValue: +inf for erosion), so a mask that is 255 up to the image's edge stays 255 there --
 // unlike k_mask_erode_min7, which reads zeros outside a bounding box.  64 x 16 outputs per workgroup, 70 x 22 bytes in LDS.
-__global__ __launch_bounds__(256) void k_edit_erode(const uint8_t *__restrict__ mask, int mstep, int W, int H, uint8_t *__restrict__ M, int mpitch)
+__device__ __forceinline__ void edit_erode_block(const uint8_t *__restrict__ mask, int mstep, int W, int H, uint8_t *__restrict__ M, int mpitch)
 {
     __shared__ uint8_t in[22][72];
     __shared__ uint8_t hm[22][64];
@@ -44,6 +45,18 @@ __global__ __launch_bounds__(256) void k_edit_erode(const uint8_t *__restrict__ 
     }
 }
 
+__global__ __launch_bounds__(256) void k_edit_erode(const uint8_t *__restrict__ mask, int mstep, int W, int H, uint8_t *__restrict__ M, int mpitch)
+{
+    edit_erode_block(mask, mstep, W, H, M, mpitch);
+}
+
+// a group of same-size images (sc_edit_batch.cpp): blockIdx.z = member, whose eroded mask is plane z of M (planes mplane bytes apart)
+__global__ __launch_bounds__(256) void k_edit_erode_group(EditJobs t, int W, int H, uint8_t *__restrict__ M, int mpitch, size_t mplane)
+{
+    const EditJob &j = t.j[blockIdx.z];
+    edit_erode_block(j.mask, j.mstep, W, H, M + mplane * blockIdx.z, mpitch);
+}
+
 void launch_edit_erode(const uint8_t *mask, int mstep, int W, int H, uint8_t *M, int mpitch, hipStream_t s)
 {
     hipLaunchKernelGGL(k_edit_erode, dim3((W + 63) / 64, (H + 15) / 16), dim3(256), 0, s, mask, mstep, W, H, M, mpitch);
@@ -65,8 +78,8 @@ template <> struct SobelK<3> { static constexpr int s[7] = { 1, 6, 15, 20, 15, 6
 __device__ __forceinline__ int sat16(int v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
 
 template <int R>
-__global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ src, int sstep, int W, int H, int lo, int hi,
-                                                   uint8_t *__restrict__ C, int cpitch)
+__device__ __forceinline__ void canny_nms_block(const uint8_t *__restrict__ src, int sstep, int W, int H, int lo, int hi,
+                                                uint8_t *__restrict__ C, int cpitch)
 {
     constexpr int IW = CN_TW + 2 + 2 * R, IH = CN_TH + 2 + 2 * R;      // staged source: tile + ring + Sobel halo
     constexpr int RW = CN_TW + 2, RH = CN_TH + 2;                       // tile + ring
@@ -142,6 +155,21 @@ __global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ s
     }
 }
 
+template <int R>
+__global__ __launch_bounds__(256) void k_canny_nms(const uint8_t *__restrict__ src, int sstep, int W, int H, int lo, int hi,
+                                                   uint8_t *__restrict__ C, int cpitch)
+{
+    canny_nms_block<R>(src, sstep, W, H, lo, hi, C, cpitch);
+}
+
+// a group: member blockIdx.z's source into plane z of the class maps (all members have one W x H, so one grid serves them all)
+template <int R>
+__global__ __launch_bounds__(256) void k_canny_nms_group(EditJobs t, int W, int H, int lo, int hi, uint8_t *__restrict__ C, int cpitch, size_t cplane)
+{
+    const EditJob &j = t.j[blockIdx.z];
+    canny_nms_block<R>(j.src, j.sstep, W, H, lo, hi, C + cplane * blockIdx.z, cpitch);
+}
+
 void launch_canny_nms(const uint8_t *src, int sstep, int W, int H, int lo, int hi, int aperture, uint8_t *C, int cpitch, hipStream_t s)
 {
     const dim3 grid((W + CN_TW - 1) / CN_TW, (H + CN_TH - 1) / CN_TH);
@@ -160,7 +188,7 @@ void launch_canny_nms(const uint8_t *src, int sstep, int W, int H, int lo, int h
 // its fixed point.  No workgroup waits for another.
 constexpr int HY_TW = 64, HY_TH = 16;
 
-__global__ __launch_bounds__(256) void k_canny_hyst(uint8_t *__restrict__ C, int cpitch, int W, int H, unsigned *mailbox, unsigned round)
+__device__ __forceinline__ void canny_hyst_block(uint8_t *__restrict__ C, int cpitch, int W, int H, unsigned *mailbox, unsigned round)
 {
     __shared__ uint8_t t[HY_TH + 2][HY_TW + 2];
     const int tx0 = blockIdx.x * HY_TW, ty0 = blockIdx.y * HY_TH;
@@ -195,6 +223,18 @@ __global__ __launch_bounds__(256) void k_canny_hyst(uint8_t *__restrict__ C, int
         if (lx == 0 || lx == HY_TW - 1 || ly == 0 || ly == HY_TH - 1) edge = 1;
     }
     if (__syncthreads_or(edge) && threadIdx.x == 0) __hip_atomic_store(mailbox, round, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ __launch_bounds__(256) void k_canny_hyst(uint8_t *__restrict__ C, int cpitch, int W, int H, unsigned *mailbox, unsigned round)
+{
+    canny_hyst_block(C, cpitch, W, H, mailbox, round);
+}
+
+// every member's map in one launch (blockIdx.z = plane), ONE mailbox for the group: a launch that stored nothing left every member's
+// map final (the argument above holds per plane; planes never read each other)
+__global__ __launch_bounds__(256) void k_canny_hyst_group(uint8_t *__restrict__ C, int cpitch, size_t cplane, int W, int H, unsigned *mailbox, unsigned round)
+{
+    canny_hyst_block(C + cplane * blockIdx.z, cpitch, W, H, mailbox, round);
 }
 
 void launch_canny_hyst(uint8_t *C, int cpitch, int W, int H, unsigned *mailbox, unsigned round, hipStream_t s)
@@ -243,8 +283,8 @@ __device__ __forceinline__ float2 edit_field(const uint8_t *__restrict__ src, in
 }
 
 template <int OP>
-__global__ __launch_bounds__(256) void k_edit_preprocess(const uint8_t *__restrict__ src, int sstep, const uint8_t *__restrict__ M, int mpitch,
-                                                         const uint8_t *__restrict__ E, Field U0, Field F, EditArgs a)
+__device__ __forceinline__ void edit_preprocess_block(const uint8_t *__restrict__ src, int sstep, const uint8_t *__restrict__ M, int mpitch,
+                                                      const uint8_t *__restrict__ E, const Field &U0, const Field &F, int c0, const EditArgs &a)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int W = U0.W, H = U0.H;
@@ -253,7 +293,7 @@ __global__ __launch_bounds__(256) void k_edit_preprocess(const uint8_t *__restri
     const bool in = x >= 1 && x <= W - 2 && y >= 1 && y <= H - 2;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        U0.at(c)[o] = x < W ? (float)src[(size_t)y * sstep + 3 * (size_t)x + c] : 0.f;
+        U0.at(c0 + c)[o] = x < W ? (float)src[(size_t)y * sstep + 3 * (size_t)x + c] : 0.f;
         float lap = 0.f;
         if (in) {
             const float2 g = edit_field<OP>(src, sstep, M, mpitch, E, x, y, c, a);
@@ -261,8 +301,25 @@ __global__ __launch_bounds__(256) void k_edit_preprocess(const uint8_t *__restri
             const float2 gu = edit_field<OP>(src, sstep, M, mpitch, E, x, y - 1, c, a);
             lap = (g.x - gl.x) + (g.y - gu.y);
         }
-        F.at(c)[o] = lap;
+        F.at(c0 + c)[o] = lap;
     }
+}
+
+template <int OP>
+__global__ __launch_bounds__(256) void k_edit_preprocess(const uint8_t *__restrict__ src, int sstep, const uint8_t *__restrict__ M, int mpitch,
+                                                         const uint8_t *__restrict__ E, Field U0, Field F, EditArgs a)
+{
+    edit_preprocess_block<OP>(src, sstep, M, mpitch, E, U0, F, 0, a);
+}
+
+// a group: member blockIdx.z writes channels 3z..3z+2 of U0 / F from its own source, eroded mask (plane z of M) and class map
+// (plane z of E) -- the single image's arithmetic, so the same bits
+template <int OP>
+__global__ __launch_bounds__(256) void k_edit_preprocess_group(EditJobs t, const uint8_t *__restrict__ M, int mpitch, size_t mplane,
+                                                               const uint8_t *__restrict__ E, Field U0, Field F, EditArgs a)
+{
+    const EditJob &j = t.j[blockIdx.z];
+    edit_preprocess_block<OP>(j.src, j.sstep, M + mplane * blockIdx.z, mpitch, E ? E + mplane * blockIdx.z : nullptr, U0, F, 3 * blockIdx.z, a);
 }
 
 void launch_edit_preprocess(int op, const float k[3], float ab, float nbeta, const uint8_t *src, int sstep, const uint8_t *M, int mpitch,
@@ -278,7 +335,7 @@ void launch_edit_preprocess(int op, const float k[3], float ab, float nbeta, con
 
 // ---------------------------------------------------------------- the frame of src into dst
 // The post-process writes the interior; dst's one-pixel frame is src's (the Dirichlet data).  One lane per frame pixel.
-__global__ __launch_bounds__(256) void k_edit_frame(const uint8_t *__restrict__ src, int sstep, uint8_t *__restrict__ dst, int dstep, int W, int H)
+__device__ __forceinline__ void edit_frame_block(const uint8_t *__restrict__ src, int sstep, uint8_t *__restrict__ dst, int dstep, int W, int H)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int x, y;
@@ -292,10 +349,82 @@ __global__ __launch_bounds__(256) void k_edit_frame(const uint8_t *__restrict__ 
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
+__global__ __launch_bounds__(256) void k_edit_frame(const uint8_t *__restrict__ src, int sstep, uint8_t *__restrict__ dst, int dstep, int W, int H)
+{
+    edit_frame_block(src, sstep, dst, dstep, W, H);
+}
+
+// a group: member blockIdx.z's frame (members whose dst is their src have nothing to copy: the launcher leaves them out)
+__global__ __launch_bounds__(256) void k_edit_frame_group(EditJobs t, int W, int H)
+{
+    const EditJob &j = t.j[blockIdx.z];
+    edit_frame_block(j.src, j.sstep, j.dst, j.dstep, W, H);
+}
+
 void launch_edit_frame(const uint8_t *src, int sstep, uint8_t *dst, int dstep, int W, int H, hipStream_t s)
 {
     const int n = 2 * W + 2 * (H - 2);
     hipLaunchKernelGGL(k_edit_frame, dim3((n + 255) / 256), dim3(256), 0, s, src, sstep, dst, dstep, W, H);
+}
+
+// ---------------------------------------------------------------- launchers of the group forms (one launch per 16 members)
+template <typename F>
+static void for_chunks(const EditJob *jobs, int n, F f)
+{
+    for (int i0 = 0; i0 < n; i0 += EditJobs::MAX) {
+        EditJobs t{};
+        const int cnt = std::min(n - i0, (int)EditJobs::MAX);
+        for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
+        f(t, i0, cnt);
+    }
+}
+
+void launch_edit_erode_group(const EditJob *jobs, int n, int W, int H, uint8_t *M, int mpitch, size_t mplane, hipStream_t s)
+{
+    for_chunks(jobs, n, [&](const EditJobs &t, int i0, int cnt) {
+        hipLaunchKernelGGL(k_edit_erode_group, dim3((W + 63) / 64, (H + 15) / 16, cnt), dim3(256), 0, s, t, W, H, M + mplane * i0, mpitch, mplane);
+    });
+}
+
+void launch_canny_nms_group(const EditJob *jobs, int n, int W, int H, int lo, int hi, int aperture, uint8_t *C, int cpitch, size_t cplane, hipStream_t s)
+{
+    for_chunks(jobs, n, [&](const EditJobs &t, int i0, int cnt) {
+        const dim3 grid((W + CN_TW - 1) / CN_TW, (H + CN_TH - 1) / CN_TH, cnt);
+        uint8_t *c = C + cplane * i0;
+        if (aperture == 7) hipLaunchKernelGGL(k_canny_nms_group<3>, grid, dim3(256), 0, s, t, W, H, lo, hi, c, cpitch, cplane);
+        else if (aperture == 5) hipLaunchKernelGGL(k_canny_nms_group<2>, grid, dim3(256), 0, s, t, W, H, lo, hi, c, cpitch, cplane);
+        else hipLaunchKernelGGL(k_canny_nms_group<1>, grid, dim3(256), 0, s, t, W, H, lo, hi, c, cpitch, cplane);
+    });
+}
+
+void launch_canny_hyst_group(uint8_t *C, int cpitch, size_t cplane, int n, int W, int H, unsigned *mailbox, unsigned round, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_canny_hyst_group, dim3((W + HY_TW - 1) / HY_TW, (H + HY_TH - 1) / HY_TH, n), dim3(256), 0, s, C, cpitch, cplane, W, H, mailbox, round);
+}
+
+void launch_edit_preprocess_group(int op, const float k[3], float ab, float nbeta, const EditJob *jobs, int n, const uint8_t *M, int mpitch,
+                                  size_t mplane, const uint8_t *E, Field U0, Field F, hipStream_t s)
+{
+    EditArgs a;
+    a.op = op; a.k[0] = k[0]; a.k[1] = k[1]; a.k[2] = k[2]; a.ab = ab; a.nbeta = nbeta;
+    for_chunks(jobs, n, [&](const EditJobs &t, int i0, int cnt) {
+        const dim3 grid(((U0.W + 3) / 4 * 4 + 63) / 64, (U0.H + 3) / 4, cnt);
+        Field u = U0, f = F;      // this launch's first member owns channel 3 i0
+        u.p = U0.p + (size_t)3 * i0 * U0.plane;
+        f.p = F.p + (size_t)3 * i0 * F.plane;
+        const uint8_t *m = M + mplane * i0, *e = E ? E + mplane * i0 : nullptr;
+        if (op == 1) hipLaunchKernelGGL(k_edit_preprocess_group<1>, grid, dim3(256), 0, s, t, m, mpitch, mplane, e, u, f, a);
+        else if (op == 2) hipLaunchKernelGGL(k_edit_preprocess_group<2>, grid, dim3(256), 0, s, t, m, mpitch, mplane, e, u, f, a);
+        else hipLaunchKernelGGL(k_edit_preprocess_group<3>, grid, dim3(256), 0, s, t, m, mpitch, mplane, e, u, f, a);
+    });
+}
+
+void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream_t s)
+{
+    const int px = 2 * W + 2 * (H - 2);
+    for_chunks(jobs, n, [&](const EditJobs &t, int, int cnt) {
+        hipLaunchKernelGGL(k_edit_frame_group, dim3((px + 255) / 256, 1, cnt), dim3(256), 0, s, t, W, H);
+    });
 }
 
 } // namespace sc

@@ -45,30 +45,24 @@ static void canny_thresholds(float low, float high, int &lo, int &hi)
     hi = (int)std::min(std::max(h, -1.0), 1048576.0);
 }
 
-// Canny of the whole image into I->d_edge (pitch I->mpitch): the class map, then hysteresis launches until one of them changed
-// no tile's edge pixel (k_canny_hyst).  The host reads the pinned mailbox after every HYST_BATCH launches: one wait per batch
-// instead of one per launch; the launches after the map is final change nothing.  C_out: the class map before hysteresis
-// (test hook; synchronises).
-int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float low, float high, int aperture, uint8_t *C_out)
+// The hysteresis launches until one of them changed no tile's edge pixel (k_canny_hyst): `launch(round)` enqueues one launch over every
+// plane of the map.  The host reads the pinned mailbox after every HYST_BATCH launches: one wait per batch instead of one per launch;
+// the launches after the map is final change nothing.
+template <typename Launch>
+static int hysteresis(Instance *I, long long pixels, Launch launch)
 {
-    int lo, hi, rc;
-    canny_thresholds(low, high, lo, hi);
-    if ((rc = ensure(I, I->d_edge, (size_t)I->mpitch * H, false))) return rc;
+    int rc;
     if ((rc = ensure_pinned(I, I->h_hyst, 64))) return rc;
-    uint8_t *E = (uint8_t *)I->d_edge.p;
-    launch_canny_nms(d_src, ss, W, H, lo, hi, aperture, E, I->mpitch, I->stream);
-    SC_HIP(I, hipGetLastError());
-    if (C_out && (rc = download_rows(I, I->h_out, C_out, W, E, I->mpitch, W, H))) return rc;
     constexpr int HYST_BATCH = 4;
     volatile unsigned *box = (volatile unsigned *)I->h_hyst.p;
     // Each launch that reports an edge change has turned at least one weak pixel strong, so the loop ends; the cap is that bound.
-    const long long max_launches = (long long)W * H + HYST_BATCH + 1;
+    const long long max_launches = pixels + HYST_BATCH + 1;
     unsigned round = 0;
     I->hyst_launches = 0; I->hyst_reads = 0;
     for (;;) {
         SC_HIP(I, hipStreamSynchronize(I->stream));      // nothing of this instance reads or writes the mailbox while it is reset
         *box = 0u;
-        for (int k = 0; k < HYST_BATCH; ++k) launch_canny_hyst(E, I->mpitch, W, H, (unsigned *)I->h_hyst.p, ++round, I->stream);
+        for (int k = 0; k < HYST_BATCH; ++k) launch((unsigned *)I->h_hyst.p, ++round);
         SC_HIP(I, hipGetLastError());
         I->hyst_launches += HYST_BATCH;
         SC_HIP(I, hipStreamSynchronize(I->stream));
@@ -77,6 +71,35 @@ int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float l
         if (I->hyst_launches > max_launches) { I->err = "hysteresis did not settle"; return SC_ERR_HIP; }
     }
     return SC_OK;
+}
+
+// Canny of the whole image into I->d_edge (pitch I->mpitch): the class map, then the hysteresis.  C_out: the class map before
+// hysteresis (test hook; synchronises).
+int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float low, float high, int aperture, uint8_t *C_out)
+{
+    int lo, hi, rc;
+    canny_thresholds(low, high, lo, hi);
+    if ((rc = ensure(I, I->d_edge, (size_t)I->mpitch * H, false))) return rc;
+    uint8_t *E = (uint8_t *)I->d_edge.p;
+    launch_canny_nms(d_src, ss, W, H, lo, hi, aperture, E, I->mpitch, I->stream);
+    SC_HIP(I, hipGetLastError());
+    if (C_out && (rc = download_rows(I, I->h_out, C_out, W, E, I->mpitch, W, H))) return rc;
+    return hysteresis(I, (long long)W * H, [&](unsigned *box, unsigned round) { launch_canny_hyst(E, I->mpitch, W, H, box, round, I->stream); });
+}
+
+// The same for a group of n same-size images: member k's class map is plane k of I->d_edge (planes mplane bytes apart).  The
+// hysteresis goes out as one launch for all members with ONE mailbox, so the host waits once per batch of launches for the group, and
+// stops after a batch whose last launch changed no member's tile edge.
+int canny_stage_group(Instance *I, const EditJob *jobs, int n, int W, int H, size_t mplane, float low, float high, int aperture)
+{
+    int lo, hi, rc;
+    canny_thresholds(low, high, lo, hi);
+    if ((rc = ensure(I, I->d_edge, mplane * n, false))) return rc;
+    uint8_t *E = (uint8_t *)I->d_edge.p;
+    launch_canny_nms_group(jobs, n, W, H, lo, hi, aperture, E, I->mpitch, mplane, I->stream);
+    SC_HIP(I, hipGetLastError());
+    return hysteresis(I, (long long)W * H * n,
+                      [&](unsigned *box, unsigned round) { launch_canny_hyst_group(E, I->mpitch, mplane, n, W, H, box, round, I->stream); });
 }
 
 // Erode (and for texture flattening Canny) + the edit's pre-process on device images: leaves d_M, d_edge and the fields.
@@ -98,6 +121,14 @@ void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src,
     const float ab = powf(p->alpha, p->beta);
     launch_edit_preprocess(p->op, k, ab, -p->beta, d_src, ss, (const uint8_t *)I->d_M.p, I->mpitch,
                            p->op == SC_EDIT_TEXTURE_FLATTENING ? (const uint8_t *)I->d_edge.p : nullptr, I->U0, I->F, I->stream);
+}
+
+void edit_preprocess_group(Instance *I, const sc_edit_params *p, const EditJob *jobs, int n, size_t mplane)
+{
+    const float k[3] = { p->blue_mul, p->green_mul, p->red_mul };
+    const float ab = powf(p->alpha, p->beta);
+    launch_edit_preprocess_group(p->op, k, ab, -p->beta, jobs, n, (const uint8_t *)I->d_M.p, I->mpitch, mplane,
+                                 p->op == SC_EDIT_TEXTURE_FLATTENING ? (const uint8_t *)I->d_edge.p : nullptr, I->U0, I->F, I->stream);
 }
 
 } // namespace sc

@@ -1,0 +1,168 @@
+// sc_edit_batch.cpp -- n whole-image edits on one instance (sc_hip_edit_device_batch): jobs partitioned by image size, every size that
+// two or more jobs share solved as ONE field of 3n channels, the rest alone through sc_hip_edit_device.
+//
+// A group: erode (one launch per 16 members) -> [Canny: class maps, hysteresis launches for all members with one mailbox] -> edit
+// pre-process (member k: channels 3k..3k+2, the single image's arithmetic) -> the instance's solve of the 3n channels -> the clone
+// group's post-process (whole-image ImageJobs: origin 0, no rectangle guard; or the armed spec_post.group splice) -> the frames of the
+// members whose dst is another image.  Kernels: sc_edit.hip.
+#include "sc_instance.h"
+#include <algorithm>
+#include <map>
+#include <utility>
+#include <vector>
+
+using namespace sc;
+
+namespace {
+
+// leaves the instance's edit state as a single call expects it on every way out (the next clone reads neither)
+struct EditScope {
+    Instance *I;
+    ~EditScope()
+    {
+        I->edit_call = false;
+        I->spec_post.armed = false;
+        I->spec_post.group.clear();
+        I->force_float_field = false;
+    }
+};
+
+int run_edit_group(Instance *I, const sc_edit_params *p, sc_edit_job *jobs, const std::vector<int> &idx)
+{
+    const int n = (int)idx.size();
+    const int W = jobs[idx[0]].cols, H = jobs[idx[0]].rows;
+    int rc;
+    EditScope scope{ I };
+    Geo g{ 0, 0, W, H, 0, 0 };
+    fill_info_geo(I, g);
+    I->hyst_launches = I->hyst_reads = 0;
+    I->mpitch = round_up(W, 64);
+    const size_t mplane = (size_t)I->mpitch * H;
+    if ((rc = ensure(I, I->d_M, mplane * n, false))) return rc;
+    if ((rc = setup_fields(I, W, H, 3 * n))) return rc;
+    std::vector<EditJob> ej(n), frames;
+    std::vector<ImageJob> ij(n);
+    for (int k = 0; k < n; ++k) {
+        const sc_edit_job &j = jobs[idx[k]];
+        ej[k] = EditJob{ j.src, j.src_step, j.mask, j.mask_step, j.dst, j.dst_step };
+        if (j.dst != j.src) frames.push_back(ej[k]);
+        ij[k] = ImageJob{};
+        ij[k].face_org = j.src; ij[k].fstep = j.src_step;
+        ij[k].body_org = j.dst; ij[k].bstep = j.dst_step;
+        ij[k].M = (const uint8_t *)I->d_M.p + mplane * k;
+    }
+    launch_edit_erode_group(ej.data(), n, W, H, (uint8_t *)I->d_M.p, I->mpitch, mplane, I->stream);
+    SC_HIP(I, hipGetLastError());
+    if (p->op == SC_EDIT_TEXTURE_FLATTENING &&
+        (rc = canny_stage_group(I, ej.data(), n, W, H, mplane, p->low_threshold, p->high_threshold, p->kernel_size))) return rc;
+    I->guard = RectGuard();
+    I->edit_call = true;          // a float right-hand side (mg_reads_half_rhs)
+    int solve_rc = SC_OK;
+    for (;;) {
+        I->result_in_U1 = false;
+        I->f_half = mg_reads_half_rhs(I);
+        I->u_half = false;
+        edit_preprocess_group(I, p, ej.data(), n, mplane);
+        SC_HIP(I, hipGetLastError());
+        I->info.sweep_launches = 0;
+        I->spec_post.group = ij;
+        I->spec_post.ev_solved = nullptr;
+        I->spec_post.armed = true; I->spec_post.done = false;     // the solver enqueues the splices behind the cycle it expects to accept
+        solve_rc = solve(I);
+        I->spec_post.armed = false;
+        I->force_float_field = false;
+        if (solve_rc != SC_RETRY_FLOAT_FIELD) break;
+        I->force_float_field = true;       // a member's 16-bit field saturated: no member was written, the group again on float fields
+        I->info.field_retry = 1;
+    }
+    const bool spliced = I->spec_post.done;
+    I->spec_post.group.clear();
+    if (solve_rc != SC_OK && solve_rc != SC_ERR_NOT_CONVERGED) return solve_rc;
+    if (!spliced) {
+        LmNodes lm;
+        if ((rc = output_nodes(I, lm))) return rc;
+        launch_postprocess_group(result(I), ij.data(), n, I->stream, lm);
+    }
+    if (!frames.empty()) launch_edit_frame_group(frames.data(), (int)frames.size(), W, H, I->stream);
+    SC_HIP(I, hipGetLastError());
+    for (int k = 0; k < n; ++k) jobs[idx[k]].rc = solve_rc;
+    I->info.group_members = n;
+    return solve_rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int sc_hip_edit_device_batch(void *inst, const sc_edit_params *p, sc_edit_job *jobs, int n)
+{
+    if (!jobs || n <= 0) return SC_ERR_BAD_ARG;
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    auto worse = [](int worst, int rc) { return (rc != SC_OK && (worst == SC_OK || worst == SC_ERR_NOT_CONVERGED)) ? rc : worst; };
+    auto alone = [&](int i) -> int {
+        sc_edit_job &j = jobs[i];
+        j.rc = sc_hip_edit_device(inst, p, j.src, j.cols, j.rows, j.src_step, j.mask, j.mask_step, j.dst, j.dst_step, false);
+        return j.rc;
+    };
+    // jobs that do not validate report their own code and are skipped; the others are partitioned by image size (first-come order).
+    // A job that validated reads SC_ERR_HIP until its group or its single run has given it a code of its own: a call that stops at a
+    // HIP error leaves the jobs it did not get to marked as failed, never as done.
+    int worst = SC_OK;
+    std::vector<std::vector<int>> parts;
+    std::map<std::pair<int, int>, size_t> part_of;
+    std::vector<int> valid;
+    for (int i = 0; i < n; ++i) {
+        sc_edit_job &j = jobs[i];
+        const int vrc = edit_validate(I, p, j.src, j.cols, j.rows, j.src_step, j.mask, j.mask_step, j.dst, j.dst_step);
+        if (vrc != SC_OK) {
+            j.rc = vrc;
+            worst = worse(worst, vrc);
+            continue;
+        }
+        j.rc = SC_ERR_HIP;
+        valid.push_back(i);
+        auto it = part_of.emplace(std::make_pair(j.cols, j.rows), parts.size());
+        if (it.second) parts.emplace_back();
+        parts[it.first->second].push_back(i);
+    }
+    // After a HIP error nothing more can be trusted on this stream, the work already enqueued for other jobs included: every job that
+    // validated reads SC_ERR_HIP, and the call returns.
+    auto hip_failed = [&]() {
+        for (int i : valid) jobs[i].rc = SC_ERR_HIP;
+        return SC_ERR_HIP;
+    };
+    const std::string bad_job_err = I->err;
+    I->stage_marks = false;
+    sc_run_info keep{};
+    int keep_hyst[2] = { 0, 0 };
+    bool have_group = false;
+    std::vector<int> singles;
+    for (const auto &q : parts) {
+        if (q.size() < 2) { singles.push_back(q[0]); continue; }
+        rc = run_edit_group(I, p, jobs, q);
+        if (rc == SC_ERR_HIP) return hip_failed();
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) {                   // the group could not run as one: its members alone
+            for (int i : q) singles.push_back(i);
+            continue;
+        }
+        worst = worse(worst, rc);
+        keep = I->info; keep_hyst[0] = I->hyst_launches; keep_hyst[1] = I->hyst_reads;
+        have_group = true;
+    }
+    std::sort(singles.begin(), singles.end());
+    for (int i : singles)
+        if ((rc = alone(i)) == SC_ERR_HIP) return hip_failed();
+        else worst = worse(worst, rc);
+    if (have_group) {                              // the statistics of the (last) group, not of a straggler
+        I->info = keep;
+        I->hyst_launches = keep_hyst[0]; I->hyst_reads = keep_hyst[1];
+    }
+    I->info.ms_h2d = I->info.ms_mask = I->info.ms_pre = I->info.ms_solve = I->info.ms_post = I->info.ms_d2h = 0.f;
+    I->info.ms_device_total = I->info.ms_call = 0.f;
+    if (I->err.empty() && worst != SC_OK) I->err = bad_job_err;
+    return worst;
+}
+
+} // extern "C"

@@ -279,6 +279,9 @@ int edit_validate(Instance *I, const sc_edit_params *p, const void *src, int col
 int canny_stage(Instance *I, const uint8_t *d_src, int W, int H, int ss, float low, float high, int aperture, uint8_t *C_out);
 int edit_stage(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int W, int H, int ss, const uint8_t *d_mask, int ms);
 void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src, int ss);     // into I->U0, I->F (setup_fields first)
+// ... the same for a group of n same-size images (sc_edit_batch.cpp): member k's eroded mask / class map in plane k of d_M / d_edge
+int canny_stage_group(Instance *I, const EditJob *jobs, int n, int W, int H, size_t mplane, float low, float high, int aperture);
+void edit_preprocess_group(Instance *I, const sc_edit_params *p, const EditJob *jobs, int n, size_t mplane);
 // sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
 void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
 int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);

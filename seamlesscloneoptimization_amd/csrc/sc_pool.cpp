@@ -1,5 +1,5 @@
 // sc_pool.cpp -- native batch driver: K library instances (= K HIP streams) on one GPU, each driven
-// by its own host thread, pulling independent clone jobs from a shared counter.
+// by its own host thread, pulling independent clone jobs -- or whole-image edits (sc_hip_pool_edit) -- from a shared counter.
 //
 // The reference has no batch or multi-stream mode (one instance, one stream, seamlessClone_imp.cu:
 // 239-263).  Clones are independent and a single clone leaves the GPU idle in its latency-bound
@@ -25,8 +25,12 @@ struct Pool {
     std::vector<std::thread> workers;
     std::mutex mu;
     std::condition_variable cv_work, cv_done;
-    // current batch
+    // current batch: clones (sc_hip_pool_run) or whole-image edits (sc_hip_pool_edit: ejobs, eparams, esorted in place of jobs, sorted)
+    enum Kind { CLONE, EDIT } kind = CLONE;
     sc_batch_job *jobs = nullptr;
+    sc_edit_job *ejobs = nullptr;
+    sc_edit_params eparams{};
+    std::vector<sc_edit_job> esorted;
     int njobs = 0, device_resident = 0;
     int group = 1;                 // device-resident jobs a worker takes at a time (sc_hip_run_device_batch)
     // group > 1: the batch's jobs gathered into groups that can share launches (`sorted`: a copy in group order, `origin[k]` = its index
@@ -55,6 +59,31 @@ void run_job(void *inst, sc_batch_job &j, int device_resident)
     }
 }
 
+void run_edit(void *inst, const sc_edit_params *p, sc_edit_job &j, int device_resident)
+{
+    if (device_resident) j.rc = sc_hip_edit_device(inst, p, j.src, j.cols, j.rows, j.src_step, j.mask, j.mask_step, j.dst, j.dst_step, false);
+    else j.rc = sc_hip_edit(inst, p, j.src, j.cols, j.rows, j.src_step, j.mask, j.mask_step, j.dst, j.dst_step);
+}
+
+// a chunk of same-size edits through one sc_hip_edit_device_batch (a chunk of one alone); codes copied back to the caller's jobs
+void run_edit_chunk(Pool *P, void *inst, int first, int cnt)
+{
+    sc_edit_job *js = P->esorted.data() + first;
+    if (cnt > 1) {
+        constexpr int unset = -2147483647;
+        for (int q = 0; q < cnt; ++q) js[q].rc = unset;
+        const int rc = sc_hip_edit_device_batch(inst, &P->eparams, js, cnt);
+        for (int q = 0; q < cnt; ++q) {
+            if (js[q].rc == unset) js[q].rc = (rc != SC_OK) ? rc : SC_ERR_HIP;      // the call failed before it got to this member
+            // a HIP error ends the whole chunk: nothing the call enqueued on that stream is trusted, whatever a member's code says
+            if (rc == SC_ERR_HIP && (js[q].rc == SC_OK || js[q].rc == SC_ERR_NOT_CONVERGED)) js[q].rc = SC_ERR_HIP;
+        }
+    } else {
+        run_edit(inst, &P->eparams, js[0], 1);
+    }
+    for (int q = 0; q < cnt; ++q) P->ejobs[P->origin[first + q]].rc = js[q].rc;
+}
+
 void worker(Pool *P, int k)
 {
     int seen = 0;
@@ -68,7 +97,15 @@ void worker(Pool *P, int k)
         const bool chunked = !P->chunks.empty();
         for (;;) {
             const int i = P->next.fetch_add(1);
-            if (chunked) {
+            if (P->kind == Pool::EDIT) {
+                if (chunked) {
+                    if (i >= (int)P->chunks.size()) break;
+                    run_edit_chunk(P, P->inst[k], P->chunks[i].first, P->chunks[i].second);
+                } else {
+                    if (i >= P->njobs) break;
+                    run_edit(P->inst[k], &P->eparams, P->ejobs[i], P->device_resident);
+                }
+            } else if (chunked) {
                 if (i >= (int)P->chunks.size()) break;
                 const int first = P->chunks[i].first, cnt = P->chunks[i].second;
                 sc_batch_job *js = P->sorted.data() + first;
@@ -100,6 +137,44 @@ Pool *get_pool(void *p)
 {
     Pool *P = (Pool *)p;
     return (P && P->magic == 0x5C10E002u) ? P : nullptr;
+}
+
+// The chunks of a device-resident edit batch (sc_hip_pool_edit, sc_hip_plan_edit_groups_pool): the jobs bucketed by image size
+// (first-come order inside a bucket), buckets largest image first, each cut into chunks of the pool's group size -- pool_group_caps with
+// the image standing in for the ROI: `cap`, or up to cap_max while the chunk stays within the pixel budget.  A bucket is cut into
+// chunks of equal size (17 jobs at a cap of 16: 9 + 8, not 16 + 1 -- a straggler of one would pay a whole solve of its own).  order[k]:
+// the job at position k; chunks: (first position, jobs).
+void edit_chunks(const int *wh, int n, int group, int streams, std::vector<int> &order, std::vector<std::pair<int, int>> &chunks)
+{
+    int cap, cap_max;
+    long budget;
+    pool_group_caps(group, n, streams, cap, cap_max, budget);
+    std::vector<std::vector<int>> buckets;
+    std::vector<std::pair<int, int>> key;
+    for (int i = 0; i < n; ++i) {
+        size_t b = 0;
+        while (b < key.size() && (key[b].first != wh[2 * i] || key[b].second != wh[2 * i + 1])) ++b;
+        if (b == key.size()) { key.emplace_back(wh[2 * i], wh[2 * i + 1]); buckets.emplace_back(); }
+        buckets[b].push_back(i);
+    }
+    std::vector<size_t> by_area(buckets.size());
+    for (size_t b = 0; b < buckets.size(); ++b) by_area[b] = b;
+    auto area = [&](size_t b) { return (long)std::max(1, key[b].first) * std::max(1, key[b].second); };
+    std::stable_sort(by_area.begin(), by_area.end(), [&](size_t x, size_t y) { return area(x) > area(y); });
+    order.clear();
+    chunks.clear();
+    for (size_t b : by_area) {
+        const int cnt = (int)buckets[b].size();
+        int per = cap;
+        if (cap_max > cap && budget > 0) per = (int)std::max<long>(cap, std::min<long>(cap_max, budget / area(b)));
+        const int pieces = (cnt + per - 1) / per;
+        for (int c = 0, at = 0; c < pieces; ++c) {
+            const int m = cnt / pieces + (c < cnt % pieces ? 1 : 0);
+            chunks.emplace_back((int)order.size(), m);
+            for (int q = 0; q < m; ++q) order.push_back(buckets[b][at + q]);
+            at += m;
+        }
+    }
 }
 
 } // namespace
@@ -199,6 +274,7 @@ int sc_hip_pool_run(void *p, sc_batch_job *jobs, int n, int device_resident)
     if (n == 0) return SC_OK;
     {
         std::lock_guard<std::mutex> lk(P->mu);
+        P->kind = Pool::CLONE;
         P->jobs = jobs; P->njobs = n; P->device_resident = device_resident;
         P->chunks.clear();
         if (device_resident && P->group != 1) {
@@ -268,6 +344,53 @@ int sc_hip_pool_run(void *p, sc_batch_job *jobs, int n, int device_resident)
     for (int i = 0; i < n; ++i)
         if (jobs[i].rc != SC_OK && jobs[i].rc != SC_ERR_NOT_CONVERGED) return jobs[i].rc;
     return SC_OK;
+}
+
+int sc_hip_pool_edit(void *pool, const sc_edit_params *p, sc_edit_job *jobs, int n, int device_resident)
+{
+    Pool *P = get_pool(pool);
+    if (!P || (n > 0 && !jobs) || n < 0) return SC_ERR_BAD_ARG;
+    if (n == 0) return SC_OK;
+    if (!p) {
+        for (int i = 0; i < n; ++i) jobs[i].rc = SC_ERR_BAD_ARG;
+        return SC_ERR_BAD_ARG;
+    }
+    {
+        std::lock_guard<std::mutex> lk(P->mu);
+        P->kind = Pool::EDIT;
+        P->ejobs = jobs; P->njobs = n; P->device_resident = device_resident;
+        P->eparams = *p;
+        P->chunks.clear();
+        if (device_resident) {
+            std::vector<int> wh(2 * (size_t)n);
+            for (int i = 0; i < n; ++i) { wh[2 * i] = jobs[i].cols; wh[2 * i + 1] = jobs[i].rows; }
+            edit_chunks(wh.data(), n, P->group, (int)P->workers.size(), P->origin, P->chunks);
+            P->esorted.clear();
+            for (int i : P->origin) P->esorted.push_back(jobs[i]);
+        }
+        P->next.store(0);
+        P->finished_workers = 0;
+        ++P->generation;
+    }
+    P->cv_work.notify_all();
+    {
+        std::unique_lock<std::mutex> lk(P->mu);
+        P->cv_done.wait(lk, [&] { return P->finished_workers == (int)P->workers.size(); });
+    }
+    for (int i = 0; i < n; ++i)
+        if (jobs[i].rc != SC_OK && jobs[i].rc != SC_ERR_NOT_CONVERGED) return jobs[i].rc;
+    return SC_OK;
+}
+
+int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int streams, int *group_of)
+{
+    if (!wh || n < 1 || !group_of || group < 0 || group > 64 || streams < 1) return SC_ERR_BAD_ARG;
+    std::vector<int> order;
+    std::vector<std::pair<int, int>> chunks;
+    edit_chunks(wh, n, group, std::min(streams, 16), order, chunks);
+    for (size_t c = 0; c < chunks.size(); ++c)
+        for (int q = 0; q < chunks[c].second; ++q) group_of[order[chunks[c].first + q]] = (int)c;
+    return (int)chunks.size();
 }
 
 } // extern "C"

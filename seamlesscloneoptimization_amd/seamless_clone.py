@@ -10,7 +10,8 @@ Same method names and argument meaning:
                                                        clone writes into it, seamlessClone_imp.cpp:470)
     sync(), destroy(), mat2py(a), py2mat(a), loadImageInCpp_Demo(path)
 Additions: setSolver(**opts), setCloneMode(mode), info(); seamlessClone(src, dst, mask, p, flags) shaped like cv2.seamlessClone;
-colorChange, illuminationChange and textureFlattening shaped like their cv2 namesakes.
+colorChange, illuminationChange and textureFlattening shaped like their cv2 namesakes; edit_batch runs one of them over many
+images through a pool (same-size images share one set of launches).
 """
 from __future__ import annotations
 
@@ -166,3 +167,64 @@ def textureFlattening(src, mask, low_threshold=30, high_threshold=45, kernel_siz
     """cv2.textureFlattening-shaped: returns a NEW image, src untouched.  kernel_size: 3, 5 or 7."""
     return _edit(capi.SC_EDIT_TEXTURE_FLATTENING, src, mask, gpu_id, solver, low_threshold=float(low_threshold),
                  high_threshold=float(high_threshold), kernel_size=int(kernel_size))
+
+
+def edit_batch(op, srcs, masks, gpu_id=0, streams=2, group=capi.SC_POOL_GROUP_AUTO, **params_and_solver):
+    """One edit (capi.SC_EDIT_COLOR_CHANGE, ..._ILLUMINATION_CHANGE or ..._TEXTURE_FLATTENING) over a list of H x W x 3 uint8 images;
+    returns a list of NEW images, the inputs untouched.  masks: one mask for every image, or a list with one per image (H x W or
+    H x W x 3, as the cv2-shaped functions take them).  Keyword arguments named like sc_edit_params fields (red_mul, alpha,
+    low_threshold, kernel_size, ...) are the edit's parameters, the others solver options (method, flags, ...).  The images go to the
+    device in one copy and come back in one; a pool of `streams` instances runs them device-resident in chunks of `group` same-size
+    images (SC_POOL_GROUP_AUTO: the pool's automatic size), each chunk one field of 3n channels."""
+    edit_keys = {name for name, _ in capi.EditParams._fields_} - {"op"}
+    params = {k: v for k, v in params_and_solver.items() if k in edit_keys}
+    solver = {k: v for k, v in params_and_solver.items() if k not in edit_keys}
+    imgs = [np.ascontiguousarray(s, np.uint8) for s in srcs]
+    if not imgs:
+        return []
+    for s in imgs:
+        if s.ndim != 3 or s.shape[2] != 3:
+            raise ValueError("every src must be H x W x 3 uint8")
+    if isinstance(masks, (list, tuple)):
+        if len(masks) != len(imgs):
+            raise ValueError("one mask per image, or one mask for all")
+        ms = [_edit_mask(m, s.shape) for m, s in zip(masks, imgs)]
+        mask_of = list(range(len(imgs)))
+    else:
+        ms = [_edit_mask(masks, imgs[0].shape)]
+        for s in imgs[1:]:
+            if s.shape != imgs[0].shape:
+                raise ValueError("one mask for all images needs images of one size")
+        mask_of = [0] * len(imgs)
+    # one device block: sources | masks | destinations, every image at a 256-byte boundary
+    def place(arrays, at):
+        offs = []
+        for a in arrays:
+            offs.append(at)
+            at += (a.nbytes + 255) // 256 * 256
+        return offs, at
+    src_off, at = place(imgs, 0)
+    mask_off, in_bytes = place(ms, at)
+    dst_off, total = place(imgs, in_bytes)
+    staged = np.zeros(in_bytes, np.uint8)
+    for a, o in zip(imgs + ms, src_off + mask_off):
+        staged[o:o + a.nbytes] = a.reshape(-1)
+    pool = capi.Pool(gpu_id, streams=streams, group=group, **solver)
+    inst = pool.instances[0]
+    d = None
+    try:
+        d = inst.malloc(total)
+        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, d, staged.ctypes.data, in_bytes))
+        jobs = capi.Instance.make_edit_jobs(len(imgs))
+        for k, (j, s) in enumerate(zip(jobs, imgs)):
+            H, W = s.shape[:2]
+            j.src, j.cols, j.rows, j.src_step = d + src_off[k], W, H, 3 * W
+            j.mask, j.mask_step = d + mask_off[mask_of[k]], W
+            j.dst, j.dst_step = d + dst_off[k], 3 * W
+        pool.edit(inst.edit_params(op, **params), jobs, device_resident=True)
+        out = inst.from_device(d + in_bytes, (total - in_bytes,))
+    finally:
+        if d is not None:
+            inst.free(d)
+        pool.close()
+    return [out[o - in_bytes:o - in_bytes + s.nbytes].reshape(s.shape).copy() for o, s in zip(dst_off, imgs)]
