@@ -411,6 +411,68 @@ SC_API int sc_hip_pool_edit(void *pool, const sc_edit_params *p, sc_edit_job *jo
  * a pool of `streams` workers with group size `group` (SC_POOL_GROUP_AUTO allowed): group_of[i] = the job's chunk.  Returns the number
  * of chunks, or SC_ERR_BAD_ARG. */
 SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int streams, int *group_of);
+
+/* ---- the Poisson solver on float32 images with caller guidance fields ------------------------------------------------------------
+ * The problem (Perez et al.): the domain is the whole cols x rows rectangle, the unknowns are rows 1..rows-2, columns 1..cols-2, and
+ * the call solves, per channel, the 5-point system the clone and edit paths solve:
+ *     u(x-1,y) + u(x+1,y) + u(x,y-1) + u(x,y+1) - 4 u(x,y) = lap(x,y)       with u = boundary on the frame (Dirichlet).
+ * SC_POISSON_GUIDANCE: lap(q) = (gx(q) - gx(q - x)) + (gy(q) - gy(q - y)), backward differences in float32, in this order (the edit
+ * pre-process's formula).  Guidance made of forward differences of an image I, with I as the boundary, therefore gives back I.
+ * SC_POISSON_LAPLACIAN: lap given directly (interior only; its frame is never read).
+ * The answer is the exact system's: no float-table correction (that belongs to the reference's 8-bit answer; as with
+ * SC_FLAG_EXACT_TABLES), and every field is float32 -- right-hand side, level 1, the field between level-0 launches (the 16-bit and
+ * float16 forms of the clone path assume 8-bit data).  Nothing is clamped or rounded.
+ * Solver options: the instance's sc_solver_opts apply except reference_warmup, the clone mode and SC_FLAG_OPENCV_GREY_MASK; p->tol
+ * replaces update_tol for the call (in the data's units; <= 0: 1e-3), and a residual tol > 0 still stops on the residual.
+ * SC_METHOD_AUTO resolves as for a single clone when n = 1 (whatever the channel count) and to SC_METHOD_MULTIGRID for n > 1.
+ * The float32 floor: multigrid corrections settle at ~1e-8 x max|u| x sqrt(cols x rows), and the stop rule
+ * fires once its predicted error is a tenth of tol -- a tol below ten times that floor ends with SC_ERR_NOT_CONVERGED after max_sweeps
+ * cycles, the result then at the floor.  The default 1e-3 suits data of unit scale; 8-bit-range data at 1024^2 want ~0.1.
+ * sc_run_info: method, cycles, converged, W x H = the image; stage times (ms_pre, ms_solve, ms_post) when bSync is set and for the
+ * host call.  The instance's stored options are unchanged by the call.
+ * Layout: ONE layout for every array of every job of a call.  Element (x, y, c) is at
+ *     x * col_stride + y * row_stride + c * channel_stride   floats from the array's pointer.
+ * Strides are positive and must nest: sorted by size (dimensions of extent 1 left out), each one exceeds the span of the smaller
+ * ones, so no two elements share an offset.  HWC: (C, cols * C or more, 1); CHW: (1, cols or more, rows * row_stride or more);
+ * RGBA-strided C = 3: (4, 4 * cols, 1).
+ * Batches (sc_hip_poisson_device): all jobs have the layout's size and are solved as one field of n x channels planes, at most 192
+ * planes per set of launches (floor(192 / channels) jobs per chunk).  Channels never interact: a member equals its solo
+ * SC_METHOD_MULTIGRID run bit for bit when the cycle counts agree, and is within the stop rule's error otherwise.
+ * Aliasing: a job's out may equal its own boundary; it must not overlap any other array of the call.  Inputs may be shared.
+ * What a call writes: the cols x rows x channels elements of out the layout names (frame = boundary's, bit for bit).  Row padding,
+ * unused channel slots (the 4th float of an RGBA-strided C = 3 layout) and memory outside the image are never written.
+ * Codes: SC_ERR_BAD_ARG for a bad kind, a non-finite tol, channels outside 1..4, a stride <= 0 or strides that do not nest;
+ * SC_ERR_BAD_SIZE for cols or rows < 3.  Per job (sc_poisson_job.rc; the job is skipped, the others run): SC_ERR_BAD_ARG for a NULL
+ * pointer the kind needs or one that is not 4-byte aligned.  SC_ERR_NOT_CONVERGED: the budget ended first, the result is written.
+ * The return value is the worst code, as in sc_hip_edit_device_batch; a HIP error marks every validated job SC_ERR_HIP. */
+#define SC_POISSON_GUIDANCE  1   /* gx, gy given (gx read at columns 0..cols-2, gy at rows 0..rows-2) */
+#define SC_POISSON_LAPLACIAN 2   /* lap given                                                          */
+#define SC_POISSON_MAX_PLANES 192
+typedef struct sc_poisson_layout {
+    int cols, rows, channels;                            /* >= 3, >= 3, 1..4                  */
+    long long col_stride, row_stride, channel_stride;    /* in floats                         */
+} sc_poisson_layout;
+typedef struct sc_poisson_params {
+    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN                                  */
+    float tol;               /* the multigrid stop rule's update_tol for this call, in the data's units; <= 0: 1e-3 */
+} sc_poisson_params;
+typedef struct sc_poisson_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE                                                           */
+    const float *lap;        /* SC_POISSON_LAPLACIAN                                                          */
+    const float *boundary;   /* its frame: the Dirichlet values; its interior: the initial guess of the iterative methods */
+    float *out;              /* every element the layout names is written; may equal boundary                  */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job                                            */
+} sc_poisson_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_poisson_check(const sc_poisson_params *p, const sc_poisson_layout *l);
+/* Device pointers.  Asynchronous unless bSync (sync the instance before reading out); bSync also records the stage times. */
+SC_API int sc_hip_poisson_device(void *instance, const sc_poisson_params *p, const sc_poisson_layout *l, sc_poisson_job *jobs, int n,
+                                 bool bSync);
+/* One problem on host arrays: the span each array occupies under the layout (offsets 0 .. the largest) goes in and out through the
+ * instance's pinned staging, and only the named elements of out are written.  Synchronous, like sc_hip_edit.  The arrays the kind
+ * does not use may be NULL. */
+SC_API int sc_hip_poisson(void *instance, const sc_poisson_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                          const float *lap, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -119,6 +119,26 @@ class EditJob(C.Structure):
                 ("dst", C.c_void_p), ("dst_step", C.c_int), ("rc", C.c_int)]
 
 
+# the Poisson solver on float32 images with caller guidance fields (sc_hip_poisson*): Instance.poisson / poisson_device
+SC_POISSON_GUIDANCE = 1
+SC_POISSON_LAPLACIAN = 2
+SC_POISSON_MAX_PLANES = 192
+
+
+class PoissonLayout(C.Structure):
+    _fields_ = [("cols", C.c_int), ("rows", C.c_int), ("channels", C.c_int),
+                ("col_stride", C.c_longlong), ("row_stride", C.c_longlong), ("channel_stride", C.c_longlong)]
+
+
+class PoissonParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("tol", C.c_float)]
+
+
+class PoissonJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p),
+                ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -280,6 +300,13 @@ def load():
     L.sc_hip_canny.restype = C.c_int
     L.sc_hip_edit_counts.argtypes = [C.c_void_p, i32p]
     L.sc_hip_edit_counts.restype = C.c_int
+    L.sc_hip_poisson_check.argtypes = [C.POINTER(PoissonParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_poisson_check.restype = C.c_int
+    L.sc_hip_poisson_device.argtypes = [C.c_void_p, C.POINTER(PoissonParams), C.POINTER(PoissonLayout), C.POINTER(PoissonJob), C.c_int,
+                                        C.c_bool]
+    L.sc_hip_poisson_device.restype = C.c_int
+    L.sc_hip_poisson.argtypes = [C.c_void_p, C.POINTER(PoissonParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 5
+    L.sc_hip_poisson.restype = C.c_int
     _lib = L
     return L
 
@@ -294,6 +321,58 @@ def _img(a: np.ndarray):
     if a.strides[-1] != 1 or (a.ndim == 3 and a.strides[1] != ch):
         raise ValueError("image rows must be contiguous (cv::Mat layout)")
     return a.ctypes.data, a.shape[1], a.shape[0], a.strides[0]
+
+
+def poisson_layout_of(a: np.ndarray) -> PoissonLayout:
+    """The PoissonLayout of a float32 array of shape H x W or H x W x C (numpy's strides, in floats)."""
+    if a.dtype != np.float32:
+        raise TypeError("Poisson arrays must be float32")
+    if a.ndim not in (2, 3):
+        raise ValueError("Poisson arrays are H x W or H x W x C")
+    if any(s % 4 for s in a.strides):
+        raise ValueError("strides must be whole floats")
+    H, W = a.shape[:2]
+    Cn = a.shape[2] if a.ndim == 3 else 1
+    rs, cs = a.strides[0] // 4, a.strides[1] // 4
+    chs = a.strides[2] // 4 if a.ndim == 3 else 1
+    return PoissonLayout(W, H, Cn, cs, rs, chs)
+
+
+def _layout_key(l: PoissonLayout):
+    return (l.cols, l.rows, l.channels, l.col_stride, l.row_stride, l.channel_stride)
+
+
+def poisson_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, layout: "PoissonLayout | None" = None, *, cols=None, rows=None,
+                  channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_poisson_check: SC_OK or the code a call with this kind, tol and layout returns before it runs anything.  The
+    layout as a PoissonLayout or as keyword fields."""
+    if layout is None:
+        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
+    return int(load().sc_hip_poisson_check(C.byref(PoissonParams(int(kind), float(tol))), C.byref(layout)))
+
+
+def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None):
+    """Checks a Poisson problem's numpy arrays before any device is touched: (kind, layout, boundary, gx, gy, lap, out) with every array
+    float32 and of boundary's shape.  The layout is numpy's strides when all arrays share them; otherwise the arrays are made
+    contiguous (out then stays the caller's and is written back by the caller: see Instance.poisson)."""
+    if (gx is None) != (gy is None):
+        raise ValueError("gx and gy go together")
+    if (gx is None) == (lap is None):
+        raise ValueError("give either gx and gy or lap")
+    kind = SC_POISSON_LAPLACIAN if lap is not None else SC_POISSON_GUIDANCE
+    arrays = {"boundary": boundary, "gx": gx, "gy": gy, "lap": lap, "out": out}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+        if a.shape != boundary.shape:
+            raise ValueError(f"{name} has shape {a.shape}, boundary {boundary.shape}")
+    if boundary.ndim not in (2, 3) or (boundary.ndim == 3 and not 1 <= boundary.shape[2] <= 4):
+        raise ValueError("Poisson arrays are H x W or H x W x C with C in 1..4")
+    if out is not None and not out.flags.writeable:
+        raise ValueError("out must be writeable")
+    return kind, boundary, gx, gy, lap, out
 
 
 class Instance:
@@ -443,6 +522,47 @@ class Instance:
         counts = np.zeros(2, np.int32)
         self._check(self.L.sc_hip_edit_counts(self.h, counts.ctypes.data_as(i32p)))
         return int(counts[0]), int(counts[1])
+
+    # ---- the Poisson solver on float32 arrays
+    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False):
+        """sc_hip_poisson on numpy float32 arrays of shape H x W or H x W x C (C 1..4): solve lap(u) = div (gx, gy) (or = lap) with
+        u = boundary on the frame; boundary's interior is the initial guess of the iterative methods.  out: an array of boundary's
+        shape to write (may be boundary itself), default a new one.  Returns out."""
+        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out)
+        if out is None:
+            out = np.empty_like(boundary)
+        given = [a for a in (boundary, gx, gy, lap, out) if a is not None]
+        lays = [poisson_layout_of(a) for a in given]
+        target = out
+        if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
+            # one layout per call: contiguous copies (an in-place call stays in place)
+            same = out is boundary
+            boundary = np.ascontiguousarray(boundary)
+            gx, gy, lap = (None if a is None else np.ascontiguousarray(a) for a in (gx, gy, lap))
+            out = boundary if same and boundary is target else np.empty_like(boundary)
+        layout = poisson_layout_of(boundary)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.L.sc_hip_poisson(self.h, C.byref(PoissonParams(kind, float(tol))), C.byref(layout), ptr(gx), ptr(gy), ptr(lap),
+                                   ptr(boundary), ptr(out))
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        if out is not target:
+            target[...] = out
+        return target
+
+    @staticmethod
+    def make_poisson_jobs(n: int):
+        return (PoissonJob * n)()
+
+    def poisson_device(self, params: PoissonParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_poisson_device: jobs is a PoissonJob array (make_poisson_jobs) of device pointers, one layout for all.  sync: bSync
+        (stage times) and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is
+        returned, other failures raise unless allow_job_errors (then they are returned as well)."""
+        rc = self.L.sc_hip_poisson_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -11,9 +11,11 @@
 //      below): groups formed, every job run exactly once, per-job codes copied back, several batches on one pool;
 //   4. the same for batches of whole-image edits (sc_hip_pool_edit): chunks of one image size, every job exactly once, codes back,
 //      and a chunk whose batch call fails with SC_ERR_HIP (after writing SC_OK into its members) reported as failed, job and pool.
+//   5. sc_hip_poisson_check over valid and invalid layouts (the overlap test's 128-bit arithmetic at extreme strides included).
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -218,6 +220,34 @@ int main()
         for (int i = 0; i < n; ++i)
             if (jobs[i].rc != (jobs[i].cols == FAILING_COLS ? SC_ERR_HIP : SC_OK)) return fail("a job of a failed batch call reads as done");
         sc_hip_pool_destroy(pool);
+    }
+    // 5: the Poisson call's validation
+    {
+        struct Case { int kind; float tol; int w, h, c; long long cs, rs, chs; int want; };
+        const long long big = 1LL << 62;
+        const Case cases[] = {
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 3, 3, 3 * 640, 1, SC_OK },                 // HWC
+            { SC_POISSON_LAPLACIAN, 1e-2f, 640, 480, 3, 1, 640, 640 * 480, SC_OK },          // CHW
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 3, 4, 4 * 640, 1, SC_OK },                 // RGBA-strided C = 3
+            { SC_POISSON_GUIDANCE, 0.f, 33, 7, 1, 1, 40, 1, SC_OK },                         // padded rows, C = 1 (channel stride free)
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 3, 2, 3 * 640, 1, SC_ERR_BAD_ARG },        // x and c overlap
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 3, 1, 640, 640, SC_ERR_BAD_ARG },          // rows and planes overlap
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 3, 3, 0, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 0, 3, 3 * 640, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 5, 5, 5 * 640, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE, 0.f, 2, 480, 3, 3, 6, 1, SC_ERR_BAD_SIZE },
+            { 3, 0.f, 640, 480, 3, 3, 3 * 640, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE, NAN, 640, 480, 3, 3, 3 * 640, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE, 0.f, 65536, 65536, 4, big / 4, big / 2, 1, SC_ERR_BAD_ARG },   // spans beyond 2^60 floats
+            { SC_POISSON_GUIDANCE, 0.f, 640, 480, 4, big, big, big, SC_ERR_BAD_ARG },
+        };
+        for (const Case &k : cases) {
+            sc_poisson_params p{ k.kind, k.tol };
+            sc_poisson_layout l{ k.w, k.h, k.c, k.cs, k.rs, k.chs };
+            if (sc_hip_poisson_check(&p, &l) != k.want) return fail("poisson_check");
+        }
+        sc_poisson_params p{ SC_POISSON_GUIDANCE, 0.f };
+        if (sc_hip_poisson_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_poisson_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("poisson_check (null)");
     }
     printf("sanitize_main: clean\n");
     return 0;

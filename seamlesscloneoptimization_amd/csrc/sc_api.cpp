@@ -340,7 +340,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     if (I->aux2) (void)hipStreamSynchronize(I->aux2);
     for (DevBuf &b : I->retired) dev_release(b);                    // blocks that growth replaced (ensure)
     for (Instance::Slab &sl : I->slabs) if (sl.base) (void)hipFree(sl.base);
-    DevBuf *bufs[] = { &I->d_face, &I->d_body_roi, &I->d_out, &I->d_mask, &I->d_in, &I->d_M, &I->d_edge, &I->d_U0, &I->d_U1, &I->d_F };
+    DevBuf *bufs[] = { &I->d_face, &I->d_body_roi, &I->d_out, &I->d_mask, &I->d_in, &I->d_M, &I->d_edge, &I->d_pois, &I->d_U0, &I->d_U1, &I->d_F };
     for (DevBuf *b : bufs) dev_release(*b);
     for (DevBuf &b : I->mg_bufs) dev_release(b);
     dev_release(I->mg_partial);

@@ -77,6 +77,16 @@ void launch_canny_hyst_group(uint8_t *C, int cpitch, size_t cplane, int n, int W
 void launch_edit_preprocess_group(int op, const float k[3], float ab, float nbeta, const EditJob *jobs, int n, const uint8_t *M, int mpitch,
                                   size_t mplane, const uint8_t *E, Field U0, Field F, hipStream_t s);
 void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream_t s);     // members whose dst is not their src
+// the Poisson solve on caller arrays (sc_poisson.hip, sc_poisson_api.cpp): one layout (W x H x C elements, strides in floats) for
+// every array of a call; pre-process into U0 / F (lap: the right-hand side given, else from gx, gy), the solution U back into out.
+// Group forms: member k owns channels C k .. C k + C - 1, one launch per 16 members (the table goes by value)
+struct PoissonGeo { int W, H, C; long long cs, rs, chs; };
+struct PoissonJobDev { const float *gx, *gy, *lap, *b; float *out; };
+struct PoissonJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; };
+void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s);
+void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s);
+void launch_poisson_out(const PoissonGeo &g, const PoissonJobDev &j, Field U, hipStream_t s);
+void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, int n, Field U, hipStream_t s);
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

@@ -158,6 +158,9 @@ struct Instance {
     // edits (sc_edit_api.cpp): Canny's class map (pitch mpitch), the hysteresis mailbox (pinned), the last edit's hysteresis counts
     DevBuf d_edge, h_hyst;
     int hyst_launches = 0, hyst_reads = 0;
+    // the Poisson solve on caller arrays (sc_poisson_api.cpp): the host call's device copies of the arrays' spans
+    DevBuf d_pois;
+    bool auto_as_single = false;           // ... one problem of up to 4 channels: SC_METHOD_AUTO decides as for a single clone (effective_method)
     // fields
     DevBuf d_U0, d_U1, d_F;
     Field U0, U1, F;      // current views into the buffers above
@@ -282,6 +285,9 @@ void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src,
 // ... the same for a group of n same-size images (sc_edit_batch.cpp): member k's eroded mask / class map in plane k of d_M / d_edge
 int canny_stage_group(Instance *I, const EditJob *jobs, int n, int W, int H, size_t mplane, float low, float high, int aperture);
 void edit_preprocess_group(Instance *I, const sc_edit_params *p, const EditJob *jobs, int n, size_t mplane);
+// sc_poisson_api.cpp: the Poisson call's validation (host-only; why: the reason) and a job's own
+int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, const char **why);
+int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why);
 // sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
 void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
 int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);

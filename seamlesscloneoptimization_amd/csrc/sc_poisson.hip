@@ -1,0 +1,178 @@
+// sc_poisson.hip -- the two launches around the solve of sc_hip_poisson (host side in sc_poisson_api.cpp): the pre-process reads
+// the caller's strided float32 arrays into the fields the solvers expect, the output launch writes the solution back.
+//
+// The field contract is k_edit_preprocess's: U0 = boundary on the whole image (frame and interior, 0 in the pad columns up to the
+// next multiple of four), F = the right-hand side on the interior, 0 on the frame and in the pads.  Member k of a group owns
+// channels C k .. C k + C - 1 of the fields (blockIdx.z = k inside a launch of up to 16 members).
+//
+// Lanes: one element (x, c) of an image row per lane, ROWS rows per workgroup walked top to bottom.  The lane space of a row is
+// (x, c) with c inner when the layout interleaves the channels (channel_stride < col_stride: HWC, RGBA-strided) and x inner
+// otherwise (planar CHW), so consecutive lanes read consecutive floats of the two common layouts.  Element (x - 1, c) of the same
+// row is then D lanes to the left (D = C interleaved, 1 planar): gx(q - x) comes from that lane through LDS, and gy(q - y) stays in
+// a register from the row before -- every guidance element is read once by one lane (plus one row and D elements of halo per
+// workgroup).
+#include "sc_common.h"
+#include <hip/hip_runtime.h>
+#include <algorithm>
+
+namespace sc {
+
+constexpr int PS_LANES = 256, PS_ROWS = 16;
+
+// the lane's element of the row space: (x, c); false beyond the row (E elements)
+__device__ __forceinline__ bool ps_lane(const PoissonGeo &g, bool inter, int wcols, int &x, int &c)
+{
+    const int e = (int)blockIdx.x * PS_LANES + (int)threadIdx.x;
+    if (inter) { x = e / g.C; c = e - x * g.C; }
+    else { c = e / wcols; x = e - c * wcols; }
+    return inter ? x < wcols : c < g.C;
+}
+
+template <bool INTER, bool LAP>
+__device__ __forceinline__ void poisson_pre_block(const PoissonGeo &g, const PoissonJobDev &j, const Field &U0, const Field &F, int c0)
+{
+    __shared__ float gxs[2][PS_LANES];
+    const int W = g.W, H = g.H, Wp = (W + 3) & ~3;
+    int x, c;
+    const bool lane = ps_lane(g, INTER, Wp, x, c);
+    const int D = INTER ? g.C : 1;
+    const int tid = (int)threadIdx.x;
+    const bool img = lane && x < W, in_x = lane && x >= 1 && x <= W - 2;
+    const long long xo = (long long)x * g.cs + (long long)c * g.chs;
+    float *const u0 = U0.p + (size_t)(c0 + c) * U0.plane + x, *const f = F.p + (size_t)(c0 + c) * F.plane + x;
+    const int y0 = (int)blockIdx.y * PS_ROWS, y1 = min(y0 + PS_ROWS, H);
+    float gyu = 0.f;
+    if (!LAP && in_x && y0 >= 1) gyu = j.gy[xo + (long long)(y0 - 1) * g.rs];
+    for (int y = y0; y < y1; ++y) {
+        const long long o = xo + (long long)y * g.rs;
+        const bool in_y = y >= 1 && y <= H - 2, in = in_x && in_y;
+        float lap = 0.f;
+        if constexpr (LAP) {
+            if (in) lap = j.lap[o];
+        } else {
+            const float gxv = (lane && x <= W - 2 && in_y) ? j.gx[o] : 0.f;      // column 0 too: the lane to its right needs it
+            const float gyv = (in_x && y <= H - 2) ? j.gy[o] : 0.f;              // row 0 too: the row below needs it
+            float *const s = gxs[y & 1];
+            s[tid] = gxv;
+            __syncthreads();         // (double-buffered: a lane writes the other half next row, which every lane finished reading before this barrier)
+            if (in) {
+                const float gxl = tid >= D ? s[tid - D] : j.gx[o - g.cs];
+                lap = (gxv - gxl) + (gyv - gyu);
+            }
+            gyu = gyv;
+        }
+        if (lane) {
+            const size_t fo = (size_t)y * U0.pitch;
+            u0[fo] = img ? j.b[o] : 0.f;
+            f[fo] = lap;
+        }
+    }
+}
+
+template <bool INTER, bool LAP>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_pre(PoissonGeo g, PoissonJobDev j, Field U0, Field F)
+{
+    poisson_pre_block<INTER, LAP>(g, j, U0, F, 0);
+}
+
+template <bool INTER, bool LAP>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_pre_group(PoissonGeo g, PoissonJobs t, Field U0, Field F)
+{
+    poisson_pre_block<INTER, LAP>(g, t.j[blockIdx.z], U0, F, g.C * (int)blockIdx.z);
+}
+
+// the solution field's interior into out, the frame from boundary (bit for bit); only the W x H x C elements the layout names
+template <bool INTER>
+__device__ __forceinline__ void poisson_out_block(const PoissonGeo &g, const PoissonJobDev &j, const Field &U, int c0)
+{
+    const int W = g.W, H = g.H;
+    int x, c;
+    if (!ps_lane(g, INTER, W, x, c)) return;
+    const bool in_x = x >= 1 && x <= W - 2;
+    const long long xo = (long long)x * g.cs + (long long)c * g.chs;
+    const float *const u = U.p + (size_t)(c0 + c) * U.plane + x;
+    const int y0 = (int)blockIdx.y * PS_ROWS, y1 = min(y0 + PS_ROWS, H);
+    for (int y = y0; y < y1; ++y) {
+        const long long o = xo + (long long)y * g.rs;
+        j.out[o] = (in_x && y >= 1 && y <= H - 2) ? u[(size_t)y * U.pitch] : j.b[o];
+    }
+}
+
+template <bool INTER>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_out(PoissonGeo g, PoissonJobDev j, Field U)
+{
+    poisson_out_block<INTER>(g, j, U, 0);
+}
+
+template <bool INTER>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_out_group(PoissonGeo g, PoissonJobs t, Field U)
+{
+    poisson_out_block<INTER>(g, t.j[blockIdx.z], U, g.C * (int)blockIdx.z);
+}
+
+// ---------------------------------------------------------------- launchers
+static bool interleaved(const PoissonGeo &g) { return g.C > 1 && g.chs < g.cs; }
+static dim3 ps_grid(const PoissonGeo &g, int wcols, int members)
+{
+    return dim3((unsigned)((wcols * g.C + PS_LANES - 1) / PS_LANES), (unsigned)((g.H + PS_ROWS - 1) / PS_ROWS), (unsigned)members);
+}
+
+void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s)
+{
+    const dim3 grid = ps_grid(g, (g.W + 3) & ~3, 1);
+    if (interleaved(g)) {
+        if (lap) hipLaunchKernelGGL((k_poisson_pre<true, true>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
+        else hipLaunchKernelGGL((k_poisson_pre<true, false>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
+    } else {
+        if (lap) hipLaunchKernelGGL((k_poisson_pre<false, true>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
+        else hipLaunchKernelGGL((k_poisson_pre<false, false>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
+    }
+}
+
+template <typename Fn>
+static void ps_chunks(const PoissonJobDev *jobs, int n, Fn fn)
+{
+    for (int i0 = 0; i0 < n; i0 += PoissonJobs::MAX) {
+        PoissonJobs t{};
+        const int cnt = std::min(n - i0, (int)PoissonJobs::MAX);
+        for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
+        fn(t, i0, cnt);
+    }
+}
+
+void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s)
+{
+    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+        const dim3 grid = ps_grid(g, (g.W + 3) & ~3, cnt);
+        Field u = U0, f = F;      // this launch's first member owns channel C i0
+        u.p = U0.p + (size_t)g.C * i0 * U0.plane;
+        f.p = F.p + (size_t)g.C * i0 * F.plane;
+        if (interleaved(g)) {
+            if (lap) hipLaunchKernelGGL((k_poisson_pre_group<true, true>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
+            else hipLaunchKernelGGL((k_poisson_pre_group<true, false>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
+        } else {
+            if (lap) hipLaunchKernelGGL((k_poisson_pre_group<false, true>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
+            else hipLaunchKernelGGL((k_poisson_pre_group<false, false>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
+        }
+    });
+}
+
+void launch_poisson_out(const PoissonGeo &g, const PoissonJobDev &j, Field U, hipStream_t s)
+{
+    const dim3 grid = ps_grid(g, g.W, 1);
+    if (interleaved(g)) hipLaunchKernelGGL(k_poisson_out<true>, grid, dim3(PS_LANES), 0, s, g, j, U);
+    else hipLaunchKernelGGL(k_poisson_out<false>, grid, dim3(PS_LANES), 0, s, g, j, U);
+}
+
+void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, int n, Field U, hipStream_t s)
+{
+    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+        const dim3 grid = ps_grid(g, g.W, cnt);
+        Field u = U;
+        u.p = U.p + (size_t)g.C * i0 * U.plane;
+        if (interleaved(g)) hipLaunchKernelGGL(k_poisson_out_group<true>, grid, dim3(PS_LANES), 0, s, g, t, u);
+        else hipLaunchKernelGGL(k_poisson_out_group<false>, grid, dim3(PS_LANES), 0, s, g, t, u);
+    });
+}
+
+} // namespace sc

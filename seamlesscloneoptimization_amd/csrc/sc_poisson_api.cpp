@@ -1,0 +1,282 @@
+// sc_poisson_api.cpp -- the Poisson solver on float32 images with caller guidance fields (sc_hip_poisson_check, sc_hip_poisson_device,
+// sc_hip_poisson).
+//
+// A call: validation -> per chunk of at most SC_POISSON_MAX_PLANES planes: setup_fields(W, H, C m) -> pre-process (U0 = boundary,
+// F = lap; sc_poisson.hip) -> the instance's solve -> output launch (interior from the solution field, frame from boundary).  The
+// solve runs under per-call options: the exact system (SC_FLAG_EXACT_TABLES: no float-table correction, which belongs to the
+// reference's 8-bit answer), all fields float32 (the float16 right-hand side and level 1 and the 16-bit field between level-0 launches
+// assume 8-bit data), update_tol = the call's tol.  No solver writes output bytes (spec_post stays disarmed).  The instance's stored
+// options are restored on every way out.
+#include "sc_instance.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+using namespace sc;
+
+namespace sc {
+
+// host-only: the call's code for these parameters and this layout (SC_OK: it may run); `why` gets the reason
+int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
+    if (p->kind != SC_POISSON_GUIDANCE && p->kind != SC_POISSON_LAPLACIAN) {
+        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN";
+        return SC_ERR_BAD_ARG;
+    }
+    if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
+    if (l->channels < 1 || l->channels > 4) { *why = "channels must be 1..4"; return SC_ERR_BAD_ARG; }
+    if (l->col_stride <= 0 || l->row_stride <= 0 || l->channel_stride <= 0) { *why = "strides must be positive"; return SC_ERR_BAD_ARG; }
+    if (l->cols < 3 || l->rows < 3) { *why = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
+    if (l->cols > 65536 || l->rows > 65536) { *why = "the image must be at most 65536 x 65536"; return SC_ERR_BAD_SIZE; }
+    // the strides must nest: sorted by size, each exceeds the span of the smaller ones (dimensions of extent 1 take no part)
+    struct Dim { unsigned __int128 s, n; } d[3] = { { (unsigned __int128)l->col_stride, (unsigned)l->cols },
+                                                     { (unsigned __int128)l->row_stride, (unsigned)l->rows },
+                                                     { (unsigned __int128)l->channel_stride, (unsigned)l->channels } };
+    std::sort(d, d + 3, [](const Dim &a, const Dim &b) { return a.s < b.s; });
+    unsigned __int128 span = 0;
+    for (const Dim &k : d) {
+        if (k.n < 2) continue;
+        if (k.s <= span) { *why = "the layout's strides overlap (they must nest: each exceeds the span of the smaller ones)"; return SC_ERR_BAD_ARG; }
+        span += k.s * (k.n - 1);
+    }
+    if (span >= ((unsigned __int128)1 << 60)) { *why = "the layout spans more than 2^60 floats"; return SC_ERR_BAD_ARG; }
+    return SC_OK;
+}
+
+// floats from an array's pointer to one past its last element under the layout
+static size_t poisson_span(const sc_poisson_layout *l)
+{
+    return (size_t)((l->cols - 1) * l->col_stride + (l->rows - 1) * l->row_stride + (l->channels - 1) * l->channel_stride) + 1;
+}
+
+static bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+
+// a job's own code: the pointers its kind needs, 4-byte aligned
+int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
+{
+    const float *need[4] = { b, out, kind == SC_POISSON_GUIDANCE ? gx : lap, kind == SC_POISSON_GUIDANCE ? gy : lap };
+    for (const float *q : need) {
+        if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
+    return SC_OK;
+}
+
+} // namespace sc
+
+namespace {
+
+void mark(Instance *I, int k)
+{
+    if (I->stage_marks) (void)hipEventRecord(I->ev[k], I->stream);
+}
+
+// The call's effective options, the instance's own restored on every way out.
+struct PoissonScope {
+    Instance *I;
+    sc_solver_opts saved;
+    PoissonScope(Instance *I_, const sc_poisson_params *p, int n_valid) : I(I_), saved(I_->opts)
+    {
+        sc_solver_opts &o = I->opts;
+        o.flags = (o.flags | SC_FLAG_EXACT_TABLES | SC_FLAG_FLOAT_RHS | SC_FLAG_FLOAT_U0 | SC_FLAG_FLOAT_L1 | SC_FLAG_FLOAT_FIELD) &
+                  ~SC_FLAG_OPENCV_GREY_MASK;
+        o.update_tol = p->tol > 0.f ? p->tol : 1e-3f;
+        o.reference_warmup = 0;
+        if (o.method == SC_METHOD_AUTO && n_valid > 1) o.method = SC_METHOD_MULTIGRID;     // a batch: the cycles, as the edit batches
+        I->auto_as_single = n_valid == 1;           // one problem: AUTO decides as for a single clone, whatever its channel count
+    }
+    ~PoissonScope()
+    {
+        I->opts = saved;
+        I->auto_as_single = false;
+        I->force_float_field = false;
+        I->spec_post.armed = false;
+        I->spec_post.group.clear();
+    }
+};
+
+// One chunk of m same-size problems as one field of C m planes.  Marks: 0 start, 5 pre-process done, 6 solve done, 7 output done.
+int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m)
+{
+    int rc;
+    if ((rc = setup_fields(I, g.W, g.H, g.C * m))) return rc;
+    I->guard = RectGuard();
+    I->spec_post.armed = false;
+    I->spec_post.group.clear();
+    I->result_in_U1 = false;
+    I->f_half = I->u_half = false;      // float32 right-hand side and initial field
+    mark(I, 0);
+    const bool lap = kind == SC_POISSON_LAPLACIAN;
+    if (m == 1) launch_poisson_pre(g, lap, jobs[0], I->U0, I->F, I->stream);
+    else launch_poisson_pre_group(g, lap, jobs, m, I->U0, I->F, I->stream);
+    SC_HIP(I, hipGetLastError());
+    mark(I, 5);
+    I->info.sweep_launches = 0;
+    const int solve_rc = solve(I);
+    if (solve_rc == SC_RETRY_FLOAT_FIELD) { I->err = "internal: a 16-bit field on the float32 path"; return SC_ERR_HIP; }
+    if (solve_rc != SC_OK && solve_rc != SC_ERR_NOT_CONVERGED) return solve_rc;
+    mark(I, 6);
+    if (m == 1) launch_poisson_out(g, jobs[0], result(I), I->stream);
+    else launch_poisson_out_group(g, jobs, m, result(I), I->stream);
+    SC_HIP(I, hipGetLastError());
+    mark(I, 7);
+    return solve_rc;
+}
+
+void add_timing(Instance *I, float t[4])
+{
+    t[0] += ev_ms(I->ev[0], I->ev[5]);
+    t[1] += ev_ms(I->ev[5], I->ev[6]);
+    t[2] += ev_ms(I->ev[6], I->ev[7]);
+    t[3] += ev_ms(I->ev[0], I->ev[7]);
+}
+
+void set_timing(Instance *I, const float t[4])
+{
+    I->info.ms_mask = 0.f;
+    I->info.ms_pre = t[0]; I->info.ms_solve = t[1]; I->info.ms_post = t[2];
+    I->info.ms_device_total = t[0] + t[1] + t[2];
+    I->info.ms_call = t[3];
+}
+
+// Every job of `valid` (indices into jobs) through chunks of at most SC_POISSON_MAX_PLANES planes.  timed: stage marks, a wait per
+// chunk, the stage times summed into t.  Codes as sc_hip_edit_device_batch: the worst; a HIP error marks every valid job.
+int poisson_run(Instance *I, const sc_poisson_params *p, const sc_poisson_layout *l, sc_poisson_job *jobs, const std::vector<int> &valid,
+                bool timed, float t[4])
+{
+    const int nv = (int)valid.size();
+    PoissonScope scope(I, p, nv);
+    const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
+    Geo geo{ 0, 0, g.W, g.H, 0, 0 };
+    fill_info_geo(I, geo);
+    I->stage_marks = timed;
+    I->marks_ends_only = false;
+    const int per = std::max(1, SC_POISSON_MAX_PLANES / g.C);
+    int worst = SC_OK;
+    std::vector<PoissonJobDev> dj;
+    for (int i0 = 0; i0 < nv; i0 += per) {
+        const int m = std::min(per, nv - i0);
+        dj.resize(m);
+        for (int k = 0; k < m; ++k) {
+            const sc_poisson_job &j = jobs[valid[i0 + k]];
+            dj[k] = PoissonJobDev{ j.gx, j.gy, j.lap, j.boundary, j.out };
+        }
+        int rc = poisson_chunk(I, p->kind, g, dj.data(), m);
+        if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
+            if (timed) {
+                SC_HIP(I, hipStreamSynchronize(I->stream));
+                add_timing(I, t);
+            }
+            for (int k = 0; k < m; ++k) jobs[valid[i0 + k]].rc = rc;
+            if (rc != SC_OK && worst == SC_OK) worst = rc;
+            I->info.group_members = m > 1 ? m : 0;
+            continue;
+        }
+        // a chunk that failed: its members and every one not yet run read its code; after a HIP error the ones already run too
+        for (int k = i0; k < nv; ++k) jobs[valid[k]].rc = rc;
+        if (rc == SC_ERR_HIP)
+            for (int k = 0; k < i0; ++k) jobs[valid[k]].rc = rc;
+        return rc;
+    }
+    return worst;
+}
+
+} // namespace
+
+extern "C" {
+
+int sc_hip_poisson_check(const sc_poisson_params *p, const sc_poisson_layout *l)
+{
+    return poisson_validate(p, l, nullptr);
+}
+
+int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poisson_layout *l, sc_poisson_job *jobs, int n, bool bSync)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    const char *why = "";
+    if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
+    if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
+    int worst = SC_OK;
+    std::vector<int> valid;
+    for (int i = 0; i < n; ++i) {
+        sc_poisson_job &j = jobs[i];
+        const int vrc = poisson_job_validate(p->kind, j.gx, j.gy, j.lap, j.boundary, j.out, &why);
+        if (vrc != SC_OK) {
+            j.rc = vrc;
+            if (worst == SC_OK) { worst = vrc; I->err = why; }
+            continue;
+        }
+        j.rc = SC_ERR_HIP;          // until its chunk has run
+        valid.push_back(i);
+    }
+    if (valid.empty()) return worst;
+    float t[4] = { 0.f, 0.f, 0.f, 0.f };
+    I->info.ms_h2d = I->info.ms_d2h = 0.f;
+    rc = poisson_run(I, p, l, jobs, valid, bSync, t);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    set_timing(I, t);               // (zeros without bSync)
+    if (worst == SC_OK) worst = rc;
+    return worst;
+}
+
+int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                   const float *lap, const float *boundary, float *out)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    const char *why = "";
+    if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
+    if ((rc = poisson_job_validate(p->kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
+    // one device block: the inputs' spans, boundary's, and out's unless out is boundary (in place); each at a 256-byte boundary
+    const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
+    const bool guidance = p->kind == SC_POISSON_GUIDANCE, in_place = out == boundary;
+    const int slots = (guidance ? 2 : 1) + 1 + (in_place ? 0 : 1);
+    if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
+    uint8_t *d = (uint8_t *)I->d_pois.p;
+    float *d_in0 = (float *)d, *d_in1 = guidance ? (float *)(d + slot) : nullptr;
+    float *d_b = (float *)(d + slot * (guidance ? 2 : 1));
+    float *d_out = in_place ? d_b : (float *)(d + slot * (slots - 1));
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
+    if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
+    if ((rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
+    sc_poisson_job job{};
+    job.gx = guidance ? d_in0 : nullptr; job.gy = d_in1; job.lap = guidance ? nullptr : d_in0;
+    job.boundary = d_b; job.out = d_out;
+    float t[4] = { 0.f, 0.f, 0.f, 0.f };
+    rc = poisson_run(I, p, l, &job, std::vector<int>{ 0 }, true, t);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    const int rc_solve = rc;
+    // out's span back into pinned staging, then only the elements the layout names into the caller's array
+    if ((rc = ensure_pinned(I, I->h_out, bytes))) return rc;
+    SC_HIP(I, hipMemcpyAsync(I->h_out.p, d_out, bytes, hipMemcpyDeviceToHost, I->stream));
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    const float *h = (const float *)I->h_out.p;
+    const int W = l->cols, H = l->rows, Cn = l->channels;
+    if (span == (size_t)W * H * Cn) {
+        copy_rows(I, (uint8_t *)out, bytes, (const uint8_t *)h, bytes, bytes, 1);     // dense: every float of the span is named
+    } else {
+        for (int y = 0; y < H; ++y)
+            for (int x = 0; x < W; ++x)
+                for (int c = 0; c < Cn; ++c) {
+                    const size_t o = (size_t)(x * l->col_stride + y * l->row_stride + c * l->channel_stride);
+                    out[o] = h[o];
+                }
+    }
+    set_timing(I, t);
+    I->info.ms_h2d = ev_ms(I->ev_k0, I->ev[0]);
+    I->info.ms_d2h = ev_ms(I->ev[7], I->ev_k1);
+    I->info.ms_call = ev_ms(I->ev_k0, I->ev_k1);
+    return rc_solve;
+}
+
+} // extern "C"

@@ -228,3 +228,95 @@ def edit_batch(op, srcs, masks, gpu_id=0, streams=2, group=capi.SC_POOL_GROUP_AU
             inst.free(d)
         pool.close()
     return [out[o - in_bytes:o - in_bytes + s.nbytes].reshape(s.shape).copy() for o, s in zip(dst_off, imgs)]
+
+
+def poisson_tol(boundary, lap_scale=0.0):
+    """A multigrid stop (update_tol, in the data's units) the float32 solve can reach on this problem: the corrections of float32
+    V-cycles settle at ~1e-8 x max|u| x sqrt(W H) (measured), and the stop rule accepts a cycle once its
+    predicted error is a tenth of update_tol, so 4e-7 x scale x sqrt(W H), at least 1e-3.  scale: max |boundary|, or lap_scale when
+    that is larger (a proxy for max |u|)."""
+    b = np.asarray(boundary)
+    scale = max(float(np.abs(b).max()) if b.size else 0.0, float(lap_scale))
+    return max(1e-3, 4e-7 * scale * float(np.sqrt(b.shape[0] * b.shape[1])))
+
+
+def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None, **solver):
+    """Solve the Poisson equation on a float32 image of shape H x W or H x W x C (C 1..4) and return a NEW array: lap(u) = div (gx, gy)
+    (backward differences of the guidance field) or = laplacian, with u = boundary on the one-pixel frame.  boundary's interior is
+    the initial guess of the iterative methods.  tol: the multigrid stop rule in the data's units (None: poisson_tol(boundary), a
+    stop float32 can reach; <= 0: the library's 1e-3); keyword arguments are solver options (method, max_sweeps, flags, ...).  The
+    exact 5-point system's answer, in float32, nothing clamped."""
+    kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian)
+    if tol is None:
+        tol = poisson_tol(b)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol)
+    finally:
+        inst.destroy()
+
+
+def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, **solver):
+    """poisson_solve over a list of same-shape problems through ONE device-resident call (sc_hip_poisson_device): the inputs go to the
+    device in one copy and the results come back in one; the problems are solved as one field of n x C planes (chunks of at most
+    SC_POISSON_MAX_PLANES planes).  tol: as poisson_solve's (None: the largest poisson_tol of the batch).  Returns a list of NEW
+    arrays."""
+    bs = list(boundaries)
+    if not bs:
+        return []
+    n = len(bs)
+    if (gxs is None) != (gys is None) or (gxs is None) == (laplacians is None):
+        raise ValueError("give either gxs and gys or laplacians")
+    fields = [gxs, gys] if gxs is not None else [laplacians]
+    for f in fields:
+        if len(f) != n:
+            raise ValueError("one guidance field (or laplacian) per boundary")
+    checked = []
+    for k in range(n):
+        if gxs is not None:
+            kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k])
+            ins = [gx, gy]
+        else:
+            kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k])
+            ins = [lap]
+        if b.shape != bs[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        checked.append([np.ascontiguousarray(a) for a in ins + [b]])
+    shape = bs[0].shape
+    if tol is None:
+        tol = max(poisson_tol(a[-1]) for a in checked)
+    nb = checked[0][0].nbytes
+    slot = (nb + 255) // 256 * 256
+    per = len(checked[0])
+    in_bytes = slot * per * n
+    staged = np.zeros(in_bytes // 4, np.float32)
+    for k, arrays in enumerate(checked):
+        for i, a in enumerate(arrays):
+            o = (k * per + i) * slot // 4
+            staged[o:o + a.size] = a.reshape(-1)
+    layout = capi.poisson_layout_of(checked[0][-1])
+    inst = capi.Instance(gpu_id)
+    d = None
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        d = inst.malloc(in_bytes + slot * n)
+        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, d, staged.ctypes.data, in_bytes))
+        jobs = capi.Instance.make_poisson_jobs(n)
+        for k, j in enumerate(jobs):
+            base = d + k * per * slot
+            if kind == capi.SC_POISSON_GUIDANCE:
+                j.gx, j.gy = base, base + slot
+            else:
+                j.lap = base
+            j.boundary = base + (per - 1) * slot
+            j.out = d + in_bytes + k * slot
+        inst.poisson_device(capi.PoissonParams(kind, float(tol)), layout, jobs)
+        out = inst.from_device(d + in_bytes, (slot * n // 4,), np.float32)
+    finally:
+        if d is not None:
+            inst.free(d)
+        inst.destroy()
+    return [out[k * slot // 4:k * slot // 4 + checked[k][-1].size].reshape(shape).copy() for k in range(n)]
