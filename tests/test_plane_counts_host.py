@@ -1,0 +1,183 @@
+"""CPU side of tests/test_gpu_plane_counts.py: the launch decisions that depend on the number of planes in a field, restated in Python, and
+the proof that the GPU file's shapes reach both sides of each of them.  Every restatement names the C++ function it mirrors; a retune of
+one of their thresholds makes a coverage assertion below fail here, on the CPU, instead of quietly dropping a branch from the GPU tests.
+
+The GPU cases (DECISION_CASES) are Poisson device batches: same-size jobs of C channels solved as one field of n * C planes, cut into
+chunks of at most SC_POISSON_MAX_PLANES planes (sc_poisson_api.cpp poisson_run).  The Poisson path runs multigrid with float32 level-1
+fields (SC_FLAG_FLOAT_L1), so its coarse levels take the non-float16 branch of launch_cycle_coarse."""
+import math
+
+import pytest
+
+from oracle import mg_np
+
+MAX_PLANES = 192                # SC_POISSON_MAX_PLANES (include/seamlessclone_hip.h)
+C0_HX = 12                      # sc_cycle0.hip: C0_HX = 4 * C0_HXQ, halo columns per side of a k_cycle0 tile
+C0_NW, C0_R = 8, 8              # sc_cycle0.hip: waves per workgroup and rows per wave of the level-0 launch
+HOST_FOLD_MAX = 16384           # sc_multigrid.cpp mg_solve: host_fold = nb_cap <= 16384
+FFT_TINY_BYTES = 4 << 20        # sc_fft.hip fft_solve_t: tiny = plane * sizeof(T) <= 4 MiB
+
+
+def tb_gen_rows(W, H, C, hx, hy):
+    """sc_sweep_tb.hip tb_gen_rows (tb_big_side() = 10^6: the 8-row default for huge levels is never reached)."""
+    nbx = (W + (256 - 2 * hx) - 1) // (256 - 2 * hx)
+    for R in (4, 6, 8):
+        rows = 8 * R - 2 * hy
+        if nbx * ((H + rows - 1) // rows) * C <= 512:
+            return R
+    return 6 if C > 3 else 4
+
+
+def tb_gen_rows_deep(W, H, C, hx, hy):
+    """sc_sweep_tb.hip tb_gen_rows_deep: 4 only where 4-row bands fit one round, 6 otherwise."""
+    if tb_gen_rows(W, H, C, hx, hy) != 4:
+        return 6
+    nbx = (W + (256 - 2 * hx) - 1) // (256 - 2 * hx)
+    rows = 8 * 4 - 2 * hy
+    return 4 if nbx * ((H + rows - 1) // rows) * C <= 512 else 6
+
+
+def cycle0_blocks(W, H, C, sweeps):
+    """sc_cycle0.hip cycle0_blocks: workgroups of a level-0 launch of depth `sweeps`."""
+    RH, HY = C0_NW * C0_R, 2 * sweeps + 2
+    return ((W + (256 - 2 * C0_HX) - 1) // (256 - 2 * C0_HX)) * ((H + (RH - 2 * HY) - 1) // (RH - 2 * HY)) * C
+
+
+def fold_side(W, H, C):
+    """sc_multigrid.cpp mg_solve: the per-workgroup correction maxima are folded on the host up to 16384 workgroups of the deepest form,
+    on the device above (launch_max_final2)."""
+    return "host" if cycle0_blocks(W, H, C, 4) <= HOST_FOLD_MAX else "device"
+
+
+def fft_launches(W, H, fp64):
+    """sc_fft.hip fft_solve_t: three launches while one plane of unknowns (transform precision) fits 4 MiB, five above."""
+    return 3 if (W - 2) * (H - 2) * (8 if fp64 else 4) <= FFT_TINY_BYTES else 5
+
+
+def default_tail_level(levels):
+    """sc_multigrid.cpp mg_default_tail_level on mg_np.build_levels: the first level >= 2 with at most 127 unknowns per side (held in
+    k_mg_tail), unless that is level 2 and level 1 has at most 64 per side; 0 when there is none."""
+    nl = len(levels)
+    a = next((l for l in range(2, nl - 1) if levels[l][0].n <= 127 and levels[l][1].n <= 127), 0)
+    level1_direct = nl > 1 and levels[1][0].n <= 64 and levels[1][1].n <= 64
+    return a if a and not (a == 2 and level1_direct) else 0
+
+
+def bottom_kind(W, H):
+    """How the default hierarchy ends: "tail" (k_mg_tail level + directly solved level below it), "level1" (level 1 solved directly),
+    "deeper" (a deeper level solved directly without k_mg_tail) or "none" (no level fits the direct solver)."""
+    levels = mg_np.build_levels(W, H)
+    if default_tail_level(levels):
+        return "tail"
+    d = mg_np.direct_level(levels)
+    return "none" if d is None else "level1" if d == 1 else "deeper"
+
+
+def coarse_forms(W, H, C):
+    """(depth, R) of every float coarse-level launch of one cycle of the default (fused) schedule: sc_multigrid.cpp vcycle -> sc_cycle0.hip
+    launch_cycle_coarse, non-float16 branch.  Levels 1 .. bottom - 1 go through it, except the level k_mg_tail serves (tail_serves: the
+    one right above the bottom).  Level 1 of a composed schedule (mg_composes_level1: >= 3 levels, bottom >= 2) does all four sweeps before
+    the restriction: depth 4, bands from tb_gen_rows_deep; the others: depth 2, bands from tb_gen_rows."""
+    levels = mg_np.build_levels(W, H)
+    b = mg_np.bottom_level(levels)
+    a = default_tail_level(levels)
+    if a:
+        b = a + 1                  # (mg_np.bottom_level agrees here; the tail level itself is launched by k_mg_tail)
+    composes = len(levels) >= 3 and b >= 2
+    out = []
+    for l in range(1, b):
+        if a and l == a:
+            continue
+        dx, dy = levels[l]
+        depth = 4 if (l == 1 and composes) else 2
+        rows = tb_gen_rows_deep if depth >= 3 else tb_gen_rows
+        out.append((depth, rows(dx.n + 2, dy.n + 2, C, C0_HX, 2 * depth + 2)))
+    return out
+
+
+def chunks(n, C):
+    """sc_poisson_api.cpp poisson_run: job counts of the chunks of n jobs of C channels."""
+    per = max(1, MAX_PLANES // C)
+    return [min(per, n - i) for i in range(0, n, per)]
+
+
+# ---- the GPU cases of tests/test_gpu_plane_counts.py::test_decision_sides (W, H, channels per job, jobs, methods)
+DECISION_CASES = [
+    (140, 40, 2, 48, ("mg",)),                    # 96 planes: depth-4 level 1 in 4-row bands (one round); tail level
+    (520, 40, 4, 48, ("mg",)),                    # 192 planes: depth 2 in 4-row bands, depth 4 in 6-row bands
+    (40, 520, 3, 64, ("mg",)),                    # 192 planes: depth 2 in 6-row bands (many rounds, C > 3)
+    (40, 720, 1, 96, ("mg",)),                    # 96 planes: depth 2 in 8-row bands
+    (700, 1026, 1, 192, ("mg",)),                 # 192 planes: the device-side fold of the correction maxima
+    (1026, 1100, 1, 2, ("fft32", "fft64")),       # 5 launches in float and in double
+    (500, 700, 2, 3, ("fft32", "fft64")),         # 3 launches in float, 5 in double
+    (130, 41, 2, 96, ("mg", "fft32", "fft64")),   # level-1 direct bottom at 192 planes; 3 launches
+    (300, 9, 1, 5, ("mg",))   ,                     # thin: no level fits the direct solver
+]
+
+
+def decision_sides(cases=DECISION_CASES):
+    """every (decision, side) the cases reach"""
+    sides = set()
+    for W, H, C, n, methods in cases:
+        for m in chunks(n, C):
+            P = m * C                              # planes of one chunk's field
+            if "mg" in methods:
+                for depth, R in coarse_forms(W, H, P):
+                    if P > 3:
+                        sides.add(("coarse rows", depth, R))
+                sides.add(("fold", fold_side(W, H, P)))
+                sides.add(("bottom", bottom_kind(W, H)))
+            for name in ("fft32", "fft64"):
+                if name in methods:
+                    sides.add(("fft launches", name, fft_launches(W, H, name == "fft64")))
+    return sides
+
+
+REQUIRED_SIDES = {
+    ("coarse rows", 2, 4), ("coarse rows", 2, 6), ("coarse rows", 2, 8),
+    ("coarse rows", 4, 4), ("coarse rows", 4, 6),
+    ("fold", "host"), ("fold", "device"),
+    ("fft launches", "fft32", 3), ("fft launches", "fft32", 5), ("fft launches", "fft64", 3), ("fft launches", "fft64", 5),
+    ("bottom", "tail"), ("bottom", "level1"), ("bottom", "none"),
+}
+
+
+def test_the_gpu_cases_cover_every_side_of_every_decision():
+    got = decision_sides()
+    missing = REQUIRED_SIDES - got
+    assert not missing, sorted(missing)
+
+
+def test_the_gpu_cases_fit_the_budget():
+    """one chunk's field at most 1.2 GB, host arrays of a case within ~3 GB (the GPU tests share inputs between jobs above 64 MB)"""
+    for W, H, C, n, _ in DECISION_CASES:
+        for m in chunks(n, C):
+            assert 4 * W * H * m * C <= 1.2e9, (W, H, C, n)
+
+
+def test_the_restated_rules_at_known_points():
+    # tb_gen_rows: one round of 4-row bands, then 6, then 8, then many rounds (6 at C > 3, 4 otherwise)
+    assert tb_gen_rows(100, 20, 1, C0_HX, 6) == 4
+    assert tb_gen_rows(100, 20, 512, C0_HX, 6) == 4 and tb_gen_rows(100, 20, 513, C0_HX, 6) == 6
+    assert tb_gen_rows(100, 36, 512, C0_HX, 6) == 6 and tb_gen_rows(100, 52, 512, C0_HX, 6) == 8
+    assert tb_gen_rows(100, 53, 512, C0_HX, 6) == 6 and tb_gen_rows(100, 53, 3, C0_HX, 6) == 4
+    assert tb_gen_rows(5000, 5000, 3, C0_HX, 6) == 4 and tb_gen_rows(5000, 5000, 4, C0_HX, 6) == 6
+    # the deep form is never 8 rows
+    assert {tb_gen_rows_deep(W, H, C, C0_HX, 10) for W in (20, 300, 2000) for H in (10, 100, 1000) for C in (1, 3, 4, 48, 192)} == {4, 6}
+    # cycle0_blocks: 232-column tiles, 64 - 2 (2 T + 2) rows
+    assert cycle0_blocks(232, 44, 1, 4) == 1 and cycle0_blocks(233, 45, 3, 4) == 12
+    assert fold_side(700, 1026, 192) == "device" and fold_side(700, 1026, 170) == "host"
+    assert fft_launches(1026, 1026, False) == 3 and fft_launches(1027, 1026, False) == 5
+    assert fft_launches(726, 726, True) == 3 and fft_launches(727, 726, True) == 5
+    assert chunks(200, 1) == [192, 8] and chunks(130, 3) == [64, 64, 2] and chunks(48, 4) == [48]
+
+
+@pytest.mark.parametrize("W,H", [(300, 260), (517, 400), (1030, 1000), (254, 127), (510, 254), (700, 1026)])
+def test_the_tail_rule_agrees_with_the_library_planner(W, H):
+    """where the library's size-class planner takes the default hierarchy unchanged (solo_differs = 0), its tail level is
+    mg_default_tail_level's"""
+    from seamlesscloneoptimization_amd import capi
+    p = capi.plan_size(W, H)
+    assert p["eligible"] == 1 and p["solo_differs"] == 0
+    assert p["tail_level"] == default_tail_level(mg_np.build_levels(W, H)) > 0
+    assert math.isclose(p["levels"], len(mg_np.build_levels(W, H)))
