@@ -444,22 +444,41 @@ SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int str
  * Codes: SC_ERR_BAD_ARG for a bad kind, a non-finite tol, channels outside 1..4, a stride <= 0 or strides that do not nest;
  * SC_ERR_BAD_SIZE for cols or rows < 3.  Per job (sc_poisson_job.rc; the job is skipped, the others run): SC_ERR_BAD_ARG for a NULL
  * pointer the kind needs or one that is not 4-byte aligned.  SC_ERR_NOT_CONVERGED: the budget ended first, the result is written.
- * The return value is the worst code, as in sc_hip_edit_device_batch; a HIP error marks every validated job SC_ERR_HIP. */
+ * The return value is the worst code, as in sc_hip_edit_device_batch; a HIP error marks every validated job SC_ERR_HIP.
+ *
+ * SC_POISSON_NEUMANN (or'ed into either kind): no boundary values are known.  All cols x rows pixels are unknowns, the stencil reflects
+ * at the border, and the call solves per channel
+ *     sum over the 2, 3 or 4 neighbours p of q inside the image of (u(p) - u(q)) = lap(q).
+ * SC_POISSON_GUIDANCE: lap(q) = (a - b) + (c - d) in float32, a = gx(q) (0 in the last column), b = gx(q - x) (0 in column 0), c = gy(q)
+ * (0 in the last row), d = gy(q - y) (0 in row 0): the normal equations of min sum (u(x+1,y) - u(x,y) - gx)^2 + (u(x,y+1) - u(x,y) - gy)^2.
+ * Forward differences of an image give back the image up to a constant; gx's last column and gy's last row are never read.
+ * SC_POISSON_LAPLACIAN: lap is read at EVERY pixel, frame included.  The system is solvable only for a lap of sum zero: the call
+ * ignores lap's DC coefficient, i.e. it solves for lap - mean(lap).
+ * The free constant: per channel mean(out) = mean(boundary) over the image's cols x rows elements (summed in double on the device);
+ * boundary may be NULL: mean zero.  Nothing else of boundary is read.  out may equal boundary.
+ * Solved directly by DCT-II transforms (the chirp convolution of SC_METHOD_FFT with a chirp of period 2n, exact eigenvalues in double,
+ * the (0, 0) coefficient set to 0), in float32, or in double with SC_FLAG_FFT_FP64.  Methods: SC_METHOD_AUTO and SC_METHOD_FFT;
+ * any other method: SC_ERR_BAD_ARG, nothing written (the multigrid and the relaxation solvers assume a zero ring on every level).
+ * sc_run_info: method SC_METHOD_FFT, sweeps 1, converged 1; ms_pre = the boundary-mean reduction, ms_post ~ 0 (the last transform
+ * launch stores into out).  tol is validated and otherwise unused.  Sizes: cols, rows >= 2; at most 8192 per side, 4096 with
+ * SC_FLAG_FFT_FP64 (SC_ERR_BAD_SIZE beyond; sc_hip_poisson_check, which knows no instance, reports the 8192 limit).  Batches: one
+ * field of n x channels planes in the same chunks; a member equals its solo run bit for bit, always. */
 #define SC_POISSON_GUIDANCE  1   /* gx, gy given (gx read at columns 0..cols-2, gy at rows 0..rows-2) */
 #define SC_POISSON_LAPLACIAN 2   /* lap given                                                          */
+#define SC_POISSON_NEUMANN   (1 << 8)   /* or'ed into SC_POISSON_GUIDANCE / SC_POISSON_LAPLACIAN: reflecting border, no Dirichlet frame */
 #define SC_POISSON_MAX_PLANES 192
 typedef struct sc_poisson_layout {
-    int cols, rows, channels;                            /* >= 3, >= 3, 1..4                  */
+    int cols, rows, channels;                            /* >= 3, >= 3 (SC_POISSON_NEUMANN: >= 2, <= 8192), 1..4 */
     long long col_stride, row_stride, channel_stride;    /* in floats                         */
 } sc_poisson_layout;
 typedef struct sc_poisson_params {
-    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN                                  */
+    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN */
     float tol;               /* the multigrid stop rule's update_tol for this call, in the data's units; <= 0: 1e-3 */
 } sc_poisson_params;
 typedef struct sc_poisson_job {
     const float *gx, *gy;    /* SC_POISSON_GUIDANCE                                                           */
     const float *lap;        /* SC_POISSON_LAPLACIAN                                                          */
-    const float *boundary;   /* its frame: the Dirichlet values; its interior: the initial guess of the iterative methods */
+    const float *boundary;   /* its frame: the Dirichlet values; its interior: the initial guess of the iterative methods (SC_POISSON_NEUMANN: only its mean; may be NULL) */
     float *out;              /* every element the layout names is written; may equal boundary                  */
     int rc;                  /* out: SC_OK or SC_ERR_* of this job                                            */
 } sc_poisson_job;

@@ -122,6 +122,7 @@ class EditJob(C.Structure):
 # the Poisson solver on float32 images with caller guidance fields (sc_hip_poisson*): Instance.poisson / poisson_device
 SC_POISSON_GUIDANCE = 1
 SC_POISSON_LAPLACIAN = 2
+SC_POISSON_NEUMANN = 1 << 8          # or'ed into either kind: reflecting border, every pixel an unknown
 SC_POISSON_MAX_PLANES = 192
 
 
@@ -351,24 +352,32 @@ def poisson_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, layout: "Po
     return int(load().sc_hip_poisson_check(C.byref(PoissonParams(int(kind), float(tol))), C.byref(layout)))
 
 
-def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None):
+def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False):
     """Checks a Poisson problem's numpy arrays before any device is touched: (kind, layout, boundary, gx, gy, lap, out) with every array
     float32 and of boundary's shape.  The layout is numpy's strides when all arrays share them; otherwise the arrays are made
-    contiguous (out then stays the caller's and is written back by the caller: see Instance.poisson)."""
+    contiguous (out then stays the caller's and is written back by the caller: see Instance.poisson).  neumann: the kind carries
+    SC_POISSON_NEUMANN and boundary may be None (the shape is then gx's or lap's)."""
     if (gx is None) != (gy is None):
         raise ValueError("gx and gy go together")
     if (gx is None) == (lap is None):
         raise ValueError("give either gx and gy or lap")
     kind = SC_POISSON_LAPLACIAN if lap is not None else SC_POISSON_GUIDANCE
+    if neumann:
+        kind |= SC_POISSON_NEUMANN
+    elif boundary is None:
+        raise ValueError("boundary may be None only for a Neumann problem (neumann=True)")
     arrays = {"boundary": boundary, "gx": gx, "gy": gy, "lap": lap, "out": out}
+    first = boundary if boundary is not None else (lap if lap is not None else gx)
     for name, a in arrays.items():
         if a is None:
             continue
         if not isinstance(a, np.ndarray) or a.dtype != np.float32:
             raise TypeError(f"{name} must be a float32 numpy array")
-        if a.shape != boundary.shape:
-            raise ValueError(f"{name} has shape {a.shape}, boundary {boundary.shape}")
-    if boundary.ndim not in (2, 3) or (boundary.ndim == 3 and not 1 <= boundary.shape[2] <= 4):
+        if not isinstance(first, np.ndarray):
+            raise TypeError("Poisson arrays must be float32 numpy arrays")
+        if a.shape != first.shape:
+            raise ValueError(f"{name} has shape {a.shape}, the problem {first.shape}")
+    if first.ndim not in (2, 3) or (first.ndim == 3 and not 1 <= first.shape[2] <= 4):
         raise ValueError("Poisson arrays are H x W or H x W x C with C in 1..4")
     if out is not None and not out.flags.writeable:
         raise ValueError("out must be writeable")
@@ -524,23 +533,26 @@ class Instance:
         return int(counts[0]), int(counts[1])
 
     # ---- the Poisson solver on float32 arrays
-    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False):
+    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False, neumann=False):
         """sc_hip_poisson on numpy float32 arrays of shape H x W or H x W x C (C 1..4): solve lap(u) = div (gx, gy) (or = lap) with
         u = boundary on the frame; boundary's interior is the initial guess of the iterative methods.  out: an array of boundary's
-        shape to write (may be boundary itself), default a new one.  Returns out."""
-        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out)
+        shape to write (may be boundary itself), default a new one.  Returns out.
+        neumann: the reflecting problem on every pixel (SC_POISSON_NEUMANN); mean(out) = mean(boundary) per channel, boundary may be
+        None (mean zero; shape and layout then come from gx / lap)."""
+        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann)
+        first = boundary if boundary is not None else (lap if lap is not None else gx)
         if out is None:
-            out = np.empty_like(boundary)
+            out = np.empty_like(first)
         given = [a for a in (boundary, gx, gy, lap, out) if a is not None]
         lays = [poisson_layout_of(a) for a in given]
         target = out
         if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
             # one layout per call: contiguous copies (an in-place call stays in place)
             same = out is boundary
-            boundary = np.ascontiguousarray(boundary)
+            boundary = None if boundary is None else np.ascontiguousarray(boundary)
             gx, gy, lap = (None if a is None else np.ascontiguousarray(a) for a in (gx, gy, lap))
-            out = boundary if same and boundary is target else np.empty_like(boundary)
-        layout = poisson_layout_of(boundary)
+            out = boundary if same and boundary is target else np.empty(first.shape, np.float32)
+        layout = poisson_layout_of(out)
         ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.L.sc_hip_poisson(self.h, C.byref(PoissonParams(kind, float(tol))), C.byref(layout), ptr(gx), ptr(gy), ptr(lap),
                                    ptr(boundary), ptr(out))

@@ -240,6 +240,16 @@ int main()
             { SC_POISSON_GUIDANCE, NAN, 640, 480, 3, 3, 3 * 640, 1, SC_ERR_BAD_ARG },
             { SC_POISSON_GUIDANCE, 0.f, 65536, 65536, 4, big / 4, big / 2, 1, SC_ERR_BAD_ARG },   // spans beyond 2^60 floats
             { SC_POISSON_GUIDANCE, 0.f, 640, 480, 4, big, big, big, SC_ERR_BAD_ARG },
+            // SC_POISSON_NEUMANN: 2 x 2 up to 8192 per side, a base kind required
+            { SC_POISSON_GUIDANCE | SC_POISSON_NEUMANN, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_NEUMANN, 0.f, 8192, 8, 3, 3, 3 * 8192, 1, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_NEUMANN, 0.f, 1, 40, 1, 1, 1, 40, SC_ERR_BAD_SIZE },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_NEUMANN, 0.f, 40, 1, 1, 1, 40, 40, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_NEUMANN, 0.f, 8193, 8, 1, 1, 8193, 8 * 8193, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_NEUMANN, 0.f, 8, 8193, 1, 1, 8, 8 * 8193, SC_ERR_BAD_SIZE },
+            { SC_POISSON_NEUMANN, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_NEUMANN | 3, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 9) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
         };
         for (const Case &k : cases) {
             sc_poisson_params p{ k.kind, k.tol };

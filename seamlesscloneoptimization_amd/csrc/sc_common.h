@@ -87,6 +87,10 @@ void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, F
 void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s);
 void launch_poisson_out(const PoissonGeo &g, const PoissonJobDev &j, Field U, hipStream_t s);
 void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, int n, Field U, hipStream_t s);
+// the Neumann solve's free constant: parts[(k C + c) np + i] = the sum in double of rows [i H / np, (i + 1) H / np) of channel c of member k's
+// boundary (0 where the job has none); np = poisson_mean_parts(H); one launch per 16 members
+int poisson_mean_parts(int H);
+void launch_poisson_mean(const PoissonGeo &g, const PoissonJobDev *jobs, int n, double *parts, hipStream_t s);
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

@@ -27,6 +27,7 @@
 //     one launch (the row never leaves LDS) -> transpose -> rows (scale 4/((w+1)(h+1)) and the store into the field fused).
 // Everything is float32 (the reference's precision); the float tables are the reference's to the letter (:596-599).
 #include "sc_instance.h"
+#include "sc_wave.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -355,6 +356,94 @@ __global__ __launch_bounds__(256) void k_fft_transpose(const T *__restrict__ in,
     }
 }
 
+// ---- the Neumann problem (SC_POISSON_NEUMANN): DCT-II / DCT-III by the same chirp convolution ------------------------------------
+// All W x H pixels are unknowns and the 5-point stencil reflects at the border: the DCT-II diagonalises it.  With N = 2n, c_m =
+// exp(i pi m^2 / N) and h_k = exp(i pi k / 2n) c_k (FftDim kind 1: the chirp kernel conj(c_m) of period 2n, M >= 2n - 1 as before),
+//     forward   X_k = sum_{j<n} x_j cos(pi (2j+1) k / 2n) = Re[ h_k sum_j (x_j c_j) conj(c_{k-j}) ]
+//     inverse   x_j = X_0 / 2 + sum_{0<k<n} X_k cos(pi (2j+1) k / 2n) = Re[ c_j sum_k (X'_k h_k) conj(c_{j-k}) ],  X'_0 = X_0 / 2
+// (2/n of the true inverse left to the caller): chirp_convolve unchanged, data at S[0 .. n), the real part at the end.
+// The launches work straight between the caller's arrays and the work planes: plane p = member C + channel of a table of up to
+// PoissonJobs::MAX jobs.
+
+// the reflecting system's right-hand side at pixel (x, y) of channel c: given, or (a - b) + (c - d) of the guidance field in float32
+template <bool LAP>
+__device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDev &j, int c, int x, int y)
+{
+    const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
+    if (LAP) return j.lap[o];
+    const float a = x < g.W - 1 ? j.gx[o] : 0.f, b = x > 0 ? j.gx[o - g.cs] : 0.f;
+    const float cc = y < g.H - 1 ? j.gy[o] : 0.f, d = y > 0 ? j.gy[o - g.rs] : 0.f;
+    return (a - b) + (cc - d);
+}
+
+// MODE 0: row r of the right-hand side (from the jobs' arrays) -> DCT-II -> out[p][r][k] (tstore: out[p][k][r])
+// MODE 1: rows of `in` (the transposed plane: row = x frequency, entries = y) -> DCT-II, / den, (0, 0) zeroed, DCT-III -> out, as MODE 0
+// MODE 2: rows of `in` [p][y][k] -> DCT-III, scale, + the plane's mean of boundary (parts: nparts sums per plane, nullptr: 0) -> the job's out
+template <int MODE, typename T, bool LAP>
+__global__ __launch_bounds__(FFT_THREADS) void k_dct(FftPlan<T> P, PoissonGeo g, PoissonJobs jobs, const T *__restrict__ in, T *__restrict__ out,
+                                                     int rows, double scale, int tstore, const double *__restrict__ parts, int nparts)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
+    __shared__ double s_mean;
+    cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
+    const int tid = threadIdx.x, r = blockIdx.x, p = blockIdx.y, n = P.n;
+    const cx2<T> *__restrict__ half = P.chirp + (n + 1);
+    const T *__restrict__ src = (MODE == 0) ? nullptr : in + ((size_t)p * rows + r) * n;
+    const int member = p / g.C, c = p - member * g.C;
+    const PoissonJobDev &J = jobs.j[(MODE == 1) ? 0 : member];
+    if (MODE == 2 && tid < 64) {              // the first wave: the parts in a fixed order (the first barrier below publishes the sum)
+        double m = 0.0;
+        if (parts) for (int i = tid; i < nparts; i += 64) m += parts[(size_t)p * nparts + i];
+        m = wave_sum(m);
+        if (tid == 0) s_mean = m / ((double)g.W * (double)g.H);
+    }
+    for (int i = tid; i < P.M; i += FFT_THREADS) {
+        cx2<T> a = mk<T>((T)0, (T)0);
+        if (i < n) {
+            T x = (MODE == 0) ? (T)dct_rhs<LAP>(g, J, c, i, r) : src[i];
+            if (MODE == 2 && i == 0) x *= (T)0.5;
+            const cx2<T> ch = (MODE == 2) ? half[i] : P.chirp[i];
+            a = mk<T>(x * ch.x, x * ch.y);
+        }
+        S[fft_pad(i)] = a;
+    }
+    __syncthreads();
+    chirp_convolve<T>(S, P, tid);
+    if (MODE == 1) {
+        // X_k = Re(h_k y_k); divide by the eigenvalue (in double, as the DST's exact branch) and feed the quotient straight into the
+        // DCT-III: the row stays in LDS (element k is read and rewritten by the same thread: no barrier in between)
+        for (int k = tid; k < n; k += FFT_THREADS) {
+            const cx2<T> y = S[fft_pad(k)], h = half[k];
+            const T X = h.x * y.x - h.y * y.y;
+            const T den = (T)((2.0 * cospi((double)r / (double)rows) - 2.0) + (2.0 * cospi((double)k / (double)n) - 2.0));
+            T q = (r == 0 && k == 0) ? (T)0 : X / den;
+            if (k == 0) q *= (T)0.5;
+            S[fft_pad(k)] = mk<T>(q * h.x, q * h.y);
+        }
+        for (int i = n + tid; i < P.M; i += FFT_THREADS) S[fft_pad(i)] = mk<T>((T)0, (T)0);
+        __syncthreads();
+        chirp_convolve<T>(S, P, tid);
+    }
+    const T mean = (MODE == 2) ? (T)s_mean : (T)0;
+    for (int k = tid; k < n; k += FFT_THREADS) {
+        const cx2<T> y = S[fft_pad(k)], ch = (MODE == 0) ? half[k] : P.chirp[k];
+        const T X = ch.x * y.x - ch.y * y.y;
+        if (MODE == 2) J.out[(long long)k * g.cs + (long long)r * g.rs + (long long)c * g.chs] = (float)(X * (T)scale + mean);
+        else if (tstore) out[((size_t)p * n + k) * rows + r] = X;
+        else out[((size_t)p * rows + r) * n + k] = X;
+    }
+}
+
+template <typename T>
+static hipError_t dct_opt_in_lds(int bytes)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<1, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<2, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e;
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 // The circular convolution's length for n unknowns: the shortest M = r 2^k >= 2n - 1 with r in {1, 3, 5} (round 5; powers of two only
 // until then: 592 unknowns -> 2048 where 1280 does, 300 -> 1024 where 640 does).  The reference hands cuFFT 2n + 2 whatever it is
@@ -399,7 +488,10 @@ struct FftBuild { cx2<T> *chirp, *bhat, *tw, *tw2; cx2<double> *tw64, *tw64_2; F
 template <typename TC, typename T>
 struct FftBuildPair { FftBuild<TC, T> b[2]; };
 
-template <typename TC, typename T>
+// KIND 0: the DST-I's tables (chirp of period N = 2(n + 1)).  KIND 1: the DCT-II / DCT-III's (N = 2n): the same chirp kernel and
+// transform with that period, and behind chirp[0 .. n] the half-sample twiddle times the chirp, h_k = exp(i pi k / 2n) c_k =
+// exp(i pi k (k + 1) / 2n), k < n (phase reduced in integers like the chirp's).
+template <typename TC, typename T, int KIND>
 __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> bp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
@@ -407,13 +499,20 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
     const FftBuild<TC, T> &B = bp.b[blockIdx.x];
     const FftPlan<TC> &P = B.P;
     const int tid = threadIdx.x, n = P.n, M = P.M;
-    const long long N2 = 4LL * (n + 1);
+    const long long N2 = KIND ? 4LL * n : 4LL * (n + 1);
+    const int N = KIND ? 2 * n : 2 * (n + 1);
     for (int i = tid; i < max(M, n + 1); i += FFT_THREADS) {          // chirp and twiddles
         if (i <= n) {
             const long long q = ((long long)i * i) % N2;
             double sn, cs;
-            sincospi((double)q / (double)(2 * (n + 1)), &sn, &cs);
+            sincospi((double)q / (double)N, &sn, &cs);
             B.chirp[i] = mk<T>((T)cs, (T)sn);
+        }
+        if (KIND && i < n) {
+            const long long q = ((long long)i * (i + 1)) % N2;
+            double sn, cs;
+            sincospi((double)q / (double)N, &sn, &cs);
+            B.chirp[n + 1 + i] = mk<T>((T)cs, (T)sn);
         }
         if (i < M) {
             double sn, cs;
@@ -435,7 +534,7 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
         else if (m >= 1 && m <= n - 1) {
             const long long q = ((long long)m * m) % N2;
             double sn, cs;
-            sincospi((double)q / (double)(2 * (n + 1)), &sn, &cs);
+            sincospi((double)q / (double)N, &sn, &cs);
             v = mk<TC>((TC)cs, (TC)(-sn));
         }
         S[fft_pad(i)] = v;
@@ -449,6 +548,16 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
         B.bhat[i] = mk<T>((T)(v.x * inv), (T)(v.y * inv));
     }
 }
+
+template <typename TC, typename T>
+static void fft_launch_build(int kind, int cnt, size_t lds, hipStream_t s, const FftBuildPair<TC, T> &bp)
+{
+    if (kind) hipLaunchKernelGGL((k_fft_build<TC, T, 1>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+    else hipLaunchKernelGGL((k_fft_build<TC, T, 0>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+}
+
+// complex elements in front of bhat: the chirp, and for the DCT kind the half-sample twiddles behind it
+static size_t fft_chirp_len(const FftDim &D) { return (size_t)(D.kind ? 2 : 1) * (D.n + 1); }
 
 template <typename T>
 static FftPlan<T> fft_plan_raw(const cx2<T> *chirp, int n, int logM)
@@ -465,15 +574,15 @@ static FftPlan<T> fft_plan_raw(const cx2<T> *chirp, int n, int logM)
 
 // The tables for n unknowns in precision T: from the instance's LRU, or queued for a build on the second stream (fft_flush_builds:
 // both directions of a solve in one launch; the caller makes the main stream wait for I->fft.ev_built before the first transform
-// launch).  `keep`: an entry that must not be evicted (the other direction of the same solve).
+// launch).  `keep`: an entry that must not be evicted (the other direction of the same solve).  kind: FftDim::kind, part of the key.
 template <typename T>
-static int fft_build_dim(Instance *I, FftDim *&out, int n, const FftDim *keep)
+static int fft_build_dim(Instance *I, FftDim *&out, int n, const FftDim *keep, int kind = 0)
 {
     const bool dbl = sizeof(T) == sizeof(double);
     FftState &S = I->fft;
     FftDim *victim = nullptr;
     for (FftDim &d : S.dims) {
-        if (d.chirp.p && d.n == n && d.dbl == dbl) { d.used = ++S.tick; out = &d; return SC_OK; }
+        if (d.chirp.p && d.n == n && d.dbl == dbl && d.kind == kind) { d.used = ++S.tick; out = &d; return SC_OK; }
         if (&d != keep && (!victim || d.used < victim->used)) victim = &d;
     }
     FftDim &D = *victim;
@@ -485,10 +594,10 @@ static int fft_build_dim(Instance *I, FftDim *&out, int n, const FftDim *keep)
         SC_HIP(I, hipStreamWaitEvent(I->stream, S.ev_built, 0));      // (ensure() waits for that stream before it frees a buffer)
         S.pending = false;
     }
-    const size_t bytes = sizeof(cx2<T>) * (4 * (size_t)M + 1);      // chirp[n + 1 <= M + 1] | bhat[M] | tw[M] | tw2[2^logM <= M]: sized by M alone, so an entry is reallocated only when M grows
+    const size_t bytes = sizeof(cx2<T>) * (4 * (size_t)M + 1 + (kind ? n + 1 : 0));      // chirp[n + 1 <= M + 1] | bhat[M] | tw[M] | tw2[2^logM <= M]: sized by M alone, so an entry is reallocated only when M grows
     D.n = 0;
     if ((rc = ensure(I, D.chirp, bytes))) return rc;
-    D.n = n; D.logM = logM; D.r = L.r; D.dbl = dbl; D.used = ++S.tick;
+    D.n = n; D.logM = logM; D.r = L.r; D.dbl = dbl; D.kind = kind; D.used = ++S.tick;
     S.req[S.nreq++] = &D;
     out = &D;
     return SC_OK;
@@ -528,7 +637,7 @@ static int fft_flush_builds(Instance *I)
         FftDim &D = *S.req[k];
         const int M = D.r << D.logM;
         cx2<T> *chirp = (cx2<T> *)D.chirp.p;
-        B.chirp = chirp; B.bhat = chirp + (D.n + 1); B.tw = B.bhat + M;
+        B.chirp = chirp; B.bhat = chirp + fft_chirp_len(D); B.tw = B.bhat + M;
         B.tw2 = D.r > 1 ? B.tw + M : nullptr;
         B.tw64 = (!dbl && tcd[k]) ? (cx2<double> *)S.tw64.p + (size_t)k * 2 * maxM : nullptr;
         B.tw64_2 = (B.tw64 && D.r > 1) ? B.tw64 + M : nullptr;
@@ -536,27 +645,28 @@ static int fft_flush_builds(Instance *I)
         B.P.n = D.n; B.P.logM = D.logM; B.P.M = M; B.P.r = D.r;
         fft_radices(D.logM, B.P.lr, B.P.npass);
     };
-    // directions whose builds run in the same arithmetic share a launch
+    // directions whose builds run in the same arithmetic and are of one kind share a launch
     for (int k = 0; k < S.nreq;) {
-        const int cnt = (k + 1 < S.nreq && tcd[k + 1] == tcd[k]) ? 2 : 1;
+        const int cnt = (k + 1 < S.nreq && tcd[k + 1] == tcd[k] && S.req[k + 1]->kind == S.req[k]->kind) ? 2 : 1;
+        const int kind = S.req[k]->kind;
         const size_t lds_elems = (size_t)fft_pad(std::max(S.req[k]->r << S.req[k]->logM, cnt > 1 ? S.req[k + 1]->r << S.req[k + 1]->logM : 0)) + 1;
         if (dbl) {
             if constexpr (sizeof(T) == sizeof(double)) {
                 FftBuildPair<double, double> bp{};
                 for (int q = 0; q < cnt; ++q) { fill(bp.b[q], k + q); bp.b[q].P.tw = bp.b[q].tw; bp.b[q].P.tw2 = bp.b[q].tw2 ? bp.b[q].tw2 : bp.b[q].tw; }
-                hipLaunchKernelGGL((k_fft_build<double, double>), dim3(cnt), dim3(FFT_THREADS), sizeof(cx2<double>) * lds_elems, I->aux, bp);
+                fft_launch_build<double, double>(kind, cnt, sizeof(cx2<double>) * lds_elems, I->aux, bp);
             }
         } else if (tcd[k]) {
             if constexpr (sizeof(T) == sizeof(float)) {
                 FftBuildPair<double, float> bp{};
                 for (int q = 0; q < cnt; ++q) { fill(bp.b[q], k + q); bp.b[q].P.tw = bp.b[q].tw64; bp.b[q].P.tw2 = bp.b[q].tw64_2 ? bp.b[q].tw64_2 : bp.b[q].tw64; }
-                hipLaunchKernelGGL((k_fft_build<double, float>), dim3(cnt), dim3(FFT_THREADS), sizeof(cx2<double>) * lds_elems, I->aux, bp);
+                fft_launch_build<double, float>(kind, cnt, sizeof(cx2<double>) * lds_elems, I->aux, bp);
             }
         } else {
             if constexpr (sizeof(T) == sizeof(float)) {
                 FftBuildPair<float, float> bp{};
                 for (int q = 0; q < cnt; ++q) { fill(bp.b[q], k + q); bp.b[q].P.tw = bp.b[q].tw; bp.b[q].P.tw2 = bp.b[q].tw2 ? bp.b[q].tw2 : bp.b[q].tw; }
-                hipLaunchKernelGGL((k_fft_build<float, float>), dim3(cnt), dim3(FFT_THREADS), sizeof(cx2<float>) * lds_elems, I->aux, bp);
+                fft_launch_build<float, float>(kind, cnt, sizeof(cx2<float>) * lds_elems, I->aux, bp);
             }
         }
         k += cnt;
@@ -610,7 +720,7 @@ static FftPlan<T> fft_plan_of(const FftDim &D)
 {
     FftPlan<T> P{};
     P.chirp = (const cx2<T> *)D.chirp.p;
-    P.bhat = P.chirp + (D.n + 1);
+    P.bhat = P.chirp + fft_chirp_len(D);
     const size_t M = (size_t)D.r << D.logM;
     P.tw = P.bhat + M;
     P.tw2 = D.r > 1 ? P.tw + M : P.tw;
@@ -633,9 +743,14 @@ static hipError_t fft_opt_in_lds(Instance *I)
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_dst<2, T>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     // the table builders: a double row of up to 2^(FFT_MAX_LOGM - 1) points, or a float row of 2^FFT_MAX_LOGM
     const int bbytes = (int)(sizeof(cx2<double>) * (size_t)fft_pad(1 << (FFT_MAX_LOGM - 1))) + 64;
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
-    if (e == hipSuccess && sizeof(T) == sizeof(float))
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    if (e == hipSuccess && sizeof(T) == sizeof(float)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    }
+    // the Neumann solve's transform kernels (dct_solve)
+    if (e == hipSuccess) e = dct_opt_in_lds<T>(bytes);
     done = e == hipSuccess;
     return e;
 }
@@ -708,6 +823,91 @@ int fft_solve(Instance *I, bool fp64)
         return SC_ERR_BAD_SIZE;
     }
     return fp64 ? fft_solve_t<double>(I) : fft_solve_t<float>(I);
+}
+
+// The Neumann solve of m same-size jobs (C m planes): boundary-mean reduction, rows (right-hand side from the jobs' arrays), columns
+// (DCT-II, divide, DCT-III), rows (DCT-III, scale 4 / (W H), + mean, into the jobs' out) -- the launches that read or write the
+// jobs' arrays go per PoissonJobs::MAX members (the table goes by value), the column launch over all planes at once.
+template <typename T>
+static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m)
+{
+    const int W = g.W, H = g.H, planes = g.C * m;
+    SC_HIP(I, fft_opt_in_lds<T>(I));
+    FftState &S = I->fft;
+    int rc;
+    FftDim *dw = nullptr, *dh = nullptr;
+    S.forked = false;
+    S.nreq = 0;
+    if ((rc = fft_build_dim<T>(I, dw, W, nullptr, 1))) return rc;
+    if ((rc = fft_build_dim<T>(I, dh, H, dw, 1))) { for (int k = 0; k < S.nreq; ++k) S.req[k]->n = 0; S.nreq = 0; return rc; }
+    if ((rc = fft_flush_builds<T>(I))) return rc;
+    const size_t plane = (size_t)W * H;
+    if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
+    if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
+    bool any_b = false;
+    for (int k = 0; k < m; ++k) any_b = any_b || jobs[k].b;
+    const int np = poisson_mean_parts(H);
+    double *parts = nullptr;
+    if (any_b) {
+        if ((rc = ensure(I, S.mean, sizeof(double) * (size_t)planes * np, false))) return rc;
+        parts = (double *)S.mean.p;
+        launch_poisson_mean(g, jobs, m, parts, I->stream);
+        SC_HIP(I, hipGetLastError());
+    }
+    stage_mark(I, 5);
+    if (S.pending) {
+        SC_HIP(I, hipStreamWaitEvent(I->stream, S.ev_built, 0));
+        S.pending = false;
+    }
+    const FftPlan<T> Pw = fft_plan_of<T>(*dw), Ph = fft_plan_of<T>(*dh);
+    const size_t ldsw = sizeof(cx2<T>) * (size_t)(fft_pad(Pw.M) + 1), ldsh = sizeof(cx2<T>) * (size_t)(fft_pad(Ph.M) + 1);
+    T *A = (T *)S.A.p, *B = (T *)S.B.p;
+    const double scale = 4.0 / ((double)W * (double)H);
+    const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as fft_solve_t: small planes are stored transposed, no transpose launches
+    // per launch of up to PoissonJobs::MAX members: fn(table, first plane, planes)
+    auto chunks = [&](auto fn) {
+        for (int i0 = 0; i0 < m; i0 += PoissonJobs::MAX) {
+            PoissonJobs t{};
+            const int cnt = std::min(m - i0, (int)PoissonJobs::MAX);
+            for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
+            fn(t, (size_t)g.C * i0, g.C * cnt);
+        }
+    };
+    const PoissonJobs none{};
+    T *rows_out = tiny ? B : A;              // the row transforms' plane; B[p][x][y] when stored transposed
+    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
+        if (lap) hipLaunchKernelGGL((k_dct<0, T, true>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, rows_out + p0 * plane, H, 1.0, tiny ? 1 : 0, (const double *)nullptr, 0);
+        else hipLaunchKernelGGL((k_dct<0, T, false>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, rows_out + p0 * plane, H, 1.0, tiny ? 1 : 0, (const double *)nullptr, 0);
+    });
+    if (tiny) {
+        hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, 1, (const double *)nullptr, 0);   // A[p][y][x]
+    } else {
+        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((W + 63) / 64, (H + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, H, W);      // B[p][x][y]
+        hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, 0, (const double *)nullptr, 0);
+        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((H + 63) / 64, (W + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, W, H);      // B[p][y][x]
+    }
+    const T *rows_in = tiny ? A : B;
+    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
+        hipLaunchKernelGGL((k_dct<2, T, false>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, rows_in + p0 * plane, (T *)nullptr, H, scale, 0,
+                           parts ? (const double *)(parts + p0 * np) : (const double *)nullptr, np);
+    });
+    SC_HIP(I, hipGetLastError());
+    stage_mark(I, 6);
+    I->info.method = SC_METHOD_FFT;
+    I->info.sweeps = 1;
+    I->info.converged = 1;
+    I->info.rel_residual = NAN;
+    I->info.sweep_launches = 3;
+    return SC_OK;
+}
+
+int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64)
+{
+    if (!fft_supported(g.W, g.H, fp64)) {
+        I->err = fp64 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: more than 4096 pixels per side" : "SC_POISSON_NEUMANN: more than 8192 pixels per side";
+        return SC_ERR_BAD_SIZE;
+    }
+    return fp64 ? dct_solve_t<double>(I, g, lap, jobs, m) : dct_solve_t<float>(I, g, lap, jobs, m);
 }
 
 } // namespace sc

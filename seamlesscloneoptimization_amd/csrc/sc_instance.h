@@ -59,7 +59,7 @@ struct DstState {
 // FFT direct solve (sc_fft.hip): per-direction chirp / transform tables and the two work planes.  The tables of a transform
 // length are built ON THE DEVICE (k_fft_build: both directions of a solve in one launch) and kept in a small LRU: a caller whose mask changes with every
 // frame meets new ROI sizes all the time, and alternating between a few sizes costs nothing.
-struct FftDim { int n = 0, logM = 0, r = 1; bool dbl = false; DevBuf chirp; unsigned long long used = 0; };   // M = r 2^logM (r = 1, 3, 5); chirp: chirp[n+1] | bhat[M] | tw[M] | tw2[2^logM] (complex float or double)
+struct FftDim { int n = 0, logM = 0, r = 1; bool dbl = false; int kind = 0; DevBuf chirp; unsigned long long used = 0; };   // M = r 2^logM (r = 1, 3, 5); kind 0 (DST-I, chirp of period 2(n+1)): chirp[n+1] | bhat[M] | tw[M] | tw2[2^logM] (complex float or double); kind 1 (DCT-II / III, period 2n): chirp[n+1] | half-sample twiddle[n+1] | bhat | tw | tw2
 struct FftFxy { int w = 0, h = 0; bool singular = false; DevBuf d, hst; hipEvent_t ev = nullptr; unsigned long long used = 0; };   // the reference's float tables fx[w] + fy[h]: device, pinned staging of its own, upload event
 struct FftState {
     enum { DIMS = 8, FXY = 4 };
@@ -68,6 +68,7 @@ struct FftState {
     unsigned long long tick = 0;
     DevBuf A, B;                           // work planes [C][h][w]
     DevBuf hst_all;                        // pinned staging of all FXY eigenvalue-table entries (one block; FftFxy::hst is unused since round 5)
+    DevBuf mean;                           // the Neumann solve's partial sums of boundary, double [planes][parts] (dct_solve)
     DevBuf tw64;                           // double twiddles of the build's own transform (float tables are built through a double FFT)
     hipEvent_t ev_fork = nullptr, ev_built = nullptr;   // the build runs on the instance's second stream
     bool pending = false;                  // ... and `stream` has not waited for ev_built yet
@@ -366,6 +367,9 @@ void rag_end(Instance *I);
 int dst_solve(Instance *I);                                           // sc_dst.hip: SC_METHOD_DST
 int fft_solve(Instance *I, bool fp64);                                // sc_fft.hip: SC_METHOD_FFT (fp64: SC_FLAG_FFT_FP64)
 bool fft_supported(int w, int h, bool fp64);
+// sc_fft.hip: the Neumann problem on caller arrays (SC_POISSON_NEUMANN): m same-size jobs as C m planes, straight from the jobs' arrays into
+// their out arrays (marks: 5 behind the boundary-mean reduction, 6 behind the last transform launch)
+int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64);
 bool wants_float_tables(const Instance *I);
 int effective_method(const Instance *I);                              // sc_solver.cpp: what SC_METHOD_AUTO resolves to for the fields bound to I
 int output_nodes(Instance *I, LmNodes &lm);  // sc_solver.cpp: the float-table correction the post-process of result(I) has to add (none: lm.CN == nullptr)

@@ -12,6 +12,7 @@
 // a register from the row before -- every guidance element is read once by one lane (plus one row and D elements of halo per
 // workgroup).
 #include "sc_common.h"
+#include "sc_wave.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
@@ -110,6 +111,30 @@ __global__ __launch_bounds__(PS_LANES) void k_poisson_out_group(PoissonGeo g, Po
     poisson_out_block<INTER>(g, t.j[blockIdx.z], U, g.C * (int)blockIdx.z);
 }
 
+// The Neumann solve's free constant (sc_fft.hip, dct_solve): sums of boundary in double.  Workgroup (i, c, k): rows [i H / np, (i + 1) H / np)
+// of channel c of member k, x inner; a lane's running sum, the wave's by shuffles, the four waves' through LDS -- one order of
+// additions per (W, H), whatever the batch, so a member's mean is its solo run's to the bit.  A job without boundary: zeros.
+__global__ __launch_bounds__(PS_LANES) void k_poisson_mean(PoissonGeo g, PoissonJobs t, double *__restrict__ parts)
+{
+    __shared__ double ws[PS_LANES / 64];
+    const PoissonJobDev &j = t.j[blockIdx.z];
+    const int c = (int)blockIdx.y, i = (int)blockIdx.x, np = (int)gridDim.x, tid = (int)threadIdx.x;
+    const int y0 = (int)((long long)i * g.H / np), y1 = (int)((long long)(i + 1) * g.H / np);
+    double s = 0.0;
+    if (j.b) {
+        const float *__restrict__ b = j.b + (long long)c * g.chs;
+        for (int y = y0; y < y1; ++y) {
+            const float *__restrict__ row = b + (long long)y * g.rs;
+#pragma unroll 4
+            for (int x = tid; x < g.W; x += PS_LANES) s += (double)row[(long long)x * g.cs];
+        }
+    }
+    s = wave_sum(s);
+    if ((tid & 63) == 0) ws[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) parts[((size_t)blockIdx.z * g.C + c) * np + i] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
 // ---------------------------------------------------------------- launchers
 static bool interleaved(const PoissonGeo &g) { return g.C > 1 && g.chs < g.cs; }
 static dim3 ps_grid(const PoissonGeo &g, int wcols, int members)
@@ -154,6 +179,17 @@ void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev
             if (lap) hipLaunchKernelGGL((k_poisson_pre_group<false, true>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
             else hipLaunchKernelGGL((k_poisson_pre_group<false, false>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
         }
+    });
+}
+
+int poisson_mean_parts(int H) { return std::min(H, 256); }
+
+void launch_poisson_mean(const PoissonGeo &g, const PoissonJobDev *jobs, int n, double *parts, hipStream_t s)
+{
+    const int np = poisson_mean_parts(g.H);
+    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+        hipLaunchKernelGGL(k_poisson_mean, dim3((unsigned)np, (unsigned)g.C, (unsigned)cnt), dim3(PS_LANES), 0, s, g, t,
+                           parts + (size_t)g.C * i0 * np);
     });
 }
 

@@ -7,6 +7,9 @@
 // (SC_FLAG_EXACT_TABLES: no float-table correction, which belongs to the reference's 8-bit answer), all fields float32 (the float16
 // right-hand side and level 1 and the 16-bit field between level-0 launches assume 8-bit data), update_tol = the call's tol.  The
 // instance's stored options and solve state (CallScope) are restored on every way out.
+//
+// SC_POISSON_NEUMANN: no fields, no pre-process or output launch -- per chunk dct_solve (sc_fft.hip) works straight between the jobs'
+// arrays: the boundary-mean reduction, then the three transform launches of the DCT solve.
 #include "sc_instance.h"
 #include <algorithm>
 #include <cmath>
@@ -24,15 +27,22 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
     if (!why) why = &dummy;
     *why = "";
     if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
-    if (p->kind != SC_POISSON_GUIDANCE && p->kind != SC_POISSON_LAPLACIAN) {
-        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN";
+    const bool neumann = (p->kind & SC_POISSON_NEUMANN) != 0;
+    const int base = p->kind & ~SC_POISSON_NEUMANN;
+    if (base != SC_POISSON_GUIDANCE && base != SC_POISSON_LAPLACIAN) {
+        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN";
         return SC_ERR_BAD_ARG;
     }
     if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
     if (l->channels < 1 || l->channels > 4) { *why = "channels must be 1..4"; return SC_ERR_BAD_ARG; }
     if (l->col_stride <= 0 || l->row_stride <= 0 || l->channel_stride <= 0) { *why = "strides must be positive"; return SC_ERR_BAD_ARG; }
-    if (l->cols < 3 || l->rows < 3) { *why = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
-    if (l->cols > 65536 || l->rows > 65536) { *why = "the image must be at most 65536 x 65536"; return SC_ERR_BAD_SIZE; }
+    if (neumann) {
+        if (l->cols < 2 || l->rows < 2) { *why = "SC_POISSON_NEUMANN: the image must be at least 2 x 2"; return SC_ERR_BAD_SIZE; }
+        if (!fft_supported(l->cols, l->rows, false)) { *why = "SC_POISSON_NEUMANN: the image must be at most 8192 x 8192"; return SC_ERR_BAD_SIZE; }
+    } else {
+        if (l->cols < 3 || l->rows < 3) { *why = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
+        if (l->cols > 65536 || l->rows > 65536) { *why = "the image must be at most 65536 x 65536"; return SC_ERR_BAD_SIZE; }
+    }
     // the strides must nest: sorted by size, each exceeds the span of the smaller ones (dimensions of extent 1 take no part)
     struct Dim { unsigned __int128 s, n; } d[3] = { { (unsigned __int128)l->col_stride, (unsigned)l->cols },
                                                      { (unsigned __int128)l->row_stride, (unsigned)l->rows },
@@ -56,10 +66,12 @@ static size_t poisson_span(const sc_poisson_layout *l)
 
 static bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-// a job's own code: the pointers its kind needs, 4-byte aligned
+// a job's own code: the pointers its kind needs, 4-byte aligned (a Neumann job may come without boundary: mean zero)
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
 {
-    const float *need[4] = { b, out, kind == SC_POISSON_GUIDANCE ? gx : lap, kind == SC_POISSON_GUIDANCE ? gy : lap };
+    const bool guidance = (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_GUIDANCE;
+    if ((kind & SC_POISSON_NEUMANN) && !b) b = out;
+    const float *need[4] = { b, out, guidance ? gx : lap, guidance ? gy : lap };
     for (const float *q : need) {
         if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
         if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
@@ -112,6 +124,32 @@ int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     return solve_rc;
 }
 
+// a Neumann call's code on this instance: the methods that serve it, the side limit of its transforms' precision
+int neumann_instance_check(Instance *I, const sc_poisson_layout *l)
+{
+    const int method = I->opts.method;
+    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
+        I->err = "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)";
+        return SC_ERR_BAD_ARG;
+    }
+    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(l->cols, l->rows, true)) {
+        I->err = "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096";
+        return SC_ERR_BAD_SIZE;
+    }
+    return SC_OK;
+}
+
+// The same for a Neumann call: no fields; marks 5 (reduction done) and 6 (transforms done) come from dct_solve, 7 = 6 (the output is
+// the last transform launch's store).
+int neumann_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m)
+{
+    stage_mark(I, 0);
+    const int rc = dct_solve(I, g, (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0);
+    if (rc) return rc;
+    stage_mark(I, 7);
+    return SC_OK;
+}
+
 void add_timing(Instance *I, float t[4])
 {
     t[0] += ev_ms(I->ev[0], I->ev[5]);
@@ -151,7 +189,7 @@ int poisson_run(Instance *I, const sc_poisson_params *p, const sc_poisson_layout
             const sc_poisson_job &j = jobs[valid[i0 + k]];
             dj[k] = PoissonJobDev{ j.gx, j.gy, j.lap, j.boundary, j.out };
         }
-        int rc = poisson_chunk(I, p->kind, g, dj.data(), m);
+        int rc = (p->kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p->kind, g, dj.data(), m) : poisson_chunk(I, p->kind, g, dj.data(), m);
         if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
             if (timed) {
                 SC_HIP(I, hipStreamSynchronize(I->stream));
@@ -187,6 +225,7 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
     if (rc) return rc;
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
+    if ((p->kind & SC_POISSON_NEUMANN) && (rc = neumann_instance_check(I, l))) return rc;
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
     std::vector<int> valid;
@@ -219,20 +258,22 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     if (rc) return rc;
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
+    if ((p->kind & SC_POISSON_NEUMANN) && (rc = neumann_instance_check(I, l))) return rc;
     if ((rc = poisson_job_validate(p->kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
     // one device block: the inputs' spans, boundary's, and out's unless out is boundary (in place); each at a 256-byte boundary
     const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
-    const bool guidance = p->kind == SC_POISSON_GUIDANCE, in_place = out == boundary;
-    const int slots = (guidance ? 2 : 1) + 1 + (in_place ? 0 : 1);
+    // (a Neumann call without boundary: no slot, no upload)
+    const bool guidance = (p->kind & ~SC_POISSON_NEUMANN) == SC_POISSON_GUIDANCE, in_place = out == boundary;
+    const int slots = (guidance ? 2 : 1) + (boundary ? 1 : 0) + (in_place ? 0 : 1);
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     uint8_t *d = (uint8_t *)I->d_pois.p;
     float *d_in0 = (float *)d, *d_in1 = guidance ? (float *)(d + slot) : nullptr;
-    float *d_b = (float *)(d + slot * (guidance ? 2 : 1));
+    float *d_b = boundary ? (float *)(d + slot * (guidance ? 2 : 1)) : nullptr;
     float *d_out = in_place ? d_b : (float *)(d + slot * (slots - 1));
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
     if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
-    if ((rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
+    if (boundary && (rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
     sc_poisson_job job{};
     job.gx = guidance ? d_in0 : nullptr; job.gy = d_in1; job.lap = guidance ? nullptr : d_in0;
     job.boundary = d_b; job.out = d_out;

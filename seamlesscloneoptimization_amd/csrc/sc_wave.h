@@ -20,6 +20,14 @@ __device__ __forceinline__ float wave_from_right(float v)  // lane i <- lane i+1
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
 }
 
+// sum of v over the 64 lanes of a wave, in every lane: a butterfly of shuffles, the same order of additions whatever the launch
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 // Workgroups of a launch are dealt round-robin over the 8 XCDs (observed on MI355X, not promised by
 // HIP: used for speed only), so linear workgroup i runs on the XCD that also runs i + 8, i + 16, ...
 // Each XCD has its own 4 MiB L2.  xcd_tile() turns the linear id into a logical tile number such that

@@ -240,29 +240,32 @@ def poisson_tol(boundary, lap_scale=0.0):
     return max(1e-3, 4e-7 * scale * float(np.sqrt(b.shape[0] * b.shape[1])))
 
 
-def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None, **solver):
+def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None, neumann=False, **solver):
     """Solve the Poisson equation on a float32 image of shape H x W or H x W x C (C 1..4) and return a NEW array: lap(u) = div (gx, gy)
     (backward differences of the guidance field) or = laplacian, with u = boundary on the one-pixel frame.  boundary's interior is
     the initial guess of the iterative methods.  tol: the multigrid stop rule in the data's units (None: poisson_tol(boundary), a
     stop float32 can reach; <= 0: the library's 1e-3); keyword arguments are solver options (method, max_sweeps, flags, ...).  The
-    exact 5-point system's answer, in float32, nothing clamped."""
-    kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian)
+    exact 5-point system's answer, in float32, nothing clamped.
+    neumann: no boundary values -- every pixel is an unknown and the field is reflected at the border (a direct DCT solve; methods
+    auto and fft).  The answer's mean per channel is boundary's; boundary may be None (mean zero).  With a laplacian, its mean is
+    projected out."""
+    kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian, neumann=neumann)
     if tol is None:
-        tol = poisson_tol(b)
+        tol = 0.0 if neumann else poisson_tol(b)
     inst = capi.Instance(gpu_id)
     try:
         if solver:
             inst.set_solver(**solver)
-        return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol)
+        return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol, neumann=neumann)
     finally:
         inst.destroy()
 
 
-def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, **solver):
+def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, neumann=False, **solver):
     """poisson_solve over a list of same-shape problems through ONE device-resident call (sc_hip_poisson_device): the inputs go to the
     device in one copy and the results come back in one; the problems are solved as one field of n x C planes (chunks of at most
     SC_POISSON_MAX_PLANES planes).  tol: as poisson_solve's (None: the largest poisson_tol of the batch).  Returns a list of NEW
-    arrays."""
+    arrays.  neumann: as poisson_solve's; boundaries may then hold None entries (mean zero)."""
     bs = list(boundaries)
     if not bs:
         return []
@@ -273,20 +276,21 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
     for f in fields:
         if len(f) != n:
             raise ValueError("one guidance field (or laplacian) per boundary")
-    checked = []
+    checked, has_b = [], []
     for k in range(n):
         if gxs is not None:
-            kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k])
+            kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k], neumann=neumann)
             ins = [gx, gy]
         else:
-            kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k])
+            kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k], neumann=neumann)
             ins = [lap]
-        if b.shape != bs[0].shape:
+        if ins[0].shape != fields[0][0].shape:
             raise ValueError("every problem of a batch must have one shape")
-        checked.append([np.ascontiguousarray(a) for a in ins + [b]])
-    shape = bs[0].shape
+        has_b.append(b is not None)
+        checked.append([np.ascontiguousarray(a) for a in ins + [b if b is not None else np.zeros_like(ins[0])]])
+    shape = fields[0][0].shape
     if tol is None:
-        tol = max(poisson_tol(a[-1]) for a in checked)
+        tol = 0.0 if neumann else max(poisson_tol(a[-1]) for a in checked)
     nb = checked[0][0].nbytes
     slot = (nb + 255) // 256 * 256
     per = len(checked[0])
@@ -307,11 +311,11 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
         jobs = capi.Instance.make_poisson_jobs(n)
         for k, j in enumerate(jobs):
             base = d + k * per * slot
-            if kind == capi.SC_POISSON_GUIDANCE:
+            if (kind & ~capi.SC_POISSON_NEUMANN) == capi.SC_POISSON_GUIDANCE:
                 j.gx, j.gy = base, base + slot
             else:
                 j.lap = base
-            j.boundary = base + (per - 1) * slot
+            j.boundary = base + (per - 1) * slot if has_b[k] else None
             j.out = d + in_bytes + k * slot
         inst.poisson_device(capi.PoissonParams(kind, float(tol)), layout, jobs)
         out = inst.from_device(d + in_bytes, (slot * n // 4,), np.float32)

@@ -1,0 +1,148 @@
+"""CPU checks of the Neumann option of the Poisson solver (SC_POISSON_NEUMANN): the test side's restatement (tests/neumann_np.py)
+against the reflecting operator applied directly, the host-only validation of sc_hip_poisson_check with the bit, the Python
+wrappers' argument checks (before any device is touched).  The sanitizer builds' new validation cases (csrc/sanitize_main.cpp) run
+under tests/test_host.py's `make sanitize` test."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi, seamless_clone
+
+import neumann_np
+from test_poisson_host import VALID
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEU = capi.SC_POISSON_NEUMANN
+KINDS = [capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN]
+
+
+@pytest.mark.parametrize("H,W,C", [(2, 2, 1), (17, 2, 1), (29, 37, 2), (50, 64, 4)])      # (W, H) = (2,2), (2,17), (37,29), (64,50)
+def test_the_restatement_solves_the_reflecting_system(H, W, C):
+    """operator(answer) = lap - mean(lap) to 1e-10 relative, the mean anchored; an image comes back from its forward differences."""
+    rng = np.random.default_rng(H * 100 + W)
+    lap = rng.normal(0, 20, (H, W, C))
+    mean = rng.uniform(-100, 100, C)
+    u = neumann_np.solve_exact(lap, mean)
+    want = lap - lap.mean(axis=(0, 1))
+    assert np.abs(neumann_np.operator(u) - want).max() <= 1e-10 * np.abs(want).max()
+    assert np.abs(u.mean(axis=(0, 1)) - mean).max() <= 1e-10 * max(1.0, np.abs(u).max())
+    assert np.abs(neumann_np.solve_exact(lap).mean(axis=(0, 1))).max() <= 1e-10 * np.abs(u).max()
+    img = rng.uniform(-50, 300, (H, W, C))
+    R = np.abs(img).max()
+    gx, gy = neumann_np.forward_differences(img)
+    gx[:, -1] = 1e9          # never read
+    gy[-1] = -1e9
+    a = gx.copy(); a[:, -1] = 0
+    b = np.zeros_like(gx); b[:, 1:] = gx[:, :-1]
+    c = gy.copy(); c[-1] = 0
+    d = np.zeros_like(gy); d[1:] = gy[:-1]
+    back = neumann_np.solve_exact((a - b) + (c - d), neumann_np.mean_of(img))
+    assert np.abs(back - img).max() <= 1e-10 * R
+    # the float32 form (the library's) is within float32 rounding of it
+    g32x, g32y = neumann_np.forward_differences(img.astype(np.float32))
+    u32 = neumann_np.solve_guidance(g32x, g32y, img.astype(np.float32))
+    assert np.abs(u32 - img).max() <= 1e-4 * R
+
+
+def test_the_divergence_is_float32_in_the_documented_order():
+    rng = np.random.default_rng(3)
+    gx = rng.normal(0, 10, (9, 11, 1)).astype(np.float32)
+    gy = rng.normal(0, 10, (9, 11, 1)).astype(np.float32)
+    lap = neumann_np.divergence(gx, gy)
+    assert lap.dtype == np.float32
+    assert lap[4, 5, 0] == np.float32(np.float32(gx[4, 5, 0] - gx[4, 4, 0]) + np.float32(gy[4, 5, 0] - gy[3, 5, 0]))
+    assert lap[0, 0, 0] == np.float32(gx[0, 0, 0] + gy[0, 0, 0])                          # b = d = 0
+    assert lap[8, 10, 0] == np.float32(np.float32(0 - gx[8, 9, 0]) + np.float32(0 - gy[7, 10, 0]))      # a = c = 0
+    assert abs(float(lap.astype(np.float64).sum())) <= 1e-3 * float(np.abs(lap).sum())  # a divergence sums to zero up to rounding
+
+
+def _check(kind, tol=0.0, **layout):
+    return capi.poisson_check(kind, tol, **layout)
+
+
+def _planar(cols, rows, channels=1):
+    return dict(cols=cols, rows=rows, channels=channels, col_stride=1, row_stride=cols, channel_stride=cols * rows)
+
+
+@pytest.mark.parametrize("name", list(VALID))
+@pytest.mark.parametrize("kind", KINDS)
+def test_poisson_check_accepts_the_valid_layouts_with_the_bit(name, kind):
+    assert _check(kind | NEU, **VALID[name]) == capi.SC_OK
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_poisson_check_sizes_with_the_bit(kind):
+    assert _check(kind | NEU, **_planar(2, 2)) == capi.SC_OK
+    assert _check(kind | NEU, **_planar(1, 40)) == capi.SC_ERR_BAD_SIZE
+    assert _check(kind | NEU, **_planar(40, 1)) == capi.SC_ERR_BAD_SIZE
+    assert _check(kind | NEU, **_planar(8192, 8, 3)) == capi.SC_OK
+    assert _check(kind | NEU, **_planar(8, 8192, 3)) == capi.SC_OK
+    assert _check(kind | NEU, **_planar(8193, 8)) == capi.SC_ERR_BAD_SIZE
+    assert _check(kind | NEU, **_planar(8, 8193)) == capi.SC_ERR_BAD_SIZE
+    # without the bit nothing changes: 2 columns are too few, 8193 is fine
+    assert _check(kind, **_planar(2, 480)) == capi.SC_ERR_BAD_SIZE
+    assert _check(kind, **_planar(8193, 8)) == capi.SC_OK
+
+
+@pytest.mark.parametrize("kind", [NEU, NEU | 3, (1 << 9) | 1, NEU | (1 << 9) | 1, 0, 3, -1])
+def test_poisson_check_rejects_bad_kinds(kind):
+    assert _check(kind, **VALID["HWC C=3"]) == capi.SC_ERR_BAD_ARG
+
+
+def test_poisson_check_still_rejects_bad_tol_and_strides_with_the_bit():
+    assert _check(capi.SC_POISSON_GUIDANCE | NEU, float("nan"), **VALID["HWC C=3"]) == capi.SC_ERR_BAD_ARG
+    bad = dict(cols=640, rows=480, channels=3, col_stride=2, row_stride=3 * 640, channel_stride=1)
+    assert _check(capi.SC_POISSON_LAPLACIAN | NEU, **bad) == capi.SC_ERR_BAD_ARG
+
+
+def _no_device(monkeypatch):
+    """Any attempt to create an instance fails the test: the wrappers must refuse their arguments first."""
+    def boom(*a, **k):
+        raise AssertionError("a device was touched before the arguments were checked")
+    monkeypatch.setattr(capi.Instance, "__init__", boom)
+
+
+@pytest.mark.parametrize("case", ["shape", "dtype", "boundary None without neumann", "neither", "both kinds", "boundary shape", "channels"])
+def test_neumann_wrappers_reject_bad_arguments_before_a_device(monkeypatch, case):
+    _no_device(monkeypatch)
+    g = np.zeros((20, 30, 3), np.float32)
+    b, neumann = None, True
+    kw = {"shape": dict(gx=np.zeros((20, 31, 3), np.float32), gy=g),
+          "dtype": dict(gx=g.astype(np.float64), gy=g),
+          "boundary None without neumann": dict(gx=g, gy=g),
+          "neither": dict(),
+          "both kinds": dict(gx=g, gy=g, laplacian=g),
+          "boundary shape": dict(laplacian=g),
+          "channels": dict(laplacian=np.zeros((20, 30, 5), np.float32))}[case]
+    if case == "boundary None without neumann":
+        neumann = False
+    if case == "boundary shape":
+        b = np.zeros((20, 30), np.float32)
+    with pytest.raises((ValueError, TypeError)):
+        seamless_clone.poisson_solve(b, neumann=neumann, **kw)
+    kwb = {("gxs" if k == "gx" else "gys" if k == "gy" else "laplacians"): [v, v] for k, v in kw.items()}
+    with pytest.raises((ValueError, TypeError)):
+        seamless_clone.poisson_solve_batch([b, b], neumann=neumann, **kwb)
+
+
+def test_poisson_arrays_carries_the_bit_and_takes_no_boundary():
+    g = np.zeros((20, 30, 3), np.float32)
+    kind, b, gx, gy, lap, out = capi.poisson_arrays(None, g, g, neumann=True)
+    assert kind == capi.SC_POISSON_GUIDANCE | NEU and b is None and gx is g
+    kind, b, _, _, lap, _ = capi.poisson_arrays(g, lap=g, neumann=True)
+    assert kind == capi.SC_POISSON_LAPLACIAN | NEU and b is g and lap is g
+    assert capi.poisson_arrays(g, g, g)[0] == capi.SC_POISSON_GUIDANCE           # the default: as before
+
+
+def test_the_header_defines_the_bit_and_keeps_the_params_layout(tmp_path):
+    src = tmp_path / "bit.c"
+    src.write_text('#include <stdio.h>\n#include "seamlessclone_hip.h"\nint main(void) { printf("%d %zu\\n", SC_POISSON_NEUMANN, '
+                   'sizeof(sc_poisson_params)); return 0; }\n')
+    exe = tmp_path / "bit"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    bit, size = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+    assert int(bit) == NEU == 256 and int(size) == 8
