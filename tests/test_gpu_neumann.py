@@ -10,7 +10,9 @@ tools/neumann_probe.py measured over SIZES and C = 1 .. 4 on this file's images 
 profiles/neumann_probe.json), rounded up to one digit: the error is a sum of ~n log n roundings amplified by 1 / lambda_min in the
 lowest modes along the long side, not a worst case, and it varies fourfold from seed to seed at that size (1.6e-3 .. 6.3e-3 R over
 four images; every other size stays below 1.7e-3 R) -- the margin is for other seeds and runtime versions.  DESIGN.md section 4 says
-which step loses the digits.  The mean: 1e-6 R per channel under both."""
+which step loses the digits.  The mean: 1e-6 R per channel under both.  Beside these, the reconstruction test holds the residual
+ratio and the error to the float32 restatement on the same input (tests/neumann_bounds.py): the 3e-2 R above lets a wrong
+coefficient through."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,6 +24,7 @@ from seamlesscloneoptimization_amd import capi  # noqa: E402
 
 import neumann_np  # noqa: E402
 import poisson_np  # noqa: E402
+from neumann_bounds import Yardstick  # noqa: E402
 
 NEU = capi.SC_POISSON_NEUMANN
 METHODS = {
@@ -70,6 +73,7 @@ def test_reconstruction_and_random_guidance_against_the_restatement(inst, W, H):
             R = float(np.abs(want).max())
             mean = neumann_np.mean_of(bb) if bb is not None else np.zeros(C)
             lap = neumann_np.divergence(ax, ay)
+            yard = Yardstick(lap, None if bb is None else mean)          # RES and ERR against the float32 restatement (neumann_bounds.py)
             for name in methods_for(W, H):
                 configure(inst, *METHODS[name])
                 out = inst.poisson(bb, gx=ax, gy=ay, neumann=True)
@@ -80,6 +84,9 @@ def test_reconstruction_and_random_guidance_against_the_restatement(inst, W, H):
                 print(f"{W}x{H}x{C} {what} {name}: err {err / R:.3g} R, mean {merr / R:.3g} R")
                 assert err <= BOUND[name] * R, (what, name, W, H, C, err / R)
                 assert merr <= MEAN_BOUND * R, (what, name, W, H, C, merr / R)
+                bad, e, r = yard.check(out, name == "fft64", name != "fft64" or what == "reconstruction")
+                print(f"    RES {r:.3g} ERR {e:.3g} / solve_f32 RES {yard.res32:.3g} ERR {yard.err32:.3g}")
+                assert not bad, (what, name, W, H, C, bad)
                 # the LAPLACIAN form fed the divergence numpy computes in the documented order: the same bits
                 out_l = inst.poisson(bb, lap=lap, neumann=True)
                 assert np.array_equal(out_l, out), (what, name, W, H, C)
