@@ -492,6 +492,56 @@ SC_API int sc_hip_poisson_device(void *instance, const sc_poisson_params *p, con
  * does not use may be NULL. */
 SC_API int sc_hip_poisson(void *instance, const sc_poisson_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                           const float *lap, const float *boundary, float *out);
+/* ---- screened Poisson solves: the same solver with a data term -------------------------------------------------------------------
+ * The problem: per channel,
+ *     minimise   lambda sum (u - d)^2 + sum |grad u - g|^2       i.e.       (A - lambda) u = div g - lambda d,      lambda > 0,
+ * A the 5-point operator of sc_hip_poisson under the same two boundary kinds: the solver of gradient-domain filtering (sharpen or
+ * flatten gradients while staying close to the input), deblocking and reconstruction with a fidelity term.
+ * kind: as sc_poisson_params.kind.  SC_POISSON_GUIDANCE forms lap = div g by the documented formula of the boundary kind, in the
+ * same float32 order; SC_POISSON_LAPLACIAN takes it as given.  The right-hand side is lap - lambda * d in float32: one multiply
+ * (lambda * d, rounded), then one subtract -- never a fused multiply-add.
+ * Dirichlet (no SC_POISSON_NEUMANN): the unknowns are the interior, u = boundary on the frame.  data and lap are read on the interior
+ * only, boundary on its frame only (its interior is never read: there is no iteration to start).  The frame of out is boundary's,
+ * bit for bit.  boundary may be the data array itself.
+ * SC_POISSON_NEUMANN: every pixel is an unknown, the stencil reflects at the border; data and lap (or the guidance) are read at every
+ * pixel; boundary is not used and may be NULL.  The screened system is regular: there is no free constant, no mean is asked for,
+ * lap's DC coefficient counts like any other (it is divided by -lambda).
+ * Solved directly, always: DST-I transforms under a frame, DCT-II / DCT-III under SC_POISSON_NEUMANN (the chirp convolutions of
+ * SC_METHOD_FFT), the coefficients divided by eigenvalue - lambda computed in double; float32 transforms, or double with
+ * SC_FLAG_FFT_FP64.  Methods: SC_METHOD_AUTO (resolves to SC_METHOD_FFT at every size and batch size) and SC_METHOD_FFT; any other
+ * method: SC_ERR_BAD_ARG, nothing written (the multigrid and relaxation kernels hold the unscreened diagonal).  Of the instance's other
+ * options only SC_FLAG_FFT_FP64 matters.  Sizes: SC_POISSON_NEUMANN cols, rows in 2..8192 (4096 with SC_FLAG_FFT_FP64); under a
+ * frame cols, rows >= 3 and at most 8192 unknowns per side, i.e. cols - 2, rows - 2 <= 8192 (4096 with SC_FLAG_FFT_FP64);
+ * SC_ERR_BAD_SIZE beyond (sc_hip_screened_check, which knows no instance, reports the float32 limits).
+ * Layout, batches (one field of n x channels planes, floor(192 / channels) jobs per chunk), what a call writes, the return value and
+ * the per-job codes: sc_hip_poisson_device's.  A member equals its solo run bit for bit, always.  Aliasing: a job's out may equal
+ * its own data or boundary; it must not overlap any other array of the call.  Inputs may be shared.
+ * Codes: SC_ERR_BAD_ARG for a lambda that is not finite or is <= 0, a bad kind, channels outside 1..4, a stride <= 0 or strides that
+ * do not nest; SC_ERR_BAD_SIZE as above.  Per job (the job is skipped, the others run): SC_ERR_BAD_ARG for a NULL or misaligned
+ * pointer the kind needs -- data always, boundary under a frame.
+ * sc_run_info: method SC_METHOD_FFT, sweeps 1, converged 1, W x H = the image; stage times when bSync is set and for the host call
+ * (under a frame ms_pre = the pre-process, ms_post = the output launch; SC_POISSON_NEUMANN: both ~ 0, the transform launches read
+ * and write the caller's arrays).  The instance's stored options are unchanged by the call. */
+typedef struct sc_screened_params {
+    int kind;                /* as sc_poisson_params.kind, SC_POISSON_NEUMANN included */
+    float lambda;            /* the data term's weight: finite, > 0 */
+} sc_screened_params;
+typedef struct sc_screened_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE                                                           */
+    const float *lap;        /* SC_POISSON_LAPLACIAN                                                          */
+    const float *data;       /* d: read on the interior (SC_POISSON_NEUMANN: at every pixel)                  */
+    const float *boundary;   /* its frame: the Dirichlet values, its interior is never read (SC_POISSON_NEUMANN: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary          */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job                                            */
+} sc_screened_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_screened_check(const sc_screened_params *p, const sc_poisson_layout *l);
+/* Device pointers.  Asynchronous unless bSync (sync the instance before reading out); bSync also records the stage times. */
+SC_API int sc_hip_screened_device(void *instance, const sc_screened_params *p, const sc_poisson_layout *l, sc_screened_job *jobs, int n,
+                                  bool bSync);
+/* One problem on host arrays, as sc_hip_poisson: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_screened(void *instance, const sc_screened_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                           const float *lap, const float *data, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

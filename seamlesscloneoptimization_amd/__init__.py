@@ -5,8 +5,9 @@ binding (capi), the reference-shaped Python class (seamless_clone), OpenCV-yml/B
 and the vs.py-equivalent checker (compare).  Nothing here imports torch or the CPU oracle.
 """
 from . import capi, compare, ymlio  # noqa: F401
-from .seamless_clone import (SeamlessClone, colorChange, edit_batch, illuminationChange, poisson_solve,  # noqa: F401
-                             poisson_solve_batch, seamlessClone, textureFlattening)
+from .seamless_clone import (SeamlessClone, colorChange, edit_batch, gradient_filter, illuminationChange,  # noqa: F401
+                             poisson_solve, poisson_solve_batch, screened_solve, screened_solve_batch, seamlessClone,
+                             textureFlattening)
 
 __all__ = ["capi", "compare", "ymlio", "SeamlessClone", "seamlessClone", "colorChange", "illuminationChange", "textureFlattening",
-           "edit_batch", "poisson_solve", "poisson_solve_batch"]
+           "edit_batch", "poisson_solve", "poisson_solve_batch", "screened_solve", "screened_solve_batch", "gradient_filter"]

@@ -140,6 +140,16 @@ class PoissonJob(C.Structure):
                 ("rc", C.c_int)]
 
 
+# screened Poisson solves (sc_hip_screened*): Instance.screened / screened_device
+class ScreenedParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("lam", C.c_float)]        # (the C field is `lambda`)
+
+
+class ScreenedJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("boundary", C.c_void_p),
+                ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -308,6 +318,13 @@ def load():
     L.sc_hip_poisson_device.restype = C.c_int
     L.sc_hip_poisson.argtypes = [C.c_void_p, C.POINTER(PoissonParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 5
     L.sc_hip_poisson.restype = C.c_int
+    L.sc_hip_screened_check.argtypes = [C.POINTER(ScreenedParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_screened_check.restype = C.c_int
+    L.sc_hip_screened_device.argtypes = [C.c_void_p, C.POINTER(ScreenedParams), C.POINTER(PoissonLayout), C.POINTER(ScreenedJob), C.c_int,
+                                         C.c_bool]
+    L.sc_hip_screened_device.restype = C.c_int
+    L.sc_hip_screened.argtypes = [C.c_void_p, C.POINTER(ScreenedParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 6
+    L.sc_hip_screened.restype = C.c_int
     _lib = L
     return L
 
@@ -382,6 +399,36 @@ def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False
     if out is not None and not out.flags.writeable:
         raise ValueError("out must be writeable")
     return kind, boundary, gx, gy, lap, out
+
+
+def screened_check(kind: int = SC_POISSON_GUIDANCE, lam: float = 1.0, layout: "PoissonLayout | None" = None, *, cols=None, rows=None,
+                   channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_screened_check: SC_OK or the code a screened call with this kind, lambda and layout returns before it runs
+    anything.  The layout as a PoissonLayout or as keyword fields."""
+    if layout is None:
+        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
+    return int(load().sc_hip_screened_check(C.byref(ScreenedParams(int(kind), float(lam))), C.byref(layout)))
+
+
+def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False):
+    """Checks a screened problem's numpy arrays and lambda before any device is touched: (kind, data, gx, gy, lap, boundary, out), every
+    array float32 and of data's shape (poisson_arrays' rules).  A Dirichlet problem (neumann=False) needs boundary; a Neumann one
+    ignores it."""
+    if data is None:
+        raise ValueError("a screened solve needs its data term")
+    if lam is None or not np.isfinite(lam) or not lam > 0:
+        raise ValueError("lam must be finite and > 0")
+    if neumann:
+        boundary = None
+    elif boundary is None:
+        raise ValueError("a Dirichlet screened solve needs boundary (neumann=True: none)")
+    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann)
+    if boundary is not None:
+        if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
+            raise TypeError("boundary must be a float32 numpy array")
+        if boundary.shape != data.shape:
+            raise ValueError(f"boundary has shape {boundary.shape}, the problem {data.shape}")
+    return kind, data, gx, gy, lap, boundary, out
 
 
 class Instance:
@@ -575,6 +622,46 @@ class Instance:
         if allow_job_errors and rc != SC_ERR_HIP:
             return rc
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
+
+    # ---- screened Poisson solves on float32 arrays
+    def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None):
+        """sc_hip_screened on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise lam sum (u - data)^2 +
+        sum |grad u - (gx, gy)|^2 (or with the divergence given as lap), with u = boundary on the frame, or, neumann, reflected at the
+        border (boundary then unused).  out: an array of data's shape to write (may be data or boundary), default a new one.
+        Returns out."""
+        kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann)
+        if out is None:
+            out = np.empty_like(data)
+        given = [a for a in (data, gx, gy, lap, boundary, out) if a is not None]
+        lays = [poisson_layout_of(a) for a in given]
+        target = out
+        if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
+            # one layout per call: contiguous copies, a new contiguous out copied back below
+            data, gx, gy, lap, boundary = (None if a is None else np.ascontiguousarray(a) for a in (data, gx, gy, lap, boundary))
+            out = np.empty(data.shape, np.float32)
+        layout = poisson_layout_of(out)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.L.sc_hip_screened(self.h, C.byref(ScreenedParams(kind, float(lam))), C.byref(layout), ptr(gx), ptr(gy), ptr(lap),
+                                    ptr(data), ptr(boundary), ptr(out))
+        self._check(rc)
+        if out is not target:
+            target[...] = out
+        return target
+
+    @staticmethod
+    def make_screened_jobs(n: int):
+        return (ScreenedJob * n)()
+
+    def screened_device(self, params: ScreenedParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_screened_device: jobs is a ScreenedJob array (make_screened_jobs) of device pointers, one layout for all.  sync: bSync
+        (stage times) and a wait for the stream.  Per-job codes in jobs[i].rc; failures raise unless allow_job_errors (then the worst
+        code is returned)."""
+        rc = self.L.sc_hip_screened_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc)
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -12,6 +12,7 @@
 //   4. the same for batches of whole-image edits (sc_hip_pool_edit): chunks of one image size, every job exactly once, codes back,
 //      and a chunk whose batch call fails with SC_ERR_HIP (after writing SC_OK into its members) reported as failed, job and pool.
 //   5. sc_hip_poisson_check over valid and invalid layouts (the overlap test's 128-bit arithmetic at extreme strides included).
+//   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
@@ -258,6 +259,37 @@ int main()
         }
         sc_poisson_params p{ SC_POISSON_GUIDANCE, 0.f };
         if (sc_hip_poisson_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_poisson_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("poisson_check (null)");
+    }
+    // 6: the screened call's validation (lambda, the kinds, the direct solves' side limits of each boundary kind)
+    {
+        struct Case { int kind; float lambda; int w, h, c; long long cs, rs, chs; int want; };
+        const float nan = std::nanf(""), inf = HUGE_VALF;
+        const int N = SC_POISSON_NEUMANN, G = SC_POISSON_GUIDANCE, Lp = SC_POISSON_LAPLACIAN;
+        const Case cases[] = {
+            { G, 0.5f, 640, 480, 3, 3, 1920, 1, SC_OK },
+            { Lp | N, 1e-3f, 640, 480, 3, 1, 640, 640 * 480, SC_OK },
+            { G, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G | N, -1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G, nan, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp, inf, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { 0, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { N, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G, 1.f, 640, 480, 3, 2, 1920, 1, SC_ERR_BAD_ARG },          // x and c overlap
+            { G | N, 1.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { G | N, 1.f, 8192, 2, 1, 1, 8192, 16384, SC_OK },
+            { G | N, 1.f, 8193, 2, 1, 1, 8193, 16386, SC_ERR_BAD_SIZE },
+            { G, 1.f, 2, 8, 1, 1, 2, 16, SC_ERR_BAD_SIZE },
+            { G, 1.f, 3, 3, 1, 1, 3, 9, SC_OK },
+            { G, 1.f, 8194, 3, 1, 1, 8194, 3 * 8194, SC_OK },               // 8192 unknowns per side
+            { Lp, 1.f, 3, 8195, 1, 1, 3, 3 * 8195, SC_ERR_BAD_SIZE },
+        };
+        for (const Case &k : cases) {
+            sc_screened_params p{ k.kind, k.lambda };
+            sc_poisson_layout l{ k.w, k.h, k.c, k.cs, k.rs, k.chs };
+            if (sc_hip_screened_check(&p, &l) != k.want) return fail("screened_check");
+        }
+        sc_screened_params p{ SC_POISSON_GUIDANCE, 1.f };
+        if (sc_hip_screened_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_screened_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("screened_check (null)");
     }
     printf("sanitize_main: clean\n");
     return 0;

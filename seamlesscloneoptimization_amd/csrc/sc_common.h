@@ -81,10 +81,21 @@ void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream
 // every array of a call; pre-process into U0 / F (lap: the right-hand side given, else from gx, gy), the solution U back into out.
 // Group forms: member k owns channels C k .. C k + C - 1, one launch per 16 members (the table goes by value)
 struct PoissonGeo { int W, H, C; long long cs, rs, chs; };
-struct PoissonJobDev { const float *gx, *gy, *lap, *b; float *out; };
+struct PoissonJobDev { const float *gx, *gy, *lap, *b; float *out; const float *d = nullptr; };      // d: a screened solve's data term
 struct PoissonJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; };
-void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s);
-void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s);
+// a screened solve's right-hand side (sc_screened_api.cpp): rhs - lam d in float32, one multiply, then one subtract -- never one fused
+// multiply-add, whatever the translation unit's contraction setting (the product is opaque to the optimiser)
+__device__ __forceinline__ float screened_rhs(float rhs, float lam, float d)
+{
+    float t = lam * d;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(t));
+#endif
+    return rhs - t;
+}
+// lam > 0: the screened right-hand side F = lap - lam d (d: PoissonJobDev::d, read on the interior); lam = 0: the launches as they were
+void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s, float lam = 0.f);
+void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s, float lam = 0.f);
 void launch_poisson_out(const PoissonGeo &g, const PoissonJobDev &j, Field U, hipStream_t s);
 void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, int n, Field U, hipStream_t s);
 // the Neumann solve's free constant: parts[(k C + c) np + i] = the sum in double of rows [i H / np, (i + 1) H / np) of channel c of member k's

@@ -288,10 +288,11 @@ __device__ __forceinline__ float fft_g(const Field &U, const Field &F, int c, in
 // MODE 0: rows of the folded right-hand side (from the fields) -> T[c][y][x]
 // MODE 1: rows of `in` (the transposed plane: row = x, entries = y) -> DST, / den, DST -> out, same layout
 // MODE 2: rows of `in` [c][y][x] -> DST, scale -> interior of the field U
+// shift: a screened solve's lambda (its exact denominator is the eigenvalue - lambda); 0 otherwise
 template <int MODE, typename T>
 __global__ __launch_bounds__(FFT_THREADS) void k_fft_dst(FftPlan<T> P, Field U, Field F, const T *__restrict__ in, T *__restrict__ out,
                                                          int rows, const float *__restrict__ f_row, const float *__restrict__ f_k, int exact,
-                                                         double scale, int tstore)
+                                                         double scale, int tstore, double shift)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
     cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
@@ -316,7 +317,7 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_dst(FftPlan<T> P, Field U, 
             const cx2<T> y = S[fft_pad(k)], ch = P.chirp[k];
             const T X = ch.x * y.y + ch.y * y.x;
             T den;
-            if (exact) den = (T)((2.0 * cospi((double)(r + 1) / (double)(rows + 1)) + 2.0 * cospi((double)k / (double)(n + 1))) - 4.0);
+            if (exact) den = (T)(((2.0 * cospi((double)(r + 1) / (double)(rows + 1)) + 2.0 * cospi((double)k / (double)(n + 1))) - 4.0) - shift);
             else den = (T)((f_row[r] + f_k[k - 1]) - 4.0f);
             const T q = X / den;
             S[fft_pad(k)] = mk<T>(q * ch.x, q * ch.y);
@@ -379,10 +380,14 @@ __device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDe
 // MODE 0: row r of the right-hand side (from the jobs' arrays) -> DCT-II -> out[p][r][k] (tstore: out[p][k][r])
 // MODE 1: rows of `in` (the transposed plane: row = x frequency, entries = y) -> DCT-II, / den, (0, 0) zeroed, DCT-III -> out, as MODE 0
 // MODE 2: rows of `in` [p][y][k] -> DCT-III, scale, + the plane's mean of boundary (parts: nparts sums per plane, nullptr: 0) -> the job's out
-template <int MODE, typename T, bool LAP>
+// SCR (a screened solve, lam > 0): MODE 0 reads the job's data term d beside the right-hand side, same element, same lane, and
+// transforms rhs - lam d (screened_rhs); MODE 1 divides by eigenvalue - lam, the (0, 0) coefficient included (by -lam: the screened
+// system is regular).  MODE 2 has no screened form: a screened solve runs it without parts.
+template <int MODE, typename T, bool LAP, bool SCR = false>
 __global__ __launch_bounds__(FFT_THREADS) void k_dct(FftPlan<T> P, PoissonGeo g, PoissonJobs jobs, const T *__restrict__ in, T *__restrict__ out,
-                                                     int rows, double scale, int tstore, const double *__restrict__ parts, int nparts)
+                                                     int rows, double scale, int tstore, const double *__restrict__ parts, int nparts, float lam)
 {
+    static_assert(!SCR || MODE != 2, "the last transform launch knows no screening");
     extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
     __shared__ double s_mean;
     cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
@@ -400,7 +405,12 @@ __global__ __launch_bounds__(FFT_THREADS) void k_dct(FftPlan<T> P, PoissonGeo g,
     for (int i = tid; i < P.M; i += FFT_THREADS) {
         cx2<T> a = mk<T>((T)0, (T)0);
         if (i < n) {
-            T x = (MODE == 0) ? (T)dct_rhs<LAP>(g, J, c, i, r) : src[i];
+            T x;
+            if constexpr (MODE == 0) {
+                float f = dct_rhs<LAP>(g, J, c, i, r);
+                if constexpr (SCR) f = screened_rhs(f, lam, J.d[(long long)i * g.cs + (long long)r * g.rs + (long long)c * g.chs]);
+                x = (T)f;
+            } else x = src[i];
             if (MODE == 2 && i == 0) x *= (T)0.5;
             const cx2<T> ch = (MODE == 2) ? half[i] : P.chirp[i];
             a = mk<T>(x * ch.x, x * ch.y);
@@ -415,8 +425,9 @@ __global__ __launch_bounds__(FFT_THREADS) void k_dct(FftPlan<T> P, PoissonGeo g,
         for (int k = tid; k < n; k += FFT_THREADS) {
             const cx2<T> y = S[fft_pad(k)], h = half[k];
             const T X = h.x * y.x - h.y * y.y;
-            const T den = (T)((2.0 * cospi((double)r / (double)rows) - 2.0) + (2.0 * cospi((double)k / (double)n) - 2.0));
-            T q = (r == 0 && k == 0) ? (T)0 : X / den;
+            const double eig = (2.0 * cospi((double)r / (double)rows) - 2.0) + (2.0 * cospi((double)k / (double)n) - 2.0);
+            const T den = (T)(SCR ? eig - (double)lam : eig);
+            T q = (!SCR && r == 0 && k == 0) ? (T)0 : X / den;
             if (k == 0) q *= (T)0.5;
             S[fft_pad(k)] = mk<T>(q * h.x, q * h.y);
         }
@@ -441,6 +452,10 @@ static hipError_t dct_opt_in_lds(int bytes)
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<1, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<2, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    // the screened forms
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<1, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     return e;
 }
 
@@ -790,21 +805,22 @@ static int fft_solve_t(Instance *I)
     T *A = (T *)S.A.p, *B = (T *)S.B.p;
     const float *fx = (const float *)X->d.p, *fy = fx + w;
     const double scale = 4.0 / ((w + 1.0) * (h + 1.0));
+    const double shift = (double)I->screen_lambda;      // a screened call (sc_screened_api.cpp); it solves the exact system
     const dim3 tg_hw((w + 63) / 64, (h + 63) / 64, C), tg_wh((h + 63) / 64, (w + 63) / 64, C);
     // Small planes (cache resident: the scattered 4- or 8-byte stores of a transposed write cost nothing there) skip the two
     // transpose launches: each transform launch writes the plane the next one reads row-wise.  Three launches instead of five:
     // 0.057 -> ~0.04 ms of a 298 x 192 clone's solve, where every launch is at its latency floor.
     const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);
     if (tiny) {
-        hipLaunchKernelGGL((k_fft_dst<0, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)nullptr, B, h, fx, fy, exact, 1.0, 1);   // B[c][x][y]
-        hipLaunchKernelGGL((k_fft_dst<1, T>), dim3(w, C), dim3(FFT_THREADS), ldsh, I->stream, Ph, U, I->F, (const T *)B, A, w, fx, fy, exact, 1.0, 1);        // A[c][y][x]
-        hipLaunchKernelGGL((k_fft_dst<2, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)A, B, h, fx, fy, exact, scale, 0);
+        hipLaunchKernelGGL((k_fft_dst<0, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)nullptr, B, h, fx, fy, exact, 1.0, 1, shift);   // B[c][x][y]
+        hipLaunchKernelGGL((k_fft_dst<1, T>), dim3(w, C), dim3(FFT_THREADS), ldsh, I->stream, Ph, U, I->F, (const T *)B, A, w, fx, fy, exact, 1.0, 1, shift);        // A[c][y][x]
+        hipLaunchKernelGGL((k_fft_dst<2, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)A, B, h, fx, fy, exact, scale, 0, shift);
     } else {
-    hipLaunchKernelGGL((k_fft_dst<0, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)nullptr, A, h, fx, fy, exact, 1.0, 0);
+    hipLaunchKernelGGL((k_fft_dst<0, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)nullptr, A, h, fx, fy, exact, 1.0, 0, shift);
     hipLaunchKernelGGL((k_fft_transpose<T>), tg_hw, dim3(256), 0, I->stream, (const T *)A, B, h, w);                 // B[c][x][y]
-    hipLaunchKernelGGL((k_fft_dst<1, T>), dim3(w, C), dim3(FFT_THREADS), ldsh, I->stream, Ph, U, I->F, (const T *)B, A, w, fx, fy, exact, 1.0, 0);
+    hipLaunchKernelGGL((k_fft_dst<1, T>), dim3(w, C), dim3(FFT_THREADS), ldsh, I->stream, Ph, U, I->F, (const T *)B, A, w, fx, fy, exact, 1.0, 0, shift);
     hipLaunchKernelGGL((k_fft_transpose<T>), tg_wh, dim3(256), 0, I->stream, (const T *)A, B, w, h);                 // B[c][y][x]
-    hipLaunchKernelGGL((k_fft_dst<2, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)B, A, h, fx, fy, exact, scale, 0);
+    hipLaunchKernelGGL((k_fft_dst<2, T>), dim3(h, C), dim3(FFT_THREADS), ldsw, I->stream, Pw, U, I->F, (const T *)B, A, h, fx, fy, exact, scale, 0, shift);
     }
     SC_HIP(I, hipGetLastError());
     I->info.sweeps = 1;
@@ -828,9 +844,12 @@ int fft_solve(Instance *I, bool fp64)
 // The Neumann solve of m same-size jobs (C m planes): boundary-mean reduction, rows (right-hand side from the jobs' arrays), columns
 // (DCT-II, divide, DCT-III), rows (DCT-III, scale 4 / (W H), + mean, into the jobs' out) -- the launches that read or write the
 // jobs' arrays go per PoissonJobs::MAX members (the table goes by value), the column launch over all planes at once.
+// lam > 0: the screened solve -- no reduction and no mean (mark 5 sits at the start), the data term read by the first row launch,
+// the denominators shifted by -lam.
 template <typename T>
-static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m)
+static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, float lam)
 {
+    const bool scr = lam > 0.f;
     const int W = g.W, H = g.H, planes = g.C * m;
     SC_HIP(I, fft_opt_in_lds<T>(I));
     FftState &S = I->fft;
@@ -845,7 +864,7 @@ static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const Poisson
     if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
     if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
     bool any_b = false;
-    for (int k = 0; k < m; ++k) any_b = any_b || jobs[k].b;
+    for (int k = 0; k < m && !scr; ++k) any_b = any_b || jobs[k].b;
     const int np = poisson_mean_parts(H);
     double *parts = nullptr;
     if (any_b) {
@@ -875,21 +894,35 @@ static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const Poisson
     };
     const PoissonJobs none{};
     T *rows_out = tiny ? B : A;              // the row transforms' plane; B[p][x][y] when stored transposed
+    const double *const no_parts = nullptr;
     chunks([&](const PoissonJobs &t, size_t p0, int np_) {
-        if (lap) hipLaunchKernelGGL((k_dct<0, T, true>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, rows_out + p0 * plane, H, 1.0, tiny ? 1 : 0, (const double *)nullptr, 0);
-        else hipLaunchKernelGGL((k_dct<0, T, false>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, rows_out + p0 * plane, H, 1.0, tiny ? 1 : 0, (const double *)nullptr, 0);
+        const dim3 grid(H, np_);
+        T *const o = rows_out + p0 * plane;
+        const int ts = tiny ? 1 : 0;
+        if (scr) {
+            if (lap) hipLaunchKernelGGL((k_dct<0, T, true, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, lam);
+            else hipLaunchKernelGGL((k_dct<0, T, false, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, lam);
+        } else {
+            if (lap) hipLaunchKernelGGL((k_dct<0, T, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, 0.f);
+            else hipLaunchKernelGGL((k_dct<0, T, false>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, 0.f);
+        }
     });
+    // the column launch: B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
+    auto columns = [&](int ts) {
+        if (scr) hipLaunchKernelGGL((k_dct<1, T, false, true>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, ts, no_parts, 0, lam);
+        else hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, ts, no_parts, 0, 0.f);
+    };
     if (tiny) {
-        hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, 1, (const double *)nullptr, 0);   // A[p][y][x]
+        columns(1);      // A[p][y][x]
     } else {
         hipLaunchKernelGGL((k_fft_transpose<T>), dim3((W + 63) / 64, (H + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, H, W);      // B[p][x][y]
-        hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, 0, (const double *)nullptr, 0);
+        columns(0);
         hipLaunchKernelGGL((k_fft_transpose<T>), dim3((H + 63) / 64, (W + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, W, H);      // B[p][y][x]
     }
     const T *rows_in = tiny ? A : B;
     chunks([&](const PoissonJobs &t, size_t p0, int np_) {
         hipLaunchKernelGGL((k_dct<2, T, false>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, rows_in + p0 * plane, (T *)nullptr, H, scale, 0,
-                           parts ? (const double *)(parts + p0 * np) : (const double *)nullptr, np);
+                           parts ? (const double *)(parts + p0 * np) : (const double *)nullptr, np, 0.f);
     });
     SC_HIP(I, hipGetLastError());
     stage_mark(I, 6);
@@ -901,13 +934,13 @@ static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const Poisson
     return SC_OK;
 }
 
-int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64)
+int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
 {
     if (!fft_supported(g.W, g.H, fp64)) {
         I->err = fp64 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: more than 4096 pixels per side" : "SC_POISSON_NEUMANN: more than 8192 pixels per side";
         return SC_ERR_BAD_SIZE;
     }
-    return fp64 ? dct_solve_t<double>(I, g, lap, jobs, m) : dct_solve_t<float>(I, g, lap, jobs, m);
+    return fp64 ? dct_solve_t<double>(I, g, lap, jobs, m, lam) : dct_solve_t<float>(I, g, lap, jobs, m, lam);
 }
 
 } // namespace sc

@@ -170,6 +170,7 @@ struct Instance {
     // the Poisson solve on caller arrays (sc_poisson_api.cpp): the host call's device copies of the arrays' spans
     DevBuf d_pois;
     bool auto_as_single = false;           // ... one problem of up to 4 channels: SC_METHOD_AUTO decides as for a single clone (effective_method)
+    float screen_lambda = 0.f;             // a screened call (sc_screened_api.cpp) is solving: fft_solve divides by eigenvalue - lambda
     // fields
     DevBuf d_U0, d_U1, d_F;
     Field U0, U1, F;      // current views into the buffers above
@@ -262,6 +263,7 @@ struct CallScope {
         I->force_float_field = false;
         I->spec_post = Instance::SpecPost();
         I->auto_as_single = false;
+        I->screen_lambda = 0.f;
     }
 };
 
@@ -317,6 +319,14 @@ void edit_preprocess_group(Instance *I, const sc_edit_params *p, const EditJob *
 // sc_poisson_api.cpp: the Poisson call's validation (host-only; why: the reason) and a job's own
 int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, const char **why);
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why);
+// ... and what the screened call (sc_screened_api.cpp) shares with it.  lam > 0: a screened call -- the jobs carry their data term
+// (PoissonJobDev::d), the solve is the direct one with shifted denominators.
+struct PoissonCall { int kind; float tol, lam; };
+size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
+bool aligned4(const void *p);
+int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
+void poisson_set_timing(Instance *I, const float t[4]);
+int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);
 // sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
 void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
 int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);
@@ -369,7 +379,8 @@ int fft_solve(Instance *I, bool fp64);                                // sc_fft.
 bool fft_supported(int w, int h, bool fp64);
 // sc_fft.hip: the Neumann problem on caller arrays (SC_POISSON_NEUMANN): m same-size jobs as C m planes, straight from the jobs' arrays into
 // their out arrays (marks: 5 behind the boundary-mean reduction, 6 behind the last transform launch)
-int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64);
+// (lam > 0: the screened solve, sc_screened_api.cpp: the jobs' data term read with the right-hand side, no mean)
+int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
 bool wants_float_tables(const Instance *I);
 int effective_method(const Instance *I);                              // sc_solver.cpp: what SC_METHOD_AUTO resolves to for the fields bound to I
 int output_nodes(Instance *I, LmNodes &lm);  // sc_solver.cpp: the float-table correction the post-process of result(I) has to add (none: lm.CN == nullptr)

@@ -15,6 +15,7 @@
 #include "sc_wave.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <type_traits>
 
 namespace sc {
 
@@ -29,8 +30,9 @@ __device__ __forceinline__ bool ps_lane(const PoissonGeo &g, bool inter, int wco
     return inter ? x < wcols : c < g.C;
 }
 
-template <bool INTER, bool LAP>
-__device__ __forceinline__ void poisson_pre_block(const PoissonGeo &g, const PoissonJobDev &j, const Field &U0, const Field &F, int c0)
+// SCR: a screened solve's right-hand side, F = lap - lam d on the interior (screened_rhs; d is read there only, once per element)
+template <bool INTER, bool LAP, bool SCR>
+__device__ __forceinline__ void poisson_pre_block(const PoissonGeo &g, const PoissonJobDev &j, const Field &U0, const Field &F, int c0, float lam)
 {
     __shared__ float gxs[2][PS_LANES];
     const int W = g.W, H = g.H, Wp = (W + 3) & ~3;
@@ -62,24 +64,27 @@ __device__ __forceinline__ void poisson_pre_block(const PoissonGeo &g, const Poi
             }
             gyu = gyv;
         }
+        if constexpr (SCR) {
+            if (in) lap = screened_rhs(lap, lam, j.d[o]);
+        }
         if (lane) {
             const size_t fo = (size_t)y * U0.pitch;
-            u0[fo] = img ? j.b[o] : 0.f;
+            u0[fo] = (img && !(SCR && in)) ? j.b[o] : 0.f;      // (a screened solve is direct: boundary's interior is never read)
             f[fo] = lap;
         }
     }
 }
 
-template <bool INTER, bool LAP>
-__global__ __launch_bounds__(PS_LANES) void k_poisson_pre(PoissonGeo g, PoissonJobDev j, Field U0, Field F)
+template <bool INTER, bool LAP, bool SCR>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_pre(PoissonGeo g, PoissonJobDev j, Field U0, Field F, float lam)
 {
-    poisson_pre_block<INTER, LAP>(g, j, U0, F, 0);
+    poisson_pre_block<INTER, LAP, SCR>(g, j, U0, F, 0, lam);
 }
 
-template <bool INTER, bool LAP>
-__global__ __launch_bounds__(PS_LANES) void k_poisson_pre_group(PoissonGeo g, PoissonJobs t, Field U0, Field F)
+template <bool INTER, bool LAP, bool SCR>
+__global__ __launch_bounds__(PS_LANES) void k_poisson_pre_group(PoissonGeo g, PoissonJobs t, Field U0, Field F, float lam)
 {
-    poisson_pre_block<INTER, LAP>(g, t.j[blockIdx.z], U0, F, g.C * (int)blockIdx.z);
+    poisson_pre_block<INTER, LAP, SCR>(g, t.j[blockIdx.z], U0, F, g.C * (int)blockIdx.z, lam);
 }
 
 // the solution field's interior into out, the frame from boundary (bit for bit); only the W x H x C elements the layout names
@@ -142,16 +147,24 @@ static dim3 ps_grid(const PoissonGeo &g, int wcols, int members)
     return dim3((unsigned)((wcols * g.C + PS_LANES - 1) / PS_LANES), (unsigned)((g.H + PS_ROWS - 1) / PS_ROWS), (unsigned)members);
 }
 
-void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s)
+// the instantiation for (interleaved, lap given, screened): fn(std::integral_constant<bool, .>...) launches it
+template <typename Fn>
+static void ps_pre_dispatch(bool inter, bool lap, bool scr, Fn fn)
+{
+    auto pick = [&](auto i, auto l) {
+        if (scr) fn(i, l, std::true_type());
+        else fn(i, l, std::false_type());
+    };
+    if (inter) { if (lap) pick(std::true_type(), std::true_type()); else pick(std::true_type(), std::false_type()); }
+    else { if (lap) pick(std::false_type(), std::true_type()); else pick(std::false_type(), std::false_type()); }
+}
+
+void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s, float lam)
 {
     const dim3 grid = ps_grid(g, (g.W + 3) & ~3, 1);
-    if (interleaved(g)) {
-        if (lap) hipLaunchKernelGGL((k_poisson_pre<true, true>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
-        else hipLaunchKernelGGL((k_poisson_pre<true, false>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
-    } else {
-        if (lap) hipLaunchKernelGGL((k_poisson_pre<false, true>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
-        else hipLaunchKernelGGL((k_poisson_pre<false, false>), grid, dim3(PS_LANES), 0, s, g, j, U0, F);
-    }
+    ps_pre_dispatch(interleaved(g), lap, lam > 0.f, [&](auto i, auto l, auto sc) {
+        hipLaunchKernelGGL((k_poisson_pre<decltype(i)::value, decltype(l)::value, decltype(sc)::value>), grid, dim3(PS_LANES), 0, s, g, j, U0, F, lam);
+    });
 }
 
 template <typename Fn>
@@ -165,20 +178,16 @@ static void ps_chunks(const PoissonJobDev *jobs, int n, Fn fn)
     }
 }
 
-void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s)
+void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s, float lam)
 {
     ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
         const dim3 grid = ps_grid(g, (g.W + 3) & ~3, cnt);
         Field u = U0, f = F;      // this launch's first member owns channel C i0
         u.p = U0.p + (size_t)g.C * i0 * U0.plane;
         f.p = F.p + (size_t)g.C * i0 * F.plane;
-        if (interleaved(g)) {
-            if (lap) hipLaunchKernelGGL((k_poisson_pre_group<true, true>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
-            else hipLaunchKernelGGL((k_poisson_pre_group<true, false>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
-        } else {
-            if (lap) hipLaunchKernelGGL((k_poisson_pre_group<false, true>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
-            else hipLaunchKernelGGL((k_poisson_pre_group<false, false>), grid, dim3(PS_LANES), 0, s, g, t, u, f);
-        }
+        ps_pre_dispatch(interleaved(g), lap, lam > 0.f, [&](auto i, auto l, auto sc) {
+            hipLaunchKernelGGL((k_poisson_pre_group<decltype(i)::value, decltype(l)::value, decltype(sc)::value>), grid, dim3(PS_LANES), 0, s, g, t, u, f, lam);
+        });
     });
 }
 

@@ -10,6 +10,9 @@
 //
 // SC_POISSON_NEUMANN: no fields, no pre-process or output launch -- per chunk dct_solve (sc_fft.hip) works straight between the jobs'
 // arrays: the boundary-mean reduction, then the three transform launches of the DCT solve.
+//
+// The screened call (sc_screened_api.cpp) runs through the same poisson_run with PoissonCall::lam > 0: the jobs carry their data
+// term, the solve is the direct one (SC_METHOD_FFT) with its denominators shifted by -lam.
 #include "sc_instance.h"
 #include <algorithm>
 #include <cmath>
@@ -59,12 +62,12 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
 }
 
 // floats from an array's pointer to one past its last element under the layout
-static size_t poisson_span(const sc_poisson_layout *l)
+size_t poisson_span(const sc_poisson_layout *l)
 {
     return (size_t)((l->cols - 1) * l->col_stride + (l->rows - 1) * l->row_stride + (l->channels - 1) * l->channel_stride) + 1;
 }
 
-static bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
 // a job's own code: the pointers its kind needs, 4-byte aligned (a Neumann job may come without boundary: mean zero)
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
@@ -87,21 +90,25 @@ namespace {
 struct PoissonScope {
     Instance *I;
     sc_solver_opts saved;
-    PoissonScope(Instance *I_, const sc_poisson_params *p, int n_valid) : I(I_), saved(I_->opts)
+    PoissonScope(Instance *I_, const PoissonCall &p, int n_valid) : I(I_), saved(I_->opts)
     {
         sc_solver_opts &o = I->opts;
         o.flags = (o.flags | SC_FLAG_EXACT_TABLES | SC_FLAG_FLOAT_RHS | SC_FLAG_FLOAT_U0 | SC_FLAG_FLOAT_L1 | SC_FLAG_FLOAT_FIELD) &
                   ~SC_FLAG_OPENCV_GREY_MASK;
-        o.update_tol = p->tol > 0.f ? p->tol : 1e-3f;
+        o.update_tol = p.tol > 0.f ? p.tol : 1e-3f;
         o.reference_warmup = 0;
         if (o.method == SC_METHOD_AUTO && n_valid > 1) o.method = SC_METHOD_MULTIGRID;     // a batch: the cycles, as the edit batches
         I->auto_as_single = n_valid == 1;           // one problem: AUTO decides as for a single clone, whatever its channel count
+        if (p.lam > 0.f) {                          // a screened call: the direct solve at any size, its denominators shifted
+            o.method = SC_METHOD_FFT;
+            I->screen_lambda = p.lam;
+        }
     }
     ~PoissonScope() { I->opts = saved; }
 };
 
 // One chunk of m same-size problems as one field of C m planes.  Marks: 0 start, 5 pre-process done, 6 solve done, 7 output done.
-int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m)
+int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
 {
     int rc;
     if ((rc = setup_fields(I, g.W, g.H, g.C * m))) return rc;
@@ -109,8 +116,8 @@ int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     stage_mark(I, 0);
     const bool lap = kind == SC_POISSON_LAPLACIAN;
     const int solve_rc = solve_step(I, SolveTarget(), [&]() -> int {      // float32 right-hand side and initial field (FLOAT_RHS | FLOAT_U0)
-        if (m == 1) launch_poisson_pre(g, lap, jobs[0], I->U0, I->F, I->stream);
-        else launch_poisson_pre_group(g, lap, jobs, m, I->U0, I->F, I->stream);
+        if (m == 1) launch_poisson_pre(g, lap, jobs[0], I->U0, I->F, I->stream, lam);
+        else launch_poisson_pre_group(g, lap, jobs, m, I->U0, I->F, I->stream, lam);
         SC_HIP(I, hipGetLastError());
         stage_mark(I, 5);
         return SC_OK;
@@ -141,10 +148,10 @@ int neumann_instance_check(Instance *I, const sc_poisson_layout *l)
 
 // The same for a Neumann call: no fields; marks 5 (reduction done) and 6 (transforms done) come from dct_solve, 7 = 6 (the output is
 // the last transform launch's store).
-int neumann_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m)
+int neumann_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
 {
     stage_mark(I, 0);
-    const int rc = dct_solve(I, g, (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0);
+    const int rc = dct_solve(I, g, (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
     if (rc) return rc;
     stage_mark(I, 7);
     return SC_OK;
@@ -158,7 +165,11 @@ void add_timing(Instance *I, float t[4])
     t[3] += ev_ms(I->ev[0], I->ev[7]);
 }
 
-void set_timing(Instance *I, const float t[4])
+} // namespace
+
+namespace sc {
+
+void poisson_set_timing(Instance *I, const float t[4])
 {
     I->info.ms_mask = 0.f;
     I->info.ms_pre = t[0]; I->info.ms_solve = t[1]; I->info.ms_post = t[2];
@@ -166,12 +177,12 @@ void set_timing(Instance *I, const float t[4])
     I->info.ms_call = t[3];
 }
 
-// Every job of `valid` (indices into jobs) through chunks of at most SC_POISSON_MAX_PLANES planes.  timed: stage marks, a wait per
-// chunk, the stage times summed into t.  Codes as sc_hip_edit_device_batch: the worst; a HIP error marks every valid job.
-int poisson_run(Instance *I, const sc_poisson_params *p, const sc_poisson_layout *l, sc_poisson_job *jobs, const std::vector<int> &valid,
+// The nv validated jobs of a call (their device arrays in dj, where each one's code goes in rcs) through chunks of at most
+// SC_POISSON_MAX_PLANES planes.  timed: stage marks, a wait per chunk, the stage times summed into t.  Codes as
+// sc_hip_edit_device_batch: the worst; a HIP error marks every job.
+int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv,
                 bool timed, float t[4])
 {
-    const int nv = (int)valid.size();
     CallScope call{ I };
     PoissonScope scope(I, p, nv);
     const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
@@ -181,35 +192,29 @@ int poisson_run(Instance *I, const sc_poisson_params *p, const sc_poisson_layout
     I->marks_ends_only = false;
     const int per = std::max(1, SC_POISSON_MAX_PLANES / g.C);
     int worst = SC_OK;
-    std::vector<PoissonJobDev> dj;
     for (int i0 = 0; i0 < nv; i0 += per) {
         const int m = std::min(per, nv - i0);
-        dj.resize(m);
-        for (int k = 0; k < m; ++k) {
-            const sc_poisson_job &j = jobs[valid[i0 + k]];
-            dj[k] = PoissonJobDev{ j.gx, j.gy, j.lap, j.boundary, j.out };
-        }
-        int rc = (p->kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p->kind, g, dj.data(), m) : poisson_chunk(I, p->kind, g, dj.data(), m);
+        int rc = (p.kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
         if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
             if (timed) {
                 SC_HIP(I, hipStreamSynchronize(I->stream));
                 add_timing(I, t);
             }
-            for (int k = 0; k < m; ++k) jobs[valid[i0 + k]].rc = rc;
+            for (int k = 0; k < m; ++k) *rcs[i0 + k] = rc;
             if (rc != SC_OK && worst == SC_OK) worst = rc;
             I->info.group_members = m > 1 ? m : 0;
             continue;
         }
         // a chunk that failed: its members and every one not yet run read its code; after a HIP error the ones already run too
-        for (int k = i0; k < nv; ++k) jobs[valid[k]].rc = rc;
+        for (int k = i0; k < nv; ++k) *rcs[k] = rc;
         if (rc == SC_ERR_HIP)
-            for (int k = 0; k < i0; ++k) jobs[valid[k]].rc = rc;
+            for (int k = 0; k < i0; ++k) *rcs[k] = rc;
         return rc;
     }
     return worst;
 }
 
-} // namespace
+} // namespace sc
 
 extern "C" {
 
@@ -228,7 +233,8 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
     if ((p->kind & SC_POISSON_NEUMANN) && (rc = neumann_instance_check(I, l))) return rc;
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
-    std::vector<int> valid;
+    std::vector<PoissonJobDev> dj;
+    std::vector<int *> rcs;
     for (int i = 0; i < n; ++i) {
         sc_poisson_job &j = jobs[i];
         const int vrc = poisson_job_validate(p->kind, j.gx, j.gy, j.lap, j.boundary, j.out, &why);
@@ -238,14 +244,15 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
             continue;
         }
         j.rc = SC_ERR_HIP;          // until its chunk has run
-        valid.push_back(i);
+        dj.push_back(PoissonJobDev{ j.gx, j.gy, j.lap, j.boundary, j.out });
+        rcs.push_back(&j.rc);
     }
-    if (valid.empty()) return worst;
+    if (dj.empty()) return worst;
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    rc = poisson_run(I, p, l, jobs, valid, bSync, t);
+    rc = poisson_run(I, PoissonCall{ p->kind, p->tol, 0.f }, l, dj.data(), rcs.data(), (int)dj.size(), bSync, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    set_timing(I, t);               // (zeros without bSync)
+    poisson_set_timing(I, t);       // (zeros without bSync)
     if (worst == SC_OK) worst = rc;
     return worst;
 }
@@ -274,14 +281,24 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
     if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
     if (boundary && (rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
-    sc_poisson_job job{};
-    job.gx = guidance ? d_in0 : nullptr; job.gy = d_in1; job.lap = guidance ? nullptr : d_in0;
-    job.boundary = d_b; job.out = d_out;
+    const PoissonJobDev job{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_b, d_out };
+    int job_rc = SC_OK, *const job_rcs[1] = { &job_rc };
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
-    rc = poisson_run(I, p, l, &job, std::vector<int>{ 0 }, true, t);
+    rc = poisson_run(I, PoissonCall{ p->kind, p->tol, 0.f }, l, &job, job_rcs, 1, true, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    const int rc_solve = rc;
-    // out's span back into pinned staging, then only the elements the layout names into the caller's array
+    return poisson_download(I, l, d_out, out, t, rc);
+}
+
+} // extern "C"
+
+namespace sc {
+
+// The host call's way back: out's span into pinned staging, then only the elements the layout names into the caller's array; the
+// call's times.  Returns rc_solve.
+int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve)
+{
+    const size_t span = poisson_span(l), bytes = span * sizeof(float);
+    int rc;
     if ((rc = ensure_pinned(I, I->h_out, bytes))) return rc;
     SC_HIP(I, hipMemcpyAsync(I->h_out.p, d_out, bytes, hipMemcpyDeviceToHost, I->stream));
     SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
@@ -298,11 +315,11 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
                     out[o] = h[o];
                 }
     }
-    set_timing(I, t);
+    poisson_set_timing(I, t);
     I->info.ms_h2d = ev_ms(I->ev_k0, I->ev[0]);
     I->info.ms_d2h = ev_ms(I->ev[7], I->ev_k1);
     I->info.ms_call = ev_ms(I->ev_k0, I->ev_k1);
     return rc_solve;
 }
 
-} // extern "C"
+} // namespace sc

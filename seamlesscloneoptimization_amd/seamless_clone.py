@@ -324,3 +324,107 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
             inst.free(d)
         inst.destroy()
     return [out[k * slot // 4:k * slot // 4 + checked[k][-1].size].reshape(shape).copy() for k in range(n)]
+
+
+def screened_solve(data, gx=None, gy=None, laplacian=None, lam=None, boundary=None, neumann=True, gpu_id=0, **solver):
+    """Screened Poisson solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
+        lam sum (u - data)^2 + sum |grad u - (gx, gy)|^2                (or with the divergence of the guidance given as laplacian),
+    i.e. (A - lam) u = div g - lam data for the 5-point operator A.  neumann (the default): every pixel is an unknown, the field is
+    reflected at the border.  neumann=False: u = boundary on the one-pixel frame (boundary required; only its frame is read).  A
+    direct solve (methods auto and fft; flags=SC_FLAG_FFT_FP64 for double transforms); lam must be finite and > 0."""
+    kind, d, gx, gy, lap, b, _ = capi.screened_arrays(data, gx, gy, laplacian, lam, boundary, neumann=neumann)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.screened(d, gx=gx, gy=gy, lap=lap, lam=lam, boundary=b, neumann=neumann)
+    finally:
+        inst.destroy()
+
+
+def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, boundaries=None, neumann=True, gpu_id=0, **solver):
+    """screened_solve over a list of same-shape problems through ONE device-resident call (sc_hip_screened_device): one copy in, one
+    copy out, the problems solved as one field of n x C planes (chunks of at most SC_POISSON_MAX_PLANES planes); every member equals
+    its solo solve bit for bit.  One lam for the batch.  boundaries: one per problem when neumann=False.  Returns a list of NEW arrays."""
+    ds = list(datas)
+    n = len(ds)
+    if lam is None or not np.isfinite(lam) or not lam > 0:
+        raise ValueError("lam must be finite and > 0")
+    if (gxs is None) != (gys is None) or (gxs is None) == (laplacians is None):
+        raise ValueError("give either gxs and gys or laplacians")
+    fields = [gxs, gys] if gxs is not None else [laplacians]
+    if not neumann:
+        if boundaries is None:
+            raise ValueError("a Dirichlet screened solve needs boundaries (neumann=True: none)")
+        fields = fields + [boundaries]
+    for f in fields:
+        if len(f) != n:
+            raise ValueError("one guidance field (or laplacian), and one boundary under a frame, per data term")
+    if not ds:
+        return []
+    checked = []
+    for k in range(n):
+        b = None if neumann else boundaries[k]
+        if gxs is not None:
+            kind, d, gx, gy, _, b, _ = capi.screened_arrays(ds[k], gxs[k], gys[k], None, lam, b, neumann=neumann)
+            arrays = [gx, gy, d]
+        else:
+            kind, d, _, _, lap, b, _ = capi.screened_arrays(ds[k], None, None, laplacians[k], lam, b, neumann=neumann)
+            arrays = [lap, d]
+        if d.shape != ds[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        checked.append([np.ascontiguousarray(a) for a in arrays + ([] if b is None else [b])])
+    shape = ds[0].shape
+    nb = checked[0][0].nbytes
+    slot = (nb + 255) // 256 * 256
+    per = len(checked[0])
+    in_bytes = slot * per * n
+    staged = np.zeros(in_bytes // 4, np.float32)
+    for k, arrays in enumerate(checked):
+        for i, a in enumerate(arrays):
+            o = (k * per + i) * slot // 4
+            staged[o:o + a.size] = a.reshape(-1)
+    layout = capi.poisson_layout_of(checked[0][0])
+    guidance = gxs is not None
+    inst = capi.Instance(gpu_id)
+    dev = None
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        dev = inst.malloc(in_bytes + slot * n)
+        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
+        jobs = capi.Instance.make_screened_jobs(n)
+        for k, j in enumerate(jobs):
+            base = dev + k * per * slot
+            if guidance:
+                j.gx, j.gy, j.data = base, base + slot, base + 2 * slot
+            else:
+                j.lap, j.data = base, base + slot
+            j.boundary = None if neumann else base + (per - 1) * slot
+            j.out = dev + in_bytes + k * slot
+        inst.screened_device(capi.ScreenedParams(kind, float(lam)), layout, jobs)
+        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
+    finally:
+        if dev is not None:
+            inst.free(dev)
+        inst.destroy()
+    return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
+
+
+def gradient_filter(image, gain, lam, neumann=True, gpu_id=0, **solver):
+    """Gradient-domain filtering of a float32 image (H x W or H x W x C): the image whose forward differences are `gain` times the
+    input's while it stays close to the input, lam weighing the closeness -- screened_solve with data = image, guidance = gain x the
+    forward differences of image, and boundary = image when neumann=False.  gain > 1 sharpens, gain < 1 flattens, gain 1 returns the
+    image (to float32 rounding).  Returns a NEW array."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    if image.ndim not in (2, 3):
+        raise ValueError("image is H x W or H x W x C")
+    if not np.isfinite(gain):
+        raise ValueError("gain must be finite")
+    g = np.float32(gain)
+    gx = np.zeros_like(image)
+    gy = np.zeros_like(image)
+    gx[:, :-1] = g * (image[:, 1:] - image[:, :-1])
+    gy[:-1] = g * (image[1:] - image[:-1])
+    return screened_solve(image, gx=gx, gy=gy, lam=lam, boundary=None if neumann else image, neumann=neumann, gpu_id=gpu_id, **solver)

@@ -1,0 +1,495 @@
+"""GPU tests of the screened Poisson solve (sc_hip_screened, sc_hip_screened_device) through capi:
+
+    (A - lam) u = lap - lam d,   lam > 0,   A the 5-point operator under a Dirichlet frame or reflecting at the border.
+
+1. identity: d = I, g = forward differences of I (boundary = I under a frame) gives back I, at every transform-length class.
+2. random inputs against the float64 restatement (tests/screened_np.py), both kinds and both boundaries; the LAPLACIAN form, given
+   numpy's divergence in the documented order, returns the GUIDANCE form's bits.
+3. the large-lam limit: max |u - d| <= max |div g - A d| / lam (the maximum principle of lam - A).
+4. batches: every member equals its solo run bit for bit; chunks, tables of more than PoissonJobs::MAX members, a skipped member.
+5. writes: only named elements change, aliasing gives the same bits, the Dirichlet frame is boundary's.
+6. refusals write nothing; the instance afterwards is the instance before.
+7. gradient_filter.
+
+Bounds.  Dirichlet and the identity (item 1): those of tests/test_gpu_poisson.py's bound() for the direct solves, restated here --
+max |out - want| <= 4e-3 R with float32 transforms, 1e-4 R with double ones, R = max |want|: screening only moves every eigenvalue
+away from zero (|eig - lam| >= |eig|, eig <= 0 < lam), so a bound the unscreened solve keeps holds a fortiori.  Neumann against the
+restatement: tests/screened_bounds.py (float32: a factor over the float32 restatement's own ERR and RES on the same input; double:
+F64_ULPS float32 ulps)."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi, seamless_clone
+
+import screened_bounds
+import screened_np
+from screened_np import DIRICHLET, NEUMANN
+
+pytestmark = pytest.mark.gpu
+
+G, L, NEU = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN, capi.SC_POISSON_NEUMANN
+PREC = {"fft32": 0, "fft64": capi.SC_FLAG_FFT_FP64}
+BOUND = {"fft32": 4e-3, "fft64": 1e-4}          # x R: test_gpu_poisson.py's bound() for SC_METHOD_FFT
+LAMS = [1e-3, 0.1, 10.0]
+SENTINEL = -7.25
+
+
+@pytest.fixture(scope="module")
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def configure(inst, method=capi.SC_METHOD_FFT, flags=0, **kw):
+    d = inst.default_opts()
+    inst.set_solver(**{k: getattr(d, k) for k, _ in capi.SolverOpts._fields_})
+    inst.set_solver(method=method, flags=flags, **kw)
+
+
+def image(H, W, C, seed):
+    return np.random.default_rng(seed).uniform(-50, 300, (H, W, C)).astype(np.float32)
+
+
+def frame_equal(a, b):
+    return (np.array_equal(a[0], b[0]) and np.array_equal(a[-1], b[-1]) and np.array_equal(a[:, 0], b[:, 0]) and
+            np.array_equal(a[:, -1], b[:, -1]))
+
+
+def check_info(inst, W, H):
+    i = inst.info()
+    assert (i.method, i.sweeps, i.converged, i.W, i.H) == (capi.SC_METHOD_FFT, 1, 1, W, H)
+
+
+# ---- 1. identity ---------------------------------------------------------------------------------------------------------------
+# Pixels per walked side.  The convolution length of n unknowns is the shortest M = r 2^k >= 2n - 1, r in {1, 3, 5}: for each class
+# the last n that fits and the first that does not -- 2^k: 8 | 9 (16), 32 | 33 (64), 128 | 129 (256); 3 2^k: 24 | 25 (48), 96 | 97
+# (192); 5 2^k: 40 | 41 (80), 160 | 161 (320) -- a prime (31, 251), and under a frame the same unknowns + 2.  The other side stays
+# short.  Then the plane sizes on both sides of the 4 MB threshold below which the transposes are fused into the transform launches
+# (1024 x 1024 floats), and one long thin strip.
+WALK = [2, 3, 4, 5, 8, 9, 24, 25, 31, 32, 33, 40, 41, 96, 97, 128, 129, 160, 161, 251]
+
+
+def identity_sizes(neumann):
+    e = 0 if neumann else 2
+    sizes = [(n + e, 7 + e) for n in WALK] + [(6 + e, n + e) for n in WALK]          # (W, H): walked along x, along y
+    sizes += [(2, 2), (3, 3)] if neumann else [(3, 3), (4, 3)]
+    sizes += [(1024 + e, 1024 + e), (1025 + e, 1024 + e), (4096 + e, 9 + e)]
+    return sorted(set(sizes))
+
+
+@pytest.mark.parametrize("prec", list(PREC))
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+def test_identity_at_every_length_class(inst, neumann, prec):
+    """d = I, g = grad I, boundary = I: out = I within BOUND x max |I|, for lam in LAMS and C in 1, 3, 4"""
+    configure(inst, capi.SC_METHOD_FFT, PREC[prec])
+    bad, worst = [], 0.0
+    for W, H in identity_sizes(neumann):
+        for C in (1, 3, 4):
+            img = image(H, W, C, W * 7 + H * 13 + C)
+            gx, gy = screened_np.forward_differences(img)
+            R = float(np.abs(img).max())
+            for lam in LAMS:
+                out = inst.screened(img, gx=gx, gy=gy, lam=lam, boundary=None if neumann else img, neumann=neumann)
+                check_info(inst, W, H)
+                e = float(np.abs(out.astype(np.float64) - img).max()) / R
+                worst = max(worst, e)
+                if not (np.isfinite(out).all() and e <= BOUND[prec]):
+                    bad.append((W, H, C, lam, e))
+                if not neumann:
+                    assert frame_equal(out, img), (W, H, C, lam)
+    print(f"SCRID {'neumann' if neumann else 'dirichlet'} {prec}: worst max|out - I| / R = {worst:.3g} (bound {BOUND[prec]:g})")
+    assert not bad, bad[:8]
+
+
+# ---- 2. against the restatement -----------------------------------------------------------------------------------------------
+EXACT_SIZES = [(2, 2), (3, 3), (2, 41), (41, 3), (37, 29), (300, 200), (723, 722), (1280, 721), (4000, 143), (1030, 1026)]      # (W, H)
+
+
+def random_problem(H, W, C, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(-50, 300, (H, W, C)).astype(np.float32), rng.normal(0, 20, (H, W, C)).astype(np.float32),
+            rng.normal(0, 20, (H, W, C)).astype(np.float32), rng.uniform(-100, 400, (H, W, C)).astype(np.float32))
+
+
+@pytest.mark.parametrize("W,H", EXACT_SIZES)
+def test_random_inputs_against_the_restatement(inst, W, H):
+    fails = []
+    for neumann in (False, True):
+        if not neumann and min(W, H) < 3:
+            continue
+        kind = NEUMANN if neumann else DIRICHLET
+        for C, lam in ((1, 1e-3), (3, 0.1), (4, 10.0)):
+            d, gx, gy, b = random_problem(H, W, C, W * 11 + H * 17 + C)
+            lap = screened_np.divergence(kind, gx, gy)
+            yard = screened_bounds.Yardstick(lam, d, lap) if neumann else None
+            want = yard.want if neumann else screened_np.solve_exact(kind, lam, d, lap, b)
+            R = float(np.abs(want).max())
+            for prec in PREC:
+                configure(inst, capi.SC_METHOD_AUTO if prec == "fft32" and C == 3 else capi.SC_METHOD_FFT, PREC[prec])
+                out = inst.screened(d, gx=gx, gy=gy, lam=lam, boundary=None if neumann else b, neumann=neumann)
+                check_info(inst, W, H)
+                assert np.isfinite(out).all()
+                if neumann:
+                    bad, err, res = yard.check(out, prec == "fft64")
+                    print(f"SCR {W}x{H} C={C} lam={lam:g} neumann {prec}: ERR {err:.3g} RES {res:.3g} / solve_f32 {yard.err32:.3g} {yard.res32:.3g}")
+                    fails += [(W, H, C, lam, prec) + x for x in bad]
+                else:
+                    e = float(np.abs(out.astype(np.float64) - want).max()) / R
+                    print(f"SCR {W}x{H} C={C} lam={lam:g} dirichlet {prec}: max|out - want| / R {e:.3g}")
+                    if not e <= BOUND[prec]:
+                        fails.append((W, H, C, lam, prec, "ERR", e, BOUND[prec]))
+                    assert frame_equal(out, b)
+                # the LAPLACIAN form on numpy's divergence: the same bits
+                out_l = inst.screened(d, lap=lap, lam=lam, boundary=None if neumann else b, neumann=neumann)
+                assert np.array_equal(out_l, out), (W, H, C, lam, prec, kind)
+    assert not fails, fails
+
+
+def test_neither_laps_frame_nor_boundarys_interior_is_read_under_a_frame(inst):
+    """Dirichlet: lap and data are read on the interior only, boundary on its frame only -- NaNs elsewhere change nothing"""
+    configure(inst)
+    H, W, C = 45, 67, 3
+    d, gx, gy, b = random_problem(H, W, C, 3)
+    lap = screened_np.divergence(DIRICHLET, gx, gy)
+    ref = inst.screened(d, lap=lap, lam=0.3, boundary=b, neumann=False)
+    inner = np.zeros((H, W, C), bool)
+    inner[1:-1, 1:-1] = True
+    lap2, d2, b2 = lap.copy(), d.copy(), b.copy()
+    lap2[~inner] = np.nan
+    d2[~inner] = np.nan
+    b2[inner] = np.nan
+    out = inst.screened(d2, lap=lap2, lam=0.3, boundary=b2, neumann=False)
+    assert np.isfinite(out).all() and np.array_equal(out, ref)
+
+
+# ---- 3. the large-lam limit ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+@pytest.mark.parametrize("lam", [100.0, 1e4])
+def test_large_lambda_stays_at_the_data(inst, neumann, lam):
+    """(lam - A)(u - d) = A d - div g with u - d = 0 on the frame (boundary = d's frame), and lam - A is an M-matrix whose rows sum
+    to at least lam: max |u - d| <= max |div g - A d| / lam.  The right-hand side in float64; 1e-4 R of slack for float32 storage."""
+    kind = NEUMANN if neumann else DIRICHLET
+    for prec in PREC:
+        configure(inst, capi.SC_METHOD_FFT, PREC[prec])
+        for W, H, C in ((37, 29, 1), (300, 200, 3), (723, 722, 4)):
+            d, gx, gy, _ = random_problem(H, W, C, W + H + C)
+            out = inst.screened(d, gx=gx, gy=gy, lam=lam, boundary=None if neumann else d, neumann=neumann)
+            div = screened_np.divergence(kind, gx, gy).astype(np.float64)
+            Ad = screened_np.operator(kind, 1.0, d) + d.astype(np.float64) * (1.0 if neumann else (np.pad(np.ones((H - 2, W - 2, C)), ((1, 1), (1, 1), (0, 0)))))
+            limit = float(np.abs(div - Ad).max()) / lam
+            R = float(np.abs(d).max())
+            got = float(np.abs(out.astype(np.float64) - d).max())
+            print(f"SCRLIM {kind} {prec} {W}x{H} C={C} lam={lam:g}: max|u - d| {got:.4g} <= {limit:.4g} + {1e-4 * R:.3g}")
+            assert got <= limit + 1e-4 * R, (kind, prec, W, H, C)
+
+
+# ---- device calls ---------------------------------------------------------------------------------------------------------------
+class Dev:
+    """Device arrays of one call: each array at a 256-byte boundary of one block, with `guard` floats of sentinel on both sides."""
+
+    def __init__(self, inst, guard=64):
+        self.inst, self.guard, self.parts, self.at = inst, guard, [], 0
+
+    def add(self, host_flat):
+        off = self.at + 4 * self.guard
+        self.parts.append((off, host_flat))
+        self.at = (off + 4 * host_flat.size + 4 * self.guard + 255) // 256 * 256
+        return len(self.parts) - 1
+
+    def upload(self, sentinel=SENTINEL):
+        self.nfloat = self.at // 4 + 64
+        host = np.full(self.nfloat, sentinel, np.float32)
+        for off, a in self.parts:
+            host[off // 4:off // 4 + a.size] = a
+        self.host = host
+        self.d = self.inst.malloc(4 * self.nfloat)
+        self.inst._check(self.inst.L.sc_hip_memcpy_h2d(self.inst.h, self.d, host.ctypes.data, 4 * self.nfloat))
+
+    def ptr(self, k):
+        return self.d + self.parts[k][0]
+
+    def download(self):
+        return self.inst.from_device(self.d, (self.nfloat,), np.float32)
+
+    def free(self):
+        self.inst.free(self.d)
+
+
+LAYOUTS = {        # (col, row, channel stride, span) in floats of an H x W x C image
+    "hwc": lambda H, W, C: (C, C * W, 1, C * W * H),
+    "padded": lambda H, W, C: (C, C * W + 5, 1, (C * W + 5) * H),
+    "chw": lambda H, W, C: (1, W, W * H, C * W * H),
+    "rgba": lambda H, W, C: (4, 4 * W, 1, 4 * W * H),
+    "transposed": lambda H, W, C: (C * H, C, 1, C * W * H),
+}
+
+
+def _batch(inst, problems, lam, neumann, layout_kind="hwc", tamper=None, guidance=True, alias=None):
+    """problems: [(d, gx, gy, b)] H x W x C.  One sc_hip_screened_device call.  alias: "data" / "boundary": out is that array.
+    Returns (rc, outputs, jobs, info, memory after, memory before, named: the mask of the floats the call may have written)."""
+    H, W, C = problems[0][0].shape
+    cs, rs, chs, span = LAYOUTS[layout_kind](H, W, C)
+    st = (4 * rs, 4 * cs, 4 * chs)
+
+    def flat(a, fill=0.0):
+        f = np.full(span, fill, np.float32)
+        np.lib.stride_tricks.as_strided(f, shape=(H, W, C), strides=st)[...] = a
+        return f
+
+    kind = DIRICHLET if not neumann else NEUMANN
+    dev = Dev(inst)
+    ids = []
+    for d, gx, gy, b in problems:
+        kd = dev.add(flat(d, SENTINEL))
+        kb = None if neumann else dev.add(flat(b, SENTINEL))
+        ins = (dev.add(flat(gx)), dev.add(flat(gy))) if guidance else (dev.add(flat(screened_np.divergence(kind, gx, gy))),)
+        ko = kd if alias == "data" else kb if alias == "boundary" else dev.add(np.full(span, SENTINEL, np.float32))
+        ids.append((ins, kd, kb, ko))
+    dev.upload()
+    jobs = capi.Instance.make_screened_jobs(len(problems))
+    for j, (ins, kd, kb, ko) in zip(jobs, ids):
+        if guidance:
+            j.gx, j.gy = dev.ptr(ins[0]), dev.ptr(ins[1])
+        else:
+            j.lap = dev.ptr(ins[0])
+        j.data, j.boundary, j.out = dev.ptr(kd), None if kb is None else dev.ptr(kb), dev.ptr(ko)
+    if tamper:
+        tamper(jobs)
+    layout = capi.PoissonLayout(W, H, C, cs, rs, chs)
+    k = (G if guidance else L) | (NEU if neumann else 0)
+    try:
+        rc = inst.screened_device(capi.ScreenedParams(k, float(lam)), layout, jobs, sync=True, allow_job_errors=True)
+        info = inst.info()
+        full = dev.download()
+    finally:
+        dev.free()
+    outs = []
+    named = np.zeros(full.size, bool)
+    for (_, _, _, ko) in ids:
+        off = dev.parts[ko][0] // 4
+        outs.append(np.array(np.lib.stride_tricks.as_strided(full[off:off + span], shape=(H, W, C), strides=st)))
+        np.lib.stride_tricks.as_strided(named[off:off + span], shape=(H, W, C), strides=(rs, cs, chs))[...] = True
+    return rc, outs, jobs, info, full, dev.host, named
+
+
+def _problems(n, H, W, C, seed):
+    return [random_problem(H, W, C, seed * 1000 + 7 * k) for k in range(n)]
+
+
+def _solo(inst, p, lam, neumann):
+    d, gx, gy, b = p
+    return inst.screened(d, gx=gx, gy=gy, lam=lam, boundary=None if neumann else b, neumann=neumann)
+
+
+# ---- 4. batches ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prec", list(PREC))
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+@pytest.mark.parametrize("n,H,W,C", [(2, 48, 64, 1), (20, 61, 97, 2), (70, 30, 40, 3), (50, 21, 33, 4)])
+def test_batches_equal_their_solo_runs_bit_for_bit(inst, neumann, prec, n, H, W, C):
+    """(20 members: more than PoissonJobs::MAX = 16 per launch table; 70 x 3 and 50 x 4 planes: two chunks of at most 192 planes)"""
+    configure(inst, capi.SC_METHOD_FFT, PREC[prec])
+    ps = _problems(n, H, W, C, n + C)
+    rc, outs, jobs, info, full, before, named = _batch(inst, ps, 0.25, neumann)
+    assert rc == capi.SC_OK and all(j.rc == capi.SC_OK for j in jobs)
+    assert (info.method, info.sweeps, info.converged, info.W, info.H) == (capi.SC_METHOD_FFT, 1, 1, W, H)
+    assert info.ms_device_total > 0 and info.ms_solve > 0
+    assert np.array_equal(full[~named], before[~named])                 # inputs and guard bands untouched
+    for k in sorted({0, 1, 15, 16, 17, n // 2, 63, 64, n - 1} & set(range(n))):
+        assert np.array_equal(outs[k], _solo(inst, ps[k], 0.25, neumann)), k
+    assert all(np.isfinite(o).all() for o in outs)
+
+
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+def test_batch_with_a_member_without_data(inst, neumann):
+    configure(inst)
+    ps = _problems(5, 40, 52, 3, 77)
+
+    def tamper(jobs):
+        jobs[1].data = None
+        jobs[3].out = jobs[3].out + 2         # misaligned
+    rc, outs, jobs, info, full, before, named = _batch(inst, ps, 2.0, neumann, tamper=tamper)
+    assert rc == capi.SC_ERR_BAD_ARG
+    assert [j.rc for j in jobs] == [capi.SC_OK, capi.SC_ERR_BAD_ARG, capi.SC_OK, capi.SC_ERR_BAD_ARG, capi.SC_OK]
+    for k in (0, 2, 4):
+        assert np.array_equal(outs[k], _solo(inst, ps[k], 2.0, neumann)), k
+    for k in (1, 3):
+        assert (outs[k] == SENTINEL).all()
+    if not neumann:
+        def no_boundary(jobs):
+            jobs[0].boundary = None
+        rc, outs, jobs, *_ = _batch(inst, ps[:2], 2.0, False, tamper=no_boundary)
+        assert rc == capi.SC_ERR_BAD_ARG and [j.rc for j in jobs] == [capi.SC_ERR_BAD_ARG, capi.SC_OK]
+        assert (outs[0] == SENTINEL).all() and np.array_equal(outs[1], _solo(inst, ps[1], 2.0, False))
+
+
+# ---- 5. writes -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+@pytest.mark.parametrize("guidance", [True, False], ids=["guidance", "laplacian"])
+def test_layouts_write_only_what_they_name_and_aliasing_keeps_the_bits(inst, neumann, guidance):
+    configure(inst)
+    for C, kinds in ((3, ("hwc", "padded", "chw", "rgba", "transposed")), (1, ("hwc", "padded", "transposed")), (4, ("hwc", "chw"))):
+        ps = _problems(3, 53, 71, C, 5 + C)
+        ref = None
+        for lk in kinds:
+            for alias in (None, "data") + (() if neumann else ("boundary",)):
+                rc, outs, jobs, info, full, before, named = _batch(inst, ps, 0.7, neumann, layout_kind=lk, guidance=guidance, alias=alias)
+                assert rc == capi.SC_OK, (lk, alias)
+                assert np.array_equal(full[~named], before[~named]), (lk, alias)      # guards, padding, unused slots, inputs
+                if ref is None:
+                    ref = outs
+                    for k in range(3):
+                        assert np.array_equal(outs[k], _solo(inst, ps[k], 0.7, neumann))
+                for k in range(3):
+                    assert np.array_equal(outs[k], ref[k]), (lk, alias, k)
+                    if not neumann:
+                        assert frame_equal(outs[k], ps[k][3]), (lk, alias, k)
+
+
+def test_host_call_layouts_and_in_place(inst):
+    """the host call through numpy views: padding and unused channel slots of out keep their bytes, every layout the same bits"""
+    configure(inst)
+    H, W, C = 83, 101, 3
+    d, gx, gy, b = random_problem(H, W, C, 9)
+    for neumann in (False, True):
+        ref = _solo(inst, (d, gx, gy, b), 0.4, neumann)
+        for kind in ("chw", "padded", "rgba", "transposed"):
+            def make(content, fill=0.0):
+                if kind == "chw":
+                    buf = np.full((C, H, W), fill, np.float32); v = buf.transpose(1, 2, 0)
+                elif kind == "padded":
+                    buf = np.full((H, W + 5, C), fill, np.float32); v = buf[:, :W]
+                elif kind == "transposed":
+                    buf = np.full((W, H, C), fill, np.float32); v = buf.transpose(1, 0, 2)
+                else:
+                    buf = np.full((H, W, 4), fill, np.float32); v = buf[:, :, :C]
+                if content is not None:
+                    v[...] = content
+                return v, buf
+            vd, vx, vy, vb = make(d)[0], make(gx)[0], make(gy)[0], make(b)[0]
+            vo, obuf = make(None, SENTINEL)
+            before = obuf.copy()
+            got = inst.screened(vd, gx=vx, gy=vy, lam=0.4, boundary=None if neumann else vb, neumann=neumann, out=vo)
+            assert got is vo and np.array_equal(np.array(vo), ref), (kind, neumann)
+            named = np.ones(obuf.shape, bool)
+            if kind == "padded":
+                named[:, W:] = False
+            elif kind == "rgba":
+                named[:, :, C:] = False
+            assert np.array_equal(obuf[~named], before[~named]), (kind, neumann)
+        for which in ("data",) + (() if neumann else ("boundary",)):
+            dd, bb = d.copy(), b.copy()
+            o = dd if which == "data" else bb
+            got = inst.screened(dd, gx=gx, gy=gy, lam=0.4, boundary=None if neumann else bb, neumann=neumann, out=o)
+            assert got is o and np.array_equal(o, ref), (which, neumann)
+        i = inst.info()
+        assert i.ms_h2d > 0 and i.ms_d2h > 0 and i.ms_solve > 0 and i.ms_call >= i.ms_device_total
+
+
+# ---- 6. refusals -------------------------------------------------------------------------------------------------------------------
+def _refused(inst, code, lam, neumann, W=40, H=30, C=1):
+    d = np.zeros((H, W, C), np.float32)
+    out = np.full((H, W, C), SENTINEL, np.float32)
+    with pytest.raises(capi.SeamlessCloneError) as e:
+        params = capi.ScreenedParams(L | (NEU if neumann else 0), lam)
+        rc = inst.L.sc_hip_screened(inst.h, capi.C.byref(params), capi.C.byref(capi.poisson_layout_of(out)), None, None, d.ctypes.data,
+                                    d.ctypes.data, d.ctypes.data, out.ctypes.data)
+        inst._check(rc)
+    assert e.value.code == code
+    assert (out == SENTINEL).all()
+    # the device entry likewise
+    ps = [(d, d, d, d)]
+    rc, outs, jobs, *_ = _batch(inst, ps, lam, neumann)
+    assert rc == code and (outs[0] == SENTINEL).all()
+
+
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+@pytest.mark.parametrize("method", [capi.SC_METHOD_MULTIGRID, capi.SC_METHOD_DST, capi.SC_METHOD_SOR, capi.SC_METHOD_JACOBI,
+                                    capi.SC_METHOD_RBGS])
+def test_other_methods_are_refused_and_write_nothing(inst, neumann, method):
+    configure(inst, method)
+    _refused(inst, capi.SC_ERR_BAD_ARG, 1.0, neumann)
+
+
+@pytest.mark.parametrize("neumann", [False, True], ids=["dirichlet", "neumann"])
+@pytest.mark.parametrize("lam", [0.0, -1.0, float("nan"), float("inf")])
+def test_bad_lambda_is_refused_and_writes_nothing(inst, neumann, lam):
+    configure(inst)
+    _refused(inst, capi.SC_ERR_BAD_ARG, lam, neumann)
+
+
+def test_sides_beyond_the_transforms_are_refused_and_write_nothing(inst):
+    configure(inst)
+    _refused(inst, capi.SC_ERR_BAD_SIZE, 1.0, True, W=8193, H=4)
+    _refused(inst, capi.SC_ERR_BAD_SIZE, 1.0, True, W=4, H=8193)
+    _refused(inst, capi.SC_ERR_BAD_SIZE, 1.0, False, W=8195, H=5)
+    configure(inst, capi.SC_METHOD_FFT, capi.SC_FLAG_FFT_FP64)
+    _refused(inst, capi.SC_ERR_BAD_SIZE, 1.0, True, W=4097, H=4)
+    _refused(inst, capi.SC_ERR_BAD_SIZE, 1.0, False, W=5, H=4099)
+    # ... and the last sizes inside run: 4096 pixels (Neumann), 4096 unknowns (Dirichlet) in double; 8192 in float32
+    for flags, n in ((capi.SC_FLAG_FFT_FP64, 4096), (0, 8192)):
+        configure(inst, capi.SC_METHOD_FFT, flags)
+        for neumann in (True, False):
+            W = n + (0 if neumann else 2)
+            img = image(5, W, 1, n)
+            gx, gy = screened_np.forward_differences(img)
+            out = inst.screened(img, gx=gx, gy=gy, lam=0.1, boundary=None if neumann else img, neumann=neumann)
+            assert float(np.abs(out.astype(np.float64) - img).max()) <= BOUND["fft64" if flags else "fft32"] * float(np.abs(img).max())
+
+
+def test_the_instance_after_a_screened_call():
+    """the stored options are those before the call, and an unscreened Poisson call returns the bits it returned before"""
+    inst = capi.Instance(0)
+    try:
+        H, W, C = 120, 160, 3
+        d, gx, gy, b = random_problem(H, W, C, 21)
+        runs = {}
+        for name, (method, flags) in {"auto": (capi.SC_METHOD_AUTO, 0), "fft32": (capi.SC_METHOD_FFT, 0),
+                                      "fft64": (capi.SC_METHOD_FFT, capi.SC_FLAG_FFT_FP64)}.items():
+            configure(inst, method, flags)
+            runs[name] = (inst.poisson(b, gx=gx, gy=gy, tol=1e-3), inst.poisson(b, gx=gx, gy=gy, neumann=True))
+        for name, (method, flags) in {"auto": (capi.SC_METHOD_AUTO, 0), "fft32": (capi.SC_METHOD_FFT, 0),
+                                      "fft64": (capi.SC_METHOD_FFT, capi.SC_FLAG_FFT_FP64)}.items():
+            configure(inst, method, flags)
+            before = inst.get_solver()
+            for neumann in (False, True):
+                inst.screened(d, gx=gx, gy=gy, lam=3.0, boundary=b, neumann=neumann)
+                after = inst.get_solver()
+                for f, _ in capi.SolverOpts._fields_:
+                    va, vb = getattr(after, f), getattr(before, f)
+                    assert (list(va) == list(vb)) if hasattr(va, "__len__") else (va == vb), f
+                assert np.array_equal(inst.poisson(b, gx=gx, gy=gy, tol=1e-3), runs[name][0]), (name, neumann)
+                assert np.array_equal(inst.poisson(b, gx=gx, gy=gy, neumann=True), runs[name][1]), (name, neumann)
+    finally:
+        inst.destroy()
+
+
+# ---- 7. the Python surface ------------------------------------------------------------------------------------------------------
+def test_gradient_filter_and_the_solve_functions():
+    img = image(150, 210, 3, 4)
+    R = float(np.abs(img).max())
+    for neumann in (True, False):
+        for lam in (1e-3, 0.5):
+            out = seamless_clone.gradient_filter(img, 1.0, lam, neumann=neumann, method=capi.SC_METHOD_FFT)
+            assert out is not img and float(np.abs(out.astype(np.float64) - img).max()) <= BOUND["fft32"] * R, (neumann, lam)
+    # gain 2, Neumann, lam = 0.5 against the restatement
+    gx, gy = screened_np.forward_differences(img)
+    gx, gy = np.float32(2.0) * gx, np.float32(2.0) * gy
+    yard = screened_bounds.Yardstick(0.5, img, screened_np.divergence(NEUMANN, gx, gy))
+    out = seamless_clone.gradient_filter(img, 2.0, 0.5)
+    bad, err, res = yard.check(out, False)
+    assert not bad, bad
+    assert np.array_equal(out, seamless_clone.screened_solve(img, gx=gx, gy=gy, lam=0.5))
+    # sharpening raises the gradients, flattening lowers them
+    tv = lambda a: float(np.abs(np.diff(a.astype(np.float64), axis=1)).mean())
+    assert tv(out) > tv(img) > tv(seamless_clone.gradient_filter(img, 0.5, 0.5))
+    # the batch function: its members are the solo solves
+    ps = _problems(3, 40, 56, 3, 8)
+    for neumann in (True, False):
+        outs = seamless_clone.screened_solve_batch([p[0] for p in ps], gxs=[p[1] for p in ps], gys=[p[2] for p in ps], lam=0.2,
+                                                   boundaries=None if neumann else [p[3] for p in ps], neumann=neumann)
+        for p, o in zip(ps, outs):
+            assert np.array_equal(o, seamless_clone.screened_solve(p[0], gx=p[1], gy=p[2], lam=0.2, boundary=None if neumann else p[3],
+                                                                   neumann=neumann))
