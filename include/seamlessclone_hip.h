@@ -462,17 +462,48 @@ SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int str
  * sc_run_info: method SC_METHOD_FFT, sweeps 1, converged 1; ms_pre = the boundary-mean reduction, ms_post ~ 0 (the last transform
  * launch stores into out).  tol is validated and otherwise unused.  Sizes: cols, rows >= 2; at most 8192 per side, 4096 with
  * SC_FLAG_FFT_FP64 (SC_ERR_BAD_SIZE beyond; sc_hip_poisson_check, which knows no instance, reports the 8192 limit).  Batches: one
- * field of n x channels planes in the same chunks; a member equals its solo run bit for bit, always. */
+ * field of n x channels planes in the same chunks; a member equals its solo run bit for bit, always.
+ *
+ * SC_POISSON_FREE_LEFT / _RIGHT / _TOP / _BOTTOM (or'ed into either kind): per-side free borders -- a region that touches the image
+ * edge, a strip pinned at its two ends, a gradient field anchored on one side.  A side without its bit is a Dirichlet line: the whole
+ * outermost row or column there, corners included, holds known values taken from boundary.  A side with its bit has no frame: its
+ * outermost pixels are unknowns and the stencil lacks the neighbour beyond them (u(outside) = u(pixel)).  Unknowns per axis: pixels
+ * less the axis's Dirichlet lines.  No bit: the Dirichlet call above, unchanged.  All four bits, with or without SC_POISSON_NEUMANN
+ * (which stays the union with any of them): the Neumann call above, bit for bit.  The 14 combinations between:
+ * SC_POISSON_GUIDANCE: lap(q) = (a - b) + (c - d) in float32, a = gx(q) (0 when q is in the last column and the right side is free),
+ * b = gx(q - x) (0 when q is in column 0 and the left side is free), c and d likewise from gy with bottom and top: both formulas
+ * above at the two extremes.  Forward differences of an image I, with I as boundary, give back I under every combination; gx's last
+ * column and gy's last row are never read.  SC_POISSON_LAPLACIAN: lap is read at every unknown and nowhere else.  An unknown next to
+ * a Dirichlet line has that line's value subtracted from its right-hand side.
+ * boundary: required as soon as one side is a Dirichlet line; only its Dirichlet lines are read (its interior and its lines on free
+ * sides never).  The system is regular: no mean is taken, no constant is free.  out: boundary's values, bit for bit, on the Dirichlet
+ * lines (corners where two meet included), the solution at every unknown; out may equal boundary.
+ * Solved directly, each axis under the transform of its two ends: DST-I between two Dirichlet lines, DCT-II / III between two free
+ * ends, and between a Dirichlet line and a free end the sine transform S[k][j] = sin(pi (2k+1) (j+1) / (2n+1)) (eigenvalues
+ * 2 cos(pi (2k+1) / (2n+1)) - 2), all by the chirp convolution of SC_METHOD_FFT, the coefficients divided by the sum of the two
+ * axes' eigenvalues in double; float32 transforms, or double with SC_FLAG_FFT_FP64.  Methods: SC_METHOD_AUTO (resolves to
+ * SC_METHOD_FFT at every size and batch size) and SC_METHOD_FFT; any other method: SC_ERR_BAD_ARG, nothing written.  Sizes: cols,
+ * rows >= 2, at least 1 and at most 8192 unknowns per axis, 4096 with SC_FLAG_FFT_FP64 (SC_ERR_BAD_SIZE beyond;
+ * sc_hip_poisson_check reports the float32 limits).  tol is validated and otherwise unused.  sc_run_info and the stage times: the
+ * Neumann call's, ms_pre and ms_post ~ 0.  Batches: the same chunks; a member equals its solo run bit for bit, always.
+ * The lowest eigenvalue of an axis with one Dirichlet end is ~(pi / (2n+1))^2, a quarter of the Dirichlet axis's: long thin float32
+ * problems pinned at one far end lose accuracy sooner than either other kind. */
 #define SC_POISSON_GUIDANCE  1   /* gx, gy given (gx read at columns 0..cols-2, gy at rows 0..rows-2) */
 #define SC_POISSON_LAPLACIAN 2   /* lap given                                                          */
 #define SC_POISSON_NEUMANN   (1 << 8)   /* or'ed into SC_POISSON_GUIDANCE / SC_POISSON_LAPLACIAN: reflecting border, no Dirichlet frame */
+/* or'ed into either kind: that side has no Dirichlet line -- its outermost pixels are unknowns and the stencil reflects there.  All four
+ * are SC_POISSON_NEUMANN.  (Bits 9..11 are not kinds.) */
+#define SC_POISSON_FREE_LEFT   (1 << 12)   /* column 0        */
+#define SC_POISSON_FREE_RIGHT  (1 << 13)   /* column cols - 1 */
+#define SC_POISSON_FREE_TOP    (1 << 14)   /* row 0           */
+#define SC_POISSON_FREE_BOTTOM (1 << 15)   /* row rows - 1    */
 #define SC_POISSON_MAX_PLANES 192
 typedef struct sc_poisson_layout {
     int cols, rows, channels;                            /* >= 3, >= 3 (SC_POISSON_NEUMANN: >= 2, <= 8192), 1..4 */
     long long col_stride, row_stride, channel_stride;    /* in floats                         */
 } sc_poisson_layout;
 typedef struct sc_poisson_params {
-    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN */
+    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN or SC_POISSON_FREE_* bits */
     float tol;               /* the multigrid stop rule's update_tol for this call, in the data's units; <= 0: 1e-3 */
 } sc_poisson_params;
 typedef struct sc_poisson_job {
@@ -521,7 +552,10 @@ SC_API int sc_hip_poisson(void *instance, const sc_poisson_params *p, const sc_p
  * pointer the kind needs -- data always, boundary under a frame.
  * sc_run_info: method SC_METHOD_FFT, sweeps 1, converged 1, W x H = the image; stage times when bSync is set and for the host call
  * (under a frame ms_pre = the pre-process, ms_post = the output launch; SC_POISSON_NEUMANN: both ~ 0, the transform launches read
- * and write the caller's arrays).  The instance's stored options are unchanged by the call. */
+ * and write the caller's arrays).  The instance's stored options are unchanged by the call.
+ * SC_POISSON_FREE_* bits: the same per-side borders as in sc_hip_poisson, the denominators shifted by -lambda; data and lap (or the
+ * guidance) are read at every unknown, boundary on its Dirichlet lines only and required if and only if some side is one; sizes, methods
+ * and stage times as there. */
 typedef struct sc_screened_params {
     int kind;                /* as sc_poisson_params.kind, SC_POISSON_NEUMANN included */
     float lambda;            /* the data term's weight: finite, > 0 */

@@ -123,6 +123,25 @@ class EditJob(C.Structure):
 SC_POISSON_GUIDANCE = 1
 SC_POISSON_LAPLACIAN = 2
 SC_POISSON_NEUMANN = 1 << 8          # or'ed into either kind: reflecting border, every pixel an unknown
+SC_POISSON_FREE_LEFT = 1 << 12       # or'ed into either kind: that side has no Dirichlet line, its outermost pixels are unknowns
+SC_POISSON_FREE_RIGHT = 1 << 13      # (all four: the Neumann problem)
+SC_POISSON_FREE_TOP = 1 << 14
+SC_POISSON_FREE_BOTTOM = 1 << 15
+SC_POISSON_FREE_ALL = SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM
+_FREE_SIDE_BITS = {"l": SC_POISSON_FREE_LEFT, "r": SC_POISSON_FREE_RIGHT, "t": SC_POISSON_FREE_TOP, "b": SC_POISSON_FREE_BOTTOM}
+
+
+def free_side_bits(free_sides="", neumann=False) -> int:
+    """The SC_POISSON_FREE_* bits of a string over the letters "lrtb" (left, right, top, bottom; order and repeats do not matter).
+    neumann=True is "lrtb" and reads SC_POISSON_NEUMANN.  Anything else raises ValueError."""
+    if not isinstance(free_sides, str):
+        raise ValueError('free_sides must be a string over the letters "lrtb"')
+    bits = 0
+    for ch in free_sides:
+        if ch not in _FREE_SIDE_BITS:
+            raise ValueError(f'free_sides: {ch!r} is none of the letters "lrtb"')
+        bits |= _FREE_SIDE_BITS[ch]
+    return SC_POISSON_NEUMANN if neumann else bits
 SC_POISSON_MAX_PLANES = 192
 
 
@@ -369,19 +388,21 @@ def poisson_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, layout: "Po
     return int(load().sc_hip_poisson_check(C.byref(PoissonParams(int(kind), float(tol))), C.byref(layout)))
 
 
-def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False):
+def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False, free_sides=""):
     """Checks a Poisson problem's numpy arrays before any device is touched: (kind, layout, boundary, gx, gy, lap, out) with every array
     float32 and of boundary's shape.  The layout is numpy's strides when all arrays share them; otherwise the arrays are made
     contiguous (out then stays the caller's and is written back by the caller: see Instance.poisson).  neumann: the kind carries
-    SC_POISSON_NEUMANN and boundary may be None (the shape is then gx's or lap's)."""
+    SC_POISSON_NEUMANN and boundary may be None (the shape is then gx's or lap's).  free_sides: the sides without a Dirichlet line,
+    a string over "lrtb" (free_side_bits); all four are the Neumann problem, with fewer boundary is required."""
+    free = free_side_bits(free_sides, neumann)
+    neumann = neumann or free == SC_POISSON_FREE_ALL
     if (gx is None) != (gy is None):
         raise ValueError("gx and gy go together")
     if (gx is None) == (lap is None):
         raise ValueError("give either gx and gy or lap")
     kind = SC_POISSON_LAPLACIAN if lap is not None else SC_POISSON_GUIDANCE
-    if neumann:
-        kind |= SC_POISSON_NEUMANN
-    elif boundary is None:
+    kind |= free
+    if boundary is None and not neumann:
         raise ValueError("boundary may be None only for a Neumann problem (neumann=True)")
     arrays = {"boundary": boundary, "gx": gx, "gy": gy, "lap": lap, "out": out}
     first = boundary if boundary is not None else (lap if lap is not None else gx)
@@ -410,19 +431,20 @@ def screened_check(kind: int = SC_POISSON_GUIDANCE, lam: float = 1.0, layout: "P
     return int(load().sc_hip_screened_check(C.byref(ScreenedParams(int(kind), float(lam))), C.byref(layout)))
 
 
-def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False):
+def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False, free_sides=""):
     """Checks a screened problem's numpy arrays and lambda before any device is touched: (kind, data, gx, gy, lap, boundary, out), every
     array float32 and of data's shape (poisson_arrays' rules).  A Dirichlet problem (neumann=False) needs boundary; a Neumann one
-    ignores it."""
+    ignores it.  free_sides: as poisson_arrays'; with a Dirichlet line left on any side boundary is required."""
+    all_free = neumann or free_side_bits(free_sides) == SC_POISSON_FREE_ALL
     if data is None:
         raise ValueError("a screened solve needs its data term")
     if lam is None or not np.isfinite(lam) or not lam > 0:
         raise ValueError("lam must be finite and > 0")
-    if neumann:
+    if all_free:
         boundary = None
     elif boundary is None:
         raise ValueError("a Dirichlet screened solve needs boundary (neumann=True: none)")
-    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann)
+    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides)
     if boundary is not None:
         if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
             raise TypeError("boundary must be a float32 numpy array")
@@ -580,13 +602,15 @@ class Instance:
         return int(counts[0]), int(counts[1])
 
     # ---- the Poisson solver on float32 arrays
-    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False, neumann=False):
+    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False, neumann=False, free_sides=""):
         """sc_hip_poisson on numpy float32 arrays of shape H x W or H x W x C (C 1..4): solve lap(u) = div (gx, gy) (or = lap) with
         u = boundary on the frame; boundary's interior is the initial guess of the iterative methods.  out: an array of boundary's
         shape to write (may be boundary itself), default a new one.  Returns out.
         neumann: the reflecting problem on every pixel (SC_POISSON_NEUMANN); mean(out) = mean(boundary) per channel, boundary may be
-        None (mean zero; shape and layout then come from gx / lap)."""
-        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann)
+        None (mean zero; shape and layout then come from gx / lap).
+        free_sides: the sides without a Dirichlet line, a string over "lrtb" (SC_POISSON_FREE_*): their outermost pixels are unknowns,
+        the other sides' outermost rows and columns keep boundary's values; a direct solve, tol unused."""
+        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann, free_sides)
         first = boundary if boundary is not None else (lap if lap is not None else gx)
         if out is None:
             out = np.empty_like(first)
@@ -624,12 +648,12 @@ class Instance:
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
     # ---- screened Poisson solves on float32 arrays
-    def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None):
+    def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None, free_sides=""):
         """sc_hip_screened on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise lam sum (u - data)^2 +
         sum |grad u - (gx, gy)|^2 (or with the divergence given as lap), with u = boundary on the frame, or, neumann, reflected at the
         border (boundary then unused).  out: an array of data's shape to write (may be data or boundary), default a new one.
-        Returns out."""
-        kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann)
+        free_sides: as poisson's (boundary is read on the remaining Dirichlet lines).  Returns out."""
+        kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann, free_sides)
         if out is None:
             out = np.empty_like(data)
         given = [a for a in (data, gx, gy, lap, boundary, out) if a is not None]

@@ -251,6 +251,27 @@ int main()
             { SC_POISSON_NEUMANN, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
             { SC_POISSON_NEUMANN | 3, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
             { (1 << 9) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            // SC_POISSON_FREE_*: any combination on a base kind; per axis 1 .. 8192 unknowns = pixels less its Dirichlet lines
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 640, 480, 3, 3, 3 * 640, 1, SC_OK },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM, 0.f, 640, 480, 3, 1, 640, 640 * 480, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_NEUMANN | SC_POISSON_FREE_LEFT, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },      // the union: all four
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_RIGHT, 0.f, 2, 3, 1, 1, 2, 6, SC_OK },                           // 1 x 1 unknowns
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_RIGHT, 0.f, 2, 2, 1, 1, 2, 4, SC_ERR_BAD_SIZE },                 // no unknown between top and bottom
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_TOP, 0.f, 2, 8, 1, 1, 2, 16, SC_ERR_BAD_SIZE },                  // none between left and right
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_TOP, 0.f, 8, 1, 1, 1, 8, 8, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 8193, 8, 1, 1, 8193, 8 * 8193, SC_OK },               // 8192 unknowns beside one Dirichlet line
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 8194, 8, 1, 1, 8194, 8 * 8194, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 8, 8194, 1, 1, 8, 8 * 8194, SC_OK },                  // ... between two
+            { SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 8, 8195, 1, 1, 8, 8 * 8195, SC_ERR_BAD_SIZE },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT, 0.f, 8192, 8, 1, 1, 8192, 8 * 8192, SC_OK },   // ... beside none
+            { SC_POISSON_LAPLACIAN | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT, 0.f, 8193, 8, 1, 1, 8193, 8 * 8193, SC_ERR_BAD_SIZE },
+            { SC_POISSON_FREE_LEFT, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },                           // no base kind
+            { SC_POISSON_FREE_LEFT | 3, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 9) | SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 11) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 16) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
         };
         for (const Case &k : cases) {
             sc_poisson_params p{ k.kind, k.tol };
@@ -282,6 +303,15 @@ int main()
             { G, 1.f, 3, 3, 1, 1, 3, 9, SC_OK },
             { G, 1.f, 8194, 3, 1, 1, 8194, 3 * 8194, SC_OK },               // 8192 unknowns per side
             { Lp, 1.f, 3, 8195, 1, 1, 3, 3 * 8195, SC_ERR_BAD_SIZE },
+            // SC_POISSON_FREE_*
+            { G | SC_POISSON_FREE_LEFT, 1.f, 640, 480, 3, 3, 1920, 1, SC_OK },
+            { Lp | SC_POISSON_FREE_TOP | SC_POISSON_FREE_RIGHT, 1e-3f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { G | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM, 1.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { G | SC_POISSON_FREE_BOTTOM, 1.f, 3, 8193, 1, 1, 3, 3 * 8193, SC_OK },
+            { G | SC_POISSON_FREE_BOTTOM, 1.f, 3, 8194, 1, 1, 3, 3 * 8194, SC_ERR_BAD_SIZE },
+            { G | SC_POISSON_FREE_BOTTOM, 1.f, 2, 8, 1, 1, 2, 16, SC_ERR_BAD_SIZE },
+            { G | SC_POISSON_FREE_BOTTOM, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { (1 << 9) | G | SC_POISSON_FREE_BOTTOM, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
         };
         for (const Case &k : cases) {
             sc_screened_params p{ k.kind, k.lambda };

@@ -83,6 +83,13 @@ void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream
 struct PoissonGeo { int W, H, C; long long cs, rs, chs; };
 struct PoissonJobDev { const float *gx, *gy, *lap, *b; float *out; const float *d = nullptr; };      // d: a screened solve's data term
 struct PoissonJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; };
+// A call with free (reflecting) sides on some but not all of the four borders (SC_POISSON_FREE_*): per axis its kind -- 0: Dirichlet
+// lines at both ends, 1: both ends free, 2: a Dirichlet line at the low end (column or row 0) and a free high end, 3: the reverse --
+// and its number of unknowns, pixels less the axis's Dirichlet lines.  (Kind 0 on both axes is the Dirichlet call, kind 1 on both the
+// Neumann call: neither comes here.)
+struct MixedGeo { int ax, ay, nx, ny; };
+__host__ __device__ __forceinline__ bool mixed_low_d(int k) { return k == 0 || k == 2; }
+__host__ __device__ __forceinline__ bool mixed_high_d(int k) { return k == 0 || k == 3; }
 // a screened solve's right-hand side (sc_screened_api.cpp): rhs - lam d in float32, one multiply, then one subtract -- never one fused
 // multiply-add, whatever the translation unit's contraction setting (the product is opaque to the optimiser)
 __device__ __forceinline__ float screened_rhs(float rhs, float lam, float d)

@@ -459,6 +459,153 @@ static hipError_t dct_opt_in_lds(int bytes)
     return e;
 }
 
+// ---- free sides on some of the four borders (SC_POISSON_FREE_*): each axis has its own transform -----------------------------------
+// Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
+// above; kind 2, a Dirichlet line at the low end and a free high end, the sine transform of odd half-frequencies
+//     S[k][j] = sin(pi (2k+1) (j+1) / (2n+1)),   k, j < n,    S S^T = (2n+1)/4 I,    eigenvalue 2 cos(pi (2k+1) / (2n+1)) - 2;
+// kind 3 is kind 2 with the spatial index reversed.  With N = 2n+1, c_m = exp(i pi m^2 / N), a_k = exp(i pi (k^2 + 2k) / N) and
+// b_j = exp(i pi (j^2 + j + 1) / N) (FftDim kind 2: a where kind 1 keeps the chirp, b where it keeps the half-sample twiddles),
+//     forward   X_k = Im[ a_k sum_j (x_j b_j) conj(c_{k-j}) ]          inverse   x_j = (4/N) Im[ b_j sum_k (X_k a_k) conj(c_{j-k}) ]
+// -- S is not symmetric: forward sums over j, inverse over k, as DCT-II and DCT-III.  So every kind is: multiply by one table, convolve
+// (chirp_convolve unchanged), multiply by another, keep the imaginary part (the real one for kind 1); the inverse swaps the tables.
+// Data sit at S[off .. off + n), off = 1 for kind 0 (its indices run from 1) and 0 otherwise.
+
+// what the forward transform multiplies sample j by in front of the convolution (and the inverse's result j behind it) ...
+template <typename T>
+__device__ __forceinline__ cx2<T> mix_tab_j(const FftPlan<T> &P, int kind, int j)
+{
+    return P.chirp[kind == 0 ? j + 1 : kind == 1 ? j : P.n + 1 + j];
+}
+// ... and coefficient k behind it (the inverse: in front)
+template <typename T>
+__device__ __forceinline__ cx2<T> mix_tab_k(const FftPlan<T> &P, int kind, int k)
+{
+    return P.chirp[kind == 0 ? k + 1 : kind == 1 ? P.n + 1 + k : k];
+}
+template <typename T>
+__device__ __forceinline__ T mix_part(int kind, cx2<T> t, cx2<T> y)      // Re(t y) for kind 1, Im(t y) otherwise
+{
+    return kind == 1 ? t.x * y.x - t.y * y.y : t.x * y.y + t.y * y.x;
+}
+// eigenvalue k (0-based) of an axis of n unknowns, in double
+__device__ __forceinline__ double mix_eig(int kind, int k, int n)
+{
+    const double a = kind == 0 ? (double)(k + 1) / (double)(n + 1) : kind == 1 ? (double)k / (double)n : (double)(2 * k + 1) / (double)(2 * n + 1);
+    return 2.0 * cospi(a) - 2.0;
+}
+
+// the system's right-hand side at the unknown at pixel (x, y): the divergence (dct_rhs: an unknown in column 0 or the last column exists
+// only where that side is free), the data term of a screened solve, then the neighbouring Dirichlet lines' values folded in as fft_g does
+template <bool LAP, bool SCR>
+__device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg, const PoissonJobDev &j, int c, int x, int y, float lam)
+{
+    const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
+    float v = dct_rhs<LAP>(g, j, c, x, y);
+    if constexpr (SCR) v = screened_rhs(v, lam, j.d[o]);
+    if (x == 1 && mixed_low_d(mg.ax)) v -= j.b[o - g.cs];
+    if (y == 1 && mixed_low_d(mg.ay)) v -= j.b[o - g.rs];
+    if (x == g.W - 2 && mixed_high_d(mg.ax)) v -= j.b[o + g.cs];
+    if (y == g.H - 2 && mixed_high_d(mg.ay)) v -= j.b[o + g.rs];
+    return v;
+}
+
+// MODE 0: row r of unknowns, its right-hand side from the jobs' arrays -> forward x transform -> out[p][r][k] (tstore: out[p][k][r])
+// MODE 1: rows of `in` (the transposed plane: row = x coefficient, entries = y) -> forward y transform, / (eigenvalue sum - lam), inverse
+//         y transform -> out, as MODE 0
+// MODE 2: rows of `in` [p][y][k] -> inverse x transform, scale -> the unknowns of the job's out; the same workgroup copies the ends of
+//         its pixel row that lie on Dirichlet lines, and the first / last one the whole top / bottom line, from boundary to out
+// rows: the other axis's unknowns.  SCR: as k_dct's (MODE 2 has no screened form).
+template <int MODE, typename T, bool LAP, bool SCR = false>
+__global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g, MixedGeo mg, PoissonJobs jobs, const T *__restrict__ in,
+                                                     T *__restrict__ out, int rows, double scale, int tstore, float lam)
+{
+    static_assert(!SCR || MODE != 2, "the last transform launch knows no screening");
+    extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
+    cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
+    const int tid = threadIdx.x, r = blockIdx.x, p = blockIdx.y, n = P.n;
+    const int kind = (MODE == 1) ? mg.ay : mg.ax;          // of the axis this launch transforms
+    const int off = kind == 0 ? 1 : 0;
+    const bool flip = kind == 3;                            // spatial index n - 1 - j
+    const T *__restrict__ src = (MODE == 0) ? nullptr : in + ((size_t)p * rows + r) * n;
+    const int member = p / g.C, c = p - member * g.C;
+    const PoissonJobDev &J = jobs.j[(MODE == 1) ? 0 : member];
+    const int x0 = mixed_low_d(mg.ax) ? 1 : 0, y0 = mixed_low_d(mg.ay) ? 1 : 0;
+    for (int i = tid; i < P.M; i += FFT_THREADS) {
+        cx2<T> a = mk<T>((T)0, (T)0);
+        const int j = i - off;
+        if (j >= 0 && j < n) {
+            T x;
+            cx2<T> t;
+            if constexpr (MODE == 0) {
+                x = (T)mix_rhs<LAP, SCR>(g, mg, J, c, x0 + (flip ? n - 1 - j : j), y0 + r, lam);
+                t = mix_tab_j<T>(P, kind, j);
+            } else if constexpr (MODE == 1) {
+                x = src[flip ? n - 1 - j : j];
+                t = mix_tab_j<T>(P, kind, j);
+            } else {
+                x = src[j];
+                if (kind == 1 && j == 0) x *= (T)0.5;
+                t = mix_tab_k<T>(P, kind, j);
+            }
+            a = mk<T>(x * t.x, x * t.y);
+        }
+        S[fft_pad(i)] = a;
+    }
+    __syncthreads();
+    chirp_convolve<T>(S, P, tid);
+    if (MODE == 1) {
+        // coefficient k of column r: divide by the two axes' eigenvalues (in double; never zero: some side is a Dirichlet line) and feed the
+        // quotient into the inverse transform, the column resident in LDS (element off + k is read and rewritten by one thread)
+        const double ex = mix_eig(mg.ax, r, rows);
+        for (int k = tid; k < n; k += FFT_THREADS) {
+            const cx2<T> t = mix_tab_k<T>(P, kind, k);
+            const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
+            const double eig = ex + mix_eig(kind, k, n);
+            T q = X / (T)(SCR ? eig - (double)lam : eig);
+            if (kind == 1 && k == 0) q *= (T)0.5;
+            S[fft_pad(off + k)] = mk<T>(q * t.x, q * t.y);
+        }
+        for (int i = tid; i < P.M; i += FFT_THREADS) if (i < off || i >= off + n) S[fft_pad(i)] = mk<T>((T)0, (T)0);
+        __syncthreads();
+        chirp_convolve<T>(S, P, tid);
+    }
+    for (int k = tid; k < n; k += FFT_THREADS) {
+        const cx2<T> t = (MODE == 0) ? mix_tab_k<T>(P, kind, k) : mix_tab_j<T>(P, kind, k);
+        const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
+        const int at = (MODE != 0 && flip) ? n - 1 - k : k;          // results of an inverse transform are spatial
+        if (MODE == 2) J.out[(long long)(x0 + at) * g.cs + (long long)(y0 + r) * g.rs + (long long)c * g.chs] = (float)(X * (T)scale);
+        else if (tstore) out[((size_t)p * n + at) * rows + r] = X;
+        else out[((size_t)p * rows + r) * n + at] = X;
+    }
+    if (MODE == 2) {
+        // the Dirichlet lines of out, boundary's bit for bit (out may be boundary: the same values again)
+        const long long oc = (long long)c * g.chs, row = (long long)(y0 + r) * g.rs;
+        if (tid == 0 && mixed_low_d(mg.ax)) J.out[row + oc] = J.b[row + oc];
+        if (tid == 1 && mixed_high_d(mg.ax)) J.out[(long long)(g.W - 1) * g.cs + row + oc] = J.b[(long long)(g.W - 1) * g.cs + row + oc];
+        if (r == 0 && mixed_low_d(mg.ay))
+            for (int x = tid; x < g.W; x += FFT_THREADS) J.out[(long long)x * g.cs + oc] = J.b[(long long)x * g.cs + oc];
+        if (r == rows - 1 && mixed_high_d(mg.ay))
+            for (int x = tid; x < g.W; x += FFT_THREADS) {
+                const long long o = (long long)x * g.cs + (long long)(g.H - 1) * g.rs + oc;
+                J.out[o] = J.b[o];
+            }
+    }
+}
+
+template <typename T>
+static hipError_t mix_opt_in_lds(int bytes)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<1, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<2, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    // the screened forms
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<1, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e;
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 // The circular convolution's length for n unknowns: the shortest M = r 2^k >= 2n - 1 with r in {1, 3, 5} (round 5; powers of two only
 // until then: 592 unknowns -> 2048 where 1280 does, 300 -> 1024 where 640 does).  The reference hands cuFFT 2n + 2 whatever it is
@@ -505,7 +652,9 @@ struct FftBuildPair { FftBuild<TC, T> b[2]; };
 
 // KIND 0: the DST-I's tables (chirp of period N = 2(n + 1)).  KIND 1: the DCT-II / DCT-III's (N = 2n): the same chirp kernel and
 // transform with that period, and behind chirp[0 .. n] the half-sample twiddle times the chirp, h_k = exp(i pi k / 2n) c_k =
-// exp(i pi k (k + 1) / 2n), k < n (phase reduced in integers like the chirp's).
+// exp(i pi k (k + 1) / 2n), k < n (phase reduced in integers like the chirp's).  KIND 2: the sine transform of a Dirichlet end paired with
+// a free end (k_mix; odd period N = 2n + 1): the chirp kernel of that period, and in the two tables' places a_k = exp(i pi (k^2 + 2k) / N)
+// and b_j = exp(i pi (j^2 + j + 1) / N), k, j < n, reduced modulo 2N likewise.
 template <typename TC, typename T, int KIND>
 __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> bp)
 {
@@ -514,17 +663,17 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
     const FftBuild<TC, T> &B = bp.b[blockIdx.x];
     const FftPlan<TC> &P = B.P;
     const int tid = threadIdx.x, n = P.n, M = P.M;
-    const long long N2 = KIND ? 4LL * n : 4LL * (n + 1);
-    const int N = KIND ? 2 * n : 2 * (n + 1);
+    const long long N2 = KIND == 2 ? 4LL * n + 2 : KIND ? 4LL * n : 4LL * (n + 1);
+    const int N = KIND == 2 ? 2 * n + 1 : KIND ? 2 * n : 2 * (n + 1);
     for (int i = tid; i < max(M, n + 1); i += FFT_THREADS) {          // chirp and twiddles
         if (i <= n) {
-            const long long q = ((long long)i * i) % N2;
+            const long long q = (KIND == 2 ? (long long)i * (i + 2) : (long long)i * i) % N2;
             double sn, cs;
             sincospi((double)q / (double)N, &sn, &cs);
             B.chirp[i] = mk<T>((T)cs, (T)sn);
         }
         if (KIND && i < n) {
-            const long long q = ((long long)i * (i + 1)) % N2;
+            const long long q = (KIND == 2 ? (long long)i * (i + 1) + 1 : (long long)i * (i + 1)) % N2;
             double sn, cs;
             sincospi((double)q / (double)N, &sn, &cs);
             B.chirp[n + 1 + i] = mk<T>((T)cs, (T)sn);
@@ -567,11 +716,12 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
 template <typename TC, typename T>
 static void fft_launch_build(int kind, int cnt, size_t lds, hipStream_t s, const FftBuildPair<TC, T> &bp)
 {
-    if (kind) hipLaunchKernelGGL((k_fft_build<TC, T, 1>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+    if (kind == 2) hipLaunchKernelGGL((k_fft_build<TC, T, 2>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+    else if (kind) hipLaunchKernelGGL((k_fft_build<TC, T, 1>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
     else hipLaunchKernelGGL((k_fft_build<TC, T, 0>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
 }
 
-// complex elements in front of bhat: the chirp, and for the DCT kind the half-sample twiddles behind it
+// complex elements in front of bhat: the chirp, and for the DCT kind the half-sample twiddles behind it (kind 2: its two tables)
 static size_t fft_chirp_len(const FftDim &D) { return (size_t)(D.kind ? 2 : 1) * (D.n + 1); }
 
 template <typename T>
@@ -760,12 +910,15 @@ static hipError_t fft_opt_in_lds(Instance *I)
     const int bbytes = (int)(sizeof(cx2<double>) * (size_t)fft_pad(1 << (FFT_MAX_LOGM - 1))) + 64;
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     if (e == hipSuccess && sizeof(T) == sizeof(float)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     }
-    // the Neumann solve's transform kernels (dct_solve)
+    // the Neumann solve's transform kernels (dct_solve), and the mixed-border solve's (mixed_solve)
     if (e == hipSuccess) e = dct_opt_in_lds<T>(bytes);
+    if (e == hipSuccess) e = mix_opt_in_lds<T>(bytes);
     done = e == hipSuccess;
     return e;
 }
@@ -941,6 +1094,92 @@ int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *j
         return SC_ERR_BAD_SIZE;
     }
     return fp64 ? dct_solve_t<double>(I, g, lap, jobs, m, lam) : dct_solve_t<float>(I, g, lap, jobs, m, lam);
+}
+
+// The solve with free sides on some of the borders, m same-size jobs (C m planes): dct_solve's three transform launches with k_mix, each
+// axis under its own transform (MixedGeo); no reduction (the system is regular), the Dirichlet lines of out written by the last launch.
+template <typename T>
+static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam)
+{
+    const bool scr = lam > 0.f;
+    const int nx = mg.nx, ny = mg.ny, planes = g.C * m;
+    SC_HIP(I, fft_opt_in_lds<T>(I));
+    FftState &S = I->fft;
+    int rc;
+    FftDim *dw = nullptr, *dh = nullptr;
+    S.forked = false;
+    S.nreq = 0;
+    if ((rc = fft_build_dim<T>(I, dw, nx, nullptr, std::min(mg.ax, 2)))) return rc;
+    if ((rc = fft_build_dim<T>(I, dh, ny, dw, std::min(mg.ay, 2)))) { for (int k = 0; k < S.nreq; ++k) S.req[k]->n = 0; S.nreq = 0; return rc; }
+    if ((rc = fft_flush_builds<T>(I))) return rc;
+    const size_t plane = (size_t)nx * ny;
+    if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
+    if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
+    stage_mark(I, 5);
+    if (S.pending) {
+        SC_HIP(I, hipStreamWaitEvent(I->stream, S.ev_built, 0));
+        S.pending = false;
+    }
+    const FftPlan<T> Pw = fft_plan_of<T>(*dw), Ph = fft_plan_of<T>(*dh);
+    const size_t ldsw = sizeof(cx2<T>) * (size_t)(fft_pad(Pw.M) + 1), ldsh = sizeof(cx2<T>) * (size_t)(fft_pad(Ph.M) + 1);
+    T *A = (T *)S.A.p, *B = (T *)S.B.p;
+    auto axis_scale = [](int kind, int n) { return kind == 0 ? 2.0 / (n + 1.0) : kind == 1 ? 2.0 / n : 4.0 / (2.0 * n + 1.0); };
+    const double scale = axis_scale(mg.ax, nx) * axis_scale(mg.ay, ny);
+    const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as dct_solve_t
+    auto chunks = [&](auto fn) {
+        for (int i0 = 0; i0 < m; i0 += PoissonJobs::MAX) {
+            PoissonJobs t{};
+            const int cnt = std::min(m - i0, (int)PoissonJobs::MAX);
+            for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
+            fn(t, (size_t)g.C * i0, g.C * cnt);
+        }
+    };
+    const PoissonJobs none{};
+    T *rows_out = tiny ? B : A;
+    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
+        const dim3 grid(ny, np_);
+        T *const o = rows_out + p0 * plane;
+        const int ts = tiny ? 1 : 0;
+        if (scr) {
+            if (lap) hipLaunchKernelGGL((k_mix<0, T, true, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, lam);
+            else hipLaunchKernelGGL((k_mix<0, T, false, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, lam);
+        } else {
+            if (lap) hipLaunchKernelGGL((k_mix<0, T, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, 0.f);
+            else hipLaunchKernelGGL((k_mix<0, T, false>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, 0.f);
+        }
+    });
+    auto columns = [&](int ts) {      // B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
+        if (scr) hipLaunchKernelGGL((k_mix<1, T, false, true>), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A, nx, 1.0, ts, lam);
+        else hipLaunchKernelGGL((k_mix<1, T, false>), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A, nx, 1.0, ts, 0.f);
+    };
+    if (tiny) {
+        columns(1);      // A[p][y][x]
+    } else {
+        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((nx + 63) / 64, (ny + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, ny, nx);      // B[p][x][y]
+        columns(0);
+        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((ny + 63) / 64, (nx + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, nx, ny);      // B[p][y][x]
+    }
+    const T *rows_in = tiny ? A : B;
+    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
+        hipLaunchKernelGGL((k_mix<2, T, false>), dim3(ny, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, rows_in + p0 * plane, (T *)nullptr, ny, scale, 0, 0.f);
+    });
+    SC_HIP(I, hipGetLastError());
+    stage_mark(I, 6);
+    I->info.method = SC_METHOD_FFT;
+    I->info.sweeps = 1;
+    I->info.converged = 1;
+    I->info.rel_residual = NAN;
+    I->info.sweep_launches = 3;
+    return SC_OK;
+}
+
+int mixed_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
+{
+    if (!fft_supported(mg.nx, mg.ny, fp64)) {
+        I->err = fp64 ? "free sides with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "free sides: more than 8192 unknowns per axis";
+        return SC_ERR_BAD_SIZE;
+    }
+    return fp64 ? mixed_solve_t<double>(I, g, mg, lap, jobs, m, lam) : mixed_solve_t<float>(I, g, mg, lap, jobs, m, lam);
 }
 
 } // namespace sc

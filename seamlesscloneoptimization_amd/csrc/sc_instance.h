@@ -321,7 +321,28 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why);
 // ... and what the screened call (sc_screened_api.cpp) shares with it.  lam > 0: a screened call -- the jobs carry their data term
 // (PoissonJobDev::d), the solve is the direct one with shifted denominators.
-struct PoissonCall { int kind; float tol, lam; };
+// A kind's parts.  The free sides as a mask (1 left, 2 right, 4 top, 8 bottom; SC_POISSON_NEUMANN: all four); the base kind (anything
+// but GUIDANCE or LAPLACIAN there is a bad kind); the kind the entry points hand on: all four sides free reads SC_POISSON_NEUMANN alone,
+// so one test of that bit finds the Neumann call and any SC_POISSON_FREE_* bit left a call with one to three free sides.
+constexpr int SC_POISSON_FREE_ALL = SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM;
+inline int poisson_free_sides(int kind) { return (kind & SC_POISSON_NEUMANN) ? 15 : (kind & SC_POISSON_FREE_ALL) >> 12; }
+inline int poisson_base(int kind) { return kind & ~(SC_POISSON_NEUMANN | SC_POISSON_FREE_ALL); }
+inline int poisson_norm_kind(int kind)
+{
+    const int f = poisson_free_sides(kind);
+    return poisson_base(kind) | (f == 15 ? SC_POISSON_NEUMANN : f << 12);
+}
+// the axis kinds and unknowns of a call with free sides `f` (f = 0, the Dirichlet frame, and f = 15 included)
+inline MixedGeo poisson_mixed_geo(int f, int cols, int rows)
+{
+    auto axis = [](bool lo, bool hi) { return lo ? (hi ? 1 : 3) : (hi ? 2 : 0); };
+    MixedGeo mg;
+    mg.ax = axis(f & 1, f & 2); mg.ay = axis(f & 4, f & 8);
+    mg.nx = cols - (mixed_low_d(mg.ax) ? 1 : 0) - (mixed_high_d(mg.ax) ? 1 : 0);
+    mg.ny = rows - (mixed_low_d(mg.ay) ? 1 : 0) - (mixed_high_d(mg.ay) ? 1 : 0);
+    return mg;
+}
+struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 bool aligned4(const void *p);
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
@@ -381,6 +402,9 @@ bool fft_supported(int w, int h, bool fp64);
 // their out arrays (marks: 5 behind the boundary-mean reduction, 6 behind the last transform launch)
 // (lam > 0: the screened solve, sc_screened_api.cpp: the jobs' data term read with the right-hand side, no mean)
 int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
+// ... and the problem with free sides on some of the borders (SC_POISSON_FREE_*; mg: poisson_mixed_geo): the same three launches, each
+// axis under its own transform; marks 5 (at the start: nothing is reduced) and 6
+int mixed_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
 bool wants_float_tables(const Instance *I);
 int effective_method(const Instance *I);                              // sc_solver.cpp: what SC_METHOD_AUTO resolves to for the fields bound to I
 int output_nodes(Instance *I, LmNodes &lm);  // sc_solver.cpp: the float-table correction the post-process of result(I) has to add (none: lm.CN == nullptr)

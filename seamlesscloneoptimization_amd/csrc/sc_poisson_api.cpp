@@ -11,6 +11,9 @@
 // SC_POISSON_NEUMANN: no fields, no pre-process or output launch -- per chunk dct_solve (sc_fft.hip) works straight between the jobs'
 // arrays: the boundary-mean reduction, then the three transform launches of the DCT solve.
 //
+// SC_POISSON_FREE_* on one to three sides: the same shape with mixed_solve -- each axis under the transform of its two ends, the
+// Dirichlet lines of out written by the last transform launch.
+//
 // The screened call (sc_screened_api.cpp) runs through the same poisson_run with PoissonCall::lam > 0: the jobs carry their data
 // term, the solve is the direct one (SC_METHOD_FFT) with its denominators shifted by -lam.
 #include "sc_instance.h"
@@ -30,10 +33,10 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
     if (!why) why = &dummy;
     *why = "";
     if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
-    const bool neumann = (p->kind & SC_POISSON_NEUMANN) != 0;
-    const int base = p->kind & ~SC_POISSON_NEUMANN;
+    const int free = poisson_free_sides(p->kind), base = poisson_base(p->kind);
+    const bool neumann = free == 15;
     if (base != SC_POISSON_GUIDANCE && base != SC_POISSON_LAPLACIAN) {
-        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN";
+        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN or SC_POISSON_FREE_* bits";
         return SC_ERR_BAD_ARG;
     }
     if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
@@ -42,6 +45,11 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
     if (neumann) {
         if (l->cols < 2 || l->rows < 2) { *why = "SC_POISSON_NEUMANN: the image must be at least 2 x 2"; return SC_ERR_BAD_SIZE; }
         if (!fft_supported(l->cols, l->rows, false)) { *why = "SC_POISSON_NEUMANN: the image must be at most 8192 x 8192"; return SC_ERR_BAD_SIZE; }
+    } else if (free) {
+        if (l->cols < 2 || l->rows < 2) { *why = "free sides: the image must be at least 2 x 2"; return SC_ERR_BAD_SIZE; }
+        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);
+        if (mg.nx < 1 || mg.ny < 1) { *why = "free sides: at least 1 unknown per axis (3 pixels between two Dirichlet lines)"; return SC_ERR_BAD_SIZE; }
+        if (!fft_supported(mg.nx, mg.ny, false)) { *why = "free sides: at most 8192 unknowns (pixels less the axis's Dirichlet lines) per axis"; return SC_ERR_BAD_SIZE; }
     } else {
         if (l->cols < 3 || l->rows < 3) { *why = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
         if (l->cols > 65536 || l->rows > 65536) { *why = "the image must be at most 65536 x 65536"; return SC_ERR_BAD_SIZE; }
@@ -69,10 +77,11 @@ size_t poisson_span(const sc_poisson_layout *l)
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-// a job's own code: the pointers its kind needs, 4-byte aligned (a Neumann job may come without boundary: mean zero)
+// a job's own code: the pointers its kind (poisson_norm_kind's) needs, 4-byte aligned (a Neumann job may come without boundary: mean
+// zero; with a Dirichlet line on any side boundary is required)
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
 {
-    const bool guidance = (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_GUIDANCE;
+    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
     if ((kind & SC_POISSON_NEUMANN) && !b) b = out;
     const float *need[4] = { b, out, guidance ? gx : lap, guidance ? gy : lap };
     for (const float *q : need) {
@@ -131,6 +140,23 @@ int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     return solve_rc;
 }
 
+// the code on this instance of a call with free sides (kind: poisson_norm_kind's): the methods that serve it, the limit of its
+// transforms' precision
+int mixed_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
+{
+    const int method = I->opts.method;
+    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
+        I->err = "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)";
+        return SC_ERR_BAD_ARG;
+    }
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), l->cols, l->rows);
+    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
+        I->err = "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
+        return SC_ERR_BAD_SIZE;
+    }
+    return SC_OK;
+}
+
 // a Neumann call's code on this instance: the methods that serve it, the side limit of its transforms' precision
 int neumann_instance_check(Instance *I, const sc_poisson_layout *l)
 {
@@ -154,6 +180,25 @@ int neumann_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     const int rc = dct_solve(I, g, (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
     if (rc) return rc;
     stage_mark(I, 7);
+    return SC_OK;
+}
+
+// ... and for a call with one to three free sides: mixed_solve, marks as the Neumann call's
+int mixed_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
+{
+    stage_mark(I, 0);
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), g.W, g.H);
+    const int rc = mixed_solve(I, g, mg, poisson_base(kind) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
+    if (rc) return rc;
+    stage_mark(I, 7);
+    return SC_OK;
+}
+
+// the instance's word on a call of this kind (poisson_norm_kind's) before anything runs
+int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
+{
+    if (kind & SC_POISSON_NEUMANN) return neumann_instance_check(I, l);
+    if (kind & SC_POISSON_FREE_ALL) return mixed_instance_check(I, kind, l);
     return SC_OK;
 }
 
@@ -194,7 +239,8 @@ int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, c
     int worst = SC_OK;
     for (int i0 = 0; i0 < nv; i0 += per) {
         const int m = std::min(per, nv - i0);
-        int rc = (p.kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
+        int rc = (p.kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p.kind, g, dj + i0, m, p.lam)
+                 : (p.kind & SC_POISSON_FREE_ALL) ? mixed_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
         if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
             if (timed) {
                 SC_HIP(I, hipStreamSynchronize(I->stream));
@@ -230,14 +276,15 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
     if (rc) return rc;
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
-    if ((p->kind & SC_POISSON_NEUMANN) && (rc = neumann_instance_check(I, l))) return rc;
+    const int kind = poisson_norm_kind(p->kind);
+    if ((rc = direct_instance_check(I, kind, l))) return rc;
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
     std::vector<PoissonJobDev> dj;
     std::vector<int *> rcs;
     for (int i = 0; i < n; ++i) {
         sc_poisson_job &j = jobs[i];
-        const int vrc = poisson_job_validate(p->kind, j.gx, j.gy, j.lap, j.boundary, j.out, &why);
+        const int vrc = poisson_job_validate(kind, j.gx, j.gy, j.lap, j.boundary, j.out, &why);
         if (vrc != SC_OK) {
             j.rc = vrc;
             if (worst == SC_OK) { worst = vrc; I->err = why; }
@@ -250,7 +297,7 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
     if (dj.empty()) return worst;
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    rc = poisson_run(I, PoissonCall{ p->kind, p->tol, 0.f }, l, dj.data(), rcs.data(), (int)dj.size(), bSync, t);
+    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, dj.data(), rcs.data(), (int)dj.size(), bSync, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     poisson_set_timing(I, t);       // (zeros without bSync)
     if (worst == SC_OK) worst = rc;
@@ -265,12 +312,13 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     if (rc) return rc;
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
-    if ((p->kind & SC_POISSON_NEUMANN) && (rc = neumann_instance_check(I, l))) return rc;
-    if ((rc = poisson_job_validate(p->kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
+    const int kind = poisson_norm_kind(p->kind);
+    if ((rc = direct_instance_check(I, kind, l))) return rc;
+    if ((rc = poisson_job_validate(kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
     // one device block: the inputs' spans, boundary's, and out's unless out is boundary (in place); each at a 256-byte boundary
     const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
     // (a Neumann call without boundary: no slot, no upload)
-    const bool guidance = (p->kind & ~SC_POISSON_NEUMANN) == SC_POISSON_GUIDANCE, in_place = out == boundary;
+    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE, in_place = out == boundary;
     const int slots = (guidance ? 2 : 1) + (boundary ? 1 : 0) + (in_place ? 0 : 1);
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     uint8_t *d = (uint8_t *)I->d_pois.p;
@@ -284,7 +332,7 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     const PoissonJobDev job{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_b, d_out };
     int job_rc = SC_OK, *const job_rcs[1] = { &job_rc };
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
-    rc = poisson_run(I, PoissonCall{ p->kind, p->tol, 0.f }, l, &job, job_rcs, 1, true, t);
+    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, &job, job_rcs, 1, true, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     return poisson_download(I, l, d_out, out, t, rc);
 }

@@ -1,0 +1,349 @@
+"""The float32 Poisson and screened solves with per-side free borders (SC_POISSON_FREE_*) on the GPU: all 14 combinations between the
+Dirichlet frame and the Neumann problem against the float64 restatement (tests/mixed_np.py), the identity, layouts, what is read and
+written, mirror images, the two extremes bit for bit, batches, refusals and the instance afterwards.  Bounds: tests/mixed_bounds.py."""
+import numpy as np
+import pytest
+
+import mixed_np
+from mixed_bounds import Yardstick
+
+pytestmark = pytest.mark.gpu
+
+from seamlesscloneoptimization_amd import capi  # noqa: E402
+
+from test_gpu_neumann import Dev, _batch, _layout_views  # noqa: E402
+
+G, L = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN
+BITS = {"l": capi.SC_POISSON_FREE_LEFT, "r": capi.SC_POISSON_FREE_RIGHT, "t": capi.SC_POISSON_FREE_TOP, "b": capi.SC_POISSON_FREE_BOTTOM}
+PREC = {"f32": 0, "f64": capi.SC_FLAG_FFT_FP64}
+MIXED = mixed_np.MIXED_SIDES
+H0, W0, C0 = 29, 37, 3
+
+
+def bits(sides):
+    return sum(BITS[ch] for ch in sides)
+
+
+@pytest.fixture()
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def configure(inst, method=capi.SC_METHOD_FFT, prec="f32"):
+    inst.set_solver(method=method, flags=(inst.default_opts().flags & ~capi.SC_FLAG_FFT_FP64) | PREC[prec])
+
+
+_INPUTS = {}
+
+
+def inputs(H=H0, W=W0, C=C0, seed=5):
+    """(img, gx, gy of a random guidance field, boundary, data), computed once per shape and never changed"""
+    key = (H, W, C, seed)
+    if key not in _INPUTS:
+        rng = np.random.default_rng(seed)
+        img = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
+        gx = rng.normal(0, 20, (H, W, C)).astype(np.float32)
+        gy = rng.normal(0, 20, (H, W, C)).astype(np.float32)
+        b = rng.uniform(-100, 400, (H, W, C)).astype(np.float32)
+        d = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
+        for a in (img, gx, gy, b, d):
+            a.flags.writeable = False
+        _INPUTS[key] = (img, gx, gy, b, d)
+    return _INPUTS[key]
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("sides", MIXED)
+def test_every_combination_against_the_restatement(inst, sides, prec):
+    """37 x 29, C = 3: guidance, laplacian (the same bits), screened with lam 1e-3 and 10; SC_METHOD_AUTO is SC_METHOD_FFT."""
+    img, gx, gy, b, d = inputs()
+    lap = mixed_np.divergence(gx, gy)
+    known = mixed_np.dirichlet_mask(sides, H0, W0)
+    fails = []
+    for method in (capi.SC_METHOD_FFT, capi.SC_METHOD_AUTO):
+        configure(inst, method, prec)
+        out = inst.poisson(b, gx=gx, gy=gy, free_sides=sides)
+        i = inst.info()
+        assert i.method == capi.SC_METHOD_FFT and i.sweeps == 1 and i.converged == 1 and (i.W, i.H) == (W0, H0)
+        assert np.array_equal(inst.poisson(b, lap=lap, free_sides=sides), out)
+        assert np.array_equal(out[known], b[known])
+        bad, err, res = Yardstick(sides, 0.0, None, lap, b).check(out, prec == "f64")
+        print("MIX %-3s %s poisson ERR %.2e RES %.2e" % (sides, prec, err, res))
+        fails.extend((sides, "poisson") + t for t in bad)
+    for lam in (1e-3, 10.0):
+        out = inst.screened(d, gx=gx, gy=gy, lam=lam, boundary=b, free_sides=sides)
+        assert inst.info().method == capi.SC_METHOD_FFT
+        assert np.array_equal(inst.screened(d, lap=lap, lam=lam, boundary=b, free_sides=sides), out)
+        assert np.array_equal(out[known], b[known])
+        bad, err, res = Yardstick(sides, lam, d, lap, b).check(out, prec == "f64")
+        print("MIX %-3s %s screened %g ERR %.2e RES %.2e" % (sides, prec, lam, err, res))
+        fails.extend((sides, lam) + t for t in bad)
+    assert not fails, fails
+
+
+@pytest.mark.parametrize("sides", MIXED)
+def test_forward_differences_of_an_image_give_back_the_image(inst, sides):
+    """g = grad I with boundary = I returns I, and so does the screened solve with d = I, whatever the sides; gx's last column and gy's
+    last row hold NaN."""
+    img = inputs()[0]
+    gx, gy = mixed_np.forward_differences(img)
+    gx[:, -1] = np.nan
+    gy[-1] = np.nan
+    R = float(np.abs(img).max())
+    lap = mixed_np.divergence(np.nan_to_num(gx), np.nan_to_num(gy))
+    configure(inst)
+    y = Yardstick(sides, 0.0, None, lap, img)
+    out = inst.poisson(img, gx=gx, gy=gy, free_sides=sides)
+    assert np.isfinite(out).all() and np.abs(out - img).max() <= (y.bounds()[0] + 1e-5) * R      # 1e-5: the float32 differences of float32 pixels (solve_exact's own distance from I)
+    ys = Yardstick(sides, 0.5, img, lap, img)
+    outs = inst.screened(img, gx=gx, gy=gy, lam=0.5, boundary=img, free_sides=sides)
+    assert np.isfinite(outs).all() and np.abs(outs - img).max() <= (ys.bounds()[0] + 1e-5) * R
+    configure(inst, prec="f64")
+    out = inst.poisson(img, gx=gx, gy=gy, free_sides=sides)
+    assert np.abs(out - img).max() <= 1e-5 * R
+
+
+@pytest.mark.parametrize("sides", ["l", "rt", "lrb", "tb"])
+def test_layouts_give_the_same_bits_and_write_only_what_they_name(inst, sides):
+    H, W, C = 43, 61, 3
+    img, gx, gy, b, d = inputs(H, W, C, seed=9)
+    configure(inst)
+    for screened in (False, True):
+        ref = None
+        for kind in ("hwc", "chw", "padded", "rgba", "transposed"):
+            make = _layout_views(H, W, C, kind, 0.0)
+            vb, vx, vy, vd = make(b)[0], make(gx)[0], make(gy)[0], make(d)[0]
+            vo, obuf = _layout_views(H, W, C, kind, -7.25)()
+            before = obuf.copy()
+            if screened:
+                got = inst.screened(vd, gx=vx, gy=vy, lam=0.25, boundary=vb, out=vo, free_sides=sides)
+            else:
+                got = inst.poisson(vb, gx=vx, gy=vy, out=vo, free_sides=sides)
+            assert got is vo
+            named = np.ones(obuf.shape, bool)
+            if kind == "padded":
+                named[:, W:] = False
+            elif kind == "rgba":
+                named[:, :, C:] = False
+            assert np.array_equal(obuf[~named], before[~named]), kind           # padding / the fourth float untouched
+            out = np.array(vo)
+            if ref is None:
+                ref = out
+            assert np.array_equal(out, ref), (kind, screened)
+        vb = b.copy()                                                            # in place: out is boundary
+        if screened:
+            got = inst.screened(d, gx=gx, gy=gy, lam=0.25, boundary=vb, out=vb, free_sides=sides)
+        else:
+            got = inst.poisson(vb, gx=gx, gy=gy, out=vb, free_sides=sides)
+        assert got is vb and np.array_equal(vb, ref)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+@pytest.mark.parametrize("sides", MIXED)
+def test_what_is_never_read(inst, sides, prec):
+    """NaN in boundary everywhere but on its Dirichlet lines (its interior and its lines on free sides), in gx's last column and gy's
+    last row, and in lap and data on the Dirichlet lines: the bits of the clean run."""
+    img, gx, gy, b, d = inputs()
+    lap = mixed_np.divergence(gx, gy)
+    known = mixed_np.dirichlet_mask(sides, H0, W0)
+    configure(inst, prec=prec)
+    ref = inst.poisson(b, gx=gx, gy=gy, free_sides=sides)
+    refs = inst.screened(d, gx=gx, gy=gy, lam=0.5, boundary=b, free_sides=sides)
+    assert np.isfinite(ref).all() and np.isfinite(refs).all()
+    db, dx, dy, dl, dd = b.copy(), gx.copy(), gy.copy(), lap.copy(), d.copy()
+    db[~known] = np.nan
+    dx[:, -1] = np.nan
+    dy[-1] = np.nan
+    dl[known] = np.nan
+    dd[known] = np.nan
+    assert np.isnan(db).sum() >= (H0 - 2) * (W0 - 2) * C0
+    assert np.array_equal(inst.poisson(db, gx=dx, gy=dy, free_sides=sides), ref)
+    assert np.array_equal(inst.poisson(db, lap=dl, free_sides=sides), ref)
+    assert np.array_equal(inst.screened(dd, gx=dx, gy=dy, lam=0.5, boundary=db, free_sides=sides), refs)
+    assert np.array_equal(inst.screened(dd, lap=dl, lam=0.5, boundary=db, free_sides=sides), refs)
+
+
+SWAP_LR = str.maketrans("lr", "rl")
+SWAP_TB = str.maketrans("tb", "bt")
+
+
+@pytest.mark.parametrize("sides", MIXED)
+def test_mirror_images(inst, sides):
+    """The problem flipped left-right with LEFT and RIGHT swapped (top-bottom with TOP and BOTTOM) is the same problem: the flipped
+    output.  Each of the two runs is within the ERR bound of the exact answer, so they are within twice it of each other."""
+    img, gx, gy, b, d = inputs()
+    lap = mixed_np.divergence(gx, gy)
+    configure(inst)
+    out = inst.screened(d, lap=lap, lam=1e-3, boundary=b, free_sides=sides)
+    y = Yardstick(sides, 1e-3, d, lap, b)
+    for axis, table in ((1, SWAP_LR), (0, SWAP_TB)):
+        f = lambda a: np.ascontiguousarray(np.flip(a, axis))          # noqa: E731
+        other = inst.screened(f(d), lap=f(lap), lam=1e-3, boundary=f(b), free_sides=sides.translate(table))
+        assert np.abs(f(other).astype(np.float64) - out).max() <= 2 * y.bounds()[0] * y.R, (sides, axis)
+        assert np.abs(f(other).astype(np.float64) - y.want).max() <= y.bounds()[0] * y.R
+
+
+def test_the_two_extremes_are_the_earlier_calls_bit_for_bit(inst):
+    img, gx, gy, b, d = inputs()
+    for prec in ("f32", "f64"):
+        configure(inst, prec=prec)
+        neu = inst.poisson(b, gx=gx, gy=gy, neumann=True)
+        assert np.array_equal(inst.poisson(b, gx=gx, gy=gy, free_sides="lrtb"), neu)
+        ps = [(b, gx, gy)]
+        for kind in (G | capi.SC_POISSON_FREE_ALL, G | capi.SC_POISSON_FREE_ALL | capi.SC_POISSON_NEUMANN, G | capi.SC_POISSON_NEUMANN | BITS["t"]):
+            rc, outs, jobs, info, dev, full, ids = _batch(inst, ps, kind=kind)
+            dev.free()
+            assert rc == capi.SC_OK and np.array_equal(outs[0], neu), kind
+        sneu = inst.screened(d, gx=gx, gy=gy, lam=0.5, neumann=True)
+        assert np.array_equal(inst.screened(d, gx=gx, gy=gy, lam=0.5, free_sides="tlbr"), sneu)
+        dirichlet = inst.poisson(b, gx=gx, gy=gy)
+        assert np.array_equal(inst.poisson(b, gx=gx, gy=gy, free_sides=""), dirichlet)
+
+
+def _problems(n, H, W, C, seed):
+    rng = np.random.default_rng(seed)
+    return [(rng.uniform(-50, 300, (H, W, C)).astype(np.float32), rng.normal(0, 15, (H, W, C)).astype(np.float32),
+             rng.normal(0, 15, (H, W, C)).astype(np.float32)) for _ in range(n)]
+
+
+@pytest.mark.parametrize("method", [capi.SC_METHOD_AUTO, capi.SC_METHOD_FFT])
+@pytest.mark.parametrize("n,H,W,C,sides", [(2, 48, 64, 1, "l"), (16, 61, 97, 2, "rt"), (70, 30, 40, 3, "ltb")])
+def test_batches_equal_their_solo_runs_bit_for_bit(inst, method, n, H, W, C, sides):
+    ps = _problems(n, H, W, C, seed=n)
+    configure(inst, method)          # AUTO stays direct for n > 1
+    rc, outs, jobs, info, dev, full, ids = _batch(inst, ps, kind=G | bits(sides))
+    try:
+        assert rc == capi.SC_OK and all(j.rc == capi.SC_OK for j in jobs)
+        per = capi.SC_POISSON_MAX_PLANES // C
+        last = n - per * ((n - 1) // per)
+        assert info.method == capi.SC_METHOD_FFT and info.sweeps == 1 and info.converged == 1
+        assert info.group_members == (last if last > 1 else 0)
+        assert info.ms_solve > 0 and info.ms_device_total > 0
+        written = np.zeros(full.size, bool)                  # nothing outside the outputs' spans was written (guard bands, inputs)
+        for (_, _, _, ko) in ids:
+            off = dev.parts[ko][0] // 4
+            written[off:off + H * W * C] = True
+        assert np.array_equal(full[~written], dev.host[~written])
+    finally:
+        dev.free()
+    for k, (b, gx, gy) in enumerate(ps):
+        assert np.array_equal(outs[k], inst.poisson(b, gx=gx, gy=gy, free_sides=sides)), k
+    b, gx, gy = ps[n - 1]
+    bad, err, res = Yardstick(sides, 0.0, None, mixed_np.divergence(gx, gy), b).check(outs[n - 1], False)
+    assert not bad, bad
+
+
+def test_batch_with_bad_jobs_and_the_rgba_layout(inst):
+    ps = _problems(5, 40, 50, 3, seed=77)
+    kind = G | bits("rb")
+
+    def tamper(jobs):
+        jobs[1].boundary = None              # a Dirichlet line is left: boundary is required
+        jobs[3].gx = jobs[3].gx + 2          # not 4-byte aligned
+    configure(inst, capi.SC_METHOD_AUTO)
+    rc, outs, jobs, info, dev, full, ids = _batch(inst, ps, tamper=tamper, kind=kind)
+    dev.free()
+    assert rc == capi.SC_ERR_BAD_ARG
+    assert [j.rc for j in jobs] == [capi.SC_OK, capi.SC_ERR_BAD_ARG, capi.SC_OK, capi.SC_ERR_BAD_ARG, capi.SC_OK]
+    for k in (1, 3):
+        assert np.all(outs[k] == -3.5), k                # skipped: never written
+    for k in (0, 2, 4):
+        b, gx, gy = ps[k]
+        assert np.array_equal(outs[k], inst.poisson(b, gx=gx, gy=gy, free_sides="rb")), k
+    rc, outs4, jobs, info, dev, full, ids = _batch(inst, ps, layout_kind="rgba", kind=kind)
+    dev.free()
+    assert rc == capi.SC_OK
+    for (_, _, _, ko) in ids:
+        off = dev.parts[ko][0] // 4
+        assert np.all(full[off:off + 4 * 50 * 40].reshape(40, 50, 4)[:, :, 3] == -3.5)
+    for k in (0, 2, 4):
+        assert np.array_equal(outs4[k], outs[k])
+
+
+@pytest.mark.parametrize("method", [capi.SC_METHOD_MULTIGRID, capi.SC_METHOD_JACOBI, capi.SC_METHOD_RBGS, capi.SC_METHOD_SOR,
+                                    capi.SC_METHOD_DST])
+def test_other_methods_are_refused_and_write_nothing(inst, method):
+    H, W, C = 40, 50, 3
+    g = np.random.default_rng(1).normal(0, 10, (H, W, C)).astype(np.float32)
+    inst.set_solver(method=method)
+    out = np.full((H, W, C), -7.25, np.float32)
+    with pytest.raises(capi.SeamlessCloneError) as e:
+        inst.poisson(g, gx=g, gy=g, out=out, free_sides="l")
+    assert e.value.code == capi.SC_ERR_BAD_ARG
+    assert "SC_METHOD_AUTO" in str(e.value) and "SC_METHOD_FFT" in str(e.value)
+    with pytest.raises(capi.SeamlessCloneError) as e:
+        inst.screened(g, gx=g, gy=g, lam=1.0, boundary=g, out=out, free_sides="tb")
+    assert e.value.code == capi.SC_ERR_BAD_ARG and "SC_METHOD_FFT" in str(e.value)
+    assert np.all(out == -7.25)
+    rc, outs, jobs, info, dev, full, ids = _batch(inst, _problems(2, H, W, C, seed=2), kind=G | bits("l"))
+    dev.free()
+    assert rc == capi.SC_ERR_BAD_ARG and np.array_equal(full, dev.host)
+
+
+def test_host_call_reports_stage_times(inst):
+    b = np.random.default_rng(2).uniform(-50, 300, (500, 600, 3)).astype(np.float32)
+    gx, gy = mixed_np.forward_differences(b)
+    configure(inst, capi.SC_METHOD_AUTO)
+    inst.poisson(b, gx=gx, gy=gy, free_sides="t")
+    i = inst.info()
+    assert i.ms_pre >= 0 and i.ms_solve > 0 and i.ms_post >= 0 and i.ms_call >= i.ms_device_total > 0
+    assert i.ms_pre < i.ms_solve and i.ms_post < i.ms_solve          # the transform launches read and write the caller's arrays
+    assert i.ms_h2d > 0 and i.ms_d2h > 0
+
+
+def test_the_instance_after_a_mixed_call():
+    """A Dirichlet Poisson call, a Neumann call and a clone on an instance that solved problems with free sides give the bytes of a fresh
+    instance (the new tables share the cache, at lengths the other kinds use here); its options are unchanged."""
+    from oracle import oracle_np
+    dst, patch, mask, cx, cy = oracle_np.synth_inputs(300, 200, margin=32)
+    rng = np.random.default_rng(1)
+    img = rng.uniform(-50, 300, (200, 300, 3)).astype(np.float32)
+    gx, gy = mixed_np.forward_differences(img)
+
+    def others(i):
+        body = dst.copy()
+        i.run(patch, body, mask, cx, cy)
+        return i.poisson(img, gx=gx, gy=gy, tol=0.05), i.poisson(img, gx=gx, gy=gy, neumann=True), body
+
+    for method, flags in ((capi.SC_METHOD_AUTO, 0), (capi.SC_METHOD_FFT, 0), (capi.SC_METHOD_FFT, capi.SC_FLAG_FFT_FP64)):
+        fresh, used = capi.Instance(0), capi.Instance(0)
+        try:
+            fresh.set_solver(method=method, flags=fresh.default_opts().flags | flags)
+            used.set_solver(method=method, flags=used.default_opts().flags | flags)
+            before = used.get_solver()
+            for shape, sides in (((200, 300, 3), "lrt"), ((199, 299, 3), "lt"), ((200, 301, 1), "r"), ((201, 300, 2), "tb")):
+                g = rng.normal(0, 10, shape).astype(np.float32)
+                used.poisson(g, gx=g, gy=g, free_sides=sides)
+                used.screened(g, gx=g, gy=g, lam=0.5, boundary=g, free_sides=sides)
+            assert bytes(before) == bytes(used.get_solver())
+            for x, y in zip(others(fresh), others(used)):
+                assert np.array_equal(x, y), (method, flags)
+            g = rng.normal(0, 10, (199, 299, 3)).astype(np.float32)
+            assert np.array_equal(used.poisson(g, gx=g, gy=g, free_sides="lt"), fresh.poisson(g, gx=g, gy=g, free_sides="lt"))
+        finally:
+            fresh.destroy()
+            used.destroy()
+
+
+def test_the_python_functions():
+    import seamlesscloneoptimization_amd as pkg
+    from seamlesscloneoptimization_amd import seamless_clone
+    img = inputs(90, 120, 3, seed=4)[0]
+    gx, gy = mixed_np.forward_differences(img)
+    R = float(np.abs(img).max())
+    lap = mixed_np.divergence(gx, gy)
+    eb = Yardstick("lb", 0.0, None, lap, img).bounds()[0] + 1e-5          # 1e-5: solve_exact's own distance from the image (float32 differences)
+    ebs = Yardstick("lb", 0.5, img, lap, img).bounds()[0] + 1e-5
+    out = seamless_clone.poisson_solve(img, gx, gy, free_sides="lb")
+    assert np.abs(out - img).max() <= eb * R
+    two = seamless_clone.poisson_solve_batch([img, img], [gx, gx], [gy, gy], free_sides="lb")
+    assert np.array_equal(two[0], out) and np.array_equal(two[1], out)
+    s = seamless_clone.screened_solve(img, gx, gy, lam=0.5, boundary=img, free_sides="lb")
+    assert np.abs(s - img).max() <= ebs * R
+    assert np.array_equal(seamless_clone.screened_solve_batch([img], [gx], [gy], lam=0.5, boundaries=[img], free_sides="lb")[0], s)
+    assert np.array_equal(seamless_clone.screened_solve(img, gx, gy, lam=0.5, free_sides="lrtb"), seamless_clone.screened_solve(img, gx, gy, lam=0.5))
+    same = seamless_clone.gradient_filter(img, 1.0, 0.5, free_sides="r")
+    assert np.abs(same - img).max() <= (Yardstick("r", 0.5, img, lap, img).bounds()[0] + 1e-5) * R
+    assert hasattr(pkg, "poisson_solve")

@@ -1,0 +1,140 @@
+"""The solve with per-side free borders (SC_POISSON_FREE_*: k_mix, k_fft_build kind 2) at every length class its transform of a
+Dirichlet end paired with a free end can get wrong, along x and along y, both orders of the ends, on both sides of the transposed-store
+cut, at its size limits (the GPU side of tests/test_mixed_host.py).
+
+Float32 transforms are held to the float32 restatement on the same input -- measured <= max(FACTOR x solve_f32's, FLOOR) for RES and
+ERR -- and double transforms to float32 ulps: tests/mixed_bounds.py says what the quantities are and where the constants come from.
+Lines MIXLEN / MIXCUT carry the measured values beside the restatement's."""
+import numpy as np
+import pytest
+
+import mixed_np
+from mixed_bounds import LENGTHS, STRIP32, STRIP64, Yardstick, length_cases, rough_inputs, smooth_input
+
+pytestmark = pytest.mark.gpu
+
+from seamlesscloneoptimization_amd import capi  # noqa: E402
+
+PREC = {"f32": 0, "f64": capi.SC_FLAG_FFT_FP64}
+
+
+@pytest.fixture()
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def configure(inst, prec, method=capi.SC_METHOD_FFT):
+    inst.set_solver(method=method, flags=(inst.default_opts().flags & ~capi.SC_FLAG_FFT_FP64) | PREC[prec])
+
+
+def solve_and_check(inst, sides, what, gx, gy, b, precs, tag, fails, laplacian=True):
+    """One input under each precision: GUIDANCE (and LAPLACIAN fed numpy's divergence: the same bits), RES / ERR against the yardstick,
+    the Dirichlet lines.  Appends to fails; returns {prec: (err, res)} and the yardstick."""
+    lap = mixed_np.divergence(gx, gy)
+    y = Yardstick(sides, 0.0, None, lap, b)
+    known = mixed_np.dirichlet_mask(sides, *b.shape[:2])
+    got = {}
+    for prec in precs:
+        configure(inst, prec)
+        out = inst.poisson(b, gx=gx, gy=gy, free_sides=sides)
+        i = inst.info()
+        if not (i.method == capi.SC_METHOD_FFT and i.converged == 1 and (i.W, i.H) == (gx.shape[1], gx.shape[0])):
+            fails.append((tag, prec, "info", i.method, i.W, i.H))
+        if laplacian and not np.array_equal(inst.poisson(b, lap=lap, free_sides=sides), out):
+            fails.append((tag, prec, "LAPLACIAN differs from GUIDANCE"))
+        if not np.isfinite(out).all():
+            fails.append((tag, prec, "not finite"))
+            continue
+        if not np.array_equal(out[known], b[known]):
+            fails.append((tag, prec, "Dirichlet lines"))
+        bad, err, res = y.check(out, prec == "f64", rough=what != "smooth", reconstruction=what == "reconstruction")
+        fails.extend((tag, prec) + t for t in bad)
+        got[prec] = (err, res)
+    return got, y
+
+
+def fmt(got, y):
+    s = "f32 -"
+    if "f32" in got:
+        s = "f32 RES %.2e (x%.1f) ERR %.2e (x%.1f) / solve_f32 %.2e %.2e" % (
+            got["f32"][1], got["f32"][1] / max(y.res32, 1e-300), got["f32"][0], got["f32"][0] / max(y.err32, 1e-300), y.res32, y.err32)
+    if "f64" in got:
+        s += " | f64 RES %.2e ERR %.2f ulp" % (got["f64"][1], got["f64"][0] * y.R / float(np.spacing(np.float32(y.R))))
+    return s
+
+
+CASES = length_cases()
+
+
+def test_the_walk_covers_what_it_says():
+    ns = {c[0] for c in CASES}
+    assert ns == set(LENGTHS) | {STRIP32, STRIP64}
+    for n in ns:
+        kinds = {(axis, mixed_np.axis_kinds(sides)) for m, axis, sides, _, _, _ in CASES if m == n}
+        for axis in "xy":
+            walked = {k[0] if axis == "x" else k[1] for a, k in kinds if a == axis}
+            assert walked == {mixed_np.DN, mixed_np.ND}, (n, axis)
+    assert all(("f64" in p) == (n <= STRIP64) for n, _, _, _, _, p in CASES)
+
+
+@pytest.mark.parametrize("n", LENGTHS + [STRIP64, STRIP32])
+def test_every_length_class_both_ways(inst, n):
+    """n unknowns along the walked axis beside one Dirichlet line (n + 1 pixels), 9 pixels the other way, C = 3: a rough reconstruction
+    and a random guidance field, both forms; from 256 unknowns up the smooth low-mode reconstruction as well (ERR only)."""
+    fails = []
+    print("\nMIXLEN n axis sides input | f32 RES (x restatement) ERR (x restatement) / solve_f32 RES ERR | f64 RES, ERR in ulps")
+    for m, axis, sides, W, H, precs in CASES:
+        if m != n:
+            continue
+        inputs = rough_inputs(W, H, 3, seed=1000 * n + 10 * len(sides) + (axis == "y"))
+        if n >= 256:
+            inputs.append(smooth_input(W, H, 3, seed=n + len(sides)))
+        for what, gx, gy, b in inputs:
+            got, y = solve_and_check(inst, sides, what, gx, gy, b, precs, (n, axis, sides, what), fails)
+            print("MIXLEN n=%4d %s %-3s %-14s | %s" % (n, axis, sides, what, fmt(got, y)))
+    assert not fails, fails
+
+
+CUT_CASES = [(300, 200, 3, "f32", True), (723, 722, 3, "f32", True), (723, 722, 3, "f64", True),          # 722 x 721 doubles: 29 808 bytes below the cut
+             (1100, 1000, 1, "f32", False), (800, 700, 1, "f64", False)]
+
+
+@pytest.mark.parametrize("W,H,C,prec,is_tiny", CUT_CASES)
+def test_both_sides_of_the_transposed_store_cut(inst, W, H, C, prec, is_tiny):
+    """plane of unknowns x sizeof(T) <= 4 MiB: stored transposed by the transform launches; above: two k_fft_transpose launches."""
+    sides = "lb"                                             # N-D along x, D-N along y
+    nx, ny = W - 1, H - 1
+    assert (nx * ny * (8 if prec == "f64" else 4) <= 4 << 20) == is_tiny
+    fails = []
+    what, gx, gy, b = rough_inputs(W, H, C, seed=W * 7 + H)[0]
+    got, y = solve_and_check(inst, sides, what, gx, gy, b, (prec,), (W, H, C, what), fails, laplacian=False)
+    print("\nMIXCUT %4dx%-4d C=%d %s | %s" % (W, H, C, "tiny" if is_tiny else "transposed", fmt(got, y)))
+    assert not fails, fails
+
+
+def test_limits_and_the_instance_after_a_refusal(inst):
+    """One unknown past the top of either precision: SC_ERR_BAD_SIZE and an untouched output, along either axis and for each number of
+    Dirichlet lines on it; the same instance then solves."""
+    for prec, top in (("f32", 8192), ("f64", 4096)):
+        configure(inst, prec)
+        for sides, W, H in (("l", top + 2, 8), ("lr", top + 1, 8), ("t", 8, top + 2), ("l", 8, top + 3)):
+            g = np.zeros((H, W, 1), np.float32)
+            out = np.full_like(g, -7.25)
+            for kw in (dict(gx=g, gy=g), dict(lap=g)):
+                with pytest.raises(capi.SeamlessCloneError) as e:
+                    inst.poisson(g, out=out, free_sides=sides, **kw)
+                assert e.value.code == capi.SC_ERR_BAD_SIZE and np.all(out == -7.25), (prec, sides, W, H)
+            with pytest.raises(capi.SeamlessCloneError) as e:
+                inst.screened(g, lap=g, lam=1.0, boundary=g, out=out, free_sides=sides)
+            assert e.value.code == capi.SC_ERR_BAD_SIZE and np.all(out == -7.25), (prec, sides, W, H)
+        g = np.zeros((8, top + 1, 1), np.float32)
+        assert not inst.poisson(g, lap=g, free_sides="l").any()                    # the top size: lap = 0, boundary = 0 -> u = 0
+    # the smallest images: 2 x 2 with one Dirichlet line each way, 2 x 3 / 3 x 2 between two
+    fails = []
+    for sides, W, H in (("lt", 2, 2), ("rb", 2, 2), ("rt", 2, 2), ("l", 2, 3), ("t", 3, 2), ("ltb", 2, 2), ("lrt", 2, 2)):
+        for what, gx, gy, b in rough_inputs(W, H, 3, seed=W + 2 * H + len(sides)):
+            got, y = solve_and_check(inst, sides, what, gx, gy, b, ("f32", "f64"), (sides, W, H, what), fails)
+            print("MIXLIM %dx%d %-3s %-14s | %s" % (W, H, sides, what, fmt(got, y)))
+    assert not fails, fails
