@@ -357,8 +357,10 @@ __global__ __launch_bounds__(256) void k_fft_transpose(const T *__restrict__ in,
     }
 }
 
-// ---- the Neumann problem (SC_POISSON_NEUMANN): DCT-II / DCT-III by the same chirp convolution ------------------------------------
-// All W x H pixels are unknowns and the 5-point stencil reflects at the border: the DCT-II diagonalises it.  With N = 2n, c_m =
+// ---- the direct solve on caller arrays: free sides on some or all of the four borders (SC_POISSON_NEUMANN, SC_POISSON_FREE_*) ------
+// One kernel (k_mix) and one driver (direct_jobs_solve) for all 15 combinations with a free side; each axis has its own transform.
+// An axis with both ends free (both axes: the Neumann problem) -- DCT-II / DCT-III by the same chirp convolution:
+// all its pixels are unknowns and the 5-point stencil reflects at its ends: the DCT-II diagonalises it.  With N = 2n, c_m =
 // exp(i pi m^2 / N) and h_k = exp(i pi k / 2n) c_k (FftDim kind 1: the chirp kernel conj(c_m) of period 2n, M >= 2n - 1 as before),
 //     forward   X_k = sum_{j<n} x_j cos(pi (2j+1) k / 2n) = Re[ h_k sum_j (x_j c_j) conj(c_{k-j}) ]
 //     inverse   x_j = X_0 / 2 + sum_{0<k<n} X_k cos(pi (2j+1) k / 2n) = Re[ c_j sum_k (X'_k h_k) conj(c_{j-k}) ],  X'_0 = X_0 / 2
@@ -377,90 +379,7 @@ __device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDe
     return (a - b) + (cc - d);
 }
 
-// MODE 0: row r of the right-hand side (from the jobs' arrays) -> DCT-II -> out[p][r][k] (tstore: out[p][k][r])
-// MODE 1: rows of `in` (the transposed plane: row = x frequency, entries = y) -> DCT-II, / den, (0, 0) zeroed, DCT-III -> out, as MODE 0
-// MODE 2: rows of `in` [p][y][k] -> DCT-III, scale, + the plane's mean of boundary (parts: nparts sums per plane, nullptr: 0) -> the job's out
-// SCR (a screened solve, lam > 0): MODE 0 reads the job's data term d beside the right-hand side, same element, same lane, and
-// transforms rhs - lam d (screened_rhs); MODE 1 divides by eigenvalue - lam, the (0, 0) coefficient included (by -lam: the screened
-// system is regular).  MODE 2 has no screened form: a screened solve runs it without parts.
-template <int MODE, typename T, bool LAP, bool SCR = false>
-__global__ __launch_bounds__(FFT_THREADS) void k_dct(FftPlan<T> P, PoissonGeo g, PoissonJobs jobs, const T *__restrict__ in, T *__restrict__ out,
-                                                     int rows, double scale, int tstore, const double *__restrict__ parts, int nparts, float lam)
-{
-    static_assert(!SCR || MODE != 2, "the last transform launch knows no screening");
-    extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
-    __shared__ double s_mean;
-    cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
-    const int tid = threadIdx.x, r = blockIdx.x, p = blockIdx.y, n = P.n;
-    const cx2<T> *__restrict__ half = P.chirp + (n + 1);
-    const T *__restrict__ src = (MODE == 0) ? nullptr : in + ((size_t)p * rows + r) * n;
-    const int member = p / g.C, c = p - member * g.C;
-    const PoissonJobDev &J = jobs.j[(MODE == 1) ? 0 : member];
-    if (MODE == 2 && tid < 64) {              // the first wave: the parts in a fixed order (the first barrier below publishes the sum)
-        double m = 0.0;
-        if (parts) for (int i = tid; i < nparts; i += 64) m += parts[(size_t)p * nparts + i];
-        m = wave_sum(m);
-        if (tid == 0) s_mean = m / ((double)g.W * (double)g.H);
-    }
-    for (int i = tid; i < P.M; i += FFT_THREADS) {
-        cx2<T> a = mk<T>((T)0, (T)0);
-        if (i < n) {
-            T x;
-            if constexpr (MODE == 0) {
-                float f = dct_rhs<LAP>(g, J, c, i, r);
-                if constexpr (SCR) f = screened_rhs(f, lam, J.d[(long long)i * g.cs + (long long)r * g.rs + (long long)c * g.chs]);
-                x = (T)f;
-            } else x = src[i];
-            if (MODE == 2 && i == 0) x *= (T)0.5;
-            const cx2<T> ch = (MODE == 2) ? half[i] : P.chirp[i];
-            a = mk<T>(x * ch.x, x * ch.y);
-        }
-        S[fft_pad(i)] = a;
-    }
-    __syncthreads();
-    chirp_convolve<T>(S, P, tid);
-    if (MODE == 1) {
-        // X_k = Re(h_k y_k); divide by the eigenvalue (in double, as the DST's exact branch) and feed the quotient straight into the
-        // DCT-III: the row stays in LDS (element k is read and rewritten by the same thread: no barrier in between)
-        for (int k = tid; k < n; k += FFT_THREADS) {
-            const cx2<T> y = S[fft_pad(k)], h = half[k];
-            const T X = h.x * y.x - h.y * y.y;
-            const double eig = (2.0 * cospi((double)r / (double)rows) - 2.0) + (2.0 * cospi((double)k / (double)n) - 2.0);
-            const T den = (T)(SCR ? eig - (double)lam : eig);
-            T q = (!SCR && r == 0 && k == 0) ? (T)0 : X / den;
-            if (k == 0) q *= (T)0.5;
-            S[fft_pad(k)] = mk<T>(q * h.x, q * h.y);
-        }
-        for (int i = n + tid; i < P.M; i += FFT_THREADS) S[fft_pad(i)] = mk<T>((T)0, (T)0);
-        __syncthreads();
-        chirp_convolve<T>(S, P, tid);
-    }
-    const T mean = (MODE == 2) ? (T)s_mean : (T)0;
-    for (int k = tid; k < n; k += FFT_THREADS) {
-        const cx2<T> y = S[fft_pad(k)], ch = (MODE == 0) ? half[k] : P.chirp[k];
-        const T X = ch.x * y.x - ch.y * y.y;
-        if (MODE == 2) J.out[(long long)k * g.cs + (long long)r * g.rs + (long long)c * g.chs] = (float)(X * (T)scale + mean);
-        else if (tstore) out[((size_t)p * n + k) * rows + r] = X;
-        else out[((size_t)p * rows + r) * n + k] = X;
-    }
-}
-
-template <typename T>
-static hipError_t dct_opt_in_lds(int bytes)
-{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<1, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<2, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    // the screened forms
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<0, T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dct<1, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
-
-// ---- free sides on some of the four borders (SC_POISSON_FREE_*): each axis has its own transform -----------------------------------
-// Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
+// The four axis kinds.  Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
 // above; kind 2, a Dirichlet line at the low end and a free high end, the sine transform of odd half-frequencies
 //     S[k][j] = sin(pi (2k+1) (j+1) / (2n+1)),   k, j < n,    S S^T = (2n+1)/4 I,    eigenvalue 2 cos(pi (2k+1) / (2n+1)) - 2;
 // kind 3 is kind 2 with the spatial index reversed.  With N = 2n+1, c_m = exp(i pi m^2 / N), a_k = exp(i pi (k^2 + 2k) / N) and
@@ -514,15 +433,23 @@ __device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg
 //         y transform -> out, as MODE 0
 // MODE 2: rows of `in` [p][y][k] -> inverse x transform, scale -> the unknowns of the job's out; the same workgroup copies the ends of
 //         its pixel row that lie on Dirichlet lines, and the first / last one the whole top / bottom line, from boundary to out
-// rows: the other axis's unknowns.  SCR: as k_dct's (MODE 2 has no screened form).
-template <int MODE, typename T, bool LAP, bool SCR = false>
+// rows: the other axis's unknowns.
+// SCR (a screened solve, lam > 0): MODE 0 reads the job's data term d beside the right-hand side, same element, same lane, and
+// transforms rhs - lam d (screened_rhs); MODE 1 divides by eigenvalue sum - lam.  MODE 2 has no screened form.
+// NEU: all four sides free -- both kinds are 1 at compile time, whatever mg says.  The unscreened system is then singular: MODE 1
+// zeroes coefficient (0, 0) (screened: divided by -lam as any other), MODE 2 adds the plane's mean of boundary (parts: nparts sums
+// per plane, nullptr: 0).
+template <int MODE, typename T, bool LAP, bool SCR, bool NEU>
 __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g, MixedGeo mg, PoissonJobs jobs, const T *__restrict__ in,
-                                                     T *__restrict__ out, int rows, double scale, int tstore, float lam)
+                                                     T *__restrict__ out, int rows, double scale, int tstore, const double *__restrict__ parts,
+                                                     int nparts, float lam)
 {
     static_assert(!SCR || MODE != 2, "the last transform launch knows no screening");
     extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
+    __shared__ double s_mean;
     cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
     const int tid = threadIdx.x, r = blockIdx.x, p = blockIdx.y, n = P.n;
+    if constexpr (NEU) mg.ax = mg.ay = 1;
     const int kind = (MODE == 1) ? mg.ay : mg.ax;          // of the axis this launch transforms
     const int off = kind == 0 ? 1 : 0;
     const bool flip = kind == 3;                            // spatial index n - 1 - j
@@ -530,6 +457,12 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
     const int member = p / g.C, c = p - member * g.C;
     const PoissonJobDev &J = jobs.j[(MODE == 1) ? 0 : member];
     const int x0 = mixed_low_d(mg.ax) ? 1 : 0, y0 = mixed_low_d(mg.ay) ? 1 : 0;
+    if (MODE == 2 && NEU && tid < 64) {       // the first wave: the parts in a fixed order (the first barrier below publishes the sum)
+        double m = 0.0;
+        if (parts) for (int i = tid; i < nparts; i += 64) m += parts[(size_t)p * nparts + i];
+        m = wave_sum(m);
+        if (tid == 0) s_mean = m / ((double)g.W * (double)g.H);
+    }
     for (int i = tid; i < P.M; i += FFT_THREADS) {
         cx2<T> a = mk<T>((T)0, (T)0);
         const int j = i - off;
@@ -554,27 +487,33 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
     __syncthreads();
     chirp_convolve<T>(S, P, tid);
     if (MODE == 1) {
-        // coefficient k of column r: divide by the two axes' eigenvalues (in double; never zero: some side is a Dirichlet line) and feed the
-        // quotient into the inverse transform, the column resident in LDS (element off + k is read and rewritten by one thread)
+        // coefficient k of column r: divide by the two axes' eigenvalues (in double; zero only at (0, 0) with all four sides free) and feed
+        // the quotient into the inverse transform, the column resident in LDS (element off + k is read and rewritten by one thread)
         const double ex = mix_eig(mg.ax, r, rows);
         for (int k = tid; k < n; k += FFT_THREADS) {
             const cx2<T> t = mix_tab_k<T>(P, kind, k);
             const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
             const double eig = ex + mix_eig(kind, k, n);
-            T q = X / (T)(SCR ? eig - (double)lam : eig);
+            const T den = (T)(SCR ? eig - (double)lam : eig);
+            T q = (!SCR && NEU && r == 0 && k == 0) ? (T)0 : X / den;
             if (kind == 1 && k == 0) q *= (T)0.5;
             S[fft_pad(off + k)] = mk<T>(q * t.x, q * t.y);
         }
-        for (int i = tid; i < P.M; i += FFT_THREADS) if (i < off || i >= off + n) S[fft_pad(i)] = mk<T>((T)0, (T)0);
+        if (tid < off) S[fft_pad(tid)] = mk<T>((T)0, (T)0);
+        for (int i = off + n + tid; i < P.M; i += FFT_THREADS) S[fft_pad(i)] = mk<T>((T)0, (T)0);
         __syncthreads();
         chirp_convolve<T>(S, P, tid);
     }
+    const T mean = (MODE == 2 && NEU) ? (T)s_mean : (T)0;
     for (int k = tid; k < n; k += FFT_THREADS) {
         const cx2<T> t = (MODE == 0) ? mix_tab_k<T>(P, kind, k) : mix_tab_j<T>(P, kind, k);
         const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
         const int at = (MODE != 0 && flip) ? n - 1 - k : k;          // results of an inverse transform are spatial
-        if (MODE == 2) J.out[(long long)(x0 + at) * g.cs + (long long)(y0 + r) * g.rs + (long long)c * g.chs] = (float)(X * (T)scale);
-        else if (tstore) out[((size_t)p * n + at) * rows + r] = X;
+        if (MODE == 2) {
+            // (two forms: X scale + 0 is not X scale when that is -0)
+            const float v = NEU ? (float)(X * (T)scale + mean) : (float)(X * (T)scale);
+            J.out[(long long)(x0 + at) * g.cs + (long long)(y0 + r) * g.rs + (long long)c * g.chs] = v;
+        } else if (tstore) out[((size_t)p * n + at) * rows + r] = X;
         else out[((size_t)p * rows + r) * n + at] = X;
     }
     if (MODE == 2) {
@@ -593,16 +532,35 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
 }
 
 template <typename T>
+using MixKernel = void (*)(FftPlan<T>, PoissonGeo, MixedGeo, PoissonJobs, const T *, T *, int, double, int, const double *, int, float);
+
+// k_mix<MODE, T, lap, scr, neu> (only MODE 0 has LAP forms, MODE 2 has no SCR form)
+template <int MODE, typename T>
+static MixKernel<T> mix_kernel(bool lap, bool scr, bool neu)
+{
+    if constexpr (MODE == 0) {
+        static constexpr MixKernel<T> k[2][2][2] = { { { k_mix<0, T, false, false, false>, k_mix<0, T, false, false, true> },
+                                                       { k_mix<0, T, false, true, false>, k_mix<0, T, false, true, true> } },
+                                                     { { k_mix<0, T, true, false, false>, k_mix<0, T, true, false, true> },
+                                                       { k_mix<0, T, true, true, false>, k_mix<0, T, true, true, true> } } };
+        return k[lap][scr][neu];
+    } else if constexpr (MODE == 1) {
+        static constexpr MixKernel<T> k[2][2] = { { k_mix<1, T, false, false, false>, k_mix<1, T, false, false, true> },
+                                                  { k_mix<1, T, false, true, false>, k_mix<1, T, false, true, true> } };
+        return k[scr][neu];
+    } else {
+        return neu ? k_mix<2, T, false, false, true> : k_mix<2, T, false, false, false>;
+    }
+}
+
+template <typename T>
 static hipError_t mix_opt_in_lds(int bytes)
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<1, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<2, T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    // the screened forms
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<0, T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix<1, T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    hipError_t e = hipSuccess;
+    auto opt = [&](MixKernel<T> k) { if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+    for (int f = 0; f < 8; ++f) {      // (MODE 1 and 2 meet each of theirs more than once)
+        opt(mix_kernel<0, T>(f & 1, f & 2, f & 4)); opt(mix_kernel<1, T>(false, f & 2, f & 4)); opt(mix_kernel<2, T>(false, false, f & 4));
+    }
     return e;
 }
 
@@ -916,8 +874,7 @@ static hipError_t fft_opt_in_lds(Instance *I)
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     }
-    // the Neumann solve's transform kernels (dct_solve), and the mixed-border solve's (mixed_solve)
-    if (e == hipSuccess) e = dct_opt_in_lds<T>(bytes);
+    // the transform kernels of the solves with free sides (direct_jobs_solve)
     if (e == hipSuccess) e = mix_opt_in_lds<T>(bytes);
     done = e == hipSuccess;
     return e;
@@ -994,114 +951,17 @@ int fft_solve(Instance *I, bool fp64)
     return fp64 ? fft_solve_t<double>(I) : fft_solve_t<float>(I);
 }
 
-// The Neumann solve of m same-size jobs (C m planes): boundary-mean reduction, rows (right-hand side from the jobs' arrays), columns
-// (DCT-II, divide, DCT-III), rows (DCT-III, scale 4 / (W H), + mean, into the jobs' out) -- the launches that read or write the
-// jobs' arrays go per PoissonJobs::MAX members (the table goes by value), the column launch over all planes at once.
-// lam > 0: the screened solve -- no reduction and no mean (mark 5 sits at the start), the data term read by the first row launch,
-// the denominators shifted by -lam.
+// The solve of m same-size jobs (C m planes) with free sides on some or all of the borders (mg: poisson_mixed_geo; all four: the
+// Neumann problem): rows (right-hand side from the jobs' arrays, forward x transform), columns (forward y transform, divide, inverse),
+// rows (inverse x transform, scale, into the jobs' out with its Dirichlet lines) -- the launches that read or write the jobs' arrays go
+// per PoissonJobs::MAX members (the table goes by value), the column launch over all planes at once.
+// All four sides free, unscreened: the system is singular -- a boundary-mean reduction first (mark 5 behind it; otherwise at the start),
+// the mean added by the last launch.  lam > 0: the screened solve -- the data term read by the first row launch, the denominators
+// shifted by -lam.
 template <typename T>
-static int dct_solve_t(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, float lam)
+static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam)
 {
-    const bool scr = lam > 0.f;
-    const int W = g.W, H = g.H, planes = g.C * m;
-    SC_HIP(I, fft_opt_in_lds<T>(I));
-    FftState &S = I->fft;
-    int rc;
-    FftDim *dw = nullptr, *dh = nullptr;
-    S.forked = false;
-    S.nreq = 0;
-    if ((rc = fft_build_dim<T>(I, dw, W, nullptr, 1))) return rc;
-    if ((rc = fft_build_dim<T>(I, dh, H, dw, 1))) { for (int k = 0; k < S.nreq; ++k) S.req[k]->n = 0; S.nreq = 0; return rc; }
-    if ((rc = fft_flush_builds<T>(I))) return rc;
-    const size_t plane = (size_t)W * H;
-    if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
-    if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
-    bool any_b = false;
-    for (int k = 0; k < m && !scr; ++k) any_b = any_b || jobs[k].b;
-    const int np = poisson_mean_parts(H);
-    double *parts = nullptr;
-    if (any_b) {
-        if ((rc = ensure(I, S.mean, sizeof(double) * (size_t)planes * np, false))) return rc;
-        parts = (double *)S.mean.p;
-        launch_poisson_mean(g, jobs, m, parts, I->stream);
-        SC_HIP(I, hipGetLastError());
-    }
-    stage_mark(I, 5);
-    if (S.pending) {
-        SC_HIP(I, hipStreamWaitEvent(I->stream, S.ev_built, 0));
-        S.pending = false;
-    }
-    const FftPlan<T> Pw = fft_plan_of<T>(*dw), Ph = fft_plan_of<T>(*dh);
-    const size_t ldsw = sizeof(cx2<T>) * (size_t)(fft_pad(Pw.M) + 1), ldsh = sizeof(cx2<T>) * (size_t)(fft_pad(Ph.M) + 1);
-    T *A = (T *)S.A.p, *B = (T *)S.B.p;
-    const double scale = 4.0 / ((double)W * (double)H);
-    const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as fft_solve_t: small planes are stored transposed, no transpose launches
-    // per launch of up to PoissonJobs::MAX members: fn(table, first plane, planes)
-    auto chunks = [&](auto fn) {
-        for (int i0 = 0; i0 < m; i0 += PoissonJobs::MAX) {
-            PoissonJobs t{};
-            const int cnt = std::min(m - i0, (int)PoissonJobs::MAX);
-            for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
-            fn(t, (size_t)g.C * i0, g.C * cnt);
-        }
-    };
-    const PoissonJobs none{};
-    T *rows_out = tiny ? B : A;              // the row transforms' plane; B[p][x][y] when stored transposed
-    const double *const no_parts = nullptr;
-    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
-        const dim3 grid(H, np_);
-        T *const o = rows_out + p0 * plane;
-        const int ts = tiny ? 1 : 0;
-        if (scr) {
-            if (lap) hipLaunchKernelGGL((k_dct<0, T, true, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, lam);
-            else hipLaunchKernelGGL((k_dct<0, T, false, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, lam);
-        } else {
-            if (lap) hipLaunchKernelGGL((k_dct<0, T, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, 0.f);
-            else hipLaunchKernelGGL((k_dct<0, T, false>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, (const T *)nullptr, o, H, 1.0, ts, no_parts, 0, 0.f);
-        }
-    });
-    // the column launch: B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
-    auto columns = [&](int ts) {
-        if (scr) hipLaunchKernelGGL((k_dct<1, T, false, true>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, ts, no_parts, 0, lam);
-        else hipLaunchKernelGGL((k_dct<1, T, false>), dim3(W, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, none, (const T *)B, A, W, 1.0, ts, no_parts, 0, 0.f);
-    };
-    if (tiny) {
-        columns(1);      // A[p][y][x]
-    } else {
-        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((W + 63) / 64, (H + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, H, W);      // B[p][x][y]
-        columns(0);
-        hipLaunchKernelGGL((k_fft_transpose<T>), dim3((H + 63) / 64, (W + 63) / 64, planes), dim3(256), 0, I->stream, (const T *)A, B, W, H);      // B[p][y][x]
-    }
-    const T *rows_in = tiny ? A : B;
-    chunks([&](const PoissonJobs &t, size_t p0, int np_) {
-        hipLaunchKernelGGL((k_dct<2, T, false>), dim3(H, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, t, rows_in + p0 * plane, (T *)nullptr, H, scale, 0,
-                           parts ? (const double *)(parts + p0 * np) : (const double *)nullptr, np, 0.f);
-    });
-    SC_HIP(I, hipGetLastError());
-    stage_mark(I, 6);
-    I->info.method = SC_METHOD_FFT;
-    I->info.sweeps = 1;
-    I->info.converged = 1;
-    I->info.rel_residual = NAN;
-    I->info.sweep_launches = 3;
-    return SC_OK;
-}
-
-int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
-{
-    if (!fft_supported(g.W, g.H, fp64)) {
-        I->err = fp64 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: more than 4096 pixels per side" : "SC_POISSON_NEUMANN: more than 8192 pixels per side";
-        return SC_ERR_BAD_SIZE;
-    }
-    return fp64 ? dct_solve_t<double>(I, g, lap, jobs, m, lam) : dct_solve_t<float>(I, g, lap, jobs, m, lam);
-}
-
-// The solve with free sides on some of the borders, m same-size jobs (C m planes): dct_solve's three transform launches with k_mix, each
-// axis under its own transform (MixedGeo); no reduction (the system is regular), the Dirichlet lines of out written by the last launch.
-template <typename T>
-static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam)
-{
-    const bool scr = lam > 0.f;
+    const bool scr = lam > 0.f, all_free = mg.ax == 1 && mg.ay == 1;
     const int nx = mg.nx, ny = mg.ny, planes = g.C * m;
     SC_HIP(I, fft_opt_in_lds<T>(I));
     FftState &S = I->fft;
@@ -1115,6 +975,16 @@ static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, b
     const size_t plane = (size_t)nx * ny;
     if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
     if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
+    bool any_b = false;
+    for (int k = 0; k < m && all_free && !scr; ++k) any_b = any_b || jobs[k].b;
+    const int np = poisson_mean_parts(g.H);
+    const double *parts = nullptr;
+    if (any_b) {
+        if ((rc = ensure(I, S.mean, sizeof(double) * (size_t)planes * np, false))) return rc;
+        launch_poisson_mean(g, jobs, m, (double *)S.mean.p, I->stream);
+        SC_HIP(I, hipGetLastError());
+        parts = (const double *)S.mean.p;
+    }
     stage_mark(I, 5);
     if (S.pending) {
         SC_HIP(I, hipStreamWaitEvent(I->stream, S.ev_built, 0));
@@ -1123,9 +993,11 @@ static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, b
     const FftPlan<T> Pw = fft_plan_of<T>(*dw), Ph = fft_plan_of<T>(*dh);
     const size_t ldsw = sizeof(cx2<T>) * (size_t)(fft_pad(Pw.M) + 1), ldsh = sizeof(cx2<T>) * (size_t)(fft_pad(Ph.M) + 1);
     T *A = (T *)S.A.p, *B = (T *)S.B.p;
+    // (the two expressions round differently in double: each path keeps the one its outputs were pinned with)
     auto axis_scale = [](int kind, int n) { return kind == 0 ? 2.0 / (n + 1.0) : kind == 1 ? 2.0 / n : 4.0 / (2.0 * n + 1.0); };
-    const double scale = axis_scale(mg.ax, nx) * axis_scale(mg.ay, ny);
-    const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as dct_solve_t
+    const double scale = all_free ? 4.0 / ((double)nx * (double)ny) : axis_scale(mg.ax, nx) * axis_scale(mg.ay, ny);
+    const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as fft_solve_t: small planes are stored transposed, no transpose launches
+    // per launch of up to PoissonJobs::MAX members: fn(table, first plane, planes)
     auto chunks = [&](auto fn) {
         for (int i0 = 0; i0 < m; i0 += PoissonJobs::MAX) {
             PoissonJobs t{};
@@ -1135,22 +1007,16 @@ static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, b
         }
     };
     const PoissonJobs none{};
-    T *rows_out = tiny ? B : A;
+    const double *const no_parts = nullptr;
+    T *rows_out = tiny ? B : A;              // the row transforms' plane; B[p][x][y] when stored transposed
     chunks([&](const PoissonJobs &t, size_t p0, int np_) {
-        const dim3 grid(ny, np_);
-        T *const o = rows_out + p0 * plane;
-        const int ts = tiny ? 1 : 0;
-        if (scr) {
-            if (lap) hipLaunchKernelGGL((k_mix<0, T, true, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, lam);
-            else hipLaunchKernelGGL((k_mix<0, T, false, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, lam);
-        } else {
-            if (lap) hipLaunchKernelGGL((k_mix<0, T, true>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, 0.f);
-            else hipLaunchKernelGGL((k_mix<0, T, false>), grid, dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr, o, ny, 1.0, ts, 0.f);
-        }
+        hipLaunchKernelGGL((mix_kernel<0, T>(lap, scr, all_free)), dim3(ny, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, (const T *)nullptr,
+                           rows_out + p0 * plane, ny, 1.0, tiny ? 1 : 0, no_parts, 0, lam);
     });
-    auto columns = [&](int ts) {      // B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
-        if (scr) hipLaunchKernelGGL((k_mix<1, T, false, true>), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A, nx, 1.0, ts, lam);
-        else hipLaunchKernelGGL((k_mix<1, T, false>), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A, nx, 1.0, ts, 0.f);
+    // the column launch: B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
+    auto columns = [&](int ts) {
+        hipLaunchKernelGGL((mix_kernel<1, T>(false, scr, all_free)), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A,
+                           nx, 1.0, ts, no_parts, 0, lam);
     };
     if (tiny) {
         columns(1);      // A[p][y][x]
@@ -1161,7 +1027,8 @@ static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, b
     }
     const T *rows_in = tiny ? A : B;
     chunks([&](const PoissonJobs &t, size_t p0, int np_) {
-        hipLaunchKernelGGL((k_mix<2, T, false>), dim3(ny, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, rows_in + p0 * plane, (T *)nullptr, ny, scale, 0, 0.f);
+        hipLaunchKernelGGL((mix_kernel<2, T>(false, false, all_free)), dim3(ny, np_), dim3(FFT_THREADS), ldsw, I->stream, Pw, g, mg, t, rows_in + p0 * plane,
+                           (T *)nullptr, ny, scale, 0, parts ? parts + p0 * np : no_parts, np, 0.f);
     });
     SC_HIP(I, hipGetLastError());
     stage_mark(I, 6);
@@ -1173,13 +1040,15 @@ static int mixed_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, b
     return SC_OK;
 }
 
-int mixed_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
+int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
 {
     if (!fft_supported(mg.nx, mg.ny, fp64)) {
-        I->err = fp64 ? "free sides with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "free sides: more than 8192 unknowns per axis";
+        if (mg.ax == 1 && mg.ay == 1)
+            I->err = fp64 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: more than 4096 pixels per side" : "SC_POISSON_NEUMANN: more than 8192 pixels per side";
+        else I->err = fp64 ? "free sides with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "free sides: more than 8192 unknowns per axis";
         return SC_ERR_BAD_SIZE;
     }
-    return fp64 ? mixed_solve_t<double>(I, g, mg, lap, jobs, m, lam) : mixed_solve_t<float>(I, g, mg, lap, jobs, m, lam);
+    return fp64 ? direct_jobs_solve_t<double>(I, g, mg, lap, jobs, m, lam) : direct_jobs_solve_t<float>(I, g, mg, lap, jobs, m, lam);
 }
 
 } // namespace sc

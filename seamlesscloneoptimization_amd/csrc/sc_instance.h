@@ -68,7 +68,7 @@ struct FftState {
     unsigned long long tick = 0;
     DevBuf A, B;                           // work planes [C][h][w]
     DevBuf hst_all;                        // pinned staging of all FXY eigenvalue-table entries (one block; FftFxy::hst is unused since round 5)
-    DevBuf mean;                           // the Neumann solve's partial sums of boundary, double [planes][parts] (dct_solve)
+    DevBuf mean;                           // the Neumann solve's partial sums of boundary, double [planes][parts] (direct_jobs_solve)
     DevBuf tw64;                           // double twiddles of the build's own transform (float tables are built through a double FFT)
     hipEvent_t ev_fork = nullptr, ev_built = nullptr;   // the build runs on the instance's second stream
     bool pending = false;                  // ... and `stream` has not waited for ev_built yet
@@ -345,6 +345,9 @@ inline MixedGeo poisson_mixed_geo(int f, int cols, int rows)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 bool aligned4(const void *p);
+// SC_FLAG_FFT_FP64's limit on a direct solve with free sides `free` (poisson_free_sides'; 0: the Dirichlet frame): `why` and
+// SC_ERR_BAD_SIZE when an axis has more unknowns than the double transforms take
+int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why);
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
 int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);
@@ -398,13 +401,11 @@ void rag_end(Instance *I);
 int dst_solve(Instance *I);                                           // sc_dst.hip: SC_METHOD_DST
 int fft_solve(Instance *I, bool fp64);                                // sc_fft.hip: SC_METHOD_FFT (fp64: SC_FLAG_FFT_FP64)
 bool fft_supported(int w, int h, bool fp64);
-// sc_fft.hip: the Neumann problem on caller arrays (SC_POISSON_NEUMANN): m same-size jobs as C m planes, straight from the jobs' arrays into
-// their out arrays (marks: 5 behind the boundary-mean reduction, 6 behind the last transform launch)
+// sc_fft.hip: the problem with free sides on some or all of the borders (SC_POISSON_FREE_*, SC_POISSON_NEUMANN; mg: poisson_mixed_geo) on
+// caller arrays: m same-size jobs as C m planes, straight from the jobs' arrays into their out arrays, each axis under its own transform
+// (marks: 5 behind the boundary-mean reduction of an unscreened Neumann solve, else at the start; 6 behind the last transform launch)
 // (lam > 0: the screened solve, sc_screened_api.cpp: the jobs' data term read with the right-hand side, no mean)
-int dct_solve(Instance *I, const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
-// ... and the problem with free sides on some of the borders (SC_POISSON_FREE_*; mg: poisson_mixed_geo): the same three launches, each
-// axis under its own transform; marks 5 (at the start: nothing is reduced) and 6
-int mixed_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
+int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
 bool wants_float_tables(const Instance *I);
 int effective_method(const Instance *I);                              // sc_solver.cpp: what SC_METHOD_AUTO resolves to for the fields bound to I
 int output_nodes(Instance *I, LmNodes &lm);  // sc_solver.cpp: the float-table correction the post-process of result(I) has to add (none: lm.CN == nullptr)

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(PS_LANES) void k_poisson_out_group(PoissonGeo g, Po
     poisson_out_block<INTER>(g, t.j[blockIdx.z], U, g.C * (int)blockIdx.z);
 }
 
-// The Neumann solve's free constant (sc_fft.hip, dct_solve): sums of boundary in double.  Workgroup (i, c, k): rows [i H / np, (i + 1) H / np)
+// The Neumann solve's free constant (sc_fft.hip, direct_jobs_solve): sums of boundary in double.  Workgroup (i, c, k): rows [i H / np, (i + 1) H / np)
 // of channel c of member k, x inner; a lane's running sum, the wave's by shuffles, the four waves' through LDS -- one order of
 // additions per (W, H), whatever the batch, so a member's mean is its solo run's to the bit.  A job without boundary: zeros.
 __global__ __launch_bounds__(PS_LANES) void k_poisson_mean(PoissonGeo g, PoissonJobs t, double *__restrict__ parts)

@@ -8,11 +8,9 @@
 // right-hand side and level 1 and the 16-bit field between level-0 launches assume 8-bit data), update_tol = the call's tol.  The
 // instance's stored options and solve state (CallScope) are restored on every way out.
 //
-// SC_POISSON_NEUMANN: no fields, no pre-process or output launch -- per chunk dct_solve (sc_fft.hip) works straight between the jobs'
-// arrays: the boundary-mean reduction, then the three transform launches of the DCT solve.
-//
-// SC_POISSON_FREE_* on one to three sides: the same shape with mixed_solve -- each axis under the transform of its two ends, the
-// Dirichlet lines of out written by the last transform launch.
+// SC_POISSON_NEUMANN and SC_POISSON_FREE_* on one to three sides: no fields, no pre-process or output launch -- per chunk
+// direct_jobs_solve (sc_fft.hip) works straight between the jobs' arrays: three transform launches, each axis under the transform of
+// its two ends, the Dirichlet lines of out written by the last one; in front of them the boundary-mean reduction of a Neumann call.
 //
 // The screened call (sc_screened_api.cpp) runs through the same poisson_run with PoissonCall::lam > 0: the jobs carry their data
 // term, the solve is the direct one (SC_METHOD_FFT) with its denominators shifted by -lam.
@@ -42,14 +40,18 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
     if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
     if (l->channels < 1 || l->channels > 4) { *why = "channels must be 1..4"; return SC_ERR_BAD_ARG; }
     if (l->col_stride <= 0 || l->row_stride <= 0 || l->channel_stride <= 0) { *why = "strides must be positive"; return SC_ERR_BAD_ARG; }
-    if (neumann) {
-        if (l->cols < 2 || l->rows < 2) { *why = "SC_POISSON_NEUMANN: the image must be at least 2 x 2"; return SC_ERR_BAD_SIZE; }
-        if (!fft_supported(l->cols, l->rows, false)) { *why = "SC_POISSON_NEUMANN: the image must be at most 8192 x 8192"; return SC_ERR_BAD_SIZE; }
-    } else if (free) {
-        if (l->cols < 2 || l->rows < 2) { *why = "free sides: the image must be at least 2 x 2"; return SC_ERR_BAD_SIZE; }
-        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);
+    if (free) {
+        if (l->cols < 2 || l->rows < 2) {
+            *why = neumann ? "SC_POISSON_NEUMANN: the image must be at least 2 x 2" : "free sides: the image must be at least 2 x 2";
+            return SC_ERR_BAD_SIZE;
+        }
+        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);       // (all four sides free: every pixel an unknown)
         if (mg.nx < 1 || mg.ny < 1) { *why = "free sides: at least 1 unknown per axis (3 pixels between two Dirichlet lines)"; return SC_ERR_BAD_SIZE; }
-        if (!fft_supported(mg.nx, mg.ny, false)) { *why = "free sides: at most 8192 unknowns (pixels less the axis's Dirichlet lines) per axis"; return SC_ERR_BAD_SIZE; }
+        if (!fft_supported(mg.nx, mg.ny, false)) {
+            *why = neumann ? "SC_POISSON_NEUMANN: the image must be at most 8192 x 8192"
+                           : "free sides: at most 8192 unknowns (pixels less the axis's Dirichlet lines) per axis";
+            return SC_ERR_BAD_SIZE;
+        }
     } else {
         if (l->cols < 3 || l->rows < 3) { *why = "the image must be at least 3 x 3"; return SC_ERR_BAD_SIZE; }
         if (l->cols > 65536 || l->rows > 65536) { *why = "the image must be at most 65536 x 65536"; return SC_ERR_BAD_SIZE; }
@@ -76,6 +78,16 @@ size_t poisson_span(const sc_poisson_layout *l)
 }
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+
+int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why)
+{
+    const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);
+    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
+        I->err = why;
+        return SC_ERR_BAD_SIZE;
+    }
+    return SC_OK;
+}
 
 // a job's own code: the pointers its kind (poisson_norm_kind's) needs, 4-byte aligned (a Neumann job may come without boundary: mean
 // zero; with a Dirichlet line on any side boundary is required)
@@ -140,66 +152,31 @@ int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     return solve_rc;
 }
 
-// the code on this instance of a call with free sides (kind: poisson_norm_kind's): the methods that serve it, the limit of its
-// transforms' precision
-int mixed_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
-{
-    const int method = I->opts.method;
-    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
-        I->err = "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)";
-        return SC_ERR_BAD_ARG;
-    }
-    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), l->cols, l->rows);
-    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
-        I->err = "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
-        return SC_ERR_BAD_SIZE;
-    }
-    return SC_OK;
-}
-
-// a Neumann call's code on this instance: the methods that serve it, the side limit of its transforms' precision
-int neumann_instance_check(Instance *I, const sc_poisson_layout *l)
-{
-    const int method = I->opts.method;
-    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
-        I->err = "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)";
-        return SC_ERR_BAD_ARG;
-    }
-    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(l->cols, l->rows, true)) {
-        I->err = "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096";
-        return SC_ERR_BAD_SIZE;
-    }
-    return SC_OK;
-}
-
-// The same for a Neumann call: no fields; marks 5 (reduction done) and 6 (transforms done) come from dct_solve, 7 = 6 (the output is
-// the last transform launch's store).
-int neumann_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
-{
-    stage_mark(I, 0);
-    const int rc = dct_solve(I, g, (kind & ~SC_POISSON_NEUMANN) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
-    if (rc) return rc;
-    stage_mark(I, 7);
-    return SC_OK;
-}
-
-// ... and for a call with one to three free sides: mixed_solve, marks as the Neumann call's
-int mixed_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
+// The same for a call with free sides (kind: poisson_norm_kind's; all four: the Neumann call): no fields; marks 5 (the Neumann call's
+// reduction done) and 6 (transforms done) come from direct_jobs_solve, 7 = 6 (the output is the last transform launch's store).
+int free_sides_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
 {
     stage_mark(I, 0);
     const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), g.W, g.H);
-    const int rc = mixed_solve(I, g, mg, poisson_base(kind) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
+    const int rc = direct_jobs_solve(I, g, mg, poisson_base(kind) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
     if (rc) return rc;
     stage_mark(I, 7);
     return SC_OK;
 }
 
-// the instance's word on a call of this kind (poisson_norm_kind's) before anything runs
+// the instance's word on a call of this kind (poisson_norm_kind's) before anything runs: with free sides, the methods that serve it
+// and the limit of its transforms' precision
 int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
 {
-    if (kind & SC_POISSON_NEUMANN) return neumann_instance_check(I, l);
-    if (kind & SC_POISSON_FREE_ALL) return mixed_instance_check(I, kind, l);
-    return SC_OK;
+    const int free = poisson_free_sides(kind), method = I->opts.method;
+    if (!free) return SC_OK;
+    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
+        I->err = free == 15 ? "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)"
+                            : "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)";
+        return SC_ERR_BAD_ARG;
+    }
+    return direct_fp64_check(I, free, l, free == 15 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
+                                                    : "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
 }
 
 void add_timing(Instance *I, float t[4])
@@ -239,8 +216,7 @@ int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, c
     int worst = SC_OK;
     for (int i0 = 0; i0 < nv; i0 += per) {
         const int m = std::min(per, nv - i0);
-        int rc = (p.kind & SC_POISSON_NEUMANN) ? neumann_chunk(I, p.kind, g, dj + i0, m, p.lam)
-                 : (p.kind & SC_POISSON_FREE_ALL) ? mixed_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
+        int rc = poisson_free_sides(p.kind) ? free_sides_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
         if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
             if (timed) {
                 SC_HIP(I, hipStreamSynchronize(I->stream));

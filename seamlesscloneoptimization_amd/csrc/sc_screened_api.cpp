@@ -1,12 +1,12 @@
 // sc_screened_api.cpp -- the screened Poisson solve on float32 images (sc_hip_screened_check, sc_hip_screened_device, sc_hip_screened):
 //     minimise lambda sum (u - d)^2 + sum |grad u - g|^2,   i.e.   (A - lambda) u = div g - lambda d,   lambda > 0,
 // A the 5-point operator of sc_hip_poisson with a Dirichlet frame, a reflecting border (SC_POISSON_NEUMANN) or Dirichlet lines on
-// some sides and free ones on the others (SC_POISSON_FREE_*: k_mix, which divides by the two axes' eigenvalue sum - lambda).
+// some sides and free ones on the others (SC_POISSON_FREE_*).
 //
 // A call is a Poisson call (sc_poisson_api.cpp: validation, chunks of at most SC_POISSON_MAX_PLANES planes, stage marks, codes) with
 // PoissonCall::lam set: the jobs carry their data term, the launches that build the right-hand side read it (F = lap - lambda d:
-// k_poisson_pre / k_poisson_pre_group; k_dct MODE 0), and the direct solves divide by eigenvalue - lambda (k_fft_dst<1>'s exact branch,
-// k_dct MODE 1).  Always the direct solve: SC_METHOD_AUTO resolves to SC_METHOD_FFT at any size.
+// k_poisson_pre / k_poisson_pre_group; k_mix MODE 0 with any free side), and the direct solves divide by eigenvalue - lambda
+// (k_fft_dst<1>'s exact branch, k_mix MODE 1).  Always the direct solve: SC_METHOD_AUTO resolves to SC_METHOD_FFT at any size.
 #include "sc_instance.h"
 #include <cmath>
 #include <vector>
@@ -42,21 +42,9 @@ int screened_instance_check(Instance *I, const sc_screened_params *p, const sc_p
         return SC_ERR_BAD_ARG;
     }
     const int free = poisson_free_sides(p->kind);
-    if (free && free != 15) {
-        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);
-        if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
-            I->err = "a screened solve with free sides and SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
-            return SC_ERR_BAD_SIZE;
-        }
-        return SC_OK;
-    }
-    const int frame = free ? 0 : 2;
-    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(l->cols - frame, l->rows - frame, true)) {
-        I->err = frame ? "a screened solve with SC_FLAG_FFT_FP64: at most 4096 unknowns (pixels - 2) per side"
-                       : "a screened SC_POISSON_NEUMANN solve with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096";
-        return SC_ERR_BAD_SIZE;
-    }
-    return SC_OK;
+    return direct_fp64_check(I, free, l, !free ? "a screened solve with SC_FLAG_FFT_FP64: at most 4096 unknowns (pixels - 2) per side"
+                                     : free == 15 ? "a screened SC_POISSON_NEUMANN solve with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
+                                                  : "a screened solve with free sides and SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
 }
 
 // a job's own code: data always, boundary with a Dirichlet line on any side, the arrays of its kind (poisson_norm_kind's), out; each

@@ -1,4 +1,4 @@
-"""The Neumann DCT solve (SC_POISSON_NEUMANN: k_dct, k_fft_build kind 1, k_poisson_mean) at every transform length class, on both
+"""The Neumann DCT solve (SC_POISSON_NEUMANN: k_mix with both axes of kind 1, k_fft_build kind 1, k_poisson_mean) at every transform length class, on both
 sides of every launch-shape cut, through the table cache with both kinds, at its size limits and over what it must never read
 (the GPU side of tests/test_neumann_lengths_host.py).
 

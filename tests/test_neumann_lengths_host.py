@@ -1,6 +1,6 @@
 """CPU side of tests/test_gpu_neumann_lengths.py: the float32 yardstick (neumann_np.solve_f32) is single precision throughout and
 stays where it was measured; the transform length classes of the Neumann solve (FftDim kind 1: n pixels, chirp of period 2n, the
-same fft_len as the DST kind); the launch-shape rules of dct_solve_t and k_poisson_mean mirrored in Python, with the sizes the GPU
+same fft_len as the DST kind); the launch-shape rules of direct_jobs_solve_t and k_poisson_mean mirrored in Python, with the sizes the GPU
 file puts on either side of each cut."""
 import numpy as np
 import pytest
@@ -9,7 +9,7 @@ import neumann_np
 from neumann_bounds import err_and_res
 from test_direct_lengths_host import fft_M, fft_max_M, fft_supported, length_classes
 
-TINY_BYTES = 4 << 20             # sc_fft.hip dct_solve_t: plane * sizeof(T) <= 4 MiB -> the plane is stored transposed, no transposes
+TINY_BYTES = 4 << 20             # sc_fft.hip direct_jobs_solve_t: plane * sizeof(T) <= 4 MiB -> the plane is stored transposed, no transposes
 JOBS_MAX = 16                    # sc_common.h PoissonJobs::MAX: members per launch that touches the callers' arrays
 MEAN_PARTS_MAX = 256             # sc_poisson.hip poisson_mean_parts
 
