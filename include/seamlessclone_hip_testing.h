@@ -116,6 +116,12 @@ SC_API int sc_hip_time_tail_phases(void *instance, unsigned long long *cycles11)
  * last interval).  Returns 0, or the number of the check that failed. */
 SC_API int sc_hip_selftest_host(void);
 
+/* host only (needs no GPU, launches nothing): the instantiation k_cycle0<T, .., PRO, .., TAG> (csrc/sc_cycle0.hip; TAG: the C0_* bits of
+ * csrc/sc_common.h) the level-0 multigrid launcher picks for facts[13] = sweeps, prolong, f_half, u_half, q16_in, q16_out, final_cycle,
+ * out_bytes, composed, l1_half, timing, bands (pointer given), rag (size class).  form[3] receives T, PRO, TAG; returns 0, or -1: no such
+ * form, nothing would be launched.  facts == NULL: form receives entry `index` of the table of instantiated forms, its length is returned. */
+SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -302,6 +302,8 @@ def load():
     L.sc_hip_reference_tables_singular.restype = C.c_int
     L.sc_hip_selftest_host.argtypes = []
     L.sc_hip_selftest_host.restype = C.c_int
+    L.sc_hip_cycle0_form.argtypes = [i32p, C.c_int, i32p]
+    L.sc_hip_cycle0_form.restype = C.c_int
     L.sc_hip_plan_groups.argtypes = [i32p, C.c_int, C.c_int, C.POINTER(SolverOpts), i32p, i32p]
     L.sc_hip_plan_groups.restype = C.c_int
     L.sc_hip_plan_size.argtypes = [C.c_int, C.c_int, C.POINTER(SolverOpts), i32p]
@@ -977,6 +979,26 @@ def plan_prepare(sizes, opts: "SolverOpts | None" = None) -> int:
 
 def plan_cache_clear() -> None:
     load().sc_hip_plan_cache_clear()
+
+
+CYCLE0_FACTS = ("sweeps", "prolong", "f_half", "u_half", "q16_in", "q16_out", "final_cycle", "out_bytes", "composed", "l1_half", "timing",
+                "bands", "rag")
+
+
+def cycle0_form(**facts):
+    """Host-only: (T, PRO, TAG) of the k_cycle0 instantiation the level-0 launcher picks for these facts of a launch descriptor
+    (CYCLE0_FACTS; those left out are 0 / false), or -1 where the library has no such form (csrc/sc_cycle0.hip)."""
+    f = (C.c_int * len(CYCLE0_FACTS))(*[int(facts.pop(k, 0)) for k in CYCLE0_FACTS])
+    if facts:
+        raise TypeError("cycle0_form: no such fact: %s" % sorted(facts))
+    out = (C.c_int * 3)()
+    return tuple(out) if load().sc_hip_cycle0_form(f, 0, out) == 0 else -1
+
+
+def cycle0_forms():
+    """Host-only: every (T, PRO, TAG) in the library's table of instantiated level-0 forms."""
+    out = (C.c_int * 3)()
+    return [tuple(out) for i in range(load().sc_hip_cycle0_form(None, -1, out)) if load().sc_hip_cycle0_form(None, i, out)]
 
 
 def plan_groups(sizes, cap: int = 0, opts: "SolverOpts | None" = None):

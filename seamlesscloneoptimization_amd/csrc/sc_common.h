@@ -123,7 +123,7 @@ void launch_preprocess(const uint8_t *body_org, int bstep, const uint8_t *face_o
 // bounding box the host assumed when it launched a clone before the device's answer was back (d_rect == nullptr: none)
 struct RectGuard { const int *d_rect = nullptr; int x0 = 0, x1 = 0, y0 = 0, y1 = 0; };
 // "Do not write": a device word the launches of one solve may set to that solve's generation number (a 16-bit fixed-point store
-// of the field saturated, k_cycle0 TAG bit 9); the output launches of the same solve then write nothing and the host repeats
+// of the field saturated, k_cycle0 with C0_Q16_OUT); the output launches of the same solve then write nothing and the host repeats
 // the clone on float fields.  A generation instead of a flag: nothing has to be reset between solves.  p == nullptr: none.
 // `host`: a second copy of the word in pinned host memory, for the host to read without a copy command (the device copy is the
 // one the output launches test: a million threads polling a word across PCIe made the splice 170 times slower).
@@ -173,7 +173,7 @@ void launch_postprocess(Field U, uint8_t *body_org, int bstep, hipStream_t s, Re
 // the same for a group (fields of 3n channels), one launch per 16 members
 void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode);
 void launch_postprocess_group(Field U, const ImageJob *jobs, int n, hipStream_t s, LmNodes lm = LmNodes(), AbortFlag ab = AbortFlag());
-// splice of output bytes a multigrid launch left planar in Q's memory (launch_cycle0_out): interleave into the destination
+// splice of output bytes a multigrid launch left planar in Q's memory (launch_cycle0, out_bytes): interleave into the destination
 void launch_splice_planar(Field Q, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), AbortFlag ab = AbortFlag());
 void launch_splice_planar_group(Field Q, const ImageJob *jobs, int n, hipStream_t s, AbortFlag ab = AbortFlag());
 void launch_half_to_float(const void *src_half, float *dst, size_t n, hipStream_t s);
@@ -200,27 +200,9 @@ int  launch_rb_tb_prolong0(Field Uin, Field Uout, Field F, int sweeps, const MGG
 int  tb_blocks_level0(int W, int H, int C, int sweeps);
 void launch_max_final(const float *d_partial, int n, unsigned *d_out, hipStream_t s);
 void launch_max_final2(const float *d_a, int na, const float *d_b, int nb, unsigned *d_out2, hipStream_t s, const unsigned *flag = nullptr);   // out[0] = max a, out[1] = max b (-1: b empty), out[2] = *flag (0 without one)
-// whole level-0 part of a V-cycle in one launch (sc_cycle0.hip): [prolong E] + `sweeps` RBGS sweeps +
-// residual + restriction into Fc.  Returns #partials written, 0 without prolong, -1 if unsupported.
-int  launch_cycle0(Field Uin, Field Uout, Field F, Field Fc, Field E, const MGGeom &g, int sweeps, bool prolong,
-                   float *partial, hipStream_t s, bool tag = false, bool f_half = false, bool u_half = false,
-                   bool final_cycle = false, float4 *bands = nullptr, bool l1_half = false, bool q16_out = false, AbortFlag sat = AbortFlag(),
-                   const RagMember *rag = nullptr);      // rag (here and below): the launch serves a size class, see RagMember
-// bands (final form, or 4 sweeps with prolongation): receives the cell shares of the float-table correction of the field the
-// launch writes, two float4 per (channel, tile row, wave, 8-column cell) -- see k_cycle0 and sc_lowmode.hip
+// tiling of a level-0 launch (sc_cycle0.hip, launch_cycle0 below)
 void cycle0_row_geometry(int H, int sweeps, int &nby, int &step, int &hy);
 int  cycle0_blocks(int W, int H, int C, int sweeps);
-// the same launch with its prolongation source composed on the fly from level 1 (before post-smoothing) and level 2
-// (sc_cycle0.hip, ComposeArgs); -1: combination not instantiated
-int  launch_cycle0_composed(Field Uin, Field Uout, Field F, Field Fc, Field U1, const MGGeom &g, int sweeps, float *partial,
-                            hipStream_t s, bool tag, bool f_half, bool final_cycle, Field E2, const MGGeom &g1, float4 *bands = nullptr, bool l1_half = false,
-                            int u_q16 = 0, AbortFlag sat = AbortFlag(), const RagMember *rag = nullptr);     // sat: where a saturating 16-bit store reports itself
-// tagged twins of the other launches of a fast-path solve, for isolated timing (sc_cycle0.hip)
-int  launch_cycle0_twin(int form, Field Uin, Field Uout, Field F, Field Fc, Field U1, const MGGeom &g, float *partial, hipStream_t s,
-                        Field E2, const MGGeom &g1, float4 *bands, const LmNodes &lm);
-// the last cycle with its result leaving as output bytes (planar, in Q's memory) instead of as a field; see sc_cycle0.hip
-int  launch_cycle0_out(Field Uin, Field Q, Field F, Field Fc, Field E, const MGGeom &g, float *partial, hipStream_t s, bool f_half,
-                       bool composed, Field E2, const MGGeom &g1, const LmNodes &lm, bool l1_half = false, const RagMember *rag = nullptr);
 // coarse level: zero-guess pre-smoothing + residual + restriction fused (Uout = smoothed correction, Fc = next RHS)
 bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io = false,
                          const RagMember *rag = nullptr, int lev = 0);
@@ -246,6 +228,41 @@ struct MGGeom { MGDim x, y; };
 // Composed prolongation source (sc_mg_device.h): the level interpolated from ran without post-smoothing and without a
 // prolongation launch of its own; E2 = finished correction of the level below it, g1 = its geometry (transfer to that level).
 struct ComposeArgs { Field E2; MGGeom g1; };
+
+// The bits of k_cycle0's template parameter TAG: the FORM of a launch (sc_cycle0.hip).
+constexpr int C0_TIMING   = 1;      // the same code under a second symbol, for isolated timing (sc_hip_time_cycle0_form)
+constexpr int C0_F_HALF   = 2;      // F holds float16 (level 0 only: the clone's right-hand side as the pre-process stored it)
+constexpr int C0_U_HALF   = 4;      // Uin holds float16: the first launch of a clone reads the 8-bit destination values the pre-process stored so
+constexpr int C0_FINAL    = 8;      // the cycle the stop rule judges: no residual / restriction; leaves the float-table correction's cell shares in `bands` if not null
+constexpr int C0_COMPOSED = 16;     // level 0 only: E is level 1's correction after pre-smoothing, the interpolated level-2 correction is added on the fly (ComposeArgs)
+constexpr int C0_OUT      = 32;     // a final cycle leaving as bytes: Uout's memory receives planar 8-bit output values (node correction added, clamped, truncated)
+constexpr int C0_BANDS    = 64;     // a full cycle that leaves the float-table correction's cell shares of the field it writes in `bands`
+constexpr int C0_L1_HALF  = 128;    // LEVEL 1's right-hand side and correction are float16: what level 0 restricts to and interpolates from, the level-1 launch's own F and Uout
+constexpr int C0_Q16_IN   = 256;    // Uin holds 16-bit fixed point (c0_load_q16): the field between the first level-0 launches of the fast path
+constexpr int C0_Q16_OUT  = 512;    // ... and so will Uout; a store that saturates reports itself (AbortFlag)
+constexpr int C0_RAG      = 1024;   // a SIZE CLASS (RagMember): strides and grid are the class's, all else the member's, read from rag[channel / 3]; tiles beyond its extent leave
+
+// One level-0 launch (sc_cycle0.hip): [prolongation of E +] `sweeps` red-black GS sweeps [+ residual + restriction into Fc]; launch_cycle0 derives (T, PRO, TAG) from these facts
+struct Cycle0Launch {
+    Field Uin, Uout, F, Fc, E;         // E: the correction interpolated from (composed: level 1's after its pre-smoothing); Fc: level 1's right-hand side
+    MGGeom g{};
+    int sweeps = 0;                    // post + pre (full cycle), post (final cycle) or pre (first launch, catch-up)
+    bool prolong = false;              // add P E first and write the per-workgroup max |P E| to `partial`
+    bool f_half = false, u_half = false, q16_in = false, q16_out = false;      // F / Uin hold float16; Uin / Uout hold 16-bit fixed point
+    bool final_cycle = false, out_bytes = false;      // the judged cycle: nothing restricted; ... leaving as planar output bytes in Uout's memory, `lm` added
+    bool composed = false;             // the prolongation source is composed from E and comp.E2 (comp.g1: level 1's geometry)
+    bool l1_half = false, timing = false;      // level 1 keeps float16 fields (mg_level1_half); the form's twin under a second symbol
+    ComposeArgs comp{};
+    float4 *bands = nullptr;           // final cycle or full cycle of four sweeps: receives the correction's cell shares, two float4 per (channel, tile row, wave, cell)
+    float *partial = nullptr;
+    LmNodes lm{};
+    AbortFlag sat{};                   // where a saturating 16-bit store reports itself
+    const RagMember *rag = nullptr;    // the launch serves a size class
+    hipStream_t s = nullptr;
+};
+bool cycle0_form(const Cycle0Launch &d, int &T, bool &PRO, int &TAG);      // the form of the launch: false if the library does not instantiate it
+int  cycle0_form_at(int i, int &T, bool &PRO, int &TAG);                   // entry i of the table of instantiated forms (if any); returns its length
+int  launch_cycle0(const Cycle0Launch &d);      // the number of partial maxima written, 0 without a prolongation, -1: form not instantiated, nothing launched
 
 // ---- size classes ("ragged groups", round 5): clones of DIFFERENT ROI sizes through one set of solver launches -----------------
 // The members of a class share the fields' strides (pitch and plane of the class's largest width / height on every level), the

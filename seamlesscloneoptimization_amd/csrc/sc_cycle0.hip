@@ -6,7 +6,7 @@
 //            max|P*E| used by the stop rule,
 //     T      red-black Gauss-Seidel sweeps (post-smoothing of this cycle and pre-smoothing of the
 //            next one back to back: T = post + pre; the first launch of a solve has T = pre; the
-//            cycle the stop rule judges has T = post and stops here: TAG bit 3),
+//            cycle the stop rule judges has T = post and stops here: C0_FINAL),
 //     then   the residual (float32 in difference form on level 0, see below) and its full-weighting
 //            restriction to the coarse RHS,
 // and writes U and the coarse RHS once.  Against the three-kernel form (smoother, residual +
@@ -14,7 +14,7 @@
 // ~12 B.  Level 0 (GEN = false): exact 5-point stencil, regular spacing, the restriction is the plain
 // 1/4-1/2-1/4 tensor stencil up to a normalisation factor at the last coarse row/column
 // (MGDim::inv_last); the RHS and, for the first launch, the incoming field may be float16 where the
-// pre-process stored them so (TAG bits 1, 2).  GEN = true: the same kernel on a coarse level, general
+// pre-process stored them so (C0_F_HALF, C0_U_HALF).  GEN = true: the same kernel on a coarse level, general
 // coefficients at the last column / row, starting from a zero correction (ZEROIN).
 //
 // Workgroups are numbered so that neighbouring tiles share an XCD and its L2 (xcd_tile, sc_wave.h).
@@ -90,7 +90,7 @@ __device__ __forceinline__ void c0_load_half_raw(const __half *__restrict__ p, i
         v[r] = *reinterpret_cast<const uint2 *>(p + (size_t)yc * P + xc);
     }
 }
-// The field BETWEEN the level-0 launches of the fast path as 16-bit fixed point (TAG bits 8, 9): code = trunc(64 u + 16384.5)
+// The field BETWEEN the level-0 launches of the fast path as 16-bit fixed point (C0_Q16_IN, C0_Q16_OUT): code = trunc(64 u + 16384.5)
 // clamped to [0, 65535], u = code / 64 - 256: the range [-256, 768) in steps of 1/64.  With a CONSERVATIVE guidance field (the
 // gradient of one image: a mask that is all 255 inside its bounding box) the solution of a clone lies in [-255, 510] -- it is
 // the source patch plus a discrete harmonic function whose boundary values are differences of 8-bit values.  A mask that mixes
@@ -162,7 +162,7 @@ __device__ __forceinline__ float c0_f_minus(const uint2 &h, float s)      // f[K
 }
 __device__ __forceinline__ float c0_comp(const float4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
-// TAG bit 4 (level 0 only): level 1 runs without post-smoothing and without its own prolongation launch.  Its finished
+// C0_COMPOSED (level 0 only): level 1 runs without post-smoothing and without its own prolongation launch.  Its finished
 // correction E1 = U1 + P21 E2 (U1: level-1 correction after pre-smoothing, E2: finished level-2 correction) is formed on
 // the fly where this kernel interpolates from it: two extra level-2 values per level-2 row and a few adds per lane.
 // Leaving out the level-1 post-smoothing changes the contraction per cycle by a few percent (oracle/mg_np.py carries
@@ -174,39 +174,30 @@ __device__ __forceinline__ float c0_comp(const float4 &v, int k) { return k == 0
 // GEN    = coarse multigrid level: general stencil coefficients at the last column / row (MGDim)
 //          and the interpolation-tail weights in the restriction of the last coarse column / row.
 // ZEROIN = the incoming correction is identically zero and is not read (first visit of a level).
-// TAG bit 0: second symbol for isolated timing; bit 1: F is float16; bit 2: Uin is float16; bit 3: last cycle (no residual /
-// restriction); bit 4: composed prolongation; bit 5: last cycle whose result leaves as bytes (Uout's memory receives planar
-// 8-bit output values: float-table node correction added, clamped, truncated) instead of as a field; bit 6: the launch
-// leaves the float-table correction's cell shares of the field it writes in `bands` (the last-cycle form does so whenever
-// `bands` is not null)
-// TAG bit 10 (round 5): the launch serves a SIZE CLASS (RagMember, sc_common.h) -- the fields' strides and the grid are the class's,
-// everything else (field size, this level's and the next one's geometry, the coarse planes' row counts) is the member's, read from
-// rag[channel / 3] (a scalar load) at entry; `lev` = the level of Uin / F in the member's hierarchy.  Tiles beyond the member's
-// extent leave (their partial maximum is 0).
+// TAG    = the form of the launch: the C0_* bits of sc_common.h.
 template <int T, int NW, int R, bool PRO, bool GEN, bool ZEROIN, int TAG = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_cycle0(Field Uin, Field Uout, Field F, Field Fc, Field E, MGGeom g,
                                                     float *__restrict__ partial, ComposeArgs comp, float4 *__restrict__ bands, LmNodes lm, AbortFlag sat,
                                                     const RagMember *__restrict__ rag, int lev)
 {
     constexpr int HY = 2 * T + 2, RH = NW * R;
-    constexpr bool RAG = (TAG & 1024) != 0;
-    constexpr bool COMP = (TAG & 16) != 0;      // E is U1; the interpolated level-2 correction is added on the fly (ComposeArgs)
+    constexpr bool RAG = (TAG & C0_RAG) != 0;
+    constexpr bool COMP = (TAG & C0_COMPOSED) != 0;      // E is U1; the interpolated level-2 correction is added on the fly (ComposeArgs)
     static_assert(!COMP || (PRO && !GEN && R % 2 == 0), "composition of two prolongations exists on level 0 only");
-    constexpr bool FINAL = (TAG & 8) != 0;      // prolongation + post-smoothing only: the cycle the stop rule is expected to accept
-    constexpr bool OUT = (TAG & 32) != 0, BANDS = ((TAG & 64) != 0 || FINAL) && !OUT;
+    constexpr bool FINAL = (TAG & C0_FINAL) != 0;      // prolongation + post-smoothing only: the cycle the stop rule is expected to accept
+    constexpr bool OUT = (TAG & C0_OUT) != 0, BANDS = ((TAG & C0_BANDS) != 0 || FINAL) && !OUT;
     static_assert(!OUT || (FINAL && !GEN), "bytes leave from the last level-0 launch only");
-    static_assert(!(TAG & 64) || !GEN, "cell shares exist on level 0 only");
-    constexpr bool HF = (TAG & 2) != 0, HU = (TAG & 4) != 0;   // HU: the first launch of a clone reads the 8-bit destination values the pre-process stored as float16
+    static_assert(!(TAG & C0_BANDS) || !GEN, "cell shares exist on level 0 only");
+    constexpr bool HF = (TAG & C0_F_HALF) != 0, HU = (TAG & C0_U_HALF) != 0;   // HU: the first launch of a clone reads the 8-bit destination values the pre-process stored as float16
     static_assert(!(HF && GEN), "float16 right-hand sides exist on level 0 only");
-    // TAG bit 7: LEVEL 1's right-hand side and correction are stored as float16 (same element pitch / plane size inside their
+    // C0_L1_HALF: LEVEL 1's right-hand side and correction are stored as float16 (same element pitch / plane size inside their
     // float buffers).  On level 0 (!GEN) that is the restriction this launch writes and the correction it interpolates from; on
     // the level-1 launch itself (GEN, ZEROIN) its own F and the correction it writes.  A correction scheme does not care: the
     // coarse problem is solved to a factor 0.05 per cycle anyway, a relative 5e-4 on its data moves the iterates by that much
     // of a correction and not the fixed point (level 0's residual is exact).  Halves the traffic of the level-1 launch and takes
     // 1 byte per unknown off every level-0 launch (oracle/mg_np.py rounds the same two fields).
-    constexpr bool L1H = (TAG & 128) != 0;
-    // TAG bits 8 / 9: the incoming / outgoing field is 16-bit fixed point (c0_load_q16)
-    constexpr bool UQI = (TAG & 256) != 0, UQO = (TAG & 512) != 0;
+    constexpr bool L1H = (TAG & C0_L1_HALF) != 0;
+    constexpr bool UQI = (TAG & C0_Q16_IN) != 0, UQO = (TAG & C0_Q16_OUT) != 0;
     static_assert(!((UQI || UQO) && (GEN || (HU && UQI) || (OUT && UQO))), "16-bit fields: level 0, between its launches");
     static_assert(!L1H || !GEN || ZEROIN, "float16 level-1 fields: the level-1 launch starts from a zero correction");
     static_assert(!(PRO && GEN), "the in-kernel prolongation relies on level 0's regular last interval");
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         }
         g = m.g[lev];
         if (PRO) E.H = m.lh[lev + 1];
-        if ((TAG & 16) != 0) { comp.g1 = m.g[lev + 1]; comp.E2.H = m.lh[lev + 2]; }
+        if ((TAG & C0_COMPOSED) != 0) { comp.g1 = m.g[lev + 1]; comp.E2.H = m.lh[lev + 2]; }
     }
     const int x = bx * (256 - 2 * C0_HX) - C0_HX + 4 * lane;
     const int y0 = by * (RH - 2 * HY) - HY + wv * R;       // even
@@ -520,7 +511,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
 #undef SC_C0_ROWS
 
     // ------------------------------------------------------------------ cell shares for the float-table correction
-    // (level 0, when the caller asks: `bands`; the last-cycle form and the forms with TAG bit 6).  The correction's restriction (sc_lowmode.hip: every 8 x 8 cell of
+    // (level 0, when the caller asks: `bands`; the last-cycle form and the forms with C0_BANDS).  The correction's restriction (sc_lowmode.hip: every 8 x 8 cell of
     // the finished field sends hat-weighted sums to its four corner nodes) needs one more pass over U; the finished field is
     // in registers right here.  A lane's four columns are half of one cell, its band of R = 8 rows (y0 is even, never a
     // multiple of 8) spans two cell rows: each lane pair writes two cell shares per band, part A for cell row y0 >> 3 and
@@ -736,181 +727,82 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
 
 constexpr int C0_NW = 8, C0_R = 8;
 
-// the level-0 forms a size class can meet (the default fast path and its continuation on float fields): first launch 134 | 512 / 134,
-// catch-up 130, full cycles 146 | 768 / 146, full cycles leaving cell shares 210 | 256 / 210, final cycle as a field 154, as bytes 186
-constexpr bool c0_rag_form(int TAG)
-{
-    return TAG == (134 | 512) || TAG == 134 || TAG == 130 || TAG == (146 | 768) || TAG == 146 || TAG == (210 | 256) || TAG == 210 ||
-           TAG == 154 || TAG == 186;
-}
-
-// rag != nullptr: the launch serves a size class (k_cycle0 TAG bit 10); -1 where that form is not instantiated
-template <int T, bool PRO, int TAG = 0, int NW = C0_NW>
-static int launch_c0(Field Uin, Field Uout, Field F, Field Fc, Field E, const MGGeom &g, float *partial, hipStream_t s,
-                     const ComposeArgs &comp = ComposeArgs(), float4 *bands = nullptr, const LmNodes &lm = LmNodes(), const AbortFlag &sat = AbortFlag(),
-                     const RagMember *rag = nullptr)
-{
-    constexpr int RH = NW * C0_R, HY = 2 * T + 2;
-    const int blocks = ((Uin.W + (256 - 2 * C0_HX) - 1) / (256 - 2 * C0_HX)) * ((Uin.H + (RH - 2 * HY) - 1) / (RH - 2 * HY)) * Uin.C;
-    if (rag) {
-        if constexpr (c0_rag_form(TAG) && NW == C0_NW)
-            hipLaunchKernelGGL((k_cycle0<T, NW, C0_R, PRO, false, false, TAG | 1024>), dim3(blocks), dim3(NW * 64), 0, s, Uin, Uout, F, Fc, E,
-                               g, partial, comp, bands, lm, sat, rag, 0);
-        else return -1;
-        return blocks;
-    }
-    hipLaunchKernelGGL((k_cycle0<T, NW, C0_R, PRO, false, false, TAG>), dim3(blocks), dim3(NW * 64), 0, s, Uin, Uout, F, Fc, E,
-                       g, partial, comp, bands, lm, sat, (const RagMember *)nullptr, 0);
-    return blocks;
-}
-
 // (Round 4, measured and not kept: sixteen-wave workgroups -- 128-row windows, one per CU -- for a single clone's two-sweep level-0
 // launches, 486 workgroups on 256 slots instead of 1080 on 512: 30.6 us against 29.0.  The launch is not paced by rounds of
 // workgroup slots; level 1's launch is, see launch_cycle_coarse.)
 
-// Level-0 launch whose prolongation source is composed on the fly: U1 = level-1 correction after its pre-smoothing (level 1
-// has no post-smoothing and no prolongation launch of its own), E2 = finished level-2 correction, g1 = level-1 geometry.
-// sweeps = post + pre (4) or, final_cycle, post (2).  Returns the number of partial maxima, -1 if not instantiated.
-// With a float16 right-hand side (f_half: the fast path) level 1's fields are float16 as well (TAG bit 7; sc_multigrid.cpp decides
-// with the same rule: mg_level1_half).  u_q16 (float16 level 1, full cycles only): Uin holds 16-bit fixed point (c0_load_q16);
-// bit 1 (value 2) set: so will Uout, clear: Uout leaves as float (the launch before the judged cycle).
-int launch_cycle0_composed(Field Uin, Field Uout, Field F, Field Fc, Field U1, const MGGeom &g, int sweeps, float *partial,
-                           hipStream_t s, bool tag, bool f_half, bool final_cycle, Field E2, const MGGeom &g1, float4 *bands, bool l1_half,
-                           int u_q16, AbortFlag sat, const RagMember *rag)
+// Every level-0 form the library instantiates, by (T, PRO, TAG): the only place that names one.  They serve (sc_multigrid.cpp) the first
+// launch of a solve (T = pre, no prolongation; on a float field: the catch-up after a rejected judged cycle), the full cycle (T = post + pre)
+// and the judged cycle (C0_FINAL, T = post) leaving a field or bytes (C0_OUT).  A composed cycle has the standard depths only: 4, final 2.
+// Level 1 is float16 only beside a float16 right-hand side: C0_FAST, the default path and the one a size class (C0_RAG) runs.  C0_TIMING
+// twins: the four launches of a fast-path solve (sc_hip_time_cycle0_form), the full cycle of the other schedules (sc_hip_time_cycle0).
+using Cycle0Kernel = void (*)(Field, Field, Field, Field, Field, MGGeom, float *, ComposeArgs, float4 *, LmNodes, AbortFlag, const RagMember *, int);
+struct Cycle0Form { int T; bool PRO; int TAG; Cycle0Kernel k; };
+#define C0_FORM(T_, PRO_, TAG_) { T_, PRO_, TAG_, k_cycle0<T_, C0_NW, C0_R, PRO_, false, false, TAG_> }
+#define C0_FORM_RAG(T_, PRO_, TAG_) C0_FORM(T_, PRO_, TAG_), C0_FORM(T_, PRO_, TAG_ | C0_RAG)
+#define C0_FORM_TWIN(T_, PRO_, TAG_) C0_FORM(T_, PRO_, TAG_), C0_FORM(T_, PRO_, TAG_ | C0_TIMING)
+constexpr int C0_FAST = C0_F_HALF | C0_L1_HALF, C0_FAST_CYCLE = C0_FAST | C0_COMPOSED, C0_Q16 = C0_Q16_IN | C0_Q16_OUT;
+static constexpr Cycle0Form c0_forms[] = {
+    // the default fast path, in the order a solve meets them: first launch (float16 field in, 16-bit or float field out; float in: the
+    // catch-up), full cycles on 16-bit fields, the cycle before the judged one (16-bit in, float out, cell shares), the judged cycle
+    C0_FORM_RAG(2, false, C0_FAST | C0_U_HALF | C0_Q16_OUT), C0_FORM(2, false, C0_FAST | C0_U_HALF | C0_Q16_OUT | C0_TIMING),
+    C0_FORM_RAG(2, false, C0_FAST | C0_U_HALF), C0_FORM_RAG(2, false, C0_FAST),
+    C0_FORM_RAG(4, true, C0_FAST_CYCLE | C0_Q16), C0_FORM(4, true, C0_FAST_CYCLE | C0_Q16 | C0_TIMING), C0_FORM(4, true, C0_FAST_CYCLE | C0_Q16 | C0_BANDS),
+    C0_FORM_RAG(4, true, C0_FAST_CYCLE | C0_Q16_IN | C0_BANDS), C0_FORM(4, true, C0_FAST_CYCLE | C0_Q16_IN | C0_BANDS | C0_TIMING),
+    C0_FORM(4, true, C0_FAST_CYCLE | C0_Q16_IN),
+    C0_FORM_RAG(2, true, C0_FAST_CYCLE | C0_FINAL | C0_OUT), C0_FORM(2, true, C0_FAST_CYCLE | C0_FINAL | C0_OUT | C0_TIMING),
+    C0_FORM_RAG(2, true, C0_FAST_CYCLE | C0_FINAL),
+    // ... and on float fields (SC_FLAG_FLOAT_FIELD, a solve that goes on after its judged cycle, the repeat after a saturated store)
+    C0_FORM_RAG(4, true, C0_FAST_CYCLE), C0_FORM(4, true, C0_FAST_CYCLE | C0_TIMING), C0_FORM_RAG(4, true, C0_FAST_CYCLE | C0_BANDS),
+    // composed cycles with float level-1 fields, on a float16 and on a float right-hand side
+    C0_FORM_TWIN(4, true, C0_COMPOSED | C0_F_HALF), C0_FORM(4, true, C0_COMPOSED | C0_F_HALF | C0_BANDS),
+    C0_FORM(2, true, C0_COMPOSED | C0_F_HALF | C0_FINAL), C0_FORM(2, true, C0_COMPOSED | C0_F_HALF | C0_FINAL | C0_OUT),
+    C0_FORM_TWIN(4, true, C0_COMPOSED), C0_FORM(4, true, C0_COMPOSED | C0_BANDS),
+    C0_FORM(2, true, C0_COMPOSED | C0_FINAL), C0_FORM(2, true, C0_COMPOSED | C0_FINAL | C0_OUT),
+    // level 1 with a prolongation launch of its own (nothing composed): every depth the schedules pre, post in {1, 2} ask for
+    C0_FORM(1, false, C0_F_HALF | C0_U_HALF), C0_FORM(2, false, C0_F_HALF | C0_U_HALF),
+    C0_FORM_TWIN(1, false, C0_F_HALF), C0_FORM_TWIN(2, false, C0_F_HALF), C0_FORM_TWIN(1, false, 0), C0_FORM_TWIN(2, false, 0),
+    C0_FORM_TWIN(2, true, C0_F_HALF), C0_FORM_TWIN(3, true, C0_F_HALF), C0_FORM_TWIN(4, true, C0_F_HALF), C0_FORM(4, true, C0_F_HALF | C0_BANDS),
+    C0_FORM_TWIN(2, true, 0), C0_FORM_TWIN(3, true, 0), C0_FORM_TWIN(4, true, 0), C0_FORM(4, true, C0_BANDS),
+    C0_FORM(1, true, C0_F_HALF | C0_FINAL), C0_FORM(2, true, C0_F_HALF | C0_FINAL), C0_FORM(2, true, C0_F_HALF | C0_FINAL | C0_OUT),
+    C0_FORM(1, true, C0_FINAL), C0_FORM(2, true, C0_FINAL), C0_FORM(2, true, C0_FINAL | C0_OUT),
+};
+#undef C0_FORM_TWIN
+#undef C0_FORM_RAG
+#undef C0_FORM
+
+static const Cycle0Form *c0_find(const Cycle0Launch &d)
 {
-    ComposeArgs ca;
-    ca.E2 = E2; ca.g1 = g1;
-    if (rag) {      // a size class: the default fast path's forms only (float16 right-hand side and level 1)
-        if (!l1_half || !f_half || tag) return -1;
-        if (final_cycle) return (sweeps == 2 && !u_q16) ? launch_c0<2, true, 154>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands, LmNodes(), AbortFlag(), rag) : -1;
-        if (sweeps != 4) return -1;
-        if (u_q16 == 3) return bands ? -1 : launch_c0<4, true, 146 | 768>(Uin, Uout, F, Fc, U1, g, partial, s, ca, nullptr, LmNodes(), sat, rag);
-        if (u_q16 == 1) return bands ? launch_c0<4, true, 210 | 256>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands, LmNodes(), AbortFlag(), rag) : -1;
-        if (u_q16) return -1;
-        return bands ? launch_c0<4, true, 210>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands, LmNodes(), AbortFlag(), rag)
-                     : launch_c0<4, true, 146>(Uin, Uout, F, Fc, U1, g, partial, s, ca, nullptr, LmNodes(), AbortFlag(), rag);
-    }
-    if (u_q16) {
-        if (!l1_half || !f_half || final_cycle || sweeps != 4) return -1;
-        if (!(u_q16 & 2)) {
-            if (tag) return -1;
-            return bands ? launch_c0<4, true, 210 | 256>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands) : launch_c0<4, true, 146 | 256>(Uin, Uout, F, Fc, U1, g, partial, s, ca);
-        }
-        if (bands && !tag) return launch_c0<4, true, 210 | 768>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands, LmNodes(), sat);
-        return tag ? launch_c0<4, true, 147 | 768>(Uin, Uout, F, Fc, U1, g, partial, s, ca, nullptr, LmNodes(), sat)
-                   : launch_c0<4, true, 146 | 768>(Uin, Uout, F, Fc, U1, g, partial, s, ca, nullptr, LmNodes(), sat);
-    }
-    if (l1_half != f_half) {           // instantiated pairs: float16 RHS with float16 level 1, float RHS with float level 1 -- and, for
-        if (l1_half) return -1;        // a level 1 that does fewer than four sweeps (mg_level1_sweeps), float16 RHS with float level 1
-        if (final_cycle) return sweeps == 2 ? launch_c0<2, true, 26>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands) : -1;
-        if (sweeps != 4) return -1;
-        if (bands && !tag) return launch_c0<4, true, 82>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands);
-        return tag ? launch_c0<4, true, 19>(Uin, Uout, F, Fc, U1, g, partial, s, ca) : launch_c0<4, true, 18>(Uin, Uout, F, Fc, U1, g, partial, s, ca);
-    }
-    if (final_cycle) {
-        if (sweeps != 2) return -1;
-        return f_half ? launch_c0<2, true, 154>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands) : launch_c0<2, true, 24>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands);
-    }
-    if (sweeps != 4) return -1;
-    if (bands && !tag) return f_half ? launch_c0<4, true, 210>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands) : launch_c0<4, true, 80>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands);
-    if (tag) return f_half ? launch_c0<4, true, 147>(Uin, Uout, F, Fc, U1, g, partial, s, ca) : launch_c0<4, true, 17>(Uin, Uout, F, Fc, U1, g, partial, s, ca);
-    return f_half ? launch_c0<4, true, 146>(Uin, Uout, F, Fc, U1, g, partial, s, ca) : launch_c0<4, true, 16>(Uin, Uout, F, Fc, U1, g, partial, s, ca);
+    // cell shares: a final cycle leaves them whenever the pointer is there (the kernel tests it), a full cycle of four sweeps in a form of its own
+    const bool shares = d.bands && d.prolong && !d.final_cycle && d.sweeps == 4;
+    const int TAG = (d.timing ? C0_TIMING : 0) | (d.f_half ? C0_F_HALF : 0) | (d.u_half ? C0_U_HALF : 0) | (d.final_cycle ? C0_FINAL : 0) |
+                    (d.composed ? C0_COMPOSED : 0) | (d.out_bytes ? C0_OUT : 0) | (shares ? C0_BANDS : 0) | (d.l1_half ? C0_L1_HALF : 0) |
+                    (d.q16_in ? C0_Q16_IN : 0) | (d.q16_out ? C0_Q16_OUT : 0) | (d.rag ? C0_RAG : 0);
+    for (const Cycle0Form &f : c0_forms)
+        if (f.TAG == TAG && f.T == d.sweeps && f.PRO == d.prolong) return &f;
+    return nullptr;
 }
 
-// sweeps = T red-black GS sweeps; prolong: add P*E first and write per-block max|P*E| to `partial`; f_half / u_half: F /
-// Uin hold float16 values (same element layout).  Returns the number of partial maxima written (0 without prolong), or -1
-// for an unsupported depth.
-int launch_cycle0(Field Uin, Field Uout, Field F, Field Fc, Field E, const MGGeom &g, int sweeps, bool prolong,
-                  float *partial, hipStream_t s, bool tag, bool f_half, bool u_half, bool final_cycle, float4 *bands, bool l1_half, bool q16_out, AbortFlag sat,
-                  const RagMember *rag)
+bool cycle0_form(const Cycle0Launch &d, int &T, bool &PRO, int &TAG)
 {
-    if (q16_out && !(l1_half && u_half)) return -1;      // the first launch of a clone on the fast path only
-    if (rag && !l1_half) return -1;                      // a size class: the fast path's forms only
-    if (l1_half) {     // level 1 keeps float16 fields (the composed schedule): the launches without a prolongation write its right-hand side
-        if (prolong || final_cycle || !f_half || tag || sweeps != 2) return -1;
-        if (q16_out) launch_c0<2, false, 134 | 512>(Uin, Uout, F, Fc, E, g, partial, s, ComposeArgs(), nullptr, LmNodes(), sat, rag);
-        else if (u_half) launch_c0<2, false, 134>(Uin, Uout, F, Fc, E, g, partial, s, ComposeArgs(), nullptr, LmNodes(), AbortFlag(), rag);
-        else launch_c0<2, false, 130>(Uin, Uout, F, Fc, E, g, partial, s, ComposeArgs(), nullptr, LmNodes(), AbortFlag(), rag);
-        return 0;
-    }
-    if (final_cycle) {   // prolongation + `sweeps` post-smoothing sweeps, nothing restricted
-        if (!prolong || u_half) return -1;
-        const ComposeArgs nc = ComposeArgs();
-        switch (sweeps) {
-        case 1: return f_half ? launch_c0<1, true, 10>(Uin, Uout, F, Fc, E, g, partial, s, nc, bands) : launch_c0<1, true, 8>(Uin, Uout, F, Fc, E, g, partial, s, nc, bands);
-        case 2: return f_half ? launch_c0<2, true, 10>(Uin, Uout, F, Fc, E, g, partial, s, nc, bands) : launch_c0<2, true, 8>(Uin, Uout, F, Fc, E, g, partial, s, nc, bands);
-        default: return -1;
-        }
-    }
-    if (u_half) {      // first launch of a clone on the float16 fields the pre-process wrote
-        if (prolong || !f_half) return -1;
-        switch (sweeps) {
-        case 1: launch_c0<1, false, 6>(Uin, Uout, F, Fc, E, g, partial, s); return 0;
-        case 2: launch_c0<2, false, 6>(Uin, Uout, F, Fc, E, g, partial, s); return 0;
-        default: return -1;
-        }
-    }
-#define SC_C0(T_, PRO_) (f_half ? (tag ? launch_c0<T_, PRO_, 3>(Uin, Uout, F, Fc, E, g, partial, s)      \
-                                       : launch_c0<T_, PRO_, 2>(Uin, Uout, F, Fc, E, g, partial, s))      \
-                                : (tag ? launch_c0<T_, PRO_, 1>(Uin, Uout, F, Fc, E, g, partial, s)      \
-                                       : launch_c0<T_, PRO_, 0>(Uin, Uout, F, Fc, E, g, partial, s)))
-    if (prolong && bands && sweeps == 4 && !tag)
-        return f_half ? launch_c0<4, true, 66>(Uin, Uout, F, Fc, E, g, partial, s, ComposeArgs(), bands) : launch_c0<4, true, 64>(Uin, Uout, F, Fc, E, g, partial, s, ComposeArgs(), bands);
-    if (prolong) {
-        switch (sweeps) {
-        case 2: return SC_C0(2, true);
-        case 3: return SC_C0(3, true);
-        case 4: return SC_C0(4, true);
-        default: return -1;
-        }
-    }
-    switch (sweeps) {
-    case 1: SC_C0(1, false); return 0;
-    case 2: SC_C0(2, false); return 0;
-    default: return -1;
-    }
-#undef SC_C0
+    const Cycle0Form *f = c0_find(d);
+    if (f) { T = f->T; PRO = f->PRO; TAG = f->TAG; }
+    return f != nullptr;
+}
+int cycle0_form_at(int i, int &T, bool &PRO, int &TAG)
+{
+    const int n = (int)(sizeof(c0_forms) / sizeof(c0_forms[0]));
+    if (i >= 0 && i < n) { T = c0_forms[i].T; PRO = c0_forms[i].PRO; TAG = c0_forms[i].TAG; }
+    return n;
 }
 
-// The last cycle of a clone with its output leaving as bytes (TAG bit 5): prolongation (composed: E = U1 with E2 / g1, else
-// E = the finished level-1 correction) + two post-smoothing sweeps; Q (a field's memory: plane c at Q.p + c Q.plane BYTES,
-// rows of Q.pitch bytes) receives the output values, lm the node correction to add (CN == nullptr: none).
-int launch_cycle0_out(Field Uin, Field Q, Field F, Field Fc, Field E, const MGGeom &g, float *partial, hipStream_t s, bool f_half,
-                      bool composed, Field E2, const MGGeom &g1, const LmNodes &lm, bool l1_half, const RagMember *rag)
+int launch_cycle0(const Cycle0Launch &d)
 {
-    ComposeArgs ca;
-    if (l1_half && !(composed && f_half)) return -1;
-    if (rag) {
-        if (!(composed && f_half && l1_half)) return -1;
-        ca.E2 = E2; ca.g1 = g1;
-        return launch_c0<2, true, 186>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm, AbortFlag(), rag);
-    }
-    if (composed && f_half && !l1_half) {
-        ca.E2 = E2; ca.g1 = g1;
-        return launch_c0<2, true, 58>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm);
-    }
-    if (composed) {
-        ca.E2 = E2; ca.g1 = g1;
-        return f_half ? launch_c0<2, true, 186>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm) : launch_c0<2, true, 56>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm);
-    }
-    return f_half ? launch_c0<2, true, 42>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm) : launch_c0<2, true, 40>(Uin, Q, F, Fc, E, g, partial, s, ca, nullptr, lm);
-}
-
-// The other three level-0 launches of a fast-path solve under a second symbol (TAG bit 0), for isolated timing (sc_hip_time_cycle0_form):
-// form 1 = the full cycle before the judged one (16-bit field in, float out, leaves the correction's cell shares: in-step symbol
-// ..., 466>), 2 = the judged cycle writing output bytes (..., 186>), 3 = the first launch of a solve (float16 initial field in,
-// 16-bit field out, no prolongation: ..., 646>).  Form 0 (..., 914> -> 915>) is launch_cycle0_composed(tag = true).
-int launch_cycle0_twin(int form, Field Uin, Field Uout, Field F, Field Fc, Field U1, const MGGeom &g, float *partial, hipStream_t s,
-                       Field E2, const MGGeom &g1, float4 *bands, const LmNodes &lm)
-{
-    ComposeArgs ca;
-    ca.E2 = E2; ca.g1 = g1;
-    switch (form) {
-    case 1: return launch_c0<4, true, 210 | 256 | 1>(Uin, Uout, F, Fc, U1, g, partial, s, ca, bands);
-    case 2: return launch_c0<2, true, 186 | 1>(Uin, Uout, F, Fc, U1, g, partial, s, ca, nullptr, lm);
-    case 3: launch_c0<2, false, 134 | 512 | 1>(Uin, Uout, F, Fc, Field(), g, partial, s); return 0;
-    default: return -1;
-    }
+    const Cycle0Form *f = c0_find(d);
+    if (!f) return -1;
+    const int blocks = cycle0_blocks(d.Uin.W, d.Uin.H, d.Uin.C, f->T);
+    hipLaunchKernelGGL(f->k, dim3(blocks), dim3(C0_NW * 64), 0, d.s, d.Uin, d.Uout, d.F, d.Fc, d.E, d.g, d.partial, d.comp, d.bands, d.lm, d.sat, d.rag, 0);
+    return f->PRO ? blocks : 0;
 }
 
 // tiling in y of a level-0 launch with `sweeps` sweeps: nby tile rows, tile row b processes field rows [b step - hy, + 64) in
@@ -929,7 +821,7 @@ int cycle0_blocks(int W, int H, int C, int sweeps)
 
 // Coarse levels (l >= 1): pre-smoothing from a zero correction + residual + restriction in one
 // launch.  Uout receives the smoothed correction, Fc the next level's RHS.
-// rag / lev: a size class (k_cycle0 TAG bit 10): level `lev` of every member's own hierarchy; instantiated for the depths the default
+// rag / lev: a size class (C0_RAG): level `lev` of every member's own hierarchy; instantiated for the depths the default
 // schedule uses -- four sweeps on float16 fields (level 1) and two on float ones (the levels below it)
 template <int T, int R, int TAG = 0, int NW = C0_NW>
 static bool launch_cn(Field Uout, Field F, Field Fc, const MGGeom &g, hipStream_t s, const RagMember *rag = nullptr, int lev = 0)
@@ -938,8 +830,8 @@ static bool launch_cn(Field Uout, Field F, Field Fc, const MGGeom &g, hipStream_
     Field none{};
     const int blocks = ((F.W + (256 - 2 * C0_HX) - 1) / (256 - 2 * C0_HX)) * ((F.H + (RH - 2 * HY) - 1) / (RH - 2 * HY)) * F.C;
     if (rag) {
-        if constexpr ((T == 4 && TAG == 128 && R != 8) || (T == 2 && TAG == 0 && NW == C0_NW))
-            hipLaunchKernelGGL((k_cycle0<T, NW, R, false, true, true, TAG | 1024>), dim3(blocks), dim3(NW * 64), 0, s, F, Uout, F, Fc, none, g,
+        if constexpr ((T == 4 && TAG == C0_L1_HALF && R != 8) || (T == 2 && TAG == 0 && NW == C0_NW))
+            hipLaunchKernelGGL((k_cycle0<T, NW, R, false, true, true, TAG | C0_RAG>), dim3(blocks), dim3(NW * 64), 0, s, F, Uout, F, Fc, none, g,
                                (float *)nullptr, ComposeArgs(), (float4 *)nullptr, LmNodes(), AbortFlag(), rag, lev);
         else return false;
         return true;
@@ -957,20 +849,9 @@ static int cn_blocks(const Field &F, int T, int R, int NW)
 }
 
 // half_io: the level's own right-hand side and the correction it writes are float16 (level 1 of the composed schedule, 4 sweeps)
+// rag: a size class makes the same choices from the class's dimensions; false where it has no such form (launch_cn)
 bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io, const RagMember *rag, int lev)
 {
-    if (rag) {          // a size class: the same choices from the class's dimensions
-        if (half_io) {
-            if (sweeps != 4) return false;
-            const int R4 = tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
-            const long b8 = cn_blocks(F, 4, 6, 8), b16 = cn_blocks(F, 4, 6, 16);
-            if (R4 == 6 && ((b8 > 512 && b16 <= 256) || (F.C > 3 && 2 * b16 < b8))) return launch_cn<4, 6, 128, 16>(Uout, F, Fc, g, s, rag, lev);
-            return R4 == 6 ? launch_cn<4, 6, 128>(Uout, F, Fc, g, s, rag, lev) : launch_cn<4, 4, 128>(Uout, F, Fc, g, s, rag, lev);
-        }
-        if (sweeps != 2) return false;
-        const int R = tb_gen_rows(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
-        return R == 8 ? launch_cn<2, 8>(Uout, F, Fc, g, s, rag, lev) : R == 6 ? launch_cn<2, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<2, 4>(Uout, F, Fc, g, s, rag, lev);
-    }
     if (half_io) {
         if (sweeps != 4) return false;
         const int R4 = tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
@@ -980,21 +861,19 @@ bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int swe
         // ... and for a GROUP of clones (tens of rounds either way) whenever the 16-wave tiling needs fewer waves in total: 76 of 96
         // rows exact instead of 28 of 48 (+0.7 % on the bench step, tools/ab_step.py).
         const long b8 = cn_blocks(F, 4, 6, 8), b16 = cn_blocks(F, 4, 6, 16);
-        if (R4 == 6 && ((b8 > 512 && b16 <= 256) || (F.C > 3 && 2 * b16 < b8))) { launch_cn<4, 6, 128, 16>(Uout, F, Fc, g, s); return true; }
-        R4 == 6 ? launch_cn<4, 6, 128>(Uout, F, Fc, g, s) : launch_cn<4, 4, 128>(Uout, F, Fc, g, s);
-        return true;
+        if (R4 == 6 && ((b8 > 512 && b16 <= 256) || (F.C > 3 && 2 * b16 < b8))) return launch_cn<4, 6, C0_L1_HALF, 16>(Uout, F, Fc, g, s, rag, lev);
+        return R4 == 6 ? launch_cn<4, 6, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev) : launch_cn<4, 4, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev);
     }
     if (sweeps < 1 || sweeps > 4) return false;
     const int R = sweeps >= 3 ? tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2) : tb_gen_rows(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
-    if (sweeps == 1) { R == 8 ? launch_cn<1, 8>(Uout, F, Fc, g, s) : R == 6 ? launch_cn<1, 6>(Uout, F, Fc, g, s) : launch_cn<1, 4>(Uout, F, Fc, g, s); }
-    else if (sweeps == 2) { R == 8 ? launch_cn<2, 8>(Uout, F, Fc, g, s) : R == 6 ? launch_cn<2, 6>(Uout, F, Fc, g, s) : launch_cn<2, 4>(Uout, F, Fc, g, s); }
-    else {
-        // deeper pre-smoothing (a level that gets no post-smoothing: 3 or 4 sweeps): 4- or 6-row bands (tb_gen_rows_deep);
-        // 8-row bands spill with the general coefficients (23 us against 20.6 us for level 1 of a 2048^2 ROI)
-        if (sweeps == 3) { R == 6 ? launch_cn<3, 6>(Uout, F, Fc, g, s) : launch_cn<3, 4>(Uout, F, Fc, g, s); }
-        else             { R == 6 ? launch_cn<4, 6>(Uout, F, Fc, g, s) : launch_cn<4, 4>(Uout, F, Fc, g, s); }
+    switch (sweeps) {
+    case 1: return R == 8 ? launch_cn<1, 8>(Uout, F, Fc, g, s, rag, lev) : R == 6 ? launch_cn<1, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<1, 4>(Uout, F, Fc, g, s, rag, lev);
+    case 2: return R == 8 ? launch_cn<2, 8>(Uout, F, Fc, g, s, rag, lev) : R == 6 ? launch_cn<2, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<2, 4>(Uout, F, Fc, g, s, rag, lev);
+    // deeper pre-smoothing (a level that gets no post-smoothing: 3 or 4 sweeps): 4- or 6-row bands (tb_gen_rows_deep);
+    // 8-row bands spill with the general coefficients (23 us against 20.6 us for level 1 of a 2048^2 ROI)
+    case 3: return R == 6 ? launch_cn<3, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<3, 4>(Uout, F, Fc, g, s, rag, lev);
+    default: return R == 6 ? launch_cn<4, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<4, 4>(Uout, F, Fc, g, s, rag, lev);
     }
-    return true;
 }
 
 } // namespace sc

@@ -367,13 +367,12 @@ int sc_hip_time_cycle0(void *p, int launches, float *ms_per_launch)
     SC_HIP(I, hipSetDevice(I->gpu));
     const bool comp = mg_composes_level1(I);          // time the form the clone itself runs
     auto once = [&]() {
-        if (comp)
-            launch_cycle0_composed(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g, 4,
-                                   (float *)I->mg_partial.p, I->stream, true, I->f_half, false, I->mg[2].U, I->mg[1].g, nullptr, I->mg_l1_half,
-                                   (I->mg_l1_half && I->mg_q16_last) ? 3 : 0);
-        else
-            launch_cycle0(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g, 4, true,
-                          (float *)I->mg_partial.p, I->stream, true, I->f_half);
+        Cycle0Launch d = level0_launch(I, comp);
+        d.sweeps = 4; d.prolong = true; d.timing = true; d.partial = (float *)I->mg_partial.p;
+        d.rag = nullptr;        // (a class's fields under the plain form: the class's dimensions)
+        d.l1_half = comp && I->mg_l1_half;
+        d.q16_in = d.q16_out = d.l1_half && I->mg_q16_last;
+        launch_cycle0(d);
         I->result_in_U1 = !I->result_in_U1;
     };
     once();
@@ -400,12 +399,19 @@ int sc_hip_time_cycle0_form(void *p, int form, int launches, float *ms_per_launc
     float4 *bands = form == 1 ? lowmode_bands_buffer(I, 4) : nullptr;
     LmNodes lm;
     if (form == 2 && I->lm.CN.p && !I->lm.singular) { lm.CN = (const float *)I->lm.CN.p; lm.ny = I->lm.ny; lm.npitch = I->lm.npitch; }
-    auto once = [&]() {
-        // values are discarded: every form reads the fields in the format it expects (whatever bits they hold) and writes the partner
-        launch_cycle0_twin(form, result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g,
-                           (float *)I->mg_partial.p, I->stream, I->mg[2].U, I->mg[1].g, bands, lm);
-    };
-    once();
+    // the other three launches of a fast-path solve as that solve says them (sc_multigrid.cpp), under their second symbols
+    Cycle0Launch d = level0_launch(I, form != 3);
+    d.timing = true; d.partial = (float *)I->mg_partial.p; d.rag = nullptr;
+    if (form == 1) {            // the full cycle before the judged one: 16-bit field in, float out, leaves the correction's cell shares
+        d.sweeps = 4; d.prolong = true; d.q16_in = true; d.bands = bands;
+    } else if (form == 2) {     // the judged cycle writing output bytes
+        d.sweeps = 2; d.prolong = true; d.final_cycle = d.out_bytes = true; d.lm = lm;
+    } else {                    // the first launch of a solve: float16 initial field in, 16-bit field out, no prolongation
+        d.sweeps = 2; d.u_half = true; d.q16_out = true;
+    }
+    // values are discarded: every form reads the fields in the format it expects (whatever bits they hold) and writes the partner
+    auto once = [&]() { return launch_cycle0(d); };
+    if (once() < 0) { I->err = "time_cycle0_form: form not instantiated"; return SC_ERR_BAD_ARG; }
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     for (int i = 0; i < launches; ++i) once();
     SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
@@ -414,6 +420,26 @@ int sc_hip_time_cycle0_form(void *p, int form, int launches, float *ms_per_launc
     lowmode_bands_written(I, nullptr);
     *ms_per_launch = ev_ms(I->ev_k0, I->ev_k1) / (float)launches;
     return SC_OK;
+}
+
+int sc_hip_cycle0_form(const int *facts, int index, int form[3])
+{
+    if (!form) return SC_ERR_BAD_ARG;
+    int T = 0, TAG = 0, rc;
+    bool PRO = false;
+    if (facts) {
+        static float4 some_bands;
+        static const RagMember some_class{};
+        Cycle0Launch d;
+        d.sweeps = facts[0]; d.prolong = facts[1]; d.f_half = facts[2]; d.u_half = facts[3]; d.q16_in = facts[4]; d.q16_out = facts[5];
+        d.final_cycle = facts[6]; d.out_bytes = facts[7]; d.composed = facts[8]; d.l1_half = facts[9]; d.timing = facts[10];
+        d.bands = facts[11] ? &some_bands : nullptr; d.rag = facts[12] ? &some_class : nullptr;
+        rc = cycle0_form(d, T, PRO, TAG) ? 0 : -1;
+    } else if ((rc = cycle0_form_at(index, T, PRO, TAG)) <= index || index < 0) {
+        return rc;
+    }
+    if (rc >= 0) { form[0] = T; form[1] = PRO; form[2] = TAG; }
+    return rc;
 }
 
 int sc_hip_time_coarse_chain(void *p, int reps, float *ms_eager, float *ms_graph, int *launches)

@@ -178,7 +178,7 @@ struct Instance {
     bool out_direct = false;               // the last solve wrote output bytes from its last cycle: result(I) is the iterate before it, not the solution
     bool f_half = false;      // F currently holds float16 values (written by the pre-process for the fused multigrid path)
     bool u_half = false;      // ... and so does the initial field U0 until the first cycle has consumed it
-    bool u_q16 = false;       // multigrid fast path, during a solve: the current field is 16-bit fixed point (sc_cycle0.hip, TAG bits 8, 9)
+    bool u_q16 = false;       // multigrid fast path, during a solve: the current field is 16-bit fixed point (sc_cycle0.hip, C0_Q16_IN / C0_Q16_OUT)
     bool mg_q16_last = false; // ... the last solve kept its field so (sc_hip_time_cycle0 times the same form)
     // 16-bit stores check their range: `sat` is the current solve's report word + generation (sc_common.h AbortFlag; p == nullptr:
     // the solve stores no 16-bit field); a solve whose word was set returns SC_RETRY_FLOAT_FIELD and solve_step repeats the
@@ -379,6 +379,7 @@ bool mg_level1_half(const Instance *I);      // sc_multigrid.cpp: level 1's righ
 int mg_time_coarse_chain(Instance *I, int reps, float *ms_eager, float *ms_graph, int *launches);   // sc_multigrid.cpp
 int mg_time_tail_phases(Instance *I, unsigned long long *out11);                                       // sc_multigrid.cpp
 bool mg_composes_level1(const Instance *I);   // sc_multigrid.cpp   // sc_multigrid.cpp: would the solve configured in I->opts read a float16 F?
+Cycle0Launch level0_launch(Instance *I, bool composed = false);   // sc_multigrid.cpp: what every level-0 launch on I's fields and hierarchy says alike
 int lowmode_correct(Instance *I, const Field &U, const Field &Out);   // sc_lowmode.hip: Out = U + float-table correction
 int lowmode_nodes(Instance *I, const Field &U, LmNodes &lm, hipStream_t on = nullptr);      // on: another stream than the instance's          // the correction of U at the node rows (what the post-process adds)
 float4 *lowmode_bands_buffer(Instance *I, int sweeps);               // where a final level-0 launch leaves the correction's cell shares (nullptr: not wanted)

@@ -8,7 +8,6 @@
 #include "sc_fd_closed.h"
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <cstring>
 #include <cstdlib>
 
@@ -635,6 +634,244 @@ bool mg_reads_half_rhs(const Instance *I)
     return !(o.flags & (SC_FLAG_FLOAT_RHS | SC_FLAG_OPENCV_GREY_MASK)) && !I->edit_call && effective_method(I) == SC_METHOD_MULTIGRID && o.tol <= 0.f && fused_level0(o) && std::min(I->F.W, I->F.H) - 2 > 3;
 }
 
+// What every level-0 launch of the fused solve says alike (sc_cycle0.hip): the solution and its partner, the right-hand sides, level 1's correction
+// (E: read by a launch that prolongs; composed: on the composed schedule, mg_composes_level1), formats, geometry, size class, stream.  A site adds the rest.
+Cycle0Launch level0_launch(Instance *I, bool composed)
+{
+    Cycle0Launch d;
+    d.Uin = result(I); d.Uout = I->result_in_U1 ? I->U0 : I->U1;
+    d.F = I->F; d.Fc = I->mg[1].F; d.E = I->mg[1].U;
+    d.g = I->mg[0].g;
+    d.f_half = I->f_half; d.l1_half = I->mg_l1_half;
+    d.rag = I->rag.dev;
+    d.s = I->stream;
+    if ((d.composed = composed)) { d.comp.E2 = I->mg[2].U; d.comp.g1 = I->mg[1].g; }
+    return d;
+}
+
+// Stop rule.  The error left after a cycle is about rho / (1 - rho) times the correction it applied, rho being the
+// contraction per cycle (measured: the prediction matches the next correction to ~10 %).  With two successive
+// corrections known the bound is applied to that prediction: error <= 0.1 x update_tol (0.025 grey levels at the
+// default 0.25, i.e. the error the plain threshold "correction <= update_tol" leaves at rho = 0.09).  A solve that
+// contracts faster stops on a larger last correction, a slower one on a smaller.  Without a previous correction
+// (max_sweeps = 1) the plain threshold decides.
+static bool stop_rule(float utol, float m, float m_prev)
+{
+    if (m_prev > 0.f) {
+        const float rho = std::min(0.5f, std::max(0.02f, m / m_prev));
+        return m * rho / (1.0f - rho) <= 0.1f * utol;
+    }
+    return m <= utol;
+}
+
+// the per-workgroup maxima of one fused solve: two cycles' worth of nb_cap each at part_base (pinned, folded by the host: host_fold; or device), `sat` behind them
+struct Level0Maxima { bool host_fold; int nb_cap; float *part_base; AbortFlag sat; };
+
+// max |correction| of the cycle just launched = max over its per-workgroup maxima (at part_now; `cyc` already counts the
+// cycle), and of the cycle before when its maxima are at hand.  A few thousand maxima are folded here on the host, out of
+// the pinned buffer the launches wrote them to (host_fold); large grids (groups of clones) reduce both lists on the device
+// first (one launch) and copy three words.  m_prev < 0: unknown.  `output` (the splice or post-process of the result, or nothing) is enqueued between the launch
+// and the read-back: it then starts without a gap while the host waits.  saturated: a 16-bit store of this solve left its range.
+template <class Output>
+static int correction_maxima(Instance *I, const Level0Maxima &x, int cyc, int nb, int nb_prev, float *part_now, Output output, float &m, float &m_prev,
+                             bool &saturated)
+{
+    m = 0.f; m_prev = -1.f;
+    int orc;
+    if (x.host_fold) {
+        const bool have_prev = nb_prev > 0;                       // the launch of the previous cycle wrote the other half
+        if ((orc = output())) return orc;
+        SC_HIP(I, hipStreamSynchronize(I->stream));               // the maxima are in the pinned buffer when the launch has ended
+        if (x.sat.p) { unsigned w; memcpy(&w, (const float *)I->h_partial.p + 2 * (size_t)x.nb_cap, sizeof(w)); saturated = w == x.sat.gen; }
+        const float *hp = (const float *)I->h_partial.p + (size_t)(cyc & 1) * x.nb_cap;            // this cycle's half
+        const float *hq = (const float *)I->h_partial.p + (size_t)((cyc + 1) & 1) * x.nb_cap;      // the previous cycle's
+        for (int i = 0; i < nb; ++i) m = hp[i] > m ? hp[i] : m;
+        if (have_prev) {
+            m_prev = 0.f;
+            for (int i = 0; i < nb_prev; ++i) m_prev = hq[i] > m_prev ? hq[i] : m_prev;
+        }
+    } else {
+        const float *part_prev = x.part_base + (size_t)((cyc + 1) & 1) * x.nb_cap;
+        launch_max_final2(part_now, nb, part_prev, nb_prev > 0 ? nb_prev : 0, I->d_maxcorr, I->stream, x.sat.p);
+        if ((orc = output())) return orc;
+        SC_HIP(I, hipMemcpyAsync(I->h_maxcorr, I->d_maxcorr, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, I->stream));
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        memcpy(&m, &I->h_maxcorr[0], sizeof(float));
+        memcpy(&m_prev, &I->h_maxcorr[1], sizeof(float));
+        saturated = x.sat.p && I->h_maxcorr[2] == x.sat.gen;
+    }
+    return SC_OK;
+}
+
+// Fused level-0 form: one launch per cycle does [prolongation +] post-smoothing of this cycle,
+// pre-smoothing of the next, residual and restriction (sc_cycle0.hip).  The first launch has no
+// correction to add.  A cycle whose result the stop rule is about to judge is launched in its
+// "final" form instead (prolongation + post-smoothing only): when the rule accepts it -- the normal
+// case for the third cycle -- nothing was computed for a cycle that never runs, and the field is
+// exactly the textbook V-cycle's; when it does not, one pre-smoothing + residual + restriction launch
+// (the form of the very first launch) catches up and the cycles continue.
+static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget)
+{
+    const sc_solver_opts &o = I->opts;
+    int rc, cyc = 0;
+    bool ok = false;
+    const bool out_wanted = I->spec_post.armed && o.tol <= 0.f && !(o.flags & SC_FLAG_KEEP_FIELD) && pre == 2 && post == 2;
+    const bool q16 = I->mg_l1_half && mg_field_q16(I, out_wanted) && budget > 1;      // (max_sweeps = 1: the first cycle is the judged one)
+    const int nb_cap = cycle0_blocks(I->F.W, I->F.H, I->F.C, 4);   // deepest form = largest halo = most workgroups
+    // The 16-bit stores check their range (sc_cycle0.hip, c0_q16_checked): one that saturates writes this solve's generation
+    // word behind the partial maxima; the output launches then write nothing, the read-back of the maxima brings the word
+    // along, and the clone is repeated on float fields (SC_RETRY_FLOAT_FIELD).  A NaN pattern: no maximum ever has these bits.
+    // Up to 16384 workgroups (single clones, small groups) the host folds the per-workgroup maxima itself -- and the launches
+    // store them (and the saturation word) STRAIGHT INTO PINNED HOST MEMORY: no read-back copy behind the judged cycle (a
+    // command of its own on the critical path, ~4 us + its gap).  Larger grids fold on the device first.
+    const bool host_fold = nb_cap <= 16384;
+    if (host_fold && (rc = ensure_pinned(I, I->h_partial, sizeof(float) * (2 * (size_t)nb_cap + 64)))) return rc;
+    float *const part_base = host_fold ? (float *)I->h_partial.p : (float *)I->mg_partial.p;
+    AbortFlag sat;
+    if (q16) {      // the device word sits behind the device list of maxima (the output launches test it there), its host copy behind the pinned one
+        sat.p = (unsigned *)((float *)I->mg_partial.p + 2 * (size_t)nb_cap);
+        sat.host = host_fold ? (unsigned *)((float *)I->h_partial.p + 2 * (size_t)nb_cap) : nullptr;
+        sat.gen = 0x7fc00000u | (++I->sat_counter & 0x3fffffu);
+    }
+    I->sat = sat;
+    const Level0Maxima maxima{ host_fold, nb_cap, part_base, sat };
+    {   // the first launch: on the float16 path the pre-process stored the initial field as float16 as well (this launch only)
+        Cycle0Launch d = level0_launch(I);
+        d.sweeps = pre; d.u_half = I->u_half; d.q16_out = q16; d.sat = sat;
+        if (launch_cycle0(d) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
+    }
+    I->result_in_U1 = !I->result_in_U1;
+    if (I->rag.dev && I->rag.ready_pending) {      // a size class: its zeroed coarse planes and tables were made on the second stream beside everything up to here
+        SC_HIP(I, hipStreamWaitEvent(I->stream, I->rag.ev_ready, 0));      // (the matrices: run_tail waits for them)
+        I->rag.ready_pending = false;
+    }
+    I->u_half = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
+    I->u_q16 = I->mg_q16_last = q16;
+    I->info.sweep_launches += 1;
+    int nb_last = 0;                   // workgroups (= partial maxima) of the previous cycle's level-0 launch
+    // Output straight from the last cycle.  When the caller armed the splice (spec_post) the cycle the stop rule is about to
+    // judge does not write its field: it adds the float-table node correction, clamps, truncates and leaves output BYTES
+    // (planar, in the memory of the partner field; a small kernel interleaves them into the destination) -- 3 bytes less
+    // written and 9 less read per pixel and channel than field + post-process.  The node correction it adds is the one of
+    // the iterate BEFORE that cycle, whose cell shares the previous launch leaves behind (lowmode_early_kind: the two
+    // differ by 0.001-0.003 grey levels, 0.05 in the worst case the stop rule admits).  If the rule rejects the cycle, the same cycle is launched again in the form
+    // that writes the field (its input is untouched) and the solve continues as without this.
+    bool saturated = false;            // set by correction_maxima
+    bool early_ready = false;          // the node correction for the judged cycle's output is on its way (early_lm; CN == nullptr: none to add)
+    bool early_cond = false;           // ... and may be used only if the judged update turns out small enough (lowmode_early_kind 3)
+    LmNodes early_lm;
+    while (cyc < budget) {
+        const bool comp1 = mg_composes_level1(I);
+        if ((rc = vcycle(I, 1, pre, post, comp1 ? (1u << 1) : 0u))) return rc;
+        // The first two corrections of a solve are never below the stop threshold unless the
+        // initial guess was already the answer, and every check costs a host round trip
+        // (~25 us), so checking starts with the third cycle.
+        const bool judged = !(cyc + 1 < 3 && cyc + 1 < budget && o.tol <= 0.f);
+        float *const part_now = part_base + (size_t)((cyc + 1) & 1) * nb_cap;    // this cycle's maxima; the previous cycle's sit in the other half
+        // the judged cycle runs in its final form; when the float-table correction will follow it leaves the correction's
+        // cell shares behind (sc_lowmode.hip), which saves the correction its own pass over the field
+        const bool next_judged = !judged && !(cyc + 2 < 3 && cyc + 2 < budget && o.tol <= 0.f);
+        // lowmode_early_kind 3: the a-priori bound does not cover this size (the float tables' low modes are off by more than 4 %);
+        // the output may still carry the earlier iterate's correction IF the judged cycle's measured update keeps the difference
+        // below the same 0.049 grey levels -- decided with the stop rule, below (early_cond)
+        const int early_kind = (out_wanted && next_judged) ? lowmode_early_kind(I, utol) : 2;
+        const int early = early_kind == 3 ? 1 : early_kind;
+        if (out_wanted && next_judged) early_cond = early_kind == 3;
+        float4 *const bands = legacy_path(o, SC_LEGACY_SEPARATE_RESTRICT) ? nullptr
+                              : judged ? lowmode_bands_buffer(I, post) : early == 1 ? lowmode_bands_buffer(I, post + pre) : nullptr;
+        if (judged && early_ready) {
+            if (I->aux_pending) {          // the node correction is ready when the launch that adds it starts
+                SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_join, 0));
+                I->aux_pending = false;
+            }
+            Cycle0Launch d = level0_launch(I, comp1);      // the judged cycle leaving as bytes
+            d.sweeps = post; d.prolong = true; d.final_cycle = d.out_bytes = true; d.partial = part_now; d.lm = early_lm;
+            const int nbo = launch_cycle0(d);
+            early_ready = false;
+            if (nbo > 0) {
+                I->info.sweep_launches += 1;
+                ++cyc;
+                SC_HIP(I, hipGetLastError());
+                const Field Q = I->result_in_U1 ? I->U0 : I->U1;
+                float m, m_prev;
+                if ((rc = correction_maxima(I, maxima, cyc, nbo, nb_last, part_now, [&]() -> int {
+                        const SolveTarget &to = I->spec_post.to;
+                        if (!to.group) launch_splice_planar(Q, to.org, to.step, I->stream, I->guard, sat);
+                        else launch_splice_planar_group(Q, to.group->data(), (int)to.group->size(), I->stream, sat);
+                        return SC_OK;
+                    }, m, m_prev, saturated))) return rc;
+                I->info.last_update = m;
+                if (saturated) { I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }      // nothing was written (AbortFlag)
+                if (stop_rule(utol, m, m_prev) && !(early_cond && I->lm.max_ratio * (double)m > 0.049)) { I->spec_post.done = true; I->out_direct = true; ok = true; break; }
+                // rejected: the same cycle again in the form that keeps the field, then on as usual
+                --cyc;
+                I->info.sweep_launches -= 1;
+            }
+        }
+        Cycle0Launch d = level0_launch(I, comp1);      // the full cycle, or the judged one as a field; the launch before the judged cycle writes float again
+        d.sweeps = judged ? post : post + pre; d.prolong = true; d.final_cycle = judged; d.partial = part_now; d.bands = bands;
+        d.q16_in = I->u_q16; d.q16_out = I->u_q16 && !next_judged; d.sat = sat;
+        const int nb = launch_cycle0(d);
+        if (nb <= 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
+        I->result_in_U1 = !I->result_in_U1;
+        if (next_judged) I->u_q16 = false;      // the launch before the judged cycle left a float field
+        lowmode_bands_written(I, bands ? result(I).p : nullptr);
+        if (!judged && early != 2) {       // the node correction the next cycle's output will carry, from this launch's field
+            early_lm = LmNodes();
+            // a group of clones: its coarse levels fill the chip, nothing to overlap (measured: -2 %); a small clone: the two
+            // cross-stream waits cost more than the 15-us chain they hide (154x100 ... 300x194 patches: +20 us; neutral at 730^2 ... 800^2,
+            // -2..3 % from 900^2 on: the threshold is 0.79 Mpix, 1 Mpix until late in round 4)
+            if (early == 1 && (I->F.C > 3 || (size_t)I->F.W * I->F.H < (size_t)3 << 18)) {
+                if ((rc = lowmode_nodes(I, result(I), early_lm))) return rc;
+            } else if (early == 1) {       // one large clone: on the second stream, beside the coarse levels of the next cycle (-15 us of 500 at 2048^2)
+                SC_HIP(I, hipEventRecord(I->ev_fork, I->stream));
+                SC_HIP(I, hipStreamWaitEvent(I->aux, I->ev_fork, 0));
+                if ((rc = lowmode_nodes(I, result(I), early_lm, I->aux))) return rc;
+                SC_HIP(I, hipEventRecord(I->ev_join, I->aux));
+                I->aux_pending = true;
+            }
+            early_ready = true;            // (early == 0: nothing to add)
+        }
+        I->info.sweep_launches += 1;
+        ++cyc;
+        SC_HIP(I, hipGetLastError());
+        const int nb_prev = nb_last;
+        nb_last = nb;
+        if (!judged) continue;
+        // the post-process goes in FIRST (see Instance::spec_post), the read-back of the maxima follows it
+        float m, m_prev;
+        if ((rc = correction_maxima(I, maxima, cyc, nb, nb_prev, part_now, [&]() -> int {
+                if (!(I->spec_post.armed && o.tol <= 0.f)) return SC_OK;
+                const int lrc = write_output(I, I->spec_post.to, sat);
+                if (lrc) return lrc;
+                I->spec_post.done = true;
+                return SC_OK;
+            }, m, m_prev, saturated))) return rc;
+        I->info.last_update = m;
+        if (saturated) { I->spec_post.done = false; I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }
+        if (o.tol > 0.f) {
+            double r[2];
+            if ((rc = eval_residual(I, r))) return rc;
+            const double rel = (r[1] > 0.0) ? std::sqrt(r[0] / r[1]) : std::sqrt(r[0]);
+            I->info.rel_residual = rel;
+            if (rel <= (double)o.tol) { ok = true; break; }
+        }
+        if (stop_rule(utol, m, m_prev)) { ok = true; break; }
+        I->spec_post.done = false;     // not converged: the field moves on, the output is written again later
+        if (cyc < budget) {            // catch up: pre-smoothing + residual + restriction for the next cycle
+            Cycle0Launch up = level0_launch(I);
+            up.sweeps = pre;
+            if (launch_cycle0(up) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
+            I->result_in_U1 = !I->result_in_U1;
+            lowmode_bands_written(I, nullptr);
+            I->info.sweep_launches += 1;
+        }
+    }
+    I->info.sweeps = cyc;
+    I->info.converged = ok ? 1 : 0;
+    return ok ? SC_OK : SC_ERR_NOT_CONVERGED;
+}
+
 int mg_solve(Instance *I)
 {
     const sc_solver_opts &o = I->opts;
@@ -661,216 +898,9 @@ int mg_solve(Instance *I)
     // writes its interior, and both buffers carry the same ring, so it stays a valid partner
     int cyc = 0;
     bool ok = false;
-    // Fused level-0 form: one launch per cycle does [prolongation +] post-smoothing of this cycle,
-    // pre-smoothing of the next, residual and restriction (sc_cycle0.hip).  The first launch has no
-    // correction to add.  A cycle whose result the stop rule is about to judge is launched in its
-    // "final" form instead (prolongation + post-smoothing only): when the rule accepts it -- the normal
-    // case for the third cycle -- nothing was computed for a cycle that never runs, and the field is
-    // exactly the textbook V-cycle's; when it does not, one pre-smoothing + residual + restriction launch
-    // (the form of the very first launch) catches up and the cycles continue.
     const bool fused0 = fused_level0(o) && I->mg.size() >= 2;
     if (I->f_half && !(fused0 && o.tol <= 0.f)) { I->err = "internal: float16 right-hand side on a path that needs float"; return SC_ERR_BAD_ARG; }
-    if (fused0) {
-        Field none{};
-        const bool out_wanted = I->spec_post.armed && o.tol <= 0.f && !(o.flags & SC_FLAG_KEEP_FIELD) && pre == 2 && post == 2;
-        const bool q16 = l1h && mg_field_q16(I, out_wanted) && budget > 1;      // (max_sweeps = 1: the first cycle is the judged one)
-        const int nb_cap = cycle0_blocks(I->F.W, I->F.H, I->F.C, 4);   // deepest form = largest halo = most workgroups
-        // The 16-bit stores check their range (sc_cycle0.hip, c0_q16_checked): one that saturates writes this solve's generation
-        // word behind the partial maxima; the output launches then write nothing, the read-back of the maxima brings the word
-        // along, and the clone is repeated on float fields (SC_RETRY_FLOAT_FIELD).  A NaN pattern: no maximum ever has these bits.
-        // Up to 16384 workgroups (single clones, small groups) the host folds the per-workgroup maxima itself -- and the launches
-        // store them (and the saturation word) STRAIGHT INTO PINNED HOST MEMORY: no read-back copy behind the judged cycle (a
-        // command of its own on the critical path, ~4 us + its gap).  Larger grids fold on the device first.
-        const bool host_fold = nb_cap <= 16384;
-        if (host_fold && (rc = ensure_pinned(I, I->h_partial, sizeof(float) * (2 * (size_t)nb_cap + 64)))) return rc;
-        float *const part_base = host_fold ? (float *)I->h_partial.p : (float *)I->mg_partial.p;
-        AbortFlag sat;
-        if (q16) {      // the device word sits behind the device list of maxima (the output launches test it there), its host copy behind the pinned one
-            sat.p = (unsigned *)((float *)I->mg_partial.p + 2 * (size_t)nb_cap);
-            sat.host = host_fold ? (unsigned *)((float *)I->h_partial.p + 2 * (size_t)nb_cap) : nullptr;
-            sat.gen = 0x7fc00000u | (++I->sat_counter & 0x3fffffu);
-        }
-        I->sat = sat;
-        // on the float16 path the pre-process stored the initial field as float16 as well (first launch only)
-        if (launch_cycle0(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, none, I->mg[0].g, pre, false, nullptr,
-                          I->stream, false, I->f_half, I->u_half, false, nullptr, l1h, q16, sat, I->rag.dev) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-        I->result_in_U1 = !I->result_in_U1;
-        if (I->rag.dev && I->rag.ready_pending) {      // a size class: its zeroed coarse planes and tables were made on the second stream beside everything up to here
-            SC_HIP(I, hipStreamWaitEvent(I->stream, I->rag.ev_ready, 0));      // (the matrices: run_tail waits for them)
-            I->rag.ready_pending = false;
-        }
-        I->u_half = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
-        I->u_q16 = I->mg_q16_last = q16;
-        I->info.sweep_launches += 1;
-        int nb_last = 0;                   // workgroups (= partial maxima) of the previous cycle's level-0 launch
-        // Output straight from the last cycle.  When the caller armed the splice (spec_post) the cycle the stop rule is about to
-        // judge does not write its field: it adds the float-table node correction, clamps, truncates and leaves output BYTES
-        // (planar, in the memory of the partner field; a small kernel interleaves them into the destination) -- 3 bytes less
-        // written and 9 less read per pixel and channel than field + post-process.  The node correction it adds is the one of
-        // the iterate BEFORE that cycle, whose cell shares the previous launch leaves behind (lowmode_early_kind: the two
-        // differ by 0.001-0.003 grey levels, 0.05 in the worst case the stop rule admits).  If the rule rejects the cycle, the same cycle is launched again in the form
-        // that writes the field (its input is untouched) and the solve continues as without this.
-        auto stop_rule = [utol](float m, float m_prev) {
-            if (m_prev > 0.f) {
-                const float rho = std::min(0.5f, std::max(0.02f, m / m_prev));
-                return m * rho / (1.0f - rho) <= 0.1f * utol;
-            }
-            return m <= utol;
-        };
-        // max |correction| of the cycle just launched = max over its per-workgroup maxima (at part_now; `cyc` already counts the
-        // cycle), and of the cycle before when its maxima are at hand.  A few thousand maxima are folded here on the host, out of
-        // the pinned buffer the launches wrote them to (host_fold); large grids (groups of clones) reduce both lists on the device
-        // first (one launch) and copy three words.  m_prev < 0: unknown.  `output` (the splice or post-process of the result, or nothing) is enqueued between the launch
-        // and the read-back: it then starts without a gap while the host waits.
-        bool saturated = false;            // set by correction_maxima: a 16-bit store of this solve left its range
-        auto correction_maxima = [&](int nb, int nb_prev, int nb_cap, float *part_now, const std::function<int()> &output, float &m, float &m_prev) -> int {
-            m = 0.f; m_prev = -1.f;
-            int orc;
-            if (host_fold) {
-                const bool have_prev = nb_prev > 0;                       // the launch of the previous cycle wrote the other half
-                if ((orc = output())) return orc;
-                SC_HIP(I, hipStreamSynchronize(I->stream));               // the maxima are in the pinned buffer when the launch has ended
-                if (sat.p) { unsigned w; memcpy(&w, (const float *)I->h_partial.p + 2 * (size_t)nb_cap, sizeof(w)); saturated = w == sat.gen; }
-                const float *hp = (const float *)I->h_partial.p + (size_t)(cyc & 1) * nb_cap;            // this cycle's half
-                const float *hq = (const float *)I->h_partial.p + (size_t)((cyc + 1) & 1) * nb_cap;      // the previous cycle's
-                for (int i = 0; i < nb; ++i) m = hp[i] > m ? hp[i] : m;
-                if (have_prev) {
-                    m_prev = 0.f;
-                    for (int i = 0; i < nb_prev; ++i) m_prev = hq[i] > m_prev ? hq[i] : m_prev;
-                }
-            } else {
-                const float *part_prev = part_base + (size_t)((cyc + 1) & 1) * nb_cap;
-                launch_max_final2(part_now, nb, part_prev, nb_prev > 0 ? nb_prev : 0, I->d_maxcorr, I->stream, sat.p);
-                if ((orc = output())) return orc;
-                SC_HIP(I, hipMemcpyAsync(I->h_maxcorr, I->d_maxcorr, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, I->stream));
-                SC_HIP(I, hipStreamSynchronize(I->stream));
-                memcpy(&m, &I->h_maxcorr[0], sizeof(float));
-                memcpy(&m_prev, &I->h_maxcorr[1], sizeof(float));
-                saturated = sat.p && I->h_maxcorr[2] == sat.gen;
-            }
-            return SC_OK;
-        };
-        bool early_ready = false;          // the node correction for the judged cycle's output is on its way (early_lm; CN == nullptr: none to add)
-        bool early_cond = false;           // ... and may be used only if the judged update turns out small enough (lowmode_early_kind 3)
-        LmNodes early_lm;
-        while (cyc < budget) {
-            const bool comp1 = mg_composes_level1(I);
-            if ((rc = vcycle(I, 1, pre, post, comp1 ? (1u << 1) : 0u))) return rc;
-            // The first two corrections of a solve are never below the stop threshold unless the
-            // initial guess was already the answer, and every check costs a host round trip
-            // (~25 us), so checking starts with the third cycle.
-            const bool judged = !(cyc + 1 < 3 && cyc + 1 < budget && o.tol <= 0.f);
-            float *const part_now = part_base + (size_t)((cyc + 1) & 1) * nb_cap;    // this cycle's maxima; the previous cycle's sit in the other half
-            // the judged cycle runs in its final form; when the float-table correction will follow it leaves the correction's
-            // cell shares behind (sc_lowmode.hip), which saves the correction its own pass over the field
-            const bool next_judged = !judged && !(cyc + 2 < 3 && cyc + 2 < budget && o.tol <= 0.f);
-            // lowmode_early_kind 3: the a-priori bound does not cover this size (the float tables' low modes are off by more than 4 %);
-            // the output may still carry the earlier iterate's correction IF the judged cycle's measured update keeps the difference
-            // below the same 0.049 grey levels -- decided with the stop rule, below (early_cond)
-            const int early_kind = (out_wanted && next_judged) ? lowmode_early_kind(I, utol) : 2;
-            const int early = early_kind == 3 ? 1 : early_kind;
-            if (out_wanted && next_judged) early_cond = early_kind == 3;
-            float4 *const bands = legacy_path(o, SC_LEGACY_SEPARATE_RESTRICT) ? nullptr
-                                  : judged ? lowmode_bands_buffer(I, post) : early == 1 ? lowmode_bands_buffer(I, post + pre) : nullptr;
-            if (judged && early_ready) {
-                if (I->aux_pending) {          // the node correction is ready when the launch that adds it starts
-                    SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_join, 0));
-                    I->aux_pending = false;
-                }
-                const int nbo = launch_cycle0_out(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g, part_now,
-                                                  I->stream, I->f_half, comp1, comp1 ? I->mg[2].U : Field(), comp1 ? I->mg[1].g : MGGeom(), early_lm, l1h, I->rag.dev);
-                early_ready = false;
-                if (nbo > 0) {
-                    I->info.sweep_launches += 1;
-                    ++cyc;
-                    SC_HIP(I, hipGetLastError());
-                    const Field Q = I->result_in_U1 ? I->U0 : I->U1;
-                    float m, m_prev;
-                    if ((rc = correction_maxima(nbo, nb_last, nb_cap, part_now, [&]() -> int {
-                            const SolveTarget &to = I->spec_post.to;
-                            if (!to.group) launch_splice_planar(Q, to.org, to.step, I->stream, I->guard, sat);
-                            else launch_splice_planar_group(Q, to.group->data(), (int)to.group->size(), I->stream, sat);
-                            return SC_OK;
-                        }, m, m_prev))) return rc;
-                    I->info.last_update = m;
-                    if (saturated) { I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }      // nothing was written (AbortFlag)
-                    if (stop_rule(m, m_prev) && !(early_cond && I->lm.max_ratio * (double)m > 0.049)) { I->spec_post.done = true; I->out_direct = true; ok = true; break; }
-                    // rejected: the same cycle again in the form that keeps the field, then on as usual
-                    --cyc;
-                    I->info.sweep_launches -= 1;
-                }
-            }
-            const int nb = comp1
-                ? launch_cycle0_composed(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U, I->mg[0].g,
-                                         judged ? post : post + pre, part_now, I->stream, false, I->f_half, judged,
-                                         I->mg[2].U, I->mg[1].g, bands, l1h, I->u_q16 ? (next_judged ? 1 : 3) : 0, sat, I->rag.dev)
-                : launch_cycle0(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, I->mg[1].U,
-                                I->mg[0].g, judged ? post : post + pre, true, part_now, I->stream,
-                                false, I->f_half, false, judged, bands);
-            if (nb <= 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-            I->result_in_U1 = !I->result_in_U1;
-            if (next_judged) I->u_q16 = false;      // the launch before the judged cycle left a float field
-            lowmode_bands_written(I, bands ? result(I).p : nullptr);
-            if (!judged && early != 2) {       // the node correction the next cycle's output will carry, from this launch's field
-                early_lm = LmNodes();
-                // a group of clones: its coarse levels fill the chip, nothing to overlap (measured: -2 %); a small clone: the two
-                // cross-stream waits cost more than the 15-us chain they hide (154x100 ... 300x194 patches: +20 us; neutral at 730^2 ... 800^2,
-                // -2..3 % from 900^2 on: the threshold is 0.79 Mpix, 1 Mpix until late in round 4)
-                if (early == 1 && (I->F.C > 3 || (size_t)I->F.W * I->F.H < (size_t)3 << 18)) {
-                    if ((rc = lowmode_nodes(I, result(I), early_lm))) return rc;
-                } else if (early == 1) {       // one large clone: on the second stream, beside the coarse levels of the next cycle (-15 us of 500 at 2048^2)
-                    SC_HIP(I, hipEventRecord(I->ev_fork, I->stream));
-                    SC_HIP(I, hipStreamWaitEvent(I->aux, I->ev_fork, 0));
-                    if ((rc = lowmode_nodes(I, result(I), early_lm, I->aux))) return rc;
-                    SC_HIP(I, hipEventRecord(I->ev_join, I->aux));
-                    I->aux_pending = true;
-                }
-                early_ready = true;            // (early == 0: nothing to add)
-            }
-            I->info.sweep_launches += 1;
-            ++cyc;
-            SC_HIP(I, hipGetLastError());
-            const int nb_prev = nb_last;
-            nb_last = nb;
-            if (!judged) continue;
-            // the post-process goes in FIRST (see Instance::spec_post), the read-back of the maxima follows it
-            float m, m_prev;
-            if ((rc = correction_maxima(nb, nb_prev, nb_cap, part_now, [&]() -> int {
-                    if (!(I->spec_post.armed && o.tol <= 0.f)) return SC_OK;
-                    const int lrc = write_output(I, I->spec_post.to, sat);
-                    if (lrc) return lrc;
-                    I->spec_post.done = true;
-                    return SC_OK;
-                }, m, m_prev))) return rc;
-            I->info.last_update = m;
-            if (saturated) { I->spec_post.done = false; I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }
-            if (o.tol > 0.f) {
-                double r[2];
-                if ((rc = eval_residual(I, r))) return rc;
-                const double rel = (r[1] > 0.0) ? std::sqrt(r[0] / r[1]) : std::sqrt(r[0]);
-                I->info.rel_residual = rel;
-                if (rel <= (double)o.tol) { ok = true; break; }
-            }
-            // Stop rule.  The error left after a cycle is about rho / (1 - rho) times the correction it applied, rho being the
-            // contraction per cycle (measured: the prediction matches the next correction to ~10 %).  With two successive
-            // corrections known the bound is applied to that prediction: error <= 0.1 x update_tol (0.025 grey levels at the
-            // default 0.25, i.e. the error the plain threshold "correction <= update_tol" leaves at rho = 0.09).  A solve that
-            // contracts faster stops on a larger last correction, a slower one on a smaller.  Without a previous correction
-            // (max_sweeps = 1) the plain threshold decides.
-            if (stop_rule(m, m_prev)) { ok = true; break; }
-            I->spec_post.done = false;     // not converged: the field moves on, the output is written again later
-            if (cyc < budget) {            // catch up: pre-smoothing + residual + restriction for the next cycle
-                if (launch_cycle0(result(I), I->result_in_U1 ? I->U0 : I->U1, I->F, I->mg[1].F, none, I->mg[0].g, pre, false,
-                                  nullptr, I->stream, false, I->f_half, false, false, nullptr, l1h, false, AbortFlag(), I->rag.dev) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-                I->result_in_U1 = !I->result_in_U1;
-                lowmode_bands_written(I, nullptr);
-                I->info.sweep_launches += 1;
-            }
-        }
-        I->info.sweeps = cyc;
-        I->info.converged = ok ? 1 : 0;
-        return ok ? SC_OK : SC_ERR_NOT_CONVERGED;
-    }
+    if (fused0) return mg_solve_fused(I, pre, post, utol, budget);      // one launch per cycle on level 0 (sc_cycle0.hip)
     while (cyc < budget) {
         if ((rc = vcycle(I, 0, pre, post))) return rc;
         ++cyc;
