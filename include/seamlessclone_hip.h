@@ -473,8 +473,8 @@ SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int str
  * SC_POISSON_GUIDANCE: lap(q) = (a - b) + (c - d) in float32, a = gx(q) (0 when q is in the last column and the right side is free),
  * b = gx(q - x) (0 when q is in column 0 and the left side is free), c and d likewise from gy with bottom and top: both formulas
  * above at the two extremes.  Forward differences of an image I, with I as boundary, give back I under every combination; gx's last
- * column and gy's last row are never read.  SC_POISSON_LAPLACIAN: lap is read at every unknown and nowhere else.  An unknown next to
- * a Dirichlet line has that line's value subtracted from its right-hand side.
+ * column and gy's last row are never read (along a non-periodic axis: see SC_POISSON_PERIODIC_* below).  SC_POISSON_LAPLACIAN: lap is
+ * read at every unknown and nowhere else.  An unknown next to a Dirichlet line has that line's value subtracted from its right-hand side.
  * boundary: required as soon as one side is a Dirichlet line; only its Dirichlet lines are read (its interior and its lines on free
  * sides never).  The system is regular: no mean is taken, no constant is free.  out: boundary's values, bit for bit, on the Dirichlet
  * lines (corners where two meet included), the solution at every unknown; out may equal boundary.
@@ -487,8 +487,29 @@ SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int str
  * sc_hip_poisson_check reports the float32 limits).  tol is validated and otherwise unused.  sc_run_info and the stage times: the
  * Neumann call's, ms_pre and ms_post ~ 0.  Batches: the same chunks; a member equals its solo run bit for bit, always.
  * The lowest eigenvalue of an axis with one Dirichlet end is ~(pi / (2n+1))^2, a quarter of the Dirichlet axis's: long thin float32
- * problems pinned at one far end lose accuracy sooner than either other kind. */
-#define SC_POISSON_GUIDANCE  1   /* gx, gy given (gx read at columns 0..cols-2, gy at rows 0..rows-2) */
+ * problems pinned at one far end lose accuracy sooner than either other kind.
+ *
+ * SC_POISSON_PERIODIC_X / _Y (or'ed into either kind): an axis that wraps -- a 360-degree panorama (x), a tileable texture (both), any
+ * field on a cylinder or torus.  A periodic axis has no Dirichlet line and no frame: all its pixels are unknowns, and the stencil's
+ * neighbour beyond either end is the pixel at the other end (at length 2 the two neighbours are the same pixel, counted twice).  The
+ * other axis keeps whatever its own two SC_POISSON_FREE_* bits say, or is periodic too: nine combinations beside the sixteen above.
+ * SC_ERR_BAD_ARG, nothing written: SC_POISSON_PERIODIC_X with SC_POISSON_FREE_LEFT or _RIGHT, SC_POISSON_PERIODIC_Y with
+ * SC_POISSON_FREE_TOP or _BOTTOM, either bit with SC_POISSON_NEUMANN or without a base kind.
+ * SC_POISSON_GUIDANCE: lap(q) = (a - b) + (c - d) in float32 as above; along a periodic x, a = gx(q) at EVERY column -- in the last one
+ * gx is the difference from the last pixel to the first -- and b = gx(q - x), which is gx of the last column when q is in column 0;
+ * likewise gy along a periodic y.  So every column of gx is read under SC_POISSON_PERIODIC_X, every row of gy under _Y.  Wrapped
+ * forward differences of an image I give back I: exactly, with I as boundary, where some side is a Dirichlet line, and up to the free
+ * constant below where none is.  SC_POISSON_LAPLACIAN: lap is read at every unknown and nowhere else.
+ * No Dirichlet line on either axis -- both periodic, or one periodic and the other free at both ends --: the unscreened system is
+ * singular and behaves as the Neumann call does: lap's DC coefficient is ignored and per channel mean(out) = mean(boundary) over all
+ * cols x rows elements (summed in double on the device); boundary may be NULL (mean zero), nothing else of it is read.  Otherwise
+ * boundary is required and read on the remaining Dirichlet lines only, which span the whole periodic extent (with a periodic x the
+ * top line is all cols pixels: there are no corners to share) and are copied to out bit for bit.
+ * Solved directly like the free sides, a periodic axis under the discrete Hartley transform H[k][j] = cos(2 pi jk/n) + sin(2 pi jk/n)
+ * (real and symmetric, H H = n I, eigenvalues 2 cos(2 pi k/n) - 2) by the same chirp convolution.  Methods, batches, aliasing, codes,
+ * sc_run_info and stage times: the free sides' (singular: ms_pre = the boundary-mean reduction).  Sizes: 2 .. 8192 pixels along a
+ * periodic axis, 4096 with SC_FLAG_FFT_FP64 (SC_ERR_BAD_SIZE outside; sc_hip_poisson_check reports the float32 limits). */
+#define SC_POISSON_GUIDANCE  1   /* gx, gy given (gx read at columns 0..cols-2, gy at rows 0..rows-2; every column / row along a periodic axis) */
 #define SC_POISSON_LAPLACIAN 2   /* lap given                                                          */
 #define SC_POISSON_NEUMANN   (1 << 8)   /* or'ed into SC_POISSON_GUIDANCE / SC_POISSON_LAPLACIAN: reflecting border, no Dirichlet frame */
 /* or'ed into either kind: that side has no Dirichlet line -- its outermost pixels are unknowns and the stencil reflects there.  All four
@@ -497,13 +518,16 @@ SC_API int sc_hip_plan_edit_groups_pool(const int *wh, int n, int group, int str
 #define SC_POISSON_FREE_RIGHT  (1 << 13)   /* column cols - 1 */
 #define SC_POISSON_FREE_TOP    (1 << 14)   /* row 0           */
 #define SC_POISSON_FREE_BOTTOM (1 << 15)   /* row rows - 1    */
+/* or'ed into either kind: that axis wraps.  (Bit 16 is not a kind.) */
+#define SC_POISSON_PERIODIC_X  (1 << 17)   /* column cols-1 is column 0's left neighbour */
+#define SC_POISSON_PERIODIC_Y  (1 << 18)   /* row rows-1 is row 0's upper neighbour      */
 #define SC_POISSON_MAX_PLANES 192
 typedef struct sc_poisson_layout {
-    int cols, rows, channels;                            /* >= 3, >= 3 (SC_POISSON_NEUMANN: >= 2, <= 8192), 1..4 */
+    int cols, rows, channels;                            /* >= 3, >= 3 (SC_POISSON_NEUMANN: >= 2, <= 8192; SC_POISSON_FREE_*, SC_POISSON_PERIODIC_*: >= 2, unknowns per axis as above), 1..4 */
     long long col_stride, row_stride, channel_stride;    /* in floats                         */
 } sc_poisson_layout;
 typedef struct sc_poisson_params {
-    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN or SC_POISSON_FREE_* bits */
+    int kind;                /* SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN, SC_POISSON_FREE_* or SC_POISSON_PERIODIC_* bits */
     float tol;               /* the multigrid stop rule's update_tol for this call, in the data's units; <= 0: 1e-3 */
 } sc_poisson_params;
 typedef struct sc_poisson_job {
@@ -555,7 +579,9 @@ SC_API int sc_hip_poisson(void *instance, const sc_poisson_params *p, const sc_p
  * and write the caller's arrays).  The instance's stored options are unchanged by the call.
  * SC_POISSON_FREE_* bits: the same per-side borders as in sc_hip_poisson, the denominators shifted by -lambda; data and lap (or the
  * guidance) are read at every unknown, boundary on its Dirichlet lines only and required if and only if some side is one; sizes, methods
- * and stage times as there. */
+ * and stage times as there.
+ * SC_POISSON_PERIODIC_* bits: the same wrapping axes as in sc_hip_poisson.  The screened system is never singular: without any
+ * Dirichlet line boundary is unused and may be NULL, and coefficient (0, 0) is divided by -lambda like any other. */
 typedef struct sc_screened_params {
     int kind;                /* as sc_poisson_params.kind, SC_POISSON_NEUMANN included */
     float lambda;            /* the data term's weight: finite, > 0 */

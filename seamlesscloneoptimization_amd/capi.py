@@ -142,6 +142,48 @@ def free_side_bits(free_sides="", neumann=False) -> int:
             raise ValueError(f'free_sides: {ch!r} is none of the letters "lrtb"')
         bits |= _FREE_SIDE_BITS[ch]
     return SC_POISSON_NEUMANN if neumann else bits
+SC_POISSON_PERIODIC_X = 1 << 17      # or'ed into either kind: the x axis wraps (column cols-1 is column 0's left neighbour)
+SC_POISSON_PERIODIC_Y = 1 << 18      # ... the y axis (row rows-1 is row 0's upper neighbour); bit 16 is not a kind
+SC_POISSON_PERIODIC_ALL = SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y
+_PERIODIC_BITS = {"x": SC_POISSON_PERIODIC_X, "y": SC_POISSON_PERIODIC_Y}
+
+
+def periodic_bits(periodic="") -> int:
+    """The SC_POISSON_PERIODIC_* bits of "x", "y", "xy" or "" (order and repeats do not matter).  Anything else raises ValueError."""
+    if not isinstance(periodic, str):
+        raise ValueError('periodic must be a string over the letters "xy"')
+    bits = 0
+    for ch in periodic:
+        if ch not in _PERIODIC_BITS:
+            raise ValueError(f'periodic: {ch!r} is neither "x" nor "y"')
+        bits |= _PERIODIC_BITS[ch]
+    return bits
+
+
+def border_bits(free_sides="", neumann=False, periodic="") -> int:
+    """free_side_bits | periodic_bits of one call's borders.  ValueError for periodic together with neumann=True or with a free side on
+    the same axis: an axis wraps or reflects, not both."""
+    per = periodic_bits(periodic)
+    if per and neumann:
+        raise ValueError("periodic excludes neumann=True: name the free sides of the other axis with free_sides")
+    free = free_side_bits(free_sides, neumann)
+    if (per & SC_POISSON_PERIODIC_X) and (free & (SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT)):
+        raise ValueError('periodic "x" excludes the free sides "l" and "r"')
+    if (per & SC_POISSON_PERIODIC_Y) and (free & (SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM)):
+        raise ValueError('periodic "y" excludes the free sides "t" and "b"')
+    return free | per
+
+
+def no_dirichlet(kind: int) -> bool:
+    """No side of a kind keeps a Dirichlet line (each axis periodic or free at both ends): the unscreened system is singular, boundary
+    gives only the mean and may be None; a screened solve does not use it."""
+    if kind & SC_POISSON_NEUMANN:
+        return True
+    x = (kind & SC_POISSON_PERIODIC_X) or (kind & SC_POISSON_FREE_LEFT and kind & SC_POISSON_FREE_RIGHT)
+    y = (kind & SC_POISSON_PERIODIC_Y) or (kind & SC_POISSON_FREE_TOP and kind & SC_POISSON_FREE_BOTTOM)
+    return bool(x and y)
+
+
 SC_POISSON_MAX_PLANES = 192
 
 
@@ -390,14 +432,16 @@ def poisson_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, layout: "Po
     return int(load().sc_hip_poisson_check(C.byref(PoissonParams(int(kind), float(tol))), C.byref(layout)))
 
 
-def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False, free_sides=""):
+def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False, free_sides="", periodic=""):
     """Checks a Poisson problem's numpy arrays before any device is touched: (kind, layout, boundary, gx, gy, lap, out) with every array
     float32 and of boundary's shape.  The layout is numpy's strides when all arrays share them; otherwise the arrays are made
     contiguous (out then stays the caller's and is written back by the caller: see Instance.poisson).  neumann: the kind carries
     SC_POISSON_NEUMANN and boundary may be None (the shape is then gx's or lap's).  free_sides: the sides without a Dirichlet line,
-    a string over "lrtb" (free_side_bits); all four are the Neumann problem, with fewer boundary is required."""
-    free = free_side_bits(free_sides, neumann)
-    neumann = neumann or free == SC_POISSON_FREE_ALL
+    a string over "lrtb" (free_side_bits); all four are the Neumann problem, with fewer boundary is required.  periodic: the axes
+    that wrap, "x", "y" or "xy" (periodic_bits; border_bits' ValueErrors); boundary may be None exactly when no side keeps a
+    Dirichlet line (no_dirichlet)."""
+    free = border_bits(free_sides, neumann, periodic)
+    neumann = no_dirichlet(free)
     if (gx is None) != (gy is None):
         raise ValueError("gx and gy go together")
     if (gx is None) == (lap is None):
@@ -405,7 +449,7 @@ def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False
     kind = SC_POISSON_LAPLACIAN if lap is not None else SC_POISSON_GUIDANCE
     kind |= free
     if boundary is None and not neumann:
-        raise ValueError("boundary may be None only for a Neumann problem (neumann=True)")
+        raise ValueError("boundary may be None only for a Neumann problem (neumann=True) or when no side keeps a Dirichlet line")
     arrays = {"boundary": boundary, "gx": gx, "gy": gy, "lap": lap, "out": out}
     first = boundary if boundary is not None else (lap if lap is not None else gx)
     for name, a in arrays.items():
@@ -433,11 +477,12 @@ def screened_check(kind: int = SC_POISSON_GUIDANCE, lam: float = 1.0, layout: "P
     return int(load().sc_hip_screened_check(C.byref(ScreenedParams(int(kind), float(lam))), C.byref(layout)))
 
 
-def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False, free_sides=""):
+def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False, free_sides="", periodic=""):
     """Checks a screened problem's numpy arrays and lambda before any device is touched: (kind, data, gx, gy, lap, boundary, out), every
     array float32 and of data's shape (poisson_arrays' rules).  A Dirichlet problem (neumann=False) needs boundary; a Neumann one
-    ignores it.  free_sides: as poisson_arrays'; with a Dirichlet line left on any side boundary is required."""
-    all_free = neumann or free_side_bits(free_sides) == SC_POISSON_FREE_ALL
+    ignores it.  free_sides, periodic: as poisson_arrays'; with a Dirichlet line left on any side boundary is required, without one it
+    is ignored."""
+    all_free = no_dirichlet(border_bits(free_sides, neumann, periodic))
     if data is None:
         raise ValueError("a screened solve needs its data term")
     if lam is None or not np.isfinite(lam) or not lam > 0:
@@ -446,7 +491,7 @@ def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, o
         boundary = None
     elif boundary is None:
         raise ValueError("a Dirichlet screened solve needs boundary (neumann=True: none)")
-    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides)
+    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides, periodic)
     if boundary is not None:
         if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
             raise TypeError("boundary must be a float32 numpy array")
@@ -604,15 +649,19 @@ class Instance:
         return int(counts[0]), int(counts[1])
 
     # ---- the Poisson solver on float32 arrays
-    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False, neumann=False, free_sides=""):
+    def poisson(self, boundary, gx=None, gy=None, lap=None, out=None, tol=0.0, allow_not_converged=False, neumann=False, free_sides="",
+                periodic=""):
         """sc_hip_poisson on numpy float32 arrays of shape H x W or H x W x C (C 1..4): solve lap(u) = div (gx, gy) (or = lap) with
         u = boundary on the frame; boundary's interior is the initial guess of the iterative methods.  out: an array of boundary's
         shape to write (may be boundary itself), default a new one.  Returns out.
         neumann: the reflecting problem on every pixel (SC_POISSON_NEUMANN); mean(out) = mean(boundary) per channel, boundary may be
         None (mean zero; shape and layout then come from gx / lap).
         free_sides: the sides without a Dirichlet line, a string over "lrtb" (SC_POISSON_FREE_*): their outermost pixels are unknowns,
-        the other sides' outermost rows and columns keep boundary's values; a direct solve, tol unused."""
-        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann, free_sides)
+        the other sides' outermost rows and columns keep boundary's values; a direct solve, tol unused.
+        periodic: the axes that wrap, "x", "y" or "xy" (SC_POISSON_PERIODIC_*): no Dirichlet line there, the pixel beyond either end is
+        the one at the other end, and gx's last column / gy's last row hold the difference across the seam.  Without a Dirichlet line
+        on the other axis either, boundary gives only the mean and may be None, as for neumann."""
+        kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann, free_sides, periodic)
         first = boundary if boundary is not None else (lap if lap is not None else gx)
         if out is None:
             out = np.empty_like(first)
@@ -650,12 +699,12 @@ class Instance:
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
     # ---- screened Poisson solves on float32 arrays
-    def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None, free_sides=""):
+    def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None, free_sides="", periodic=""):
         """sc_hip_screened on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise lam sum (u - data)^2 +
         sum |grad u - (gx, gy)|^2 (or with the divergence given as lap), with u = boundary on the frame, or, neumann, reflected at the
         border (boundary then unused).  out: an array of data's shape to write (may be data or boundary), default a new one.
-        free_sides: as poisson's (boundary is read on the remaining Dirichlet lines).  Returns out."""
-        kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann, free_sides)
+        free_sides, periodic: as poisson's (boundary is read on the remaining Dirichlet lines).  Returns out."""
+        kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann, free_sides, periodic)
         if out is None:
             out = np.empty_like(data)
         given = [a for a in (data, gx, gy, lap, boundary, out) if a is not None]

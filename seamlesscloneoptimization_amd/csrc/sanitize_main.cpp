@@ -272,6 +272,34 @@ int main()
             { (1 << 9) | SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
             { (1 << 11) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
             { (1 << 16) | SC_POISSON_GUIDANCE, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            // SC_POISSON_PERIODIC_*: 2 .. 8192 pixels along a periodic axis, the other axis under its own rules; no free side on a periodic
+            // axis, no SC_POISSON_NEUMANN, a base kind required
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 640, 480, 3, 3, 3 * 640, 1, SC_OK },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_PERIODIC_Y, 0.f, 640, 480, 3, 1, 640, 640 * 480, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_LEFT, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 2, 3, 1, 1, 2, 6, SC_OK },                               // 2 x 1 unknowns
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 2, 2, 1, 1, 2, 4, SC_ERR_BAD_SIZE },                     // no unknown between top and bottom
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 1, 40, 1, 1, 1, 40, SC_ERR_BAD_SIZE },                   // length 1
+            { SC_POISSON_LAPLACIAN | SC_POISSON_PERIODIC_Y, 0.f, 40, 1, 1, 1, 40, 40, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y, 0.f, 1, 1, 1, 1, 1, 1, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 8192, 8, 1, 1, 8192, 8 * 8192, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 8193, 8, 1, 1, 8193, 8 * 8193, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y, 0.f, 8, 8192, 1, 1, 8, 8 * 8192, SC_OK },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y, 0.f, 8, 8193, 1, 1, 8, 8 * 8193, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 8, 8194, 1, 1, 8, 8 * 8194, SC_OK },                     // the other axis between two Dirichlet lines
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 8, 8195, 1, 1, 8, 8 * 8195, SC_ERR_BAD_SIZE },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_FREE_LEFT, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_FREE_RIGHT, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_TOP, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_BOTTOM, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X | SC_POISSON_NEUMANN, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_LAPLACIAN | SC_POISSON_PERIODIC_Y | SC_POISSON_NEUMANN, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { SC_POISSON_PERIODIC_X, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },                             // no base kind
+            { SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y | 3, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 16) | SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
+            { (1 << 19) | SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_Y, 0.f, 640, 480, 1, 1, 640, 640 * 480, SC_ERR_BAD_ARG },
         };
         for (const Case &k : cases) {
             sc_poisson_params p{ k.kind, k.tol };
@@ -312,6 +340,20 @@ int main()
             { G | SC_POISSON_FREE_BOTTOM, 1.f, 2, 8, 1, 1, 2, 16, SC_ERR_BAD_SIZE },
             { G | SC_POISSON_FREE_BOTTOM, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
             { (1 << 9) | G | SC_POISSON_FREE_BOTTOM, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            // SC_POISSON_PERIODIC_*
+            { G | SC_POISSON_PERIODIC_X, 1.f, 640, 480, 3, 3, 1920, 1, SC_OK },
+            { Lp | SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y, 1e-3f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { G | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT, 1.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { G | SC_POISSON_PERIODIC_Y, 1.f, 3, 8192, 1, 1, 3, 3 * 8192, SC_OK },
+            { G | SC_POISSON_PERIODIC_Y, 1.f, 3, 8193, 1, 1, 3, 3 * 8193, SC_ERR_BAD_SIZE },
+            { G | SC_POISSON_PERIODIC_Y, 1.f, 3, 1, 1, 1, 3, 3, SC_ERR_BAD_SIZE },
+            { G | SC_POISSON_PERIODIC_X, 1.f, 1, 8, 1, 1, 1, 8, SC_ERR_BAD_SIZE },
+            { G | SC_POISSON_PERIODIC_X | SC_POISSON_FREE_RIGHT, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_TOP, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G | SC_POISSON_PERIODIC_X | N, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { SC_POISSON_PERIODIC_X, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { G | SC_POISSON_PERIODIC_X, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { (1 << 16) | G | SC_POISSON_PERIODIC_X, 1.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
         };
         for (const Case &k : cases) {
             sc_screened_params p{ k.kind, k.lambda };

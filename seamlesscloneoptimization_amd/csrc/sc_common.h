@@ -86,10 +86,15 @@ struct PoissonJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; };
 // A call with free (reflecting) sides on some but not all of the four borders (SC_POISSON_FREE_*): per axis its kind -- 0: Dirichlet
 // lines at both ends, 1: both ends free, 2: a Dirichlet line at the low end (column or row 0) and a free high end, 3: the reverse --
 // and its number of unknowns, pixels less the axis's Dirichlet lines.  (Kind 0 on both axes is the Dirichlet call, kind 1 on both the
-// Neumann call: neither comes here.)
+// Neumann call: neither comes here.)  Kind 4 (SC_POISSON_PERIODIC_X / _Y): the axis wraps -- no Dirichlet line, every pixel an unknown, the
+// neighbour beyond either end is the pixel at the other end.
 struct MixedGeo { int ax, ay, nx, ny; };
+constexpr int MIXED_PERIODIC = 4;
 __host__ __device__ __forceinline__ bool mixed_low_d(int k) { return k == 0 || k == 2; }
 __host__ __device__ __forceinline__ bool mixed_high_d(int k) { return k == 0 || k == 3; }
+// the axis's operator has the eigenvalue 0 (its constant vector): no Dirichlet line at either end.  Both axes: the unscreened system is
+// singular (the Neumann call, and any pairing of a periodic axis with a periodic or free-free one)
+__host__ __device__ __forceinline__ bool mixed_zero_eig(int k) { return k == 1 || k == MIXED_PERIODIC; }
 // a screened solve's right-hand side (sc_screened_api.cpp): rhs - lam d in float32, one multiply, then one subtract -- never one fused
 // multiply-add, whatever the translation unit's contraction setting (the product is opaque to the optimiser)
 __device__ __forceinline__ float screened_rhs(float rhs, float lam, float d)

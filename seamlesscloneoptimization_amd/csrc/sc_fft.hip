@@ -357,8 +357,10 @@ __global__ __launch_bounds__(256) void k_fft_transpose(const T *__restrict__ in,
     }
 }
 
-// ---- the direct solve on caller arrays: free sides on some or all of the four borders (SC_POISSON_NEUMANN, SC_POISSON_FREE_*) ------
-// One kernel (k_mix) and one driver (direct_jobs_solve) for all 15 combinations with a free side; each axis has its own transform.
+// ---- the direct solve on caller arrays: free sides on some or all of the four borders (SC_POISSON_NEUMANN, SC_POISSON_FREE_*), periodic
+// axes (SC_POISSON_PERIODIC_*) ------
+// One kernel (k_mix) and one driver (direct_jobs_solve) for all 15 combinations with a free side and the 9 with a periodic axis; each axis
+// has its own transform.
 // An axis with both ends free (both axes: the Neumann problem) -- DCT-II / DCT-III by the same chirp convolution:
 // all its pixels are unknowns and the 5-point stencil reflects at its ends: the DCT-II diagonalises it.  With N = 2n, c_m =
 // exp(i pi m^2 / N) and h_k = exp(i pi k / 2n) c_k (FftDim kind 1: the chirp kernel conj(c_m) of period 2n, M >= 2n - 1 as before),
@@ -369,17 +371,19 @@ __global__ __launch_bounds__(256) void k_fft_transpose(const T *__restrict__ in,
 // PoissonJobs::MAX jobs.
 
 // the reflecting system's right-hand side at pixel (x, y) of channel c: given, or (a - b) + (c - d) of the guidance field in float32
+// (px / py: that axis wraps -- the difference stored in the last column / row runs from the last pixel to the first, and column / row 0
+// takes it as its backward difference)
 template <bool LAP>
-__device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDev &j, int c, int x, int y)
+__device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDev &j, int c, int x, int y, bool px, bool py)
 {
     const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
     if (LAP) return j.lap[o];
-    const float a = x < g.W - 1 ? j.gx[o] : 0.f, b = x > 0 ? j.gx[o - g.cs] : 0.f;
-    const float cc = y < g.H - 1 ? j.gy[o] : 0.f, d = y > 0 ? j.gy[o - g.rs] : 0.f;
+    const float a = (x < g.W - 1 || px) ? j.gx[o] : 0.f, b = x > 0 ? j.gx[o - g.cs] : px ? j.gx[o + (long long)(g.W - 1) * g.cs] : 0.f;
+    const float cc = (y < g.H - 1 || py) ? j.gy[o] : 0.f, d = y > 0 ? j.gy[o - g.rs] : py ? j.gy[o + (long long)(g.H - 1) * g.rs] : 0.f;
     return (a - b) + (cc - d);
 }
 
-// The four axis kinds.  Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
+// The five axis kinds.  Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
 // above; kind 2, a Dirichlet line at the low end and a free high end, the sine transform of odd half-frequencies
 //     S[k][j] = sin(pi (2k+1) (j+1) / (2n+1)),   k, j < n,    S S^T = (2n+1)/4 I,    eigenvalue 2 cos(pi (2k+1) / (2n+1)) - 2;
 // kind 3 is kind 2 with the spatial index reversed.  With N = 2n+1, c_m = exp(i pi m^2 / N), a_k = exp(i pi (k^2 + 2k) / N) and
@@ -388,38 +392,46 @@ __device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDe
 // -- S is not symmetric: forward sums over j, inverse over k, as DCT-II and DCT-III.  So every kind is: multiply by one table, convolve
 // (chirp_convolve unchanged), multiply by another, keep the imaginary part (the real one for kind 1); the inverse swaps the tables.
 // Data sit at S[off .. off + n), off = 1 for kind 0 (its indices run from 1) and 0 otherwise.
+// Kind 4 (MIXED_PERIODIC), an axis that wraps: the discrete Hartley transform H[k][j] = cos(2 pi jk / n) + sin(2 pi jk / n), real and
+// symmetric, H H = n I, eigenvalue 2 cos(2 pi k / n) - 2 (the cosine and the sine of one frequency share it).  With N = n, c_m =
+// exp(i pi m^2 / n) (2jk = j^2 + k^2 - (k - j)^2),
+//     X_k = Re[ (1 - i) c_k sum_j (x_j c_j) conj(c_{k-j}) ]
+// -- one real per coefficient where a complex DFT would double the planes between the launches.  Tables c_j and (1 - i) c_k (FftDim kind
+// 4), the real part kept; the inverse is the same transform (the constant 1 - i moves in front of the convolution), 1/n left to the caller.
+// Only |k - j| <= n - 1 enters, so M >= 2n - 1 as for every other kind.
 
 // what the forward transform multiplies sample j by in front of the convolution (and the inverse's result j behind it) ...
 template <typename T>
 __device__ __forceinline__ cx2<T> mix_tab_j(const FftPlan<T> &P, int kind, int j)
 {
-    return P.chirp[kind == 0 ? j + 1 : kind == 1 ? j : P.n + 1 + j];
+    return P.chirp[kind == 0 ? j + 1 : (kind == 1 || kind == MIXED_PERIODIC) ? j : P.n + 1 + j];
 }
 // ... and coefficient k behind it (the inverse: in front)
 template <typename T>
 __device__ __forceinline__ cx2<T> mix_tab_k(const FftPlan<T> &P, int kind, int k)
 {
-    return P.chirp[kind == 0 ? k + 1 : kind == 1 ? P.n + 1 + k : k];
+    return P.chirp[kind == 0 ? k + 1 : (kind == 1 || kind == MIXED_PERIODIC) ? P.n + 1 + k : k];
 }
 template <typename T>
-__device__ __forceinline__ T mix_part(int kind, cx2<T> t, cx2<T> y)      // Re(t y) for kind 1, Im(t y) otherwise
+__device__ __forceinline__ T mix_part(int kind, cx2<T> t, cx2<T> y)      // Re(t y) for kinds 1 and 4, Im(t y) otherwise
 {
-    return kind == 1 ? t.x * y.x - t.y * y.y : t.x * y.y + t.y * y.x;
+    return (kind == 1 || kind == MIXED_PERIODIC) ? t.x * y.x - t.y * y.y : t.x * y.y + t.y * y.x;
 }
 // eigenvalue k (0-based) of an axis of n unknowns, in double
 __device__ __forceinline__ double mix_eig(int kind, int k, int n)
 {
-    const double a = kind == 0 ? (double)(k + 1) / (double)(n + 1) : kind == 1 ? (double)k / (double)n : (double)(2 * k + 1) / (double)(2 * n + 1);
+    const double a = kind == 0 ? (double)(k + 1) / (double)(n + 1) : kind == 1 ? (double)k / (double)n
+                   : kind == MIXED_PERIODIC ? (double)(2 * k) / (double)n : (double)(2 * k + 1) / (double)(2 * n + 1);
     return 2.0 * cospi(a) - 2.0;
 }
 
 // the system's right-hand side at the unknown at pixel (x, y): the divergence (dct_rhs: an unknown in column 0 or the last column exists
-// only where that side is free), the data term of a screened solve, then the neighbouring Dirichlet lines' values folded in as fft_g does
+// only where that side is free or the axis wraps), the data term of a screened solve, then the neighbouring Dirichlet lines' values folded in as fft_g does
 template <bool LAP, bool SCR>
 __device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg, const PoissonJobDev &j, int c, int x, int y, float lam)
 {
     const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
-    float v = dct_rhs<LAP>(g, j, c, x, y);
+    float v = dct_rhs<LAP>(g, j, c, x, y, mg.ax == MIXED_PERIODIC, mg.ay == MIXED_PERIODIC);
     if constexpr (SCR) v = screened_rhs(v, lam, j.d[o]);
     if (x == 1 && mixed_low_d(mg.ax)) v -= j.b[o - g.cs];
     if (y == 1 && mixed_low_d(mg.ay)) v -= j.b[o - g.rs];
@@ -439,6 +451,8 @@ __device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg
 // NEU: all four sides free -- both kinds are 1 at compile time, whatever mg says.  The unscreened system is then singular: MODE 1
 // zeroes coefficient (0, 0) (screened: divided by -lam as any other), MODE 2 adds the plane's mean of boundary (parts: nparts sums
 // per plane, nullptr: 0).
+// Not NEU, but neither axis with a Dirichlet line at run time (mixed_zero_eig of both: a periodic axis beside a periodic or free-free one):
+// the same singular system -- the same zeroed coefficient and the same added mean, decided per launch from mg.
 template <int MODE, typename T, bool LAP, bool SCR, bool NEU>
 __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g, MixedGeo mg, PoissonJobs jobs, const T *__restrict__ in,
                                                      T *__restrict__ out, int rows, double scale, int tstore, const double *__restrict__ parts,
@@ -457,7 +471,8 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
     const int member = p / g.C, c = p - member * g.C;
     const PoissonJobDev &J = jobs.j[(MODE == 1) ? 0 : member];
     const int x0 = mixed_low_d(mg.ax) ? 1 : 0, y0 = mixed_low_d(mg.ay) ? 1 : 0;
-    if (MODE == 2 && NEU && tid < 64) {       // the first wave: the parts in a fixed order (the first barrier below publishes the sum)
+    const bool sing = NEU || (mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay));      // no Dirichlet line on any side
+    if (MODE == 2 && sing && tid < 64) {       // the first wave: the parts in a fixed order (the first barrier below publishes the sum)
         double m = 0.0;
         if (parts) for (int i = tid; i < nparts; i += 64) m += parts[(size_t)p * nparts + i];
         m = wave_sum(m);
@@ -487,7 +502,7 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
     __syncthreads();
     chirp_convolve<T>(S, P, tid);
     if (MODE == 1) {
-        // coefficient k of column r: divide by the two axes' eigenvalues (in double; zero only at (0, 0) with all four sides free) and feed
+        // coefficient k of column r: divide by the two axes' eigenvalues (in double; zero only at (0, 0) of a singular system) and feed
         // the quotient into the inverse transform, the column resident in LDS (element off + k is read and rewritten by one thread)
         const double ex = mix_eig(mg.ax, r, rows);
         for (int k = tid; k < n; k += FFT_THREADS) {
@@ -495,7 +510,7 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
             const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
             const double eig = ex + mix_eig(kind, k, n);
             const T den = (T)(SCR ? eig - (double)lam : eig);
-            T q = (!SCR && NEU && r == 0 && k == 0) ? (T)0 : X / den;
+            T q = (!SCR && sing && r == 0 && k == 0) ? (T)0 : X / den;
             if (kind == 1 && k == 0) q *= (T)0.5;
             S[fft_pad(off + k)] = mk<T>(q * t.x, q * t.y);
         }
@@ -504,14 +519,14 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
         __syncthreads();
         chirp_convolve<T>(S, P, tid);
     }
-    const T mean = (MODE == 2 && NEU) ? (T)s_mean : (T)0;
+    const T mean = (MODE == 2 && sing) ? (T)s_mean : (T)0;
     for (int k = tid; k < n; k += FFT_THREADS) {
         const cx2<T> t = (MODE == 0) ? mix_tab_k<T>(P, kind, k) : mix_tab_j<T>(P, kind, k);
         const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
         const int at = (MODE != 0 && flip) ? n - 1 - k : k;          // results of an inverse transform are spatial
         if (MODE == 2) {
             // (two forms: X scale + 0 is not X scale when that is -0)
-            const float v = NEU ? (float)(X * (T)scale + mean) : (float)(X * (T)scale);
+            const float v = sing ? (float)(X * (T)scale + mean) : (float)(X * (T)scale);
             J.out[(long long)(x0 + at) * g.cs + (long long)(y0 + r) * g.rs + (long long)c * g.chs] = v;
         } else if (tstore) out[((size_t)p * n + at) * rows + r] = X;
         else out[((size_t)p * rows + r) * n + at] = X;
@@ -612,7 +627,8 @@ struct FftBuildPair { FftBuild<TC, T> b[2]; };
 // transform with that period, and behind chirp[0 .. n] the half-sample twiddle times the chirp, h_k = exp(i pi k / 2n) c_k =
 // exp(i pi k (k + 1) / 2n), k < n (phase reduced in integers like the chirp's).  KIND 2: the sine transform of a Dirichlet end paired with
 // a free end (k_mix; odd period N = 2n + 1): the chirp kernel of that period, and in the two tables' places a_k = exp(i pi (k^2 + 2k) / N)
-// and b_j = exp(i pi (j^2 + j + 1) / N), k, j < n, reduced modulo 2N likewise.
+// and b_j = exp(i pi (j^2 + j + 1) / N), k, j < n, reduced modulo 2N likewise.  KIND 4: the Hartley transform of a periodic axis (k_mix;
+// period N = n): the chirp kernel of that period, and behind chirp[0 .. n] the table (1 - i) c_k, k < n.
 template <typename TC, typename T, int KIND>
 __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> bp)
 {
@@ -621,8 +637,8 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
     const FftBuild<TC, T> &B = bp.b[blockIdx.x];
     const FftPlan<TC> &P = B.P;
     const int tid = threadIdx.x, n = P.n, M = P.M;
-    const long long N2 = KIND == 2 ? 4LL * n + 2 : KIND ? 4LL * n : 4LL * (n + 1);
-    const int N = KIND == 2 ? 2 * n + 1 : KIND ? 2 * n : 2 * (n + 1);
+    const long long N2 = KIND == 4 ? 2LL * n : KIND == 2 ? 4LL * n + 2 : KIND ? 4LL * n : 4LL * (n + 1);
+    const int N = KIND == 4 ? n : KIND == 2 ? 2 * n + 1 : KIND ? 2 * n : 2 * (n + 1);
     for (int i = tid; i < max(M, n + 1); i += FFT_THREADS) {          // chirp and twiddles
         if (i <= n) {
             const long long q = (KIND == 2 ? (long long)i * (i + 2) : (long long)i * i) % N2;
@@ -631,10 +647,10 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
             B.chirp[i] = mk<T>((T)cs, (T)sn);
         }
         if (KIND && i < n) {
-            const long long q = (KIND == 2 ? (long long)i * (i + 1) + 1 : (long long)i * (i + 1)) % N2;
+            const long long q = (KIND == 4 ? (long long)i * i : KIND == 2 ? (long long)i * (i + 1) + 1 : (long long)i * (i + 1)) % N2;
             double sn, cs;
             sincospi((double)q / (double)N, &sn, &cs);
-            B.chirp[n + 1 + i] = mk<T>((T)cs, (T)sn);
+            B.chirp[n + 1 + i] = KIND == 4 ? mk<T>((T)(cs + sn), (T)(sn - cs)) : mk<T>((T)cs, (T)sn);      // (1 - i)(cs + i sn)
         }
         if (i < M) {
             double sn, cs;
@@ -674,12 +690,13 @@ __global__ __launch_bounds__(FFT_THREADS) void k_fft_build(FftBuildPair<TC, T> b
 template <typename TC, typename T>
 static void fft_launch_build(int kind, int cnt, size_t lds, hipStream_t s, const FftBuildPair<TC, T> &bp)
 {
-    if (kind == 2) hipLaunchKernelGGL((k_fft_build<TC, T, 2>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+    if (kind == 4) hipLaunchKernelGGL((k_fft_build<TC, T, 4>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
+    else if (kind == 2) hipLaunchKernelGGL((k_fft_build<TC, T, 2>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
     else if (kind) hipLaunchKernelGGL((k_fft_build<TC, T, 1>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
     else hipLaunchKernelGGL((k_fft_build<TC, T, 0>), dim3(cnt), dim3(FFT_THREADS), lds, s, bp);
 }
 
-// complex elements in front of bhat: the chirp, and for the DCT kind the half-sample twiddles behind it (kind 2: its two tables)
+// complex elements in front of bhat: the chirp, and for the DCT kind the half-sample twiddles behind it (kinds 2 and 4: their two tables)
 static size_t fft_chirp_len(const FftDim &D) { return (size_t)(D.kind ? 2 : 1) * (D.n + 1); }
 
 template <typename T>
@@ -869,10 +886,12 @@ static hipError_t fft_opt_in_lds(Instance *I)
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<double, T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     if (e == hipSuccess && sizeof(T) == sizeof(float)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_build<float, float, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, bbytes);
     }
     // the transform kernels of the solves with free sides (direct_jobs_solve)
     if (e == hipSuccess) e = mix_opt_in_lds<T>(bytes);
@@ -955,13 +974,14 @@ int fft_solve(Instance *I, bool fp64)
 // Neumann problem): rows (right-hand side from the jobs' arrays, forward x transform), columns (forward y transform, divide, inverse),
 // rows (inverse x transform, scale, into the jobs' out with its Dirichlet lines) -- the launches that read or write the jobs' arrays go
 // per PoissonJobs::MAX members (the table goes by value), the column launch over all planes at once.
-// All four sides free, unscreened: the system is singular -- a boundary-mean reduction first (mark 5 behind it; otherwise at the start),
-// the mean added by the last launch.  lam > 0: the screened solve -- the data term read by the first row launch, the denominators
+// No Dirichlet line on any side (all four free, or a periodic axis beside a periodic or free-free one), unscreened: the system is singular
+// -- a boundary-mean reduction first (mark 5 behind it; otherwise at the start), the mean added by the last launch.  lam > 0: the screened solve -- the data term read by the first row launch, the denominators
 // shifted by -lam.
 template <typename T>
 static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam)
 {
-    const bool scr = lam > 0.f, all_free = mg.ax == 1 && mg.ay == 1;
+    const bool scr = lam > 0.f, all_free = mg.ax == 1 && mg.ay == 1, singular = mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay);
+    auto table_kind = [](int k) { return k == 3 ? 2 : k; };      // FftDim::kind: kind 3 is kind 2 with the spatial index reversed
     const int nx = mg.nx, ny = mg.ny, planes = g.C * m;
     SC_HIP(I, fft_opt_in_lds<T>(I));
     FftState &S = I->fft;
@@ -969,14 +989,14 @@ static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo 
     FftDim *dw = nullptr, *dh = nullptr;
     S.forked = false;
     S.nreq = 0;
-    if ((rc = fft_build_dim<T>(I, dw, nx, nullptr, std::min(mg.ax, 2)))) return rc;
-    if ((rc = fft_build_dim<T>(I, dh, ny, dw, std::min(mg.ay, 2)))) { for (int k = 0; k < S.nreq; ++k) S.req[k]->n = 0; S.nreq = 0; return rc; }
+    if ((rc = fft_build_dim<T>(I, dw, nx, nullptr, table_kind(mg.ax)))) return rc;
+    if ((rc = fft_build_dim<T>(I, dh, ny, dw, table_kind(mg.ay)))) { for (int k = 0; k < S.nreq; ++k) S.req[k]->n = 0; S.nreq = 0; return rc; }
     if ((rc = fft_flush_builds<T>(I))) return rc;
     const size_t plane = (size_t)nx * ny;
     if ((rc = ensure(I, S.A, sizeof(T) * plane * planes, false))) return rc;
     if ((rc = ensure(I, S.B, sizeof(T) * plane * planes, false))) return rc;
     bool any_b = false;
-    for (int k = 0; k < m && all_free && !scr; ++k) any_b = any_b || jobs[k].b;
+    for (int k = 0; k < m && singular && !scr; ++k) any_b = any_b || jobs[k].b;
     const int np = poisson_mean_parts(g.H);
     const double *parts = nullptr;
     if (any_b) {
@@ -994,7 +1014,7 @@ static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo 
     const size_t ldsw = sizeof(cx2<T>) * (size_t)(fft_pad(Pw.M) + 1), ldsh = sizeof(cx2<T>) * (size_t)(fft_pad(Ph.M) + 1);
     T *A = (T *)S.A.p, *B = (T *)S.B.p;
     // (the two expressions round differently in double: each path keeps the one its outputs were pinned with)
-    auto axis_scale = [](int kind, int n) { return kind == 0 ? 2.0 / (n + 1.0) : kind == 1 ? 2.0 / n : 4.0 / (2.0 * n + 1.0); };
+    auto axis_scale = [](int kind, int n) { return kind == 0 ? 2.0 / (n + 1.0) : kind == 1 ? 2.0 / n : kind == MIXED_PERIODIC ? 1.0 / n : 4.0 / (2.0 * n + 1.0); };
     const double scale = all_free ? 4.0 / ((double)nx * (double)ny) : axis_scale(mg.ax, nx) * axis_scale(mg.ay, ny);
     const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as fft_solve_t: small planes are stored transposed, no transpose launches
     // per launch of up to PoissonJobs::MAX members: fn(table, first plane, planes)
@@ -1045,6 +1065,8 @@ int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool
     if (!fft_supported(mg.nx, mg.ny, fp64)) {
         if (mg.ax == 1 && mg.ay == 1)
             I->err = fp64 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: more than 4096 pixels per side" : "SC_POISSON_NEUMANN: more than 8192 pixels per side";
+        else if (mg.ax == MIXED_PERIODIC || mg.ay == MIXED_PERIODIC)
+            I->err = fp64 ? "periodic axes with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "periodic axes: more than 8192 unknowns per axis";
         else I->err = fp64 ? "free sides with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "free sides: more than 8192 unknowns per axis";
         return SC_ERR_BAD_SIZE;
     }

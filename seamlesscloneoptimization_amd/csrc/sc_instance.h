@@ -59,7 +59,7 @@ struct DstState {
 // FFT direct solve (sc_fft.hip): per-direction chirp / transform tables and the two work planes.  The tables of a transform
 // length are built ON THE DEVICE (k_fft_build: both directions of a solve in one launch) and kept in a small LRU: a caller whose mask changes with every
 // frame meets new ROI sizes all the time, and alternating between a few sizes costs nothing.
-struct FftDim { int n = 0, logM = 0, r = 1; bool dbl = false; int kind = 0; DevBuf chirp; unsigned long long used = 0; };   // M = r 2^logM (r = 1, 3, 5); kind 0 (DST-I, chirp of period 2(n+1)): chirp[n+1] | bhat[M] | tw[M] | tw2[2^logM] (complex float or double); kind 1 (DCT-II / III, period 2n): chirp[n+1] | half-sample twiddle[n+1] | bhat | tw | tw2
+struct FftDim { int n = 0, logM = 0, r = 1; bool dbl = false; int kind = 0; DevBuf chirp; unsigned long long used = 0; };   // M = r 2^logM (r = 1, 3, 5); kind 0 (DST-I, chirp of period 2(n+1)): chirp[n+1] | bhat[M] | tw[M] | tw2[2^logM] (complex float or double); kind 1 (DCT-II / III, period 2n): chirp[n+1] | half-sample twiddle[n+1] | bhat | tw | tw2; kinds 2 (one Dirichlet end, period 2n+1) and 4 (periodic, Hartley, period n): two tables of n+1 in those places
 struct FftFxy { int w = 0, h = 0; bool singular = false; DevBuf d, hst; hipEvent_t ev = nullptr; unsigned long long used = 0; };   // the reference's float tables fx[w] + fy[h]: device, pinned staging of its own, upload event
 struct FftState {
     enum { DIMS = 8, FXY = 4 };
@@ -321,33 +321,46 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why);
 // ... and what the screened call (sc_screened_api.cpp) shares with it.  lam > 0: a screened call -- the jobs carry their data term
 // (PoissonJobDev::d), the solve is the direct one with shifted denominators.
-// A kind's parts.  The free sides as a mask (1 left, 2 right, 4 top, 8 bottom; SC_POISSON_NEUMANN: all four); the base kind (anything
-// but GUIDANCE or LAPLACIAN there is a bad kind); the kind the entry points hand on: all four sides free reads SC_POISSON_NEUMANN alone,
-// so one test of that bit finds the Neumann call and any SC_POISSON_FREE_* bit left a call with one to three free sides.
+// A kind's parts.  The free sides as a mask (1 left, 2 right, 4 top, 8 bottom; SC_POISSON_NEUMANN: all four); the periodic axes as a
+// mask (1 x, 2 y); the base kind (anything but GUIDANCE or LAPLACIAN there is a bad kind); the kind the entry points hand on: all four
+// sides free reads SC_POISSON_NEUMANN alone, so one test of that bit finds the Neumann call and any SC_POISSON_FREE_* bit left a call
+// with one to three free sides; the periodic bits pass through.
 constexpr int SC_POISSON_FREE_ALL = SC_POISSON_FREE_LEFT | SC_POISSON_FREE_RIGHT | SC_POISSON_FREE_TOP | SC_POISSON_FREE_BOTTOM;
+constexpr int SC_POISSON_PERIODIC_ALL = SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y;
 inline int poisson_free_sides(int kind) { return (kind & SC_POISSON_NEUMANN) ? 15 : (kind & SC_POISSON_FREE_ALL) >> 12; }
-inline int poisson_base(int kind) { return kind & ~(SC_POISSON_NEUMANN | SC_POISSON_FREE_ALL); }
+inline int poisson_periodic(int kind) { return (kind & SC_POISSON_PERIODIC_ALL) >> 17; }
+inline int poisson_base(int kind) { return kind & ~(SC_POISSON_NEUMANN | SC_POISSON_FREE_ALL | SC_POISSON_PERIODIC_ALL); }
 inline int poisson_norm_kind(int kind)
 {
     const int f = poisson_free_sides(kind);
-    return poisson_base(kind) | (f == 15 ? SC_POISSON_NEUMANN : f << 12);
+    return poisson_base(kind) | (f == 15 ? SC_POISSON_NEUMANN : f << 12) | (kind & SC_POISSON_PERIODIC_ALL);
 }
-// the axis kinds and unknowns of a call with free sides `f` (f = 0, the Dirichlet frame, and f = 15 included)
-inline MixedGeo poisson_mixed_geo(int f, int cols, int rows)
+// a call the transforms on caller arrays serve (direct_jobs_solve): a free side or a periodic axis
+inline bool poisson_direct(int kind) { return poisson_free_sides(kind) || poisson_periodic(kind); }
+// the axis kinds and unknowns of a call with free sides `f` (f = 0, the Dirichlet frame, and f = 15 included) and periodic axes `per`
+// (a periodic axis has no free side: poisson_validate)
+inline MixedGeo poisson_mixed_geo(int f, int cols, int rows, int per)
 {
     auto axis = [](bool lo, bool hi) { return lo ? (hi ? 1 : 3) : (hi ? 2 : 0); };
     MixedGeo mg;
-    mg.ax = axis(f & 1, f & 2); mg.ay = axis(f & 4, f & 8);
+    mg.ax = (per & 1) ? MIXED_PERIODIC : axis(f & 1, f & 2);
+    mg.ay = (per & 2) ? MIXED_PERIODIC : axis(f & 4, f & 8);
     mg.nx = cols - (mixed_low_d(mg.ax) ? 1 : 0) - (mixed_high_d(mg.ax) ? 1 : 0);
     mg.ny = rows - (mixed_low_d(mg.ay) ? 1 : 0) - (mixed_high_d(mg.ay) ? 1 : 0);
     return mg;
 }
+// no side of the kind (poisson_norm_kind's) keeps a Dirichlet line: boundary is read for its mean alone (unscreened; may be NULL) or not at all
+inline bool poisson_no_dirichlet(int kind)
+{
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), 4, 4, poisson_periodic(kind));
+    return mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay);
+}
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 bool aligned4(const void *p);
-// SC_FLAG_FFT_FP64's limit on a direct solve with free sides `free` (poisson_free_sides'; 0: the Dirichlet frame): `why` and
-// SC_ERR_BAD_SIZE when an axis has more unknowns than the double transforms take
-int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why);
+// SC_FLAG_FFT_FP64's limit on a direct solve with free sides `free` (poisson_free_sides'; 0: the Dirichlet frame) and periodic axes `per`
+// (poisson_periodic's): `why` and SC_ERR_BAD_SIZE when an axis has more unknowns than the double transforms take
+int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why, int per);
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
 int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);
@@ -402,9 +415,9 @@ void rag_end(Instance *I);
 int dst_solve(Instance *I);                                           // sc_dst.hip: SC_METHOD_DST
 int fft_solve(Instance *I, bool fp64);                                // sc_fft.hip: SC_METHOD_FFT (fp64: SC_FLAG_FFT_FP64)
 bool fft_supported(int w, int h, bool fp64);
-// sc_fft.hip: the problem with free sides on some or all of the borders (SC_POISSON_FREE_*, SC_POISSON_NEUMANN; mg: poisson_mixed_geo) on
-// caller arrays: m same-size jobs as C m planes, straight from the jobs' arrays into their out arrays, each axis under its own transform
-// (marks: 5 behind the boundary-mean reduction of an unscreened Neumann solve, else at the start; 6 behind the last transform launch)
+// sc_fft.hip: the problem with free sides on some or all of the borders or periodic axes (SC_POISSON_FREE_*, SC_POISSON_NEUMANN,
+// SC_POISSON_PERIODIC_*; mg: poisson_mixed_geo) on caller arrays: m same-size jobs as C m planes, straight from the jobs' arrays into their out arrays, each axis under its own transform
+// (marks: 5 behind the boundary-mean reduction of an unscreened singular solve -- no Dirichlet line on any side --, else at the start; 6 behind the last transform launch)
 // (lam > 0: the screened solve, sc_screened_api.cpp: the jobs' data term read with the right-hand side, no mean)
 int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
 bool wants_float_tables(const Instance *I);

@@ -11,6 +11,8 @@
 // SC_POISSON_NEUMANN and SC_POISSON_FREE_* on one to three sides: no fields, no pre-process or output launch -- per chunk
 // direct_jobs_solve (sc_fft.hip) works straight between the jobs' arrays: three transform launches, each axis under the transform of
 // its two ends, the Dirichlet lines of out written by the last one; in front of them the boundary-mean reduction of a Neumann call.
+// SC_POISSON_PERIODIC_X / _Y: the same path -- a periodic axis is one more axis kind of those launches; without a Dirichlet line on the
+// other axis either, the call is singular like the Neumann one and has its reduction.
 //
 // The screened call (sc_screened_api.cpp) runs through the same poisson_run with PoissonCall::lam > 0: the jobs carry their data
 // term, the solve is the direct one (SC_METHOD_FFT) with its denominators shifted by -lam.
@@ -31,24 +33,34 @@ int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, con
     if (!why) why = &dummy;
     *why = "";
     if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
-    const int free = poisson_free_sides(p->kind), base = poisson_base(p->kind);
+    const int free = poisson_free_sides(p->kind), per = poisson_periodic(p->kind), base = poisson_base(p->kind);
     const bool neumann = free == 15;
     if (base != SC_POISSON_GUIDANCE && base != SC_POISSON_LAPLACIAN) {
-        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN or SC_POISSON_FREE_* bits";
+        *why = "kind must be SC_POISSON_GUIDANCE or SC_POISSON_LAPLACIAN, alone or with SC_POISSON_NEUMANN, SC_POISSON_FREE_* or SC_POISSON_PERIODIC_* bits";
+        return SC_ERR_BAD_ARG;
+    }
+    if (per && (p->kind & SC_POISSON_NEUMANN)) { *why = "SC_POISSON_PERIODIC_* with SC_POISSON_NEUMANN: an axis wraps or reflects, not both"; return SC_ERR_BAD_ARG; }
+    if (((per & 1) && (free & 3)) || ((per & 2) && (free & 12))) {
+        *why = "a periodic axis has no free side: SC_POISSON_PERIODIC_X excludes SC_POISSON_FREE_LEFT / _RIGHT, SC_POISSON_PERIODIC_Y excludes _TOP / _BOTTOM";
         return SC_ERR_BAD_ARG;
     }
     if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
     if (l->channels < 1 || l->channels > 4) { *why = "channels must be 1..4"; return SC_ERR_BAD_ARG; }
     if (l->col_stride <= 0 || l->row_stride <= 0 || l->channel_stride <= 0) { *why = "strides must be positive"; return SC_ERR_BAD_ARG; }
-    if (free) {
+    if (free || per) {
         if (l->cols < 2 || l->rows < 2) {
-            *why = neumann ? "SC_POISSON_NEUMANN: the image must be at least 2 x 2" : "free sides: the image must be at least 2 x 2";
+            *why = neumann ? "SC_POISSON_NEUMANN: the image must be at least 2 x 2" : per ? "periodic axes: the image must be at least 2 x 2" : "free sides: the image must be at least 2 x 2";
             return SC_ERR_BAD_SIZE;
         }
-        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);       // (all four sides free: every pixel an unknown)
-        if (mg.nx < 1 || mg.ny < 1) { *why = "free sides: at least 1 unknown per axis (3 pixels between two Dirichlet lines)"; return SC_ERR_BAD_SIZE; }
+        const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows, per);       // (all four sides free: every pixel an unknown)
+        if (mg.nx < 1 || mg.ny < 1) {
+            *why = per ? "periodic axes: at least 1 unknown along the other axis (3 pixels between two Dirichlet lines)"
+                       : "free sides: at least 1 unknown per axis (3 pixels between two Dirichlet lines)";
+            return SC_ERR_BAD_SIZE;
+        }
         if (!fft_supported(mg.nx, mg.ny, false)) {
             *why = neumann ? "SC_POISSON_NEUMANN: the image must be at most 8192 x 8192"
+                 : per ? "periodic axes: at most 8192 unknowns (pixels less the axis's Dirichlet lines) per axis"
                            : "free sides: at most 8192 unknowns (pixels less the axis's Dirichlet lines) per axis";
             return SC_ERR_BAD_SIZE;
         }
@@ -79,9 +91,9 @@ size_t poisson_span(const sc_poisson_layout *l)
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why)
+int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why, int per)
 {
-    const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows);
+    const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows, per);
     if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
         I->err = why;
         return SC_ERR_BAD_SIZE;
@@ -89,12 +101,13 @@ int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const c
     return SC_OK;
 }
 
-// a job's own code: the pointers its kind (poisson_norm_kind's) needs, 4-byte aligned (a Neumann job may come without boundary: mean
-// zero; with a Dirichlet line on any side boundary is required)
+// a job's own code: the pointers its kind (poisson_norm_kind's) needs, 4-byte aligned (a job without a Dirichlet line on any side -- the
+// Neumann call, a periodic axis beside a periodic or free-free one -- may come without boundary: mean zero; with a Dirichlet line on any
+// side boundary is required)
 int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
 {
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
-    if ((kind & SC_POISSON_NEUMANN) && !b) b = out;
+    if (poisson_no_dirichlet(kind) && !b) b = out;
     const float *need[4] = { b, out, guidance ? gx : lap, guidance ? gy : lap };
     for (const float *q : need) {
         if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
@@ -152,12 +165,12 @@ int poisson_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDe
     return solve_rc;
 }
 
-// The same for a call with free sides (kind: poisson_norm_kind's; all four: the Neumann call): no fields; marks 5 (the Neumann call's
-// reduction done) and 6 (transforms done) come from direct_jobs_solve, 7 = 6 (the output is the last transform launch's store).
+// The same for a call with free sides or periodic axes (kind: poisson_norm_kind's; all four free: the Neumann call): no fields; marks 5
+// (a singular call's reduction done) and 6 (transforms done) come from direct_jobs_solve, 7 = 6 (the output is the last transform launch's store).
 int free_sides_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJobDev *jobs, int m, float lam)
 {
     stage_mark(I, 0);
-    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), g.W, g.H);
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), g.W, g.H, poisson_periodic(kind));
     const int rc = direct_jobs_solve(I, g, mg, poisson_base(kind) == SC_POISSON_LAPLACIAN, jobs, m, (I->opts.flags & SC_FLAG_FFT_FP64) != 0, lam);
     if (rc) return rc;
     stage_mark(I, 7);
@@ -168,15 +181,17 @@ int free_sides_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJo
 // and the limit of its transforms' precision
 int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
 {
-    const int free = poisson_free_sides(kind), method = I->opts.method;
-    if (!free) return SC_OK;
+    const int free = poisson_free_sides(kind), per = poisson_periodic(kind), method = I->opts.method;
+    if (!free && !per) return SC_OK;
     if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
-        I->err = free == 15 ? "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)"
+        I->err = per ? "periodic axes (SC_POISSON_PERIODIC_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)"
+               : free == 15 ? "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)"
                             : "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)";
         return SC_ERR_BAD_ARG;
     }
-    return direct_fp64_check(I, free, l, free == 15 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
-                                                    : "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
+    return direct_fp64_check(I, free, l, per ? "periodic axes with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis"
+                                         : free == 15 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
+                                                      : "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis", per);
 }
 
 void add_timing(Instance *I, float t[4])
@@ -216,7 +231,7 @@ int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, c
     int worst = SC_OK;
     for (int i0 = 0; i0 < nv; i0 += per) {
         const int m = std::min(per, nv - i0);
-        int rc = poisson_free_sides(p.kind) ? free_sides_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
+        int rc = poisson_direct(p.kind) ? free_sides_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
         if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
             if (timed) {
                 SC_HIP(I, hipStreamSynchronize(I->stream));
@@ -293,7 +308,7 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     if ((rc = poisson_job_validate(kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
     // one device block: the inputs' spans, boundary's, and out's unless out is boundary (in place); each at a 256-byte boundary
     const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
-    // (a Neumann call without boundary: no slot, no upload)
+    // (a call without a Dirichlet line and without boundary: no slot, no upload)
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE, in_place = out == boundary;
     const int slots = (guidance ? 2 : 1) + (boundary ? 1 : 0) + (in_place ? 0 : 1);
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;

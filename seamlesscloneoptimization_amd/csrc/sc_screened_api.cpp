@@ -1,7 +1,7 @@
 // sc_screened_api.cpp -- the screened Poisson solve on float32 images (sc_hip_screened_check, sc_hip_screened_device, sc_hip_screened):
 //     minimise lambda sum (u - d)^2 + sum |grad u - g|^2,   i.e.   (A - lambda) u = div g - lambda d,   lambda > 0,
 // A the 5-point operator of sc_hip_poisson with a Dirichlet frame, a reflecting border (SC_POISSON_NEUMANN) or Dirichlet lines on
-// some sides and free ones on the others (SC_POISSON_FREE_*).
+// some sides and free ones on the others (SC_POISSON_FREE_*), or with axes that wrap (SC_POISSON_PERIODIC_*).
 //
 // A call is a Poisson call (sc_poisson_api.cpp: validation, chunks of at most SC_POISSON_MAX_PLANES planes, stage marks, codes) with
 // PoissonCall::lam set: the jobs carry their data term, the launches that build the right-hand side read it (F = lap - lambda d:
@@ -26,7 +26,7 @@ int screened_validate(const sc_screened_params *p, const sc_poisson_layout *l, c
     const sc_poisson_params pp{ p->kind, 0.f };
     const int rc = poisson_validate(&pp, l, why);       // kind, channels, strides; the Neumann side limit; at least 3 x 3 under a frame
     if (rc) return rc;
-    if (!poisson_free_sides(p->kind) && !fft_supported(l->cols - 2, l->rows - 2, false)) {
+    if (!poisson_direct(p->kind) && !fft_supported(l->cols - 2, l->rows - 2, false)) {
         *why = "a screened solve is a direct solve: at most 8192 unknowns (pixels - 2) per side";
         return SC_ERR_BAD_SIZE;
     }
@@ -41,10 +41,11 @@ int screened_instance_check(Instance *I, const sc_screened_params *p, const sc_p
         I->err = "a screened solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know the unscreened operator)";
         return SC_ERR_BAD_ARG;
     }
-    const int free = poisson_free_sides(p->kind);
-    return direct_fp64_check(I, free, l, !free ? "a screened solve with SC_FLAG_FFT_FP64: at most 4096 unknowns (pixels - 2) per side"
+    const int free = poisson_free_sides(p->kind), per = poisson_periodic(p->kind);
+    return direct_fp64_check(I, free, l, per ? "a screened solve with periodic axes and SC_FLAG_FFT_FP64: at most 4096 unknowns per axis"
+                                     : !free ? "a screened solve with SC_FLAG_FFT_FP64: at most 4096 unknowns (pixels - 2) per side"
                                      : free == 15 ? "a screened SC_POISSON_NEUMANN solve with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
-                                                  : "a screened solve with free sides and SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
+                                                  : "a screened solve with free sides and SC_FLAG_FFT_FP64: at most 4096 unknowns per axis", per);
 }
 
 // a job's own code: data always, boundary with a Dirichlet line on any side, the arrays of its kind (poisson_norm_kind's), out; each
@@ -54,13 +55,13 @@ int screened_job_validate(int kind, const float *gx, const float *gy, const floa
 {
     if (!data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
     if (!aligned4(data)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
-    // (a Neumann job's boundary is not read: poisson_job_validate then checks out in its place)
-    return poisson_job_validate(kind, gx, gy, lap, (kind & SC_POISSON_NEUMANN) ? nullptr : b, out, why);
+    // (without a Dirichlet line on any side boundary is not read: poisson_job_validate then checks out in its place)
+    return poisson_job_validate(kind, gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out, why);
 }
 
 PoissonJobDev dev_job(int kind, const float *gx, const float *gy, const float *lap, const float *data, const float *b, float *out)
 {
-    PoissonJobDev j{ gx, gy, lap, (kind & SC_POISSON_NEUMANN) ? nullptr : b, out };
+    PoissonJobDev j{ gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out };
     j.d = data;
     return j;
 }
@@ -123,7 +124,7 @@ int sc_hip_screened(void *inst, const sc_screened_params *p, const sc_poisson_la
     // of out unless out is data or boundary (in place); each at a 256-byte boundary
     const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
-    if (kind & SC_POISSON_NEUMANN) boundary = nullptr;
+    if (poisson_no_dirichlet(kind)) boundary = nullptr;
     const bool b_is_d = boundary == data, own_b = boundary && !b_is_d, in_place = out == data || (boundary && out == boundary);
     const int n_in = guidance ? 2 : 1, slots = n_in + 1 + (own_b ? 1 : 0) + (in_place ? 0 : 1);
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;

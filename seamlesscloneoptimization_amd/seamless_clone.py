@@ -240,12 +240,12 @@ def poisson_tol(boundary, lap_scale=0.0):
     return max(1e-3, 4e-7 * scale * float(np.sqrt(b.shape[0] * b.shape[1])))
 
 
-def _direct(neumann, free_sides):
-    """Is a call with these borders one of the direct solves that use no tol (any free side)?"""
-    return bool(neumann) or capi.free_side_bits(free_sides) != 0
+def _direct(neumann, free_sides, periodic=""):
+    """Is a call with these borders one of the direct solves that use no tol (any free side or periodic axis)?"""
+    return bool(neumann) or capi.free_side_bits(free_sides) != 0 or capi.periodic_bits(periodic) != 0
 
 
-def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None, neumann=False, free_sides="", **solver):
+def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None, neumann=False, free_sides="", periodic="", **solver):
     """Solve the Poisson equation on a float32 image of shape H x W or H x W x C (C 1..4) and return a NEW array: lap(u) = div (gx, gy)
     (backward differences of the guidance field) or = laplacian, with u = boundary on the one-pixel frame.  boundary's interior is
     the initial guess of the iterative methods.  tol: the multigrid stop rule in the data's units (None: poisson_tol(boundary), a
@@ -256,24 +256,29 @@ def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None
     projected out.
     free_sides: the sides without known values, a string over "lrtb" (left, right, top, bottom) -- a region that touches the image
     edge, a strip pinned at two ends.  Their outermost pixels are unknowns and the field is reflected there; the other sides'
-    outermost rows and columns keep boundary's values.  A direct solve (methods auto and fft), tol unused; "lrtb" is neumann=True."""
-    kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian, neumann=neumann, free_sides=free_sides)
+    outermost rows and columns keep boundary's values.  A direct solve (methods auto and fft), tol unused; "lrtb" is neumann=True.
+    periodic: the axes that wrap, "x" (a 360-degree panorama), "y" or "xy" (a tileable texture): no known values along them, the pixel
+    beyond either end is the one at the other end; gx's last column / gy's last row then hold the difference across the seam.  Not
+    with neumann=True or a free side of the same axis (ValueError).  When the other axis has no Dirichlet line either, the answer's
+    mean is boundary's, which may be None, as for neumann."""
+    kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian, neumann=neumann, free_sides=free_sides, periodic=periodic)
     if tol is None:
-        tol = 0.0 if _direct(neumann, free_sides) else poisson_tol(b)
+        tol = 0.0 if _direct(neumann, free_sides, periodic) else poisson_tol(b)
     inst = capi.Instance(gpu_id)
     try:
         if solver:
             inst.set_solver(**solver)
-        return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol, neumann=neumann, free_sides=free_sides)
+        return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol, neumann=neumann, free_sides=free_sides, periodic=periodic)
     finally:
         inst.destroy()
 
 
-def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, neumann=False, free_sides="", **solver):
+def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, neumann=False, free_sides="", periodic="",
+                        **solver):
     """poisson_solve over a list of same-shape problems through ONE device-resident call (sc_hip_poisson_device): the inputs go to the
     device in one copy and the results come back in one; the problems are solved as one field of n x C planes (chunks of at most
     SC_POISSON_MAX_PLANES planes).  tol: as poisson_solve's (None: the largest poisson_tol of the batch).  Returns a list of NEW
-    arrays.  neumann: as poisson_solve's; boundaries may then hold None entries (mean zero).  free_sides: as poisson_solve's."""
+    arrays.  neumann: as poisson_solve's; boundaries may then hold None entries (mean zero).  free_sides, periodic: as poisson_solve's."""
     bs = list(boundaries)
     if not bs:
         return []
@@ -287,10 +292,10 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
     checked, has_b = [], []
     for k in range(n):
         if gxs is not None:
-            kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k], neumann=neumann, free_sides=free_sides)
+            kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k], neumann=neumann, free_sides=free_sides, periodic=periodic)
             ins = [gx, gy]
         else:
-            kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k], neumann=neumann, free_sides=free_sides)
+            kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k], neumann=neumann, free_sides=free_sides, periodic=periodic)
             ins = [lap]
         if ins[0].shape != fields[0][0].shape:
             raise ValueError("every problem of a batch must have one shape")
@@ -298,7 +303,7 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
         checked.append([np.ascontiguousarray(a) for a in ins + [b if b is not None else np.zeros_like(ins[0])]])
     shape = fields[0][0].shape
     if tol is None:
-        tol = 0.0 if _direct(neumann, free_sides) else max(poisson_tol(a[-1]) for a in checked)
+        tol = 0.0 if _direct(neumann, free_sides, periodic) else max(poisson_tol(a[-1]) for a in checked)
     nb = checked[0][0].nbytes
     slot = (nb + 255) // 256 * 256
     per = len(checked[0])
@@ -319,7 +324,7 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
         jobs = capi.Instance.make_poisson_jobs(n)
         for k, j in enumerate(jobs):
             base = d + k * per * slot
-            if (kind & ~(capi.SC_POISSON_NEUMANN | capi.SC_POISSON_FREE_ALL)) == capi.SC_POISSON_GUIDANCE:
+            if (kind & ~(capi.SC_POISSON_NEUMANN | capi.SC_POISSON_FREE_ALL | capi.SC_POISSON_PERIODIC_ALL)) == capi.SC_POISSON_GUIDANCE:
                 j.gx, j.gy = base, base + slot
             else:
                 j.lap = base
@@ -334,40 +339,51 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
     return [out[k * slot // 4:k * slot // 4 + checked[k][-1].size].reshape(shape).copy() for k in range(n)]
 
 
-def _screened_borders(neumann, free_sides):
-    """(neumann, free_sides) of a screened wrapper whose default is neumann=True: a free_sides given (not None) overrides that default."""
+def _screened_borders(neumann, free_sides, periodic=""):
+    """(neumann, free_sides) of a screened wrapper whose default is neumann=True: a free_sides given (not None) overrides that default.
+    So does a periodic axis: neumann is dropped, and with free_sides None the non-periodic axis is free at both ends."""
+    per = capi.periodic_bits(periodic)
+    if per:
+        if free_sides is None:
+            free_sides = ("" if per & capi.SC_POISSON_PERIODIC_X else "lr") + ("" if per & capi.SC_POISSON_PERIODIC_Y else "tb")
+        return False, free_sides
     if free_sides is None:
         return neumann, ""
     all_free = capi.free_side_bits(free_sides) == capi.SC_POISSON_FREE_ALL
     return all_free, "" if all_free else free_sides
 
 
-def screened_solve(data, gx=None, gy=None, laplacian=None, lam=None, boundary=None, neumann=True, gpu_id=0, free_sides=None, **solver):
+def screened_solve(data, gx=None, gy=None, laplacian=None, lam=None, boundary=None, neumann=True, gpu_id=0, free_sides=None, periodic="",
+                   **solver):
     """Screened Poisson solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
         lam sum (u - data)^2 + sum |grad u - (gx, gy)|^2                (or with the divergence of the guidance given as laplacian),
     i.e. (A - lam) u = div g - lam data for the 5-point operator A.  neumann (the default): every pixel is an unknown, the field is
     reflected at the border.  neumann=False: u = boundary on the one-pixel frame (boundary required; only its frame is read).  A
     direct solve (methods auto and fft; flags=SC_FLAG_FFT_FP64 for double transforms); lam must be finite and > 0.
     free_sides: a string over "lrtb", the sides without known values (poisson_solve's); giving it overrides the neumann default: ""
-    is the Dirichlet frame, "lrtb" the Neumann problem, anything between needs boundary for the remaining Dirichlet lines."""
-    neumann, free_sides = _screened_borders(neumann, free_sides)
-    kind, d, gx, gy, lap, b, _ = capi.screened_arrays(data, gx, gy, laplacian, lam, boundary, neumann=neumann, free_sides=free_sides)
+    is the Dirichlet frame, "lrtb" the Neumann problem, anything between needs boundary for the remaining Dirichlet lines.
+    periodic: the axes that wrap (poisson_solve's); it too overrides the neumann default, and with free_sides None the other axis is
+    free at both ends (no boundary needed)."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    kind, d, gx, gy, lap, b, _ = capi.screened_arrays(data, gx, gy, laplacian, lam, boundary, neumann=neumann, free_sides=free_sides,
+                                                      periodic=periodic)
     inst = capi.Instance(gpu_id)
     try:
         if solver:
             inst.set_solver(**solver)
-        return inst.screened(d, gx=gx, gy=gy, lap=lap, lam=lam, boundary=b, neumann=neumann, free_sides=free_sides)
+        return inst.screened(d, gx=gx, gy=gy, lap=lap, lam=lam, boundary=b, neumann=neumann, free_sides=free_sides, periodic=periodic)
     finally:
         inst.destroy()
 
 
 def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, boundaries=None, neumann=True, gpu_id=0, free_sides=None,
-                         **solver):
+                         periodic="", **solver):
     """screened_solve over a list of same-shape problems through ONE device-resident call (sc_hip_screened_device): one copy in, one
     copy out, the problems solved as one field of n x C planes (chunks of at most SC_POISSON_MAX_PLANES planes); every member equals
-    its solo solve bit for bit.  One lam for the batch.  boundaries: one per problem when neumann=False.  free_sides: as
+    its solo solve bit for bit.  One lam for the batch.  boundaries: one per problem when neumann=False.  free_sides, periodic: as
     screened_solve's.  Returns a list of NEW arrays."""
-    neumann, free_sides = _screened_borders(neumann, free_sides)
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))      # no side keeps a Dirichlet line
     ds = list(datas)
     n = len(ds)
     if lam is None or not np.isfinite(lam) or not lam > 0:
@@ -375,7 +391,7 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
     if (gxs is None) != (gys is None) or (gxs is None) == (laplacians is None):
         raise ValueError("give either gxs and gys or laplacians")
     fields = [gxs, gys] if gxs is not None else [laplacians]
-    if not neumann:
+    if not no_boundary:
         if boundaries is None:
             raise ValueError("a Dirichlet screened solve needs boundaries (neumann=True: none)")
         fields = fields + [boundaries]
@@ -386,12 +402,12 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
         return []
     checked = []
     for k in range(n):
-        b = None if neumann else boundaries[k]
+        b = None if no_boundary else boundaries[k]
         if gxs is not None:
-            kind, d, gx, gy, _, b, _ = capi.screened_arrays(ds[k], gxs[k], gys[k], None, lam, b, neumann=neumann, free_sides=free_sides)
+            kind, d, gx, gy, _, b, _ = capi.screened_arrays(ds[k], gxs[k], gys[k], None, lam, b, neumann=neumann, free_sides=free_sides, periodic=periodic)
             arrays = [gx, gy, d]
         else:
-            kind, d, _, _, lap, b, _ = capi.screened_arrays(ds[k], None, None, laplacians[k], lam, b, neumann=neumann, free_sides=free_sides)
+            kind, d, _, _, lap, b, _ = capi.screened_arrays(ds[k], None, None, laplacians[k], lam, b, neumann=neumann, free_sides=free_sides, periodic=periodic)
             arrays = [lap, d]
         if d.shape != ds[0].shape:
             raise ValueError("every problem of a batch must have one shape")
@@ -422,7 +438,7 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
                 j.gx, j.gy, j.data = base, base + slot, base + 2 * slot
             else:
                 j.lap, j.data = base, base + slot
-            j.boundary = None if neumann else base + (per - 1) * slot
+            j.boundary = None if no_boundary else base + (per - 1) * slot
             j.out = dev + in_bytes + k * slot
         inst.screened_device(capi.ScreenedParams(kind, float(lam)), layout, jobs)
         out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
@@ -433,13 +449,13 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
     return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
 
 
-def gradient_filter(image, gain, lam, neumann=True, gpu_id=0, free_sides=None, **solver):
+def gradient_filter(image, gain, lam, neumann=True, gpu_id=0, free_sides=None, periodic="", **solver):
     """Gradient-domain filtering of a float32 image (H x W or H x W x C): the image whose forward differences are `gain` times the
     input's while it stays close to the input, lam weighing the closeness -- screened_solve with data = image, guidance = gain x the
     forward differences of image, and boundary = image when neumann=False.  gain > 1 sharpens, gain < 1 flattens, gain 1 returns the
     image (to float32 rounding).  free_sides: as screened_solve's (the image itself is the boundary of the remaining Dirichlet lines).
-    Returns a NEW array."""
-    neumann, free_sides = _screened_borders(neumann, free_sides)
+    periodic: as screened_solve's; the forward differences then wrap along those axes.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     if not isinstance(image, np.ndarray) or image.dtype != np.float32:
         raise TypeError("image must be a float32 numpy array")
     if image.ndim not in (2, 3):
@@ -451,5 +467,46 @@ def gradient_filter(image, gain, lam, neumann=True, gpu_id=0, free_sides=None, *
     gy = np.zeros_like(image)
     gx[:, :-1] = g * (image[:, 1:] - image[:, :-1])
     gy[:-1] = g * (image[1:] - image[:-1])
+    if "x" in periodic:
+        gx[:, -1] = g * (image[:, 0] - image[:, -1])
+    if "y" in periodic:
+        gy[-1] = g * (image[0] - image[-1])
     return screened_solve(image, gx=gx, gy=gy, lam=lam, boundary=None if neumann else image, neumann=neumann, gpu_id=gpu_id,
-                          free_sides=None if neumann else free_sides, **solver)
+                          free_sides=None if neumann else free_sides, periodic=periodic, **solver)
+
+
+def wrapped_forward_differences(image, axes="xy"):
+    """(gx, gy) of a float32 image: forward differences, the last column of gx / row of gy holding the difference from the last pixel to
+    the first along the axes named in `axes` (0 along the others): the guidance of a periodic solve that gives the image back."""
+    capi.periodic_bits(axes)
+    gx = np.zeros_like(image)
+    gy = np.zeros_like(image)
+    gx[:, :-1] = image[:, 1:] - image[:, :-1]
+    gy[:-1] = image[1:] - image[:-1]
+    if "x" in axes:
+        gx[:, -1] = image[:, 0] - image[:, -1]
+    if "y" in axes:
+        gy[-1] = image[0] - image[-1]
+    return gx, gy
+
+
+def make_tileable(image, lam=0.0, axes="xy", gpu_id=0, **solver):
+    """A copy of a float32 image (H x W or H x W x C) that tiles without a seam along `axes` ("x", "y" or "xy"): the image whose wrapped
+    forward differences are the input's, except across the seam (gx's last column, gy's last row, for the named axes), where they are
+    0 -- the jump between the last pixel and the first is spread over the whole image.  Solved periodically along `axes`, the other
+    axis free at both ends.  lam > 0: screened_solve(image, gx, gy, lam=lam, periodic=axes), the result stays close to the image;
+    lam = 0: poisson_solve(image, gx, gy, periodic=axes, free_sides=<the other axis's two sides>), which keeps the image's mean.
+    lam < 0 or not finite: ValueError.  Returns a NEW array."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    if image.ndim not in (2, 3):
+        raise ValueError("image is H x W or H x W x C")
+    if not capi.periodic_bits(axes):
+        raise ValueError('axes must name at least one of "x" and "y"')
+    if lam is None or not np.isfinite(lam) or lam < 0:
+        raise ValueError("lam must be finite and >= 0 (0: the unscreened solve)")
+    gx, gy = wrapped_forward_differences(image, "")
+    if lam > 0:
+        return screened_solve(image, gx=gx, gy=gy, lam=lam, periodic=axes, gpu_id=gpu_id, **solver)
+    _, free_sides = _screened_borders(False, None, axes)
+    return poisson_solve(image, gx=gx, gy=gy, periodic=axes, free_sides=free_sides, gpu_id=gpu_id, **solver)

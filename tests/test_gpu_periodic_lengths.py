@@ -1,0 +1,104 @@
+"""The solve with periodic axes (SC_POISSON_PERIODIC_X / _Y: k_mix kind 4, k_fft_build kind 4) at every length class the Hartley
+transform of a periodic axis can get wrong, along x and along y, beside every kind of the other axis, at its size limits (the GPU
+side of tests/test_periodic_host.py).
+
+Float32 transforms are held to the float32 restatement on the same input -- measured <= max(FACTOR x solve_f32's, FLOOR) for RES and
+ERR -- and double transforms to float32 ulps: tests/periodic_bounds.py says what the quantities are and where the constants come from.
+Lines PERLEN carry the measured values beside the restatement's."""
+import numpy as np
+import pytest
+
+import periodic_np as pn
+from periodic_bounds import LENGTHS, OTHER_KINDS, STRIP32, STRIP64, Yardstick, length_cases, rough_inputs, smooth_input
+
+pytestmark = pytest.mark.gpu
+
+from seamlesscloneoptimization_amd import capi  # noqa: E402
+
+PREC = {"f32": 0, "f64": capi.SC_FLAG_FFT_FP64}
+
+
+@pytest.fixture()
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def configure(inst, prec, method=capi.SC_METHOD_FFT):
+    inst.set_solver(method=method, flags=(inst.default_opts().flags & ~capi.SC_FLAG_FFT_FP64) | PREC[prec])
+
+
+def solve_and_check(inst, sides, periodic, what, gx, gy, b, precs, tag, fails):
+    """One input under each precision: GUIDANCE (and LAPLACIAN fed numpy's divergence: the same bits), RES / ERR against the yardstick,
+    the Dirichlet lines.  Appends to fails; returns {prec: (err, res)} and the yardstick."""
+    lap = pn.divergence(gx, gy, periodic)
+    y = Yardstick(sides, periodic, 0.0, None, lap, b)
+    known = pn.dirichlet_mask(sides, periodic, *b.shape[:2])
+    kw = dict(free_sides=sides, periodic=periodic)
+    got = {}
+    for prec in precs:
+        configure(inst, prec)
+        out = inst.poisson(b, gx=gx, gy=gy, **kw)
+        i = inst.info()
+        if not (i.method == capi.SC_METHOD_FFT and i.converged == 1 and (i.W, i.H) == (gx.shape[1], gx.shape[0])):
+            fails.append((tag, prec, "info", i.method, i.W, i.H))
+        if not np.array_equal(inst.poisson(b, lap=lap, **kw), out):
+            fails.append((tag, prec, "LAPLACIAN differs from GUIDANCE"))
+        if not np.isfinite(out).all():
+            fails.append((tag, prec, "not finite"))
+            continue
+        if not np.array_equal(out[known], b[known]):
+            fails.append((tag, prec, "Dirichlet lines"))
+        bad, err, res = y.check(out, prec == "f64", rough=what != "smooth", reconstruction=what == "reconstruction")
+        fails.extend((tag, prec) + t for t in bad)
+        got[prec] = (err, res)
+    return got, y
+
+
+def fmt(got, y):
+    s = "f32 -"
+    if "f32" in got:
+        s = "f32 RES %.2e (x%.1f) ERR %.2e (x%.1f) / solve_f32 %.2e %.2e" % (
+            got["f32"][1], got["f32"][1] / max(y.res32, 1e-300), got["f32"][0], got["f32"][0] / max(y.err32, 1e-300), y.res32, y.err32)
+    if "f64" in got:
+        s += " | f64 RES %.2e ERR %.2f ulp" % (got["f64"][1], got["f64"][0] * y.R / float(np.spacing(np.float32(y.R))))
+    return s
+
+
+CASES = length_cases()
+
+
+def test_the_walk_covers_what_it_says():
+    ns = {c[0] for c in CASES}
+    assert ns == set(LENGTHS) | {STRIP32, STRIP64}
+    assert {2, 3, 4, 5, 24, 32, 33, 40, 129, 300} == set(LENGTHS) and (STRIP32, STRIP64) == (8192, 4096)
+    for n in ns:
+        for axis in "xy":
+            others = set()
+            for m, a, sides, periodic, W, H, precs in CASES:
+                if m != n or a != axis:
+                    continue
+                ax, ay = pn.axis_kinds(sides, periodic)
+                assert (ax if axis == "x" else ay) == pn.PP and (W if axis == "x" else H) == n
+                others.add(ay if axis == "x" else ax)
+            assert others == {pn.DD, pn.NN, pn.DN, pn.PP} and len(OTHER_KINDS) == 4, (n, axis)
+    assert all(("f64" in p) == (n <= STRIP64) for n, _, _, _, _, _, p in CASES)
+
+
+@pytest.mark.parametrize("axis", ["x", "y"])
+def test_every_length_class(inst, axis):
+    """length_cases() along one axis: rough inputs everywhere, the smooth low-mode reconstruction from 256 pixels up"""
+    fails = []
+    for n, a, sides, periodic, W, H, precs in CASES:
+        if a != axis:
+            continue
+        seed = 1000 * n + 10 * len(sides) + 100 * len(periodic) + (axis == "y")
+        ins = rough_inputs(W, H, 3, seed, periodic)
+        if n >= 256:
+            ins.append(smooth_input(W, H, 3, n + len(sides) + len(periodic), periodic))
+        for what, gx, gy, b in ins:
+            tag = "n=%d %s [%s] %s %s" % (n, axis, sides, periodic, what)
+            got, y = solve_and_check(inst, sides, periodic, what, gx, gy, b, precs, tag, fails)
+            print("PERLEN %-40s %s" % (tag, fmt(got, y)))
+    assert not fails, fails

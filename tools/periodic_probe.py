@@ -1,0 +1,163 @@
+#!/usr/bin/env python3
+"""Measures the Poisson solver's periodic axes (SC_POISSON_PERIODIC_X / _Y) on the GPU.
+
+--lengths   the length walk of tests/periodic_bounds.py (length_cases(): every length class of the Hartley transform of a periodic axis,
+            along x and y, beside each kind of the other axis; rough inputs, and the smooth low-mode reconstruction from 256 pixels
+            up): per case RES and ERR of the float32 transforms beside the float32 restatement's (tests/periodic_np.solve_f32) and of
+            the double transforms in float32 ulps, then the summary the bounds of tests/periodic_bounds.py are taken from -- the worst
+            ratios over the inputs with a periodic length above 3, the worst values at 2 and 3 -- and the constants the project's rule
+            gives from them (twice the worst, rounded up to one digit).  Written to --lengths-out (profiles/periodic_lengths.txt).
+(default)   device time (sc_run_info.ms_device_total of a bSync call on device arrays) of one solve periodic in x and y beside the
+            SC_POISSON_NEUMANN solve of the same arrays on the same instance, 2048 x 2048 x 3 and 300 x 200 x 3: median of --calls
+            calls after --warmup, the two alternating.  Written to --out (profiles/periodic_probe.json).
+
+    python tools/periodic_probe.py [--lengths] [--lengths-out FILE] [--out FILE] [--calls 25] [--warmup 5]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from seamlesscloneoptimization_amd import capi  # noqa: E402
+import periodic_np  # noqa: E402
+from periodic_bounds import Yardstick, length_cases, rough_inputs, smooth_input  # noqa: E402
+
+PREC = {"f32": 0, "f64": capi.SC_FLAG_FFT_FP64}
+
+
+def configure(inst, prec):
+    inst.set_solver(method=capi.SC_METHOD_FFT, flags=(inst.default_opts().flags & ~capi.SC_FLAG_FFT_FP64) | PREC[prec])
+
+
+def twice_rounded_up(v):
+    """2 v rounded up to one significant digit"""
+    v = 2.0 * v
+    if v <= 0:
+        return 0.0
+    e = math.floor(math.log10(v))
+    return float("%.0e" % (math.ceil(v / 10.0 ** e - 1e-12) * 10.0 ** e))
+
+
+def lengths(inst, path):
+    lines = ["n axis sides periodic WxH input | f32 RES (x restatement) ERR (x restatement) | solve_f32 RES ERR | f64 RES, ERR in float32 ulps"]
+    worst = {"res_ratio": (0.0, None), "err_ratio": (0.0, None), "res_small": (0.0, None), "err_small": (0.0, None),
+             "f64_ulps": (0.0, None), "f64_res_reconstruction": (0.0, None), "err_smooth_ratio": (0.0, None)}
+
+    def note(key, value, tag):
+        if value > worst[key][0]:
+            worst[key] = (value, tag)
+
+    for n, axis, sides, periodic, W, H, precs in length_cases():
+        seed = 1000 * n + 10 * len(sides) + 100 * len(periodic) + (axis == "y")
+        inputs = rough_inputs(W, H, 3, seed, periodic)
+        if n >= 256:
+            inputs.append(smooth_input(W, H, 3, n + len(sides) + len(periodic), periodic))
+        for what, gx, gy, b in inputs:
+            lap = periodic_np.divergence(gx, gy, periodic)
+            y = Yardstick(sides, periodic, 0.0, None, lap, b)
+            tag = "n=%d %s [%s] %s %s" % (n, axis, sides, periodic, what)
+            s = "n=%4d %s %-2s %-2s %4dx%-4d %-14s |" % (n, axis, sides or "-", periodic, W, H, what)
+            for prec in precs:
+                configure(inst, prec)
+                err, res = y.measure(inst.poisson(b, gx=gx, gy=gy, free_sides=sides, periodic=periodic))
+                if prec == "f32":
+                    rr, er = res / max(y.res32, 1e-300), err / max(y.err32, 1e-300)
+                    s += " f32 RES %.2e (x%.1f) ERR %.2e (x%.1f) | solve_f32 %.2e %.2e |" % (res, rr, err, er, y.res32, y.err32)
+                    if what == "smooth":
+                        note("err_smooth_ratio", er, tag)
+                    elif n > 3:
+                        note("res_ratio", rr, tag)
+                        note("err_ratio", er, tag)
+                    else:
+                        note("res_small", res, tag)
+                        note("err_small", err, tag)
+                else:
+                    ulps = err * y.R / float(np.spacing(np.float32(y.R)))
+                    s += " f64 RES %.2e ERR %.2f ulp" % (res, ulps)
+                    note("f64_ulps", ulps, tag)
+                    if what == "reconstruction":
+                        note("f64_res_reconstruction", res, tag)
+            lines.append(s)
+            print(s, flush=True)
+    lines.append("")
+    for key, (value, tag) in worst.items():
+        lines.append("WORST %-24s %.3e   at %s" % (key, value, tag))
+        print(lines[-1], flush=True)
+    lines.append("")
+    for name, key in (("RES_FACTOR", "res_ratio"), ("RES_FLOOR", "res_small"), ("ERR_FACTOR", "err_ratio"), ("ERR_FLOOR", "err_small"),
+                      ("ERR_SMOOTH_FACTOR", "err_smooth_ratio")):
+        lines.append("RULE  %-18s = %g      (twice %.3e, rounded up to one digit)" % (name, twice_rounded_up(worst[key][0]), worst[key][0]))
+        print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def timing(inst, path, calls, warmup):
+    rows = []
+    for W, H in ((2048, 2048), (300, 200)):
+        C = 3
+        rng = np.random.default_rng(W + H)
+        arrays = [rng.normal(0, 20, (H, W, C)).astype(np.float32) for _ in range(2)] + [rng.uniform(-50, 300, (H, W, C)).astype(np.float32)]
+        nbytes = arrays[0].nbytes
+        slot = (nbytes + 255) // 256 * 256
+        d = inst.malloc(4 * slot)
+        try:
+            for k, a in enumerate(arrays):
+                inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, d + k * slot, a.ctypes.data, nbytes))
+            layout = capi.poisson_layout_of(arrays[0])
+            configure(inst, "f32")
+            times = {"periodic_xy": [], "neumann": []}
+            kinds = {"periodic_xy": capi.SC_POISSON_GUIDANCE | capi.SC_POISSON_PERIODIC_X | capi.SC_POISSON_PERIODIC_Y,
+                     "neumann": capi.SC_POISSON_GUIDANCE | capi.SC_POISSON_NEUMANN}
+            for it in range(warmup + calls):
+                for name, kind in kinds.items():
+                    jobs = capi.Instance.make_poisson_jobs(1)
+                    jobs[0].gx, jobs[0].gy, jobs[0].boundary, jobs[0].out = d, d + slot, d + 2 * slot, d + 3 * slot
+                    inst.poisson_device(capi.PoissonParams(kind, 0.0), layout, jobs, sync=True)
+                    if it >= warmup:
+                        times[name].append(inst.info().ms_device_total)
+            row = {"W": W, "H": H, "C": C, "calls": calls, "warmup": warmup}
+            for name, t in times.items():
+                row[name + "_ms_median"] = float(np.median(t))
+                row[name + "_ms_min"] = float(np.min(t))
+            row["periodic_over_neumann"] = row["periodic_xy_ms_median"] / row["neumann_ms_median"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        finally:
+            inst.free(d)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump({"what": "device ms of one float32 solve, periodic in x and y vs SC_POISSON_NEUMANN, same arrays and instance", "rows": rows}, f, indent=1)
+        f.write("\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lengths", action="store_true")
+    ap.add_argument("--lengths-out", default=os.path.join(ROOT, "profiles", "periodic_lengths.txt"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "periodic_probe.json"))
+    ap.add_argument("--calls", type=int, default=25)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    inst = capi.Instance(0)
+    try:
+        if a.lengths:
+            lengths(inst, a.lengths_out)
+        else:
+            timing(inst, a.out, a.calls, a.warmup)
+    finally:
+        inst.destroy()
+
+
+if __name__ == "__main__":
+    main()
