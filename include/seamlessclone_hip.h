@@ -602,6 +602,58 @@ SC_API int sc_hip_screened_device(void *instance, const sc_screened_params *p, c
 /* One problem on host arrays, as sc_hip_poisson: spans in and out through pinned staging, only the named elements of out written. */
 SC_API int sc_hip_screened(void *instance, const sc_screened_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                            const float *lap, const float *data, const float *boundary, float *out);
+/* ---- weighted solves: a data term whose weight varies from pixel to pixel ---------------------------------------------------------
+ * The problem: per channel,
+ *     minimise   sum_q w(q) (u(q) - d(q))^2 + sum |grad u - g|^2       i.e.       (A - W) u = div g - W d,      W = diag(w), w >= 0,
+ * A the 5-point operator of sc_hip_poisson under the same border kinds: scattered or scribbled constraints (w > 0 at a few pixels),
+ * confidence-weighted reconstruction, soft regions of any shape (a large w pins u to d), the inner step of reweighted solves.
+ * kind, layout, chunks of at most 192 planes, what a call writes, aliasing and the per-job codes: sc_hip_screened_device's.  weight is
+ * read like data: at every unknown, under the call's layout, per channel; it must not overlap out.  The right-hand side is lap - w * d
+ * in float32, one rounded multiply, then one subtract, as the screened call forms lap - lambda * d.  boundary is read on Dirichlet lines
+ * only and copied to out bit for bit.
+ * Solved by conjugate gradients on the device, preconditioned by the screened direct solve with the constant lambda-bar = precond_lambda,
+ * or the mean of w over the unknowns of the call's chunk (a constant w converges in one iteration, random weights
+ * over two decades in about ten, a half-plane of zero weight in tens).  The vectors are float32, every dot product is summed in double
+ * in one fixed order: two runs of one call give the same bytes.  SC_FLAG_FFT_FP64: the preconditioner's transforms in double.
+ * Methods: SC_METHOD_AUTO and SC_METHOD_FFT; sizes: the direct solves' limits, a Dirichlet frame on all four sides included.
+ * Stop rule: ||r||_2 <= tol ||b||_2 on every plane of the chunk, r the iteration's own residual.  The norms of iteration k reach the
+ * host SC_WEIGHTED_POLL iterations later (a pinned mailbox and an event per iteration, so the stream never waits for the host): a call
+ * runs up to SC_WEIGHTED_POLL iterations past the one that met tol, and writes its last iterate.  SC_ERR_NOT_CONVERGED when max_iters
+ * ends first: the last iterate is written -- of all iterates the one with the smallest error in the energy norm.
+ * Host waits: one for the weights' statistics (their mean and validity, per chunk), the stop rule's reads, and one for the last
+ * iteration's norms; the output launch behind them is asynchronous unless bSync.
+ * Batches: every plane has its own alpha, beta and norms, but the stop is joint and the automatic lambda-bar is the chunk's: a member
+ * agrees with its solo run to the stop rule's error, not bit for bit.
+ * Codes: SC_ERR_BAD_ARG for a non-finite tol or precond_lambda, a method other than AUTO or FFT, a bad kind or layout (the screened
+ * call's); per job SC_ERR_BAD_ARG for a NULL or misaligned pointer the kind needs (weight and data always), for a weight that is negative
+ * or not finite anywhere in the job, and, in a call without any Dirichlet line, for a channel whose weights are all zero ("no data
+ * weight and no Dirichlet line": the system is singular) -- nothing of such a job is written, the others run.
+ * sc_run_info: method SC_METHOD_FFT, sweeps = iterations, converged, rel_residual = the worst plane's final ||r|| / ||b||, W x H = the
+ * image (the last chunk's figures); ms_solve = ms_call = the call's stream time when bSync is set and for the host call. */
+#define SC_WEIGHTED_POLL 4   /* iterations between an iteration and the host's read of its norms */
+typedef struct sc_weighted_params {
+    int   kind;              /* as sc_screened_params.kind: base kind | NEUMANN | FREE_* | PERIODIC_* */
+    float tol;               /* stop when ||r||_2 <= tol * ||b||_2 on every plane; <= 0: 1e-5 */
+    int   max_iters;         /* <= 0: 200 */
+    float precond_lambda;    /* the constant of the preconditioner (A - lambda); <= 0: the mean of w over the unknowns of the call's chunk */
+} sc_weighted_params;
+typedef struct sc_weighted_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE */
+    const float *lap;        /* SC_POISSON_LAPLACIAN */
+    const float *data;       /* d: read at every unknown */
+    const float *weight;     /* w >= 0: read at every unknown */
+    const float *boundary;   /* its Dirichlet lines (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_weighted_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_weighted_check(const sc_weighted_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_weighted_device(void *instance, const sc_weighted_params *p, const sc_poisson_layout *l, sc_weighted_job *jobs, int n,
+                                  bool bSync);
+/* One problem on host arrays, as sc_hip_screened: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_weighted(void *instance, const sc_weighted_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                           const float *lap, const float *data, const float *weight, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -211,6 +211,19 @@ class ScreenedJob(C.Structure):
                 ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# weighted solves (sc_hip_weighted*): Instance.weighted / weighted_device
+SC_WEIGHTED_POLL = 4        # iterations between an iteration and the host's read of its norms (seamlessclone_hip.h)
+
+
+class WeightedParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("tol", C.c_float), ("max_iters", C.c_int), ("precond_lambda", C.c_float)]
+
+
+class WeightedJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("weight", C.c_void_p),
+                ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -388,6 +401,13 @@ def load():
     L.sc_hip_screened_device.restype = C.c_int
     L.sc_hip_screened.argtypes = [C.c_void_p, C.POINTER(ScreenedParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 6
     L.sc_hip_screened.restype = C.c_int
+    L.sc_hip_weighted_check.argtypes = [C.POINTER(WeightedParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_weighted_check.restype = C.c_int
+    L.sc_hip_weighted_device.argtypes = [C.c_void_p, C.POINTER(WeightedParams), C.POINTER(PoissonLayout), C.POINTER(WeightedJob), C.c_int,
+                                         C.c_bool]
+    L.sc_hip_weighted_device.restype = C.c_int
+    L.sc_hip_weighted.argtypes = [C.c_void_p, C.POINTER(WeightedParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 7
+    L.sc_hip_weighted.restype = C.c_int
     _lib = L
     return L
 
@@ -498,6 +518,47 @@ def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, o
         if boundary.shape != data.shape:
             raise ValueError(f"boundary has shape {boundary.shape}, the problem {data.shape}")
     return kind, data, gx, gy, lap, boundary, out
+
+
+def weighted_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0,
+                   layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                   channel_stride=None) -> int:
+    """Host-only sc_hip_weighted_check: SC_OK or the code a weighted call with these parameters and this layout returns before it runs
+    anything.  The layout as a PoissonLayout or as keyword fields."""
+    if layout is None:
+        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
+    p = WeightedParams(int(kind), float(tol), int(max_iters), float(precond_lambda))
+    return int(load().sc_hip_weighted_check(C.byref(p), C.byref(layout)))
+
+
+def weighted_arrays(data, weight, gx=None, gy=None, lap=None, boundary=None, out=None, neumann=False, free_sides="", periodic=""):
+    """Checks a weighted problem's numpy arrays before any device is touched: (kind, data, weight, gx, gy, lap, boundary, out), every
+    array float32 and of data's shape, except that a 2-D weight beside 3-D data is broadcast over the channels.  Neither gx, gy nor lap:
+    zero guidance (lap = 0).  boundary is required when a side keeps a Dirichlet line and ignored otherwise."""
+    all_free = no_dirichlet(border_bits(free_sides, neumann, periodic))
+    if data is None or weight is None:
+        raise ValueError("a weighted solve needs its data term and its weights")
+    if not isinstance(data, np.ndarray) or data.dtype != np.float32:
+        raise TypeError("data must be a float32 numpy array")
+    if not isinstance(weight, np.ndarray) or weight.dtype != np.float32:
+        raise TypeError("weight must be a float32 numpy array")
+    if weight.ndim == 2 and data.ndim == 3 and weight.shape == data.shape[:2]:
+        weight = np.ascontiguousarray(np.broadcast_to(weight[:, :, None], data.shape))
+    if weight.shape != data.shape:
+        raise ValueError(f"weight has shape {weight.shape}, the problem {data.shape}")
+    if gx is None and gy is None and lap is None:
+        lap = np.zeros(data.shape, np.float32)
+    if all_free:
+        boundary = None
+    elif boundary is None:
+        raise ValueError("a weighted solve with a Dirichlet line needs boundary")
+    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides, periodic)
+    if boundary is not None:
+        if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
+            raise TypeError("boundary must be a float32 numpy array")
+        if boundary.shape != data.shape:
+            raise ValueError(f"boundary has shape {boundary.shape}, the problem {data.shape}")
+    return kind, data, weight, gx, gy, lap, boundary, out
 
 
 class Instance:
@@ -737,6 +798,50 @@ class Instance:
         if allow_job_errors and rc != SC_ERR_HIP:
             return rc
         return self._check(rc)
+
+    # ---- weighted solves on float32 arrays
+    def weighted(self, data, weight, gx=None, gy=None, lap=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
+                 tol=0.0, max_iters=0, precond_lambda=0.0, allow_not_converged=False):
+        """sc_hip_weighted on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise sum weight (u - data)^2 +
+        sum |grad u - (gx, gy)|^2 (or with the divergence given as lap; neither: zero guidance) under the borders of poisson()
+        (neumann, free_sides, periodic; boundary on the remaining Dirichlet lines).  weight >= 0, of data's shape or H x W (broadcast
+        over the channels).  tol, max_iters, precond_lambda: sc_weighted_params' (0: the defaults).  out: an array of data's shape
+        to write (may be data or boundary), default a new one.  Returns out; info() has the iterations and the final residual."""
+        kind, data, weight, gx, gy, lap, boundary, out = weighted_arrays(data, weight, gx, gy, lap, boundary, out, neumann, free_sides,
+                                                                         periodic)
+        if out is None:
+            out = np.empty_like(data)
+        given = [a for a in (data, weight, gx, gy, lap, boundary, out) if a is not None]
+        lays = [poisson_layout_of(a) for a in given]
+        target = out
+        if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
+            # one layout per call: contiguous copies, a new contiguous out copied back below
+            data, weight, gx, gy, lap, boundary = (None if a is None else np.ascontiguousarray(a) for a in (data, weight, gx, gy, lap, boundary))
+            out = np.empty(data.shape, np.float32)
+        layout = poisson_layout_of(out)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        p = WeightedParams(kind, float(tol), int(max_iters), float(precond_lambda))
+        rc = self.L.sc_hip_weighted(self.h, C.byref(p), C.byref(layout), ptr(gx), ptr(gy), ptr(lap), ptr(data), ptr(weight), ptr(boundary),
+                                    ptr(out))
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        if out is not target:
+            target[...] = out
+        return target
+
+    @staticmethod
+    def make_weighted_jobs(n: int):
+        return (WeightedJob * n)()
+
+    def weighted_device(self, params: WeightedParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_weighted_device: jobs is a WeightedJob array (make_weighted_jobs) of device pointers, one layout for all.  sync: bSync
+        and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other
+        failures raise unless allow_job_errors (then they are returned as well)."""
+        rc = self.L.sc_hip_weighted_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -13,6 +13,8 @@
 //      and a chunk whose batch call fails with SC_ERR_HIP (after writing SC_OK into its members) reported as failed, job and pool.
 //   5. sc_hip_poisson_check over valid and invalid layouts (the overlap test's 128-bit arithmetic at extreme strides included).
 //   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
+//   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
+//      launch, so it is not reachable here).
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
@@ -362,6 +364,40 @@ int main()
         }
         sc_screened_params p{ SC_POISSON_GUIDANCE, 1.f };
         if (sc_hip_screened_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_screened_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("screened_check (null)");
+    }
+    // 7: the weighted call's validation
+    {
+        struct Case { int kind; float tol; int iters; float plam; int w, h, c; long long cs, rs, chs; int want; };
+        const float nan = std::nanf(""), inf = HUGE_VALF;
+        const int G = SC_POISSON_GUIDANCE, Lp = SC_POISSON_LAPLACIAN, N = SC_POISSON_NEUMANN;
+        const Case cases[] = {
+            { G, 0.f, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_OK },
+            { Lp | N, 1e-6f, 50, 0.5f, 640, 480, 3, 3, 1920, 1, SC_OK },
+            { Lp | N, -1.f, -5, -1.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { Lp | SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y, 0.f, 0, 0.f, 2, 2, 4, 4, 8, 1, SC_OK },
+            { Lp | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_TOP, 0.f, 0, 0.f, 2, 2, 1, 1, 2, 4, SC_OK },
+            { Lp | N, nan, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp | N, inf, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp | N, 0.f, 0, nan, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp | N, 0.f, 0, -inf, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { 0, 0.f, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp | N | SC_POISSON_PERIODIC_X, 0.f, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp | SC_POISSON_PERIODIC_Y | SC_POISSON_FREE_TOP, 0.f, 0, 0.f, 640, 480, 3, 3, 1920, 1, SC_ERR_BAD_ARG },
+            { Lp, 0.f, 0, 0.f, 2, 7, 1, 1, 2, 14, SC_ERR_BAD_SIZE },
+            { Lp, 0.f, 0, 0.f, 8194, 3, 1, 1, 8194, 24582, SC_OK },
+            { Lp, 0.f, 0, 0.f, 8195, 3, 1, 1, 8195, 24585, SC_ERR_BAD_SIZE },
+            { Lp | N, 0.f, 0, 0.f, 8193, 2, 1, 1, 8193, 16386, SC_ERR_BAD_SIZE },
+            { Lp | N, 0.f, 0, 0.f, 640, 480, 3, 3, 1919, 1, SC_ERR_BAD_ARG },
+            { Lp | N, 0.f, 0, 0.f, 640, 480, 5, 5, 3200, 1, SC_ERR_BAD_ARG },
+            { Lp | N, 0.f, 0, 0.f, 640, 480, 3, 1LL << 58, 1LL << 59, 1, SC_ERR_BAD_ARG },
+        };
+        for (const Case &k : cases) {
+            sc_weighted_params p{ k.kind, k.tol, k.iters, k.plam };
+            sc_poisson_layout l{ k.w, k.h, k.c, k.cs, k.rs, k.chs };
+            if (sc_hip_weighted_check(&p, &l) != k.want) return fail("weighted_check");
+        }
+        sc_weighted_params p{ SC_POISSON_GUIDANCE, 0.f, 0, 0.f };
+        if (sc_hip_weighted_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_weighted_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("weighted_check (null)");
     }
     printf("sanitize_main: clean\n");
     return 0;

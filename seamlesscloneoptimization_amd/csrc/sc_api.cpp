@@ -353,6 +353,9 @@ void my_seamlessclone_api_imp_destroy(void *p)
     }
     if (I->fft.ev_fork) (void)hipEventDestroy(I->fft.ev_fork);
     if (I->fft.ev_built) (void)hipEventDestroy(I->fft.ev_built);
+    for (DevBuf *b : { &I->wt.u, &I->wt.r, &I->wt.p, &I->wt.q, &I->wt.w, &I->wt.red }) dev_release(*b);
+    if (I->wt.h_red.p) (void)hipHostFree(I->wt.h_red.p);
+    for (hipEvent_t e : I->wt.ev) if (e) (void)hipEventDestroy(e);
     dev_release(I->mg_fd);
     dev_release(I->rag.d_aux);
     if (I->rag.h_stage.p) (void)hipHostFree(I->rag.h_stage.p);

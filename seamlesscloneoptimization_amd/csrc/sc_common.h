@@ -105,6 +105,20 @@ __device__ __forceinline__ float screened_rhs(float rhs, float lam, float d)
 #endif
     return rhs - t;
 }
+#if defined(__HIPCC__)
+// the reflecting system's right-hand side at pixel (x, y) of channel c: given, or (a - b) + (c - d) of the guidance field in float32
+// (px / py: that axis wraps -- the difference stored in the last column / row runs from the last pixel to the first, and column / row 0
+// takes it as its backward difference)
+template <bool LAP>
+__device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDev &j, int c, int x, int y, bool px, bool py)
+{
+    const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
+    if (LAP) return j.lap[o];
+    const float a = (x < g.W - 1 || px) ? j.gx[o] : 0.f, b = x > 0 ? j.gx[o - g.cs] : px ? j.gx[o + (long long)(g.W - 1) * g.cs] : 0.f;
+    const float cc = (y < g.H - 1 || py) ? j.gy[o] : 0.f, d = y > 0 ? j.gy[o - g.rs] : py ? j.gy[o + (long long)(g.H - 1) * g.rs] : 0.f;
+    return (a - b) + (cc - d);
+}
+#endif
 // lam > 0: the screened right-hand side F = lap - lam d (d: PoissonJobDev::d, read on the interior); lam = 0: the launches as they were
 void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, Field U0, Field F, hipStream_t s, float lam = 0.f);
 void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s, float lam = 0.f);
@@ -114,6 +128,35 @@ void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, in
 // boundary (0 where the job has none); np = poisson_mean_parts(H); one launch per 16 members
 int poisson_mean_parts(int H);
 void launch_poisson_mean(const PoissonGeo &g, const PoissonJobDev *jobs, int n, double *parts, hipStream_t s);
+// ---- the weighted solve (sc_weighted.hip: kernels; sc_weighted_api.cpp: the iteration): conjugate gradients on (A - W) u = b, W = diag(w) >= 0,
+// preconditioned by direct_jobs_solve with the constant lambda-bar.  Work planes are compact float32: only the nx x ny unknowns of
+// MixedGeo, row after row, planes `stride` floats apart (a multiple of 4: float4 access); plane p = member C + channel.
+// Tiling of the launches that walk a plane in 2-D (weights' statistics, set-up, operator): column group x of 256 columns, band y of `rows`
+// rows, one partial sum per workgroup, cg * bands <= WEIGHTED_PARTS of them per plane; of the element-wise launches (update, dot):
+// `eparts` segments of whole float4 groups.  Partial sums are doubles at parts[plane * WEIGHTED_PARTS + i]; whoever needs a total
+// adds the parts of its plane itself, in one fixed order (first wave, then shuffles): no atomics, no host round trip.
+struct WeightedJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX]; };
+constexpr int WEIGHTED_PARTS = 256;
+struct WeightedGeo { int nx, ny, ax, ay, x0, y0, cg, bands, rows, eparts, egroups; long long stride; };
+WeightedGeo weighted_geo(const MixedGeo &mg);
+inline int weighted_op_parts(const WeightedGeo &wg) { return wg.cg * wg.bands; }
+// stats[(plane * WEIGHTED_PARTS + i) * 2] = the part's sum of w over the unknowns, [.. + 1] = how many of them are negative or not finite
+void launch_weighted_stats(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, const float *const *w, int m, double *stats, hipStream_t s);
+// R = b = lap - w d (screened_rhs's order) less the neighbouring Dirichlet lines' values, Wc = w, bb = the parts of b . b
+void launch_weighted_setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, int m, float *R, float *Wc,
+                           double *bb, hipStream_t s);
+// residual = false: Q = (A - W) P, parts of P . Q;  true: Q = Q - (A - W) P in place, parts of Q . Q
+void launch_weighted_op(const WeightedGeo &wg, int planes, bool residual, const float *P, const float *Wc, float *Q, double *parts, hipStream_t s);
+// alpha = sum(rz) / sum(pq) per plane (0 when that is not finite);  U += alpha P,  R -= alpha Q,  rr = the parts of R . R
+void launch_weighted_update(const WeightedGeo &wg, int planes, float *U, float *R, const float *P, const float *Q, const double *rz, const double *pq,
+                            double *rr, hipStream_t s);
+// rz = the parts of R . Z;  rr_tot[plane] = the sum of the nrr parts of rr (for the stop rule)
+void launch_weighted_dot(const WeightedGeo &wg, int planes, const float *R, const float *Z, double *rz, const double *rr, int nrr, double *rr_tot,
+                         hipStream_t s);
+// P = Z + beta P, beta = sum(rz) / sum(rz_old) per plane (rz_old == nullptr: P = Z)
+void launch_weighted_dir(const WeightedGeo &wg, int planes, float *P, const float *Z, const double *rz, const double *rz_old, hipStream_t s);
+// the jobs' out: U at the unknowns, boundary's values on the Dirichlet lines
+void launch_weighted_out(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, int m, const float *U, hipStream_t s);
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

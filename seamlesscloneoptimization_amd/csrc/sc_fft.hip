@@ -370,18 +370,7 @@ __global__ __launch_bounds__(256) void k_fft_transpose(const T *__restrict__ in,
 // The launches work straight between the caller's arrays and the work planes: plane p = member C + channel of a table of up to
 // PoissonJobs::MAX jobs.
 
-// the reflecting system's right-hand side at pixel (x, y) of channel c: given, or (a - b) + (c - d) of the guidance field in float32
-// (px / py: that axis wraps -- the difference stored in the last column / row runs from the last pixel to the first, and column / row 0
-// takes it as its backward difference)
-template <bool LAP>
-__device__ __forceinline__ float dct_rhs(const PoissonGeo &g, const PoissonJobDev &j, int c, int x, int y, bool px, bool py)
-{
-    const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
-    if (LAP) return j.lap[o];
-    const float a = (x < g.W - 1 || px) ? j.gx[o] : 0.f, b = x > 0 ? j.gx[o - g.cs] : px ? j.gx[o + (long long)(g.W - 1) * g.cs] : 0.f;
-    const float cc = (y < g.H - 1 || py) ? j.gy[o] : 0.f, d = y > 0 ? j.gy[o - g.rs] : py ? j.gy[o + (long long)(g.H - 1) * g.rs] : 0.f;
-    return (a - b) + (cc - d);
-}
+// (the reflecting system's right-hand side at a pixel, dct_rhs: sc_common.h -- the weighted solve's set-up launch forms it too)
 
 // The five axis kinds.  Per axis of n unknowns (MixedGeo): kind 0, Dirichlet lines at both ends, the DST-I above; kind 1, both ends free, the DCT-II / III
 // above; kind 2, a Dirichlet line at the low end and a free high end, the sine transform of odd half-frequencies
@@ -432,11 +421,15 @@ __device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg
 {
     const long long o = (long long)x * g.cs + (long long)y * g.rs + (long long)c * g.chs;
     float v = dct_rhs<LAP>(g, j, c, x, y, mg.ax == MIXED_PERIODIC, mg.ay == MIXED_PERIODIC);
-    if constexpr (SCR) v = screened_rhs(v, lam, j.d[o]);
-    if (x == 1 && mixed_low_d(mg.ax)) v -= j.b[o - g.cs];
-    if (y == 1 && mixed_low_d(mg.ay)) v -= j.b[o - g.rs];
-    if (x == g.W - 2 && mixed_high_d(mg.ax)) v -= j.b[o + g.cs];
-    if (y == g.H - 2 && mixed_high_d(mg.ay)) v -= j.b[o + g.rs];
+    // (a job without d or without b: both zero -- the preconditioner step of the weighted solve, sc_weighted_api.cpp, whose planes hold
+    // unknowns only and are homogeneous on the Dirichlet lines)
+    if constexpr (SCR) { if (j.d) v = screened_rhs(v, lam, j.d[o]); }
+    if (j.b) {
+        if (x == 1 && mixed_low_d(mg.ax)) v -= j.b[o - g.cs];
+        if (y == 1 && mixed_low_d(mg.ay)) v -= j.b[o - g.rs];
+        if (x == g.W - 2 && mixed_high_d(mg.ax)) v -= j.b[o + g.cs];
+        if (y == g.H - 2 && mixed_high_d(mg.ay)) v -= j.b[o + g.rs];
+    }
     return v;
 }
 
@@ -531,8 +524,9 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
         } else if (tstore) out[((size_t)p * n + at) * rows + r] = X;
         else out[((size_t)p * rows + r) * n + at] = X;
     }
-    if (MODE == 2) {
-        // the Dirichlet lines of out, boundary's bit for bit (out may be boundary: the same values again)
+    if (MODE == 2 && J.b) {
+        // the Dirichlet lines of out, boundary's bit for bit (out may be boundary: the same values again; a job without boundary -- the
+        // weighted solve's work planes -- has no such lines to write)
         const long long oc = (long long)c * g.chs, row = (long long)(y0 + r) * g.rs;
         if (tid == 0 && mixed_low_d(mg.ax)) J.out[row + oc] = J.b[row + oc];
         if (tid == 1 && mixed_high_d(mg.ax)) J.out[(long long)(g.W - 1) * g.cs + row + oc] = J.b[(long long)(g.W - 1) * g.cs + row + oc];

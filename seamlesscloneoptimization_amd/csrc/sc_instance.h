@@ -77,6 +77,17 @@ struct FftState {
     bool forked = false;                   // this solve has already put the second stream behind the main one (one fork per solve: both directions' tables and the eigenvalue tables ride on it)
 };
 
+// the weighted solve (sc_weighted_api.cpp): conjugate-gradient work planes [planes][WeightedGeo::stride] of float32 (q holds A p, then the
+// preconditioned residual z), the double partial sums, and the stop rule's mailbox: the per-plane ||r||^2 of iteration k goes to slot
+// k % RING of the pinned block with event k % RING behind it, and the host reads iteration k - LAG before it enqueues iteration k
+struct WeightedState {
+    enum { LAG = SC_WEIGHTED_POLL, RING = SC_WEIGHTED_POLL + 1 };
+    DevBuf u, r, p, q, w;
+    DevBuf red;                            // double: weight statistics | b.b | p.q | r.r | r.z of even / odd iterations (WEIGHTED_PARTS per plane each) | ||r||^2 per plane
+    DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane
+    hipEvent_t ev[RING]{};
+};
+
 struct MGLevel {
     Field U, F, T;   // correction, RHS, scratch (residual field); level 0 aliases the instance fields
     MGGeom g;        // geometry of this level and of its transfer to the next coarser one
@@ -224,6 +235,7 @@ struct Instance {
     RagState rag;
     DstState dst;
     FftState fft;
+    WeightedState wt;
     bool fft_lds_float = false, fft_lds_double = false;   // this instance's device has the FFT kernels opted in to > 64 KB of LDS (sc_fft.hip)
     // reductions / mailboxes
     DevBuf d_rects, h_rects;     // bounding boxes of a group of clones (sc_hip_run_device_batch): device, pinned

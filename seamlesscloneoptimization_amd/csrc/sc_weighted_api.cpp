@@ -1,0 +1,354 @@
+// sc_weighted_api.cpp -- the weighted solve on float32 images (sc_hip_weighted_check, sc_hip_weighted_device, sc_hip_weighted):
+//     minimise sum w (u - d)^2 + sum |grad u - g|^2,   i.e.   (A - W) u = div g - W d,   W = diag(w), w >= 0,
+// A the 5-point operator of sc_hip_poisson under every border kind (a Dirichlet frame, SC_POISSON_NEUMANN, SC_POISSON_FREE_*,
+// SC_POISSON_PERIODIC_*).
+//
+// A call: validation -> per chunk of at most SC_POISSON_MAX_PLANES planes
+//   1. the weights' statistics (one launch, one host read -- the call's one mandatory wait): per plane the sum of w and the number of
+//      weights that are negative or not finite.  A job with such a weight, or -- without any Dirichlet line -- with a channel of zero
+//      weight, gets SC_ERR_BAD_ARG and leaves the chunk; lambda-bar = precond_lambda, or the mean of w over the unknowns that remain.
+//   2. set-up: b = lap - w d less the neighbouring Dirichlet values, and w itself, onto compact work planes that hold the unknowns only
+//      (from here on every vector is homogeneous on the Dirichlet lines).
+//   3. u0 = M^-1 b, r = b - (A - W) u0, z = M^-1 r, p = z;  M = A - lambda-bar through direct_jobs_solve in its Laplacian form on the work
+//      planes: jobs without data term and without boundary (both mean zero there), under a PoissonGeo that addresses the planes' rows by
+//      pixel coordinates.  A frame on all four sides takes the same road, both axes of kind 0.
+//   4. the iteration (sc_weighted.hip): q = (A - W) p | u += alpha p, r -= alpha q | z = M^-1 r | r . z | p = z + beta p -- four launches
+//      of this file's and the preconditioner's three or five, nothing read by the host but the stop rule's norms, SC_WEIGHTED_POLL
+//      iterations late.
+//   5. u and the Dirichlet lines of boundary into the jobs' out.
+#include "sc_instance.h"
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+using namespace sc;
+
+namespace {
+
+constexpr int W_LAG = WeightedState::LAG, W_RING = WeightedState::RING;
+
+int weighted_validate(const sc_weighted_params *p, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
+    if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
+    if (!std::isfinite(p->precond_lambda)) { *why = "precond_lambda must be finite"; return SC_ERR_BAD_ARG; }
+    const sc_poisson_params pp{ p->kind, 0.f };
+    const int rc = poisson_validate(&pp, l, why);
+    if (rc) return rc;
+    if (!poisson_direct(p->kind) && !fft_supported(l->cols - 2, l->rows - 2, false)) {
+        *why = "a weighted solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side";
+        return SC_ERR_BAD_SIZE;
+    }
+    return SC_OK;
+}
+
+int weighted_instance_check(Instance *I, const sc_weighted_params *p, const sc_poisson_layout *l)
+{
+    const int method = I->opts.method;
+    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
+        I->err = "a weighted solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
+        return SC_ERR_BAD_ARG;
+    }
+    return direct_fp64_check(I, poisson_free_sides(p->kind), l, "a weighted solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis",
+                             poisson_periodic(p->kind));
+}
+
+int weighted_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *data, const float *w, const float *b,
+                          const float *out, const char **why)
+{
+    if (!data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
+    if (!w) { *why = "null weight pointer"; return SC_ERR_BAD_ARG; }
+    if (!aligned4(data) || !aligned4(w)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    return poisson_job_validate(kind, gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out, why);
+}
+
+struct WJob { PoissonJobDev j; const float *w; int *rc; };
+
+WJob dev_job(int kind, const float *gx, const float *gy, const float *lap, const float *data, const float *w, const float *b, float *out, int *rc)
+{
+    WJob o{ PoissonJobDev{ gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out }, w, rc };
+    o.j.d = data;
+    return o;
+}
+
+struct WCall { int kind; float tol; int max_iters; float plam; };
+
+struct ChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
+
+// One chunk of m same-size jobs.  Jobs whose weights do not pass get their code here and take no further part; the rest share one
+// iteration and one code (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call).
+int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jobs, int m, ChunkResult &res, int &job_errors)
+{
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
+    const WeightedGeo wg = weighted_geo(mg);
+    const bool lap = poisson_base(call.kind) == SC_POISSON_LAPLACIAN, no_dirichlet = poisson_no_dirichlet(call.kind);
+    const bool fp64 = (I->opts.flags & SC_FLAG_FFT_FP64) != 0;
+    const int nop = weighted_op_parts(wg);
+    WeightedState &S = I->wt;
+    hipStream_t s = I->stream;
+    int rc;
+    for (hipEvent_t &e : S.ev)
+        if (!e) SC_HIP(I, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // the partial sums: statistics (2 per part) | bb | pq | rr | rz[0] | rz[1] | rr_tot
+    const size_t all_planes = (size_t)g.C * m, per = all_planes * WEIGHTED_PARTS;
+    if ((rc = ensure(I, S.red, sizeof(double) * (per * 7 + all_planes), false))) return rc;
+    if ((rc = ensure_pinned(I, S.h_red, sizeof(double) * (per * 2 + per + all_planes * W_RING)))) return rc;
+    double *d_stats = (double *)S.red.p, *d_bb = d_stats + 2 * per, *d_pq = d_bb + per, *d_rr = d_pq + per;
+    double *d_rz[2] = { d_rr + per, d_rr + 2 * per }, *d_tot = d_rr + 3 * per;
+    double *h_stats = (double *)S.h_red.p, *h_bb = h_stats + 2 * per, *h_tot = h_bb + per;
+
+    // 1. the weights
+    std::vector<PoissonJobDev> dj(m);
+    std::vector<const float *> dw(m);
+    for (int k = 0; k < m; ++k) { dj[k] = jobs[k].j; dw[k] = jobs[k].w; }
+    launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * 2 * per, hipMemcpyDeviceToHost, s));
+    SC_HIP(I, hipStreamSynchronize(s));
+    std::vector<WJob> live;
+    double wsum = 0.0;
+    for (int k = 0; k < m; ++k) {
+        double job_sum = 0.0;
+        bool bad = false, empty = false;
+        for (int c = 0; c < g.C; ++c) {
+            const double *st = h_stats + ((size_t)k * g.C + c) * WEIGHTED_PARTS * 2;
+            double sum = 0.0;
+            for (int i = 0; i < nop; ++i) { sum += st[2 * i]; bad = bad || st[2 * i + 1] != 0.0; }
+            empty = empty || !(sum > 0.0);
+            job_sum += sum;
+        }
+        if (bad || !std::isfinite(job_sum)) {
+            *jobs[k].rc = SC_ERR_BAD_ARG;
+            if (!job_errors++) I->err = "a weight is negative or not finite";
+        } else if (no_dirichlet && empty) {
+            *jobs[k].rc = SC_ERR_BAD_ARG;
+            if (!job_errors++) I->err = "no data weight and no Dirichlet line";
+        } else {
+            live.push_back(jobs[k]);
+            wsum += job_sum;
+        }
+    }
+    const int mv = (int)live.size(), planes = g.C * mv;
+    res = ChunkResult();
+    if (!mv) return SC_OK;
+    const double n_unknowns = (double)wg.nx * (double)wg.ny * (double)planes;
+    const float lam = call.plam > 0.f ? call.plam : (float)(wsum / n_unknowns);      // (0: no weight anywhere, under Dirichlet lines -- the unscreened solve)
+    for (int k = 0; k < mv; ++k) { dj[k] = live[k].j; dw[k] = live[k].w; }
+
+    // 2. the work planes
+    const size_t plane_bytes = sizeof(float) * (size_t)wg.stride * planes;
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w })
+        if ((rc = ensure(I, *b, plane_bytes, false))) return rc;
+    float *U = (float *)S.u.p, *R = (float *)S.r.p, *P = (float *)S.p.p, *Q = (float *)S.q.p, *Wc = (float *)S.w.p, *Z = Q;
+    launch_weighted_setup(g, wg, lap, dj.data(), dw.data(), mv, R, Wc, d_bb, s);
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipMemcpyAsync(h_bb, d_bb, sizeof(double) * (size_t)planes * WEIGHTED_PARTS, hipMemcpyDeviceToHost, s));
+
+    // 3. the preconditioner: (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the
+    // pointers are moved back by the first unknown's offset, and only unknowns are ever addressed (no boundary: no Dirichlet line is
+    // read or written)
+    const PoissonGeo pg{ g.W, g.H, g.C, 1, (long long)wg.nx, wg.stride };
+    const long long shift = (long long)wg.x0 + (long long)wg.y0 * wg.nx;
+    std::vector<PoissonJobDev> pj(mv);
+    auto precond = [&](const float *in, float *out) -> int {
+        for (int k = 0; k < mv; ++k) {
+            const long long o = (long long)k * g.C * wg.stride - shift;
+            pj[k] = PoissonJobDev{ nullptr, nullptr, in + o, nullptr, out + o };
+        }
+        return direct_jobs_solve(I, pg, mg, true, pj.data(), mv, fp64, lam);
+    };
+    // the stop rule's mailbox: iteration k's norms into slot k % W_RING, event k % W_RING behind them
+    auto post_norms = [&](int k) -> int {
+        SC_HIP(I, hipMemcpyAsync(h_tot + (size_t)(k % W_RING) * planes, d_tot, sizeof(double) * planes, hipMemcpyDeviceToHost, s));
+        SC_HIP(I, hipEventRecord(S.ev[k % W_RING], s));
+        return SC_OK;
+    };
+    const double tol = call.tol > 0.f ? (double)call.tol : 1e-5;
+    const int max_iters = call.max_iters > 0 ? call.max_iters : 200;
+    std::vector<double> bb(planes, 0.0);
+    bool have_bb = false;
+    // the worst plane's ||r|| / ||b|| of iteration k (waits for its event)
+    auto read_norms = [&](int k, double &worst) -> int {
+        SC_HIP(I, hipEventSynchronize(S.ev[k % W_RING]));
+        if (!have_bb) {          // (copied in front of every slot)
+            for (int p = 0; p < planes; ++p)
+                for (int i = 0; i < nop; ++i) bb[p] += h_bb[(size_t)p * WEIGHTED_PARTS + i];
+            have_bb = true;
+        }
+        worst = 0.0;
+        const double *t = h_tot + (size_t)(k % W_RING) * planes;
+        for (int p = 0; p < planes; ++p) {
+            const double rel = bb[p] > 0.0 ? std::sqrt(t[p] / bb[p]) : (t[p] > 0.0 ? INFINITY : 0.0);
+            worst = rel > worst || rel != rel ? rel : worst;
+        }
+        return SC_OK;
+    };
+    if ((rc = precond(R, U))) return rc;                                           // u0 = M^-1 b
+    launch_weighted_op(wg, planes, true, U, Wc, R, d_rr, s);                       // r = b - (A - W) u0
+    if ((rc = precond(R, Z))) return rc;
+    launch_weighted_dot(wg, planes, R, Z, d_rz[0], d_rr, nop, d_tot, s);
+    if ((rc = post_norms(0))) return rc;
+    launch_weighted_dir(wg, planes, P, Z, d_rz[0], nullptr, s);                    // p = z
+    SC_HIP(I, hipGetLastError());
+
+    // 4. the iteration
+    int iters = 0;
+    bool seen = false;
+    double worst = 0.0;
+    for (int k = 1; k <= max_iters; ++k) {
+        if (k - W_LAG >= 0) {
+            if ((rc = read_norms(k - W_LAG, worst))) return rc;
+            if (worst <= tol) { seen = true; break; }
+            if (worst != worst) break;                                             // NaN: nothing more to gain
+        }
+        launch_weighted_op(wg, planes, false, P, Wc, Q, d_pq, s);
+        launch_weighted_update(wg, planes, U, R, P, Q, d_rz[(k - 1) & 1], d_pq, d_rr, s);
+        if ((rc = precond(R, Z))) return rc;
+        launch_weighted_dot(wg, planes, R, Z, d_rz[k & 1], d_rr, wg.eparts, d_tot, s);
+        if ((rc = post_norms(k))) return rc;
+        launch_weighted_dir(wg, planes, P, Z, d_rz[k & 1], d_rz[(k - 1) & 1], s);
+        SC_HIP(I, hipGetLastError());
+        iters = k;
+    }
+    // the norms not yet read: an iteration at or behind the one that was seen may have met tol as well; the last one is reported
+    for (int k = std::max(0, iters - W_LAG + 1); k <= iters; ++k) {
+        if ((rc = read_norms(k, worst))) return rc;
+        if (worst <= tol) seen = true;
+    }
+    res.iters = iters;
+    res.rel = worst;
+    res.converged = seen;
+
+    // 5. the output
+    launch_weighted_out(g, wg, dj.data(), mv, U, s);
+    SC_HIP(I, hipGetLastError());
+    const int code = res.converged ? SC_OK : SC_ERR_NOT_CONVERGED;
+    for (int k = 0; k < mv; ++k) *live[k].rc = code;
+    return code;
+}
+
+// The validated jobs of a call through chunks.  Returns the worst code (job errors of the weights included); a HIP error (or any other
+// error of a chunk) marks every job not yet finished, and after a HIP error the finished ones too.
+int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, std::vector<WJob> &jobs, bool timed)
+{
+    CallScope scope{ I };
+    const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
+    Geo geo{ 0, 0, g.W, g.H, 0, 0 };
+    fill_info_geo(I, geo);
+    I->stage_marks = false;          // (direct_jobs_solve's marks: a call of many solves records none)
+    if (timed) SC_HIP(I, hipEventRecord(I->ev[0], I->stream));
+    const int per = std::max(1, SC_POISSON_MAX_PLANES / g.C), nv = (int)jobs.size();
+    int worst = SC_OK, job_errors = 0, sweeps = 0;
+    bool converged = true;
+    double rel = 0.0;
+    for (int i0 = 0; i0 < nv; i0 += per) {
+        const int m = std::min(per, nv - i0);
+        ChunkResult res;
+        const int rc = weighted_chunk(I, call, g, jobs.data() + i0, m, res, job_errors);
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) {
+            for (int k = i0; k < nv; ++k) *jobs[k].rc = rc;
+            if (rc == SC_ERR_HIP)
+                for (int k = 0; k < i0; ++k) *jobs[k].rc = rc;
+            return rc;
+        }
+        worst = worse(worst, rc);
+        sweeps = std::max(sweeps, res.iters);
+        converged = converged && res.converged;
+        rel = std::max(rel, res.rel);
+        I->info.group_members = m > 1 ? m : 0;
+    }
+    if (job_errors) worst = worse(worst, SC_ERR_BAD_ARG);
+    I->info.method = SC_METHOD_FFT;
+    I->info.sweeps = sweeps;
+    I->info.converged = converged ? 1 : 0;
+    I->info.rel_residual = rel;
+    I->info.sweep_launches = sweeps;
+    I->info.ms_mask = I->info.ms_pre = I->info.ms_post = 0.f;
+    I->info.ms_solve = I->info.ms_device_total = I->info.ms_call = 0.f;
+    if (timed) {
+        SC_HIP(I, hipEventRecord(I->ev[7], I->stream));
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        I->info.ms_solve = I->info.ms_device_total = I->info.ms_call = ev_ms(I->ev[0], I->ev[7]);
+    }
+    return worst;
+}
+
+} // namespace
+
+extern "C" {
+
+int sc_hip_weighted_check(const sc_weighted_params *p, const sc_poisson_layout *l)
+{
+    return weighted_validate(p, l, nullptr);
+}
+
+int sc_hip_weighted_device(void *inst, const sc_weighted_params *p, const sc_poisson_layout *l, sc_weighted_job *jobs, int n, bool bSync)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    const char *why = "";
+    if ((rc = weighted_validate(p, l, &why))) { I->err = why; return rc; }
+    if ((rc = weighted_instance_check(I, p, l))) return rc;
+    const int kind = poisson_norm_kind(p->kind);
+    if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
+    int worst = SC_OK;
+    std::vector<WJob> wj;
+    for (int i = 0; i < n; ++i) {
+        sc_weighted_job &j = jobs[i];
+        const int vrc = weighted_job_validate(kind, j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, &why);
+        if (vrc != SC_OK) {
+            j.rc = vrc;
+            if (worst == SC_OK) { worst = vrc; I->err = why; }
+            continue;
+        }
+        j.rc = SC_ERR_HIP;          // until its chunk has run
+        wj.push_back(dev_job(kind, j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, &j.rc));
+    }
+    if (wj.empty()) return worst;
+    I->info.ms_h2d = I->info.ms_d2h = 0.f;
+    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, wj, bSync);
+    return worse(worst, rc);
+}
+
+int sc_hip_weighted(void *inst, const sc_weighted_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                    const float *lap, const float *data, const float *weight, const float *boundary, float *out)
+{
+    Instance *I;
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    const char *why = "";
+    if ((rc = weighted_validate(p, l, &why))) { I->err = why; return rc; }
+    if ((rc = weighted_instance_check(I, p, l))) return rc;
+    const int kind = poisson_norm_kind(p->kind);
+    if ((rc = weighted_job_validate(kind, gx, gy, lap, data, weight, boundary, out, &why))) { I->err = why; return rc; }
+    // one device block, as sc_hip_screened's, with the weights' span behind the data's
+    const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
+    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
+    if (poisson_no_dirichlet(kind)) boundary = nullptr;
+    const bool b_is_d = boundary == data, own_b = boundary && !b_is_d, in_place = out == data || (boundary && out == boundary);
+    const int n_in = guidance ? 2 : 1, slots = n_in + 2 + (own_b ? 1 : 0) + (in_place ? 0 : 1);
+    if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
+    uint8_t *d = (uint8_t *)I->d_pois.p;
+    float *d_in0 = (float *)d, *d_in1 = guidance ? (float *)(d + slot) : nullptr;
+    float *d_d = (float *)(d + slot * n_in), *d_w = (float *)(d + slot * (n_in + 1));
+    float *d_b = own_b ? (float *)(d + slot * (n_in + 2)) : (boundary ? d_d : nullptr);
+    float *d_out = !in_place ? (float *)(d + slot * (slots - 1)) : (out == data ? d_d : d_b);
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
+    if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
+    if ((rc = upload_rows(I, I->h_in, d_d, bytes, (const uint8_t *)data, bytes, bytes, 1))) return rc;
+    if ((rc = upload_rows(I, I->h_out, d_w, bytes, (const uint8_t *)weight, bytes, bytes, 1))) return rc;      // (h_out: free until the download)
+    if (own_b && (rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
+    int job_rc = SC_ERR_HIP;
+    std::vector<WJob> wj{ dev_job(kind, guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_d, d_w, d_b, d_out, &job_rc) };
+    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, wj, true);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };
+    return poisson_download(I, l, d_out, out, t, rc);
+}
+
+} // extern "C"

@@ -449,6 +449,115 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
     return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
 
 
+def weighted_solve(data, weight, gx=None, gy=None, laplacian=None, boundary=None, neumann=True, free_sides=None, periodic="", tol=None,
+                   max_iters=None, precond_lambda=None, gpu_id=0, **solver):
+    """Weighted solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
+        sum weight (u - data)^2 + sum |grad u - (gx, gy)|^2           (or with the divergence of the guidance given as laplacian;
+    neither: zero guidance), i.e. (A - W) u = div g - W data, W = diag(weight), weight >= 0 of data's shape or H x W (broadcast over
+    the channels).  Borders as screened_solve's: neumann (the default), free_sides, periodic; boundary on the remaining Dirichlet lines.
+    Conjugate gradients on the GPU, preconditioned by the screened direct solve with the mean weight (precond_lambda overrides it);
+    stops at ||r|| <= tol ||b|| (default 1e-5) or after max_iters (default 200) iterations, which raises SC_ERR_NOT_CONVERGED.  Without
+    any Dirichlet line a channel needs a positive weight somewhere.  flags=SC_FLAG_FFT_FP64: the preconditioner in double."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.weighted(data, weight, gx=gx, gy=gy, lap=laplacian, boundary=boundary, neumann=neumann, free_sides=free_sides,
+                             periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0, precond_lambda=precond_lambda or 0.0)
+    finally:
+        inst.destroy()
+
+
+def weighted_solve_batch(datas, weights, gxs=None, gys=None, laplacians=None, boundaries=None, neumann=True, free_sides=None, periodic="",
+                         tol=None, max_iters=None, precond_lambda=None, gpu_id=0, **solver):
+    """weighted_solve over a list of same-shape problems through ONE device-resident call (sc_hip_weighted_device): one copy in, one
+    copy out, the problems iterated as one field of n x C planes (chunks of at most SC_POISSON_MAX_PLANES planes).  Every plane has its
+    own step sizes, but the stop is joint and the automatic preconditioner constant is the chunk's mean weight: a member agrees with its
+    solo solve to the stop rule's error.  Neither gxs, gys nor laplacians: zero guidance.  Returns a list of NEW arrays."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
+    ds, ws = list(datas), list(weights)
+    n = len(ds)
+    if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None):
+        raise ValueError("give gxs and gys, or laplacians, or neither")
+    fields = [ws] + ([gxs, gys] if gxs is not None else [laplacians] if laplacians is not None else [])
+    if not no_boundary:
+        if boundaries is None:
+            raise ValueError("a weighted solve with a Dirichlet line needs boundaries")
+        fields = fields + [boundaries]
+    for f in fields:
+        if len(f) != n:
+            raise ValueError("one weight, one guidance field (or laplacian) and, with a Dirichlet line, one boundary per data term")
+    if not ds:
+        return []
+    checked = []
+    for k in range(n):
+        b = None if no_boundary else boundaries[k]
+        kind, d, w, gx, gy, lap, b, _ = capi.weighted_arrays(ds[k], ws[k], None if gxs is None else gxs[k], None if gys is None else gys[k],
+                                                             None if laplacians is None else laplacians[k], b, neumann=neumann,
+                                                             free_sides=free_sides, periodic=periodic)
+        if d.shape != ds[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        arrays = ([gx, gy] if gx is not None else [lap]) + [d, w] + ([] if b is None else [b])
+        checked.append([np.ascontiguousarray(a) for a in arrays])
+    shape = ds[0].shape
+    slot = (checked[0][0].nbytes + 255) // 256 * 256
+    per = len(checked[0])
+    in_bytes = slot * per * n
+    staged = np.zeros(in_bytes // 4, np.float32)
+    for k, arrays in enumerate(checked):
+        for i, a in enumerate(arrays):
+            o = (k * per + i) * slot // 4
+            staged[o:o + a.size] = a.reshape(-1)
+    layout = capi.poisson_layout_of(checked[0][0])
+    guidance = gxs is not None
+    inst = capi.Instance(gpu_id)
+    dev = None
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        dev = inst.malloc(in_bytes + slot * n)
+        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
+        jobs = capi.Instance.make_weighted_jobs(n)
+        for k, j in enumerate(jobs):
+            base = dev + k * per * slot
+            n_in = 2 if guidance else 1
+            if guidance:
+                j.gx, j.gy = base, base + slot
+            else:
+                j.lap = base
+            j.data, j.weight = base + n_in * slot, base + (n_in + 1) * slot
+            j.boundary = None if no_boundary else base + (per - 1) * slot
+            j.out = dev + in_bytes + k * slot
+        rc = inst.weighted_device(capi.WeightedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0)), layout, jobs)
+        inst._check(rc)
+        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
+    finally:
+        if dev is not None:
+            inst.free(dev)
+        inst.destroy()
+    return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
+
+
+def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, **solver):
+    """Fills a float32 image (H x W or H x W x C) from the pixels where known_mask (H x W, anything truthy) is set: the weighted solve
+    with weight = strength on the mask and 0 elsewhere, data = values, under reflecting borders, with zero guidance (a membrane through
+    the known pixels) or image_gradients = (gx, gy), forward differences the result should have.  strength weighs closeness to the known
+    values against the guidance: large values pin them.  Returns a NEW array."""
+    if not isinstance(values, np.ndarray) or values.dtype != np.float32:
+        raise TypeError("values must be a float32 numpy array")
+    m = np.asarray(known_mask)
+    if m.shape != values.shape[:2]:
+        raise ValueError(f"known_mask has shape {m.shape}, the image {values.shape[:2]}")
+    if not np.isfinite(strength) or not strength > 0:
+        raise ValueError("strength must be finite and > 0")
+    w = np.where(m.astype(bool), np.float32(strength), np.float32(0)).astype(np.float32)
+    gx, gy = (None, None) if image_gradients is None else image_gradients
+    return weighted_solve(np.where(m.astype(bool).reshape(m.shape + (1,) * (values.ndim - 2)), values, np.float32(0)).astype(np.float32), w,
+                          gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
+
+
 def gradient_filter(image, gain, lam, neumann=True, gpu_id=0, free_sides=None, periodic="", **solver):
     """Gradient-domain filtering of a float32 image (H x W or H x W x C): the image whose forward differences are `gain` times the
     input's while it stays close to the input, lam weighing the closeness -- screened_solve with data = image, guidance = gain x the

@@ -1,0 +1,298 @@
+"""GPU tests of the weighted solve (sc_hip_weighted, sc_hip_weighted_device) through capi:
+
+    (A - W) u = lap - w d,   W = diag(w), w >= 0,   A the 5-point operator under every border kind.
+
+1. against the dense float64 solve (tests/weighted_np.py) at 33 x 47, 16 x 5 and 2 x 7 pixels, five border kinds, three kinds of
+   weights: ERR and RES within tests/weighted_bounds.py's bounds, the iteration count within twice the reference iteration's plus the
+   polling period.  (A frame around 2 x 7 pixels leaves no unknown: that one case holds the call to its refusal instead.)
+2. a constant weight: at most 1 + SC_WEIGHTED_POLL iterations, and screened_solve's answer within the screened bounds.
+3. layouts: HWC, CHW with padded rows, RGBA-strided C = 3 inside guard bands, on device arrays: nothing but the named elements is
+   written, the Dirichlet lines are boundary's bits, out may be data or boundary.
+4. a batch of five problems with different weights: each within ERR of its own exact solution; two calls, the same bytes.
+5. codes: a negative weight in one job of three, zero weights with and without Dirichlet lines, a budget that ends first.
+6. SC_FLAG_FFT_FP64, and the Python surface (a 2-D weight, interpolate_constraints)."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi, seamless_clone
+
+import periodic_np
+import screened_bounds
+import screened_np
+import weighted_bounds as wb
+import weighted_np
+
+pytestmark = pytest.mark.gpu
+
+L = capi.SC_POISSON_LAPLACIAN
+SENTINEL = -7.25
+POLL = capi.SC_WEIGHTED_POLL
+
+
+@pytest.fixture(scope="module")
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def configure(inst, flags=0):
+    d = inst.default_opts()
+    inst.set_solver(**{k: getattr(d, k) for k, _ in capi.SolverOpts._fields_})
+    inst.set_solver(flags=flags)
+
+
+def solve(inst, sides, periodic, data, weight, lap, boundary, **kw):
+    b = boundary if weighted_np.has_dirichlet(sides, periodic) else None
+    return inst.weighted(data, weight, lap=lap, boundary=b, free_sides=sides, periodic=periodic, **kw)
+
+
+_yard = {}
+
+
+def yardstick(border, size, wkind):
+    """the references of one input, computed once"""
+    key = (border, size, wkind)
+    if key not in _yard:
+        _, sides, periodic = next(b for b in wb.BORDERS if b[0] == border)
+        data, weight, lap, boundary = wb.make_input(size[0], size[1], 3, wkind)
+        _yard[key] = (wb.Yardstick(sides, periodic, weight, data, lap, boundary), data, weight, lap, boundary, sides, periodic)
+    return _yard[key]
+
+
+# ---- 1. against the exact solve ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wkind", wb.WEIGHTS)
+@pytest.mark.parametrize("size", wb.SIZES, ids=lambda s: f"{s[1]}x{s[0]}")
+@pytest.mark.parametrize("border", [b[0] for b in wb.BORDERS])
+def test_against_the_exact_solve(inst, border, size, wkind):
+    configure(inst)
+    H, W = size
+    if border == "frame" and min(H, W) < 3:
+        # no unknown between the Dirichlet lines: the call refuses, on the host and on the instance alike
+        data, weight, lap, boundary = wb.make_input(H, W, 3, wkind)
+        assert capi.weighted_check(L, layout=capi.poisson_layout_of(data)) == capi.SC_ERR_BAD_SIZE
+        with pytest.raises(capi.SeamlessCloneError) as e:
+            inst.weighted(data, weight, lap=lap, boundary=boundary, free_sides="")
+        assert e.value.code == capi.SC_ERR_BAD_SIZE
+        return
+    y, data, weight, lap, boundary, sides, periodic = yardstick(border, size, wkind)
+    blk = weighted_np.unknowns(sides, periodic, H, W)
+    if wkind == "sparse":
+        assert (weight[blk].reshape(-1, 3).sum(0) >= 1).all(), "the seed must set a pixel in every channel"
+    out = solve(inst, sides, periodic, data, weight, lap, boundary)
+    info = inst.info()
+    bad, err, res = y.check(out)
+    print(f"WEIGHTED {border} {W}x{H} {wkind}: ERR {err:.3g} (pcg_f32 {y.err32:.3g}) RES {res:.3g} (pcg_f32 {y.res32:.3g}) "
+          f"sweeps {info.sweeps} (pcg_f32 {y.iters32}) rel {info.rel_residual:.3g}")
+    assert (info.method, info.converged, info.W, info.H) == (capi.SC_METHOD_FFT, 1, W, H)
+    assert info.rel_residual <= 1e-5
+    assert info.sweeps <= y.max_sweeps(), (info.sweeps, y.iters32)
+    assert not bad, bad
+    if weighted_np.has_dirichlet(sides, periodic):
+        m = periodic_np.dirichlet_mask(sides, periodic, H, W)
+        assert np.array_equal(out[m], boundary[m])
+
+
+# ---- 2. a constant weight is the screened solve -----------------------------------------------------------------------------------
+def test_constant_weight_ties_to_the_screened_solve(inst):
+    configure(inst)
+    H, W = 47, 33
+    data, _, lap, _ = wb.make_input(H, W, 3, "constant")
+    weight = np.full((H, W, 3), 0.3, np.float32)
+    out = inst.weighted(data, weight, lap=lap, neumann=True)
+    info = inst.info()
+    assert info.converged == 1 and info.sweeps <= 1 + POLL, info.sweeps
+    ys = screened_bounds.Yardstick(0.3, data, lap)
+    bad, err, res = ys.check(out, False)
+    print(f"WEIGHTED constant 0.3: ERR {err:.3g} RES {res:.3g} against the screened bounds, sweeps {info.sweeps}")
+    assert not bad, bad
+    ref = inst.screened(data, lap=lap, lam=0.3, neumann=True)
+    assert not ys.check(ref, False)[0]
+
+
+# ---- 3. layouts -----------------------------------------------------------------------------------------------------------------
+def _layout_views(name, H, W):
+    """(backing array filled with SENTINEL, the H x W x 3 view of it)"""
+    if name == "hwc":
+        back = np.full((H, W, 3), SENTINEL, np.float32)
+        return back, back
+    if name == "chw_padded":
+        back = np.full((3, H, W + 5), SENTINEL, np.float32)
+        return back, back[:, :, :W].transpose(1, 2, 0)
+    back = np.full((H + 4, W, 4), SENTINEL, np.float32)          # RGBA-strided C = 3 inside guard bands of two rows
+    return back, back[2:-2, :, :3]
+
+
+@pytest.mark.parametrize("alias", ["none", "data", "boundary"])
+@pytest.mark.parametrize("layout", ["hwc", "chw_padded", "rgba_guarded"])
+def test_layouts_write_only_named_elements(inst, layout, alias):
+    configure(inst)
+    H, W = 23, 17
+    sides, periodic = "lt", ""                  # Dirichlet lines right and bottom
+    data, weight, lap, boundary = wb.make_input(H, W, 3, "loguniform", seed=3)
+    want = weighted_np.solve_exact(sides, periodic, weight, data, lap, boundary)
+    arrays = {}
+    for name, a in (("data", data), ("weight", weight), ("lap", lap), ("boundary", boundary), ("out", None)):
+        back, view = _layout_views(layout, H, W)
+        if a is not None:
+            view[...] = a
+        arrays[name] = (back, view)
+    lay = capi.poisson_layout_of(arrays["data"][1])
+    off = lambda name: arrays[name][1].__array_interface__["data"][0] - arrays[name][0].__array_interface__["data"][0]
+    dev = {name: inst.to_device(back) for name, (back, _) in arrays.items()}
+    try:
+        jobs = capi.Instance.make_weighted_jobs(1)
+        j = jobs[0]
+        j.lap, j.data, j.weight, j.boundary = (dev[n] + off(n) for n in ("lap", "data", "weight", "boundary"))
+        target = "out" if alias == "none" else alias
+        j.out = dev[target] + off(target)
+        kind = L | capi.border_bits(sides, False, periodic)
+        rc = inst.weighted_device(capi.WeightedParams(kind, 0.0, 0, 0.0), lay, jobs)
+        assert rc == capi.SC_OK and j.rc == capi.SC_OK
+        got_back = inst.from_device(dev[target], arrays[target][0].shape, np.float32)
+        others = {n: inst.from_device(dev[n], arrays[n][0].shape, np.float32) for n in arrays if n != target}
+    finally:
+        for p in dev.values():
+            inst.free(p)
+    for n, a in others.items():
+        assert np.array_equal(a, arrays[n][0]), f"{n} was written"
+    # the named elements of the target hold the solution, everything else of its backing array is as it was
+    probe = arrays[target][0].copy()
+    view = _view_of(probe, layout, H, W)
+    got = _view_of(got_back, layout, H, W).copy()
+    view[...] = got
+    assert np.array_equal(probe, got_back), "padding, the 4th slot or a guard band was written"
+    m = periodic_np.dirichlet_mask(sides, periodic, H, W)
+    assert np.array_equal(got[m], boundary[m]), "Dirichlet lines must be boundary's bits"
+    err = float(np.abs(got.astype(np.float64) - want).max()) / float(np.abs(want).max())
+    assert err <= 1e-4, err          # (the sharp bound is item 1's; here: the solution is in place)
+
+
+def _view_of(back, layout, H, W):
+    if layout == "hwc":
+        return back
+    if layout == "chw_padded":
+        return back[:, :, :W].transpose(1, 2, 0)
+    return back[2:-2, :, :3]
+
+
+# ---- 4. batches -----------------------------------------------------------------------------------------------------------------
+def test_batch_members_and_repeatability(inst):
+    H, W, n = 23, 17, 5
+    kinds = ["constant", "loguniform", "sparse", "loguniform", "sparse"]
+    probs = [wb.make_input(H, W, 3, kinds[k], seed=10 + k) for k in range(n)]
+    for k in range(n):
+        assert (probs[k][1].reshape(-1, 3).sum(0) > 0).all()
+    runs = [seamless_clone.weighted_solve_batch([p[0] for p in probs], [p[1] for p in probs], laplacians=[p[2] for p in probs], neumann=True)
+            for _ in range(2)]
+    for a, b in zip(*runs):
+        assert a.tobytes() == b.tobytes(), "two identical calls must give identical bytes"
+    # the reference iteration of a member runs under the preconditioner the library gives it: the chunk's mean weight
+    lam = np.float32(np.mean([p[1].astype(np.float64).mean() for p in probs]))
+    for k, (data, weight, lap, boundary) in enumerate(probs):
+        y = wb.Yardstick("lrtb", "", weight, data, lap, None, precond_lambda=lam)
+        err, res = y.measure(runs[0][k])
+        eb = max(wb.ERR_FACTOR * y.err32, wb.ERR_FLOOR)
+        print(f"WEIGHTED batch member {k} ({kinds[k]}): ERR {err:.3g} (bound {eb:.3g})")
+        assert err <= eb, (k, err, eb)
+
+
+# ---- 5. codes -------------------------------------------------------------------------------------------------------------------
+def test_negative_weight_fails_its_job_only(inst):
+    configure(inst)
+    H, W = 23, 17
+    probs = [wb.make_input(H, W, 3, "loguniform", seed=20 + k) for k in range(3)]
+    probs[1][1][5, 7, 1] = -0.5
+    lay = capi.poisson_layout_of(probs[0][0])
+    dev = []
+    try:
+        jobs = capi.Instance.make_weighted_jobs(3)
+        for k, (data, weight, lap, _) in enumerate(probs):
+            ptrs = [inst.to_device(a) for a in (lap, data, weight, np.full((H, W, 3), SENTINEL, np.float32))]
+            dev += ptrs
+            jobs[k].lap, jobs[k].data, jobs[k].weight, jobs[k].out = ptrs
+        rc = inst.weighted_device(capi.WeightedParams(L | capi.SC_POISSON_NEUMANN, 0.0, 0, 0.0), lay, jobs, allow_job_errors=True)
+        assert rc == capi.SC_ERR_BAD_ARG
+        assert [j.rc for j in jobs] == [capi.SC_OK, capi.SC_ERR_BAD_ARG, capi.SC_OK]
+        outs = [inst.from_device(jobs[k].out, (H, W, 3), np.float32) for k in range(3)]
+    finally:
+        for p in dev:
+            inst.free(p)
+    assert (outs[1] == SENTINEL).all(), "a refused job must not be written"
+    for k in (0, 2):
+        data, weight, lap, _ = probs[k]
+        want = weighted_np.solve_exact("lrtb", "", weight, data, lap)
+        assert float(np.abs(outs[k] - want).max()) / float(np.abs(want).max()) <= 1e-4
+
+
+def test_zero_weights(inst):
+    configure(inst)
+    H, W = 23, 17
+    data, _, lap, boundary = wb.make_input(H, W, 3, "constant", seed=30)
+    zero = np.zeros((H, W, 3), np.float32)
+    with pytest.raises(capi.SeamlessCloneError) as e:
+        inst.weighted(data, zero, lap=lap, neumann=True)
+    assert e.value.code == capi.SC_ERR_BAD_ARG and "no data weight and no Dirichlet line" in str(e.value)
+    out = inst.weighted(data, zero, lap=lap, boundary=boundary, free_sides="")
+    assert inst.info().converged == 1
+    ref = inst.poisson(boundary, lap=lap, free_sides="")
+    want = periodic_np.solve_exact("", "", 0.0, None, lap, boundary)
+    R = float(np.abs(want).max())
+    e_out, e_ref = float(np.abs(out - want).max()) / R, float(np.abs(ref - want).max()) / R
+    print(f"WEIGHTED zero weights under a frame: ERR {e_out:.3g}, poisson_solve {e_ref:.3g}")
+    assert e_out <= 4e-3 and e_ref <= 4e-3          # test_gpu_poisson.py's bound for the float32 direct solve
+    assert np.array_equal(out[periodic_np.dirichlet_mask("", "", H, W)], boundary[periodic_np.dirichlet_mask("", "", H, W)])
+
+
+def test_budget_ends_first(inst):
+    configure(inst)
+    H = W = 64
+    data, _, lap, _ = wb.make_input(H, W, 1, "constant", seed=40)
+    weight = wb.weights("halfplane", (H, W, 1), 0)
+    out = inst.weighted(data, weight, lap=lap, neumann=True, max_iters=3, allow_not_converged=True)
+    info = inst.info()
+    with pytest.raises(capi.SeamlessCloneError) as e:
+        inst.weighted(data, weight, lap=lap, neumann=True, max_iters=3)
+    assert e.value.code == capi.SC_ERR_NOT_CONVERGED
+    assert np.isfinite(out).all() and info.converged == 0 and info.sweeps == 3 and info.rel_residual > 1e-5
+
+
+# ---- 6. double preconditioner, the Python surface ---------------------------------------------------------------------------------
+def test_fp64_preconditioner(inst):
+    configure(inst, capi.SC_FLAG_FFT_FP64)
+    try:
+        y, data, weight, lap, boundary, sides, periodic = yardstick("free_lt", (47, 33), "loguniform")
+        out = solve(inst, sides, periodic, data, weight, lap, boundary)
+        bad, err, res = y.check(out)
+        print(f"WEIGHTED fp64 preconditioner: ERR {err:.3g} RES {res:.3g} sweeps {inst.info().sweeps}")
+        assert not bad, bad
+        assert inst.info().sweeps <= y.max_sweeps()
+    finally:
+        configure(inst)
+
+
+def test_python_surface():
+    H, W = 23, 17
+    data, weight, lap, _ = wb.make_input(H, W, 3, "loguniform", seed=50)
+    w2 = np.ascontiguousarray(weight[:, :, 0])
+    a = seamless_clone.weighted_solve(data, w2, laplacian=lap)
+    b = seamless_clone.weighted_solve(data, np.repeat(w2[:, :, None], 3, 2), laplacian=lap)
+    assert a.tobytes() == b.tobytes()
+    # a linear ramp from its two end columns
+    ramp = np.tile(np.linspace(-1.0, 2.0, W, dtype=np.float32)[None, :, None], (H, 1, 2))
+    mask = np.zeros((H, W), bool)
+    mask[:, 0] = mask[:, -1] = True
+    strength = 4.0
+    got = seamless_clone.interpolate_constraints(ramp, mask, strength=strength)
+    w = np.where(mask[:, :, None], np.float32(strength), np.float32(0)) * np.ones((1, 1, 2), np.float32)
+    d = np.where(mask[:, :, None], ramp, np.float32(0)).astype(np.float32)
+    y = wb.Yardstick("lrtb", "", w.astype(np.float32), d, np.zeros_like(d), None)
+    err, _ = y.measure(got)
+    eb = max(wb.ERR_FACTOR * y.err32, wb.ERR_FLOOR)
+    print(f"WEIGHTED interpolate_constraints: ERR {err:.3g} (bound {eb:.3g}), max |want - ramp| {np.abs(y.want - ramp).max():.3g}")
+    assert err <= eb
+    # the exact minimiser is a ramp between the end columns, which give way by (its slope) / strength at most: strength (u - d) there
+    # balances the one difference across the column's inner edge, and the membrane's slope is below the data's
+    assert np.abs(y.want - ramp).max() <= (3.0 / (W - 1)) / strength

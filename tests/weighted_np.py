@@ -1,0 +1,179 @@
+"""The test side's restatement of the weighted solve (sc_hip_weighted*), numpy only.
+
+A problem's borders are (sides, periodic) as in periodic_np: `sides` names the sides WITHOUT a Dirichlet line, `periodic` the axes
+that wrap.  Per channel the library solves
+    (A - W) u = lap - w d        at the unknowns,        W = diag(w), w >= 0,
+lap given or the float32 divergence of a guidance field (periodic_np.divergence), u = boundary on the Dirichlet lines.  rhs() is the
+library's float32 right-hand side to the letter: the product w * d rounded to float32, then subtracted from lap.
+
+solve_exact() assembles A - W densely in float64 from the two axes' 1-D operators (axis_matrix: a Kronecker sum) and solves it with
+LAPACK: no transform, nothing shared with the library or with the other restatements.  operator() and residual() apply the stencil
+directly (periodic_np.operator).  pcg_f32() is the library's iteration restated in numpy: float32 vectors, float64 dot products,
+preconditioned by periodic_np.solve_f32 with the constant lambda-bar -- the yardstick of the GPU tests' bounds and iteration counts
+(tests/weighted_bounds.py).  Arrays are H x W x C (H x W accepted)."""
+from __future__ import annotations
+
+import numpy as np
+
+import periodic_np
+
+DD, NN, DN, ND, PP = periodic_np.DD, periodic_np.NN, periodic_np.DN, periodic_np.ND, periodic_np.PP
+
+
+def _hwc(a):
+    return a[:, :, None] if a.ndim == 2 else a
+
+
+def unknowns(sides, periodic, H, W):
+    return periodic_np.unknowns(sides, periodic, H, W)
+
+
+def has_dirichlet(sides, periodic):
+    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    return not (ax in (NN, PP) and ay in (NN, PP))
+
+
+def rhs(sides, periodic, weight, data, lap):
+    """lap - w * d in float32 at the unknowns (one multiply, then one subtract), 0 on the Dirichlet lines"""
+    lap, d, w = (_hwc(np.asarray(a, np.float32)) for a in (lap, data, weight))
+    f = lap - w * d
+    assert f.dtype == np.float32
+    out = np.zeros_like(f)
+    blk = unknowns(sides, periodic, *f.shape[:2])
+    out[blk] = f[blk]
+    return out
+
+
+def operator(sides, periodic, weight, u):
+    """(A - W) u in float64 at the unknowns (the Dirichlet lines of u hold the known values), 0 on the Dirichlet lines"""
+    u = _hwc(np.asarray(u, np.float64))
+    w = _hwc(np.asarray(weight, np.float32)).astype(np.float64)
+    r = periodic_np.operator(sides, periodic, 0.0, u)
+    blk = unknowns(sides, periodic, *u.shape[:2])
+    r[blk] -= (w * u)[blk]
+    return r
+
+
+def residual(sides, periodic, weight, u, data, lap):
+    """operator(u) - rhs in float64 (0 on the Dirichlet lines)"""
+    return operator(sides, periodic, weight, u) - rhs(sides, periodic, weight, data, lap).astype(np.float64)
+
+
+def _low_d(kind):
+    return kind in (DD, DN)
+
+
+def _high_d(kind):
+    return kind in (DD, ND)
+
+
+def _axis_apply(u, axis, kind):
+    """the 1-D operator along `axis` of the unknown block u, in u's dtype: sum over the neighbours that exist of (u_n - u); beyond a
+    Dirichlet line u_n = 0, beyond a free end no term, beyond the end of a periodic axis the pixel at the other end"""
+    n = u.shape[axis]
+    lo, hi = np.roll(u, 1, axis) - u, np.roll(u, -1, axis) - u
+    first = [slice(None)] * u.ndim
+    last = [slice(None)] * u.ndim
+    first[axis], last[axis] = slice(0, 1), slice(n - 1, n)
+    first, last = tuple(first), tuple(last)
+    if kind != PP:
+        lo[first] = -u[first] if _low_d(kind) else 0
+        hi[last] = -u[last] if _high_d(kind) else 0
+    return lo + hi
+
+
+def axis_matrix(kind, n):
+    """the 1-D operator of an axis of n unknowns as a dense float64 matrix"""
+    return _axis_apply(np.eye(n), 0, kind)
+
+
+def block_operator(ax, ay, w, u):
+    """(A - W) u on the unknown block [ny][nx][C], homogeneous Dirichlet lines, in u's dtype"""
+    return (_axis_apply(u, 1, ax) + _axis_apply(u, 0, ay)) - w * u
+
+
+def folded_rhs(sides, periodic, weight, data, lap, boundary, dtype=np.float64):
+    """the interior system's right-hand side on the unknown block: rhs less the neighbouring Dirichlet lines' values"""
+    f = rhs(sides, periodic, weight, data, lap)
+    blk = unknowns(sides, periodic, *f.shape[:2])
+    g = f[blk].astype(dtype)
+    if has_dirichlet(sides, periodic):
+        g = g - periodic_np._fold(sides, periodic, _hwc(np.asarray(boundary, dtype))).astype(dtype)
+    return g
+
+
+def solve_exact(sides, periodic, weight, data, lap, boundary=None):
+    """float64 solution of (A - W) u = rhs: boundary's values on the Dirichlet lines, the solution at the unknowns; data's shape.
+    Dense: meant for a few thousand unknowns."""
+    shape = np.asarray(data).shape
+    w = _hwc(np.asarray(weight, np.float32)).astype(np.float64)
+    H, W, C = w.shape
+    blk = unknowns(sides, periodic, H, W)
+    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    g = folded_rhs(sides, periodic, weight, data, lap, boundary)
+    ny, nx = g.shape[:2]
+    A = np.kron(np.eye(ny), axis_matrix(ax, nx)) + np.kron(axis_matrix(ay, ny), np.eye(nx))
+    out = _hwc(np.asarray(boundary, np.float64)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C))
+    for c in range(C):
+        M = A - np.diag(w[blk][:, :, c].reshape(-1))
+        out[blk[0], blk[1], c] = np.linalg.solve(M, g[:, :, c].reshape(-1)).reshape(ny, nx)
+    return out.reshape(shape)
+
+
+def mean_weight(sides, periodic, weight):
+    """the library's automatic lambda-bar of one problem: the mean of w over its unknowns (summed in double), as a float32"""
+    w = _hwc(np.asarray(weight, np.float32))
+    return np.float32(w[unknowns(sides, periodic, *w.shape[:2])].astype(np.float64).mean())
+
+
+def _precond(sides, periodic, lam, r_blk, shape):
+    """(A - lam)^-1 r on the unknown block in float32 (periodic_np.solve_f32 with zero data and a zero boundary)"""
+    H, W, C = shape
+    full = np.zeros((H, W, C), np.float32)
+    blk = unknowns(sides, periodic, H, W)
+    full[blk] = r_blk
+    zero = np.zeros((H, W, C), np.float32)
+    z = periodic_np.solve_f32(sides, periodic, float(lam), zero if lam else None, full, zero)
+    return np.asarray(z, np.float32)[blk]
+
+
+def pcg_f32(sides, periodic, weight, data, lap, boundary=None, tol=1e-5, max_iters=200, precond_lambda=None):
+    """The library's iteration in numpy: conjugate gradients on (A - W) u = b in float32 with float64 dot products, per channel its own
+    alpha and beta, preconditioned by the float32 direct solve of A - lambda-bar (default: the mean weight), started from M^-1 b;
+    stops when ||r|| <= tol ||b|| on every channel, r the iteration's own residual.  Returns (u of data's shape with boundary's values
+    on the Dirichlet lines, iterations, the worst channel's final ||r|| / ||b||)."""
+    shape = np.asarray(data).shape
+    w_full = _hwc(np.asarray(weight, np.float32))
+    H, W, C = w_full.shape
+    blk = unknowns(sides, periodic, H, W)
+    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    w = w_full[blk]
+    lam = mean_weight(sides, periodic, weight) if precond_lambda is None else np.float32(precond_lambda)
+    b = folded_rhs(sides, periodic, weight, data, lap, boundary, np.float32)
+    dot = lambda a, c: np.einsum("yxc,yxc->c", a.astype(np.float64), c.astype(np.float64))
+    bb = dot(b, b)
+    rel = lambda r: float(np.sqrt(np.max(np.where(bb > 0, dot(r, r) / np.where(bb > 0, bb, 1.0), 0.0))))
+    M = lambda r: _precond(sides, periodic, lam, r, (H, W, C))
+    u = M(b)
+    r = b - block_operator(ax, ay, w, u)
+    assert r.dtype == np.float32
+    z = M(r)
+    p = z.copy()
+    rho = dot(r, z)
+    it = 0
+    while rel(r) > tol and it < max_iters:
+        q = block_operator(ax, ay, w, p)
+        pq = dot(p, q)
+        alpha = np.where(pq != 0, rho / np.where(pq != 0, pq, 1.0), 0.0).astype(np.float32)
+        u = u + alpha * p
+        r = r - alpha * q
+        z = M(r)
+        rho_new = dot(r, z)
+        beta = np.where(rho != 0, rho_new / np.where(rho != 0, rho, 1.0), 0.0).astype(np.float32)
+        p = z + beta * p
+        rho = rho_new
+        it += 1
+        assert u.dtype == np.float32 and p.dtype == np.float32
+    out = _hwc(np.asarray(boundary, np.float32)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C), np.float32)
+    out[blk] = u
+    return out.reshape(shape), it, rel(r)
