@@ -443,13 +443,27 @@ def _layout_key(l: PoissonLayout):
     return (l.cols, l.rows, l.channels, l.col_stride, l.row_stride, l.channel_stride)
 
 
+def _check_call(fn, params, layout, **fields) -> int:
+    """A host-only sc_hip_*_check: the layout as a PoissonLayout or as keyword fields."""
+    if layout is None:
+        layout = PoissonLayout(*(int(fields[name]) for name, _ in PoissonLayout._fields_))
+    return int(getattr(load(), fn)(C.byref(params), C.byref(layout)))
+
+
+def _same_shape_f32(name, a, ref):
+    """a is a float32 numpy array of ref's shape, or the families' TypeError / ValueError."""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+        raise TypeError(f"{name} must be a float32 numpy array")
+    if a.shape != ref.shape:
+        raise ValueError(f"{name} has shape {a.shape}, the problem {ref.shape}")
+
+
 def poisson_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, layout: "PoissonLayout | None" = None, *, cols=None, rows=None,
                   channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
     """Host-only sc_hip_poisson_check: SC_OK or the code a call with this kind, tol and layout returns before it runs anything.  The
     layout as a PoissonLayout or as keyword fields."""
-    if layout is None:
-        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
-    return int(load().sc_hip_poisson_check(C.byref(PoissonParams(int(kind), float(tol))), C.byref(layout)))
+    return _check_call("sc_hip_poisson_check", PoissonParams(int(kind), float(tol)), layout, cols=cols, rows=rows, channels=channels,
+                       col_stride=col_stride, row_stride=row_stride, channel_stride=channel_stride)
 
 
 def poisson_arrays(boundary, gx=None, gy=None, lap=None, out=None, neumann=False, free_sides="", periodic=""):
@@ -492,9 +506,8 @@ def screened_check(kind: int = SC_POISSON_GUIDANCE, lam: float = 1.0, layout: "P
                    channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
     """Host-only sc_hip_screened_check: SC_OK or the code a screened call with this kind, lambda and layout returns before it runs
     anything.  The layout as a PoissonLayout or as keyword fields."""
-    if layout is None:
-        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
-    return int(load().sc_hip_screened_check(C.byref(ScreenedParams(int(kind), float(lam))), C.byref(layout)))
+    return _check_call("sc_hip_screened_check", ScreenedParams(int(kind), float(lam)), layout, cols=cols, rows=rows, channels=channels,
+                       col_stride=col_stride, row_stride=row_stride, channel_stride=channel_stride)
 
 
 def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, out=None, neumann=False, free_sides="", periodic=""):
@@ -513,10 +526,7 @@ def screened_arrays(data, gx=None, gy=None, lap=None, lam=None, boundary=None, o
         raise ValueError("a Dirichlet screened solve needs boundary (neumann=True: none)")
     kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides, periodic)
     if boundary is not None:
-        if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
-            raise TypeError("boundary must be a float32 numpy array")
-        if boundary.shape != data.shape:
-            raise ValueError(f"boundary has shape {boundary.shape}, the problem {data.shape}")
+        _same_shape_f32("boundary", boundary, data)
     return kind, data, gx, gy, lap, boundary, out
 
 
@@ -525,10 +535,9 @@ def weighted_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, max_iters:
                    channel_stride=None) -> int:
     """Host-only sc_hip_weighted_check: SC_OK or the code a weighted call with these parameters and this layout returns before it runs
     anything.  The layout as a PoissonLayout or as keyword fields."""
-    if layout is None:
-        layout = PoissonLayout(int(cols), int(rows), int(channels), int(col_stride), int(row_stride), int(channel_stride))
     p = WeightedParams(int(kind), float(tol), int(max_iters), float(precond_lambda))
-    return int(load().sc_hip_weighted_check(C.byref(p), C.byref(layout)))
+    return _check_call("sc_hip_weighted_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
 
 
 def weighted_arrays(data, weight, gx=None, gy=None, lap=None, boundary=None, out=None, neumann=False, free_sides="", periodic=""):
@@ -538,14 +547,10 @@ def weighted_arrays(data, weight, gx=None, gy=None, lap=None, boundary=None, out
     all_free = no_dirichlet(border_bits(free_sides, neumann, periodic))
     if data is None or weight is None:
         raise ValueError("a weighted solve needs its data term and its weights")
-    if not isinstance(data, np.ndarray) or data.dtype != np.float32:
-        raise TypeError("data must be a float32 numpy array")
-    if not isinstance(weight, np.ndarray) or weight.dtype != np.float32:
-        raise TypeError("weight must be a float32 numpy array")
-    if weight.ndim == 2 and data.ndim == 3 and weight.shape == data.shape[:2]:
+    _same_shape_f32("data", data, data)
+    if isinstance(weight, np.ndarray) and weight.ndim == 2 and data.ndim == 3 and weight.shape == data.shape[:2]:
         weight = np.ascontiguousarray(np.broadcast_to(weight[:, :, None], data.shape))
-    if weight.shape != data.shape:
-        raise ValueError(f"weight has shape {weight.shape}, the problem {data.shape}")
+    _same_shape_f32("weight", weight, data)
     if gx is None and gy is None and lap is None:
         lap = np.zeros(data.shape, np.float32)
     if all_free:
@@ -554,10 +559,7 @@ def weighted_arrays(data, weight, gx=None, gy=None, lap=None, boundary=None, out
         raise ValueError("a weighted solve with a Dirichlet line needs boundary")
     kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides, periodic)
     if boundary is not None:
-        if not isinstance(boundary, np.ndarray) or boundary.dtype != np.float32:
-            raise TypeError("boundary must be a float32 numpy array")
-        if boundary.shape != data.shape:
-            raise ValueError(f"boundary has shape {boundary.shape}, the problem {data.shape}")
+        _same_shape_f32("boundary", boundary, data)
     return kind, data, weight, gx, gy, lap, boundary, out
 
 
@@ -724,25 +726,37 @@ class Instance:
         on the other axis either, boundary gives only the mean and may be None, as for neumann."""
         kind, boundary, gx, gy, lap, out = poisson_arrays(boundary, gx, gy, lap, out, neumann, free_sides, periodic)
         first = boundary if boundary is not None else (lap if lap is not None else gx)
-        if out is None:
-            out = np.empty_like(first)
-        given = [a for a in (boundary, gx, gy, lap, out) if a is not None]
-        lays = [poisson_layout_of(a) for a in given]
-        target = out
+        return self._host_call("sc_hip_poisson", PoissonParams(kind, float(tol)), (gx, gy, lap, boundary), out, first,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else (), in_place=3)
+
+    def _host_call(self, fn, params, arrays, out, first, allow, in_place=None):
+        """One host call of a float32 family: arrays in the C entry's order (None: absent), out or None (a new array of first's shape).
+        One layout per call: numpy's strides when all arrays share them and they are positive, else contiguous copies and a
+        contiguous out that is copied back.  in_place: the index of the array an `out is arrays[in_place]` call keeps as its out
+        through the copies.  Returns the caller's out."""
+        target = out = np.empty_like(first) if out is None else out
+        lays = [poisson_layout_of(a) for a in (*arrays, out) if a is not None]
         if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
-            # one layout per call: contiguous copies (an in-place call stays in place)
-            same = out is boundary
-            boundary = None if boundary is None else np.ascontiguousarray(boundary)
-            gx, gy, lap = (None if a is None else np.ascontiguousarray(a) for a in (gx, gy, lap))
-            out = boundary if same and boundary is target else np.empty(first.shape, np.float32)
+            same = in_place is not None and out is arrays[in_place]
+            arrays = [None if a is None else np.ascontiguousarray(a) for a in arrays]
+            out = arrays[in_place] if same and arrays[in_place] is target else np.empty(first.shape, np.float32)
         layout = poisson_layout_of(out)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.L.sc_hip_poisson(self.h, C.byref(PoissonParams(kind, float(tol))), C.byref(layout), ptr(gx), ptr(gy), ptr(lap),
-                                   ptr(boundary), ptr(out))
-        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        rc = getattr(self.L, fn)(self.h, C.byref(params), C.byref(layout), *(None if a is None else a.ctypes.data for a in arrays),
+                                 out.ctypes.data)
+        self._check(rc, allow=allow)
         if out is not target:
             target[...] = out
         return target
+
+    def _device_call(self, fn, params, layout, jobs, sync, allow_job_errors, allow):
+        """One device call of a float32 family: bSync and a wait for the stream when sync; the worst code, raised unless it is in
+        allow or allow_job_errors lets it through (SC_ERR_HIP always raises)."""
+        rc = getattr(self.L, fn)(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc, allow=allow)
 
     @staticmethod
     def make_poisson_jobs(n: int):
@@ -752,12 +766,7 @@ class Instance:
         """sc_hip_poisson_device: jobs is a PoissonJob array (make_poisson_jobs) of device pointers, one layout for all.  sync: bSync
         (stage times) and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is
         returned, other failures raise unless allow_job_errors (then they are returned as well)."""
-        rc = self.L.sc_hip_poisson_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
-        if sync:
-            self.sync()
-        if allow_job_errors and rc != SC_ERR_HIP:
-            return rc
-        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
+        return self._device_call("sc_hip_poisson_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- screened Poisson solves on float32 arrays
     def screened(self, data, gx=None, gy=None, lap=None, lam=None, boundary=None, neumann=False, out=None, free_sides="", periodic=""):
@@ -766,23 +775,7 @@ class Instance:
         border (boundary then unused).  out: an array of data's shape to write (may be data or boundary), default a new one.
         free_sides, periodic: as poisson's (boundary is read on the remaining Dirichlet lines).  Returns out."""
         kind, data, gx, gy, lap, boundary, out = screened_arrays(data, gx, gy, lap, lam, boundary, out, neumann, free_sides, periodic)
-        if out is None:
-            out = np.empty_like(data)
-        given = [a for a in (data, gx, gy, lap, boundary, out) if a is not None]
-        lays = [poisson_layout_of(a) for a in given]
-        target = out
-        if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
-            # one layout per call: contiguous copies, a new contiguous out copied back below
-            data, gx, gy, lap, boundary = (None if a is None else np.ascontiguousarray(a) for a in (data, gx, gy, lap, boundary))
-            out = np.empty(data.shape, np.float32)
-        layout = poisson_layout_of(out)
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.L.sc_hip_screened(self.h, C.byref(ScreenedParams(kind, float(lam))), C.byref(layout), ptr(gx), ptr(gy), ptr(lap),
-                                    ptr(data), ptr(boundary), ptr(out))
-        self._check(rc)
-        if out is not target:
-            target[...] = out
-        return target
+        return self._host_call("sc_hip_screened", ScreenedParams(kind, float(lam)), (gx, gy, lap, data, boundary), out, data, ())
 
     @staticmethod
     def make_screened_jobs(n: int):
@@ -792,12 +785,7 @@ class Instance:
         """sc_hip_screened_device: jobs is a ScreenedJob array (make_screened_jobs) of device pointers, one layout for all.  sync: bSync
         (stage times) and a wait for the stream.  Per-job codes in jobs[i].rc; failures raise unless allow_job_errors (then the worst
         code is returned)."""
-        rc = self.L.sc_hip_screened_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
-        if sync:
-            self.sync()
-        if allow_job_errors and rc != SC_ERR_HIP:
-            return rc
-        return self._check(rc)
+        return self._device_call("sc_hip_screened_device", params, layout, jobs, sync, allow_job_errors, ())
 
     # ---- weighted solves on float32 arrays
     def weighted(self, data, weight, gx=None, gy=None, lap=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
@@ -809,24 +797,9 @@ class Instance:
         to write (may be data or boundary), default a new one.  Returns out; info() has the iterations and the final residual."""
         kind, data, weight, gx, gy, lap, boundary, out = weighted_arrays(data, weight, gx, gy, lap, boundary, out, neumann, free_sides,
                                                                          periodic)
-        if out is None:
-            out = np.empty_like(data)
-        given = [a for a in (data, weight, gx, gy, lap, boundary, out) if a is not None]
-        lays = [poisson_layout_of(a) for a in given]
-        target = out
-        if len({_layout_key(l) for l in lays}) != 1 or any(l.col_stride <= 0 or l.row_stride <= 0 or l.channel_stride <= 0 for l in lays):
-            # one layout per call: contiguous copies, a new contiguous out copied back below
-            data, weight, gx, gy, lap, boundary = (None if a is None else np.ascontiguousarray(a) for a in (data, weight, gx, gy, lap, boundary))
-            out = np.empty(data.shape, np.float32)
-        layout = poisson_layout_of(out)
-        ptr = lambda a: None if a is None else a.ctypes.data
         p = WeightedParams(kind, float(tol), int(max_iters), float(precond_lambda))
-        rc = self.L.sc_hip_weighted(self.h, C.byref(p), C.byref(layout), ptr(gx), ptr(gy), ptr(lap), ptr(data), ptr(weight), ptr(boundary),
-                                    ptr(out))
-        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
-        if out is not target:
-            target[...] = out
-        return target
+        return self._host_call("sc_hip_weighted", p, (gx, gy, lap, data, weight, boundary), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
 
     @staticmethod
     def make_weighted_jobs(n: int):
@@ -836,12 +809,7 @@ class Instance:
         """sc_hip_weighted_device: jobs is a WeightedJob array (make_weighted_jobs) of device pointers, one layout for all.  sync: bSync
         and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other
         failures raise unless allow_job_errors (then they are returned as well)."""
-        rc = self.L.sc_hip_weighted_device(self.h, C.byref(params), C.byref(layout), jobs, len(jobs), bool(sync))
-        if sync:
-            self.sync()
-        if allow_job_errors and rc != SC_ERR_HIP:
-            return rc
-        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
+        return self._device_call("sc_hip_weighted_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -5,6 +5,7 @@
 #pragma once
 #include "sc_common.h"
 #include "sc_hostcopy.h"
+#include <algorithm>
 #include <memory>
 #include <cmath>
 
@@ -328,11 +329,10 @@ void edit_preprocess(Instance *I, const sc_edit_params *p, const uint8_t *d_src,
 // ... the same for a group of n same-size images (sc_edit_batch.cpp): member k's eroded mask / class map in plane k of d_M / d_edge
 int canny_stage_group(Instance *I, const EditJob *jobs, int n, int W, int H, size_t mplane, float low, float high, int aperture);
 void edit_preprocess_group(Instance *I, const sc_edit_params *p, const EditJob *jobs, int n, size_t mplane);
-// sc_poisson_api.cpp: the Poisson call's validation (host-only; why: the reason) and a job's own
+// sc_poisson_api.cpp: the Poisson call's validation (host-only; why: the reason) ...
 int poisson_validate(const sc_poisson_params *p, const sc_poisson_layout *l, const char **why);
-int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why);
-// ... and what the screened call (sc_screened_api.cpp) shares with it.  lam > 0: a screened call -- the jobs carry their data term
-// (PoissonJobDev::d), the solve is the direct one with shifted denominators.
+// ... and the front end the float32 families share (sc_poisson_api.cpp, sc_screened_api.cpp, sc_weighted_api.cpp; DESIGN.md "float32
+// call front end"): validation, job intake, host staging, the chunk loop and the way back.
 // A kind's parts.  The free sides as a mask (1 left, 2 right, 4 top, 8 bottom; SC_POISSON_NEUMANN: all four); the periodic axes as a
 // mask (1 x, 2 y); the base kind (anything but GUIDANCE or LAPLACIAN there is a bad kind); the kind the entry points hand on: all four
 // sides free reads SC_POISSON_NEUMANN alone, so one test of that bit finds the Neumann call and any SC_POISSON_FREE_* bit left a call
@@ -367,12 +367,72 @@ inline bool poisson_no_dirichlet(int kind)
     const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), 4, 4, poisson_periodic(kind));
     return mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay);
 }
+// lam > 0: a screened call -- the jobs carry their data term (PoissonJobDev::d), the solve is the direct one with shifted denominators
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
-bool aligned4(const void *p);
-// SC_FLAG_FFT_FP64's limit on a direct solve with free sides `free` (poisson_free_sides'; 0: the Dirichlet frame) and periodic axes `per`
-// (poisson_periodic's): `why` and SC_ERR_BAD_SIZE when an axis has more unknowns than the double transforms take
-int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why, int per);
+// What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2 };
+struct FloatArrays { const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; };
+// A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
+// family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
+int family_validate(const int *kind, const sc_poisson_layout *l, const char *own, const char *limit_why, const char **why);
+// The instance's word on a direct solve before anything runs: the method must be SC_METHOD_AUTO or SC_METHOD_FFT (`method_why`), and
+// under SC_FLAG_FFT_FP64 no axis may have more unknowns than the double transforms take (`fp64_why`, SC_ERR_BAD_SIZE).
+int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, const char *method_why, const char *fp64_why);
+// A job's own code: the pointers its kind (poisson_norm_kind's) and family need, each 4-byte aligned.  Without a Dirichlet line on any
+// side a Poisson job may come without boundary (mean zero) and the other families do not read it: float_dev_job drops it there.
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why);
+PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
+// The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT) and where each one's code goes.
+struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w; std::vector<int *> rcs; };
+// A device call's job intake: arrays_of(job) names one public job's arrays.  A job that fails float_job_validate gets its code; the
+// others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
+// empty: nothing to run).
+template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int carries, Job *jobs, int n, ArraysOf arrays_of, FloatJobs &v)
+{
+    if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
+    int worst = SC_OK;
+    const char *why = "";
+    for (int i = 0; i < n; ++i) {
+        Job &j = jobs[i];
+        const FloatArrays a = arrays_of(j);
+        const int vrc = float_job_validate(kind, carries, a, &why);
+        if (vrc != SC_OK) {
+            j.rc = vrc;
+            if (worst == SC_OK) { worst = vrc; I->err = why; }
+            continue;
+        }
+        j.rc = SC_ERR_HIP;          // until its chunk has run
+        v.dj.push_back(float_dev_job(kind, carries, a));
+        v.w.push_back(a.weight);
+        v.rcs.push_back(&j.rc);
+    }
+    return worst;
+}
+// A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
+// boundary unless it is data | out unless it is data or boundary (in place) --, uploaded in that order.  job: the device job
+// (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights.
+struct FloatStaged { PoissonJobDev job; const float *d_w; };
+int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s);
+// nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and
+// sets their codes.  SC_OK and SC_ERR_NOT_CONVERGED let the call go on; any other code ends it: that chunk's jobs and every one not
+// yet run read it, after SC_ERR_HIP the ones already run too.  Returns that code, else the worst.
+template <class Chunk> int run_chunks(Instance *I, int C, int *const *rcs, int nv, Chunk chunk)
+{
+    const int per = std::max(1, SC_POISSON_MAX_PLANES / C);
+    int worst = SC_OK;
+    for (int i0 = 0; i0 < nv; i0 += per) {
+        const int m = std::min(per, nv - i0);
+        const int rc = chunk(i0, m);
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) {
+            for (int k = rc == SC_ERR_HIP ? 0 : i0; k < nv; ++k) *rcs[k] = rc;
+            return rc;
+        }
+        worst = worse(worst, rc);
+        I->info.group_members = m > 1 ? m : 0;
+    }
+    return worst;
+}
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
 int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);

@@ -1,5 +1,7 @@
 // sc_poisson_api.cpp -- the Poisson solver on float32 images with caller guidance fields (sc_hip_poisson_check, sc_hip_poisson_device,
-// sc_hip_poisson).
+// sc_hip_poisson), and the front end it shares with the screened and the weighted call (sc_screened_api.cpp, sc_weighted_api.cpp):
+// family_validate, direct_instance_check, float_job_validate, float_stage and poisson_download here, float_intake and run_chunks in
+// sc_instance.h.
 //
 // A call: validation -> per chunk of at most SC_POISSON_MAX_PLANES planes: setup_fields(W, H, C m) -> pre-process (U0 = boundary,
 // F = lap; sc_poisson.hip) -> the drivers' shared solve step (solve_step, with no output target: spec_post stays disarmed) -> output
@@ -89,30 +91,81 @@ size_t poisson_span(const sc_poisson_layout *l)
     return (size_t)((l->cols - 1) * l->col_stride + (l->rows - 1) * l->row_stride + (l->channels - 1) * l->channel_stride) + 1;
 }
 
-bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+static bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-int direct_fp64_check(Instance *I, int free, const sc_poisson_layout *l, const char *why, int per)
+int family_validate(const int *kind, const sc_poisson_layout *l, const char *own, const char *limit_why, const char **why)
 {
-    const MixedGeo mg = poisson_mixed_geo(free, l->cols, l->rows, per);
-    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) {
-        I->err = why;
-        return SC_ERR_BAD_SIZE;
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (!kind || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
+    if (own) { *why = own; return SC_ERR_BAD_ARG; }
+    const sc_poisson_params pp{ *kind, 0.f };
+    const int rc = poisson_validate(&pp, l, why);       // kind, channels, strides; the direct calls' side limits; at least 3 x 3 under a frame
+    if (rc) return rc;
+    if (!poisson_direct(*kind) && !fft_supported(l->cols - 2, l->rows - 2, false)) { *why = limit_why; return SC_ERR_BAD_SIZE; }
+    return SC_OK;
+}
+
+int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, const char *method_why, const char *fp64_why)
+{
+    if (I->opts.method != SC_METHOD_AUTO && I->opts.method != SC_METHOD_FFT) { I->err = method_why; return SC_ERR_BAD_ARG; }
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(kind), l->cols, l->rows, poisson_periodic(kind));
+    if ((I->opts.flags & SC_FLAG_FFT_FP64) && !fft_supported(mg.nx, mg.ny, true)) { I->err = fp64_why; return SC_ERR_BAD_SIZE; }
+    return SC_OK;
+}
+
+// (a job without a Dirichlet line on any side -- the Neumann call, a periodic axis beside a periodic or free-free one -- needs no
+// boundary: out is then checked in its place)
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why)
+{
+    if ((carries & FLOAT_DATA) && !a.data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
+    if ((carries & FLOAT_WEIGHT) && !a.weight) { *why = "null weight pointer"; return SC_ERR_BAD_ARG; }
+    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
+    const float *b = poisson_no_dirichlet(kind) && (carries || !a.boundary) ? a.out : a.boundary;
+    const float *need[6] = { a.data, a.weight, b, a.out, guidance ? a.gx : a.lap, guidance ? a.gy : a.lap };
+    for (int i = 0; i < 6; ++i) {
+        const float *q = need[i];
+        if (i < 2 && !(carries & (i ? FLOAT_WEIGHT : FLOAT_DATA))) continue;      // not this family's
+        if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
     }
     return SC_OK;
 }
 
-// a job's own code: the pointers its kind (poisson_norm_kind's) needs, 4-byte aligned (a job without a Dirichlet line on any side -- the
-// Neumann call, a periodic axis beside a periodic or free-free one -- may come without boundary: mean zero; with a Dirichlet line on any
-// side boundary is required)
-int poisson_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *b, const float *out, const char **why)
+PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a)
 {
+    PoissonJobDev j{ a.gx, a.gy, a.lap, carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary, a.out };
+    if (carries & FLOAT_DATA) j.d = a.data;
+    return j;
+}
+
+int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s)
+{
+    const size_t bytes = poisson_span(l) * sizeof(float), slot = (bytes + 255) / 256 * 256;
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
-    if (poisson_no_dirichlet(kind) && !b) b = out;
-    const float *need[4] = { b, out, guidance ? gx : lap, guidance ? gy : lap };
-    for (const float *q : need) {
-        if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
-        if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
-    }
+    const float *data = carries & FLOAT_DATA ? a.data : nullptr, *weight = carries & FLOAT_WEIGHT ? a.weight : nullptr;
+    // (the Poisson call keeps a boundary without a Dirichlet line: it gives the mean)
+    const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
+    const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
+    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1);
+    int rc, at = 0;
+    if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
+    auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
+    auto upload = [&](DevBuf &stage, float *d, const float *h) {
+        return d ? upload_rows(I, stage, d, bytes, (const uint8_t *)h, bytes, bytes, 1) : SC_OK;
+    };
+    float *d_in0 = next(true), *d_in1 = next(guidance), *d_d = next(data != nullptr), *d_w = next(weight != nullptr);
+    float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
+    float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
+    if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
+    if ((rc = upload(I->h_in, d_d, data))) return rc;
+    if ((rc = upload(I->h_out, d_w, weight))) return rc;      // (h_out: free until the download)
+    if ((rc = upload(I->h_mask, own_b ? d_b : nullptr, boundary))) return rc;
+    s.job = float_dev_job(kind, carries, FloatArrays{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_d, d_w, d_b, d_out });
+    s.d_w = d_w;
     return SC_OK;
 }
 
@@ -179,19 +232,17 @@ int free_sides_chunk(Instance *I, int kind, const PoissonGeo &g, const PoissonJo
 
 // the instance's word on a call of this kind (poisson_norm_kind's) before anything runs: with free sides, the methods that serve it
 // and the limit of its transforms' precision
-int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
+int poisson_instance_check(Instance *I, int kind, const sc_poisson_layout *l)
 {
-    const int free = poisson_free_sides(kind), per = poisson_periodic(kind), method = I->opts.method;
+    const int free = poisson_free_sides(kind), per = poisson_periodic(kind);
     if (!free && !per) return SC_OK;
-    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
-        I->err = per ? "periodic axes (SC_POISSON_PERIODIC_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)"
+    return direct_instance_check(I, kind, l,
+                 per ? "periodic axes (SC_POISSON_PERIODIC_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)"
                : free == 15 ? "SC_POISSON_NEUMANN is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers know Dirichlet problems)"
-                            : "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)";
-        return SC_ERR_BAD_ARG;
-    }
-    return direct_fp64_check(I, free, l, per ? "periodic axes with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis"
-                                         : free == 15 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
-                                                      : "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis", per);
+                            : "free sides (SC_POISSON_FREE_*) are solved by SC_METHOD_AUTO and SC_METHOD_FFT only (the multigrid and the relaxation solvers assume a zero ring on every level)",
+                 per ? "periodic axes with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis"
+               : free == 15 ? "SC_POISSON_NEUMANN with SC_FLAG_FFT_FP64: the image must be at most 4096 x 4096"
+                            : "free sides with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
 }
 
 void add_timing(Instance *I, float t[4])
@@ -227,28 +278,16 @@ int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, c
     fill_info_geo(I, geo);
     I->stage_marks = timed;
     I->marks_ends_only = false;
-    const int per = std::max(1, SC_POISSON_MAX_PLANES / g.C);
-    int worst = SC_OK;
-    for (int i0 = 0; i0 < nv; i0 += per) {
-        const int m = std::min(per, nv - i0);
-        int rc = poisson_direct(p.kind) ? free_sides_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
-        if (rc == SC_OK || rc == SC_ERR_NOT_CONVERGED) {
-            if (timed) {
-                SC_HIP(I, hipStreamSynchronize(I->stream));
-                add_timing(I, t);
-            }
-            for (int k = 0; k < m; ++k) *rcs[i0 + k] = rc;
-            if (rc != SC_OK && worst == SC_OK) worst = rc;
-            I->info.group_members = m > 1 ? m : 0;
-            continue;
+    return run_chunks(I, g.C, rcs, nv, [&](int i0, int m) -> int {
+        const int rc = poisson_direct(p.kind) ? free_sides_chunk(I, p.kind, g, dj + i0, m, p.lam) : poisson_chunk(I, p.kind, g, dj + i0, m, p.lam);
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+        if (timed) {
+            SC_HIP(I, hipStreamSynchronize(I->stream));
+            add_timing(I, t);
         }
-        // a chunk that failed: its members and every one not yet run read its code; after a HIP error the ones already run too
-        for (int k = i0; k < nv; ++k) *rcs[k] = rc;
-        if (rc == SC_ERR_HIP)
-            for (int k = 0; k < i0; ++k) *rcs[k] = rc;
+        for (int k = 0; k < m; ++k) *rcs[i0 + k] = rc;
         return rc;
-    }
-    return worst;
+    });
 }
 
 } // namespace sc
@@ -268,31 +307,17 @@ int sc_hip_poisson_device(void *inst, const sc_poisson_params *p, const sc_poiss
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
     const int kind = poisson_norm_kind(p->kind);
-    if ((rc = direct_instance_check(I, kind, l))) return rc;
-    if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
-    int worst = SC_OK;
-    std::vector<PoissonJobDev> dj;
-    std::vector<int *> rcs;
-    for (int i = 0; i < n; ++i) {
-        sc_poisson_job &j = jobs[i];
-        const int vrc = poisson_job_validate(kind, j.gx, j.gy, j.lap, j.boundary, j.out, &why);
-        if (vrc != SC_OK) {
-            j.rc = vrc;
-            if (worst == SC_OK) { worst = vrc; I->err = why; }
-            continue;
-        }
-        j.rc = SC_ERR_HIP;          // until its chunk has run
-        dj.push_back(PoissonJobDev{ j.gx, j.gy, j.lap, j.boundary, j.out });
-        rcs.push_back(&j.rc);
-    }
-    if (dj.empty()) return worst;
+    if ((rc = poisson_instance_check(I, kind, l))) return rc;
+    FloatJobs v;
+    const int worst = float_intake(I, kind, 0, jobs, n, [](const sc_poisson_job &j) {
+        return FloatArrays{ j.gx, j.gy, j.lap, nullptr, nullptr, j.boundary, j.out }; }, v);
+    if (v.rcs.empty()) return worst;
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, dj.data(), rcs.data(), (int)dj.size(), bSync, t);
+    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), bSync, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     poisson_set_timing(I, t);       // (zeros without bSync)
-    if (worst == SC_OK) worst = rc;
-    return worst;
+    return worst == SC_OK ? rc : worst;
 }
 
 int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
@@ -304,28 +329,16 @@ int sc_hip_poisson(void *inst, const sc_poisson_params *p, const sc_poisson_layo
     const char *why = "";
     if ((rc = poisson_validate(p, l, &why))) { I->err = why; return rc; }
     const int kind = poisson_norm_kind(p->kind);
-    if ((rc = direct_instance_check(I, kind, l))) return rc;
-    if ((rc = poisson_job_validate(kind, gx, gy, lap, boundary, out, &why))) { I->err = why; return rc; }
-    // one device block: the inputs' spans, boundary's, and out's unless out is boundary (in place); each at a 256-byte boundary
-    const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
-    // (a call without a Dirichlet line and without boundary: no slot, no upload)
-    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE, in_place = out == boundary;
-    const int slots = (guidance ? 2 : 1) + (boundary ? 1 : 0) + (in_place ? 0 : 1);
-    if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
-    uint8_t *d = (uint8_t *)I->d_pois.p;
-    float *d_in0 = (float *)d, *d_in1 = guidance ? (float *)(d + slot) : nullptr;
-    float *d_b = boundary ? (float *)(d + slot * (guidance ? 2 : 1)) : nullptr;
-    float *d_out = in_place ? d_b : (float *)(d + slot * (slots - 1));
-    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
-    if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
-    if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
-    if (boundary && (rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
-    const PoissonJobDev job{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_b, d_out };
+    if ((rc = poisson_instance_check(I, kind, l))) return rc;
+    const FloatArrays a{ gx, gy, lap, nullptr, nullptr, boundary, out };
+    if ((rc = float_job_validate(kind, 0, a, &why))) { I->err = why; return rc; }
+    FloatStaged s;
+    if ((rc = float_stage(I, l, kind, 0, a, s))) return rc;
     int job_rc = SC_OK, *const job_rcs[1] = { &job_rc };
     float t[4] = { 0.f, 0.f, 0.f, 0.f };
-    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, &job, job_rcs, 1, true, t);
+    rc = poisson_run(I, PoissonCall{ kind, p->tol, 0.f }, l, &s.job, job_rcs, 1, true, t);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    return poisson_download(I, l, d_out, out, t, rc);
+    return poisson_download(I, l, s.job.out, out, t, rc);
 }
 
 } // extern "C"

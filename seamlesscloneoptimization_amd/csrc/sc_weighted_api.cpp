@@ -3,7 +3,8 @@
 // A the 5-point operator of sc_hip_poisson under every border kind (a Dirichlet frame, SC_POISSON_NEUMANN, SC_POISSON_FREE_*,
 // SC_POISSON_PERIODIC_*).
 //
-// A call: validation -> per chunk of at most SC_POISSON_MAX_PLANES planes
+// A call: the float32 families' front end (sc_poisson_api.cpp: validation, job intake or host staging, run_chunks) -> per chunk of at
+// most SC_POISSON_MAX_PLANES planes
 //   1. the weights' statistics (one launch, one host read -- the call's one mandatory wait): per plane the sum of w and the number of
 //      weights that are negative or not finite.  A job with such a weight, or -- without any Dirichlet line -- with a channel of zero
 //      weight, gets SC_ERR_BAD_ARG and leaves the chunk; lambda-bar = precond_lambda, or the mean of w over the unknowns that remain.
@@ -29,49 +30,23 @@ constexpr int W_LAG = WeightedState::LAG, W_RING = WeightedState::RING;
 
 int weighted_validate(const sc_weighted_params *p, const sc_poisson_layout *l, const char **why)
 {
-    const char *dummy;
-    if (!why) why = &dummy;
-    *why = "";
-    if (!p || !l) { *why = "null pointer"; return SC_ERR_BAD_ARG; }
-    if (!std::isfinite(p->tol)) { *why = "tol must be finite"; return SC_ERR_BAD_ARG; }
-    if (!std::isfinite(p->precond_lambda)) { *why = "precond_lambda must be finite"; return SC_ERR_BAD_ARG; }
-    const sc_poisson_params pp{ p->kind, 0.f };
-    const int rc = poisson_validate(&pp, l, why);
+    const char *own = !p ? nullptr : !std::isfinite(p->tol) ? "tol must be finite"
+                    : !std::isfinite(p->precond_lambda) ? "precond_lambda must be finite" : nullptr;
+    return family_validate(p ? &p->kind : nullptr, l, own,
+                           "a weighted solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side", why);
+}
+
+// what every entry starts with: the instance, the call's validation and the instance's word on it; kind: poisson_norm_kind's
+int weighted_begin(void *inst, const sc_weighted_params *p, const sc_poisson_layout *l, Instance *&I, int &kind)
+{
+    int rc = begin_call(inst, I);
     if (rc) return rc;
-    if (!poisson_direct(p->kind) && !fft_supported(l->cols - 2, l->rows - 2, false)) {
-        *why = "a weighted solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side";
-        return SC_ERR_BAD_SIZE;
-    }
-    return SC_OK;
-}
-
-int weighted_instance_check(Instance *I, const sc_weighted_params *p, const sc_poisson_layout *l)
-{
-    const int method = I->opts.method;
-    if (method != SC_METHOD_AUTO && method != SC_METHOD_FFT) {
-        I->err = "a weighted solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
-        return SC_ERR_BAD_ARG;
-    }
-    return direct_fp64_check(I, poisson_free_sides(p->kind), l, "a weighted solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis",
-                             poisson_periodic(p->kind));
-}
-
-int weighted_job_validate(int kind, const float *gx, const float *gy, const float *lap, const float *data, const float *w, const float *b,
-                          const float *out, const char **why)
-{
-    if (!data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
-    if (!w) { *why = "null weight pointer"; return SC_ERR_BAD_ARG; }
-    if (!aligned4(data) || !aligned4(w)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
-    return poisson_job_validate(kind, gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out, why);
-}
-
-struct WJob { PoissonJobDev j; const float *w; int *rc; };
-
-WJob dev_job(int kind, const float *gx, const float *gy, const float *lap, const float *data, const float *w, const float *b, float *out, int *rc)
-{
-    WJob o{ PoissonJobDev{ gx, gy, lap, poisson_no_dirichlet(kind) ? nullptr : b, out }, w, rc };
-    o.j.d = data;
-    return o;
+    const char *why = "";
+    if ((rc = weighted_validate(p, l, &why))) { I->err = why; return rc; }
+    kind = poisson_norm_kind(p->kind);
+    return direct_instance_check(I, kind, l,
+        "a weighted solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)",
+        "a weighted solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
 }
 
 struct WCall { int kind; float tol; int max_iters; float plam; };
@@ -80,7 +55,8 @@ struct ChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
 
 // One chunk of m same-size jobs.  Jobs whose weights do not pass get their code here and take no further part; the rest share one
 // iteration and one code (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call).
-int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jobs, int m, ChunkResult &res, int &job_errors)
+int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const PoissonJobDev *jobs, const float *const *ws, int *const *rcs, int m,
+                   ChunkResult &res, int &job_errors)
 {
     const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
     const WeightedGeo wg = weighted_geo(mg);
@@ -101,14 +77,13 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jo
     double *h_stats = (double *)S.h_red.p, *h_bb = h_stats + 2 * per, *h_tot = h_bb + per;
 
     // 1. the weights
-    std::vector<PoissonJobDev> dj(m);
-    std::vector<const float *> dw(m);
-    for (int k = 0; k < m; ++k) { dj[k] = jobs[k].j; dw[k] = jobs[k].w; }
+    std::vector<PoissonJobDev> dj(jobs, jobs + m);
+    std::vector<const float *> dw(ws, ws + m);
     launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
     SC_HIP(I, hipGetLastError());
     SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * 2 * per, hipMemcpyDeviceToHost, s));
     SC_HIP(I, hipStreamSynchronize(s));
-    std::vector<WJob> live;
+    std::vector<int *> live;       // the codes of the jobs that stay, their arrays moved to the front of dj and dw
     double wsum = 0.0;
     for (int k = 0; k < m; ++k) {
         double job_sum = 0.0;
@@ -121,13 +96,15 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jo
             job_sum += sum;
         }
         if (bad || !std::isfinite(job_sum)) {
-            *jobs[k].rc = SC_ERR_BAD_ARG;
+            *rcs[k] = SC_ERR_BAD_ARG;
             if (!job_errors++) I->err = "a weight is negative or not finite";
         } else if (no_dirichlet && empty) {
-            *jobs[k].rc = SC_ERR_BAD_ARG;
+            *rcs[k] = SC_ERR_BAD_ARG;
             if (!job_errors++) I->err = "no data weight and no Dirichlet line";
         } else {
-            live.push_back(jobs[k]);
+            dj[live.size()] = dj[k];
+            dw[live.size()] = dw[k];
+            live.push_back(rcs[k]);
             wsum += job_sum;
         }
     }
@@ -136,7 +113,6 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jo
     if (!mv) return SC_OK;
     const double n_unknowns = (double)wg.nx * (double)wg.ny * (double)planes;
     const float lam = call.plam > 0.f ? call.plam : (float)(wsum / n_unknowns);      // (0: no weight anywhere, under Dirichlet lines -- the unscreened solve)
-    for (int k = 0; k < mv; ++k) { dj[k] = live[k].j; dw[k] = live[k].w; }
 
     // 2. the work planes
     const size_t plane_bytes = sizeof(float) * (size_t)wg.stride * planes;
@@ -226,13 +202,13 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, WJob *jo
     launch_weighted_out(g, wg, dj.data(), mv, U, s);
     SC_HIP(I, hipGetLastError());
     const int code = res.converged ? SC_OK : SC_ERR_NOT_CONVERGED;
-    for (int k = 0; k < mv; ++k) *live[k].rc = code;
+    for (int k = 0; k < mv; ++k) *live[k] = code;
     return code;
 }
 
-// The validated jobs of a call through chunks.  Returns the worst code (job errors of the weights included); a HIP error (or any other
-// error of a chunk) marks every job not yet finished, and after a HIP error the finished ones too.
-int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, std::vector<WJob> &jobs, bool timed)
+// The validated jobs of a call through chunks (run_chunks).  Returns the worst code, job errors of the weights included.
+int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, const PoissonJobDev *jobs, const float *const *ws, int *const *rcs,
+                 int nv, bool timed)
 {
     CallScope scope{ I };
     const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
@@ -240,26 +216,18 @@ int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, std
     fill_info_geo(I, geo);
     I->stage_marks = false;          // (direct_jobs_solve's marks: a call of many solves records none)
     if (timed) SC_HIP(I, hipEventRecord(I->ev[0], I->stream));
-    const int per = std::max(1, SC_POISSON_MAX_PLANES / g.C), nv = (int)jobs.size();
-    int worst = SC_OK, job_errors = 0, sweeps = 0;
+    int job_errors = 0, sweeps = 0;
     bool converged = true;
     double rel = 0.0;
-    for (int i0 = 0; i0 < nv; i0 += per) {
-        const int m = std::min(per, nv - i0);
+    int worst = run_chunks(I, g.C, rcs, nv, [&](int i0, int m) {
         ChunkResult res;
-        const int rc = weighted_chunk(I, call, g, jobs.data() + i0, m, res, job_errors);
-        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) {
-            for (int k = i0; k < nv; ++k) *jobs[k].rc = rc;
-            if (rc == SC_ERR_HIP)
-                for (int k = 0; k < i0; ++k) *jobs[k].rc = rc;
-            return rc;
-        }
-        worst = worse(worst, rc);
+        const int rc = weighted_chunk(I, call, g, jobs + i0, ws + i0, rcs + i0, m, res, job_errors);
         sweeps = std::max(sweeps, res.iters);
         converged = converged && res.converged;
         rel = std::max(rel, res.rel);
-        I->info.group_members = m > 1 ? m : 0;
-    }
+        return rc;
+    });
+    if (worst != SC_OK && worst != SC_ERR_NOT_CONVERGED) return worst;
     if (job_errors) worst = worse(worst, SC_ERR_BAD_ARG);
     I->info.method = SC_METHOD_FFT;
     I->info.sweeps = sweeps;
@@ -288,29 +256,14 @@ int sc_hip_weighted_check(const sc_weighted_params *p, const sc_poisson_layout *
 int sc_hip_weighted_device(void *inst, const sc_weighted_params *p, const sc_poisson_layout *l, sc_weighted_job *jobs, int n, bool bSync)
 {
     Instance *I;
-    int rc = begin_call(inst, I);
+    int kind, rc = weighted_begin(inst, p, l, I, kind);
     if (rc) return rc;
-    const char *why = "";
-    if ((rc = weighted_validate(p, l, &why))) { I->err = why; return rc; }
-    if ((rc = weighted_instance_check(I, p, l))) return rc;
-    const int kind = poisson_norm_kind(p->kind);
-    if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
-    int worst = SC_OK;
-    std::vector<WJob> wj;
-    for (int i = 0; i < n; ++i) {
-        sc_weighted_job &j = jobs[i];
-        const int vrc = weighted_job_validate(kind, j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, &why);
-        if (vrc != SC_OK) {
-            j.rc = vrc;
-            if (worst == SC_OK) { worst = vrc; I->err = why; }
-            continue;
-        }
-        j.rc = SC_ERR_HIP;          // until its chunk has run
-        wj.push_back(dev_job(kind, j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, &j.rc));
-    }
-    if (wj.empty()) return worst;
+    FloatJobs v;
+    const int worst = float_intake(I, kind, FLOAT_DATA | FLOAT_WEIGHT, jobs, n, [](const sc_weighted_job &j) {
+        return FloatArrays{ j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out }; }, v);
+    if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, wj, bSync);
+    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, v.dj.data(), v.w.data(), v.rcs.data(), (int)v.rcs.size(), bSync);
     return worse(worst, rc);
 }
 
@@ -318,37 +271,18 @@ int sc_hip_weighted(void *inst, const sc_weighted_params *p, const sc_poisson_la
                     const float *lap, const float *data, const float *weight, const float *boundary, float *out)
 {
     Instance *I;
-    int rc = begin_call(inst, I);
+    int kind, rc = weighted_begin(inst, p, l, I, kind);
     if (rc) return rc;
+    const FloatArrays a{ gx, gy, lap, data, weight, boundary, out };
     const char *why = "";
-    if ((rc = weighted_validate(p, l, &why))) { I->err = why; return rc; }
-    if ((rc = weighted_instance_check(I, p, l))) return rc;
-    const int kind = poisson_norm_kind(p->kind);
-    if ((rc = weighted_job_validate(kind, gx, gy, lap, data, weight, boundary, out, &why))) { I->err = why; return rc; }
-    // one device block, as sc_hip_screened's, with the weights' span behind the data's
-    const size_t span = poisson_span(l), bytes = span * sizeof(float), slot = (bytes + 255) / 256 * 256;
-    const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
-    if (poisson_no_dirichlet(kind)) boundary = nullptr;
-    const bool b_is_d = boundary == data, own_b = boundary && !b_is_d, in_place = out == data || (boundary && out == boundary);
-    const int n_in = guidance ? 2 : 1, slots = n_in + 2 + (own_b ? 1 : 0) + (in_place ? 0 : 1);
-    if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
-    uint8_t *d = (uint8_t *)I->d_pois.p;
-    float *d_in0 = (float *)d, *d_in1 = guidance ? (float *)(d + slot) : nullptr;
-    float *d_d = (float *)(d + slot * n_in), *d_w = (float *)(d + slot * (n_in + 1));
-    float *d_b = own_b ? (float *)(d + slot * (n_in + 2)) : (boundary ? d_d : nullptr);
-    float *d_out = !in_place ? (float *)(d + slot * (slots - 1)) : (out == data ? d_d : d_b);
-    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
-    if ((rc = upload_rows(I, I->h_face, d_in0, bytes, (const uint8_t *)(guidance ? gx : lap), bytes, bytes, 1))) return rc;
-    if (guidance && (rc = upload_rows(I, I->h_body, d_in1, bytes, (const uint8_t *)gy, bytes, bytes, 1))) return rc;
-    if ((rc = upload_rows(I, I->h_in, d_d, bytes, (const uint8_t *)data, bytes, bytes, 1))) return rc;
-    if ((rc = upload_rows(I, I->h_out, d_w, bytes, (const uint8_t *)weight, bytes, bytes, 1))) return rc;      // (h_out: free until the download)
-    if (own_b && (rc = upload_rows(I, I->h_mask, d_b, bytes, (const uint8_t *)boundary, bytes, bytes, 1))) return rc;
-    int job_rc = SC_ERR_HIP;
-    std::vector<WJob> wj{ dev_job(kind, guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_d, d_w, d_b, d_out, &job_rc) };
-    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, wj, true);
+    if ((rc = float_job_validate(kind, FLOAT_DATA | FLOAT_WEIGHT, a, &why))) { I->err = why; return rc; }
+    FloatStaged s;
+    if ((rc = float_stage(I, l, kind, FLOAT_DATA | FLOAT_WEIGHT, a, s))) return rc;
+    int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
+    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, &s.job, &s.d_w, job_rcs, 1, true);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };
-    return poisson_download(I, l, d_out, out, t, rc);
+    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: weighted_run times the call whole)
+    return poisson_download(I, l, s.job.out, out, t, rc);
 }
 
 } // extern "C"

@@ -273,6 +273,43 @@ def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None
         inst.destroy()
 
 
+def _float_batch(members, make_jobs, call, gpu_id, solver):
+    """The device side of a float32 family's batch.  members: per problem its arrays in slot order, all of one shape, each as
+    (the job field that points to it, the array) -- field None: the array takes its slot, the job's pointer stays NULL.  One device
+    block holds every member's arrays and, behind them, every member's out, each at a 256-byte boundary; one copy in, the device
+    call, one copy back.  call(inst, layout, jobs) runs the family's device call.  Returns the members' results as new arrays."""
+    fields = [[f for f, _ in m] for m in members]
+    members = [[np.ascontiguousarray(a) for _, a in m] for m in members]
+    n, per, ref = len(members), len(members[0]), members[0][0]
+    slot = (ref.nbytes + 255) // 256 * 256
+    in_bytes = slot * per * n
+    staged = np.zeros(in_bytes // 4, np.float32)
+    for k, arrays in enumerate(members):
+        for i, a in enumerate(arrays):
+            o = (k * per + i) * slot // 4
+            staged[o:o + a.size] = a.reshape(-1)
+    inst = capi.Instance(gpu_id)
+    dev = None
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        dev = inst.malloc(in_bytes + slot * n)
+        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
+        jobs = make_jobs(n)
+        for k, j in enumerate(jobs):
+            for i, f in enumerate(fields[k]):
+                if f is not None:
+                    setattr(j, f, dev + (k * per + i) * slot)
+            j.out = dev + in_bytes + k * slot
+        call(inst, capi.poisson_layout_of(ref), jobs)
+        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
+    finally:
+        if dev is not None:
+            inst.free(dev)
+        inst.destroy()
+    return [out[k * slot // 4:k * slot // 4 + ref.size].reshape(ref.shape).copy() for k in range(n)]
+
+
 def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=0, tol=None, neumann=False, free_sides="", periodic="",
                         **solver):
     """poisson_solve over a list of same-shape problems through ONE device-resident call (sc_hip_poisson_device): the inputs go to the
@@ -289,54 +326,21 @@ def poisson_solve_batch(boundaries, gxs=None, gys=None, laplacians=None, gpu_id=
     for f in fields:
         if len(f) != n:
             raise ValueError("one guidance field (or laplacian) per boundary")
-    checked, has_b = [], []
+    checked = []
     for k in range(n):
         if gxs is not None:
             kind, b, gx, gy, _, _ = capi.poisson_arrays(bs[k], gxs[k], gys[k], neumann=neumann, free_sides=free_sides, periodic=periodic)
-            ins = [gx, gy]
+            ins = [("gx", gx), ("gy", gy)]
         else:
             kind, b, _, _, lap, _ = capi.poisson_arrays(bs[k], lap=laplacians[k], neumann=neumann, free_sides=free_sides, periodic=periodic)
-            ins = [lap]
-        if ins[0].shape != fields[0][0].shape:
+            ins = [("lap", lap)]
+        if ins[0][1].shape != fields[0][0].shape:
             raise ValueError("every problem of a batch must have one shape")
-        has_b.append(b is not None)
-        checked.append([np.ascontiguousarray(a) for a in ins + [b if b is not None else np.zeros_like(ins[0])]])
-    shape = fields[0][0].shape
+        checked.append(ins + [("boundary", b) if b is not None else (None, np.zeros_like(ins[0][1]))])
     if tol is None:
-        tol = 0.0 if _direct(neumann, free_sides, periodic) else max(poisson_tol(a[-1]) for a in checked)
-    nb = checked[0][0].nbytes
-    slot = (nb + 255) // 256 * 256
-    per = len(checked[0])
-    in_bytes = slot * per * n
-    staged = np.zeros(in_bytes // 4, np.float32)
-    for k, arrays in enumerate(checked):
-        for i, a in enumerate(arrays):
-            o = (k * per + i) * slot // 4
-            staged[o:o + a.size] = a.reshape(-1)
-    layout = capi.poisson_layout_of(checked[0][-1])
-    inst = capi.Instance(gpu_id)
-    d = None
-    try:
-        if solver:
-            inst.set_solver(**solver)
-        d = inst.malloc(in_bytes + slot * n)
-        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, d, staged.ctypes.data, in_bytes))
-        jobs = capi.Instance.make_poisson_jobs(n)
-        for k, j in enumerate(jobs):
-            base = d + k * per * slot
-            if (kind & ~(capi.SC_POISSON_NEUMANN | capi.SC_POISSON_FREE_ALL | capi.SC_POISSON_PERIODIC_ALL)) == capi.SC_POISSON_GUIDANCE:
-                j.gx, j.gy = base, base + slot
-            else:
-                j.lap = base
-            j.boundary = base + (per - 1) * slot if has_b[k] else None
-            j.out = d + in_bytes + k * slot
-        inst.poisson_device(capi.PoissonParams(kind, float(tol)), layout, jobs)
-        out = inst.from_device(d + in_bytes, (slot * n // 4,), np.float32)
-    finally:
-        if d is not None:
-            inst.free(d)
-        inst.destroy()
-    return [out[k * slot // 4:k * slot // 4 + checked[k][-1].size].reshape(shape).copy() for k in range(n)]
+        tol = 0.0 if _direct(neumann, free_sides, periodic) else max(poisson_tol(m[-1][1]) for m in checked)
+    return _float_batch(checked, capi.Instance.make_poisson_jobs,
+                        lambda inst, layout, jobs: inst.poisson_device(capi.PoissonParams(kind, float(tol)), layout, jobs), gpu_id, solver)
 
 
 def _screened_borders(neumann, free_sides, periodic=""):
@@ -405,48 +409,15 @@ def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, b
         b = None if no_boundary else boundaries[k]
         if gxs is not None:
             kind, d, gx, gy, _, b, _ = capi.screened_arrays(ds[k], gxs[k], gys[k], None, lam, b, neumann=neumann, free_sides=free_sides, periodic=periodic)
-            arrays = [gx, gy, d]
+            arrays = [("gx", gx), ("gy", gy), ("data", d)]
         else:
             kind, d, _, _, lap, b, _ = capi.screened_arrays(ds[k], None, None, laplacians[k], lam, b, neumann=neumann, free_sides=free_sides, periodic=periodic)
-            arrays = [lap, d]
+            arrays = [("lap", lap), ("data", d)]
         if d.shape != ds[0].shape:
             raise ValueError("every problem of a batch must have one shape")
-        checked.append([np.ascontiguousarray(a) for a in arrays + ([] if b is None else [b])])
-    shape = ds[0].shape
-    nb = checked[0][0].nbytes
-    slot = (nb + 255) // 256 * 256
-    per = len(checked[0])
-    in_bytes = slot * per * n
-    staged = np.zeros(in_bytes // 4, np.float32)
-    for k, arrays in enumerate(checked):
-        for i, a in enumerate(arrays):
-            o = (k * per + i) * slot // 4
-            staged[o:o + a.size] = a.reshape(-1)
-    layout = capi.poisson_layout_of(checked[0][0])
-    guidance = gxs is not None
-    inst = capi.Instance(gpu_id)
-    dev = None
-    try:
-        if solver:
-            inst.set_solver(**solver)
-        dev = inst.malloc(in_bytes + slot * n)
-        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
-        jobs = capi.Instance.make_screened_jobs(n)
-        for k, j in enumerate(jobs):
-            base = dev + k * per * slot
-            if guidance:
-                j.gx, j.gy, j.data = base, base + slot, base + 2 * slot
-            else:
-                j.lap, j.data = base, base + slot
-            j.boundary = None if no_boundary else base + (per - 1) * slot
-            j.out = dev + in_bytes + k * slot
-        inst.screened_device(capi.ScreenedParams(kind, float(lam)), layout, jobs)
-        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
-    finally:
-        if dev is not None:
-            inst.free(dev)
-        inst.destroy()
-    return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
+        checked.append(arrays + ([] if b is None else [("boundary", b)]))
+    return _float_batch(checked, capi.Instance.make_screened_jobs,
+                        lambda inst, layout, jobs: inst.screened_device(capi.ScreenedParams(kind, float(lam)), layout, jobs), gpu_id, solver)
 
 
 def weighted_solve(data, weight, gx=None, gy=None, laplacian=None, boundary=None, neumann=True, free_sides=None, periodic="", tol=None,
@@ -499,45 +470,11 @@ def weighted_solve_batch(datas, weights, gxs=None, gys=None, laplacians=None, bo
                                                              free_sides=free_sides, periodic=periodic)
         if d.shape != ds[0].shape:
             raise ValueError("every problem of a batch must have one shape")
-        arrays = ([gx, gy] if gx is not None else [lap]) + [d, w] + ([] if b is None else [b])
-        checked.append([np.ascontiguousarray(a) for a in arrays])
-    shape = ds[0].shape
-    slot = (checked[0][0].nbytes + 255) // 256 * 256
-    per = len(checked[0])
-    in_bytes = slot * per * n
-    staged = np.zeros(in_bytes // 4, np.float32)
-    for k, arrays in enumerate(checked):
-        for i, a in enumerate(arrays):
-            o = (k * per + i) * slot // 4
-            staged[o:o + a.size] = a.reshape(-1)
-    layout = capi.poisson_layout_of(checked[0][0])
-    guidance = gxs is not None
-    inst = capi.Instance(gpu_id)
-    dev = None
-    try:
-        if solver:
-            inst.set_solver(**solver)
-        dev = inst.malloc(in_bytes + slot * n)
-        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
-        jobs = capi.Instance.make_weighted_jobs(n)
-        for k, j in enumerate(jobs):
-            base = dev + k * per * slot
-            n_in = 2 if guidance else 1
-            if guidance:
-                j.gx, j.gy = base, base + slot
-            else:
-                j.lap = base
-            j.data, j.weight = base + n_in * slot, base + (n_in + 1) * slot
-            j.boundary = None if no_boundary else base + (per - 1) * slot
-            j.out = dev + in_bytes + k * slot
-        rc = inst.weighted_device(capi.WeightedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0)), layout, jobs)
-        inst._check(rc)
-        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
-    finally:
-        if dev is not None:
-            inst.free(dev)
-        inst.destroy()
-    return [out[k * slot // 4:k * slot // 4 + ds[0].size].reshape(shape).copy() for k in range(n)]
+        arrays = [("gx", gx), ("gy", gy)] if gx is not None else [("lap", lap)]
+        checked.append(arrays + [("data", d), ("weight", w)] + ([] if b is None else [("boundary", b)]))
+    params = capi.WeightedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0))
+    return _float_batch(checked, capi.Instance.make_weighted_jobs,
+                        lambda inst, layout, jobs: inst._check(inst.weighted_device(params, layout, jobs)), gpu_id, solver)
 
 
 def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, **solver):
