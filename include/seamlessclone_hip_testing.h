@@ -30,6 +30,9 @@ extern "C" {
                                             (pre-smoothing + residual + restriction, direct solve, prolongation + post-smoothing).  Default
                                             since round 4 where that level has at most 127 unknowns per side: ONE launch, the level in
                                             registers (k_mg_tail).  Same arithmetic per point                                            */
+#define SC_LEGACY_UNPACKED_TILES 8        /*   multigrid, coarse levels: every column tile in a workgroup of its own.  Default: where the last
+                                            column tile of a level needs at most half a wave, one workgroup serves that tile of several
+                                            planes (sc_hip_coarse_tile_plan).  Same values, bit for bit                                   */
 #define SC_FLAG_KEEP_FIELD     (1 << 7)  /* sc_hip_run*: keep the solution field on the device (sc_hip_field_store,
                                             _residual, _finish after a run): the last multigrid cycle writes the field
                                             and a post-process launch reads it.  Default: that cycle writes the output
@@ -121,6 +124,17 @@ SC_API int sc_hip_selftest_host(void);
  * out_bytes, composed, l1_half, timing, bands (pointer given), rag (size class).  form[3] receives T, PRO, TAG; returns 0, or -1: no such
  * form, nothing would be launched.  facts == NULL: form receives entry `index` of the table of instantiated forms, its length is returned. */
 SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
+
+/* Host only, nothing is launched: the column tiling of a coarse-level multigrid launch and what the lanes of its workgroups serve.
+ * facts = { W, H, C (field width and height, ring included; planes), useful width, halo (columns a tile owns; halo columns per side: 232, 12
+ * for the way down, 248, 4 for the way up), rows a tile owns, size class (0 / 1), unpacked (1: SC_LEGACY_UNPACKED_TILES), first workgroup,
+ * number of workgroups n (0: the plan only) }.
+ * plan = { full column tiles (one plane per workgroup), lanes per slot of a packed workgroup, planes per packed workgroup K (1: nothing
+ * packed), workgroups of the launch }, then 130 ints for each of the n workgroups from `first workgroup` on (logical numbers): its row
+ * tile, its lanes per slot (64: a full tile; lane l is lane l % that of its slot, and a halo lane where that is below halo / 4 or among
+ * the last halo / 4), and per lane its plane (>= C: an empty slot) and first column.  Returns 0, SC_ERR_BAD_ARG for facts outside their
+ * ranges. */
+SC_API int sc_hip_coarse_tile_plan(const int *facts, int *plan);
 
 #ifdef __cplusplus
 }

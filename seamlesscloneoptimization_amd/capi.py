@@ -58,7 +58,7 @@ SC_FLAG_NO_COMPOSE_L1 = 1 << 3
 SC_FLAG_VCYCLE_BOTTOM = 1 << 4
 SC_FLAG_EXACT_TABLES = 1 << 5
 SC_FLAG_LEGACY_PATHS = 1 << 6      # run the superseded launch forms named in SolverOpts.legacy_paths (SC_LEGACY_* bits)
-SC_LEGACY_SEPARATE_RESTRICT, SC_LEGACY_BOTTOM_F32, SC_LEGACY_SEPARATE_TAIL = 1, 2, 4
+SC_LEGACY_SEPARATE_RESTRICT, SC_LEGACY_BOTTOM_F32, SC_LEGACY_SEPARATE_TAIL, SC_LEGACY_UNPACKED_TILES = 1, 2, 4, 8
 SC_FLAG_KEEP_FIELD = 1 << 7
 SC_FLAG_FFT_FP64 = 1 << 8
 SC_FLAG_OPENCV_GREY_MASK = 1 << 9
@@ -359,6 +359,8 @@ def load():
     L.sc_hip_selftest_host.restype = C.c_int
     L.sc_hip_cycle0_form.argtypes = [i32p, C.c_int, i32p]
     L.sc_hip_cycle0_form.restype = C.c_int
+    L.sc_hip_coarse_tile_plan.argtypes = [i32p, i32p]
+    L.sc_hip_coarse_tile_plan.restype = C.c_int
     L.sc_hip_plan_groups.argtypes = [i32p, C.c_int, C.c_int, C.POINTER(SolverOpts), i32p, i32p]
     L.sc_hip_plan_groups.restype = C.c_int
     L.sc_hip_plan_size.argtypes = [C.c_int, C.c_int, C.POINTER(SolverOpts), i32p]
@@ -1115,6 +1117,26 @@ def cycle0_form(**facts):
         raise TypeError("cycle0_form: no such fact: %s" % sorted(facts))
     out = (C.c_int * 3)()
     return tuple(out) if load().sc_hip_cycle0_form(f, 0, out) == 0 else -1
+
+
+def coarse_tile_plan(W, H, C_, useful, halo, rows, size_class=False, unpacked=False, lanes=False):
+    """Host-only: the column tiling of a coarse-level multigrid launch: (full column tiles, lanes per slot, planes per packed
+    workgroup, workgroups).  lanes=True: also, per workgroup, (row tile [n], lanes per slot [n], plane [n, 64], first column [n, 64])."""
+    f = (C.c_int * 10)(W, H, C_, useful, halo, rows, int(size_class), int(unpacked), 0, 0)
+    head = np.zeros(4, np.int32)
+    rc = load().sc_hip_coarse_tile_plan(f, head.ctypes.data_as(i32p))
+    if rc != 0:
+        raise SeamlessCloneError(rc, "coarse_tile_plan")
+    if not lanes:
+        return tuple(int(v) for v in head)
+    n = int(head[3])
+    f[9] = n
+    out = np.zeros(4 + 130 * n, np.int32)
+    rc = load().sc_hip_coarse_tile_plan(f, out.ctypes.data_as(i32p))
+    if rc != 0:
+        raise SeamlessCloneError(rc, "coarse_tile_plan")
+    t = out[4:].reshape(n, 130)
+    return tuple(int(v) for v in head), (t[:, 0], t[:, 1], t[:, 2::2], t[:, 3::2])
 
 
 def cycle0_forms():

@@ -237,13 +237,58 @@ bool launch_rb_tb(Field Uin, Field Uout, Field F, int sweeps, float omega, hipSt
 int  tb_max_depth(int method);
 int  tb_hard_max_depth(int method);
 long tb_big_side();
-int  tb_gen_rows(int W, int H, int C, int hx, int hy);   // band height (rows per lane) of a coarse-level launch
-int  tb_gen_rows_deep(int W, int H, int C, int hx, int hy);   // the same for launches of depth 3 or 4: 4 or 6
+// Column tiling of a coarse-level launch (k_cycle0's GEN forms, k_rb_tb's GEN forms): a plane is cut into column tiles one wave wide that
+// own `uw` = 256 - 2 hx columns each, and row tiles that own `rows` rows.  The LAST column tile of a level whose width lies just above a
+// multiple of uw owns a few columns only (widths 1025, 513, 257 of a 2048^2 ROI: 97, 49, 25 of 232); where it needs at most half a wave --
+// its own columns and hx halo columns on either side -- one workgroup serves that tile of K planes: the wave is cut into K slots of `lps`
+// lanes (a power of two), slot k holds plane c0 + k at columns x_res - hx + 4 (lane % lps).  Rows stay wave-uniform.  Workgroups are
+// numbered full tiles first (column tile fastest, then row tile, then plane), packed tiles behind them (row tile fastest, then pack).
+// One definition for the launchers and the kernels: what is counted is what runs.  A size class never packs (its members differ in width
+// and leave empty tiles early), nor does a launch asked for the unpacked tiling (SC_LEGACY_UNPACKED_TILES).
+struct TilePlan { int nbx, nby, full, lps, lg, K, blocks; };      // full: column tiles served one plane per workgroup (nbx, or nbx - 1 when the last one is packed); lps = 1 << lg
+__host__ __device__ inline TilePlan coarse_tile_plan(int W, int H, int C, int uw, int hx, int rows, bool size_class, bool pack = true)
+{
+    TilePlan p;
+    p.nbx = (W + uw - 1) / uw; p.nby = (H + rows - 1) / rows;
+    p.full = p.nbx; p.lps = 64; p.lg = 6; p.K = 1;
+    const int need = (W - (p.nbx - 1) * uw + 2 * hx + 3) / 4;      // float4 lanes of the last tile: the columns it owns and a halo on either side (at least 3)
+    if (pack && !size_class && need <= 32) {
+        p.lg = 32 - __builtin_clz((unsigned)(need - 1));            // the smallest power of two that holds them
+        p.lps = 1 << p.lg; p.K = 64 >> p.lg; p.full = p.nbx - 1;
+    }
+    p.blocks = p.nby * (p.full * C + (p.nbx - p.full) * ((C + p.K - 1) >> (6 - p.lg)));
+    return p;
+}
+// what lane `lane` of workgroup `tile` (the logical number, after xcd_tile) serves: row tile, plane (>= C: an empty slot of the last pack),
+// first column, lane index inside its slot and the slot's width in lanes (a full tile: the lane itself, 64).  Two integer divisions on
+// either path (the kernels decode their workgroup number with this: a division is some forty instructions of a launch's prologue).
+struct TileLane { int by, c, x, sl, lps; };
+__host__ __device__ inline TileLane coarse_tile_lane(const TilePlan &p, int C, int uw, int hx, int tile, int lane)
+{
+    TileLane t;
+    const int nfull = p.full * p.nby * C;
+    if (tile < nfull) {
+        const int q = tile / p.full;
+        t.c = q / p.nby; t.by = q - t.c * p.nby;
+        t.x = (tile - q * p.full) * uw - hx + 4 * lane; t.sl = lane; t.lps = 64;
+    } else {
+        const int k = tile - nfull, g = k / p.nby;
+        t.by = k - g * p.nby; t.lps = p.lps; t.sl = lane & (p.lps - 1);
+        t.c = (g << (6 - p.lg)) + (lane >> p.lg);
+        t.x = p.full * uw - hx + 4 * t.sl;
+    }
+    return t;
+}
+// band height (rows per lane) of a coarse-level launch; pack: the launch packs its last column tiles (coarse_tile_plan) where the band
+// height is at most pack_rows (k_cycle0's coarse forms pack with 4- and 6-row bands: 8-row bands have no registers left for a plane per lane)
+int  tb_gen_rows(int W, int H, int C, int hx, int hy, bool pack = false, int pack_rows = 8);
+int  tb_gen_rows_deep(int W, int H, int C, int hx, int hy, bool pack = false);   // the same for launches of depth 3 or 4: 4 or 6
 struct MGGeom;
 struct ComposeArgs;
 struct RagMember;
 constexpr int TBM_PLAIN = 0, TBM_PROLONG = 1, TBM_ZEROIN = 4;   // mode of launch_rb_tb_gen
-bool launch_rb_tb_gen(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &g, int mode, Field E, hipStream_t s, const RagMember *rag = nullptr, int lev = 0);
+bool launch_rb_tb_gen(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &g, int mode, Field E, hipStream_t s, const RagMember *rag = nullptr, int lev = 0,
+                      bool pack = true);      // pack = false: every column tile in a workgroup of its own (SC_LEGACY_UNPACKED_TILES)
 int  launch_rb_tb_prolong0(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &g, Field E, float *partial, hipStream_t s);
 int  tb_blocks_level0(int W, int H, int C, int sweeps);
 void launch_max_final(const float *d_partial, int n, unsigned *d_out, hipStream_t s);
@@ -253,7 +298,7 @@ void cycle0_row_geometry(int H, int sweeps, int &nby, int &step, int &hy);
 int  cycle0_blocks(int W, int H, int C, int sweeps);
 // coarse level: zero-guess pre-smoothing + residual + restriction fused (Uout = smoothed correction, Fc = next RHS)
 bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io = false,
-                         const RagMember *rag = nullptr, int lev = 0);
+                         const RagMember *rag = nullptr, int lev = 0, bool pack = true);
 
 // residual: d_out[0] = sum r^2, d_out[1] = sum lap^2 (double); d_partials holds >= 2*max_blocks doubles
 int  residual_max_blocks();
@@ -288,6 +333,8 @@ constexpr int C0_BANDS    = 64;     // a full cycle that leaves the float-table 
 constexpr int C0_L1_HALF  = 128;    // LEVEL 1's right-hand side and correction are float16: what level 0 restricts to and interpolates from, the level-1 launch's own F and Uout
 constexpr int C0_Q16_IN   = 256;    // Uin holds 16-bit fixed point (c0_load_q16): the field between the first level-0 launches of the fast path
 constexpr int C0_Q16_OUT  = 512;    // ... and so will Uout; a store that saturates reports itself (AbortFlag)
+constexpr int C0_PACK_ROWS = 6;     // ... with bands of at most this many rows per lane
+constexpr int C0_PACK     = 2048;   // coarse levels only (GEN, ZEROIN): the last column tile of several planes in one workgroup, plane and column per lane (coarse_tile_plan)
 constexpr int C0_RAG      = 1024;   // a SIZE CLASS (RagMember): strides and grid are the class's, all else the member's, read from rag[channel / 3]; tiles beyond its extent leave
 
 // One level-0 launch (sc_cycle0.hip): [prolongation of E +] `sweeps` red-black GS sweeps [+ residual + restriction into Fc]; launch_cycle0 derives (T, PRO, TAG) from these facts

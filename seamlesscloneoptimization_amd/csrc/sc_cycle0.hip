@@ -175,6 +175,11 @@ __device__ __forceinline__ float c0_comp(const float4 &v, int k) { return k == 0
 //          and the interpolation-tail weights in the restriction of the last coarse column / row.
 // ZEROIN = the incoming correction is identically zero and is not read (first visit of a level).
 // TAG    = the form of the launch: the C0_* bits of sc_common.h.
+// C0_PACK (coarse forms): the last column tile of several planes shares a workgroup (coarse_tile_plan, sc_common.h).  There the plane and
+// the column are per lane; rows, the LDS exchanges and the barriers are as in every other tile.  A full-wave shift at a slot's edge brings
+// in a value of the neighbouring plane where lane 0 / 63 of a full tile receive a zero: it lands in a halo lane at depth 0 and moves one
+// column per half-step, and 2T + 2 <= C0_HX keeps it out of the residual and the restriction of every exact column -- what is written is,
+// bit for bit, what the unpacked tiling writes.
 template <int T, int NW, int R, bool PRO, bool GEN, bool ZEROIN, int TAG = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_cycle0(Field Uin, Field Uout, Field F, Field Fc, Field E, MGGeom g,
                                                     float *__restrict__ partial, ComposeArgs comp, float4 *__restrict__ bands, LmNodes lm, AbortFlag sat,
@@ -212,7 +217,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     // 1-D launch; the tile this workgroup owns is chosen so that neighbouring tiles share an XCD (L2)
     const int nbx = (W + (256 - 2 * C0_HX) - 1) / (256 - 2 * C0_HX), nby = (H + (RH - 2 * HY) - 1) / (RH - 2 * HY);
     const int tile = xcd_tile(blockIdx.x, gridDim.x);
-    const int bx = tile % nbx, by = (tile / nbx) % nby, c = tile / (nbx * nby);
+    constexpr bool PACK = (TAG & C0_PACK) != 0;
+    static_assert(!PACK || (GEN && ZEROIN && !PRO && !RAG), "packed column tiles: the coarse forms of one size");
+    TileLane tl{};
+    if constexpr (PACK) tl = coarse_tile_lane(coarse_tile_plan(W, H, Uin.C, 256 - 2 * C0_HX, C0_HX, RH - 2 * HY, false), Uin.C, 256 - 2 * C0_HX, C0_HX, tile, lane);
+    const int bx = tile % nbx, by = PACK ? tl.by : (tile / nbx) % nby;
+    const int c = PACK ? min(tl.c, Uin.C - 1) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing
+    const int sl = PACK ? tl.sl : lane, lps = PACK ? tl.lps : 64;        // lane index inside its slot, lanes per slot
+    const bool live = !PACK || tl.c < Uin.C;                             // the slot holds a plane of the field
     if constexpr (RAG) {
         const RagMember &m = rag[c / 3];
         W = m.lw[lev]; H = m.lh[lev];
@@ -224,7 +236,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         if (PRO) E.H = m.lh[lev + 1];
         if ((TAG & C0_COMPOSED) != 0) { comp.g1 = m.g[lev + 1]; comp.E2.H = m.lh[lev + 2]; }
     }
-    const int x = bx * (256 - 2 * C0_HX) - C0_HX + 4 * lane;
+    const int x = PACK ? tl.x : bx * (256 - 2 * C0_HX) - C0_HX + 4 * lane;
     const int y0 = by * (RH - 2 * HY) - HY + wv * R;       // even
     float4 u[R], f[HF ? 1 : R];
     uint2 fh[HF ? R : 1];        // float16 right-hand side, kept packed (c0_minus_f)
@@ -305,7 +317,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     // the coarse windows clear of the last coarse column / row (no ghost value, nothing outside the coarse interior).  Those
     // waves take mask-free forms of the prolongation, the half-steps and the residual below; the test is wave-uniform and
     // the values they produce are the same, operation for operation, as the checked forms produce there.
-    const int xw = bx * (256 - 2 * C0_HX) - C0_HX;             // column of lane 0
+    const int xw = bx * (256 - 2 * C0_HX) - C0_HX;             // column of lane 0 (level 0 only: `inner`)
     // (Level 0 only.  The same split on the coarse levels -- regular stencil for waves clear of the last column / row --
     // was measured and changes nothing there: 20.6 vs 20.8 us on level 1 of a 2048^2 ROI; those launches are bounded by the
     // latency of one workgroup, not by instruction count; the many-round launches of a group of clones do not gain either:
@@ -622,7 +634,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         __syncthreads();
         const float2 hup = (wv > 0) ? hedge[0][wv - 1][lane] : make_float2(0.f, 0.f);
         const float2 hdn = (GEN && wv < NW - 1) ? hedge[1][wv + 1][lane] : make_float2(0.f, 0.f);
-        const bool lane_out = (lane >= C0_HXQ) && (lane < 64 - C0_HXQ);
+        const bool lane_out = (sl >= C0_HXQ) && (sl < lps - C0_HXQ) && live;
         float *__restrict__ fc = Fc.at(c);
         const float fx0 = (I == g.x.nc) ? 2.0f * g.x.inv_last : 1.0f;
         const float fx1 = (I + 1 == g.x.nc) ? 2.0f * g.x.inv_last : 1.0f;
@@ -657,7 +669,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     }
 
     // ------------------------------------------------------------------ write back the exact inner tile
-    if (lane < C0_HXQ || lane >= 64 - C0_HXQ || x >= P || x >= W) return;
+    if (sl < C0_HXQ || sl >= lps - C0_HXQ || !live || x >= P || x >= W) return;
     if constexpr (OUT) {
         // the result leaves as output values: u + node correction (the arithmetic of the post-process, sc_kernels.hip),
         // clamped to [0, 255], truncated; plane c of Uout's memory, rows of P bytes.  The splice kernel interleaves.
@@ -823,12 +835,19 @@ int cycle0_blocks(int W, int H, int C, int sweeps)
 // launch.  Uout receives the smoothed correction, Fc the next level's RHS.
 // rag / lev: a size class (C0_RAG): level `lev` of every member's own hierarchy; instantiated for the depths the default
 // schedule uses -- four sweeps on float16 fields (level 1) and two on float ones (the levels below it)
+// pack: the last column tile of several planes in one workgroup wherever the plan says so (C0_PACK twin, smaller grid)
 template <int T, int R, int TAG = 0, int NW = C0_NW>
-static bool launch_cn(Field Uout, Field F, Field Fc, const MGGeom &g, hipStream_t s, const RagMember *rag = nullptr, int lev = 0)
+static bool launch_cn(Field Uout, Field F, Field Fc, const MGGeom &g, hipStream_t s, const RagMember *rag, int lev, bool pack)
 {
     constexpr int RH = NW * R, HY = 2 * T + 2;
     Field none{};
-    const int blocks = ((F.W + (256 - 2 * C0_HX) - 1) / (256 - 2 * C0_HX)) * ((F.H + (RH - 2 * HY) - 1) / (RH - 2 * HY)) * F.C;
+    const TilePlan tp = coarse_tile_plan(F.W, F.H, F.C, 256 - 2 * C0_HX, C0_HX, RH - 2 * HY, rag != nullptr, pack && R <= C0_PACK_ROWS);
+    const int blocks = tp.blocks;
+    if constexpr (R <= C0_PACK_ROWS) if (tp.K >= 2) {
+        hipLaunchKernelGGL((k_cycle0<T, NW, R, false, true, true, TAG | C0_PACK>), dim3(blocks), dim3(NW * 64), 0, s, F /*unused Uin: geometry only*/,
+                           Uout, F, Fc, none, g, (float *)nullptr, ComposeArgs(), (float4 *)nullptr, LmNodes(), AbortFlag(), (const RagMember *)nullptr, 0);
+        return true;
+    }
     if (rag) {
         if constexpr ((T == 4 && TAG == C0_L1_HALF && R != 8) || (T == 2 && TAG == 0 && NW == C0_NW))
             hipLaunchKernelGGL((k_cycle0<T, NW, R, false, true, true, TAG | C0_RAG>), dim3(blocks), dim3(NW * 64), 0, s, F, Uout, F, Fc, none, g,
@@ -842,37 +861,38 @@ static bool launch_cn(Field Uout, Field F, Field Fc, const MGGeom &g, hipStream_
 }
 
 // workgroups of a coarse-level launch with NW waves of R rows each at depth T
-static int cn_blocks(const Field &F, int T, int R, int NW)
+static int cn_blocks(const Field &F, int T, int R, int NW, bool size_class, bool pack)
 {
     const int RH = NW * R, HY = 2 * T + 2;
-    return ((F.W + (256 - 2 * C0_HX) - 1) / (256 - 2 * C0_HX)) * ((F.H + (RH - 2 * HY) - 1) / (RH - 2 * HY)) * F.C;
+    return coarse_tile_plan(F.W, F.H, F.C, 256 - 2 * C0_HX, C0_HX, RH - 2 * HY, size_class, pack).blocks;
 }
 
 // half_io: the level's own right-hand side and the correction it writes are float16 (level 1 of the composed schedule, 4 sweeps)
 // rag: a size class makes the same choices from the class's dimensions; false where it has no such form (launch_cn)
-bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io, const RagMember *rag, int lev)
+bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io, const RagMember *rag, int lev, bool pack)
 {
+    pack = pack && !rag;
     if (half_io) {
         if (sweeps != 4) return false;
-        const int R4 = tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
+        const int R4 = tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2, pack);
         // Round 4: a single clone's level 1 at 2048^2 is 555 eight-wave workgroups on 512 slots (two per CU): 43 of them make a second
         // round and the launch takes 18 us for 10 us of work.  Sixteen-wave workgroups (96-row windows, 76 of them exact instead of
         // 28 of 48; one per CU) need 210: one round.  Taken whenever it turns more than one round of the 8-wave form into one.
         // ... and for a GROUP of clones (tens of rounds either way) whenever the 16-wave tiling needs fewer waves in total: 76 of 96
         // rows exact instead of 28 of 48 (+0.7 % on the bench step, tools/ab_step.py).
-        const long b8 = cn_blocks(F, 4, 6, 8), b16 = cn_blocks(F, 4, 6, 16);
-        if (R4 == 6 && ((b8 > 512 && b16 <= 256) || (F.C > 3 && 2 * b16 < b8))) return launch_cn<4, 6, C0_L1_HALF, 16>(Uout, F, Fc, g, s, rag, lev);
-        return R4 == 6 ? launch_cn<4, 6, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev) : launch_cn<4, 4, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev);
+        const long b8 = cn_blocks(F, 4, 6, 8, rag != nullptr, pack), b16 = cn_blocks(F, 4, 6, 16, rag != nullptr, pack);
+        if (R4 == 6 && ((b8 > 512 && b16 <= 256) || (F.C > 3 && 2 * b16 < b8))) return launch_cn<4, 6, C0_L1_HALF, 16>(Uout, F, Fc, g, s, rag, lev, pack);
+        return R4 == 6 ? launch_cn<4, 6, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev, pack) : launch_cn<4, 4, C0_L1_HALF>(Uout, F, Fc, g, s, rag, lev, pack);
     }
     if (sweeps < 1 || sweeps > 4) return false;
-    const int R = sweeps >= 3 ? tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2) : tb_gen_rows(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2);
+    const int R = sweeps >= 3 ? tb_gen_rows_deep(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2, pack) : tb_gen_rows(F.W, F.H, F.C, C0_HX, 2 * sweeps + 2, pack, C0_PACK_ROWS);
     switch (sweeps) {
-    case 1: return R == 8 ? launch_cn<1, 8>(Uout, F, Fc, g, s, rag, lev) : R == 6 ? launch_cn<1, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<1, 4>(Uout, F, Fc, g, s, rag, lev);
-    case 2: return R == 8 ? launch_cn<2, 8>(Uout, F, Fc, g, s, rag, lev) : R == 6 ? launch_cn<2, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<2, 4>(Uout, F, Fc, g, s, rag, lev);
+    case 1: return R == 8 ? launch_cn<1, 8>(Uout, F, Fc, g, s, rag, lev, pack) : R == 6 ? launch_cn<1, 6>(Uout, F, Fc, g, s, rag, lev, pack) : launch_cn<1, 4>(Uout, F, Fc, g, s, rag, lev, pack);
+    case 2: return R == 8 ? launch_cn<2, 8>(Uout, F, Fc, g, s, rag, lev, pack) : R == 6 ? launch_cn<2, 6>(Uout, F, Fc, g, s, rag, lev, pack) : launch_cn<2, 4>(Uout, F, Fc, g, s, rag, lev, pack);
     // deeper pre-smoothing (a level that gets no post-smoothing: 3 or 4 sweeps): 4- or 6-row bands (tb_gen_rows_deep);
     // 8-row bands spill with the general coefficients (23 us against 20.6 us for level 1 of a 2048^2 ROI)
-    case 3: return R == 6 ? launch_cn<3, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<3, 4>(Uout, F, Fc, g, s, rag, lev);
-    default: return R == 6 ? launch_cn<4, 6>(Uout, F, Fc, g, s, rag, lev) : launch_cn<4, 4>(Uout, F, Fc, g, s, rag, lev);
+    case 3: return R == 6 ? launch_cn<3, 6>(Uout, F, Fc, g, s, rag, lev, pack) : launch_cn<3, 4>(Uout, F, Fc, g, s, rag, lev, pack);
+    default: return R == 6 ? launch_cn<4, 6>(Uout, F, Fc, g, s, rag, lev, pack) : launch_cn<4, 4>(Uout, F, Fc, g, s, rag, lev, pack);
     }
 }
 

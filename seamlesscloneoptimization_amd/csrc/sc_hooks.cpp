@@ -422,6 +422,24 @@ int sc_hip_time_cycle0_form(void *p, int form, int launches, float *ms_per_launc
     return SC_OK;
 }
 
+int sc_hip_coarse_tile_plan(const int *facts, int *plan)
+{
+    if (!facts || !plan) return SC_ERR_BAD_ARG;
+    const int W = facts[0], H = facts[1], C = facts[2], uw = facts[3], hx = facts[4], rows = facts[5], first = facts[8], n = facts[9];
+    if (W < 1 || H < 1 || C < 1 || hx < 4 || hx % 4 || uw != 256 - 2 * hx || rows < 1 || first < 0 || n < 0) return SC_ERR_BAD_ARG;
+    const TilePlan tp = coarse_tile_plan(W, H, C, uw, hx, rows, facts[6] != 0, facts[7] == 0);
+    if ((long)first + n > tp.blocks) return SC_ERR_BAD_ARG;
+    plan[0] = tp.full; plan[1] = tp.lps; plan[2] = tp.K; plan[3] = tp.blocks;
+    for (int k = 0; k < n; ++k) {
+        int *o = plan + 4 + 130 * (size_t)k;
+        for (int lane = 0; lane < 64; ++lane) {
+            const TileLane tl = coarse_tile_lane(tp, C, uw, hx, first + k, lane);
+            o[0] = tl.by; o[1] = tl.lps; o[2 + 2 * lane] = tl.c; o[3 + 2 * lane] = tl.x;
+        }
+    }
+    return SC_OK;
+}
+
 int sc_hip_cycle0_form(const int *facts, int index, int form[3])
 {
     if (!form) return SC_ERR_BAD_ARG;

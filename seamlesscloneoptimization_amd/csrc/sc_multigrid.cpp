@@ -498,7 +498,7 @@ static int smooth_gen(Instance *I, size_t l, int n, int mode, Field E)
     int left = n;
     while (left > 0) {
         const int T = std::min(2, left);
-        if (!launch_rb_tb_gen(L.U, L.T, L.F, T, L.g, mode, E, I->stream, I->rag.dev, (int)l)) {
+        if (!launch_rb_tb_gen(L.U, L.T, L.F, T, L.g, mode, E, I->stream, I->rag.dev, (int)l, !legacy_path(I->opts, SC_LEGACY_UNPACKED_TILES))) {
             if (I->rag.dev) { I->err = "size class: coarse-level form not instantiated"; return SC_ERR_BAD_ARG; }
             break;
         }
@@ -551,7 +551,8 @@ static int vcycle(Instance *I, size_t l, int pre, int post, unsigned no_post = 0
     if (l == 0) {
         if ((rc = run_sweeps(I, SC_METHOD_RBGS, pre_here, 1.0f, I->opts.sweeps_per_launch))) return rc;
     } else if (pre_here > 0 && I->opts.sweeps_per_launch != 1 &&
-               launch_cycle_coarse(L.T, L.F, Lc.F, L.g, pre_here, I->stream, l == 1 && skip_post && mg_level1_half(I), I->rag.dev, (int)l)) {
+               launch_cycle_coarse(L.T, L.F, Lc.F, L.g, pre_here, I->stream, l == 1 && skip_post && mg_level1_half(I), I->rag.dev, (int)l,
+                                   !legacy_path(I->opts, SC_LEGACY_UNPACKED_TILES))) {
         std::swap(L.U, L.T);      // one launch did all three
         restricted = true;
     } else if (I->rag.dev) {

@@ -46,6 +46,12 @@ __device__ __forceinline__ void tb_load(const float *__restrict__ p, int P, int 
 constexpr int TB_PROLONG = 1, TB_MAXC = 2, TB_ZEROIN = 4;
 constexpr int TB_TAG = 8;   // no effect on the code: a second symbol for the isolated roofline launches (see k_jacobi)
 constexpr int TB_RAG = 16;  // the launch serves a size class (RagMember, sc_common.h): level `lev` of every member's own hierarchy
+// TB_PACK (coarse levels): the last column tile of several planes shares a workgroup (coarse_tile_plan, sc_common.h).  In those workgroups
+// the plane and the column are per lane; rows, the LDS edge exchange and the barriers are as in every other tile.  A full-wave shift at a
+// slot's edge brings in a value of the neighbouring plane where lane 0 / 63 of a full tile receive a zero: it lands in a halo lane at
+// depth 0 and moves one column per half-step, so 2T <= HX keeps it out of every exact column -- the values written are those of the
+// unpacked tiling, bit for bit.
+constexpr int TB_PACK = 32;
 
 template <int T, int NW, int R, bool SOR, bool GEN, int FLAGS, int HXQ = 1>
 __global__ __launch_bounds__(NW * 64) void k_rb_tb(Field Uin, Field Uout, Field F, float omega, MGGeom g, Field E,
@@ -59,9 +65,16 @@ __global__ __launch_bounds__(NW * 64) void k_rb_tb(Field Uin, Field Uout, Field 
     int W = Uin.W, H = Uin.H;
     const int P = Uin.pitch;
     // 1-D launch; neighbouring tiles are given to the same XCD so that they share its L2 (sc_wave.h)
+    constexpr bool PACK = (FLAGS & TB_PACK) != 0;
+    static_assert(!PACK || (GEN && !(FLAGS & (TB_RAG | TB_MAXC))), "packed column tiles: coarse levels of one size, no per-workgroup maximum");
     const int nbx = (W + (256 - 2 * HX) - 1) / (256 - 2 * HX), nby = (H + (RH - 2 * HY) - 1) / (RH - 2 * HY);
     const int tile = xcd_tile(blockIdx.x, gridDim.x);
-    const int bx = tile % nbx, by = (tile / nbx) % nby, c = tile / (nbx * nby);
+    TileLane tl{};
+    if constexpr (PACK) tl = coarse_tile_lane(coarse_tile_plan(W, H, Uin.C, 256 - 2 * HX, HX, RH - 2 * HY, false), Uin.C, 256 - 2 * HX, HX, tile, lane);
+    const int bx = tile % nbx, by = PACK ? tl.by : (tile / nbx) % nby;
+    const int c = PACK ? min(tl.c, Uin.C - 1) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing
+    const int sl = PACK ? tl.sl : lane, lps = PACK ? tl.lps : 64;        // lane index inside its slot, lanes per slot
+    const bool live = !PACK || tl.c < Uin.C;                             // the slot holds a plane of the field
     if constexpr ((FLAGS & TB_RAG) != 0) {      // the member's own level inside the class's strides; tiles beyond it leave (block-uniform, before any barrier)
         const RagMember &m = rag[c / 3];
         W = m.lw[lev]; H = m.lh[lev];
@@ -72,7 +85,7 @@ __global__ __launch_bounds__(NW * 64) void k_rb_tb(Field Uin, Field Uout, Field 
         g = m.g[lev];
         if (FLAGS & TB_PROLONG) E.H = m.lh[lev + 1];
     }
-    const int x = bx * (256 - 2 * HX) - HX + 4 * lane;
+    const int x = PACK ? tl.x : bx * (256 - 2 * HX) - HX + 4 * lane;
     const int ry = by * (RH - 2 * HY) - HY;
     const int y0 = ry + wv * R;
     float4 u[R], f[R];
@@ -172,7 +185,7 @@ __global__ __launch_bounds__(NW * 64) void k_rb_tb(Field Uin, Field Uout, Field 
         }
     }
     // write back the exact inner tile (ring rows/columns are copied through unchanged)
-    if (lane < HXQ || lane >= 64 - HXQ || x >= P || x >= W) return;
+    if (sl < HXQ || sl >= lps - HXQ || !live || x >= P || x >= W) return;
     float *__restrict__ out = Uout.at(c);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -267,6 +280,17 @@ static int launch_rb_t(Field Uin, Field Uout, Field F, float omega, const MGGeom
     return blocks;
 }
 
+// a coarse level of one size: the TB_PACK twin and its smaller grid wherever the plan packs the last column tile, else the form above
+template <int T, int MODE, int R>
+static void launch_rb_gen(Field Uin, Field Uout, Field F, const MGGeom &g, Field E, hipStream_t s, bool pack)
+{
+    static_assert(2 * T <= TB_HX, "the coarse-level forms have a one-lane column halo");
+    const TilePlan tp = coarse_tile_plan(Uin.W, Uin.H, Uin.C, 256 - 2 * TB_HX, TB_HX, 8 * R - 4 * T, false, pack);
+    if (tp.K < 2) { launch_rb_t<T, 8, false, true, MODE, R>(Uin, Uout, F, 1.0f, g, E, nullptr, s); return; }
+    hipLaunchKernelGGL((k_rb_tb<T, 8, R, false, true, MODE | TB_PACK, 1>), dim3(tp.blocks), dim3(8 * 64), 0, s, Uin, Uout, F, 1.0f, g, E, (float *)nullptr,
+                       (const RagMember *)nullptr, 0);
+}
+
 bool launch_rb_tb(Field Uin, Field Uout, Field F, int sweeps, float omega, hipStream_t s, bool tag)
 {
     const bool sor = omega != 1.0f;
@@ -318,14 +342,11 @@ long tb_big_side()
 // ~100 VGPRs two workgroups fit a CU, so what matters is the number of rounds the grid needs over the
 // chip's 512 slots: take the smallest R whose grid fits one round; if none does (large levels) the
 // short 4-row bands won every measurement on single clones (tools/bench_configs.py c3/c4).
-int tb_gen_rows(int W, int H, int C, int hx, int hy)
+int tb_gen_rows(int W, int H, int C, int hx, int hy, bool pack, int pack_rows)
 {
     if ((long)W * H >= tb_big_side() * tb_big_side()) return 8;
-    const int nbx = (W + (256 - 2 * hx) - 1) / (256 - 2 * hx);
-    for (int R = 4; R <= 8; R += 2) {
-        const int rows = 8 * R - 2 * hy;
-        if (nbx * ((H + rows - 1) / rows) * C <= 512) return R;
-    }
+    for (int R = 4; R <= 8; R += 2)
+        if (coarse_tile_plan(W, H, C, 256 - 2 * hx, hx, 8 * R - 2 * hy, false, pack && R <= pack_rows).blocks <= 512) return R;
     // Many rounds either way.  A single clone's large levels: the short 4-row bands (above).  A GROUP of clones (C > 3: tens of
     // rounds, throughput not latency): 6-row bands -- 36 of 48 rows exact at depth 2 instead of 20 of 32 -- measured +0.9 % on the
     // bench step of 32 x 2048^2 (round 4, tools/ab_step.py: 6.263 -> 6.205 ms, three alternating repetitions within 0.1 %).
@@ -336,19 +357,19 @@ int tb_gen_rows(int W, int H, int C, int hx, int hy)
 // is 2T + 2 = 8 or 10 rows, so 4-row bands keep only 16 or 12 of 32 rows and are worth it only while they make the grid
 // fit one round; beyond that 6-row bands (28 of 48 at depth 4) are the efficient form -- 8-row bands spill with the
 // general coefficients.  Measured on level 1 of a group of eight 2048^2 clones: 141 us with 4 rows, 103 us with 6.
-int tb_gen_rows_deep(int W, int H, int C, int hx, int hy)
+int tb_gen_rows_deep(int W, int H, int C, int hx, int hy, bool pack)
 {
-    const int R = tb_gen_rows(W, H, C, hx, hy);
+    const int R = tb_gen_rows(W, H, C, hx, hy, pack, C0_PACK_ROWS);
     if (R != 4) return 6;
-    const int nbx = (W + (256 - 2 * hx) - 1) / (256 - 2 * hx), rows = 8 * 4 - 2 * hy;
-    return (nbx * ((H + rows - 1) / rows) * C <= 512) ? 4 : 6;
+    return coarse_tile_plan(W, H, C, 256 - 2 * hx, hx, 8 * 4 - 2 * hy, false, pack).blocks <= 512 ? 4 : 6;
 }
 
 // coarse multigrid levels: Gauss-Seidel only (omega = 1).  mode: 0 plain, TB_ZEROIN, TB_PROLONG (with E).
-bool launch_rb_tb_gen(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &g, int mode, Field E, hipStream_t s, const RagMember *rag, int lev)
+bool launch_rb_tb_gen(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &g, int mode, Field E, hipStream_t s, const RagMember *rag, int lev, bool pack)
 {
     if (sweeps != 1 && sweeps != 2) return false;
-    const int R = tb_gen_rows(Uin.W, Uin.H, Uin.C, TB_HX, 2 * sweeps);
+    pack = pack && !rag;
+    const int R = tb_gen_rows(Uin.W, Uin.H, Uin.C, TB_HX, 2 * sweeps, pack);
     if (rag) {          // a size class: the post-smoothing form of the default schedule (two sweeps behind the prolongation)
         if (sweeps != 2 || mode != TB_PROLONG) return false;
         R == 8 ? launch_rb_t<2, 8, false, true, TB_PROLONG | TB_RAG, 8>(Uin, Uout, F, 1.0f, g, E, nullptr, s, rag, lev)
@@ -357,9 +378,9 @@ bool launch_rb_tb_gen(Field Uin, Field Uout, Field F, int sweeps, const MGGeom &
         return true;
     }
 #define SC_GEN_R(TT, MODE)                                                                                          \
-    (R == 8 ? launch_rb_t<TT, 8, false, true, MODE, 8>(Uin, Uout, F, 1.0f, g, E, nullptr, s)                        \
-   : R == 6 ? launch_rb_t<TT, 8, false, true, MODE, 6>(Uin, Uout, F, 1.0f, g, E, nullptr, s)                        \
-            : launch_rb_t<TT, 8, false, true, MODE, 4>(Uin, Uout, F, 1.0f, g, E, nullptr, s))
+    (R == 8 ? launch_rb_gen<TT, MODE, 8>(Uin, Uout, F, g, E, s, pack)                                               \
+   : R == 6 ? launch_rb_gen<TT, MODE, 6>(Uin, Uout, F, g, E, s, pack)                                               \
+            : launch_rb_gen<TT, MODE, 4>(Uin, Uout, F, g, E, s, pack))
 #define SC_GEN_CASE(TT)                                                                                             \
     { if (mode == 0) SC_GEN_R(TT, 0); else if (mode == TB_ZEROIN) SC_GEN_R(TT, TB_ZEROIN); else SC_GEN_R(TT, TB_PROLONG); }
     if (sweeps == 1) SC_GEN_CASE(1) else SC_GEN_CASE(2)

@@ -1,6 +1,6 @@
 """A/B of sc_solver_opts variants on the bench's timed step, in ONE process on one box (boxes differ by +-2 %):
 python tools/ab_step.py "<name>=<field>:<value>[,<field>:<value>...]" ...      e.g.  base=flags:0 f32=flags:2050
-Fields: any sc_solver_opts member; `reserved0` sets reserved[0]."""
+Fields: any sc_solver_opts member (flags:64,legacy_paths:<SC_LEGACY_* bits> runs a superseded launch form)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,13 +27,10 @@ for b in range(batch):
 
 def apply(fields):
     o = inst.get_solver()
-    o.reserved[0] = 0
+    o.legacy_paths = 0
     o.flags = 0
     for k, v in fields:
-        if k == "reserved0":
-            o.reserved[0] = v
-        else:
-            setattr(o, k, v)
+        setattr(o, k, v)
     import ctypes as C
     assert pool.L.sc_hip_pool_set_solver(pool.h, C.byref(o)) == 0
 
