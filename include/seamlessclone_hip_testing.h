@@ -136,6 +136,24 @@ SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
  * ranges. */
 SC_API int sc_hip_coarse_tile_plan(const int *facts, int *plan);
 
+/* Host only, nothing is launched: the level-0 launches of a fused multigrid solve (csrc/sc_multigrid.cpp: fused_next, the function the solve
+ * itself asks) for facts[12] = pre, post (1 or 2), budget (max_sweeps, 1..64), tol > 0, out_wanted (the splice is armed, no tol, no
+ * SC_FLAG_KEEP_FIELD, V(2,2)), q16 (the field starts as 16-bit fixed point), u_half (the initial field is float16), level 1 composed,
+ * SC_LEGACY_SEPARATE_RESTRICT, the early node correction's kind (0 nothing to add, 1 allowed, 2 not, 3 allowed if the judged update is
+ * small), bytes form instantiated, small (more than 3 planes or fewer than 3 << 18 pixels) -- and for what the read-back behind each
+ * judged launch shows: verdicts[k] = 0 accept, 1 reject, 2 an update the stop rule accepts but the early condition does not (an accept
+ * where that condition does not apply), 3 the saturation word (an accept unless q16); the last entry repeats, none = accept.
+ * rows receives SC_FUSED_ROW ints per launch -- kind (1 first launch, 2 full cycle, 3 full cycle before the judged one, 4 judged cycle
+ * leaving bytes, 5 judged cycle leaving its field, 6 catch-up), sweeps, prolong, final_cycle, out_bytes, u_half, q16_in, q16_out,
+ * composed, bands (sweeps the bands buffer it receives is sized for, 0: none), lm (carries the early node correction), nodes (a node
+ * correction is computed from its result: 1 on the main stream, 2 on the second, 3 there is nothing to add, 0 no), judged (the stop rule
+ * reads its maxima), coarse_first (levels 1 .. bottom run in front of it), sat (it is given the saturation word), bands asked (sweeps the
+ * bands buffer asked for in front of it is sized for), early kind asked in front of it, cycles completed in front of it -- and behind the
+ * last row sc_run_info's sweeps and sweep_launches and the solve's code (0, SC_ERR_NOT_CONVERGED, 1: repeated on float fields).
+ * Returns the number of launches, SC_ERR_BAD_ARG for facts outside their ranges or fewer than SC_FUSED_ROW * launches + 3 ints of capacity. */
+#define SC_FUSED_ROW 18
+SC_API int sc_hip_fused_schedule(const int *facts, const int *verdicts, int nverdicts, int *rows, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,7 +129,7 @@ def prolong(E, dx: Dim, dy: Dim):
     return out.astype(F32)
 
 
-# ---- which level the library's bottom kernel solves directly (mirrors sc_multigrid.cpp: bottom_start, build_fd)
+# ---- which level the library's bottom kernel solves directly (mirrors sc_mg_levels.cpp: bottom_start, build_fd)
 MG_BOTTOM_LDS_BYTES = 152 * 1024
 MG_BOTTOM_MAX_LEVELS = 12
 
@@ -148,7 +148,7 @@ def bottom_start(levels) -> int:
 
 
 def bottom_level(levels, matrix_cores=True):
-    """The library's I->mg_bottom (sc_multigrid.cpp build_levels): the first level handled by the bottom of the cycle.  Rounds
+    """The library's I->mg_bottom (sc_mg_levels.cpp build_levels): the first level handled by the bottom of the cycle.  Rounds
     1-3 and SC_FLAG_BOTTOM_F32: the LDS-fit rule (bottom_start).  Default since round 4: the first level >= 2 with at most 127
     unknowns per side is the deepest one smoothed (k_mg_tail holds it in registers) and the level below it is the bottom; a ROI
     whose level 1 already fits the matrix-core solve (<= 96 per side) keeps that."""
@@ -167,7 +167,7 @@ def bottom_level(levels, matrix_cores=True):
 def direct_level(levels, matrix_cores=True):
     """Index of the level solved exactly (fast diagonalisation), or None.  matrix_cores (the library's default since round 4):
     the bottom's first level is solved on the matrix cores whenever both sides have at most 96 unknowns, without an LDS budget
-    to meet (sc_multigrid.cpp build_fd, k_mg_bottom_mm); False = SC_FLAG_BOTTOM_F32, the LDS-resident float32 form."""
+    to meet (sc_mg_levels.cpp build_fd, k_mg_bottom_mm); False = SC_FLAG_BOTTOM_F32, the LDS-resident float32 form."""
     planes = 0
     b = bottom_level(levels, matrix_cores)
     for l in range(b, len(levels)):

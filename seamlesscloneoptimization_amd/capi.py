@@ -361,6 +361,8 @@ def load():
     L.sc_hip_cycle0_form.restype = C.c_int
     L.sc_hip_coarse_tile_plan.argtypes = [i32p, i32p]
     L.sc_hip_coarse_tile_plan.restype = C.c_int
+    L.sc_hip_fused_schedule.argtypes = [i32p, i32p, C.c_int, i32p, C.c_int]
+    L.sc_hip_fused_schedule.restype = C.c_int
     L.sc_hip_plan_groups.argtypes = [i32p, C.c_int, C.c_int, C.POINTER(SolverOpts), i32p, i32p]
     L.sc_hip_plan_groups.restype = C.c_int
     L.sc_hip_plan_size.argtypes = [C.c_int, C.c_int, C.POINTER(SolverOpts), i32p]
@@ -1137,6 +1139,30 @@ def coarse_tile_plan(W, H, C_, useful, halo, rows, size_class=False, unpacked=Fa
         raise SeamlessCloneError(rc, "coarse_tile_plan")
     t = out[4:].reshape(n, 130)
     return tuple(int(v) for v in head), (t[:, 0], t[:, 1], t[:, 2::2], t[:, 3::2])
+
+
+FUSED_FACTS = ("pre", "post", "budget", "tol", "out_wanted", "q16", "u_half", "composed", "separate_restrict", "early_kind", "bytes_form", "small")
+FUSED_ROW = ("kind", "sweeps", "prolong", "final_cycle", "out_bytes", "u_half", "q16_in", "q16_out", "composed", "bands", "lm", "nodes", "judged",
+             "coarse_first", "sat", "bands_asked", "early_asked", "cycle")
+
+
+def fused_schedule(verdicts=(), **facts):
+    """Host-only: the level-0 launches of a fused multigrid solve with these facts (FUSED_FACTS; defaults: the default clone's) whose
+    judged launches meet `verdicts` (sc_hip_fused_schedule): ([one dict of FUSED_ROW per launch], sweeps, sweep_launches, code)."""
+    d = dict(pre=2, post=2, budget=30, tol=0, out_wanted=1, q16=1, u_half=1, composed=1, separate_restrict=0, early_kind=1, bytes_form=1, small=1)
+    unknown = sorted(set(facts) - set(d))
+    if unknown:
+        raise TypeError("fused_schedule: no such fact: %s" % unknown)
+    d.update(facts)
+    f = (C.c_int * len(FUSED_FACTS))(*[int(d[k]) for k in FUSED_FACTS])
+    v = (C.c_int * max(1, len(verdicts)))(*[int(x) for x in verdicts])
+    cap = len(FUSED_ROW) * (3 * int(d["budget"]) + 2) + 3
+    out = (C.c_int * cap)()
+    n = load().sc_hip_fused_schedule(f, v, len(verdicts), out, cap)
+    if n < 0:
+        raise SeamlessCloneError(n, "fused_schedule")
+    k = len(FUSED_ROW)
+    return [dict(zip(FUSED_ROW, out[k * i:k * i + k])) for i in range(n)], out[k * n], out[k * n + 1], out[k * n + 2]
 
 
 def cycle0_forms():

@@ -15,6 +15,7 @@
 //   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
 //      launch, so it is not reachable here).
+//   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include <atomic>
@@ -398,6 +399,31 @@ int main()
         }
         sc_weighted_params p{ SC_POISSON_GUIDANCE, 0.f, 0, 0.f };
         if (sc_hip_weighted_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_weighted_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("weighted_check (null)");
+    }
+    // 8: the schedule of a fused multigrid solve over a few hundred inputs: every row a launch that exists, the counts those of the rows
+    {
+        std::vector<int> rows(SC_FUSED_ROW * (3 * 6 + 2) + 3);
+        unsigned s = 4242u;
+        for (int i = 0; i < 600; ++i) {
+            int facts[12], verdicts[4];
+            for (int k = 0; k < 12; ++k) { s = s * 1664525u + 1013904223u; facts[k] = (int)((s >> 13) & 1u); }
+            facts[0] += 1; facts[1] += 1; facts[2] = 1 + i % 6; facts[9] = (i / 6) % 4;
+            for (int k = 0; k < 4; ++k) { s = s * 1664525u + 1013904223u; verdicts[k] = (int)((s >> 11) & 3u); }
+            const int n = sc_hip_fused_schedule(facts, verdicts, i % 5, rows.data(), (int)rows.size());
+            if (n < 1 || n > 3 * facts[2] + 1) return fail("fused_schedule: launches");
+            int launches = 0;
+            for (int r = 0; r < n; ++r) {
+                const int *row = &rows[SC_FUSED_ROW * (size_t)r];
+                if (row[0] < 1 || row[0] > 6 || row[1] < 1 || row[1] > 4 || row[17] < 0 || row[17] >= facts[2]) return fail("fused_schedule: a row");
+                launches += row[0] != 4;
+            }
+            const int *tail = &rows[SC_FUSED_ROW * (size_t)n];
+            if (tail[0] < 1 || tail[0] > facts[2] || tail[1] < launches || tail[1] > n) return fail("fused_schedule: counts");
+            if (sc_hip_fused_schedule(facts, verdicts, i % 5, rows.data(), SC_FUSED_ROW * n + 2) != SC_ERR_BAD_ARG) return fail("fused_schedule wrote past its capacity");
+        }
+        int facts[12] = { 2, 2, 0, 0, 1, 1, 1, 1, 0, 1, 1, 1 };
+        if (sc_hip_fused_schedule(facts, nullptr, 0, rows.data(), (int)rows.size()) != SC_ERR_BAD_ARG) return fail("fused_schedule took budget 0");
+        if (sc_hip_fused_schedule(nullptr, nullptr, 0, rows.data(), (int)rows.size()) != SC_ERR_BAD_ARG) return fail("fused_schedule (null)");
     }
     printf("sanitize_main: clean\n");
     return 0;

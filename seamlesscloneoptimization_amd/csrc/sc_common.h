@@ -390,7 +390,7 @@ void launch_fill_zero(Field U, hipStream_t s);
 constexpr int MG_BOTTOM_MAX_LEVELS = 12;
 constexpr int MG_BOTTOM_LDS_BYTES = 152 * 1024;   // of the CU's 160 KiB
 struct MGBottomLevel { MGGeom g; float omega; int offU, offF, pitch; };   // LDS offsets / row pitch in floats
-// Direct solve of one bottom level by fast diagonalisation (sc_multigrid.cpp builds the matrices):
+// Direct solve of one bottom level by fast diagonalisation (sc_mg_levels.cpp has the matrices built: build_fd):
 // the level's operator is a tensor sum Tx (x) I + I (x) Ty of two tridiagonal 1-D operators, so with
 // Tx = Vx Lx Vx^-1, Ty = Vy Ly Vy^-1 the solution of A U = F is
 //     U = Vy [ (Vy^-1 F Vx^-T) / (ly_j + lx_i) ] Vx^T      -- four small dense products in LDS.

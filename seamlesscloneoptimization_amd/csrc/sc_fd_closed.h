@@ -18,7 +18,7 @@
 // keeps its relative accuracy.  One thread per eigenvalue: 50 bisection steps of two sincos each; no iteration over the matrix.
 //
 // E T E^-1 is symmetric for E = diag(1, .., 1, 1/sqrt(cw)); with q_k = E v_k / |E v_k|:  T = V L V^-1,  V = E^-1 Q,  V^-1 = Q^T E
-// (the same objects sc_multigrid.cpp's QL-based FD1 holds; sc_hip_selftest_host compares the two).
+// (the same objects sc_fd_selftest.cpp's QL-based FD1 holds; sc_hip_selftest_host compares the two).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -24,6 +24,79 @@ static int float_rhs(Instance *I)
     return SC_OK;
 }
 
+// Measurement hook (sc_hip_time_coarse_chain): the launch-bound part of a cycle -- levels 2 .. bottom .. 2: seven dependent launches
+// for a 2048^2 clone, 2 % of the unknowns -- run `reps` times back to back on the hierarchy the last multigrid solve left, (a) as
+// plain launches and (b) captured once into a HIP graph and replayed.  hipEvents on the instance's stream around each batch.
+// Values are discarded (level 2's right-hand side is whatever the last cycle left there).
+static int mg_time_coarse_chain(Instance *I, int reps, float *ms_eager, float *ms_graph, int *launches)
+{
+    if (I->mg.size() < 4 || I->mg_bottom < 3 || !mg_composes_level1(I)) { I->err = "time_coarse_chain: run a multigrid clone of at least ~500^2 first"; return SC_ERR_BAD_ARG; }
+    const int pre = mg_params(I->opts).pre, post = mg_params(I->opts).post;
+    int rc;
+    if ((rc = fd_wait(I))) return rc;
+    *launches = (int)(2 * (I->mg_bottom - 2) + 1) - (tail_serves(I, I->mg_bottom - 1) ? 2 : 0);
+    if ((rc = vcycle(I, 2, pre, post))) return rc;                       // warm
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    for (int i = 0; i < reps; ++i) if ((rc = vcycle(I, 2, pre, post))) return rc;
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    float ms = 0.f;
+    SC_HIP(I, hipEventElapsedTime(&ms, I->ev_k0, I->ev_k1));
+    *ms_eager = ms / (float)reps;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    SC_HIP(I, hipStreamBeginCapture(I->stream, hipStreamCaptureModeThreadLocal));
+    rc = vcycle(I, 2, pre, post);
+    hipError_t e = hipStreamEndCapture(I->stream, &graph);
+    if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); return rc ? rc : hip_fail(I, e, "hipStreamEndCapture"); }
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) { (void)hipGraphDestroy(graph); return hip_fail(I, e, "hipGraphInstantiate"); }
+    (void)hipGraphLaunch(exec, I->stream);                                 // warm (uploads the executable graph)
+    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
+    for (int i = 0; i < reps; ++i) (void)hipGraphLaunch(exec, I->stream);
+    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
+    e = hipStreamSynchronize(I->stream);
+    (void)hipGraphExecDestroy(exec);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) return hip_fail(I, e, "hipStreamSynchronize");
+    SC_HIP(I, hipEventElapsedTime(&ms, I->ev_k0, I->ev_k1));
+    *ms_graph = ms / (float)reps;
+    return SC_OK;
+}
+
+// Measurement hook (sc_hip_time_tail_phases): one k_mg_tail launch on the hierarchy the last multigrid solve left, with the shader
+// clock of channel 0's first thread at its eleven phase boundaries: entry | right-hand side in registers | pre-smoothing done |
+// residual + restriction done (level B's right-hand side in LDS) | products 1, 2, 3, 4 | prolongation + edge exchange |
+// post-smoothing | stores issued.  Differences are cycles of the shader clock.
+static int mg_time_tail_phases(Instance *I, unsigned long long *out11)
+{
+    if (I->mg.size() < 4 || I->mg_bottom < 3 || !tail_serves(I, I->mg_bottom - 1)) { I->err = "time_tail_phases: the last run was not a multigrid solve whose bottom runs as k_mg_tail"; return SC_ERR_BAD_ARG; }
+    const int pre = mg_params(I->opts).pre, post = mg_params(I->opts).post;
+    unsigned long long *d = nullptr;
+    SC_HIP(I, hipMalloc(&d, 11 * sizeof(unsigned long long)));
+    bool done = false;
+    int rc = run_tail(I, I->mg_bottom - 1, pre, post, done);             // warm
+    if (!rc) rc = run_tail(I, I->mg_bottom - 1, pre, post, done, d);
+    hipError_t e = hipStreamSynchronize(I->stream);
+    if (!rc && e == hipSuccess && done) e = hipMemcpy(out11, d, 11 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return hip_fail(I, e, "time_tail_phases");
+    return done ? SC_OK : SC_ERR_BAD_ARG;
+}
+
+// A step of the default fast-path solve's schedule (sc_multigrid.cpp: V(2,2), output bytes wanted, the early node correction allowed),
+// by kind: the launches the timing hooks below repeat are the solve's own.
+static FusedStep default_step(int kind, bool q16, bool composed)
+{
+    FusedSchedule S{ FusedFacts{ 2, 2, mg_params(sc_solver_opts{}).budget, false, true, q16, q16, composed, false, true } };
+    for (;;) {
+        FusedStep s = fused_next(S, VERDICT_REJECT);
+        if (s.ask_early) fused_early(S, s, 1);
+        if (s.kind == kind || s.kind == FUSED_DONE) return s;
+    }
+}
+
 extern "C" {
 
 int sc_hip_selftest_host(void)
@@ -366,12 +439,13 @@ int sc_hip_time_cycle0(void *p, int launches, float *ms_per_launch)
     if (!I->F.p || I->mg.size() < 2 || !I->mg_partial.p) { I->err = "time_cycle0: run a multigrid clone first"; return SC_ERR_BAD_ARG; }
     SC_HIP(I, hipSetDevice(I->gpu));
     const bool comp = mg_composes_level1(I);          // time the form the clone itself runs
+    const bool l1_half = comp && I->mg_l1_half;
+    const FusedStep full = default_step(FUSED_FULL, l1_half && I->mg_q16_last, comp);
     auto once = [&]() {
-        Cycle0Launch d = level0_launch(I, comp);
-        d.sweeps = 4; d.prolong = true; d.timing = true; d.partial = (float *)I->mg_partial.p;
+        Cycle0Launch d = step_launch(level0_launch(I, comp), full);
+        d.timing = true; d.partial = (float *)I->mg_partial.p;
         d.rag = nullptr;        // (a class's fields under the plain form: the class's dimensions)
-        d.l1_half = comp && I->mg_l1_half;
-        d.q16_in = d.q16_out = d.l1_half && I->mg_q16_last;
+        d.l1_half = l1_half;
         launch_cycle0(d);
         I->result_in_U1 = !I->result_in_U1;
     };
@@ -399,16 +473,14 @@ int sc_hip_time_cycle0_form(void *p, int form, int launches, float *ms_per_launc
     float4 *bands = form == 1 ? lowmode_bands_buffer(I, 4) : nullptr;
     LmNodes lm;
     if (form == 2 && I->lm.CN.p && !I->lm.singular) { lm.CN = (const float *)I->lm.CN.p; lm.ny = I->lm.ny; lm.npitch = I->lm.npitch; }
-    // the other three launches of a fast-path solve as that solve says them (sc_multigrid.cpp), under their second symbols
-    Cycle0Launch d = level0_launch(I, form != 3);
+    // the other three launches of a fast-path solve -- the full cycle before the judged one (16-bit field in, float out, leaves the correction's
+    // cell shares), the judged cycle writing output bytes, the first launch (float16 initial field in, 16-bit field out, no prolongation) -- as
+    // that solve's schedule says them, under their second symbols
+    const FusedStep s = default_step(form == 1 ? FUSED_BEFORE_JUDGED : form == 2 ? FUSED_JUDGED_BYTES : FUSED_FIRST, true, true);
+    Cycle0Launch d = step_launch(level0_launch(I, s.composed), s);
     d.timing = true; d.partial = (float *)I->mg_partial.p; d.rag = nullptr;
-    if (form == 1) {            // the full cycle before the judged one: 16-bit field in, float out, leaves the correction's cell shares
-        d.sweeps = 4; d.prolong = true; d.q16_in = true; d.bands = bands;
-    } else if (form == 2) {     // the judged cycle writing output bytes
-        d.sweeps = 2; d.prolong = true; d.final_cycle = d.out_bytes = true; d.lm = lm;
-    } else {                    // the first launch of a solve: float16 initial field in, 16-bit field out, no prolongation
-        d.sweeps = 2; d.u_half = true; d.q16_out = true;
-    }
+    if (s.bands) d.bands = bands;
+    if (s.lm) d.lm = lm;
     // values are discarded: every form reads the fields in the format it expects (whatever bits they hold) and writes the partner
     auto once = [&]() { return launch_cycle0(d); };
     if (once() < 0) { I->err = "time_cycle0_form: form not instantiated"; return SC_ERR_BAD_ARG; }
@@ -458,6 +530,36 @@ int sc_hip_cycle0_form(const int *facts, int index, int form[3])
     }
     if (rc >= 0) { form[0] = T; form[1] = PRO; form[2] = TAG; }
     return rc;
+}
+
+int sc_hip_fused_schedule(const int *facts, const int *verdicts, int nverdicts, int *rows, int capacity)
+{
+    if (!facts || !rows || nverdicts < 0 || (nverdicts > 0 && !verdicts)) return SC_ERR_BAD_ARG;
+    const int pre = facts[0], post = facts[1], budget = facts[2], early_kind = facts[9];
+    if (pre < 1 || pre > 2 || post < 1 || post > 2 || budget < 1 || budget > 64 || early_kind < 0 || early_kind > 3) return SC_ERR_BAD_ARG;
+    const bool bytes_form = facts[10] != 0;
+    FusedSchedule S{ FusedFacts{ pre, post, budget, facts[3] != 0, facts[4] != 0, facts[5] != 0, facts[6] != 0, facts[7] != 0, facts[8] != 0, facts[11] != 0 } };
+    int n = 0, used = 0, verdict = VERDICT_NONE;
+    for (;;) {
+        FusedStep s = fused_next(S, verdict);
+        if (s.kind == FUSED_DONE) break;
+        if (s.ask_early) fused_early(S, s, early_kind);
+        if (capacity < SC_FUSED_ROW * (n + 1) + 3) return SC_ERR_BAD_ARG;
+        const int row[SC_FUSED_ROW] = { s.kind, s.sweeps, s.prolong, s.final_cycle, s.out_bytes, s.u_half, s.q16_in, s.q16_out, s.composed, s.bands, s.lm,
+                                        s.nodes, s.judged, s.coarse_first, s.sat, s.bands_sweeps, s.ask_early, S.cyc };
+        std::memcpy(rows + SC_FUSED_ROW * n++, row, sizeof(row));
+        verdict = VERDICT_NONE;
+        if (!s.judged) continue;
+        if (s.out_bytes && !bytes_form) { verdict = VERDICT_NO_FORM; continue; }
+        // what the read-back showed, as the driver reads it: the early condition applies to conditional bytes only, the saturation word to a 16-bit solve
+        verdict = nverdicts ? verdicts[std::min(used++, nverdicts - 1)] : VERDICT_ACCEPT;
+        if (verdict < VERDICT_ACCEPT || verdict > VERDICT_SATURATED) return SC_ERR_BAD_ARG;
+        if (verdict == VERDICT_REJECT_EARLY && !(s.out_bytes && S.early_cond)) verdict = VERDICT_ACCEPT;
+        if (verdict == VERDICT_SATURATED && !S.f.q16) verdict = VERDICT_ACCEPT;
+    }
+    if (capacity < SC_FUSED_ROW * n + 3) return SC_ERR_BAD_ARG;
+    rows[SC_FUSED_ROW * n] = S.cyc; rows[SC_FUSED_ROW * n + 1] = S.sweep_launches; rows[SC_FUSED_ROW * n + 2] = S.result;
+    return n;
 }
 
 int sc_hip_time_coarse_chain(void *p, int reps, float *ms_eager, float *ms_graph, int *launches)

@@ -19,7 +19,7 @@ struct DevBuf {
 // releases a device buffer on instance teardown: its own hipMalloc block, or nothing for a piece of a slab
 inline void dev_release(DevBuf &b) { if (b.p && b.own) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
 
-// eigen-decomposition of one 1-D level operator (sc_multigrid.cpp, fast-diagonalisation bottom solve)
+// eigen-decomposition of one 1-D level operator (sc_fd_selftest.cpp: the host reference of the fast-diagonalisation bottom solve)
 struct FD1 {
     int n = 0;
     float cw_last = 0.f, d_last = 0.f;     // together with n: the key
@@ -297,7 +297,7 @@ int hip_fail(Instance *I, hipError_t e, const char *what);
 
 int ensure(Instance *I, DevBuf &b, size_t bytes, bool zero = true);
 int ensure_pinned(Instance *I, DevBuf &b, size_t bytes);
-double fd_selftest_error();   // sc_multigrid.cpp
+double fd_selftest_error();   // sc_fd_selftest.cpp
 double fd_closed_selftest_error();
 int setup_fields(Instance *I, int W, int H, int C);
 
@@ -461,10 +461,71 @@ template <class Pre> int solve_step(Instance *I, const SolveTarget &t, Pre &&pre
 int write_output(Instance *I, const SolveTarget &t, AbortFlag sat = AbortFlag());   // the post-process of result(I) into t
 bool mg_reads_half_rhs(const Instance *I);
 bool mg_level1_half(const Instance *I);      // sc_multigrid.cpp: level 1's right-hand side and correction are stored as float16 in the solve configured in I
-int mg_time_coarse_chain(Instance *I, int reps, float *ms_eager, float *ms_graph, int *launches);   // sc_multigrid.cpp
-int mg_time_tail_phases(Instance *I, unsigned long long *out11);                                       // sc_multigrid.cpp
-bool mg_composes_level1(const Instance *I);   // sc_multigrid.cpp   // sc_multigrid.cpp: would the solve configured in I->opts read a float16 F?
+bool mg_composes_level1(const Instance *I);   // sc_multigrid.cpp: level 1 runs pre-smoothing only, the level-0 launch composes its prolongation source
+// the cycle's sweeps, the stop rule's threshold and the budget of cycles: the options, or their defaults
+struct MGParams { int pre, post, budget; float utol; };
+inline MGParams mg_params(const sc_solver_opts &o)
+{
+    return { o.mg_pre > 0 ? o.mg_pre : 2, o.mg_post > 0 ? o.mg_post : 2, o.max_sweeps > 0 ? o.max_sweeps : 30, o.update_tol > 0.f ? o.update_tol : 0.25f };
+}
+// the bottom's matrices may still be in the making on the second stream (build_fd, rag_begin_builds): the main stream waits for them once
+inline int fd_wait(Instance *I)
+{
+    if (I->fd_pending) {
+        SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_fd, 0));
+        I->fd_pending = false;
+    }
+    return SC_OK;
+}
+// sc_multigrid.cpp, for the measurement hooks (sc_hooks.cpp): one cycle from level l down and up again; the level above the bottom and
+// the bottom in one launch (done: the launch serves this shape), and whether the solve runs level l so
+int vcycle(Instance *I, size_t l, int pre, int post, unsigned no_post = 0);
+int run_tail(Instance *I, size_t l, int pre, int post, bool &done, unsigned long long *stamps = nullptr);
+bool tail_serves(const Instance *I, size_t l);
+
+// ---- the schedule of a fused multigrid solve (sc_multigrid.cpp): which level-0 launch comes next, as a function of the solve's facts
+// and of what the stop rule answered so far.  No instance, no pointer, no HIP call: mg_solve_fused launches what it says, the
+// measurement hooks time four of its steps, sc_hip_fused_schedule lists them.
+// Steps: the first launch (pre-smoothing + residual + restriction, no prolongation) | the full cycle | the full cycle before the judged
+// one (16-bit field in, float out, may leave the node correction's cell shares) | the judged cycle leaving output bytes | ... leaving
+// its field | the catch-up launch behind a rejected judged cycle (the form of the first launch)
+enum { FUSED_DONE = 0, FUSED_FIRST, FUSED_FULL, FUSED_BEFORE_JUDGED, FUSED_JUDGED_BYTES, FUSED_JUDGED_FIELD, FUSED_CATCH_UP };
+// REJECT_EARLY: by FusedSchedule::early_cond; NO_FORM: the bytes form is not instantiated, nothing was launched
+enum { VERDICT_NONE = -1, VERDICT_ACCEPT = 0, VERDICT_REJECT, VERDICT_REJECT_EARLY, VERDICT_SATURATED, VERDICT_NO_FORM };
+enum { NODES_NONE = 0, NODES_MAIN, NODES_SECOND, NODES_NOTHING };
+struct FusedFacts {
+    int pre, post, budget;
+    bool tol;                  // a residual tolerance is set: every cycle is judged
+    bool out_wanted, q16;      // the judged cycle may leave output bytes; the field starts as 16-bit fixed point (mg_solve_fused)
+    bool u_half, composed;     // the initial field is float16; mg_composes_level1
+    bool separate_restrict;    // SC_LEGACY_SEPARATE_RESTRICT: no launch leaves cell shares
+    bool small;                // more than 3 planes, or fewer than 3 << 18 pixels: the early node correction stays on the main stream
+};
+struct FusedStep {
+    int kind = FUSED_DONE, sweeps = 0;
+    bool prolong = false, final_cycle = false, out_bytes = false, u_half = false, q16_in = false, q16_out = false, composed = false;
+    bool coarse_first = false; // the step opens a cycle: levels 1 .. bottom run in front of it
+    int bands_sweeps = 0;      // ... and the cycle's bands buffer is asked for then, sized for this many sweeps (0: none)
+    int bands = 0;             // the launch receives that buffer (sweeps it is sized for; 0: it does not)
+    bool ask_early = false;    // lowmode_early_kind's answer decides the rest of the step: fused_early, in front of the bands buffer
+    bool lm = false;           // the launch carries the early node correction (the main stream waits for it first)
+    int nodes = NODES_NONE;    // the correction the next cycle's bytes carry is computed from this launch's result: on the main stream, the second, or there is none to add
+    bool judged = false;       // the stop rule reads the launch's maxima; the next fused_next takes its verdict
+    bool sat = false;          // the launch is given the solve's saturation word
+};
+struct FusedSchedule {
+    FusedFacts f;
+    int last = -1, cyc = 0;    // kind of the step handed out last (-1: none yet); cycles completed in front of it
+    int sweep_launches = 0;    // as sc_run_info counts them (a bytes form counts once it is accepted)
+    int result = SC_OK;        // at FUSED_DONE: SC_OK, SC_ERR_NOT_CONVERGED or SC_RETRY_FLOAT_FIELD
+    bool early_ready = false;  // the node correction for the judged cycle's bytes is on its way
+    bool early_cond = false;   // ... and the bytes stand only if the judged update is small enough (lowmode_early_kind 3)
+    bool u_q16 = false;        // the field is 16-bit fixed point
+};
+FusedStep fused_next(FusedSchedule &S, int verdict = VERDICT_NONE);
+void fused_early(FusedSchedule &S, FusedStep &s, int early_kind);
 Cycle0Launch level0_launch(Instance *I, bool composed = false);   // sc_multigrid.cpp: what every level-0 launch on I's fields and hierarchy says alike
+Cycle0Launch step_launch(Cycle0Launch d, const FusedStep &s);     // ... and what step s adds to it: everything but buffers, `timing` and `rag`
 int lowmode_correct(Instance *I, const Field &U, const Field &Out);   // sc_lowmode.hip: Out = U + float-table correction
 int lowmode_nodes(Instance *I, const Field &U, LmNodes &lm, hipStream_t on = nullptr);      // on: another stream than the instance's          // the correction of U at the node rows (what the post-process adds)
 float4 *lowmode_bands_buffer(Instance *I, int sweeps);               // where a final level-0 launch leaves the correction's cell shares (nullptr: not wanted)
@@ -478,9 +539,12 @@ bool lowmode_part_map(int H, int sweeps, std::vector<int> &m, int &band_rows);
 bool lowmode_part_map(int H, int sweeps, int *m, int &band_rows);      // ... into 4 ints per cell row, all -1 on entry
 int lowmode_projection_splits(int nxt, int nkb);                      // row splits of the coarse projection for a ROI with nxt column tiles
 void launch_lm_tables_rag(const RagMember *rag, int members, int max_rows, int Kxp, int Kyp, hipStream_t s);
-void mg_plan_levels(int W, int H, std::vector<MGGeom> &g);           // sc_multigrid.cpp
+void mg_plan_levels(int W, int H, std::vector<MGGeom> &g);           // sc_mg_levels.cpp
 size_t mg_default_tail_level(const std::vector<MGGeom> &g);
-int mg_build_levels_rag(Instance *I, hipStream_t zero_on);           // sc_multigrid.cpp: the class's level planes, zeroed on the given stream
+MGDim make_dim(int n, double a, int nc);                             // one direction of a level: n unknowns, last interval a, nc coarse unknowns
+int bottom_pitch(const MGLevel &L);                                  // row pitch of a level inside the bottom kernel's LDS
+int build_levels(Instance *I);                                       // the hierarchy of the fields bound to I (kept while their size stays)
+int mg_build_levels_rag(Instance *I, hipStream_t zero_on);           // the class's level planes, zeroed on the given stream
 int rag_begin_table(Instance *I, const std::vector<SizePlan> &members);      // the members' table and host tables, uploaded on the instance's stream (sets I->rag.dev)
 int rag_begin_builds(Instance *I);                                           // ... then everything the device builds per call, on two more streams
 void rag_end(Instance *I);

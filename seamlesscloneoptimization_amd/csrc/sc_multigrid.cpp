@@ -1,266 +1,17 @@
 // sc_multigrid.cpp -- geometric multigrid V-cycle for the ROI Poisson system (SURVEY.md
 // section 8 row f1): red-black GS smoothing, residual in double, normalised-transpose
-// restriction, bilinear prolongation.  Arbitrary ROI sizes coarsen by letting the LAST grid
-// interval of each level differ from the others (MGDim), so the Dirichlet ring never moves.
+// restriction, bilinear prolongation, on the hierarchy sc_mg_levels.cpp builds.
 // Level 0 runs the exact 5-point kernels of the sweep solvers; coarser levels the general
 // ones.  Converges ~20x per V(2,2) cycle at every size tried (tools/mg_proto2.py).
+// In this file: the cycle (vcycle, the bottom and tail launches), the predicates that choose the
+// field formats, the stop rule, the schedule of a fused solve's level-0 launches and the two drivers.
 #include "sc_instance.h"
-#include "sc_fd_closed.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
 
 namespace sc {
-
-static void coarsen_1d(int n, double a, int &nc, double &ac)
-{
-    if (n % 2 == 1) { nc = (n - 1) / 2; ac = (1.0 + a) / 2.0; }       // boundary stays (1+a)/2 coarse cells away
-    else if (a >= 1.0) { nc = n / 2; ac = a / 2.0; }                   // keep the last point
-    else { nc = n / 2 - 1; ac = 1.0 + a / 2.0; }                       // drop it: gap would fall below 1/2
-}
-
-static MGDim make_dim(int n, double a, int nc)
-{
-    MGDim d;
-    d.n = n; d.nc = nc; d.alpha = (float)a;
-    d.cw_last = (float)(2.0 / (1.0 + a));
-    d.d_last = (float)(2.0 / a);
-    const int tail = n - 2 * nc;          // 0, 1 or 2 fine points beyond the last coarse point
-    const double D = n + a - 2.0 * nc;    // their distance budget to the boundary
-    d.tw1 = tail >= 1 ? (float)(1.0 - 1.0 / D) : 0.f;
-    d.tw2 = tail >= 2 ? (float)(1.0 - 2.0 / D) : 0.f;
-    d.inv_last = (float)(1.0 / (1.5 + (double)d.tw1 + (double)d.tw2));
-    return d;
-}
-
-static Field level_field(void *p, int W, int H, int C)
-{
-    Field f;
-    f.p = (float *)p; f.W = W; f.H = H; f.C = C;
-    // at least two pad columns behind the ring: the level-0 kernel reads three coarse columns starting at an even column <= nc
-    // (k_cycle0's prolongation), and must find them where it expects them, not shifted by an address clamp
-    f.pitch = round_up(W + 2, 64);
-    f.plane = (size_t)f.pitch * H;
-    return f;
-}
-
-// LDS floats level l needs inside the bottom kernel: U and F planes, odd row pitch
-static int bottom_pitch(const MGLevel &L) { return (L.g.x.n + 2) | 1; }
-static long bottom_floats(const MGLevel &L) { return 2L * bottom_pitch(L) * (L.g.y.n + 2); }
-
-// first level handled by the fused bottom kernel: the first l >= 1 from which all remaining
-// levels fit the LDS budget together (never level 0: it runs the exact kernels)
-static size_t bottom_start(Instance *I)
-{
-    for (size_t l = 1; l < I->mg.size(); ++l) {
-        if (I->mg.size() - l > (size_t)MG_BOTTOM_MAX_LEVELS) continue;
-        long tot = 0;
-        for (size_t k = l; k < I->mg.size(); ++k) tot += bottom_floats(I->mg[k]);
-        if (tot * (long)sizeof(float) <= (long)MG_BOTTOM_LDS_BYTES) return l;
-    }
-    return I->mg.size();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Direct solve of the bottom's first level(s) by fast diagonalisation.
-// A level's operator is  (A u)[y][x] = sum_x' Tx[x][x'] u[y][x'] + sum_y' Ty[y][y'] u[y'][x]  with
-// tridiagonal 1-D parts: rows (1, -2, 1), last row (cw_last, -d_last) (MGDim).  T is not symmetric
-// (the last sub-diagonal is cw_last, the super-diagonal above it 1) but E T E^-1 is, with
-// E = diag(1, .., 1, 1/sqrt(cw_last)); its eigen-decomposition Q L Q^T gives T = V L V^-1 with
-// V = E^-1 Q, V^-1 = Q^T E.  Everything here is double; the device gets float matrices.
-// ---------------------------------------------------------------------------------------------
-// Eigen-decomposition of a symmetric tridiagonal matrix by implicit QL with Wilkinson shifts.
-// d: diagonal (n) -> eigenvalues; e: sub-diagonal, e[i] couples i and i+1 (n-1 used, e[n-1] = 0);
-// zt: n x n, row k = eigenvector k on return (kept transposed so the rotation loop is contiguous).
-static bool tridiag_ql(int n, std::vector<double> &d, std::vector<double> &e, std::vector<double> &zt)
-{
-    zt.assign((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) zt[(size_t)i * n + i] = 1.0;
-    for (int l = 0; l < n; ++l) {
-        int iter = 0, m;
-        do {
-            for (m = l; m < n - 1; ++m) {
-                const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]);
-                if (std::fabs(e[m]) <= 1.1e-16 * dd) break;
-            }
-            if (m != l) {
-                if (++iter > 80) return false;
-                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-                double r = std::hypot(g, 1.0);
-                g = d[m] - d[l] + e[l] / (g + (g >= 0.0 ? std::fabs(r) : -std::fabs(r)));
-                double s = 1.0, c = 1.0, p = 0.0;
-                int i;
-                for (i = m - 1; i >= l; --i) {
-                    double f = s * e[i];
-                    const double b = c * e[i];
-                    r = std::hypot(f, g);
-                    e[i + 1] = r;
-                    if (r == 0.0) { d[i + 1] -= p; e[m] = 0.0; break; }
-                    s = f / r; c = g / r;
-                    g = d[i + 1] - p;
-                    r = (d[i] - g) * s + 2.0 * c * b;
-                    p = s * r;
-                    d[i + 1] = g + p;
-                    g = c * r - b;
-                    double *zi = &zt[(size_t)i * n], *zi1 = &zt[(size_t)(i + 1) * n];
-                    for (int k = 0; k < n; ++k) {
-                        f = zi1[k];
-                        zi1[k] = s * zi[k] + c * f;
-                        zi[k] = c * zi[k] - s * f;
-                    }
-                }
-                if (r == 0.0 && i >= l) continue;
-                d[l] -= p; e[l] = g; e[m] = 0.0;
-            }
-        } while (m != l);
-    }
-    return true;
-}
-
-static bool fd_decompose(const MGDim &g, FD1 &o)
-{
-    const int n = g.n;
-    o.n = n; o.cw_last = g.cw_last; o.d_last = g.d_last;
-    o.ee.assign(n, 1.0);
-    std::vector<double> d(n, -2.0), e(n, 0.0);
-    for (int i = 0; i + 1 < n; ++i) e[i] = 1.0;
-    d[n - 1] = -(double)g.d_last;
-    if (n >= 2) {
-        e[n - 2] = std::sqrt((double)g.cw_last);          // sqrt(sub * super) = sqrt(cw_last * 1)
-        o.ee[n - 1] = 1.0 / std::sqrt((double)g.cw_last);
-    }
-    if (!tridiag_ql(n, d, e, o.q)) return false;
-    o.lam = d;
-    return true;
-}
-
-// host-only check of the decomposition (sc_hip_selftest_host): max |T v_k - l_k v_k| and max |V^-1 V - I| over a few
-// level operators, regular and with an irregular last interval
-double fd_selftest_error()
-{
-    double worst = 0.0;
-    const int ns[] = { 1, 2, 3, 7, 31, 63, 74, 128 };
-    const double alphas[] = { 1.0, 0.5, 0.75, 1.5, 0.96875 };
-    for (int n : ns)
-        for (double a : alphas) {
-            MGDim g = make_dim(n, a, 0);
-            FD1 f;
-            if (!fd_decompose(g, f)) return 1e30;
-            auto T = [&](int i, int j) -> double {          // the level operator itself
-                if (i == j) return i == n - 1 ? -(double)g.d_last : -2.0;
-                if (j == i + 1) return 1.0;
-                if (j == i - 1) return i == n - 1 ? (double)g.cw_last : 1.0;
-                return 0.0;
-            };
-            for (int k = 0; k < n; ++k) {
-                for (int i = 0; i < n; ++i) {
-                    double tv = 0.0;
-                    for (int j = std::max(0, i - 1); j <= std::min(n - 1, i + 1); ++j) tv += T(i, j) * f.q[(size_t)k * n + j] / f.ee[j];
-                    worst = std::max(worst, std::fabs(tv - f.lam[k] * f.q[(size_t)k * n + i] / f.ee[i]));
-                }
-                for (int m = 0; m < n; ++m) {                // rows of V^-1 = Q^T E against columns of V = E^-1 Q
-                    double dot = 0.0;
-                    for (int i = 0; i < n; ++i) dot += f.q[(size_t)k * n + i] * f.ee[i] * f.q[(size_t)m * n + i] / f.ee[i];
-                    worst = std::max(worst, std::fabs(dot - (k == m ? 1.0 : 0.0)));
-                }
-            }
-        }
-    return worst;
-}
-
-// Chooses the bottom level solved directly and has its matrices built ON THE DEVICE from the closed-form eigenpairs of the
-// level's two 1-D operators (sc_fd_closed.h, k_fd_build) -- no host eigen-solve, no staging copy, no wait.  The build runs on
-// the instance's second stream, beside the first launches of the clone that needs it; run_bottom() makes the main stream
-// wait for it.  (Rounds 1-3 ran the implicit-QL solve above on the host for every new ROI size: 0.1-0.3 ms per direction at
-// n = 63, as long as the clone itself; it now only serves sc_hip_selftest_host as the reference the closed form is checked
-// against.)  I->fd_level = -1 when nothing fits.
-static int build_fd(Instance *I)
-{
-    I->fd_level = -1;
-    if ((I->opts.flags & SC_FLAG_VCYCLE_BOTTOM) || I->mg_bottom >= I->mg.size()) return SC_OK;
-    long planes = 0;
-    I->fd_mm = false;
-    for (size_t l = I->mg_bottom; l < I->mg.size(); ++l) {
-        const MGLevel &L = I->mg[l];
-        planes += bottom_floats(L);
-        const int nx = L.g.x.n, ny = L.g.y.n, nxp = round_up(nx, 4), nyp = round_up(ny, 4);
-        const int dmax = I->opts.mg_direct_max > 0 ? std::min(I->opts.mg_direct_max, 128) : SC_MG_DIRECT_MAX_DEFAULT;
-        if (nx > dmax || ny > dmax) continue;
-        // the bottom's first level on the matrix cores (k_mg_bottom_mm): up to 96 unknowns per side, no LDS budget to meet
-        const bool mm = l == I->mg_bottom && nx <= 96 && ny <= 96 && !legacy_path(I->opts, SC_LEGACY_BOTTOM_F32);
-        if (!mm && (planes + fd_lds_floats(nxp, nyp)) * (long)sizeof(float) > (long)MG_BOTTOM_LDS_BYTES) continue;
-        const long nf = (fd_mat_floats(nxp, nyp) + 15) & ~15L;          // the matrix-core operands behind the float matrices, 64-byte aligned
-        const int NPX = round_up(nx, 32), NPY = round_up(ny, 32);
-        int rc;
-        if (I->fd_pending) {          // a build nobody waited for (a solve that never reached its bottom): order it in front of whatever
-            SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_fd, 0));      // follows on the main stream -- ensure() below waits for that stream before it frees
-            I->fd_pending = false;
-        }
-        if ((rc = ensure(I, I->mg_fd, sizeof(float) * (size_t)nf + (mm ? (size_t)fd_mm_bytes(NPX, NPY) : 0)))) return rc;
-        // everything that read the previous matrices has been enqueued on the main stream: the build starts behind it
-        SC_HIP(I, hipEventRecord(I->ev_fd_fork, I->stream));
-        SC_HIP(I, hipStreamWaitEvent(I->aux, I->ev_fd_fork, 0));
-        launch_fd_build((float *)I->mg_fd.p, L.g, nxp, nyp, I->aux, mm ? (unsigned char *)((float *)I->mg_fd.p + nf) : nullptr, NPX, NPY);
-        SC_HIP(I, hipGetLastError());
-        SC_HIP(I, hipEventRecord(I->ev_fd, I->aux));
-        I->fd_pending = true;
-        I->fd_level = (int)(l - I->mg_bottom);
-        I->fd_nxp = nxp; I->fd_nyp = nyp;
-        I->fd_mm = mm; I->fd_npx = NPX; I->fd_npy = NPY; I->fd_mm_off = (size_t)nf;
-        return SC_OK;
-    }
-    return SC_OK;
-}
-
-// host-only check of the closed form (sc_hip_selftest_host): its matrices V, V^-1 and eigenvalues against the QL-based
-// decomposition over level operators of every size the bottom solve can meet, regular and with an irregular last interval
-// on either side of the alpha = 0.7071 threshold (one eigenvalue below -4).  Returns the worst deviation found.
-double fd_closed_selftest_error()
-{
-    double worst = 0.0;
-    const double alphas[] = { 1.0, 0.5, 0.625, 0.70703125, 0.7109375, 0.75, 0.875, 1.125, 1.25, 1.5, 0.96875 };
-    for (int n = 1; n <= 128; n += (n < 20 ? 1 : 9))
-        for (double a : alphas) {
-            MGDim g = make_dim(n, a, 0);
-            FD1 f;
-            if (!fd_decompose(g, f)) return 1e30;
-            std::vector<FdPair> p(n);
-            for (int k = 0; k < n; ++k) p[k] = fd_pair(k, n, (double)g.cw_last, (double)g.d_last);
-            // eigenvalues: the two sets must agree as sets (QL's order is arbitrary)
-            std::vector<double> la(f.lam), lb(n);
-            for (int k = 0; k < n; ++k) lb[k] = p[k].lam;
-            std::sort(la.begin(), la.end()); std::sort(lb.begin(), lb.end());
-            for (int k = 0; k < n; ++k) worst = std::max(worst, std::fabs(la[k] - lb[k]));
-            // T v = lambda v for the closed form's own vectors, and V^-1 V = I
-            auto T = [&](int i, int j) -> double {
-                if (i == j) return i == n - 1 ? -(double)g.d_last : -2.0;
-                if (j == i + 1) return 1.0;
-                if (j == i - 1) return i == n - 1 ? (double)g.cw_last : 1.0;
-                return 0.0;
-            };
-            std::vector<double> V((size_t)n * n), Vi((size_t)n * n);      // V[x][k], Vinv[k][x]
-            for (int k = 0; k < n; ++k)
-                for (int x = 0; x < n; ++x) {
-                    const double v = fd_component(p[k], x + 1, n) * p[k].inv_norm;
-                    V[(size_t)x * n + k] = v;
-                    Vi[(size_t)k * n + x] = v * (x == n - 1 ? 1.0 / (double)g.cw_last : 1.0);
-                }
-            for (int k = 0; k < n; ++k) {
-                for (int i = 0; i < n; ++i) {
-                    double tv = 0.0;
-                    for (int j = std::max(0, i - 1); j <= std::min(n - 1, i + 1); ++j) tv += T(i, j) * V[(size_t)j * n + k];
-                    worst = std::max(worst, std::fabs(tv - p[k].lam * V[(size_t)i * n + k]));
-                }
-                for (int m = 0; m < n; ++m) {
-                    double dot = 0.0;
-                    for (int x = 0; x < n; ++x) dot += Vi[(size_t)k * n + x] * V[(size_t)x * n + m];
-                    worst = std::max(worst, std::fabs(dot - (k == m ? 1.0 : 0.0)));
-                }
-            }
-        }
-    return worst;
-}
 
 static int run_bottom(Instance *I, size_t l0, int pre, int post)
 {
@@ -289,10 +40,8 @@ static int run_bottom(Instance *I, size_t l0, int pre, int post)
     a.lds_floats = off;
     a.Ftop = I->mg[l0].F;
     a.Utop = I->mg[l0].U;
-    if (I->fd_pending) {          // the matrices of a new hierarchy are being built on the second stream (build_fd)
-        SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_fd, 0));
-        I->fd_pending = false;
-    }
+    int rc;
+    if ((rc = fd_wait(I))) return rc;          // the matrices of a new hierarchy are being built on the second stream (build_fd)
     if (I->fd_mm && I->fd_level == 0) {      // the usual case: this level solved directly on the matrix cores, nothing below it is visited
         MGBottomMM m;
         m.mm = (const unsigned char *)((const float *)I->mg_fd.p + I->fd_mm_off);
@@ -307,16 +56,16 @@ static int run_bottom(Instance *I, size_t l0, int pre, int post)
 // The level above the bottom and the bottom in one launch (k_mg_tail): level l is that level, the bottom's first level is the one
 // solved directly on the matrix cores with at most 64 padded unknowns per side, and l itself is a plain float level (>= 2: level 1
 // has its own composed / float16 forms).
-static bool tail_serves(const Instance *I, size_t l)
+bool tail_serves(const Instance *I, size_t l)
 {
     if (l < 2 || l + 1 != I->mg_bottom || legacy_path(I->opts, SC_LEGACY_SEPARATE_TAIL) || I->opts.sweeps_per_launch == 1) return false;
     if (!I->fd_mm || I->fd_level != 0 || I->fd_npx > 64 || I->fd_npy > 64) return false;
-    if ((I->opts.mg_pre > 0 ? I->opts.mg_pre : 2) < 1) return false;          // the launch takes the residual of the colour swept last as zero
+    if (mg_params(I->opts).pre < 1) return false;          // the launch takes the residual of the colour swept last as zero
     const MGGeom &g = I->mg[l].g;
     return g.x.n <= 127 && g.y.n <= 127 && g.x.nc <= 63 && g.y.nc <= 63;
 }
 
-static int run_tail(Instance *I, size_t l, int pre, int post, bool &done, unsigned long long *stamps = nullptr)
+int run_tail(Instance *I, size_t l, int pre, int post, bool &done, unsigned long long *stamps)
 {
     done = false;
     MGTail t;
@@ -324,168 +73,9 @@ static int run_tail(Instance *I, size_t l, int pre, int post, bool &done, unsign
     t.mm = (const unsigned char *)((const float *)I->mg_fd.p + I->fd_mm_off);
     t.F = I->mg[l].F; t.U = I->mg[l].U; t.g = I->mg[l].g; t.pre = pre; t.post = post;
     t.rag = I->rag.dev; t.lev = (int)l; t.rag_uniform = I->rag.pad_uniform;
-    if (I->fd_pending) {
-        SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_fd, 0));
-        I->fd_pending = false;
-    }
+    int rc;
+    if ((rc = fd_wait(I))) return rc;
     done = launch_mg_tail(t, I->fd_npx, I->fd_npy, I->F.C, I->stream);
-    return SC_OK;
-}
-
-// The ladder of levels of a W x H field (ring included): the geometry of every level (and of its transfer to the next coarser one).
-// Host arithmetic only; the size-class planner (sc_ragged.cpp) runs it per member.
-void mg_plan_levels(int W, int H, std::vector<MGGeom> &g)
-{
-    struct L1 { int nx, ny; double ax, ay; };
-    std::vector<L1> ls;
-    ls.push_back({ W - 2, H - 2, 1.0, 1.0 });
-    while (std::min(ls.back().nx, ls.back().ny) > 3) {
-        L1 c;
-        coarsen_1d(ls.back().nx, ls.back().ax, c.nx, c.ax);
-        coarsen_1d(ls.back().ny, ls.back().ay, c.ny, c.ay);
-        if (c.nx < 1 || c.ny < 1) break;
-        ls.push_back(c);
-    }
-    const size_t nl = ls.size();
-    g.resize(nl);
-    for (size_t l = 0; l < nl; ++l) {
-        const int ncx = (l + 1 < nl) ? ls[l + 1].nx : 0, ncy = (l + 1 < nl) ? ls[l + 1].ny : 0;
-        g[l].x = make_dim(ls[l].nx, ls[l].ax, ncx);
-        g[l].y = make_dim(ls[l].ny, ls[l].ay, ncy);
-    }
-}
-
-// The default hierarchy's deepest launched level (see build_levels): the first level >= 2 with at most 127 unknowns per side, held in
-// registers by k_mg_tail with the level below it solved directly in the same launch; 0: this ladder ends differently (its level 1
-// is solved directly -- at most 64 unknowns per side: 10-13 us per solve for a group of sixteen, against ~24 for a level-1 launch plus
-// k_mg_tail; up to 96 until late in round 5, but the 96-wide solve takes 31-34 us (ROIs of 131..194 pixels: measured on groups of
-// 16, tools/class_timeline.sh) --, or no such level exists)
-size_t mg_default_tail_level(const std::vector<MGGeom> &g)
-{
-    const size_t nl = g.size();
-    size_t a = 0;
-    for (size_t l = 2; l + 1 < nl && !a; ++l)
-        if (g[l].x.n <= 127 && g[l].y.n <= 127) a = l;
-    const bool level1_direct = nl > 1 && g[1].x.n <= 64 && g[1].y.n <= 64;
-    return (a && !(a == 2 && level1_direct)) ? a : 0;
-}
-
-static int build_levels(Instance *I)
-{
-    if (I->rag.dev) {          // a size class: rag_begin_builds built the hierarchy (mg_build_levels_rag)
-        if (!I->rag.levels_built || I->mg.empty()) { I->err = "size class: hierarchy missing"; return SC_ERR_BAD_ARG; }
-        return SC_OK;
-    }
-    const int W = I->F.W, H = I->F.H, C = I->F.C;
-    if (!I->mg.empty() && I->mg[0].F.p == I->F.p && I->mg[0].F.W == W && I->mg[0].F.H == H && I->mg[0].F.C == C)
-        return SC_OK;
-    I->info.new_size = 1;
-    I->mg.clear();
-    std::vector<MGGeom> plan;
-    mg_plan_levels(W, H, plan);
-    const size_t nl = plan.size();
-    if (I->mg_bufs.size() < 3 * nl) I->mg_bufs.resize(3 * nl);
-    I->mg.resize(nl);
-    ZeroJobs zj{};
-    for (size_t l = 0; l < nl; ++l) {
-        MGLevel &L = I->mg[l];
-        L.g = plan[l];
-        const double rho = 0.5 * (std::cos(M_PI / (L.g.x.n + 1.0)) + std::cos(M_PI / (L.g.y.n + 1.0)));
-        L.omega = (float)(2.0 / (1.0 + std::sqrt(std::max(0.0, 1.0 - rho * rho))));
-        if (l == 0) continue; // level 0 aliases the instance fields, bound per cycle
-        const int Wl = L.g.x.n + 2, Hl = L.g.y.n + 2;
-        Field proto = level_field(nullptr, Wl, Hl, C);
-        for (int k = 0; k < 3; ++k) {
-            int rc = ensure(I, I->mg_bufs[3 * l + k], proto.bytes() + 4096, false);      // (zeroed below, by the launch that zeroes every plane)
-            if (rc) return rc;
-        }
-        L.U = level_field(I->mg_bufs[3 * l + 0].p, Wl, Hl, C);
-        L.F = level_field(I->mg_bufs[3 * l + 1].p, Wl, Hl, C);
-        L.T = level_field(I->mg_bufs[3 * l + 2].p, Wl, Hl, C);
-        // rings and pads of F/U must be zero; ensure() zero-fills fresh memory, but a reused
-        // larger buffer may hold stale data from another ROI size: every plane of every level in ONE launch below
-        // (24-36 memsets were 70-100 us of launches in front of the first clone at a new size)
-        for (const Field *f : { &L.U, &L.F, &L.T }) {
-            if (zj.count == ZeroJobs::MAX) { launch_zero_multi(zj, I->stream); zj.count = 0; }
-            zj.p[zj.count] = f->p; zj.n16[zj.count] = (f->bytes() + 15) / 16; ++zj.count;       // buffers are 4096 bytes larger than the field
-        }
-    }
-    launch_zero_multi(zj, I->stream);
-    SC_HIP(I, hipGetLastError());
-    I->mg[0].F = I->F;
-    I->mg_bottom = bottom_start(I);
-    // Default hierarchy since round 4: the deepest launched level ("A") is the first one (>= 2) with at most 127 unknowns per side --
-    // k_mg_tail holds it in registers -- and the level below it ("B", at most 63 per side) is the one solved directly, on the matrix
-    // cores, inside the same launch.  The LDS-fit rule above chose the bottom in rounds 1-3; where it landed on a level with 97 .. ~190
-    // unknowns on a side (ROIs like 2090 x 1632, 2500 x 1300, 3540^2: no matrix-core solve, an LDS-resident V-cycle inside
-    // k_mg_bottom instead) a cycle cost 60 us more than at the sizes next to it (0.55 against 0.38 ms for one clone).  Kept: a ROI
-    // whose level 1 fits the matrix-core solve at 64 (solved there; at 65..96 only where the ladder has no level for k_mg_tail),
-    // the flags that ask for the older bottoms.
-    if (!(I->opts.flags & SC_FLAG_VCYCLE_BOTTOM) && !legacy_path(I->opts, SC_LEGACY_BOTTOM_F32) && I->opts.mg_direct_max <= 0) {
-        const size_t a = mg_default_tail_level(plan);
-        const bool level1_direct = nl > 1 && I->mg[1].g.x.n <= 96 && I->mg[1].g.y.n <= 96;
-        if (a) I->mg_bottom = a + 1;
-        else if (!level1_direct)
-            for (size_t l = 1; l < nl; ++l)
-                if (I->mg[l].g.x.n <= 96 && I->mg[l].g.y.n <= 96) { I->mg_bottom = l; break; }
-    }
-    I->mg_l1_half = false;        // fresh planes: all zero in either format
-    return build_fd(I);
-}
-
-// The hierarchy of a SIZE CLASS (RagState, sc_instance.h): level planes at the class's strides -- the largest width and height any
-// member has on that level --, every plane zeroed (a member's ring and what lies beyond it must be zero, and the slot may have held a
-// larger member a call ago), the members' bottom matrices by one launch on the second stream.  The per-member geometries are in the
-// table on the device; I->mg[l].g holds the class's MAXIMA (grid sizes and the launchers' shape tests read those).
-// Called from rag_begin_builds: the zeroing goes to `zero_on` (the instance's second stream, which the main stream joins in front of its
-// first coarse-level launch, mg_solve) -- the caller has ordered that stream behind everything that read the planes before.
-int mg_build_levels_rag(Instance *I, hipStream_t zero_on)
-{
-    RagState &R = I->rag;
-    R.levels_built = false;
-    const int C = I->F.C, n = R.n;
-    const size_t nl = (size_t)R.nl;
-    I->info.new_size = 1;
-    I->mg.clear();
-    if (I->mg_bufs.size() < 3 * nl) I->mg_bufs.resize(3 * nl);
-    I->mg.resize(nl);
-    ZeroJobs zj{};
-    for (size_t l = 0; l < nl; ++l) {
-        MGLevel &L = I->mg[l];
-        L.g = R.host[0].g[l];
-        for (int i = 1; i < n; ++i) {
-            const MGGeom &g = R.host[i].g[l];
-            L.g.x.n = std::max(L.g.x.n, g.x.n); L.g.x.nc = std::max(L.g.x.nc, g.x.nc);
-            L.g.y.n = std::max(L.g.y.n, g.y.n); L.g.y.nc = std::max(L.g.y.nc, g.y.nc);
-        }
-        L.omega = 1.f;
-        if (l == 0) continue;
-        const int Wl = L.g.x.n + 2, Hl = L.g.y.n + 2;
-        Field proto = level_field(nullptr, Wl, Hl, C);
-        for (int k = 0; k < 3; ++k) {
-            int rc = ensure(I, I->mg_bufs[3 * l + k], proto.bytes() + 4096, false);      // (zeroed below, by the launch that zeroes every plane)
-            if (rc) return rc;
-        }
-        L.U = level_field(I->mg_bufs[3 * l + 0].p, Wl, Hl, C);
-        L.F = level_field(I->mg_bufs[3 * l + 1].p, Wl, Hl, C);
-        L.T = level_field(I->mg_bufs[3 * l + 2].p, Wl, Hl, C);
-        // What must be zero: a member's ring and everything beyond it in the planes a finer level interpolates FROM -- U and its
-        // ping-pong partner T (the launches write a member's own extent only, and the slot may have held a larger member a call
-        // ago).  Right-hand sides are read under the interior masks only: F needs nothing.
-        for (const Field *f : { &L.U, &L.T }) {
-            if (zj.count == ZeroJobs::MAX) { launch_zero_multi(zj, zero_on); zj.count = 0; }
-            zj.p[zj.count] = f->p; zj.n16[zj.count] = (f->bytes() + 15) / 16; ++zj.count;
-        }
-    }
-    launch_zero_multi(zj, zero_on);
-    SC_HIP(I, hipGetLastError());
-    I->mg[0].F = I->F;
-    I->mg_bottom = (size_t)R.tail + 1;
-    I->mg_l1_half = true;      // a class runs the fast path (plan_size): float16 level 1, and its planes are all zero -- valid in either format, nothing to re-zero in mg_solve
-    // the class's bottom: every member's level below `tail` solved directly on the matrix cores inside k_mg_tail, operands padded
-    // alike; the matrices are being built on the third stream since rag_begin_builds (run_tail waits for them)
-    I->fd_level = 0; I->fd_mm = true; I->fd_npx = R.npx; I->fd_npy = R.npy; I->fd_nxp = I->fd_nyp = 0; I->fd_mm_off = 0;
-    R.levels_built = true;
     return SC_OK;
 }
 
@@ -518,7 +108,7 @@ static int smooth_gen(Instance *I, size_t l, int n, int mode, Field E)
 // from "its correction + the interpolated correction of the level below" directly (sc_mg_device.h, ComposeArgs).  Used for
 // level 1 (composed by the level-0 launch); doing the same for level 3 inside level 2's post launch was measured neutral
 // (481 vs 494 us for a single 2048^2 clone, no change in throughput) and is not kept.
-static int vcycle(Instance *I, size_t l, int pre, int post, unsigned no_post = 0)
+int vcycle(Instance *I, size_t l, int pre, int post, unsigned no_post)
 {
     const bool skip_post = l > 0 && l < 32 && ((no_post >> l) & 1u);
     MGLevel &L = I->mg[l];
@@ -595,7 +185,7 @@ static int vcycle(Instance *I, size_t l, int pre, int post, unsigned no_post = 0
 // path (sweep solvers, unfused cycle, residual-based stop rule, stage hooks) needs the float field.
 static bool fused_level0(const sc_solver_opts &o)
 {
-    const int pre = o.mg_pre > 0 ? o.mg_pre : 2, post = o.mg_post > 0 ? o.mg_post : 2;
+    const int pre = mg_params(o).pre, post = mg_params(o).post;
     return o.sweeps_per_launch != 1 && pre >= 1 && pre <= 2 && post >= 1 && post <= 2;   // the forms sc_cycle0.hip instantiates
 }
 
@@ -606,7 +196,7 @@ static bool fused_level0(const sc_solver_opts &o)
 bool mg_composes_level1(const Instance *I)
 {
     const sc_solver_opts &o = I->opts;
-    const int pre = o.mg_pre > 0 ? o.mg_pre : 2, post = o.mg_post > 0 ? o.mg_post : 2;
+    const int pre = mg_params(o).pre, post = mg_params(o).post;
     return !(o.flags & SC_FLAG_NO_COMPOSE_L1) && I->mg.size() >= 3 && I->mg_bottom >= 2 && pre == 2 && post == 2;
 }
 
@@ -704,6 +294,7 @@ static int correction_maxima(Instance *I, const Level0Maxima &x, int cyc, int nb
     return SC_OK;
 }
 
+// ---- the schedule of a fused solve ------------------------------------------------------------------------------------------------
 // Fused level-0 form: one launch per cycle does [prolongation +] post-smoothing of this cycle,
 // pre-smoothing of the next, residual and restriction (sc_cycle0.hip).  The first launch has no
 // correction to add.  A cycle whose result the stop rule is about to judge is launched in its
@@ -711,11 +302,115 @@ static int correction_maxima(Instance *I, const Level0Maxima &x, int cyc, int nb
 // case for the third cycle -- nothing was computed for a cycle that never runs, and the field is
 // exactly the textbook V-cycle's; when it does not, one pre-smoothing + residual + restriction launch
 // (the form of the very first launch) catches up and the cycles continue.
+//
+// Output straight from the last cycle.  When the caller armed the splice (out_wanted) the judged cycle does not write its field: it
+// adds the float-table node correction, clamps, truncates and leaves output BYTES (planar, in the memory of the partner field; a small
+// kernel interleaves them into the destination) -- 3 bytes less written and 9 less read per pixel and channel than field +
+// post-process.  The node correction it adds is the one of the iterate BEFORE that cycle, whose cell shares the previous launch leaves
+// behind (lowmode_early_kind: the two differ by 0.001-0.003 grey levels, 0.05 in the worst case the stop rule admits).  If the rule
+// rejects the cycle, the same cycle is launched again in the form that writes the field (its input is untouched) and the solve
+// continues as without this.
+
+// Is the cycle behind `cyc` completed ones judged?  The first two corrections of a solve are never below the stop threshold unless the
+// initial guess was already the answer, and every check costs a host round trip (~25 us), so checking starts with the third cycle.
+static bool fused_judged(const FusedFacts &f, int cyc) { return !(cyc + 1 < 3 && cyc + 1 < f.budget && !f.tol); }
+
+// the launch that opens the cycle behind S.cyc completed ones -- or, behind that cycle's refused bytes form, its field form
+static FusedStep fused_cycle(FusedSchedule &S, bool bytes_refused)
+{
+    const FusedFacts &f = S.f;
+    const bool judged = fused_judged(f, S.cyc), next_judged = !judged && fused_judged(f, S.cyc + 1);
+    FusedStep s;
+    s.prolong = true; s.composed = f.composed; s.coarse_first = !bytes_refused;
+    s.judged = s.final_cycle = judged;      // the judged cycle runs in its final form and leaves the node correction's cell shares (sc_lowmode.hip)
+    s.sweeps = judged ? f.post : f.post + f.pre;
+    const int bands = judged && !f.separate_restrict ? f.post : 0;
+    s.bands_sweeps = bytes_refused ? 0 : bands;      // (asked for when the cycle opened)
+    if (judged && S.early_ready) {
+        s.kind = FUSED_JUDGED_BYTES; s.out_bytes = s.lm = true;
+        S.early_ready = false;
+        return s;
+    }
+    s.kind = judged ? FUSED_JUDGED_FIELD : next_judged ? FUSED_BEFORE_JUDGED : FUSED_FULL;
+    s.bands = bands; s.sat = true;
+    s.q16_in = S.u_q16; s.q16_out = S.u_q16 && !next_judged;      // the launch before the judged cycle writes float again
+    s.ask_early = f.out_wanted && next_judged;
+    return s;
+}
+
+// The step before the judged cycle of a solve that wants bytes, once lowmode_early_kind has answered: 1 the bytes may carry the node
+// correction of this step's result, which leaves its cell shares; 3 the a-priori bound does not cover this size (the float tables' low
+// modes are off by more than 4 %) -- the same, but the bytes stand only IF the judged cycle's measured update keeps the difference
+// below the same 0.049 grey levels (early_cond, decided with the stop rule); 0 there is no correction to add; 2 the field-keeping path.
+void fused_early(FusedSchedule &S, FusedStep &s, int early_kind)
+{
+    const FusedFacts &f = S.f;
+    S.early_cond = early_kind == 3;
+    if (early_kind == 2) return;
+    if (early_kind == 0) s.nodes = NODES_NOTHING;
+    else {
+        if (!f.separate_restrict) s.bands = s.bands_sweeps = f.post + f.pre;
+        // a group of clones: its coarse levels fill the chip, nothing to overlap (measured: -2 %); a small clone: the two
+        // cross-stream waits cost more than the 15-us chain they hide (154x100 ... 300x194 patches: +20 us; neutral at 730^2 ... 800^2,
+        // -2..3 % from 900^2 on: the threshold is 0.79 Mpix, 1 Mpix until late in round 4); one large clone: on the second stream,
+        // beside the coarse levels of the next cycle (-15 us of 500 at 2048^2)
+        s.nodes = f.small ? NODES_MAIN : NODES_SECOND;
+    }
+    S.early_ready = true;
+}
+
+// The next level-0 launch of the solve; `verdict`: what the stop rule made of the step handed out last, where that one was judged.
+FusedStep fused_next(FusedSchedule &S, int verdict)
+{
+    const FusedFacts &f = S.f;
+    const bool was_cycle = S.last == FUSED_FULL || S.last == FUSED_BEFORE_JUDGED || S.last == FUSED_JUDGED_BYTES || S.last == FUSED_JUDGED_FIELD;
+    const bool was_judged = S.last == FUSED_JUDGED_BYTES || S.last == FUSED_JUDGED_FIELD;
+    FusedStep s;
+    if (S.last < 0) {
+        // on the float16 path the pre-process stored the initial field as float16 as well (this launch only)
+        s.kind = FUSED_FIRST; s.sweeps = f.pre; s.u_half = f.u_half; s.q16_out = f.q16; s.sat = true;
+    } else if (S.last == FUSED_JUDGED_BYTES && verdict != VERDICT_ACCEPT && verdict != VERDICT_SATURATED) {
+        s = fused_cycle(S, true);          // refused: the same cycle again in the form that keeps the field, then on as usual
+    } else {
+        if (S.last == FUSED_JUDGED_BYTES) S.sweep_launches += 1;
+        if (was_cycle) S.cyc += 1;
+        if (was_judged && verdict == VERDICT_ACCEPT) S.result = SC_OK;
+        else if (was_judged && verdict == VERDICT_SATURATED) S.result = SC_RETRY_FLOAT_FIELD;      // nothing was written (AbortFlag)
+        else if (S.cyc >= f.budget) S.result = SC_ERR_NOT_CONVERGED;
+        else if (S.last == FUSED_JUDGED_FIELD) { s.kind = FUSED_CATCH_UP; s.sweeps = f.pre; }      // pre-smoothing + residual + restriction for the next cycle
+        else s = fused_cycle(S, false);
+    }
+    if (s.kind != FUSED_DONE && s.kind != FUSED_JUDGED_BYTES) S.sweep_launches += 1;
+    S.u_q16 = s.q16_out;
+    S.last = s.kind;
+    return s;
+}
+
+Cycle0Launch step_launch(Cycle0Launch d, const FusedStep &s)
+{
+    d.sweeps = s.sweeps; d.prolong = s.prolong; d.final_cycle = s.final_cycle; d.out_bytes = s.out_bytes;
+    d.u_half = s.u_half; d.q16_in = s.q16_in; d.q16_out = s.q16_out;
+    return d;
+}
+
+// the optional residual-based stop (tol > 0): the relative residual into the run's info; stop: it meets the tolerance
+static int residual_stop(Instance *I, bool &stop)
+{
+    double r[2];
+    int rc = eval_residual(I, r);
+    if (rc) return rc;
+    const double rel = (r[1] > 0.0) ? std::sqrt(r[0] / r[1]) : std::sqrt(r[0]);
+    I->info.rel_residual = rel;
+    stop = rel <= (double)I->opts.tol;
+    return SC_OK;
+}
+
+// The fused solve: asks the schedule for the next level-0 launch, runs the coarse levels in front of a launch that opens a cycle,
+// launches it, and where the step is judged hands the stop rule's verdict back.
 static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget)
 {
     const sc_solver_opts &o = I->opts;
-    int rc, cyc = 0;
-    bool ok = false;
+    int rc;
     const bool out_wanted = I->spec_post.armed && o.tol <= 0.f && !(o.flags & SC_FLAG_KEEP_FIELD) && pre == 2 && post == 2;
     const bool q16 = I->mg_l1_half && mg_field_q16(I, out_wanted) && budget > 1;      // (max_sweeps = 1: the first cycle is the judged one)
     const int nb_cap = cycle0_blocks(I->F.W, I->F.H, I->F.C, 4);   // deepest form = largest halo = most workgroups
@@ -736,141 +431,102 @@ static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget
     }
     I->sat = sat;
     const Level0Maxima maxima{ host_fold, nb_cap, part_base, sat };
-    {   // the first launch: on the float16 path the pre-process stored the initial field as float16 as well (this launch only)
-        Cycle0Launch d = level0_launch(I);
-        d.sweeps = pre; d.u_half = I->u_half; d.q16_out = q16; d.sat = sat;
-        if (launch_cycle0(d) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-    }
-    I->result_in_U1 = !I->result_in_U1;
-    if (I->rag.dev && I->rag.ready_pending) {      // a size class: its zeroed coarse planes and tables were made on the second stream beside everything up to here
-        SC_HIP(I, hipStreamWaitEvent(I->stream, I->rag.ev_ready, 0));      // (the matrices: run_tail waits for them)
-        I->rag.ready_pending = false;
-    }
-    I->u_half = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
-    I->u_q16 = I->mg_q16_last = q16;
-    I->info.sweep_launches += 1;
+    FusedSchedule S{ FusedFacts{ pre, post, budget, o.tol > 0.f, out_wanted, q16, I->u_half, mg_composes_level1(I), legacy_path(o, SC_LEGACY_SEPARATE_RESTRICT),
+                                 I->F.C > 3 || (size_t)I->F.W * I->F.H < (size_t)3 << 18 } };
+    const int launches_before = I->info.sweep_launches;
     int nb_last = 0;                   // workgroups (= partial maxima) of the previous cycle's level-0 launch
-    // Output straight from the last cycle.  When the caller armed the splice (spec_post) the cycle the stop rule is about to
-    // judge does not write its field: it adds the float-table node correction, clamps, truncates and leaves output BYTES
-    // (planar, in the memory of the partner field; a small kernel interleaves them into the destination) -- 3 bytes less
-    // written and 9 less read per pixel and channel than field + post-process.  The node correction it adds is the one of
-    // the iterate BEFORE that cycle, whose cell shares the previous launch leaves behind (lowmode_early_kind: the two
-    // differ by 0.001-0.003 grey levels, 0.05 in the worst case the stop rule admits).  If the rule rejects the cycle, the same cycle is launched again in the form
-    // that writes the field (its input is untouched) and the solve continues as without this.
-    bool saturated = false;            // set by correction_maxima
-    bool early_ready = false;          // the node correction for the judged cycle's output is on its way (early_lm; CN == nullptr: none to add)
-    bool early_cond = false;           // ... and may be used only if the judged update turns out small enough (lowmode_early_kind 3)
-    LmNodes early_lm;
-    while (cyc < budget) {
-        const bool comp1 = mg_composes_level1(I);
-        if ((rc = vcycle(I, 1, pre, post, comp1 ? (1u << 1) : 0u))) return rc;
-        // The first two corrections of a solve are never below the stop threshold unless the
-        // initial guess was already the answer, and every check costs a host round trip
-        // (~25 us), so checking starts with the third cycle.
-        const bool judged = !(cyc + 1 < 3 && cyc + 1 < budget && o.tol <= 0.f);
-        float *const part_now = part_base + (size_t)((cyc + 1) & 1) * nb_cap;    // this cycle's maxima; the previous cycle's sit in the other half
-        // the judged cycle runs in its final form; when the float-table correction will follow it leaves the correction's
-        // cell shares behind (sc_lowmode.hip), which saves the correction its own pass over the field
-        const bool next_judged = !judged && !(cyc + 2 < 3 && cyc + 2 < budget && o.tol <= 0.f);
-        // lowmode_early_kind 3: the a-priori bound does not cover this size (the float tables' low modes are off by more than 4 %);
-        // the output may still carry the earlier iterate's correction IF the judged cycle's measured update keeps the difference
-        // below the same 0.049 grey levels -- decided with the stop rule, below (early_cond)
-        const int early_kind = (out_wanted && next_judged) ? lowmode_early_kind(I, utol) : 2;
-        const int early = early_kind == 3 ? 1 : early_kind;
-        if (out_wanted && next_judged) early_cond = early_kind == 3;
-        float4 *const bands = legacy_path(o, SC_LEGACY_SEPARATE_RESTRICT) ? nullptr
-                              : judged ? lowmode_bands_buffer(I, post) : early == 1 ? lowmode_bands_buffer(I, post + pre) : nullptr;
-        if (judged && early_ready) {
-            if (I->aux_pending) {          // the node correction is ready when the launch that adds it starts
-                SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_join, 0));
-                I->aux_pending = false;
-            }
-            Cycle0Launch d = level0_launch(I, comp1);      // the judged cycle leaving as bytes
-            d.sweeps = post; d.prolong = true; d.final_cycle = d.out_bytes = true; d.partial = part_now; d.lm = early_lm;
-            const int nbo = launch_cycle0(d);
-            early_ready = false;
-            if (nbo > 0) {
-                I->info.sweep_launches += 1;
-                ++cyc;
-                SC_HIP(I, hipGetLastError());
-                const Field Q = I->result_in_U1 ? I->U0 : I->U1;
-                float m, m_prev;
-                if ((rc = correction_maxima(I, maxima, cyc, nbo, nb_last, part_now, [&]() -> int {
-                        const SolveTarget &to = I->spec_post.to;
-                        if (!to.group) launch_splice_planar(Q, to.org, to.step, I->stream, I->guard, sat);
-                        else launch_splice_planar_group(Q, to.group->data(), (int)to.group->size(), I->stream, sat);
-                        return SC_OK;
-                    }, m, m_prev, saturated))) return rc;
-                I->info.last_update = m;
-                if (saturated) { I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }      // nothing was written (AbortFlag)
-                if (stop_rule(utol, m, m_prev) && !(early_cond && I->lm.max_ratio * (double)m > 0.049)) { I->spec_post.done = true; I->out_direct = true; ok = true; break; }
-                // rejected: the same cycle again in the form that keeps the field, then on as usual
-                --cyc;
-                I->info.sweep_launches -= 1;
-            }
+    float4 *bands = nullptr;           // the current cycle's buffer for the node correction's cell shares
+    LmNodes early_lm;                  // the node correction for the judged cycle's bytes (CN == nullptr: none to add)
+    int verdict = VERDICT_NONE;
+    for (;;) {
+        FusedStep s = fused_next(S, verdict);
+        I->info.sweep_launches = launches_before + S.sweep_launches;
+        if (s.kind == FUSED_DONE) break;
+        verdict = VERDICT_NONE;
+        if (s.coarse_first && (rc = vcycle(I, 1, pre, post, s.composed ? (1u << 1) : 0u))) return rc;
+        if (s.ask_early) fused_early(S, s, lowmode_early_kind(I, utol));
+        if (s.coarse_first) bands = s.bands_sweeps ? lowmode_bands_buffer(I, s.bands_sweeps) : nullptr;
+        if (s.lm && I->aux_pending) {          // the node correction is ready when the launch that adds it starts
+            SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_join, 0));
+            I->aux_pending = false;
         }
-        Cycle0Launch d = level0_launch(I, comp1);      // the full cycle, or the judged one as a field; the launch before the judged cycle writes float again
-        d.sweeps = judged ? post : post + pre; d.prolong = true; d.final_cycle = judged; d.partial = part_now; d.bands = bands;
-        d.q16_in = I->u_q16; d.q16_out = I->u_q16 && !next_judged; d.sat = sat;
+        float *const part_now = part_base + (size_t)((S.cyc + 1) & 1) * nb_cap;    // this cycle's maxima; the previous cycle's sit in the other half
+        Cycle0Launch d = step_launch(level0_launch(I, s.composed), s);
+        if (s.prolong) d.partial = part_now;
+        if (s.bands) d.bands = bands;
+        if (s.lm) d.lm = early_lm;
+        if (s.sat) d.sat = sat;
         const int nb = launch_cycle0(d);
-        if (nb <= 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-        I->result_in_U1 = !I->result_in_U1;
-        if (next_judged) I->u_q16 = false;      // the launch before the judged cycle left a float field
-        lowmode_bands_written(I, bands ? result(I).p : nullptr);
-        if (!judged && early != 2) {       // the node correction the next cycle's output will carry, from this launch's field
+        if (s.out_bytes && nb <= 0) { verdict = VERDICT_NO_FORM; continue; }
+        if (s.prolong ? nb <= 0 : nb < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
+        const Field Q = I->result_in_U1 ? I->U0 : I->U1;      // (where a bytes form left its bytes)
+        if (!s.out_bytes) I->result_in_U1 = !I->result_in_U1;
+        if (s.kind == FUSED_FIRST) {
+            if (I->rag.dev && I->rag.ready_pending) {      // a size class: its zeroed coarse planes and tables were made on the second stream beside everything up to here
+                SC_HIP(I, hipStreamWaitEvent(I->stream, I->rag.ev_ready, 0));      // (the matrices: run_tail waits for them)
+                I->rag.ready_pending = false;
+            }
+            I->u_half = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
+            I->mg_q16_last = q16;
+        } else if (!s.out_bytes) {
+            lowmode_bands_written(I, d.bands ? result(I).p : nullptr);
+        }
+        I->u_q16 = s.q16_out;
+        if (s.nodes != NODES_NONE) {       // the node correction the next cycle's output will carry, from this launch's field
             early_lm = LmNodes();
-            // a group of clones: its coarse levels fill the chip, nothing to overlap (measured: -2 %); a small clone: the two
-            // cross-stream waits cost more than the 15-us chain they hide (154x100 ... 300x194 patches: +20 us; neutral at 730^2 ... 800^2,
-            // -2..3 % from 900^2 on: the threshold is 0.79 Mpix, 1 Mpix until late in round 4)
-            if (early == 1 && (I->F.C > 3 || (size_t)I->F.W * I->F.H < (size_t)3 << 18)) {
+            if (s.nodes == NODES_MAIN) {
                 if ((rc = lowmode_nodes(I, result(I), early_lm))) return rc;
-            } else if (early == 1) {       // one large clone: on the second stream, beside the coarse levels of the next cycle (-15 us of 500 at 2048^2)
+            } else if (s.nodes == NODES_SECOND) {
                 SC_HIP(I, hipEventRecord(I->ev_fork, I->stream));
                 SC_HIP(I, hipStreamWaitEvent(I->aux, I->ev_fork, 0));
                 if ((rc = lowmode_nodes(I, result(I), early_lm, I->aux))) return rc;
                 SC_HIP(I, hipEventRecord(I->ev_join, I->aux));
                 I->aux_pending = true;
             }
-            early_ready = true;            // (early == 0: nothing to add)
         }
-        I->info.sweep_launches += 1;
-        ++cyc;
+        if (!s.prolong) continue;
         SC_HIP(I, hipGetLastError());
         const int nb_prev = nb_last;
-        nb_last = nb;
-        if (!judged) continue;
-        // the post-process goes in FIRST (see Instance::spec_post), the read-back of the maxima follows it
+        if (!s.out_bytes) nb_last = nb;
+        if (!s.judged) continue;
+        // the output goes in FIRST (see Instance::spec_post), the read-back of the maxima follows it
         float m, m_prev;
-        if ((rc = correction_maxima(I, maxima, cyc, nb, nb_prev, part_now, [&]() -> int {
-                if (!(I->spec_post.armed && o.tol <= 0.f)) return SC_OK;
-                const int lrc = write_output(I, I->spec_post.to, sat);
-                if (lrc) return lrc;
-                I->spec_post.done = true;
-                return SC_OK;
-            }, m, m_prev, saturated))) return rc;
+        bool saturated = false;
+        if (s.out_bytes)
+            rc = correction_maxima(I, maxima, S.cyc + 1, nb, nb_prev, part_now, [&]() -> int {
+                    const SolveTarget &to = I->spec_post.to;
+                    if (!to.group) launch_splice_planar(Q, to.org, to.step, I->stream, I->guard, sat);
+                    else launch_splice_planar_group(Q, to.group->data(), (int)to.group->size(), I->stream, sat);
+                    return SC_OK;
+                }, m, m_prev, saturated);
+        else
+            rc = correction_maxima(I, maxima, S.cyc + 1, nb, nb_prev, part_now, [&]() -> int {
+                    if (!(I->spec_post.armed && o.tol <= 0.f)) return SC_OK;
+                    const int lrc = write_output(I, I->spec_post.to, sat);
+                    if (lrc) return lrc;
+                    I->spec_post.done = true;
+                    return SC_OK;
+                }, m, m_prev, saturated);
+        if (rc) return rc;
         I->info.last_update = m;
-        if (saturated) { I->spec_post.done = false; I->info.sweeps = cyc; return SC_RETRY_FLOAT_FIELD; }
-        if (o.tol > 0.f) {
-            double r[2];
-            if ((rc = eval_residual(I, r))) return rc;
-            const double rel = (r[1] > 0.0) ? std::sqrt(r[0] / r[1]) : std::sqrt(r[0]);
-            I->info.rel_residual = rel;
-            if (rel <= (double)o.tol) { ok = true; break; }
-        }
-        if (stop_rule(utol, m, m_prev)) { ok = true; break; }
-        I->spec_post.done = false;     // not converged: the field moves on, the output is written again later
-        if (cyc < budget) {            // catch up: pre-smoothing + residual + restriction for the next cycle
-            Cycle0Launch up = level0_launch(I);
-            up.sweeps = pre;
-            if (launch_cycle0(up) < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
-            I->result_in_U1 = !I->result_in_U1;
-            lowmode_bands_written(I, nullptr);
-            I->info.sweep_launches += 1;
+        bool stop = false;
+        if (saturated) {
+            if (!s.out_bytes) I->spec_post.done = false;
+            verdict = VERDICT_SATURATED;
+        } else if (s.out_bytes) {
+            const bool early_ok = !(S.early_cond && I->lm.max_ratio * (double)m > 0.049);
+            if (stop_rule(utol, m, m_prev) && early_ok) { I->spec_post.done = true; I->out_direct = true; verdict = VERDICT_ACCEPT; }
+            else verdict = early_ok ? VERDICT_REJECT : VERDICT_REJECT_EARLY;
+        } else {
+            if (o.tol > 0.f && (rc = residual_stop(I, stop))) return rc;
+            if (stop || stop_rule(utol, m, m_prev)) verdict = VERDICT_ACCEPT;
+            else { I->spec_post.done = false; verdict = VERDICT_REJECT; }     // not converged: the field moves on, the output is written again later
         }
     }
-    I->info.sweeps = cyc;
-    I->info.converged = ok ? 1 : 0;
-    return ok ? SC_OK : SC_ERR_NOT_CONVERGED;
+    I->info.sweeps = S.cyc;
+    if (S.result == SC_RETRY_FLOAT_FIELD) return S.result;
+    I->info.converged = S.result == SC_OK ? 1 : 0;
+    return S.result;
 }
 
 int mg_solve(Instance *I)
@@ -883,9 +539,9 @@ int mg_solve(Instance *I)
                                 cycle0_blocks(I->F.W, I->F.H, I->F.C, 4));      // the deepest forms have the most workgroups
         if ((rc = ensure(I, I->mg_partial, sizeof(float) * (2 * (size_t)nb + 64)))) return rc;   // two cycles' worth (see the stop rule) + the saturation word behind them
     }
-    const int pre = o.mg_pre > 0 ? o.mg_pre : 2, post = o.mg_post > 0 ? o.mg_post : 2;
-    const float utol = o.update_tol > 0.f ? o.update_tol : 0.25f;
-    const int budget = o.max_sweeps > 0 ? o.max_sweeps : 30;
+    const MGParams mp = mg_params(o);
+    const int pre = mp.pre, post = mp.post, budget = mp.budget;
+    const float utol = mp.utol;
     // level 1 in float16 or float: the two formats put a plane's ring and pads at different bytes, so a switch re-zeroes the planes
     const bool l1h = I->mg.size() >= 2 && mg_level1_half(I);
     if (I->mg.size() >= 2 && l1h != I->mg_l1_half) {
@@ -913,81 +569,14 @@ int mg_solve(Instance *I)
         unsigned bits = *I->h_maxcorr;
         memcpy(&m, &bits, sizeof(float));
         I->info.last_update = m;
-        if (o.tol > 0.f) { // optional residual-based stop
-            double r[2];
-            if ((rc = eval_residual(I, r))) return rc;
-            const double rel = (r[1] > 0.0) ? std::sqrt(r[0] / r[1]) : std::sqrt(r[0]);
-            I->info.rel_residual = rel;
-            if (rel <= (double)o.tol) { ok = true; break; }
-        }
+        bool stop = false;
+        if (o.tol > 0.f && (rc = residual_stop(I, stop))) return rc;
+        if (stop) { ok = true; break; }
         if (m <= utol) { ok = true; break; }
     }
     I->info.sweeps = cyc;
     I->info.converged = ok ? 1 : 0;
     return ok ? SC_OK : SC_ERR_NOT_CONVERGED;
-}
-
-// Measurement hook (sc_hip_time_coarse_chain): the launch-bound part of a cycle -- levels 2 .. bottom .. 2: seven dependent launches
-// for a 2048^2 clone, 2 % of the unknowns -- run `reps` times back to back on the hierarchy the last multigrid solve left, (a) as
-// plain launches and (b) captured once into a HIP graph and replayed.  hipEvents on the instance's stream around each batch.
-// Values are discarded (level 2's right-hand side is whatever the last cycle left there).
-int mg_time_coarse_chain(Instance *I, int reps, float *ms_eager, float *ms_graph, int *launches)
-{
-    if (I->mg.size() < 4 || I->mg_bottom < 3 || !mg_composes_level1(I)) { I->err = "time_coarse_chain: run a multigrid clone of at least ~500^2 first"; return SC_ERR_BAD_ARG; }
-    const sc_solver_opts &o = I->opts;
-    const int pre = o.mg_pre > 0 ? o.mg_pre : 2, post = o.mg_post > 0 ? o.mg_post : 2;
-    int rc;
-    if (I->fd_pending) { SC_HIP(I, hipStreamWaitEvent(I->stream, I->ev_fd, 0)); I->fd_pending = false; }
-    *launches = (int)(2 * (I->mg_bottom - 2) + 1) - (tail_serves(I, I->mg_bottom - 1) ? 2 : 0);
-    if ((rc = vcycle(I, 2, pre, post))) return rc;                       // warm
-    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
-    for (int i = 0; i < reps; ++i) if ((rc = vcycle(I, 2, pre, post))) return rc;
-    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
-    SC_HIP(I, hipStreamSynchronize(I->stream));
-    float ms = 0.f;
-    SC_HIP(I, hipEventElapsedTime(&ms, I->ev_k0, I->ev_k1));
-    *ms_eager = ms / (float)reps;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    SC_HIP(I, hipStreamBeginCapture(I->stream, hipStreamCaptureModeThreadLocal));
-    rc = vcycle(I, 2, pre, post);
-    hipError_t e = hipStreamEndCapture(I->stream, &graph);
-    if (rc || e != hipSuccess || !graph) { if (graph) (void)hipGraphDestroy(graph); return rc ? rc : hip_fail(I, e, "hipStreamEndCapture"); }
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) { (void)hipGraphDestroy(graph); return hip_fail(I, e, "hipGraphInstantiate"); }
-    (void)hipGraphLaunch(exec, I->stream);                                 // warm (uploads the executable graph)
-    SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
-    for (int i = 0; i < reps; ++i) (void)hipGraphLaunch(exec, I->stream);
-    SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
-    e = hipStreamSynchronize(I->stream);
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) return hip_fail(I, e, "hipStreamSynchronize");
-    SC_HIP(I, hipEventElapsedTime(&ms, I->ev_k0, I->ev_k1));
-    *ms_graph = ms / (float)reps;
-    return SC_OK;
-}
-
-// Measurement hook (sc_hip_time_tail_phases): one k_mg_tail launch on the hierarchy the last multigrid solve left, with the shader
-// clock of channel 0's first thread at its eleven phase boundaries: entry | right-hand side in registers | pre-smoothing done |
-// residual + restriction done (level B's right-hand side in LDS) | products 1, 2, 3, 4 | prolongation + edge exchange |
-// post-smoothing | stores issued.  Differences are cycles of the shader clock.
-int mg_time_tail_phases(Instance *I, unsigned long long *out11)
-{
-    if (I->mg.size() < 4 || I->mg_bottom < 3 || !tail_serves(I, I->mg_bottom - 1)) { I->err = "time_tail_phases: the last run was not a multigrid solve whose bottom runs as k_mg_tail"; return SC_ERR_BAD_ARG; }
-    const sc_solver_opts &o = I->opts;
-    const int pre = o.mg_pre > 0 ? o.mg_pre : 2, post = o.mg_post > 0 ? o.mg_post : 2;
-    unsigned long long *d = nullptr;
-    SC_HIP(I, hipMalloc(&d, 11 * sizeof(unsigned long long)));
-    bool done = false;
-    int rc = run_tail(I, I->mg_bottom - 1, pre, post, done);             // warm
-    if (!rc) rc = run_tail(I, I->mg_bottom - 1, pre, post, done, d);
-    hipError_t e = hipStreamSynchronize(I->stream);
-    if (!rc && e == hipSuccess && done) e = hipMemcpy(out11, d, 11 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(I, e, "time_tail_phases");
-    return done ? SC_OK : SC_ERR_BAD_ARG;
 }
 
 } // namespace sc

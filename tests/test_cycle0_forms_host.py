@@ -21,8 +21,8 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cyc
 
 
 def descriptor(launcher, r):
-    """The recorded arguments of an old launcher as the facts of a Cycle0Launch, as the call sites translate them (sc_multigrid.cpp,
-    sc_hooks.cpp)."""
+    """The recorded arguments of an old launcher as the facts of a Cycle0Launch, as the call sites translate them: step_launch on a step of the fused solve's
+    schedule (sc_multigrid.cpp), which sc_hooks.cpp's timing twins use as well (tests/test_fused_schedule_host.py)."""
     if launcher == "cycle0":
         return dict(sweeps=r["sweeps"], prolong=r["prolong"], timing=r["tag"], f_half=r["f_half"], u_half=r["u_half"],
                     final_cycle=r["final_cycle"], bands=r["bands"], l1_half=r["l1_half"], q16_out=r["q16_out"], rag=r["rag"])

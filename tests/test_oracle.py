@@ -371,7 +371,7 @@ def test_fixed16_field_in_the_first_stores_leaves_no_trace():
 
 
 def test_bottom_level_rule_of_round_4():
-    """oracle/mg_np.bottom_level mirrors sc_multigrid.cpp build_levels: wherever a level >= 2 with at most 127 unknowns per side has a
+    """oracle/mg_np.bottom_level mirrors sc_mg_levels.cpp build_levels: wherever a level >= 2 with at most 127 unknowns per side has a
     level below it, the bottom is that level below (<= 63 per side: the pair k_mg_tail runs in one launch), unless level 1 itself
     already fits the matrix-core solve; never deeper than necessary; thin ROIs without such a pair keep the LDS-fit rule."""
     from oracle import mg_np

@@ -55,7 +55,7 @@ def fft_launches(W, H, fp64):
 
 
 def default_tail_level(levels):
-    """sc_multigrid.cpp mg_default_tail_level on mg_np.build_levels: the first level >= 2 with at most 127 unknowns per side (held in
+    """sc_mg_levels.cpp mg_default_tail_level on mg_np.build_levels: the first level >= 2 with at most 127 unknowns per side (held in
     k_mg_tail), unless that is level 2 and level 1 has at most 64 per side; 0 when there is none."""
     nl = len(levels)
     a = next((l for l in range(2, nl - 1) if levels[l][0].n <= 127 and levels[l][1].n <= 127), 0)
