@@ -654,6 +654,73 @@ SC_API int sc_hip_weighted_device(void *instance, const sc_weighted_params *p, c
 /* One problem on host arrays, as sc_hip_screened: spans in and out through pinned staging, only the named elements of out written. */
 SC_API int sc_hip_weighted(void *instance, const sc_weighted_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                            const float *lap, const float *data, const float *weight, const float *boundary, float *out);
+/* ---- WLS solves: per-link smoothness weights on the gradient term -------------------------------------------------------------------
+ * The problem: per channel,
+ *     minimise   sum_p w(p) (u(p) - d(p))^2  +  sum_x-links sx (u(x+1,y) - u(x,y) - gx)^2  +  sum_y-links sy (u(x,y+1) - u(x,y) - gy)^2
+ * i.e. at every unknown p
+ *     sum_q s(p,q) (u(q) - u(p)) - w(p) u(p)  =  div(s g)(p) - w(p) d(p),
+ *     div(s g)(x,y) = sx(x,y) gx(x,y) - sx(x-1,y) gx(x-1,y) + sy(x,y) gy(x,y) - sy(x,y-1) gy(x,y-1),
+ * the sum over the neighbours q that exist under the call's border kind -- the weighted-least-squares operator of edge-preserving
+ * smoothing and base / detail decomposition, colourisation and scribble propagation that stops at image edges, guided upsampling of
+ * depth or flow, and the inner step of reweighted (robust, TV-like) gradient solves.  With every link 1 it is sc_hip_weighted's problem.
+ * kind, layout, chunks of at most 192 planes, what a call writes, aliasing of out with data or boundary: sc_hip_weighted_device's.
+ * Links: smooth_x(x,y) is the weight of the link between pixels (x,y) and (x+1,y), smooth_y(x,y) that of (x,y) - (x,y+1), both under
+ * the call's layout, per channel, like weight.  A link is LIVE when at least one of its ends is an unknown.  Along a periodic axis the
+ * element in the last column of smooth_x (last row of smooth_y) is the link from the last pixel to the first, as for gx / gy; otherwise
+ * that element is not live.  A link between two pixels of one Dirichlet line is not live.  Elements that are not live are never
+ * read.  A live link to a Dirichlet pixel q adds s to the diagonal at its unknown end and s * boundary(q) to the right-hand side.
+ * Every live link must be finite and > 0 (a zero would cut the graph and can leave a part of it singular); weight >= 0 as in the
+ * weighted call.  smooth_x, smooth_y and weight must not overlap out: a job in which the span of one of them under the layout (offsets
+ * 0 .. the largest) shares a float with out's span is refused.
+ * The right-hand side, in float32, in this order:  with SC_POISSON_LAPLACIAN lap is taken as div(s g), already weighted, and gx, gy
+ * are unused; with SC_POISSON_GUIDANCE each product s * g is rounded on its own (never fused into the difference), the differences are
+ * taken as sc_hip_poisson's reflecting and periodic kinds take them, (a - b) + (c - d) with a = sx(x,y) gx(x,y), b = sx(x-1,y) gx(x-1,y),
+ * c = sy(x,y) gy(x,y), d = sy(x,y-1) gy(x,y-1), a term whose link does not exist counting 0 and column / row 0 of a periodic axis
+ * taking the last column / row as its backward term.  Then - w * d: one rounded multiply, one subtract, as in the weighted call.  Then
+ * the Dirichlet terms, each a rounded product s * boundary subtracted in turn: west, north, east, south.
+ * Solved by the weighted call's conjugate gradients -- float32 vectors, every dot product summed in double in one fixed order (two runs
+ * of one call give the same bytes), the stop rule ||r||_2 <= tol ||b||_2 on every plane of the chunk read SC_WEIGHTED_POLL iterations
+ * late, SC_ERR_NOT_CONVERGED with the last iterate written when max_iters ends first -- preconditioned by M = s-bar (A - w-bar / s-bar),
+ * A the constant-coefficient operator of the border kind through the direct solve: s-bar = precond_smooth, or the arithmetic mean of the
+ * live links of the call's chunk; w-bar = precond_lambda, or the mean of w over its unknowns.  Constant links c and a constant weight
+ * need no iteration; under a constant weight random links over two decades take about twenty and a contrast of 100 across image edges
+ * about fifty; a data weight that varies as well adds to that (43 and 56 at 1024 x 1024 with w log-uniform over two decades), sparse
+ * data weights can take a hundred or more (DESIGN.md sections 4 and 7).  SC_FLAG_FFT_FP64: the preconditioner's transforms in double.
+ * Methods, sizes, batches (one joint stop, the chunk's s-bar and w-bar: a member agrees with its solo run to the stop rule's error, not
+ * bit for bit), host waits and sc_run_info: the weighted call's.  rel_residual is the last iterate's: under strongly varying links the
+ * residual of conjugate gradients is not monotone (the error in the energy norm is), so after the up to SC_WEIGHTED_POLL iterations
+ * past the one that met tol it may lie somewhat above tol in a call that converged.
+ * Codes: SC_ERR_BAD_ARG for a non-finite tol, precond_lambda or precond_smooth, a method other than AUTO or FFT, a bad kind or layout;
+ * SC_ERR_BAD_SIZE as the weighted call.  Per job SC_ERR_BAD_ARG for a NULL or misaligned pointer the kind needs (data, weight, smooth_x
+ * and smooth_y always), for smooth_x, smooth_y or weight overlapping out, for a weight that is negative or not finite, for a live link
+ * that is not finite or not > 0 and, without any Dirichlet line, for a channel whose weights are all zero -- nothing of such a job is
+ * written, the others run. */
+typedef struct sc_wls_params {
+    int   kind;              /* as sc_weighted_params.kind */
+    float tol;               /* stop when ||r||_2 <= tol * ||b||_2 on every plane; <= 0: 1e-5 */
+    int   max_iters;         /* <= 0: 400 */
+    float precond_lambda;    /* w-bar of the preconditioner; <= 0: the mean of w over the unknowns of the call's chunk */
+    float precond_smooth;    /* s-bar of the preconditioner; <= 0: the mean of the live links of the call's chunk */
+} sc_wls_params;
+typedef struct sc_wls_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE */
+    const float *lap;        /* SC_POISSON_LAPLACIAN: div(s g), already weighted */
+    const float *data;       /* d: read at every unknown */
+    const float *weight;     /* w >= 0: read at every unknown */
+    const float *smooth_x;   /* > 0: the link (x,y) - (x+1,y); live links only are read */
+    const float *smooth_y;   /* > 0: the link (x,y) - (x,y+1); live links only are read */
+    const float *boundary;   /* its Dirichlet lines (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_wls_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_wls_check(const sc_wls_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_wls_device(void *instance, const sc_wls_params *p, const sc_poisson_layout *l, sc_wls_job *jobs, int n, bool bSync);
+/* One problem on host arrays, as sc_hip_weighted: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_wls(void *instance, const sc_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                      const float *lap, const float *data, const float *weight, const float *smooth_x, const float *smooth_y,
+                      const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

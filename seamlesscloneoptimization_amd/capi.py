@@ -224,6 +224,16 @@ class WeightedJob(C.Structure):
                 ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# WLS solves (sc_hip_wls*): Instance.wls / wls_device
+class WlsParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("tol", C.c_float), ("max_iters", C.c_int), ("precond_lambda", C.c_float), ("precond_smooth", C.c_float)]
+
+
+class WlsJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("weight", C.c_void_p),
+                ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -412,6 +422,12 @@ def load():
     L.sc_hip_weighted_device.restype = C.c_int
     L.sc_hip_weighted.argtypes = [C.c_void_p, C.POINTER(WeightedParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 7
     L.sc_hip_weighted.restype = C.c_int
+    L.sc_hip_wls_check.argtypes = [C.POINTER(WlsParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_wls_check.restype = C.c_int
+    L.sc_hip_wls_device.argtypes = [C.c_void_p, C.POINTER(WlsParams), C.POINTER(PoissonLayout), C.POINTER(WlsJob), C.c_int, C.c_bool]
+    L.sc_hip_wls_device.restype = C.c_int
+    L.sc_hip_wls.argtypes = [C.c_void_p, C.POINTER(WlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
+    L.sc_hip_wls.restype = C.c_int
     _lib = L
     return L
 
@@ -565,6 +581,58 @@ def weighted_arrays(data, weight, gx=None, gy=None, lap=None, boundary=None, out
     if boundary is not None:
         _same_shape_f32("boundary", boundary, data)
     return kind, data, weight, gx, gy, lap, boundary, out
+
+
+def wls_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0,
+              layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+              channel_stride=None) -> int:
+    """Host-only sc_hip_wls_check: SC_OK or the code a WLS call with these parameters and this layout returns before it runs anything.
+    The layout as a PoissonLayout or as keyword fields."""
+    p = WlsParams(int(kind), float(tol), int(max_iters), float(precond_lambda), float(precond_smooth))
+    return _check_call("sc_hip_wls_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def live_links(kind: int, H: int, W: int):
+    """(live_x, live_y), boolean H x W: the elements of smooth_x / smooth_y that a WLS call of this kind reads -- the links with at least
+    one end among the unknowns; the last column / row holds the wrapping link of a periodic axis and is not live otherwise."""
+    px, py = bool(kind & SC_POISSON_PERIODIC_X), bool(kind & SC_POISSON_PERIODIC_Y)
+    neu = bool(kind & SC_POISSON_NEUMANN)
+    unknown = np.ones((H, W), bool)
+    if not px:
+        unknown[:, 0] &= neu or bool(kind & SC_POISSON_FREE_LEFT)
+        unknown[:, -1] &= neu or bool(kind & SC_POISSON_FREE_RIGHT)
+    if not py:
+        unknown[0] &= neu or bool(kind & SC_POISSON_FREE_TOP)
+        unknown[-1] &= neu or bool(kind & SC_POISSON_FREE_BOTTOM)
+    lx = unknown | np.roll(unknown, -1, 1)
+    ly = unknown | np.roll(unknown, -1, 0)
+    if not px:
+        lx[:, -1] = False
+    if not py:
+        ly[-1] = False
+    return lx, ly
+
+
+def wls_arrays(data, weight, smooth_x, smooth_y, gx=None, gy=None, lap=None, boundary=None, out=None, neumann=False, free_sides="",
+               periodic=""):
+    """Checks a WLS problem's numpy arrays before any device is touched: (kind, data, weight, smooth_x, smooth_y, gx, gy, lap, boundary,
+    out), weighted_arrays' rules for all but the link weights.  smooth_x, smooth_y: float32, of data's shape or H x W (broadcast over
+    the channels), finite and > 0 on every live link (live_links); what is not live may hold anything."""
+    if smooth_x is None or smooth_y is None:
+        raise ValueError("a WLS solve needs its link weights smooth_x and smooth_y")
+    kind, data, weight, gx, gy, lap, boundary, out = weighted_arrays(data, weight, gx, gy, lap, boundary, out, neumann, free_sides, periodic)
+    lx, ly = live_links(kind, *data.shape[:2])
+    links = []
+    for name, a, live in (("smooth_x", smooth_x, lx), ("smooth_y", smooth_y, ly)):
+        if isinstance(a, np.ndarray) and a.ndim == 2 and data.ndim == 3 and a.shape == data.shape[:2]:
+            a = np.ascontiguousarray(np.broadcast_to(a[:, :, None], data.shape))
+        _same_shape_f32(name, a, data)
+        v = a[live]
+        if not (np.isfinite(v).all() and (v > 0).all()):
+            raise ValueError(f"{name} must be finite and > 0 on every live link")
+        links.append(a)
+    return kind, data, weight, links[0], links[1], gx, gy, lap, boundary, out
 
 
 class Instance:
@@ -814,6 +882,30 @@ class Instance:
         and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other
         failures raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_weighted_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- WLS solves on float32 arrays
+    def wls(self, data, weight, smooth_x, smooth_y, gx=None, gy=None, lap=None, boundary=None, neumann=False, out=None, free_sides="",
+            periodic="", tol=0.0, max_iters=0, precond_lambda=0.0, precond_smooth=0.0, allow_not_converged=False):
+        """sc_hip_wls on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise sum weight (u - data)^2 +
+        sum smooth_x (d_x u - gx)^2 + sum smooth_y (d_y u - gy)^2 (or with div(smooth g) given as lap; neither: zero guidance) under the
+        borders of poisson().  smooth_x[y, x] weighs the link (x, y) - (x + 1, y), smooth_y[y, x] the link (x, y) - (x, y + 1); > 0 on
+        every live link (live_links), of data's shape or H x W.  tol, max_iters, precond_lambda, precond_smooth: sc_wls_params' (0: the
+        defaults).  Returns out; info() has the iterations and the final residual."""
+        kind, data, weight, sx, sy, gx, gy, lap, boundary, out = wls_arrays(data, weight, smooth_x, smooth_y, gx, gy, lap, boundary, out,
+                                                                            neumann, free_sides, periodic)
+        p = WlsParams(kind, float(tol), int(max_iters), float(precond_lambda), float(precond_smooth))
+        return self._host_call("sc_hip_wls", p, (gx, gy, lap, data, weight, sx, sy, boundary), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_wls_jobs(n: int):
+        return (WlsJob * n)()
+
+    def wls_device(self, params: WlsParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_wls_device: jobs is a WlsJob array (make_wls_jobs) of device pointers, one layout for all.  sync: bSync and a wait for
+        the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures raise unless
+        allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -14,7 +14,7 @@
 //   5. sc_hip_poisson_check over valid and invalid layouts (the overlap test's 128-bit arithmetic at extreme strides included).
 //   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
-//      launch, so it is not reachable here).
+//      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
@@ -396,6 +396,10 @@ int main()
             sc_weighted_params p{ k.kind, k.tol, k.iters, k.plam };
             sc_poisson_layout l{ k.w, k.h, k.c, k.cs, k.rs, k.chs };
             if (sc_hip_weighted_check(&p, &l) != k.want) return fail("weighted_check");
+            sc_wls_params q{ k.kind, k.tol, k.iters, k.plam, 0.f };
+            if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check");
+            q.precond_smooth = k.plam;          // (the same values make the same verdicts)
+            if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check (precond_smooth)");
         }
         sc_weighted_params p{ SC_POISSON_GUIDANCE, 0.f, 0, 0.f };
         if (sc_hip_weighted_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_weighted_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("weighted_check (null)");

@@ -353,7 +353,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     }
     if (I->fft.ev_fork) (void)hipEventDestroy(I->fft.ev_fork);
     if (I->fft.ev_built) (void)hipEventDestroy(I->fft.ev_built);
-    for (DevBuf *b : { &I->wt.u, &I->wt.r, &I->wt.p, &I->wt.q, &I->wt.w, &I->wt.red }) dev_release(*b);
+    for (DevBuf *b : { &I->wt.u, &I->wt.r, &I->wt.p, &I->wt.q, &I->wt.w, &I->wt.e, &I->wt.s, &I->wt.dg, &I->wt.red }) dev_release(*b);
     if (I->wt.h_red.p) (void)hipHostFree(I->wt.h_red.p);
     for (hipEvent_t e : I->wt.ev) if (e) (void)hipEventDestroy(e);
     dev_release(I->mg_fd);
@@ -374,7 +374,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     if (I->h_maxcorr) (void)hipHostFree(I->h_maxcorr);
     if (I->h_rect) (void)hipHostFree(I->h_rect);
     if (I->h_red) (void)hipHostFree(I->h_red);
-    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in, &I->h_hyst }) if (b->p) (void)hipHostFree(b->p);
+    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in, &I->h_hyst, &I->h_sx, &I->h_sy }) if (b->p) (void)hipHostFree(b->p);
     for (int i = 0; i < 8; ++i) if (I->ev[i]) (void)hipEventDestroy(I->ev[i]);
     for (int i = 0; i < 8; ++i) if (I->ev_chunk[i]) (void)hipEventDestroy(I->ev_chunk[i]);
     if (I->ev_k0) (void)hipEventDestroy(I->ev_k0);

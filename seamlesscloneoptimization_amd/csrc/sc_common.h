@@ -157,6 +157,25 @@ void launch_weighted_dot(const WeightedGeo &wg, int planes, const float *R, cons
 void launch_weighted_dir(const WeightedGeo &wg, int planes, float *P, const float *Z, const double *rz, const double *rz_old, hipStream_t s);
 // the jobs' out: U at the unknowns, boundary's values on the Dirichlet lines
 void launch_weighted_out(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, int m, const float *U, hipStream_t s);
+// ---- the WLS solve (sc_wls.hip: kernels; sc_wls_api.cpp: its side of the shared iteration): the weighted solve's conjugate gradients on
+// L u = b, (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p), with per-link weights sx, sy > 0 under the call's layout.  Work planes,
+// tiling and partial sums are the weighted solve's (WeightedGeo); the update, dot, direction and output launches are its own.
+struct WlsJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX]; };
+constexpr int WLS_STATS = 4;
+// the live links of one plane: those with at least one end among the unknowns
+double wls_live_links(const WeightedGeo &wg);
+// stats[(plane * WEIGHTED_PARTS + i) * WLS_STATS + ..] = the part's sum of w | how many w are negative or not finite | the sum of its
+// live links, each counted once | how many of them are not finite or not > 0
+void launch_wls_stats(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                      const float *const *sy, int m, double *stats, hipStream_t s);
+// R = b (the order: seamlessclone_hip.h, the WLS section), E / S = the link to the next unknown column / row (0: none), Dg = the sum of
+// the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b
+void launch_wls_setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                      const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
+// residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
+void launch_wls_op(const WeightedGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
+                   double *parts, hipStream_t s);
+void launch_wls_scale(const WeightedGeo &wg, int planes, float *U, float f, hipStream_t s);      // U *= f
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

@@ -84,7 +84,8 @@ struct FftState {
 struct WeightedState {
     enum { LAG = SC_WEIGHTED_POLL, RING = SC_WEIGHTED_POLL + 1 };
     DevBuf u, r, p, q, w;
-    DevBuf red;                            // double: weight statistics | b.b | p.q | r.r | r.z of even / odd iterations (WEIGHTED_PARTS per plane each) | ||r||^2 per plane
+    DevBuf e, s, dg;                       // the WLS solve's coefficient planes (sc_wls.hip): links east, links south, the diagonal
+    DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (WEIGHTED_PARTS per plane each) | ||r||^2 per plane
     DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane
     hipEvent_t ev[RING]{};
 };
@@ -171,6 +172,7 @@ struct Instance {
     // page-locked host staging (grow-only): pageable caller images are packed here row by row so
     // each image crosses PCIe as ONE DMA instead of one slow pageable 2-D copy
     DevBuf h_face, h_body, h_mask, h_out;
+    DevBuf h_sx, h_sy;                             // a WLS host call's two link arrays (float_stage)
     std::unique_ptr<RowCopier> copier;   // helper threads for the packing / splicing copies (created on first use)
     hipEvent_t ev_chunk[8]{};            // D2H chunk completions (host path): splice chunk k while k+1 is in flight
     // ROI mask after 3x erode
@@ -371,8 +373,8 @@ inline bool poisson_no_dirichlet(int kind)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 // What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
-enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2 };
-struct FloatArrays { const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; };
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4 };
+struct FloatArrays { const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; const float *smooth_x = nullptr, *smooth_y = nullptr; };
 // A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
 // family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
 int family_validate(const int *kind, const sc_poisson_layout *l, const char *own, const char *limit_why, const char **why);
@@ -381,14 +383,18 @@ int family_validate(const int *kind, const sc_poisson_layout *l, const char *own
 int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, const char *method_why, const char *fp64_why);
 // A job's own code: the pointers its kind (poisson_norm_kind's) and family need, each 4-byte aligned.  Without a Dirichlet line on any
 // side a Poisson job may come without boundary (mean zero) and the other families do not read it: float_dev_job drops it there.
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why);
+// FLOAT_SMOOTH: the two link arrays as well, and -- span > 0, the floats an array occupies under the call's layout (poisson_span) --
+// neither they nor weight may share a float of their span with out's.
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0);
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
-// The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT) and where each one's code goes.
-struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w; std::vector<int *> rcs; };
+// The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT), their link weights (NULL without
+// FLOAT_SMOOTH) and where each one's code goes.
+struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy; std::vector<int *> rcs; };
 // A device call's job intake: arrays_of(job) names one public job's arrays.  A job that fails float_job_validate gets its code; the
 // others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
 // empty: nothing to run).
-template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int carries, Job *jobs, int n, ArraysOf arrays_of, FloatJobs &v)
+template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int carries, Job *jobs, int n, ArraysOf arrays_of, FloatJobs &v,
+                                                      size_t span = 0)
 {
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
@@ -396,7 +402,7 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
     for (int i = 0; i < n; ++i) {
         Job &j = jobs[i];
         const FloatArrays a = arrays_of(j);
-        const int vrc = float_job_validate(kind, carries, a, &why);
+        const int vrc = float_job_validate(kind, carries, a, &why, span);
         if (vrc != SC_OK) {
             j.rc = vrc;
             if (worst == SC_OK) { worst = vrc; I->err = why; }
@@ -405,14 +411,16 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
         j.rc = SC_ERR_HIP;          // until its chunk has run
         v.dj.push_back(float_dev_job(kind, carries, a));
         v.w.push_back(a.weight);
+        v.sx.push_back(a.smooth_x);
+        v.sy.push_back(a.smooth_y);
         v.rcs.push_back(&j.rc);
     }
     return worst;
 }
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
-// boundary unless it is data | out unless it is data or boundary (in place) --, uploaded in that order.  job: the device job
-// (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights.
-struct FloatStaged { PoissonJobDev job; const float *d_w; };
+// boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y --, uploaded in that order.  job: the
+// device job (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights, d_sx, d_sy: the link weights.
+struct FloatStaged { PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr; };
 int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s);
 // nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and
 // sets their codes.  SC_OK and SC_ERR_NOT_CONVERGED let the call go on; any other code ends it: that chunk's jobs and every one not
@@ -433,6 +441,38 @@ template <class Chunk> int run_chunks(Instance *I, int C, int *const *rcs, int n
     }
     return worst;
 }
+// The preconditioned conjugate gradients that the weighted and the WLS call share (pcg_run, sc_weighted_api.cpp), and what a family tells
+// the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat` doubles per part; the
+// driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets SC_ERR_BAD_ARG and
+// leaves; NULL: it stays, its arrays move to the front and its sums count) -> precond_constant -> setup -> scale_start on u0 -> apply,
+// once in its residual form and then once per iteration.  Everything else -- the preconditioner through direct_jobs_solve, the update, dot and direction launches,
+// the stop rule's mailbox, the output launch -- is the driver's own and the same for both families.
+struct PcgOperator {
+    const int nstat;                       // doubles per part of the statistics launch
+    std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
+    explicit PcgOperator(int nstat_) : nstat(nstat_) {}
+    virtual ~PcgOperator() = default;
+    virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
+    virtual void stats(const PoissonGeo &g, const WeightedGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
+    // st: job k's statistics, its C planes' WEIGHTED_PARTS * nstat doubles each, of which the first `parts` parts are set
+    virtual const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) = 0;
+    virtual float precond_constant(const PoissonGeo &g, const WeightedGeo &wg, int mv) = 0;      // lam: the driver's preconditioner is A - lam
+    virtual int setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, int mv, float *R, double *bb) = 0;      // R = b, the coefficient planes, bb = the parts of b . b
+    // the start u0 = (A - lam)^-1 b where the family's preconditioner is a multiple of A - lam: its one-off factor (a constant factor
+    // on the preconditioner changes no later iterate, so the loop never applies it).  The default: none.
+    virtual void scale_start(const WeightedGeo &wg, int planes, float *U, hipStream_t s) {}
+    virtual void apply(const WeightedGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) = 0;
+    // the sum of field f of one plane's statistics over its first `parts` parts
+    double stat_sum(const double *plane, int parts, int f) const
+    {
+        double sum = 0.0;
+        for (int i = 0; i < parts; ++i) sum += plane[(size_t)nstat * i + f];
+        return sum;
+    }
+};
+struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
+// The validated jobs of a call through chunks (run_chunks) and sc_run_info.  Returns the worst code, the jobs' own refusals included.
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed);
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
 int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);

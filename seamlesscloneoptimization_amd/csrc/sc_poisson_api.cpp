@@ -117,7 +117,7 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 
 // (a job without a Dirichlet line on any side -- the Neumann call, a periodic axis beside a periodic or free-free one -- needs no
 // boundary: out is then checked in its place)
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why)
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span)
 {
     if ((carries & FLOAT_DATA) && !a.data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
     if ((carries & FLOAT_WEIGHT) && !a.weight) { *why = "null weight pointer"; return SC_ERR_BAD_ARG; }
@@ -129,6 +129,15 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
         if (i < 2 && !(carries & (i ? FLOAT_WEIGHT : FLOAT_DATA))) continue;      // not this family's
         if (!q) { *why = "null array pointer"; return SC_ERR_BAD_ARG; }
         if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
+    if (carries & FLOAT_SMOOTH) {
+        for (const float *q : { a.smooth_x, a.smooth_y }) {
+            if (!q) { *why = "null smooth_x or smooth_y pointer"; return SC_ERR_BAD_ARG; }
+            if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+        }
+        const uintptr_t o = (uintptr_t)a.out, bytes = span * sizeof(float);
+        for (const float *q : { a.weight, a.smooth_x, a.smooth_y })
+            if (span && (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes) { *why = "weight, smooth_x or smooth_y overlaps out"; return SC_ERR_BAD_ARG; }
     }
     return SC_OK;
 }
@@ -148,7 +157,8 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     // (the Poisson call keeps a boundary without a Dirichlet line: it gives the mean)
     const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
-    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1);
+    const bool smooth = (carries & FLOAT_SMOOTH) != 0;
+    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -158,6 +168,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_in0 = next(true), *d_in1 = next(guidance), *d_d = next(data != nullptr), *d_w = next(weight != nullptr);
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
+    float *d_sx = next(smooth), *d_sy = next(smooth);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -166,6 +177,10 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     if ((rc = upload(I->h_mask, own_b ? d_b : nullptr, boundary))) return rc;
     s.job = float_dev_job(kind, carries, FloatArrays{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_d, d_w, d_b, d_out });
     s.d_w = d_w;
+    if ((rc = upload(I->h_sx, d_sx, a.smooth_x))) return rc;      // (pinned blocks of their own: the uploads stay back to back)
+    if ((rc = upload(I->h_sy, d_sy, a.smooth_y))) return rc;
+    s.d_sx = d_sx;
+    s.d_sy = d_sy;
     return SC_OK;
 }
 

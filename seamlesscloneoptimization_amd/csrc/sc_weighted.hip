@@ -9,25 +9,12 @@
 // three plane transfers: p and w in, q out).  Reductions: a lane's running sum in double, the wave's by sc_wave.h's shuffles, the four
 // waves' through LDS in a fixed order; a plane's total is added up from its parts by every workgroup that needs it, again in one
 // order -- two runs of a call give the same bytes.
-#include "sc_common.h"
-#include "sc_wave.h"
-#include <algorithm>
+#include "sc_pcg_device.h"
 #include <cmath>
 
 namespace sc {
 
 namespace {
-
-constexpr int WL = 256;      // lanes per workgroup
-
-// the workgroup's sum (valid in every lane after the barrier); ws: 4 doubles of LDS of this call's own
-__device__ __forceinline__ double block_sum(double v, double *ws)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
 
 // a plane's total from its n parts: the calling wave's 64 lanes stride through them, then the butterfly
 __device__ __forceinline__ double parts_sum(const double *__restrict__ p, int n, int lane)
@@ -142,14 +129,6 @@ __global__ __launch_bounds__(WL) void k_w_op(WeightedGeo wg, const float *__rest
     }
     s = block_sum(s, ws);
     if (threadIdx.x == 0) parts[(size_t)blockIdx.z * WEIGHTED_PARTS + blockIdx.y * wg.cg + blockIdx.x] = s;
-}
-
-// the float4 groups [g0, g1) of a plane of n floats that segment `part` owns
-__device__ __forceinline__ void segment(const WeightedGeo &wg, int part, int &g0, int &g1)
-{
-    const int per = (wg.egroups + wg.eparts - 1) / wg.eparts;
-    g0 = part * per;
-    g1 = min(g0 + per, wg.egroups);
 }
 
 __global__ __launch_bounds__(WL) void k_w_update(WeightedGeo wg, float *__restrict__ U, float *__restrict__ R, const float *__restrict__ P,

@@ -17,6 +17,9 @@
 //      of this file's and the preconditioner's three or five, nothing read by the host but the stop rule's norms, SC_WEIGHTED_POLL
 //      iterations late.
 //   5. u and the Dirichlet lines of boundary into the jobs' out.
+// The iteration (pcg_chunk, pcg_run) is shared with the WLS call (sc_wls_api.cpp): a family describes its operator to it as a PcgOperator
+// (sc_instance.h) -- statistics and what they refuse, the preconditioner's constant, set-up, a factor on the start, operator application; WeightedOperator below
+// is this family's, and steps 1 to 5 are the launches it has always made, in the same order.
 #include "sc_instance.h"
 #include <algorithm>
 #include <cmath>
@@ -49,80 +52,112 @@ int weighted_begin(void *inst, const sc_weighted_params *p, const sc_poisson_lay
         "a weighted solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
 }
 
-struct WCall { int kind; float tol; int max_iters; float plam; };
-
 struct ChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
 
-// One chunk of m same-size jobs.  Jobs whose weights do not pass get their code here and take no further part; the rest share one
-// iteration and one code (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call).
-int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const PoissonJobDev *jobs, const float *const *ws, int *const *rcs, int m,
-                   ChunkResult &res, int &job_errors)
+// This family's operator: A - W on the work planes, W = the weights copied onto S.w.
+struct WeightedOperator final : PcgOperator {
+    Instance *I;
+    const float *const *all_w;
+    float plam;
+    std::vector<const float *> dw;
+    int kept = 0;
+    double wsum = 0.0;
+    WeightedOperator(Instance *I_, const float *const *w, float plam_) : PcgOperator(2), I(I_), all_w(w), plam(plam_) {}
+    void begin(int i0, int m) override { dw.assign(all_w + i0, all_w + i0 + m); kept = 0; wsum = 0.0; }
+    void stats(const PoissonGeo &g, const WeightedGeo &wg, int m, double *d_stats, hipStream_t s) override
+    {
+        launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
+    }
+    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
+    {
+        double job_sum = 0.0;
+        bool bad = false, empty = false;
+        for (int c = 0; c < g.C; ++c) {
+            const double *plane = st + (size_t)c * WEIGHTED_PARTS * 2;
+            const double sum = stat_sum(plane, parts, 0);
+            bad = bad || stat_sum(plane, parts, 1) != 0.0;
+            empty = empty || !(sum > 0.0);
+            job_sum += sum;
+        }
+        if (bad || !std::isfinite(job_sum)) return "a weight is negative or not finite";
+        if (no_dirichlet && empty) return "no data weight and no Dirichlet line";
+        dw[kept++] = dw[k];
+        wsum += job_sum;
+        return nullptr;
+    }
+    float precond_constant(const PoissonGeo &g, const WeightedGeo &wg, int mv) override
+    {
+        const double n_unknowns = (double)wg.nx * (double)wg.ny * (double)(g.C * mv);
+        return plam > 0.f ? plam : (float)(wsum / n_unknowns);      // (0: no weight anywhere, under Dirichlet lines -- the unscreened solve)
+    }
+    int setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, int mv, float *R, double *bb) override
+    {
+        const int rc = ensure(I, I->wt.w, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
+        if (rc) return rc;
+        launch_weighted_setup(g, wg, lap, dj.data(), dw.data(), mv, R, (float *)I->wt.w.p, bb, I->stream);
+        return SC_OK;
+    }
+    void apply(const WeightedGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
+    {
+        launch_weighted_op(wg, planes, residual, P, (const float *)I->wt.w.p, Q, parts, s);
+    }
+};
+
+} // namespace
+
+namespace sc {
+
+// One chunk of m same-size jobs.  Jobs that their family's statistics refuse get their code here and take no further part; the rest
+// share one iteration and one code (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call).
+static int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, ChunkResult &res, int &job_errors)
 {
     const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
     const WeightedGeo wg = weighted_geo(mg);
     const bool lap = poisson_base(call.kind) == SC_POISSON_LAPLACIAN, no_dirichlet = poisson_no_dirichlet(call.kind);
     const bool fp64 = (I->opts.flags & SC_FLAG_FFT_FP64) != 0;
-    const int nop = weighted_op_parts(wg);
+    const int nop = weighted_op_parts(wg), nstat = op.nstat;
     WeightedState &S = I->wt;
     hipStream_t s = I->stream;
     int rc;
     for (hipEvent_t &e : S.ev)
         if (!e) SC_HIP(I, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // the partial sums: statistics (2 per part) | bb | pq | rr | rz[0] | rz[1] | rr_tot
+    // the partial sums: statistics (nstat per part) | bb | pq | rr | rz[0] | rz[1] | rr_tot
     const size_t all_planes = (size_t)g.C * m, per = all_planes * WEIGHTED_PARTS;
-    if ((rc = ensure(I, S.red, sizeof(double) * (per * 7 + all_planes), false))) return rc;
-    if ((rc = ensure_pinned(I, S.h_red, sizeof(double) * (per * 2 + per + all_planes * W_RING)))) return rc;
-    double *d_stats = (double *)S.red.p, *d_bb = d_stats + 2 * per, *d_pq = d_bb + per, *d_rr = d_pq + per;
+    if ((rc = ensure(I, S.red, sizeof(double) * (per * (nstat + 5) + all_planes), false))) return rc;
+    if ((rc = ensure_pinned(I, S.h_red, sizeof(double) * (per * nstat + per + all_planes * W_RING)))) return rc;
+    double *d_stats = (double *)S.red.p, *d_bb = d_stats + nstat * per, *d_pq = d_bb + per, *d_rr = d_pq + per;
     double *d_rz[2] = { d_rr + per, d_rr + 2 * per }, *d_tot = d_rr + 3 * per;
-    double *h_stats = (double *)S.h_red.p, *h_bb = h_stats + 2 * per, *h_tot = h_bb + per;
+    double *h_stats = (double *)S.h_red.p, *h_bb = h_stats + nstat * per, *h_tot = h_bb + per;
 
-    // 1. the weights
-    std::vector<PoissonJobDev> dj(jobs, jobs + m);
-    std::vector<const float *> dw(ws, ws + m);
-    launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
+    // 1. the statistics
+    op.stats(g, wg, m, d_stats, s);
     SC_HIP(I, hipGetLastError());
-    SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * 2 * per, hipMemcpyDeviceToHost, s));
+    SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * nstat * per, hipMemcpyDeviceToHost, s));
     SC_HIP(I, hipStreamSynchronize(s));
-    std::vector<int *> live;       // the codes of the jobs that stay, their arrays moved to the front of dj and dw
-    double wsum = 0.0;
+    std::vector<int *> live;       // the codes of the jobs that stay, their arrays moved to the front
     for (int k = 0; k < m; ++k) {
-        double job_sum = 0.0;
-        bool bad = false, empty = false;
-        for (int c = 0; c < g.C; ++c) {
-            const double *st = h_stats + ((size_t)k * g.C + c) * WEIGHTED_PARTS * 2;
-            double sum = 0.0;
-            for (int i = 0; i < nop; ++i) { sum += st[2 * i]; bad = bad || st[2 * i + 1] != 0.0; }
-            empty = empty || !(sum > 0.0);
-            job_sum += sum;
-        }
-        if (bad || !std::isfinite(job_sum)) {
+        const char *why = op.judge(g, k, h_stats + (size_t)k * g.C * WEIGHTED_PARTS * nstat, nop, no_dirichlet);
+        if (why) {
             *rcs[k] = SC_ERR_BAD_ARG;
-            if (!job_errors++) I->err = "a weight is negative or not finite";
-        } else if (no_dirichlet && empty) {
-            *rcs[k] = SC_ERR_BAD_ARG;
-            if (!job_errors++) I->err = "no data weight and no Dirichlet line";
+            if (!job_errors++) I->err = why;
         } else {
-            dj[live.size()] = dj[k];
-            dw[live.size()] = dw[k];
+            op.dj[live.size()] = op.dj[k];
             live.push_back(rcs[k]);
-            wsum += job_sum;
         }
     }
     const int mv = (int)live.size(), planes = g.C * mv;
     res = ChunkResult();
     if (!mv) return SC_OK;
-    const double n_unknowns = (double)wg.nx * (double)wg.ny * (double)planes;
-    const float lam = call.plam > 0.f ? call.plam : (float)(wsum / n_unknowns);      // (0: no weight anywhere, under Dirichlet lines -- the unscreened solve)
+    const float lam = op.precond_constant(g, wg, mv);
 
     // 2. the work planes
     const size_t plane_bytes = sizeof(float) * (size_t)wg.stride * planes;
-    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w })
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q })
         if ((rc = ensure(I, *b, plane_bytes, false))) return rc;
-    float *U = (float *)S.u.p, *R = (float *)S.r.p, *P = (float *)S.p.p, *Q = (float *)S.q.p, *Wc = (float *)S.w.p, *Z = Q;
-    launch_weighted_setup(g, wg, lap, dj.data(), dw.data(), mv, R, Wc, d_bb, s);
+    float *U = (float *)S.u.p, *R = (float *)S.r.p, *P = (float *)S.p.p, *Q = (float *)S.q.p, *Z = Q;
+    if ((rc = op.setup(g, wg, lap, mv, R, d_bb))) return rc;
     SC_HIP(I, hipGetLastError());
     SC_HIP(I, hipMemcpyAsync(h_bb, d_bb, sizeof(double) * (size_t)planes * WEIGHTED_PARTS, hipMemcpyDeviceToHost, s));
-
     // 3. the preconditioner: (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the
     // pointers are moved back by the first unknown's offset, and only unknowns are ever addressed (no boundary: no Dirichlet line is
     // read or written)
@@ -143,7 +178,7 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const Po
         return SC_OK;
     };
     const double tol = call.tol > 0.f ? (double)call.tol : 1e-5;
-    const int max_iters = call.max_iters > 0 ? call.max_iters : 200;
+    const int max_iters = call.max_iters > 0 ? call.max_iters : call.default_iters;
     std::vector<double> bb(planes, 0.0);
     bool have_bb = false;
     // the worst plane's ||r|| / ||b|| of iteration k (waits for its event)
@@ -163,7 +198,8 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const Po
         return SC_OK;
     };
     if ((rc = precond(R, U))) return rc;                                           // u0 = M^-1 b
-    launch_weighted_op(wg, planes, true, U, Wc, R, d_rr, s);                       // r = b - (A - W) u0
+    op.scale_start(wg, planes, U, s);
+    op.apply(wg, planes, true, U, R, d_rr, s);                                     // r = b - (A - W) u0
     if ((rc = precond(R, Z))) return rc;
     launch_weighted_dot(wg, planes, R, Z, d_rz[0], d_rr, nop, d_tot, s);
     if ((rc = post_norms(0))) return rc;
@@ -180,7 +216,7 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const Po
             if (worst <= tol) { seen = true; break; }
             if (worst != worst) break;                                             // NaN: nothing more to gain
         }
-        launch_weighted_op(wg, planes, false, P, Wc, Q, d_pq, s);
+        op.apply(wg, planes, false, P, Q, d_pq, s);
         launch_weighted_update(wg, planes, U, R, P, Q, d_rz[(k - 1) & 1], d_pq, d_rr, s);
         if ((rc = precond(R, Z))) return rc;
         launch_weighted_dot(wg, planes, R, Z, d_rz[k & 1], d_rr, wg.eparts, d_tot, s);
@@ -199,16 +235,14 @@ int weighted_chunk(Instance *I, const WCall &call, const PoissonGeo &g, const Po
     res.converged = seen;
 
     // 5. the output
-    launch_weighted_out(g, wg, dj.data(), mv, U, s);
+    launch_weighted_out(g, wg, op.dj.data(), mv, U, s);
     SC_HIP(I, hipGetLastError());
     const int code = res.converged ? SC_OK : SC_ERR_NOT_CONVERGED;
     for (int k = 0; k < mv; ++k) *live[k] = code;
     return code;
 }
 
-// The validated jobs of a call through chunks (run_chunks).  Returns the worst code, job errors of the weights included.
-int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, const PoissonJobDev *jobs, const float *const *ws, int *const *rcs,
-                 int nv, bool timed)
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed)
 {
     CallScope scope{ I };
     const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
@@ -221,7 +255,9 @@ int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, con
     double rel = 0.0;
     int worst = run_chunks(I, g.C, rcs, nv, [&](int i0, int m) {
         ChunkResult res;
-        const int rc = weighted_chunk(I, call, g, jobs + i0, ws + i0, rcs + i0, m, res, job_errors);
+        op.dj.assign(jobs + i0, jobs + i0 + m);
+        op.begin(i0, m);
+        const int rc = pcg_chunk(I, call, g, op, rcs + i0, m, res, job_errors);
         sweeps = std::max(sweeps, res.iters);
         converged = converged && res.converged;
         rel = std::max(rel, res.rel);
@@ -244,7 +280,7 @@ int weighted_run(Instance *I, const WCall &call, const sc_poisson_layout *l, con
     return worst;
 }
 
-} // namespace
+} // namespace sc
 
 extern "C" {
 
@@ -263,7 +299,8 @@ int sc_hip_weighted_device(void *inst, const sc_weighted_params *p, const sc_poi
         return FloatArrays{ j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out }; }, v);
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, v.dj.data(), v.w.data(), v.rcs.data(), (int)v.rcs.size(), bSync);
+    WeightedOperator op(I, v.w.data(), p->precond_lambda);
+    rc = pcg_run(I, PcgCall{ kind, p->tol, p->max_iters, 200 }, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), bSync);
     return worse(worst, rc);
 }
 
@@ -279,9 +316,10 @@ int sc_hip_weighted(void *inst, const sc_weighted_params *p, const sc_poisson_la
     FloatStaged s;
     if ((rc = float_stage(I, l, kind, FLOAT_DATA | FLOAT_WEIGHT, a, s))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
-    rc = weighted_run(I, WCall{ kind, p->tol, p->max_iters, p->precond_lambda }, l, &s.job, &s.d_w, job_rcs, 1, true);
+    WeightedOperator op(I, &s.d_w, p->precond_lambda);
+    rc = pcg_run(I, PcgCall{ kind, p->tol, p->max_iters, 200 }, l, op, &s.job, job_rcs, 1, true);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: weighted_run times the call whole)
+    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)
     return poisson_download(I, l, s.job.out, out, t, rc);
 }
 

@@ -477,11 +477,104 @@ def weighted_solve_batch(datas, weights, gxs=None, gys=None, laplacians=None, bo
                         lambda inst, layout, jobs: inst._check(inst.weighted_device(params, layout, jobs)), gpu_id, solver)
 
 
-def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, **solver):
+def wls_solve(data, weight, smooth_x, smooth_y, gx=None, gy=None, laplacian=None, boundary=None, neumann=True, free_sides=None, periodic="",
+              tol=None, max_iters=None, precond_lambda=None, precond_smooth=None, gpu_id=0, **solver):
+    """WLS solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
+        sum weight (u - data)^2 + sum smooth_x (u[y, x+1] - u[y, x] - gx)^2 + sum smooth_y (u[y+1, x] - u[y, x] - gy)^2
+    (or with div(smooth g) given as laplacian; neither: zero guidance): weighted_solve with a weight on every link between two
+    neighbouring pixels.  smooth_x[y, x] weighs the link (x, y) - (x + 1, y), smooth_y[y, x] the link (x, y) - (x, y + 1); float32, of
+    data's shape or H x W, finite and > 0 on every link that has an unknown end (the last column / row counts only along a periodic
+    axis, where it holds the link across the seam).  Borders, tol and weight as weighted_solve's; max_iters defaults to 400.  The
+    preconditioner is the direct solve scaled by the mean link weight (precond_smooth overrides it) with the mean data weight over it as
+    its constant (precond_lambda overrides the mean data weight)."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.wls(data, weight, smooth_x, smooth_y, gx=gx, gy=gy, lap=laplacian, boundary=boundary, neumann=neumann,
+                        free_sides=free_sides, periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0,
+                        precond_lambda=precond_lambda or 0.0, precond_smooth=precond_smooth or 0.0)
+    finally:
+        inst.destroy()
+
+
+def wls_solve_batch(datas, weights, smooth_xs, smooth_ys, gxs=None, gys=None, laplacians=None, boundaries=None, neumann=True, free_sides=None,
+                    periodic="", tol=None, max_iters=None, precond_lambda=None, precond_smooth=None, gpu_id=0, **solver):
+    """wls_solve over a list of same-shape problems through ONE device-resident call (sc_hip_wls_device), as weighted_solve_batch: one
+    copy in, one copy out, one joint stop, the preconditioner's two constants the chunk's means -- a member agrees with its solo solve to
+    the stop rule's error.  Returns a list of NEW arrays."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
+    ds, ws, sxs, sys_ = list(datas), list(weights), list(smooth_xs), list(smooth_ys)
+    n = len(ds)
+    if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None):
+        raise ValueError("give gxs and gys, or laplacians, or neither")
+    fields = [ws, sxs, sys_] + ([gxs, gys] if gxs is not None else [laplacians] if laplacians is not None else [])
+    if not no_boundary:
+        if boundaries is None:
+            raise ValueError("a WLS solve with a Dirichlet line needs boundaries")
+        fields = fields + [boundaries]
+    for f in fields:
+        if len(f) != n:
+            raise ValueError("one weight, one pair of link weights, one guidance field (or laplacian) and, with a Dirichlet line, one boundary "
+                             "per data term")
+    if not ds:
+        return []
+    checked = []
+    for k in range(n):
+        b = None if no_boundary else boundaries[k]
+        kind, d, w, sx, sy, gx, gy, lap, b, _ = capi.wls_arrays(ds[k], ws[k], sxs[k], sys_[k], None if gxs is None else gxs[k],
+                                                                None if gys is None else gys[k],
+                                                                None if laplacians is None else laplacians[k], b, neumann=neumann,
+                                                                free_sides=free_sides, periodic=periodic)
+        if d.shape != ds[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        arrays = [("gx", gx), ("gy", gy)] if gx is not None else [("lap", lap)]
+        checked.append(arrays + [("data", d), ("weight", w), ("smooth_x", sx), ("smooth_y", sy)] + ([] if b is None else [("boundary", b)]))
+    params = capi.WlsParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0), float(precond_smooth or 0.0))
+    return _float_batch(checked, capi.Instance.make_wls_jobs,
+                        lambda inst, layout, jobs: inst._check(inst.wls_device(params, layout, jobs)), gpu_id, solver)
+
+
+def _forward_abs_differences(a):
+    """(|d/dx|, |d/dy|), H x W float64, of an H x W or H x W x C array (the root of the channels' summed squares); the last column / row,
+    which has no forward neighbour, holds 0"""
+    a = np.asarray(a, np.float64)
+    a = a[:, :, None] if a.ndim == 2 else a
+    dx, dy = np.zeros(a.shape[:2]), np.zeros(a.shape[:2])
+    dx[:, :-1] = np.sqrt(((a[:, 1:] - a[:, :-1]) ** 2).sum(2))
+    dy[:-1] = np.sqrt(((a[1:] - a[:-1]) ** 2).sum(2))
+    return dx, dy
+
+
+def wls_filter(image, lam=1.0, alpha=1.2, eps=1e-4, guide=None, gpu_id=0, **solver):
+    """Edge-preserving smoothing of a float32 image (H x W or H x W x C) by weighted least squares (Farbman, Fattal, Lischinski, Szeliski
+    2008): the image u that minimises sum (u - image)^2 + sum s |grad u|^2 with the link weights
+        s = lam / (|forward difference of l|^alpha + eps),      l = log(luminance + 1e-6) of the image, or of `guide`,
+    luminance the mean over the channels clipped at 0 -- smooth where l is flat, free to jump where l jumps.  lam sets the amount of
+    smoothing, alpha how sharply it falls off at edges.  Reflecting borders; the base layer of a base / detail decomposition (the detail
+    is image - result).  Returns a NEW array."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    if not (np.isfinite(lam) and lam > 0 and np.isfinite(alpha) and alpha >= 0 and np.isfinite(eps) and eps > 0):
+        raise ValueError("lam and eps must be finite and > 0, alpha finite and >= 0")
+    g = np.asarray(image if guide is None else guide, np.float64)
+    if g.shape[:2] != image.shape[:2]:
+        raise ValueError(f"guide has shape {g.shape[:2]}, the image {image.shape[:2]}")
+    lum = np.log(np.maximum(g if g.ndim == 2 else g.mean(2), 0.0) + 1e-6)
+    sx, sy = ((lam / (d ** alpha + eps)).astype(np.float32) for d in _forward_abs_differences(lum))
+    return wls_solve(image, np.ones(image.shape[:2], np.float32), sx, sy, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, guide=None, edge_sigma=None, **solver):
     """Fills a float32 image (H x W or H x W x C) from the pixels where known_mask (H x W, anything truthy) is set: the weighted solve
     with weight = strength on the mask and 0 elsewhere, data = values, under reflecting borders, with zero guidance (a membrane through
     the known pixels) or image_gradients = (gx, gy), forward differences the result should have.  strength weighs closeness to the known
-    values against the guidance: large values pin them.  Returns a NEW array."""
+    values against the guidance: large values pin them.  Returns a NEW array.
+    guide (H x W or H x W x C, any real dtype): the values stop spreading at the guide's edges -- the WLS solve with the link weights
+    exp(-d^2 / (2 edge_sigma^2)) + 1e-3, d the guide's forward difference (over its channels: the root of the summed squares);
+    edge_sigma None: a tenth of the guide's range.  Without a guide edge_sigma must be None too."""
     if not isinstance(values, np.ndarray) or values.dtype != np.float32:
         raise TypeError("values must be a float32 numpy array")
     m = np.asarray(known_mask)
@@ -491,6 +584,18 @@ def interpolate_constraints(values, known_mask, image_gradients=None, strength=1
         raise ValueError("strength must be finite and > 0")
     w = np.where(m.astype(bool), np.float32(strength), np.float32(0)).astype(np.float32)
     gx, gy = (None, None) if image_gradients is None else image_gradients
+    if guide is None and edge_sigma is not None:
+        raise ValueError("edge_sigma needs a guide")
+    if guide is not None:
+        g = np.asarray(guide, np.float64)
+        if g.shape[:2] != values.shape[:2]:
+            raise ValueError(f"guide has shape {g.shape[:2]}, the image {values.shape[:2]}")
+        sigma = 0.1 * float(g.max() - g.min()) if edge_sigma is None else float(edge_sigma)
+        if not np.isfinite(sigma) or not sigma > 0:
+            raise ValueError("edge_sigma must be finite and > 0 (None: a tenth of the guide's range, which must not be flat)")
+        sx, sy = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in _forward_abs_differences(g))
+        d = np.where(m.astype(bool).reshape(m.shape + (1,) * (values.ndim - 2)), values, np.float32(0)).astype(np.float32)
+        return wls_solve(d, w, sx, sy, gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
     return weighted_solve(np.where(m.astype(bool).reshape(m.shape + (1,) * (values.ndim - 2)), values, np.float32(0)).astype(np.float32), w,
                           gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
 

@@ -1,0 +1,144 @@
+"""CPU tests of the WLS solve: the numpy restatement (tests/wls_np.py) against its own dense solve and against the weighted restatement,
+sc_hip_wls_check's codes beside sc_hip_weighted_check's, what capi.wls_arrays refuses, and the entry points' presence in the library."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi
+
+import periodic_np
+import weighted_np
+import wls_bounds as lb
+import wls_np
+
+G, L = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN
+NEU, PX, PY = capi.SC_POISSON_NEUMANN, capi.SC_POISSON_PERIODIC_X, capi.SC_POISSON_PERIODIC_Y
+HWC = dict(cols=33, rows=47, channels=3, col_stride=3, row_stride=99, channel_stride=1)
+BORDERS = {b[0]: b[1:] for b in lb.BORDERS}
+
+
+def test_entry_points_are_exported():
+    lib = capi.load()
+    for name in ("sc_hip_wls_check", "sc_hip_wls_device", "sc_hip_wls"):
+        assert name in capi.declared_symbols()
+        assert hasattr(lib, name), name
+
+
+def _problem(border, H, W, C, wkind, skind, seed=0):
+    sides, periodic = BORDERS[border]
+    data, weight, sx, sy, lap, boundary = lb.make_input(H, W, C, wkind, skind, seed)
+    sx, sy = lb.dead_to_nan(sides, periodic, sx, sy)
+    return sides, periodic, data, weight, sx, sy, lap, boundary if wls_np.has_dirichlet(sides, periodic) else None
+
+
+@pytest.mark.parametrize("skind", ["loguniform", "edges"])
+@pytest.mark.parametrize("border", list(BORDERS))
+def test_reference_iteration_against_the_exact_solve(border, skind):
+    """pcg_f32 reaches 1e-5 well inside the budget and lands on the dense solve; the dense solve leaves no residual in operator()"""
+    sides, periodic, data, weight, sx, sy, lap, b = _problem(border, 21, 16, 2, "sparse", skind, seed=2)
+    assert (weight[wls_np.unknowns(sides, periodic, 21, 16)].reshape(-1, 2).sum(0) > 0).all()
+    want = wls_np.solve_exact(sides, periodic, weight, sx, sy, data, lap, b)
+    f = np.abs(wls_np.rhs(sides, periodic, weight, data, lap)).max()
+    assert np.abs(wls_np.residual(sides, periodic, weight, sx, sy, want, data, lap)).max() <= 1e-11 * max(f, np.nanmax(sx))
+    u, iters, rel = wls_np.pcg_f32(sides, periodic, weight, sx, sy, data, lap, b)
+    assert rel <= 1e-5 and iters <= 100, (iters, rel)
+    assert np.abs(u - want).max() <= 2e-4 * np.abs(want).max()
+    if b is not None:
+        m = periodic_np.dirichlet_mask(sides, periodic, 21, 16)
+        assert np.array_equal(want[m], b[m].astype(np.float64)) and np.array_equal(u[m], b[m])
+
+
+@pytest.mark.parametrize("border", list(BORDERS))
+def test_unit_links_are_the_weighted_solve(border):
+    sides, periodic, data, weight, _, _, lap, b = _problem(border, 19, 13, 2, "loguniform", "constant")
+    one = np.ones_like(data)
+    sx, sy = lb.dead_to_nan(sides, periodic, one, one)
+    mine = wls_np.folded_rhs(sides, periodic, weight, sx, sy, data, lap, b, np.float32)
+    theirs = weighted_np.folded_rhs(sides, periodic, weight, data, lap, b, np.float32)
+    # (the weighted restatement subtracts the sum of the Dirichlet neighbours, this one each in turn: the same bytes wherever an unknown
+    # has at most one of them, and the corners differ by a rounding of the sum)
+    assert np.array_equal(wls_np.rhs(sides, periodic, weight, data, lap), weighted_np.rhs(sides, periodic, weight, data, lap))
+    inner = (slice(1, -1), slice(1, -1))
+    assert np.array_equal(mine[inner], theirs[inner])
+    assert np.abs(mine - theirs).max() <= 4 * np.finfo(np.float32).eps * np.abs(theirs).max()
+    got = wls_np.solve_exact(sides, periodic, weight, sx, sy, data, lap, b)
+    want = weighted_np.solve_exact(sides, periodic, weight, data, lap, b)
+    assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
+    gx, gy = (0.1 * np.random.default_rng(3).standard_normal((2,) + data.shape)).astype(np.float32)
+    assert np.array_equal(wls_np.divergence(sides, periodic, sx, sy, gx, gy)[wls_np.unknowns(sides, periodic, 19, 13)],
+                          periodic_np.divergence(gx, gy, periodic)[wls_np.unknowns(sides, periodic, 19, 13)])
+
+
+@pytest.mark.parametrize("border", list(BORDERS))
+def test_constant_links_scale_the_weighted_solve(border):
+    """links c everywhere: L = c (A - W / c), so u(w, lap) is the weighted solution of (w / c, lap / c) -- with a power of two for c
+    the two right-hand sides are the same floats scaled"""
+    sides, periodic, data, weight, _, _, lap, b = _problem(border, 19, 13, 2, "loguniform", "constant")
+    c = np.float32(0.25)
+    sx, sy = lb.dead_to_nan(sides, periodic, np.full_like(data, c), np.full_like(data, c))
+    got = wls_np.solve_exact(sides, periodic, weight, sx, sy, data, lap, b)
+    want = weighted_np.solve_exact(sides, periodic, weight / c, data, lap / c, b)
+    assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
+
+
+def test_check_codes_are_the_weighted_calls():
+    bad_arg, bad_size = capi.SC_ERR_BAD_ARG, capi.SC_ERR_BAD_SIZE
+    big = lambda cols, rows: dict(cols=cols, rows=rows, channels=1, col_stride=1, row_stride=cols, channel_stride=cols * rows)
+    layouts = [HWC, big(8192, 2), big(8193, 2), big(8194, 3), big(8195, 3), big(2, 7), big(1, 7), big(8193, 3),
+               dict(HWC, channels=5, col_stride=5, row_stride=165), dict(HWC, row_stride=98), dict(HWC, col_stride=2), dict(HWC, col_stride=0)]
+    kinds = [0, NEU, G, L, L | NEU, L | NEU | PX, L | PX, L | PX | PY, L | PX | capi.SC_POISSON_FREE_LEFT, L | PY | capi.SC_POISSON_FREE_BOTTOM,
+             G | capi.SC_POISSON_FREE_LEFT | capi.SC_POISSON_FREE_TOP]
+    seen = set()
+    for lay in layouts:
+        for kind in kinds:
+            code = capi.wls_check(kind, **lay)
+            assert code == capi.weighted_check(kind, **lay), (kind, lay)
+            seen.add(code)
+    assert seen == {capi.SC_OK, bad_arg, bad_size}
+    ok = L | NEU
+    assert capi.wls_check(ok, tol=1e-6, max_iters=50, precond_lambda=0.5, precond_smooth=2.0, **HWC) == capi.SC_OK
+    assert capi.wls_check(ok, tol=-1.0, max_iters=-3, precond_lambda=-2.0, precond_smooth=-1.0, **HWC) == capi.SC_OK      # <= 0: the defaults
+    for name in ("tol", "precond_lambda", "precond_smooth"):
+        for v in (float("nan"), float("inf"), float("-inf")):
+            assert capi.wls_check(ok, **{name: v}, **HWC) == bad_arg, (name, v)
+    lib = capi.load()
+    assert lib.sc_hip_wls_check(None, None) == bad_arg
+
+
+def test_numpy_side_refuses_what_the_library_refuses():
+    H, W = 5, 6
+    data = np.zeros((H, W, 3), np.float32)
+    w = np.ones((H, W), np.float32)
+    one = np.ones((H, W, 3), np.float32)
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        sx = one.copy()
+        sx[2, 3, 1] = bad
+        with pytest.raises(ValueError, match="smooth_x"):
+            capi.wls_arrays(data, w, sx, one, neumann=True)
+        with pytest.raises(ValueError, match="smooth_y"):
+            capi.wls_arrays(data, w, one, sx, neumann=True)
+    with pytest.raises(ValueError):
+        capi.wls_arrays(data, w, np.ones((H, W + 1), np.float32), one, neumann=True)
+    with pytest.raises(ValueError):
+        capi.wls_arrays(data, w, one, np.ones((H, W, 2), np.float32), neumann=True)
+    with pytest.raises(TypeError):
+        capi.wls_arrays(data, w, one.astype(np.float64), one, neumann=True)
+    with pytest.raises(ValueError):
+        capi.wls_arrays(data, w, None, one, neumann=True)
+    with pytest.raises(ValueError):
+        capi.wls_arrays(data, w, one, one, neumann=False)          # a Dirichlet line needs boundary
+    # what is not live may hold anything: the last column / row without a periodic axis, links along Dirichlet lines
+    for sides, periodic in (("lrtb", ""), ("", ""), ("lt", ""), ("", "x"), ("", "xy")):
+        sx, sy = lb.dead_to_nan(sides, periodic, one, one)
+        b = data if wls_np.has_dirichlet(sides, periodic) else None
+        kind, d, ww, gsx, gsy, gx, gy, lap, bb, out = capi.wls_arrays(data, w, sx, sy[:, :, 0].copy(), boundary=b, free_sides=sides, periodic=periodic)
+        assert ww.shape == gsx.shape == gsy.shape == data.shape and lap is not None and not lap.any()
+        lx, ly = capi.live_links(kind, H, W)
+        want_x, want_y = wls_np.live_links(sides, periodic, H, W)
+        assert np.array_equal(lx, want_x) and np.array_equal(ly, want_y)
+        if periodic != "xy":
+            sx[np.nonzero(~lx)[0][0], np.nonzero(~lx)[1][0], 0] = 1.0          # (still fine)
+            sx[np.nonzero(lx)[0][0], np.nonzero(lx)[1][0], 2] = np.nan
+            with pytest.raises(ValueError):
+                capi.wls_arrays(data, w, sx, sy, boundary=b, free_sides=sides, periodic=periodic)
