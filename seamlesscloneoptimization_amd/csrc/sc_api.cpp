@@ -8,7 +8,7 @@
 //   has, :1012) -> H2D of the face/body ROI only -> fused erode -> fused pre-process and
 //   iterative solve (solve_step, sc_solver.cpp) -> fused post-process into the body ROI -> D2H of the interior straight
 //   into the caller's image (replaces the reference's D2H + host splice loop, :470-483).
-#include "sc_instance.h"
+#include "sc_pcg.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -289,6 +289,7 @@ void *my_seamlessclone_api_imp_create_instance(int gpu_id)
     if (hipSetDevice(gpu_id) != hipSuccess) return nullptr;
     Instance *I = new (std::nothrow) Instance();
     if (!I) return nullptr;
+    if (!(I->pcg = new (std::nothrow) PcgState())) { delete I; return nullptr; }
     I->gpu = gpu_id;
     sc_hip_default_opts(&I->opts);
     bool ok = hipStreamCreateWithFlags(&I->stream, hipStreamNonBlocking) == hipSuccess;
@@ -353,9 +354,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     }
     if (I->fft.ev_fork) (void)hipEventDestroy(I->fft.ev_fork);
     if (I->fft.ev_built) (void)hipEventDestroy(I->fft.ev_built);
-    for (DevBuf *b : { &I->wt.u, &I->wt.r, &I->wt.p, &I->wt.q, &I->wt.w, &I->wt.e, &I->wt.s, &I->wt.dg, &I->wt.red }) dev_release(*b);
-    if (I->wt.h_red.p) (void)hipHostFree(I->wt.h_red.p);
-    for (hipEvent_t e : I->wt.ev) if (e) (void)hipEventDestroy(e);
+    pcg_release(I);
     dev_release(I->mg_fd);
     dev_release(I->rag.d_aux);
     if (I->rag.h_stage.p) (void)hipHostFree(I->rag.h_stage.p);

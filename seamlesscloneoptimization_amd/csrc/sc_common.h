@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "../../include/seamlessclone_hip_testing.h"
@@ -83,6 +84,17 @@ void launch_edit_frame_group(const EditJob *jobs, int n, int W, int H, hipStream
 struct PoissonGeo { int W, H, C; long long cs, rs, chs; };
 struct PoissonJobDev { const float *gx, *gy, *lap, *b; float *out; const float *d = nullptr; };      // d: a screened solve's data term
 struct PoissonJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; };
+// m jobs through tables of Table::MAX that go by value in the kernel arguments: fill(table, i, k) sets slot i from job k, fn(table, i0, cnt)
+// launches jobs i0 .. i0 + cnt - 1
+template <class Table, class Fill, class Fn> void for_job_tables(int m, Fill fill, Fn fn)
+{
+    for (int i0 = 0; i0 < m; i0 += Table::MAX) {
+        Table t{};
+        const int cnt = std::min(m - i0, (int)Table::MAX);
+        for (int i = 0; i < cnt; ++i) fill(t, i, i0 + i);
+        fn(t, i0, cnt);
+    }
+}
 // A call with free (reflecting) sides on some but not all of the four borders (SC_POISSON_FREE_*): per axis its kind -- 0: Dirichlet
 // lines at both ends, 1: both ends free, 2: a Dirichlet line at the low end (column or row 0) and a free high end, 3: the reverse --
 // and its number of unknowns, pixels less the axis's Dirichlet lines.  (Kind 0 on both axes is the Dirichlet call, kind 1 on both the
@@ -128,54 +140,6 @@ void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, in
 // boundary (0 where the job has none); np = poisson_mean_parts(H); one launch per 16 members
 int poisson_mean_parts(int H);
 void launch_poisson_mean(const PoissonGeo &g, const PoissonJobDev *jobs, int n, double *parts, hipStream_t s);
-// ---- the weighted solve (sc_weighted.hip: kernels; sc_weighted_api.cpp: the iteration): conjugate gradients on (A - W) u = b, W = diag(w) >= 0,
-// preconditioned by direct_jobs_solve with the constant lambda-bar.  Work planes are compact float32: only the nx x ny unknowns of
-// MixedGeo, row after row, planes `stride` floats apart (a multiple of 4: float4 access); plane p = member C + channel.
-// Tiling of the launches that walk a plane in 2-D (weights' statistics, set-up, operator): column group x of 256 columns, band y of `rows`
-// rows, one partial sum per workgroup, cg * bands <= WEIGHTED_PARTS of them per plane; of the element-wise launches (update, dot):
-// `eparts` segments of whole float4 groups.  Partial sums are doubles at parts[plane * WEIGHTED_PARTS + i]; whoever needs a total
-// adds the parts of its plane itself, in one fixed order (first wave, then shuffles): no atomics, no host round trip.
-struct WeightedJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX]; };
-constexpr int WEIGHTED_PARTS = 256;
-struct WeightedGeo { int nx, ny, ax, ay, x0, y0, cg, bands, rows, eparts, egroups; long long stride; };
-WeightedGeo weighted_geo(const MixedGeo &mg);
-inline int weighted_op_parts(const WeightedGeo &wg) { return wg.cg * wg.bands; }
-// stats[(plane * WEIGHTED_PARTS + i) * 2] = the part's sum of w over the unknowns, [.. + 1] = how many of them are negative or not finite
-void launch_weighted_stats(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, const float *const *w, int m, double *stats, hipStream_t s);
-// R = b = lap - w d (screened_rhs's order) less the neighbouring Dirichlet lines' values, Wc = w, bb = the parts of b . b
-void launch_weighted_setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, int m, float *R, float *Wc,
-                           double *bb, hipStream_t s);
-// residual = false: Q = (A - W) P, parts of P . Q;  true: Q = Q - (A - W) P in place, parts of Q . Q
-void launch_weighted_op(const WeightedGeo &wg, int planes, bool residual, const float *P, const float *Wc, float *Q, double *parts, hipStream_t s);
-// alpha = sum(rz) / sum(pq) per plane (0 when that is not finite);  U += alpha P,  R -= alpha Q,  rr = the parts of R . R
-void launch_weighted_update(const WeightedGeo &wg, int planes, float *U, float *R, const float *P, const float *Q, const double *rz, const double *pq,
-                            double *rr, hipStream_t s);
-// rz = the parts of R . Z;  rr_tot[plane] = the sum of the nrr parts of rr (for the stop rule)
-void launch_weighted_dot(const WeightedGeo &wg, int planes, const float *R, const float *Z, double *rz, const double *rr, int nrr, double *rr_tot,
-                         hipStream_t s);
-// P = Z + beta P, beta = sum(rz) / sum(rz_old) per plane (rz_old == nullptr: P = Z)
-void launch_weighted_dir(const WeightedGeo &wg, int planes, float *P, const float *Z, const double *rz, const double *rz_old, hipStream_t s);
-// the jobs' out: U at the unknowns, boundary's values on the Dirichlet lines
-void launch_weighted_out(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, int m, const float *U, hipStream_t s);
-// ---- the WLS solve (sc_wls.hip: kernels; sc_wls_api.cpp: its side of the shared iteration): the weighted solve's conjugate gradients on
-// L u = b, (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p), with per-link weights sx, sy > 0 under the call's layout.  Work planes,
-// tiling and partial sums are the weighted solve's (WeightedGeo); the update, dot, direction and output launches are its own.
-struct WlsJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX]; };
-constexpr int WLS_STATS = 4;
-// the live links of one plane: those with at least one end among the unknowns
-double wls_live_links(const WeightedGeo &wg);
-// stats[(plane * WEIGHTED_PARTS + i) * WLS_STATS + ..] = the part's sum of w | how many w are negative or not finite | the sum of its
-// live links, each counted once | how many of them are not finite or not > 0
-void launch_wls_stats(const PoissonGeo &g, const WeightedGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, double *stats, hipStream_t s);
-// R = b (the order: seamlessclone_hip.h, the WLS section), E / S = the link to the next unknown column / row (0: none), Dg = the sum of
-// the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b
-void launch_wls_setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
-// residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
-void launch_wls_op(const WeightedGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
-                   double *parts, hipStream_t s);
-void launch_wls_scale(const WeightedGeo &wg, int planes, float *U, float f, hipStream_t s);      // U *= f
 size_t mask_bbox_group_parts(const MaskJob *jobs, int n);            // ints of scratch the group scan needs (one set of extrema per workgroup)
 void launch_mask_bbox_group(const MaskJob *jobs, int n, hipStream_t s, int *parts);
 void launch_mask_erode3_group(const MaskJob *jobs, int n, hipStream_t s);

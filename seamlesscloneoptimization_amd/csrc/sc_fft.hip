@@ -1013,12 +1013,8 @@ static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo 
     const bool tiny = plane * sizeof(T) <= ((size_t)4 << 20);      // as fft_solve_t: small planes are stored transposed, no transpose launches
     // per launch of up to PoissonJobs::MAX members: fn(table, first plane, planes)
     auto chunks = [&](auto fn) {
-        for (int i0 = 0; i0 < m; i0 += PoissonJobs::MAX) {
-            PoissonJobs t{};
-            const int cnt = std::min(m - i0, (int)PoissonJobs::MAX);
-            for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
-            fn(t, (size_t)g.C * i0, g.C * cnt);
-        }
+        for_job_tables<PoissonJobs>(m, [&](PoissonJobs &t, int i, int k) { t.j[i] = jobs[k]; },
+                                    [&](const PoissonJobs &t, int i0, int cnt) { fn(t, (size_t)g.C * i0, g.C * cnt); });
     };
     const PoissonJobs none{};
     const double *const no_parts = nullptr;

@@ -78,17 +78,7 @@ struct FftState {
     bool forked = false;                   // this solve has already put the second stream behind the main one (one fork per solve: both directions' tables and the eigenvalue tables ride on it)
 };
 
-// the weighted solve (sc_weighted_api.cpp): conjugate-gradient work planes [planes][WeightedGeo::stride] of float32 (q holds A p, then the
-// preconditioned residual z), the double partial sums, and the stop rule's mailbox: the per-plane ||r||^2 of iteration k goes to slot
-// k % RING of the pinned block with event k % RING behind it, and the host reads iteration k - LAG before it enqueues iteration k
-struct WeightedState {
-    enum { LAG = SC_WEIGHTED_POLL, RING = SC_WEIGHTED_POLL + 1 };
-    DevBuf u, r, p, q, w;
-    DevBuf e, s, dg;                       // the WLS solve's coefficient planes (sc_wls.hip): links east, links south, the diagonal
-    DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (WEIGHTED_PARTS per plane each) | ||r||^2 per plane
-    DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane
-    hipEvent_t ev[RING]{};
-};
+struct PcgState;      // the conjugate-gradient families' work planes and mailbox (sc_pcg.h)
 
 struct MGLevel {
     Field U, F, T;   // correction, RHS, scratch (residual field); level 0 aliases the instance fields
@@ -238,7 +228,7 @@ struct Instance {
     RagState rag;
     DstState dst;
     FftState fft;
-    WeightedState wt;
+    PcgState *pcg = nullptr;     // made with the instance (sc_api.cpp: creation fails without it), freed by pcg_release: never null in a call
     bool fft_lds_float = false, fft_lds_double = false;   // this instance's device has the FFT kernels opted in to > 64 KB of LDS (sc_fft.hip)
     // reductions / mailboxes
     DevBuf d_rects, h_rects;     // bounding boxes of a group of clones (sc_hip_run_device_batch): device, pinned
@@ -441,38 +431,6 @@ template <class Chunk> int run_chunks(Instance *I, int C, int *const *rcs, int n
     }
     return worst;
 }
-// The preconditioned conjugate gradients that the weighted and the WLS call share (pcg_run, sc_weighted_api.cpp), and what a family tells
-// the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat` doubles per part; the
-// driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets SC_ERR_BAD_ARG and
-// leaves; NULL: it stays, its arrays move to the front and its sums count) -> precond_constant -> setup -> scale_start on u0 -> apply,
-// once in its residual form and then once per iteration.  Everything else -- the preconditioner through direct_jobs_solve, the update, dot and direction launches,
-// the stop rule's mailbox, the output launch -- is the driver's own and the same for both families.
-struct PcgOperator {
-    const int nstat;                       // doubles per part of the statistics launch
-    std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
-    explicit PcgOperator(int nstat_) : nstat(nstat_) {}
-    virtual ~PcgOperator() = default;
-    virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
-    virtual void stats(const PoissonGeo &g, const WeightedGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
-    // st: job k's statistics, its C planes' WEIGHTED_PARTS * nstat doubles each, of which the first `parts` parts are set
-    virtual const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) = 0;
-    virtual float precond_constant(const PoissonGeo &g, const WeightedGeo &wg, int mv) = 0;      // lam: the driver's preconditioner is A - lam
-    virtual int setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, int mv, float *R, double *bb) = 0;      // R = b, the coefficient planes, bb = the parts of b . b
-    // the start u0 = (A - lam)^-1 b where the family's preconditioner is a multiple of A - lam: its one-off factor (a constant factor
-    // on the preconditioner changes no later iterate, so the loop never applies it).  The default: none.
-    virtual void scale_start(const WeightedGeo &wg, int planes, float *U, hipStream_t s) {}
-    virtual void apply(const WeightedGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) = 0;
-    // the sum of field f of one plane's statistics over its first `parts` parts
-    double stat_sum(const double *plane, int parts, int f) const
-    {
-        double sum = 0.0;
-        for (int i = 0; i < parts; ++i) sum += plane[(size_t)nstat * i + f];
-        return sum;
-    }
-};
-struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
-// The validated jobs of a call through chunks (run_chunks) and sc_run_info.  Returns the worst code, the jobs' own refusals included.
-int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed);
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
 int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);

@@ -1,0 +1,105 @@
+// sc_pcg.h -- the preconditioned conjugate gradients that the weighted and the WLS call share: the work planes' geometry and tiling, the
+// instance's state, what a family tells the iteration about its operator (PcgOperator), the driver (pcg_run, sc_pcg.cpp) and the
+// launches (sc_pcg.hip: the shared ones; sc_weighted.hip, sc_wls.hip: a family's statistics, set-up and operator).
+//     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
+// Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
+// float4 access); plane p = member C + channel.  Tiling of the launches that walk a plane in 2-D (statistics, set-up, operator): column
+// group x of 256 columns, band y of `rows` rows, one partial sum per workgroup, cg * bands <= PCG_PARTS of them per plane; of the
+// element-wise launches (update, dot, direction, scale): `eparts` segments of whole float4 groups.  Partial sums are doubles at
+// parts[plane * PCG_PARTS + i]; whoever needs a total adds the parts of its plane itself, in one fixed order (first wave, then
+// shuffles): no atomics, no host round trip.
+#pragma once
+#include "sc_instance.h"
+
+namespace sc {
+
+constexpr int PCG_PARTS = 256;
+struct PcgGeo { int nx, ny, ax, ay, x0, y0, cg, bands, rows, eparts, egroups; long long stride; };
+PcgGeo pcg_geo(const MixedGeo &mg);
+inline int pcg_op_parts(const PcgGeo &wg) { return wg.cg * wg.bands; }
+
+// The instance's state (Instance::pcg, made with the instance): work planes [planes][PcgGeo::stride] of float32 (q holds L p, then the
+// preconditioned residual z), the double partial sums, and the stop rule's mailbox: the per-plane ||r||^2 of iteration k goes to slot
+// k % RING of the pinned block with event k % RING behind it, and the host reads iteration k - LAG before it enqueues iteration k
+struct PcgState {
+    enum { LAG = SC_WEIGHTED_POLL, RING = SC_WEIGHTED_POLL + 1 };
+    DevBuf u, r, p, q;
+    DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
+    DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
+    DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane
+    DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane
+    hipEvent_t ev[RING]{};
+};
+void pcg_release(Instance *I);             // frees Instance::pcg and all it holds
+
+// What a family tells the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat`
+// doubles per part; the driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets
+// SC_ERR_BAD_ARG and leaves; NULL: it stays, its arrays move to the front and its sums count) -> precond_constant -> setup ->
+// scale_start on u0 -> apply, once in its residual form and then once per iteration.  Everything else -- the preconditioner through
+// direct_jobs_solve, the update, dot and direction launches, the stop rule's mailbox, the output launch -- is the driver's own.
+struct PcgOperator {
+    const int nstat;                       // doubles per part of the statistics launch
+    std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
+    explicit PcgOperator(int nstat_) : nstat(nstat_) {}
+    virtual ~PcgOperator() = default;
+    virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
+    virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
+    // st: job k's statistics, its C planes' PCG_PARTS * nstat doubles each, of which the first `parts` parts are set
+    virtual const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) = 0;
+    virtual float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) = 0;      // lam: the driver's preconditioner is A - lam
+    virtual int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) = 0;      // R = b, the coefficient planes, bb = the parts of b . b
+    // the start u0 = (A - lam)^-1 b where the family's preconditioner is a multiple of A - lam: its one-off factor (a constant factor
+    // on the preconditioner changes no later iterate, so the loop never applies it).  The default: none.
+    virtual void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) {}
+    virtual void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) = 0;
+    // the sum of field f of one plane's statistics over its first `parts` parts
+    double stat_sum(const double *plane, int parts, int f) const
+    {
+        double sum = 0.0;
+        for (int i = 0; i < parts; ++i) sum += plane[(size_t)nstat * i + f];
+        return sum;
+    }
+};
+struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
+// The validated jobs of a call through chunks (run_chunks) and sc_run_info.  Returns the worst code, the jobs' own refusals included.
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed);
+
+// ---- the shared launches (sc_pcg.hip)
+// alpha = sum(rz) / sum(pq) per plane (0 when that is not finite);  U += alpha P,  R -= alpha Q,  rr = the parts of R . R
+void launch_pcg_update(const PcgGeo &wg, int planes, float *U, float *R, const float *P, const float *Q, const double *rz, const double *pq, double *rr, hipStream_t s);
+// rz = the parts of R . Z;  rr_tot[plane] = the sum of the nrr parts of rr (for the stop rule)
+void launch_pcg_dot(const PcgGeo &wg, int planes, const float *R, const float *Z, double *rz, const double *rr, int nrr, double *rr_tot, hipStream_t s);
+// P = Z + beta P, beta = sum(rz) / sum(rz_old) per plane (rz_old == nullptr: P = Z)
+void launch_pcg_dir(const PcgGeo &wg, int planes, float *P, const float *Z, const double *rz, const double *rz_old, hipStream_t s);
+void launch_pcg_scale(const PcgGeo &wg, int planes, float *U, float f, hipStream_t s);      // U *= f
+// the jobs' out: U at the unknowns, boundary's values on the Dirichlet lines
+void launch_pcg_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, int m, const float *U, hipStream_t s);
+
+// ---- the weighted family (sc_weighted.hip): L = A - W, W = diag(w) >= 0
+struct WeightedJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX]; };
+// stats[(plane * PCG_PARTS + i) * 2] = the part's sum of w over the unknowns, [.. + 1] = how many of them are negative or not finite
+void launch_weighted_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, int m, double *stats, hipStream_t s);
+// R = b = lap - w d (screened_rhs's order) less the neighbouring Dirichlet lines' values, Wc = w, bb = the parts of b . b
+void launch_weighted_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, int m, float *R, float *Wc,
+                           double *bb, hipStream_t s);
+// residual = false: Q = (A - W) P, parts of P . Q;  true: Q = Q - (A - W) P in place, parts of Q . Q
+void launch_weighted_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *Wc, float *Q, double *parts, hipStream_t s);
+
+// ---- the WLS family (sc_wls.hip): (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p), per-link weights sx, sy > 0 under the call's layout
+struct WlsJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX]; };
+constexpr int WLS_STATS = 4;
+// the live links of one plane: those with at least one end among the unknowns
+double wls_live_links(const PcgGeo &wg);
+// stats[(plane * PCG_PARTS + i) * WLS_STATS + ..] = the part's sum of w | how many w are negative or not finite | the sum of its
+// live links, each counted once | how many of them are not finite or not > 0
+void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                      const float *const *sy, int m, double *stats, hipStream_t s);
+// R = b (the order: seamlessclone_hip.h, the WLS section), E / S = the link to the next unknown column / row (0: none), Dg = the sum of
+// the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b
+void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                      const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
+// residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
+void launch_wls_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
+                   double *parts, hipStream_t s);
+
+} // namespace sc

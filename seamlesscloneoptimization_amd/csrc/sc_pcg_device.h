@@ -1,7 +1,8 @@
-// sc_pcg_device.h -- what the kernels of the two conjugate-gradient families share (sc_weighted.hip, sc_wls.hip): the workgroup's size, its
-// sum in one fixed order, and the segment of a plane that one workgroup of an element-wise launch owns (sc_common.h, WeightedGeo).
+// sc_pcg_device.h -- what the kernels of the conjugate-gradient families share (sc_pcg.hip, sc_weighted.hip, sc_wls.hip): the workgroup's
+// size and its sum in one fixed order, and one walk of each kind over the work planes (sc_pcg.h, PcgGeo) -- the element-wise walk of a
+// segment's float4 groups, the band of a statistics or set-up launch, and the operator's walk with a family's coefficients as a policy.
 #pragma once
-#include "sc_common.h"
+#include "sc_pcg.h"
 #include "sc_wave.h"
 #include <algorithm>
 
@@ -18,14 +19,6 @@ __device__ __forceinline__ double block_sum(double v, double *ws)
     return (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 
-// the float4 groups [g0, g1) of a plane of n floats that segment `part` owns
-__device__ __forceinline__ void segment(const WeightedGeo &wg, int part, int &g0, int &g1)
-{
-    const int per = (wg.egroups + wg.eparts - 1) / wg.eparts;
-    g0 = part * per;
-    g1 = min(g0 + per, wg.egroups);
-}
-
 // a * b rounded to float32 on its own: never one half of a fused multiply-add, whatever the translation unit's contraction setting
 // (the product is opaque to the optimiser, as in screened_rhs)
 __device__ __forceinline__ float rounded_product(float a, float b)
@@ -35,6 +28,97 @@ __device__ __forceinline__ float rounded_product(float a, float b)
     asm volatile("" : "+v"(t));
 #endif
     return t;
+}
+
+// The element-wise walk (grid: eparts x planes): segment blockIdx.x of plane blockIdx.y is `per` float4 groups, a lane takes every
+// WL-th of them; group(i) for a whole group at float offset i, tail(e) for each float of the plane's last, partial group.
+template <class Group, class Tail>
+__device__ __forceinline__ void pcg_elements(const PcgGeo &wg, Group group, Tail tail)
+{
+    const int n = wg.nx * wg.ny, per = (wg.egroups + wg.eparts - 1) / wg.eparts;
+    const int g0 = (int)blockIdx.x * per, g1 = min(g0 + per, wg.egroups);
+    const size_t base = (size_t)blockIdx.y * wg.stride;
+    for (int gi = g0 + (int)threadIdx.x; gi < g1; gi += WL) {
+        if (gi * 4 + 3 < n) group(base + (size_t)gi * 4);
+        else
+            for (int k = gi * 4; k < n; ++k) tail(base + k);
+    }
+}
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+// a group's share of a lane's double sum, in the one order every such sum is added
+__device__ __forceinline__ double dot4(float4 a, float4 b)
+{
+    return ((double)a.x * b.x + (double)a.y * b.y) + ((double)a.z * b.z + (double)a.w * b.w);
+}
+
+// The band of a statistics or set-up launch (grid: cg x bands x planes): plane p = member C + channel c, this lane's column x of the
+// unknowns (one only where x < nx), rows [y0, y1); pixel(g, X, Y): the offset of pixel (X, Y) = (x0 + x, y0 + y) of the channel under
+// the call's layout.  (The kernels keep their own row loop and work-plane index: behind a helper that takes the geometry they cost
+// scalar registers.)
+struct PcgBand {
+    int p, member, c, x, y0, y1;
+    __device__ __forceinline__ PcgBand(const PoissonGeo &g, const PcgGeo &wg)
+    {
+        p = (int)blockIdx.z; member = p / g.C; c = p - member * g.C; x = (int)blockIdx.x * WL + (int)threadIdx.x;
+        y0 = (int)blockIdx.y * wg.rows; y1 = min(y0 + wg.rows, wg.ny);
+    }
+    __device__ __forceinline__ long long pixel(const PoissonGeo &g, int X, int Y) const { return (long long)X * g.cs + (long long)Y * g.rs + (long long)c * g.chs; }
+};
+// the workgroup's sum of v into field f of its part: parts[(plane * PCG_PARTS + band * cg + column group) * per + f]
+__device__ __forceinline__ void part_store(double v, double *ws, const PcgGeo &wg, double *__restrict__ parts, int per = 1, int f = 0)
+{
+    v = block_sum(v, ws);
+    if (threadIdx.x == 0) parts[((size_t)blockIdx.z * PCG_PARTS + blockIdx.y * wg.cg + blockIdx.x) * per + f] = v;
+}
+
+// The operator's launch (grid: cg x bands x planes), one kernel for every family.  RES false: Q = L P and the parts of P . Q;  true:
+// Q -= L P and the parts of Q . Q.  A lane owns one column of its band, keeps the row above, its own and the row below in registers, and
+// reads the left and right neighbours from the cache lines its wave loads anyway -- no LDS, no barrier inside the walk.  A neighbour that
+// does not exist (beyond a free end or a Dirichlet line) has index -1 and the value 0.  The family's coefficients are the policy K, built
+// from the launch's coefficient planes `coef` (the kernel has no others to read): start(wg, base, x, ya) once per lane (base: the
+// plane's first element, ya: the row above the band, -1: none), then per row value(wg, x, xl, y, ro, i, l, r, up, dn, cur) = (L P) at element i = base + ro + x (ro = y nx; xl: the left column, -1: none), which loads the
+// row's coefficients and rolls whatever the policy carries from row to row.  (The walk is the kernel itself and not a function under
+// two kernels: inlined from a function it cost the WLS instantiation two scalar registers.)
+template <bool RES, class K, class... C>
+__global__ __launch_bounds__(WL) void k_pcg_op(PcgGeo wg, const float *__restrict__ P, float *__restrict__ Q, double *__restrict__ parts,
+                                                const C *__restrict__... coef)
+{
+    __shared__ double ws[4];
+    K k{ coef... };
+    const int x = (int)blockIdx.x * WL + (int)threadIdx.x, nx = wg.nx, ny = wg.ny;
+    const int y0 = (int)blockIdx.y * wg.rows, y1 = min(y0 + wg.rows, ny);
+    const size_t base = (size_t)blockIdx.z * wg.stride;
+    const float *__restrict__ pl = P + base;
+    double s = 0.0;
+    if (x < nx) {
+        const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
+        const int xl = x > 0 ? x - 1 : px ? nx - 1 : -1, xr = x < nx - 1 ? x + 1 : px ? 0 : -1;
+        auto row_above = [&](int y) { return y > 0 ? y - 1 : py ? ny - 1 : -1; };
+        auto row_below = [&](int y) { return y < ny - 1 ? y + 1 : py ? 0 : -1; };
+        const int ya = row_above(y0);
+        float up = ya >= 0 ? pl[(size_t)ya * nx + x] : 0.f, cur = pl[(size_t)y0 * nx + x];
+        k.start(wg, base, x, ya);
+        for (int y = y0; y < y1; ++y) {
+            const int yb = row_below(y);
+            const float dn = yb >= 0 ? pl[(size_t)yb * nx + x] : 0.f;
+            const size_t ro = (size_t)y * nx;
+            const float l = xl >= 0 ? pl[ro + xl] : 0.f, r = xr >= 0 ? pl[ro + xr] : 0.f;
+            const size_t i = base + ro + x;
+            const float v = k.value(wg, x, xl, y, ro, i, l, r, up, dn, cur);
+            if (RES) {
+                const float q = Q[i] - v;
+                Q[i] = q;
+                s += (double)q * (double)q;
+            } else {
+                Q[i] = v;
+                s += (double)cur * (double)v;
+            }
+            up = cur;
+            cur = dn;
+        }
+    }
+    part_store(s, ws, wg, parts);
 }
 
 } // namespace sc

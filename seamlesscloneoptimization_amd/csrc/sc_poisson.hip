@@ -167,20 +167,9 @@ void launch_poisson_pre(const PoissonGeo &g, bool lap, const PoissonJobDev &j, F
     });
 }
 
-template <typename Fn>
-static void ps_chunks(const PoissonJobDev *jobs, int n, Fn fn)
-{
-    for (int i0 = 0; i0 < n; i0 += PoissonJobs::MAX) {
-        PoissonJobs t{};
-        const int cnt = std::min(n - i0, (int)PoissonJobs::MAX);
-        for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
-        fn(t, i0, cnt);
-    }
-}
-
 void launch_poisson_pre_group(const PoissonGeo &g, bool lap, const PoissonJobDev *jobs, int n, Field U0, Field F, hipStream_t s, float lam)
 {
-    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+    for_job_tables<PoissonJobs>(n, [&](PoissonJobs &t, int i, int k) { t.j[i] = jobs[k]; }, [&](const PoissonJobs &t, int i0, int cnt) {
         const dim3 grid = ps_grid(g, (g.W + 3) & ~3, cnt);
         Field u = U0, f = F;      // this launch's first member owns channel C i0
         u.p = U0.p + (size_t)g.C * i0 * U0.plane;
@@ -196,7 +185,7 @@ int poisson_mean_parts(int H) { return std::min(H, 256); }
 void launch_poisson_mean(const PoissonGeo &g, const PoissonJobDev *jobs, int n, double *parts, hipStream_t s)
 {
     const int np = poisson_mean_parts(g.H);
-    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+    for_job_tables<PoissonJobs>(n, [&](PoissonJobs &t, int i, int k) { t.j[i] = jobs[k]; }, [&](const PoissonJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_poisson_mean, dim3((unsigned)np, (unsigned)g.C, (unsigned)cnt), dim3(PS_LANES), 0, s, g, t,
                            parts + (size_t)g.C * i0 * np);
     });
@@ -211,7 +200,7 @@ void launch_poisson_out(const PoissonGeo &g, const PoissonJobDev &j, Field U, hi
 
 void launch_poisson_out_group(const PoissonGeo &g, const PoissonJobDev *jobs, int n, Field U, hipStream_t s)
 {
-    ps_chunks(jobs, n, [&](const PoissonJobs &t, int i0, int cnt) {
+    for_job_tables<PoissonJobs>(n, [&](PoissonJobs &t, int i, int k) { t.j[i] = jobs[k]; }, [&](const PoissonJobs &t, int i0, int cnt) {
         const dim3 grid = ps_grid(g, g.W, cnt);
         Field u = U;
         u.p = U.p + (size_t)g.C * i0 * U.plane;

@@ -3,15 +3,15 @@
 //     minimise sum w (u - d)^2 + sum_x-links sx (u(x+1, y) - u(x, y) - gx)^2 + sum_y-links sy (u(x, y+1) - u(x, y) - gy)^2,
 //     i.e.   L u = div(s g) - W d,     (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p),
 // under every border kind of sc_hip_weighted.  The call is the weighted call with another operator: the same front end (float_intake,
-// float_stage with FLOAT_SMOOTH), the same iteration (pcg_run, sc_weighted_api.cpp), this file's WlsOperator in place of the weighted
+// float_stage with FLOAT_SMOOTH), the same iteration (pcg_run, sc_pcg.cpp), this file's WlsOperator in place of the weighted
 // one:
 //   statistics  per plane the sums of w and of the live links and how many of each are invalid (k_wls_stats); a job with an invalid
 //               weight or link, or -- without any Dirichlet line -- with a channel of zero weight, gets SC_ERR_BAD_ARG and leaves.
 //   constants   s-bar = precond_smooth, or the mean live link of the chunk's remaining jobs; w-bar = precond_lambda, or their mean
 //               weight.  The preconditioner is M = s-bar (A - w-bar / s-bar): the direct solve with lam = w-bar / s-bar, and the
 //               factor 1 / s-bar once, on u0.
-//   set-up      b and the planes E, S, Dg (k_wls_setup);   operator   k_wls_op.
-#include "sc_instance.h"
+//   set-up      b and the planes E, S, Dg (k_wls_setup);   operator   k_pcg_op with WlsCoef.
+#include "sc_pcg.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -62,7 +62,7 @@ struct WlsOperator final : PcgOperator {
         kept = 0;
         wsum = ssum = 0.0;
     }
-    void stats(const PoissonGeo &g, const WeightedGeo &wg, int m, double *d_stats, hipStream_t s) override
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {
         launch_wls_stats(g, wg, dj.data(), dw.data(), dsx.data(), dsy.data(), m, d_stats, s);
     }
@@ -71,7 +71,7 @@ struct WlsOperator final : PcgOperator {
         double job_w = 0.0, job_s = 0.0;
         bool bad_w = false, bad_s = false, empty = false;
         for (int c = 0; c < g.C; ++c) {
-            const double *plane = st + (size_t)c * WEIGHTED_PARTS * WLS_STATS;
+            const double *plane = st + (size_t)c * PCG_PARTS * WLS_STATS;
             const double sum = stat_sum(plane, parts, 0);
             bad_w = bad_w || stat_sum(plane, parts, 1) != 0.0;
             bad_s = bad_s || stat_sum(plane, parts, 3) != 0.0;
@@ -89,7 +89,7 @@ struct WlsOperator final : PcgOperator {
         ssum += job_s;
         return nullptr;
     }
-    float precond_constant(const PoissonGeo &g, const WeightedGeo &wg, int mv) override
+    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
     {
         const double planes = (double)(g.C * mv);
         const double wbar = plam > 0.f ? (double)plam : wsum / ((double)wg.nx * (double)wg.ny * planes);
@@ -98,10 +98,10 @@ struct WlsOperator final : PcgOperator {
         u0_scale = (float)(1.0 / sbar);
         return (float)(wbar / sbar);
     }
-    void scale_start(const WeightedGeo &wg, int planes, float *U, hipStream_t s) override { launch_wls_scale(wg, planes, U, u0_scale, s); }
-    int setup(const PoissonGeo &g, const WeightedGeo &wg, bool lap, int mv, float *R, double *bb) override
+    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override { launch_pcg_scale(wg, planes, U, u0_scale, s); }
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
     {
-        WeightedState &S = I->wt;
+        PcgState &S = *I->pcg;
         for (DevBuf *b : { &S.e, &S.s, &S.dg }) {
             const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
             if (rc) return rc;
@@ -110,9 +110,9 @@ struct WlsOperator final : PcgOperator {
                          I->stream);
         return SC_OK;
     }
-    void apply(const WeightedGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
+    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
     {
-        const WeightedState &S = I->wt;
+        const PcgState &S = *I->pcg;
         launch_wls_op(wg, planes, residual, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.dg.p, Q, parts, s);
     }
 };

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import pcg_np
 import periodic_np
 import weighted_np
 
@@ -162,30 +163,7 @@ def pcg_f32(sides, periodic, weight, sx, sy, data, lap, boundary=None, tol=1e-5,
     wbar = mean_weight(sides, periodic, weight) if precond_lambda is None else float(np.float32(precond_lambda))
     lam, scale = np.float32(wbar / sbar), np.float32(1.0 / sbar)
     b = folded_rhs(sides, periodic, weight, sx, sy, data, lap, boundary, np.float32)
-    dot = lambda a, c: np.einsum("yxc,yxc->c", a.astype(np.float64), c.astype(np.float64))
-    bb = dot(b, b)
-    rel = lambda r: float(np.sqrt(np.max(np.where(bb > 0, dot(r, r) / np.where(bb > 0, bb, 1.0), 0.0))))
-    M = lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C))
-    u = M(b) * scale
-    r = b - block_operator(links, dg, u)
-    assert r.dtype == np.float32
-    z = M(r)
-    p = z.copy()
-    rho = dot(r, z)
-    it = 0
-    while rel(r) > tol and it < max_iters:
-        q = block_operator(links, dg, p)
-        pq = dot(p, q)
-        alpha = np.where(pq != 0, rho / np.where(pq != 0, pq, 1.0), 0.0).astype(np.float32)
-        u = u + alpha * p
-        r = r - alpha * q
-        z = M(r)
-        rho_new = dot(r, z)
-        beta = np.where(rho != 0, rho_new / np.where(rho != 0, rho, 1.0), 0.0).astype(np.float32)
-        p = z + beta * p
-        rho = rho_new
-        it += 1
-        assert u.dtype == np.float32 and p.dtype == np.float32
     out = _hwc(np.asarray(boundary, np.float32)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C), np.float32)
-    out[blk] = u
-    return out.reshape(shape), it, rel(r)
+    out, it, rel = pcg_np.pcg_f32(b, lambda p: block_operator(links, dg, p), lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C)),
+                                  scale, tol, max_iters, out, blk)
+    return out.reshape(shape), it, rel

@@ -29,6 +29,7 @@ for src in args:
 names = subprocess.run(["c++filt"], input="\n".join(c["name"] for c in lines), capture_output=True, text=True, check=True).stdout.splitlines()
 out = []
 for c, n in zip(lines, names):
+    n = n.replace("(anonymous namespace)::", "")
     m = re.match(r"(?:void )?(?:sc::)?(\w+)<(.*)>\(", n)
     if m and m.group(1) in NAMES:
         vals = [{"false": "0", "true": "1"}.get(v.strip(), v.strip()) for v in m.group(2).split(",")]

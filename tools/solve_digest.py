@@ -5,6 +5,13 @@ their outputs are the same line for line.  Every group runs GUIDANCE and LAPLACI
 SC_FLAG_FFT_FP64 transforms, the Neumann problem with and without boundary.
 
     python tools/solve_digest.py [--root DIR] > profiles/solve_digest_<build>.txt      (--root: another checkout's built package)
+
+--pcg: instead, the conjugate-gradient families (weighted, WLS), "<case name> <SHA-256 of out> <info().sweeps>", at the smallest shapes
+where their shared walks can go wrong: every pair of axis kinds, a periodic axis of length 2, one unknown, a plane that is no multiple
+of a float4 group, two column groups, several bands and element-wise segments, two job tables, a refused job in a batch, a zero-weight
+plane, a budget that ends the solve.
+
+    python tools/solve_digest.py --pcg [--root DIR] > profiles/pcg_digest_<build>.txt
 """
 import argparse
 import hashlib
@@ -16,7 +23,9 @@ import numpy as np
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.abspath(ap.parse_args().root))
+ap.add_argument("--pcg", action="store_true")
+ARGS = ap.parse_args()
+sys.path.insert(0, os.path.abspath(ARGS.root))
 
 from seamlesscloneoptimization_amd import capi  # noqa: E402
 
@@ -99,9 +108,101 @@ def batch(inst, name, sides, W, H, m):
         emit("%s [%s] x%d %s" % (name, sides, m, tag[:-2]), b"".join(got[k, outs[k], :n].tobytes() for k in range(m)))
 
 
+# ---- the conjugate-gradient families (--pcg)
+AXES = [("", ""), ("01", ""), ("1", ""), ("0", ""), ("", "p")]      # axis kind (MixedGeo) -> (free ends: 0 low, 1 high; periodic)
+FIELDS = ("gx", "gy", "lap", "data", "weight", "sx", "sy", "boundary")
+FORMS = [(f, p, l, "%s %s %s" % (f, p, "lap" if l else "gxy")) for f in ("weighted", "wls") for p in ("f32", "f64") for l in (False, True)]
+
+
+def pcg_arrays(name, k, H, W, C):
+    """one problem's float32 H x W x C arrays by FIELDS' names: weights log-uniform in [1e-2, 1], links in [0.05, 1]"""
+    rng = np.random.default_rng([zlib.crc32(name.encode()), k])
+    u = lambda lo, hi: rng.uniform(lo, hi, (H, W, C)).astype(np.float32)       # noqa: E731
+    e = lambda lo: np.exp(u(np.log(lo), 0)).astype(np.float32)                 # noqa: E731
+    return dict(gx=u(-2, 2), gy=u(-2, 2), lap=u(-4, 4), data=u(-50, 300), weight=e(1e-2), sx=e(0.05), sy=e(0.05), boundary=u(-100, 400))
+
+
+def pcg_emit(inst, name, sides, periodic, tag, out_bytes, refused=False):
+    print("%s [%s|%s] %s" % (name, sides or "-", periodic or "-", tag), hashlib.sha256(out_bytes).hexdigest(), "refused" if refused else inst.info().sweeps, flush=True)
+
+
+def pcg_single(inst, name, sides, periodic, W, H, C, zero_weight_plane=False, **kw):
+    """host calls of both families, both forms, both precisions"""
+    for family, prec, lap, tag in FORMS:
+        configure(inst, capi.SC_FLAG_FFT_FP64 if prec == "f64" else 0)
+        a = pcg_arrays(name, 0, H, W, C)
+        if zero_weight_plane:
+            a["weight"][:, :, 0] = 0.0
+        kw.update(dict(gx=None, gy=None, lap=a["lap"]) if lap else dict(gx=a["gx"], gy=a["gy"], lap=None))
+        links = (a["sx"], a["sy"]) if family == "wls" else ()
+        try:
+            out, refused = getattr(inst, family)(a["data"], a["weight"], *links, boundary=a["boundary"], free_sides=sides, periodic=periodic, **kw), False
+        except capi.SeamlessCloneError as e:                 # (a shape the library refuses: the refusal is the result)
+            out, refused = np.frombuffer(str(e).encode(), np.uint8), True
+        pcg_emit(inst, name, sides, periodic, tag, np.ascontiguousarray(out).tobytes(), refused)
+
+
+def pcg_batch(inst, name, sides, periodic, W, H, C, m, refuse=None):
+    """m jobs in one device call; refuse: the job whose first weight is negative (its statistics refuse it: the survivors' arrays move
+    to the front).  The digest covers every job's out slot and the jobs' codes."""
+    n, slot, nf = W * H * C, (W * H * C + 63) // 64 * 64, len(FIELDS)
+    layout = capi.PoissonLayout(W, H, C, C, W * C, 1)
+    for family, prec, lap, tag in FORMS:
+        configure(inst, capi.SC_FLAG_FFT_FP64 if prec == "f64" else 0)
+        host = np.zeros((m, nf + 1, slot), np.float32)               # FIELDS, out
+        for k in range(m):
+            a = pcg_arrays(name, k, H, W, C)
+            if k == refuse:
+                a["weight"][0, 0, 0] = -1.0
+            host[k, :nf, :n] = [a[f].reshape(-1) for f in FIELDS]
+        dev = inst.malloc(host.nbytes)
+        try:
+            inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, host.ctypes.data, host.nbytes))
+            at = lambda k, f: dev + 4 * slot * ((nf + 1) * k + (FIELDS + ("out",)).index(f))      # noqa: E731
+            jobs = capi.Instance.make_weighted_jobs(m) if family == "weighted" else capi.Instance.make_wls_jobs(m)
+            for k, j in enumerate(jobs):
+                j.gx, j.gy, j.lap = (None, None, at(k, "lap")) if lap else (at(k, "gx"), at(k, "gy"), None)
+                j.data, j.weight, j.boundary, j.out = at(k, "data"), at(k, "weight"), at(k, "boundary"), at(k, "out")
+                if family == "wls":
+                    j.smooth_x, j.smooth_y = at(k, "sx"), at(k, "sy")
+            kind = (capi.SC_POISSON_LAPLACIAN if lap else capi.SC_POISSON_GUIDANCE) | capi.free_side_bits(sides) | capi.periodic_bits(periodic)
+            if family == "weighted":
+                inst.weighted_device(capi.WeightedParams(kind, 0.0, 0, 0.0), layout, jobs, allow_job_errors=True)
+            else:
+                inst.wls_device(capi.WlsParams(kind, 0.0, 0, 0.0, 0.0), layout, jobs, allow_job_errors=True)
+            got = inst.from_device(dev, host.shape, np.float32)
+        finally:
+            inst.free(dev)
+        pcg_emit(inst, name, sides, periodic, "x%d %s" % (m, tag), got[:, nf, :n].tobytes() + np.array([j.rc for j in jobs], np.int32).tobytes())
+
+
+def pcg_main(inst):
+    for fx, px in AXES:                                              # every pair of axis kinds
+        for fy, py in AXES:
+            sides = fx.replace("0", "l").replace("1", "r") + fy.replace("0", "t").replace("1", "b")
+            pcg_single(inst, "axes 37x29 C3", sides, px.replace("p", "x") + py.replace("p", "y"), 37, 29, 3)
+    pcg_single(inst, "wrap 2x29 C3", "", "x", 2, 29, 3)              # a periodic axis of length 2
+    pcg_single(inst, "wrap 37x2 C3", "lr", "y", 37, 2, 3)
+    pcg_single(inst, "one unknown 3x3 C3", "", "", 3, 3, 3)
+    for sides, periodic in (("", ""), ("lrtb", ""), ("r", "y")):     # n % 4 != 0; the frame's plane: 15 unknowns
+        pcg_single(inst, "tail 7x5 C1", sides, periodic, 7, 5, 1)
+    for sides, periodic in (("", ""), ("lrtb", ""), ("lt", ""), ("", "x"), ("", "xy")):
+        pcg_single(inst, "column groups 300x20 C3", sides, periodic, 300, 20, 3)
+        pcg_single(inst, "bands 40x130 C3", sides, periodic, 40, 130, 3)
+    for sides, periodic in (("", ""), ("lrtb", "")):
+        pcg_batch(inst, "tables 33x31 C1", sides, periodic, 33, 31, 1, 17)
+        pcg_batch(inst, "refused 21x19 C3", sides, periodic, 21, 19, 3, 4, refuse=1)
+    pcg_single(inst, "zero-weight plane 37x29 C3", "", "", 37, 29, 3, zero_weight_plane=True)
+    pcg_single(inst, "zero-weight plane 37x29 C3", "t", "x", 37, 29, 3, zero_weight_plane=True)
+    for sides, periodic in (("", ""), ("lrtb", "")):
+        pcg_single(inst, "budget 40x130 C3", sides, periodic, 40, 130, 3, max_iters=3, allow_not_converged=True)
+
+
 def main():
     inst = capi.Instance(0)
     try:
+        if ARGS.pcg:
+            return pcg_main(inst)
         for f in range(16):                                          # every border combination; all-Dirichlet is the untouched control
             single(inst, "borders 37x29 C3 hwc", "".join(s for s, bit in zip("lrtb", (1, 2, 4, 8)) if f & bit), 37, 29, 3, False)
         for W, H in ((2, 2), (2, 41), (41, 2), (300, 200), (723, 722)):      # degenerate and mixed-radix lengths

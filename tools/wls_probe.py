@@ -11,8 +11,8 @@
            (tools/weighted_probe.py's): per kind of links (log-uniform over two decades; edges: tests/wls_bounds.py's checkerboard) a
            default call's iterations and time, and calls of 4 and of 12 iterations (tol far below the float32 floor, so the budget ends
            them), their difference / 8 = the time per iteration; beside them the same three figures of sc_hip_weighted on the same
-           data weights.  The two families' iterations differ in the operator launch alone (k_wls_op, five plane transfers, for
-           k_w_op, three).  Median of --calls after --warmup.  Written as JSON lines to --time-out (default
+           data weights.  The two families' iterations differ in the operator launch alone (k_pcg_op with WlsCoef, five plane
+           transfers, for WeightedCoef's three).  Median of --calls after --warmup.  Written as JSON lines to --time-out (default
            profiles/wls_probe.json, appended).
            Kernel times: the same leg under  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/wls_probe.py --time --calls 3
 
