@@ -336,8 +336,11 @@ typedef struct sc_batch_job {
     uint8_t *body;       int body_cols, body_rows, body_step;
     const uint8_t *mask; int mask_cols, mask_rows, mask_step;
     int centerX, centerY;
-    const uint8_t *body_restore;   /* device-resident batches only: if non-NULL, body is refreshed from
-                                      this device image (body_step * body_rows bytes) before the clone */
+    const uint8_t *body_restore;   /* device-resident batches only: if non-NULL, body is refreshed from this device image
+                                      (body_step * body_rows bytes) as part of the clone: after the call's work body holds
+                                      those bytes with the clone's result in the ROI interior.  A group copies only what
+                                      its clone does not write and reads the ROI's pixels from this image, so it must stay
+                                      valid and unchanged until the call's work has finished (the instance's sync) */
     int rc;                        /* out: SC_OK or SC_ERR_* of this job */
 } sc_batch_job;
 /* n device-resident clones on ONE instance.  Members whose ROIs have the same size (W x H; masks, positions and

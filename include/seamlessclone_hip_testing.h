@@ -154,6 +154,12 @@ SC_API int sc_hip_coarse_tile_plan(const int *facts, int *plan);
 #define SC_FUSED_ROW 18
 SC_API int sc_hip_fused_schedule(const int *facts, const int *verdicts, int nverdicts, int *rows, int capacity);
 
+/* Host only, nothing is launched: the byte spans [begin, end) that sc_hip_run_device_batch copies from sc_batch_job.body_restore for a
+ * grouped member whose ROI interior the clone writes -- the image's step x rows bytes without the interior (byte columns
+ * [3 (ltx + 1), 3 (ltx + W - 1)) of rows lty + 1 .. lty + H - 2) of the W x H ROI at (ltx, lty).  spans receives begin, end per span in
+ * ascending order.  Returns their number; SC_ERR_BAD_ARG for a ROI outside the image or more spans than `capacity`. */
+SC_API int sc_hip_restore_spans(long long step, int rows, int ltx, int lty, int W, int H, long long *spans, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -373,6 +373,8 @@ def load():
     L.sc_hip_coarse_tile_plan.restype = C.c_int
     L.sc_hip_fused_schedule.argtypes = [i32p, i32p, C.c_int, i32p, C.c_int]
     L.sc_hip_fused_schedule.restype = C.c_int
+    L.sc_hip_restore_spans.argtypes = [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_longlong), C.c_int]
+    L.sc_hip_restore_spans.restype = C.c_int
     L.sc_hip_plan_groups.argtypes = [i32p, C.c_int, C.c_int, C.POINTER(SolverOpts), i32p, i32p]
     L.sc_hip_plan_groups.restype = C.c_int
     L.sc_hip_plan_size.argtypes = [C.c_int, C.c_int, C.POINTER(SolverOpts), i32p]
@@ -1255,6 +1257,16 @@ def fused_schedule(verdicts=(), **facts):
         raise SeamlessCloneError(n, "fused_schedule")
     k = len(FUSED_ROW)
     return [dict(zip(FUSED_ROW, out[k * i:k * i + k])) for i in range(n)], out[k * n], out[k * n + 1], out[k * n + 2]
+
+
+def restore_spans(step, rows, ltx, lty, W, H):
+    """Host-only: the byte spans [(begin, end), ...] a grouped member's frame-only restore copies (sc_hip_restore_spans)."""
+    cap = max(2, int(H))
+    out = (C.c_longlong * (2 * cap))()
+    n = load().sc_hip_restore_spans(int(step), int(rows), int(ltx), int(lty), int(W), int(H), out, cap)
+    if n < 0:
+        raise SeamlessCloneError(n, "restore_spans")
+    return [(out[2 * k], out[2 * k + 1]) for k in range(n)]
 
 
 def cycle0_forms():

@@ -16,8 +16,10 @@
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
 //      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
+//   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -428,6 +430,27 @@ int main()
         int facts[12] = { 2, 2, 0, 0, 1, 1, 1, 1, 0, 1, 1, 1 };
         if (sc_hip_fused_schedule(facts, nullptr, 0, rows.data(), (int)rows.size()) != SC_ERR_BAD_ARG) return fail("fused_schedule took budget 0");
         if (sc_hip_fused_schedule(nullptr, nullptr, 0, rows.data(), (int)rows.size()) != SC_ERR_BAD_ARG) return fail("fused_schedule (null)");
+    }
+    // 9: the spans of a frame-only restore, applied as copies between heap blocks of exactly step x rows bytes (a span that leaves the
+    //    image is the sanitizer's to report); the interior stays untouched, a capacity one short is refused
+    {
+        for (int i = 0; i < 400; ++i) {
+            const int W = 1 + i % 9, H = 1 + (i / 9) % 8, ltx = i % 5, lty = (i / 5) % 3, cols = ltx + W + i % 3, rows = lty + H + (i / 3) % 2;
+            const long long step = 3 * cols + i % 4;
+            std::vector<long long> sp(2 * (size_t)(H + 1));
+            const int n = sc_hip_restore_spans(step, rows, ltx, lty, W, H, sp.data(), H + 1);
+            if (n < 1 || n > std::max(1, H - 1)) return fail("restore_spans: count");
+            std::vector<uint8_t> src((size_t)step * rows, 1), dst((size_t)step * rows, 0);
+            for (int k = 0; k < n; ++k) memcpy(dst.data() + sp[2 * k], src.data() + sp[2 * k], (size_t)(sp[2 * k + 1] - sp[2 * k]));
+            for (int y = 0; y < rows; ++y)
+                for (long long x = 0; x < step; ++x) {
+                    const bool inside = y > lty && y < lty + H - 1 && x >= 3 * (ltx + 1) && x < 3 * (ltx + W - 1);
+                    if (dst[(size_t)y * step + x] != (inside ? 0 : 1)) return fail("restore_spans: a byte");
+                }
+            if (sc_hip_restore_spans(step, rows, ltx, lty, W, H, sp.data(), n - 1) != SC_ERR_BAD_ARG) return fail("restore_spans wrote past its capacity");
+        }
+        long long sp[4];
+        if (sc_hip_restore_spans(30, 4, 8, 0, 5, 3, sp, 2) != SC_ERR_BAD_ARG || sc_hip_restore_spans(30, 4, 0, 0, 5, 3, nullptr, 2) != SC_ERR_BAD_ARG) return fail("restore_spans (bad geometry)");
     }
     printf("sanitize_main: clean\n");
     return 0;

@@ -8,6 +8,28 @@
 
 using namespace sc;
 
+namespace sc {
+
+// The frame of a destination (sc_common.h, FrameSpans): what splice_block and postprocess_block leave alone -- the ROI's ring, everything
+// around the ROI, row padding, the bytes behind the last pixel of a row.  The interior they write is the byte columns
+// [3 (ltx + 1), 3 (ltx + W - 1)) of rows lty + 1 .. lty + H - 2; the bytes from the end of one interior row's interior to the start of
+// the next one's are contiguous in memory, so the H - 2 interior rows leave H - 3 runs between them.  The ROI lies inside the image
+// (check_roi) and 3 * cols <= step, so every run has at least six bytes and the tail ends at the image's last byte.
+FrameSpans frame_spans(size_t step, int rows, int ltx, int lty, int W, int H)
+{
+    FrameSpans f{};
+    f.bytes = step * (size_t)rows;
+    f.head_end = f.tail_begin = f.bytes;
+    if (W < 3 || H < 3) return f;          // no interior: nothing the clone writes
+    const size_t c0 = 3 * (size_t)(ltx + 1), c1 = 3 * (size_t)(ltx + W - 1), top = (size_t)(lty + 1) * step;
+    f.head_end = top + c0;
+    f.mid_first = top + c1; f.mid_len = step - (c1 - c0); f.stride = step; f.mids = H - 3;
+    f.tail_begin = top + (size_t)(H - 3) * step + c1;
+    return f;
+}
+
+} // namespace sc
+
 // ---- n device-resident clones through ONE set of launches ------------------------------------------------------
 // The solver treats the channels of a field as independent planes, so n clones whose ROIs have the same size are one
 // field of 3n channels: every multigrid launch is n times larger (the coarse levels stop being launch-latency bound,
@@ -29,9 +51,18 @@ struct RagScope {      // leaves the size-class mode on every way out
 
 // members idx[0..n) of `jobs` as one field of 3n channels: all with the same ROI size (plans == nullptr), or a SIZE CLASS (sc_ragged.cpp:
 // plans[k] = member idx[k]'s plan; the fields take the class's largest width and height).  guess: the predicted rectangles the
-// members were launched on (nullptr: their boxes are the device's), d_r: the device rectangles of ALL members of the call
+// members were launched on (nullptr: their boxes are the device's), d_r: the device rectangles of ALL members of the call.
+// frame[i]: only the frame of member i's destination was restored (sc_hip_run_device_batch), so its destination pixels are READ from
+// body_restore; its output is written to body as ever.  Such a member's interior holds stale bytes until it is SPLICED, and a code of
+// SC_OK or SC_ERR_NOT_CONVERGED from here says an output launch over every member's interior is in the stream:
+//  - the accepted bytes form: launch_splice_planar_group in mg_solve_fused, which then sets spec_post.done (VERDICT_ACCEPT);
+//  - write_output: mg_solve_fused's behind a judged cycle that leaves its field (spec_post.done), else the line behind solve_step below
+//    (every other solver, a budget that ran out, a rejected bytes form);
+//  - the saturation retry inside solve_step: the first attempt's output launches carried the solve's AbortFlag and wrote nothing, the
+//    pre-process runs again -- from body_src, the pristine pixels -- and the second attempt ends in one of the two lines above.
+// What is left is the member's own guard (a predicted box the device did not find): the caller compares and restores.
 int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &idx, const std::vector<Geo> &geo, const int *guess, int *d_r,
-                      const std::vector<SizePlan> *plans)
+                      const std::vector<SizePlan> *plans, const std::vector<char> &frame)
 {
     const int n = (int)idx.size();
     Geo g0 = geo[idx[0]];
@@ -53,7 +84,8 @@ int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &i
         mj[k].rect = d_r + GROUP_RS * i;
         mj[k].g = geo[i]; mj[k].M = (uint8_t *)I->d_M.p + mplane * k; mj[k].mpitch = I->mpitch;
         ij[k].face_org = j.face + (size_t)geo[i].y0 * j.face_step + 3 * geo[i].x0; ij[k].fstep = j.face_step;
-        ij[k].body_org = j.body + (size_t)geo[i].lty * j.body_step + 3 * geo[i].ltx; ij[k].bstep = j.body_step;
+        const size_t roi = (size_t)geo[i].lty * j.body_step + 3 * geo[i].ltx;
+        ij[k].body_org = j.body + roi; ij[k].body_src = frame[i] ? j.body_restore + roi : j.body + roi; ij[k].bstep = j.body_step;
         ij[k].M = (const uint8_t *)I->d_M.p + mplane * k;
         ij[k].d_rect = guess ? d_r + GROUP_RS * i : nullptr;
         if (guess) { ij[k].rx0 = guess[4 * i]; ij[k].rx1 = guess[4 * i + 1]; ij[k].ry0 = guess[4 * i + 2]; ij[k].ry1 = guess[4 * i + 3]; }
@@ -125,7 +157,12 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
         for (int i = 0; i < n; ++i) worst = worse(worst, alone(i));
         return worst;
     };
-    {   // refresh the destinations that ask for it: one launch per 16 (k_copy_group); odd alignments take the runtime's copy
+    // Refresh the destinations that ask for it: one launch per 16 (k_copy_group); odd alignments take the runtime's copy.  frame[i]:
+    // only the frame of member i's destination (frame_spans) -- its clone writes the rest.  The calls that group nothing restore
+    // everything at once; a call that may group restores behind the host's decision on who is grouped (below).
+    std::vector<char> frame(n, 0);
+    std::vector<Geo> geo(n);
+    auto restore = [&]() -> int {
         CopyJobs cj{};
         int cn = 0;
         auto flush = [&]() { if (cn) { launch_copy_group(cj, cn, I->stream); cn = 0; } };
@@ -138,12 +175,23 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
                 continue;
             }
             cj.dst[cn] = j.body; cj.src[cn] = j.body_restore; cj.bytes[cn] = bytes;
+            cj.frame[cn] = frame[i] ? frame_spans((size_t)j.body_step, j.body_rows, geo[i].ltx, geo[i].lty, geo[i].W, geo[i].H) : FrameSpans{};
             if (++cn == CopyJobs::MAX) flush();
         }
         flush();
         SC_HIP(I, hipGetLastError());
-    }
-    if (n == 1 || I->opts.reference_warmup || (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK)) return one_by_one();
+        return SC_OK;
+    };
+    // the interior ROWS of a member whose frame alone was restored and that was not spliced: with them its destination is the restore
+    // source again, byte for byte
+    auto restore_rows = [&](int i) -> int {
+        const sc_batch_job &j = jobs[i];
+        const size_t at = (size_t)(geo[i].lty + 1) * j.body_step, end = std::min((size_t)(geo[i].lty + geo[i].H - 1) * j.body_step, (size_t)j.body_step * j.body_rows);
+        frame[i] = 0;
+        SC_HIP(I, hipMemcpyAsync(j.body + at, j.body_restore + at, end - at, hipMemcpyDeviceToDevice, I->stream));
+        return SC_OK;
+    };
+    if (n == 1 || I->opts.reference_warmup || (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK)) return (rc = restore()) ? rc : one_by_one();
     // members whose images do not even validate run alone (and report their own error); the others are candidates for a group
     std::vector<char> usable(n, 1);
     int nusable = 0;
@@ -154,12 +202,14 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
         else ++nusable;
     }
     I->err.clear();
-    if (nusable < 2) return one_by_one();
+    if (nusable < 2) return (rc = restore()) ? rc : one_by_one();
     I->stage_marks = false;
     // --- bounding boxes of all masks, one read-back
     constexpr int RS = GROUP_RS;
-    if ((rc = ensure(I, I->d_rects, (size_t)n * RS * sizeof(int)))) return rc;
-    if ((rc = ensure_pinned(I, I->h_rects, (size_t)n * 2 * RS * sizeof(int)))) return rc;
+    if ((rc = ensure(I, I->d_rects, (size_t)n * RS * sizeof(int))) || (rc = ensure_pinned(I, I->h_rects, (size_t)n * 2 * RS * sizeof(int)))) {
+        restore();
+        return rc;
+    }
     // (the fold launch writes every usable member's rectangle to d_r AND into the pinned h_out: no seeds to upload, nothing to read back)
     int *h_out = (int *)I->h_rects.p + RS * n, *d_r = (int *)I->d_rects.p;
     {
@@ -172,7 +222,10 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
             m.rect = d_r + RS * i; m.rect_host = h_out + RS * i;
             mj.push_back(m);
         }
-        if ((rc = ensure(I, I->d_bbox_parts, sizeof(int) * mask_bbox_group_parts(mj.data(), (int)mj.size())))) return rc;
+        if ((rc = ensure(I, I->d_bbox_parts, sizeof(int) * mask_bbox_group_parts(mj.data(), (int)mj.size())))) {
+            restore();
+            return rc;
+        }
         launch_mask_bbox_group(mj.data(), (int)mj.size(), I->stream, (int *)I->d_bbox_parts.p);
     }
     SC_HIP(I, hipGetLastError());
@@ -183,7 +236,6 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
     // wait in front of the erodes.  Every member's splice carries its guess and writes nothing unless the device found
     // that box; the host compares when the answers are in (they are by the time the solver has waited for its stop rule)
     // and repeats the members that were guessed wrong, one by one on their true boxes.
-    std::vector<Geo> geo(n);
     std::vector<int> guess(4 * (size_t)n);
     bool speculative = !(I->opts.flags & SC_FLAG_NO_SPECULATE) && I->group_spec_cooldown == 0;
     if (I->group_spec_cooldown > 0) --I->group_spec_cooldown;
@@ -228,13 +280,27 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
         for (size_t k = 0; k < cand.size(); ++k) plan_size(I->opts, geo[cand[k]].W, geo[cand[k]].H, plans[k]);
         plan_groups(plans, n, parts);
     }
+    std::vector<int> singles;
+    for (int i = 0; i < n; ++i) if (!grouped[i]) singles.push_back(i);
+    for (const auto &pq : parts) if (pq.size() < 2) { singles.push_back(cand[pq[0]]); grouped[cand[pq[0]]] = 0; }
+    // --- the restore, now that the host knows who is grouped.  A member that is launched on its predicted box in a part of two or more
+    //     gets its frame only: the group reads its ROI from body_restore and writes the interior.  Both pointers must take the kernel's
+    //     16-byte copies, and no other job of the call may share the destination (its restore or its clone would meet this one's stale
+    //     interior).  Everyone else -- no prediction, alone, misaligned, shared -- gets the whole image as before.
+    if (speculative)
+        for (int i = 0; i < n; ++i) {
+            const sc_batch_job &j = jobs[i];
+            if (!grouped[i] || !j.body_restore || j.body_restore == j.body || geo[i].W < 3 || geo[i].H < 3 || (((uintptr_t)j.body | (uintptr_t)j.body_restore) & 15) != 0) continue;
+            bool shared = false;
+            for (int k = 0; k < n && !shared; ++k) shared = k != i && jobs[k].body == j.body;
+            frame[i] = !shared;
+        }
+    if ((rc = restore())) return rc;
     int worst = SC_OK;
     sc_run_info keep{};
     bool have_group = false;
-    std::vector<int> singles;
-    for (int i = 0; i < n; ++i) if (!grouped[i]) singles.push_back(i);
     for (const auto &pq : parts) {
-        if (pq.size() < 2) { singles.push_back(cand[pq[0]]); grouped[cand[pq[0]]] = 0; continue; }
+        if (pq.size() < 2) continue;
         std::vector<int> q(pq.size());
         std::vector<SizePlan> qp;
         bool uniform = true;
@@ -243,8 +309,15 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
             uniform = uniform && geo[q[k]].W == geo[q[0]].W && geo[q[k]].H == geo[q[0]].H;
         }
         if (!uniform) for (int k : pq) qp.push_back(plans[k]);
-        rc = run_group_members(I, jobs, q, geo, speculative ? guess.data() : nullptr, d_r, uniform ? nullptr : &qp);
-        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;          // a HIP error: nothing more can be trusted on this stream
+        rc = run_group_members(I, jobs, q, geo, speculative ? guess.data() : nullptr, d_r, uniform ? nullptr : &qp, frame);
+        if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) {
+            // nothing of this part or of the ones behind it was spliced.  A HIP error: nothing more can be trusted on this stream
+            if (rc != SC_ERR_HIP && hipEventSynchronize(I->ev_rects) == hipSuccess)
+                for (int i = 0; i < n; ++i)
+                    if (frame[i] == 1 || (frame[i] == 2 && memcmp(&guess[4 * i], h_out + RS * i, 4 * sizeof(int)) != 0)) (void)restore_rows(i);
+            return rc;
+        }
+        for (int i : q) frame[i] = frame[i] ? 2 : 0;          // spliced, if the device found the predicted box
         worst = worse(worst, rc);
         keep = I->info; have_group = true;
     }
@@ -256,6 +329,7 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
         for (int i = 0; i < n; ++i)
             if (grouped[i] && memcmp(&guess[4 * i], h_out + RS * i, 4 * sizeof(int)) != 0) {
                 I->group_spec_cooldown = 8;
+                if (frame[i] && (rc = restore_rows(i))) return rc;   // (its interior was not even restored)
                 singles.push_back(i);                          // its destination was not touched: repeat it alone on its true box
             }
     }
@@ -322,6 +396,22 @@ int sc_hip_plan_prepare(const int *wh, int n, const sc_solver_opts *opts)
 }
 
 void sc_hip_plan_cache_clear(void) { plan_cache_clear(); }
+
+int sc_hip_restore_spans(long long step, int rows, int ltx, int lty, int W, int H, long long *spans, int capacity)
+{
+    if (!spans || step < 3 || rows < 1 || ltx < 0 || lty < 0 || W < 1 || H < 1 || 3 * ((long long)ltx + W) > step || lty + H > rows) return SC_ERR_BAD_ARG;
+    const FrameSpans f = frame_spans((size_t)step, rows, ltx, lty, W, H);
+    int k = 0;
+    auto put = [&](size_t a, size_t b) {
+        if (a >= b) return;
+        if (k < capacity) { spans[2 * k] = (long long)a; spans[2 * k + 1] = (long long)b; }
+        ++k;
+    };
+    put(0, f.head_end);
+    for (int r = 0; r < f.mids; ++r) put(f.mid_first + (size_t)r * f.stride, f.mid_first + (size_t)r * f.stride + f.mid_len);
+    put(f.tail_begin, f.bytes);
+    return k <= capacity ? k : SC_ERR_BAD_ARG;
+}
 
 int sc_hip_reference_tables_singular(int w, int h)
 {

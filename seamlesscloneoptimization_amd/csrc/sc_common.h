@@ -45,7 +45,9 @@ struct MaskJob {
 struct MaskJobs { enum { MAX = 16 }; MaskJob j[MAX]; };     // by value in the kernel arguments
 // pre- / post-process of the members of a group: ROI origins in the images and the member's eroded mask; member i owns
 // channels 3i..3i+2 of the fields (blockIdx.z = i)
-struct ImageJob { const uint8_t *face_org; int fstep; uint8_t *body_org; int bstep; const uint8_t *M;
+// body_org: where the member's output is WRITTEN; body_src: where its destination pixels are READ (the pre-process), at the same
+// step -- body_org itself, or the same ROI of the restore source when the group restores only the destination's frame (sc_batch.cpp)
+struct ImageJob { const uint8_t *face_org; int fstep; uint8_t *body_org; const uint8_t *body_src; int bstep; const uint8_t *M;
                   const int *d_rect; int rx0, rx1, ry0, ry1;
                   int W, H; };      // W > 0: the member's own ROI size inside fields laid out for a larger one (a size class, RagMember); 0: the fields' size   // d_rect != nullptr: the member ran on a PREDICTED bounding box and is spliced only if the device found exactly that box (RectGuard semantics)
 struct ImageJobs { enum { MAX = 16 }; ImageJob j[MAX]; };
@@ -208,8 +210,16 @@ void launch_postprocess_group(Field U, const ImageJob *jobs, int n, hipStream_t 
 void launch_splice_planar(Field Q, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), AbortFlag ab = AbortFlag());
 void launch_splice_planar_group(Field Q, const ImageJob *jobs, int n, hipStream_t s, AbortFlag ab = AbortFlag());
 void launch_half_to_float(const void *src_half, float *dst, size_t n, hipStream_t s);
-// up to 16 device-to-device copies in one launch (16-byte aligned pointers)
-struct CopyJobs { enum { MAX = 16 }; void *dst[MAX]; const void *src[MAX]; size_t bytes[MAX]; };
+// The FRAME of a destination whose ROI interior a clone is going to write: every byte of the image's step x rows except the interior
+// columns of the interior rows.  In memory that is a head [0, head_end), `mids` runs of mid_len bytes `stride` apart from mid_first
+// (the bytes behind one interior row's last interior pixel up to the next row's first), and a tail [tail_begin, bytes).  A ROI
+// without interior: the head is the whole image (head_end == bytes, no mids, tail_begin == bytes).
+struct FrameSpans { size_t bytes, head_end, mid_first, mid_len, stride, tail_begin; int mids; };
+// the one place that computes them (host only): image of `step` bytes x `rows`, ROI of W x H pixels (3 bytes each) at (ltx, lty)
+FrameSpans frame_spans(size_t step, int rows, int ltx, int lty, int W, int H);
+// up to 16 device-to-device copies in one launch (16-byte aligned pointers).  frame[i].bytes != 0: only that frame of member i is
+// copied (frame[i].bytes == bytes[i]); 0, as CopyJobs{} leaves it: all of bytes[i]
+struct CopyJobs { enum { MAX = 16 }; void *dst[MAX]; const void *src[MAX]; size_t bytes[MAX]; FrameSpans frame[MAX]; };
 void launch_copy_group(const CopyJobs &t, int n, hipStream_t s);
 
 void launch_jacobi(Field Uin, Field Uout, Field F, hipStream_t s, bool tag = false, int lds_tile_rows = 0);

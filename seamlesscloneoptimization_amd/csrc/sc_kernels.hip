@@ -688,7 +688,7 @@ __global__ __launch_bounds__(256) void k_preprocess_group(ImageJobs t, int mpitc
         if ((int)blockIdx.x * P4_TW >= j.W || (int)blockIdx.y * P4_TH >= j.H) return;
         U0.W = F.W = j.W; U0.H = F.H = j.H;
     }
-    preprocess_block<HF, HU, false, false, MODE>(j.body_org, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
+    preprocess_block<HF, HU, false, false, MODE>(j.body_src, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
 }
 
 template <int MODE>
@@ -752,16 +752,47 @@ void launch_preprocess(const uint8_t *body_org, int bstep, const uint8_t *face_o
     else launch_preprocess_mode<SC_NORMAL_CLONE>(g4, body_org, bstep, face_org, fstep, M, mpitch, U0, U1, F, s, f_half, u_half, bb);
 }
 
+// bytes [a, b) of one member by lanes `lane` of `lanes`: source and destination are 16-byte aligned at byte 0, so the run is the
+// bytes up to its first 16-byte boundary, whole uint4s, and the bytes behind its last boundary -- nothing outside [a, b) is touched
+__device__ __forceinline__ void copy_run(const uint8_t *__restrict__ s, uint8_t *__restrict__ d, size_t a, size_t b, size_t lane, size_t lanes)
+{
+    if (a >= b) return;
+    size_t a16 = (a + 15) & ~(size_t)15;
+    if (a16 > b) a16 = b;
+    const size_t b16 = a16 + ((b - a16) & ~(size_t)15);          // a16 <= b16 <= b, b - b16 < 16
+    if (lane < 16) {
+        if (a + lane < a16) d[a + lane] = s[a + lane];
+        if (b16 + lane < b) d[b16 + lane] = s[b16 + lane];
+    }
+    for (size_t o = a16 + 16 * lane; o < b16; o += 16 * lanes) *reinterpret_cast<uint4 *>(d + o) = *reinterpret_cast<const uint4 *>(s + o);
+}
+
 // Device-to-device refresh of the destinations of a group of clones (sc_batch_job.body_restore) in ONE launch: sixteen separate
 // 16 MB copies run at 2.7 TB/s (each too short to fill the chip, 3 % of a bench step); one launch over all of them streams.
-// 16-byte aligned pointers, sizes in bytes (a tail below 16 bytes is copied bytewise).
+// 16-byte aligned pointers, sizes in bytes (a tail below 16 bytes is copied bytewise).  A member whose clone is going to write its
+// ROI's interior has only its FRAME copied (CopyJobs::frame, sc_batch.cpp): 79 % of the bench's destination bytes are interior.
 __global__ __launch_bounds__(256) void k_copy_group(CopyJobs t)
 {
     const int m = blockIdx.y;
+    const size_t T = (size_t)gridDim.x * 256;              // four fully coalesced 16-byte loads in flight per lane
+    if (t.frame[m].bytes) {
+        // only the frame of this destination (FrameSpans, sc_common.h; block-uniform): head and tail by all of the member's lanes,
+        // the runs between the interior rows by groups of sixteen lanes, one run at a time
+        const FrameSpans &f = t.frame[m];
+        const uint8_t *__restrict__ s = reinterpret_cast<const uint8_t *>(t.src[m]);
+        uint8_t *__restrict__ d = reinterpret_cast<uint8_t *>(t.dst[m]);
+        const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+        copy_run(s, d, 0, f.head_end, g, T);
+        copy_run(s, d, f.tail_begin, f.bytes, g, T);
+        for (size_t k = g >> 4; k < (size_t)f.mids; k += T >> 4) {
+            const size_t a = f.mid_first + k * f.stride;
+            copy_run(s, d, a, a + f.mid_len, g & 15, 16);
+        }
+        return;
+    }
     const uint4 *__restrict__ s4 = reinterpret_cast<const uint4 *>(t.src[m]);
     uint4 *__restrict__ d4 = reinterpret_cast<uint4 *>(t.dst[m]);
     const size_t n16 = t.bytes[m] >> 4;
-    const size_t T = (size_t)gridDim.x * 256;              // four fully coalesced 16-byte loads in flight per lane
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += 4 * T) {
         const size_t i1 = i + T, i2 = i + 2 * T, i3 = i + 3 * T;
         const uint4 a = s4[i], b = s4[i1 < n16 ? i1 : i], c = s4[i2 < n16 ? i2 : i], d = s4[i3 < n16 ? i3 : i];
@@ -778,8 +809,13 @@ __global__ __launch_bounds__(256) void k_copy_group(CopyJobs t)
 
 void launch_copy_group(const CopyJobs &t, int n, hipStream_t s)
 {
+    // sized by the member with the most to move; a frame's runs between the interior rows count a quarter of their bytes, of 256 at
+    // least (sixteen lanes take one run at a time)
     size_t mx = 0;
-    for (int i = 0; i < n; ++i) mx = std::max(mx, t.bytes[i]);
+    for (int i = 0; i < n; ++i) {
+        const FrameSpans &f = t.frame[i];
+        mx = std::max(mx, f.bytes ? f.head_end + (f.bytes - f.tail_begin) + (size_t)f.mids * std::max<size_t>(f.mid_len, 256) / 4 : t.bytes[i]);
+    }
     const unsigned gx = (unsigned)std::min<size_t>(2048, std::max<size_t>(1, (mx / 16 + 1023) / 1024));
     hipLaunchKernelGGL(k_copy_group, dim3(gx, n), dim3(256), 0, s, t);
 }
