@@ -724,6 +724,69 @@ SC_API int sc_hip_wls_device(void *instance, const sc_wls_params *p, const sc_po
 SC_API int sc_hip_wls(void *instance, const sc_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                       const float *lap, const float *data, const float *weight, const float *smooth_x, const float *smooth_y,
                       const float *boundary, float *out);
+/* ---- robust solves: Lp penalties on the gradient and on the data term, by reweighting on the device -----------------------------------
+ * The problem: per channel, with exponents 0 < p <= 2 on the gradient term and 0 < q <= 2 on the data term,
+ *     minimise   sum_p w(p) phi_q(u(p) - d(p); eps_d)  +  sum_x-links c_x phi_p(u(x+1,y) - u(x,y) - gx; eps_g)
+ *                                                      +  sum_y-links c_y phi_p(u(x,y+1) - u(x,y) - gy; eps_g),
+ *     phi_r(t; eps) = (2 / r) (t^2 + eps^2)^(r/2)      (r = 2: t^2, eps is not used),
+ * under every border kind of sc_hip_wls -- integrating gradient fields with gross outliers (photometric stereo, edited or thresholded
+ * gradients), total-variation denoising (p = 1, q = 2: ROF; q = 1: TV-L1), robust fusion.  The penalty is anisotropic: one residual per
+ * link.  With p < 1 (or q < 1) the energy is not convex and the call finds a local minimum, the one its quadratic start leads to.
+ * Solved by iteratively reweighted least squares.  Round 0 is the quadratic problem with links c and weights w: sc_hip_wls's system,
+ * set up and solved as that call does (without base links: with every link 1).  Round k >= 1 solves the WLS system with
+ *     s_x = c_x rho_p(u_x - gx),   s_y = c_y rho_p(u_y - gy),   w' = w rho_q(u - d),      rho_r(t) = (t^2 + eps^2)^((r-2)/2),
+ * taken at round k - 1's iterate (u beyond a Dirichlet line is boundary's value there; the link across a periodic seam wraps), started
+ * from that iterate: r = b - L u, z = M^-1 r, p = z.  Conjugate gradients started there lower the round's quadratic surrogate at every
+ * iterate, so a round lowers the energy even when its solve stops early.  rho in float32: r = 2: exactly 1, the base value passes through
+ * without a multiply; r = 1: 1.0f / sqrtf(t * t + eps * eps), square and sum each rounded; any other r: powf(t * t + eps * eps, (r - 2) / 2).
+ * The right-hand side of a round is sc_hip_wls's, in its order, from s and w'.  The preconditioner's s-bar and w-bar are each round's
+ * own means.
+ * With p = q = 2 no reweighting round runs and the call writes the bytes of sc_hip_wls with default parameters bar tol and max_iters
+ * (links of 1.0f when the job has no base links).
+ * Rounds: at most max_rounds after the quadratic one; the call stops earlier when in the last round no plane's energy fell by more
+ * than round_tol times its energy (the rule needs two rounds' energies: rounds 0 and 1 always run).  Running out of rounds is SC_OK.
+ * Host waits: the WLS call's per inner solve, and one more per round: the read of the sums of k_robust_setup (s-bar, w-bar, the energies).
+ * The energy of the final iterate takes one more launch of that kernel and one more wait, also when p = q = 2.
+ * Arrays, layout, chunks, aliasing and per-job codes: sc_hip_wls_device's; gx, gy are required (the base kind must be SC_POISSON_GUIDANCE:
+ * the residual needs g itself).  smooth_x, smooth_y: the base links c, both or neither; in a device call all jobs carry them or none
+ * does (the first job decides, a job that differs gets SC_ERR_BAD_ARG).  They and weight must be valid as in sc_hip_wls.
+ * Codes: SC_ERR_BAD_ARG for an exponent outside (0, 2], an eps that is not finite or not > 0 where its exponent is not 2, a non-finite
+ * tol or round_tol, a Laplacian base, exactly one of smooth_x / smooth_y; the others are the WLS call's.  SC_ERR_NOT_CONVERGED only when
+ * an inner solve ran out of max_iters (the rounds go on from its last iterate; the last iterate is written).
+ * sc_run_info: sweeps = the inner iterations of all rounds, converged = the round rule was met (always 1 when p = q = 2), rel_residual
+ * = the last inner solve's; the rest as the WLS call.
+ * Not offered: isotropic TV (the per-pixel gradient magnitude), joint-channel TV, a robust term through the 8-bit entry points. */
+typedef struct sc_robust_params {
+    int   kind;              /* as sc_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
+    float p_grad, eps_grad;  /* 0 < p <= 2; eps > 0 and finite (unused when p == 2) */
+    float p_data, eps_data;  /* likewise for the data term */
+    int   max_rounds;        /* reweighting rounds after the quadratic solve; <= 0: 15 */
+    float round_tol;         /* stop when no plane's energy fell by more than round_tol * its energy in the last round; 0: 1e-4; < 0: never stop early */
+    float tol;               /* inner solves: ||r||_2 <= tol * ||b||_2 on every plane; <= 0: 1e-5 */
+    int   max_iters;         /* per inner solve; <= 0: 400 */
+} sc_robust_params;
+typedef struct sc_robust_job {
+    const float *gx, *gy;    /* the guidance: required */
+    const float *data;       /* d: read at every unknown */
+    const float *weight;     /* w >= 0: read at every unknown */
+    const float *smooth_x;   /* the base links c > 0, live ones only are read; both NULL: all 1 */
+    const float *smooth_y;
+    const float *boundary;   /* its Dirichlet lines (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_robust_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_robust_check(const sc_robust_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_robust_device(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, sc_robust_job *jobs, int n, bool bSync);
+/* One problem on host arrays, as sc_hip_wls: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                         const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
+                         float *out);
+/* The last robust call's last chunk, round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+ * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
+ * that round's inner iterations.  Either pointer may be NULL. */
+SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -234,6 +234,17 @@ class WlsJob(C.Structure):
                 ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
+class RobustParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("p_grad", C.c_float), ("eps_grad", C.c_float), ("p_data", C.c_float), ("eps_data", C.c_float),
+                ("max_rounds", C.c_int), ("round_tol", C.c_float), ("tol", C.c_float), ("max_iters", C.c_int)]
+
+
+class RobustJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("data", C.c_void_p), ("weight", C.c_void_p), ("smooth_x", C.c_void_p),
+                ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -430,6 +441,14 @@ def load():
     L.sc_hip_wls_device.restype = C.c_int
     L.sc_hip_wls.argtypes = [C.c_void_p, C.POINTER(WlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
     L.sc_hip_wls.restype = C.c_int
+    L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_robust_check.restype = C.c_int
+    L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
+    L.sc_hip_robust_device.restype = C.c_int
+    L.sc_hip_robust.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 8
+    L.sc_hip_robust.restype = C.c_int
+    L.sc_hip_robust_trace.argtypes = [C.c_void_p, f64p, i32p, C.c_int]
+    L.sc_hip_robust_trace.restype = C.c_int
     _lib = L
     return L
 
@@ -635,6 +654,40 @@ def wls_arrays(data, weight, smooth_x, smooth_y, gx=None, gy=None, lap=None, bou
             raise ValueError(f"{name} must be finite and > 0 on every live link")
         links.append(a)
     return kind, data, weight, links[0], links[1], gx, gy, lap, boundary, out
+
+
+def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
+                 max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
+                 cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_robust_check: SC_OK or the code a robust call with these parameters and this layout returns before it runs
+    anything.  The layout as a PoissonLayout or as keyword fields."""
+    p = RobustParams(int(kind), float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
+                     int(max_iters))
+    return _check_call("sc_hip_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def robust_arrays(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, out=None, neumann=False, free_sides="", periodic="",
+                  p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3):
+    """Checks a robust problem's numpy arrays and penalties before any device is touched: (kind, gx, gy, data, weight, smooth_x, smooth_y,
+    boundary, out), weighted_arrays' rules for data, weight and boundary and wls_arrays' for the base links, which come both or not at
+    all (None: all 1).  gx and gy are required: the residual of a link needs the guidance itself.  Exponents in (0, 2]; an eps finite
+    and > 0 wherever its exponent is not 2."""
+    if gx is None or gy is None:
+        raise ValueError("a robust solve needs the guidance gx and gy (there is no Laplacian form)")
+    if (smooth_x is None) != (smooth_y is None):
+        raise ValueError("smooth_x and smooth_y go together (both None: all base links 1)")
+    for name, r, eps in (("grad", p_grad, eps_grad), ("data", p_data, eps_data)):
+        if not (np.isfinite(r) and 0 < r <= 2):
+            raise ValueError(f"p_{name} must lie in (0, 2]")
+        if r != 2 and not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps_{name} must be finite and > 0")
+    if smooth_x is None:
+        kind, data, weight, gx, gy, _, boundary, out = weighted_arrays(data, weight, gx, gy, None, boundary, out, neumann, free_sides, periodic)
+    else:
+        kind, data, weight, smooth_x, smooth_y, gx, gy, _, boundary, out = wls_arrays(data, weight, smooth_x, smooth_y, gx, gy, None, boundary,
+                                                                                     out, neumann, free_sides, periodic)
+    return kind, gx, gy, data, weight, smooth_x, smooth_y, boundary, out
 
 
 class Instance:
@@ -908,6 +961,41 @@ class Instance:
         the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures raise unless
         allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- robust solves on float32 arrays
+    def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
+               p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0,
+               allow_not_converged=False):
+        """sc_hip_robust on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise sum weight phi_q(u - data) +
+        sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy), phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2), p = p_grad, q = p_data, by
+        reweighted WLS solves on the device, under the borders of poisson().  smooth_x, smooth_y: the base links as in wls(), or None
+        (all 1).  max_rounds, round_tol, tol, max_iters: sc_robust_params' (0: the defaults; round_tol < 0: never stop early).  Returns
+        out; info() has the total of the inner iterations and whether the round rule was met, robust_trace() the rounds."""
+        kind, gx, gy, data, weight, sx, sy, boundary, out = robust_arrays(gx, gy, data, weight, smooth_x, smooth_y, boundary, out, neumann,
+                                                                          free_sides, periodic, p_grad, eps_grad, p_data, eps_data)
+        p = RobustParams(kind, float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
+                         int(max_iters))
+        return self._host_call("sc_hip_robust", p, (gx, gy, data, weight, sx, sy, boundary), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_robust_jobs(n: int):
+        return (RobustJob * n)()
+
+    def robust_device(self, params: RobustParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_robust_device: jobs is a RobustJob array (make_robust_jobs) of device pointers, one layout for all.  sync: bSync and a
+        wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures
+        raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    def robust_trace(self):
+        """(energy, iters) of the last robust call's last chunk: float64 and int32 arrays with one entry per round, the quadratic one
+        included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
+        n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
+        energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        if n:
+            self.L.sc_hip_robust_trace(self.h, energy.ctypes.data_as(f64p), iters.ctypes.data_as(i32p), n)
+        return energy, iters
 
     # ---- device-resident images
     def malloc(self, nbytes):

@@ -14,7 +14,8 @@
 //   5. sc_hip_poisson_check over valid and invalid layouts (the overlap test's 128-bit arithmetic at extreme strides included).
 //   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
-//      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda.
+//      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda, and
+//      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
@@ -402,6 +403,15 @@ int main()
             if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check");
             q.precond_smooth = k.plam;          // (the same values make the same verdicts)
             if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check (precond_smooth)");
+            // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
+            const bool lap_base = (k.kind & 3) == SC_POISSON_LAPLACIAN;
+            sc_robust_params r{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
+            const int got = sc_hip_robust_check(&r, &l);
+            if (lap_base ? got != SC_ERR_BAD_ARG : got != k.want) return fail("robust_check");
+            r.p_grad = 2.5f;
+            if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (p_grad)");
+            r.p_grad = 1.f; r.eps_grad = 0.f;
+            if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (eps_grad)");
         }
         sc_weighted_params p{ SC_POISSON_GUIDANCE, 0.f, 0, 0.f };
         if (sc_hip_weighted_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_weighted_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("weighted_check (null)");

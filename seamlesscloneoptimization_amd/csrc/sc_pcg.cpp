@@ -11,6 +11,9 @@
 //      family's and the preconditioner's three or five, nothing read by the host but the stop rule's norms, SC_WEIGHTED_POLL iterations
 //      late.
 //   5. u and the Dirichlet lines of boundary into the jobs' out.
+// Step 1 and the buffers are pcg_chunk_begin, steps 3 and 4 pcg_chunk_iterate -- which can also start from a U already on the work
+// plane: no u0, r = b - L u at once -- and step 5 pcg_chunk_finish; the weighted and the WLS call run them once each around their set-up
+// (pcg_chunk), the robust call (sc_robust_api.cpp) runs one iterate per reweighting round between one begin and one finish.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cmath>
@@ -22,60 +25,81 @@ namespace {
 
 constexpr int W_LAG = PcgState::LAG, W_RING = PcgState::RING;
 
-struct ChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
+} // namespace
 
 // One chunk of m same-size jobs.  Jobs that their family's statistics refuse get their code here and take no further part; the rest
-// share one iteration and one code (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call).
-int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, ChunkResult &res, int &job_errors)
+// share every solve and one code.
+int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, int &job_errors, PcgChunk &c)
 {
-    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
-    const PcgGeo wg = pcg_geo(mg);
-    const bool lap = poisson_base(call.kind) == SC_POISSON_LAPLACIAN, no_dirichlet = poisson_no_dirichlet(call.kind);
-    const bool fp64 = (I->opts.flags & SC_FLAG_FFT_FP64) != 0;
-    const int nop = pcg_op_parts(wg), nstat = op.nstat;
+    c = PcgChunk();
+    c.I = I;
+    c.call = call;
+    c.g = g;
+    c.mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
+    c.wg = pcg_geo(c.mg);
+    const PcgGeo &wg = c.wg;
+    const bool no_dirichlet = poisson_no_dirichlet(call.kind);
+    const int nop = c.nop = pcg_op_parts(wg), nstat = op.nstat, nround = op.nround;
     PcgState &S = *I->pcg;
     hipStream_t s = I->stream;
     int rc;
     for (hipEvent_t &e : S.ev)
         if (!e) SC_HIP(I, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    // the partial sums: statistics (nstat per part) | bb | pq | rr | rz[0] | rz[1] | rr_tot
+    // the partial sums: statistics (nstat per part) | bb | pq | rr | rz[0] | rz[1] | rr_tot | the family's round sums (nround per part)
     const size_t all_planes = (size_t)g.C * m, per = all_planes * PCG_PARTS;
-    if ((rc = ensure(I, S.red, sizeof(double) * (per * (nstat + 5) + all_planes), false))) return rc;
-    if ((rc = ensure_pinned(I, S.h_red, sizeof(double) * (per * nstat + per + all_planes * W_RING)))) return rc;
-    double *d_stats = (double *)S.red.p, *d_bb = d_stats + nstat * per, *d_pq = d_bb + per, *d_rr = d_pq + per;
-    double *d_rz[2] = { d_rr + per, d_rr + 2 * per }, *d_tot = d_rr + 3 * per;
-    double *h_stats = (double *)S.h_red.p, *h_bb = h_stats + nstat * per, *h_tot = h_bb + per;
+    if ((rc = ensure(I, S.red, sizeof(double) * (per * (nstat + 5) + all_planes + per * nround), false))) return rc;
+    if ((rc = ensure_pinned(I, S.h_red, sizeof(double) * (per * nstat + per + all_planes * W_RING + per * nround)))) return rc;
+    double *d_stats = (double *)S.red.p, *d_rr;
+    c.d_bb = d_stats + nstat * per; c.d_pq = c.d_bb + per; c.d_rr = d_rr = c.d_pq + per;
+    c.d_rz[0] = d_rr + per; c.d_rz[1] = d_rr + 2 * per; c.d_tot = d_rr + 3 * per; c.d_round = c.d_tot + all_planes;
+    double *h_stats = (double *)S.h_red.p;
+    c.h_bb = h_stats + nstat * per; c.h_tot = c.h_bb + per; c.h_round = c.h_tot + all_planes * W_RING;
 
-    // 1. the statistics
+    // the statistics
     op.stats(g, wg, m, d_stats, s);
     SC_HIP(I, hipGetLastError());
     SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * nstat * per, hipMemcpyDeviceToHost, s));
     SC_HIP(I, hipStreamSynchronize(s));
-    std::vector<int *> live;       // the codes of the jobs that stay, their arrays moved to the front
-    for (int k = 0; k < m; ++k) {
+    for (int k = 0; k < m; ++k) {          // the jobs that stay: their arrays move to the front
         const char *why = op.judge(g, k, h_stats + (size_t)k * g.C * PCG_PARTS * nstat, nop, no_dirichlet);
         if (why) {
             *rcs[k] = SC_ERR_BAD_ARG;
             if (!job_errors++) I->err = why;
         } else {
-            op.dj[live.size()] = op.dj[k];
-            live.push_back(rcs[k]);
+            op.dj[c.live.size()] = op.dj[k];
+            c.live.push_back(rcs[k]);
         }
     }
-    const int mv = (int)live.size(), planes = g.C * mv;
-    res = ChunkResult();
-    if (!mv) return SC_OK;
-    const float lam = op.precond_constant(g, wg, mv);
+    c.mv = (int)c.live.size();
+    c.planes = g.C * c.mv;
+    if (!c.mv) return SC_OK;
 
-    // 2. the work planes
-    const size_t plane_bytes = sizeof(float) * (size_t)wg.stride * planes;
+    // the work planes
+    const size_t plane_bytes = sizeof(float) * (size_t)wg.stride * c.planes;
     for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q })
         if ((rc = ensure(I, *b, plane_bytes, false))) return rc;
-    float *U = (float *)S.u.p, *R = (float *)S.r.p, *P = (float *)S.p.p, *Q = (float *)S.q.p, *Z = Q;
-    if ((rc = op.setup(g, wg, lap, mv, R, d_bb))) return rc;
-    SC_HIP(I, hipGetLastError());
+    c.U = (float *)S.u.p; c.R = (float *)S.r.p; c.P = (float *)S.p.p; c.Q = (float *)S.q.p;
+    return SC_OK;
+}
+
+int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &res)
+{
+    Instance *I = c.I;
+    const PoissonGeo &g = c.g;
+    const MixedGeo &mg = c.mg;
+    const PcgGeo &wg = c.wg;
+    const PcgCall &call = c.call;
+    const bool fp64 = (I->opts.flags & SC_FLAG_FFT_FP64) != 0;
+    const int nop = c.nop, mv = c.mv, planes = c.planes;
+    PcgState &S = *I->pcg;
+    hipStream_t s = I->stream;
+    float *U = c.U, *R = c.R, *P = c.P, *Q = c.Q, *Z = Q;
+    double *d_bb = c.d_bb, *d_pq = c.d_pq, *d_rr = c.d_rr, *const *d_rz = c.d_rz, *d_tot = c.d_tot, *h_bb = c.h_bb, *h_tot = c.h_tot;
+    int rc;
+    res = PcgChunkResult();
+    const float lam = op.precond_constant(g, wg, mv);
     SC_HIP(I, hipMemcpyAsync(h_bb, d_bb, sizeof(double) * (size_t)planes * PCG_PARTS, hipMemcpyDeviceToHost, s));
-    // 3. the preconditioner: (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the
+    // the preconditioner: (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the
     // pointers are moved back by the first unknown's offset, and only unknowns are ever addressed (no boundary: no Dirichlet line is
     // read or written)
     const PoissonGeo pg{ g.W, g.H, g.C, 1, (long long)wg.nx, wg.stride };
@@ -114,8 +138,10 @@ int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator
         }
         return SC_OK;
     };
-    if ((rc = precond(R, U))) return rc;                                           // u0 = M^-1 b
-    op.scale_start(wg, planes, U, s);
+    if (!warm) {
+        if ((rc = precond(R, U))) return rc;                                       // u0 = M^-1 b
+        op.scale_start(wg, planes, U, s);
+    }
     op.apply(wg, planes, true, U, R, d_rr, s);                                     // r = b - L u0
     if ((rc = precond(R, Z))) return rc;
     launch_pcg_dot(wg, planes, R, Z, d_rz[0], d_rr, nop, d_tot, s);
@@ -123,7 +149,7 @@ int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator
     launch_pcg_dir(wg, planes, P, Z, d_rz[0], nullptr, s);                    // p = z
     SC_HIP(I, hipGetLastError());
 
-    // 4. the iteration
+    // the iteration
     int iters = 0;
     bool seen = false;
     double worst = 0.0;
@@ -150,19 +176,39 @@ int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator
     res.iters = iters;
     res.rel = worst;
     res.converged = seen;
+    return SC_OK;
+}
 
-    // 5. the output
-    launch_pcg_out(g, wg, op.dj.data(), mv, U, s);
+int pcg_chunk_finish(PcgChunk &c, PcgOperator &op, int code)
+{
+    Instance *I = c.I;
+    launch_pcg_out(c.g, c.wg, op.dj.data(), c.mv, c.U, I->stream);
     SC_HIP(I, hipGetLastError());
-    const int code = res.converged ? SC_OK : SC_ERR_NOT_CONVERGED;
-    for (int k = 0; k < mv; ++k) *live[k] = code;
+    for (int k = 0; k < c.mv; ++k) *c.live[k] = code;
     return code;
+}
+
+namespace {
+
+// the weighted and the WLS call's chunk: one cold solve (the return value: SC_OK or SC_ERR_NOT_CONVERGED, or an error that ends the call)
+int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res, int &job_errors)
+{
+    PcgChunk c;
+    int rc = pcg_chunk_begin(I, call, g, op, rcs, m, job_errors, c);
+    res = PcgChunkResult();
+    if (rc || !c.mv) return rc;
+    if ((rc = op.setup(g, c.wg, poisson_base(call.kind) == SC_POISSON_LAPLACIAN, c.mv, c.R, c.d_bb))) return rc;
+    SC_HIP(I, hipGetLastError());
+    if ((rc = pcg_chunk_iterate(c, op, false, res))) return rc;
+    return pcg_chunk_finish(c, op, res.converged ? SC_OK : SC_ERR_NOT_CONVERGED);
 }
 
 } // namespace
 
-int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed)
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed,
+            PcgChunkFn chunk)
 {
+    if (!chunk) chunk = pcg_chunk;
     CallScope scope{ I };
     const PoissonGeo g{ l->cols, l->rows, l->channels, l->col_stride, l->row_stride, l->channel_stride };
     Geo geo{ 0, 0, g.W, g.H, 0, 0 };
@@ -173,10 +219,10 @@ int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOpe
     bool converged = true;
     double rel = 0.0;
     int worst = run_chunks(I, g.C, rcs, nv, [&](int i0, int m) {
-        ChunkResult res;
+        PcgChunkResult res;
         op.dj.assign(jobs + i0, jobs + i0 + m);
         op.begin(i0, m);
-        const int rc = pcg_chunk(I, call, g, op, rcs + i0, m, res, job_errors);
+        const int rc = chunk(I, call, g, op, rcs + i0, m, res, job_errors);
         sweeps = std::max(sweeps, res.iters);
         converged = converged && res.converged;
         rel = std::max(rel, res.rel);

@@ -26,21 +26,25 @@ struct PcgState {
     DevBuf u, r, p, q;
     DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
-    DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane
-    DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane
+    DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane | a family's round sums
+    DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane | a family's round sums
     hipEvent_t ev[RING]{};
+    std::vector<double> trace_energy;      // the last robust call's last chunk (sc_hip_robust_trace): per round the energy of its iterate
+    std::vector<int> trace_iters;          // ... and its inner iterations
 };
 void pcg_release(Instance *I);             // frees Instance::pcg and all it holds
 
 // What a family tells the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat`
 // doubles per part; the driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets
-// SC_ERR_BAD_ARG and leaves; NULL: it stays, its arrays move to the front and its sums count) -> precond_constant -> setup ->
-// scale_start on u0 -> apply, once in its residual form and then once per iteration.  Everything else -- the preconditioner through
-// direct_jobs_solve, the update, dot and direction launches, the stop rule's mailbox, the output launch -- is the driver's own.
+// SC_ERR_BAD_ARG and leaves; NULL: it stays, its arrays move to the front and its sums count) -> setup -> precond_constant ->
+// scale_start on u0 (a cold start only) -> apply, once in its residual form and then once per iteration.  Everything else -- the
+// preconditioner through direct_jobs_solve, the update, dot and direction launches, the stop rule's mailbox, the output launch -- is
+// the driver's own.
 struct PcgOperator {
     const int nstat;                       // doubles per part of the statistics launch
+    const int nround;                      // doubles per part a family's own later launches sum (PcgChunk::d_round; the robust call's rounds)
     std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
-    explicit PcgOperator(int nstat_) : nstat(nstat_) {}
+    explicit PcgOperator(int nstat_, int nround_ = 0) : nstat(nstat_), nround(nround_) {}
     virtual ~PcgOperator() = default;
     virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
     virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
@@ -61,8 +65,37 @@ struct PcgOperator {
     }
 };
 struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
+struct PcgChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
+// One chunk of m same-size jobs between its prologue and its output, in three steps a family's driver may put its own between:
+//   pcg_chunk_begin    the statistics, the judgement of every job (a refused one gets SC_ERR_BAD_ARG and leaves), the buffers; mv = the
+//                      jobs that stay (0: nothing more to do)
+//   pcg_chunk_iterate  one solve of L u = b: R holds b, d_bb the parts of b . b, the operator's coefficient planes are set.  Cold: u0 =
+//                      M^-1 b times scale_start's factor.  Warm: U holds the start.  Either way r = b - L u through apply's residual
+//                      form, z = M^-1 r, p = z, then the iteration; M = A - precond_constant().  res: this solve's figures
+//   pcg_chunk_finish   U and the Dirichlet lines into the jobs' out, `code` to every job that stayed
+struct PcgChunk {
+    Instance *I = nullptr;
+    PcgCall call{};
+    PoissonGeo g{};
+    MixedGeo mg{};
+    PcgGeo wg{};
+    int mv = 0, planes = 0, nop = 0;
+    float *U = nullptr, *R = nullptr, *P = nullptr, *Q = nullptr;
+    double *d_bb = nullptr, *d_pq = nullptr, *d_rr = nullptr, *d_rz[2] = { nullptr, nullptr }, *d_tot = nullptr, *h_bb = nullptr, *h_tot = nullptr;
+    double *d_round = nullptr, *h_round = nullptr;      // PcgOperator::nround doubles per part, PCG_PARTS parts per plane
+    std::vector<int *> live;                            // the codes of the jobs that stay
+};
+int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, int &job_errors, PcgChunk &c);
+int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &res);
+int pcg_chunk_finish(PcgChunk &c, PcgOperator &op, int code);
+// one chunk of a call: jobs i0 .. of the call's are op.dj already; sets res and the jobs' codes, returns the chunk's code (run_chunks')
+using PcgChunkFn = int (*)(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res,
+                           int &job_errors);
 // The validated jobs of a call through chunks (run_chunks) and sc_run_info.  Returns the worst code, the jobs' own refusals included.
-int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed);
+// chunk: NULL: begin, setup, one cold solve, finish (the weighted and the WLS call).  sc_run_info's sweeps, converged and rel_residual
+// are the chunks' res: the most iterations, all converged, the worst residual.
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed,
+            PcgChunkFn chunk = nullptr);
 
 // ---- the shared launches (sc_pcg.hip)
 // alpha = sum(rz) / sum(pq) per plane (0 when that is not finite);  U += alpha P,  R -= alpha Q,  rr = the parts of R . R
@@ -95,11 +128,24 @@ double wls_live_links(const PcgGeo &wg);
 void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                       const float *const *sy, int m, double *stats, hipStream_t s);
 // R = b (the order: seamlessclone_hip.h, the WLS section), E / S = the link to the next unknown column / row (0: none), Dg = the sum of
-// the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b
+// the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b.  sx NULL (for every job of the call; guidance form
+// only): every link that exists is 1 and neither array is read -- the bytes of a call given arrays of 1.0f
 void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                       const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
 // residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
 void launch_wls_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
                    double *parts, hipStream_t s);
+
+// ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
+// one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;
+// eps2 = eps * eps rounded to float32, half_exp = (r - 2) / 2, scale = 2 / r
+struct RobustTerm { int mode; float eps2, half_exp, scale; };
+constexpr int ROBUST_SUMS = 3;
+// k_wls_setup with s = c rho_p(link residual of U), w' = w rho_q(U - d) (c = sx, sy; NULL for every job: 1): R = b, E, S, Dg as
+// launch_wls_setup in its guidance form, bb = the parts of b . b, sums[(plane * PCG_PARTS + i) * ROBUST_SUMS + ..] = the part's sum of
+// w' | the sum of its live links s, each counted once as launch_wls_stats counts them | the energy of U
+void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                         const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
+                         float *Dg, double *bb, double *sums, hipStream_t s);
 
 } // namespace sc

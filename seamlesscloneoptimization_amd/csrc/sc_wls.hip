@@ -23,10 +23,18 @@ namespace {
 
 // the four incident links of the unknown at pixel (X, Y), offset o, of one channel: 0 where there is none (then nothing is read)
 struct Links { float west, east, north, south; };
+template <bool ONE = false>
 __device__ __forceinline__ Links links_at(const PoissonGeo &g, const float *__restrict__ sx, const float *__restrict__ sy, int X, int Y, long long o,
                                           bool px, bool py)
 {
     Links k;
+    if (ONE) {          // every link that exists is 1: nothing is read
+        k.east = (X < g.W - 1 || px) ? 1.f : 0.f;
+        k.west = (X > 0 || px) ? 1.f : 0.f;
+        k.south = (Y < g.H - 1 || py) ? 1.f : 0.f;
+        k.north = (Y > 0 || py) ? 1.f : 0.f;
+        return k;
+    }
     k.east = (X < g.W - 1 || px) ? sx[o] : 0.f;
     k.west = X > 0 ? sx[o - g.cs] : px ? sx[o + (long long)(g.W - 1) * g.cs] : 0.f;
     k.south = (Y < g.H - 1 || py) ? sy[o] : 0.f;
@@ -65,8 +73,9 @@ __global__ __launch_bounds__(WL) void k_wls_stats(PoissonGeo g, PcgGeo wg, WlsJo
 }
 
 // b in the order the header states: the products s g each rounded on its own, (a - b) + (c - d) as dct_rhs, then - w d as screened_rhs,
-// then the Dirichlet neighbours' s * boundary, west, north, east, south, each product rounded on its own
-template <bool LAP>
+// then the Dirichlet neighbours' s * boundary, west, north, east, south, each product rounded on its own.  ONE: every link is 1 and
+// t.sx, t.sy are not read (the robust call's quadratic round without base links) -- the bytes of a call given arrays of 1.0f
+template <bool LAP, bool ONE>
 __global__ __launch_bounds__(WL) void k_wls_setup(PoissonGeo g, PcgGeo wg, WlsJobs t, float *__restrict__ R, float *__restrict__ E,
                                                    float *__restrict__ S, float *__restrict__ Dg, double *__restrict__ bb)
 {
@@ -80,7 +89,7 @@ __global__ __launch_bounds__(WL) void k_wls_setup(PoissonGeo g, PcgGeo wg, WlsJo
         for (int y = bd.y0; y < bd.y1; ++y) {
             const int X = wg.x0 + bd.x, Y = wg.y0 + y;
             const long long o = bd.pixel(g, X, Y);
-            const Links k = links_at(g, t.sx[bd.member], t.sy[bd.member], X, Y, o, px, py);
+            const Links k = links_at<ONE>(g, t.sx[bd.member], t.sy[bd.member], X, Y, o, px, py);
             float v;
             if (LAP) v = j.lap[o];
             else {
@@ -151,8 +160,9 @@ void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const Poi
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;
-        if (lap) hipLaunchKernelGGL(k_wls_setup<true>, grid, dim3(WL), 0, s, g, wg, t, R + o, E + o, S + o, Dg + o, b);
-        else hipLaunchKernelGGL(k_wls_setup<false>, grid, dim3(WL), 0, s, g, wg, t, R + o, E + o, S + o, Dg + o, b);
+        if (!t.sx[0]) hipLaunchKernelGGL((k_wls_setup<false, true>), grid, dim3(WL), 0, s, g, wg, t, R + o, E + o, S + o, Dg + o, b);
+        else if (lap) hipLaunchKernelGGL((k_wls_setup<true, false>), grid, dim3(WL), 0, s, g, wg, t, R + o, E + o, S + o, Dg + o, b);
+        else hipLaunchKernelGGL((k_wls_setup<false, false>), grid, dim3(WL), 0, s, g, wg, t, R + o, E + o, S + o, Dg + o, b);
     });
 }
 

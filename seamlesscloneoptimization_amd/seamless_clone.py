@@ -537,6 +537,105 @@ def wls_solve_batch(datas, weights, smooth_xs, smooth_ys, gxs=None, gys=None, la
                         lambda inst, layout, jobs: inst._check(inst.wls_device(params, layout, jobs)), gpu_id, solver)
 
 
+def _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters):
+    return capi.RobustParams(kind, float(p), float(eps_grad), float(q), float(eps_data), int(max_rounds or 0), float(round_tol or 0.0),
+                             float(tol or 0.0), int(max_iters or 0))
+
+
+def robust_solve(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3, neumann=True,
+                 free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, **solver):
+    """Robust gradient solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
+        sum weight phi_q(u - data) + sum smooth_x phi_p(u[y, x+1] - u[y, x] - gx) + sum smooth_y phi_p(u[y+1, x] - u[y, x] - gy),
+        phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),      0 < p, q <= 2,
+    by iteratively reweighted least squares on the GPU: the quadratic problem (wls_solve's; smooth_x, smooth_y None: every base link 1)
+    and then up to max_rounds (default 15) WLS solves whose links and weights come from the previous iterate, each started from it.
+    p = 1 is the anisotropic total variation of the gradient residual (one residual per link), q = 1 an L1 data term; eps_grad,
+    eps_data round the penalties off near 0 (in the data's units: a hundredth to a thousandth of its range).  With an exponent below 1
+    the energy is not convex and the result is a local minimum.  round_tol (default 1e-4): stop when no channel's energy fell by more
+    than that fraction in the last round; negative: run every round.  tol, max_iters: the inner solves' (wls_solve's).  Borders,
+    boundary and weight as wls_solve's."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        return inst.robust(gx, gy, data, weight, smooth_x, smooth_y, boundary=boundary, neumann=neumann, free_sides=free_sides,
+                           periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0,
+                           round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0)
+    finally:
+        inst.destroy()
+
+
+def robust_solve_batch(gxs, gys, datas, weights, smooth_xs=None, smooth_ys=None, boundaries=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
+                       neumann=True, free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0,
+                       **solver):
+    """robust_solve over a list of same-shape problems through ONE device-resident call (sc_hip_robust_device), as wls_solve_batch: the
+    rounds, the inner stops and the preconditioner's constants are joint, so a member agrees with its solo solve to the inner solves'
+    error as the rounds carry it, not bit for bit.  Base links for every problem or for none.  Returns a list of NEW arrays."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
+    ds, ws, xs, ys = list(datas), list(weights), list(gxs), list(gys)
+    n = len(ds)
+    if (smooth_xs is None) != (smooth_ys is None):
+        raise ValueError("smooth_xs and smooth_ys go together")
+    fields = [ws, xs, ys] + ([] if smooth_xs is None else [list(smooth_xs), list(smooth_ys)])
+    if not no_boundary:
+        if boundaries is None:
+            raise ValueError("a robust solve with a Dirichlet line needs boundaries")
+        fields = fields + [boundaries]
+    for f in fields:
+        if len(f) != n:
+            raise ValueError("one weight, one guidance field, one pair of base links (or none at all) and, with a Dirichlet line, one "
+                             "boundary per data term")
+    if not ds:
+        return []
+    checked = []
+    for k in range(n):
+        kind, gx, gy, d, w, sx, sy, b, _ = capi.robust_arrays(xs[k], ys[k], ds[k], ws[k], None if smooth_xs is None else smooth_xs[k],
+                                                              None if smooth_ys is None else smooth_ys[k],
+                                                              None if no_boundary else boundaries[k], neumann=neumann, free_sides=free_sides,
+                                                              periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data)
+        if d.shape != ds[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        checked.append([("gx", gx), ("gy", gy), ("data", d), ("weight", w)] + ([] if sx is None else [("smooth_x", sx), ("smooth_y", sy)]) +
+                       ([] if b is None else [("boundary", b)]))
+    params = _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters)
+    return _float_batch(checked, capi.Instance.make_robust_jobs,
+                        lambda inst, layout, jobs: inst._check(inst.robust_device(params, layout, jobs)), gpu_id, solver)
+
+
+def tv_denoise(image, lam, p=1.0, q=2.0, eps=1e-2, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """Total-variation denoising of a float32 image (H x W or H x W x C): the image u that minimises
+        lam sum phi_q(u - image) + sum phi_p(forward differences of u)
+    under reflecting borders -- robust_solve with zero guidance, data = image and weight = lam.  The default p = 1, q = 2 is the
+    (anisotropic) Rudin-Osher-Fatemi model, q = 1 gives TV-L1; p = q = 2 is plain quadratic smoothing.  lam weighs closeness to the image
+    against flatness; eps (in the image's units) rounds both penalties off near 0.  Returns a NEW array."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    if not (np.isfinite(lam) and lam > 0):
+        raise ValueError("lam must be finite and > 0")
+    zero = np.zeros_like(image)
+    return robust_solve(zero, zero, image, np.full(image.shape, lam, np.float32), p=p, q=q, eps_grad=eps, eps_data=eps, neumann=True,
+                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+
+
+def integrate_gradients(gx, gy, boundary=None, p=1.0, eps=1e-3, anchor=1e-3, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """Integrates a float32 gradient field (gx, gy: forward differences, H x W or H x W x C) into an image with an Lp penalty on the
+    residual of every link: p = 1 (the default) ignores gross outliers in the field that a least-squares integration (p = 2) would
+    smear over the image.  boundary given: its outermost rows and columns are the image's (a Dirichlet frame).  None: reflecting borders,
+    and the free constant is held by a data term of weight `anchor` towards 0 -- small enough to leave the shape alone, so the
+    result is the integral up to (nearly) a constant.  eps rounds the penalty off near 0, in the field's units.  Returns a NEW array."""
+    if not isinstance(gx, np.ndarray) or gx.dtype != np.float32:
+        raise TypeError("gx and gy must be float32 numpy arrays")
+    if boundary is None and not (np.isfinite(anchor) and anchor > 0):
+        raise ValueError("anchor must be finite and > 0")
+    if boundary is not None:
+        return robust_solve(gx, gy, np.zeros_like(gx), np.zeros_like(gx), boundary=boundary, p=p, eps_grad=eps, neumann=False,
+                            max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+    return robust_solve(gx, gy, np.zeros_like(gx), np.full(gx.shape, anchor, np.float32), p=p, eps_grad=eps, neumann=True,
+                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+
+
 def _forward_abs_differences(a):
     """(|d/dx|, |d/dy|), H x W float64, of an H x W or H x W x C array (the root of the channels' summed squares); the last column / row,
     which has no forward neighbour, holds 0"""

@@ -1,0 +1,194 @@
+"""CPU tests of the robust solve: the entry points' presence, the ctypes structures against the header, sc_hip_robust_check's codes
+beside sc_hip_wls_check's, what capi.robust_arrays refuses, and the numpy restatement (tests/robust_np.py) against itself: p = q = 2 is
+the WLS solve, the energies of the exact rounds never rise for p = 1, and the exact rounds recover the outlier test's image as far as
+tests/test_gpu_robust.py's bound assumes."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi
+
+import robust_bounds as rb
+import robust_np
+import wls_np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G, L = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN
+NEU, PX, PY = capi.SC_POISSON_NEUMANN, capi.SC_POISSON_PERIODIC_X, capi.SC_POISSON_PERIODIC_Y
+HWC = dict(cols=33, rows=47, channels=3, col_stride=3, row_stride=99, channel_stride=1)
+BORDERS = {b[0]: b[1:] for b in rb.BORDERS}
+
+
+def test_entry_points_are_declared_and_exported():
+    lib = capi.load()
+    for name in ("sc_hip_robust_check", "sc_hip_robust_device", "sc_hip_robust", "sc_hip_robust_trace"):
+        assert name in capi.declared_symbols(capi.HEADER_PATH)
+        assert hasattr(lib, name), name
+    import seamlesscloneoptimization_amd as pkg
+    for name in ("robust_solve", "robust_solve_batch", "tv_denoise", "integrate_gradients"):
+        assert name in pkg.__all__ and callable(getattr(pkg, name))
+
+
+@pytest.mark.parametrize("cname,pyname", [("sc_robust_params", "RobustParams"), ("sc_robust_job", "RobustJob")])
+def test_robust_structs_match_the_header_layout(tmp_path, cname, pyname):
+    import ctypes
+    cls = getattr(capi, pyname)
+    lines = [f'printf("{cname} %zu\\n", sizeof({cname}));']
+    for fname, _ in cls._fields_:
+        lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "seamlessclone_hip.h"\nint main(void) {\n' + "\n".join(lines) +
+                   "\nreturn 0; }\n")
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(out[cname]) == ctypes.sizeof(cls)
+    for fname, _ in cls._fields_:
+        assert int(out[f"{cname}.{fname}"]) == getattr(cls, fname).offset, fname
+
+
+def test_check_codes():
+    bad_arg, bad_size = capi.SC_ERR_BAD_ARG, capi.SC_ERR_BAD_SIZE
+    ok = G | NEU
+    assert capi.robust_check(ok, **HWC) == capi.SC_OK
+    assert capi.robust_check(ok, p_grad=2.0, eps_grad=0.0, p_data=2.0, eps_data=float("nan"), **HWC) == capi.SC_OK      # eps unused at 2
+    assert capi.robust_check(ok, p_grad=0.5, p_data=0.25, max_rounds=-1, round_tol=-1.0, tol=-1.0, max_iters=-1, **HWC) == capi.SC_OK
+    for name in ("p_grad", "p_data"):
+        for v in (0.0, -1.0, 2.0001, 3.0, float("nan"), float("inf")):
+            assert capi.robust_check(ok, **{name: v}, **HWC) == bad_arg, (name, v)
+    for name in ("eps_grad", "eps_data"):
+        for v in (0.0, -1e-3, float("nan"), float("inf")):
+            assert capi.robust_check(ok, p_grad=1.0, p_data=1.0, **{name: v}, **HWC) == bad_arg, (name, v)
+    for name in ("tol", "round_tol"):
+        for v in (float("nan"), float("inf")):
+            assert capi.robust_check(ok, **{name: v}, **HWC) == bad_arg, (name, v)
+    # a Laplacian base: the residual needs g itself
+    for bits in (0, NEU, PX, PX | PY, capi.SC_POISSON_FREE_LEFT):
+        assert capi.wls_check(L | bits, **HWC) == capi.SC_OK
+        assert capi.robust_check(L | bits, **HWC) == bad_arg
+    # ... and everything sc_hip_wls_check refuses, with its code
+    big = lambda cols, rows: dict(cols=cols, rows=rows, channels=1, col_stride=1, row_stride=cols, channel_stride=cols * rows)
+    layouts = [HWC, big(8192, 2), big(8193, 2), big(8194, 3), big(8195, 3), big(2, 7), big(1, 7), big(8193, 3),
+               dict(HWC, channels=5, col_stride=5, row_stride=165), dict(HWC, row_stride=98), dict(HWC, col_stride=2), dict(HWC, col_stride=0)]
+    kinds = [0, NEU, G, G | NEU, G | NEU | PX, G | PX, G | PX | PY, G | PX | capi.SC_POISSON_FREE_LEFT, G | PY | capi.SC_POISSON_FREE_BOTTOM,
+             G | capi.SC_POISSON_FREE_LEFT | capi.SC_POISSON_FREE_TOP]
+    seen = set()
+    for lay in layouts:
+        for kind in kinds:
+            code = capi.robust_check(kind, **lay)
+            assert code == capi.wls_check(kind, **lay), (kind, lay)
+            seen.add(code)
+    assert seen == {capi.SC_OK, bad_arg, bad_size}
+    assert capi.load().sc_hip_robust_check(None, None) == bad_arg
+
+
+def test_numpy_side_refuses_what_the_library_refuses():
+    H, W = 5, 6
+    z = np.zeros((H, W, 3), np.float32)
+    one = np.ones((H, W, 3), np.float32)
+    kind, gx, gy, d, w, sx, sy, b, out = capi.robust_arrays(z, z, z, np.ones((H, W), np.float32), neumann=True)
+    assert kind == G | NEU and sx is None and sy is None and b is None and w.shape == z.shape
+    with pytest.raises(ValueError, match="guidance"):
+        capi.robust_arrays(None, None, z, one, neumann=True)
+    with pytest.raises(ValueError, match="go together"):
+        capi.robust_arrays(z, z, z, one, one, None, neumann=True)
+    with pytest.raises(ValueError, match="go together"):
+        capi.robust_arrays(z, z, z, one, None, one, neumann=True)
+    for name in ("p_grad", "p_data"):
+        for v in (0.0, -1.0, 2.5, np.nan):
+            with pytest.raises(ValueError, match=name):
+                capi.robust_arrays(z, z, z, one, neumann=True, **{name: v})
+    for name in ("eps_grad", "eps_data"):
+        for v in (0.0, -1.0, np.nan, np.inf):
+            with pytest.raises(ValueError, match=name):
+                capi.robust_arrays(z, z, z, one, neumann=True, p_grad=1.0, p_data=1.0, **{name: v})
+    capi.robust_arrays(z, z, z, one, neumann=True, p_grad=2.0, eps_grad=0.0, p_data=2.0, eps_data=np.nan)      # unused at 2
+    with pytest.raises(ValueError):
+        capi.robust_arrays(z, z, z, one, neumann=False)          # a Dirichlet line needs boundary
+    with pytest.raises(TypeError):
+        capi.robust_arrays(z.astype(np.float64), z, z, one, neumann=True)
+    with pytest.raises(ValueError):
+        capi.robust_arrays(z[:, :-1], z, z, one, neumann=True)
+    bad = one.copy()
+    bad[2, 3, 1] = 0.0
+    with pytest.raises(ValueError, match="smooth_x"):
+        capi.robust_arrays(z, z, z, one, bad, one, neumann=True)
+    # dead base links may hold anything
+    for sides, periodic in (("lrtb", ""), ("", ""), ("lt", ""), ("", "x"), ("", "xy")):
+        sx, sy = rb.dead_to_nan(sides, periodic, one, one)
+        capi.robust_arrays(z, z, z, one, sx, sy, boundary=z if wls_np.has_dirichlet(sides, periodic) else None, free_sides=sides, periodic=periodic)
+
+
+@pytest.mark.parametrize("links", [False, True])
+@pytest.mark.parametrize("border", list(BORDERS))
+def test_quadratic_rounds_are_the_wls_solve(border, links):
+    sides, periodic = BORDERS[border]
+    a = rb.with_dead_nan(sides, periodic, rb.make_input(13, 11, 2, "dense", links))
+    b = a["boundary"] if wls_np.has_dirichlet(sides, periodic) else None
+    us = robust_np.irls_exact(sides, periodic, 2.0, 2.0, 0.0, 0.0, a["weight"], a["cx"], a["cy"], a["gx"], a["gy"], a["data"], a["boundary"], 5)
+    assert len(us) == 1
+    one = np.ones_like(a["data"])
+    cx, cy = (one, one) if a["cx"] is None else (a["cx"], a["cy"])
+    want = wls_np.solve_exact(sides, periodic, a["weight"], cx, cy, a["data"], wls_np.divergence(sides, periodic, cx, cy, a["gx"], a["gy"]), b)
+    assert np.array_equal(us[0], want)
+    u32, its = robust_np.irls_f32(sides, periodic, 2.0, 2.0, 0.0, 0.0, a["weight"], a["cx"], a["cy"], a["gx"], a["gy"], a["data"], a["boundary"], 5)
+    ref, it, _ = wls_np.pcg_f32(sides, periodic, a["weight"], cx, cy, a["data"], wls_np.divergence(sides, periodic, cx, cy, a["gx"], a["gy"]), b)
+    assert len(u32) == 1 and its == [it] and np.array_equal(u32[0], ref)
+    # the weights of a quadratic round are the base values' own bits
+    sx, sy, w2 = robust_np.reweigh(sides, periodic, 2.0, 2.0, 0.0, 0.0, a["weight"], a["cx"], a["cy"], a["gx"], a["gy"], a["data"], us[0])
+    lx, ly = wls_np.live_links(sides, periodic, 13, 11)
+    assert np.array_equal(sx[lx], cx[lx]) and np.array_equal(sy[ly], cy[ly]) and np.array_equal(w2, a["weight"])
+
+
+@pytest.mark.parametrize("q", [2.0, 1.0])
+@pytest.mark.parametrize("border", list(BORDERS))
+def test_energies_never_rise_for_p_1(border, q):
+    sides, periodic = BORDERS[border]
+    a = rb.with_dead_nan(sides, periodic, rb.make_input(16, 21, 2, "sparse", True, seed=1))
+    eps = 1e-3 * a["range"]
+    fixed = (a["weight"], a["cx"], a["cy"], a["gx"], a["gy"], a["data"])
+    us = robust_np.irls_exact(sides, periodic, 1.0, q, eps, eps, *fixed, a["boundary"], 8)
+    e = np.array([robust_np.energy(sides, periodic, 1.0, q, eps, eps, *fixed, u) for u in us])
+    assert np.isfinite(e).all() and (np.diff(e, axis=0) <= 1e-12 * e[:-1]).all(), e
+    assert (e[-1] < 0.9 * e[0]).all(), "the rounds must matter on this input"
+    # the library's rounds in float32 follow them
+    u32, its = robust_np.irls_f32(sides, periodic, 1.0, q, eps, eps, *fixed, a["boundary"], 8)
+    assert len(u32) == 9 and max(its) < 400
+    assert np.abs(u32[-1] - us[-1]).max() <= 2e-3 * a["range"]
+    if wls_np.has_dirichlet(sides, periodic):
+        import periodic_np
+        m = periodic_np.dirichlet_mask(sides, periodic, 16, 21)
+        assert np.array_equal(u32[-1][m], a["boundary"][m])
+
+
+def test_float32_rho_rule():
+    t = np.float32([0.0, 1e-4, -0.3, 2.5])
+    eps = 1e-3
+    assert np.array_equal(robust_np.rho(2.0, eps, t), np.ones(4, np.float32))
+    q = t * t + np.float32(eps) * np.float32(eps)
+    assert q.dtype == np.float32 and np.array_equal(robust_np.rho(1.0, eps, t), np.float32(1) / np.sqrt(q))
+    got = robust_np.rho(1.5, eps, t)
+    assert got.dtype == np.float32 and np.allclose(got, (t.astype(np.float64) ** 2 + eps ** 2) ** -0.25, rtol=1e-5)
+    # phi'(t) = 2 t rho(t): the weights are the majoriser's
+    tt = np.float64(0.37)
+    for r in (0.5, 1.0, 1.5, 2.0):
+        h = 1e-6
+        slope = (robust_np.phi(r, eps, tt + h) - robust_np.phi(r, eps, tt - h)) / (2 * h)
+        assert abs(slope - 2 * tt * robust_np.rho(r, eps, np.float64(tt), np.float64)) <= 1e-6
+
+
+@pytest.mark.parametrize("size", [(47, 33), (9, 300)], ids=["33x47", "300x9"])
+@pytest.mark.parametrize("border", ["frame", "free_l", "periodic_x"])
+def test_exact_rounds_recover_the_image_under_outliers(border, size):
+    """float64 rounds with exact inner solves: the RMS error against the true image falls by about 200 to 340 times against the
+    least-squares integration; the GPU test asks 50 of the float32 library"""
+    sides, periodic, a, img = rb.robust_problem(size[0], size[1], border)
+    us = robust_np.irls_exact(sides, periodic, 1.0, 2.0, 1e-3, 1e-3, a["weight"], None, None, a["gx"], a["gy"], a["data"], a["boundary"], 10)
+    rms = lambda u: float(np.sqrt(np.mean((u - img) ** 2)))
+    ratio = rms(us[0]) / rms(us[-1])
+    print(f"robust recovery {border} {size[1]}x{size[0]}: p = 2 RMS {rms(us[0]):.3g}, p = 1 RMS {rms(us[-1]):.3g}, ratio {ratio:.0f}")
+    assert 199 <= ratio <= 340
