@@ -1,5 +1,6 @@
-// sc_pcg.cpp -- the preconditioned conjugate gradients of the weighted and the WLS call (sc_pcg.h): a family's entry points hand pcg_run
-// their validated jobs and a PcgOperator.  Per chunk of at most SC_POISSON_MAX_PLANES planes (run_chunks):
+// sc_pcg.cpp -- the preconditioned conjugate gradients of the weighted, the WLS and the robust call (sc_pcg.h): a family's entry points
+// run pcg_begin and then pcg_host_call or pcg_device_call, which hand pcg_run the validated jobs and the family's PcgOperator.  Per chunk
+// of at most SC_POISSON_MAX_PLANES planes (run_chunks):
 //   1. the family's statistics (one launch, one host read -- the call's one mandatory wait); a job they refuse gets SC_ERR_BAD_ARG and
 //      leaves the chunk, the rest give the preconditioner's constant lam.
 //   2. set-up: b and the family's coefficients onto compact work planes that hold the unknowns only (from here on every vector is
@@ -243,6 +244,21 @@ int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOpe
         I->info.ms_solve = I->info.ms_device_total = I->info.ms_call = ev_ms(I->ev[0], I->ev[7]);
     }
     return worst;
+}
+
+int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, int carries, const FloatArrays &a, PcgOperator &op, PcgChunkFn chunk)
+{
+    const char *why = "";
+    int rc;
+    if ((rc = float_job_validate(call.kind, carries, a, &why, poisson_span(l)))) { I->err = why; return rc; }
+    FloatStaged s;
+    if ((rc = float_stage(I, l, call.kind, carries, a, s))) return rc;
+    int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
+    op.bind(&s.d_w, &s.d_sx, &s.d_sy);
+    rc = pcg_run(I, call, l, op, &s.job, job_rcs, 1, true, chunk);
+    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
+    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)
+    return poisson_download(I, l, s.job.out, a.out, t, rc);
 }
 
 void pcg_release(Instance *I)

@@ -1,6 +1,8 @@
-// sc_pcg.h -- the preconditioned conjugate gradients that the weighted and the WLS call share: the work planes' geometry and tiling, the
-// instance's state, what a family tells the iteration about its operator (PcgOperator), the driver (pcg_run, sc_pcg.cpp) and the
-// launches (sc_pcg.hip: the shared ones; sc_weighted.hip, sc_wls.hip: a family's statistics, set-up and operator).
+// sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
+// tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
+// it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
+// sc_wls.hip, sc_robust.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
+// (WlsOperator, sc_wls_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
 // Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
 // float4 access); plane p = member C + channel.  Tiling of the launches that walk a plane in 2-D (statistics, set-up, operator): column
@@ -10,6 +12,7 @@
 // shuffles): no atomics, no host round trip.
 #pragma once
 #include "sc_instance.h"
+#include <cmath>
 
 namespace sc {
 
@@ -46,6 +49,8 @@ struct PcgOperator {
     std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
     explicit PcgOperator(int nstat_, int nround_ = 0) : nstat(nstat_), nround(nround_) {}
     virtual ~PcgOperator() = default;
+    // the call's weights and link weights, one pointer per job (pcg_host_call, pcg_device_call: once the staged or taken-in tables exist)
+    virtual void bind(const float *const *w, const float *const *sx, const float *const *sy) = 0;
     virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
     virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
     // st: job k's statistics, its C planes' PCG_PARTS * nstat doubles each, of which the first `parts` parts are set
@@ -62,6 +67,24 @@ struct PcgOperator {
         double sum = 0.0;
         for (int i = 0; i < parts; ++i) sum += plane[(size_t)nstat * i + f];
         return sum;
+    }
+    // A job's weights, fields 0 (the sum) and 1 (how many are invalid) of its statistics: the reason they refuse it, or `own` (the
+    // family's own reason against the job, which ranks behind an invalid weight), or a channel without weight where nothing else
+    // pins it; NULL: none.  job_w: the job's sum.
+    const char *judge_weights(const PoissonGeo &g, const double *st, int parts, bool no_dirichlet, const char *own, double &job_w) const
+    {
+        bool bad = false, empty = false;
+        job_w = 0.0;
+        for (int c = 0; c < g.C; ++c) {
+            const double *plane = st + (size_t)c * PCG_PARTS * nstat;
+            const double sum = stat_sum(plane, parts, 0);
+            bad = bad || stat_sum(plane, parts, 1) != 0.0;
+            empty = empty || !(sum > 0.0);
+            job_w += sum;
+        }
+        if (bad || !std::isfinite(job_w)) return "a weight is negative or not finite";
+        if (own) return own;
+        return no_dirichlet && empty ? "no data weight and no Dirichlet line" : nullptr;
     }
 };
 struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
@@ -96,6 +119,33 @@ using PcgChunkFn = int (*)(Instance *I, const PcgCall &call, const PoissonGeo &g
 // are the chunks' res: the most iterations, all converged, the worst residual.
 int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed,
             PcgChunkFn chunk = nullptr);
+// What every entry of the three families starts with: the instance, the family's validation of the call (its sc_hip_*_check) and the
+// instance's word on a direct solve, with the family's two reasons; kind: poisson_norm_kind's
+template <class Params> int pcg_begin(void *inst, const Params *p, const sc_poisson_layout *l,
+                                      int (*validate)(const Params *, const sc_poisson_layout *, const char **), const char *method_why,
+                                      const char *fp64_why, Instance *&I, int &kind)
+{
+    int rc = begin_call(inst, I);
+    if (rc) return rc;
+    const char *why = "";
+    if ((rc = validate(p, l, &why))) { I->err = why; return rc; }
+    kind = poisson_norm_kind(p->kind);
+    return direct_instance_check(I, kind, l, method_why, fp64_why);
+}
+// ... and ends with.  A host entry: the job's validation, float_stage, op bound to the staged arrays, pcg_run, the download into out
+int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, int carries, const FloatArrays &a, PcgOperator &op,
+                  PcgChunkFn chunk = nullptr);
+// A device entry: float_intake (the jobs it refuses get their codes), op bound to the others' arrays, pcg_run; the worst code
+template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, int carries, Job *jobs, int n,
+                                                         ArraysOf arrays_of, PcgOperator &op, bool timed, PcgChunkFn chunk = nullptr)
+{
+    FloatJobs v;
+    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, poisson_span(l));
+    if (v.rcs.empty()) return worst;
+    I->info.ms_h2d = I->info.ms_d2h = 0.f;
+    op.bind(v.w.data(), v.sx.data(), v.sy.data());
+    return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
+}
 
 // ---- the shared launches (sc_pcg.hip)
 // alpha = sum(rz) / sum(pq) per plane (0 when that is not finite);  U += alpha P,  R -= alpha Q,  rr = the parts of R . R
@@ -120,6 +170,11 @@ void launch_weighted_op(const PcgGeo &wg, int planes, bool residual, const float
 
 // ---- the WLS family (sc_wls.hip): (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p), per-link weights sx, sy > 0 under the call's layout
 struct WlsJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX]; };
+// m jobs and their arrays through WlsJobs tables: fn(table, i0, cnt) launches jobs i0 .. i0 + cnt - 1 (for_job_tables)
+template <class Fn> void for_wls_tables(const PoissonJobDev *jobs, const float *const *w, const float *const *sx, const float *const *sy, int m, Fn fn)
+{
+    for_job_tables<WlsJobs>(m, [&](WlsJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; }, fn);
+}
 constexpr int WLS_STATS = 4;
 // the live links of one plane: those with at least one end among the unknowns
 double wls_live_links(const PcgGeo &wg);
@@ -135,6 +190,31 @@ void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const Poi
 // residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
 void launch_wls_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
                    double *parts, hipStream_t s);
+// The operator of the system "data weights + per-link weights" (sc_wls_api.cpp): the WLS call's, and through RobustOperator
+// (sc_robust_api.cpp) every round's of the robust call.  links: the jobs carry link weights; without them every link that exists is 1 --
+// the weighted call's statistics (two fields, the links not judged), s-bar = 1, launch_wls_setup's constant-link form.  plam, psmooth:
+// precond_lambda and precond_smooth (0: the means).
+struct WlsOperator : PcgOperator {
+    Instance *const I;
+    const bool links;
+    const float plam, psmooth;
+    const float *const *all_w = nullptr, *const *all_sx = nullptr, *const *all_sy = nullptr;
+    std::vector<const float *> dw, dsx, dsy;      // the chunk's; behind judge: of the jobs that stay, in front
+    int kept = 0;
+    double wsum = 0.0, ssum = 0.0;                 // the sums of the weights and of the live links of the jobs that stay
+    bool unit_links = false;                       // every live link is 1: s-bar is
+    float u0_scale = 1.f;                          // 1 / s-bar
+    WlsOperator(Instance *I_, bool links_, float plam_, float psmooth_, int nround_ = 0)
+        : PcgOperator(links_ ? WLS_STATS : 2, nround_), I(I_), links(links_), plam(plam_), psmooth(psmooth_) {}
+    void bind(const float *const *w, const float *const *sx, const float *const *sy) override { all_w = w; all_sx = sx; all_sy = sy; }
+    void begin(int i0, int m) override;
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override;
+    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override;
+    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override;
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override;
+    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override;
+    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override;
+};
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;

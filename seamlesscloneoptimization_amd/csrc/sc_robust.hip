@@ -134,7 +134,7 @@ void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJob
                          const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                          float *Dg, double *bb, double *sums, hipStream_t s)
 {
-    for_job_tables<WlsJobs>(m, [&](WlsJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; }, [&](const WlsJobs &t, int i0, int cnt) {
+    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
         if (t.sx[0]) hipLaunchKernelGGL(k_robust_setup<true>, grid, dim3(WL), 0, s, g, wg, t, grad, data, U + o, R + o, E + o, S + o, Dg + o, bb + po, sums + po * ROBUST_SUMS);

@@ -2,11 +2,12 @@
 // sc_hip_robust_trace): Lp penalties on the gradient and on the data term,
 //     minimise sum w phi_q(u - d) + sum_x-links c_x phi_p(u(x+1,y) - u(x,y) - gx) + sum_y-links c_y phi_p(u(x,y+1) - u(x,y) - gy),
 //     phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),      0 < p, q <= 2,
-// by iteratively reweighted least squares on the device, under every border kind of sc_hip_wls.  The front end is the WLS call's
-// (float_intake, float_stage; FLOAT_SMOOTH when the jobs carry base links c), the iteration the shared conjugate gradients in their
-// three steps (sc_pcg.h: pcg_chunk_begin / pcg_chunk_iterate / pcg_chunk_finish).  Per chunk:
-//   round 0     the quadratic problem, to the letter the WLS call's chunk with links c (all 1 without base links: the weighted call's
-//               statistics, k_wls_setup's constant-link form): statistics, judgement, set-up, a cold solve from u0 = M^-1 b.
+// by iteratively reweighted least squares on the device, under every border kind of sc_hip_wls.  The entry code is the WLS call's
+// (sc_pcg.h: pcg_begin, pcg_host_call, pcg_device_call; FLOAT_SMOOTH when the jobs carry base links c), the iteration the shared
+// conjugate gradients in their three steps (pcg_chunk_begin / pcg_chunk_iterate / pcg_chunk_finish), the operator the WLS call's
+// (WlsOperator, sc_wls_api.cpp): this file's RobustOperator adds the reweighting to it.  Per chunk:
+//   round 0     the quadratic problem: WlsOperator's chunk with links c (without base links: its form without link weights):
+//               statistics, judgement, set-up, a cold solve from u0 = M^-1 b.
 //   round k     k_robust_setup at the iterate of round k - 1: b, E, S, Dg with s = c rho_p, w' = w rho_q, and per part b . b, the sums
 //               of w' and of the live links and the energy of that iterate; one host read of those (the round's one mandatory wait)
 //               gives s-bar and w-bar of M = s-bar (A - w-bar / s-bar) and the round rule's energies; then a warm solve: r = b - L u,
@@ -39,17 +40,8 @@ int robust_validate(const sc_robust_params *p, const sc_poisson_layout *l, const
                            "a robust solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side", why);
 }
 
-int robust_begin(void *inst, const sc_robust_params *p, const sc_poisson_layout *l, Instance *&I, int &kind)
-{
-    int rc = begin_call(inst, I);
-    if (rc) return rc;
-    const char *why = "";
-    if ((rc = robust_validate(p, l, &why))) { I->err = why; return rc; }
-    kind = poisson_norm_kind(p->kind);
-    return direct_instance_check(I, kind, l,
-        "a robust solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)",
-        "a robust solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis");
-}
+constexpr const char *METHOD_WHY = "a robust solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
+constexpr const char *FP64_WHY = "a robust solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
 
 RobustTerm robust_term(float r, float eps)
 {
@@ -64,80 +56,13 @@ RobustTerm robust_term(float r, float eps)
 int carries_of(bool base_links) { return FLOAT_DATA | FLOAT_WEIGHT | (base_links ? FLOAT_SMOOTH : 0); }
 
 // The WLS operator with the links of the current round: round 0 from the caller's arrays, later rounds from the iterate.
-struct RobustOperator final : PcgOperator {
-    Instance *I;
+struct RobustOperator final : WlsOperator {
     const sc_robust_params prm;
-    const bool base_links;
     const RobustTerm grad, data;
-    const float *const *all_w, *const *all_sx, *const *all_sy;
-    std::vector<const float *> dw, dsx, dsy;
-    int kept = 0;
-    double wsum = 0.0, ssum = 0.0;
-    bool unit_links = false;               // round 0 without base links: every live link is 1
-    float u0_scale = 1.f;                  // 1 / s-bar of the current round
-    RobustOperator(Instance *I_, const float *const *w, const float *const *sx, const float *const *sy, bool base_links_, const sc_robust_params *p)
-        : PcgOperator(base_links_ ? WLS_STATS : 2, ROBUST_SUMS), I(I_), prm(*p), base_links(base_links_), grad(robust_term(p->p_grad, p->eps_grad)),
-          data(robust_term(p->p_data, p->eps_data)), all_w(w), all_sx(sx), all_sy(sy) {}
+    RobustOperator(Instance *I_, bool base_links, const sc_robust_params *p)
+        : WlsOperator(I_, base_links, 0.f, 0.f, ROBUST_SUMS), prm(*p), grad(robust_term(p->p_grad, p->eps_grad)),
+          data(robust_term(p->p_data, p->eps_data)) {}
     bool quadratic() const { return grad.mode == 0 && data.mode == 0; }
-    void begin(int i0, int m) override
-    {
-        dw.assign(all_w + i0, all_w + i0 + m);
-        dsx.assign(all_sx + i0, all_sx + i0 + m);
-        dsy.assign(all_sy + i0, all_sy + i0 + m);
-        kept = 0;
-        wsum = ssum = 0.0;
-        unit_links = !base_links;
-    }
-    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
-    {
-        if (base_links) launch_wls_stats(g, wg, dj.data(), dw.data(), dsx.data(), dsy.data(), m, d_stats, s);
-        else launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
-    }
-    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
-    {
-        double job_w = 0.0, job_s = 0.0;
-        bool bad_w = false, bad_s = false, empty = false;
-        for (int c = 0; c < g.C; ++c) {
-            const double *plane = st + (size_t)c * PCG_PARTS * nstat;
-            const double sum = stat_sum(plane, parts, 0);
-            bad_w = bad_w || stat_sum(plane, parts, 1) != 0.0;
-            if (base_links) {
-                bad_s = bad_s || stat_sum(plane, parts, 3) != 0.0;
-                job_s += stat_sum(plane, parts, 2);
-            }
-            empty = empty || !(sum > 0.0);
-            job_w += sum;
-        }
-        if (bad_w || !std::isfinite(job_w)) return "a weight is negative or not finite";
-        if (bad_s || !std::isfinite(job_s)) return "a live link weight is not finite or not > 0";
-        if (no_dirichlet && empty) return "no data weight and no Dirichlet line";
-        dw[kept] = dw[k];
-        dsx[kept] = dsx[k];
-        dsy[kept++] = dsy[k];
-        wsum += job_w;
-        ssum += job_s;
-        return nullptr;
-    }
-    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
-    {
-        const double planes = (double)(g.C * mv);
-        const double wbar = wsum / ((double)wg.nx * (double)wg.ny * planes);
-        const double links = wls_live_links(wg) * planes, sbar = unit_links || !(links > 0.0) ? 1.0 : ssum / links;
-        u0_scale = (float)(1.0 / sbar);
-        return (float)(wbar / sbar);
-    }
-    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override { launch_pcg_scale(wg, planes, U, u0_scale, s); }
-    // round 0: the WLS set-up with the base links
-    int setup(const PoissonGeo &g, const PcgGeo &wg, bool, int mv, float *R, double *bb) override
-    {
-        PcgState &S = *I->pcg;
-        for (DevBuf *b : { &S.e, &S.s, &S.dg }) {
-            const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
-            if (rc) return rc;
-        }
-        launch_wls_setup(g, wg, false, dj.data(), dw.data(), dsx.data(), dsy.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb, I->stream);
-        return SC_OK;
-    }
     // a later round: the system at the chunk's iterate, its means, and that iterate's energy per plane (one wait)
     int reweigh(PcgChunk &c, std::vector<double> &energy)
     {
@@ -159,11 +84,6 @@ struct RobustOperator final : PcgOperator {
             }
         }
         return SC_OK;
-    }
-    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
-    {
-        const PcgState &S = *I->pcg;
-        launch_wls_op(wg, planes, residual, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.dg.p, Q, parts, s);
     }
 };
 
@@ -227,41 +147,28 @@ int sc_hip_robust_check(const sc_robust_params *p, const sc_poisson_layout *l)
 int sc_hip_robust_device(void *inst, const sc_robust_params *p, const sc_poisson_layout *l, sc_robust_job *jobs, int n, bool bSync)
 {
     Instance *I;
-    int kind, rc = robust_begin(inst, p, l, I, kind);
+    int kind, rc = pcg_begin(inst, p, l, robust_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
     // base links: all jobs or none, as the first job has them; a job that differs is refused (as one with exactly one of the two arrays)
     const bool base_links = jobs && n > 0 && (jobs[0].smooth_x || jobs[0].smooth_y);
-    FloatJobs v;
-    const int worst = float_intake(I, kind, carries_of(base_links), jobs, n, [base_links](const sc_robust_job &j) {
+    RobustOperator op(I, base_links, p);
+    return pcg_device_call(I, robust_call(kind, p), l, carries_of(base_links), jobs, n, [base_links](const sc_robust_job &j) {
         const bool stray = !base_links && (j.smooth_x || j.smooth_y);          // (refused through its data pointer: "null data pointer")
-        return FloatArrays{ j.gx, j.gy, nullptr, stray ? nullptr : j.data, j.weight, j.boundary, j.out, j.smooth_x, j.smooth_y }; }, v, poisson_span(l));
-    if (v.rcs.empty()) return worst;
-    I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    RobustOperator op(I, v.w.data(), v.sx.data(), v.sy.data(), base_links, p);
-    rc = pcg_run(I, robust_call(kind, p), l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), bSync, robust_chunk);
-    return worse(worst, rc);
+        return FloatArrays{ j.gx, j.gy, nullptr, stray ? nullptr : j.data, j.weight, j.boundary, j.out, j.smooth_x, j.smooth_y }; }, op, bSync,
+        robust_chunk);
 }
 
 int sc_hip_robust(void *inst, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *data,
                   const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary, float *out)
 {
     Instance *I;
-    int kind, rc = robust_begin(inst, p, l, I, kind);
+    int kind, rc = pcg_begin(inst, p, l, robust_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
     if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: all base links 1)"; return SC_ERR_BAD_ARG; }
     const bool base_links = smooth_x != nullptr;
-    const int carries = carries_of(base_links);
-    const FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y };
-    const char *why = "";
-    if ((rc = float_job_validate(kind, carries, a, &why, poisson_span(l)))) { I->err = why; return rc; }
-    FloatStaged s;
-    if ((rc = float_stage(I, l, kind, carries, a, s))) return rc;
-    int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
-    RobustOperator op(I, &s.d_w, &s.d_sx, &s.d_sy, base_links, p);
-    rc = pcg_run(I, robust_call(kind, p), l, op, &s.job, job_rcs, 1, true, robust_chunk);
-    if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
-    const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)
-    return poisson_download(I, l, s.job.out, out, t, rc);
+    RobustOperator op(I, base_links, p);
+    return pcg_host_call(I, robust_call(kind, p), l, carries_of(base_links), FloatArrays{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y },
+                         op, robust_chunk);
 }
 
 int sc_hip_robust_trace(void *inst, double *energy, int *iters, int cap)

@@ -147,7 +147,7 @@ double wls_live_links(const PcgGeo &wg)
 void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                       const float *const *sy, int m, double *stats, hipStream_t s)
 {
-    for_job_tables<WlsJobs>(m, [&](WlsJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; }, [&](const WlsJobs &t, int i0, int cnt) {
+    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_wls_stats, dim3((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, t,
                            stats + (size_t)g.C * i0 * PCG_PARTS * WLS_STATS);
     });
@@ -156,7 +156,7 @@ void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev
 void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                       const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s)
 {
-    for_job_tables<WlsJobs>(m, [&](WlsJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; }, [&](const WlsJobs &t, int i0, int cnt) {
+    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;

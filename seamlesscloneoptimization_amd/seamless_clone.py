@@ -15,6 +15,8 @@ images through a pool (same-size images share one set of launches).
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from . import capi
@@ -105,21 +107,28 @@ class SeamlessClone:
         return self.instance_ptr.info() if self.instance_ptr is not None else None
 
 
+@contextlib.contextmanager
+def _instance(gpu_id, solver):
+    """The instance of one call: made on gpu_id, the solver options set when any are given, destroyed on every way out."""
+    inst = capi.Instance(gpu_id)
+    try:
+        if solver:
+            inst.set_solver(**solver)
+        yield inst
+    finally:
+        inst.destroy()
+
+
 def seamlessClone(src, dst, mask, p, flags=capi.SC_NORMAL_CLONE, gpu_id=0, **solver):
     """cv2.seamlessClone-shaped convenience: returns a NEW blended image, dst untouched.  flags: cv2.NORMAL_CLONE (1),
     cv2.MIXED_CLONE (2) or cv2.MONOCHROME_TRANSFER (3)."""
     if flags not in capi.CLONE_MODES:
         raise ValueError("flags must be NORMAL_CLONE (1), MIXED_CLONE (2) or MONOCHROME_TRANSFER (3), not %r" % (flags,))
     out = np.array(dst, np.uint8, copy=True, order="C")
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         if flags != capi.SC_NORMAL_CLONE:
             inst.set_clone_mode(flags)
         inst.run(np.ascontiguousarray(src), out, np.ascontiguousarray(mask), int(p[0]), int(p[1]), sync=True)
-    finally:
-        inst.destroy()
     return out
 
 
@@ -143,13 +152,8 @@ def _edit(op, src, mask, gpu_id, solver, **params):
     if s.ndim != 3 or s.shape[2] != 3:
         raise ValueError("src must be H x W x 3 uint8")
     m = _edit_mask(mask, s.shape)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.edit(inst.edit_params(op, **params), s, m)
-    finally:
-        inst.destroy()
 
 
 def colorChange(src, mask, red_mul=1.0, green_mul=1.0, blue_mul=1.0, gpu_id=0, **solver):
@@ -264,13 +268,8 @@ def poisson_solve(boundary, gx=None, gy=None, laplacian=None, gpu_id=0, tol=None
     kind, b, gx, gy, lap, _ = capi.poisson_arrays(boundary, gx, gy, laplacian, neumann=neumann, free_sides=free_sides, periodic=periodic)
     if tol is None:
         tol = 0.0 if _direct(neumann, free_sides, periodic) else poisson_tol(b)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.poisson(b, gx=gx, gy=gy, lap=lap, tol=tol, neumann=neumann, free_sides=free_sides, periodic=periodic)
-    finally:
-        inst.destroy()
 
 
 def _float_batch(members, make_jobs, call, gpu_id, solver):
@@ -288,25 +287,20 @@ def _float_batch(members, make_jobs, call, gpu_id, solver):
         for i, a in enumerate(arrays):
             o = (k * per + i) * slot // 4
             staged[o:o + a.size] = a.reshape(-1)
-    inst = capi.Instance(gpu_id)
-    dev = None
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         dev = inst.malloc(in_bytes + slot * n)
-        inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
-        jobs = make_jobs(n)
-        for k, j in enumerate(jobs):
-            for i, f in enumerate(fields[k]):
-                if f is not None:
-                    setattr(j, f, dev + (k * per + i) * slot)
-            j.out = dev + in_bytes + k * slot
-        call(inst, capi.poisson_layout_of(ref), jobs)
-        out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
-    finally:
-        if dev is not None:
+        try:
+            inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, staged.ctypes.data, in_bytes))
+            jobs = make_jobs(n)
+            for k, j in enumerate(jobs):
+                for i, f in enumerate(fields[k]):
+                    if f is not None:
+                        setattr(j, f, dev + (k * per + i) * slot)
+                j.out = dev + in_bytes + k * slot
+            call(inst, capi.poisson_layout_of(ref), jobs)
+            out = inst.from_device(dev + in_bytes, (slot * n // 4,), np.float32)
+        finally:
             inst.free(dev)
-        inst.destroy()
     return [out[k * slot // 4:k * slot // 4 + ref.size].reshape(ref.shape).copy() for k in range(n)]
 
 
@@ -371,13 +365,8 @@ def screened_solve(data, gx=None, gy=None, laplacian=None, lam=None, boundary=No
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     kind, d, gx, gy, lap, b, _ = capi.screened_arrays(data, gx, gy, laplacian, lam, boundary, neumann=neumann, free_sides=free_sides,
                                                       periodic=periodic)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.screened(d, gx=gx, gy=gy, lap=lap, lam=lam, boundary=b, neumann=neumann, free_sides=free_sides, periodic=periodic)
-    finally:
-        inst.destroy()
 
 
 def screened_solve_batch(datas, gxs=None, gys=None, laplacians=None, lam=None, boundaries=None, neumann=True, gpu_id=0, free_sides=None,
@@ -430,14 +419,48 @@ def weighted_solve(data, weight, gx=None, gy=None, laplacian=None, boundary=None
     stops at ||r|| <= tol ||b|| (default 1e-5) or after max_iters (default 200) iterations, which raises SC_ERR_NOT_CONVERGED.  Without
     any Dirichlet line a channel needs a positive weight somewhere.  flags=SC_FLAG_FFT_FP64: the preconditioner in double."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.weighted(data, weight, gx=gx, gy=gy, lap=laplacian, boundary=boundary, neumann=neumann, free_sides=free_sides,
                              periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0, precond_lambda=precond_lambda or 0.0)
-    finally:
-        inst.destroy()
+
+
+def _pcg_batch(noun, datas, boundaries, neumann, free_sides, periodic, gpu_id, solver, *, required, optional, refusal, length_why, arrays_of,
+               slots, params_of, make_jobs, device_call):
+    """What weighted_solve_batch, wls_solve_batch and robust_solve_batch do alike.  required, optional: the per-problem input lists
+    beside datas, by the job field each fills, in the order their lengths are checked (an optional one may be None: not given);
+    boundaries joins them as "boundary" when a side keeps a Dirichlet line.  refusal: the wrapper's own word against its arguments
+    (None: none), raised in its place among the checks.  arrays_of(data, inputs, borders): the family's capi.*_arrays on one problem
+    (inputs: its members of the lists by name, borders: neumann, free_sides, periodic as keywords) -> (kind, its checked arrays by job
+    field).  slots: the order of a member's arrays in the device block (_float_batch).  params_of(kind): the call's parameters;
+    device_call(inst, params, layout, jobs): the family's device call."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
+    ds = list(datas)
+    lists = {f: list(v) for f, v in required.items()}
+    n = len(ds)
+    if refusal:
+        raise ValueError(refusal)
+    lists.update({f: v for f, v in optional.items() if v is not None})
+    if not no_boundary:
+        if boundaries is None:
+            raise ValueError(f"a {noun} solve with a Dirichlet line needs boundaries")
+        lists["boundary"] = boundaries
+    for v in lists.values():
+        if len(v) != n:
+            raise ValueError(length_why)
+    if not ds:
+        return []
+    checked = []
+    for k in range(n):
+        kind, arrays = arrays_of(ds[k], {f: v[k] for f, v in lists.items()}, dict(neumann=neumann, free_sides=free_sides, periodic=periodic))
+        if arrays["data"].shape != ds[0].shape:
+            raise ValueError("every problem of a batch must have one shape")
+        checked.append([(f, arrays[f]) for f in slots if arrays.get(f) is not None])
+    params = params_of(kind)
+    return _float_batch(checked, make_jobs, lambda inst, layout, jobs: inst._check(device_call(inst, params, layout, jobs)), gpu_id, solver)
+
+
+_GUIDANCE_WHY = "give gxs and gys, or laplacians, or neither"
 
 
 def weighted_solve_batch(datas, weights, gxs=None, gys=None, laplacians=None, boundaries=None, neumann=True, free_sides=None, periodic="",
@@ -446,35 +469,16 @@ def weighted_solve_batch(datas, weights, gxs=None, gys=None, laplacians=None, bo
     copy out, the problems iterated as one field of n x C planes (chunks of at most SC_POISSON_MAX_PLANES planes).  Every plane has its
     own step sizes, but the stop is joint and the automatic preconditioner constant is the chunk's mean weight: a member agrees with its
     solo solve to the stop rule's error.  Neither gxs, gys nor laplacians: zero guidance.  Returns a list of NEW arrays."""
-    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
-    ds, ws = list(datas), list(weights)
-    n = len(ds)
-    if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None):
-        raise ValueError("give gxs and gys, or laplacians, or neither")
-    fields = [ws] + ([gxs, gys] if gxs is not None else [laplacians] if laplacians is not None else [])
-    if not no_boundary:
-        if boundaries is None:
-            raise ValueError("a weighted solve with a Dirichlet line needs boundaries")
-        fields = fields + [boundaries]
-    for f in fields:
-        if len(f) != n:
-            raise ValueError("one weight, one guidance field (or laplacian) and, with a Dirichlet line, one boundary per data term")
-    if not ds:
-        return []
-    checked = []
-    for k in range(n):
-        b = None if no_boundary else boundaries[k]
-        kind, d, w, gx, gy, lap, b, _ = capi.weighted_arrays(ds[k], ws[k], None if gxs is None else gxs[k], None if gys is None else gys[k],
-                                                             None if laplacians is None else laplacians[k], b, neumann=neumann,
-                                                             free_sides=free_sides, periodic=periodic)
-        if d.shape != ds[0].shape:
-            raise ValueError("every problem of a batch must have one shape")
-        arrays = [("gx", gx), ("gy", gy)] if gx is not None else [("lap", lap)]
-        checked.append(arrays + [("data", d), ("weight", w)] + ([] if b is None else [("boundary", b)]))
-    params = capi.WeightedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0))
-    return _float_batch(checked, capi.Instance.make_weighted_jobs,
-                        lambda inst, layout, jobs: inst._check(inst.weighted_device(params, layout, jobs)), gpu_id, solver)
+    def arrays_of(d, a, borders):
+        kind, d, w, gx, gy, lap, b, _ = capi.weighted_arrays(d, a["weight"], a.get("gx"), a.get("gy"), a.get("lap"), a.get("boundary"), **borders)
+        return kind, dict(gx=gx, gy=gy, lap=lap, data=d, weight=w, boundary=b)
+    return _pcg_batch("weighted", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(weight=weights), optional=dict(gx=gxs, gy=gys, lap=laplacians),
+                      refusal=_GUIDANCE_WHY if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None) else None,
+                      length_why="one weight, one guidance field (or laplacian) and, with a Dirichlet line, one boundary per data term",
+                      arrays_of=arrays_of, slots=("gx", "gy", "lap", "data", "weight", "boundary"),
+                      params_of=lambda kind: capi.WeightedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0)),
+                      make_jobs=capi.Instance.make_weighted_jobs, device_call=capi.Instance.weighted_device)
 
 
 def wls_solve(data, weight, smooth_x, smooth_y, gx=None, gy=None, laplacian=None, boundary=None, neumann=True, free_sides=None, periodic="",
@@ -488,15 +492,10 @@ def wls_solve(data, weight, smooth_x, smooth_y, gx=None, gy=None, laplacian=None
     preconditioner is the direct solve scaled by the mean link weight (precond_smooth overrides it) with the mean data weight over it as
     its constant (precond_lambda overrides the mean data weight)."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.wls(data, weight, smooth_x, smooth_y, gx=gx, gy=gy, lap=laplacian, boundary=boundary, neumann=neumann,
                         free_sides=free_sides, periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0,
                         precond_lambda=precond_lambda or 0.0, precond_smooth=precond_smooth or 0.0)
-    finally:
-        inst.destroy()
 
 
 def wls_solve_batch(datas, weights, smooth_xs, smooth_ys, gxs=None, gys=None, laplacians=None, boundaries=None, neumann=True, free_sides=None,
@@ -504,37 +503,19 @@ def wls_solve_batch(datas, weights, smooth_xs, smooth_ys, gxs=None, gys=None, la
     """wls_solve over a list of same-shape problems through ONE device-resident call (sc_hip_wls_device), as weighted_solve_batch: one
     copy in, one copy out, one joint stop, the preconditioner's two constants the chunk's means -- a member agrees with its solo solve to
     the stop rule's error.  Returns a list of NEW arrays."""
-    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
-    ds, ws, sxs, sys_ = list(datas), list(weights), list(smooth_xs), list(smooth_ys)
-    n = len(ds)
-    if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None):
-        raise ValueError("give gxs and gys, or laplacians, or neither")
-    fields = [ws, sxs, sys_] + ([gxs, gys] if gxs is not None else [laplacians] if laplacians is not None else [])
-    if not no_boundary:
-        if boundaries is None:
-            raise ValueError("a WLS solve with a Dirichlet line needs boundaries")
-        fields = fields + [boundaries]
-    for f in fields:
-        if len(f) != n:
-            raise ValueError("one weight, one pair of link weights, one guidance field (or laplacian) and, with a Dirichlet line, one boundary "
-                             "per data term")
-    if not ds:
-        return []
-    checked = []
-    for k in range(n):
-        b = None if no_boundary else boundaries[k]
-        kind, d, w, sx, sy, gx, gy, lap, b, _ = capi.wls_arrays(ds[k], ws[k], sxs[k], sys_[k], None if gxs is None else gxs[k],
-                                                                None if gys is None else gys[k],
-                                                                None if laplacians is None else laplacians[k], b, neumann=neumann,
-                                                                free_sides=free_sides, periodic=periodic)
-        if d.shape != ds[0].shape:
-            raise ValueError("every problem of a batch must have one shape")
-        arrays = [("gx", gx), ("gy", gy)] if gx is not None else [("lap", lap)]
-        checked.append(arrays + [("data", d), ("weight", w), ("smooth_x", sx), ("smooth_y", sy)] + ([] if b is None else [("boundary", b)]))
-    params = capi.WlsParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0), float(precond_smooth or 0.0))
-    return _float_batch(checked, capi.Instance.make_wls_jobs,
-                        lambda inst, layout, jobs: inst._check(inst.wls_device(params, layout, jobs)), gpu_id, solver)
+    def arrays_of(d, a, borders):
+        kind, d, w, sx, sy, gx, gy, lap, b, _ = capi.wls_arrays(d, a["weight"], a["smooth_x"], a["smooth_y"], a.get("gx"), a.get("gy"), a.get("lap"),
+                                                                a.get("boundary"), **borders)
+        return kind, dict(gx=gx, gy=gy, lap=lap, data=d, weight=w, smooth_x=sx, smooth_y=sy, boundary=b)
+    return _pcg_batch("WLS", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(weight=weights, smooth_x=smooth_xs, smooth_y=smooth_ys), optional=dict(gx=gxs, gy=gys, lap=laplacians),
+                      refusal=_GUIDANCE_WHY if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None) else None,
+                      length_why="one weight, one pair of link weights, one guidance field (or laplacian) and, with a Dirichlet line, one boundary "
+                                 "per data term",
+                      arrays_of=arrays_of, slots=("gx", "gy", "lap", "data", "weight", "smooth_x", "smooth_y", "boundary"),
+                      params_of=lambda kind: capi.WlsParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0),
+                                                            float(precond_smooth or 0.0)),
+                      make_jobs=capi.Instance.make_wls_jobs, device_call=capi.Instance.wls_device)
 
 
 def _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters):
@@ -555,15 +536,10 @@ def robust_solve(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=No
     than that fraction in the last round; negative: run every round.  tol, max_iters: the inner solves' (wls_solve's).  Borders,
     boundary and weight as wls_solve's."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    inst = capi.Instance(gpu_id)
-    try:
-        if solver:
-            inst.set_solver(**solver)
+    with _instance(gpu_id, solver) as inst:
         return inst.robust(gx, gy, data, weight, smooth_x, smooth_y, boundary=boundary, neumann=neumann, free_sides=free_sides,
                            periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0,
                            round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0)
-    finally:
-        inst.destroy()
 
 
 def robust_solve_batch(gxs, gys, datas, weights, smooth_xs=None, smooth_ys=None, boundaries=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
@@ -572,36 +548,18 @@ def robust_solve_batch(gxs, gys, datas, weights, smooth_xs=None, smooth_ys=None,
     """robust_solve over a list of same-shape problems through ONE device-resident call (sc_hip_robust_device), as wls_solve_batch: the
     rounds, the inner stops and the preconditioner's constants are joint, so a member agrees with its solo solve to the inner solves'
     error as the rounds carry it, not bit for bit.  Base links for every problem or for none.  Returns a list of NEW arrays."""
-    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
-    no_boundary = capi.no_dirichlet(capi.border_bits(free_sides, neumann, periodic))
-    ds, ws, xs, ys = list(datas), list(weights), list(gxs), list(gys)
-    n = len(ds)
-    if (smooth_xs is None) != (smooth_ys is None):
-        raise ValueError("smooth_xs and smooth_ys go together")
-    fields = [ws, xs, ys] + ([] if smooth_xs is None else [list(smooth_xs), list(smooth_ys)])
-    if not no_boundary:
-        if boundaries is None:
-            raise ValueError("a robust solve with a Dirichlet line needs boundaries")
-        fields = fields + [boundaries]
-    for f in fields:
-        if len(f) != n:
-            raise ValueError("one weight, one guidance field, one pair of base links (or none at all) and, with a Dirichlet line, one "
-                             "boundary per data term")
-    if not ds:
-        return []
-    checked = []
-    for k in range(n):
-        kind, gx, gy, d, w, sx, sy, b, _ = capi.robust_arrays(xs[k], ys[k], ds[k], ws[k], None if smooth_xs is None else smooth_xs[k],
-                                                              None if smooth_ys is None else smooth_ys[k],
-                                                              None if no_boundary else boundaries[k], neumann=neumann, free_sides=free_sides,
-                                                              periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data)
-        if d.shape != ds[0].shape:
-            raise ValueError("every problem of a batch must have one shape")
-        checked.append([("gx", gx), ("gy", gy), ("data", d), ("weight", w)] + ([] if sx is None else [("smooth_x", sx), ("smooth_y", sy)]) +
-                       ([] if b is None else [("boundary", b)]))
-    params = _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters)
-    return _float_batch(checked, capi.Instance.make_robust_jobs,
-                        lambda inst, layout, jobs: inst._check(inst.robust_device(params, layout, jobs)), gpu_id, solver)
+    def arrays_of(d, a, borders):
+        kind, gx, gy, d, w, sx, sy, b, _ = capi.robust_arrays(a["gx"], a["gy"], d, a["weight"], a.get("smooth_x"), a.get("smooth_y"), a.get("boundary"),
+                                                              **borders, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data)
+        return kind, dict(gx=gx, gy=gy, data=d, weight=w, smooth_x=sx, smooth_y=sy, boundary=b)
+    return _pcg_batch("robust", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(weight=weights, gx=gxs, gy=gys), optional=dict(smooth_x=smooth_xs, smooth_y=smooth_ys),
+                      refusal="smooth_xs and smooth_ys go together" if (smooth_xs is None) != (smooth_ys is None) else None,
+                      length_why="one weight, one guidance field, one pair of base links (or none at all) and, with a Dirichlet line, one "
+                                 "boundary per data term",
+                      arrays_of=arrays_of, slots=("gx", "gy", "data", "weight", "smooth_x", "smooth_y", "boundary"),
+                      params_of=lambda kind: _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters),
+                      make_jobs=capi.Instance.make_robust_jobs, device_call=capi.Instance.robust_device)
 
 
 def tv_denoise(image, lam, p=1.0, q=2.0, eps=1e-2, max_rounds=None, round_tol=None, gpu_id=0, **solver):

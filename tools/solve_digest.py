@@ -6,10 +6,12 @@ SC_FLAG_FFT_FP64 transforms, the Neumann problem with and without boundary.
 
     python tools/solve_digest.py [--root DIR] > profiles/solve_digest_<build>.txt      (--root: another checkout's built package)
 
---pcg: instead, the conjugate-gradient families (weighted, WLS), "<case name> <SHA-256 of out> <info().sweeps>", at the smallest shapes
-where their shared walks can go wrong: every pair of axis kinds, a periodic axis of length 2, one unknown, a plane that is no multiple
-of a float4 group, two column groups, several bands and element-wise segments, two job tables, a refused job in a batch, a zero-weight
-plane, a budget that ends the solve.
+--pcg: instead, the conjugate-gradient families (weighted, WLS, robust), "<case name> <SHA-256 of out> <info().sweeps>", at the smallest
+shapes where their shared walks can go wrong: every pair of axis kinds, a periodic axis of length 2, one unknown, a plane that is no
+multiple of a float4 group, two column groups, several bands and element-wise segments, two job tables, a refused job in a batch, a
+zero-weight plane, a budget that ends the solve.  The robust lines (three rounds, every one run; float32 and double preconditioner,
+with and without base links, three pairs of exponents; guidance form only) follow a case's weighted and WLS lines and hash
+robust_trace()'s energies and iterations behind out; one more batch of theirs has links on job 1 alone, which the call refuses.
 
     python tools/solve_digest.py --pcg [--root DIR] > profiles/pcg_digest_<build>.txt
 """
@@ -112,6 +114,10 @@ def batch(inst, name, sides, W, H, m):
 AXES = [("", ""), ("01", ""), ("1", ""), ("0", ""), ("", "p")]      # axis kind (MixedGeo) -> (free ends: 0 low, 1 high; periodic)
 FIELDS = ("gx", "gy", "lap", "data", "weight", "sx", "sy", "boundary")
 FORMS = [(f, p, l, "%s %s %s" % (f, p, "lap" if l else "gxy")) for f in ("weighted", "wls") for p in ("f32", "f64") for l in (False, True)]
+# the robust family's: (precision, base links?, p_grad, p_data, tag)
+ROBUST_FORMS = [(f, c, p, q, "robust %s %s p=%g q=%g" % (f, "links" if c else "unit", p, q))
+                for f in ("f32", "f64") for c in (False, True) for p, q in ((2.0, 2.0), (1.0, 2.0), (0.8, 1.0))]
+ROBUST = dict(eps_grad=0.5, eps_data=0.5, max_rounds=3, round_tol=-1.0)
 
 
 def pcg_arrays(name, k, H, W, C):
@@ -140,14 +146,36 @@ def pcg_single(inst, name, sides, periodic, W, H, C, zero_weight_plane=False, **
         except capi.SeamlessCloneError as e:                 # (a shape the library refuses: the refusal is the result)
             out, refused = np.frombuffer(str(e).encode(), np.uint8), True
         pcg_emit(inst, name, sides, periodic, tag, np.ascontiguousarray(out).tobytes(), refused)
+    for k in ("gx", "gy", "lap"):
+        kw.pop(k)
+    for prec, links, p, q, tag in ROBUST_FORMS:
+        configure(inst, capi.SC_FLAG_FFT_FP64 if prec == "f64" else 0)
+        a = pcg_arrays(name, 0, H, W, C)
+        if zero_weight_plane:
+            a["weight"][:, :, 0] = 0.0
+        base = (a["sx"], a["sy"]) if links else ()
+        try:
+            out = inst.robust(a["gx"], a["gy"], a["data"], a["weight"], *base, boundary=a["boundary"], free_sides=sides, periodic=periodic,
+                              p_grad=p, p_data=q, **ROBUST, **kw)
+            pcg_emit(inst, name, sides, periodic, tag, np.ascontiguousarray(out).tobytes() + robust_trace_bytes(inst))
+        except capi.SeamlessCloneError as e:
+            pcg_emit(inst, name, sides, periodic, tag, str(e).encode(), True)
 
 
-def pcg_batch(inst, name, sides, periodic, W, H, C, m, refuse=None):
+def robust_trace_bytes(inst):
+    energy, iters = inst.robust_trace()
+    return energy.tobytes() + iters.tobytes()
+
+
+def pcg_batch(inst, name, sides, periodic, W, H, C, m, refuse=None, stray=None):
     """m jobs in one device call; refuse: the job whose first weight is negative (its statistics refuse it: the survivors' arrays move
-    to the front).  The digest covers every job's out slot and the jobs' codes."""
+    to the front).  The digest covers every job's out slot and the jobs' codes.  stray: the robust forms without base links alone, with
+    links on that job all the same."""
     n, slot, nf = W * H * C, (W * H * C + 63) // 64 * 64, len(FIELDS)
     layout = capi.PoissonLayout(W, H, C, C, W * C, 1)
-    for family, prec, lap, tag in FORMS:
+    forms = [f + (None,) for f in FORMS if stray is None]
+    forms += [("robust", prec, False, tag, (links, p, q)) for prec, links, p, q, tag in ROBUST_FORMS if stray is None or not links]
+    for family, prec, lap, tag, rb in forms:
         configure(inst, capi.SC_FLAG_FFT_FP64 if prec == "f64" else 0)
         host = np.zeros((m, nf + 1, slot), np.float32)               # FIELDS, out
         for k in range(m):
@@ -159,21 +187,28 @@ def pcg_batch(inst, name, sides, periodic, W, H, C, m, refuse=None):
         try:
             inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, host.ctypes.data, host.nbytes))
             at = lambda k, f: dev + 4 * slot * ((nf + 1) * k + (FIELDS + ("out",)).index(f))      # noqa: E731
-            jobs = capi.Instance.make_weighted_jobs(m) if family == "weighted" else capi.Instance.make_wls_jobs(m)
+            jobs = getattr(capi.Instance, "make_%s_jobs" % family)(m)
             for k, j in enumerate(jobs):
-                j.gx, j.gy, j.lap = (None, None, at(k, "lap")) if lap else (at(k, "gx"), at(k, "gy"), None)
+                if lap:
+                    j.lap = at(k, "lap")
+                else:
+                    j.gx, j.gy = at(k, "gx"), at(k, "gy")
                 j.data, j.weight, j.boundary, j.out = at(k, "data"), at(k, "weight"), at(k, "boundary"), at(k, "out")
-                if family == "wls":
+                if family == "wls" or (rb and (rb[0] or k == stray)):
                     j.smooth_x, j.smooth_y = at(k, "sx"), at(k, "sy")
             kind = (capi.SC_POISSON_LAPLACIAN if lap else capi.SC_POISSON_GUIDANCE) | capi.free_side_bits(sides) | capi.periodic_bits(periodic)
             if family == "weighted":
                 inst.weighted_device(capi.WeightedParams(kind, 0.0, 0, 0.0), layout, jobs, allow_job_errors=True)
-            else:
+            elif family == "wls":
                 inst.wls_device(capi.WlsParams(kind, 0.0, 0, 0.0, 0.0), layout, jobs, allow_job_errors=True)
+            else:
+                inst.robust_device(capi.RobustParams(kind, rb[1], ROBUST["eps_grad"], rb[2], ROBUST["eps_data"], ROBUST["max_rounds"],
+                                                     ROBUST["round_tol"], 0.0, 0), layout, jobs, allow_job_errors=True)
             got = inst.from_device(dev, host.shape, np.float32)
         finally:
             inst.free(dev)
-        pcg_emit(inst, name, sides, periodic, "x%d %s" % (m, tag), got[:, nf, :n].tobytes() + np.array([j.rc for j in jobs], np.int32).tobytes())
+        pcg_emit(inst, name, sides, periodic, "x%d %s" % (m, tag), got[:, nf, :n].tobytes() + (robust_trace_bytes(inst) if rb else b"") +
+                 np.array([j.rc for j in jobs], np.int32).tobytes())
 
 
 def pcg_main(inst):
@@ -192,6 +227,7 @@ def pcg_main(inst):
     for sides, periodic in (("", ""), ("lrtb", "")):
         pcg_batch(inst, "tables 33x31 C1", sides, periodic, 33, 31, 1, 17)
         pcg_batch(inst, "refused 21x19 C3", sides, periodic, 21, 19, 3, 4, refuse=1)
+        pcg_batch(inst, "stray links 21x19 C3", sides, periodic, 21, 19, 3, 4, stray=1)
     pcg_single(inst, "zero-weight plane 37x29 C3", "", "", 37, 29, 3, zero_weight_plane=True)
     pcg_single(inst, "zero-weight plane 37x29 C3", "t", "x", 37, 29, 3, zero_weight_plane=True)
     for sides, periodic in (("", ""), ("lrtb", "")):
