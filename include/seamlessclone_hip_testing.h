@@ -33,6 +33,13 @@ extern "C" {
 #define SC_LEGACY_UNPACKED_TILES 8        /*   multigrid, coarse levels: every column tile in a workgroup of its own.  Default: where the last
                                             column tile of a level needs at most half a wave, one workgroup serves that tile of several
                                             planes (sc_hip_coarse_tile_plan).  Same values, bit for bit                                   */
+#define SC_LEGACY_SPLICE_LAUNCH 16        /*   multigrid, same-size groups: the judged cycle always leaves its bytes planar and a splice launch
+                                            (k_splice_planar_group) interleaves them into the destinations.  Default: from
+                                            members x level-0 tiles = SC_OUT3_MIN_TILES on (sc_instance.h) one workgroup of the judged launch
+                                            serves the three channels of a member's tile and writes the interleaved bytes itself
+                                            (k_cycle0 with C0_OUT3).  Same bytes                                                         */
+#define SC_FORCE_INTERLEAVED_OUT 32      /*   ... and that form wherever it exists (a same-size group of up to 16 members on the default
+                                            path), whatever the threshold says: tests and A/B runs                                       */
 #define SC_FLAG_KEEP_FIELD     (1 << 7)  /* sc_hip_run*: keep the solution field on the device (sc_hip_field_store,
                                             _residual, _finish after a run): the last multigrid cycle writes the field
                                             and a post-process launch reads it.  Default: that cycle writes the output
@@ -121,9 +128,14 @@ SC_API int sc_hip_selftest_host(void);
 
 /* host only (needs no GPU, launches nothing): the instantiation k_cycle0<T, .., PRO, .., TAG> (csrc/sc_cycle0.hip; TAG: the C0_* bits of
  * csrc/sc_common.h) the level-0 multigrid launcher picks for facts[13] = sweeps, prolong, f_half, u_half, q16_in, q16_out, final_cycle,
- * out_bytes, composed, l1_half, timing, bands (pointer given), rag (size class).  form[3] receives T, PRO, TAG; returns 0, or -1: no such
+ * out_bytes (+ 2: as interleaved bytes into the members' destinations, out_interleaved), composed, l1_half, timing, bands (pointer given), rag (size class).  form[3] receives T, PRO, TAG; returns 0, or -1: no such
  * form, nothing would be launched.  facts == NULL: form receives entry `index` of the table of instantiated forms, its length is returned. */
 SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
+
+/* Who wrote the output bytes of the judged multigrid cycles that left bytes on this instance since this was last asked (asking clears
+ * it): bit 0 a splice launch behind planar bytes, bit 1 the judged launch itself, interleaved (k_cycle0 with C0_OUT3: same-size groups,
+ * see SC_LEGACY_SPLICE_LAUNCH).  SC_ERR_BAD_ARG for a bad handle. */
+SC_API int sc_hip_bytes_writer(void *instance);
 
 /* Host only, nothing is launched: the column tiling of a coarse-level multigrid launch and what the lanes of its workgroups serve.
  * facts = { W, H, C (field width and height, ring included; planes), useful width, halo (columns a tile owns; halo columns per side: 232, 12

@@ -59,6 +59,8 @@ SC_FLAG_VCYCLE_BOTTOM = 1 << 4
 SC_FLAG_EXACT_TABLES = 1 << 5
 SC_FLAG_LEGACY_PATHS = 1 << 6      # run the superseded launch forms named in SolverOpts.legacy_paths (SC_LEGACY_* bits)
 SC_LEGACY_SEPARATE_RESTRICT, SC_LEGACY_BOTTOM_F32, SC_LEGACY_SEPARATE_TAIL, SC_LEGACY_UNPACKED_TILES = 1, 2, 4, 8
+SC_LEGACY_SPLICE_LAUNCH = 16       # same-size groups: the judged cycle leaves planar bytes and a splice launch interleaves them, always
+SC_FORCE_INTERLEAVED_OUT = 32      # ... the judged launch writes the interleaved bytes itself wherever that form exists, whatever the threshold
 SC_FLAG_KEEP_FIELD = 1 << 7
 SC_FLAG_FFT_FP64 = 1 << 8
 SC_FLAG_OPENCV_GREY_MASK = 1 << 9
@@ -340,6 +342,8 @@ def load():
     L.sc_hip_field_residual.restype = C.c_int
     L.sc_hip_field_solve.argtypes = [C.c_void_p]
     L.sc_hip_field_solve.restype = C.c_int
+    L.sc_hip_bytes_writer.argtypes = [C.c_void_p]
+    L.sc_hip_bytes_writer.restype = C.c_int
     L.sc_hip_field_shape.argtypes = [C.c_void_p, i32p]
     L.sc_hip_field_shape.restype = C.c_int
     L.sc_hip_field_store.argtypes = [C.c_void_p, f32p, C.c_size_t]
@@ -1078,6 +1082,10 @@ class Instance:
         Cc, H, W = U.shape
         self._check(self.L.sc_hip_field_load(self.h, W, H, Cc, U.ctypes.data_as(f32p), lap.ctypes.data_as(f32p)))
 
+    def bytes_writer(self):
+        """Who wrote the judged cycles' bytes since the last call of this (which clears it): bit 0 a splice launch, bit 1 the judged launch itself, interleaved."""
+        return int(self.L.sc_hip_bytes_writer(self.h))
+
     def field_shape(self):
         whc = np.zeros(3, np.int32)
         self._check(self.L.sc_hip_field_shape(self.h, whc.ctypes.data_as(i32p)))
@@ -1296,6 +1304,8 @@ CYCLE0_FACTS = ("sweeps", "prolong", "f_half", "u_half", "q16_in", "q16_out", "f
 def cycle0_form(**facts):
     """Host-only: (T, PRO, TAG) of the k_cycle0 instantiation the level-0 launcher picks for these facts of a launch descriptor
     (CYCLE0_FACTS; those left out are 0 / false), or -1 where the library has no such form (csrc/sc_cycle0.hip)."""
+    if facts.pop("out_interleaved", 0):      # travels as bit 1 of out_bytes (sc_hip_cycle0_form)
+        facts["out_bytes"] = int(bool(facts.get("out_bytes", 0))) | 2
     f = (C.c_int * len(CYCLE0_FACTS))(*[int(facts.pop(k, 0)) for k in CYCLE0_FACTS])
     if facts:
         raise TypeError("cycle0_form: no such fact: %s" % sorted(facts))

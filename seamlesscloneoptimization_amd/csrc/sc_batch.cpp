@@ -55,7 +55,9 @@ struct RagScope {      // leaves the size-class mode on every way out
 // frame[i]: only the frame of member i's destination was restored (sc_hip_run_device_batch), so its destination pixels are READ from
 // body_restore; its output is written to body as ever.  Such a member's interior holds stale bytes until it is SPLICED, and a code of
 // SC_OK or SC_ERR_NOT_CONVERGED from here says an output launch over every member's interior is in the stream:
-//  - the accepted bytes form: launch_splice_planar_group in mg_solve_fused, which then sets spec_post.done (VERDICT_ACCEPT);
+//  - the accepted bytes form in mg_solve_fused, which then sets spec_post.done (VERDICT_ACCEPT): the judged launch itself where it writes
+//    the members' interleaved bytes (k_cycle0 with C0_OUT3: every interior pixel of every member, the same guards as the splice), else
+//    launch_splice_planar_group behind it;
 //  - write_output: mg_solve_fused's behind a judged cycle that leaves its field (spec_post.done), else the line behind solve_step below
 //    (every other solver, a budget that ran out, a rejected bytes form);
 //  - the saturation retry inside solve_step: the first attempt's output launches carried the solve's AbortFlag and wrote nothing, the

@@ -328,6 +328,7 @@ constexpr int C0_Q16_IN   = 256;    // Uin holds 16-bit fixed point (c0_load_q16
 constexpr int C0_Q16_OUT  = 512;    // ... and so will Uout; a store that saturates reports itself (AbortFlag)
 constexpr int C0_PACK_ROWS = 6;     // ... with bands of at most this many rows per lane
 constexpr int C0_PACK     = 2048;   // coarse levels only (GEN, ZEROIN): the last column tile of several planes in one workgroup, plane and column per lane (coarse_tile_plan)
+constexpr int C0_OUT3     = 4096;   // with C0_OUT | C0_FINAL, a same-size group: one workgroup per (member, tile) runs the member's three channels in turn and writes the tile's interleaved bytes into the destination itself (ImageJobs); nothing planar is stored, no splice launch follows
 constexpr int C0_RAG      = 1024;   // a SIZE CLASS (RagMember): strides and grid are the class's, all else the member's, read from rag[channel / 3]; tiles beyond its extent leave
 
 // One level-0 launch (sc_cycle0.hip): [prolongation of E +] `sweeps` red-black GS sweeps [+ residual + restriction into Fc]; launch_cycle0 derives (T, PRO, TAG) from these facts
@@ -338,6 +339,8 @@ struct Cycle0Launch {
     bool prolong = false;              // add P E first and write the per-workgroup max |P E| to `partial`
     bool f_half = false, u_half = false, q16_in = false, q16_out = false;      // F / Uin hold float16; Uin / Uout hold 16-bit fixed point
     bool final_cycle = false, out_bytes = false;      // the judged cycle: nothing restricted; ... leaving as planar output bytes in Uout's memory, `lm` added
+    bool out_interleaved = false;      // ... leaving as interleaved bytes in the destinations of `jobs` instead (C0_OUT3): members 0 .. njobs - 1 <= ImageJobs::MAX own channels 3i .. 3i + 2; `sat` set: nothing is written
+    const ImageJob *jobs = nullptr; int njobs = 0;
     bool composed = false;             // the prolongation source is composed from E and comp.E2 (comp.g1: level 1's geometry)
     bool l1_half = false, timing = false;      // level 1 keeps float16 fields (mg_level1_half); the form's twin under a second symbol
     ComposeArgs comp{};

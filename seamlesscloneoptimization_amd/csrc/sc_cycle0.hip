@@ -180,18 +180,74 @@ __device__ __forceinline__ float c0_comp(const float4 &v, int k) { return k == 0
 // in a value of the neighbouring plane where lane 0 / 63 of a full tile receive a zero: it lands in a halo lane at depth 0 and moves one
 // column per half-step, and 2T + 2 <= C0_HX keeps it out of the residual and the restriction of every exact column -- what is written is,
 // bit for bit, what the unpacked tiling writes.
-template <int T, int NW, int R, bool PRO, bool GEN, bool ZEROIN, int TAG = 0>
+// C0_OUT3 (the judged bytes form of a same-size group): the grid is one workgroup per (member, tile); it runs the body below for the
+// member's three channels in turn, parks each channel's finished bytes of the exact tile in LDS (c0_out3_stage) and then writes the
+// tile's interior pixels INTERLEAVED into the member's destination itself (c0_out3_write): no planar byte plane, no splice launch.
+// The launch's one extra argument, the members' ImageJobs, is the pack X3 (empty for every other form: their signature is unchanged).
+constexpr int C0_OUT3_ROWS = 52, C0_OUT3_WORDS = (256 - 2 * C0_HX) / 4;      // the exact tile of the two-sweep form: rows, planar words per row and channel
+// the lane's number in its wave, counted afresh behind a zero whose origin is hidden from the optimiser: no register carries it from one pass to the next
+__device__ __forceinline__ int c0_lane_again() { int z = 0; asm volatile("" : "+v"(z)); return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z)); }
+template <bool ON> __device__ __forceinline__ float c0_opaque_s(float v) { if constexpr (ON) asm volatile("" : "+s"(v)); return v; }
+template <bool ON> __device__ __forceinline__ int c0_opaque_s(int v) { if constexpr (ON) asm volatile("" : "+s"(v)); return v; }
+template <int N> __device__ __forceinline__ unsigned *c0_out3_stage() { __shared__ unsigned stage[N]; return stage; }
+// Rows of the tile (rows y0t .., columns x0t ..) as 24-bit pixels into the destination `body` (the pointer of ROI pixel (0, 0), rows
+// `bstep` bytes apart), by splice_block's rule (sc_kernels.hip): interior pixels only (1 <= x <= W - 2, 1 <= y <= H - 2); a word store
+// only for a word that is 4-byte aligned in the destination and lies wholly inside the tile's interior run, single bytes otherwise;
+// no destination byte is read.  A wave serves a row; lane j owns the three destination words that start 12 j bytes behind the aligned
+// word holding the row's first tile byte, i.e. the tile row's bytes 12 j - a .. 12 j - a + 11 (a: that first byte's misalignment; byte o
+// of a tile row is channel o % 3 of tile pixel o / 3), taken from planar words j - 1 and j of the three channels.
+__device__ __forceinline__ void c0_out3_write(const unsigned *__restrict__ stage, uint8_t *__restrict__ body, int bstep, int W, int H, int x0t, int y0t,
+                                              int wv, int lane, int nw)
+{
+    const int lo = 3 * (max(x0t, 1) - x0t), hi = 3 * (min(x0t + 4 * C0_OUT3_WORDS, W - 1) - x0t);      // the tile row's interior bytes [lo, hi)
+    for (int rr = wv; rr < C0_OUT3_ROWS; rr += nw) {
+        const int y = y0t + rr;
+        if (y < 1 || y > H - 2) continue;
+        uint8_t *d = body + (size_t)y * bstep + 3 * (size_t)x0t;
+        const int a = (int)((uintptr_t)d & 3);
+        const int o0 = 12 * lane - a;
+        if (o0 >= hi || o0 + 12 <= lo) continue;
+        const int jc = min(lane, C0_OUT3_WORDS - 1), jp = max(min(lane - 1, C0_OUT3_WORDS - 1), 0);      // (a clamped word only feeds bytes outside [lo, hi))
+        unsigned pc[3], pp[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned *row = stage + (c * C0_OUT3_ROWS + rr) * C0_OUT3_WORDS;
+            pc[c] = row[jc]; pp[c] = row[jp];
+        }
+        unsigned w[4];      // tile-row bytes 12 lane - 4 .. 12 lane + 11
+        w[0] = ((pp[2] >> 16) & 255u) | ((pp[0] >> 24) << 8) | ((pp[1] >> 24) << 16) | ((pp[2] >> 24) << 24);
+        w[1] = (pc[0] & 255u) | ((pc[1] & 255u) << 8) | ((pc[2] & 255u) << 16) | (((pc[0] >> 8) & 255u) << 24);
+        w[2] = ((pc[1] >> 8) & 255u) | (((pc[2] >> 8) & 255u) << 8) | (((pc[0] >> 16) & 255u) << 16) | (((pc[1] >> 16) & 255u) << 24);
+        w[3] = ((pc[2] >> 16) & 255u) | ((pc[0] >> 24) << 8) | ((pc[1] >> 24) << 16) | ((pc[2] >> 24) << 24);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const unsigned v = (unsigned)(((((unsigned long long)w[k + 1]) << 32) | w[k]) >> (8 * (4 - a)));      // a = 0: w[k + 1]
+            const int o = o0 + 4 * k;
+            if (o >= lo && o + 4 <= hi) *reinterpret_cast<unsigned *>(d + o) = v;
+            else {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (o + b >= lo && o + b < hi) d[o + b] = (uint8_t)(v >> (8 * b));
+            }
+        }
+    }
+}
+
+template <int T, int NW, int R, bool PRO, bool GEN, bool ZEROIN, int TAG = 0, class... X3>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) void k_cycle0(Field Uin, Field Uout, Field F, Field Fc, Field E, MGGeom g,
                                                     float *__restrict__ partial, ComposeArgs comp, float4 *__restrict__ bands, LmNodes lm, AbortFlag sat,
-                                                    const RagMember *__restrict__ rag, int lev)
+                                                    const RagMember *__restrict__ rag, int lev, X3... x3)
 {
     constexpr int HY = 2 * T + 2, RH = NW * R;
+    constexpr bool OUT3 = (TAG & C0_OUT3) != 0;
+    static_assert(sizeof...(X3) == (OUT3 ? 1 : 0), "the members' jobs travel with the three-channel bytes form only");
     constexpr bool RAG = (TAG & C0_RAG) != 0;
     constexpr bool COMP = (TAG & C0_COMPOSED) != 0;      // E is U1; the interpolated level-2 correction is added on the fly (ComposeArgs)
     static_assert(!COMP || (PRO && !GEN && R % 2 == 0), "composition of two prolongations exists on level 0 only");
     constexpr bool FINAL = (TAG & C0_FINAL) != 0;      // prolongation + post-smoothing only: the cycle the stop rule is expected to accept
     constexpr bool OUT = (TAG & C0_OUT) != 0, BANDS = ((TAG & C0_BANDS) != 0 || FINAL) && !OUT;
     static_assert(!OUT || (FINAL && !GEN), "bytes leave from the last level-0 launch only");
+    static_assert(!OUT3 || (OUT && !RAG && T == 2 && RH - 2 * HY == C0_OUT3_ROWS), "interleaved bytes: the judged two-sweep form of a same-size group");
     static_assert(!(TAG & C0_BANDS) || !GEN, "cell shares exist on level 0 only");
     constexpr bool HF = (TAG & C0_F_HALF) != 0, HU = (TAG & C0_U_HALF) != 0;   // HU: the first launch of a clone reads the 8-bit destination values the pre-process stored as float16
     static_assert(!(HF && GEN), "float16 right-hand sides exist on level 0 only");
@@ -222,11 +278,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     TileLane tl{};
     if constexpr (PACK) tl = coarse_tile_lane(coarse_tile_plan(W, H, Uin.C, 256 - 2 * C0_HX, C0_HX, RH - 2 * HY, false), Uin.C, 256 - 2 * C0_HX, C0_HX, tile, lane);
     const int bx = tile % nbx, by = PACK ? tl.by : (tile / nbx) % nby;
-    const int c = PACK ? min(tl.c, Uin.C - 1) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing
+    const int c_first = PACK ? min(tl.c, Uin.C - 1) : OUT3 ? 3 * (tile / (nbx * nby)) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing   // OUT3: the tile's member, channels c_first .. c_first + 2 in turn
     const int sl = PACK ? tl.sl : lane, lps = PACK ? tl.lps : 64;        // lane index inside its slot, lanes per slot
     const bool live = !PACK || tl.c < Uin.C;                             // the slot holds a plane of the field
     if constexpr (RAG) {
-        const RagMember &m = rag[c / 3];
+        const RagMember &m = rag[c_first / 3];
         W = m.lw[lev]; H = m.lh[lev];
         if (bx * (256 - 2 * C0_HX) >= W || by * (RH - 2 * HY) >= H) {      // nothing of this member in the tile's exact output (block-uniform, before any barrier)
             if (PRO && threadIdx.x == 0) partial[tile] = 0.f;
@@ -236,8 +292,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         if (PRO) E.H = m.lh[lev + 1];
         if ((TAG & C0_COMPOSED) != 0) { comp.g1 = m.g[lev + 1]; comp.E2.H = m.lh[lev + 2]; }
     }
+    // OUT3: the body runs once per channel of the member (every other form: once, no loop).  What a channel's pass derives from the lane and
+    // the tile is derived AGAIN in every pass -- the sources are made opaque here -- so that nothing but the sources stays in registers from
+    // one pass to the next: the body's register budget is that of the one-channel form.
+    const int lane_wg = lane, wv_wg = wv, bx_wg = bx, by_wg = by;
+    const MGGeom &g_wg = g;
+    const ComposeArgs &comp_wg = comp;
+    int ci = 0, c_run = c_first, pt_run = OUT3 ? tile + 2 * (c_first / 3) * (nbx * nby) : tile;      // the pass's channel and the index of its (channel, tile) maximum: channel-major, as every form's
+    const int pt_step = nbx * nby;
+    _Pragma("nounroll") do {
+    const int lane = OUT3 ? c0_lane_again() : lane_wg, wv = c0_opaque_s<OUT3>(wv_wg), bx = c0_opaque_s<OUT3>(bx_wg), by = c0_opaque_s<OUT3>(by_wg);
+    std::conditional_t<OUT3, MGGeom, const MGGeom &> g = g_wg;      // (OUT3: copies of its own ...)
+    std::conditional_t<OUT3, ComposeArgs, const ComposeArgs &> comp = comp_wg;
+    if constexpr (OUT3) {      // ... in which the weights the prolongation derives its ghost weights from are opaque too
+        g.x.tw1 = c0_opaque_s<OUT3>(g.x.tw1); g.y.tw1 = c0_opaque_s<OUT3>(g.y.tw1);
+        comp.g1.x.tw1 = c0_opaque_s<OUT3>(comp.g1.x.tw1); comp.g1.y.tw1 = c0_opaque_s<OUT3>(comp.g1.y.tw1);
+    }
     const int x = PACK ? tl.x : bx * (256 - 2 * C0_HX) - C0_HX + 4 * lane;
     const int y0 = by * (RH - 2 * HY) - HY + wv * R;       // even
+    const int c = OUT3 ? c_run : c_first, ptile = OUT3 ? pt_run : tile;
     float4 u[R], f[HF ? 1 : R];
     uint2 fh[HF ? R : 1];        // float16 right-hand side, kept packed (c0_minus_f)
     if (ZEROIN) {
@@ -443,11 +516,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         __shared__ float red[NW];
         if (lane == 0) red[wv] = m;
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if (OUT3 ? (lane == 0 && wv == 0) : threadIdx.x == 0) {
             float mm = red[0];
 #pragma unroll
             for (int w = 1; w < NW; ++w) mm = fmaxf(mm, red[w]);
-            partial[tile] = mm;
+            partial[ptile] = mm;
         }
     }
 
@@ -669,7 +742,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     }
 
     // ------------------------------------------------------------------ write back the exact inner tile
-    if (sl < C0_HXQ || sl >= lps - C0_HXQ || !live || x >= P || x >= W) return;
+    if constexpr (OUT3) {
+        if (lane < C0_HXQ || lane >= 64 - C0_HXQ || x >= P || x >= W) continue;      // (no return: the barriers of the next channel and of the write are ahead)
+    } else if (sl < C0_HXQ || sl >= lps - C0_HXQ || !live || x >= P || x >= W) return;
     if constexpr (OUT) {
         // the result leaves as output values: u + node correction (the arithmetic of the post-process, sc_kernels.hip),
         // clamped to [0, 255], truncated; plane c of Uout's memory, rows of P bytes.  The splice kernel interleaves.
@@ -697,9 +772,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
                 const bool second = (y >> 3) != Yc0;       // wave-uniform: the band's rows lie in cell rows Yc0 and Yc0 + 1
                 lm_add4_nodes(second ? nd[1][0] : nd[0][0], second ? nd[1][1] : nd[0][1], second ? nd[2][0] : nd[1][0], second ? nd[2][1] : nd[1][1], x, y, v);
             }
-            *reinterpret_cast<unsigned *>(q + (size_t)y * P + x) = lm_byte(v.x) | (lm_byte(v.y) << 8) | (lm_byte(v.z) << 16) | (lm_byte(v.w) << 24);
+            const unsigned px4 = lm_byte(v.x) | (lm_byte(v.y) << 8) | (lm_byte(v.z) << 16) | (lm_byte(v.w) << 24);
+            if constexpr (OUT3) c0_out3_stage<3 * C0_OUT3_ROWS * C0_OUT3_WORDS>()[(ci * C0_OUT3_ROWS + (yr - HY)) * C0_OUT3_WORDS + (lane - C0_HXQ)] = px4;
+            else *reinterpret_cast<unsigned *>(q + (size_t)y * P + x) = px4;
         }
-        return;
+        if constexpr (OUT3) continue; else return;
     }
     if constexpr (GEN && L1H) {      // the level-1 correction leaves as float16: level 0's prolongation reads it that way
         __half *__restrict__ outh = reinterpret_cast<__half *>(Uout.p) + (size_t)c * Uout.plane;
@@ -734,6 +811,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (int r = 0; r < R; ++r) {
         const int yr = wv * R + r, y = y0 + r;
         if (yr >= HY && yr < RH - HY && y >= 0 && y < H) *reinterpret_cast<float4 *>(out + (size_t)y * P + x) = u[r];
+    }
+    } while (OUT3 && (c_run += 1, pt_run += pt_step, ++ci < 3));      // (the channels of an OUT3 workgroup)
+    if constexpr (OUT3) {
+        // the splice's two tests, block-uniform, once: a solve whose 16-bit field saturated and a member launched on a predicted box the
+        // device did not find write nothing (the maxima above are needed either way)
+        const ImageJobs &t = (x3, ...);
+        const ImageJob &j = t.j[c_first / 3];
+        __syncthreads();
+        if (abort_set(sat)) return;
+        if (j.d_rect && (j.d_rect[0] != j.rx0 || j.d_rect[1] != j.rx1 || j.d_rect[2] != j.ry0 || j.d_rect[3] != j.ry1)) return;
+        c0_out3_write(c0_out3_stage<3 * C0_OUT3_ROWS * C0_OUT3_WORDS>(), j.body_org, j.bstep, W, H, bx * (256 - 2 * C0_HX), by * (RH - 2 * HY), wv, c0_lane_again(), NW);
     }
 }
 
@@ -783,8 +871,18 @@ static constexpr Cycle0Form c0_forms[] = {
 #undef C0_FORM_RAG
 #undef C0_FORM
 
+// ... and the one form outside that table: the judged bytes form of a same-size group that writes the destinations itself (C0_OUT3).
+// Only what the fast path runs: two sweeps behind a composed prolongation, float16 right-hand side and level 1, float field in.
+constexpr int C0_OUT3_TAG = C0_FAST_CYCLE | C0_FINAL | C0_OUT | C0_OUT3;
+static bool c0_is_out3(const Cycle0Launch &d)
+{
+    return d.out_interleaved && d.out_bytes && d.final_cycle && d.prolong && d.composed && d.sweeps == 2 && d.f_half && d.l1_half && !d.u_half && !d.q16_in &&
+           !d.q16_out && !d.timing && !d.rag;
+}
+
 static const Cycle0Form *c0_find(const Cycle0Launch &d)
 {
+    if (d.out_interleaved) return nullptr;      // not a form of the table (cycle0_form, launch_cycle0)
     // cell shares: a final cycle leaves them whenever the pointer is there (the kernel tests it), a full cycle of four sweeps in a form of its own
     const bool shares = d.bands && d.prolong && !d.final_cycle && d.sweeps == 4;
     const int TAG = (d.timing ? C0_TIMING : 0) | (d.f_half ? C0_F_HALF : 0) | (d.u_half ? C0_U_HALF : 0) | (d.final_cycle ? C0_FINAL : 0) |
@@ -797,6 +895,7 @@ static const Cycle0Form *c0_find(const Cycle0Launch &d)
 
 bool cycle0_form(const Cycle0Launch &d, int &T, bool &PRO, int &TAG)
 {
+    if (c0_is_out3(d)) { T = 2; PRO = true; TAG = C0_OUT3_TAG; return true; }
     const Cycle0Form *f = c0_find(d);
     if (f) { T = f->T; PRO = f->PRO; TAG = f->TAG; }
     return f != nullptr;
@@ -810,6 +909,15 @@ int cycle0_form_at(int i, int &T, bool &PRO, int &TAG)
 
 int launch_cycle0(const Cycle0Launch &d)
 {
+    if (d.out_interleaved) {
+        if (!c0_is_out3(d) || !d.jobs || d.njobs < 1 || d.njobs > (int)ImageJobs::MAX || d.Uin.C != 3 * d.njobs) return -1;
+        ImageJobs t{};
+        for (int i = 0; i < d.njobs; ++i) t.j[i] = d.jobs[i];
+        const int blocks = cycle0_blocks(d.Uin.W, d.Uin.H, d.njobs, 2);      // one workgroup per (member, tile); three maxima each
+        hipLaunchKernelGGL((k_cycle0<2, C0_NW, C0_R, true, false, false, C0_OUT3_TAG, ImageJobs>), dim3(blocks), dim3(C0_NW * 64), 0, d.s, d.Uin, d.Uout, d.F, d.Fc,
+                           d.E, d.g, d.partial, d.comp, d.bands, d.lm, d.sat, d.rag, 0, t);
+        return 3 * blocks;
+    }
     const Cycle0Form *f = c0_find(d);
     if (!f) return -1;
     const int blocks = cycle0_blocks(d.Uin.W, d.Uin.H, d.Uin.C, f->T);

@@ -282,6 +282,15 @@ int sc_hip_edit_counts(void *p, int counts[2])
     return SC_OK;
 }
 
+int sc_hip_bytes_writer(void *p)
+{
+    Instance *I = get(p);
+    if (!I) return SC_ERR_BAD_ARG;
+    const int w = I->bytes_writer;
+    I->bytes_writer = 0;
+    return w;
+}
+
 int sc_hip_field_load(void *p, int W, int H, int C, const float *U, const float *lap)
 {
     Instance *I = get(p);
@@ -522,7 +531,7 @@ int sc_hip_cycle0_form(const int *facts, int index, int form[3])
         static const RagMember some_class{};
         Cycle0Launch d;
         d.sweeps = facts[0]; d.prolong = facts[1]; d.f_half = facts[2]; d.u_half = facts[3]; d.q16_in = facts[4]; d.q16_out = facts[5];
-        d.final_cycle = facts[6]; d.out_bytes = facts[7]; d.composed = facts[8]; d.l1_half = facts[9]; d.timing = facts[10];
+        d.final_cycle = facts[6]; d.out_bytes = (facts[7] & 1) != 0; d.out_interleaved = (facts[7] & 2) != 0; d.composed = facts[8]; d.l1_half = facts[9]; d.timing = facts[10];
         d.bands = facts[11] ? &some_bands : nullptr; d.rag = facts[12] ? &some_class : nullptr;
         rc = cycle0_form(d, T, PRO, TAG) ? 0 : -1;
     } else if ((rc = cycle0_form_at(index, T, PRO, TAG)) <= index || index < 0) {

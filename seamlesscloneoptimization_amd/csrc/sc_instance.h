@@ -179,6 +179,7 @@ struct Instance {
     DevBuf d_U0, d_U1, d_F;
     Field U0, U1, F;      // current views into the buffers above
     bool result_in_U1 = false;
+    int bytes_writer = 0;                  // sc_hip_bytes_writer (which clears it): judged bytes left bit 0 planar + a splice launch, bit 1 interleaved from the judged launch
     bool out_direct = false;               // the last solve wrote output bytes from its last cycle: result(I) is the iterate before it, not the solution
     bool f_half = false;      // F currently holds float16 values (written by the pre-process for the fused multigrid path)
     bool u_half = false;      // ... and so does the initial field U0 until the first cycle has consumed it
@@ -274,6 +275,12 @@ struct CallScope {
 
 // a superseded launch form asked for (SC_FLAG_LEGACY_PATHS + sc_solver_opts.legacy_paths)
 inline bool legacy_path(const sc_solver_opts &o, int which) { return (o.flags & SC_FLAG_LEGACY_PATHS) && (o.legacy_paths & which); }
+// The judged bytes launch of a same-size group writes the destinations itself (k_cycle0 with C0_OUT3, sc_cycle0.hip) from this many
+// (member, level-0 tile) workgroups on; below, and for size classes, groups of more than ImageJobs::MAX members and single clones, it
+// leaves planar bytes and a splice launch follows.  The cut is measured (profiles/out3_threshold.txt): from 200 on -- two
+// members at 1024^2, the smallest group measured -- the new form is never slower than the splice beyond the runs' spread, and it gains from
+// 720 on (two members at 2048^2: 1.4 %; sixteen: 2.8 %).  Nothing smaller was measured: it keeps the splice.
+constexpr long SC_OUT3_MIN_TILES = 200;
 
 // internal return code of a solve (never crosses the C ABI): a 16-bit fixed-point store saturated, no output was written;
 // solve_step repeats the pre-process and the solve with Instance::force_float_field set

@@ -456,10 +456,27 @@ static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget
         if (s.bands) d.bands = bands;
         if (s.lm) d.lm = early_lm;
         if (s.sat) d.sat = sat;
+        // The judged bytes of a same-size group (no size class, one table of jobs): the launch writes the members' destinations itself where
+        // that form exists and the grid is large enough to pay for workgroups of three-fold length; it is given the members' jobs (their
+        // guards) and the saturation word, the splice's two tests, and no splice launch follows.
+        bool interleaved = false;
+        if (s.out_bytes) {
+            const SolveTarget &to = I->spec_post.to;
+            if (to.group && !d.rag && to.group->size() <= (size_t)ImageJobs::MAX && to.group->size() * 3 == (size_t)I->F.C && (*to.group)[0].W == 0 &&
+                !legacy_path(o, SC_LEGACY_SPLICE_LAUNCH)) {
+                const long tiles = (long)cycle0_blocks(I->F.W, I->F.H, (int)to.group->size(), s.sweeps);
+                Cycle0Launch d3 = d;
+                d3.out_interleaved = true; d3.jobs = to.group->data(); d3.njobs = (int)to.group->size(); d3.sat = sat;
+                int T3, TAG3;
+                bool PRO3;
+                if ((tiles >= SC_OUT3_MIN_TILES || legacy_path(o, SC_FORCE_INTERLEAVED_OUT)) && cycle0_form(d3, T3, PRO3, TAG3)) { d = d3; interleaved = true; }
+            }
+        }
         const int nb = launch_cycle0(d);
         if (s.out_bytes && nb <= 0) { verdict = VERDICT_NO_FORM; continue; }
         if (s.prolong ? nb <= 0 : nb < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
         const Field Q = I->result_in_U1 ? I->U0 : I->U1;      // (where a bytes form left its bytes)
+        if (s.out_bytes) I->bytes_writer |= interleaved ? 2 : 1;
         if (!s.out_bytes) I->result_in_U1 = !I->result_in_U1;
         if (s.kind == FUSED_FIRST) {
             if (I->rag.dev && I->rag.ready_pending) {      // a size class: its zeroed coarse planes and tables were made on the second stream beside everything up to here
@@ -495,6 +512,7 @@ static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget
         if (s.out_bytes)
             rc = correction_maxima(I, maxima, S.cyc + 1, nb, nb_prev, part_now, [&]() -> int {
                     const SolveTarget &to = I->spec_post.to;
+                    if (interleaved) return SC_OK;      // the judged launch wrote the destinations itself
                     if (!to.group) launch_splice_planar(Q, to.org, to.step, I->stream, I->guard, sat);
                     else launch_splice_planar_group(Q, to.group->data(), (int)to.group->size(), I->stream, sat);
                     return SC_OK;

@@ -104,6 +104,12 @@ def main():
         mask[9:-11, 7:-5] = 255
         out = inst.edit(inst.edit_params(capi.SC_EDIT_COLOR_CHANGE, red_mul=1.5, green_mul=0.7, blue_mul=1.1), img, mask, allow_not_converged=True)
         emit("colorChange 203x141", out.tobytes(), inst.info())
+        # a same-size group whose judged launch may write the interleaved bytes itself (C0_OUT3): by the default rule, forced, and through the splice launch
+        for oname, bit in (("defaults", 0), ("forced_interleaved", getattr(F, "SC_FORCE_INTERLEAVED_OUT", None)), ("legacy_splice", getattr(F, "SC_LEGACY_SPLICE_LAUNCH", None))):
+            if bit is None:      # (--root: a build from before these switches)
+                continue
+            configure(inst, dict(legacy_paths=bit), F.SC_FLAG_LEGACY_PATHS if bit else 0)
+            batch(inst, "batch 16 x 470x300 %s" % oname, [(470, 300)] * 16, 70)
     finally:
         inst.destroy()
 
