@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
-import periodic_np
+import direct_np
 import wls_np
 import weighted_np
 
@@ -77,7 +77,7 @@ def energy(sides, periodic, p, q, eps_g, eps_d, weight, cx, cy, gx, gy, data, u)
     shape = w.shape
     H, W = shape[:2]
     lx, ly = wls_np.live_links(sides, periodic, H, W)
-    unk = ~periodic_np.dirichlet_mask(sides, periodic, H, W)
+    unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
     uu = _hwc(np.asarray(u, np.float64))
     with np.errstate(invalid="ignore"):
         tx, ty = link_residuals(uu, gx, gy, np.float64)
@@ -143,7 +143,7 @@ def irls_f32(sides, periodic, p, q, eps_g, eps_d, weight, cx, cy, gx, gy, data, 
     H, W, C = w.shape
     b_img = _start_image(sides, periodic, boundary, w.shape)
     blk = wls_np.unknowns(sides, periodic, H, W)
-    unk = ~periodic_np.dirichlet_mask(sides, periodic, H, W)
+    unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
     sx, sy = _ones_if_none(cx, w.shape), _ones_if_none(cy, w.shape)
     lap = wls_np.divergence(sides, periodic, sx, sy, gx, gy)
     u0, it, _ = wls_np.pcg_f32(sides, periodic, w, sx, sy, d, lap, b_img, tol=tol, max_iters=max_iters)

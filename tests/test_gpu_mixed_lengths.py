@@ -3,13 +3,16 @@ Dirichlet end paired with a free end can get wrong, along x and along y, both or
 cut, at its size limits (the GPU side of tests/test_mixed_host.py).
 
 Float32 transforms are held to the float32 restatement on the same input -- measured <= max(FACTOR x solve_f32's, FLOOR) for RES and
-ERR -- and double transforms to float32 ulps: tests/mixed_bounds.py says what the quantities are and where the constants come from.
+ERR -- and double transforms to float32 ulps: tests/direct_bounds.py says what the quantities are and where the constants come from.
 Lines MIXLEN / MIXCUT carry the measured values beside the restatement's."""
 import numpy as np
 import pytest
 
-import mixed_np
-from mixed_bounds import LENGTHS, STRIP32, STRIP64, Yardstick, length_cases, rough_inputs, smooth_input
+import direct_np as dn
+from direct_bounds import MIXED, rough_inputs, smooth_input
+from direct_bounds import MIXED_LENGTHS as LENGTHS, MIXED_STRIP32 as STRIP32, MIXED_STRIP64 as STRIP64, mixed_length_cases as length_cases
+
+Yardstick = MIXED.yardstick
 
 pytestmark = pytest.mark.gpu
 
@@ -32,9 +35,9 @@ def configure(inst, prec, method=capi.SC_METHOD_FFT):
 def solve_and_check(inst, sides, what, gx, gy, b, precs, tag, fails, laplacian=True):
     """One input under each precision: GUIDANCE (and LAPLACIAN fed numpy's divergence: the same bits), RES / ERR against the yardstick,
     the Dirichlet lines.  Appends to fails; returns {prec: (err, res)} and the yardstick."""
-    lap = mixed_np.divergence(gx, gy)
-    y = Yardstick(sides, 0.0, None, lap, b)
-    known = mixed_np.dirichlet_mask(sides, *b.shape[:2])
+    lap = dn.divergence(gx, gy)
+    y = Yardstick(sides, "", 0.0, None, lap, b)
+    known = dn.dirichlet_mask(sides, "", *b.shape[:2])
     got = {}
     for prec in precs:
         configure(inst, prec)
@@ -72,10 +75,10 @@ def test_the_walk_covers_what_it_says():
     ns = {c[0] for c in CASES}
     assert ns == set(LENGTHS) | {STRIP32, STRIP64}
     for n in ns:
-        kinds = {(axis, mixed_np.axis_kinds(sides)) for m, axis, sides, _, _, _ in CASES if m == n}
+        kinds = {(axis, dn.axis_kinds(sides)) for m, axis, sides, _, _, _ in CASES if m == n}
         for axis in "xy":
             walked = {k[0] if axis == "x" else k[1] for a, k in kinds if a == axis}
-            assert walked == {mixed_np.DN, mixed_np.ND}, (n, axis)
+            assert walked == {dn.DN, dn.ND}, (n, axis)
     assert all(("f64" in p) == (n <= STRIP64) for n, _, _, _, _, p in CASES)
 
 

@@ -1,5 +1,5 @@
 """GPU checks of the Neumann option of the Poisson solver (SC_POISSON_NEUMANN through sc_hip_poisson and sc_hip_poisson_device) against
-the test side's restatement (tests/neumann_np.py) on the same float32 inputs: reconstruction from forward differences and random
+the test side's restatement (tests/direct_np.py) on the same float32 inputs: reconstruction from forward differences and random
 guidance fields under every method that serves the option, the LAPLACIAN and GUIDANCE forms, the mean anchor, layouts and guard bands,
 batches, the refused methods and sizes, and the instance's state afterwards.  R = max |u_exact|.
 
@@ -11,7 +11,7 @@ profiles/neumann_probe.json), rounded up to one digit: the error is a sum of ~n 
 lowest modes along the long side, not a worst case, and it varies fourfold from seed to seed at that size (1.6e-3 .. 6.3e-3 R over
 four images; every other size stays below 1.7e-3 R) -- the margin is for other seeds and runtime versions.  DESIGN.md section 4 says
 which step loses the digits.  The mean: 1e-6 R per channel under both.  Beside these, the reconstruction test holds the residual
-ratio and the error to the float32 restatement on the same input (tests/neumann_bounds.py): the 3e-2 R above lets a wrong
+ratio and the error to the float32 restatement on the same input (tests/direct_bounds.py): the 3e-2 R above lets a wrong
 coefficient through."""
 from __future__ import annotations
 
@@ -22,11 +22,12 @@ pytestmark = pytest.mark.gpu
 
 from seamlesscloneoptimization_amd import capi  # noqa: E402
 
-import neumann_np  # noqa: E402
+import direct_np as dn  # noqa: E402
 import poisson_np  # noqa: E402
-from neumann_bounds import Yardstick  # noqa: E402
+from direct_bounds import NEUMANN  # noqa: E402
 
 NEU = capi.SC_POISSON_NEUMANN
+Yardstick = NEUMANN.yardstick
 METHODS = {
     "auto": (capi.SC_METHOD_AUTO, 0),
     "fft32": (capi.SC_METHOD_FFT, 0),
@@ -64,16 +65,16 @@ def test_reconstruction_and_random_guidance_against_the_restatement(inst, W, H):
     for C in (1, 2, 3, 4):
         rng = np.random.default_rng(W * 7 + H * 13 + C)
         img = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-        fx, fy = neumann_np.forward_differences(img)
+        fx, fy = dn.forward_differences(img)
         b = rng.uniform(-100, 400, (H, W, C)).astype(np.float32)
         gx = rng.normal(0, 20, (H, W, C)).astype(np.float32)
         gy = rng.normal(0, 20, (H, W, C)).astype(np.float32)
         for what, ax, ay, bb in (("reconstruction", fx, fy, img), ("random", gx, gy, b), ("random, no boundary", gx, gy, None)):
-            want = neumann_np.solve_guidance(ax, ay, bb)
+            want = dn.solve_free(dn.divergence(ax, ay), bb)
             R = float(np.abs(want).max())
-            mean = neumann_np.mean_of(bb) if bb is not None else np.zeros(C)
-            lap = neumann_np.divergence(ax, ay)
-            yard = Yardstick(lap, None if bb is None else mean)          # RES and ERR against the float32 restatement (neumann_bounds.py)
+            mean = dn.mean_of(bb) if bb is not None else np.zeros(C)
+            lap = dn.divergence(ax, ay)
+            yard = Yardstick("lrtb", "", 0.0, None, lap, bb)          # RES and ERR against the float32 restatement (direct_bounds.py)
             for name in methods_for(W, H):
                 configure(inst, *METHODS[name])
                 out = inst.poisson(bb, gx=ax, gy=ay, neumann=True)
@@ -99,18 +100,18 @@ def test_a_constant_added_to_lap_is_projected_out(inst, name):
     roundings reach the other coefficients -- before the (0, 0) coefficient is dropped."""
     H, W, C = 200, 300, 3
     rng = np.random.default_rng(12)
-    lap = neumann_np.divergence(rng.normal(0, 20, (H, W, C)).astype(np.float32), rng.normal(0, 20, (H, W, C)).astype(np.float32))
+    lap = dn.divergence(rng.normal(0, 20, (H, W, C)).astype(np.float32), rng.normal(0, 20, (H, W, C)).astype(np.float32))
     shifted = (lap + np.float32(3.0)).astype(np.float32)
     b = rng.uniform(-100, 400, (H, W, C)).astype(np.float32)
     configure(inst, *METHODS[name])
     for rhs in (lap, shifted):
-        want = neumann_np.solve_laplacian(rhs, b)
+        want = dn.solve_free(rhs, b)
         R = float(np.abs(want).max())
         out = inst.poisson(b, lap=rhs, neumann=True)
         assert np.abs(out.astype(np.float64) - want).max() <= BOUND[name] * R
-        assert np.abs(out.astype(np.float64).mean(axis=(0, 1)) - neumann_np.mean_of(b)).max() <= MEAN_BOUND * R
+        assert np.abs(out.astype(np.float64).mean(axis=(0, 1)) - dn.mean_of(b)).max() <= MEAN_BOUND * R
     # the two right-hand sides differ by the constant and by float32 rounding only: so do the exact answers
-    assert np.abs(neumann_np.solve_laplacian(shifted, b) - neumann_np.solve_laplacian(lap, b)).max() <= 1e-5 * R
+    assert np.abs(dn.solve_free(shifted, b) - dn.solve_free(lap, b)).max() <= 1e-5 * R
 
 
 @pytest.mark.parametrize("name", list(METHODS))
@@ -286,7 +287,7 @@ def test_batches_equal_their_solo_runs_bit_for_bit(inst, name, n, H, W, C):
     for k, (b, gx, gy) in enumerate(ps):
         solo = inst.poisson(b, gx=gx, gy=gy, neumann=True)
         assert np.array_equal(outs[k], solo), k
-    want = neumann_np.solve_guidance(ps[1][1], ps[1][2], ps[1][0])          # (a member without boundary)
+    want = dn.solve_free(dn.divergence(ps[1][1], ps[1][2]), ps[1][0])          # (a member without boundary)
     assert ps[1][0] is None and np.abs(outs[1] - want).max() <= BOUND[name] * np.abs(want).max()
 
 
@@ -305,7 +306,7 @@ def test_batch_with_bad_jobs(inst):
         assert np.all(outs[k] == -3.5), k                # skipped: never written
     for k in (0, 2, 4):
         b, gx, gy = ps[k]
-        want = neumann_np.solve_guidance(gx, gy, b)
+        want = dn.solve_free(dn.divergence(gx, gy), b)
         assert np.abs(outs[k] - want).max() <= BOUND["auto"] * np.abs(want).max(), k
 
 
@@ -358,7 +359,7 @@ def test_double_transforms_stop_at_4096_per_side(inst):
 def test_host_call_reports_stage_times(inst):
     rng = np.random.default_rng(2)
     b = rng.uniform(-50, 300, (500, 600, 3)).astype(np.float32)
-    gx, gy = neumann_np.forward_differences(b)
+    gx, gy = dn.forward_differences(b)
     configure(inst, capi.SC_METHOD_AUTO)
     inst.poisson(b, gx=gx, gy=gy, neumann=True)
     i = inst.info()
@@ -410,16 +411,16 @@ def test_poisson_solve_functions():
     import seamlesscloneoptimization_amd as pkg
     rng = np.random.default_rng(4)
     img = rng.uniform(-50, 300, (90, 120, 3)).astype(np.float32)
-    gx, gy = neumann_np.forward_differences(img)
+    gx, gy = dn.forward_differences(img)
     R = float(np.abs(img).max())
     out = pkg.poisson_solve(img, gx, gy, neumann=True)
     assert np.abs(out - img).max() <= BOUND["auto"] * R
     zero = pkg.poisson_solve(None, gx, gy, neumann=True, method=capi.SC_METHOD_FFT, flags=capi.SC_FLAG_FFT_FP64)
-    assert np.abs(zero.astype(np.float64) - (img - neumann_np.mean_of(img))).max() <= 1e-5 * R      # (img's own float32 differences)
+    assert np.abs(zero.astype(np.float64) - (img - dn.mean_of(img))).max() <= 1e-5 * R      # (img's own float32 differences)
     two = pkg.poisson_solve_batch([img, None], [gx, gx], [gy, gy], neumann=True)
     assert np.array_equal(two[0], out)
     assert np.array_equal(two[1], pkg.poisson_solve(None, gx, gy, neumann=True))
-    lap = neumann_np.divergence(gx, gy)
+    lap = dn.divergence(gx, gy)
     one = pkg.poisson_solve_batch([img], laplacians=[lap], neumann=True)[0]
     assert np.array_equal(one, out)
     out2 = pkg.poisson_solve(img[:, :, 0], gx[:, :, 0].copy(), gy[:, :, 0].copy(), neumann=True)      # 2-D arrays are one channel

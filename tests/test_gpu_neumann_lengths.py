@@ -3,16 +3,18 @@ sides of every launch-shape cut, through the table cache with both kinds, at its
 (the GPU side of tests/test_neumann_lengths_host.py).
 
 Float32 transforms are held to the float32 restatement on the same input -- measured <= max(FACTOR x solve_f32's, FLOOR) for the
-residual ratio RES and the error ERR -- and double transforms to float32 ulps: tests/neumann_bounds.py says what the quantities
+residual ratio RES and the error ERR -- and double transforms to float32 ulps: tests/direct_bounds.py says what the quantities
 are and where the constants come from.  The older bounds of tests/test_gpu_neumann.py (3e-2 R, 1e-6 R, the mean) hold as well.
 Lines NEULEN / NEULOW / NEUCUT / NEULIM carry the measured values beside the restatement's."""
 import numpy as np
 import pytest
 
-import neumann_np
-from neumann_bounds import Yardstick
+import direct_np as dn
+from direct_bounds import NEUMANN
 from test_direct_lengths_host import fft_M
 from test_neumann_lengths_host import JOBS_MAX, mean_parts, neumann_classes, tiny
+
+Yardstick = NEUMANN.yardstick
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +41,7 @@ def _rough(W, H, C, seed):
     """[(name, gx, gy, boundary)]: the reconstruction of a white-noise image, and a random guidance field with a random boundary"""
     rng = np.random.default_rng(seed)
     img = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-    fx, fy = neumann_np.forward_differences(img)
+    fx, fy = dn.forward_differences(img)
     b = rng.uniform(-100, 400, (H, W, C)).astype(np.float32)
     gx = rng.normal(0, 20, (H, W, C)).astype(np.float32)
     gy = rng.normal(0, 20, (H, W, C)).astype(np.float32)
@@ -49,9 +51,9 @@ def _rough(W, H, C, seed):
 def _solve_and_check(inst, gx, gy, b, precs, tag, fails, rough=True, laplacian=True, old=True):
     """One input under each precision: GUIDANCE (and LAPLACIAN fed numpy's divergence: the same bits), RES / ERR against the
     yardstick, the older bounds.  Appends to fails; returns {prec: (err, res)} and the yardstick."""
-    lap = neumann_np.divergence(gx, gy)
-    mean = neumann_np.mean_of(b) if b is not None else None
-    y = Yardstick(lap, mean)
+    lap = dn.divergence(gx, gy)
+    mean = dn.mean_of(b) if b is not None else None
+    y = Yardstick("lrtb", "", 0.0, None, lap, b)
     got = {}
     for prec in precs:
         _configure(inst, prec)
@@ -116,8 +118,8 @@ def test_low_modes_on_smooth_images(inst):
     print("\nNEULOW W x H | f32 ERR (x restatement) ...")
     for W, H in _low_mode_sizes():
         C = 3 if W * H < 1 << 20 else 2
-        sm = neumann_np.smooth_image(H, W, C, seed=W + 3 * H)
-        fx, fy = neumann_np.forward_differences(sm)
+        sm = dn.smooth_image(H, W, C, seed=W + 3 * H)
+        fx, fy = dn.forward_differences(sm)
         precs = ("f32", "f64") if max(W, H) <= 4096 else ("f32",)
         got, y = _solve_and_check(inst, fx, fy, sm, precs, (W, H, "smooth"), fails, rough=False)
         print("NEULOW %4dx%-4d C=%d | %s" % (W, H, C, _fmt(got, y)))
@@ -182,7 +184,7 @@ def test_batches_above_the_cut_equal_their_solo_runs(inst, m, W, H, C, prec):
     outs, info = _batch_against_solo(inst, ps, prec)
     assert info.method == capi.SC_METHOD_FFT and info.group_members == m
     b, gx, gy = ps[m - 1]                                   # the last member (the second chunk's at 17) against the yardstick
-    y = Yardstick(neumann_np.divergence(gx, gy), None if b is None else neumann_np.mean_of(b))
+    y = Yardstick("lrtb", "", 0.0, None, dn.divergence(gx, gy), b)
     bad, err, res = y.check(outs[m - 1], prec == "f64", prec == "f32")          # (random guidance: no RES bound in double)
     assert not bad, (bad, err, res)
 
@@ -208,8 +210,8 @@ def test_chunks_of_16_members_and_the_mean_parts(inst, H, C):
             if C == 4 and m == 49:
                 assert per == 48 and last == 1              # the call crossed SC_POISSON_MAX_PLANES: a chunk of 48 and one of 1
             for k, (b, gx, gy) in enumerate(ps):
-                mean = np.zeros(C) if b is None else neumann_np.mean_of(b)
-                want = neumann_np.solve_exact(neumann_np.divergence(gx, gy), mean)
+                mean = np.zeros(C) if b is None else dn.mean_of(b)
+                want = dn.solve_free(dn.divergence(gx, gy), b)
                 R = float(np.abs(want).max())
                 got = outs[k].astype(np.float64)
                 assert np.abs(got.mean(axis=(0, 1)) - mean).max() <= MEAN_BOUND * R, (m, k, prec, b is None)
@@ -378,7 +380,7 @@ def test_padding_and_the_unused_float_are_never_read(inst, kind, prec):
     b = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
     gx = rng.normal(0, 10, (H, W, C)).astype(np.float32)
     gy = rng.normal(0, 10, (H, W, C)).astype(np.float32)
-    lap = neumann_np.divergence(gx, gy)
+    lap = dn.divergence(gx, gy)
     _configure(inst, prec)
     ref = inst.poisson(b, gx=gx, gy=gy, neumann=True)
     assert np.isfinite(ref).all()

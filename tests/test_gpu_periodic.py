@@ -1,11 +1,13 @@
 """The float32 Poisson and screened solves with periodic axes (SC_POISSON_PERIODIC_X / _Y) on the GPU: the nine combinations against the
-float64 restatement (tests/periodic_np.py), the identity and what is never read, the singular combinations, cyclic shifts, lengths 2
-and 3, layouts, batches, refusals, the instance afterwards and make_tileable.  Bounds: tests/periodic_bounds.py."""
+float64 restatement (tests/direct_np.py), the identity and what is never read, the singular combinations, cyclic shifts, lengths 2
+and 3, layouts, batches, refusals, the instance afterwards and make_tileable.  Bounds: tests/direct_bounds.py."""
 import numpy as np
 import pytest
 
-import periodic_np as pn
-from periodic_bounds import Yardstick
+import direct_np as pn
+from direct_bounds import PERIODIC
+
+Yardstick = PERIODIC.yardstick
 
 pytestmark = pytest.mark.gpu
 

@@ -3,13 +3,16 @@ transform of a periodic axis can get wrong, along x and along y, beside every ki
 side of tests/test_periodic_host.py).
 
 Float32 transforms are held to the float32 restatement on the same input -- measured <= max(FACTOR x solve_f32's, FLOOR) for RES and
-ERR -- and double transforms to float32 ulps: tests/periodic_bounds.py says what the quantities are and where the constants come from.
+ERR -- and double transforms to float32 ulps: tests/direct_bounds.py says what the quantities are and where the constants come from.
 Lines PERLEN carry the measured values beside the restatement's."""
 import numpy as np
 import pytest
 
-import periodic_np as pn
-from periodic_bounds import LENGTHS, OTHER_KINDS, STRIP32, STRIP64, Yardstick, length_cases, rough_inputs, smooth_input
+import direct_np as pn
+from direct_bounds import OTHER_KINDS, PERIODIC, rough_inputs, smooth_input
+from direct_bounds import PERIODIC_LENGTHS as LENGTHS, PERIODIC_STRIP32 as STRIP32, PERIODIC_STRIP64 as STRIP64, periodic_length_cases as length_cases
+
+Yardstick = PERIODIC.yardstick
 
 pytestmark = pytest.mark.gpu
 

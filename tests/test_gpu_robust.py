@@ -21,7 +21,7 @@ import pytest
 
 from seamlesscloneoptimization_amd import capi, seamless_clone
 
-import periodic_np
+import direct_np
 import robust_bounds as rb
 import robust_np
 import wls_np
@@ -161,7 +161,7 @@ def test_against_the_exact_rounds(inst, case):
     assert erel <= rb.ENERGY_REL, (erel, rb.ENERGY_REL)
     check_energies(y, energy)
     if wls_np.has_dirichlet(sides, periodic):
-        m = periodic_np.dirichlet_mask(sides, periodic, H, W)
+        m = direct_np.dirichlet_mask(sides, periodic, H, W)
         assert np.array_equal(out[m], a["boundary"][m])
 
 

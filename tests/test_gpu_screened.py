@@ -3,7 +3,7 @@
     (A - lam) u = lap - lam d,   lam > 0,   A the 5-point operator under a Dirichlet frame or reflecting at the border.
 
 1. identity: d = I, g = forward differences of I (boundary = I under a frame) gives back I, at every transform-length class.
-2. random inputs against the float64 restatement (tests/screened_np.py), both kinds and both boundaries; the LAPLACIAN form, given
+2. random inputs against the float64 restatement (tests/direct_np.py), both kinds and both boundaries; the LAPLACIAN form, given
    numpy's divergence in the documented order, returns the GUIDANCE form's bits.
 3. the large-lam limit: max |u - d| <= max |div g - A d| / lam (the maximum principle of lam - A).
 4. batches: every member equals its solo run bit for bit; chunks, tables of more than PoissonJobs::MAX members, a skipped member.
@@ -14,7 +14,7 @@
 Bounds.  Dirichlet and the identity (item 1): those of tests/test_gpu_poisson.py's bound() for the direct solves, restated here --
 max |out - want| <= 4e-3 R with float32 transforms, 1e-4 R with double ones, R = max |want|: screening only moves every eigenvalue
 away from zero (|eig - lam| >= |eig|, eig <= 0 < lam), so a bound the unscreened solve keeps holds a fortiori.  Neumann against the
-restatement: tests/screened_bounds.py (float32: a factor over the float32 restatement's own ERR and RES on the same input; double:
+restatement: tests/direct_bounds.py (float32: a factor over the float32 restatement's own ERR and RES on the same input; double:
 F64_ULPS float32 ulps)."""
 from __future__ import annotations
 
@@ -23,9 +23,16 @@ import pytest
 
 from seamlesscloneoptimization_amd import capi, seamless_clone
 
-import screened_bounds
-import screened_np
-from screened_np import DIRICHLET, NEUMANN
+import direct_np as dn
+import poisson_np
+from direct_bounds import SCREENED
+
+DIRICHLET, NEUMANN = "", "lrtb"          # the two boundary kinds as direct_np's sides
+
+
+def divergence(kind, gx, gy):
+    """the library's float32 right-hand side of a guidance field under this boundary kind (Dirichlet: 0 on the frame)"""
+    return (dn if kind == NEUMANN else poisson_np).divergence(np.asarray(gx, np.float32), np.asarray(gy, np.float32))
 
 pytestmark = pytest.mark.gpu
 
@@ -89,7 +96,7 @@ def test_identity_at_every_length_class(inst, neumann, prec):
     for W, H in identity_sizes(neumann):
         for C in (1, 3, 4):
             img = image(H, W, C, W * 7 + H * 13 + C)
-            gx, gy = screened_np.forward_differences(img)
+            gx, gy = dn.forward_differences(img)
             R = float(np.abs(img).max())
             for lam in LAMS:
                 out = inst.screened(img, gx=gx, gy=gy, lam=lam, boundary=None if neumann else img, neumann=neumann)
@@ -123,9 +130,9 @@ def test_random_inputs_against_the_restatement(inst, W, H):
         kind = NEUMANN if neumann else DIRICHLET
         for C, lam in ((1, 1e-3), (3, 0.1), (4, 10.0)):
             d, gx, gy, b = random_problem(H, W, C, W * 11 + H * 17 + C)
-            lap = screened_np.divergence(kind, gx, gy)
-            yard = screened_bounds.Yardstick(lam, d, lap) if neumann else None
-            want = yard.want if neumann else screened_np.solve_exact(kind, lam, d, lap, b)
+            lap = divergence(kind, gx, gy)
+            yard = SCREENED.yardstick(kind, "", lam, d, lap, None) if neumann else None
+            want = yard.want if neumann else dn.solve_exact(kind, "", lam, d, lap, b)
             R = float(np.abs(want).max())
             for prec in PREC:
                 configure(inst, capi.SC_METHOD_AUTO if prec == "fft32" and C == 3 else capi.SC_METHOD_FFT, PREC[prec])
@@ -153,7 +160,7 @@ def test_neither_laps_frame_nor_boundarys_interior_is_read_under_a_frame(inst):
     configure(inst)
     H, W, C = 45, 67, 3
     d, gx, gy, b = random_problem(H, W, C, 3)
-    lap = screened_np.divergence(DIRICHLET, gx, gy)
+    lap = divergence(DIRICHLET, gx, gy)
     ref = inst.screened(d, lap=lap, lam=0.3, boundary=b, neumann=False)
     inner = np.zeros((H, W, C), bool)
     inner[1:-1, 1:-1] = True
@@ -177,8 +184,8 @@ def test_large_lambda_stays_at_the_data(inst, neumann, lam):
         for W, H, C in ((37, 29, 1), (300, 200, 3), (723, 722, 4)):
             d, gx, gy, _ = random_problem(H, W, C, W + H + C)
             out = inst.screened(d, gx=gx, gy=gy, lam=lam, boundary=None if neumann else d, neumann=neumann)
-            div = screened_np.divergence(kind, gx, gy).astype(np.float64)
-            Ad = screened_np.operator(kind, 1.0, d) + d.astype(np.float64) * (1.0 if neumann else (np.pad(np.ones((H - 2, W - 2, C)), ((1, 1), (1, 1), (0, 0)))))
+            div = divergence(kind, gx, gy).astype(np.float64)
+            Ad = dn.operator(kind, "", 1.0, d) + d.astype(np.float64) * (1.0 if neumann else (np.pad(np.ones((H - 2, W - 2, C)), ((1, 1), (1, 1), (0, 0)))))
             limit = float(np.abs(div - Ad).max()) / lam
             R = float(np.abs(d).max())
             got = float(np.abs(out.astype(np.float64) - d).max())
@@ -245,7 +252,7 @@ def _batch(inst, problems, lam, neumann, layout_kind="hwc", tamper=None, guidanc
     for d, gx, gy, b in problems:
         kd = dev.add(flat(d, SENTINEL))
         kb = None if neumann else dev.add(flat(b, SENTINEL))
-        ins = (dev.add(flat(gx)), dev.add(flat(gy))) if guidance else (dev.add(flat(screened_np.divergence(kind, gx, gy))),)
+        ins = (dev.add(flat(gx)), dev.add(flat(gy))) if guidance else (dev.add(flat(divergence(kind, gx, gy))),)
         ko = kd if alias == "data" else kb if alias == "boundary" else dev.add(np.full(span, SENTINEL, np.float32))
         ids.append((ins, kd, kb, ko))
     dev.upload()
@@ -434,7 +441,7 @@ def test_sides_beyond_the_transforms_are_refused_and_write_nothing(inst):
         for neumann in (True, False):
             W = n + (0 if neumann else 2)
             img = image(5, W, 1, n)
-            gx, gy = screened_np.forward_differences(img)
+            gx, gy = dn.forward_differences(img)
             out = inst.screened(img, gx=gx, gy=gy, lam=0.1, boundary=None if neumann else img, neumann=neumann)
             assert float(np.abs(out.astype(np.float64) - img).max()) <= BOUND["fft64" if flags else "fft32"] * float(np.abs(img).max())
 
@@ -475,9 +482,9 @@ def test_gradient_filter_and_the_solve_functions():
             out = seamless_clone.gradient_filter(img, 1.0, lam, neumann=neumann, method=capi.SC_METHOD_FFT)
             assert out is not img and float(np.abs(out.astype(np.float64) - img).max()) <= BOUND["fft32"] * R, (neumann, lam)
     # gain 2, Neumann, lam = 0.5 against the restatement
-    gx, gy = screened_np.forward_differences(img)
+    gx, gy = dn.forward_differences(img)
     gx, gy = np.float32(2.0) * gx, np.float32(2.0) * gy
-    yard = screened_bounds.Yardstick(0.5, img, screened_np.divergence(NEUMANN, gx, gy))
+    yard = SCREENED.yardstick(NEUMANN, "", 0.5, img, divergence(NEUMANN, gx, gy), None)
     out = seamless_clone.gradient_filter(img, 2.0, 0.5)
     bad, err, res = yard.check(out, False)
     assert not bad, bad

@@ -1,5 +1,5 @@
 """CPU checks of the per-side free borders of the float32 Poisson solver (SC_POISSON_FREE_*): the test side's restatement
-(tests/mixed_np.py) against a dense assembly of the operator solved by np.linalg.solve, for all 16 side combinations with and without
+(tests/direct_np.py) against a dense assembly of the operator solved by np.linalg.solve, for all 16 side combinations with and without
 a data term; the host-only validation of sc_hip_poisson_check / sc_hip_screened_check with the bits (sizes per axis kind); the Python
 wrappers' free_sides argument (before any device is touched).  The sanitizer builds' new validation rows (csrc/sanitize_main.cpp) run
 under tests/test_host.py's `make sanitize` test."""
@@ -10,10 +10,8 @@ import pytest
 
 from seamlesscloneoptimization_amd import capi, seamless_clone
 
-import mixed_np
-import neumann_np
+import direct_np as dn
 import poisson_np
-import screened_np
 
 G, L = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN
 FL, FR, FT, FB = capi.SC_POISSON_FREE_LEFT, capi.SC_POISSON_FREE_RIGHT, capi.SC_POISSON_FREE_TOP, capi.SC_POISSON_FREE_BOTTOM
@@ -24,12 +22,12 @@ def bits(sides):
     return sum(BITS[ch] for ch in sides)
 
 
-def dense_operator(sides, H, W, lam):
+def dense_operator(sides, H, W, lam, periodic=""):
     """(A - lam) over the unknowns as a dense matrix, the known neighbours' coefficients as a second one: row by row from the definition
-    -- for each of the four neighbours of an unknown: an unknown (+1, -1 on the diagonal), a pixel of a Dirichlet line (+1 on its value,
-    -1 on the diagonal), or beyond a free side (nothing)."""
-    ys, xs = mixed_np.unknowns(sides, H, W)
-    known = mixed_np.dirichlet_mask(sides, H, W)
+    -- for each of the four neighbours of an unknown (beyond the end of a periodic axis: the pixel at the other end): an unknown (+1, -1
+    on the diagonal), a pixel of a Dirichlet line (+1 on its value, -1 on the diagonal), or beyond a free side (nothing)."""
+    ys, xs = dn.unknowns(sides, periodic, H, W)
+    known = dn.dirichlet_mask(sides, periodic, H, W)
     index = -np.ones((H, W), int)
     cells = [(y, x) for y in range(ys.start, ys.stop) for x in range(xs.start, xs.stop)]
     for i, (y, x) in enumerate(cells):
@@ -39,6 +37,10 @@ def dense_operator(sides, H, W, lam):
     for i, (y, x) in enumerate(cells):
         A[i, i] -= lam
         for yy, xx in ((y, x - 1), (y, x + 1), (y - 1, x), (y + 1, x)):
+            if "x" in periodic:
+                xx %= W
+            if "y" in periodic:
+                yy %= H
             if not (0 <= yy < H and 0 <= xx < W):
                 continue
             A[i, i] -= 1.0
@@ -49,69 +51,71 @@ def dense_operator(sides, H, W, lam):
     return A, K, cells
 
 
+def check_against_the_dense_system(sides, periodic, lam, H, W, rng, C=2):
+    """solve_exact on random float32 inputs against np.linalg.solve of the assembled system (a singular one: the mean-zero least-squares
+    solution for the right-hand side less its mean); the Dirichlet lines are boundary's, and the stencil applied directly agrees"""
+    lap = rng.normal(0, 20, (H, W, C)).astype(np.float32)
+    data = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
+    b = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
+    f = dn.rhs(sides, periodic, lam, data, lap).astype(np.float64)
+    A, K, cells = dense_operator(sides, H, W, float(np.float32(lam)), periodic)
+    u = dn.solve_exact(sides, periodic, lam, data, lap, b)
+    singular = dn.singular(sides, periodic, lam)
+    for c in range(C):
+        rhs = np.array([f[y, x, c] for y, x in cells]) - K @ b[:, :, c].astype(np.float64).reshape(-1)
+        got = np.array([u[y, x, c] for y, x in cells])
+        if singular:                                          # solvable for the right-hand side less its mean, up to a constant
+            rhs = rhs - rhs.mean()
+            want = np.linalg.lstsq(A, rhs, rcond=None)[0]
+            want -= want.mean()
+            assert abs(got.mean()) <= 1e-9 * max(1.0, np.abs(got).max())
+        else:
+            want = np.linalg.solve(A, rhs)
+        assert np.abs(got - want).max() <= 1e-9 * max(1.0, np.abs(want).max()), (sides, periodic, lam, H, W)
+    if not singular:
+        known = dn.dirichlet_mask(sides, periodic, H, W)
+        assert np.array_equal(u[known], b.astype(np.float64)[known])
+        r = dn.residual(sides, periodic, lam, u, data, lap)
+        assert np.abs(r).max() <= 1e-9 * max(1.0, np.abs(f).max(), np.abs(b).max())
+
+
 SHAPES = [(12, 14), (3, 3), (2, 3), (3, 2), (2, 2), (2, 9), (10, 2), (3, 7), (5, 4)]          # (H, W): up to 12 x 10 unknowns, down to 1 along an axis
 
 
 @pytest.mark.parametrize("lam", [0.0, 1e-3, 10.0])
-@pytest.mark.parametrize("sides", mixed_np.ALL_SIDES)
+@pytest.mark.parametrize("sides", dn.ALL_SIDES)
 def test_the_restatement_solves_the_densely_assembled_system(sides, lam):
     rng = np.random.default_rng(len(sides) * 7 + int(lam * 10))
     done = 0
     for H, W in SHAPES:
-        ys, xs = mixed_np.unknowns(sides, H, W)
+        ys, xs = dn.unknowns(sides, "", H, W)
         if ys.stop - ys.start < 1 or xs.stop - xs.start < 1:
             continue                                              # no unknown between two Dirichlet lines 2 pixels apart
         done += 1
-        C = 2
-        lap = rng.normal(0, 20, (H, W, C)).astype(np.float32)
-        data = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-        b = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-        f = mixed_np.rhs(sides, lam, data, lap).astype(np.float64)
-        A, K, cells = dense_operator(sides, H, W, float(np.float32(lam)))
-        u = mixed_np.solve_exact(sides, lam, data, lap, b)
-        singular = len(sides) == 4 and lam == 0.0
-        for c in range(C):
-            rhs = np.array([f[y, x, c] for y, x in cells]) - K @ b[:, :, c].astype(np.float64).reshape(-1)
-            got = np.array([u[y, x, c] for y, x in cells])
-            if singular:                                          # the Neumann problem: solvable for the right-hand side less its mean, up to a constant
-                rhs = rhs - rhs.mean()
-                want = np.linalg.lstsq(A, rhs, rcond=None)[0]
-                want -= want.mean()
-                assert abs(got.mean()) <= 1e-9 * max(1.0, np.abs(got).max())
-            else:
-                want = np.linalg.solve(A, rhs)
-            assert np.abs(got - want).max() <= 1e-9 * max(1.0, np.abs(want).max()), (sides, lam, H, W)
-        # the Dirichlet lines are boundary's, and the stencil applied directly agrees
-        known = mixed_np.dirichlet_mask(sides, H, W)
-        assert np.array_equal(u[known], b.astype(np.float64)[known])
-        if not singular:
-            r = mixed_np.residual(sides, lam, u, data, lap)
-            assert np.abs(r).max() <= 1e-9 * max(1.0, np.abs(f).max(), np.abs(b).max())
+        check_against_the_dense_system(sides, "", lam, H, W, rng)
     assert done >= 4
 
 
-@pytest.mark.parametrize("sides", mixed_np.ALL_SIDES)
-def test_the_restatement_is_the_earlier_ones_at_the_extremes_and_returns_an_image(sides):
+@pytest.mark.parametrize("sides", dn.ALL_SIDES)
+def test_the_restatement_returns_an_image_and_the_frame_is_the_oracles(sides):
     rng = np.random.default_rng(11)
     H, W, C = 29, 37, 2
     img = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-    gx, gy = mixed_np.forward_differences(img)
+    gx, gy = dn.forward_differences(img)
     gx[:, -1] = np.nan            # never read
     gy[-1] = np.nan
-    lap = mixed_np.divergence(gx, gy)
+    lap = dn.divergence(gx, gy)
     R = float(np.abs(img).max())
-    u = mixed_np.solve_exact(sides, 0.0, None, lap, img)
+    u = dn.solve_exact(sides, "", 0.0, None, lap, img)
     if len(sides) == 4:
         u = u + img.astype(np.float64).mean(axis=(0, 1))
     assert np.abs(u - img).max() <= 1e-5 * R                     # float32 differences of float32 pixels
-    us = mixed_np.solve_exact(sides, 0.5, img, lap, img)
+    us = dn.solve_exact(sides, "", 0.5, img, lap, img)
     assert np.abs(us - img).max() <= 1e-5 * R
-    u32 = mixed_np.solve_f32(sides, 0.5, img, lap, img)
+    u32 = dn.solve_f32(sides, "", 0.5, img, lap, img)
     assert u32.dtype == np.float32 and np.abs(u32 - img).max() <= 1e-3 * R
-    if sides == "":
-        assert np.abs(us - screened_np.solve_exact(screened_np.DIRICHLET, 0.5, img, poisson_np.divergence(gx, gy), img)).max() <= 1e-9 * R
-    if len(sides) == 4:
-        assert np.abs(us - screened_np.solve_exact(screened_np.NEUMANN, 0.5, img, neumann_np.divergence(gx, gy))).max() <= 1e-9 * R
+    if sides == "":               # the frame problem through the oracle's DST: an independent solve
+        assert np.abs(u - poisson_np.solve_exact(img, poisson_np.divergence(gx, gy))).max() <= 1e-9 * R
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 7, 40])
@@ -123,14 +127,14 @@ def test_the_half_frequency_sine_transform(n):
     assert np.abs(S @ S.T - (2 * n + 1) / 4.0 * np.eye(n)).max() <= 1e-12 * n
     T = -2.0 * np.eye(n) + np.eye(n, k=1) + np.eye(n, k=-1)
     T[n - 1, n - 1] = -1.0
-    assert np.abs(T @ S.T - S.T * mixed_np.axis_eigenvalues(mixed_np.DN, n)[None, :]).max() <= 1e-12
+    assert np.abs(T @ S.T - S.T * dn.axis_eigenvalues(dn.DN, n)[None, :]).max() <= 1e-12
     x = np.random.default_rng(n).normal(0, 1, (n, 3))
-    X = mixed_np._forward(mixed_np.DN, x, 0)
+    X = dn.forward(dn.DN, x, 0)
     assert np.abs(X - S @ x).max() <= 1e-12 * n
-    assert np.abs(mixed_np._inverse(mixed_np.DN, X, 0) - x).max() <= 1e-12 * n
-    Xr = mixed_np._forward(mixed_np.ND, x, 0)
+    assert np.abs(dn.inverse(dn.DN, X, 0) - x).max() <= 1e-12 * n
+    Xr = dn.forward(dn.ND, x, 0)
     assert np.abs(Xr - S @ x[::-1]).max() <= 1e-12 * n
-    assert np.abs(mixed_np._inverse(mixed_np.ND, Xr, 0) - x).max() <= 1e-12 * n
+    assert np.abs(dn.inverse(dn.ND, Xr, 0) - x).max() <= 1e-12 * n
 
 
 # ---- the host-only validation: these return SC_ERR_BAD_ARG without the feature
@@ -140,7 +144,7 @@ def _planar(cols, rows, channels=1):
 
 
 @pytest.mark.parametrize("kind", [G, L])
-@pytest.mark.parametrize("sides", mixed_np.ALL_SIDES[1:])
+@pytest.mark.parametrize("sides", dn.ALL_SIDES[1:])
 def test_the_checks_accept_every_combination_of_free_sides(sides, kind):
     assert capi.poisson_check(kind | bits(sides), 0.0, **_planar(37, 29, 3)) == capi.SC_OK
     assert capi.screened_check(kind | bits(sides), 0.5, **_planar(37, 29, 3)) == capi.SC_OK
@@ -156,7 +160,7 @@ def _axis_limits(free_lo, free_hi):
     return max(2, 1 + lines), 8192 + lines
 
 
-@pytest.mark.parametrize("sides", mixed_np.MIXED_SIDES)
+@pytest.mark.parametrize("sides", dn.MIXED_SIDES)
 def test_the_checks_know_the_size_limits_of_each_axis_kind(sides):
     kind = G | bits(sides)
     xlo, xhi = _axis_limits("l" in sides, "r" in sides)

@@ -1,12 +1,12 @@
-"""CPU side of tests/test_gpu_neumann_lengths.py: the float32 yardstick (neumann_np.solve_f32) is single precision throughout and
+"""CPU side of tests/test_gpu_neumann_lengths.py: the float32 yardstick (direct_np.solve_f32 of the problem ("lrtb", "")) is single precision throughout and
 stays where it was measured; the transform length classes of the Neumann solve (FftDim kind 1: n pixels, chirp of period 2n, the
 same fft_len as the DST kind); the launch-shape rules of direct_jobs_solve_t and k_poisson_mean mirrored in Python, with the sizes the GPU
 file puts on either side of each cut."""
 import numpy as np
 import pytest
 
-import neumann_np
-from neumann_bounds import err_and_res
+import direct_bounds
+import direct_np as dn
 from test_direct_lengths_host import fft_M, fft_max_M, fft_supported, length_classes
 
 TINY_BYTES = 4 << 20             # sc_fft.hip direct_jobs_solve_t: plane * sizeof(T) <= 4 MiB -> the plane is stored transposed, no transposes
@@ -38,10 +38,22 @@ def mean_part_rows(H):
     return [((i + 1) * H) // n - (i * H) // n for i in range(n)]
 
 
+def solve_exact(lap):
+    return dn.solve_exact("lrtb", "", 0.0, None, lap)
+
+
+def solve_f32(lap, order=dn.ROWS_FIRST):
+    return dn.solve_f32("lrtb", "", 0.0, None, lap, order=order)
+
+
+def err_and_res(u, lap, want):
+    return direct_bounds.err_and_res("lrtb", "", 0.0, u, None, lap, want, direct_bounds.NEUMANN.by_differences)
+
+
 def rough_case(W, H, C, seed):
     """white noise in [-50, 300] and the float32 divergence of its float32 forward differences"""
     img = np.random.default_rng(seed).uniform(-50, 300, (H, W, C)).astype(np.float32)
-    return img, neumann_np.divergence(*neumann_np.forward_differences(img))
+    return img, dn.divergence(*dn.forward_differences(img))
 
 
 # ------------------------------------------------------------------------------------------------------------ the yardstick
@@ -49,22 +61,22 @@ def test_solve_f32_is_single_precision_throughout():
     """float32 out, no float64 inside (the transforms assert their own dtypes as they run), and measurably less exact than the
     float64 solve: at 300 x 200 solve_exact leaves a residual below 1e-12, the float32 restatement one above 1e-8."""
     img, lap = rough_case(300, 200, 2, 3)
-    want = neumann_np.solve_exact(lap)
-    for x_first in (True, False):
-        u = neumann_np.solve_f32(lap, x_first=x_first)
+    want = solve_exact(lap)
+    for order in (dn.ROWS_FIRST, dn.COLUMNS_FIRST):
+        u = solve_f32(lap, order)
         assert u.dtype == np.float32 and u.shape == lap.shape
         e32, r32 = err_and_res(u, lap, want)
         e64, r64 = err_and_res(want, lap, want)
         assert r64 <= 1e-12 and e64 == 0.0
         assert 1e-8 <= r32 <= 1e-6 and 1e-7 <= e32 <= 1e-4, (e32, r32)
     for axis in (0, 1):
-        X = neumann_np._dct2_f32(lap[:, :, 0], axis)
-        assert X.dtype == np.float32 and neumann_np._idct2_f32(X, axis).dtype == np.float32
-        back = neumann_np._idct2_f32(X, axis)
+        X = dn.dct2(lap[:, :, 0], axis, True)
+        assert X.dtype == np.float32 and dn.idct2(X, axis, True).dtype == np.float32
+        back = dn.idct2(X, axis, True)
         assert np.abs(back - lap[:, :, 0]).max() <= 1e-5 * np.abs(lap).max()
-        assert np.abs(X - neumann_np._dct2(lap[:, :, 0].astype(np.float64), axis)).max() <= 1e-5 * np.abs(X).max()
+        assert np.abs(X - dn.dct2(lap[:, :, 0].astype(np.float64), axis)).max() <= 1e-5 * np.abs(X).max()
     m = np.array([3.0, -7.0])
-    assert np.abs(neumann_np.solve_f32(lap, m).astype(np.float64).mean(axis=(0, 1)) - m).max() <= 1e-4
+    assert np.abs((solve_f32(lap) + m.astype(np.float32)).astype(np.float64).mean(axis=(0, 1)) - m).max() <= 1e-4
 
 
 # (W, H): ERR measured for the float32 restatement on one white-noise image (the table of the issue this file answers)
@@ -79,9 +91,9 @@ def test_solve_f32_stays_where_it_was_measured(W, H):
     result), RES <= 1e-6 -- thin strips at 8192 included: the residual is not amplified by 1 / lambda_min.  One image per size (the
     table's own axis order, columns first): ERR at 8192 varies fourfold from image to image."""
     img, lap = rough_case(W, H, 1, W * 7 + H * 13 + 1)
-    want = neumann_np.solve_exact(lap)
-    e, r = err_and_res(neumann_np.solve_f32(lap, x_first=False), lap, want)
-    _, rx = err_and_res(neumann_np.solve_f32(lap), lap, want)
+    want = solve_exact(lap)
+    e, r = err_and_res(solve_f32(lap, dn.COLUMNS_FIRST), lap, want)
+    _, rx = err_and_res(solve_f32(lap), lap, want)
     print("solve_f32 %dx%d: ERR %.2e (table %.2e) RES %.2e / %.2e" % (W, H, e, MEASURED_ERR[(W, H)], r, rx))
     assert e <= max(2 * MEASURED_ERR[(W, H)], ULP), (W, H, e)
     assert r <= 1e-6 and rx <= 1e-6, (W, H, r, rx)
@@ -92,14 +104,14 @@ def test_smooth_inputs_are_where_the_restatement_is_exact(W, H):
     """The low-mode check's premise: the restatement's ERR on smooth_image's reconstruction is at least 20 times below its ERR on
     the rough image of the same size, in either axis order."""
     _, lap = rough_case(W, H, 1, W * 7 + H * 13 + 1)
-    sm = neumann_np.smooth_image(H, W, 1, 5)
+    sm = dn.smooth_image(H, W, 1, 5)
     assert sm.dtype == np.float32 and np.ptp(sm) > 10
-    slap = neumann_np.divergence(*neumann_np.forward_differences(sm))
-    want, swant = neumann_np.solve_exact(lap), neumann_np.solve_exact(slap)
-    for x_first in (True, False):
-        rough = err_and_res(neumann_np.solve_f32(lap, x_first=x_first), lap, want)[0]
-        smooth = err_and_res(neumann_np.solve_f32(slap, x_first=x_first), slap, swant)[0]
-        assert 20 * smooth <= rough, (W, H, x_first, smooth, rough)
+    slap = dn.divergence(*dn.forward_differences(sm))
+    want, swant = solve_exact(lap), solve_exact(slap)
+    for order in (dn.ROWS_FIRST, dn.COLUMNS_FIRST):
+        rough = err_and_res(solve_f32(lap, order), lap, want)[0]
+        smooth = err_and_res(solve_f32(slap, order), slap, swant)[0]
+        assert 20 * smooth <= rough, (W, H, order, smooth, rough)
 
 
 # -------------------------------------------------------------------------------------------------------- length classes

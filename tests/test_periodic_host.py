@@ -5,9 +5,9 @@ import ctypes
 import numpy as np
 import pytest
 
-import mixed_np
-import periodic_np as pn
+import direct_np as pn
 from seamlesscloneoptimization_amd import capi, seamless_clone
+from test_mixed_host import check_against_the_dense_system, dense_operator
 
 G, L = capi.SC_POISSON_GUIDANCE, capi.SC_POISSON_LAPLACIAN
 PX, PY = capi.SC_POISSON_PERIODIC_X, capi.SC_POISSON_PERIODIC_Y
@@ -50,38 +50,16 @@ def test_hartley_chirp_form(n):
 
 
 # ---- the restatement
-def dense_operator(sides, periodic, lam, H, W):
-    """(A - lam) over all H x W pixels as a matrix, rows of Dirichlet pixels zero"""
-    blk = pn.unknowns(sides, periodic, H, W)
-    unknown = np.zeros((H, W), bool)
-    unknown[blk] = True
-    A = np.zeros((H * W, H * W))
-    for y in range(H):
-        for x in range(W):
-            if not unknown[y, x]:
-                continue
-            q = y * W + x
-            for dx, dy in ((1, 0), (-1, 0), (0, 1), (0, -1)):
-                xx, yy = x + dx, y + dy
-                if "x" in periodic:
-                    xx %= W
-                if "y" in periodic:
-                    yy %= H
-                if 0 <= xx < W and 0 <= yy < H:          # beyond a free side: no term
-                    A[q, yy * W + xx] += 1.0
-                    A[q, q] -= 1.0
-            A[q, q] -= lam
-    return A
-
-
 @pytest.mark.parametrize("W,H", [(7, 5), (12, 9)])
 @pytest.mark.parametrize("sides,periodic", pn.COMBOS)
 def test_restatement(sides, periodic, W, H):
     rng = np.random.default_rng(W * H + len(sides))
     for lam in (0.0, 0.5):
         u = rng.normal(0, 10, (H, W, 1))
-        A = dense_operator(sides, periodic, float(np.float32(lam)), H, W)
-        assert np.allclose(pn.operator(sides, periodic, lam, u).reshape(-1), A @ u.reshape(-1), atol=1e-10)
+        A, K, cells = dense_operator(sides, H, W, float(np.float32(lam)), periodic)
+        Au = pn.operator(sides, periodic, lam, u)
+        assert np.allclose([Au[y, x, 0] for y, x in cells], A @ [u[y, x, 0] for y, x in cells] + K @ u.reshape(-1), atol=1e-10)
+        assert not Au[pn.dirichlet_mask(sides, periodic, H, W)].any()
         lap = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
         d = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
         b = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
@@ -99,18 +77,12 @@ def test_restatement(sides, periodic, W, H):
         assert s32.dtype == np.float32 and np.abs(s32 - sol).max() <= 1e-4 * np.abs(sol).max()
 
 
-@pytest.mark.parametrize("sides", mixed_np.ALL_SIDES)
-def test_restatement_without_periodic_is_mixed(sides):
-    W, H = 7, 5
-    rng = np.random.default_rng(len(sides))
-    lap = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
-    d = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
-    b = rng.normal(0, 20, (H, W, 2)).astype(np.float32)
+@pytest.mark.parametrize("sides,periodic", [(s, "") for s in pn.ALL_SIDES] + pn.COMBOS)
+def test_restatement_solves_the_dense_system(sides, periodic):
+    """every border combination, with and without a periodic axis, unscreened and screened, against np.linalg.solve"""
+    rng = np.random.default_rng(len(sides) + 10 * len(periodic))
     for lam in (0.0, 0.5):
-        a, m = pn.solve_exact(sides, "", lam, d, lap, b), mixed_np.solve_exact(sides, lam, d, lap, b)
-        assert np.abs(a - m).max() <= 1e-12 * max(1.0, np.abs(m).max())
-    gx, gy = rng.normal(0, 1, (H, W)).astype(np.float32), rng.normal(0, 1, (H, W)).astype(np.float32)
-    assert np.array_equal(pn.divergence(gx, gy, ""), mixed_np.divergence(gx, gy))
+        check_against_the_dense_system(sides, periodic, lam, 5, 7, rng)
 
 
 def test_wrapped_differences_and_divergence():

@@ -160,8 +160,8 @@ def test_energies_never_rise_for_p_1(border, q):
     assert len(u32) == 9 and max(its) < 400
     assert np.abs(u32[-1] - us[-1]).max() <= 2e-3 * a["range"]
     if wls_np.has_dirichlet(sides, periodic):
-        import periodic_np
-        m = periodic_np.dirichlet_mask(sides, periodic, 16, 21)
+        import direct_np
+        m = direct_np.dirichlet_mask(sides, periodic, 16, 21)
         assert np.array_equal(u32[-1][m], a["boundary"][m])
 
 

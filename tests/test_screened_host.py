@@ -1,6 +1,6 @@
 """CPU checks of the screened Poisson solve's public surface (sc_hip_screened_check, sc_hip_screened_device, sc_hip_screened): the
 exported symbols, the two structures against the header as a C compiler lays them out, the host-only validation, the test side's
-restatement (tests/screened_np.py) against the stencil, and the Python wrappers' argument checks, which run before any device is
+restatement (tests/direct_np.py, the frame and the Neumann problem with a data term) against the stencil and the dense system, and the Python wrappers' argument checks, which run before any device is
 touched."""
 from __future__ import annotations
 
@@ -13,7 +13,9 @@ import pytest
 
 from seamlesscloneoptimization_amd import capi, seamless_clone
 
-import screened_np
+import direct_np as dn
+import poisson_np
+from test_mixed_host import dense_operator
 from test_poisson_host import VALID
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,11 +99,13 @@ def test_screened_check_size_limits_of_each_boundary_kind():
     assert capi.load().sc_hip_screened_check(None, None) == capi.SC_ERR_BAD_ARG
 
 
-SIZES = {screened_np.NEUMANN: [(2, 2, 1), (2, 5, 2), (3, 3, 1), (7, 2, 1), (37, 29, 3), (64, 50, 4), (9, 130, 1)],
-         screened_np.DIRICHLET: [(3, 3, 1), (3, 17, 2), (19, 3, 1), (37, 29, 3), (64, 50, 4), (9, 130, 1)]}
+DIRICHLET, NEUMANN = "", "lrtb"          # the two boundary kinds of sc_hip_screened as direct_np's sides
+SIZES = {NEUMANN: [(2, 2, 1), (2, 5, 2), (3, 3, 1), (7, 2, 1), (37, 29, 3), (64, 50, 4), (9, 130, 1)],
+         DIRICHLET: [(3, 3, 1), (3, 17, 2), (19, 3, 1), (37, 29, 3), (64, 50, 4), (9, 130, 1)]}
+BOTH_KINDS = [pytest.param(DIRICHLET, id="dirichlet"), pytest.param(NEUMANN, id="neumann")]
 
 
-@pytest.mark.parametrize("kind", [screened_np.DIRICHLET, screened_np.NEUMANN])
+@pytest.mark.parametrize("kind", BOTH_KINDS)
 @pytest.mark.parametrize("lam", [1e-3, 0.1, 10.0, 1e4])
 def test_screened_np_solves_its_system(kind, lam):
     """float64: max residual / max rhs <= 1e-10, the frame is boundary's, for a random right-hand side, data term and boundary"""
@@ -110,20 +114,20 @@ def test_screened_np_solves_its_system(kind, lam):
         d = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
         lap = rng.normal(0, 40, (H, W, C)).astype(np.float32)
         b = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-        u = screened_np.solve_exact(kind, lam, d, lap, b)
-        f = np.abs(screened_np.rhs(kind, lam, d, lap)).max()
+        u = dn.solve_exact(kind, "", lam, d, lap, b)
+        f = np.abs(dn.rhs(kind, "", lam, d, lap)).max()
         # (Dirichlet: the frame's values are part of the system's right-hand side: measure against the larger of the two)
-        scale = max(f, np.abs(b).max()) if kind == screened_np.DIRICHLET else f
-        assert np.abs(screened_np.residual(kind, lam, u, d, lap)).max() <= 1e-10 * scale, (H, W, C)
-        if kind == screened_np.DIRICHLET:
+        scale = max(f, np.abs(b).max()) if kind == DIRICHLET else f
+        assert np.abs(dn.residual(kind, "", lam, u, d, lap)).max() <= 1e-10 * scale, (H, W, C)
+        if kind == DIRICHLET:
             for fr in (np.s_[0], np.s_[-1], np.s_[:, 0], np.s_[:, -1]):
                 assert np.array_equal(u[fr], b[fr].astype(np.float64))
         # the float32 restatement solves the same system to float32 rounding
-        u32 = screened_np.solve_f32(kind, lam, d, lap, b)
+        u32 = dn.solve_f32(kind, "", lam, d, lap, b)
         assert u32.dtype == np.float32 and np.abs(u32 - u).max() <= 1e-3 * np.abs(u).max(), (H, W, C)
 
 
-@pytest.mark.parametrize("kind", [screened_np.DIRICHLET, screened_np.NEUMANN])
+@pytest.mark.parametrize("kind", BOTH_KINDS)
 @pytest.mark.parametrize("lam", [1e-3, 0.1, 10.0])
 def test_screened_np_returns_the_image_for_its_own_gradients(kind, lam):
     """d = I, g = grad I (boundary = I): u = I, to 1e-10 max |I|, with every step in float64 (the float32 right-hand side's rounding
@@ -131,8 +135,8 @@ def test_screened_np_returns_the_image_for_its_own_gradients(kind, lam):
     rng = np.random.default_rng(5)
     for H, W, C in SIZES[kind]:
         img = rng.uniform(-50, 300, (H, W, C))
-        gx, gy = screened_np.forward_differences(img)
-        if kind == screened_np.NEUMANN:
+        gx, gy = dn.forward_differences(img)
+        if kind == NEUMANN:
             a = gx.copy(); a[:, -1] = 0
             b = np.zeros_like(gx); b[:, 1:] = gx[:, :-1]
             c = gy.copy(); c[-1] = 0
@@ -143,41 +147,33 @@ def test_screened_np_returns_the_image_for_its_own_gradients(kind, lam):
             lap[1:-1, 1:-1] = (gx[1:-1, 1:-1] - gx[1:-1, :-2]) + (gy[1:-1, 1:-1] - gy[:-2, 1:-1])
         # (A - lam) I = lap - lam I exactly in exact arithmetic: check the operator, then the solve through float64 transforms
         f64 = lap - float(np.float32(lam)) * img
-        r = screened_np.operator(kind, lam, img) - (f64 if kind == screened_np.NEUMANN else np.pad(f64[1:-1, 1:-1], ((1, 1), (1, 1), (0, 0))))
+        r = dn.operator(kind, "", lam, img) - (f64 if kind == NEUMANN else np.pad(f64[1:-1, 1:-1], ((1, 1), (1, 1), (0, 0))))
         assert np.abs(r).max() <= 1e-10 * np.abs(img).max() * max(1.0, lam), (H, W, C)
-        u = _solve64(kind, lam, f64, img)
+        if kind == DIRICHLET:
+            f64 = np.pad(f64[1:-1, 1:-1], ((1, 1), (1, 1), (0, 0)))
+        u = dn.solve_rhs(kind, "", lam, f64, img)
         assert np.abs(u - img).max() <= 1e-10 * np.abs(img).max(), (H, W, C)
-
-
-def _solve64(kind, lam, f64, boundary):
-    """screened_np.solve_exact's transforms on a float64 right-hand side"""
-    import neumann_np
-    H, W, C = f64.shape
-    den = screened_np._eig(kind, H, W) - float(np.float32(lam))
-    if kind == screened_np.NEUMANN:
-        out = np.empty_like(f64)
-        for c in range(C):
-            out[:, :, c] = neumann_np._idct2(neumann_np._idct2(neumann_np._dct2(neumann_np._dct2(f64[:, :, c], 0), 1) / den, 1), 0)
-        return out
-    out = boundary.copy()
-    g = f64[1:-1, 1:-1] - screened_np._frame_fold(boundary)
-    X = screened_np._dst1(screened_np._dst1(g, 0), 1) / den[:, :, None]
-    out[1:-1, 1:-1] = screened_np._dst1(screened_np._dst1(X, 1), 0) * (4.0 / ((W - 1.0) * (H - 1.0)))
-    return out
+        if H * W <= 37 * 29:          # small enough for it: the densely assembled system, solved by LAPACK
+            A, K, cells = dense_operator(kind, H, W, float(np.float32(lam)))
+            for c in range(C):
+                want = np.linalg.solve(A, np.array([f64[y, x, c] for y, x in cells]) - K @ img[:, :, c].reshape(-1))
+                assert np.abs(np.array([u[y, x, c] for y, x in cells]) - want).max() <= 1e-9 * np.abs(img).max(), (H, W, C)
+        else:                         # the stencil applied to the solve's answer
+            assert np.abs(dn.operator(kind, "", lam, u) - f64).max() <= 1e-10 * np.abs(img).max() * max(1.0, lam), (H, W, C)
 
 
 def test_screened_np_float32_forms_give_back_the_image():
     """the library's float32 forms (float32 divergence, float32 right-hand side): the image within float32 rounding"""
     rng = np.random.default_rng(6)
-    for kind in (screened_np.DIRICHLET, screened_np.NEUMANN):
+    for kind in (DIRICHLET, NEUMANN):
         for lam in (1e-3, 0.1, 10.0):
             img = rng.uniform(0, 255, (37, 29, 3)).astype(np.float32)
-            gx, gy = screened_np.forward_differences(img)
-            u = screened_np.solve_exact(kind, lam, img, screened_np.divergence(kind, gx, gy), img)
+            gx, gy = dn.forward_differences(img)
+            u = dn.solve_exact(kind, "", lam, img, (dn if kind == NEUMANN else poisson_np).divergence(gx, gy), img)
             assert np.abs(u - img).max() <= 1e-4 * 255, (kind, lam)
     # the right-hand side's order: the product is rounded before the subtraction
     lap, d, lam = np.float32(3.0000002), np.float32(1.0000001), np.float32(0.3)
-    f = screened_np.rhs(screened_np.NEUMANN, lam, np.full((2, 2), d), np.full((2, 2), lap))
+    f = dn.rhs(NEUMANN, "", lam, np.full((2, 2), d), np.full((2, 2), lap))
     assert f.dtype == np.float32 and f[0, 0] == np.float32(lap - np.float32(lam * d))
 
 

@@ -7,7 +7,7 @@ import pytest
 
 from seamlesscloneoptimization_amd import capi
 
-import periodic_np
+import direct_np
 import weighted_np
 import wls_bounds as lb
 import wls_np
@@ -45,7 +45,7 @@ def test_reference_iteration_against_the_exact_solve(border, skind):
     assert rel <= 1e-5 and iters <= 100, (iters, rel)
     assert np.abs(u - want).max() <= 2e-4 * np.abs(want).max()
     if b is not None:
-        m = periodic_np.dirichlet_mask(sides, periodic, 21, 16)
+        m = direct_np.dirichlet_mask(sides, periodic, 21, 16)
         assert np.array_equal(want[m], b[m].astype(np.float64)) and np.array_equal(u[m], b[m])
 
 
@@ -67,7 +67,7 @@ def test_unit_links_are_the_weighted_solve(border):
     assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
     gx, gy = (0.1 * np.random.default_rng(3).standard_normal((2,) + data.shape)).astype(np.float32)
     assert np.array_equal(wls_np.divergence(sides, periodic, sx, sy, gx, gy)[wls_np.unknowns(sides, periodic, 19, 13)],
-                          periodic_np.divergence(gx, gy, periodic)[wls_np.unknowns(sides, periodic, 19, 13)])
+                          direct_np.divergence(gx, gy, periodic)[wls_np.unknowns(sides, periodic, 19, 13)])
 
 
 @pytest.mark.parametrize("border", list(BORDERS))

@@ -1,5 +1,5 @@
 """The quantities the weighted GPU tests hold the library to, their bounds and their inputs (tests/test_gpu_weighted.py), after the
-pattern of tests/screened_bounds.py with W = diag(w) in place of lambda:
+pattern of tests/direct_bounds.py with W = diag(w) in place of lambda:
 
     RES  max |(A - W) u - rhs| / max |rhs|        rhs = lap - w d in the library's float32 order, the rest in float64
     ERR  max |u - solve_exact| / R,  R = max |solve_exact|
@@ -13,7 +13,6 @@ needed no iteration at all (a constant weight: its error is one direct solve's, 
 Iterations:  sweeps <= 2 x pcg_f32's count + SC_WEIGHTED_POLL, both from the reference iteration."""
 import numpy as np
 
-import periodic_np
 import weighted_np
 
 POLL = 4                                       # SC_WEIGHTED_POLL

@@ -1,24 +1,24 @@
 """The test side's restatement of the weighted solve (sc_hip_weighted*), numpy only.
 
-A problem's borders are (sides, periodic) as in periodic_np: `sides` names the sides WITHOUT a Dirichlet line, `periodic` the axes
+A problem's borders are (sides, periodic) as in direct_np: `sides` names the sides WITHOUT a Dirichlet line, `periodic` the axes
 that wrap.  Per channel the library solves
     (A - W) u = lap - w d        at the unknowns,        W = diag(w), w >= 0,
-lap given or the float32 divergence of a guidance field (periodic_np.divergence), u = boundary on the Dirichlet lines.  rhs() is the
+lap given or the float32 divergence of a guidance field (direct_np.divergence), u = boundary on the Dirichlet lines.  rhs() is the
 library's float32 right-hand side to the letter: the product w * d rounded to float32, then subtracted from lap.
 
 solve_exact() assembles A - W densely in float64 from the two axes' 1-D operators (axis_matrix: a Kronecker sum) and solves it with
 LAPACK: no transform, nothing shared with the library or with the other restatements.  operator() and residual() apply the stencil
-directly (periodic_np.operator).  pcg_f32() is the library's iteration restated in numpy: float32 vectors, float64 dot products,
-preconditioned by periodic_np.solve_f32 with the constant lambda-bar -- the yardstick of the GPU tests' bounds and iteration counts
+directly (direct_np.operator).  pcg_f32() is the library's iteration restated in numpy: float32 vectors, float64 dot products,
+preconditioned by direct_np.solve_f32 with the constant lambda-bar -- the yardstick of the GPU tests' bounds and iteration counts
 (tests/weighted_bounds.py).  Arrays are H x W x C (H x W accepted)."""
 from __future__ import annotations
 
 import numpy as np
 
 import pcg_np
-import periodic_np
+import direct_np
 
-DD, NN, DN, ND, PP = periodic_np.DD, periodic_np.NN, periodic_np.DN, periodic_np.ND, periodic_np.PP
+DD, NN, DN, ND, PP = direct_np.DD, direct_np.NN, direct_np.DN, direct_np.ND, direct_np.PP
 
 
 def _hwc(a):
@@ -26,11 +26,11 @@ def _hwc(a):
 
 
 def unknowns(sides, periodic, H, W):
-    return periodic_np.unknowns(sides, periodic, H, W)
+    return direct_np.unknowns(sides, periodic, H, W)
 
 
 def has_dirichlet(sides, periodic):
-    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    ax, ay = direct_np.axis_kinds(sides, periodic)
     return not (ax in (NN, PP) and ay in (NN, PP))
 
 
@@ -49,7 +49,7 @@ def operator(sides, periodic, weight, u):
     """(A - W) u in float64 at the unknowns (the Dirichlet lines of u hold the known values), 0 on the Dirichlet lines"""
     u = _hwc(np.asarray(u, np.float64))
     w = _hwc(np.asarray(weight, np.float32)).astype(np.float64)
-    r = periodic_np.operator(sides, periodic, 0.0, u)
+    r = direct_np.operator(sides, periodic, 0.0, u)
     blk = unknowns(sides, periodic, *u.shape[:2])
     r[blk] -= (w * u)[blk]
     return r
@@ -99,7 +99,7 @@ def folded_rhs(sides, periodic, weight, data, lap, boundary, dtype=np.float64):
     blk = unknowns(sides, periodic, *f.shape[:2])
     g = f[blk].astype(dtype)
     if has_dirichlet(sides, periodic):
-        g = g - periodic_np._fold(sides, periodic, _hwc(np.asarray(boundary, dtype))).astype(dtype)
+        g = g - direct_np.fold(sides, periodic, _hwc(np.asarray(boundary, dtype))).astype(dtype)
     return g
 
 
@@ -110,7 +110,7 @@ def solve_exact(sides, periodic, weight, data, lap, boundary=None):
     w = _hwc(np.asarray(weight, np.float32)).astype(np.float64)
     H, W, C = w.shape
     blk = unknowns(sides, periodic, H, W)
-    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    ax, ay = direct_np.axis_kinds(sides, periodic)
     g = folded_rhs(sides, periodic, weight, data, lap, boundary)
     ny, nx = g.shape[:2]
     A = np.kron(np.eye(ny), axis_matrix(ax, nx)) + np.kron(axis_matrix(ay, ny), np.eye(nx))
@@ -128,13 +128,14 @@ def mean_weight(sides, periodic, weight):
 
 
 def _precond(sides, periodic, lam, r_blk, shape):
-    """(A - lam)^-1 r on the unknown block in float32 (periodic_np.solve_f32 with zero data and a zero boundary)"""
+    """(A - lam)^-1 r on the unknown block in float32 (direct_np.solve_f32 with zero data and a zero boundary, rows first
+    both ways: the order the weighted, WLS and robust constants were measured with)"""
     H, W, C = shape
     full = np.zeros((H, W, C), np.float32)
     blk = unknowns(sides, periodic, H, W)
     full[blk] = r_blk
     zero = np.zeros((H, W, C), np.float32)
-    z = periodic_np.solve_f32(sides, periodic, float(lam), zero if lam else None, full, zero)
+    z = direct_np.solve_f32(sides, periodic, float(lam), zero if lam else None, full, zero, order=direct_np.ROWS_FIRST_BOTH_WAYS)
     return np.asarray(z, np.float32)[blk]
 
 
@@ -147,7 +148,7 @@ def pcg_f32(sides, periodic, weight, data, lap, boundary=None, tol=1e-5, max_ite
     w_full = _hwc(np.asarray(weight, np.float32))
     H, W, C = w_full.shape
     blk = unknowns(sides, periodic, H, W)
-    ax, ay = periodic_np.axis_kinds(sides, periodic)
+    ax, ay = direct_np.axis_kinds(sides, periodic)
     w = w_full[blk]
     lam = mean_weight(sides, periodic, weight) if precond_lambda is None else np.float32(precond_lambda)
     b = folded_rhs(sides, periodic, weight, data, lap, boundary, np.float32)

@@ -10,14 +10,14 @@ divergence() and folded_rhs(dtype=float32) are the library's float32 right-hand 
 product s * g rounded on its own, (a - b) + (c - d), then - w * d (one multiply, one subtract), then the Dirichlet terms s * boundary
 subtracted west, north, east, south.  operator() / residual() apply the stencil in float64.  solve_exact() assembles L densely in
 float64 from the links, entry by entry, and solves with LAPACK.  pcg_f32() is the library's iteration: float32 vectors, float64 dot
-products, preconditioned by periodic_np.solve_f32 with lam = w-bar / s-bar, started from u0 = (1 / s-bar) (A - lam)^-1 b -- the
+products, preconditioned by direct_np.solve_f32 with lam = w-bar / s-bar, started from u0 = (1 / s-bar) (A - lam)^-1 b -- the
 yardstick of tests/wls_bounds.py.  Arrays are H x W x C (H x W accepted)."""
 from __future__ import annotations
 
 import numpy as np
 
 import pcg_np
-import periodic_np
+import direct_np
 import weighted_np
 
 _hwc = weighted_np._hwc
@@ -27,7 +27,7 @@ has_dirichlet = weighted_np.has_dirichlet
 
 def live_links(sides, periodic, H, W):
     """(live_x, live_y), boolean H x W"""
-    unk = ~periodic_np.dirichlet_mask(sides, periodic, H, W)
+    unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
     lx, ly = unk | np.roll(unk, -1, 1), unk | np.roll(unk, -1, 0)
     if "x" not in periodic:
         lx[:, -1] = False
@@ -69,7 +69,7 @@ def folded_rhs(sides, periodic, weight, sx, sy, data, lap, boundary, dtype=np.fl
     blk = unknowns(sides, periodic, H, W)
     g = f[blk].astype(dtype)
     if has_dirichlet(sides, periodic):
-        fr = np.where(periodic_np.dirichlet_mask(sides, periodic, H, W)[:, :, None], _hwc(np.asarray(boundary, np.float32)), np.float32(0)).astype(dtype)
+        fr = np.where(direct_np.dirichlet_mask(sides, periodic, H, W)[:, :, None], _hwc(np.asarray(boundary, np.float32)), np.float32(0)).astype(dtype)
         west, east, north, south = _links(sides, periodic, sx, sy, dtype)
         for link, shift, axis in ((west, 1, 1), (north, 1, 0), (east, -1, 1), (south, -1, 0)):
             g = g - (link * np.roll(fr, shift, axis))[blk]          # (a wrapped neighbour is never on a Dirichlet line)
@@ -102,7 +102,7 @@ def solve_exact(sides, periodic, weight, sx, sy, data, lap, boundary=None):
     sxf, syf = _hwc(np.asarray(sx, np.float32)), _hwc(np.asarray(sy, np.float32))
     H, W, C = w.shape
     blk = unknowns(sides, periodic, H, W)
-    unk = ~periodic_np.dirichlet_mask(sides, periodic, H, W)
+    unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
     lx, ly = live_links(sides, periodic, H, W)
     index = np.full((H, W), -1)
     index[blk] = np.arange(unk.sum()).reshape(index[blk].shape)
@@ -153,7 +153,7 @@ def pcg_f32(sides, periodic, weight, sx, sy, data, lap, boundary=None, tol=1e-5,
     w_full = _hwc(np.asarray(weight, np.float32))
     H, W, C = w_full.shape
     blk = unknowns(sides, periodic, H, W)
-    unk = ~periodic_np.dirichlet_mask(sides, periodic, H, W)
+    unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
     full = _links(sides, periodic, sx, sy, np.float32)
     dg = (((full[0] + full[1]) + (full[2] + full[3])) + w_full)[blk]
     # the links between two unknowns: the neighbour in that direction (with wrap) is an unknown too

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Measures the Poisson solver's per-side free borders (SC_POISSON_FREE_*) on the GPU.
 
---lengths   the length walk of tests/mixed_bounds.py (length_cases(): every length class of the transform of a Dirichlet end paired
+--lengths   the length walk of tests/direct_bounds.py (mixed_length_cases(): every length class of the transform of a Dirichlet end paired
             with a free end, along x and y, both orders of the ends, both kinds of the other axis; rough inputs, and the smooth
             low-mode reconstruction from 256 unknowns up): per case RES and ERR of the float32 transforms beside the float32
-            restatement's (tests/mixed_np.solve_f32) and of the double transforms in float32 ulps, then the summary the bounds of
-            tests/mixed_bounds.py are taken from -- the worst ratios over the inputs with more than 3 unknowns along the walked axis,
+            restatement's (tests/direct_np.solve_f32) and of the double transforms in float32 ulps, then the summary the bounds of
+            direct_bounds.MIXED are taken from -- the worst ratios over the inputs with more than 3 unknowns along the walked axis,
             the worst values at 1 to 3.  Written to --lengths-out (profiles/mixed_lengths.txt).
 (default)   device time (sc_run_info.ms_device_total of a bSync call on device arrays) of one mixed solve -- left side free, the rest
             Dirichlet lines -- beside the SC_POISSON_NEUMANN solve of the same arrays on the same instance, 2048 x 2048 x 3 and
@@ -28,8 +28,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from seamlesscloneoptimization_amd import capi  # noqa: E402
-import mixed_np  # noqa: E402
-from mixed_bounds import Yardstick, length_cases, rough_inputs, smooth_input  # noqa: E402
+import direct_np  # noqa: E402
+from direct_bounds import MIXED, mixed_length_cases as length_cases, rough_inputs, smooth_input  # noqa: E402
 
 PREC = {"f32": 0, "f64": capi.SC_FLAG_FFT_FP64}
 
@@ -52,8 +52,8 @@ def lengths(inst, path):
         if n >= 256:
             inputs.append(smooth_input(W, H, 3, seed=n + len(sides)))
         for what, gx, gy, b in inputs:
-            lap = mixed_np.divergence(gx, gy)
-            y = Yardstick(sides, 0.0, None, lap, b)
+            lap = direct_np.divergence(gx, gy)
+            y = MIXED.yardstick(sides, "", 0.0, None, lap, b)
             tag = "n=%d %s %s %s" % (n, axis, sides, what)
             s = "n=%4d %s %-3s %4dx%-4d %-14s |" % (n, axis, sides, W, H, what)
             for prec in precs:

@@ -2,7 +2,7 @@
 """Measures the Neumann option of the Poisson solver (SC_POISSON_NEUMANN) on the GPU and writes profiles/neumann_probe.json:
 
 accuracy  max |out - want| / R per size, for the float32 and the double transforms, on the two problems the tests use
-          (reconstruction from forward differences; random guidance, sigma = 20, random boundary); want = tests/neumann_np.py on the
+          (reconstruction from forward differences; random guidance, sigma = 20, random boundary); want = tests/direct_np.py on the
           same float32 inputs, R = max |want|.  The float32 figures set the bound of tests/test_gpu_neumann.py (4 x the worst,
           rounded up to one digit).
 time      device time (sc_run_info.ms_device_total of a bSync call on device arrays) of the Neumann call and of the Dirichlet
@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from seamlesscloneoptimization_amd import capi  # noqa: E402
-import neumann_np  # noqa: E402
+import direct_np  # noqa: E402
 
 SIZES = [(2, 2), (2, 41), (41, 2), (37, 29), (300, 200), (723, 722), (1280, 721), (4000, 143), (2050, 1030), (8192, 64)]      # (W, H)
 TIME_SIZES = [(300, 200), (512, 512), (1024, 1024), (2048, 2048), (4096, 4096)]
@@ -46,12 +46,12 @@ def accuracy(inst):
         for C in (1, 2, 3, 4):
             rng = np.random.default_rng(W * 7 + H * 13 + C)
             img = rng.uniform(-50, 300, (H, W, C)).astype(np.float32)
-            gx, gy = neumann_np.forward_differences(img)
+            gx, gy = direct_np.forward_differences(img)
             b = rng.uniform(-100, 400, (H, W, C)).astype(np.float32)
             rx = rng.normal(0, 20, (H, W, C)).astype(np.float32)
             ry = rng.normal(0, 20, (H, W, C)).astype(np.float32)
-            problems = {"reconstruction": (gx, gy, img, neumann_np.solve_guidance(gx, gy, img)),
-                        "random": (rx, ry, b, neumann_np.solve_guidance(rx, ry, b))}
+            problems = {"reconstruction": (gx, gy, img, direct_np.solve_free(direct_np.divergence(gx, gy), img)),
+                        "random": (rx, ry, b, direct_np.solve_free(direct_np.divergence(rx, ry), b))}
             for prec, flags in (("float32", 0), ("double", capi.SC_FLAG_FFT_FP64)):
                 if prec == "double" and max(W, H) > 4096:
                     continue
@@ -60,7 +60,7 @@ def accuracy(inst):
                     out = inst.poisson(bb, gx=ax, gy=ay, neumann=True).astype(np.float64)
                     R = float(np.abs(want).max())
                     for key, v in ((f"{name}_{prec}_rel_err", float(np.abs(out - want).max()) / R),
-                                   (f"{name}_{prec}_mean_rel_err", float(np.abs(out.mean(axis=(0, 1)) - neumann_np.mean_of(bb)).max()) / R)):
+                                   (f"{name}_{prec}_mean_rel_err", float(np.abs(out.mean(axis=(0, 1)) - direct_np.mean_of(bb)).max()) / R)):
                         row[key] = max(row.get(key, 0.0), v)
                         if key.endswith("float32_rel_err"):
                             row.setdefault(key + "_by_C", []).append(v)
@@ -113,7 +113,7 @@ def main():
     ap.add_argument("--skip-time", action="store_true")
     a = ap.parse_args()
     inst = capi.Instance(0)
-    res = {"what": "tools/neumann_probe.py: SC_POISSON_NEUMANN on one MI355X; rel_err = max |out - want| / max |want| against tests/neumann_np.py"}
+    res = {"what": "tools/neumann_probe.py: SC_POISSON_NEUMANN on one MI355X; rel_err = max |out - want| / max |want| against tests/direct_np.py"}
     try:
         if not a.skip_accuracy:
             res["accuracy"] = accuracy(inst)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measures the screened Poisson solve (sc_hip_screened*) on the GPU.
 
---lengths  the Neumann float32 solve's ERR and RES (tests/screened_bounds.py) beside the float32 restatement's over the length walk of
+--lengths  the Neumann float32 solve's ERR and RES (tests/direct_bounds.py) beside the float32 restatement's over the length walk of
            tests/test_gpu_screened.py (every convolution-length class along x and along y, the sizes of its restatement test), random
            guidance, data and lam in 1e-3, 0.1, 10: one line per input, then the worst ratios over the inputs with more than 3 pixels
            along both sides and the worst values at 2 or 3 pixels -- what RES_FACTOR / RES_FLOOR / ERR_FACTOR / ERR_FLOOR are set from.
@@ -36,13 +36,13 @@ def configure(capi, inst, method, flags=0):
 
 def lengths(capi, inst, path):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import screened_bounds
-    import screened_np
+    import direct_np
+    from direct_bounds import SCREENED
     import test_gpu_screened as T
     sizes = sorted(set(T.identity_sizes(True)) | set(T.EXACT_SIZES))
     configure(capi, inst, capi.SC_METHOD_FFT)
-    lines = ["# screened Neumann solve, float32 transforms: ERR and RES (tests/screened_bounds.py) beside the float32 restatement's",
-             "# (screened_np.solve_f32) on the same input; random guidance (sigma 20), random data; one MI355X run of",
+    lines = ["# screened Neumann solve, float32 transforms: ERR and RES (tests/direct_bounds.py) beside the float32 restatement's",
+             "# (direct_np.solve_f32) on the same input; random guidance (sigma 20), random data; one MI355X run of",
              "# python tools/screened_probe.py --lengths",
              "SCRLEN W H C lam | f32 RES (x restatement) ERR (x restatement) / solve_f32 RES ERR"]
     worst = {"res_ratio": (0, None), "err_ratio": (0, None), "res_small": (0, None), "err_small": (0, None)}
@@ -51,8 +51,8 @@ def lengths(capi, inst, path):
             if W * H > 300000 and C > 1 and lam != 0.1:
                 continue
             d, gx, gy, _ = T.random_problem(H, W, C, W * 11 + H * 17 + C)
-            lap = screened_np.divergence(screened_np.NEUMANN, gx, gy)
-            y = screened_bounds.Yardstick(lam, d, lap)
+            lap = direct_np.divergence(gx, gy)
+            y = SCREENED.yardstick("lrtb", "", lam, d, lap, None)
             out = inst.screened(d, gx=gx, gy=gy, lam=lam, neumann=True)
             err, res = y.measure(out)
             rr, er = res / y.res32, err / y.err32
