@@ -730,8 +730,9 @@ SC_API int sc_hip_wls(void *instance, const sc_wls_params *p, const sc_poisson_l
  *                                                      +  sum_y-links c_y phi_p(u(x,y+1) - u(x,y) - gy; eps_g),
  *     phi_r(t; eps) = (2 / r) (t^2 + eps^2)^(r/2)      (r = 2: t^2, eps is not used),
  * under every border kind of sc_hip_wls -- integrating gradient fields with gross outliers (photometric stereo, edited or thresholded
- * gradients), total-variation denoising (p = 1, q = 2: ROF; q = 1: TV-L1), robust fusion.  The penalty is anisotropic: one residual per
- * link.  With p < 1 (or q < 1) the energy is not convex and the call finds a local minimum, the one its quadratic start leads to.
+ * gradients), total-variation denoising (p = 1, q = 2: ROF; q = 1: TV-L1), robust fusion.  By default the penalty is anisotropic: one
+ * residual per link; SC_ROBUST_ISOTROPIC and SC_ROBUST_JOINT_CHANNELS (below) couple the links of a pixel and of a job's channels.
+ * With p < 1 (or q < 1) the energy is not convex and the call finds a local minimum, the one its quadratic start leads to.
  * Solved by iteratively reweighted least squares.  Round 0 is the quadratic problem with links c and weights w: sc_hip_wls's system,
  * set up and solved as that call does (without base links: with every link 1).  Round k >= 1 solves the WLS system with
  *     s_x = c_x rho_p(u_x - gx),   s_y = c_y rho_p(u_y - gy),   w' = w rho_q(u - d),      rho_r(t) = (t^2 + eps^2)^((r-2)/2),
@@ -755,13 +756,32 @@ SC_API int sc_hip_wls(void *instance, const sc_wls_params *p, const sc_poisson_l
  * an inner solve ran out of max_iters (the rounds go on from its last iterate; the last iterate is written).
  * sc_run_info: sweeps = the inner iterations of all rounds, converged = the round rule was met (always 1 when p = q = 2), rel_residual
  * = the last inner solve's; the rest as the WLS call.
- * Not offered: isotropic TV (the per-pixel gradient magnitude), joint-channel TV, a robust term through the 8-bit entry points. */
+ * Coupled gradient terms: two bits of sc_robust_params.kind (of that struct only: every other call refuses them with SC_ERR_BAD_ARG).
+ * They couple the gradient term; the data term stays per pixel and per channel.  The owner of a link is its low end: pixel (x, y) owns
+ * its x-link to (x+1, y) and its y-link to (x, y+1), along a periodic axis the last pixel the wrapped link; a pixel of a Dirichlet line
+ * can own a live link; a dead link and a pixel without a live forward link contribute nothing.  With t = (u_hi - u_lo) - g of a live
+ * link on channel k and a = c t^2 (c: the base link, 1 without), the gradient term is
+ *     neither bit               sum_links c phi_p(t)                                             (as above, to the byte)
+ *     SC_ROBUST_ISOTROPIC       sum_k sum_pixels psi_p(a_x + a_y)
+ *     SC_ROBUST_JOINT_CHANNELS  sum_x-links psi_p(sum_k a_x) + sum_y-links psi_p(sum_k a_y)
+ *     both (vectorial TV)       sum_pixels psi_p(sum_k (a_x + a_y)),          psi_p(M) = (2 / p) (M + eps^2)^(p/2):
+ * the base links sit inside the magnitude M.  Round k >= 1 then solves the WLS system with s = c rho_p(M) on every link that shares M,
+ * rho_p(M) = (M + eps^2)^((p-2)/2); psi_p is concave in M for p <= 2, so a round still lowers the energy.  In float32: t t rounded,
+ * times c rounded (no base links: no multiply), a_x + a_y within a pixel, then the running sum over the channels 0 .. C - 1, Q = M +
+ * eps eps, rho = 1.0f / sqrtf(Q) (p = 1) or powf(Q, (p - 2) / 2), s = c rho rounded; both ends of a link use the same bits.  The first
+ * (quadratic) round is untouched.  With p_grad = 2 the bits change nothing (the bytes of the call without them); with one channel
+ * SC_ROBUST_JOINT_CHANNELS changes nothing.  Under SC_ROBUST_JOINT_CHANNELS the round rule judges a job's energy (the sum over its
+ * planes) instead of every plane's.  A chunk holds whole jobs: channels of different jobs never couple.  Each coupled round takes two
+ * launches for its system (k_robust_rho, k_robust_setup_rho) and still one host wait.
+ * Not offered: a robust term through the 8-bit entry points, a joint or isotropic data term. */
+#define SC_ROBUST_ISOTROPIC       (1 << 20)   /* sc_robust_params.kind: one penalty per pixel over its two forward links */
+#define SC_ROBUST_JOINT_CHANNELS  (1 << 21)   /* sc_robust_params.kind: one penalty over all channels of a job           */
 typedef struct sc_robust_params {
-    int   kind;              /* as sc_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
+    int   kind;              /* as sc_wls_params.kind; the base must be SC_POISSON_GUIDANCE; | SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS */
     float p_grad, eps_grad;  /* 0 < p <= 2; eps > 0 and finite (unused when p == 2) */
     float p_data, eps_data;  /* likewise for the data term */
     int   max_rounds;        /* reweighting rounds after the quadratic solve; <= 0: 15 */
-    float round_tol;         /* stop when no plane's energy fell by more than round_tol * its energy in the last round; 0: 1e-4; < 0: never stop early */
+    float round_tol;         /* stop when no plane's (SC_ROBUST_JOINT_CHANNELS: no job's) energy fell by more than round_tol * its energy in the last round; 0: 1e-4; < 0: never stop early */
     float tol;               /* inner solves: ||r||_2 <= tol * ||b||_2 on every plane; <= 0: 1e-5 */
     int   max_iters;         /* per inner solve; <= 0: 400 */
 } sc_robust_params;

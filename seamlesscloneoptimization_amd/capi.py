@@ -237,6 +237,14 @@ class WlsJob(C.Structure):
 
 
 # robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
+SC_ROBUST_ISOTROPIC = 1 << 20        # or'ed into RobustParams.kind only: one penalty per pixel over its two forward links
+SC_ROBUST_JOINT_CHANNELS = 1 << 21   # ... one penalty over all channels of a job (both: vectorial TV)
+
+
+def robust_coupling_bits(isotropic=False, joint_channels=False) -> int:
+    return (SC_ROBUST_ISOTROPIC if isotropic else 0) | (SC_ROBUST_JOINT_CHANNELS if joint_channels else 0)
+
+
 class RobustParams(C.Structure):
     _fields_ = [("kind", C.c_int), ("p_grad", C.c_float), ("eps_grad", C.c_float), ("p_data", C.c_float), ("eps_data", C.c_float),
                 ("max_rounds", C.c_int), ("round_tol", C.c_float), ("tol", C.c_float), ("max_iters", C.c_int)]
@@ -662,21 +670,23 @@ def wls_arrays(data, weight, smooth_x, smooth_y, gx=None, gy=None, lap=None, bou
 
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
                  max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
-                 cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
+                 cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None, isotropic=False,
+                 joint_channels=False) -> int:
     """Host-only sc_hip_robust_check: SC_OK or the code a robust call with these parameters and this layout returns before it runs
-    anything.  The layout as a PoissonLayout or as keyword fields."""
-    p = RobustParams(int(kind), float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
+    anything.  The layout as a PoissonLayout or as keyword fields.  isotropic, joint_channels: SC_ROBUST_ISOTROPIC and
+    SC_ROBUST_JOINT_CHANNELS or'ed into kind (which may carry them itself)."""
+    p = RobustParams(int(kind) | robust_coupling_bits(isotropic, joint_channels), float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
                      int(max_iters))
     return _check_call("sc_hip_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
                        row_stride=row_stride, channel_stride=channel_stride)
 
 
 def robust_arrays(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, out=None, neumann=False, free_sides="", periodic="",
-                  p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3):
+                  p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, isotropic=False, joint_channels=False):
     """Checks a robust problem's numpy arrays and penalties before any device is touched: (kind, gx, gy, data, weight, smooth_x, smooth_y,
     boundary, out), weighted_arrays' rules for data, weight and boundary and wls_arrays' for the base links, which come both or not at
     all (None: all 1).  gx and gy are required: the residual of a link needs the guidance itself.  Exponents in (0, 2]; an eps finite
-    and > 0 wherever its exponent is not 2."""
+    and > 0 wherever its exponent is not 2.  isotropic, joint_channels: kind carries SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS."""
     if gx is None or gy is None:
         raise ValueError("a robust solve needs the guidance gx and gy (there is no Laplacian form)")
     if (smooth_x is None) != (smooth_y is None):
@@ -691,7 +701,7 @@ def robust_arrays(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=N
     else:
         kind, data, weight, smooth_x, smooth_y, gx, gy, _, boundary, out = wls_arrays(data, weight, smooth_x, smooth_y, gx, gy, None, boundary,
                                                                                      out, neumann, free_sides, periodic)
-    return kind, gx, gy, data, weight, smooth_x, smooth_y, boundary, out
+    return kind | robust_coupling_bits(isotropic, joint_channels), gx, gy, data, weight, smooth_x, smooth_y, boundary, out
 
 
 class Instance:
@@ -969,14 +979,16 @@ class Instance:
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
                p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0,
-               allow_not_converged=False):
+               allow_not_converged=False, isotropic=False, joint_channels=False):
         """sc_hip_robust on numpy float32 arrays of shape H x W or H x W x C (C 1..4): minimise sum weight phi_q(u - data) +
         sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy), phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2), p = p_grad, q = p_data, by
         reweighted WLS solves on the device, under the borders of poisson().  smooth_x, smooth_y: the base links as in wls(), or None
-        (all 1).  max_rounds, round_tol, tol, max_iters: sc_robust_params' (0: the defaults; round_tol < 0: never stop early).  Returns
+        (all 1).  isotropic: one penalty per pixel over its two forward links (SC_ROBUST_ISOTROPIC); joint_channels: one penalty over
+        all channels (SC_ROBUST_JOINT_CHANNELS); both: vectorial TV.  max_rounds, round_tol, tol, max_iters: sc_robust_params' (0: the defaults; round_tol < 0: never stop early).  Returns
         out; info() has the total of the inner iterations and whether the round rule was met, robust_trace() the rounds."""
         kind, gx, gy, data, weight, sx, sy, boundary, out = robust_arrays(gx, gy, data, weight, smooth_x, smooth_y, boundary, out, neumann,
-                                                                          free_sides, periodic, p_grad, eps_grad, p_data, eps_data)
+                                                                          free_sides, periodic, p_grad, eps_grad, p_data, eps_data, isotropic,
+                                                                          joint_channels)
         p = RobustParams(kind, float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
                          int(max_iters))
         return self._host_call("sc_hip_robust", p, (gx, gy, data, weight, sx, sy, boundary), out, data,

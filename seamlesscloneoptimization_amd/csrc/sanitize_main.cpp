@@ -15,7 +15,8 @@
 //   6. sc_hip_screened_check: lambda, the kinds and the side limits of each boundary kind.
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
 //      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda, and
-//      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps.
+//      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps; the coupling
+//      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
@@ -412,6 +413,17 @@ int main()
             if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (p_grad)");
             r.p_grad = 1.f; r.eps_grad = 0.f;
             if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (eps_grad)");
+            // the coupling bits: the robust call's verdict does not change with them, every other family refuses them
+            r.eps_grad = 1e-3f;
+            for (int bits : { SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS, SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS }) {
+                r.kind = k.kind | bits;
+                if (sc_hip_robust_check(&r, &l) != got) return fail("robust_check (coupling bits)");
+                p.kind = q.kind = k.kind | bits;
+                if (sc_hip_weighted_check(&p, &l) != SC_ERR_BAD_ARG || sc_hip_wls_check(&q, &l) != SC_ERR_BAD_ARG) return fail("weighted_check / wls_check (coupling bits)");
+                sc_poisson_params pp{ k.kind | bits, 0.f };
+                sc_screened_params sp{ k.kind | bits, 1.f };
+                if (sc_hip_poisson_check(&pp, &l) != SC_ERR_BAD_ARG || sc_hip_screened_check(&sp, &l) != SC_ERR_BAD_ARG) return fail("poisson_check / screened_check (coupling bits)");
+            }
         }
         sc_weighted_params p{ SC_POISSON_GUIDANCE, 0.f, 0, 0.f };
         if (sc_hip_weighted_check(nullptr, nullptr) != SC_ERR_BAD_ARG || sc_hip_weighted_check(&p, nullptr) != SC_ERR_BAD_ARG) return fail("weighted_check (null)");

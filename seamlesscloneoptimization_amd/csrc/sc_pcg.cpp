@@ -265,7 +265,7 @@ void pcg_release(Instance *I)
 {
     if (!I->pcg) return;
     PcgState &S = *I->pcg;
-    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.red }) dev_release(*b);
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.rho, &S.red }) dev_release(*b);
     if (S.h_red.p) (void)hipHostFree(S.h_red.p);
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);
     delete I->pcg;

@@ -29,6 +29,7 @@ struct PcgState {
     DevBuf u, r, p, q;
     DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
+    DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude
     DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane | a family's round sums
     DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane | a family's round sums
     hipEvent_t ev[RING]{};
@@ -227,5 +228,20 @@ constexpr int ROBUST_SUMS = 3;
 void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                          const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                          float *Dg, double *bb, double *sums, hipStream_t s);
+// The coupled forms (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS; p_grad < 2 only): one magnitude M over the links that share a
+// penalty, s = c rho_p(M) on each of them.  Two launches: k_robust_rho writes rho of every owner (a link's low end) to the rho planes
+// -- addressed by pixel, rows of x0 + nx floats, robust_rho_stride apart; per unit (a job under ROBUST_JOINT, else a plane) one plane
+// (ROBUST_ISO) or two (x-links, y-links) -- and esum[plane * PCG_PARTS + i] = the part's gradient energy, under ROBUST_JOINT on the
+// job's channel-0 plane only (the others' are not written); k_robust_setup_rho is launch_robust_setup with s read from those planes,
+// field 2 of its sums the data term's energy alone.
+constexpr int ROBUST_ISO = 1, ROBUST_JOINT = 2;
+inline long long robust_rho_stride(const PcgGeo &wg) { return ((long long)(wg.x0 + wg.nx) * (wg.y0 + wg.ny) + 63) / 64 * 64; }
+inline size_t robust_rho_floats(const PcgGeo &wg, int C, int m, int coupling)
+{
+    return (size_t)robust_rho_stride(wg) * ((coupling & ROBUST_ISO) ? 1 : 2) * ((coupling & ROBUST_JOINT) ? m : C * m);
+}
+void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                           const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
+                           float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
 
 } // namespace sc

@@ -1,5 +1,6 @@
-// sc_robust.hip -- the robust call's one kernel of its own (sc_hip_robust*, sc_robust_api.cpp): k_robust_setup, k_wls_setup (sc_wls.hip) with
-// the links computed from the current iterate instead of read from the caller.  One reweighting round of
+// sc_robust.hip -- the robust call's kernels of its own (sc_hip_robust*, sc_robust_api.cpp): k_robust_setup, k_wls_setup (sc_wls.hip) with
+// the links computed from the current iterate instead of read from the caller, and behind it the two launches of the coupled forms
+// (isotropic, joint channels: k_robust_rho, k_robust_setup_rho).  One reweighting round of
 //     minimise  sum w phi_q(u - d) + sum_x-links c_x phi_p(u(x+1,y) - u(x,y) - gx) + sum_y-links c_y phi_p(u(x,y+1) - u(x,y) - gy),
 //     phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),
 // is the WLS system with s = c rho_p(link residual), w' = w rho_q(u - d), rho_r(t) = (t^2 + eps^2)^((r-2)/2), all at the iterate U on
@@ -128,7 +129,209 @@ __global__ __launch_bounds__(WL) void k_robust_setup(PoissonGeo g, PcgGeo wg, Wl
     part_store(s_e, ws[3], wg, sums, ROBUST_SUMS, 2);
 }
 
+// ---- the coupled forms (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS): one penalty psi_p(M) = (2 / p) (M + eps^2)^(p/2) over the
+// magnitude M that several links share -- a = c t^2 of a pixel's two forward links (ISO), of all channels of a job (JOINT), or both.
+// Every link of a magnitude gets s = c rho_p(M), rho_p(M) = (M + eps^2)^((p-2)/2).  A link's owner is its low end, so a lane needs
+// magnitudes its west and north neighbours own, under JOINT every channel of them: two launches per round instead of recomputing them.
+//   k_robust_rho        walks the owners -- the unknowns, and through the unknown next to it a pixel of a low-side Dirichlet line --
+//                       and writes rho to the rho planes, which are addressed by pixel: [Y][X], X < x0 + nx, Y < y0 + ny.  One plane
+//                       per unit (ISO) or two, the x-links' and the y-links' (not ISO); a unit is a job (JOINT) or a plane.  Per part
+//                       the gradient energy, every owner once; under JOINT it is the job's, booked on its channel-0 plane.
+//   k_robust_setup_rho  k_robust_setup with s = c rho read at the pixel, its west and its north neighbour; its energy is the data term's.
+// float32: t t rounded, times c rounded (no base links: no multiply), a_x + a_y within a pixel, then the running sum over the channels
+// 0 .. C - 1, Q = M + eps eps, rho = 1 / sqrtf(Q) (p = 1) or powf(Q, (p - 2) / 2), s = c rho rounded.  Both ends of a link read the same
+// rho and the same c: the same bits, L stays symmetric.  p = 2 never comes here (launch_robust_coupled: the bits change nothing then).
+struct RhoGeo { int rw, ncomp; long long rstride; };
+
+template <bool BASE>
+__device__ __forceinline__ float robust_sq(const float *__restrict__ c, long long o, float t)
+{
+    const float q = rounded_product(t, t);
+    return BASE ? rounded_product(c[o], q) : q;
+}
+// rho_p(M) and the magnitude's energy (2 / p) Q rho in double from the float32 Q and rho
+__device__ __forceinline__ float coupled_rho(const RobustTerm &r, float m, double &e)
+{
+    const float q = m + r.eps2, rho = r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
+    e = (double)r.scale * ((double)q * (double)rho);
+    return rho;
+}
+
+// grid: cg x bands x units; esum[(the unit's first plane * PCG_PARTS + part)] = the part's gradient energy
+template <bool BASE, bool ISO, bool JOINT>
+__global__ __launch_bounds__(WL) void k_robust_rho(PoissonGeo g, PcgGeo wg, WlsJobs t, RobustTerm tg, RhoGeo rg, const float *__restrict__ U,
+                                                    float *__restrict__ Rho, double *__restrict__ esum)
+{
+    __shared__ double ws[4];
+    const int unit = (int)blockIdx.z, member = JOINT ? unit : unit / g.C;
+    const int k0 = JOINT ? 0 : unit - member * g.C, k1 = JOINT ? g.C : k0 + 1;
+    const PoissonJobDev &j = t.j[member];
+    const float *__restrict__ sx = t.sx[member], *__restrict__ sy = t.sy[member];
+    const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
+    const int nx = wg.nx, ny = wg.ny, x = (int)blockIdx.x * WL + (int)threadIdx.x;
+    const int y0 = (int)blockIdx.y * wg.rows, y1 = min(y0 + wg.rows, ny);
+    float *__restrict__ rx = Rho + (size_t)unit * rg.ncomp * rg.rstride, *__restrict__ ry = ISO ? rx : rx + rg.rstride;
+    double s_e = 0.0;
+    if (x < nx) {
+        const int X = wg.x0 + x;
+        const bool has_e = X < g.W - 1 || px;
+        const bool dir_w = X == 1 && mixed_low_d(wg.ax), dir_e = X == g.W - 2 && mixed_high_d(wg.ax);
+        for (int y = y0; y < y1; ++y) {
+            const int Y = wg.y0 + y;
+            const size_t ro = (size_t)y * nx;
+            const bool has_s = Y < g.H - 1 || py;
+            const bool dir_n = Y == 1 && mixed_low_d(wg.ay), dir_s = Y == g.H - 2 && mixed_high_d(wg.ay);
+            // the magnitudes: this pixel's (mx: its x-link's, or under ISO both links'; my: its y-link's), the west Dirichlet pixel's
+            // x-link (mw), the north Dirichlet pixel's y-link (mn) -- a Dirichlet pixel owns no other live link
+            float mx = 0.f, my = 0.f, mw = 0.f, mn = 0.f;
+            for (int k = k0; k < k1; ++k) {
+                const long long o = (long long)X * g.cs + (long long)Y * g.rs + (long long)k * g.chs;
+                const float *__restrict__ ul = U + (size_t)(member * g.C + k) * wg.stride;
+                const float uc = ul[ro + x];
+                float ax = 0.f, ay = 0.f;
+                if (has_e) {
+                    const float ue = dir_e ? j.b[o + g.cs] : ul[ro + (x < nx - 1 ? x + 1 : 0)];
+                    ax = robust_sq<BASE>(sx, o, (ue - uc) - j.gx[o]);
+                }
+                if (has_s) {
+                    const float us = dir_s ? j.b[o + g.rs] : ul[(size_t)(y < ny - 1 ? y + 1 : 0) * nx + x];
+                    ay = robust_sq<BASE>(sy, o, (us - uc) - j.gy[o]);
+                }
+                if (ISO) mx += ax + ay;
+                else { mx += ax; my += ay; }
+                if (dir_w) mw += robust_sq<BASE>(sx, o - g.cs, (uc - j.b[o - g.cs]) - j.gx[o - g.cs]);
+                if (dir_n) mn += robust_sq<BASE>(sy, o - g.rs, (uc - j.b[o - g.rs]) - j.gy[o - g.rs]);
+            }
+            const size_t i = (size_t)Y * rg.rw + X;
+            double e_x = 0.0, e_y = 0.0, e_w = 0.0, e_n = 0.0;
+            if (ISO ? (has_e || has_s) : has_e) rx[i] = coupled_rho(tg, mx, e_x);
+            if (!ISO && has_s) ry[i] = coupled_rho(tg, my, e_y);
+            if (dir_w) rx[i - 1] = coupled_rho(tg, mw, e_w);
+            if (dir_n) ry[i - rg.rw] = coupled_rho(tg, mn, e_n);
+            s_e += (e_x + e_y) + (e_w + e_n);
+        }
+    }
+    s_e = block_sum(s_e, ws);
+    if (threadIdx.x == 0) esum[(size_t)(JOINT ? unit * g.C : unit) * PCG_PARTS + blockIdx.y * wg.cg + blockIdx.x] = s_e;
+}
+
+// k_robust_setup (its walk, its order, its sums) with the links' rho read from the rho planes; field 2 of the sums: the data term's energy
+template <bool BASE, bool ISO, bool JOINT>
+__global__ __launch_bounds__(WL) void k_robust_setup_rho(PoissonGeo g, PcgGeo wg, WlsJobs t, RobustTerm td, RhoGeo rg, const float *__restrict__ Rho,
+                                                          const float *__restrict__ U, float *__restrict__ R, float *__restrict__ E,
+                                                          float *__restrict__ S, float *__restrict__ Dg, double *__restrict__ bb,
+                                                          double *__restrict__ sums)
+{
+    __shared__ double ws[4][4];
+    const PcgBand bd(g, wg);
+    const PoissonJobDev &j = t.j[bd.member];
+    const float *__restrict__ w = t.w[bd.member], *__restrict__ sx = t.sx[bd.member], *__restrict__ sy = t.sy[bd.member];
+    const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
+    const int nx = wg.nx, ny = wg.ny, x = bd.x;
+    const float *__restrict__ ul = U + (size_t)bd.p * wg.stride;
+    const float *__restrict__ rx = Rho + (size_t)(JOINT ? bd.member : bd.p) * rg.ncomp * rg.rstride, *__restrict__ ry = ISO ? rx : rx + rg.rstride;
+    double s_bb = 0.0, s_w = 0.0, s_l = 0.0, s_e = 0.0;
+    if (x < nx) {
+        const int X = wg.x0 + x;
+        const bool has_e = X < g.W - 1 || px, has_w = X > 0 || px;
+        const bool dir_w = X == 1 && mixed_low_d(wg.ax), dir_e = X == g.W - 2 && mixed_high_d(wg.ax);
+        const long long west = X > 0 ? -g.cs : (long long)(g.W - 1) * g.cs;        // from a pixel to the element of its west link
+        const int Xw = X > 0 ? X - 1 : g.W - 1;                                     // the owner of the west link
+        float north = 0.f;
+        for (int y = bd.y0; y < bd.y1; ++y) {
+            const int Y = wg.y0 + y;
+            const long long o = bd.pixel(g, X, Y);
+            const size_t ro = (size_t)y * nx, rr = (size_t)Y * rg.rw;
+            const bool has_s = Y < g.H - 1 || py, has_n = Y > 0 || py;
+            const bool dir_n = Y == 1 && mixed_low_d(wg.ay), dir_s = Y == g.H - 2 && mixed_high_d(wg.ay);
+            const float uc = ul[ro + x];
+            float east = 0.f, westl = 0.f, south = 0.f;
+            float a = 0.f, b = 0.f, cc = 0.f, d = 0.f, b_e = 0.f, b_w = 0.f, b_n = 0.f, b_s = 0.f;
+            if (has_e) {
+                if (dir_e) b_e = j.b[o + g.cs];
+                east = BASE ? rounded_product(sx[o], rx[rr + X]) : rx[rr + X];
+                a = rounded_product(east, j.gx[o]);
+            }
+            if (has_w) {
+                if (dir_w) b_w = j.b[o - g.cs];
+                westl = BASE ? rounded_product(sx[o + west], rx[rr + Xw]) : rx[rr + Xw];
+                b = rounded_product(westl, j.gx[o + west]);
+            }
+            if (has_s) {
+                if (dir_s) b_s = j.b[o + g.rs];
+                south = BASE ? rounded_product(sy[o], ry[rr + X]) : ry[rr + X];
+                cc = rounded_product(south, j.gy[o]);
+            }
+            if (has_n) {
+                const long long on = Y > 0 ? o - g.rs : o + (long long)(g.H - 1) * g.rs;
+                if (dir_n) b_n = j.b[o - g.rs];
+                if (y == bd.y0) {
+                    const size_t rn = (size_t)(Y > 0 ? Y - 1 : g.H - 1) * rg.rw + X;
+                    north = BASE ? rounded_product(sy[on], ry[rn]) : ry[rn];
+                }
+                d = rounded_product(north, j.gy[on]);
+            } else north = 0.f;
+            float v = (a - b) + (cc - d);
+            // the data term at the iterate: w' = w rho_q(u - d)
+            const float wv = w[o], dv = j.d[o];
+            float q;
+            const float rho = robust_rho(td, uc - dv, q), wr = td.mode == 0 ? wv : rounded_product(wv, rho);
+            v = screened_rhs(v, wr, dv);
+            if (dir_w) v -= rounded_product(westl, b_w);
+            if (dir_n) v -= rounded_product(north, b_n);
+            if (dir_e) v -= rounded_product(east, b_e);
+            if (dir_s) v -= rounded_product(south, b_s);
+            const size_t i = (size_t)bd.p * wg.stride + ro + x;
+            R[i] = v;
+            E[i] = (x < nx - 1 || px) ? east : 0.f;
+            S[i] = (y < ny - 1 || py) ? south : 0.f;
+            Dg[i] = ((westl + east) + (north + south)) + wr;
+            s_bb += (double)v * (double)v;
+            s_w += (double)wr;
+            s_l += ((double)east + (double)south) + ((dir_w ? (double)westl : 0.0) + (dir_n ? (double)north : 0.0));
+            s_e += robust_phi(td, wv, q, rho);
+            north = south;
+        }
+    }
+    part_store(s_bb, ws[0], wg, bb);
+    part_store(s_w, ws[1], wg, sums, ROBUST_SUMS, 0);
+    part_store(s_l, ws[2], wg, sums, ROBUST_SUMS, 1);
+    part_store(s_e, ws[3], wg, sums, ROBUST_SUMS, 2);
+}
+
+template <bool BASE, bool ISO, bool JOINT>
+void coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const WlsJobs &t, int cnt, const RobustTerm &grad, const RobustTerm &data,
+                      const RhoGeo &rg, const float *U, float *Rho, float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum,
+                      hipStream_t s)
+{
+    const unsigned planes = (unsigned)(g.C * cnt);
+    hipLaunchKernelGGL((k_robust_rho<BASE, ISO, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, JOINT ? (unsigned)cnt : planes), dim3(WL), 0, s, g, wg,
+                       t, grad, rg, U, Rho, esum);
+    hipLaunchKernelGGL((k_robust_setup_rho<BASE, ISO, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, planes), dim3(WL), 0, s, g, wg, t, data, rg,
+                       Rho, U, R, E, S, Dg, bb, sums);
+}
+
 } // namespace
+
+void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                           const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
+                           float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s)
+{
+    const bool iso = (coupling & ROBUST_ISO) != 0, joint = (coupling & ROBUST_JOINT) != 0;
+    RhoGeo rg;
+    rg.rw = wg.x0 + wg.nx;
+    rg.ncomp = iso ? 1 : 2;
+    rg.rstride = robust_rho_stride(wg);
+    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
+        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
+        float *rho = Rho + (size_t)(joint ? i0 : g.C * i0) * rg.ncomp * rg.rstride;
+        const bool base = t.sx[0] != nullptr;
+#define SC_COUPLED(B, I, J) coupled_launches<B, I, J>(g, wg, t, cnt, grad, data, rg, U + o, rho, R + o, E + o, S + o, Dg + o, bb + po, sums + po * ROBUST_SUMS, esum + po, s)
+        if (base) { if (iso) { if (joint) SC_COUPLED(true, true, true); else SC_COUPLED(true, true, false); } else SC_COUPLED(true, false, true); }
+        else { if (iso) { if (joint) SC_COUPLED(false, true, true); else SC_COUPLED(false, true, false); } else SC_COUPLED(false, false, true); }
+#undef SC_COUPLED
+    });
+}
 
 void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
                          const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,

@@ -13,7 +13,10 @@
 //               gives s-bar and w-bar of M = s-bar (A - w-bar / s-bar) and the round rule's energies; then a warm solve: r = b - L u,
 //               z = M^-1 r, p = z.  Conjugate gradients started at u lower the round's quadratic surrogate at every iterate, so a
 //               round lowers the robust energy even when its solve stops early.
-//   the end     the round rule (no plane's energy fell by more than round_tol times its energy) or max_rounds.  The energy of the last
+//               With SC_ROBUST_ISOTROPIC / SC_ROBUST_JOINT_CHANNELS (and p_grad < 2; a joint form needs two channels) the system
+//               comes from launch_robust_coupled's two launches instead: rho of every shared magnitude, then the set-up that reads
+//               it; the gradient energy is the first launch's, under the joint forms one number per job on its channel-0 plane.
+//   the end     the round rule (no plane's -- joint forms: no job's -- energy fell by more than round_tol times its energy) or max_rounds.  The energy of the last
 //               iterate comes from one more k_robust_setup launch rather than an energy-only kernel: one launch of ~ the set-up's
 //               time per call against a second kernel to keep in step with the first; what it writes to b, E, S, Dg is not used.
 #include "sc_pcg.h"
@@ -28,15 +31,18 @@ namespace {
 bool bad_exponent(float r) { return !(r > 0.f && r <= 2.f); }
 bool bad_eps(float r, float eps) { return r != 2.f && !(std::isfinite(eps) && eps > 0.f); }
 
+constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
+
 int robust_validate(const sc_robust_params *p, const sc_poisson_layout *l, const char **why)
 {
+    const int kind = p ? p->kind & ~COUPLING_BITS : 0;          // the two bits are this call's own: the family's kinds know nothing of them
     const char *own = !p ? nullptr
                     : bad_exponent(p->p_grad) || bad_exponent(p->p_data) ? "p_grad and p_data must lie in (0, 2]"
                     : bad_eps(p->p_grad, p->eps_grad) || bad_eps(p->p_data, p->eps_data) ? "eps_grad and eps_data must be finite and > 0 where their exponent is not 2"
                     : !std::isfinite(p->tol) ? "tol must be finite"
                     : !std::isfinite(p->round_tol) ? "round_tol must be finite"
-                    : poisson_base(p->kind) == SC_POISSON_LAPLACIAN ? "a robust solve needs the guidance itself: the base kind must be SC_POISSON_GUIDANCE" : nullptr;
-    return family_validate(p ? &p->kind : nullptr, l, own,
+                    : poisson_base(kind) == SC_POISSON_LAPLACIAN ? "a robust solve needs the guidance itself: the base kind must be SC_POISSON_GUIDANCE" : nullptr;
+    return family_validate(p ? &kind : nullptr, l, own,
                            "a robust solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side", why);
 }
 
@@ -59,20 +65,33 @@ int carries_of(bool base_links) { return FLOAT_DATA | FLOAT_WEIGHT | (base_links
 struct RobustOperator final : WlsOperator {
     const sc_robust_params prm;
     const RobustTerm grad, data;
+    const int bits;          // ROBUST_ISO | ROBUST_JOINT as the caller set them
     RobustOperator(Instance *I_, bool base_links, const sc_robust_params *p)
-        : WlsOperator(I_, base_links, 0.f, 0.f, ROBUST_SUMS), prm(*p), grad(robust_term(p->p_grad, p->eps_grad)),
-          data(robust_term(p->p_data, p->eps_data)) {}
+        : WlsOperator(I_, base_links, 0.f, 0.f, ROBUST_SUMS + 1), prm(*p), grad(robust_term(p->p_grad, p->eps_grad)),
+          data(robust_term(p->p_data, p->eps_data)),
+          bits(((p->kind & SC_ROBUST_ISOTROPIC) ? ROBUST_ISO : 0) | ((p->kind & SC_ROBUST_JOINT_CHANNELS) ? ROBUST_JOINT : 0)) {}
     bool quadratic() const { return grad.mode == 0 && data.mode == 0; }
-    // a later round: the system at the chunk's iterate, its means, and that iterate's energy per plane (one wait)
+    // the coupling that changes anything: none with p_grad = 2 (every form is sum c t^2), no joint form of one channel
+    int coupling(int C) const { return grad.mode == 0 ? 0 : C == 1 ? bits & ~ROBUST_JOINT : bits; }
+    // A later round: the system at the chunk's iterate, its means, and that iterate's energy (one wait) -- per plane, or per job where
+    // the channels are coupled (the round rule's units)
     int reweigh(PcgChunk &c, std::vector<double> &energy)
     {
         PcgState &S = *I->pcg;
-        launch_robust_setup(c.g, c.wg, dj.data(), dw.data(), dsx.data(), dsy.data(), c.mv, grad, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
-                            (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
+        const int cpl = coupling(c.g.C), per = (cpl & ROBUST_JOINT) ? c.g.C : 1;
+        const size_t parts = (size_t)c.planes * PCG_PARTS;
+        if (cpl) {
+            const int rc = ensure(I, S.rho, sizeof(float) * robust_rho_floats(c.wg, c.g.C, c.mv, cpl), false);
+            if (rc) return rc;
+            launch_robust_coupled(c.g, c.wg, dj.data(), dw.data(), dsx.data(), dsy.data(), c.mv, grad, data, cpl, c.U, (float *)S.rho.p, c.R,
+                                  (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, c.d_bb, c.d_round, c.d_round + parts * ROBUST_SUMS, I->stream);
+        } else
+            launch_robust_setup(c.g, c.wg, dj.data(), dw.data(), dsx.data(), dsy.data(), c.mv, grad, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
+                                (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
         SC_HIP(I, hipGetLastError());
-        SC_HIP(I, hipMemcpyAsync(c.h_round, c.d_round, sizeof(double) * (size_t)c.planes * PCG_PARTS * ROBUST_SUMS, hipMemcpyDeviceToHost, I->stream));
+        SC_HIP(I, hipMemcpyAsync(c.h_round, c.d_round, sizeof(double) * parts * (ROBUST_SUMS + (cpl ? 1 : 0)), hipMemcpyDeviceToHost, I->stream));
         SC_HIP(I, hipStreamSynchronize(I->stream));
-        energy.assign(c.planes, 0.0);
+        energy.assign(c.planes / per, 0.0);
         wsum = ssum = 0.0;
         unit_links = false;
         for (int p = 0; p < c.planes; ++p) {
@@ -80,8 +99,11 @@ struct RobustOperator final : WlsOperator {
             for (int i = 0; i < c.nop; ++i) {
                 wsum += plane[(size_t)i * ROBUST_SUMS];
                 ssum += plane[(size_t)i * ROBUST_SUMS + 1];
-                energy[p] += plane[(size_t)i * ROBUST_SUMS + 2];
+                energy[p / per] += plane[(size_t)i * ROBUST_SUMS + 2];
             }
+            // the coupled forms' gradient energy: the rho launch's parts, a job's on its channel-0 plane
+            const double *grad_parts = c.h_round + parts * ROBUST_SUMS + (size_t)p * PCG_PARTS;
+            for (int i = 0; cpl && p % per == 0 && i < c.nop; ++i) energy[p / per] += grad_parts[i];
         }
         return SC_OK;
     }
@@ -117,7 +139,7 @@ int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOpera
         S.trace_energy.push_back(sum);
         if (k >= 2 && round_tol >= 0.0) {
             met = true;
-            for (int p = 0; p < c.planes; ++p)
+            for (size_t p = 0; p < cur.size(); ++p)
                 if (prev[p] - cur[p] > round_tol * prev[p]) met = false;
         }
         if (met || k > max_rounds) break;
@@ -149,6 +171,7 @@ int sc_hip_robust_device(void *inst, const sc_robust_params *p, const sc_poisson
     Instance *I;
     int kind, rc = pcg_begin(inst, p, l, robust_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
+    kind &= ~COUPLING_BITS;          // (poisson_norm_kind passes them through; RobustOperator has them from p)
     // base links: all jobs or none, as the first job has them; a job that differs is refused (as one with exactly one of the two arrays)
     const bool base_links = jobs && n > 0 && (jobs[0].smooth_x || jobs[0].smooth_y);
     RobustOperator op(I, base_links, p);
@@ -164,6 +187,7 @@ int sc_hip_robust(void *inst, const sc_robust_params *p, const sc_poisson_layout
     Instance *I;
     int kind, rc = pcg_begin(inst, p, l, robust_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
+    kind &= ~COUPLING_BITS;          // (poisson_norm_kind passes them through; RobustOperator has them from p)
     if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: all base links 1)"; return SC_ERR_BAD_ARG; }
     const bool base_links = smooth_x != nullptr;
     RobustOperator op(I, base_links, p);

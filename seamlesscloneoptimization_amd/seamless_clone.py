@@ -524,33 +524,40 @@ def _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, m
 
 
 def robust_solve(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3, neumann=True,
-                 free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, **solver):
+                 free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False,
+                 joint_channels=False, **solver):
     """Robust gradient solve on a float32 image of shape H x W or H x W x C (C 1..4); returns a NEW array u that minimises
         sum weight phi_q(u - data) + sum smooth_x phi_p(u[y, x+1] - u[y, x] - gx) + sum smooth_y phi_p(u[y+1, x] - u[y, x] - gy),
         phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),      0 < p, q <= 2,
     by iteratively reweighted least squares on the GPU: the quadratic problem (wls_solve's; smooth_x, smooth_y None: every base link 1)
     and then up to max_rounds (default 15) WLS solves whose links and weights come from the previous iterate, each started from it.
-    p = 1 is the anisotropic total variation of the gradient residual (one residual per link), q = 1 an L1 data term; eps_grad,
+    p = 1 is the anisotropic total variation of the gradient residual (one residual per link), q = 1 an L1 data term.  isotropic=True
+    takes one penalty per pixel over its two forward links, psi_p(c_x t_x^2 + c_y t_y^2) with psi_p(M) = (2 / p) (M + eps^2)^(p/2) (p = 1:
+    the isotropic total variation, no staircases along the axes); joint_channels=True takes one penalty over all channels of a link
+    (no colour fringes at edges); both: vectorial TV, one magnitude per pixel.  They couple the gradient term only.  eps_grad,
     eps_data round the penalties off near 0 (in the data's units: a hundredth to a thousandth of its range).  With an exponent below 1
-    the energy is not convex and the result is a local minimum.  round_tol (default 1e-4): stop when no channel's energy fell by more
-    than that fraction in the last round; negative: run every round.  tol, max_iters: the inner solves' (wls_solve's).  Borders,
+    the energy is not convex and the result is a local minimum.  round_tol (default 1e-4): stop when no channel's energy (with
+    joint_channels: the image's) fell by more than that fraction in the last round; negative: run every round.  tol, max_iters: the inner solves' (wls_solve's).  Borders,
     boundary and weight as wls_solve's."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     with _instance(gpu_id, solver) as inst:
         return inst.robust(gx, gy, data, weight, smooth_x, smooth_y, boundary=boundary, neumann=neumann, free_sides=free_sides,
                            periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0,
-                           round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0)
+                           round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0, isotropic=isotropic,
+                           joint_channels=joint_channels)
 
 
 def robust_solve_batch(gxs, gys, datas, weights, smooth_xs=None, smooth_ys=None, boundaries=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
                        neumann=True, free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0,
-                       **solver):
+                       isotropic=False, joint_channels=False, **solver):
     """robust_solve over a list of same-shape problems through ONE device-resident call (sc_hip_robust_device), as wls_solve_batch: the
     rounds, the inner stops and the preconditioner's constants are joint, so a member agrees with its solo solve to the inner solves'
-    error as the rounds carry it, not bit for bit.  Base links for every problem or for none.  Returns a list of NEW arrays."""
+    error as the rounds carry it, not bit for bit.  Base links for every problem or for none.  isotropic, joint_channels: robust_solve's
+    (channels couple within a problem, never across problems).  Returns a list of NEW arrays."""
     def arrays_of(d, a, borders):
         kind, gx, gy, d, w, sx, sy, b, _ = capi.robust_arrays(a["gx"], a["gy"], d, a["weight"], a.get("smooth_x"), a.get("smooth_y"), a.get("boundary"),
-                                                              **borders, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data)
+                                                              **borders, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data,
+                                                              isotropic=isotropic, joint_channels=joint_channels)
         return kind, dict(gx=gx, gy=gy, data=d, weight=w, smooth_x=sx, smooth_y=sy, boundary=b)
     return _pcg_batch("robust", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
                       required=dict(weight=weights, gx=gxs, gy=gys), optional=dict(smooth_x=smooth_xs, smooth_y=smooth_ys),
@@ -562,11 +569,14 @@ def robust_solve_batch(gxs, gys, datas, weights, smooth_xs=None, smooth_ys=None,
                       make_jobs=capi.Instance.make_robust_jobs, device_call=capi.Instance.robust_device)
 
 
-def tv_denoise(image, lam, p=1.0, q=2.0, eps=1e-2, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+def tv_denoise(image, lam, p=1.0, q=2.0, eps=1e-2, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False, joint_channels=False,
+               **solver):
     """Total-variation denoising of a float32 image (H x W or H x W x C): the image u that minimises
         lam sum phi_q(u - image) + sum phi_p(forward differences of u)
     under reflecting borders -- robust_solve with zero guidance, data = image and weight = lam.  The default p = 1, q = 2 is the
-    (anisotropic) Rudin-Osher-Fatemi model, q = 1 gives TV-L1; p = q = 2 is plain quadratic smoothing.  lam weighs closeness to the image
+    anisotropic form of the Rudin-Osher-Fatemi model (one penalty per link); isotropic=True is ROF as usually meant: the penalty on
+    the gradient's magnitude per pixel, which does not round discs into diamonds.  joint_channels=True takes the magnitude over all
+    channels (with isotropic=True: vectorial TV, no colour fringes).  q = 1 gives TV-L1; p = q = 2 is plain quadratic smoothing.  lam weighs closeness to the image
     against flatness; eps (in the image's units) rounds both penalties off near 0.  Returns a NEW array."""
     if not isinstance(image, np.ndarray) or image.dtype != np.float32:
         raise TypeError("image must be a float32 numpy array")
@@ -574,24 +584,26 @@ def tv_denoise(image, lam, p=1.0, q=2.0, eps=1e-2, max_rounds=None, round_tol=No
         raise ValueError("lam must be finite and > 0")
     zero = np.zeros_like(image)
     return robust_solve(zero, zero, image, np.full(image.shape, lam, np.float32), p=p, q=q, eps_grad=eps, eps_data=eps, neumann=True,
-                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, joint_channels=joint_channels, **solver)
 
 
-def integrate_gradients(gx, gy, boundary=None, p=1.0, eps=1e-3, anchor=1e-3, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+def integrate_gradients(gx, gy, boundary=None, p=1.0, eps=1e-3, anchor=1e-3, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False,
+                        joint_channels=False, **solver):
     """Integrates a float32 gradient field (gx, gy: forward differences, H x W or H x W x C) into an image with an Lp penalty on the
     residual of every link: p = 1 (the default) ignores gross outliers in the field that a least-squares integration (p = 2) would
     smear over the image.  boundary given: its outermost rows and columns are the image's (a Dirichlet frame).  None: reflecting borders,
     and the free constant is held by a data term of weight `anchor` towards 0 -- small enough to leave the shape alone, so the
-    result is the integral up to (nearly) a constant.  eps rounds the penalty off near 0, in the field's units.  Returns a NEW array."""
+    result is the integral up to (nearly) a constant.  eps rounds the penalty off near 0, in the field's units.  isotropic,
+    joint_channels: robust_solve's -- one penalty on the residual vector of a pixel, of all channels, or both.  Returns a NEW array."""
     if not isinstance(gx, np.ndarray) or gx.dtype != np.float32:
         raise TypeError("gx and gy must be float32 numpy arrays")
     if boundary is None and not (np.isfinite(anchor) and anchor > 0):
         raise ValueError("anchor must be finite and > 0")
     if boundary is not None:
         return robust_solve(gx, gy, np.zeros_like(gx), np.zeros_like(gx), boundary=boundary, p=p, eps_grad=eps, neumann=False,
-                            max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+                            max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, joint_channels=joint_channels, **solver)
     return robust_solve(gx, gy, np.zeros_like(gx), np.full(gx.shape, anchor, np.float32), p=p, eps_grad=eps, neumann=True,
-                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+                        max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, joint_channels=joint_channels, **solver)
 
 
 def _forward_abs_differences(a):

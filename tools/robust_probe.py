@@ -18,7 +18,17 @@
            Kernel times (k_robust_setup beside k_wls_setup): the same leg under
                rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/robust_probe.py --time --calls 1 --warmup 0 --no-host-loop
 
-    python tools/robust_probe.py --lengths --time [--calls 5] [--warmup 1]
+--coupling iso | joint | both | all    the coupled gradient terms (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) instead:
+           --lengths  the same figures against tests/robust_coupled_np.py over tests/robust_coupled_bounds.py's cases (accuracy_cases,
+                      and large_cases: RES and ENERGY only) and the length walk with the chosen couplings in turn, to
+                      profiles/robust_coupled_lengths.txt -- what robust_coupled_bounds' constants are set from.
+           --time     tv_denoise's problem (zero guidance, weight 2, p = 1, q = 2, eps = 1e-2) at 1024^2, C = 3, Neumann, on resident
+                      arrays, 8 fixed rounds: the call's device time, the rounds' inner iterations and the final energy of the
+                      anisotropic form and of every chosen coupling, to profiles/robust_coupled_probe.json.  Kernel times
+                      (k_robust_rho and k_robust_setup_rho beside k_robust_setup): the same leg under rocprofv3 as above, with
+                      --base-links for the launches' base-link forms.
+
+    python tools/robust_probe.py --lengths --time [--calls 5] [--warmup 1] [--coupling all]
 """
 from __future__ import annotations
 
@@ -115,6 +125,101 @@ def lengths(capi, inst, path):
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+
+
+def coupled_lengths(capi, inst, path, couplings):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import robust_bounds as rb
+    import robust_coupled_bounds as cb
+    import robust_coupled_np as rc
+    borders = {b[0]: b[1:] for b in cb.BORDERS}
+    cases = [c + (0, True) for c in cb.accuracy_cases() if c[7] in couplings] + [c + (0, False) for c in cb.large_cases() if c[7] in couplings]
+    i = 0
+    for name in ("neumann", "free_lt"):
+        for n in WALK:
+            for pq, epsf, links, wk in (((1.0, 2.0), 1e-3, False, "sparse"), ((1.5, 2.0), 1e-2, True, "dense")):
+                for size in ((7, n), (n, 6)):
+                    cases.append((name, size, pq, epsf, links, wk, 3, couplings[i % len(couplings)], 1, True))
+                    i += 1
+    lines = ["# robust solve, coupled gradient terms, float32, 8 fixed rounds: ERR, RES, ENERGY (tests/robust_coupled_bounds.py) beside the",
+             "# restatement's rounds (robust_coupled_np.irls_f32, inner tol 1e-5) on the same input; one MI355X run of",
+             "# python tools/robust_probe.py --lengths --coupling " + ("all" if len(couplings) == 3 else rc.NAMES[couplings[0]]),
+             "CLEN coupling border W H C p q eps links weights | ERR (x irls_f32) RES (x irls_f32) ENERGY rel rise sweeps / irls_f32 ERR RES iterations"]
+    worst = {k: (0.0, None) for k in ("err_ratio", "res_ratio", "err_zero", "res_zero", "energy_rel")}
+    worst["energy_rise"] = (-1.0, None)
+    for name, (H, W), (p, q), epsf, links, wk, C, cpl, seed, exact in cases:
+        sides, periodic = borders[name]
+        a = rb.with_dead_nan(sides, periodic, rb.make_input(H, W, C, wk, links, seed))
+        eps = epsf * a["range"]
+        y = cb.Yardstick(sides, periodic, p, q, eps, eps, a, cpl, exact=exact)
+        kw = dict(isotropic=bool(cpl & rc.ISO), joint_channels=bool(cpl & rc.JOINT))
+        prev = run_rounds(inst, sides, periodic, p, q, eps, a, cb.ROUNDS - 1, **kw)
+        out = run_rounds(inst, sides, periodic, p, q, eps, a, cb.ROUNDS, **kw)
+        sweeps = inst.info().sweeps
+        energy, iters = inst.robust_trace()
+        err, res = y.measure(prev, out)
+        want_e = float(y.energy(out).sum())
+        erel = abs(float(energy[-1]) - want_e) / want_e
+        rise = float(np.max(np.diff(energy) / energy[:-1]))
+        tag = f"{rc.NAMES[cpl]} {name} {W}x{H}x{C} p={p} q={q} eps={epsf} links={int(links)} {wk}"
+        er = err / y.err32 if y.err32 > 0 else float("nan")
+        rr = res / y.res32 if y.res32 > 0 else float("nan")
+        lines.append(f"CLEN {rc.NAMES[cpl]:9s} {name:11s} {W:3d} {H:3d} {C} {p} {q} {epsf:g} {int(links)} {wk:6s} | ERR {err:.2e} (x{er:.2f}) RES {res:.2e} "
+                     f"(x{rr:.2f}) ENERGY {erel:.2e} rise {rise:+.1e} sweeps {sweeps:3d} / irls_f32 {y.err32:.2e} {y.res32:.2e} {sum(y.iters32):3d}")
+        print(lines[-1], flush=True)
+        for key, ratio, value, ref in (("err", er, err, y.err32), ("res", rr, res, y.res32)):
+            if ref > 0:
+                worst[key + "_ratio"] = max(worst[key + "_ratio"], (ratio, tag))
+            elif exact or key == "res":
+                worst[key + "_zero"] = max(worst[key + "_zero"], (value, tag))
+        worst["energy_rel"] = max(worst["energy_rel"], (erel, tag))
+        worst["energy_rise"] = max(worst["energy_rise"], (rise, tag))
+    for k, (v, tag) in worst.items():
+        lines.append(f"CLEN worst {k}: {v:.4g} ({tag})")
+        print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def coupled_timing(capi, inst, path, calls, warmup, couplings, base_links):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import robust_bounds as rb
+    import robust_coupled_np as rc
+    n, rounds = 1024, 8
+    img = (rb.clean_image(n, n, 3) + 0.1 * np.random.default_rng(5).standard_normal((n, n, 3))).astype(np.float32)
+    zero = np.zeros_like(img)
+    lay = capi.poisson_layout_of(img)
+    G = capi.SC_POISSON_GUIDANCE | capi.SC_POISSON_NEUMANN
+    host = {"gx": zero, "gy": zero, "data": img, "weight": np.full(img.shape, 2.0, np.float32)}
+    if base_links:
+        rng = np.random.default_rng(7)
+        host["smooth_x"], host["smooth_y"] = (np.exp(rng.uniform(np.log(0.25), 0.0, img.shape)).astype(np.float32) for _ in range(2))
+    dev = {k: inst.to_device(v) for k, v in host.items()}
+    dev["out"] = inst.malloc(img.nbytes)
+    try:
+        jobs = capi.Instance.make_robust_jobs(1)
+        for k, ptr in dev.items():
+            setattr(jobs[0], k, ptr)
+        for cpl in [0] + list(couplings):
+            prm = capi.RobustParams(G | capi.robust_coupling_bits(bool(cpl & rc.ISO), bool(cpl & rc.JOINT)), 1.0, 1e-2, 2.0, 1e-2, rounds, -1.0, 0.0, 0)
+            ms = []
+            for i in range(warmup + calls):
+                inst.robust_device(prm, lay, jobs)
+                if i >= warmup:
+                    ms.append(inst.info().ms_call)
+            energy, iters = inst.robust_trace()
+            rec = {"probe": "robust_coupled_time", "form": rc.NAMES[cpl], "size": n, "channels": 3, "border": "neumann", "base_links": bool(base_links),
+                   "problem": "tv_denoise: zero guidance, weight 2, p = 1, q = 2, eps = 1e-2", "rounds": rounds, "calls": calls,
+                   "ms_call": round(float(np.median(ms)), 4), "inner_iterations": [int(v) for v in iters], "sweeps": int(inst.info().sweeps),
+                   "energy_first_last": [float(energy[0]), float(energy[-1])]}
+            print(json.dumps(rec), flush=True)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+    finally:
+        for p in dev.values():
+            inst.free(p)
 
 
 def timing(capi, inst, path, calls, warmup, host_loop):
@@ -220,15 +325,29 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-host-loop", action="store_true")
+    ap.add_argument("--coupling", choices=["iso", "joint", "both", "all"], help="measure the coupled gradient terms instead")
+    ap.add_argument("--base-links", action="store_true", help="--coupling --time: the jobs carry base links")
     a = ap.parse_args()
+    if a.coupling:
+        couplings = {"iso": [1], "joint": [2], "both": [3], "all": [1, 2, 3]}[a.coupling]
+        if a.lengths_out == ap.get_default("lengths_out"):
+            a.lengths_out = os.path.join(ROOT, "profiles", "robust_coupled_lengths.txt")
+        if a.time_out == ap.get_default("time_out"):
+            a.time_out = os.path.join(ROOT, "profiles", "robust_coupled_probe.json")
     sys.path.insert(0, ROOT)
     from seamlesscloneoptimization_amd import capi
     inst = capi.Instance(0)
     try:
-        if a.lengths:
-            lengths(capi, inst, a.lengths_out)
-        if a.time:
-            timing(capi, inst, a.time_out, a.calls, a.warmup, not a.no_host_loop)
+        if a.coupling:
+            if a.lengths:
+                coupled_lengths(capi, inst, a.lengths_out, couplings)
+            if a.time:
+                coupled_timing(capi, inst, a.time_out, a.calls, a.warmup, couplings, a.base_links)
+        else:
+            if a.lengths:
+                lengths(capi, inst, a.lengths_out)
+            if a.time:
+                timing(capi, inst, a.time_out, a.calls, a.warmup, not a.no_host_loop)
     finally:
         inst.destroy()
 
