@@ -807,6 +807,86 @@ SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poi
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
+/* ---- region solves: known pixels, outside pixels, a domain of any shape -----------------------------------------------------------------
+ * The problem: sc_hip_wls's, per channel, with one more array, state, under the call's layout (float32, per channel, read like weight).
+ * Its values are exactly 0.0f, 1.0f or 2.0f:
+ *     SC_REGION_UNKNOWN (0)   the pixel is solved for;
+ *     SC_REGION_KNOWN   (1)   u = data there, exactly;
+ *     SC_REGION_OUTSIDE (2)   the pixel is not part of the domain: every link to it does not exist (a natural border, as at a free side).
+ * This is the region Omega of Poisson image editing in any shape (values fixed everywhere outside it), hard constraints at arbitrary
+ * pixels (inpainting a hole from its rim, scribbles that hold exactly, depth or flow completion from valid samples) and domains with
+ * holes or cuts (invalid depth, the outside of a segmentation).  state is consulted only at the pixels the border kind calls unknowns;
+ * Dirichlet lines keep their meaning and are read from boundary.  Every border kind of sc_hip_wls is accepted.
+ * Links: a link is LIVE IN THE REGION when it is live in the WLS sense, neither end is OUTSIDE and at least one end is an UNKNOWN
+ * pixel.  KNOWN - KNOWN links and KNOWN - Dirichlet links are dead.  A link to a KNOWN pixel q acts as a link to a Dirichlet pixel: it
+ * adds s to the diagonal of its unknown end and s * data(q) to the right-hand side.  smooth_x and smooth_y are both given or both NULL;
+ * NULL: every link is 1 (the bytes of a call given arrays of 1.0f).
+ * The data term: weight may be NULL: there is no data term, and data is then not read at UNKNOWN pixels (with every state 0 the
+ * bytes of sc_hip_wls given a weight array of 0.0f).  In a device call the first job decides for weight and for the link arrays; a job
+ * that differs gets SC_ERR_BAD_ARG.
+ * The right-hand side at an UNKNOWN pixel, in float32, in this order: with SC_POISSON_LAPLACIAN lap is taken as given (read at UNKNOWN
+ * pixels only); with SC_POISSON_GUIDANCE (a - b) + (c - d) of the separately rounded products s * g as in sc_hip_wls, the term of a link
+ * that is not live in the region counting 0 and not read.  Then - w * d, one rounded multiply and one subtract (weight given).  Then
+ * the Dirichlet lines' terms s * boundary: west, north, east, south.  Then the KNOWN neighbours' terms s * data(q): west, north, east,
+ * south.  Each is a rounded product subtracted in turn.
+ * What is read: state at every pixel the border kind calls an unknown; weight and lap at UNKNOWN pixels; a link weight and its g only
+ * where the link is live in the region; data at UNKNOWN pixels when weight is given, and at KNOWN and OUTSIDE pixels always; boundary
+ * on its Dirichlet lines.  Nothing else is read.
+ * What is written: every element the layout names -- the solution at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels,
+ * boundary's bits on the Dirichlet lines.  out may equal data or boundary.  state, weight and the link arrays must not overlap out
+ * (sc_hip_wls's span rule).
+ * Solved by the WLS call's conjugate gradients on the whole rectangle, unknowns and others alike: the set-up leaves every coefficient and
+ * the right-hand side 0 at a pixel that is not UNKNOWN, which makes the iteration that of the UNKNOWN pixels alone, preconditioned by
+ * M = s-bar (A - w-bar / s-bar), A the constant-coefficient operator of the border kind on the whole rectangle: s-bar = precond_smooth,
+ * or the mean of the links live in the region over the call's chunk; w-bar = precond_lambda, or (the sum of w over the UNKNOWN pixels +
+ * the sum of the UNKNOWN - KNOWN links) / (the number of UNKNOWN pixels) over the chunk.  The rectangle's solve does not know where the
+ * constraints are: with unit links and zero guidance, scattered known pixels take about 30 iterations at any size, regions whose values
+ * come from their rim alone about 1.5 times more per doubling of the side -- at 1024 x 1024 an ellipse of unknowns 123, a known frame
+ * around an excluded blob 197, at 2048 x 2048 194 and 311 (DESIGN.md sections 4 and 7); raise max_iters for larger ones.
+ * Stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, chunks, batches (a member agrees with its solo run to the stop rule's error),
+ * methods, sizes, host waits and sc_run_info: the WLS call's.  A plane without any UNKNOWN pixel is valid: it converges without an
+ * iteration, data and boundary are copied.  Two runs of one call give the same bytes.  With every state 0 the call writes the bytes of
+ * sc_hip_wls with the same parameters.
+ * Codes: the WLS call's for parameters and layout.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others run -- for a
+ * state element that is not 0, 1 or 2 (NaN included); a weight that is negative or not finite or a link that is not finite or not > 0,
+ * judged where it is read; a NULL or misaligned pointer the call needs (data and state always), exactly one of smooth_x / smooth_y,
+ * a weight or link arrays where the first job has none (or the reverse), state, weight or a link array overlapping out; and, in a call
+ * without any Dirichlet line, a channel with UNKNOWN pixels but no UNKNOWN - KNOWN link and no positive weight ("nothing pins the
+ * channel").
+ * NOT detected, the caller's responsibility: a connected component of UNKNOWN pixels that nothing pins (no KNOWN neighbour, no Dirichlet
+ * line, no weight) while other components are pinned.  In the guidance form the system stays consistent and the call returns some
+ * constant offset on that component; with SC_POISSON_LAPLACIAN it need not converge.
+ * Not offered: region states in the robust call or through the 8-bit clone and edit entry points. */
+#define SC_REGION_UNKNOWN 0
+#define SC_REGION_KNOWN   1
+#define SC_REGION_OUTSIDE 2
+typedef struct sc_region_params {
+    int   kind;              /* as sc_wls_params.kind */
+    float tol;               /* stop when ||r||_2 <= tol * ||b||_2 on every plane; <= 0: 1e-5 */
+    int   max_iters;         /* <= 0: 400 */
+    float precond_lambda;    /* w-bar of the preconditioner; <= 0: (sum of w + sum of UNKNOWN - KNOWN links) / UNKNOWN pixels of the chunk */
+    float precond_smooth;    /* s-bar of the preconditioner; <= 0: the mean of the links live in the region of the chunk */
+} sc_region_params;
+typedef struct sc_region_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE: read at links live in the region */
+    const float *lap;        /* SC_POISSON_LAPLACIAN: read at UNKNOWN pixels */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* > 0 where live in the region; both NULL: every link 1 */
+    const float *smooth_y;
+    const float *boundary;   /* its Dirichlet lines (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_region_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_region_check(const sc_region_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_region_device(void *instance, const sc_region_params *p, const sc_poisson_layout *l, sc_region_job *jobs, int n, bool bSync);
+/* One problem on host arrays, as sc_hip_wls: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                         const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x,
+                         const float *smooth_y, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -236,6 +236,22 @@ class WlsJob(C.Structure):
                 ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# region solves (sc_hip_region*): Instance.region / region_device -- the values of a state array (float32 0.0, 1.0, 2.0 on the device)
+SC_REGION_UNKNOWN = 0       # solved for
+SC_REGION_KNOWN = 1         # u = data there, exactly
+SC_REGION_OUTSIDE = 2       # not part of the domain: its links do not exist
+
+
+class RegionParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("tol", C.c_float), ("max_iters", C.c_int), ("precond_lambda", C.c_float), ("precond_smooth", C.c_float)]
+
+
+class RegionJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p),
+                ("weight", C.c_void_p), ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p),
+                ("rc", C.c_int)]
+
+
 # robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
 SC_ROBUST_ISOTROPIC = 1 << 20        # or'ed into RobustParams.kind only: one penalty per pixel over its two forward links
 SC_ROBUST_JOINT_CHANNELS = 1 << 21   # ... one penalty over all channels of a job (both: vectorial TV)
@@ -453,6 +469,12 @@ def load():
     L.sc_hip_wls_device.restype = C.c_int
     L.sc_hip_wls.argtypes = [C.c_void_p, C.POINTER(WlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
     L.sc_hip_wls.restype = C.c_int
+    L.sc_hip_region_check.argtypes = [C.POINTER(RegionParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_region_check.restype = C.c_int
+    L.sc_hip_region_device.argtypes = [C.c_void_p, C.POINTER(RegionParams), C.POINTER(PoissonLayout), C.POINTER(RegionJob), C.c_int, C.c_bool]
+    L.sc_hip_region_device.restype = C.c_int
+    L.sc_hip_region.argtypes = [C.c_void_p, C.POINTER(RegionParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 10
+    L.sc_hip_region.restype = C.c_int
     L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_robust_check.restype = C.c_int
     L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
@@ -626,18 +648,25 @@ def wls_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, max_iters: int 
                        row_stride=row_stride, channel_stride=channel_stride)
 
 
+def border_unknowns(kind: int, H: int, W: int):
+    """Boolean H x W: the pixels a call of this kind calls unknowns (everything but its Dirichlet lines) -- where a region call reads state."""
+    px, py = bool(kind & SC_POISSON_PERIODIC_X), bool(kind & SC_POISSON_PERIODIC_Y)
+    neu = bool(kind & SC_POISSON_NEUMANN)
+    u = np.ones((H, W), bool)
+    if not px:
+        u[:, 0] &= neu or bool(kind & SC_POISSON_FREE_LEFT)
+        u[:, -1] &= neu or bool(kind & SC_POISSON_FREE_RIGHT)
+    if not py:
+        u[0] &= neu or bool(kind & SC_POISSON_FREE_TOP)
+        u[-1] &= neu or bool(kind & SC_POISSON_FREE_BOTTOM)
+    return u
+
+
 def live_links(kind: int, H: int, W: int):
     """(live_x, live_y), boolean H x W: the elements of smooth_x / smooth_y that a WLS call of this kind reads -- the links with at least
     one end among the unknowns; the last column / row holds the wrapping link of a periodic axis and is not live otherwise."""
     px, py = bool(kind & SC_POISSON_PERIODIC_X), bool(kind & SC_POISSON_PERIODIC_Y)
-    neu = bool(kind & SC_POISSON_NEUMANN)
-    unknown = np.ones((H, W), bool)
-    if not px:
-        unknown[:, 0] &= neu or bool(kind & SC_POISSON_FREE_LEFT)
-        unknown[:, -1] &= neu or bool(kind & SC_POISSON_FREE_RIGHT)
-    if not py:
-        unknown[0] &= neu or bool(kind & SC_POISSON_FREE_TOP)
-        unknown[-1] &= neu or bool(kind & SC_POISSON_FREE_BOTTOM)
+    unknown = border_unknowns(kind, H, W)
     lx = unknown | np.roll(unknown, -1, 1)
     ly = unknown | np.roll(unknown, -1, 0)
     if not px:
@@ -666,6 +695,111 @@ def wls_arrays(data, weight, smooth_x, smooth_y, gx=None, gy=None, lap=None, bou
             raise ValueError(f"{name} must be finite and > 0 on every live link")
         links.append(a)
     return kind, data, weight, links[0], links[1], gx, gy, lap, boundary, out
+
+
+def region_check(kind: int = SC_POISSON_GUIDANCE, tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0,
+                 layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                 channel_stride=None) -> int:
+    """Host-only sc_hip_region_check: SC_OK or the code a region call with these parameters and this layout returns before it runs
+    anything.  The layout as a PoissonLayout or as keyword fields."""
+    p = RegionParams(int(kind), float(tol), int(max_iters), float(precond_lambda), float(precond_smooth))
+    return _check_call("sc_hip_region_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def region_unpinned(kind: int, state, weight=None):
+    """Boolean array of state's shape (H x W or H x W x C): the UNKNOWN pixels of connected components that nothing pins -- no KNOWN
+    neighbour, no Dirichlet line of the kind next to them and no positive weight (weight None: no data term).  A flood fill in numpy from
+    the pinned pixels through the links between UNKNOWN pixels; a region call does not detect such components (its result there is
+    some constant in the guidance form)."""
+    st = np.asarray(state)
+    st3 = st[:, :, None] if st.ndim == 2 else st
+    H, W = st3.shape[:2]
+    px, py = bool(kind & SC_POISSON_PERIODIC_X), bool(kind & SC_POISSON_PERIODIC_Y)
+    inside = border_unknowns(kind, H, W)[:, :, None]
+    unk = (st3 == SC_REGION_UNKNOWN) & inside
+    # a Dirichlet pixel acts as a KNOWN one
+    fixed = ((st3 == SC_REGION_KNOWN) & inside) | np.broadcast_to(~inside, st3.shape)
+
+    def neighbours(a):          # the four shifted copies of a: a's value at the pixel across each link, False where there is none
+        out = []
+        for axis, wraps in ((1, px), (0, py)):
+            for step in (1, -1):
+                r = np.roll(a, step, axis).copy()
+                if not wraps:
+                    edge = [slice(None)] * 3
+                    edge[axis] = 0 if step == 1 else -1
+                    r[tuple(edge)] = False
+                out.append(r)
+        return out
+
+    pinned = unk & np.logical_or.reduce(neighbours(fixed))
+    if weight is not None:
+        w = np.asarray(weight)
+        pinned |= unk & ((w[:, :, None] if w.ndim == 2 else w) > 0)
+    while True:
+        grown = pinned | (unk & np.logical_or.reduce(neighbours(pinned)))
+        if (grown == pinned).all():
+            break
+        pinned = grown
+    loose = unk & ~pinned
+    return loose[:, :, 0] if st.ndim == 2 else loose
+
+
+def region_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, gx=None, gy=None, lap=None, boundary=None, out=None, neumann=False,
+                  free_sides="", periodic=""):
+    """Checks a region problem's numpy arrays before any device is touched: (kind, data, state, weight, smooth_x, smooth_y, gx, gy, lap,
+    boundary, out).  data: float32, H x W or H x W x C.  state: of data's shape or H x W (broadcast over the channels); float32, an
+    integer type or bool, holding SC_REGION_UNKNOWN (0, False), SC_REGION_KNOWN (1, True) or SC_REGION_OUTSIDE (2) at every pixel the
+    borders call an unknown (border_unknowns; elsewhere it is not read) -- returned as float32.  weight: None (no data term) or as
+    weighted_arrays'.  smooth_x, smooth_y: both None (every link 1) or as wls_arrays', judged on the device where they are live in the
+    region.  Neither gx, gy nor lap: zero guidance (lap = 0).  boundary is required when a side keeps a Dirichlet line."""
+    all_free = no_dirichlet(border_bits(free_sides, neumann, periodic))
+    if data is None or state is None:
+        raise ValueError("a region solve needs data and state")
+    _same_shape_f32("data", data, data)
+    if not isinstance(state, np.ndarray):
+        raise TypeError("state must be a numpy array (float32, an integer type or bool)")
+    if state.dtype != np.float32 and state.dtype != np.bool_ and not np.issubdtype(state.dtype, np.integer):
+        raise TypeError("state must be float32, an integer type or bool")
+    if (smooth_x is None) != (smooth_y is None):
+        raise ValueError("smooth_x and smooth_y go together (both None: every link 1)")
+
+    def broadcast(name, a):
+        if a.ndim == 2 and data.ndim == 3 and a.shape == data.shape[:2]:
+            a = np.ascontiguousarray(np.broadcast_to(a[:, :, None], data.shape))
+        if a.shape != data.shape:
+            raise ValueError(f"{name} has shape {a.shape}, the problem {data.shape}")
+        return a
+
+    state = broadcast("state", state.astype(np.float32))
+    if gx is None and gy is None and lap is None:
+        lap = np.zeros(data.shape, np.float32)
+    if all_free:
+        boundary = None
+    elif boundary is None:
+        raise ValueError("a region solve with a Dirichlet line needs boundary")
+    kind, _, gx, gy, lap, out = poisson_arrays(data, gx, gy, lap, out, neumann, free_sides, periodic)
+    read = border_unknowns(kind, *data.shape[:2])
+    if not np.isin(state[read], (0.0, 1.0, 2.0)).all():
+        raise ValueError("state must hold 0 (unknown), 1 (known) or 2 (outside) at every pixel the borders call an unknown")
+    if boundary is not None:
+        _same_shape_f32("boundary", boundary, data)
+    if weight is not None:
+        if not isinstance(weight, np.ndarray):
+            raise TypeError("weight must be a float32 numpy array")
+        weight = broadcast("weight", weight)
+        _same_shape_f32("weight", weight, data)
+    if smooth_x is not None:
+        links = []
+        for name, a in (("smooth_x", smooth_x), ("smooth_y", smooth_y)):
+            if not isinstance(a, np.ndarray):
+                raise TypeError(f"{name} must be a float32 numpy array")
+            a = broadcast(name, a)
+            _same_shape_f32(name, a, data)
+            links.append(a)
+        smooth_x, smooth_y = links
+    return kind, data, state, weight, smooth_x, smooth_y, gx, gy, lap, boundary, out
 
 
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
@@ -975,6 +1109,30 @@ class Instance:
         the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures raise unless
         allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- region solves on float32 arrays
+    def region(self, data, state, weight=None, smooth_x=None, smooth_y=None, gx=None, gy=None, lap=None, boundary=None, neumann=False,
+               out=None, free_sides="", periodic="", tol=0.0, max_iters=0, precond_lambda=0.0, precond_smooth=0.0, allow_not_converged=False):
+        """sc_hip_region on numpy float32 arrays of shape H x W or H x W x C (C 1..4): wls()'s problem on a domain of any shape.
+        state (region_arrays' types; of data's shape or H x W) says of every pixel inside the borders whether it is solved for
+        (SC_REGION_UNKNOWN), held at data's value (SC_REGION_KNOWN) or not part of the domain (SC_REGION_OUTSIDE: no link reaches it).
+        weight None: no data term; smooth_x, smooth_y None: every link 1.  Returns out: the solution at UNKNOWN pixels, data at KNOWN
+        and OUTSIDE ones, boundary on the Dirichlet lines; info() has the iterations and the final residual."""
+        kind, data, state, weight, sx, sy, gx, gy, lap, boundary, out = region_arrays(data, state, weight, smooth_x, smooth_y, gx, gy, lap,
+                                                                                      boundary, out, neumann, free_sides, periodic)
+        p = RegionParams(kind, float(tol), int(max_iters), float(precond_lambda), float(precond_smooth))
+        return self._host_call("sc_hip_region", p, (gx, gy, lap, data, state, weight, sx, sy, boundary), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_region_jobs(n: int):
+        return (RegionJob * n)()
+
+    def region_device(self, params: RegionParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_region_device: jobs is a RegionJob array (make_region_jobs) of device pointers, one layout for all.  sync: bSync and a
+        wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures
+        raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_region_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",

@@ -404,6 +404,10 @@ int main()
             if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check");
             q.precond_smooth = k.plam;          // (the same values make the same verdicts)
             if (sc_hip_wls_check(&q, &l) != k.want) return fail("wls_check (precond_smooth)");
+            sc_region_params rg{ k.kind, k.tol, k.iters, k.plam, 0.f };          // the region call: the WLS call's verdicts
+            if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check");
+            rg.precond_smooth = k.plam;
+            if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check (precond_smooth)");
             // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
             const bool lap_base = (k.kind & 3) == SC_POISSON_LAPLACIAN;
             sc_robust_params r{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
@@ -420,6 +424,8 @@ int main()
                 if (sc_hip_robust_check(&r, &l) != got) return fail("robust_check (coupling bits)");
                 p.kind = q.kind = k.kind | bits;
                 if (sc_hip_weighted_check(&p, &l) != SC_ERR_BAD_ARG || sc_hip_wls_check(&q, &l) != SC_ERR_BAD_ARG) return fail("weighted_check / wls_check (coupling bits)");
+                rg.kind = k.kind | bits;
+                if (sc_hip_region_check(&rg, &l) != SC_ERR_BAD_ARG) return fail("region_check (coupling bits)");
                 sc_poisson_params pp{ k.kind | bits, 0.f };
                 sc_screened_params sp{ k.kind | bits, 1.f };
                 if (sc_hip_poisson_check(&pp, &l) != SC_ERR_BAD_ARG || sc_hip_screened_check(&sp, &l) != SC_ERR_BAD_ARG) return fail("poisson_check / screened_check (coupling bits)");

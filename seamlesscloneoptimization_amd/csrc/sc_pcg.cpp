@@ -30,6 +30,8 @@ constexpr int W_LAG = PcgState::LAG, W_RING = PcgState::RING;
 
 // One chunk of m same-size jobs.  Jobs that their family's statistics refuse get their code here and take no further part; the rest
 // share every solve and one code.
+void PcgOperator::out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) { launch_pcg_out(g, wg, dj.data(), mv, U, s); }
+
 int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, int &job_errors, PcgChunk &c)
 {
     c = PcgChunk();
@@ -183,7 +185,7 @@ int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &r
 int pcg_chunk_finish(PcgChunk &c, PcgOperator &op, int code)
 {
     Instance *I = c.I;
-    launch_pcg_out(c.g, c.wg, op.dj.data(), c.mv, c.U, I->stream);
+    op.out(c.g, c.wg, c.mv, c.U, I->stream);
     SC_HIP(I, hipGetLastError());
     for (int k = 0; k < c.mv; ++k) *c.live[k] = code;
     return code;
@@ -255,6 +257,7 @@ int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, 
     if ((rc = float_stage(I, l, call.kind, carries, a, s))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
     op.bind(&s.d_w, &s.d_sx, &s.d_sy);
+    op.bind_state(&s.d_state);
     rc = pcg_run(I, call, l, op, &s.job, job_rcs, 1, true, chunk);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)

@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
+// sc_wls.hip, sc_robust.hip, sc_region.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
 // (WlsOperator, sc_wls_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
 // Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
@@ -52,6 +52,7 @@ struct PcgOperator {
     virtual ~PcgOperator() = default;
     // the call's weights and link weights, one pointer per job (pcg_host_call, pcg_device_call: once the staged or taken-in tables exist)
     virtual void bind(const float *const *w, const float *const *sx, const float *const *sy) = 0;
+    virtual void bind_state(const float *const *state) {}                           // ... and its state arrays (the region call's; the others have none)
     virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
     virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
     // st: job k's statistics, its C planes' PCG_PARTS * nstat doubles each, of which the first `parts` parts are set
@@ -62,6 +63,8 @@ struct PcgOperator {
     // on the preconditioner changes no later iterate, so the loop never applies it).  The default: none.
     virtual void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) {}
     virtual void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) = 0;
+    // the output launch of the mv jobs that stayed (dj): by default U at the unknowns and boundary's values on the Dirichlet lines
+    virtual void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s);
     // the sum of field f of one plane's statistics over its first `parts` parts
     double stat_sum(const double *plane, int parts, int f) const
     {
@@ -145,6 +148,7 @@ template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgC
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
     op.bind(v.w.data(), v.sx.data(), v.sy.data());
+    op.bind_state(v.st.data());
     return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
 }
 
@@ -205,8 +209,8 @@ struct WlsOperator : PcgOperator {
     double wsum = 0.0, ssum = 0.0;                 // the sums of the weights and of the live links of the jobs that stay
     bool unit_links = false;                       // every live link is 1: s-bar is
     float u0_scale = 1.f;                          // 1 / s-bar
-    WlsOperator(Instance *I_, bool links_, float plam_, float psmooth_, int nround_ = 0)
-        : PcgOperator(links_ ? WLS_STATS : 2, nround_), I(I_), links(links_), plam(plam_), psmooth(psmooth_) {}
+    WlsOperator(Instance *I_, bool links_, float plam_, float psmooth_, int nround_ = 0, int nstat_ = 0)      // nstat_: a subclass's own statistics
+        : PcgOperator(nstat_ ? nstat_ : links_ ? WLS_STATS : 2, nround_), I(I_), links(links_), plam(plam_), psmooth(psmooth_) {}
     void bind(const float *const *w, const float *const *sx, const float *const *sy) override { all_w = w; all_sx = sx; all_sy = sy; }
     void begin(int i0, int m) override;
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override;
@@ -216,6 +220,22 @@ struct WlsOperator : PcgOperator {
     void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override;
     void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override;
 };
+
+// ---- the region family (sc_region.hip): the WLS system on a domain of any shape -- per job one more array, state, under the call's
+// layout: 0 an unknown, 1 known (u = data), 2 outside the domain (its links do not exist); w NULL: no data term, sx NULL: every link 1
+struct RegionJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX], *st[MAX]; };
+constexpr int REGION_STATS = 8;
+// stats[(plane * PCG_PARTS + i) * REGION_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
+// the sum of its links live in the region, each counted once | how many of them are invalid | its UNKNOWN pixels | the sum of its
+// UNKNOWN - KNOWN links | its state elements that are not 0, 1 or 2 | its links live in the region
+void launch_region_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                         const float *const *sy, const float *const *st, int m, double *stats, hipStream_t s);
+// R = b (the order: seamlessclone_hip.h, the region section); E / S = the link to the next column / row where both ends are UNKNOWN; Dg =
+// the sum of the incident links live in the region plus w; all four 0 at every pixel that is not UNKNOWN; bb = the parts of b . b
+void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
+                         const float *const *sy, const float *const *st, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
+// the jobs' out: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
+void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *st, int m, const float *U, hipStream_t s);
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;

@@ -135,9 +135,18 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
             if (!q) { *why = "null smooth_x or smooth_y pointer"; return SC_ERR_BAD_ARG; }
             if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
         }
+    }
+    if (carries & FLOAT_STATE) {
+        if (!a.state) { *why = "null state pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(a.state)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
+    if (span && (carries & (FLOAT_SMOOTH | FLOAT_STATE))) {
         const uintptr_t o = (uintptr_t)a.out, bytes = span * sizeof(float);
-        for (const float *q : { a.weight, a.smooth_x, a.smooth_y })
-            if (span && (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes) { *why = "weight, smooth_x or smooth_y overlaps out"; return SC_ERR_BAD_ARG; }
+        auto overlaps = [&](const float *q) { return (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes; };
+        for (const float *q : { carries & FLOAT_WEIGHT ? a.weight : nullptr, carries & FLOAT_SMOOTH ? a.smooth_x : nullptr,
+                                carries & FLOAT_SMOOTH ? a.smooth_y : nullptr })
+            if (q && overlaps(q)) { *why = "weight, smooth_x or smooth_y overlaps out"; return SC_ERR_BAD_ARG; }
+        if ((carries & FLOAT_STATE) && overlaps(a.state)) { *why = "state overlaps out"; return SC_ERR_BAD_ARG; }
     }
     return SC_OK;
 }
@@ -157,8 +166,8 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     // (the Poisson call keeps a boundary without a Dirichlet line: it gives the mean)
     const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
-    const bool smooth = (carries & FLOAT_SMOOTH) != 0;
-    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0);
+    const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0;
+    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -168,7 +177,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_in0 = next(true), *d_in1 = next(guidance), *d_d = next(data != nullptr), *d_w = next(weight != nullptr);
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
-    float *d_sx = next(smooth), *d_sy = next(smooth);
+    float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -181,6 +190,8 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     if ((rc = upload(I->h_sy, d_sy, a.smooth_y))) return rc;
     s.d_sx = d_sx;
     s.d_sy = d_sy;
+    if ((rc = upload(I->h_state, d_state, a.state))) return rc;
+    s.d_state = d_state;
     return SC_OK;
 }
 

@@ -518,6 +518,110 @@ def wls_solve_batch(datas, weights, smooth_xs, smooth_ys, gxs=None, gys=None, la
                       make_jobs=capi.Instance.make_wls_jobs, device_call=capi.Instance.wls_device)
 
 
+def _region_validate(kind, state, weight):
+    loose = capi.region_unpinned(kind, state, weight)
+    if loose.any():
+        raise ValueError(f"validate: {int(loose.sum())} unknown pixels lie in components that nothing pins (no known neighbour, no Dirichlet "
+                         "line, no weight)")
+
+
+def region_solve(data, state, gx=None, gy=None, laplacian=None, weight=None, smooth_x=None, smooth_y=None, boundary=None, neumann=True,
+                 free_sides=None, periodic="", tol=None, validate=False, max_iters=None, precond_lambda=None, precond_smooth=None, gpu_id=0,
+                 **solver):
+    """Region solve on a float32 image of shape H x W or H x W x C (C 1..4): wls_solve's problem on a domain of any shape, with hard
+    constraints at any pixel.  state (of data's shape or H x W; float32, integers or bool) holds per pixel 0 (False): solved for, 1
+    (True): known, the result is data there exactly, 2: outside the domain, no link reaches the pixel (a natural border, as at a free
+    side); the result is data at known and outside pixels.  weight None: no data term (otherwise read at the unknown pixels, like data);
+    smooth_x, smooth_y None: every link 1.  Guidance, borders (neumann by default), tol, max_iters (400), precond_lambda, precond_smooth:
+    wls_solve's.  Every connected component of unknown pixels must be pinned by a known neighbour, a Dirichlet line or a positive
+    weight; the library only notices a whole channel that nothing pins -- validate=True checks every component first (a numpy flood
+    fill) and raises ValueError.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    kind, data, state, weight, sx, sy, gx, gy, lap, b, _ = capi.region_arrays(data, state, weight, smooth_x, smooth_y, gx, gy, laplacian, boundary,
+                                                                             neumann=neumann, free_sides=free_sides, periodic=periodic)
+    if validate:
+        _region_validate(kind, state, weight)
+    with _instance(gpu_id, solver) as inst:
+        return inst.region(data, state, weight, sx, sy, gx=gx, gy=gy, lap=lap, boundary=b, neumann=neumann, free_sides=free_sides,
+                           periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0, precond_lambda=precond_lambda or 0.0,
+                           precond_smooth=precond_smooth or 0.0)
+
+
+def region_solve_batch(datas, states, gxs=None, gys=None, laplacians=None, weights=None, smooth_xs=None, smooth_ys=None, boundaries=None,
+                       neumann=True, free_sides=None, periodic="", tol=None, validate=False, max_iters=None, precond_lambda=None,
+                       precond_smooth=None, gpu_id=0, **solver):
+    """region_solve over a list of same-shape problems through ONE device-resident call (sc_hip_region_device), as wls_solve_batch: one
+    copy in, one copy out, one joint stop, the preconditioner's two constants the chunk's -- a member agrees with its solo solve to the
+    stop rule's error.  weights, smooth_xs and smooth_ys: for every problem or None.  Returns a list of NEW arrays."""
+    def arrays_of(d, a, borders):
+        kind, d, st, w, sx, sy, gx, gy, lap, b, _ = capi.region_arrays(d, a["state"], a.get("weight"), a.get("smooth_x"), a.get("smooth_y"),
+                                                                      a.get("gx"), a.get("gy"), a.get("lap"), a.get("boundary"), **borders)
+        if validate:
+            _region_validate(kind, st, w)
+        return kind, dict(gx=gx, gy=gy, lap=lap, data=d, state=st, weight=w, smooth_x=sx, smooth_y=sy, boundary=b)
+    refusal = _GUIDANCE_WHY if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None) else \
+        "smooth_xs and smooth_ys go together" if (smooth_xs is None) != (smooth_ys is None) else None
+    return _pcg_batch("region", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(state=states), optional=dict(gx=gxs, gy=gys, lap=laplacians, weight=weights, smooth_x=smooth_xs, smooth_y=smooth_ys),
+                      refusal=refusal,
+                      length_why="one state and, where given, one weight, one pair of link weights, one guidance field (or laplacian) and, with a "
+                                 "Dirichlet line, one boundary per data term",
+                      arrays_of=arrays_of, slots=("gx", "gy", "lap", "data", "state", "weight", "smooth_x", "smooth_y", "boundary"),
+                      params_of=lambda kind: capi.RegionParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0),
+                                                               float(precond_smooth or 0.0)),
+                      make_jobs=capi.Instance.make_region_jobs, device_call=capi.Instance.region_device)
+
+
+def _mask_of(name, mask, image):
+    m = np.asarray(mask)
+    if m.shape != image.shape[:2]:
+        raise ValueError(f"{name} has shape {m.shape}, the image {image.shape[:2]}")
+    return m.astype(bool)
+
+
+def inpaint(image, hole, gpu_id=0, **solver):
+    """Membrane fill of a float32 image (H x W or H x W x C): the pixels where hole (H x W, anything truthy) is set are replaced by the
+    harmonic interpolation of the pixels around them -- region_solve with zero guidance, every pixel outside the hole known, reflecting
+    borders where the hole touches the image's edge.  Returns a NEW array; pixels outside the hole keep their bits."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    h = _mask_of("hole", hole, image)
+    if h.all():
+        raise ValueError("the hole covers the whole image: nothing to fill it from")
+    state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    return region_solve(image, state, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def _forward_differences(a):
+    """(d/dx, d/dy) of a float32 array, of its shape: a[y, x+1] - a[y, x] and a[y+1, x] - a[y, x]; the last column / row holds 0"""
+    gx, gy = np.zeros_like(a), np.zeros_like(a)
+    gx[:, :-1] = a[:, 1:] - a[:, :-1]
+    gy[:-1] = a[1:] - a[:-1]
+    return gx, gy
+
+
+def poisson_clone(src, dst, mask, mixed=False, gpu_id=0, **solver):
+    """Poisson image editing (Perez, Gangnet, Blake 2003) on float32 images of one shape (H x W or H x W x C): inside mask (H x W,
+    anything truthy) the result has src's forward differences, outside it is dst, bit for bit, and it is continuous across the mask's
+    edge -- the region of the paper in its exact shape, solved in float32 (seamlessClone is the 8-bit clone of a patch at a position).
+    mixed: per link the guidance is src's difference or dst's, whichever is larger in magnitude (mixed gradients: dst's texture shows
+    through flat parts of src).  A mask that touches the image's edge gets a reflecting border there.  Returns a NEW array."""
+    for name, a in (("src", src), ("dst", dst)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+    if src.shape != dst.shape:
+        raise ValueError(f"src has shape {src.shape}, dst {dst.shape}")
+    m = _mask_of("mask", mask, dst)
+    if m.all():
+        raise ValueError("the mask covers the whole image: nothing of dst is left to join")
+    gx, gy = _forward_differences(src)
+    if mixed:
+        dx, dy = _forward_differences(dst)
+        gx, gy = np.where(np.abs(dx) > np.abs(gx), dx, gx), np.where(np.abs(dy) > np.abs(gy), dy, gy)
+    state = np.where(m, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    return region_solve(dst, state, gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
+
+
 def _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters):
     return capi.RobustParams(kind, float(p), float(eps_grad), float(q), float(eps_data), int(max_rounds or 0), float(round_tol or 0.0),
                              float(tol or 0.0), int(max_iters or 0))
@@ -636,14 +740,16 @@ def wls_filter(image, lam=1.0, alpha=1.2, eps=1e-4, guide=None, gpu_id=0, **solv
     return wls_solve(image, np.ones(image.shape[:2], np.float32), sx, sy, neumann=True, gpu_id=gpu_id, **solver)
 
 
-def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, guide=None, edge_sigma=None, **solver):
+def interpolate_constraints(values, known_mask, image_gradients=None, strength=1.0, gpu_id=0, guide=None, edge_sigma=None, hard=False, **solver):
     """Fills a float32 image (H x W or H x W x C) from the pixels where known_mask (H x W, anything truthy) is set: the weighted solve
     with weight = strength on the mask and 0 elsewhere, data = values, under reflecting borders, with zero guidance (a membrane through
     the known pixels) or image_gradients = (gx, gy), forward differences the result should have.  strength weighs closeness to the known
     values against the guidance: large values pin them.  Returns a NEW array.
     guide (H x W or H x W x C, any real dtype): the values stop spreading at the guide's edges -- the WLS solve with the link weights
     exp(-d^2 / (2 edge_sigma^2)) + 1e-3, d the guide's forward difference (over its channels: the root of the summed squares);
-    edge_sigma None: a tenth of the guide's range.  Without a guide edge_sigma must be None too."""
+    edge_sigma None: a tenth of the guide's range.  Without a guide edge_sigma must be None too.
+    hard: the known pixels hold exactly (region_solve with them as known pixels) instead of being pulled towards their values by a
+    weight; strength is then unused, and every part of the image must contain a known pixel."""
     if not isinstance(values, np.ndarray) or values.dtype != np.float32:
         raise TypeError("values must be a float32 numpy array")
     m = np.asarray(known_mask)
@@ -663,8 +769,12 @@ def interpolate_constraints(values, known_mask, image_gradients=None, strength=1
         if not np.isfinite(sigma) or not sigma > 0:
             raise ValueError("edge_sigma must be finite and > 0 (None: a tenth of the guide's range, which must not be flat)")
         sx, sy = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in _forward_abs_differences(g))
+        if hard:
+            return region_solve(values, m.astype(bool), gx=gx, gy=gy, smooth_x=sx, smooth_y=sy, neumann=True, gpu_id=gpu_id, **solver)
         d = np.where(m.astype(bool).reshape(m.shape + (1,) * (values.ndim - 2)), values, np.float32(0)).astype(np.float32)
         return wls_solve(d, w, sx, sy, gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
+    if hard:
+        return region_solve(values, m.astype(bool), gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
     return weighted_solve(np.where(m.astype(bool).reshape(m.shape + (1,) * (values.ndim - 2)), values, np.float32(0)).astype(np.float32), w,
                           gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
 
