@@ -887,6 +887,83 @@ SC_API int sc_hip_region_device(void *instance, const sc_region_params *p, const
 SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x,
                          const float *smooth_y, const float *boundary, float *out);
+/* ---- volume solves: region solves on frame stacks with temporal links ------------------------------------------------------------------
+ * A stack of `frames` >= 2 images (video frames, CT or MRI slices, a depth stack) shares one sc_poisson_layout; in every array of a job
+ * frame t begins frame_stride floats behind frame t - 1.  The unknown is u_t(q).  Per channel the call minimises
+ *     sum_t [ sum_q w (u_t - d_t)^2 + sum |grad u_t - g_t|^2 ]  +  tau sum_{t < frames - 1} sum_q (u_{t+1}(q) - u_t(q) - gt_t(q))^2
+ * over the pixels whose state is SC_REGION_UNKNOWN; u = data where state is SC_REGION_KNOWN; a link does not exist if either of its ends
+ * is SC_REGION_OUTSIDE.  Within a frame this is sc_hip_region's problem with every spatial link 1: border kinds (all of them, periodic
+ * axes included), links live in the region, KNOWN neighbours folded into the right-hand side.  A known keyframe is a frame of 1s:
+ * flicker-free cloning, video inpainting, keyframe propagation, smoothing of a volume along its third axis.
+ * Temporal links: the link between (q, t) and (q, t + 1) follows the spatial rule -- it is live when neither end is OUTSIDE and at
+ * least one end is UNKNOWN.  Its weight is the constant tau.  A KNOWN temporal neighbour adds tau to the diagonal of its unknown end and
+ * tau * data to the right-hand side.  The two ends of time are free: no frame lies before the first or after the last.  Pixels on the
+ * border kind's Dirichlet lines are Dirichlet in every frame; they have no temporal links, as they have no spatial links among
+ * themselves.  gt holds frames - 1 frames (gt_t at t * frame_stride) and may be NULL: zeros, plain temporal smoothness.
+ * SC_POISSON_LAPLACIAN: lap is the complete right-hand side of the three-dimensional system at UNKNOWN pixels (before the Dirichlet and
+ * KNOWN neighbours are folded in, as in sc_hip_region); gx, gy and gt are not read.
+ * weight may be NULL (no data term; data is then not read at UNKNOWN pixels); data and state are required.  In a device call the first
+ * volume decides for weight; a volume that differs gets SC_ERR_BAD_ARG.  gt is each volume's own choice.
+ * The right-hand side at an UNKNOWN pixel, in float32, in this order:
+ *   1. sc_hip_region's guidance sum for the frame, (a - b) + (c - d) of the products 1 * g, a link not live in the region counting 0
+ *      and not read (SC_POISSON_LAPLACIAN: lap, and step 2 is left out);
+ *   2. + (e - f): e the rounded product tau * gt_t(q) where the link to frame t + 1 is live, f the rounded product tau * gt_{t-1}(q)
+ *      where the link to frame t - 1 is live; otherwise each counts 0 and is not read (gt NULL: both 0);
+ *   3. - w * d, one rounded multiply and one subtract (weight given);
+ *   4. the Dirichlet lines' terms 1 * boundary: west, north, east, south;
+ *   5. the KNOWN spatial neighbours' terms 1 * data(q): west, north, east, south;
+ *   6. the KNOWN temporal neighbours' terms tau * data: previous frame, then next frame;
+ *   7. every product of 4 to 6 is rounded on its own and subtracted in turn.
+ * What is read and written is sc_hip_region's, frame by frame: out gets the solution at UNKNOWN pixels, data's bits at KNOWN and
+ * OUTSIDE pixels and boundary's bits on the Dirichlet lines of every frame; row padding, unused channel slots and the floats between
+ * frames are never written.  gt is read only at live temporal links.  out may equal data or boundary; state and weight must not
+ * overlap out (the span rule, the span being all frames').
+ * Solved by conjugate gradients on one system per (volume, channel): the residual norm of the stop rule and the scalars of the
+ * iteration are one per (volume, channel), summed over all its frames.  The preconditioner is M = A - w-bar + tau A_t on the whole
+ * rectangle x frames, A the constant-coefficient operator of the border kind and A_t the free-ended second difference along the
+ * frames; w-bar = precond_lambda, or (the sum of w over the UNKNOWN pixels + the sum of all UNKNOWN - KNOWN links, a spatial one 1 and
+ * a temporal one tau) / (the number of UNKNOWN pixels) over the chunk.  M is inverted exactly: an orthonormal DCT-II along the frames,
+ * one screened direct solve per mode k shifted by w-bar + tau (2 - 2 cos(pi k / frames)), the transposed transform.  With a constant
+ * weight and every state 0 the first iterate is the answer.
+ * Size: frames * channels <= SC_POISSON_MAX_PLANES, else SC_ERR_BAD_SIZE; a chunk holds floor(SC_POISSON_MAX_PLANES / (frames *
+ * channels)) volumes.  Stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, methods, SC_FLAG_FFT_FP64 limits, host waits and
+ * sc_run_info: the region call's.  Two runs of one call give the same bytes.
+ * Codes: SC_ERR_BAD_ARG for frames < 2, a frame_stride below the span of one frame under the layout (frames would overlap), tau that
+ * is not finite or not > 0, and everything sc_hip_region_check refuses.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the
+ * others run -- for every per-job refusal of the region call, with the pin check judged per channel over the whole volume and not per
+ * frame: a channel whose middle frames hold no KNOWN pixel is fine when time links them to frames that do.  A channel is refused only
+ * when the call has no Dirichlet line, the channel has UNKNOWN pixels, and the volume has no UNKNOWN - KNOWN link of either kind and
+ * no positive weight.  Not detected, as in the region call: a connected component (through spatial and temporal links) that nothing
+ * pins while others are pinned.
+ * Not offered: per-link spatial or temporal weights, robust penalties, periodic time, the 8-bit entry points. */
+typedef struct sc_volume_params {
+    int       kind;            /* as sc_region_params.kind */
+    int       frames;          /* >= 2; frames * channels <= SC_POISSON_MAX_PLANES */
+    long long frame_stride;    /* floats from a frame to the next in every array; at least the span of one frame under the layout */
+    float     tau;             /* the temporal links' weight; finite, > 0 */
+    float     tol;             /* stop when ||r||_2 <= tol * ||b||_2 on every (volume, channel); <= 0: 1e-5 */
+    int       max_iters;       /* <= 0: 400 */
+    float     precond_lambda;  /* w-bar of the preconditioner; <= 0: (sum of w + sum of UNKNOWN - KNOWN links) / UNKNOWN pixels of the chunk */
+} sc_volume_params;
+typedef struct sc_volume_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE: `frames` frames, read at links live in the region */
+    const float *gt;         /* SC_POISSON_GUIDANCE: frames - 1 frames, read at live temporal links; NULL: zeros */
+    const float *lap;        /* SC_POISSON_LAPLACIAN: read at UNKNOWN pixels */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *boundary;   /* its Dirichlet lines in every frame (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names in every frame is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_volume_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_check(const sc_volume_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_device(void *instance, const sc_volume_params *p, const sc_poisson_layout *l, sc_volume_job *jobs, int n, bool bSync);
+/* One volume on host arrays, as sc_hip_region: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_volume(void *instance, const sc_volume_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                         const float *gt, const float *lap, const float *data, const float *state, const float *weight,
+                         const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

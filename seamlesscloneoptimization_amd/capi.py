@@ -252,6 +252,17 @@ class RegionJob(C.Structure):
                 ("rc", C.c_int)]
 
 
+# volume solves (sc_hip_volume*): Instance.volume / volume_device -- region solves on frame stacks with temporal links
+class VolumeParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("frames", C.c_int), ("frame_stride", C.c_longlong), ("tau", C.c_float), ("tol", C.c_float),
+                ("max_iters", C.c_int), ("precond_lambda", C.c_float)]
+
+
+class VolumeJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("gt", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p),
+                ("weight", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
 SC_ROBUST_ISOTROPIC = 1 << 20        # or'ed into RobustParams.kind only: one penalty per pixel over its two forward links
 SC_ROBUST_JOINT_CHANNELS = 1 << 21   # ... one penalty over all channels of a job (both: vectorial TV)
@@ -475,6 +486,12 @@ def load():
     L.sc_hip_region_device.restype = C.c_int
     L.sc_hip_region.argtypes = [C.c_void_p, C.POINTER(RegionParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 10
     L.sc_hip_region.restype = C.c_int
+    L.sc_hip_volume_check.argtypes = [C.POINTER(VolumeParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_check.restype = C.c_int
+    L.sc_hip_volume_device.argtypes = [C.c_void_p, C.POINTER(VolumeParams), C.POINTER(PoissonLayout), C.POINTER(VolumeJob), C.c_int, C.c_bool]
+    L.sc_hip_volume_device.restype = C.c_int
+    L.sc_hip_volume.argtypes = [C.c_void_p, C.POINTER(VolumeParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
+    L.sc_hip_volume.restype = C.c_int
     L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_robust_check.restype = C.c_int
     L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
@@ -800,6 +817,79 @@ def region_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, gx=Non
             links.append(a)
         smooth_x, smooth_y = links
     return kind, data, state, weight, smooth_x, smooth_y, gx, gy, lap, boundary, out
+
+
+def volume_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, tol: float = 0.0, max_iters: int = 0,
+                 precond_lambda: float = 0.0, layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None,
+                 row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_volume_check: SC_OK or the code a volume call with these parameters and this layout returns before it runs
+    anything.  The layout (of one frame) as a PoissonLayout or as keyword fields."""
+    p = VolumeParams(int(kind), int(frames), int(frame_stride), float(tau), float(tol), int(max_iters), float(precond_lambda))
+    return _check_call("sc_hip_volume_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_arrays(data, state, weight=None, gx=None, gy=None, gt=None, lap=None, boundary=None, tau=1.0, neumann=False, free_sides="",
+                  periodic=""):
+    """Checks a volume problem's numpy arrays before any device is touched: (kind, data, state, weight, gx, gy, gt, lap, boundary), every
+    array C-contiguous float32.  data: float32, T x H x W or T x H x W x C with T >= 2 and T * C <= 192.  state: of data's shape or
+    T x H x W (broadcast over the channels), region_arrays' types and values.  weight: None or of data's shape (or T x H x W).  gx, gy: of
+    data's shape, together; gt: (T - 1) x H x W (x C), only beside gx and gy; lap: of data's shape, instead of the three.  None of them:
+    zero guidance.  boundary: of data's shape, required when a side keeps a Dirichlet line.  tau: finite and > 0."""
+    all_free = no_dirichlet(border_bits(free_sides, neumann, periodic))
+    if data is None or state is None:
+        raise ValueError("a volume solve needs data and state")
+    if not isinstance(data, np.ndarray) or data.dtype != np.float32:
+        raise TypeError("data must be a float32 numpy array")
+    if data.ndim not in (3, 4) or (data.ndim == 4 and not 1 <= data.shape[3] <= 4):
+        raise ValueError("volume arrays are T x H x W or T x H x W x C with C in 1..4")
+    T, Cn = data.shape[0], (data.shape[3] if data.ndim == 4 else 1)
+    if T < 2:
+        raise ValueError("a volume has at least 2 frames")
+    if T * Cn > 192:
+        raise ValueError("frames x channels must be at most 192")
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError("tau must be finite and > 0")
+    if not isinstance(state, np.ndarray):
+        raise TypeError("state must be a numpy array (float32, an integer type or bool)")
+    if state.dtype != np.float32 and state.dtype != np.bool_ and not np.issubdtype(state.dtype, np.integer):
+        raise TypeError("state must be float32, an integer type or bool")
+
+    def shaped(name, a, shape, broadcast=False):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+        if broadcast and a.ndim == 3 and len(shape) == 4 and a.shape == shape[:3]:
+            a = np.broadcast_to(a[:, :, :, None], shape)
+        if a.shape != shape:
+            raise ValueError(f"{name} has shape {a.shape}, the problem {shape}")
+        return np.ascontiguousarray(a)
+
+    data = np.ascontiguousarray(data)
+    state = shaped("state", state.astype(np.float32), data.shape, True)
+    if (gx is None) != (gy is None):
+        raise ValueError("gx and gy go together")
+    if lap is not None and (gx is not None or gt is not None):
+        raise ValueError("either guidance (gx, gy and, if wanted, gt) or lap, not both")
+    if gt is not None and gx is None:
+        raise ValueError("gt goes with gx and gy")
+    if gx is None and lap is None:
+        lap = np.zeros(data.shape, np.float32)
+    kind = (SC_POISSON_LAPLACIAN if lap is not None else SC_POISSON_GUIDANCE) | border_bits(free_sides, neumann, periodic)
+    gx, gy, lap = (None if a is None else shaped(n, a, data.shape) for n, a in (("gx", gx), ("gy", gy), ("lap", lap)))
+    if gt is not None:
+        gt = shaped("gt", gt, (T - 1,) + data.shape[1:])
+    if all_free:
+        boundary = None
+    elif boundary is None:
+        raise ValueError("a volume solve with a Dirichlet line needs boundary")
+    else:
+        boundary = shaped("boundary", boundary, data.shape)
+    if weight is not None:
+        weight = shaped("weight", weight, data.shape, True)
+    read = border_unknowns(kind, *data.shape[1:3])
+    if not np.isin(state[:, read], (0.0, 1.0, 2.0)).all():
+        raise ValueError("state must hold 0 (unknown), 1 (known) or 2 (outside) at every pixel the borders call an unknown")
+    return kind, data, state, weight, gx, gy, gt, lap, boundary
 
 
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
@@ -1133,6 +1223,33 @@ class Instance:
         wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures
         raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_region_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- volume solves on float32 arrays
+    def volume(self, data, state, weight=None, gx=None, gy=None, gt=None, lap=None, boundary=None, tau=1.0, neumann=False, free_sides="",
+               periodic="", tol=0.0, max_iters=0, precond_lambda=0.0, allow_not_converged=False):
+        """sc_hip_volume on numpy float32 arrays of shape T x H x W or T x H x W x C (volume_arrays' rules): region()'s problem with unit
+        links on every frame, the frames joined by temporal links of weight tau; gt ((T - 1) x H x W (x C), or None: zeros) is the wanted
+        difference from a frame to the next.  Returns a NEW array: the solution at UNKNOWN pixels, data at KNOWN and OUTSIDE ones,
+        boundary on the Dirichlet lines of every frame; info() has the iterations and the final residual."""
+        kind, data, state, weight, gx, gy, gt, lap, boundary = volume_arrays(data, state, weight, gx, gy, gt, lap, boundary, tau, neumann,
+                                                                             free_sides, periodic)
+        layout = poisson_layout_of(data[0])
+        p = VolumeParams(kind, data.shape[0], data[0].size, float(tau), float(tol), int(max_iters), float(precond_lambda))
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                  (gx, gy, gt, lap, data, state, weight, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    @staticmethod
+    def make_volume_jobs(n: int):
+        return (VolumeJob * n)()
+
+    def volume_device(self, params: VolumeParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_device: jobs is a VolumeJob array (make_volume_jobs) of device pointers, one frame layout and one frame stride
+        for all.  sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is
+        returned, other failures raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_volume_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",

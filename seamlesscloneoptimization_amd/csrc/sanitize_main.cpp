@@ -16,7 +16,8 @@
 //   7. sc_hip_weighted_check: tol, precond_lambda, the kinds, the side limits and the layouts (the chunk driver behind it starts with a
 //      launch, so it is not reachable here); sc_hip_wls_check beside it on the same cases, precond_smooth like precond_lambda, and
 //      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps; the coupling
-//      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check.
+//      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check;
+//      sc_hip_volume_check: the same verdicts for two frames a frame's span apart, then frames, the plane limit, frame_stride and tau.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
@@ -408,6 +409,28 @@ int main()
             if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check");
             rg.precond_smooth = k.plam;
             if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check (precond_smooth)");
+            // the volume call: the region call's verdicts for two frames a frame's span apart, then its own refusals
+            const long long span = k.want == SC_OK ? (k.w - 1) * k.cs + (k.h - 1) * k.rs + (k.c - 1) * k.chs + 1 : 1LL << 40;
+            sc_volume_params vp{ k.kind, 2, span, 1.f, k.tol, k.iters, k.plam };
+            if (sc_hip_volume_check(&vp, &l) != k.want) return fail("volume_check");
+            vp.kind = k.kind | SC_ROBUST_ISOTROPIC;
+            if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_ARG) return fail("volume_check (coupling bits)");
+            vp.kind = k.kind;
+            if (k.want == SC_OK) {
+                vp.frames = 1;
+                if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_ARG) return fail("volume_check (frames < 2)");
+                vp.frames = SC_POISSON_MAX_PLANES / k.c;
+                if (sc_hip_volume_check(&vp, &l) != SC_OK) return fail("volume_check (the plane limit)");
+                vp.frames = SC_POISSON_MAX_PLANES / k.c + 1;
+                if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_SIZE) return fail("volume_check (beyond the plane limit)");
+                vp.frames = 2; vp.frame_stride = span - 1;
+                if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_ARG) return fail("volume_check (frame_stride)");
+                vp.frame_stride = span;
+                for (float tau : { 0.f, -1.f, nan, inf }) {
+                    vp.tau = tau;
+                    if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_ARG) return fail("volume_check (tau)");
+                }
+            }
             // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
             const bool lap_base = (k.kind & 3) == SC_POISSON_LAPLACIAN;
             sc_robust_params r{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };

@@ -446,12 +446,15 @@ __device__ __forceinline__ float mix_rhs(const PoissonGeo &g, const MixedGeo &mg
 // per plane, nullptr: 0).
 // Not NEU, but neither axis with a Dirichlet line at run time (mixed_zero_eig of both: a periodic axis beside a periodic or free-free one):
 // the same singular system -- the same zeroed coefficient and the same added mean, decided per launch from mg.
-template <int MODE, typename T, bool LAP, bool SCR, bool NEU>
+// TAB (MODE 1, SCR): a shift per plane -- parts[p], a float's value as a double, in lam's place (MODE 1 has no other use for parts);
+// a plane of a singular system whose shift is 0 gets coefficient (0, 0) set to 0 as the unscreened form does.
+template <int MODE, typename T, bool LAP, bool SCR, bool NEU, bool TAB = false>
 __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g, MixedGeo mg, PoissonJobs jobs, const T *__restrict__ in,
                                                      T *__restrict__ out, int rows, double scale, int tstore, const double *__restrict__ parts,
                                                      int nparts, float lam)
 {
     static_assert(!SCR || MODE != 2, "the last transform launch knows no screening");
+    static_assert(!TAB || (MODE == 1 && SCR), "a shift per plane: the column launch of a screened solve");
     extern __shared__ __attribute__((aligned(16))) unsigned char fft_smem[];
     __shared__ double s_mean;
     cx2<T> *__restrict__ S = reinterpret_cast<cx2<T> *>(fft_smem);
@@ -498,12 +501,15 @@ __global__ __launch_bounds__(FFT_THREADS) void k_mix(FftPlan<T> P, PoissonGeo g,
         // coefficient k of column r: divide by the two axes' eigenvalues (in double; zero only at (0, 0) of a singular system) and feed
         // the quotient into the inverse transform, the column resident in LDS (element off + k is read and rewritten by one thread)
         const double ex = mix_eig(mg.ax, r, rows);
+        double shift = (double)lam;
+        if constexpr (TAB) shift = parts[p];
+        const bool zero00 = TAB ? (sing && shift == 0.0) : (!SCR && sing);
         for (int k = tid; k < n; k += FFT_THREADS) {
             const cx2<T> t = mix_tab_k<T>(P, kind, k);
             const T X = mix_part<T>(kind, t, S[fft_pad(off + k)]);
             const double eig = ex + mix_eig(kind, k, n);
-            const T den = (T)(SCR ? eig - (double)lam : eig);
-            T q = (!SCR && sing && r == 0 && k == 0) ? (T)0 : X / den;
+            const T den = (T)(SCR ? eig - shift : eig);
+            T q = (zero00 && r == 0 && k == 0) ? (T)0 : X / den;
             if (kind == 1 && k == 0) q *= (T)0.5;
             S[fft_pad(off + k)] = mk<T>(q * t.x, q * t.y);
         }
@@ -570,6 +576,7 @@ static hipError_t mix_opt_in_lds(int bytes)
     for (int f = 0; f < 8; ++f) {      // (MODE 1 and 2 meet each of theirs more than once)
         opt(mix_kernel<0, T>(f & 1, f & 2, f & 4)); opt(mix_kernel<1, T>(false, f & 2, f & 4)); opt(mix_kernel<2, T>(false, false, f & 4));
     }
+    opt(k_mix<1, T, false, true, false, true>); opt(k_mix<1, T, false, true, true, true>);
     return e;
 }
 
@@ -972,9 +979,9 @@ int fft_solve(Instance *I, bool fp64)
 // -- a boundary-mean reduction first (mark 5 behind it; otherwise at the start), the mean added by the last launch.  lam > 0: the screened solve -- the data term read by the first row launch, the denominators
 // shifted by -lam.
 template <typename T>
-static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam)
+static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, float lam, const double *lam_tab)
 {
-    const bool scr = lam > 0.f, all_free = mg.ax == 1 && mg.ay == 1, singular = mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay);
+    const bool scr = lam > 0.f || lam_tab, all_free = mg.ax == 1 && mg.ay == 1, singular = mixed_zero_eig(mg.ax) && mixed_zero_eig(mg.ay);
     auto table_kind = [](int k) { return k == 3 ? 2 : k; };      // FftDim::kind: kind 3 is kind 2 with the spatial index reversed
     const int nx = mg.nx, ny = mg.ny, planes = g.C * m;
     SC_HIP(I, fft_opt_in_lds<T>(I));
@@ -1025,8 +1032,9 @@ static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo 
     });
     // the column launch: B[p][x][y] -> A, stored transposed again (ts) when the planes are tiny
     auto columns = [&](int ts) {
-        hipLaunchKernelGGL((mix_kernel<1, T>(false, scr, all_free)), dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A,
-                           nx, 1.0, ts, no_parts, 0, lam);
+        const MixKernel<T> k = !lam_tab ? mix_kernel<1, T>(false, scr, all_free) : all_free ? k_mix<1, T, false, true, true, true> : k_mix<1, T, false, true, false, true>;
+        hipLaunchKernelGGL(k, dim3(nx, planes), dim3(FFT_THREADS), ldsh, I->stream, Ph, g, mg, none, (const T *)B, A, nx, 1.0, ts, lam_tab ? lam_tab : no_parts,
+                           0, lam);
     };
     if (tiny) {
         columns(1);      // A[p][y][x]
@@ -1050,7 +1058,7 @@ static int direct_jobs_solve_t(Instance *I, const PoissonGeo &g, const MixedGeo 
     return SC_OK;
 }
 
-int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam)
+int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam, const double *lam_tab)
 {
     if (!fft_supported(mg.nx, mg.ny, fp64)) {
         if (mg.ax == 1 && mg.ay == 1)
@@ -1060,7 +1068,7 @@ int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool
         else I->err = fp64 ? "free sides with SC_FLAG_FFT_FP64: more than 4096 unknowns per axis" : "free sides: more than 8192 unknowns per axis";
         return SC_ERR_BAD_SIZE;
     }
-    return fp64 ? direct_jobs_solve_t<double>(I, g, mg, lap, jobs, m, lam) : direct_jobs_solve_t<float>(I, g, mg, lap, jobs, m, lam);
+    return fp64 ? direct_jobs_solve_t<double>(I, g, mg, lap, jobs, m, lam, lam_tab) : direct_jobs_solve_t<float>(I, g, mg, lap, jobs, m, lam, lam_tab);
 }
 
 } // namespace sc

@@ -371,10 +371,11 @@ inline bool poisson_no_dirichlet(int kind)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 // What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
-enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8 };
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16 };
 struct FloatArrays {
     const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; const float *smooth_x = nullptr, *smooth_y = nullptr;
     const float *state = nullptr;      // FLOAT_STATE: the region call's state array
+    const float *gt = nullptr;         // FLOAT_GT: the volume call's temporal guidance (may be NULL: zeros)
 };
 // A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
 // family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
@@ -391,7 +392,7 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
 // The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT), their link weights (NULL without
 // FLOAT_SMOOTH) and where each one's code goes.
-struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy, st; std::vector<int *> rcs; };
+struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy, st, gt; std::vector<int *> rcs; };
 // A device call's job intake: arrays_of(job) names one public job's arrays.  A job that fails float_job_validate gets its code; the
 // others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
 // empty: nothing to run).
@@ -416,6 +417,7 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
         v.sx.push_back(a.smooth_x);
         v.sy.push_back(a.smooth_y);
         v.st.push_back(a.state);
+        v.gt.push_back(a.gt);
         v.rcs.push_back(&j.rc);
     }
     return worst;
@@ -423,8 +425,11 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
 // boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state --, uploaded in that order.  job: the
 // device job (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights, d_sx, d_sy: the link weights, d_state: the states.
-struct FloatStaged { PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr, *d_state = nullptr; };
-int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s);
+// frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; gt, FLOAT_GT
+// and not NULL, holds frames - 1 and goes behind state (through the link arrays' pinned block, which a volume call leaves free).
+struct FloatStaged { PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr, *d_state = nullptr, *d_gt = nullptr; };
+int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames = 1,
+                long long frame_stride = 0);
 // nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and
 // sets their codes.  SC_OK and SC_ERR_NOT_CONVERGED let the call go on; any other code ends it: that chunk's jobs and every one not
 // yet run read it, after SC_ERR_HIP the ones already run too.  Returns that code, else the worst.
@@ -446,7 +451,8 @@ template <class Chunk> int run_chunks(Instance *I, int C, int *const *rcs, int n
 }
 int poisson_run(Instance *I, const PoissonCall &p, const sc_poisson_layout *l, const PoissonJobDev *dj, int *const *rcs, int nv, bool timed, float t[4]);
 void poisson_set_timing(Instance *I, const float t[4]);
-int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve);
+int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve, int frames = 1,
+                     long long frame_stride = 0);
 // sc_arena.cpp: row copies between caller memory, pinned staging and the device (no 2-D copies)
 void copy_rows(Instance *I, uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t row_bytes, int rows);
 int upload_rows(Instance *I, DevBuf &stage, void *d, size_t dpitch, const uint8_t *h, size_t hpitch, size_t row_bytes, int rows);
@@ -566,7 +572,10 @@ bool fft_supported(int w, int h, bool fp64);
 // SC_POISSON_PERIODIC_*; mg: poisson_mixed_geo) on caller arrays: m same-size jobs as C m planes, straight from the jobs' arrays into their out arrays, each axis under its own transform
 // (marks: 5 behind the boundary-mean reduction of an unscreened singular solve -- no Dirichlet line on any side --, else at the start; 6 behind the last transform launch)
 // (lam > 0: the screened solve, sc_screened_api.cpp: the jobs' data term read with the right-hand side, no mean)
-int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f);
+// lam_tab (device; NULL: none): one shift per plane in lam's place, lam_tab[member C + channel], each a float's value; a plane whose
+// shift is 0 in a system without any Dirichlet line is the singular solve (its coefficient (0, 0) is set to 0)
+int direct_jobs_solve(Instance *I, const PoissonGeo &g, const MixedGeo &mg, bool lap, const PoissonJobDev *jobs, int m, bool fp64, float lam = 0.f,
+                      const double *lam_tab = nullptr);
 bool wants_float_tables(const Instance *I);
 int effective_method(const Instance *I);                              // sc_solver.cpp: what SC_METHOD_AUTO resolves to for the fields bound to I
 int output_nodes(Instance *I, LmNodes &lm);  // sc_solver.cpp: the float-table correction the post-process of result(I) has to add (none: lm.CN == nullptr)

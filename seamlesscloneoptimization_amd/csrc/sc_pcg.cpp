@@ -7,7 +7,8 @@
 //      homogeneous on the Dirichlet lines).
 //   3. u0 = M^-1 b (times the family's factor), r = b - L u0, z = M^-1 r, p = z;  M = A - lam through direct_jobs_solve in its Laplacian
 //      form on the work planes: jobs without data term and without boundary (both mean zero there), under a PoissonGeo that addresses
-//      the planes' rows by pixel coordinates.  A frame on all four sides takes the same road, both axes of kind 0.
+//      the planes' rows by pixel coordinates.  A frame on all four sides takes the same road, both axes of kind 0.  (PcgOperator::precond;
+//      the volume family puts its own M^-1 there: a transform along the frames around the same direct solve.)
 //   4. the iteration: q = L p | u += alpha p, r -= alpha q | z = M^-1 r | r . z | p = z + beta p -- four launches of sc_pcg.hip's and the
 //      family's and the preconditioner's three or five, nothing read by the host but the stop rule's norms, SC_WEIGHTED_POLL iterations
 //      late.
@@ -32,6 +33,22 @@ constexpr int W_LAG = PcgState::LAG, W_RING = PcgState::RING;
 // share every solve and one code.
 void PcgOperator::out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) { launch_pcg_out(g, wg, dj.data(), mv, U, s); }
 
+// (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the pointers are moved back by the
+// first unknown's offset, and only unknowns are ever addressed (no boundary: no Dirichlet line is read or written)
+int PcgOperator::precond(const PcgChunk &c, float lam, bool fp64, const float *in, float *out)
+{
+    const PoissonGeo &g = c.g;
+    const PcgGeo &wg = c.wg;
+    const PoissonGeo pg{ g.W, g.H, g.C, 1, (long long)wg.nx, wg.stride };
+    const long long shift = (long long)wg.x0 + (long long)wg.y0 * wg.nx;
+    std::vector<PoissonJobDev> pj(c.mv);
+    for (int k = 0; k < c.mv; ++k) {
+        const long long o = (long long)k * g.C * wg.stride - shift;
+        pj[k] = PoissonJobDev{ nullptr, nullptr, in + o, nullptr, out + o };
+    }
+    return direct_jobs_solve(c.I, pg, c.mg, true, pj.data(), c.mv, fp64, lam);
+}
+
 int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, int &job_errors, PcgChunk &c)
 {
     c = PcgChunk();
@@ -39,7 +56,7 @@ int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOp
     c.call = call;
     c.g = g;
     c.mg = poisson_mixed_geo(poisson_free_sides(call.kind), g.W, g.H, poisson_periodic(call.kind));
-    c.wg = pcg_geo(c.mg);
+    c.wg = op.work_geo(c.mg);
     const PcgGeo &wg = c.wg;
     const bool no_dirichlet = poisson_no_dirichlet(call.kind);
     const int nop = c.nop = pcg_op_parts(wg), nstat = op.nstat, nround = op.nround;
@@ -89,7 +106,6 @@ int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &r
 {
     Instance *I = c.I;
     const PoissonGeo &g = c.g;
-    const MixedGeo &mg = c.mg;
     const PcgGeo &wg = c.wg;
     const PcgCall &call = c.call;
     const bool fp64 = (I->opts.flags & SC_FLAG_FFT_FP64) != 0;
@@ -102,19 +118,7 @@ int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &r
     res = PcgChunkResult();
     const float lam = op.precond_constant(g, wg, mv);
     SC_HIP(I, hipMemcpyAsync(h_bb, d_bb, sizeof(double) * (size_t)planes * PCG_PARTS, hipMemcpyDeviceToHost, s));
-    // the preconditioner: (A - lam) out = in on the work planes.  Pixel (x, y) of a plane is its unknown (x - x0, y - y0): the
-    // pointers are moved back by the first unknown's offset, and only unknowns are ever addressed (no boundary: no Dirichlet line is
-    // read or written)
-    const PoissonGeo pg{ g.W, g.H, g.C, 1, (long long)wg.nx, wg.stride };
-    const long long shift = (long long)wg.x0 + (long long)wg.y0 * wg.nx;
-    std::vector<PoissonJobDev> pj(mv);
-    auto precond = [&](const float *in, float *out) -> int {
-        for (int k = 0; k < mv; ++k) {
-            const long long o = (long long)k * g.C * wg.stride - shift;
-            pj[k] = PoissonJobDev{ nullptr, nullptr, in + o, nullptr, out + o };
-        }
-        return direct_jobs_solve(I, pg, mg, true, pj.data(), mv, fp64, lam);
-    };
+    auto precond = [&](const float *in, float *out) -> int { return op.precond(c, lam, fp64, in, out); };      // the family's M^-1
     // the stop rule's mailbox: iteration k's norms into slot k % W_RING, event k % W_RING behind them
     auto post_norms = [&](int k) -> int {
         SC_HIP(I, hipMemcpyAsync(h_tot + (size_t)(k % W_RING) * planes, d_tot, sizeof(double) * planes, hipMemcpyDeviceToHost, s));
@@ -221,7 +225,7 @@ int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOpe
     int job_errors = 0, sweeps = 0;
     bool converged = true;
     double rel = 0.0;
-    int worst = run_chunks(I, g.C, rcs, nv, [&](int i0, int m) {
+    int worst = run_chunks(I, op.chunk_planes(g.C), rcs, nv, [&](int i0, int m) {
         PcgChunkResult res;
         op.dj.assign(jobs + i0, jobs + i0 + m);
         op.begin(i0, m);
@@ -252,23 +256,24 @@ int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, 
 {
     const char *why = "";
     int rc;
-    if ((rc = float_job_validate(call.kind, carries, a, &why, poisson_span(l)))) { I->err = why; return rc; }
+    if ((rc = float_job_validate(call.kind, carries, a, &why, pcg_call_span(call, l)))) { I->err = why; return rc; }
     FloatStaged s;
-    if ((rc = float_stage(I, l, call.kind, carries, a, s))) return rc;
+    if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
     op.bind(&s.d_w, &s.d_sx, &s.d_sy);
     op.bind_state(&s.d_state);
+    op.bind_gt(&s.d_gt);
     rc = pcg_run(I, call, l, op, &s.job, job_rcs, 1, true, chunk);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)
-    return poisson_download(I, l, s.job.out, a.out, t, rc);
+    return poisson_download(I, l, s.job.out, a.out, t, rc, call.frames, call.frame_stride);
 }
 
 void pcg_release(Instance *I)
 {
     if (!I->pcg) return;
     PcgState &S = *I->pcg;
-    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.rho, &S.red }) dev_release(*b);
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.f, &S.dct, &S.tab, &S.rho, &S.red }) dev_release(*b);
     if (S.h_red.p) (void)hipHostFree(S.h_red.p);
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);
     delete I->pcg;

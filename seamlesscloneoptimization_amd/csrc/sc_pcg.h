@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_volume.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
 // (WlsOperator, sc_wls_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
 // Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
@@ -29,6 +29,7 @@ struct PcgState {
     DevBuf u, r, p, q;
     DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
+    DevBuf f, dct, tab;                    // the volume solve's (sc_volume.hip): links to the next frame; the transformed planes; the DCT table (float) and the modes' shifts (double)
     DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude
     DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane | a family's round sums
     DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane | a family's round sums
@@ -41,9 +42,11 @@ void pcg_release(Instance *I);             // frees Instance::pcg and all it hol
 // What a family tells the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat`
 // doubles per part; the driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets
 // SC_ERR_BAD_ARG and leaves; NULL: it stays, its arrays move to the front and its sums count) -> setup -> precond_constant ->
-// scale_start on u0 (a cold start only) -> apply, once in its residual form and then once per iteration.  Everything else -- the
-// preconditioner through direct_jobs_solve, the update, dot and direction launches, the stop rule's mailbox, the output launch -- is
-// the driver's own.
+// scale_start on u0 (a cold start only) -> apply, once in its residual form and then once per iteration, precond wherever M^-1 is
+// applied.  Everything else -- the update, dot and direction launches, the stop rule's mailbox -- is the driver's own, and so are the
+// defaults of precond (direct_jobs_solve with precond_constant's lam), out, work_geo and chunk_planes, which only the volume family
+// replaces.
+struct PcgChunk;
 struct PcgOperator {
     const int nstat;                       // doubles per part of the statistics launch
     const int nround;                      // doubles per part a family's own later launches sum (PcgChunk::d_round; the robust call's rounds)
@@ -53,6 +56,11 @@ struct PcgOperator {
     // the call's weights and link weights, one pointer per job (pcg_host_call, pcg_device_call: once the staged or taken-in tables exist)
     virtual void bind(const float *const *w, const float *const *sx, const float *const *sy) = 0;
     virtual void bind_state(const float *const *state) {}                           // ... and its state arrays (the region call's; the others have none)
+    virtual void bind_gt(const float *const *gt) {}                                 // ... and its temporal guidance (the volume call's; NULL entries: zeros)
+    // work planes per job and channel that run_chunks counts against SC_POISSON_MAX_PLANES (the volume call: its frames), and the work
+    // planes' geometry: by default one plane of mg's unknowns per (job, channel) (the volume call: its frames stacked along y)
+    virtual int chunk_planes(int C) const { return C; }
+    virtual PcgGeo work_geo(const MixedGeo &mg) const { return pcg_geo(mg); }
     virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
     virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
     // st: job k's statistics, its C planes' PCG_PARTS * nstat doubles each, of which the first `parts` parts are set
@@ -65,6 +73,9 @@ struct PcgOperator {
     virtual void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) = 0;
     // the output launch of the mv jobs that stayed (dj): by default U at the unknowns and boundary's values on the Dirichlet lines
     virtual void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s);
+    // the preconditioner: out = M^-1 in on the chunk's work planes.  The default: (A - lam) out = in through direct_jobs_solve, plane
+    // by plane (lam: precond_constant's)
+    virtual int precond(const PcgChunk &c, float lam, bool fp64, const float *in, float *out);
     // the sum of field f of one plane's statistics over its first `parts` parts
     double stat_sum(const double *plane, int parts, int f) const
     {
@@ -91,7 +102,11 @@ struct PcgOperator {
         return no_dirichlet && empty ? "no data weight and no Dirichlet line" : nullptr;
     }
 };
-struct PcgCall { int kind; float tol; int max_iters; int default_iters; };      // kind: poisson_norm_kind's
+// kind: poisson_norm_kind's; frames, frame_stride: the volume call's -- a job's arrays are `frames` images under the layout, frame_stride
+// floats apart (gt: frames - 1 of them)
+struct PcgCall { int kind; float tol; int max_iters; int default_iters; int frames = 1; long long frame_stride = 0; };
+// the floats from an array's pointer to one past its last element, all frames of the call
+inline size_t pcg_call_span(const PcgCall &call, const sc_poisson_layout *l) { return poisson_span(l) + (size_t)(call.frames - 1) * (size_t)call.frame_stride; }
 struct PcgChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
 // One chunk of m same-size jobs between its prologue and its output, in three steps a family's driver may put its own between:
 //   pcg_chunk_begin    the statistics, the judgement of every job (a refused one gets SC_ERR_BAD_ARG and leaves), the buffers; mv = the
@@ -144,11 +159,12 @@ template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgC
                                                          ArraysOf arrays_of, PcgOperator &op, bool timed, PcgChunkFn chunk = nullptr)
 {
     FloatJobs v;
-    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, poisson_span(l));
+    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l));
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
     op.bind(v.w.data(), v.sx.data(), v.sy.data());
     op.bind_state(v.st.data());
+    op.bind_gt(v.gt.data());
     return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
 }
 
@@ -236,6 +252,33 @@ void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const 
                          const float *const *sy, const float *const *st, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
 // the jobs' out: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
 void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *st, int m, const float *U, hipStream_t s);
+
+// ---- the volume family (sc_volume.hip): the region system with unit spatial links on a stack of T frames, plus temporal links of the
+// constant weight tau between (q, t) and (q, t + 1).  A job's arrays hold T frames (gt: T - 1) fs floats apart.  Work planes: one per
+// (volume, channel), the frames stacked along y: wg.ny = T * (a frame's rows of unknowns), wg from VolumeOperator::work_geo.
+struct VolumeJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *st[MAX], *gt[MAX]; };
+struct VolumeGeo { int T, ny; long long fs; float tau; };      // ny: a frame's rows of unknowns
+constexpr int VOLUME_STATS = 5;
+// stats[(plane * PCG_PARTS + i) * VOLUME_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
+// its UNKNOWN pixels | the sum of its UNKNOWN - KNOWN links (spatial 1, temporal tau) | its state elements that are not 0, 1 or 2
+void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *w,
+                         const float *const *st, int m, double *stats, hipStream_t s);
+// R = b (the order: seamlessclone_hip.h, the volume section); E / S / F = the link to the next column / row / frame where both ends are
+// UNKNOWN (1, 1, tau); Dg = the sum of the incident live links plus w; all five 0 at every pixel that is not UNKNOWN; bb = the parts of b . b
+void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const float *const *w,
+                         const float *const *st, const float *const *gt, int m, float *R, float *E, float *S, float *F, float *Dg, double *bb,
+                         hipStream_t s);
+// residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
+void launch_volume_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool residual, const float *P, const float *E, const float *S, const float *F,
+                      const float *Dg, float *Q, double *parts, hipStream_t s);
+// D[k * T + t] = the orthonormal DCT-II along the frames (computed in double, rounded to float32); lam[p * T + k] = the shift of mode k
+// of every one of the `planes` work planes: (float)(wbar + tau (2 - 2 cos(pi k / T))) as a double
+void launch_volume_tables(int T, int planes, double wbar, double tau, float *D, double *lam, hipStream_t s);
+// out[p][k] = sum_t D[k][t] in[p][t] (transposed: sum_t D[t][k] in[p][t]) for every pixel of the frames of `planes` work planes
+void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool transposed, const float *D, const float *in, float *out, hipStream_t s);
+// the jobs' out, frame by frame: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
+void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *st, int m,
+                       const float *U, hipStream_t s);
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;

@@ -140,6 +140,7 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
         if (!a.state) { *why = "null state pointer"; return SC_ERR_BAD_ARG; }
         if (!aligned4(a.state)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
     }
+    if ((carries & FLOAT_GT) && a.gt && !aligned4(a.gt)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
     if (span && (carries & (FLOAT_SMOOTH | FLOAT_STATE))) {
         const uintptr_t o = (uintptr_t)a.out, bytes = span * sizeof(float);
         auto overlaps = [&](const float *q) { return (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes; };
@@ -158,16 +159,16 @@ PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a)
     return j;
 }
 
-int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s)
+int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames, long long frame_stride)
 {
-    const size_t bytes = poisson_span(l) * sizeof(float), slot = (bytes + 255) / 256 * 256;
+    const size_t bytes = (poisson_span(l) + (size_t)(frames - 1) * (size_t)frame_stride) * sizeof(float), slot = (bytes + 255) / 256 * 256;
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
     const float *data = carries & FLOAT_DATA ? a.data : nullptr, *weight = carries & FLOAT_WEIGHT ? a.weight : nullptr;
     // (the Poisson call keeps a boundary without a Dirichlet line: it gives the mean)
     const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
-    const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0;
-    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0);
+    const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0, gt = (carries & FLOAT_GT) && guidance && a.gt;
+    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0) + (gt ? 1 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -177,7 +178,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_in0 = next(true), *d_in1 = next(guidance), *d_d = next(data != nullptr), *d_w = next(weight != nullptr);
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
-    float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state);
+    float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state), *d_gt = next(gt);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -192,6 +193,11 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     s.d_sy = d_sy;
     if ((rc = upload(I->h_state, d_state, a.state))) return rc;
     s.d_state = d_state;
+    if (d_gt) {          // (one frame less than the others)
+        const size_t gbytes = bytes - (size_t)frame_stride * sizeof(float);
+        if ((rc = upload_rows(I, I->h_sx, d_gt, gbytes, (const uint8_t *)a.gt, gbytes, gbytes, 1))) return rc;
+    }
+    s.d_gt = d_gt;
     return SC_OK;
 }
 
@@ -373,9 +379,9 @@ namespace sc {
 
 // The host call's way back: out's span into pinned staging, then only the elements the layout names into the caller's array; the
 // call's times.  Returns rc_solve.
-int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve)
+int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out, float *out, const float t[4], int rc_solve, int frames, long long frame_stride)
 {
-    const size_t span = poisson_span(l), bytes = span * sizeof(float);
+    const size_t span = poisson_span(l) + (size_t)(frames - 1) * (size_t)frame_stride, bytes = span * sizeof(float);
     int rc;
     if ((rc = ensure_pinned(I, I->h_out, bytes))) return rc;
     SC_HIP(I, hipMemcpyAsync(I->h_out.p, d_out, bytes, hipMemcpyDeviceToHost, I->stream));
@@ -383,15 +389,16 @@ int poisson_download(Instance *I, const sc_poisson_layout *l, const float *d_out
     SC_HIP(I, hipStreamSynchronize(I->stream));
     const float *h = (const float *)I->h_out.p;
     const int W = l->cols, H = l->rows, Cn = l->channels;
-    if (span == (size_t)W * H * Cn) {
+    if (span == (size_t)W * H * Cn * frames) {
         copy_rows(I, (uint8_t *)out, bytes, (const uint8_t *)h, bytes, bytes, 1);     // dense: every float of the span is named
     } else {
-        for (int y = 0; y < H; ++y)
-            for (int x = 0; x < W; ++x)
-                for (int c = 0; c < Cn; ++c) {
-                    const size_t o = (size_t)(x * l->col_stride + y * l->row_stride + c * l->channel_stride);
-                    out[o] = h[o];
-                }
+        for (int f = 0; f < frames; ++f)
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x)
+                    for (int c = 0; c < Cn; ++c) {
+                        const size_t o = (size_t)f * (size_t)frame_stride + (size_t)(x * l->col_stride + y * l->row_stride + c * l->channel_stride);
+                        out[o] = h[o];
+                    }
     }
     poisson_set_timing(I, t);
     I->info.ms_h2d = ev_ms(I->ev_k0, I->ev[0]);

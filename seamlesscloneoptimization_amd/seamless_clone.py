@@ -622,6 +622,71 @@ def poisson_clone(src, dst, mask, mixed=False, gpu_id=0, **solver):
     return region_solve(dst, state, gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
 
 
+def volume_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, weight=None, boundary=None, tau=1.0, neumann=True, free_sides=None,
+                 periodic="", tol=None, max_iters=None, gpu_id=0, **solver):
+    """Volume solve on a float32 frame stack of shape T x H x W or T x H x W x C (C 1..4, T * C <= 192): region_solve's problem with unit
+    links on every frame, and every pixel joined to the same pixel of the next frame by a link of weight tau -- per channel it minimises
+    sum_t [sum w (u_t - d_t)^2 + sum |grad u_t - (gx_t, gy_t)|^2] + tau sum_t sum (u_{t+1} - u_t - gt_t)^2 over the pixels whose state
+    is 0, with u = data where state is 1 and no link to a pixel whose state is 2.  A known keyframe is a frame of 1s.  gt ((T - 1) x H x
+    W (x C)): the wanted change from frame to frame; None: plain temporal smoothness.  laplacian: the whole right-hand side in place of
+    gx, gy, gt.  Borders (neumann by default), tol, max_iters (400): region_solve's.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    _, data, state, weight, gx, gy, gt, lap, b = capi.volume_arrays(data, state, weight, gx, gy, gt, laplacian, boundary, tau, neumann=neumann,
+                                                                     free_sides=free_sides, periodic=periodic)
+    with _instance(gpu_id, solver) as inst:
+        return inst.volume(data, state, weight, gx, gy, gt, lap, b, tau=tau, neumann=neumann, free_sides=free_sides, periodic=periodic,
+                           tol=tol or 0.0, max_iters=max_iters or 0)
+
+
+def _video_masks(name, masks, frames):
+    m = np.asarray(masks)
+    if m.shape != frames.shape[:3]:
+        raise ValueError(f"{name} has shape {m.shape}, the frames {frames.shape[:3]}")
+    return m.astype(bool)
+
+
+def inpaint_video(frames, holes, tau=1.0, gpu_id=0, **solver):
+    """Membrane fill of a float32 video (T x H x W or T x H x W x C): inpaint() with temporal links of weight tau.  The pixels where
+    holes (T x H x W, anything truthy) is set are filled from the pixels around them in space and time, so a place hidden in one frame is
+    filled from the frames where it is visible, and the fill does not flicker.  Returns a NEW array; pixels outside the holes keep their
+    bits."""
+    if not isinstance(frames, np.ndarray) or frames.dtype != np.float32:
+        raise TypeError("frames must be a float32 numpy array")
+    if frames.ndim not in (3, 4):
+        raise ValueError("frames are T x H x W or T x H x W x C")
+    h = _video_masks("holes", holes, frames)
+    if h.all():
+        raise ValueError("the holes cover every frame: nothing to fill them from")
+    state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    return volume_solve(frames, state, tau=tau, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, gpu_id=0, **solver):
+    """poisson_clone on every frame of float32 videos of one shape (T x H x W or T x H x W x C), the frames joined by temporal links of
+    weight tau whose guidance is srcs' difference from frame to frame where both frames' masks (T x H x W) are set, 0 elsewhere: the
+    clone follows the source's change over time and does not flicker.  mixed: poisson_clone's, per frame.  Returns a NEW array."""
+    for name, a in (("srcs", srcs), ("dsts", dsts)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+    if srcs.shape != dsts.shape:
+        raise ValueError(f"srcs has shape {srcs.shape}, dsts {dsts.shape}")
+    if dsts.ndim not in (3, 4):
+        raise ValueError("frames are T x H x W or T x H x W x C")
+    m = _video_masks("masks", masks, dsts)
+    if m.all():
+        raise ValueError("the masks cover every frame: nothing of dsts is left to join")
+    gx, gy = np.zeros_like(srcs), np.zeros_like(srcs)
+    for t in range(srcs.shape[0]):
+        gx[t], gy[t] = _forward_differences(srcs[t])
+        if mixed:
+            dx, dy = _forward_differences(dsts[t])
+            gx[t], gy[t] = np.where(np.abs(dx) > np.abs(gx[t]), dx, gx[t]), np.where(np.abs(dy) > np.abs(gy[t]), dy, gy[t])
+    both = (m[1:] & m[:-1]).reshape(m[1:].shape + (1,) * (srcs.ndim - 3))
+    gt = np.where(both, srcs[1:] - srcs[:-1], np.float32(0)).astype(np.float32)
+    state = np.where(m, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    return volume_solve(dsts, state, gx=gx, gy=gy, gt=gt, tau=tau, neumann=True, gpu_id=gpu_id, **solver)
+
+
 def _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters):
     return capi.RobustParams(kind, float(p), float(eps_grad), float(q), float(eps_data), int(max_rounds or 0), float(round_tol or 0.0),
                              float(tol or 0.0), int(max_iters or 0))

@@ -7,7 +7,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 want = sys.argv[2:]
 by = defaultdict(list)
 for r in rows:
-    name = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void sc::", "").replace("sc::", "")
+    name = re.sub(r"\(.*", "", r["Kernel_Name"].replace("(anonymous namespace)::", "")).replace("void sc::", "").replace("sc::", "")
     if want and not any(w in name for w in want):
         continue
     wg = int(r["Grid_Size_X"]) // max(int(r.get("Workgroup_Size_X", "1") or 1), 1)
