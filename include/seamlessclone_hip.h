@@ -935,7 +935,8 @@ SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poi
  * when the call has no Dirichlet line, the channel has UNKNOWN pixels, and the volume has no UNKNOWN - KNOWN link of either kind and
  * no positive weight.  Not detected, as in the region call: a connected component (through spatial and temporal links) that nothing
  * pins while others are pinned.
- * Not offered: per-link spatial or temporal weights, robust penalties, periodic time, the 8-bit entry points. */
+ * Not offered here: per-link spatial or temporal weights and periodic time (sc_hip_volume_wls has both); anywhere: robust penalties on
+ * volumes, the 8-bit entry points. */
 typedef struct sc_volume_params {
     int       kind;            /* as sc_region_params.kind */
     int       frames;          /* >= 2; frames * channels <= SC_POISSON_MAX_PLANES */
@@ -964,6 +965,88 @@ SC_API int sc_hip_volume_device(void *instance, const sc_volume_params *p, const
 SC_API int sc_hip_volume(void *instance, const sc_volume_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *gt, const float *lap, const float *data, const float *state, const float *weight,
                          const float *boundary, float *out);
+/* ---- WLS volume solves: per-link weights in space and time, looping time ------------------------------------------------------------------
+ * sc_hip_volume's problem with a weight on every link, as sc_hip_region has them within an image, and optionally periodic time.  Per
+ * channel the call minimises
+ *     sum_t [ sum_q w (u_t - d_t)^2 + sum sx (dx u_t - gx_t)^2 + sum sy (dy u_t - gy_t)^2 ]  +  sum_t sum_q lt (u_{t+1}(q) - u_t(q) - gt_t(q))^2
+ * over the UNKNOWN pixels.  The temporal link lt is tau when smooth_t is NULL, else the float32 product tau * smooth_t, rounded once.
+ * Edge-aware smoothing of video that does not flicker, scribble, colour or depth propagation that stops at edges in space and in time,
+ * clones whose temporal coupling is switched down where the frames disagree, seamless loops.
+ * States, the liveness of spatial and temporal links, Dirichlet lines, what is copied to out and what is never written: sc_hip_volume's.
+ * smooth_x, smooth_y: `frames` frames, each stored at its link's low end as in sc_hip_region (the last pixel of a periodic axis holds the
+ * wrapping link), read only at links live in the region; both given or both NULL: every spatial link 1.
+ * smooth_t and gt: element (q, t) belongs to the link from frame t to frame t + 1.  With time_periodic = 0 both hold frames - 1 frames
+ * and the two ends of time are free.  With time_periodic = 1 (frames >= 3) both hold `frames` frames, frame frames - 1 of them is the
+ * link from the last frame to frame 0, and that link follows the same liveness rule as any other.  Each is read only at live temporal
+ * links.  In a device call the first volume decides for weight, for smooth_x / smooth_y and for smooth_t (the two judged separately); a
+ * volume that differs gets SC_ERR_BAD_ARG.  gt is each volume's own choice.
+ * The right-hand side at an UNKNOWN pixel, in float32: the seven steps of sc_hip_volume, where
+ *   1. each 1 * g is the rounded product s * g of the link's own weight (SC_POISSON_LAPLACIAN: lap, and step 2 is left out);
+ *   2. e is the rounded product lt * gt of the link to the next frame, f that of the link to the previous frame, each with its own lt;
+ *      under periodic time the previous frame of frame 0 is frame frames - 1 and the next frame of frame frames - 1 is frame 0;
+ *   3. - w * d as there;
+ *   4. the Dirichlet lines' terms s * boundary with their link's s: west, north, east, south;
+ *   5. the KNOWN spatial neighbours' terms s * data(q) likewise;
+ *   6. the KNOWN temporal neighbours' terms lt * data: previous frame, then next frame;
+ *   7. every product of 4 to 6 is rounded on its own and subtracted in turn.
+ * The diagonal is (((lw + le) + (ln + ls)) + (lb + lf)) + w over the live links west, east, north, south, back, forward.
+ * What is read: sc_hip_volume's elements; a link weight only where its link is live.  A NaN at a dead link is fine.  weight, state and
+ * the three link arrays must not overlap out (the span rule; a temporal array's span is its own frames').
+ * Ties: with all three link arrays NULL and time_periodic = 0 the call writes the bytes of sc_hip_volume with the same parameters;
+ * arrays of 1.0f give the bytes of NULL arrays.  Two runs of one call give the same bytes.
+ * Solved as sc_hip_volume: conjugate gradients on one system per (volume, channel), preconditioned by
+ *     M = s-bar A - w-bar + tau-bar A_t
+ * on the whole rectangle x frames, exact for constant coefficients.  s-bar = precond_smooth, or the mean of the spatial links live in
+ * the region over the chunk (exactly 1 without smooth_x or without such a link); tau-bar = precond_tau, or the mean of the live temporal
+ * links lt (exactly tau without smooth_t or without such a link); w-bar = precond_lambda, or (the sum of w over the UNKNOWN pixels + the
+ * sum of the UNKNOWN - KNOWN links' weights, spatial and temporal) / (the number of UNKNOWN pixels).  M is inverted by an orthonormal
+ * table product along the frames, one screened direct solve per mode k shifted by (w-bar + tau-bar mu_k) / s-bar, and the transposed
+ * product: with free time the DCT-II and mu_k = 2 - 2 cos(pi k / frames), with periodic time the Hartley table (cos + sin)(2 pi k t /
+ * frames) / sqrt(frames) and mu_k = 2 - 2 cos(2 pi k / frames).  Measured on one MI355X with 1 in 30 pixels known: links
+ * log-uniform over two decades 38 - 40 iterations, links over three to four decades 94 - 140 (raise max_iters for more contrast).
+ * Size, chunks, stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, methods, SC_FLAG_FFT_FP64 limits, host waits, sc_run_info:
+ * sc_hip_volume's.
+ * Codes: everything sc_hip_volume_check refuses, and SC_ERR_BAD_ARG for time_periodic that is not 0 or 1, frames < 3 with
+ * time_periodic, precond_smooth or precond_tau that is not finite.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others
+ * run -- for every per-job refusal of sc_hip_volume; exactly one of smooth_x / smooth_y; link arrays where the first volume has none, or
+ * the reverse; a link array overlapping out; a live link that is not finite or not > 0 (smooth_t as well as its product with tau),
+ * judged only where it is read.  The pin check is sc_hip_volume's; an UNKNOWN - KNOWN link counts its own weight.
+ * Not offered: robust penalties on volumes, motion-compensated temporal links, the 8-bit entry points. */
+typedef struct sc_volume_wls_params {
+    int       kind;            /* as sc_volume_params.kind */
+    int       frames;          /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
+    long long frame_stride;    /* floats from a frame to the next in every array; at least the span of one frame under the layout */
+    float     tau;             /* multiplies every temporal link; finite, > 0 */
+    int       time_periodic;   /* 0: the ends of time are free; 1: frame frames - 1 is linked to frame 0 */
+    float     tol;             /* stop when ||r||_2 <= tol * ||b||_2 on every (volume, channel); <= 0: 1e-5 */
+    int       max_iters;       /* <= 0: 400 */
+    float     precond_lambda;  /* w-bar of the preconditioner; <= 0: the chunk's mean */
+    float     precond_smooth;  /* s-bar; <= 0: the mean of the spatial links live in the region of the chunk */
+    float     precond_tau;     /* tau-bar; <= 0: the mean of the live temporal links of the chunk */
+} sc_volume_wls_params;
+typedef struct sc_volume_wls_job {
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE: `frames` frames, read at links live in the region */
+    const float *gt;         /* SC_POISSON_GUIDANCE: frames - 1 frames (time_periodic: frames), read at live temporal links; NULL: zeros */
+    const float *lap;        /* SC_POISSON_LAPLACIAN: read at UNKNOWN pixels */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* `frames` frames, > 0 at links live in the region; both NULL: every spatial link 1 */
+    const float *smooth_y;
+    const float *smooth_t;   /* frames - 1 frames (time_periodic: frames), > 0 at live temporal links; NULL: every temporal link tau */
+    const float *boundary;   /* its Dirichlet lines in every frame (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names in every frame is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_volume_wls_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_wls_check(const sc_volume_wls_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_wls_device(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_wls_job *jobs, int n,
+                                    bool bSync);
+/* One volume on host arrays, as sc_hip_volume: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                             const float *gt, const float *lap, const float *data, const float *state, const float *weight,
+                             const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -263,6 +263,19 @@ class VolumeJob(C.Structure):
                 ("weight", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# WLS volume solves (sc_hip_volume_wls*): Instance.volume_wls / volume_wls_device -- volume solves with per-link weights in space and
+# time and, if asked, periodic time
+class VolumeWlsParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("frames", C.c_int), ("frame_stride", C.c_longlong), ("tau", C.c_float), ("time_periodic", C.c_int),
+                ("tol", C.c_float), ("max_iters", C.c_int), ("precond_lambda", C.c_float), ("precond_smooth", C.c_float), ("precond_tau", C.c_float)]
+
+
+class VolumeWlsJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("gt", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p),
+                ("weight", C.c_void_p), ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("smooth_t", C.c_void_p), ("boundary", C.c_void_p),
+                ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
 SC_ROBUST_ISOTROPIC = 1 << 20        # or'ed into RobustParams.kind only: one penalty per pixel over its two forward links
 SC_ROBUST_JOINT_CHANNELS = 1 << 21   # ... one penalty over all channels of a job (both: vectorial TV)
@@ -492,6 +505,13 @@ def load():
     L.sc_hip_volume_device.restype = C.c_int
     L.sc_hip_volume.argtypes = [C.c_void_p, C.POINTER(VolumeParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
     L.sc_hip_volume.restype = C.c_int
+    L.sc_hip_volume_wls_check.argtypes = [C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_wls_check.restype = C.c_int
+    L.sc_hip_volume_wls_device.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout), C.POINTER(VolumeWlsJob), C.c_int,
+                                           C.c_bool]
+    L.sc_hip_volume_wls_device.restype = C.c_int
+    L.sc_hip_volume_wls.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 12
+    L.sc_hip_volume_wls.restype = C.c_int
     L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_robust_check.restype = C.c_int
     L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
@@ -892,6 +912,63 @@ def volume_arrays(data, state, weight=None, gx=None, gy=None, gt=None, lap=None,
     return kind, data, state, weight, gx, gy, gt, lap, boundary
 
 
+def volume_wls_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                     tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0, precond_tau: float = 0.0,
+                     layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                     channel_stride=None) -> int:
+    """Host-only sc_hip_volume_wls_check: SC_OK or the code a WLS volume call with these parameters and this layout returns before it
+    runs anything.  The layout (of one frame) as a PoissonLayout or as keyword fields."""
+    p = VolumeWlsParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(tol), int(max_iters),
+                        float(precond_lambda), float(precond_smooth), float(precond_tau))
+    return _check_call("sc_hip_volume_wls_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_wls_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gx=None, gy=None, gt=None, lap=None, boundary=None,
+                      tau=1.0, loop=False, neumann=False, free_sides="", periodic=""):
+    """Checks a WLS volume problem's numpy arrays before any device is touched: (kind, data, state, weight, smooth_x, smooth_y, smooth_t,
+    gx, gy, gt, lap, boundary), every array C-contiguous float32.  volume_arrays' rules for all but the link weights and the temporal
+    arrays' length: gt and smooth_t hold T - 1 frames, with loop (periodic time, T >= 3) T frames, the last of them the link from frame
+    T - 1 to frame 0.  smooth_x, smooth_y: together, of data's shape or T x H x W (broadcast over the channels); smooth_t likewise at its
+    own length.  Their values are judged on the device where their links are live."""
+    if not isinstance(data, np.ndarray) or data.dtype != np.float32:
+        raise TypeError("data must be a float32 numpy array")
+    if data.ndim not in (3, 4):
+        raise ValueError("volume arrays are T x H x W or T x H x W x C with C in 1..4")
+    T = data.shape[0]
+    if loop and T < 3:
+        raise ValueError("a looping volume has at least 3 frames")
+    if (smooth_x is None) != (smooth_y is None):
+        raise ValueError("smooth_x and smooth_y go together (both None: every spatial link 1)")
+    tshape = ((T if loop else T - 1),) + data.shape[1:]
+
+    def shaped(name, a, shape):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+        if a.ndim == 3 and len(shape) == 4 and a.shape == shape[:3]:
+            a = np.broadcast_to(a[:, :, :, None], shape)
+        if a.shape != shape:
+            raise ValueError(f"{name} has shape {a.shape}, the problem {shape}")
+        return np.ascontiguousarray(a)
+
+    if gt is not None and loop:          # (volume_arrays checks gt at T - 1 frames: the wrapping frame is checked here)
+        if gx is None or lap is not None:
+            raise ValueError("gt goes with gx and gy")
+        gt_full = shaped("gt", gt, tshape)
+        gt = gt_full[:T - 1]
+    else:
+        gt_full = None
+    kind, data, state, weight, gx, gy, gt, lap, boundary = volume_arrays(data, state, weight, gx, gy, gt, lap, boundary, tau, neumann, free_sides,
+                                                                         periodic)
+    if gt_full is not None:
+        gt = gt_full
+    if smooth_x is not None:
+        smooth_x, smooth_y = shaped("smooth_x", smooth_x, data.shape), shaped("smooth_y", smooth_y, data.shape)
+    if smooth_t is not None:
+        smooth_t = shaped("smooth_t", smooth_t, tshape)
+    return kind, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, lap, boundary
+
+
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
                  max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
                  cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None, isotropic=False,
@@ -1250,6 +1327,36 @@ class Instance:
         for all.  sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is
         returned, other failures raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_volume_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- WLS volume solves on float32 arrays
+    def volume_wls(self, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gx=None, gy=None, gt=None, lap=None, boundary=None,
+                   tau=1.0, loop=False, neumann=False, free_sides="", periodic="", tol=0.0, max_iters=0, precond_lambda=0.0, precond_smooth=0.0,
+                   precond_tau=0.0, allow_not_converged=False):
+        """sc_hip_volume_wls on numpy float32 arrays of shape T x H x W or T x H x W x C (volume_wls_arrays' rules): volume()'s problem with
+        the spatial links smooth_x, smooth_y (None: 1) and the temporal links tau * smooth_t (None: tau); loop: periodic time -- frame
+        T - 1 is linked to frame 0, gt and smooth_t hold T frames.  Returns a NEW array composed as volume()'s; info() has the iterations
+        and the final residual."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, lap, boundary = volume_wls_arrays(data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                              gx, gy, gt, lap, boundary, tau, loop, neumann,
+                                                                                              free_sides, periodic)
+        layout = poisson_layout_of(data[0])
+        p = VolumeWlsParams(kind, data.shape[0], data[0].size, float(tau), 1 if loop else 0, float(tol), int(max_iters), float(precond_lambda),
+                            float(precond_smooth), float(precond_tau))
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_wls(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                      (gx, gy, gt, lap, data, state, weight, sx, sy, smt, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    @staticmethod
+    def make_volume_wls_jobs(n: int):
+        return (VolumeWlsJob * n)()
+
+    def volume_wls_device(self, params: VolumeWlsParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_wls_device: jobs is a VolumeWlsJob array (make_volume_wls_jobs) of device pointers, one frame layout and one
+        frame stride for all.  sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code:
+        SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_volume_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",

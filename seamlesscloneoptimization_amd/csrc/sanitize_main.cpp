@@ -18,6 +18,7 @@
 //      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps; the coupling
 //      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check;
 //      sc_hip_volume_check: the same verdicts for two frames a frame's span apart, then frames, the plane limit, frame_stride and tau.
+//      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
@@ -429,6 +430,44 @@ int main()
                 for (float tau : { 0.f, -1.f, nan, inf }) {
                     vp.tau = tau;
                     if (sc_hip_volume_check(&vp, &l) != SC_ERR_BAD_ARG) return fail("volume_check (tau)");
+                }
+            }
+            // the WLS volume call: the volume call's verdicts on the same cases under either kind of time, then its own refusals
+            for (int tp = 0; tp < 2; ++tp) {
+                const int fr = tp ? 3 : 2;
+                sc_volume_wls_params wp{ k.kind, fr, span, 1.f, tp, k.tol, k.iters, k.plam, 0.f, 0.f };
+                if (sc_hip_volume_wls_check(&wp, &l) != k.want) return fail("volume_wls_check");
+                wp.precond_smooth = wp.precond_tau = k.plam;          // (the same values make the same verdicts)
+                if (sc_hip_volume_wls_check(&wp, &l) != k.want) return fail("volume_wls_check (precond_smooth, precond_tau)");
+                wp.precond_smooth = wp.precond_tau = 0.f;
+                wp.kind = k.kind | SC_ROBUST_ISOTROPIC;
+                if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (coupling bits)");
+                wp.kind = k.kind;
+                if (k.want != SC_OK) continue;
+                wp.frames = tp ? 2 : 1;
+                if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (too few frames)");
+                wp.frames = SC_POISSON_MAX_PLANES / k.c;
+                if (sc_hip_volume_wls_check(&wp, &l) != SC_OK) return fail("volume_wls_check (the plane limit)");
+                wp.frames = SC_POISSON_MAX_PLANES / k.c + 1;
+                if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_SIZE) return fail("volume_wls_check (beyond the plane limit)");
+                wp.frames = fr; wp.frame_stride = span - 1;
+                if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (frame_stride)");
+                wp.frame_stride = span;
+                for (float tau : { 0.f, -1.f, nan, inf }) {
+                    wp.tau = tau;
+                    if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (tau)");
+                }
+                wp.tau = 1.f;
+                for (float v : { nan, inf, -inf }) {
+                    wp.precond_smooth = v;
+                    if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (precond_smooth)");
+                    wp.precond_smooth = 0.f; wp.precond_tau = v;
+                    if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (precond_tau)");
+                    wp.precond_tau = 0.f;
+                }
+                for (int bad : { 2, -1 }) {
+                    wp.time_periodic = bad;
+                    if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (time_periodic)");
                 }
             }
             // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps

@@ -164,6 +164,7 @@ struct Instance {
     DevBuf h_face, h_body, h_mask, h_out;
     DevBuf h_sx, h_sy;                             // a WLS host call's two link arrays (float_stage)
     DevBuf h_state;                                // a region host call's state array (float_stage)
+    DevBuf h_gt, h_smt;                            // a volume host call's temporal guidance and temporal link weights (float_stage)
     std::unique_ptr<RowCopier> copier;   // helper threads for the packing / splicing copies (created on first use)
     hipEvent_t ev_chunk[8]{};            // D2H chunk completions (host path): splice chunk k while k+1 is in flight
     // ROI mask after 3x erode
@@ -371,11 +372,13 @@ inline bool poisson_no_dirichlet(int kind)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 // What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
-enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16 };
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16, FLOAT_SMOOTH_T = 32 };
 struct FloatArrays {
     const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; const float *smooth_x = nullptr, *smooth_y = nullptr;
     const float *state = nullptr;      // FLOAT_STATE: the region call's state array
     const float *gt = nullptr;         // FLOAT_GT: the volume call's temporal guidance (may be NULL: zeros)
+    const float *smooth_t = nullptr;   // FLOAT_SMOOTH_T: the WLS volume call's temporal link weights
+    const char *refuse = nullptr;      // the family's own reason against this job (float_job_validate: SC_ERR_BAD_ARG with it)
 };
 // A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
 // family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
@@ -387,17 +390,18 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 // side a Poisson job may come without boundary (mean zero) and the other families do not read it: float_dev_job drops it there.
 // FLOAT_SMOOTH: the two link arrays as well, and -- span > 0, the floats an array occupies under the call's layout (poisson_span) --
 // neither they nor weight may share a float of their span with out's.  FLOAT_STATE: the state array as well, under the same span rule
-// (which then holds for whichever of weight and the link arrays the call carries).
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0);
+// (which then holds for whichever of weight and the link arrays the call carries).  FLOAT_SMOOTH_T: the temporal link array as well; it
+// occupies tspan floats (the call's temporal frames) and may share none of them with out's span.
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0, size_t tspan = 0);
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
 // The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT), their link weights (NULL without
 // FLOAT_SMOOTH) and where each one's code goes.
-struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy, st, gt; std::vector<int *> rcs; };
+struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy, st, gt, smt; std::vector<int *> rcs; };
 // A device call's job intake: arrays_of(job) names one public job's arrays.  A job that fails float_job_validate gets its code; the
 // others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
 // empty: nothing to run).
 template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int carries, Job *jobs, int n, ArraysOf arrays_of, FloatJobs &v,
-                                                      size_t span = 0)
+                                                      size_t span = 0, size_t tspan = 0)
 {
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
@@ -405,7 +409,7 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
     for (int i = 0; i < n; ++i) {
         Job &j = jobs[i];
         const FloatArrays a = arrays_of(j);
-        const int vrc = float_job_validate(kind, carries, a, &why, span);
+        const int vrc = float_job_validate(kind, carries, a, &why, span, tspan);
         if (vrc != SC_OK) {
             j.rc = vrc;
             if (worst == SC_OK) { worst = vrc; I->err = why; }
@@ -418,6 +422,7 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
         v.sy.push_back(a.smooth_y);
         v.st.push_back(a.state);
         v.gt.push_back(a.gt);
+        v.smt.push_back(a.smooth_t);
         v.rcs.push_back(&j.rc);
     }
     return worst;
@@ -425,11 +430,14 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
 // boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state --, uploaded in that order.  job: the
 // device job (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights, d_sx, d_sy: the link weights, d_state: the states.
-// frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; gt, FLOAT_GT
-// and not NULL, holds frames - 1 and goes behind state (through the link arrays' pinned block, which a volume call leaves free).
-struct FloatStaged { PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr, *d_state = nullptr, *d_gt = nullptr; };
+// frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; the
+// temporal arrays -- gt, FLOAT_GT and not NULL, and smooth_t, FLOAT_SMOOTH_T -- hold tframes of them (0: frames - 1) and go behind
+// state, each through a pinned block of its own.
+struct FloatStaged {
+    PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr, *d_state = nullptr, *d_gt = nullptr, *d_smt = nullptr;
+};
 int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames = 1,
-                long long frame_stride = 0);
+                long long frame_stride = 0, int tframes = 0);
 // nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and
 // sets their codes.  SC_OK and SC_ERR_NOT_CONVERGED let the call go on; any other code ends it: that chunk's jobs and every one not
 // yet run read it, after SC_ERR_HIP the ones already run too.  Returns that code, else the worst.

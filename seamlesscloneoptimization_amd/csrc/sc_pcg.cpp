@@ -256,13 +256,14 @@ int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, 
 {
     const char *why = "";
     int rc;
-    if ((rc = float_job_validate(call.kind, carries, a, &why, pcg_call_span(call, l)))) { I->err = why; return rc; }
+    if ((rc = float_job_validate(call.kind, carries, a, &why, pcg_call_span(call, l), pcg_call_tspan(call, l)))) { I->err = why; return rc; }
     FloatStaged s;
-    if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride))) return rc;
+    if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride, call.tframes))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
     op.bind(&s.d_w, &s.d_sx, &s.d_sy);
     op.bind_state(&s.d_state);
     op.bind_gt(&s.d_gt);
+    op.bind_smooth_t(&s.d_smt);
     rc = pcg_run(I, call, l, op, &s.job, job_rcs, 1, true, chunk);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)

@@ -57,6 +57,7 @@ struct PcgOperator {
     virtual void bind(const float *const *w, const float *const *sx, const float *const *sy) = 0;
     virtual void bind_state(const float *const *state) {}                           // ... and its state arrays (the region call's; the others have none)
     virtual void bind_gt(const float *const *gt) {}                                 // ... and its temporal guidance (the volume call's; NULL entries: zeros)
+    virtual void bind_smooth_t(const float *const *smooth_t) {}                     // ... and its temporal link weights (the WLS volume call's; NULL entries: every one tau)
     // work planes per job and channel that run_chunks counts against SC_POISSON_MAX_PLANES (the volume call: its frames), and the work
     // planes' geometry: by default one plane of mg's unknowns per (job, channel) (the volume call: its frames stacked along y)
     virtual int chunk_planes(int C) const { return C; }
@@ -103,10 +104,14 @@ struct PcgOperator {
     }
 };
 // kind: poisson_norm_kind's; frames, frame_stride: the volume call's -- a job's arrays are `frames` images under the layout, frame_stride
-// floats apart (gt: frames - 1 of them)
-struct PcgCall { int kind; float tol; int max_iters; int default_iters; int frames = 1; long long frame_stride = 0; };
-// the floats from an array's pointer to one past its last element, all frames of the call
+// floats apart; tframes: how many of them the temporal arrays hold (gt, smooth_t: frames - 1 with free time, frames with periodic time)
+struct PcgCall { int kind; float tol; int max_iters; int default_iters; int frames = 1; long long frame_stride = 0; int tframes = 0; };
+// the floats from an array's pointer to one past its last element, all frames of the call (pcg_call_tspan: of a temporal array)
 inline size_t pcg_call_span(const PcgCall &call, const sc_poisson_layout *l) { return poisson_span(l) + (size_t)(call.frames - 1) * (size_t)call.frame_stride; }
+inline size_t pcg_call_tspan(const PcgCall &call, const sc_poisson_layout *l)
+{
+    return call.tframes > 0 ? poisson_span(l) + (size_t)(call.tframes - 1) * (size_t)call.frame_stride : 0;
+}
 struct PcgChunkResult { int iters = 0; bool converged = true; double rel = 0.0; };
 // One chunk of m same-size jobs between its prologue and its output, in three steps a family's driver may put its own between:
 //   pcg_chunk_begin    the statistics, the judgement of every job (a refused one gets SC_ERR_BAD_ARG and leaves), the buffers; mv = the
@@ -159,12 +164,13 @@ template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgC
                                                          ArraysOf arrays_of, PcgOperator &op, bool timed, PcgChunkFn chunk = nullptr)
 {
     FloatJobs v;
-    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l));
+    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l), pcg_call_tspan(call, l));
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
     op.bind(v.w.data(), v.sx.data(), v.sy.data());
     op.bind_state(v.st.data());
     op.bind_gt(v.gt.data());
+    op.bind_smooth_t(v.smt.data());
     return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
 }
 
@@ -253,27 +259,36 @@ void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const 
 // the jobs' out: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
 void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *st, int m, const float *U, hipStream_t s);
 
-// ---- the volume family (sc_volume.hip): the region system with unit spatial links on a stack of T frames, plus temporal links of the
-// constant weight tau between (q, t) and (q, t + 1).  A job's arrays hold T frames (gt: T - 1) fs floats apart.  Work planes: one per
-// (volume, channel), the frames stacked along y: wg.ny = T * (a frame's rows of unknowns), wg from VolumeOperator::work_geo.
-struct VolumeJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *st[MAX], *gt[MAX]; };
-struct VolumeGeo { int T, ny; long long fs; float tau; };      // ny: a frame's rows of unknowns
-constexpr int VOLUME_STATS = 5;
+// ---- the volume family (sc_volume.hip): the region system on a stack of T frames, plus temporal links between (q, t) and (q, t + 1)
+// -- and, under periodic time, between (q, T - 1) and (q, 0).  A spatial link weighs sx / sy (NULL: 1), a temporal one lt = tau * smt
+// rounded to float32 (smt NULL: tau).  A job's arrays hold T frames fs floats apart (gt, smt: T - 1, with periodic time T; element
+// (q, t) belongs to the link from frame t to the next).  Work planes: one per (volume, channel), the frames stacked along y: wg.ny =
+// T * (a frame's rows of unknowns), wg from VolumeOperator::work_geo.
+struct VolumeJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *st[MAX], *gt[MAX], *sx[MAX], *sy[MAX], *smt[MAX]; };
+struct VolumeGeo { int T, ny; long long fs; float tau; int periodic; };      // ny: a frame's rows of unknowns; periodic: time wraps
+// a volume job's arrays beside its PoissonJobDev, one pointer per job each (an array of NULLs where the call has none)
+struct VolumeArrays { const float *const *w, *const *st, *const *gt, *const *sx, *const *sy, *const *smt; };
+constexpr int VOLUME_STATS = 11, VOLUME_STATS_PLAIN = 5;
 // stats[(plane * PCG_PARTS + i) * VOLUME_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
-// its UNKNOWN pixels | the sum of its UNKNOWN - KNOWN links (spatial 1, temporal tau) | its state elements that are not 0, 1 or 2
-void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *w,
-                         const float *const *st, int m, double *stats, hipStream_t s);
-// R = b (the order: seamlessclone_hip.h, the volume section); E / S / F = the link to the next column / row / frame where both ends are
-// UNKNOWN (1, 1, tau); Dg = the sum of the incident live links plus w; all five 0 at every pixel that is not UNKNOWN; bb = the parts of b . b
-void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const float *const *w,
-                         const float *const *st, const float *const *gt, int m, float *R, float *E, float *S, float *F, float *Dg, double *bb,
-                         hipStream_t s);
+// its UNKNOWN pixels | the sum of its UNKNOWN - KNOWN links' weights, spatial and temporal | its state elements that are not 0, 1 or 2 |
+// the sum of its spatial links live in the region (k_region_stats' owner rule) | how many there are | how many are invalid | the sum of
+// its live temporal links lt (the earlier frame owns a link, frame T - 1 the wrapping one) | how many there are | how many are invalid.
+// A call without any link array under free time (a.sx[0] and a.smt[0] NULL, vg.periodic 0) has parts of the first VOLUME_STATS_PLAIN
+// fields alone, as sc_hip_volume always had: stats[(plane * PCG_PARTS + i) * VOLUME_STATS_PLAIN + ..].
+void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+                         double *stats, hipStream_t s);
+// R = b (the order: seamlessclone_hip.h, the volume sections); E / S / F = the link to the next column / row / frame where both ends are
+// UNKNOWN (F in the last frame's rows: the wrapping link, 0 with free time); Dg = the sum of the incident live links plus w; all five 0
+// at every pixel that is not UNKNOWN; bb = the parts of b . b
+void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+                         float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s);
 // residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
 void launch_volume_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool residual, const float *P, const float *E, const float *S, const float *F,
                       const float *Dg, float *Q, double *parts, hipStream_t s);
-// D[k * T + t] = the orthonormal DCT-II along the frames (computed in double, rounded to float32); lam[p * T + k] = the shift of mode k
-// of every one of the `planes` work planes: (float)(wbar + tau (2 - 2 cos(pi k / T))) as a double
-void launch_volume_tables(int T, int planes, double wbar, double tau, float *D, double *lam, hipStream_t s);
+// D[k * T + t] = the orthonormal transform along the frames that diagonalises A_t (free time: the DCT-II; periodic time: the Hartley
+// table, symmetric and its own inverse), computed in double, rounded to float32; lam[p * T + k] = the shift of mode k of every one of
+// the `planes` work planes: (float)((wbar + tau mu_k) / sbar) as a double, mu_k = 2 - 2 cos(pi k / T), periodic: 2 - 2 cos(2 pi k / T)
+void launch_volume_tables(int T, int planes, bool periodic, double wbar, double tau, double sbar, float *D, double *lam, hipStream_t s);
 // out[p][k] = sum_t D[k][t] in[p][t] (transposed: sum_t D[t][k] in[p][t]) for every pixel of the frames of `planes` work planes
 void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool transposed, const float *D, const float *in, float *out, hipStream_t s);
 // the jobs' out, frame by frame: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines

@@ -117,8 +117,9 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 
 // (a job without a Dirichlet line on any side -- the Neumann call, a periodic axis beside a periodic or free-free one -- needs no
 // boundary: out is then checked in its place)
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span)
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span, size_t tspan)
 {
+    if (a.refuse) { *why = a.refuse; return SC_ERR_BAD_ARG; }
     if ((carries & FLOAT_DATA) && !a.data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
     if ((carries & FLOAT_WEIGHT) && !a.weight) { *why = "null weight pointer"; return SC_ERR_BAD_ARG; }
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
@@ -141,6 +142,10 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
         if (!aligned4(a.state)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
     }
     if ((carries & FLOAT_GT) && a.gt && !aligned4(a.gt)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    if (carries & FLOAT_SMOOTH_T) {
+        if (!a.smooth_t) { *why = "null smooth_t pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(a.smooth_t)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
     if (span && (carries & (FLOAT_SMOOTH | FLOAT_STATE))) {
         const uintptr_t o = (uintptr_t)a.out, bytes = span * sizeof(float);
         auto overlaps = [&](const float *q) { return (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes; };
@@ -148,6 +153,10 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
                                 carries & FLOAT_SMOOTH ? a.smooth_y : nullptr })
             if (q && overlaps(q)) { *why = "weight, smooth_x or smooth_y overlaps out"; return SC_ERR_BAD_ARG; }
         if ((carries & FLOAT_STATE) && overlaps(a.state)) { *why = "state overlaps out"; return SC_ERR_BAD_ARG; }
+    }
+    if (span && tspan && (carries & FLOAT_SMOOTH_T)) {          // (its own length: the call's temporal frames)
+        const uintptr_t o = (uintptr_t)a.out, q = (uintptr_t)a.smooth_t;
+        if (q < o + span * sizeof(float) && o < q + tspan * sizeof(float)) { *why = "smooth_t overlaps out"; return SC_ERR_BAD_ARG; }
     }
     return SC_OK;
 }
@@ -159,7 +168,8 @@ PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a)
     return j;
 }
 
-int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames, long long frame_stride)
+int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames, long long frame_stride,
+                int tframes)
 {
     const size_t bytes = (poisson_span(l) + (size_t)(frames - 1) * (size_t)frame_stride) * sizeof(float), slot = (bytes + 255) / 256 * 256;
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
@@ -168,7 +178,9 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
     const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0, gt = (carries & FLOAT_GT) && guidance && a.gt;
-    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0) + (gt ? 1 : 0);
+    const bool smooth_t = (carries & FLOAT_SMOOTH_T) != 0;
+    const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0) + (gt ? 1 : 0) +
+                      (smooth_t ? 1 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -178,7 +190,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_in0 = next(true), *d_in1 = next(guidance), *d_d = next(data != nullptr), *d_w = next(weight != nullptr);
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
-    float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state), *d_gt = next(gt);
+    float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state), *d_gt = next(gt), *d_smt = next(smooth_t);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -193,11 +205,12 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     s.d_sy = d_sy;
     if ((rc = upload(I->h_state, d_state, a.state))) return rc;
     s.d_state = d_state;
-    if (d_gt) {          // (one frame less than the others)
-        const size_t gbytes = bytes - (size_t)frame_stride * sizeof(float);
-        if ((rc = upload_rows(I, I->h_sx, d_gt, gbytes, (const uint8_t *)a.gt, gbytes, gbytes, 1))) return rc;
-    }
+    // the temporal arrays: tframes frames (0: one less than the others)
+    const size_t tbytes = (poisson_span(l) + (size_t)((tframes > 0 ? tframes : frames - 1) - 1) * (size_t)frame_stride) * sizeof(float);
+    if (d_gt && (rc = upload_rows(I, I->h_gt, d_gt, tbytes, (const uint8_t *)a.gt, tbytes, tbytes, 1))) return rc;
     s.d_gt = d_gt;
+    if (d_smt && (rc = upload_rows(I, I->h_smt, d_smt, tbytes, (const uint8_t *)a.smooth_t, tbytes, tbytes, 1))) return rc;
+    s.d_smt = d_smt;
     return SC_OK;
 }
 

@@ -1,20 +1,22 @@
-// sc_volume.hip -- the volume family's kernels (sc_hip_volume*, sc_volume_api.cpp) under the shared conjugate gradients (sc_pcg.h): the
-// region family's system (sc_region.hip) with unit spatial links on a stack of T frames, plus temporal links of the constant weight tau
-// between pixel q of frame t and pixel q of frame t + 1.  A temporal link follows the spatial rule: it is live when neither end is
-// OUTSIDE and at least one end is UNKNOWN; a KNOWN temporal neighbour adds tau to the diagonal of its unknown end and tau * data to the
-// right-hand side; the two ends of time are free.  Pixels on the border kind's Dirichlet lines are no part of a work plane and have no
-// temporal links.
+// sc_volume.hip -- the volume families' kernels (sc_hip_volume*, sc_hip_volume_wls*; sc_volume_api.cpp) under the shared conjugate
+// gradients (sc_pcg.h): the region family's system (sc_region.hip) on a stack of T frames, plus temporal links between pixel q of frame t
+// and pixel q of frame t + 1.  A spatial link weighs sx / sy as in the region family (no arrays: 1), a temporal one lt = tau * smooth_t,
+// one rounded float32 product (no array: tau).  A temporal link follows the spatial rule: it is live when neither end is OUTSIDE and at
+// least one end is UNKNOWN; a KNOWN temporal neighbour adds lt to the diagonal of its unknown end and lt * data to the right-hand side.
+// The two ends of time are free, or -- periodic time -- frame T - 1 is linked to frame 0 by a link like any other, stored with frame
+// T - 1.  Pixels on the border kind's Dirichlet lines are no part of a work plane and have no temporal links.
 //
 // Work planes: one per (volume, channel), the T frames stacked along y -- nx x (T ny), frame t at rows [t ny, (t + 1) ny).  So the
 // element-wise launches, the partial sums and the stop rule of sc_pcg.hip see one system per (volume, channel) and need not know about
 // frames; the launches here do.  Coefficient planes: E, S, Dg as the region family's (S is 0 in a frame's last row unless y wraps, and
-// then joins the frame's own first row) and F, the link to the next frame.  As in the region family every coefficient and the
-// right-hand side are 0 at a pixel that is not UNKNOWN, and E, S, F are kept only where both ends are UNKNOWN, which makes the iteration
-// that of the UNKNOWN pixels alone (sc_region.hip: why).
+// then joins the frame's own first row) and F, the link to the next frame (in the last frame's rows: the wrapping link, 0 with free
+// time).  As in the region family every coefficient and the right-hand side are 0 at a pixel that is not UNKNOWN, and E, S, F are kept
+// only where both ends are UNKNOWN, which makes the iteration that of the UNKNOWN pixels alone (sc_region.hip: why).
 //
-// The preconditioner M = A - w-bar + tau A_t (A_t: the free-ended second difference along the frames) is inverted exactly: the
-// orthonormal DCT-II along the frames (k_volume_dct) turns it into T two-dimensional screened problems, mode k shifted by
-// w-bar + tau (2 - 2 cos(pi k / T)), which one direct_jobs_solve with a shift per plane solves; the transposed transform goes back.
+// The preconditioner M = s-bar A - w-bar + tau-bar A_t (A_t: the second difference along the frames, free-ended or circulant) is
+// inverted exactly: an orthonormal table product along the frames (k_volume_dct; the DCT-II, or the Hartley table under periodic time)
+// turns it into T two-dimensional screened problems, mode k shifted by (w-bar + tau-bar mu_k) / s-bar, which one direct_jobs_solve with
+// a shift per plane solves; the transposed product goes back.  The factor 1 / s-bar that is left goes once on u0 (PcgOperator::scale_start).
 #include "sc_region_device.h"
 #include <cmath>
 #include <vector>
@@ -32,16 +34,49 @@ struct FrameRow {
 // the pixel across a temporal link: NB_NONE beyond either end of time
 __device__ __forceinline__ int time_kind(const float *__restrict__ st, long long o, bool exists) { return exists ? state_kind(st[o]) : NB_NONE; }
 
+__device__ __forceinline__ bool bad_link(float v) { return !(v > 0.f) || v > 3.4028234e38f; }
+
+// The two temporal neighbours of frame t's element at offset o: where they lie -- the wrap of periodic time included -- and whether
+// they exist.  The link to the previous frame, its weight and its guidance value are stored at ob, those to the next frame at o.
+struct TimeAround {
+    long long ob, of;
+    bool hb, hf;
+    // wraps false (a launch under free time, known at compile time): one frame before and behind, nothing else is computed
+    __device__ __forceinline__ TimeAround(const VolumeGeo &vg, int t, long long o, bool wraps)
+    {
+        if (!wraps) {
+            ob = o - vg.fs; of = o + vg.fs;
+            hb = t > 0; hf = t < vg.T - 1;
+            return;
+        }
+        const long long wrap = (long long)(vg.T - 1) * vg.fs;
+        ob = t > 0 ? o - vg.fs : o + wrap;
+        of = t < vg.T - 1 ? o + vg.fs : o - wrap;
+        hb = t > 0 || vg.periodic;
+        hf = t < vg.T - 1 || vg.periodic;
+    }
+};
+// the weight of the temporal link stored at element e: tau * smooth_t, one rounded product (no array: tau)
+__device__ __forceinline__ float time_link(const float *__restrict__ smt, long long e, float tau) { return smt ? rounded_product(tau, smt[e]) : tau; }
+
 // Per plane and part (VOLUME_STATS doubles): the sum of w over the UNKNOWN pixels | how many of those w are invalid | the UNKNOWN
-// pixels | the sum of the UNKNOWN - KNOWN links, a spatial one 1 and a temporal one tau, each counted once by its low end (k_region_stats'
-// rule; the earlier frame owns a temporal link) | the state elements that are not exactly 0, 1 or 2.  t.w NULL: no data term.
+// pixels | the sum of the UNKNOWN - KNOWN links' weights, each counted once by its low end (k_region_stats' rule; the earlier frame owns
+// a temporal link, frame T - 1 the wrapping one) | the state elements that are not exactly 0, 1 or 2 | the sum of the spatial links
+// live in the region, each counted once as k_region_stats counts them | how many | how many of them are invalid | the sum of the live
+// temporal links lt | how many | how many of them are invalid (smooth_t or its product with tau not finite or not > 0).
+// t.w NULL: no data term; t.sx NULL: every spatial link 1; t.smt NULL: every temporal link tau.  LNK false (a call without any link
+// array under free time -- sc_hip_volume's): the links are not looked at, an UNKNOWN - KNOWN link counts 1 or tau, time does not wrap,
+// and a part is the first VOLUME_STATS_PLAIN fields alone; true: every other call, VOLUME_STATS fields per part.
+template <bool LNK>
 __global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, double *__restrict__ stats)
 {
-    __shared__ double ws[VOLUME_STATS][4];
+    constexpr int NS = LNK ? VOLUME_STATS : VOLUME_STATS_PLAIN;
+    __shared__ double ws[NS][4];
     const PcgBand b(g, wg);
     const float *__restrict__ w = t.w[b.member], *__restrict__ st = t.st[b.member];
+    const float *__restrict__ sx = t.sx[b.member], *__restrict__ sy = t.sy[b.member], *__restrict__ smt = t.smt[b.member];
     const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
-    double sw = 0.0, bw = 0.0, nu = 0.0, uk = 0.0, bst = 0.0;
+    double sw = 0.0, bw = 0.0, nu = 0.0, uk = 0.0, bst = 0.0, ss = 0.0, ns = 0.0, bs = 0.0, sl = 0.0, nt = 0.0, bt = 0.0;
     if (b.x < wg.nx)
         for (int y = b.y0; y < b.y1; ++y) {
             const FrameRow fr(vg, y);
@@ -60,24 +95,59 @@ __global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, Vo
                 }
             }
             const Around a(g, wg, st, X, Y, o, px, py);
-            if (kp + a.ke == NB_KNOWN) uk += 1.0;      // one end UNKNOWN (0), the other KNOWN (1)
-            if (kp + a.ks == NB_KNOWN) uk += 1.0;
-            if (kp + time_kind(st, o + vg.fs, fr.t < vg.T - 1) == NB_KNOWN) uk += (double)vg.tau;
+            // the spatial link towards a neighbour of kind kq, stored at element e of its array: live in the region?
+            auto link = [&](int kq, const float *__restrict__ arr, long long e) {
+                if (kq == NB_NONE || (kp != NB_UNKNOWN && kq != NB_UNKNOWN)) return;
+                const float s = arr ? arr[e] : 1.f;
+                if (bad_link(s)) bs += 1.0;
+                ss += (double)s;
+                ns += 1.0;
+                if (kp + kq == NB_KNOWN) uk += (double)s;      // one end UNKNOWN (0), the other KNOWN (1)
+            };
+            const TimeAround ta(vg, fr.t, o, LNK);
+            const int kf = time_kind(st, ta.of, ta.hf);
+            if (!LNK) {
+                if (kp + a.ke == NB_KNOWN) uk += 1.0;
+                if (kp + a.ks == NB_KNOWN) uk += 1.0;
+                if (kp + kf == NB_KNOWN) uk += (double)vg.tau;
+                continue;
+            }
+            link(a.ke, sx, o);
+            link(a.ks, sy, o);
+            if (a.kw == NB_DIRICHLET) link(a.kw, sx, a.ow);
+            if (a.kn == NB_DIRICHLET) link(a.kn, sy, a.on);
+            if (kf != NB_NONE && (kp == NB_UNKNOWN || kf == NB_UNKNOWN)) {
+                const float lt = time_link(smt, o, vg.tau);
+                if (bad_link(lt) || (smt && bad_link(smt[o]))) bt += 1.0;
+                sl += (double)lt;
+                nt += 1.0;
+                if (kp + kf == NB_KNOWN) uk += (double)lt;
+            }
         }
-    part_store(sw, ws[0], wg, stats, VOLUME_STATS, 0);
-    part_store(bw, ws[1], wg, stats, VOLUME_STATS, 1);
-    part_store(nu, ws[2], wg, stats, VOLUME_STATS, 2);
-    part_store(uk, ws[3], wg, stats, VOLUME_STATS, 3);
-    part_store(bst, ws[4], wg, stats, VOLUME_STATS, 4);
+    part_store(sw, ws[0], wg, stats, NS, 0);
+    part_store(bw, ws[1], wg, stats, NS, 1);
+    part_store(nu, ws[2], wg, stats, NS, 2);
+    part_store(uk, ws[3], wg, stats, NS, 3);
+    part_store(bst, ws[4], wg, stats, NS, 4);
+    if constexpr (LNK) {
+        part_store(ss, ws[5], wg, stats, NS, 5);
+        part_store(ns, ws[6], wg, stats, NS, 6);
+        part_store(bs, ws[7], wg, stats, NS, 7);
+        part_store(sl, ws[8], wg, stats, NS, 8);
+        part_store(nt, ws[9], wg, stats, NS, 9);
+        part_store(bt, ws[10], wg, stats, NS, 10);
+    }
 }
 
-// k_region_setup's walk with every spatial link 1, frame by frame, and the temporal part.  b in the order the header states: the
-// region call's guidance sum (a - b) + (c - d); + (e - f), e = tau * gt_t where the link to the next frame is live, f = tau * gt_(t-1)
+// k_region_setup's walk, frame by frame, and the temporal part.  b in the order the header states: the region call's guidance sum
+// (a - b) + (c - d) of the rounded products s * g; + (e - f), e = lt * gt_t where the link to the next frame is live, f = lt * gt_(t-1)
 // where the one to the previous frame is (gt NULL: zeros; a link that is not live counts 0 and is not read); - w d (NOW: no data term);
-// the Dirichlet lines' terms, west, north, east, south; the KNOWN spatial neighbours' likewise; the KNOWN temporal neighbours' tau *
+// the Dirichlet lines' terms, west, north, east, south; the KNOWN spatial neighbours' likewise; the KNOWN temporal neighbours' lt *
 // data, previous frame, then next -- every product rounded on its own and subtracted in turn.  LAP: lap is the whole right-hand side
-// before the folded terms, gx, gy, gt are not read.
-template <bool LAP, bool NOW>
+// before the folded terms, gx, gy, gt are not read.  LNK false (a call without any link array under free time): every spatial link is 1, every
+// temporal one tau, no link array is looked at and time does not wrap -- the set-up sc_hip_volume always had; true: each array is a uniform pointer test.  1 * g = g and tau * 1 = tau exactly, so arrays of
+// 1.0f give the bytes of no arrays.
+template <bool LAP, bool NOW, bool LNK>
 __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, float *__restrict__ R, float *__restrict__ E,
                                                       float *__restrict__ S, float *__restrict__ F, float *__restrict__ Dg, double *__restrict__ bb)
 {
@@ -85,6 +155,7 @@ __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, Vo
     const PcgBand bd(g, wg);
     const PoissonJobDev &j = t.j[bd.member];
     const float *__restrict__ w = t.w[bd.member], *__restrict__ st = t.st[bd.member], *__restrict__ gt = t.gt[bd.member];
+    const float *__restrict__ sx = t.sx[bd.member], *__restrict__ sy = t.sy[bd.member], *__restrict__ smt = t.smt[bd.member];
     const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
     const float tau = vg.tau;
     double s = 0.0;
@@ -96,19 +167,20 @@ __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, Vo
             float v = 0.f, e = 0.f, so = 0.f, f = 0.f, dg = 0.f;
             if (st[o] == 0.f) {
                 const Around a(g, wg, st, X, Y, o, px, py);
-                const int kb = time_kind(st, o - vg.fs, fr.t > 0), kf = time_kind(st, o + vg.fs, fr.t < vg.T - 1);
-                const float lw = a.kw == NB_NONE ? 0.f : 1.f, le = a.ke == NB_NONE ? 0.f : 1.f;
-                const float ln = a.kn == NB_NONE ? 0.f : 1.f, ls = a.ks == NB_NONE ? 0.f : 1.f;
-                const float lb = kb == NB_NONE ? 0.f : tau, lf = kf == NB_NONE ? 0.f : tau;
+                const TimeAround ta(vg, fr.t, o, LNK);
+                const int kb = time_kind(st, ta.ob, ta.hb), kf = time_kind(st, ta.of, ta.hf);
+                const float lw = a.kw == NB_NONE ? 0.f : LNK && sx ? sx[a.ow] : 1.f, le = a.ke == NB_NONE ? 0.f : LNK && sx ? sx[o] : 1.f;
+                const float ln = a.kn == NB_NONE ? 0.f : LNK && sy ? sy[a.on] : 1.f, ls = a.ks == NB_NONE ? 0.f : LNK && sy ? sy[o] : 1.f;
+                const float lb = kb == NB_NONE ? 0.f : LNK ? time_link(smt, ta.ob, tau) : tau, lf = kf == NB_NONE ? 0.f : LNK ? time_link(smt, o, tau) : tau;
                 if (LAP) v = j.lap[o];
                 else {
-                    const float ta = a.ke == NB_NONE ? 0.f : rounded_product(le, j.gx[o]);
-                    const float tb = a.kw == NB_NONE ? 0.f : rounded_product(lw, j.gx[a.ow]);
-                    const float tc = a.ks == NB_NONE ? 0.f : rounded_product(ls, j.gy[o]);
-                    const float td = a.kn == NB_NONE ? 0.f : rounded_product(ln, j.gy[a.on]);
-                    const float te = (kf == NB_NONE || !gt) ? 0.f : rounded_product(tau, gt[o]);
-                    const float tf = (kb == NB_NONE || !gt) ? 0.f : rounded_product(tau, gt[o - vg.fs]);
-                    v = ((ta - tb) + (tc - td)) + (te - tf);
+                    const float pa = a.ke == NB_NONE ? 0.f : rounded_product(le, j.gx[o]);
+                    const float pb = a.kw == NB_NONE ? 0.f : rounded_product(lw, j.gx[a.ow]);
+                    const float pc = a.ks == NB_NONE ? 0.f : rounded_product(ls, j.gy[o]);
+                    const float pd = a.kn == NB_NONE ? 0.f : rounded_product(ln, j.gy[a.on]);
+                    const float pe = (kf == NB_NONE || !gt) ? 0.f : rounded_product(lf, gt[o]);
+                    const float pf = (kb == NB_NONE || !gt) ? 0.f : rounded_product(lb, gt[ta.ob]);
+                    v = ((pa - pb) + (pc - pd)) + (pe - pf);
                 }
                 float wv = 0.f;
                 if (!NOW) {
@@ -123,11 +195,11 @@ __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, Vo
                 if (a.kn == NB_KNOWN) v -= rounded_product(ln, j.d[a.on]);
                 if (a.ke == NB_KNOWN) v -= rounded_product(le, j.d[a.oe]);
                 if (a.ks == NB_KNOWN) v -= rounded_product(ls, j.d[a.os]);
-                if (kb == NB_KNOWN) v -= rounded_product(tau, j.d[o - vg.fs]);
-                if (kf == NB_KNOWN) v -= rounded_product(tau, j.d[o + vg.fs]);
+                if (kb == NB_KNOWN) v -= rounded_product(lb, j.d[ta.ob]);
+                if (kf == NB_KNOWN) v -= rounded_product(lf, j.d[ta.of]);
                 e = a.ke == NB_UNKNOWN ? le : 0.f;
                 so = a.ks == NB_UNKNOWN ? ls : 0.f;
-                f = kf == NB_UNKNOWN ? tau : 0.f;
+                f = kf == NB_UNKNOWN ? lf : 0.f;
                 dg = (((lw + le) + (ln + ls)) + (lb + lf)) + wv;
             }
             const size_t i = (size_t)bd.p * wg.stride + (size_t)y * wg.nx + bd.x;
@@ -145,9 +217,11 @@ __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, Vo
 // F_t(q) P_(t+1)(q) + F_(t-1)(q) P_(t-1)(q).  RES false: Q = L P and the parts of P . Q;  true: Q -= L P and the parts of Q . Q.  A
 // lane owns one column of its band and rolls the row above, its own and the row below through registers, with the north link; where
 // the band crosses into the next frame the roll starts again (the row above is then the frame's last one where y wraps, else none).
-// The two temporal neighbours of its element lie one frame of nx ny floats before and behind it in the same plane.  No atomics, no LDS
-// but the block sum's.
-template <bool RES>
+// The two temporal neighbours of its element lie one frame of nx ny floats before and behind it in the same plane.  PER (periodic
+// time, decided at compile time: the free-time form is the code it was): the neighbour before frame 0 is frame T - 1, through the
+// wrapping link that F holds in the last frame's rows, and the neighbour behind frame T - 1 is frame 0.  No atomics, no LDS but the
+// block sum's.
+template <bool RES, bool PER>
 __global__ __launch_bounds__(WL) void k_volume_op(PcgGeo wg, VolumeGeo vg, const float *__restrict__ P, float *__restrict__ Q, double *__restrict__ parts,
                                                    const float *__restrict__ E, const float *__restrict__ S, const float *__restrict__ F,
                                                    const float *__restrict__ Dg)
@@ -173,8 +247,15 @@ __global__ __launch_bounds__(WL) void k_volume_op(PcgGeo wg, VolumeGeo vg, const
             const size_t ro = (size_t)y * nx, i = base + ro + x;
             const float l = xl >= 0 ? pl[ro + xl] : 0.f, r = xr >= 0 ? pl[ro + xr] : 0.f;
             const float e_l = xl >= 0 ? el[ro + xl] : 0.f, e_r = el[ro + x], s_dn = sl[ro + x];
-            const float tb = fr.t > 0 ? fl[ro + x - n2] * pl[ro + x - n2] : 0.f;
-            const float tf = fr.t < vg.T - 1 ? fl[ro + x] * pl[ro + x + n2] : 0.f;
+            float tb, tf;
+            if (PER) {
+                const size_t wrap = (size_t)(vg.T - 1) * n2, ib = fr.t > 0 ? ro + x - n2 : ro + x + wrap;
+                tb = fl[ib] * pl[ib];
+                tf = fl[ro + x] * pl[fr.t < vg.T - 1 ? ro + x + n2 : ro + x - wrap];
+            } else {
+                tb = fr.t > 0 ? fl[ro + x - n2] * pl[ro + x - n2] : 0.f;
+                tf = fr.t < vg.T - 1 ? fl[ro + x] * pl[ro + x + n2] : 0.f;
+            }
             const float v = (((e_l * l + e_r * r) + (s_up * up + s_dn * dn)) + (tb + tf)) - Dg[i] * cur;
             if (RES) {
                 const float q = Q[i] - v;
@@ -199,17 +280,24 @@ __global__ __launch_bounds__(WL) void k_volume_op(PcgGeo wg, VolumeGeo vg, const
     part_store(s, ws, wg, parts);
 }
 
-// One workgroup, lane i of it: D[k T + t] = sqrt((k ? 2 : 1) / T) cos(pi (2t + 1) k / (2T)) in double, rounded to float32; the shift of
-// mode k, lam[p T + k] = wbar + tau (2 - 2 cos(pi k / T)) in double, rounded to float32, for each of the planes
-__global__ __launch_bounds__(WL) void k_volume_tables(int T, int planes, double wbar, double tau, float *__restrict__ D, double *__restrict__ lam)
+// One workgroup, lane i of it.  Free time: D[k T + t] = sqrt((k ? 2 : 1) / T) cos(pi (2t + 1) k / (2T)), mu_k = 2 - 2 cos(pi k / T);
+// periodic time: the Hartley table D[k T + t] = (cos + sin)(2 pi k t / T) / sqrt(T) -- symmetric, orthonormal, its own inverse, and it
+// diagonalises every symmetric circulant --, mu_k = 2 - 2 cos(2 pi k / T).  In double, rounded to float32; the shift of mode k,
+// lam[p T + k] = (wbar + tau mu_k) / sbar in double, rounded to float32, for each of the planes
+__global__ __launch_bounds__(WL) void k_volume_tables(int T, int planes, int periodic, double wbar, double tau, double sbar, float *__restrict__ D,
+                                                       double *__restrict__ lam)
 {
     for (int i = (int)threadIdx.x; i < T * T; i += WL) {
         const int k = i / T, t = i - k * T;
-        D[i] = (float)(sqrt((k ? 2.0 : 1.0) / (double)T) * cospi((double)((2 * t + 1) * k) / (2.0 * (double)T)));
+        if (periodic) {
+            const double a = 2.0 * (double)((k * t) % T) / (double)T;
+            D[i] = (float)((cospi(a) + sinpi(a)) / sqrt((double)T));
+        } else D[i] = (float)(sqrt((k ? 2.0 : 1.0) / (double)T) * cospi((double)((2 * t + 1) * k) / (2.0 * (double)T)));
     }
     for (int i = (int)threadIdx.x; i < planes * T; i += WL) {
         const int k = i % T;
-        lam[i] = (double)(float)(wbar + tau * (2.0 - 2.0 * cospi((double)k / (double)T)));
+        const double shift = wbar + tau * (2.0 - 2.0 * cospi((periodic ? 2.0 : 1.0) * (double)k / (double)T));
+        lam[i] = (double)(float)(shift / sbar);
     }
 }
 
@@ -243,36 +331,45 @@ __global__ __launch_bounds__(WL) void k_volume_out(PoissonGeo g, PcgGeo wg, Volu
     else j.out[o] = j.b[o];
 }
 
-template <class Fn> void for_volume_tables(const PoissonJobDev *jobs, const float *const *w, const float *const *st, const float *const *gt, int m, Fn fn)
+template <class Fn> void for_volume_tables(const PoissonJobDev *jobs, const VolumeArrays &a, int m, Fn fn)
 {
-    for_job_tables<VolumeJobs>(m, [&](VolumeJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.st[i] = st[k]; t.gt[i] = gt[k]; }, fn);
+    for_job_tables<VolumeJobs>(m, [&](VolumeJobs &t, int i, int k) {
+        t.j[i] = jobs[k]; t.w[i] = a.w[k]; t.st[i] = a.st[k]; t.gt[i] = a.gt[k]; t.sx[i] = a.sx[k]; t.sy[i] = a.sy[k]; t.smt[i] = a.smt[k]; }, fn);
+}
+
+template <bool LNK> void setup_form(bool lap, bool now, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg,
+                                    const VolumeJobs &t, float *R, float *E, float *S, float *F, float *Dg, double *b)
+{
+    if (lap && now) hipLaunchKernelGGL((k_volume_setup<true, true, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
+    else if (lap) hipLaunchKernelGGL((k_volume_setup<true, false, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
+    else if (now) hipLaunchKernelGGL((k_volume_setup<false, true, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
+    else hipLaunchKernelGGL((k_volume_setup<false, false, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
 }
 
 } // namespace
 
-void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *w,
-                         const float *const *st, int m, double *stats, hipStream_t s)
+void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+                         double *stats, hipStream_t s)
 {
-    const std::vector<const float *> none((size_t)m, nullptr);
-    for_volume_tables(jobs, w, st, none.data(), m, [&](const VolumeJobs &t, int i0, int cnt) {
-        hipLaunchKernelGGL(k_volume_stats, dim3((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, vg, t,
-                           stats + (size_t)g.C * i0 * PCG_PARTS * VOLUME_STATS);
+    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
+        const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
+        const bool general = t.sx[0] || t.smt[0] || vg.periodic;
+        double *st = stats + (size_t)g.C * i0 * PCG_PARTS * (general ? VOLUME_STATS : VOLUME_STATS_PLAIN);
+        if (general) hipLaunchKernelGGL(k_volume_stats<true>, grid, dim3(WL), 0, s, g, wg, vg, t, st);
+        else hipLaunchKernelGGL(k_volume_stats<false>, grid, dim3(WL), 0, s, g, wg, vg, t, st);
     });
 }
 
-void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const float *const *w,
-                         const float *const *st, const float *const *gt, int m, float *R, float *E, float *S, float *F, float *Dg, double *bb,
-                         hipStream_t s)
+void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+                         float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s)
 {
-    for_volume_tables(jobs, w, st, gt, m, [&](const VolumeJobs &t, int i0, int cnt) {
+    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;
         const bool now = !t.w[0];
-        if (lap && now) hipLaunchKernelGGL((k_volume_setup<true, true>), grid, dim3(WL), 0, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
-        else if (lap) hipLaunchKernelGGL((k_volume_setup<true, false>), grid, dim3(WL), 0, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
-        else if (now) hipLaunchKernelGGL((k_volume_setup<false, true>), grid, dim3(WL), 0, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
-        else hipLaunchKernelGGL((k_volume_setup<false, false>), grid, dim3(WL), 0, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
+        if (t.sx[0] || t.smt[0] || vg.periodic) setup_form<true>(lap, now, grid, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
+        else setup_form<false>(lap, now, grid, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, b);
     });
 }
 
@@ -280,13 +377,16 @@ void launch_volume_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool re
                       const float *Dg, float *Q, double *parts, hipStream_t s)
 {
     const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)planes);
-    if (residual) hipLaunchKernelGGL(k_volume_op<true>, grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
-    else hipLaunchKernelGGL(k_volume_op<false>, grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
+    if (vg.periodic) {
+        if (residual) hipLaunchKernelGGL((k_volume_op<true, true>), grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
+        else hipLaunchKernelGGL((k_volume_op<false, true>), grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
+    } else if (residual) hipLaunchKernelGGL((k_volume_op<true, false>), grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
+    else hipLaunchKernelGGL((k_volume_op<false, false>), grid, dim3(WL), 0, s, wg, vg, P, Q, parts, E, S, F, Dg);
 }
 
-void launch_volume_tables(int T, int planes, double wbar, double tau, float *D, double *lam, hipStream_t s)
+void launch_volume_tables(int T, int planes, bool periodic, double wbar, double tau, double sbar, float *D, double *lam, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_volume_tables, dim3(1), dim3(WL), 0, s, T, planes, wbar, tau, D, lam);
+    hipLaunchKernelGGL(k_volume_tables, dim3(1), dim3(WL), 0, s, T, planes, periodic ? 1 : 0, wbar, tau, sbar, D, lam);
 }
 
 void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool transposed, const float *D, const float *in, float *out, hipStream_t s)
@@ -300,7 +400,8 @@ void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &v
                        const float *U, hipStream_t s)
 {
     const std::vector<const float *> none((size_t)m, nullptr);
-    for_volume_tables(jobs, none.data(), st, none.data(), m, [&](const VolumeJobs &t, int i0, int cnt) {
+    const VolumeArrays a{ none.data(), st, none.data(), none.data(), none.data(), none.data() };
+    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_volume_out, dim3((unsigned)((g.W + WL - 1) / WL), (unsigned)g.H, (unsigned)(g.C * cnt * vg.T)), dim3(WL), 0, s, g, wg, vg, t,
                            U + (size_t)g.C * i0 * wg.stride);
     });

@@ -1,18 +1,23 @@
-// sc_volume_api.cpp -- the volume solve on float32 frame stacks (sc_hip_volume_check, sc_hip_volume_device, sc_hip_volume): the region
-// call's problem with unit spatial links on every one of `frames` images that share a layout, coupled by temporal links of the constant
-// weight tau (sc_volume.hip: the system and its work planes).  The entry code and the iteration are the shared ones (sc_pcg.h; the
-// front end with FLOAT_STATE | FLOAT_GT and the call's frame stride); VolumeOperator tells them
+// sc_volume_api.cpp -- the volume solves on float32 frame stacks (sc_hip_volume_check, sc_hip_volume_device, sc_hip_volume, and the
+// same three of sc_hip_volume_wls): the region call's problem on every one of `frames` images that share a layout, coupled by temporal
+// links (sc_volume.hip: the system and its work planes).  sc_hip_volume has unit spatial links, temporal links of the constant weight
+// tau and free ends of time; sc_hip_volume_wls takes per-link weights smooth_x, smooth_y, smooth_t and, if asked, periodic time.  One
+// operator serves both: sc_hip_volume is the call without link arrays under free time.  The entry code and the iteration are the
+// shared ones (sc_pcg.h; the front end with FLOAT_STATE | FLOAT_GT, FLOAT_SMOOTH and FLOAT_SMOOTH_T where the call has the arrays, the
+// call's frame stride and the frames its temporal arrays hold); VolumeOperator tells them
 //   chunks      frames * channels work planes count per volume against SC_POISSON_MAX_PLANES;
 //   geometry    one work plane per (volume, channel), its frames stacked along y: alpha, beta and the stop rule's norm are one per
 //               (volume, channel), summed over all its frames, with the shared launches unchanged;
-//   statistics  k_volume_stats; a volume with a state that is not 0, 1 or 2, an invalid weight where one is read, or -- without any
-//               Dirichlet line -- a channel with UNKNOWN pixels that no KNOWN neighbour in space or time and no weight pins anywhere in
-//               the volume gets SC_ERR_BAD_ARG and leaves;
-//   constants   w-bar = precond_lambda, or (sum of w + sum of the UNKNOWN - KNOWN links, spatial 1 and temporal tau) / (UNKNOWN pixels)
-//               over the chunk's remaining volumes;
+//   statistics  k_volume_stats; a volume with a state that is not 0, 1 or 2, an invalid weight or link where one is read, or -- without
+//               any Dirichlet line -- a channel with UNKNOWN pixels that no KNOWN neighbour in space or time and no weight pins anywhere
+//               in the volume gets SC_ERR_BAD_ARG and leaves;
+//   constants   over the chunk's remaining volumes: s-bar = precond_smooth, or the mean of the spatial links live in the region (1
+//               without link arrays); tau-bar = precond_tau, or the mean of the live temporal links (tau without smooth_t); w-bar =
+//               precond_lambda, or (sum of w + sum of the UNKNOWN - KNOWN links' weights) / (UNKNOWN pixels);
 //   set-up      k_volume_setup;   operator   k_volume_op;   output   k_volume_out;
-//   M^-1        k_volume_dct along the frames, one direct_jobs_solve over all frames * channels * volumes planes with the shift
-//               w-bar + tau (2 - 2 cos(pi k / frames)) of mode k, k_volume_dct transposed: exact for constant coefficients.
+//   M^-1        M = s-bar A - w-bar + tau-bar A_t: k_volume_dct along the frames (the DCT-II; periodic time: the Hartley table), one
+//               direct_jobs_solve over all frames * channels * volumes planes with the shift (w-bar + tau-bar mu_k) / s-bar of mode k,
+//               k_volume_dct transposed: exact for constant coefficients.  The factor 1 / s-bar goes once on u0 (scale_start).
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -23,14 +28,18 @@ using namespace sc;
 
 namespace {
 
-int volume_validate(const sc_volume_params *p, const sc_poisson_layout *l, const char **why)
+int volume_wls_validate(const sc_volume_wls_params *p, const sc_poisson_layout *l, const char **why)
 {
     const char *dummy;
     if (!why) why = &dummy;
     const char *own = !p ? nullptr : !std::isfinite(p->tol) ? "tol must be finite"
                     : !std::isfinite(p->precond_lambda) ? "precond_lambda must be finite"
+                    : !std::isfinite(p->precond_smooth) ? "precond_smooth must be finite"
+                    : !std::isfinite(p->precond_tau) ? "precond_tau must be finite"
                     : !(std::isfinite(p->tau) && p->tau > 0.f) ? "tau must be finite and > 0"
-                    : p->frames < 2 ? "a volume has at least 2 frames" : nullptr;
+                    : (p->time_periodic != 0 && p->time_periodic != 1) ? "time_periodic must be 0 or 1"
+                    : p->frames < 2 ? "a volume has at least 2 frames"
+                    : (p->time_periodic && p->frames < 3) ? "periodic time needs at least 3 frames" : nullptr;
     const int rc = family_validate(p ? &p->kind : nullptr, l, own,
                                    "a volume solve is preconditioned by a direct solve: at most 8192 unknowns (pixels - 2) per side", why);
     if (rc) return rc;
@@ -43,26 +52,51 @@ int volume_validate(const sc_volume_params *p, const sc_poisson_layout *l, const
     return SC_OK;
 }
 
+// sc_hip_volume's parameters as the general call's: no constants for link arrays, free time
+sc_volume_wls_params wls_params_of(const sc_volume_params *p)
+{
+    return sc_volume_wls_params{ p->kind, p->frames, p->frame_stride, p->tau, 0, p->tol, p->max_iters, p->precond_lambda, 0.f, 0.f };
+}
+
+int volume_validate(const sc_volume_params *p, const sc_poisson_layout *l, const char **why)
+{
+    if (!p) return volume_wls_validate(nullptr, l, why);
+    const sc_volume_wls_params q = wls_params_of(p);
+    return volume_wls_validate(&q, l, why);
+}
+
 constexpr const char *METHOD_WHY = "a volume solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
 constexpr const char *FP64_WHY = "a volume solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
 
-int carries_of(bool weight) { return FLOAT_DATA | FLOAT_STATE | FLOAT_GT | (weight ? FLOAT_WEIGHT : 0); }
+int carries_of(bool weight, bool links, bool tlinks)
+{
+    return FLOAT_DATA | FLOAT_STATE | FLOAT_GT | (weight ? FLOAT_WEIGHT : 0) | (links ? FLOAT_SMOOTH : 0) | (tlinks ? FLOAT_SMOOTH_T : 0);
+}
 
+// links, tlinks: the call's volumes carry smooth_x / smooth_y, smooth_t
 struct VolumeOperator : PcgOperator {
     Instance *const I;
     const int T;
     const long long fs;
-    const float tau, plam;
+    const float tau, plam, psmooth, ptau;
+    const bool periodic, links, tlinks;
     const float *const *all_w = nullptr, *const *all_st = nullptr, *const *all_gt = nullptr;
-    std::vector<const float *> dw, dst, dgt;      // the chunk's; behind judge: of the volumes that stay, in front
+    const float *const *all_sx = nullptr, *const *all_sy = nullptr, *const *all_smt = nullptr;
+    std::vector<const float *> dw, dst, dgt, dsx, dsy, dsmt;      // the chunk's; behind judge: of the volumes that stay, in front
     int kept = 0;
-    double wsum = 0.0, unknowns = 0.0, uksum = 0.0;      // of the volumes that stay
-    VolumeOperator(Instance *I_, const sc_volume_params *p)
-        : PcgOperator(VOLUME_STATS), I(I_), T(p->frames), fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda) {}
-    VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau }; }
-    void bind(const float *const *w, const float *const *, const float *const *) override { all_w = w; }
+    // of the volumes that stay: the sums of w and of the UNKNOWN - KNOWN links, the UNKNOWN pixels, the sum and the number of the spatial
+    // links live in the region and of the live temporal links
+    double wsum = 0.0, unknowns = 0.0, uksum = 0.0, ssum = 0.0, scount = 0.0, tsum = 0.0, tcount = 0.0;
+    float u0_scale = 1.f;                                          // 1 / s-bar
+    VolumeOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_)
+        : PcgOperator(links_ || tlinks_ || p->time_periodic ? VOLUME_STATS : VOLUME_STATS_PLAIN), I(I_), T(p->frames), fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda), psmooth(p->precond_smooth),
+          ptau(p->precond_tau), periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
+    VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau, periodic ? 1 : 0 }; }
+    VolumeArrays arrays() const { return VolumeArrays{ dw.data(), dst.data(), dgt.data(), dsx.data(), dsy.data(), dsmt.data() }; }
+    void bind(const float *const *w, const float *const *sx, const float *const *sy) override { all_w = w; all_sx = sx; all_sy = sy; }
     void bind_state(const float *const *st) override { all_st = st; }
     void bind_gt(const float *const *gt) override { all_gt = gt; }
+    void bind_smooth_t(const float *const *smt) override { all_smt = smt; }
     int chunk_planes(int C) const override { return C * T; }
     PcgGeo work_geo(const MixedGeo &mg) const override
     {
@@ -75,43 +109,66 @@ struct VolumeOperator : PcgOperator {
         dw.assign(all_w + i0, all_w + i0 + m);
         dst.assign(all_st + i0, all_st + i0 + m);
         dgt.assign(all_gt + i0, all_gt + i0 + m);
+        // (a call without link arrays: whatever the front end holds in their place is not looked at)
+        if (links) { dsx.assign(all_sx + i0, all_sx + i0 + m); dsy.assign(all_sy + i0, all_sy + i0 + m); }
+        else { dsx.assign((size_t)m, nullptr); dsy.assign((size_t)m, nullptr); }
+        if (tlinks) dsmt.assign(all_smt + i0, all_smt + i0 + m);
+        else dsmt.assign((size_t)m, nullptr);
         kept = 0;
-        wsum = unknowns = uksum = 0.0;
+        wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0;
     }
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {
-        launch_volume_stats(g, wg, geo(wg), dj.data(), dw.data(), dst.data(), m, d_stats, s);
+        launch_volume_stats(g, wg, geo(wg), dj.data(), arrays(), m, d_stats, s);
     }
     const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
     {
         double job[VOLUME_STATS] = {};
+        const int nf = nstat;      // (a call without link arrays under free time: the link fields do not exist)
         bool loose = false;
         for (int c = 0; c < g.C; ++c) {      // a plane is the channel's whole volume: the pin check is the volume's, not a frame's
-            const double *plane = st + (size_t)c * PCG_PARTS * VOLUME_STATS;
-            double f[VOLUME_STATS];
-            for (int i = 0; i < VOLUME_STATS; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
+            const double *plane = st + (size_t)c * PCG_PARTS * nstat;
+            double f[VOLUME_STATS] = {};
+            for (int i = 0; i < nf; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
             loose = loose || (no_dirichlet && f[2] > 0.0 && !(f[3] > 0.0) && !(f[0] > 0.0));
         }
         if (job[4] != 0.0) return "a state element is not 0, 1 or 2";
         if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
+        if (job[7] != 0.0 || !std::isfinite(job[5])) return "a spatial link weight live in the region is not finite or not > 0";
+        if (job[10] != 0.0 || !std::isfinite(job[8])) return "a live temporal link weight is not finite or not > 0";
         if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link in space or time and no data weight";
         dw[kept] = dw[k];
         dgt[kept] = dgt[k];
+        dsx[kept] = dsx[k];
+        dsy[kept] = dsy[k];
+        dsmt[kept] = dsmt[k];
         dst[kept++] = dst[k];
         wsum += job[0];
         unknowns += job[2];
         uksum += job[3];
+        ssum += job[5];
+        scount += job[6];
+        tsum += job[8];
+        tcount += job[9];
         return nullptr;
     }
-    // w-bar; the DCT table and the modes' shifts of this chunk go to the device here
+    // w-bar; the table along the frames and the modes' shifts of this chunk go to the device here
     float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
     {
+        const double sbar = psmooth > 0.f ? (double)psmooth : !links || !(scount > 0.0) ? 1.0 : ssum / scount;
+        const double tbar = ptau > 0.f ? (double)ptau : !tlinks || !(tcount > 0.0) ? (double)tau : tsum / tcount;
         // (a chunk without any UNKNOWN pixel: b = 0 on every plane, any regular M serves)
         const double wbar = plam > 0.f ? (double)plam : unknowns > 0.0 ? (wsum + uksum) / unknowns : 1.0;
         // without a Dirichlet line the rectangle's A is singular: judge kept only volumes whose every channel is pinned
         assert(!(mixed_zero_eig(wg.ax) && mixed_zero_eig(wg.ay)) || wbar > 0.0);
-        launch_volume_tables(T, g.C * mv, wbar, (double)tau, table(), shifts(), I->stream);
+        u0_scale = (float)(1.0 / sbar);
+        launch_volume_tables(T, g.C * mv, periodic, wbar, tbar, sbar, table(), shifts(), I->stream);
         return (float)wbar;
+    }
+    // the factor 1 / s-bar that the modes' solves leave out (1: no launch)
+    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override
+    {
+        if (u0_scale != 1.f) launch_pcg_scale(wg, planes, U, u0_scale, s);
     }
     // PcgState::tab: the shifts (double, planes * T of them at most SC_POISSON_MAX_PLANES) | the T x T table (float)
     double *shifts() const { return (double *)I->pcg->tab.p; }
@@ -123,8 +180,8 @@ struct VolumeOperator : PcgOperator {
         for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
             if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
         if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
-        launch_volume_setup(g, wg, geo(wg), lap, dj.data(), dw.data(), dst.data(), dgt.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p,
-                            (float *)S.dg.p, bb, I->stream);
+        launch_volume_setup(g, wg, geo(wg), lap, dj.data(), arrays(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, bb,
+                            I->stream);
         return SC_OK;
     }
     void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
@@ -159,7 +216,31 @@ struct VolumeOperator : PcgOperator {
     }
 };
 
-PcgCall volume_call(int kind, const sc_volume_params *p) { return PcgCall{ kind, p->tol, p->max_iters, 400, p->frames, p->frame_stride }; }
+PcgCall volume_call(int kind, const sc_volume_wls_params *p)
+{
+    return PcgCall{ kind, p->tol, p->max_iters, 400, p->frames, p->frame_stride, p->time_periodic ? p->frames : p->frames - 1 };
+}
+
+// the device call of both families, on either's jobs (links_of(job): its three link arrays, NULLs for sc_hip_volume's); the data term
+// and the link arrays: all volumes or none, as the first one has them -- smooth_x / smooth_y and smooth_t judged separately; a volume
+// that differs is refused with a reason of its own (as one with exactly one of smooth_x / smooth_y is by the front end)
+struct VolumeLinks { const float *sx, *sy, *smt; };
+template <class Job, class LinksOf>
+int volume_device_call(Instance *I, int kind, const sc_volume_wls_params *p, const sc_poisson_layout *l, Job *jobs, int n, bool bSync, LinksOf links_of)
+{
+    const VolumeLinks first = jobs && n > 0 ? links_of(jobs[0]) : VolumeLinks{ nullptr, nullptr, nullptr };
+    const bool weight = jobs && n > 0 && jobs[0].weight, links = first.sx || first.sy, tlinks = first.smt != nullptr;
+    VolumeOperator op(I, p, links, tlinks);
+    return pcg_device_call(I, volume_call(kind, p), l, carries_of(weight, links, tlinks), jobs, n, [=](const Job &j) {
+        const VolumeLinks k = links_of(j);
+        FloatArrays a{ j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, k.sx, k.sy, j.state };
+        a.gt = j.gt;
+        a.smooth_t = k.smt;
+        a.refuse = !weight && j.weight ? "a volume has a weight where the first volume of the call has none"
+                 : !links && (k.sx || k.sy) ? "a volume has smooth_x / smooth_y where the first volume of the call has none"
+                 : !tlinks && k.smt ? "a volume has smooth_t where the first volume of the call has none" : nullptr;
+        return a; }, op, bSync);
+}
 
 } // namespace
 
@@ -175,14 +256,8 @@ int sc_hip_volume_device(void *inst, const sc_volume_params *p, const sc_poisson
     Instance *I;
     int kind, rc = pcg_begin(inst, p, l, volume_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
-    // the data term: all volumes or none, as the first one has it; a volume that differs is refused
-    const bool weight = jobs && n > 0 && jobs[0].weight;
-    VolumeOperator op(I, p);
-    return pcg_device_call(I, volume_call(kind, p), l, carries_of(weight), jobs, n, [weight](const sc_volume_job &j) {
-        const bool stray = !weight && j.weight;      // (refused through its data pointer)
-        FloatArrays a{ j.gx, j.gy, j.lap, stray ? nullptr : j.data, j.weight, j.boundary, j.out, nullptr, nullptr, j.state };
-        a.gt = j.gt;
-        return a; }, op, bSync);
+    const sc_volume_wls_params q = wls_params_of(p);
+    return volume_device_call(I, kind, &q, l, jobs, n, bSync, [](const sc_volume_job &) { return VolumeLinks{ nullptr, nullptr, nullptr }; });
 }
 
 int sc_hip_volume(void *inst, const sc_volume_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
@@ -191,10 +266,40 @@ int sc_hip_volume(void *inst, const sc_volume_params *p, const sc_poisson_layout
     Instance *I;
     int kind, rc = pcg_begin(inst, p, l, volume_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
-    VolumeOperator op(I, p);
+    const sc_volume_wls_params q = wls_params_of(p);
+    VolumeOperator op(I, &q, false, false);
     FloatArrays a{ gx, gy, lap, data, weight, boundary, out, nullptr, nullptr, state };
     a.gt = gt;
-    return pcg_host_call(I, volume_call(kind, p), l, carries_of(weight != nullptr), a, op);
+    return pcg_host_call(I, volume_call(kind, &q), l, carries_of(weight != nullptr, false, false), a, op);
+}
+
+int sc_hip_volume_wls_check(const sc_volume_wls_params *p, const sc_poisson_layout *l)
+{
+    return volume_wls_validate(p, l, nullptr);
+}
+
+int sc_hip_volume_wls_device(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_wls_job *jobs, int n, bool bSync)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_wls_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    return volume_device_call(I, kind, p, l, jobs, n, bSync, [](const sc_volume_wls_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t }; });
+}
+
+int sc_hip_volume_wls(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
+                      const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                      const float *smooth_t, const float *boundary, float *out)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_wls_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial link 1)"; return SC_ERR_BAD_ARG; }
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    VolumeOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, lap, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    return pcg_host_call(I, volume_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op);
 }
 
 } // extern "C"

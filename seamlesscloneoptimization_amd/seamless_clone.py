@@ -905,3 +905,104 @@ def make_tileable(image, lam=0.0, axes="xy", gpu_id=0, **solver):
         return screened_solve(image, gx=gx, gy=gy, lam=lam, periodic=axes, gpu_id=gpu_id, **solver)
     _, free_sides = _screened_borders(False, None, axes)
     return poisson_solve(image, gx=gx, gy=gy, periodic=axes, free_sides=free_sides, gpu_id=gpu_id, **solver)
+
+
+def volume_wls_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None,
+                     tau=1.0, loop=False, neumann=True, free_sides=None, periodic="", tol=None, max_iters=None, gpu_id=0, **solver):
+    """volume_solve with a weight on every link: per channel it minimises sum_t [sum w (u_t - d_t)^2 + sum smooth_x (d_x u_t - gx_t)^2 +
+    sum smooth_y (d_y u_t - gy_t)^2] + sum_t sum tau smooth_t (u_{t+1} - u_t - gt_t)^2.  smooth_x, smooth_y (together; None: 1): T x H x
+    W (x C), each at its link's low end as in region_solve.  smooth_t (None: 1) and gt: element [t] belongs to the link from frame t to
+    frame t + 1, T - 1 frames.  loop: time is periodic -- frame T - 1 is linked to frame 0 (T >= 3), and smooth_t and gt hold T frames,
+    the last one that link's.  Links must be finite and > 0 where they are live.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    _, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary = capi.volume_wls_arrays(
+        data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau, bool(loop), neumann=neumann, free_sides=free_sides,
+        periodic=periodic)
+    with _instance(gpu_id, solver) as inst:
+        return inst.volume_wls(data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau=tau, loop=bool(loop),
+                               neumann=neumann, free_sides=free_sides, periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0)
+
+
+def _video_of(name, a):
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+        raise TypeError(f"{name} must be a float32 numpy array")
+    if a.ndim not in (3, 4):
+        raise ValueError(f"{name} are T x H x W or T x H x W x C")
+    return a
+
+
+def _video_abs_differences(g, loop):
+    """(|d/dx|, |d/dy|, |d/dt|) of a T x H x W (x C) array in float64, T x H x W each (d/dt: T - 1 frames, with loop T: the last one from
+    frame T - 1 to frame 0); over the channels the root of the summed squares; where there is no forward neighbour, 0"""
+    g = np.asarray(g, np.float64)
+    g = g[:, :, :, None] if g.ndim == 3 else g
+    per = [_forward_abs_differences(f) for f in g]
+    nxt = np.roll(g, -1, 0) if loop else g[1:]
+    return np.stack([p[0] for p in per]), np.stack([p[1] for p in per]), np.sqrt(((nxt - g[:nxt.shape[0]]) ** 2).sum(3))
+
+
+def wls_filter_video(frames, lam=1.0, alpha=1.2, eps=1e-4, tau=1.0, guide=None, loop=False, gpu_id=0, **solver):
+    """wls_filter on a float32 video (T x H x W or T x H x W x C) with the same links along time: the video u that minimises
+    sum (u - frames)^2 + sum s |grad u|^2 + tau sum s_t (u_{t+1} - u_t)^2, every link lam / (|forward difference of l|^alpha + eps) in x,
+    y and t, l = log(luminance + 1e-6) of the frames, or of `guide` -- the temporal link from the difference between consecutive frames'
+    l.  Smooth where the video is flat in space and steady in time, free to jump at edges, cuts and moving edges: the base layer does
+    not flicker.  loop: the last frame is joined to the first.  Returns a NEW array."""
+    frames = _video_of("frames", frames)
+    if not (np.isfinite(lam) and lam > 0 and np.isfinite(alpha) and alpha >= 0 and np.isfinite(eps) and eps > 0):
+        raise ValueError("lam and eps must be finite and > 0, alpha finite and >= 0")
+    g = np.asarray(frames if guide is None else guide, np.float64)
+    if g.shape[:3] != frames.shape[:3]:
+        raise ValueError(f"guide has shape {g.shape[:3]}, the frames {frames.shape[:3]}")
+    lum = np.log(np.maximum(g if g.ndim == 3 else g.mean(3), 0.0) + 1e-6)
+    sx, sy, st = ((lam / (d ** alpha + eps)).astype(np.float32) for d in _video_abs_differences(lum, loop))
+    return volume_wls_solve(frames, np.zeros(frames.shape[:3], np.uint8), weight=np.ones(frames.shape[:3], np.float32), smooth_x=sx, smooth_y=sy,
+                            smooth_t=st, tau=tau, loop=loop, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, tau=1.0, hard=True, loop=False, strength=1.0, gpu_id=0, **solver):
+    """interpolate_constraints with a guide on a float32 video (T x H x W or T x H x W x C): the values at the pixels where known_mask
+    (T x H x W) is set spread through space and time and stop at the guide's edges in both -- every link exp(-d^2 / (2 edge_sigma^2)) +
+    1e-3, d the guide's forward difference in x, y or t (edge_sigma None: a tenth of the guide's range).  Scribble, colour or depth
+    propagation from a few frames or a few pixels.  hard: the known pixels hold exactly; else they carry the weight `strength`.
+    loop: the last frame is joined to the first.  Returns a NEW array."""
+    values = _video_of("values", values)
+    m = _video_masks("known_mask", known_mask, values)
+    if guide is None:
+        raise ValueError("interpolate_constraints_video needs a guide")
+    g = np.asarray(guide, np.float64)
+    if g.shape[:3] != values.shape[:3]:
+        raise ValueError(f"guide has shape {g.shape[:3]}, the frames {values.shape[:3]}")
+    if not np.isfinite(strength) or not strength > 0:
+        raise ValueError("strength must be finite and > 0")
+    sigma = 0.1 * float(g.max() - g.min()) if edge_sigma is None else float(edge_sigma)
+    if not np.isfinite(sigma) or not sigma > 0:
+        raise ValueError("edge_sigma must be finite and > 0 (None: a tenth of the guide's range, which must not be flat)")
+    if not m.any():
+        raise ValueError("known_mask is empty: nothing to spread")
+    sx, sy, st = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in _video_abs_differences(g, loop))
+    if hard:
+        state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
+        return volume_wls_solve(values, state, smooth_x=sx, smooth_y=sy, smooth_t=st, tau=tau, loop=loop, neumann=True, gpu_id=gpu_id, **solver)
+    d = np.where(m.reshape(m.shape + (1,) * (values.ndim - 3)), values, np.float32(0)).astype(np.float32)
+    w = np.where(m, np.float32(strength), np.float32(0)).astype(np.float32)
+    return volume_wls_solve(d, np.zeros(m.shape, np.uint8), weight=w, smooth_x=sx, smooth_y=sy, smooth_t=st, tau=tau, loop=loop, neumann=True,
+                            gpu_id=gpu_id, **solver)
+
+
+def make_loop(frames, lam=1e-2, tau=1.0, gpu_id=0, **solver):
+    """A copy of a float32 clip (T x H x W or T x H x W x C, T >= 3) that loops without a seam: make_tileable along time.  The clip
+    whose forward differences in x, y and t are the input's, except from the last frame to the first, where the wanted difference is 0
+    -- the jump at the seam is spread over all frames.  Time is periodic, the frames' borders reflect; the result stays close to the
+    input with weight lam, which also pins the solve: lam must be finite and > 0.  Only lam holds the clip's mean level: in float32 it is
+    held to about 1e-7 / lam of the values' size (1e-5 at the default).  Returns a NEW array."""
+    frames = _video_of("frames", frames)
+    if frames.shape[0] < 3:
+        raise ValueError("a loop has at least 3 frames")
+    if lam is None or not np.isfinite(lam) or not lam > 0:
+        raise ValueError("lam must be finite and > 0: the weight pins the solve")
+    gx, gy, gt = np.zeros_like(frames), np.zeros_like(frames), np.zeros_like(frames)
+    for t in range(frames.shape[0]):
+        gx[t], gy[t] = _forward_differences(frames[t])
+    gt[:-1] = frames[1:] - frames[:-1]          # (the wrapping link's stays 0)
+    return volume_wls_solve(frames, np.zeros(frames.shape[:3], np.uint8), gx=gx, gy=gy, gt=gt, weight=np.full(frames.shape[:3], lam, np.float32),
+                            tau=tau, loop=True, neumann=True, gpu_id=gpu_id, **solver)

@@ -1,0 +1,518 @@
+"""GPU tests of the WLS volume solve (sc_hip_volume_wls, sc_hip_volume_wls_device) through capi: volume solves with per-link weights in
+space and time and, if asked, periodic time.
+
+1. against the float64 solve (tests/volume_wls_np.py) on tests/volume_wls_bounds.py's matrix through the host call: 33 x 47, 300 x 9,
+   2 x 7 and 16 x 5 pixels, 2 / 3 / 5 / 8 frames, 1 and 3 channels, tau 0.1 / 1 / 10, five border kinds, five state patterns, weights
+   none / constant / sparse, the three forms of the right-hand side, links none / xy / t / xyt log-uniform over two decades, free and
+   periodic time: ERR and RES within the bounds, the iteration count within twice the reference iteration's plus the polling period,
+   out's bits at KNOWN and OUTSIDE pixels data's and on the Dirichlet lines boundary's.
+2. ties: no link arrays under free time give the bytes of sc_hip_volume, arrays of 1.0f the bytes of no arrays; constant links with a
+   constant weight and every state 0 converge within SC_WEIGHTED_POLL sweeps; identical frames under periodic time give the
+   single-frame sc_hip_region answer; two runs of one call give the same bytes.
+3. periodic time: the answer of an input rolled along the frames is the rolled answer.
+4. the device call: HWC and CHW with padded rows, a frame stride that leaves a gap, guard frames around every array (gt and smooth_t at
+   `frames` frames), NaN in every element the header says is not read: nothing but the named elements of out is written, out may be data.
+5. batches: two volumes beside a third with a bad live link (SC_ERR_BAD_ARG, its out untouched), the same values at dead links, a
+   volume with link arrays where the first has none, nine 3-channel volumes of 8 frames in two chunks.
+6. wls_filter_video, interpolate_constraints_video, make_loop and volume_wls_solve against the float64 solve."""
+from __future__ import annotations
+
+import functools
+
+import numpy as np
+import pytest
+
+from seamlesscloneoptimization_amd import capi, seamless_clone
+
+import volume_wls_bounds as wb
+import volume_wls_np as vw
+
+pytestmark = pytest.mark.gpu
+
+L, G = capi.SC_POISSON_LAPLACIAN, capi.SC_POISSON_GUIDANCE
+SENTINEL = -7.25
+POLL = capi.SC_WEIGHTED_POLL
+
+
+@pytest.fixture(scope="module")
+def inst():
+    i = capi.Instance(0)
+    yield i
+    i.destroy()
+
+
+def boundary_of(p):
+    return p["boundary"] if vw.has_dirichlet(p["sides"], p["periodic"]) else None
+
+
+def solve(inst, p, form="lap", **kw):
+    return inst.volume_wls(p["data"], p["state"], p["weight"], boundary=boundary_of(p), tau=p["tau"], free_sides=p["sides"], periodic=p["periodic"],
+                           **wb.call_args(p, form), **kw)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def assert_copied_bits(p, out):
+    """out at KNOWN and OUTSIDE pixels is data, on the Dirichlet lines boundary, bit for bit"""
+    k = vw.kinds(p["sides"], p["periodic"], p["state"])
+    out = out.reshape(k.shape)
+    held = (k == vw.KNOWN) | (k == vw.OUTSIDE)
+    assert np.array_equal(bits(out)[held], bits(p["data"].reshape(k.shape))[held]), "KNOWN and OUTSIDE pixels must be data's bits"
+    line = k == vw.DIRICHLET
+    assert np.array_equal(bits(out)[line], bits(p["boundary"].reshape(k.shape))[line]), "Dirichlet lines must be boundary's bits"
+    assert np.isfinite(out[k == vw.UNKNOWN]).all(), "an unread element's NaN reached the answer"
+
+
+def rel_err(p, got, want):
+    unk = vw.kinds(p["sides"], p["periodic"], p["state"]) == vw.UNKNOWN
+    w = np.asarray(want, np.float64).reshape(unk.shape)
+    return float(np.abs(np.asarray(got, np.float64).reshape(unk.shape) - w)[unk].max()) / float(np.abs(w[unk]).max())
+
+
+def assert_yardstick(tag, p, form, out, y=None):
+    """out lies within the yardstick's ERR and RES bounds for this input"""
+    y = y or wb.Yardstick(p, form)
+    bad, err, res = y.check(out)
+    print(f"VOLUME_WLS {tag}: ERR {err:.3g} (pcg_f32 {y.err32:.3g}) RES {res:.3g} (pcg_f32 {y.res32:.3g})")
+    assert not bad, bad
+
+
+# ---- 1. against the exact solve ------------------------------------------------------------------------------------------------
+_CASES = wb.matrix()
+_IDS = [f"{b}-{W}x{H}x{C}x{T}-tau{tau:g}-{p}-{wk}-{f}-{ln}-{tm}" for b, H, W, C, T, tau, p, wk, f, ln, tm in _CASES]
+
+
+@pytest.mark.parametrize("i", range(len(_CASES)), ids=_IDS)
+def test_against_the_exact_solve(inst, i):
+    H, W = _CASES[i][1:3]
+    p, form, y = wb.matrix_case(i)
+    assert y.rel32 <= 1e-5 and y.iters32 < wb.MAX_ITERS, "the reference iteration must converge on every input"
+    out = solve(inst, p, form)
+    info = inst.info()
+    bad, err, res = y.check(out)
+    print(f"VOLUME_WLS {_IDS[i]}: ERR {err:.3g} (pcg_f32 {y.err32:.3g}) RES {res:.3g} (pcg_f32 {y.res32:.3g}) sweeps {info.sweeps} "
+          f"(pcg_f32 {y.iters32}) rel {info.rel_residual:.3g}")
+    assert (info.method, info.converged, info.W, info.H) == (capi.SC_METHOD_FFT, 1, W, H)
+    assert info.sweeps <= y.max_sweeps(), (info.sweeps, y.iters32)
+    assert not bad, bad
+    assert_copied_bits(p, out)
+
+
+# ---- 2. ties ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", wb.FORMS)
+@pytest.mark.parametrize("case", [("neumann", 47, 33, 3, 5, "scatter", "sparse"), ("free_lt", 9, 300, 1, 3, "hole", None),
+                                  ("periodic_x", 7, 2, 3, 8, "keyframes", "constant")], ids=lambda c: f"{c[0]}-{c[2]}x{c[1]}x{c[4]}")
+def test_no_link_arrays_under_free_time_give_the_bytes_of_the_volume_call(inst, case, form):
+    border, H, W, C, T, pattern, wk = case
+    p = wb.nan_unread(wb.make_input(border, H, W, C, T, 0.7, pattern, wk))
+    a = wb.vb.call_args(p, form)
+    want = inst.volume(p["data"], p["state"], p["weight"], boundary=boundary_of(p), tau=p["tau"], free_sides=p["sides"], periodic=p["periodic"], **a)
+    sweeps = inst.info().sweeps
+    got = solve(inst, p, form)
+    assert got.tobytes() == want.tobytes() and inst.info().sweeps == sweeps
+
+
+@pytest.mark.parametrize("time", wb.TIMES)
+@pytest.mark.parametrize("form", wb.FORMS)
+def test_arrays_of_ones_give_the_bytes_of_no_arrays(inst, form, time):
+    p = wb.nan_unread(wb.make_input("free_lt", 23, 17, 3, 4, 1.7, "scatter", "sparse", "none", time, seed=4))
+    want = solve(inst, p, form)
+    sweeps = inst.info().sweeps
+    lx, ly, lt = vw.live_links(p["sides"], p["periodic"], p["tper"], p["state"])
+    nan = np.float32(np.nan)
+    ones = dict(p, sx=np.where(lx, np.float32(1), nan), sy=np.where(ly, np.float32(1), nan), smt=np.where(lt, np.float32(1), nan))
+    got = solve(inst, ones, form)
+    assert got.tobytes() == want.tobytes() and inst.info().sweeps == sweeps
+    # ... and each kind of link array on its own
+    for part in (dict(p, sx=ones["sx"], sy=ones["sy"]), dict(p, smt=ones["smt"])):
+        assert solve(inst, part, form).tobytes() == want.tobytes()
+
+
+# (a frame around 2 x 7 pixels leaves no unknown: that one combination does not exist)
+_CONSTANT = [(b[0], shape) for b in wb.BORDERS for shape in [(47, 33, 5), (9, 300, 3), (7, 2, 8)] if not (b[0] == "frame" and min(shape[:2]) < 3)]
+
+
+@pytest.mark.parametrize("time", wb.TIMES)
+@pytest.mark.parametrize("form", wb.FORMS)
+@pytest.mark.parametrize("border,shape", _CONSTANT, ids=[f"{b}-{s[1]}x{s[0]}x{s[2]}" for b, s in _CONSTANT])
+def test_constant_links_need_no_iteration(inst, border, shape, form, time):
+    """every state 0, a constant weight and constant links sx = sy = a, smooth_t = b: M is the operator itself, so u0 = M^-1 b / s-bar is
+    the answer and the stop rule sees it with the first norms it reads, SC_WEIGHTED_POLL iterations in"""
+    H, W, T = shape
+    p = wb.make_input(border, H, W, 3, T, wb.TAUS[(H + T) % 3], "all", "constant", "none", time)
+    p["state"] = np.zeros_like(p["state"])
+    p["sx"] = p["sy"] = np.full(p["data"].shape, 2.5, np.float32)
+    p["smt"] = np.full(p["gt"].shape, 0.4, np.float32)
+    solve(inst, p, form)
+    info = inst.info()
+    print(f"VOLUME_WLS constant {border} {W}x{H}x{T} {form} {time}: sweeps {info.sweeps} rel {info.rel_residual:.3g}")
+    assert info.converged == 1 and info.sweeps <= POLL, info.sweeps
+
+
+@pytest.mark.parametrize("wk", [None, "sparse"])
+@pytest.mark.parametrize("border", ["neumann", "frame", "periodic_x"])
+def test_identical_frames_under_periodic_time_give_the_region_answer(inst, border, wk):
+    """the same frame T times with the same spatial links, no gt, time periodic: no temporal link carries anything, whatever it weighs,
+    and every frame solves the region call's problem"""
+    T, H, W, C = 5, 23, 17, 3
+    p = wb.make_input(border, H, W, C, T, 1.0, "scatter", wk, "xyt", "periodic", seed=2)
+    for name in ("state", "data", "weight", "lap", "gx", "gy", "boundary", "sx", "sy"):
+        if p[name] is not None:
+            p[name] = np.ascontiguousarray(np.broadcast_to(p[name][0], p[name].shape))
+    y = wb.Yardstick(p, "guidance")
+    out = solve(inst, p, "guidance")
+    flat = inst.region(p["data"][0], p["state"][0], None if wk is None else p["weight"][0], p["sx"][0], p["sy"][0], gx=p["gx"][0], gy=p["gy"][0],
+                       boundary=None if boundary_of(p) is None else p["boundary"][0], free_sides=p["sides"], periodic=p["periodic"])
+    err = rel_err(p, out, np.broadcast_to(flat, out.shape))
+    print(f"VOLUME_WLS identical frames {border} {wk}: distance to sc_hip_region {err:.3g}, ERR bound {y.bounds()[0]:.3g} (pcg_f32 {y.err32:.3g})")
+    assert err <= y.bounds()[0], (err, y.bounds()[0])
+
+
+@pytest.mark.parametrize("time", wb.TIMES)
+def test_two_runs_give_the_same_bytes(inst, time):
+    p = wb.nan_unread(wb.make_input("periodic_x", 47, 33, 3, 5, 1.0, "scatter", "sparse", "xyt", time))
+    a, b = solve(inst, p, "gt"), solve(inst, p, "gt")
+    assert a.tobytes() == b.tobytes()
+
+
+# ---- 3. periodic time ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [3, 8])
+def test_rolling_the_frames_rolls_the_answer(inst, T):
+    """under periodic time no frame is the first: every array rolled by r frames gives the answer rolled by r frames, to the stop rule's
+    error on either side -- twice the ERR bound"""
+    p = wb.make_input("neumann", 23, 17, 3, T, 1.0, "scatter", "sparse", "xyt", "periodic", seed=5)
+    y = wb.Yardstick(p, "gt")
+    out = solve(inst, p, "gt")
+    assert_yardstick(f"roll base T={T}", p, "gt", out, y)
+    for r in (1, T - 1):
+        q = {n: (np.ascontiguousarray(np.roll(a, r, 0)) if isinstance(a, np.ndarray) else a) for n, a in p.items()}
+        got = solve(inst, q, "gt")
+        err = rel_err(q, got, np.roll(out, r, 0))
+        print(f"VOLUME_WLS roll T={T} by {r}: {err:.3g}, twice the ERR bound {2 * y.bounds()[0]:.3g}")
+        assert err <= 2 * y.bounds()[0], (r, err)
+
+
+# ---- 4. the device call -------------------------------------------------------------------------------------------------------------
+def _layout_views(name, T, H, W, fill):
+    """(backing array filled with `fill`, its T x H x W x 3 view): a guard frame before and after, a gap between the frames"""
+    if name == "hwc":
+        back = np.full((T + 2, H + 2, W, 3), fill, np.float32)          # two rows between the frames
+        return back, back[1:-1, :H]
+    back = np.full((T + 2, 3, H + 1, W + 5), fill, np.float32)          # CHW, padded rows, a row between the planes
+    return back, back[1:-1, :, :H, :W].transpose(0, 2, 3, 1)
+
+
+_FIELDS = ("data", "state", "weight", "gx", "gy", "gt", "boundary", "smooth_x", "smooth_y", "smooth_t")
+_NAMES = dict(smooth_x="sx", smooth_y="sy", smooth_t="smt")
+
+
+@pytest.mark.parametrize("alias", ["none", "data"])
+@pytest.mark.parametrize("layout", ["hwc", "chw_padded"])
+def test_device_layouts_write_only_named_elements(inst, layout, alias):
+    T, H, W = 4, 23, 17
+    p = wb.nan_unread(wb.make_input("free_lt", H, W, 3, T, 1.3, "scatter", "sparse", "xyt", "periodic", seed=3))          # Dirichlet lines right and bottom
+    arrays = {}
+    for name in _FIELDS + ("out",):
+        back, view = _layout_views(layout, T, H, W, np.nan if name in ("gx", "gy", "gt", "smooth_x", "smooth_y", "smooth_t") else SENTINEL)
+        if name != "out":
+            view[...] = p[_NAMES.get(name, name)]          # (gt and smooth_t: T frames under periodic time)
+        arrays[name] = (back, view)
+    lay = capi.poisson_layout_of(arrays["data"][1][0])
+    stride = arrays["data"][1].strides[0] // 4
+    assert stride > (H - 1) * lay.row_stride + (W - 1) * lay.col_stride + 2 * lay.channel_stride + 1, "the frames leave a gap"
+    off = lambda name: arrays[name][1].__array_interface__["data"][0] - arrays[name][0].__array_interface__["data"][0]
+    dev = {name: inst.to_device(back) for name, (back, _) in arrays.items()}
+    try:
+        jobs = capi.Instance.make_volume_wls_jobs(1)
+        j = jobs[0]
+        for name in _FIELDS:
+            setattr(j, name, dev[name] + off(name))
+        target = "out" if alias == "none" else alias
+        j.out = dev[target] + off(target)
+        kind = G | capi.border_bits(p["sides"], False, p["periodic"])
+        rc = inst.volume_wls_device(capi.VolumeWlsParams(kind, T, stride, 1.3, 1, 0.0, 0, 0.0, 0.0, 0.0), lay, jobs)
+        assert rc == capi.SC_OK and j.rc == capi.SC_OK
+        got_back = inst.from_device(dev[target], arrays[target][0].shape, np.float32)
+        others = {n: inst.from_device(dev[n], arrays[n][0].shape, np.float32) for n in arrays if n != target}
+    finally:
+        for q in dev.values():
+            inst.free(q)
+    for n, a in others.items():
+        assert np.array_equal(a, arrays[n][0], equal_nan=True), f"{n} was written"
+    # the named elements of the target hold the answer; its guard frames, its padding and the gaps between its frames are as they were
+    view_of = lambda back: back[1:-1, :H] if layout == "hwc" else back[1:-1, :, :H, :W].transpose(0, 2, 3, 1)
+    probe = arrays[target][0].copy()
+    got = view_of(got_back).copy()
+    view_of(probe)[...] = got
+    assert np.array_equal(probe, got_back, equal_nan=True), "a guard frame, the padding or a gap between frames was written"
+    assert_copied_bits(p, got)
+    assert_yardstick(f"device {layout} out={alias}", p, "gt", got)
+
+
+# ---- 5. batches ---------------------------------------------------------------------------------------------------------------------
+def _device_jobs(inst, probs, form="lap"):
+    """VolumeWlsJob array of the inputs on dense device arrays, each with an out full of SENTINEL; (jobs, pointers to free)"""
+    jobs = capi.Instance.make_volume_wls_jobs(len(probs))
+    dev = []
+    for k, p in enumerate(probs):
+        fields = dict(wb.vb.call_args(p, form), data=p["data"], state=p["state"], weight=p["weight"], boundary=boundary_of(p), smooth_x=p["sx"],
+                      smooth_y=p["sy"], smooth_t=p["smt"])
+        for name, a in fields.items():
+            if a is not None:
+                dev.append(inst.to_device(np.ascontiguousarray(a, np.float32)))
+                setattr(jobs[k], name, dev[-1])
+        dev.append(inst.to_device(np.full(p["data"].shape, SENTINEL, np.float32)))
+        jobs[k].out = dev[-1]
+    return jobs, dev
+
+
+def _run_batch(inst, probs, form="lap"):
+    p0 = probs[0]
+    T, H, W, C = p0["data"].shape
+    jobs, dev = _device_jobs(inst, probs, form)
+    try:
+        kind = (L if form == "lap" else G) | capi.border_bits(p0["sides"], False, p0["periodic"])
+        params = capi.VolumeWlsParams(kind, T, H * W * C, p0["tau"], 1 if p0["tper"] else 0, 0.0, 0, 0.0, 0.0, 0.0)
+        rc = inst.volume_wls_device(params, capi.poisson_layout_of(p0["data"][0]), jobs, allow_job_errors=True)
+        codes = [j.rc for j in jobs]
+        outs = [inst.from_device(j.out, p0["data"].shape, np.float32) for j in jobs]
+    finally:
+        for q in dev:
+            inst.free(q)
+    return rc, codes, outs
+
+
+def _check_members(probs, outs, chunks, form, yardsticks=None):
+    for members in chunks:
+        means = wb.chunk_means([probs[k] for k in members])
+        for k in members:
+            y = yardsticks[k] if yardsticks else wb.Yardstick(probs[k], form, means=means)
+            bad, err, res = y.check(outs[k])
+            print(f"VOLUME_WLS batch member {k}: ERR {err:.3g} (pcg_f32 {y.err32:.3g}) RES {res:.3g} (pcg_f32 {y.res32:.3g})")
+            assert not bad, (k, bad)
+            assert_copied_bits(probs[k], outs[k])
+
+
+@functools.lru_cache(maxsize=None)
+def _trio():
+    """three volumes with all link arrays under periodic time, and the first two's yardsticks with the means of a chunk of those two"""
+    probs = [wb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", "xyt", "periodic", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
+    means = wb.chunk_means(probs[:2])
+    return probs, [wb.Yardstick(p, "gt", means=means) for p in probs[:2]]
+
+
+def _link_element(p, name, live):
+    """the index of a live (or dead) element of a link array of the third volume, away from the array's ends"""
+    lx, _, lt = vw.live_links(p["sides"], p["periodic"], p["tper"], p["state"])
+    where = np.argwhere((lx if name == "sx" else lt) == live)
+    return tuple(where[len(where) // 2])
+
+
+@pytest.mark.parametrize("bad", [0.0, -1.0, float("nan"), float("inf")], ids=["zero", "negative", "nan", "inf"])
+@pytest.mark.parametrize("name", ["sx", "smt"])
+def test_a_bad_live_link_fails_its_volume_only(inst, name, bad):
+    probs, yardsticks = _trio()
+    third = dict(probs[2], **{name: probs[2][name].copy()})
+    third[name][_link_element(third, name, True)] = bad
+    rc, codes, outs = _run_batch(inst, [probs[0], probs[1], third], "gt")
+    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_OK, capi.SC_OK, capi.SC_ERR_BAD_ARG], (rc, codes)
+    assert (outs[2] == SENTINEL).all(), "a refused volume must not be written"
+    _check_members(probs, outs, [[0, 1]], "gt", yardsticks)
+
+
+def test_bad_values_at_dead_links_are_accepted(inst):
+    probs, _ = _trio()
+    third = dict(probs[2], sx=probs[2]["sx"].copy(), smt=probs[2]["smt"].copy())
+    for name in ("sx", "smt"):
+        dead = np.argwhere((vw.live_links(third["sides"], third["periodic"], third["tper"], third["state"])[0 if name == "sx" else 2]) == False)  # noqa: E712
+        assert len(dead) >= 4
+        for i, bad in enumerate((0.0, -1.0, np.nan, np.inf)):
+            third[name][tuple(dead[(i * len(dead)) // 4])] = bad
+    rc, codes, outs = _run_batch(inst, [probs[0], probs[1], third], "gt")
+    assert rc == capi.SC_OK and codes == [capi.SC_OK] * 3, (rc, codes)
+    _check_members([probs[0], probs[1], third], outs, [[0, 1, 2]], "gt")
+
+
+@pytest.mark.parametrize("extra", ["xy", "t", "x"])
+def test_link_arrays_where_the_first_volume_has_none_are_refused(inst, extra):
+    """the first volume decides, for smooth_x / smooth_y and for smooth_t separately; exactly one of smooth_x / smooth_y is refused too"""
+    probs, _ = _trio()
+    if extra == "x":
+        first, other = probs[0], dict(probs[1], sy=None)
+    else:
+        strip = dict(sx=None, sy=None) if extra == "xy" else dict(smt=None)
+        first, other = dict(probs[0], **strip), probs[1]
+    rc, codes, outs = _run_batch(inst, [first, other], "gt")
+    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_OK, capi.SC_ERR_BAD_ARG], (rc, codes)
+    assert (outs[1] == SENTINEL).all(), "a refused volume must not be written"
+    _check_members([first], outs, [[0]], "gt")
+    # ... and the reverse: the first has them, the second does not
+    if extra != "x":
+        rc, codes, outs = _run_batch(inst, [other, first], "gt")
+        assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_OK, capi.SC_ERR_BAD_ARG], (rc, codes)
+        assert (outs[1] == SENTINEL).all()
+
+
+def test_nine_volumes_run_in_two_chunks(inst):
+    """8 frames x 3 channels are 24 planes: a chunk holds 8 volumes, the ninth runs in a second one"""
+    pats = ("hole", "scatter", "keyframes", "split", "all")
+    probs = [wb.make_input("neumann", 7, 5, 3, 8, 1.0, pats[k % 5], "sparse", "xyt", "periodic", seed=50 + k) for k in range(9)]
+    rc, codes, outs = _run_batch(inst, probs)
+    assert rc == capi.SC_OK and codes == [capi.SC_OK] * 9, (rc, codes)
+    _check_members(probs, outs, [list(range(8)), [8]], "lap")
+
+
+def _run_placed(inst, p, place, form="gt"):
+    """one volume through the device call with the arrays named in `place` (name -> float offset) and out at float offset place["out"]
+    of one device block; (code, the block's floats after the call, the block's floats before it)"""
+    T, H, W, C = p["data"].shape
+    jobs, dev = _device_jobs(inst, [p], form)
+    n = p["data"].size
+    host = np.full(3 * n, SENTINEL, np.float32)
+    for name, at in place.items():
+        if name != "out":
+            a = np.ascontiguousarray(p[_NAMES[name]], np.float32).ravel()
+            host[at:at + a.size] = a
+    block = inst.to_device(host)
+    dev.append(block)
+    try:
+        for name, at in place.items():
+            setattr(jobs[0], name, block + 4 * at)
+        kind = G | capi.border_bits(p["sides"], False, p["periodic"])
+        params = capi.VolumeWlsParams(kind, T, H * W * C, p["tau"], 1 if p["tper"] else 0, 0.0, 0, 0.0, 0.0, 0.0)
+        inst.volume_wls_device(params, capi.poisson_layout_of(p["data"][0]), jobs, allow_job_errors=True)
+        return jobs[0].rc, inst.from_device(block, host.shape, np.float32), host
+    finally:
+        for q in dev:
+            inst.free(q)
+
+
+@pytest.mark.parametrize("name", ["smooth_x", "smooth_y", "smooth_t"])
+def test_a_link_array_that_overlaps_out_is_refused(inst, name):
+    """the span rule: a link array may share no float of its span with out's -- here its last float is out's first"""
+    p = wb.make_input("free_lt", 9, 7, 3, 4, 1.0, "scatter", "constant", "xyt", "periodic", seed=30)
+    size = p[_NAMES[name]].size
+    rc, after, before = _run_placed(inst, p, {name: 0, "out": size - 1})
+    assert rc == capi.SC_ERR_BAD_ARG
+    assert np.array_equal(after, before), "a refused volume must not be written"
+    rc, after, before = _run_placed(inst, p, {name: 0, "out": size})          # one float further: side by side
+    assert rc == capi.SC_OK
+    assert_yardstick(f"{name} ends where out begins", p, "gt", after[size:size + p["data"].size].reshape(p["data"].shape))
+    assert np.array_equal(after[:size], before[:size]) and (after[size + p["data"].size:] == SENTINEL).all()
+
+
+def test_the_span_of_smooth_t_is_its_own_frames(inst):
+    """smooth_t of frames - 1 frames that ends where out begins is fine under free time; the same placement under periodic time, where
+    smooth_t holds `frames` frames, overlaps out's first frame"""
+    p = wb.make_input("free_lt", 9, 7, 3, 4, 1.0, "scatter", "constant", "t", "free", seed=31)
+    frame = p["data"][0].size
+    rc, after, before = _run_placed(inst, p, {"smooth_t": 0, "out": 3 * frame})
+    assert rc == capi.SC_OK
+    assert_yardstick("smooth_t before out, free time", p, "gt", after[3 * frame:7 * frame].reshape(p["data"].shape))
+    q = wb.make_input("free_lt", 9, 7, 3, 4, 1.0, "scatter", "constant", "t", "periodic", seed=31)
+    rc, after, before = _run_placed(inst, q, {"smooth_t": 0, "out": 3 * frame})
+    assert rc == capi.SC_ERR_BAD_ARG and np.array_equal(after, before)
+
+
+# ---- 6. the Python entry points ---------------------------------------------------------------------------------------------------------
+def _video(T, H, W, C, seed):
+    rng = np.random.default_rng(seed)
+    t, y, x = np.mgrid[0:T, 0:H, 0:W]
+    base = 2.0 + np.sin((x + 2 * t) / 5.0) + np.cos(y / 4.0) + 0.1 * t + (x > W // 2) * 0.8
+    return (base[:, :, :, None] + 0.05 * rng.standard_normal((T, H, W, C))).astype(np.float32)
+
+
+def _problem(v, state, weight, sx, sy, smt, tau, loop, data=None, **guidance):
+    shape = v.shape
+    full = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(a.reshape(a.shape + (1,) * (len(shape) - a.ndim)), a.shape[:1] + shape[1:]), np.float32)
+    p = dict(sides="lrtb", periodic="", tper=loop, tau=tau, state=full(state.astype(np.float32)), data=v if data is None else data, weight=full(weight),
+             sx=full(sx), sy=full(sy), smt=full(smt), boundary=None, lap=np.zeros_like(v), gx=None, gy=None, gt=None)
+    p.update(guidance)
+    return p
+
+
+@pytest.mark.parametrize("loop", [False, True])
+def test_wls_filter_video_against_the_exact_solve(loop):
+    T, H, W, C = 4, 19, 23, 3
+    v = _video(T, H, W, C, 1)
+    out = seamless_clone.wls_filter_video(v, lam=0.5, alpha=1.2, eps=1e-2, tau=2.0, loop=loop)
+    lum = np.log(np.maximum(np.asarray(v, np.float64).mean(3), 0.0) + 1e-6)
+    sx, sy, smt = ((0.5 / (d ** 1.2 + 1e-2)).astype(np.float32) for d in seamless_clone._video_abs_differences(lum, loop))
+    p = _problem(v, np.zeros((T, H, W)), np.ones((T, H, W), np.float32), sx, sy, smt, 2.0, loop)
+    assert_yardstick(f"wls_filter_video loop={loop}", p, "lap", out)
+    # smoothing: the result varies less than the input and keeps the step at W // 2
+    assert np.abs(np.diff(out, axis=2)).mean() < np.abs(np.diff(v, axis=2)).mean()
+
+
+@pytest.mark.parametrize("hard", [True, False])
+def test_interpolate_constraints_video_against_the_exact_solve(hard):
+    T, H, W, C = 4, 19, 23, 3
+    guide = _video(T, H, W, 1, 2)
+    values = _video(T, H, W, C, 3)
+    known = np.random.default_rng(4).random((T, H, W)) < 0.05
+    known[1:3] = False                                      # two frames are filled through time alone
+    sigma = 0.3
+    out = seamless_clone.interpolate_constraints_video(values, known, guide, edge_sigma=sigma, tau=1.5, hard=hard, loop=True, strength=2.0)
+    sx, sy, smt = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in seamless_clone._video_abs_differences(guide, True))
+    if hard:
+        p = _problem(values, np.where(known, 1, 0), None, sx, sy, smt, 1.5, True)
+        assert np.array_equal(bits(out)[known], bits(values)[known])
+    else:
+        d = np.where(known[:, :, :, None], values, np.float32(0)).astype(np.float32)
+        p = _problem(values, np.zeros((T, H, W)), np.where(known, np.float32(2), np.float32(0)), sx, sy, smt, 1.5, True, data=d)
+    assert_yardstick(f"interpolate_constraints_video hard={hard}", p, "lap", out)
+
+
+def _loop_problem(v, lam):
+    T, H, W, _ = v.shape
+    gx, gy, gt = np.zeros_like(v), np.zeros_like(v), np.zeros_like(v)
+    for t in range(T):
+        gx[t], gy[t] = seamless_clone._forward_differences(v[t])
+    gt[:-1] = v[1:] - v[:-1]
+    return _problem(v, np.zeros((T, H, W)), np.full((T, H, W), lam, np.float32), None, None, None, 1.0, True, gx=gx, gy=gy, gt=gt, lap=None)
+
+
+def test_make_loop_against_the_exact_solve():
+    """make_loop at lam = 0.3, the weight the bounds' floors were measured at ("constant"), within the ordinary bounds; then at its default
+    lam = 1e-2.  Every coefficient is constant, so the reference iteration takes no step and the ERR bound is its floor.  At lam = 1e-2
+    nothing but lam holds the clip's mean level: an eigenvalue lam + mu of M divides whatever float32 rounding the right-hand side carries
+    in that mode, while the residual, which the stop rule sees, is not divided.  So RES keeps its bound, and ERR is held in two parts:
+      the whole error             the constant mode, eigenvalue lam:      the floor x 0.3 / lam                     (30 x);
+      less its per-channel mean   every other mode, eigenvalue at least lam + 2 - 2 cos(pi / W), the longest axis' first mode
+                                  (W = 23 columns, reflecting; time's first mode is 1, the rows' larger):  the floor x 0.3 / that  (10.5 x).
+    A wrong wrap link or a wrong gt across the seam is no constant and not small: it fails the first run and the second part.
+    Measured on one MI355X at lam = 1e-2: ERR 1.56e-5 (pcg_f32 4.8e-7), RES 2.4e-6 (pcg_f32 3.1e-6); out - exact has a mean of -5.5e-5
+    per channel and deviates from it by at most 1.2e-5, with max |exact| 4.33."""
+    T, H, W, C = 6, 19, 23, 3
+    v = _video(T, H, W, C, 5)
+    out = seamless_clone.make_loop(v, lam=0.3, tau=1.0)
+    assert_yardstick("make_loop lam=0.3", _loop_problem(v, 0.3), "gt", out)
+    lam = 1e-2
+    out = seamless_clone.make_loop(v, lam=lam, tau=1.0)
+    y = wb.Yardstick(_loop_problem(v, lam), "gt")
+    assert y.iters32 == 0
+    err, res = y.measure(out)
+    diff = np.asarray(out, np.float64) - y.want
+    offset = diff.mean(axis=(0, 1, 2))
+    rest = float(np.abs(diff - offset).max()) / float(np.abs(y.want).max())
+    print(f"VOLUME_WLS make_loop: ERR {err:.3g} (pcg_f32 {y.err32:.3g}) RES {res:.3g} (pcg_f32 {y.res32:.3g}); per channel the mean of out - exact "
+          f"{offset}, less it ERR {rest:.3g}, max |exact| {np.abs(y.want).max():.3g}")
+    eb, rb = y.bounds()
+    assert res <= rb, (res, rb)
+    assert err <= max(eb, wb.ERR_FLOOR * 0.3 / lam), (err, eb)
+    assert rest <= max(eb, wb.ERR_FLOOR * 0.3 / (lam + 2.0 - 2.0 * np.cos(np.pi / W))), (rest, eb)
+    # the seam: the jump from the last frame to the first has shrunk
+    assert np.abs(out[0] - out[-1]).mean() < 0.5 * np.abs(v[0] - v[-1]).mean()
+    with pytest.raises(ValueError):
+        seamless_clone.make_loop(v, lam=0.0)
+
+
+def test_volume_wls_solve_against_the_exact_solve():
+    p = wb.make_input("periodic_x", 23, 17, 3, 5, 0.5, "scatter", "sparse", "xyt", "periodic", seed=7)
+    out = seamless_clone.volume_wls_solve(p["data"], p["state"], gx=p["gx"], gy=p["gy"], gt=p["gt"], weight=p["weight"], smooth_x=p["sx"],
+                                          smooth_y=p["sy"], smooth_t=p["smt"], boundary=p["boundary"], tau=0.5, loop=True, neumann=False, free_sides="",
+                                          periodic="x")
+    assert_yardstick("volume_wls_solve", p, "gt", out)
+    assert_copied_bits(p, out)

@@ -15,6 +15,10 @@
 --kernels  GPU: one scatter volume of 512^2 x 1 x 16 frames and one scatter region image of 2048^2 x 1 -- the same number of pixels --
            each solved once, for a kernel trace taken around this process: the volume operator beside the WLS operator per unknown, the
            two transforms along the frames as a share of one application of the preconditioner.
+--hash     GPU: sha256 of sc_hip_volume's out, and the iteration count, on seeded inputs -- the inputs of tests/volume_bounds.py's matrix()
+           with NaN in every element that is not read, and three 384 x 256 x 3 x 8 volumes (keyframes, moving hole, scatter) -- one line
+           each on standard output.  With --tree DIR the package and library of another build of this repository (tools/ab_trees.sh
+           build) are loaded in place of this tree's; two such listings compare equal when the two builds write the same bytes.
 
     python tools/volume_probe.py --lengths --time [--calls 3] [--warmup 1]
 """
@@ -148,17 +152,37 @@ def kernels(capi, inst):
     print("region 2048 2048 iterations", inst.info().sweeps, flush=True)
 
 
+def hashes(capi, inst):
+    import hashlib
+    import volume_bounds as vb
+    for i, (border, H, W, C, T, tau, pattern, wk, form) in enumerate(vb.matrix()):
+        p = vb.nan_unread(vb.make_input(border, H, W, C, T, tau, pattern, wk))
+        out = volume_call(inst, p, form)
+        print("HASH", i, border, W, H, C, T, form, inst.info().sweeps, hashlib.sha256(out.tobytes()).hexdigest(), flush=True)
+    T, H, W, C = 8, 256, 384, 3
+    data = big_data(T, H, W, C, np.random.default_rng(5))
+    for case in ("keyframes", "hole", "scatter"):
+        out = inst.volume(data, big_state(case, T, H, W, C), lap=np.zeros_like(data), tau=1.0, neumann=True, allow_not_converged=True)
+        print("HASH", case, W, H, C, T, inst.info().sweeps, hashlib.sha256(out.tobytes()).hexdigest(), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lengths", action="store_true")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--hash", action="store_true")
+    ap.add_argument("--tree", default=None, help="with --hash: another build of this repository whose package is loaded")
     ap.add_argument("--lengths-out", default=os.path.join(ROOT, "profiles", "volume_lengths.txt"))
     ap.add_argument("--time-out", default=os.path.join(ROOT, "profiles", "volume_probe.json"))
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     a = ap.parse_args()
+    if a.tree:
+        sys.path.insert(0, os.path.abspath(a.tree))
     from seamlesscloneoptimization_amd import capi
+    if a.tree and not os.path.abspath(capi.__file__).startswith(os.path.abspath(a.tree) + os.sep):
+        raise SystemExit(f"--tree {a.tree}: the package was loaded from {capi.__file__}")
     inst = capi.Instance(0)
     try:
         if a.lengths:
@@ -167,6 +191,8 @@ def main():
             timing(capi, inst, a.time_out, a.calls, a.warmup)
         if a.kernels:
             kernels(capi, inst)
+        if a.hash:
+            hashes(capi, inst)
     finally:
         inst.destroy()
 
