@@ -21,8 +21,12 @@
 //      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
+//  10. a job's side arrays (SideArrays; sc_instance.h, sc_pcg.h): for_side_tables fills every family's table, 20 jobs as 16 + 4, each
+//      slot with exactly its table's members of the matching record; float_intake pairs every array of a job it takes in with that job
+//      and stores NULL for what the call does not carry.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
+#include "sc_pcg.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -100,6 +104,30 @@ void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, i
 void __hipRegisterManagedVar(void *, void *, void *, const char *, size_t, unsigned) {}
 void __hipRegisterSurface(void **, void *, char *, char *, int, int) {}
 void __hipRegisterTexture(void **, void *, char *, char *, int, int, int) {}
+}
+
+// 10: the pointer that stands for array `which` (0 .. 5: w, sx, sy, st, gt, smt; 6 ..: a PoissonJobDev's or a public job's others) of job k; never read
+static const float *fake(int k, int which) { return (const float *)(uintptr_t)(0x10000 * (k + 1) + 0x100 * (which + 1)); }
+// m jobs through Table's tables: the callback sees them in order, Table::MAX at a time; in every slot the job is job k's and each member
+// the table has (members(t): its arrays in w, sx, sy, st, gt, smt order, nullptr for one it lacks) is record k's; the rest of a table is zeros
+template <class Table, class Members> static bool tables_ok(const sc::PoissonJobDev *jobs, const sc::SideArrays *sides, int m, Members members)
+{
+    int calls = 0, seen = 0;
+    bool ok = true;
+    sc::for_side_tables<Table>(jobs, sides, m, [&](const Table &t, int i0, int cnt) {
+        ok = ok && i0 == seen && cnt == std::min(m - i0, (int)Table::MAX);
+        const auto mem = members(t);
+        const float *const *const *has = mem.a;
+        for (int i = 0; i < (int)Table::MAX; ++i) {
+            const int k = i0 + i;
+            const bool used = i < cnt;
+            for (int a = 0; a < 6; ++a) ok = ok && (!has[a] || has[a][i] == (used ? fake(k, a) : nullptr));
+            ok = ok && t.j[i].gx == (used ? fake(k, 6) : nullptr) && t.j[i].out == (used ? (float *)fake(k, 7) : nullptr) && t.j[i].d == (used ? fake(k, 8) : nullptr);
+        }
+        seen += cnt;
+        ++calls;
+    });
+    return ok && seen == m && calls == (m + (int)Table::MAX - 1) / (int)Table::MAX;
 }
 
 static int fail(const char *what) { fprintf(stderr, "sanitize_main: %s\n", what); return 1; }
@@ -541,6 +569,69 @@ int main()
         }
         long long sp[4];
         if (sc_hip_restore_spans(30, 4, 8, 0, 5, 3, sp, 2) != SC_ERR_BAD_ARG || sc_hip_restore_spans(30, 4, 0, 0, 5, 3, nullptr, 2) != SC_ERR_BAD_ARG) return fail("restore_spans (bad geometry)");
+    }
+    // 10: a job's side arrays from the record to the kernels' tables, and from the public jobs to the record
+    {
+        using namespace sc;
+        const int m = 20;
+        std::vector<PoissonJobDev> jobs(m);
+        std::vector<SideArrays> sides(m);
+        for (int k = 0; k < m; ++k) {
+            jobs[k] = PoissonJobDev{ fake(k, 6), nullptr, nullptr, nullptr, (float *)fake(k, 7), fake(k, 8) };
+            sides[k] = SideArrays{ fake(k, 0), fake(k, 1), fake(k, 2), fake(k, 3), fake(k, 4), fake(k, 5) };
+        }
+        struct Members { const float *const *a[6]; };
+        if (!tables_ok<VolumeJobs>(jobs.data(), sides.data(), m, [](const VolumeJobs &t) { return Members{ { t.w, t.sx, t.sy, t.st, t.gt, t.smt } }; })) return fail("for_side_tables<VolumeJobs>");
+        if (!tables_ok<RegionJobs>(jobs.data(), sides.data(), m, [](const RegionJobs &t) { return Members{ { t.w, t.sx, t.sy, t.st, nullptr, nullptr } }; })) return fail("for_side_tables<RegionJobs>");
+        if (!tables_ok<WlsJobs>(jobs.data(), sides.data(), m, [](const WlsJobs &t) { return Members{ { t.w, t.sx, t.sy, nullptr, nullptr, nullptr } }; })) return fail("for_side_tables<WlsJobs>");
+        if (!tables_ok<WeightedJobs>(jobs.data(), sides.data(), m, [](const WeightedJobs &t) { return Members{ { t.w, nullptr, nullptr, nullptr, nullptr, nullptr } }; })) return fail("for_side_tables<WeightedJobs>");
+
+        // the intake: job 1 without state and job 3 with an unaligned smooth_t are refused; what stays is paired job by job
+        const int all = FLOAT_DATA | FLOAT_WEIGHT | FLOAT_SMOOTH | FLOAT_STATE | FLOAT_GT | FLOAT_SMOOTH_T;
+        auto arrays_of = [](const sc_volume_wls_job &j) {
+            FloatArrays a{ j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, j.smooth_x, j.smooth_y, j.state };
+            a.gt = j.gt;
+            a.smooth_t = j.smooth_t;
+            return a;
+        };
+        for (int pass = 0; pass < 2; ++pass) {
+            const bool links = pass == 0;
+            const int carries = links ? all : all & ~(FLOAT_SMOOTH | FLOAT_SMOOTH_T);
+            sc_volume_wls_job pub[5];
+            for (int k = 0; k < 5; ++k) {
+                pub[k] = sc_volume_wls_job{ fake(k, 6), fake(k, 9), fake(k, 4), nullptr, fake(k, 8), k == 1 ? nullptr : fake(k, 3), fake(k, 0),
+                                            links ? fake(k, 1) : nullptr, links ? fake(k, 2) : nullptr,
+                                            !links ? nullptr : k == 3 ? (const float *)((uintptr_t)fake(k, 5) + 2) : fake(k, 5), fake(k, 10),
+                                            (float *)fake(k, 7), 12345 };
+            }
+            Instance inst;
+            FloatJobs v;
+            const int rc = float_intake(&inst, SC_POISSON_GUIDANCE, carries, pub, 5, arrays_of, v);
+            const std::vector<int> stay = links ? std::vector<int>{ 0, 2, 4 } : std::vector<int>{ 0, 2, 3, 4 };
+            if (rc != SC_ERR_BAD_ARG || inst.err != "null state pointer") return fail("float_intake: the worst code and the first reason");
+            if (v.dj.size() != stay.size() || v.side.size() != stay.size() || v.rcs.size() != stay.size()) return fail("float_intake: how many jobs stay");
+            if (pub[1].rc != SC_ERR_BAD_ARG || (links && pub[3].rc != SC_ERR_BAD_ARG)) return fail("float_intake: a refused job's code");
+            for (size_t i = 0; i < stay.size(); ++i) {
+                const int k = stay[i];
+                const SideArrays &a = v.side[i];
+                if (v.rcs[i] != &pub[k].rc || pub[k].rc != SC_ERR_HIP) return fail("float_intake: where a job's code goes");
+                if (v.dj[i].gx != fake(k, 6) || v.dj[i].gy != fake(k, 9) || v.dj[i].b != fake(k, 10) || v.dj[i].out != (float *)fake(k, 7) || v.dj[i].d != fake(k, 8))
+                    return fail("float_intake: a job's own arrays");
+                if (a.w != fake(k, 0) || a.st != fake(k, 3) || a.gt != fake(k, 4)) return fail("float_intake: w, st or gt of another job");
+                if (links ? (a.sx != fake(k, 1) || a.sy != fake(k, 2) || a.smt != fake(k, 5)) : (a.sx || a.sy || a.smt))
+                    return fail("float_intake: sx, sy or smt of another job, or not NULL where the call carries none");
+            }
+        }
+        // ... and an array the call does not carry is NULL in the record whatever the job brings (the entries refuse such a job before)
+        {
+            sc_volume_wls_job one{ fake(0, 6), fake(0, 9), fake(0, 4), nullptr, fake(0, 8), fake(0, 3), fake(0, 0), fake(0, 1), fake(0, 2), fake(0, 5), fake(0, 10),
+                                   (float *)fake(0, 7), 0 };
+            Instance inst;
+            FloatJobs v;
+            if (float_intake(&inst, SC_POISSON_GUIDANCE, FLOAT_DATA | FLOAT_STATE, &one, 1, arrays_of, v) != SC_OK || v.side.size() != 1) return fail("float_intake (a plain region call)");
+            const SideArrays &a = v.side[0];
+            if (a.w || a.sx || a.sy || a.gt || a.smt || a.st != fake(0, 3)) return fail("float_intake: an array the call does not carry must be NULL");
+        }
     }
     printf("sanitize_main: clean\n");
     return 0;

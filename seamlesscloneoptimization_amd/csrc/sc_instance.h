@@ -394,9 +394,14 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 // occupies tspan floats (the call's temporal frames) and may share none of them with out's span.
 int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0, size_t tspan = 0);
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
-// The validated jobs of a device call: their device forms, their weights (NULL without FLOAT_WEIGHT), their link weights (NULL without
-// FLOAT_SMOOTH) and where each one's code goes.
-struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<const float *> w, sx, sy, st, gt, smt; std::vector<int *> rcs; };
+// A job's side arrays: what a family's set-up reads beside the job's PoissonJobDev -- data weights, spatial link weights, the region
+// and volume calls' state, the volume calls' temporal guidance and temporal link weights.  Device pointers; an array the call does not
+// carry (its FLOAT_* bit is not in `carries`) is NULL: float_intake and float_stage say so, nobody behind them asks again.  One record
+// per job, beside its PoissonJobDev from there to the kernels' tables (sc_pcg.h: PcgOperator::ds, for_side_tables).
+struct SideArrays { const float *w = nullptr, *sx = nullptr, *sy = nullptr, *st = nullptr, *gt = nullptr, *smt = nullptr; };
+// The validated jobs of a device call: their device forms (contiguous: the Poisson and the screened call hand dj.data() to the solve),
+// their side arrays and where each one's code goes.
+struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<SideArrays> side; std::vector<int *> rcs; };
 // A device call's job intake: arrays_of(job) names one public job's arrays.  A job that fails float_job_validate gets its code; the
 // others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
 // empty: nothing to run).
@@ -417,25 +422,21 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
         }
         j.rc = SC_ERR_HIP;          // until its chunk has run
         v.dj.push_back(float_dev_job(kind, carries, a));
-        v.w.push_back(a.weight);
-        v.sx.push_back(a.smooth_x);
-        v.sy.push_back(a.smooth_y);
-        v.st.push_back(a.state);
-        v.gt.push_back(a.gt);
-        v.smt.push_back(a.smooth_t);
+        const bool smooth = (carries & FLOAT_SMOOTH) != 0;
+        v.side.push_back(SideArrays{ carries & FLOAT_WEIGHT ? a.weight : nullptr, smooth ? a.smooth_x : nullptr, smooth ? a.smooth_y : nullptr,
+                                     carries & FLOAT_STATE ? a.state : nullptr, carries & FLOAT_GT ? a.gt : nullptr,
+                                     carries & FLOAT_SMOOTH_T ? a.smooth_t : nullptr });
         v.rcs.push_back(&j.rc);
     }
     return worst;
 }
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
 // boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state --, uploaded in that order.  job: the
-// device job (float_dev_job's rules; job.out is what poisson_download reads), d_w: the weights, d_sx, d_sy: the link weights, d_state: the states.
+// device job (float_dev_job's rules; job.out is what poisson_download reads), side: the staged side arrays (NULL where the call carries none).
 // frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; the
 // temporal arrays -- gt, FLOAT_GT and not NULL, and smooth_t, FLOAT_SMOOTH_T -- hold tframes of them (0: frames - 1) and go behind
 // state, each through a pinned block of its own.
-struct FloatStaged {
-    PoissonJobDev job; const float *d_w; const float *d_sx = nullptr, *d_sy = nullptr, *d_state = nullptr, *d_gt = nullptr, *d_smt = nullptr;
-};
+struct FloatStaged { PoissonJobDev job; SideArrays side; };
 int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames = 1,
                 long long frame_stride = 0, int tframes = 0);
 // nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and

@@ -1,6 +1,7 @@
 // sc_pcg.cpp -- the preconditioned conjugate gradients of the weighted, the WLS and the robust call (sc_pcg.h): a family's entry points
-// run pcg_begin and then pcg_host_call or pcg_device_call, which hand pcg_run the validated jobs and the family's PcgOperator.  Per chunk
-// of at most SC_POISSON_MAX_PLANES planes (run_chunks):
+// run pcg_begin and then pcg_host_call or pcg_device_call, which hand pcg_run the validated jobs, their side arrays (SideArrays: one
+// record per job) and the family's PcgOperator.  Per chunk of at most SC_POISSON_MAX_PLANES planes (run_chunks) the driver gives the
+// operator the chunk's jobs and records (dj, ds) and keeps the two in step: when a job leaves, both move up in one statement.
 //   1. the family's statistics (one launch, one host read -- the call's one mandatory wait); a job they refuse gets SC_ERR_BAD_ARG and
 //      leaves the chunk, the rest give the preconditioner's constant lam.
 //   2. set-up: b and the family's coefficients onto compact work planes that hold the unknowns only (from here on every vector is
@@ -80,13 +81,13 @@ int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOp
     SC_HIP(I, hipGetLastError());
     SC_HIP(I, hipMemcpyAsync(h_stats, d_stats, sizeof(double) * nstat * per, hipMemcpyDeviceToHost, s));
     SC_HIP(I, hipStreamSynchronize(s));
-    for (int k = 0; k < m; ++k) {          // the jobs that stay: their arrays move to the front
+    for (int k = 0; k < m; ++k) {          // the jobs that stay: they and their side arrays move to the front
         const char *why = op.judge(g, k, h_stats + (size_t)k * g.C * PCG_PARTS * nstat, nop, no_dirichlet);
         if (why) {
             *rcs[k] = SC_ERR_BAD_ARG;
             if (!job_errors++) I->err = why;
         } else {
-            op.dj[c.live.size()] = op.dj[k];
+            op.dj[c.live.size()] = op.dj[k], op.ds[c.live.size()] = op.ds[k];
             c.live.push_back(rcs[k]);
         }
     }
@@ -212,8 +213,8 @@ int pcg_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator
 
 } // namespace
 
-int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed,
-            PcgChunkFn chunk)
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, const SideArrays *sides,
+            int *const *rcs, int nv, bool timed, PcgChunkFn chunk)
 {
     if (!chunk) chunk = pcg_chunk;
     CallScope scope{ I };
@@ -228,7 +229,8 @@ int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOpe
     int worst = run_chunks(I, op.chunk_planes(g.C), rcs, nv, [&](int i0, int m) {
         PcgChunkResult res;
         op.dj.assign(jobs + i0, jobs + i0 + m);
-        op.begin(i0, m);
+        op.ds.assign(sides + i0, sides + i0 + m);
+        op.begin();
         const int rc = chunk(I, call, g, op, rcs + i0, m, res, job_errors);
         sweeps = std::max(sweeps, res.iters);
         converged = converged && res.converged;
@@ -260,11 +262,7 @@ int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, 
     FloatStaged s;
     if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride, call.tframes))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
-    op.bind(&s.d_w, &s.d_sx, &s.d_sy);
-    op.bind_state(&s.d_state);
-    op.bind_gt(&s.d_gt);
-    op.bind_smooth_t(&s.d_smt);
-    rc = pcg_run(I, call, l, op, &s.job, job_rcs, 1, true, chunk);
+    rc = pcg_run(I, call, l, op, &s.job, &s.side, job_rcs, 1, true, chunk);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
     const float t[4] = { 0.f, I->info.ms_solve, 0.f, I->info.ms_call };     // (one solve stage: pcg_run times the call whole)
     return poisson_download(I, l, s.job.out, a.out, t, rc, call.frames, call.frame_stride);

@@ -41,7 +41,7 @@ void pcg_release(Instance *I);             // frees Instance::pcg and all it hol
 
 // What a family tells the iteration about its operator.  Per chunk, in this order: begin -> stats (one launch per 16 jobs, `nstat`
 // doubles per part; the driver reads them back: the chunk's one mandatory wait) -> judge for every job, in order (a reason: the job gets
-// SC_ERR_BAD_ARG and leaves; NULL: it stays, its arrays move to the front and its sums count) -> setup -> precond_constant ->
+// SC_ERR_BAD_ARG and leaves; NULL: it stays, its sums count, and the driver moves its dj and ds to the front) -> setup -> precond_constant ->
 // scale_start on u0 (a cold start only) -> apply, once in its residual form and then once per iteration, precond wherever M^-1 is
 // applied.  Everything else -- the update, dot and direction launches, the stop rule's mailbox -- is the driver's own, and so are the
 // defaults of precond (direct_jobs_solve with precond_constant's lam), out, work_geo and chunk_planes, which only the volume family
@@ -51,18 +51,14 @@ struct PcgOperator {
     const int nstat;                       // doubles per part of the statistics launch
     const int nround;                      // doubles per part a family's own later launches sum (PcgChunk::d_round; the robust call's rounds)
     std::vector<PoissonJobDev> dj;         // the chunk's jobs; behind judge: the ones that stay, in front
+    std::vector<SideArrays> ds;            // ... and their side arrays, record k beside job k: the driver assigns and moves the two together
     explicit PcgOperator(int nstat_, int nround_ = 0) : nstat(nstat_), nround(nround_) {}
     virtual ~PcgOperator() = default;
-    // the call's weights and link weights, one pointer per job (pcg_host_call, pcg_device_call: once the staged or taken-in tables exist)
-    virtual void bind(const float *const *w, const float *const *sx, const float *const *sy) = 0;
-    virtual void bind_state(const float *const *state) {}                           // ... and its state arrays (the region call's; the others have none)
-    virtual void bind_gt(const float *const *gt) {}                                 // ... and its temporal guidance (the volume call's; NULL entries: zeros)
-    virtual void bind_smooth_t(const float *const *smooth_t) {}                     // ... and its temporal link weights (the WLS volume call's; NULL entries: every one tau)
     // work planes per job and channel that run_chunks counts against SC_POISSON_MAX_PLANES (the volume call: its frames), and the work
     // planes' geometry: by default one plane of mg's unknowns per (job, channel) (the volume call: its frames stacked along y)
     virtual int chunk_planes(int C) const { return C; }
     virtual PcgGeo work_geo(const MixedGeo &mg) const { return pcg_geo(mg); }
-    virtual void begin(int i0, int m) = 0;                                          // the chunk is jobs i0 .. i0 + m - 1 of the call
+    virtual void begin() = 0;                                                       // a new chunk (dj, ds are set): the running sums start over
     virtual void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) = 0;
     // st: job k's statistics, its C planes' PCG_PARTS * nstat doubles each, of which the first `parts` parts are set
     virtual const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) = 0;
@@ -135,14 +131,15 @@ struct PcgChunk {
 int pcg_chunk_begin(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, int &job_errors, PcgChunk &c);
 int pcg_chunk_iterate(PcgChunk &c, PcgOperator &op, bool warm, PcgChunkResult &res);
 int pcg_chunk_finish(PcgChunk &c, PcgOperator &op, int code);
-// one chunk of a call: jobs i0 .. of the call's are op.dj already; sets res and the jobs' codes, returns the chunk's code (run_chunks')
+// one chunk of a call: jobs i0 .. of the call's and their side arrays are op.dj and op.ds already; sets res and the jobs' codes, returns the chunk's code (run_chunks')
 using PcgChunkFn = int (*)(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res,
                            int &job_errors);
-// The validated jobs of a call through chunks (run_chunks) and sc_run_info.  Returns the worst code, the jobs' own refusals included.
+// The validated jobs of a call and their side arrays (sides[k]: job k's) through chunks (run_chunks) and sc_run_info.  Returns the worst
+// code, the jobs' own refusals included.
 // chunk: NULL: begin, setup, one cold solve, finish (the weighted and the WLS call).  sc_run_info's sweeps, converged and rel_residual
 // are the chunks' res: the most iterations, all converged, the worst residual.
-int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, int *const *rcs, int nv, bool timed,
-            PcgChunkFn chunk = nullptr);
+int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOperator &op, const PoissonJobDev *jobs, const SideArrays *sides, int *const *rcs,
+            int nv, bool timed, PcgChunkFn chunk = nullptr);
 // What every entry of the three families starts with: the instance, the family's validation of the call (its sc_hip_*_check) and the
 // instance's word on a direct solve, with the family's two reasons; kind: poisson_norm_kind's
 template <class Params> int pcg_begin(void *inst, const Params *p, const sc_poisson_layout *l,
@@ -156,10 +153,10 @@ template <class Params> int pcg_begin(void *inst, const Params *p, const sc_pois
     kind = poisson_norm_kind(p->kind);
     return direct_instance_check(I, kind, l, method_why, fp64_why);
 }
-// ... and ends with.  A host entry: the job's validation, float_stage, op bound to the staged arrays, pcg_run, the download into out
+// ... and ends with.  A host entry: the job's validation, float_stage, pcg_run on the staged job and its side arrays, the download into out
 int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, int carries, const FloatArrays &a, PcgOperator &op,
                   PcgChunkFn chunk = nullptr);
-// A device entry: float_intake (the jobs it refuses get their codes), op bound to the others' arrays, pcg_run; the worst code
+// A device entry: float_intake (the jobs it refuses get their codes), pcg_run on the others and their side arrays; the worst code
 template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, int carries, Job *jobs, int n,
                                                          ArraysOf arrays_of, PcgOperator &op, bool timed, PcgChunkFn chunk = nullptr)
 {
@@ -167,11 +164,7 @@ template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgC
     const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l), pcg_call_tspan(call, l));
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
-    op.bind(v.w.data(), v.sx.data(), v.sy.data());
-    op.bind_state(v.st.data());
-    op.bind_gt(v.gt.data());
-    op.bind_smooth_t(v.smt.data());
-    return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
+    return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.side.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
 }
 
 // ---- the shared launches (sc_pcg.hip)
@@ -185,35 +178,44 @@ void launch_pcg_scale(const PcgGeo &wg, int planes, float *U, float f, hipStream
 // the jobs' out: U at the unknowns, boundary's values on the Dirichlet lines
 void launch_pcg_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, int m, const float *U, hipStream_t s);
 
+// ---- the families' launches.  Those that read the jobs' arrays take m jobs and their side arrays (sides[k]: job k's) and go through the
+// family's table, a kernel parameter: Table::set(i, job, side) copies into slot i the members that table has (host side only; the
+// layout is the kernels').  fn(table, i0, cnt) launches jobs i0 .. i0 + cnt - 1 (for_job_tables); what a launch decides by "the call
+// has this array" it reads off the table's first record.
+template <class Table, class Fn> void for_side_tables(const PoissonJobDev *jobs, const SideArrays *sides, int m, Fn fn)
+{
+    for_job_tables<Table>(m, [&](Table &t, int i, int k) { t.set(i, jobs[k], sides[k]); }, fn);
+}
+
 // ---- the weighted family (sc_weighted.hip): L = A - W, W = diag(w) >= 0
-struct WeightedJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX]; };
+struct WeightedJobs {
+    enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX];
+    void set(int i, const PoissonJobDev &job, const SideArrays &a) { j[i] = job; w[i] = a.w; }
+};
 // stats[(plane * PCG_PARTS + i) * 2] = the part's sum of w over the unknowns, [.. + 1] = how many of them are negative or not finite
-void launch_weighted_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, int m, double *stats, hipStream_t s);
+void launch_weighted_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats, hipStream_t s);
 // R = b = lap - w d (screened_rhs's order) less the neighbouring Dirichlet lines' values, Wc = w, bb = the parts of b . b
-void launch_weighted_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, int m, float *R, float *Wc,
+void launch_weighted_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R, float *Wc,
                            double *bb, hipStream_t s);
 // residual = false: Q = (A - W) P, parts of P . Q;  true: Q = Q - (A - W) P in place, parts of Q . Q
 void launch_weighted_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *Wc, float *Q, double *parts, hipStream_t s);
 
 // ---- the WLS family (sc_wls.hip): (L u)(p) = sum_q s(p, q) (u(q) - u(p)) - w(p) u(p), per-link weights sx, sy > 0 under the call's layout
-struct WlsJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX]; };
-// m jobs and their arrays through WlsJobs tables: fn(table, i0, cnt) launches jobs i0 .. i0 + cnt - 1 (for_job_tables)
-template <class Fn> void for_wls_tables(const PoissonJobDev *jobs, const float *const *w, const float *const *sx, const float *const *sy, int m, Fn fn)
-{
-    for_job_tables<WlsJobs>(m, [&](WlsJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; }, fn);
-}
+struct WlsJobs {
+    enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX];
+    void set(int i, const PoissonJobDev &job, const SideArrays &a) { j[i] = job; w[i] = a.w; sx[i] = a.sx; sy[i] = a.sy; }
+};
 constexpr int WLS_STATS = 4;
 // the live links of one plane: those with at least one end among the unknowns
 double wls_live_links(const PcgGeo &wg);
 // stats[(plane * PCG_PARTS + i) * WLS_STATS + ..] = the part's sum of w | how many w are negative or not finite | the sum of its
 // live links, each counted once | how many of them are not finite or not > 0
-void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, double *stats, hipStream_t s);
+void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats, hipStream_t s);
 // R = b (the order: seamlessclone_hip.h, the WLS section), E / S = the link to the next unknown column / row (0: none), Dg = the sum of
 // the four incident links, Dirichlet ones included, plus w; bb = the parts of b . b.  sx NULL (for every job of the call; guidance form
 // only): every link that exists is 1 and neither array is read -- the bytes of a call given arrays of 1.0f
-void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
+void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R, float *E,
+                      float *S, float *Dg, double *bb, hipStream_t s);
 // residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
 void launch_wls_op(const PcgGeo &wg, int planes, bool residual, const float *P, const float *E, const float *S, const float *Dg, float *Q,
                    double *parts, hipStream_t s);
@@ -225,16 +227,12 @@ struct WlsOperator : PcgOperator {
     Instance *const I;
     const bool links;
     const float plam, psmooth;
-    const float *const *all_w = nullptr, *const *all_sx = nullptr, *const *all_sy = nullptr;
-    std::vector<const float *> dw, dsx, dsy;      // the chunk's; behind judge: of the jobs that stay, in front
-    int kept = 0;
     double wsum = 0.0, ssum = 0.0;                 // the sums of the weights and of the live links of the jobs that stay
     bool unit_links = false;                       // every live link is 1: s-bar is
     float u0_scale = 1.f;                          // 1 / s-bar
     WlsOperator(Instance *I_, bool links_, float plam_, float psmooth_, int nround_ = 0, int nstat_ = 0)      // nstat_: a subclass's own statistics
         : PcgOperator(nstat_ ? nstat_ : links_ ? WLS_STATS : 2, nround_), I(I_), links(links_), plam(plam_), psmooth(psmooth_) {}
-    void bind(const float *const *w, const float *const *sx, const float *const *sy) override { all_w = w; all_sx = sx; all_sy = sy; }
-    void begin(int i0, int m) override;
+    void begin() override;
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override;
     const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override;
     float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override;
@@ -245,42 +243,48 @@ struct WlsOperator : PcgOperator {
 
 // ---- the region family (sc_region.hip): the WLS system on a domain of any shape -- per job one more array, state, under the call's
 // layout: 0 an unknown, 1 known (u = data), 2 outside the domain (its links do not exist); w NULL: no data term, sx NULL: every link 1
-struct RegionJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX], *st[MAX]; };
+struct RegionJobs {
+    enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX], *st[MAX];
+    void set(int i, const PoissonJobDev &job, const SideArrays &a) { j[i] = job; w[i] = a.w; sx[i] = a.sx; sy[i] = a.sy; st[i] = a.st; }
+};
 constexpr int REGION_STATS = 8;
 // stats[(plane * PCG_PARTS + i) * REGION_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
 // the sum of its links live in the region, each counted once | how many of them are invalid | its UNKNOWN pixels | the sum of its
 // UNKNOWN - KNOWN links | its state elements that are not 0, 1 or 2 | its links live in the region
-void launch_region_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, const float *const *st, int m, double *stats, hipStream_t s);
+void launch_region_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats, hipStream_t s);
 // R = b (the order: seamlessclone_hip.h, the region section); E / S = the link to the next column / row where both ends are UNKNOWN; Dg =
 // the sum of the incident links live in the region plus w; all four 0 at every pixel that is not UNKNOWN; bb = the parts of b . b
-void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, const float *const *st, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s);
+void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R, float *E,
+                         float *S, float *Dg, double *bb, hipStream_t s);
 // the jobs' out: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
-void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *st, int m, const float *U, hipStream_t s);
+void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const float *U, hipStream_t s);
 
 // ---- the volume family (sc_volume.hip): the region system on a stack of T frames, plus temporal links between (q, t) and (q, t + 1)
 // -- and, under periodic time, between (q, T - 1) and (q, 0).  A spatial link weighs sx / sy (NULL: 1), a temporal one lt = tau * smt
 // rounded to float32 (smt NULL: tau).  A job's arrays hold T frames fs floats apart (gt, smt: T - 1, with periodic time T; element
 // (q, t) belongs to the link from frame t to the next).  Work planes: one per (volume, channel), the frames stacked along y: wg.ny =
 // T * (a frame's rows of unknowns), wg from VolumeOperator::work_geo.
-struct VolumeJobs { enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *st[MAX], *gt[MAX], *sx[MAX], *sy[MAX], *smt[MAX]; };
+struct VolumeJobs {
+    enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *st[MAX], *gt[MAX], *sx[MAX], *sy[MAX], *smt[MAX];
+    void set(int i, const PoissonJobDev &job, const SideArrays &a)
+    {
+        j[i] = job; w[i] = a.w; st[i] = a.st; gt[i] = a.gt; sx[i] = a.sx; sy[i] = a.sy; smt[i] = a.smt;
+    }
+};
 struct VolumeGeo { int T, ny; long long fs; float tau; int periodic; };      // ny: a frame's rows of unknowns; periodic: time wraps
-// a volume job's arrays beside its PoissonJobDev, one pointer per job each (an array of NULLs where the call has none)
-struct VolumeArrays { const float *const *w, *const *st, *const *gt, *const *sx, *const *sy, *const *smt; };
 constexpr int VOLUME_STATS = 11, VOLUME_STATS_PLAIN = 5;
 // stats[(plane * PCG_PARTS + i) * VOLUME_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
 // its UNKNOWN pixels | the sum of its UNKNOWN - KNOWN links' weights, spatial and temporal | its state elements that are not 0, 1 or 2 |
 // the sum of its spatial links live in the region (k_region_stats' owner rule) | how many there are | how many are invalid | the sum of
 // its live temporal links lt (the earlier frame owns a link, frame T - 1 the wrapping one) | how many there are | how many are invalid.
-// A call without any link array under free time (a.sx[0] and a.smt[0] NULL, vg.periodic 0) has parts of the first VOLUME_STATS_PLAIN
+// A call without any link array under free time (the first record's sx and smt NULL, vg.periodic 0) has parts of the first VOLUME_STATS_PLAIN
 // fields alone, as sc_hip_volume always had: stats[(plane * PCG_PARTS + i) * VOLUME_STATS_PLAIN + ..].
-void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                          double *stats, hipStream_t s);
 // R = b (the order: seamlessclone_hip.h, the volume sections); E / S / F = the link to the next column / row / frame where both ends are
 // UNKNOWN (F in the last frame's rows: the wrapping link, 0 with free time); Dg = the sum of the incident live links plus w; all five 0
 // at every pixel that is not UNKNOWN; bb = the parts of b . b
-void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                          float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s);
 // residual = false: Q = L P, parts of P . Q;  true: Q = Q - L P in place, parts of Q . Q
 void launch_volume_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool residual, const float *P, const float *E, const float *S, const float *F,
@@ -292,7 +296,7 @@ void launch_volume_tables(int T, int planes, bool periodic, double wbar, double 
 // out[p][k] = sum_t D[k][t] in[p][t] (transposed: sum_t D[t][k] in[p][t]) for every pixel of the frames of `planes` work planes
 void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool transposed, const float *D, const float *in, float *out, hipStream_t s);
 // the jobs' out, frame by frame: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
-void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *st, int m,
+void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                        const float *U, hipStream_t s);
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
@@ -303,8 +307,7 @@ constexpr int ROBUST_SUMS = 3;
 // k_wls_setup with s = c rho_p(link residual of U), w' = w rho_q(U - d) (c = sx, sy; NULL for every job: 1): R = b, E, S, Dg as
 // launch_wls_setup in its guidance form, bb = the parts of b . b, sums[(plane * PCG_PARTS + i) * ROBUST_SUMS + ..] = the part's sum of
 // w' | the sum of its live links s, each counted once as launch_wls_stats counts them | the energy of U
-void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
+void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                          float *Dg, double *bb, double *sums, hipStream_t s);
 // The coupled forms (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS; p_grad < 2 only): one magnitude M over the links that share a
 // penalty, s = c rho_p(M) on each of them.  Two launches: k_robust_rho writes rho of every owner (a link's low end) to the rho planes
@@ -318,8 +321,7 @@ inline size_t robust_rho_floats(const PcgGeo &wg, int C, int m, int coupling)
 {
     return (size_t)robust_rho_stride(wg) * ((coupling & ROBUST_ISO) ? 1 : 2) * ((coupling & ROBUST_JOINT) ? m : C * m);
 }
-void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                           const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
+void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
                            float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
 
 } // namespace sc

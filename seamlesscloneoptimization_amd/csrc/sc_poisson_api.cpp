@@ -198,19 +198,14 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     if ((rc = upload(I->h_out, d_w, weight))) return rc;      // (h_out: free until the download)
     if ((rc = upload(I->h_mask, own_b ? d_b : nullptr, boundary))) return rc;
     s.job = float_dev_job(kind, carries, FloatArrays{ guidance ? d_in0 : nullptr, d_in1, guidance ? nullptr : d_in0, d_d, d_w, d_b, d_out });
-    s.d_w = d_w;
     if ((rc = upload(I->h_sx, d_sx, a.smooth_x))) return rc;      // (pinned blocks of their own: the uploads stay back to back)
     if ((rc = upload(I->h_sy, d_sy, a.smooth_y))) return rc;
-    s.d_sx = d_sx;
-    s.d_sy = d_sy;
     if ((rc = upload(I->h_state, d_state, a.state))) return rc;
-    s.d_state = d_state;
     // the temporal arrays: tframes frames (0: one less than the others)
     const size_t tbytes = (poisson_span(l) + (size_t)((tframes > 0 ? tframes : frames - 1) - 1) * (size_t)frame_stride) * sizeof(float);
     if (d_gt && (rc = upload_rows(I, I->h_gt, d_gt, tbytes, (const uint8_t *)a.gt, tbytes, tbytes, 1))) return rc;
-    s.d_gt = d_gt;
     if (d_smt && (rc = upload_rows(I, I->h_smt, d_smt, tbytes, (const uint8_t *)a.smooth_t, tbytes, tbytes, 1))) return rc;
-    s.d_smt = d_smt;
+    s.side = SideArrays{ d_w, d_sx, d_sy, d_state, d_gt, d_smt };      // (an array the call does not carry has no slot: NULL)
     return SC_OK;
 }
 

@@ -159,12 +159,6 @@ __global__ __launch_bounds__(WL) void k_region_out(PoissonGeo g, PcgGeo wg, Regi
     else j.out[o] = j.b[o];
 }
 
-template <class Fn> void for_region_tables(const PoissonJobDev *jobs, const float *const *w, const float *const *sx, const float *const *sy,
-                                           const float *const *st, int m, Fn fn)
-{
-    for_job_tables<RegionJobs>(m, [&](RegionJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; t.sx[i] = sx[k]; t.sy[i] = sy[k]; t.st[i] = st[k]; }, fn);
-}
-
 template <bool LAP, bool ONE> void setup_form(bool now, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const RegionJobs &t, float *R,
                                               float *E, float *S, float *Dg, double *bb)
 {
@@ -174,19 +168,18 @@ template <bool LAP, bool ONE> void setup_form(bool now, dim3 grid, hipStream_t s
 
 } // namespace
 
-void launch_region_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, const float *const *st, int m, double *stats, hipStream_t s)
+void launch_region_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats, hipStream_t s)
 {
-    for_region_tables(jobs, w, sx, sy, st, m, [&](const RegionJobs &t, int i0, int cnt) {
+    for_side_tables<RegionJobs>(jobs, sides, m, [&](const RegionJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_region_stats, dim3((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, t,
                            stats + (size_t)g.C * i0 * PCG_PARTS * REGION_STATS);
     });
 }
 
-void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, const float *const *st, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s)
+void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R, float *E,
+                         float *S, float *Dg, double *bb, hipStream_t s)
 {
-    for_region_tables(jobs, w, sx, sy, st, m, [&](const RegionJobs &t, int i0, int cnt) {
+    for_side_tables<RegionJobs>(jobs, sides, m, [&](const RegionJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;
@@ -198,10 +191,9 @@ void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const 
     });
 }
 
-void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *st, int m, const float *U, hipStream_t s)
+void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const float *U, hipStream_t s)
 {
-    const std::vector<const float *> none((size_t)m, nullptr);
-    for_region_tables(jobs, none.data(), none.data(), none.data(), st, m, [&](const RegionJobs &t, int i0, int cnt) {
+    for_side_tables<RegionJobs>(jobs, sides, m, [&](const RegionJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_region_out, dim3((unsigned)((g.W + WL - 1) / WL), (unsigned)g.H, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, t,
                            U + (size_t)g.C * i0 * wg.stride);
     });

@@ -10,6 +10,7 @@
 //               arrays); w-bar = precond_lambda, or (sum of w + sum of the UNKNOWN - KNOWN links) / (UNKNOWN pixels) over them: a KNOWN
 //               neighbour holds its pixel as a data weight of the link's size would.  M = s-bar (A - w-bar / s-bar) on the whole rectangle.
 //   set-up      k_region_setup;   operator   the WLS one (launch_wls_op);   output   k_region_out in place of the shared launch.
+// state travels as every side array does: SideArrays::st, in PcgOperator::ds beside the job.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -36,21 +37,17 @@ int carries_of(bool weight, bool links) { return FLOAT_DATA | FLOAT_STATE | (wei
 
 struct RegionOperator : WlsOperator {
     const bool has_w;
-    const float *const *all_st = nullptr;
-    std::vector<const float *> dst;              // the chunk's state arrays; behind judge: of the jobs that stay, in front
     double unknowns = 0.0, uksum = 0.0, lcount = 0.0;      // of the jobs that stay: UNKNOWN pixels, the sum of UNKNOWN - KNOWN links, links live in the region
     RegionOperator(Instance *I_, bool weight, bool links_, float plam_, float psmooth_)
         : WlsOperator(I_, links_, plam_, psmooth_, 0, REGION_STATS), has_w(weight) {}
-    void bind_state(const float *const *st) override { all_st = st; }
-    void begin(int i0, int m) override
+    void begin() override
     {
-        WlsOperator::begin(i0, m);
-        dst.assign(all_st + i0, all_st + i0 + m);
+        WlsOperator::begin();
         unknowns = uksum = lcount = 0.0;
     }
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {
-        launch_region_stats(g, wg, dj.data(), dw.data(), dsx.data(), dsy.data(), dst.data(), m, d_stats, s);
+        launch_region_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
     }
     const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
     {
@@ -67,10 +64,6 @@ struct RegionOperator : WlsOperator {
         if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
         if (job[3] != 0.0 || !std::isfinite(job[2])) return "a link weight live in the region is not finite or not > 0";
         if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link and no data weight";
-        dw[kept] = dw[k];
-        dsx[kept] = dsx[k];
-        dsy[kept] = dsy[k];
-        dst[kept++] = dst[k];
         wsum += job[0];
         ssum += job[2];
         unknowns += job[4];
@@ -95,13 +88,12 @@ struct RegionOperator : WlsOperator {
             const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
             if (rc) return rc;
         }
-        launch_region_setup(g, wg, lap, dj.data(), dw.data(), dsx.data(), dsy.data(), dst.data(), mv, R, (float *)S.e.p, (float *)S.s.p,
-                            (float *)S.dg.p, bb, I->stream);
+        launch_region_setup(g, wg, lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb, I->stream);
         return SC_OK;
     }
     void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override
     {
-        launch_region_out(g, wg, dj.data(), dst.data(), mv, U, s);
+        launch_region_out(g, wg, dj.data(), ds.data(), mv, U, s);
     }
 };
 

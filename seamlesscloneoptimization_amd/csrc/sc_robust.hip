@@ -313,8 +313,7 @@ void coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const WlsJobs &t, i
 
 } // namespace
 
-void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                           const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
+void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
                            float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s)
 {
     const bool iso = (coupling & ROBUST_ISO) != 0, joint = (coupling & ROBUST_JOINT) != 0;
@@ -322,7 +321,7 @@ void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJ
     rg.rw = wg.x0 + wg.nx;
     rg.ncomp = iso ? 1 : 2;
     rg.rstride = robust_rho_stride(wg);
-    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
+    for_side_tables<WlsJobs>(jobs, sides, m, [&](const WlsJobs &t, int i0, int cnt) {
         const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
         float *rho = Rho + (size_t)(joint ? i0 : g.C * i0) * rg.ncomp * rg.rstride;
         const bool base = t.sx[0] != nullptr;
@@ -333,11 +332,10 @@ void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJ
     });
 }
 
-void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                         const float *const *sy, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
+void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                          float *Dg, double *bb, double *sums, hipStream_t s)
 {
-    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
+    for_side_tables<WlsJobs>(jobs, sides, m, [&](const WlsJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
         if (t.sx[0]) hipLaunchKernelGGL(k_robust_setup<true>, grid, dim3(WL), 0, s, g, wg, t, grad, data, U + o, R + o, E + o, S + o, Dg + o, bb + po, sums + po * ROBUST_SUMS);

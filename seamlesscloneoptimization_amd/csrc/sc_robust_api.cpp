@@ -83,11 +83,11 @@ struct RobustOperator final : WlsOperator {
         if (cpl) {
             const int rc = ensure(I, S.rho, sizeof(float) * robust_rho_floats(c.wg, c.g.C, c.mv, cpl), false);
             if (rc) return rc;
-            launch_robust_coupled(c.g, c.wg, dj.data(), dw.data(), dsx.data(), dsy.data(), c.mv, grad, data, cpl, c.U, (float *)S.rho.p, c.R,
-                                  (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, c.d_bb, c.d_round, c.d_round + parts * ROBUST_SUMS, I->stream);
+            launch_robust_coupled(c.g, c.wg, dj.data(), ds.data(), c.mv, grad, data, cpl, c.U, (float *)S.rho.p, c.R, (float *)S.e.p,
+                                  (float *)S.s.p, (float *)S.dg.p, c.d_bb, c.d_round, c.d_round + parts * ROBUST_SUMS, I->stream);
         } else
-            launch_robust_setup(c.g, c.wg, dj.data(), dw.data(), dsx.data(), dsy.data(), c.mv, grad, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
-                                (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
+            launch_robust_setup(c.g, c.wg, dj.data(), ds.data(), c.mv, grad, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, c.d_bb,
+                                c.d_round, I->stream);
         SC_HIP(I, hipGetLastError());
         SC_HIP(I, hipMemcpyAsync(c.h_round, c.d_round, sizeof(double) * parts * (ROBUST_SUMS + (cpl ? 1 : 0)), hipMemcpyDeviceToHost, I->stream));
         SC_HIP(I, hipStreamSynchronize(I->stream));

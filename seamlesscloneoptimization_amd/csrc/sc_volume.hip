@@ -331,12 +331,6 @@ __global__ __launch_bounds__(WL) void k_volume_out(PoissonGeo g, PcgGeo wg, Volu
     else j.out[o] = j.b[o];
 }
 
-template <class Fn> void for_volume_tables(const PoissonJobDev *jobs, const VolumeArrays &a, int m, Fn fn)
-{
-    for_job_tables<VolumeJobs>(m, [&](VolumeJobs &t, int i, int k) {
-        t.j[i] = jobs[k]; t.w[i] = a.w[k]; t.st[i] = a.st[k]; t.gt[i] = a.gt[k]; t.sx[i] = a.sx[k]; t.sy[i] = a.sy[k]; t.smt[i] = a.smt[k]; }, fn);
-}
-
 template <bool LNK> void setup_form(bool lap, bool now, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg,
                                     const VolumeJobs &t, float *R, float *E, float *S, float *F, float *Dg, double *b)
 {
@@ -348,10 +342,10 @@ template <bool LNK> void setup_form(bool lap, bool now, dim3 grid, hipStream_t s
 
 } // namespace
 
-void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                          double *stats, hipStream_t s)
 {
-    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const bool general = t.sx[0] || t.smt[0] || vg.periodic;
         double *st = stats + (size_t)g.C * i0 * PCG_PARTS * (general ? VOLUME_STATS : VOLUME_STATS_PLAIN);
@@ -360,10 +354,10 @@ void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo 
     });
 }
 
-void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const VolumeArrays &a, int m,
+void launch_volume_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                          float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s)
 {
-    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;
@@ -396,12 +390,10 @@ void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool t
     else hipLaunchKernelGGL(k_volume_dct<false>, grid, dim3(WL), 0, s, wg, vg, D, in, out);
 }
 
-void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const float *const *st, int m,
+void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                        const float *U, hipStream_t s)
 {
-    const std::vector<const float *> none((size_t)m, nullptr);
-    const VolumeArrays a{ none.data(), st, none.data(), none.data(), none.data(), none.data() };
-    for_volume_tables(jobs, a, m, [&](const VolumeJobs &t, int i0, int cnt) {
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_volume_out, dim3((unsigned)((g.W + WL - 1) / WL), (unsigned)g.H, (unsigned)(g.C * cnt * vg.T)), dim3(WL), 0, s, g, wg, vg, t,
                            U + (size_t)g.C * i0 * wg.stride);
     });

@@ -18,6 +18,7 @@
 //   M^-1        M = s-bar A - w-bar + tau-bar A_t: k_volume_dct along the frames (the DCT-II; periodic time: the Hartley table), one
 //               direct_jobs_solve over all frames * channels * volumes planes with the shift (w-bar + tau-bar mu_k) / s-bar of mode k,
 //               k_volume_dct transposed: exact for constant coefficients.  The factor 1 / s-bar goes once on u0 (scale_start).
+// All six side arrays of a volume come in PcgOperator::ds beside the job (NULL where the call carries none: the front end's word).
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -80,10 +81,6 @@ struct VolumeOperator : PcgOperator {
     const long long fs;
     const float tau, plam, psmooth, ptau;
     const bool periodic, links, tlinks;
-    const float *const *all_w = nullptr, *const *all_st = nullptr, *const *all_gt = nullptr;
-    const float *const *all_sx = nullptr, *const *all_sy = nullptr, *const *all_smt = nullptr;
-    std::vector<const float *> dw, dst, dgt, dsx, dsy, dsmt;      // the chunk's; behind judge: of the volumes that stay, in front
-    int kept = 0;
     // of the volumes that stay: the sums of w and of the UNKNOWN - KNOWN links, the UNKNOWN pixels, the sum and the number of the spatial
     // links live in the region and of the live temporal links
     double wsum = 0.0, unknowns = 0.0, uksum = 0.0, ssum = 0.0, scount = 0.0, tsum = 0.0, tcount = 0.0;
@@ -92,11 +89,6 @@ struct VolumeOperator : PcgOperator {
         : PcgOperator(links_ || tlinks_ || p->time_periodic ? VOLUME_STATS : VOLUME_STATS_PLAIN), I(I_), T(p->frames), fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda), psmooth(p->precond_smooth),
           ptau(p->precond_tau), periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
     VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau, periodic ? 1 : 0 }; }
-    VolumeArrays arrays() const { return VolumeArrays{ dw.data(), dst.data(), dgt.data(), dsx.data(), dsy.data(), dsmt.data() }; }
-    void bind(const float *const *w, const float *const *sx, const float *const *sy) override { all_w = w; all_sx = sx; all_sy = sy; }
-    void bind_state(const float *const *st) override { all_st = st; }
-    void bind_gt(const float *const *gt) override { all_gt = gt; }
-    void bind_smooth_t(const float *const *smt) override { all_smt = smt; }
     int chunk_planes(int C) const override { return C * T; }
     PcgGeo work_geo(const MixedGeo &mg) const override
     {
@@ -104,22 +96,10 @@ struct VolumeOperator : PcgOperator {
         tall.ny = mg.ny * T;
         return pcg_geo(tall);
     }
-    void begin(int i0, int m) override
-    {
-        dw.assign(all_w + i0, all_w + i0 + m);
-        dst.assign(all_st + i0, all_st + i0 + m);
-        dgt.assign(all_gt + i0, all_gt + i0 + m);
-        // (a call without link arrays: whatever the front end holds in their place is not looked at)
-        if (links) { dsx.assign(all_sx + i0, all_sx + i0 + m); dsy.assign(all_sy + i0, all_sy + i0 + m); }
-        else { dsx.assign((size_t)m, nullptr); dsy.assign((size_t)m, nullptr); }
-        if (tlinks) dsmt.assign(all_smt + i0, all_smt + i0 + m);
-        else dsmt.assign((size_t)m, nullptr);
-        kept = 0;
-        wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0;
-    }
+    void begin() override { wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0; }
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {
-        launch_volume_stats(g, wg, geo(wg), dj.data(), arrays(), m, d_stats, s);
+        launch_volume_stats(g, wg, geo(wg), dj.data(), ds.data(), m, d_stats, s);
     }
     const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
     {
@@ -137,12 +117,6 @@ struct VolumeOperator : PcgOperator {
         if (job[7] != 0.0 || !std::isfinite(job[5])) return "a spatial link weight live in the region is not finite or not > 0";
         if (job[10] != 0.0 || !std::isfinite(job[8])) return "a live temporal link weight is not finite or not > 0";
         if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link in space or time and no data weight";
-        dw[kept] = dw[k];
-        dgt[kept] = dgt[k];
-        dsx[kept] = dsx[k];
-        dsy[kept] = dsy[k];
-        dsmt[kept] = dsmt[k];
-        dst[kept++] = dst[k];
         wsum += job[0];
         unknowns += job[2];
         uksum += job[3];
@@ -180,7 +154,7 @@ struct VolumeOperator : PcgOperator {
         for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
             if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
         if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
-        launch_volume_setup(g, wg, geo(wg), lap, dj.data(), arrays(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, bb,
+        launch_volume_setup(g, wg, geo(wg), lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, bb,
                             I->stream);
         return SC_OK;
     }
@@ -212,7 +186,7 @@ struct VolumeOperator : PcgOperator {
     }
     void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override
     {
-        launch_volume_out(g, wg, geo(wg), dj.data(), dst.data(), mv, U, s);
+        launch_volume_out(g, wg, geo(wg), dj.data(), ds.data(), mv, U, s);
     }
 };
 

@@ -77,19 +77,19 @@ struct WeightedCoef {
 
 } // namespace
 
-void launch_weighted_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, int m, double *stats,
+void launch_weighted_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats,
                            hipStream_t s)
 {
-    for_job_tables<WeightedJobs>(m, [&](WeightedJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; }, [&](const WeightedJobs &t, int i0, int cnt) {
+    for_side_tables<WeightedJobs>(jobs, sides, m, [&](const WeightedJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_w_stats, dim3((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, t,
                            stats + (size_t)g.C * i0 * PCG_PARTS * 2);
     });
 }
 
-void launch_weighted_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, int m, float *R,
+void launch_weighted_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R,
                            float *Wc, double *bb, hipStream_t s)
 {
-    for_job_tables<WeightedJobs>(m, [&](WeightedJobs &t, int i, int k) { t.j[i] = jobs[k]; t.w[i] = w[k]; }, [&](const WeightedJobs &t, int i0, int cnt) {
+    for_side_tables<WeightedJobs>(jobs, sides, m, [&](const WeightedJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t p0 = (size_t)g.C * i0;
         if (lap) hipLaunchKernelGGL(k_w_setup<true>, grid, dim3(WL), 0, s, g, wg, t, R + p0 * wg.stride, Wc + p0 * wg.stride, bb + p0 * PCG_PARTS);

@@ -2,7 +2,8 @@
 //     minimise sum w (u - d)^2 + sum |grad u - g|^2,   i.e.   (A - W) u = div g - W d,   W = diag(w), w >= 0,
 // A the 5-point operator of sc_hip_poisson under every border kind (a Dirichlet frame, SC_POISSON_NEUMANN, SC_POISSON_FREE_*,
 // SC_POISSON_PERIODIC_*).  A call: the conjugate-gradient families' entry code (sc_pcg.h: pcg_begin, then pcg_host_call or
-// pcg_device_call around the float32 families' front end and pcg_run) with this file's validation and its WeightedOperator:
+// pcg_device_call around the float32 families' front end and pcg_run) with this file's validation and its WeightedOperator, which
+// reads the chunk's jobs and their weights where the driver keeps them (PcgOperator::dj, ds):
 //   statistics  per plane the sum of w and the number of weights that are negative or not finite (k_w_stats); a job with such a weight,
 //               or -- without any Dirichlet line -- with a channel of zero weight, gets SC_ERR_BAD_ARG and leaves.
 //   constant    lambda-bar = precond_lambda, or the mean of w over the unknowns that remain: the preconditioner is M = A - lambda-bar.
@@ -31,24 +32,19 @@ constexpr const char *FP64_WHY = "a weighted solve with SC_FLAG_FFT_FP64: at mos
 // This family's operator: A - W on the work planes, W = the weights copied onto S.w.
 struct WeightedOperator final : PcgOperator {
     Instance *I;
-    const float *const *all_w = nullptr;
     float plam;
-    std::vector<const float *> dw;
-    int kept = 0;
     double wsum = 0.0;
     WeightedOperator(Instance *I_, float plam_) : PcgOperator(2), I(I_), plam(plam_) {}
-    void bind(const float *const *w, const float *const *, const float *const *) override { all_w = w; }
-    void begin(int i0, int m) override { dw.assign(all_w + i0, all_w + i0 + m); kept = 0; wsum = 0.0; }
+    void begin() override { wsum = 0.0; }
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {
-        launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
+        launch_weighted_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
     }
     const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
     {
         double job_sum;
         const char *why = judge_weights(g, st, parts, no_dirichlet, nullptr, job_sum);
         if (why) return why;
-        dw[kept++] = dw[k];
         wsum += job_sum;
         return nullptr;
     }
@@ -61,7 +57,7 @@ struct WeightedOperator final : PcgOperator {
     {
         const int rc = ensure(I, I->pcg->w, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
         if (rc) return rc;
-        launch_weighted_setup(g, wg, lap, dj.data(), dw.data(), mv, R, (float *)I->pcg->w.p, bb, I->stream);
+        launch_weighted_setup(g, wg, lap, dj.data(), ds.data(), mv, R, (float *)I->pcg->w.p, bb, I->stream);
         return SC_OK;
     }
     void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override

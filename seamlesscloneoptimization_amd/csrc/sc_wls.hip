@@ -144,19 +144,18 @@ double wls_live_links(const PcgGeo &wg)
     return per_row * wg.ny + per_col * wg.nx;
 }
 
-void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, double *stats, hipStream_t s)
+void launch_wls_stats(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, double *stats, hipStream_t s)
 {
-    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
+    for_side_tables<WlsJobs>(jobs, sides, m, [&](const WlsJobs &t, int i0, int cnt) {
         hipLaunchKernelGGL(k_wls_stats, dim3((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt)), dim3(WL), 0, s, g, wg, t,
                            stats + (size_t)g.C * i0 * PCG_PARTS * WLS_STATS);
     });
 }
 
-void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const float *const *w, const float *const *sx,
-                      const float *const *sy, int m, float *R, float *E, float *S, float *Dg, double *bb, hipStream_t s)
+void launch_wls_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides, int m, float *R, float *E,
+                      float *S, float *Dg, double *bb, hipStream_t s)
 {
-    for_wls_tables(jobs, w, sx, sy, m, [&](const WlsJobs &t, int i0, int cnt) {
+    for_side_tables<WlsJobs>(jobs, sides, m, [&](const WlsJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride;
         double *b = bb + (size_t)g.C * i0 * PCG_PARTS;

@@ -12,6 +12,7 @@
 //               precond_lambda, or their mean weight.  The preconditioner is M = s-bar (A - w-bar / s-bar): the direct solve with
 //               lam = w-bar / s-bar, and the factor 1 / s-bar once, on u0.
 //   set-up      b and the planes E, S, Dg (k_wls_setup; without link weights its constant-link form);   operator   k_pcg_op with WlsCoef.
+// The jobs' arrays are the driver's (PcgOperator::dj, ds: it moves the jobs that stay to the front); the operator keeps the running sums.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cmath>
@@ -38,20 +39,16 @@ constexpr const char *FP64_WHY = "a WLS solve with SC_FLAG_FFT_FP64: at most 409
 
 namespace sc {
 
-void WlsOperator::begin(int i0, int m)
+void WlsOperator::begin()
 {
-    dw.assign(all_w + i0, all_w + i0 + m);
-    dsx.assign(all_sx + i0, all_sx + i0 + m);
-    dsy.assign(all_sy + i0, all_sy + i0 + m);
-    kept = 0;
     wsum = ssum = 0.0;
     unit_links = !links;
 }
 
 void WlsOperator::stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s)
 {
-    if (links) launch_wls_stats(g, wg, dj.data(), dw.data(), dsx.data(), dsy.data(), m, d_stats, s);
-    else launch_weighted_stats(g, wg, dj.data(), dw.data(), m, d_stats, s);
+    if (links) launch_wls_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
+    else launch_weighted_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
 }
 
 const char *WlsOperator::judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet)
@@ -66,9 +63,6 @@ const char *WlsOperator::judge(const PoissonGeo &g, int k, const double *st, int
     const char *why = judge_weights(g, st, parts, no_dirichlet,
                                     bad_s || !std::isfinite(job_s) ? "a live link weight is not finite or not > 0" : nullptr, job_w);
     if (why) return why;
-    dw[kept] = dw[k];
-    dsx[kept] = dsx[k];
-    dsy[kept++] = dsy[k];
     wsum += job_w;
     ssum += job_s;
     return nullptr;
@@ -93,8 +87,7 @@ int WlsOperator::setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, 
         const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
         if (rc) return rc;
     }
-    launch_wls_setup(g, wg, lap, dj.data(), dw.data(), dsx.data(), dsy.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb,
-                     I->stream);
+    launch_wls_setup(g, wg, lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb, I->stream);
     return SC_OK;
 }
 

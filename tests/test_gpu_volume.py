@@ -8,7 +8,8 @@
    answer; two runs of one call give the same bytes.
 3. the device call: HWC and CHW with padded rows, a frame stride that leaves a gap, guard frames around every array, NaN in every
    element the header says is not read: nothing but the named elements of out is written, out may be data.
-4. batches: two volumes solved in one call beside a third with a bad state element (SC_ERR_BAD_ARG, its out untouched); nine 3-channel
+4. batches: two volumes solved in one call beside a third with a bad state element, in front of them, between them and behind them
+   (SC_ERR_BAD_ARG, its out untouched); nine 3-channel
    volumes of 8 frames in two chunks.
 5. the plane limit: 64 frames x 3 channels runs, one frame more is refused.
 6. the pin judgement is the volume's: keyframes pin the frames between them; without them the channel is refused.
@@ -243,14 +244,16 @@ def _check_members(probs, outs, chunks, form):
             assert_copied_bits(probs[k], outs[k])
 
 
-@pytest.mark.parametrize("bad", [3.0, float("nan")])
-def test_a_bad_state_fails_its_volume_only(inst, bad):
+@pytest.mark.parametrize("bad,at", [pytest.param(bad, at, id=f"{bad}" if at == 2 else f"{bad}-at{at}") for at in (2, 0, 1) for bad in (3.0, float("nan"))])
+def test_a_bad_state_fails_its_volume_only(inst, bad, at):
+    """at: the refused volume's place in the batch -- in front of a volume that stays, that one and all its arrays move up together"""
     probs = [vb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
-    probs[2]["state"][2, 5, 7, 1] = bad
+    probs[at]["state"][2, 5, 7, 1] = bad
+    stay = [k for k in range(3) if k != at]
     rc, codes, outs = _run_batch(inst, probs, "gt")
-    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_OK, capi.SC_OK, capi.SC_ERR_BAD_ARG], (rc, codes)
-    assert (outs[2] == SENTINEL).all(), "a refused volume must not be written"
-    _check_members(probs, outs, [[0, 1]], "gt")
+    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_ERR_BAD_ARG if k == at else capi.SC_OK for k in range(3)], (rc, codes)
+    assert (outs[at] == SENTINEL).all(), "a refused volume must not be written"
+    _check_members(probs, outs, [stay], "gt")
 
 
 def test_nine_volumes_run_in_two_chunks(inst):

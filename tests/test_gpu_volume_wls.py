@@ -12,7 +12,8 @@ space and time and, if asked, periodic time.
 3. periodic time: the answer of an input rolled along the frames is the rolled answer.
 4. the device call: HWC and CHW with padded rows, a frame stride that leaves a gap, guard frames around every array (gt and smooth_t at
    `frames` frames), NaN in every element the header says is not read: nothing but the named elements of out is written, out may be data.
-5. batches: two volumes beside a third with a bad live link (SC_ERR_BAD_ARG, its out untouched), the same values at dead links, a
+5. batches: two volumes beside a third with a bad live link, behind them and in front of them (SC_ERR_BAD_ARG, its out untouched), the
+   same values at dead links, a
    volume with link arrays where the first has none, nine 3-channel volumes of 8 frames in two chunks.
 6. wls_filter_video, interpolate_constraints_video, make_loop and volume_wls_solve against the float64 solve."""
 from __future__ import annotations
@@ -297,33 +298,46 @@ def _check_members(probs, outs, chunks, form, yardsticks=None):
 
 @functools.lru_cache(maxsize=None)
 def _trio():
-    """three volumes with all link arrays under periodic time, and the first two's yardsticks with the means of a chunk of those two"""
-    probs = [wb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", "xyt", "periodic", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
-    means = wb.chunk_means(probs[:2])
-    return probs, [wb.Yardstick(p, "gt", means=means) for p in probs[:2]]
+    """three volumes with all link arrays under periodic time"""
+    return [wb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", "xyt", "periodic", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
+
+
+@functools.lru_cache(maxsize=None)
+def _pair_yardsticks(at):
+    """the yardsticks of the two volumes of the trio that stay when volume `at` is refused, with the means of a chunk of those two: {k: yardstick}"""
+    probs = _trio()
+    stay = [k for k in range(3) if k != at]
+    means = wb.chunk_means([probs[k] for k in stay])
+    return {k: wb.Yardstick(probs[k], "gt", means=means) for k in stay}
 
 
 def _link_element(p, name, live):
-    """the index of a live (or dead) element of a link array of the third volume, away from the array's ends"""
+    """the index of a live (or dead) element of a link array of volume p, away from the array's ends"""
     lx, _, lt = vw.live_links(p["sides"], p["periodic"], p["tper"], p["state"])
     where = np.argwhere((lx if name == "sx" else lt) == live)
     return tuple(where[len(where) // 2])
 
 
-@pytest.mark.parametrize("bad", [0.0, -1.0, float("nan"), float("inf")], ids=["zero", "negative", "nan", "inf"])
-@pytest.mark.parametrize("name", ["sx", "smt"])
-def test_a_bad_live_link_fails_its_volume_only(inst, name, bad):
-    probs, yardsticks = _trio()
-    third = dict(probs[2], **{name: probs[2][name].copy()})
-    third[name][_link_element(third, name, True)] = bad
-    rc, codes, outs = _run_batch(inst, [probs[0], probs[1], third], "gt")
-    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_OK, capi.SC_OK, capi.SC_ERR_BAD_ARG], (rc, codes)
-    assert (outs[2] == SENTINEL).all(), "a refused volume must not be written"
-    _check_members(probs, outs, [[0, 1]], "gt", yardsticks)
+_BAD_LINKS = [pytest.param(name, bad, at, id=f"{name}-{tag}" if at == 2 else f"{name}-{tag}-at{at}") for at in (2, 0)
+              for tag, bad in (("zero", 0.0), ("negative", -1.0), ("nan", float("nan")), ("inf", float("inf"))) for name in ("sx", "smt")]
+
+
+@pytest.mark.parametrize("name,bad,at", _BAD_LINKS)
+def test_a_bad_live_link_fails_its_volume_only(inst, name, bad, at):
+    """at: the refused volume's place in the batch -- in front, the two that stay and all their arrays move up together (the first volume
+    still carries every array: the call does)"""
+    probs = list(_trio())
+    probs[at] = dict(probs[at], **{name: probs[at][name].copy()})
+    probs[at][name][_link_element(probs[at], name, True)] = bad
+    stay = [k for k in range(3) if k != at]
+    rc, codes, outs = _run_batch(inst, probs, "gt")
+    assert rc == capi.SC_ERR_BAD_ARG and codes == [capi.SC_ERR_BAD_ARG if k == at else capi.SC_OK for k in range(3)], (rc, codes)
+    assert (outs[at] == SENTINEL).all(), "a refused volume must not be written"
+    _check_members(probs, outs, [stay], "gt", _pair_yardsticks(at))
 
 
 def test_bad_values_at_dead_links_are_accepted(inst):
-    probs, _ = _trio()
+    probs = _trio()
     third = dict(probs[2], sx=probs[2]["sx"].copy(), smt=probs[2]["smt"].copy())
     for name in ("sx", "smt"):
         dead = np.argwhere((vw.live_links(third["sides"], third["periodic"], third["tper"], third["state"])[0 if name == "sx" else 2]) == False)  # noqa: E712
@@ -338,7 +352,7 @@ def test_bad_values_at_dead_links_are_accepted(inst):
 @pytest.mark.parametrize("extra", ["xy", "t", "x"])
 def test_link_arrays_where_the_first_volume_has_none_are_refused(inst, extra):
     """the first volume decides, for smooth_x / smooth_y and for smooth_t separately; exactly one of smooth_x / smooth_y is refused too"""
-    probs, _ = _trio()
+    probs = _trio()
     if extra == "x":
         first, other = probs[0], dict(probs[1], sy=None)
     else:

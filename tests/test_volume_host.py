@@ -237,6 +237,21 @@ def test_inputs_are_fair_and_the_reference_iteration_meets_the_exact_solve(i):
     assert volume_np.folded_rhs(*vb.np_args(q, form), bq, np.float32).tobytes() == volume_np.folded_rhs(*vb.np_args(p, form), b, np.float32).tobytes()
 
 
+@pytest.mark.parametrize("at", [0, 1, 2])
+def test_the_batch_trio_is_fair_whichever_volume_leaves(at):
+    """tests/test_gpu_volume.py refuses volume `at` of this trio: the two that stay, under the w-bar of a chunk of those two, converge in
+    the reference iteration to a finite exact solve"""
+    probs = [vb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
+    stay = [probs[k] for k in range(3) if k != at]
+    m = [volume_np.precond_mean(p["sides"], p["periodic"], p["state"], p["weight"], p["tau"]) for p in stay]
+    lam = sum(w * n for w, n in m) / sum(n for _, n in m)
+    for p in stay:
+        y = vb.Yardstick(p, "gt", precond_lambda=lam)
+        assert np.isfinite(y.want).all() and np.isfinite([y.err32, y.res32]).all()
+        assert y.rel32 <= 1e-5 and y.iters32 < vb.MAX_ITERS, (y.rel32, y.iters32)
+        assert not volume_np.unpinned_components(p["sides"], p["periodic"], p["state"], p["weight"]).any()
+
+
 def test_unpinned_components_goes_through_time():
     st = np.zeros((3, 4, 5, 1), np.float32)
     assert volume_np.unpinned_components("lrtb", "", st).all()                      # nothing pins anything

@@ -250,3 +250,17 @@ def test_inputs_are_fair(i):
         if a is not None:
             assert 0.1 <= a.min() and a.max() <= 10.0 and a.max() / a.min() > 30
     assert y.err32 < 1e-3
+
+
+@pytest.mark.parametrize("at", [0, 2])
+def test_the_batch_trio_is_fair_whichever_volume_leaves(at):
+    """tests/test_gpu_volume_wls.py refuses volume `at` of this trio: the two that stay, under the means of a chunk of those two, converge
+    in the reference iteration to a finite exact solve"""
+    probs = [wb.make_input("free_lt", 23, 17, 3, 4, 1.0, pat, "constant", "xyt", "periodic", seed=20 + k) for k, pat in enumerate(("hole", "scatter", "keyframes"))]
+    stay = [probs[k] for k in range(3) if k != at]
+    means = wb.chunk_means(stay)
+    for p in stay:
+        y = wb.Yardstick(p, "gt", means=means)
+        assert np.isfinite(y.want).all() and np.isfinite([y.err32, y.res32]).all()
+        assert y.rel32 <= 1e-5 and y.iters32 < wb.MAX_ITERS, (y.rel32, y.iters32)
+        assert not vw.unpinned_components(p["sides"], p["periodic"], p["tper"], p["state"], p["weight"]).any()

@@ -13,7 +13,7 @@
            along y (Neumann and free left + top; scatter and split): one line per input, then the worst ratios and the worst values where
            the reference iteration took no step -- what RES_FACTOR / RES_FLOOR / ERR_FACTOR / ERR_FLOOR are set from.  Written to
            --lengths-out (default profiles/region_lengths.txt).
---time     GPU: iterations and stream time (sc_run_info.ms_solve of host calls, median of --calls after --warmup) at 1024^2 x 3 channels
+--time     GPU: iterations, stream time (sc_run_info.ms_solve) and wall time of host calls (medians of --calls after --warmup) at 1024^2 x 3 channels
            and 2048^2 x 1 channel, Neumann borders, unit links, zero guidance: an ellipse of unknowns, 1 in 30 known pixels scattered
            plus an excluded blob, a known frame plus an excluded blob, and the membrane fill of a hole 200 pixels across.  Beside each
            the only other route to the same answer: the soft constraint w = 1e4 at the pinned pixels through sc_hip_weighted (through
@@ -30,6 +30,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -157,15 +158,18 @@ def timing(capi, inst, path, calls, warmup):
             for case in ("ellipse", "scatter", "frame_blob", "inpaint200"):
                 st = big_state(case, H, W, C)
                 unk = st == 0
-                ms, its = [], []
+                ms, wall, its = [], [], []
                 for k in range(warmup + calls):
+                    t0 = time.perf_counter()
                     out = inst.region(data, st, lap=lap, neumann=True, allow_not_converged=True)
+                    t1 = time.perf_counter()
                     info = inst.info()
                     if k >= warmup:
                         ms.append(info.ms_solve)
+                        wall.append(1e3 * (t1 - t0))
                         its.append(info.sweeps)
                 rec = dict(probe="region", size=[W, H, C], case=case, unknown=int(unk.sum()), iterations=its[-1], converged=int(info.converged),
-                           rel_residual=float(info.rel_residual), ms_solve=med(ms))
+                           rel_residual=float(info.rel_residual), ms_solve=med(ms), ms_wall=med(wall))
                 # the soft route: w = 1e4 at the pinned pixels
                 w = np.where(st == 1, np.float32(1e4), np.float32(0)).astype(np.float32)
                 soft_ms, soft = [], None

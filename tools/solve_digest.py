@@ -12,6 +12,10 @@ multiple of a float4 group, two column groups, several bands and element-wise se
 zero-weight plane, a budget that ends the solve.  The robust lines (three rounds, every one run; float32 and double preconditioner,
 with and without base links, three pairs of exponents; guidance form only) follow a case's weighted and WLS lines and hash
 robust_trace()'s energies and iterations behind out; one more batch of theirs has links on job 1 alone, which the call refuses.
+Behind them the families whose jobs carry a state array (region, volume, WLS volume; four frames): 17 x 23 pixels of three channels
+and 16 x 5 of one (under a frame 14 unknown columns, no multiple of a float4), guidance and Laplacian forms, with and without weight
+and link arrays, free and periodic time, and per family two device batches -- three jobs of which job 0 has a bad state element (the
+two that stay and every array of theirs move to the front) and 17 one-channel jobs (two job tables).  --sides: these lines alone.
 
     python tools/solve_digest.py --pcg [--root DIR] > profiles/pcg_digest_<build>.txt
 """
@@ -26,6 +30,7 @@ import numpy as np
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--pcg", action="store_true")
+ap.add_argument("--sides", action="store_true")
 ARGS = ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.root))
 
@@ -211,6 +216,128 @@ def pcg_batch(inst, name, sides, periodic, W, H, C, m, refuse=None, stray=None):
                  np.array([j.rc for j in jobs], np.int32).tobytes())
 
 
+# ---- the families with a state array: region, volume (T frames, temporal links), WLS volume (per-link weights, periodic time)
+SIDE_FIELDS = ("gx", "gy", "gt", "lap", "data", "state", "weight", "sx", "sy", "smt", "boundary")
+SIDE_T = 4
+
+
+def side_arrays(name, k, T, H, W, C):
+    """one problem's float32 T x H x W x C arrays by SIDE_FIELDS' names (gt and smt at T frames: free time reads T - 1 of them).  state:
+    even k a hole of UNKNOWN pixels in KNOWN ones that moves with the frame and with k, one corner OUTSIDE; odd k the three states
+    scattered.  Every array differs from job to job."""
+    rng = np.random.default_rng([zlib.crc32(name.encode()), k])
+    u = lambda lo, hi: rng.uniform(lo, hi, (T, H, W, C)).astype(np.float32)    # noqa: E731
+    e = lambda lo: np.exp(u(np.log(lo), 0)).astype(np.float32)                 # noqa: E731
+    a = dict(gx=u(-2, 2), gy=u(-2, 2), gt=u(-2, 2), lap=u(-4, 4), data=u(-50, 300), weight=e(1e-2), sx=e(0.05), sy=e(0.05), smt=e(0.05),
+             boundary=u(-100, 400))
+    if k % 2:
+        st = rng.choice(np.array([0, 1, 2], np.float32), (T, H, W), p=(0.6, 0.3, 0.1))
+    else:
+        st = np.ones((T, H, W), np.float32)
+        for t in range(T):
+            st[t, H // 4:H - H // 4, W // 4:W - W // 4] = 0
+            st[t] = np.roll(st[t], (t + k) % 3 - 1, axis=1)
+        st[:, :2, :3] = 2
+    a["state"] = np.ascontiguousarray(np.broadcast_to(st[:, :, :, None], (T, H, W, C)))
+    return a
+
+
+def side_forms(family):
+    """(lap?, weight?, spatial links?, temporal links?, periodic time?, tag) of a family's calls"""
+    for lap in (False, True):
+        for w in (False, True):
+            for xy, t, loop in {"region": ((False, False, False), (True, False, False)), "volume": ((False, False, False),),
+                                "volume_wls": ((False, False, False), (False, False, True), (True, False, False), (False, True, True), (True, True, False),
+                                               (True, True, True))}[family]:
+                    yield lap, w, xy, t, loop, "%s %s %s %s%s %s" % (family, "lap" if lap else "gxy", "w" if w else "-", "xy" if xy else "--",
+                                                                     "t" if t else "-", "loop" if loop else "free")
+
+
+def side_single(inst, name, sides, periodic, W, H, C):
+    """host calls of the three families in every form"""
+    configure(inst, 0)
+    for family in ("region", "volume", "volume_wls"):
+        T = 1 if family == "region" else SIDE_T
+        for lap, w, xy, t, loop, tag in side_forms(family):
+            a = side_arrays(name, 0, T, H, W, C)
+            n = T if loop else T - 1
+            kw = dict(lap=a["lap"]) if lap else dict(gx=a["gx"], gy=a["gy"]) if family == "region" else dict(gx=a["gx"], gy=a["gy"], gt=a["gt"][:n])
+            if xy:
+                kw.update(smooth_x=a["sx"], smooth_y=a["sy"])
+            if t:
+                kw.update(smooth_t=a["smt"][:n])
+            if family == "volume_wls":
+                kw.update(loop=loop)
+            if family == "region":
+                kw = {key: v[0] for key, v in kw.items()}
+            pick = (lambda x: x[0]) if family == "region" else (lambda x: x)
+            try:
+                out, refused = getattr(inst, family)(pick(a["data"]), pick(a["state"]), pick(a["weight"]) if w else None, boundary=pick(a["boundary"]),
+                                                     free_sides=sides, periodic=periodic, **kw), False
+            except capi.SeamlessCloneError as err:           # (a problem the statistics refuse: the refusal is the result)
+                out, refused = np.frombuffer(str(err).encode(), np.uint8), True
+            pcg_emit(inst, name, sides, periodic, tag, np.ascontiguousarray(out).tobytes(), refused)
+
+
+def side_batch(inst, name, sides, periodic, W, H, C, m, refuse=None):
+    """m jobs in one device call of each family, with every array the family has and with none but state; refuse: the job with a state
+    element 3 (its statistics refuse it).  The digest covers every job's out and the jobs' codes."""
+    configure(inst, 0)
+    nf = len(SIDE_FIELDS)
+    for family in ("region", "volume", "volume_wls"):
+        T = 1 if family == "region" else SIDE_T
+        n, slot = T * W * H * C, (T * W * H * C + 63) // 64 * 64
+        layout = capi.PoissonLayout(W, H, C, C, W * C, 1)
+        for lap, w, xy, t, loop, tag in side_forms(family):
+            if lap == w or xy != (w and family != "volume") or t != (w and family == "volume_wls"):      # every array the family has in the guidance form, none in the Laplacian one
+                continue
+            host = np.zeros((m, nf + 1, slot), np.float32)           # SIDE_FIELDS, out
+            for k in range(m):
+                a = side_arrays(name, k, T, H, W, C)
+                if k == refuse:
+                    a["state"][T // 2, H // 2, W // 2, 0] = 3.0
+                host[k, :nf, :n] = [a[f].reshape(-1) for f in SIDE_FIELDS]
+            dev = inst.malloc(host.nbytes)
+            try:
+                inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, host.ctypes.data, host.nbytes))
+                at = lambda k, f: dev + 4 * slot * ((nf + 1) * k + (SIDE_FIELDS + ("out",)).index(f))      # noqa: E731
+                jobs = getattr(capi.Instance, "make_%s_jobs" % family)(m)
+                for k, j in enumerate(jobs):
+                    if lap:
+                        j.lap = at(k, "lap")
+                    else:
+                        j.gx, j.gy = at(k, "gx"), at(k, "gy")
+                        if family != "region":
+                            j.gt = at(k, "gt")
+                    j.data, j.state, j.boundary, j.out = at(k, "data"), at(k, "state"), at(k, "boundary"), at(k, "out")
+                    if w:
+                        j.weight = at(k, "weight")
+                    if xy:
+                        j.smooth_x, j.smooth_y = at(k, "sx"), at(k, "sy")
+                    if t:
+                        j.smooth_t = at(k, "smt")
+                kind = (capi.SC_POISSON_LAPLACIAN if lap else capi.SC_POISSON_GUIDANCE) | capi.free_side_bits(sides) | capi.periodic_bits(periodic)
+                if family == "region":
+                    inst.region_device(capi.RegionParams(kind, 0.0, 0, 0.0, 0.0), layout, jobs, allow_job_errors=True)
+                elif family == "volume":
+                    inst.volume_device(capi.VolumeParams(kind, T, W * H * C, 0.7, 0.0, 0, 0.0), layout, jobs, allow_job_errors=True)
+                else:
+                    inst.volume_wls_device(capi.VolumeWlsParams(kind, T, W * H * C, 0.7, 1 if loop else 0, 0.0, 0, 0.0, 0.0, 0.0), layout, jobs,
+                                           allow_job_errors=True)
+                got = inst.from_device(dev, host.shape, np.float32)
+            finally:
+                inst.free(dev)
+            pcg_emit(inst, name, sides, periodic, "x%d %s" % (m, tag), got[:, nf, :n].tobytes() + np.array([j.rc for j in jobs], np.int32).tobytes())
+
+
+def side_main(inst):
+    for sides in ("", "lt"):
+        side_single(inst, "sides 17x23 C3", sides, "", 17, 23, 3)
+    side_single(inst, "sides tail 16x5 C1", "", "", 16, 5, 1)
+    side_batch(inst, "sides refused 17x23 C3", "lt", "", 17, 23, 3, 3, refuse=0)
+    side_batch(inst, "sides tables 16x5 C1", "lt", "", 16, 5, 1, 17)
+
+
 def pcg_main(inst):
     for fx, px in AXES:                                              # every pair of axis kinds
         for fy, py in AXES:
@@ -232,11 +359,14 @@ def pcg_main(inst):
     pcg_single(inst, "zero-weight plane 37x29 C3", "t", "x", 37, 29, 3, zero_weight_plane=True)
     for sides, periodic in (("", ""), ("lrtb", "")):
         pcg_single(inst, "budget 40x130 C3", sides, periodic, 40, 130, 3, max_iters=3, allow_not_converged=True)
+    side_main(inst)
 
 
 def main():
     inst = capi.Instance(0)
     try:
+        if ARGS.sides:
+            return side_main(inst)
         if ARGS.pcg:
             return pcg_main(inst)
         for f in range(16):                                          # every border combination; all-Dirichlet is the untouched control

@@ -8,7 +8,7 @@
            of time rotating): one line per input, then the worst ratios and the worst values where the reference iteration took no
            step -- what RES_FACTOR / RES_FLOOR / ERR_FACTOR / ERR_FLOOR are set from.  Written to --lengths-out (default
            profiles/volume_wls_lengths.txt).
---time     GPU: iterations and stream time (sc_run_info.ms_solve of host calls, median of --calls after --warmup) at 512^2 x 3 channels x
+--time     GPU: iterations, stream time (sc_run_info.ms_solve) and wall time of host calls (medians of --calls after --warmup) at 512^2 x 3 channels x
            16 frames and 1024^2 x 1 channel x 32 frames, Neumann borders, zero guidance, tau = 1, 1 in 30 known pixels scattered around
            an excluded tube: unit links (sc_hip_volume's problem through this call), wls_filter_video's links from the data's own
            log-luminance (their contrast is reported), links log-uniform over two decades, each under free and under periodic time.
@@ -24,6 +24,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -130,16 +131,19 @@ def timing(capi, inst, path, calls, warmup):
             for kind in ("unit", "wls_filter", "two_decades"):
                 for loop in (False, True):
                     sx, sy, smt, contrast = big_links(kind, data, loop)
-                    ms, its = [], []
+                    ms, wall, its = [], [], []
                     for k in range(warmup + calls):
+                        t0 = time.perf_counter()
                         inst.volume_wls(data, st, None, sx, sy, smt, lap=lap, tau=1.0, loop=loop, neumann=True, allow_not_converged=True)
+                        t1 = time.perf_counter()
                         info = inst.info()
                         if k >= warmup:
                             ms.append(info.ms_solve)
+                            wall.append(1e3 * (t1 - t0))
                             its.append(info.sweeps)
                     rec = dict(probe="volume_wls", size=[W, H, C, T], tau=1.0, links=kind, contrast=contrast, time="periodic" if loop else "free",
                                unknown=int((st == 0).sum()), iterations=its[-1], converged=int(info.converged), rel_residual=float(info.rel_residual),
-                               ms_solve=float(np.median(ms)))
+                               ms_solve=float(np.median(ms)), ms_wall=float(np.median(wall)))
                     f.write(json.dumps(rec) + "\n")
                     f.flush()
                     print(json.dumps(rec), flush=True)
