@@ -148,6 +148,15 @@ SC_API int sc_hip_bytes_writer(void *instance);
  * ranges. */
 SC_API int sc_hip_coarse_tile_plan(const int *facts, int *plan);
 
+/* Host only, nothing is launched: the tiling of the work planes a conjugate-gradient call (sc_hip_weighted, _wls, _robust, _region,
+ * _volume, _volume_wls) would run with on images of cols x rows pixels under the border word `kind` (a base kind with its SC_POISSON_NEUMANN,
+ * SC_POISSON_FREE_* or SC_POISSON_PERIODIC_* bits, as the calls take it); frames: a volume call's (its frames' unknowns stacked along
+ * y), 1: not a volume.  The functions the calls themselves ask (csrc/sc_pcg.h: PcgOperator::work_geo).
+ * plan = { nx, ny (the unknowns of a work plane), x0, y0 (the first unknown's pixel), cg (column groups of 256 columns), bands, rows
+ * (per band; cg * bands partial sums per plane), eparts (segments of the element-wise launches), egroups (float4 groups of a plane),
+ * stride (floats between planes) }.  Returns 0, or the code the calls' checks give this kind and size. */
+SC_API int sc_hip_pcg_plan(int cols, int rows, int kind, int frames, long long plan[10]);
+
 /* Host only, nothing is launched: the level-0 launches of a fused multigrid solve (csrc/sc_multigrid.cpp: fused_next, the function the solve
  * itself asks) for facts[12] = pre, post (1 or 2), budget (max_sweeps, 1..64), tol > 0, out_wanted (the splice is armed, no tol, no
  * SC_FLAG_KEEP_FIELD, V(2,2)), q16 (the field starts as 16-bit fixed point), u_half (the initial field is float16), level 1 composed,

@@ -434,6 +434,8 @@ def load():
     L.sc_hip_cycle0_form.restype = C.c_int
     L.sc_hip_coarse_tile_plan.argtypes = [i32p, i32p]
     L.sc_hip_coarse_tile_plan.restype = C.c_int
+    L.sc_hip_pcg_plan.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong)]
+    L.sc_hip_pcg_plan.restype = C.c_int
     L.sc_hip_fused_schedule.argtypes = [i32p, i32p, C.c_int, i32p, C.c_int]
     L.sc_hip_fused_schedule.restype = C.c_int
     L.sc_hip_restore_spans.argtypes = [C.c_longlong] + [C.c_int] * 5 + [C.POINTER(C.c_longlong), C.c_int]
@@ -1725,6 +1727,19 @@ def coarse_tile_plan(W, H, C_, useful, halo, rows, size_class=False, unpacked=Fa
         raise SeamlessCloneError(rc, "coarse_tile_plan")
     t = out[4:].reshape(n, 130)
     return tuple(int(v) for v in head), (t[:, 0], t[:, 1], t[:, 2::2], t[:, 3::2])
+
+
+PCG_PLAN = ("nx", "ny", "x0", "y0", "cg", "bands", "rows", "eparts", "egroups", "stride")
+
+
+def pcg_plan(cols, rows, kind, frames=1):
+    """Host-only: the tiling of the work planes a conjugate-gradient call (weighted, WLS, robust, region; frames > 1: a volume call)
+    runs with on cols x rows pixels under the border word `kind` (sc_hip_pcg_plan): a dict of PCG_PLAN."""
+    out = (C.c_longlong * len(PCG_PLAN))()
+    rc = load().sc_hip_pcg_plan(int(cols), int(rows), int(kind), int(frames), out)
+    if rc != 0:
+        raise SeamlessCloneError(rc, "pcg_plan")
+    return dict(zip(PCG_PLAN, (int(v) for v in out)))
 
 
 FUSED_FACTS = ("pre", "post", "budget", "tol", "out_wanted", "q16", "u_half", "composed", "separate_restrict", "early_kind", "bytes_form", "small")

@@ -24,6 +24,7 @@
 //  10. a job's side arrays (SideArrays; sc_instance.h, sc_pcg.h): for_side_tables fills every family's table, 20 jobs as 16 + 4, each
 //      slot with exactly its table's members of the matching record; float_intake pairs every array of a job it takes in with that job
 //      and stores NULL for what the call does not carry.
+//  11. sc_hip_pcg_plan: the work planes' tiling over a walk of sizes, borders and frame counts, its invariants, its refusals.
 // Exit code 0 = clean (a sanitizer report aborts with its own).
 #include "../../include/seamlessclone_hip_testing.h"
 #include "sc_pcg.h"
@@ -632,6 +633,27 @@ int main()
             const SideArrays &a = v.side[0];
             if (a.w || a.sx || a.sy || a.gt || a.smt || a.st != fake(0, 3)) return fail("float_intake: an array the call does not carry must be NULL");
         }
+    }
+    // 11: the conjugate-gradient families' tiling: every part and segment has a slot, no band is empty, the bands cover the rows
+    {
+        const int kinds[] = { SC_POISSON_LAPLACIAN, SC_POISSON_LAPLACIAN | SC_POISSON_NEUMANN, SC_POISSON_GUIDANCE | SC_POISSON_FREE_LEFT | SC_POISSON_FREE_TOP,
+                              SC_POISSON_GUIDANCE | SC_POISSON_PERIODIC_X, SC_POISSON_LAPLACIAN | SC_POISSON_PERIODIC_X | SC_POISSON_PERIODIC_Y };
+        for (int kind : kinds)
+            for (int frames : { 1, 2, 17, 64, SC_POISSON_MAX_PLANES })
+                for (int cols = 3; cols <= 2105; cols += (cols < 20 ? 1 : 83))
+                    for (int rows = 3; rows <= 2205; rows += (rows < 70 ? 1 : 61)) {
+                        long long p[10];
+                        if (sc_hip_pcg_plan(cols, rows, kind, frames, p) != SC_OK) return fail("pcg_plan");
+                        const long long nx = p[0], ny = p[1], cg = p[4], bands = p[5], rows_per = p[6], eparts = p[7], egroups = p[8], stride = p[9];
+                        if (nx < 1 || nx > cols || ny < 1 || ny > (long long)rows * frames || ny % frames) return fail("pcg_plan: the unknown block");
+                        if (cg != (nx + 255) / 256 || cg * bands > sc::PCG_PARTS || bands * rows_per < ny || (bands - 1) * rows_per >= ny) return fail("pcg_plan: the bands");
+                        if (eparts < 1 || eparts > sc::PCG_PARTS || egroups != (nx * ny + 3) / 4 || eparts * ((egroups + eparts - 1) / eparts) < egroups) return fail("pcg_plan: the segments");
+                        if (stride % 64 || stride < nx * ny) return fail("pcg_plan: the stride");
+                    }
+        long long p[10];
+        if (sc_hip_pcg_plan(2, 7, SC_POISSON_LAPLACIAN, 1, p) != SC_ERR_BAD_SIZE || sc_hip_pcg_plan(33, 47, SC_POISSON_NEUMANN, 1, p) != SC_ERR_BAD_ARG ||
+            sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, 0, p) != SC_ERR_BAD_ARG || sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, SC_POISSON_MAX_PLANES + 1, p) != SC_ERR_BAD_ARG ||
+            sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, 1, nullptr) != SC_ERR_BAD_ARG) return fail("pcg_plan (refusals)");
     }
     printf("sanitize_main: clean\n");
     return 0;

@@ -1,7 +1,7 @@
 // sc_hooks.cpp -- the test and measurement hooks of include/seamlessclone_hip_testing.h: the host-only self test, the stage hooks
 // (mask stage, right-hand side), the solver hooks on caller-supplied fields and the kernel timings bench.py reads.  No clone path
 // calls into this file.
-#include "sc_instance.h"
+#include "sc_pcg.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -518,6 +518,20 @@ int sc_hip_coarse_tile_plan(const int *facts, int *plan)
             o[0] = tl.by; o[1] = tl.lps; o[2 + 2 * lane] = tl.c; o[3 + 2 * lane] = tl.x;
         }
     }
+    return SC_OK;
+}
+
+int sc_hip_pcg_plan(int cols, int rows, int kind, int frames, long long plan[10])
+{
+    if (!plan || frames < 1 || frames > SC_POISSON_MAX_PLANES) return SC_ERR_BAD_ARG;
+    const sc_poisson_layout l{ cols, rows, 1, 1, (long long)cols, (long long)cols * rows };
+    const int rc = family_validate(&kind, &l, nullptr, "at most 8192 unknowns (pixels - 2) per side", nullptr);
+    if (rc) return rc;
+    const int k = poisson_norm_kind(kind);
+    const MixedGeo mg = poisson_mixed_geo(poisson_free_sides(k), cols, rows, poisson_periodic(k));      // pcg_chunk_begin's
+    const PcgGeo wg = frames > 1 ? volume_work_geo(mg, frames) : pcg_geo(mg);                            // PcgOperator::work_geo's two forms
+    const long long out[10] = { wg.nx, wg.ny, wg.x0, wg.y0, wg.cg, wg.bands, wg.rows, wg.eparts, wg.egroups, wg.stride };
+    std::copy(out, out + 10, plan);
     return SC_OK;
 }
 

@@ -272,6 +272,13 @@ struct VolumeJobs {
     }
 };
 struct VolumeGeo { int T, ny; long long fs; float tau; int periodic; };      // ny: a frame's rows of unknowns; periodic: time wraps
+// the work planes' geometry of a volume of T frames of mg's unknowns (VolumeOperator::work_geo; sc_hip_pcg_plan)
+inline PcgGeo volume_work_geo(const MixedGeo &mg, int T)
+{
+    MixedGeo tall = mg;
+    tall.ny = mg.ny * T;
+    return pcg_geo(tall);
+}
 constexpr int VOLUME_STATS = 11, VOLUME_STATS_PLAIN = 5;
 // stats[(plane * PCG_PARTS + i) * VOLUME_STATS + ..] = the part's sum of w over the UNKNOWN pixels | how many of those w are invalid |
 // its UNKNOWN pixels | the sum of its UNKNOWN - KNOWN links' weights, spatial and temporal | its state elements that are not 0, 1 or 2 |

@@ -90,12 +90,7 @@ struct VolumeOperator : PcgOperator {
           ptau(p->precond_tau), periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
     VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau, periodic ? 1 : 0 }; }
     int chunk_planes(int C) const override { return C * T; }
-    PcgGeo work_geo(const MixedGeo &mg) const override
-    {
-        MixedGeo tall = mg;
-        tall.ny = mg.ny * T;
-        return pcg_geo(tall);
-    }
+    PcgGeo work_geo(const MixedGeo &mg) const override { return volume_work_geo(mg, T); }
     void begin() override { wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0; }
     void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
     {

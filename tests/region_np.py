@@ -14,10 +14,11 @@ at UNKNOWN pixels without a weight, or boundary off its Dirichlet lines (the GPU
 folded_rhs(dtype=float32) is the library's b to the letter of seamlessclone_hip.h: (a - b) + (c - d) of separately rounded products
 s * g (or lap), then - w * d, then the Dirichlet lines' s * boundary west, north, east, south, then the KNOWN neighbours' s * data west,
 north, east, south, each a rounded product subtracted in turn; 0 at every pixel of the block that is not UNKNOWN.  solve_exact()
-assembles the matrix over the UNKNOWN pixels only, link by link, in float64 and solves it with LAPACK.  pcg_f32() is the library's
-iteration: on the whole unknown block, with coefficient planes that are 0 at every pixel that is not UNKNOWN, preconditioned by the
-rectangle's direct solve (weighted_np._precond) -- the yardstick of tests/region_bounds.py.  unpinned_components() finds the UNKNOWN
-components that nothing holds (the library does not)."""
+assembles the matrix over the UNKNOWN pixels only, link by link, in float64 and solves it with LAPACK (above wls_np.DENSE_LIMIT UNKNOWN
+pixels: the same entries sparse, factored by scipy).  pcg_f32() is the library's iteration: on the whole unknown block, with coefficient
+planes that are 0 at every pixel that is not UNKNOWN, preconditioned by the rectangle's direct solve (weighted_np._precond) -- the
+yardstick of tests/region_bounds.py; pcg(dtype=float64) is its float64 twin, the yardstick of single iterates
+(tests/pcg_steps_bounds.py).  unpinned_components() finds the UNKNOWN components that nothing holds (the library does not)."""
 from __future__ import annotations
 
 import numpy as np
@@ -124,9 +125,11 @@ def _compose(sides, periodic, state, data, boundary, u_blk, dtype):
     return out
 
 
-def solve_exact(sides, periodic, state, weight, sx, sy, data, lap, boundary=None):
-    """float64 solution: the dense system over the UNKNOWN pixels only, assembled link by link (a link between two UNKNOWN pixels
-    enters both rows, a link to a KNOWN or Dirichlet pixel the diagonal of its UNKNOWN end only); data's shape, composed like out"""
+def solve_exact(sides, periodic, state, weight, sx, sy, data, lap, boundary=None, dense=None):
+    """float64 solution: the system over the UNKNOWN pixels only, assembled link by link (a link between two UNKNOWN pixels enters
+    both rows, a link to a KNOWN or Dirichlet pixel the diagonal of its UNKNOWN end only); data's shape, composed like out.  dense: None:
+    a dense matrix and LAPACK up to wls_np.DENSE_LIMIT UNKNOWN pixels per channel, above it the same entries sparse; True / False force
+    one of the two."""
     shape = np.asarray(data).shape
     k = kinds(sides, periodic, state)
     H, W, C = k.shape
@@ -143,20 +146,20 @@ def solve_exact(sides, periodic, state, weight, sx, sy, data, lap, boundary=None
             continue
         index = np.full((H, W), -1)
         index[unk] = np.arange(n)
-        M = np.zeros((n, n))
+        entries = []          # (row, column, value); an entry named twice counts twice
         if weight is not None:
-            M[np.arange(n), np.arange(n)] = -_hwc(np.asarray(weight, np.float32))[:, :, c][unk].astype(np.float64)
+            entries.append((np.arange(n), np.arange(n), -_hwc(np.asarray(weight, np.float32))[:, :, c][unk].astype(np.float64)))
         for live, s, axis in ((lx[:, :, c], sxf[:, :, c], 1), (ly[:, :, c], syf[:, :, c], 0)):
             ys, xs = np.nonzero(live)
             i, j = index[ys, xs], np.roll(index, -1, axis)[ys, xs]
             v = s[ys, xs].astype(np.float64)
             for a, b in ((i, j), (j, i)):
                 ok = a >= 0
-                np.add.at(M, (a[ok], a[ok]), -v[ok])
+                entries.append((a[ok], a[ok], -v[ok]))
                 both = ok & (b >= 0)
-                np.add.at(M, (a[both], b[both]), v[both])
+                entries.append((a[both], b[both], v[both]))
         sol = np.zeros((H, W))
-        sol[unk] = np.linalg.solve(M, g[:, :, c][unk[blk]])
+        sol[unk] = wls_np.solve_entries(entries, n, g[:, :, c][unk[blk]], dense if dense is not None else n <= wls_np.DENSE_LIMIT)
         u[:, :, c] = sol[blk]
     return _compose(sides, periodic, state, data, boundary, u, np.float64).reshape(shape)
 
@@ -203,46 +206,66 @@ def precond_means(sides, periodic, state, weight, sx, sy):
     return sbar, ((wsum + uk) / n if n else sbar), v.size, n
 
 
-def pcg_f32(sides, periodic, state, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None):
-    """The library's iteration in numpy, on the whole unknown block.  Returns (out, iterations, the worst channel's final ||r|| / ||b||)."""
+def pcg(sides, periodic, state, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None,
+        dtype=np.float32, keep=None):
+    """The library's iteration in numpy, on the whole unknown block; dtype float64: the same iteration on float64 vectors and
+    coefficient planes with the float64 direct solve (lam and the start's factor the same float32).  keep: a list that receives every iterate,
+    composed like out.  Returns (out, iterations, the worst channel's final ||r|| / ||b||)."""
     shape = np.asarray(data).shape
     k = kinds(sides, periodic, state)
     H, W, C = k.shape
     blk = unknowns(sides, periodic, H, W)
-    links, dg = _planes(sides, periodic, state, weight, sx, sy, np.float32)
+    links, dg = _planes(sides, periodic, state, weight, sx, sy, dtype)
     sbar, wbar, _, _ = precond_means(sides, periodic, state, weight, sx, sy)
     sbar = sbar if precond_smooth is None else float(np.float32(precond_smooth))
     wbar = wbar if precond_lambda is None else float(np.float32(precond_lambda))
     lam, scale = np.float32(wbar / sbar), np.float32(1.0 / sbar)
-    b = folded_rhs(sides, periodic, state, weight, sx, sy, data, lap, boundary, np.float32)
-    scratch = np.zeros((H, W, C), np.float32)
-    scratch, it, rel = pcg_np.pcg_f32(b, lambda p: wls_np.block_operator(links, dg, p),
-                                      lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C)), scale, tol, max_iters, scratch, blk)
-    return _compose(sides, periodic, state, data, boundary, scratch[blk], np.float32).reshape(shape), it, rel
+    b = folded_rhs(sides, periodic, state, weight, sx, sy, data, lap, boundary, dtype)
+    scratch = np.zeros((H, W, C), dtype)
+    us = []
+    scratch, it, rel = pcg_np.pcg(b, lambda p: wls_np.block_operator(links, dg, p),
+                                  lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C), dtype), dtype(scale), tol, max_iters, scratch, blk,
+                                  dtype, us)
+    if keep is not None:
+        keep += [_compose(sides, periodic, state, data, boundary, u, dtype).reshape(shape) for u in us]
+    return _compose(sides, periodic, state, data, boundary, scratch[blk], dtype).reshape(shape), it, rel
+
+
+def pcg_f32(sides, periodic, state, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None):
+    """pcg() in the library's arithmetic: float32 vectors, the float32 direct solve"""
+    return pcg(sides, periodic, state, weight, sx, sy, data, lap, boundary, tol, max_iters, precond_lambda, precond_smooth, np.float32)
 
 
 def unpinned_components(sides, periodic, state, weight=None):
     """boolean H x W x C: the UNKNOWN pixels of connected components (through links between UNKNOWN pixels) that have no KNOWN or
-    Dirichlet neighbour and no positive weight.  Label propagation: every pixel takes the smallest label among itself and its UNKNOWN
-    neighbours until nothing changes."""
+    Dirichlet neighbour and no positive weight.  Components: scipy.ndimage.label per channel (4-connected), and the labels that meet
+    across the wrap of a periodic axis joined."""
+    import scipy.ndimage
     k = kinds(sides, periodic, state)
     unk = k == UNKNOWN
-    big = k.size
-    label = np.where(unk, np.arange(k.size).reshape(k.shape), big)
-    while True:
-        new = label
-        for shift, axis in _SHIFTS:
-            new = np.minimum(new, _neighbour(label, shift, axis, periodic, big))
-        new = np.where(unk, new, big)
-        if np.array_equal(new, label):
-            break
-        label = new
     held = np.zeros(k.shape, bool)
     for shift, axis in _SHIFTS:
         q = _neighbour(k, shift, axis, periodic, OUTSIDE)
         held |= (q == KNOWN) | (q == DIRICHLET)
     if weight is not None:
         held |= np.where(unk, _hwc(np.asarray(weight, np.float32)), np.float32(0)) > 0
-    # (labels are global indices that include the channel: components of different channels never share one)
-    pinned = np.unique(label[unk & held])
-    return unk & ~np.isin(label, pinned)
+    out = np.zeros(k.shape, bool)
+    for c in range(k.shape[2]):
+        label, n = scipy.ndimage.label(unk[:, :, c])
+        root = np.arange(n + 1)
+
+        def find(i):
+            while root[i] != i:
+                root[i] = root[root[i]]
+                i = root[i]
+            return i
+        for name, first, last in (("x", label[:, 0], label[:, -1]), ("y", label[0], label[-1])):
+            if name in periodic:
+                for a, b in zip(first, last):
+                    if a and b:
+                        root[find(a)] = find(b)
+        root = np.array([find(i) for i in range(n + 1)])
+        pinned = np.zeros(n + 1, bool)
+        pinned[root[label[unk[:, :, c] & held[:, :, c]]]] = True
+        out[:, :, c] = unk[:, :, c] & ~pinned[root[label]]
+    return out

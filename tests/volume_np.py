@@ -242,30 +242,40 @@ def _compose(sides, periodic, state, data, boundary, u_blk, dtype):
     return np.stack([region_np._compose(sides, periodic, st[t], d[t], None if bd is None else bd[t], u_blk[t], dtype) for t in range(st.shape[0])])
 
 
-def pcg_f32(sides, periodic, state, weight, tau, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None):
-    """The library's iteration in numpy: one system per channel over all frames.  Returns (out, iterations, the worst channel's final
+def pcg(sides, periodic, state, weight, tau, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, dtype=np.float32, keep=None):
+    """The library's iteration in numpy: one system per channel over all frames; dtype float64: the same iteration on float64 vectors and
+    coefficient planes, the table along the frames unrounded and every mode's direct solve in float64 (the modes' shifts the same
+    float32).  keep: a list that receives every iterate, composed like out.  Returns (out, iterations, the worst channel's final
     ||r|| / ||b||)."""
     shape = np.asarray(data).shape
     k = kinds(sides, periodic, state)
     T, H, W, C = k.shape
-    links, dg = _planes(sides, periodic, state, weight, tau, np.float32)
+    links, dg = _planes(sides, periodic, state, weight, tau, dtype)
     wbar = precond_mean(sides, periodic, state, weight, tau)[0] if precond_lambda is None else float(np.float32(precond_lambda))
-    D = dct_table(T).astype(np.float32)
+    D = dct_table(T).astype(dtype)
     shifts = mode_shifts(T, wbar, tau)
-    b = folded_rhs(sides, periodic, state, weight, tau, data, lap, boundary, np.float32)
+    b = folded_rhs(sides, periodic, state, weight, tau, data, lap, boundary, dtype)
     _, ny, nx, _ = b.shape
     tall = lambda a: a.reshape(T * ny, nx, C)
     frames = lambda a: a.reshape(T, ny, nx, C)
 
     def precond(r):
         X = np.einsum("kt,tyxc->kyxc", D, frames(r))
-        Z = np.stack([weighted_np._precond(sides, periodic, shifts[m], X[m], (H, W, C)) for m in range(T)])
-        return tall(np.einsum("kt,kyxc->tyxc", D, Z).astype(np.float32))
+        Z = np.stack([weighted_np._precond(sides, periodic, shifts[m], X[m], (H, W, C), dtype) for m in range(T)])
+        return tall(np.einsum("kt,kyxc->tyxc", D, Z).astype(dtype))
 
-    scratch = np.zeros((T * ny, nx, C), np.float32)
-    scratch, it, rel = pcg_np.pcg_f32(tall(b), lambda p: tall(block_operator(links, dg, frames(p))), precond, None, tol, max_iters, scratch,
-                                      (slice(None), slice(None)))
-    return _compose(sides, periodic, state, data, boundary, frames(scratch), np.float32).reshape(shape), it, rel
+    scratch = np.zeros((T * ny, nx, C), dtype)
+    us = []
+    scratch, it, rel = pcg_np.pcg(tall(b), lambda p: tall(block_operator(links, dg, frames(p))), precond, None, tol, max_iters, scratch,
+                                  (slice(None), slice(None)), dtype, us)
+    if keep is not None:
+        keep += [_compose(sides, periodic, state, data, boundary, frames(u), dtype).reshape(shape) for u in us]
+    return _compose(sides, periodic, state, data, boundary, frames(scratch), dtype).reshape(shape), it, rel
+
+
+def pcg_f32(sides, periodic, state, weight, tau, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None):
+    """pcg() in the library's arithmetic: float32 vectors, table and direct solves"""
+    return pcg(sides, periodic, state, weight, tau, data, lap, boundary, tol, max_iters, precond_lambda, np.float32)
 
 
 def unpinned_components(sides, periodic, state, weight=None):

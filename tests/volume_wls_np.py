@@ -282,34 +282,44 @@ def solve_exact(args, boundary=None, dense=None):
     return volume_np._compose(sides, periodic, state, data, boundary, u, np.float64).reshape(shape)
 
 
-def pcg_f32(args, boundary=None, tol=1e-5, max_iters=400, means=None):
+def pcg(args, boundary=None, tol=1e-5, max_iters=400, means=None, dtype=np.float32, keep=None):
     """The library's iteration in numpy: one system per channel over all frames, preconditioned by the table product along the frames
     (time_table in float32), the float32 direct solve of every mode with mode_shifts' shift, and the transposed product; the start is
     M^-1 b times 1 / s-bar.  means: (s-bar, tau-bar, w-bar) where they are not the input's own (a member of a batch: the chunk's).
+    dtype float64: the same iteration on float64 vectors and coefficient planes, the table unrounded and every mode's direct solve in
+    float64 (the modes' shifts and the start's factor the same float32).  keep: a list that receives every iterate, composed like out.
     Returns (out, iterations, the worst channel's final ||r|| / ||b||)."""
     sides, periodic, tper, state, weight, sx, sy, smt, tau, data, lap = args
     shape = np.asarray(data).shape
     k = kinds(sides, periodic, state)
     T, H, W, C = k.shape
-    links, dg = _planes(sides, periodic, tper, state, weight, sx, sy, smt, tau, np.float32)
+    links, dg = _planes(sides, periodic, tper, state, weight, sx, sy, smt, tau, dtype)
     sbar, tbar, wbar = precond_means(sides, periodic, tper, state, weight, sx, sy, smt, tau)[:3] if means is None else means
-    D = time_table(T, tper).astype(np.float32)
+    D = time_table(T, tper).astype(dtype)
     shifts = mode_shifts(T, wbar, tbar, sbar, tper)
     scale = np.float32(1.0 / sbar)
-    b = folded_rhs(*args, boundary, np.float32)
+    b = folded_rhs(*args, boundary, dtype)
     _, ny, nx, _ = b.shape
     tall = lambda a: a.reshape(T * ny, nx, C)
     frames = lambda a: a.reshape(T, ny, nx, C)
 
     def precond(r):
         X = np.einsum("kt,tyxc->kyxc", D, frames(r))
-        Z = np.stack([weighted_np._precond(sides, periodic, shifts[m], X[m], (H, W, C)) for m in range(T)])
-        return tall(np.einsum("kt,kyxc->tyxc", D, Z).astype(np.float32))
+        Z = np.stack([weighted_np._precond(sides, periodic, shifts[m], X[m], (H, W, C), dtype) for m in range(T)])
+        return tall(np.einsum("kt,kyxc->tyxc", D, Z).astype(dtype))
 
-    scratch = np.zeros((T * ny, nx, C), np.float32)
-    scratch, it, rel = pcg_np.pcg_f32(tall(b), lambda p: tall(block_operator(links, dg, frames(p))), precond, None if scale == 1 else scale, tol,
-                                      max_iters, scratch, (slice(None), slice(None)))
-    return volume_np._compose(sides, periodic, state, data, boundary, frames(scratch), np.float32).reshape(shape), it, rel
+    scratch = np.zeros((T * ny, nx, C), dtype)
+    us = []
+    scratch, it, rel = pcg_np.pcg(tall(b), lambda p: tall(block_operator(links, dg, frames(p))), precond, None if scale == 1 else dtype(scale), tol,
+                                  max_iters, scratch, (slice(None), slice(None)), dtype, us)
+    if keep is not None:
+        keep += [volume_np._compose(sides, periodic, state, data, boundary, frames(u), dtype).reshape(shape) for u in us]
+    return volume_np._compose(sides, periodic, state, data, boundary, frames(scratch), dtype).reshape(shape), it, rel
+
+
+def pcg_f32(args, boundary=None, tol=1e-5, max_iters=400, means=None):
+    """pcg() in the library's arithmetic: float32 vectors, table and direct solves -- the yardstick of tests/volume_wls_bounds.py"""
+    return pcg(args, boundary, tol, max_iters, means, np.float32)
 
 
 def unpinned_components(sides, periodic, tper, state, weight=None):

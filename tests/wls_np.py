@@ -8,10 +8,11 @@ read: links with at least one unknown end.  Nothing here reads any other element
 
 divergence() and folded_rhs(dtype=float32) are the library's float32 right-hand side to the letter of seamlessclone_hip.h: every
 product s * g rounded on its own, (a - b) + (c - d), then - w * d (one multiply, one subtract), then the Dirichlet terms s * boundary
-subtracted west, north, east, south.  operator() / residual() apply the stencil in float64.  solve_exact() assembles L densely in
-float64 from the links, entry by entry, and solves with LAPACK.  pcg_f32() is the library's iteration: float32 vectors, float64 dot
-products, preconditioned by direct_np.solve_f32 with lam = w-bar / s-bar, started from u0 = (1 / s-bar) (A - lam)^-1 b -- the
-yardstick of tests/wls_bounds.py.  Arrays are H x W x C (H x W accepted)."""
+subtracted west, north, east, south.  operator() / residual() apply the stencil in float64.  solve_exact() assembles L in float64 from
+the links, entry by entry, and solves with LAPACK (above DENSE_LIMIT unknowns: the same entries sparse, factored by scipy).  pcg_f32()
+is the library's iteration: float32 vectors, float64 dot products, preconditioned by direct_np.solve_f32 with lam = w-bar / s-bar,
+started from u0 = (1 / s-bar) (A - lam)^-1 b -- the yardstick of tests/wls_bounds.py; pcg(dtype=float64) is its float64 twin, the
+yardstick of single iterates (tests/pcg_steps_bounds.py).  Arrays are H x W x C (H x W accepted)."""
 from __future__ import annotations
 
 import numpy as np
@@ -94,9 +95,26 @@ def residual(sides, periodic, weight, sx, sy, u, data, lap):
     return operator(sides, periodic, weight, sx, sy, u) - rhs(sides, periodic, weight, data, lap).astype(np.float64)
 
 
-def solve_exact(sides, periodic, weight, sx, sy, data, lap, boundary=None):
+DENSE_LIMIT = weighted_np.DENSE_LIMIT
+
+
+def solve_entries(entries, n, g, dense):
+    """the float64 solution of M x = g, M the n x n matrix of the entries [(rows, columns, values)] (an entry named twice counts
+    twice): dense through LAPACK, or sparse through weighted_np.sparse_solve"""
+    rows, cols, vals = (np.concatenate([e[i] for e in entries]) for i in range(3))
+    if dense:
+        M = np.zeros((n, n))
+        np.add.at(M, (rows, cols), vals)
+        return np.linalg.solve(M, g)
+    import scipy.sparse
+    return weighted_np.sparse_solve(scipy.sparse.coo_matrix((vals, (rows, cols)), shape=(n, n)), g)
+
+
+def solve_exact(sides, periodic, weight, sx, sy, data, lap, boundary=None, dense=None):
     """float64 solution of L u = rhs: boundary's values on the Dirichlet lines, the solution at the unknowns; data's shape.  The matrix
-    is assembled link by link: a link between two unknowns enters both rows, a link to a Dirichlet pixel the diagonal only."""
+    is assembled link by link: a link between two unknowns enters both rows, a link to a Dirichlet pixel the diagonal only.  dense:
+    None: a dense matrix and LAPACK up to DENSE_LIMIT unknowns, above it the same entries sparse (weighted_np.sparse_solve); True / False
+    force one of the two."""
     shape = np.asarray(data).shape
     w = _hwc(np.asarray(weight, np.float32)).astype(np.float64)
     sxf, syf = _hwc(np.asarray(sx, np.float32)), _hwc(np.asarray(sy, np.float32))
@@ -109,19 +127,20 @@ def solve_exact(sides, periodic, weight, sx, sy, data, lap, boundary=None):
     n = int(unk.sum())
     g = folded_rhs(sides, periodic, weight, sx, sy, data, lap, boundary)
     out = _hwc(np.asarray(boundary, np.float64)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C))
+    dense = dense if dense is not None else n <= DENSE_LIMIT
     for c in range(C):
-        M = np.zeros((n, n))
-        M[np.arange(n), np.arange(n)] = -w[blk][:, :, c].reshape(-1)
+        # the entries (row, column, value); an entry named twice counts twice
+        entries = [(np.arange(n), np.arange(n), -w[blk][:, :, c].reshape(-1))]
         for live, s, axis in ((lx, sxf, 1), (ly, syf, 0)):
             ys, xs = np.nonzero(live)
             i, j = index[ys, xs], np.roll(index, -1, axis)[ys, xs]
             v = s[ys, xs, c].astype(np.float64)
             for a, b in ((i, j), (j, i)):
                 ok = a >= 0
-                np.add.at(M, (a[ok], a[ok]), -v[ok])
+                entries.append((a[ok], a[ok], -v[ok]))
                 both = ok & (b >= 0)
-                np.add.at(M, (a[both], b[both]), v[both])
-        out[blk[0], blk[1], c] = np.linalg.solve(M, g[:, :, c].reshape(-1)).reshape(g.shape[:2])
+                entries.append((a[both], b[both], v[both]))
+        out[blk[0], blk[1], c] = solve_entries(entries, n, g[:, :, c].reshape(-1), dense).reshape(g.shape[:2])
     return out.reshape(shape)
 
 
@@ -146,24 +165,35 @@ def block_operator(links, dg, u):
     return ((west * np.roll(u, 1, 1) + east * np.roll(u, -1, 1)) + (north * np.roll(u, 1, 0) + south * np.roll(u, -1, 0))) - dg * u
 
 
-def pcg_f32(sides, periodic, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None):
-    """The library's iteration in numpy.  Returns (u of data's shape with boundary's values on the Dirichlet lines, iterations, the
-    worst channel's final ||r|| / ||b||)."""
+def pcg(sides, periodic, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None,
+        dtype=np.float32, keep=None):
+    """The library's iteration in numpy; dtype float64: the same iteration on float64 vectors, links and diagonal with the float64
+    direct solve (lam and the start's factor the same float32).  keep: a list that receives every iterate, composed like the return
+    value's first element.  Returns (u of data's shape with boundary's values on the Dirichlet
+    lines, iterations, the worst channel's final ||r|| / ||b||)."""
     shape = np.asarray(data).shape
     w_full = _hwc(np.asarray(weight, np.float32))
     H, W, C = w_full.shape
     blk = unknowns(sides, periodic, H, W)
     unk = ~direct_np.dirichlet_mask(sides, periodic, H, W)
-    full = _links(sides, periodic, sx, sy, np.float32)
-    dg = (((full[0] + full[1]) + (full[2] + full[3])) + w_full)[blk]
+    full = _links(sides, periodic, sx, sy, dtype)
+    dg = (((full[0] + full[1]) + (full[2] + full[3])) + w_full.astype(dtype))[blk]
     # the links between two unknowns: the neighbour in that direction (with wrap) is an unknown too
-    links = tuple(np.where(np.roll(unk, shift, axis)[:, :, None], f, np.float32(0))[blk]
+    links = tuple(np.where(np.roll(unk, shift, axis)[:, :, None], f, dtype(0))[blk]
                   for f, shift, axis in zip(full, (1, -1, 1, -1), (1, 1, 0, 0)))
     sbar = mean_link(sides, periodic, sx, sy) if precond_smooth is None else float(np.float32(precond_smooth))
     wbar = mean_weight(sides, periodic, weight) if precond_lambda is None else float(np.float32(precond_lambda))
     lam, scale = np.float32(wbar / sbar), np.float32(1.0 / sbar)
-    b = folded_rhs(sides, periodic, weight, sx, sy, data, lap, boundary, np.float32)
-    out = _hwc(np.asarray(boundary, np.float32)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C), np.float32)
-    out, it, rel = pcg_np.pcg_f32(b, lambda p: block_operator(links, dg, p), lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C)),
-                                  scale, tol, max_iters, out, blk)
+    b = folded_rhs(sides, periodic, weight, sx, sy, data, lap, boundary, dtype)
+    out = _hwc(np.asarray(boundary, dtype)).copy() if has_dirichlet(sides, periodic) else np.zeros((H, W, C), dtype)
+    us = []
+    out, it, rel = pcg_np.pcg(b, lambda p: block_operator(links, dg, p), lambda r: weighted_np._precond(sides, periodic, lam, r, (H, W, C), dtype),
+                              dtype(scale), tol, max_iters, out, blk, dtype, us)
+    if keep is not None:
+        keep += [weighted_np._placed(out, blk, u).reshape(shape) for u in us]
     return out.reshape(shape), it, rel
+
+
+def pcg_f32(sides, periodic, weight, sx, sy, data, lap, boundary=None, tol=1e-5, max_iters=400, precond_lambda=None, precond_smooth=None):
+    """pcg() in the library's arithmetic: float32 vectors, the float32 direct solve"""
+    return pcg(sides, periodic, weight, sx, sy, data, lap, boundary, tol, max_iters, precond_lambda, precond_smooth, np.float32)
