@@ -40,6 +40,13 @@ extern "C" {
                                             (k_cycle0 with C0_OUT3).  Same bytes                                                         */
 #define SC_FORCE_INTERLEAVED_OUT 32      /*   ... and that form wherever it exists (a same-size group of up to 16 members on the default
                                             path), whatever the threshold says: tests and A/B runs                                       */
+#define SC_LEGACY_U0_PLANES     64        /*   multigrid, same-size groups: the pre-process always stores the destination's 8-bit ROI values as
+                                            float16 planes and the first level-0 launch reads those.  Default: from members x level-0 tiles =
+                                            SC_IN3_MIN_TILES on (sc_instance.h) the pre-process stores no initial field and one workgroup of
+                                            the first launch serves the three channels of a member's tile from the destination's own bytes
+                                            (k_cycle0 with C0_IN3).  Same values, same bytes                                              */
+#define SC_FORCE_U0_BYTES       128       /*   ... and that form wherever it exists (a same-size group of up to 16 members on the default
+                                            path), whatever the threshold says: tests and A/B runs                                       */
 #define SC_FLAG_KEEP_FIELD     (1 << 7)  /* sc_hip_run*: keep the solution field on the device (sc_hip_field_store,
                                             _residual, _finish after a run): the last multigrid cycle writes the field
                                             and a post-process launch reads it.  Default: that cycle writes the output
@@ -127,7 +134,8 @@ SC_API int sc_hip_time_tail_phases(void *instance, unsigned long long *cycles11)
 SC_API int sc_hip_selftest_host(void);
 
 /* host only (needs no GPU, launches nothing): the instantiation k_cycle0<T, .., PRO, .., TAG> (csrc/sc_cycle0.hip; TAG: the C0_* bits of
- * csrc/sc_common.h) the level-0 multigrid launcher picks for facts[13] = sweeps, prolong, f_half, u_half, q16_in, q16_out, final_cycle,
+ * csrc/sc_common.h) the level-0 multigrid launcher picks for facts[13] = sweeps, prolong, f_half, u_half, q16_in, q16_out, final_cycle (u_half + 2: the initial field
+ * is read from the members' destination bytes instead, in_bytes),
  * out_bytes (+ 2: as interleaved bytes into the members' destinations, out_interleaved), composed, l1_half, timing, bands (pointer given), rag (size class).  form[3] receives T, PRO, TAG; returns 0, or -1: no such
  * form, nothing would be launched.  facts == NULL: form receives entry `index` of the table of instantiated forms, its length is returned. */
 SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
@@ -136,6 +144,17 @@ SC_API int sc_hip_cycle0_form(const int *facts, int index, int form[3]);
  * it): bit 0 a splice launch behind planar bytes, bit 1 the judged launch itself, interleaved (k_cycle0 with C0_OUT3: same-size groups,
  * see SC_LEGACY_SPLICE_LAUNCH).  SC_ERR_BAD_ARG for a bad handle. */
 SC_API int sc_hip_bytes_writer(void *instance);
+/* Where the first level-0 launches of the fused multigrid solves on this instance read their initial field since this was last asked
+ * (asking clears it): bit 0 the float16 planes the pre-process stored, bit 1 the members' destination bytes (k_cycle0 with C0_IN3,
+ * see SC_LEGACY_U0_PLANES), bit 2 float16 planes that a safety-net launch filled because the pre-process had stored none and the
+ * solve had no bytes form.  SC_ERR_BAD_ARG for a bad handle. */
+SC_API int sc_hip_u0_reader(void *instance);
+/* Host only, nothing is launched: what the 64 lanes of a wave whose lane 0 serves column xw fetch of the interleaved ROI row of W
+ * pixels at `row` for that form, by the rule the kernel runs (csrc/sc_u0_bytes.h), read from host memory here.
+ * out[64][16], per lane = { offset of the first of four dwords from `row`, re-alignment shift, bit k set: dword k was read (the others
+ * count as 0), 1: the wave takes the unguarded 16-byte load, then per channel 0, 1, 2 the four values of columns xw + 4 lane .. + 3
+ * (clamped as the kernel clamps) }. */
+SC_API int sc_hip_u0_bytes_fetch(const uint8_t *row, int W, int xw, int *out);
 
 /* Host only, nothing is launched: the column tiling of a coarse-level multigrid launch and what the lanes of its workgroups serve.
  * facts = { W, H, C (field width and height, ring included; planes), useful width, halo (columns a tile owns; halo columns per side: 232, 12

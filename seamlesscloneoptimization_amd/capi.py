@@ -61,6 +61,8 @@ SC_FLAG_LEGACY_PATHS = 1 << 6      # run the superseded launch forms named in So
 SC_LEGACY_SEPARATE_RESTRICT, SC_LEGACY_BOTTOM_F32, SC_LEGACY_SEPARATE_TAIL, SC_LEGACY_UNPACKED_TILES = 1, 2, 4, 8
 SC_LEGACY_SPLICE_LAUNCH = 16       # same-size groups: the judged cycle leaves planar bytes and a splice launch interleaves them, always
 SC_FORCE_INTERLEAVED_OUT = 32      # ... the judged launch writes the interleaved bytes itself wherever that form exists, whatever the threshold
+SC_LEGACY_U0_PLANES = 64           # same-size groups: the pre-process stores the float16 initial field and the first level-0 launch reads it, always
+SC_FORCE_U0_BYTES = 128            # ... the first launch reads the destinations' bytes wherever that form exists, whatever the threshold
 SC_FLAG_KEEP_FIELD = 1 << 7
 SC_FLAG_FFT_FP64 = 1 << 8
 SC_FLAG_OPENCV_GREY_MASK = 1 << 9
@@ -392,6 +394,10 @@ def load():
     L.sc_hip_field_solve.restype = C.c_int
     L.sc_hip_bytes_writer.argtypes = [C.c_void_p]
     L.sc_hip_bytes_writer.restype = C.c_int
+    L.sc_hip_u0_reader.argtypes = [C.c_void_p]
+    L.sc_hip_u0_reader.restype = C.c_int
+    L.sc_hip_u0_bytes_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p]
+    L.sc_hip_u0_bytes_fetch.restype = C.c_int
     L.sc_hip_field_shape.argtypes = [C.c_void_p, i32p]
     L.sc_hip_field_shape.restype = C.c_int
     L.sc_hip_field_store.argtypes = [C.c_void_p, f32p, C.c_size_t]
@@ -1482,6 +1488,11 @@ class Instance:
         """Who wrote the judged cycles' bytes since the last call of this (which clears it): bit 0 a splice launch, bit 1 the judged launch itself, interleaved."""
         return int(self.L.sc_hip_bytes_writer(self.h))
 
+    def u0_reader(self):
+        """Where the first level-0 launches read their initial field since the last call of this (which clears it): bit 0 float16 planes,
+        bit 1 the destinations' bytes, bit 2 planes a safety-net launch filled."""
+        return int(self.L.sc_hip_u0_reader(self.h))
+
     def field_shape(self):
         whc = np.zeros(3, np.int32)
         self._check(self.L.sc_hip_field_shape(self.h, whc.ctypes.data_as(i32p)))
@@ -1702,11 +1713,24 @@ def cycle0_form(**facts):
     (CYCLE0_FACTS; those left out are 0 / false), or -1 where the library has no such form (csrc/sc_cycle0.hip)."""
     if facts.pop("out_interleaved", 0):      # travels as bit 1 of out_bytes (sc_hip_cycle0_form)
         facts["out_bytes"] = int(bool(facts.get("out_bytes", 0))) | 2
+    if facts.pop("in_bytes", 0):             # ... and as bit 1 of u_half
+        facts["u_half"] = int(bool(facts.get("u_half", 0))) | 2
     f = (C.c_int * len(CYCLE0_FACTS))(*[int(facts.pop(k, 0)) for k in CYCLE0_FACTS])
     if facts:
         raise TypeError("cycle0_form: no such fact: %s" % sorted(facts))
     out = (C.c_int * 3)()
     return tuple(out) if load().sc_hip_cycle0_form(f, 0, out) == 0 else -1
+
+
+def u0_bytes_fetch(buf, offset, W, xw):
+    """Host-only: what the first launch that reads destination bytes fetches for the 64 lanes of a wave whose lane 0 serves column xw, of
+    one ROI row (csrc/sc_u0_bytes.h): the row starts `offset` bytes into the uint8 array `buf`.  Returns an int32 array [64, 16]:
+    offset of the first dword from the row, shift, mask of dwords read, unguarded, then the four values of each of the three channels."""
+    out = np.empty((64, 16), np.int32)
+    rc = load().sc_hip_u0_bytes_fetch(C.c_void_p(buf.ctypes.data + offset), W, xw, out.ctypes.data_as(i32p))
+    if rc:
+        raise ValueError("sc_hip_u0_bytes_fetch: %d" % rc)
+    return out
 
 
 def coarse_tile_plan(W, H, C_, useful, halo, rows, size_class=False, unpacked=False, lanes=False):

@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -654,6 +655,34 @@ int main()
         if (sc_hip_pcg_plan(2, 7, SC_POISSON_LAPLACIAN, 1, p) != SC_ERR_BAD_SIZE || sc_hip_pcg_plan(33, 47, SC_POISSON_NEUMANN, 1, p) != SC_ERR_BAD_ARG ||
             sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, 0, p) != SC_ERR_BAD_ARG || sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, SC_POISSON_MAX_PLANES + 1, p) != SC_ERR_BAD_ARG ||
             sc_hip_pcg_plan(33, 47, SC_POISSON_LAPLACIAN, 1, nullptr) != SC_ERR_BAD_ARG) return fail("pcg_plan (refusals)");
+    }
+    // 12: the first level-0 launch that reads a group's destination bytes (sc_u0_bytes.h): the row sits in an allocation that ends 3
+    // bytes behind it and starts 4 + its misalignment before it -- the farthest the rule may read -- so a fetch beyond is this program's to find
+    {
+        std::vector<int> out(64 * 16);
+        for (int W = 3; W <= 600; ++W)
+            for (int al = 0; al < 4; ++al) {
+                const size_t lead = 4 + (size_t)al;
+                std::unique_ptr<uint8_t[]> buf(new uint8_t[lead + 3 * (size_t)W + 3]);
+                uint8_t *base = buf.get();
+                if (((uintptr_t)base & 3) != 0) return fail("u0_bytes: allocation alignment");
+                uint8_t *row = base + lead;
+                for (size_t i = 0; i < lead + 3 * (size_t)W + 3; ++i) base[i] = (uint8_t)(i * 37u + (unsigned)W);
+                const int nbx = (W + 231) / 232;
+                for (int bx : { 0, nbx / 2, nbx - 1 }) {
+                    const int xw = bx * 232 - 12;
+                    if (sc_hip_u0_bytes_fetch(row, W, xw, out.data()) != SC_OK) return fail("u0_bytes_fetch");
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int *o = &out[16 * lane];
+                        const int x = std::min(std::max(xw + 4 * lane, 0), W);
+                        for (int k = 0; k < 4; ++k) {
+                            if ((o[2] >> k & 1) && !(o[0] + 4 * k + 3 >= 0 && o[0] + 4 * k < 3 * W)) return fail("u0_bytes: a dword outside the row was read");
+                            for (int ci = 0; ci < 3; ++ci)
+                                if (o[4 + 4 * ci + k] != (x + k < W ? (int)row[3 * (x + k) + ci] : 0)) return fail("u0_bytes: value");
+                        }
+                    }
+                }
+            }
     }
     printf("sanitize_main: clean\n");
     return 0;

@@ -213,7 +213,7 @@ int setup_fields(Instance *I, int W, int H, int C)
     I->F = make_field(I->d_F.p, W, H, C);
     I->result_in_U1 = false;
     I->f_half = false;        // whoever fills F next says what it holds
-    I->u_half = false;
+    I->u_half = I->u0_bytes = false;
     if (!same) I->mg.clear(); // the multigrid hierarchy is rebuilt only when the ROI shape changes
     return SC_OK;
 }

@@ -103,7 +103,7 @@ int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &i
     I->guard = RectGuard();
     const SolveTarget to{ nullptr, 0, &ij };
     const int solve_rc = solve_step(I, to, [&]() -> int {
-        launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half, I->clone_mode);
+        launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half, I->clone_mode, !I->u0_bytes);
         SC_HIP(I, hipGetLastError());
         // a size class: the launches that build its per-call state (rag_begin_builds: 12 us of host time) go in HERE, while the device
         // erodes and pre-processes -- neither reads the table (member sizes travel in the ImageJobs); with all of rag_begin in front of

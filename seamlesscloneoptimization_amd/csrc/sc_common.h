@@ -204,7 +204,10 @@ __device__ __forceinline__ float lm_bilinear(const LmNodes &lm, int c, int x, in
 #endif
 void launch_postprocess(Field U, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), LmNodes lm = LmNodes(), AbortFlag ab = AbortFlag());
 // the same for a group (fields of 3n channels), one launch per 16 members
-void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode);
+// store_u0 = false (float16 fields only): the initial field is not stored -- the first level-0 launch reads the destinations' bytes (C0_IN3)
+void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode, bool store_u0 = true);
+// ... and the launch that stores those float16 planes after all (what the pre-process would have stored), for a solve whose first launch has no bytes form
+void launch_u0_half_group(const ImageJob *jobs, int n, Field U0, hipStream_t s);
 void launch_postprocess_group(Field U, const ImageJob *jobs, int n, hipStream_t s, LmNodes lm = LmNodes(), AbortFlag ab = AbortFlag());
 // splice of output bytes a multigrid launch left planar in Q's memory (launch_cycle0, out_bytes): interleave into the destination
 void launch_splice_planar(Field Q, uint8_t *body_org, int bstep, hipStream_t s, RectGuard guard = RectGuard(), AbortFlag ab = AbortFlag());
@@ -329,6 +332,7 @@ constexpr int C0_Q16_OUT  = 512;    // ... and so will Uout; a store that satura
 constexpr int C0_PACK_ROWS = 6;     // ... with bands of at most this many rows per lane
 constexpr int C0_PACK     = 2048;   // coarse levels only (GEN, ZEROIN): the last column tile of several planes in one workgroup, plane and column per lane (coarse_tile_plan)
 constexpr int C0_OUT3     = 4096;   // with C0_OUT | C0_FINAL, a same-size group: one workgroup per (member, tile) runs the member's three channels in turn and writes the tile's interleaved bytes into the destination itself (ImageJobs); nothing planar is stored, no splice launch follows
+constexpr int C0_IN3      = 8192;   // the first launch of a same-size group, member-major like C0_OUT3: the initial field is read from the members' destination bytes (ImageJob::body_src) instead of float16 planes; Uin carries geometry only
 constexpr int C0_RAG      = 1024;   // a SIZE CLASS (RagMember): strides and grid are the class's, all else the member's, read from rag[channel / 3]; tiles beyond its extent leave
 
 // One level-0 launch (sc_cycle0.hip): [prolongation of E +] `sweeps` red-black GS sweeps [+ residual + restriction into Fc]; launch_cycle0 derives (T, PRO, TAG) from these facts
@@ -340,6 +344,7 @@ struct Cycle0Launch {
     bool f_half = false, u_half = false, q16_in = false, q16_out = false;      // F / Uin hold float16; Uin / Uout hold 16-bit fixed point
     bool final_cycle = false, out_bytes = false;      // the judged cycle: nothing restricted; ... leaving as planar output bytes in Uout's memory, `lm` added
     bool out_interleaved = false;      // ... leaving as interleaved bytes in the destinations of `jobs` instead (C0_OUT3): members 0 .. njobs - 1 <= ImageJobs::MAX own channels 3i .. 3i + 2; `sat` set: nothing is written
+    bool in_bytes = false;             // the first launch of a same-size group reads the initial field from the destinations of `jobs` (their body_src) instead of Uin (C0_IN3): not u_half, Uin is geometry only
     const ImageJob *jobs = nullptr; int njobs = 0;
     bool composed = false;             // the prolongation source is composed from E and comp.E2 (comp.g1: level 1's geometry)
     bool l1_half = false, timing = false;      // level 1 keeps float16 fields (mg_level1_half); the form's twin under a second symbol

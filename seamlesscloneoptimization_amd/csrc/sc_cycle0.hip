@@ -33,6 +33,7 @@
 #include <hip/hip_fp16.h>
 #include "sc_wave.h"
 #include "sc_mg_device.h"
+#include "sc_u0_bytes.h"
 #include <type_traits>
 
 namespace sc {
@@ -131,6 +132,33 @@ __device__ __forceinline__ unsigned c0_q16_checked(float u, int &seen)
     return (unsigned)min(max(i, 0), 65535);
 }
 
+// C0_IN3: the same values from the destination's own interleaved bytes (sc_u0_bytes.h): ROI pixels x .. x + 3 of rows y0 .. y0 + R - 1 of
+// the image whose ROI pixel (0, 0) is at `body`, rows `bstep` bytes apart, ALL THREE channels from one 16-byte window per row: ch[r][c]
+// holds channel c of the row's four pixels, a byte each.  Rows and columns are clamped as c0_load clamps them.  unguarded (wave-uniform):
+// one 16-byte load per row; else dword by dword under the pre-process's bounds rule.
+template <int R>
+__device__ __forceinline__ void c0_load_bytes(const uint8_t *__restrict__ body, int bstep, int W, int H, int xc, int y0, bool unguarded, unsigned (&ch)[R][3])
+{
+    U0Quad raw[R];
+    int sh[R];
+    if (unguarded) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint8_t *row = body + (size_t)min(max(y0 + r, 0), H - 1) * bstep;
+            raw[r] = u0_fetch_unguarded(row, u0_first_dword(row, xc, sh[r]));
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint8_t *row = body + (size_t)min(max(y0 + r, 0), H - 1) * bstep;
+            unsigned fetched;
+            raw[r] = u0_fetch_guarded(row, W, u0_first_dword(row, xc, sh[r]), fetched);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) u0_channels(raw[r], sh[r], ch[r]);
+}
+
 // Level 0 (regular stencil) holds q = -f/4 instead of f (exact in either format: a power-of-two scaling): the Gauss-Seidel
 // update 0.25 (S - f) is then ONE fused multiply-add, fma(S, 0.25, q) -- S/4 and q are exact, so the single rounding of the
 // fma is the rounding of 0.25 (S - f), bit for bit what the subtract-then-scale form gives -- and the residual's f - X is
@@ -184,6 +212,10 @@ __device__ __forceinline__ float c0_comp(const float4 &v, int k) { return k == 0
 // member's three channels in turn, parks each channel's finished bytes of the exact tile in LDS (c0_out3_stage) and then writes the
 // tile's interior pixels INTERLEAVED into the member's destination itself (c0_out3_write): no planar byte plane, no splice launch.
 // The launch's one extra argument, the members' ImageJobs, is the pack X3 (empty for every other form: their signature is unchanged).
+// C0_IN3 (the first launch of a fused solve of a same-size group): the same member-major grid and loop on the INPUT side.  The field is
+// not read from float16 planes the pre-process stored but from the members' destination bytes themselves (ImageJob::body_src, the
+// pointer the pre-process reads): the first pass fetches the tile's interleaved bytes once, sorts them by channel and keeps the second and
+// third channel's in registers for their passes.  Uin carries geometry only.  Everything behind the load is the one-channel form's code.
 constexpr int C0_OUT3_ROWS = 52, C0_OUT3_WORDS = (256 - 2 * C0_HX) / 4;      // the exact tile of the two-sweep form: rows, planar words per row and channel
 // the lane's number in its wave, counted afresh behind a zero whose origin is hidden from the optimiser: no register carries it from one pass to the next
 __device__ __forceinline__ int c0_lane_again() { int z = 0; asm volatile("" : "+v"(z)); return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z)); }
@@ -239,8 +271,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
                                                     const RagMember *__restrict__ rag, int lev, X3... x3)
 {
     constexpr int HY = 2 * T + 2, RH = NW * R;
-    constexpr bool OUT3 = (TAG & C0_OUT3) != 0;
-    static_assert(sizeof...(X3) == (OUT3 ? 1 : 0), "the members' jobs travel with the three-channel bytes form only");
+    constexpr bool OUT3 = (TAG & C0_OUT3) != 0, IN3 = (TAG & C0_IN3) != 0, MM = OUT3 || IN3;      // MM: member-major, one workgroup per (member, tile)
+    static_assert(sizeof...(X3) == (MM ? 1 : 0), "the members' jobs travel with the member-major forms only");
+    static_assert(!IN3 || (!OUT3 && !PRO && !GEN && !ZEROIN && T == 2 && !(TAG & (C0_RAG | C0_U_HALF | C0_Q16_IN | C0_FINAL))), "destination bytes in: the first two-sweep launch of a same-size group");
     constexpr bool RAG = (TAG & C0_RAG) != 0;
     constexpr bool COMP = (TAG & C0_COMPOSED) != 0;      // E is U1; the interpolated level-2 correction is added on the fly (ComposeArgs)
     static_assert(!COMP || (PRO && !GEN && R % 2 == 0), "composition of two prolongations exists on level 0 only");
@@ -278,7 +311,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     TileLane tl{};
     if constexpr (PACK) tl = coarse_tile_lane(coarse_tile_plan(W, H, Uin.C, 256 - 2 * C0_HX, C0_HX, RH - 2 * HY, false), Uin.C, 256 - 2 * C0_HX, C0_HX, tile, lane);
     const int bx = tile % nbx, by = PACK ? tl.by : (tile / nbx) % nby;
-    const int c_first = PACK ? min(tl.c, Uin.C - 1) : OUT3 ? 3 * (tile / (nbx * nby)) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing   // OUT3: the tile's member, channels c_first .. c_first + 2 in turn
+    const int c_first = PACK ? min(tl.c, Uin.C - 1) : MM ? 3 * (tile / (nbx * nby)) : tile / (nbx * nby);      // an empty slot of the last pack loads the last plane and stores nothing   // OUT3: the tile's member, channels c_first .. c_first + 2 in turn
     const int sl = PACK ? tl.sl : lane, lps = PACK ? tl.lps : 64;        // lane index inside its slot, lanes per slot
     const bool live = !PACK || tl.c < Uin.C;                             // the slot holds a plane of the field
     if constexpr (RAG) {
@@ -292,30 +325,59 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         if (PRO) E.H = m.lh[lev + 1];
         if ((TAG & C0_COMPOSED) != 0) { comp.g1 = m.g[lev + 1]; comp.E2.H = m.lh[lev + 2]; }
     }
-    // OUT3: the body runs once per channel of the member (every other form: once, no loop).  What a channel's pass derives from the lane and
+    // Member-major (OUT3, IN3): the body runs once per channel of the member (every other form: once, no loop).  What a channel's pass derives from the lane and
     // the tile is derived AGAIN in every pass -- the sources are made opaque here -- so that nothing but the sources stays in registers from
-    // one pass to the next: the body's register budget is that of the one-channel form.
+    // one pass to the next (IN3: and the two channels' bytes still to come, `held`): the body's register budget is that of the one-channel form.
     const int lane_wg = lane, wv_wg = wv, bx_wg = bx, by_wg = by;
     const MGGeom &g_wg = g;
     const ComposeArgs &comp_wg = comp;
     int ci = 0, c_run = c_first, pt_run = OUT3 ? tile + 2 * (c_first / 3) * (nbx * nby) : tile;      // the pass's channel and the index of its (channel, tile) maximum: channel-major, as every form's
     const int pt_step = nbx * nby;
+    unsigned held[IN3 ? R : 1][2];      // IN3: channels 1 and 2 of the lane's pixels, a byte each, from the first pass's one fetch
+    (void)held;
     _Pragma("nounroll") do {
-    const int lane = OUT3 ? c0_lane_again() : lane_wg, wv = c0_opaque_s<OUT3>(wv_wg), bx = c0_opaque_s<OUT3>(bx_wg), by = c0_opaque_s<OUT3>(by_wg);
-    std::conditional_t<OUT3, MGGeom, const MGGeom &> g = g_wg;      // (OUT3: copies of its own ...)
-    std::conditional_t<OUT3, ComposeArgs, const ComposeArgs &> comp = comp_wg;
-    if constexpr (OUT3) {      // ... in which the weights the prolongation derives its ghost weights from are opaque too
-        g.x.tw1 = c0_opaque_s<OUT3>(g.x.tw1); g.y.tw1 = c0_opaque_s<OUT3>(g.y.tw1);
-        comp.g1.x.tw1 = c0_opaque_s<OUT3>(comp.g1.x.tw1); comp.g1.y.tw1 = c0_opaque_s<OUT3>(comp.g1.y.tw1);
+    const int lane = MM ? c0_lane_again() : lane_wg, wv = c0_opaque_s<MM>(wv_wg), bx = c0_opaque_s<MM>(bx_wg), by = c0_opaque_s<MM>(by_wg);
+    std::conditional_t<MM, MGGeom, const MGGeom &> g = g_wg;      // (member-major: copies of its own ...)
+    std::conditional_t<MM, ComposeArgs, const ComposeArgs &> comp = comp_wg;
+    if constexpr (MM) {      // ... in which the weights the prolongation derives its ghost weights from are opaque too
+        g.x.tw1 = c0_opaque_s<MM>(g.x.tw1); g.y.tw1 = c0_opaque_s<MM>(g.y.tw1);
+        comp.g1.x.tw1 = c0_opaque_s<MM>(comp.g1.x.tw1); comp.g1.y.tw1 = c0_opaque_s<MM>(comp.g1.y.tw1);
     }
     const int x = PACK ? tl.x : bx * (256 - 2 * C0_HX) - C0_HX + 4 * lane;
     const int y0 = by * (RH - 2 * HY) - HY + wv * R;       // even
-    const int c = OUT3 ? c_run : c_first, ptile = OUT3 ? pt_run : tile;
+    const int c = MM ? c_run : c_first, ptile = OUT3 ? pt_run : tile;
     float4 u[R], f[HF ? 1 : R];
     uint2 fh[HF ? R : 1];        // float16 right-hand side, kept packed (c0_minus_f)
     if (ZEROIN) {
 #pragma unroll
         for (int r = 0; r < R; ++r) u[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else if constexpr (IN3) {
+        // (the pass's first edge[0] store below cannot race the previous pass's residual reads of edge[0]: those reads precede the hedge
+        //  barrier, which every wave of the workgroup has passed before any of them starts this pass; hedge itself is read behind that
+        //  barrier and stored again only behind the 2 T + 1 barriers of this pass's sweeps)
+        // The member's bytes are fetched ONCE, in the first pass: a window holds all three channels, and the second and third channel wait
+        // in 2 R registers (held) -- the one thing besides the sources that stays in registers from pass to pass; the later passes load no field.
+        const int xc = u0_clamp_x(x, W);
+        unsigned word[R];
+        if (ci == 0) {
+            const ImageJobs &t = (x3, ...);
+            const ImageJob &j = t.j[c_first / 3];
+            const int xw0 = bx * (256 - 2 * C0_HX) - C0_HX;
+            const bool whole = u0_wave_unguarded(xw0, W) && (y0 >= 1) && (y0 + R - 1 <= H - 2);      // the wave-uniform `inner` test below: its columns lie at least 4 inside the ROI row
+            unsigned ch[R][3];
+            c0_load_bytes<R>(j.body_src, j.bstep, W, H, xc, y0, whole, ch);
+#pragma unroll
+            for (int r = 0; r < R; ++r) { word[r] = ch[r][0]; held[r][0] = ch[r][1]; held[r][1] = ch[r][2]; }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) word[r] = ci == 1 ? held[r][0] : held[r][1];
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float o[4];
+            u0_values(word[r], xc, W, o);
+            u[r] = make_float4(o[0], o[1], o[2], o[3]);
+        }
     } else if (HU) {
         c0_load_half<R>(reinterpret_cast<const __half *>(Uin.p) + (size_t)c * Uin.plane, P, H, x, y0, u);
     } else if (UQI) {
@@ -742,7 +804,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
     }
 
     // ------------------------------------------------------------------ write back the exact inner tile
-    if constexpr (OUT3) {
+    if constexpr (MM) {
         if (lane < C0_HXQ || lane >= 64 - C0_HXQ || x >= P || x >= W) continue;      // (no return: the barriers of the next channel and of the write are ahead)
     } else if (sl < C0_HXQ || sl >= lps - C0_HXQ || !live || x >= P || x >= W) return;
     if constexpr (OUT) {
@@ -804,7 +866,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         }
         const int seen = s0 | (x + 1 < W ? s1 : 0) | (x + 2 < W ? s2 : 0) | (x + 3 < W ? s3 : 0);
         if ((seen & ~0xffff) && sat.p) { *sat.p = sat.gen; if (sat.host) *sat.host = sat.gen; }       // rare; every writer stores the same word
-        return;
+        if constexpr (MM) continue; else return;
     }
     float *__restrict__ out = Uout.at(c);
 #pragma unroll
@@ -812,7 +874,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4))) vo
         const int yr = wv * R + r, y = y0 + r;
         if (yr >= HY && yr < RH - HY && y >= 0 && y < H) *reinterpret_cast<float4 *>(out + (size_t)y * P + x) = u[r];
     }
-    } while (OUT3 && (c_run += 1, pt_run += pt_step, ++ci < 3));      // (the channels of an OUT3 workgroup)
+    } while (MM && (c_run += 1, pt_run += pt_step, ++ci < 3));      // (the channels of a member-major workgroup)
     if constexpr (OUT3) {
         // the splice's two tests, block-uniform, once: a solve whose 16-bit field saturated and a member launched on a predicted box the
         // device did not find write nothing (the maxima above are needed either way)
@@ -880,9 +942,18 @@ static bool c0_is_out3(const Cycle0Launch &d)
            !d.q16_out && !d.timing && !d.rag;
 }
 
+// ... and the two forms of the first launch that read the members' destination bytes (C0_IN3): leaving a 16-bit field (the fast path) or a
+// float one (the repeat after a saturated store, SC_FLAG_FLOAT_FIELD, max_sweeps = 1)
+constexpr int C0_IN3_TAG = C0_FAST | C0_IN3;
+static bool c0_is_in3(const Cycle0Launch &d)
+{
+    return d.in_bytes && !d.out_interleaved && !d.out_bytes && !d.final_cycle && !d.prolong && !d.composed && d.sweeps == 2 && d.f_half && d.l1_half && !d.u_half &&
+           !d.q16_in && !d.timing && !d.rag;      // (a bands pointer: ignored by a launch without prolongation, as in the table)
+}
+
 static const Cycle0Form *c0_find(const Cycle0Launch &d)
 {
-    if (d.out_interleaved) return nullptr;      // not a form of the table (cycle0_form, launch_cycle0)
+    if (d.out_interleaved || d.in_bytes) return nullptr;      // not a form of the table (cycle0_form, launch_cycle0)
     // cell shares: a final cycle leaves them whenever the pointer is there (the kernel tests it), a full cycle of four sweeps in a form of its own
     const bool shares = d.bands && d.prolong && !d.final_cycle && d.sweeps == 4;
     const int TAG = (d.timing ? C0_TIMING : 0) | (d.f_half ? C0_F_HALF : 0) | (d.u_half ? C0_U_HALF : 0) | (d.final_cycle ? C0_FINAL : 0) |
@@ -896,6 +967,7 @@ static const Cycle0Form *c0_find(const Cycle0Launch &d)
 bool cycle0_form(const Cycle0Launch &d, int &T, bool &PRO, int &TAG)
 {
     if (c0_is_out3(d)) { T = 2; PRO = true; TAG = C0_OUT3_TAG; return true; }
+    if (c0_is_in3(d)) { T = 2; PRO = false; TAG = C0_IN3_TAG | (d.q16_out ? C0_Q16_OUT : 0); return true; }
     const Cycle0Form *f = c0_find(d);
     if (f) { T = f->T; PRO = f->PRO; TAG = f->TAG; }
     return f != nullptr;
@@ -917,6 +989,19 @@ int launch_cycle0(const Cycle0Launch &d)
         hipLaunchKernelGGL((k_cycle0<2, C0_NW, C0_R, true, false, false, C0_OUT3_TAG, ImageJobs>), dim3(blocks), dim3(C0_NW * 64), 0, d.s, d.Uin, d.Uout, d.F, d.Fc,
                            d.E, d.g, d.partial, d.comp, d.bands, d.lm, d.sat, d.rag, 0, t);
         return 3 * blocks;
+    }
+    if (d.in_bytes) {
+        if (!c0_is_in3(d) || !d.jobs || d.njobs < 1 || d.njobs > (int)ImageJobs::MAX || d.Uin.C != 3 * d.njobs) return -1;
+        ImageJobs t{};
+        for (int i = 0; i < d.njobs; ++i) t.j[i] = d.jobs[i];
+        const int blocks = cycle0_blocks(d.Uin.W, d.Uin.H, d.njobs, 2);      // one workgroup per (member, tile)
+        if (d.q16_out)
+            hipLaunchKernelGGL((k_cycle0<2, C0_NW, C0_R, false, false, false, C0_IN3_TAG | C0_Q16_OUT, ImageJobs>), dim3(blocks), dim3(C0_NW * 64), 0, d.s, d.Uin, d.Uout,
+                               d.F, d.Fc, d.E, d.g, d.partial, d.comp, d.bands, d.lm, d.sat, d.rag, 0, t);
+        else
+            hipLaunchKernelGGL((k_cycle0<2, C0_NW, C0_R, false, false, false, C0_IN3_TAG, ImageJobs>), dim3(blocks), dim3(C0_NW * 64), 0, d.s, d.Uin, d.Uout,
+                               d.F, d.Fc, d.E, d.g, d.partial, d.comp, d.bands, d.lm, d.sat, d.rag, 0, t);
+        return 0;
     }
     const Cycle0Form *f = c0_find(d);
     if (!f) return -1;

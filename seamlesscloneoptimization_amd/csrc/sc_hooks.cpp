@@ -2,6 +2,7 @@
 // (mask stage, right-hand side), the solver hooks on caller-supplied fields and the kernel timings bench.py reads.  No clone path
 // calls into this file.
 #include "sc_pcg.h"
+#include "sc_u0_bytes.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -291,6 +292,36 @@ int sc_hip_bytes_writer(void *p)
     return w;
 }
 
+int sc_hip_u0_reader(void *p)
+{
+    Instance *I = get(p);
+    if (!I) return SC_ERR_BAD_ARG;
+    const int w = I->u0_reader;
+    I->u0_reader = 0;
+    return w;
+}
+
+int sc_hip_u0_bytes_fetch(const uint8_t *row, int W, int xw, int *out)
+{
+    if (!row || !out || W < 1) return SC_ERR_BAD_ARG;
+    const bool whole = u0_wave_unguarded(xw, W);
+    for (int lane = 0; lane < 64; ++lane, out += 16) {
+        const int xc = u0_clamp_x(xw + 4 * lane, W);
+        int shift;
+        const int q = u0_first_dword(row, xc, shift);
+        unsigned fetched = 15u, ch[3];
+        const U0Quad v = whole ? u0_fetch_unguarded(row, q) : u0_fetch_guarded(row, W, q, fetched);
+        u0_channels(v, shift, ch);
+        out[0] = q; out[1] = shift; out[2] = (int)fetched; out[3] = whole ? 1 : 0;
+        for (int c = 0; c < 3; ++c) {
+            float f[4];
+            u0_values(ch[c], xc, W, f);
+            for (int k = 0; k < 4; ++k) out[4 + 4 * c + k] = (int)f[k];
+        }
+    }
+    return SC_OK;
+}
+
 int sc_hip_field_load(void *p, int W, int H, int C, const float *U, const float *lap)
 {
     Instance *I = get(p);
@@ -544,7 +575,7 @@ int sc_hip_cycle0_form(const int *facts, int index, int form[3])
         static float4 some_bands;
         static const RagMember some_class{};
         Cycle0Launch d;
-        d.sweeps = facts[0]; d.prolong = facts[1]; d.f_half = facts[2]; d.u_half = facts[3]; d.q16_in = facts[4]; d.q16_out = facts[5];
+        d.sweeps = facts[0]; d.prolong = facts[1]; d.f_half = facts[2]; d.u_half = (facts[3] & 1) != 0; d.in_bytes = (facts[3] & 2) != 0; d.q16_in = facts[4]; d.q16_out = facts[5];
         d.final_cycle = facts[6]; d.out_bytes = (facts[7] & 1) != 0; d.out_interleaved = (facts[7] & 2) != 0; d.composed = facts[8]; d.l1_half = facts[9]; d.timing = facts[10];
         d.bands = facts[11] ? &some_bands : nullptr; d.rag = facts[12] ? &some_class : nullptr;
         rc = cycle0_form(d, T, PRO, TAG) ? 0 : -1;

@@ -185,6 +185,10 @@ struct Instance {
     bool out_direct = false;               // the last solve wrote output bytes from its last cycle: result(I) is the iterate before it, not the solution
     bool f_half = false;      // F currently holds float16 values (written by the pre-process for the fused multigrid path)
     bool u_half = false;      // ... and so does the initial field U0 until the first cycle has consumed it
+    // ... unless u0_bytes: a same-size group whose pre-process stores no U0 at all -- the first level-0 launch reads the members' destination
+    // bytes itself (k_cycle0 with C0_IN3).  Decided once per attempt by solve_prepare, before the pre-process is enqueued.
+    bool u0_bytes = false;
+    int u0_reader = 0;        // sc_hip_u0_reader (which clears it): the first launches read bit 0 float16 planes, bit 1 destination bytes, bit 2 planes a safety-net launch filled
     bool u_q16 = false;       // multigrid fast path, during a solve: the current field is 16-bit fixed point (sc_cycle0.hip, C0_Q16_IN / C0_Q16_OUT)
     bool mg_q16_last = false; // ... the last solve kept its field so (sc_hip_time_cycle0 times the same form)
     // 16-bit stores check their range: `sat` is the current solve's report word + generation (sc_common.h AbortFlag; p == nullptr:
@@ -283,6 +287,11 @@ inline bool legacy_path(const sc_solver_opts &o, int which) { return (o.flags & 
 // members at 1024^2, the smallest group measured -- the new form is never slower than the splice beyond the runs' spread, and it gains from
 // 720 on (two members at 2048^2: 1.4 %; sixteen: 2.8 %).  Nothing smaller was measured: it keeps the splice.
 constexpr long SC_OUT3_MIN_TILES = 200;
+// The first launch of such a group reads the destinations' bytes (C0_IN3), and its pre-process stores no float16 initial field, from this
+// many (member, level-0 tile) workgroups on; below, the planes as ever.  Measured (profiles/in3_threshold.txt): 60 and 120
+// tiles (2 and 4 members at 512^2) are 5.3 and 3.7 % SLOWER with the bytes; from 200 (2 x 1024^2: +0.3 %, inside the runs' spread) the new form
+// is never slower beyond the spread, and it gains from 720 on (2 x 2048^2: 0.8 %, 8 x 1024^2: 1.7 %, 16 x 2048^2: 1.2 %).
+constexpr long SC_IN3_MIN_TILES = 200;
 
 // internal return code of a solve (never crosses the C ABI): a 16-bit fixed-point store saturated, no output was written;
 // solve_step repeats the pre-process and the solve with Instance::force_float_field set
@@ -473,13 +482,13 @@ int solve(Instance *I);
 // enqueues the pre-process for the current I->f_half / I->u_half (and the caller's own marks) and returns a code.  A solve whose
 // 16-bit field saturated wrote nothing: pre() and the solve go again on float fields (info.field_retry).  Unless the solver wrote
 // the output itself (spec_post.done), the caller then writes it with write_output.  Run under a CallScope.
-void solve_prepare(Instance *I);                         // the field formats the pre-process is to write
+void solve_prepare(Instance *I, const SolveTarget &t = SolveTarget());      // the field formats the pre-process is to write (t: u0_bytes is a group's)
 int solve_attempt(Instance *I, const SolveTarget &t);    // SC_RETRY_FLOAT_FIELD: force_float_field is set, repeat both
 template <class Pre> int solve_step(Instance *I, const SolveTarget &t, Pre &&pre)
 {
     int rc;
     do {
-        solve_prepare(I);
+        solve_prepare(I, t);
         if ((rc = pre())) return rc;
     } while ((rc = solve_attempt(I, t)) == SC_RETRY_FLOAT_FIELD);
     return rc;

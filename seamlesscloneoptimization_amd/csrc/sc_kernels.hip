@@ -496,7 +496,8 @@ __device__ __forceinline__ void p4_window(const unsigned *row, int word0, int sh
 // and (x+j+1, y-1) -- the row above needs the fifth word then, like the centre row.  MONOCHROME: the patch's gradients are those
 // of its grey image, cvtColor(BGR2GRAY)'s integer formula for 8-bit data, formed once per pixel for all three channels.  Every
 // gradient stays an integer in [-255, 255], the right-hand side one in [-1020, 1020].  Not combined with GREY.
-template <bool HF, bool HU, bool GREY = false, bool ER = false, int MODE = SC_NORMAL_CLONE>
+// SU = false (a same-size group on float16 fields whose first level-0 launch reads the destination bytes itself, C0_IN3): U0 is not stored.
+template <bool HF, bool HU, bool GREY = false, bool ER = false, int MODE = SC_NORMAL_CLONE, bool SU = true>
 __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ body, int bstep,
                                                  const uint8_t *__restrict__ face, int fstep,
                                                  const uint8_t *__restrict__ M, int mpitch,
@@ -640,7 +641,8 @@ __device__ __forceinline__ void preprocess_block(const uint8_t *__restrict__ bod
             }
             lv[j] = lap;
         }
-        if (HU) {
+        if (!SU) {
+        } else if (HU) {
             const __half2 a = __floats2half2_rn(uv[0], uv[1]), b2 = __floats2half2_rn(uv[2], uv[3]);
             uint2 pk; pk.x = *reinterpret_cast<const unsigned *>(&a); pk.y = *reinterpret_cast<const unsigned *>(&b2);
             *reinterpret_cast<uint2 *>(reinterpret_cast<__half *>(U0.p) + (size_t)(c0 + c) * U0.plane + o) = pk;
@@ -680,7 +682,7 @@ __global__ __launch_bounds__(256) void k_preprocess(const uint8_t *__restrict__ 
 }
 
 // a group of clones in one launch: blockIdx.z = member, which owns channels 3z..3z+2 of the group's fields
-template <bool HF, bool HU, int MODE = SC_NORMAL_CLONE>
+template <bool HF, bool HU, int MODE = SC_NORMAL_CLONE, bool SU = true>
 __global__ __launch_bounds__(256) void k_preprocess_group(ImageJobs t, int mpitch, Field U0, Field F)
 {
     const ImageJob &j = t.j[blockIdx.z];
@@ -688,11 +690,11 @@ __global__ __launch_bounds__(256) void k_preprocess_group(ImageJobs t, int mpitc
         if ((int)blockIdx.x * P4_TW >= j.W || (int)blockIdx.y * P4_TH >= j.H) return;
         U0.W = F.W = j.W; U0.H = F.H = j.H;
     }
-    preprocess_block<HF, HU, false, false, MODE>(j.body_src, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
+    preprocess_block<HF, HU, false, false, MODE, SU>(j.body_src, j.bstep, j.face_org, j.fstep, j.M, mpitch, U0, F, 3 * blockIdx.z, (int)blockIdx.y);
 }
 
 template <int MODE>
-static void launch_preprocess_group_mode(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half)
+static void launch_preprocess_group_mode(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, bool store_u0)
 {
     for (int i0 = 0; i0 < n; i0 += ImageJobs::MAX) {
         ImageJobs t{};
@@ -702,17 +704,49 @@ static void launch_preprocess_group_mode(const ImageJob *jobs, int n, int mpitch
         u.p = u_half ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(U0.p) + (size_t)3 * i0 * U0.plane) : U0.p + (size_t)3 * i0 * U0.plane;
         f.p = f_half ? reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(F.p) + (size_t)3 * i0 * F.plane) : F.p + (size_t)3 * i0 * F.plane;
         dim3 g4((U0.W + P4_TW - 1) / P4_TW, (U0.H + P4_TH - 1) / P4_TH, cnt);
-        if (f_half && u_half) hipLaunchKernelGGL((k_preprocess_group<true, true, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
+        if (f_half && u_half && !store_u0) hipLaunchKernelGGL((k_preprocess_group<true, true, MODE, false>), g4, dim3(256), 0, s, t, mpitch, u, f);
+        else if (f_half && u_half) hipLaunchKernelGGL((k_preprocess_group<true, true, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
         else if (f_half) hipLaunchKernelGGL((k_preprocess_group<true, false, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
         else hipLaunchKernelGGL((k_preprocess_group<false, false, MODE>), g4, dim3(256), 0, s, t, mpitch, u, f);
     }
 }
 
-void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode)
+void launch_preprocess_group(const ImageJob *jobs, int n, int mpitch, Field U0, Field F, hipStream_t s, bool f_half, bool u_half, int mode, bool store_u0)
 {
-    if (mode == SC_MIXED_CLONE) launch_preprocess_group_mode<SC_MIXED_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half);
-    else if (mode == SC_MONOCHROME_TRANSFER) launch_preprocess_group_mode<SC_MONOCHROME_TRANSFER>(jobs, n, mpitch, U0, F, s, f_half, u_half);
-    else launch_preprocess_group_mode<SC_NORMAL_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half);
+    if (mode == SC_MIXED_CLONE) launch_preprocess_group_mode<SC_MIXED_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half, store_u0);
+    else if (mode == SC_MONOCHROME_TRANSFER) launch_preprocess_group_mode<SC_MONOCHROME_TRANSFER>(jobs, n, mpitch, U0, F, s, f_half, u_half, store_u0);
+    else launch_preprocess_group_mode<SC_NORMAL_CLONE>(jobs, n, mpitch, U0, F, s, f_half, u_half, store_u0);
+}
+
+// The float16 planes of U0 the pre-process did not store (store_u0 = false), for a solve whose first launch turns out to have no form
+// that reads the destination bytes: lane = four pixels of a row, the values and the zeros beyond W the pre-process stores.  Rare, not tuned.
+__global__ __launch_bounds__(256) void k_u0_half_group(ImageJobs t, Field U0)
+{
+    const ImageJob &j = t.j[blockIdx.z];
+    const int x = 4 * (int)(blockIdx.x * 64 + (threadIdx.x & 63)), y = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    if (x >= U0.W || y >= U0.H) return;
+    const uint8_t *row = j.body_src + (size_t)y * j.bstep;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float uv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) uv[k] = (x + k < U0.W) ? (float)row[3 * (min(x + k, U0.W - 1)) + c] : 0.f;
+        const __half2 a = __floats2half2_rn(uv[0], uv[1]), b2 = __floats2half2_rn(uv[2], uv[3]);
+        uint2 pk; pk.x = *reinterpret_cast<const unsigned *>(&a); pk.y = *reinterpret_cast<const unsigned *>(&b2);
+        *reinterpret_cast<uint2 *>(reinterpret_cast<__half *>(U0.p) + (size_t)(3 * blockIdx.z + c) * U0.plane + (size_t)y * U0.pitch + x) = pk;
+    }
+}
+
+void launch_u0_half_group(const ImageJob *jobs, int n, Field U0, hipStream_t s)
+{
+    for (int i0 = 0; i0 < n; i0 += ImageJobs::MAX) {
+        ImageJobs t{};
+        const int cnt = std::min(n - i0, (int)ImageJobs::MAX);
+        for (int i = 0; i < cnt; ++i) t.j[i] = jobs[i0 + i];
+        Field u = U0;
+        u.p = reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(U0.p) + (size_t)3 * i0 * U0.plane);
+        hipLaunchKernelGGL(k_u0_half_group, dim3((U0.W + 255) / 256, (U0.H + 3) / 4, cnt), dim3(256), 0, s, t, u);
+    }
 }
 
 // the launch of one clone's tiles (and of its bounding-box scan: bb.scan_rows > 0) under clone mode MODE

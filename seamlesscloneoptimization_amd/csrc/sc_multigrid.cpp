@@ -472,6 +472,23 @@ static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget
                 if ((tiles >= SC_OUT3_MIN_TILES || legacy_path(o, SC_FORCE_INTERLEAVED_OUT)) && cycle0_form(d3, T3, PRO3, TAG3)) { d = d3; interleaved = true; }
             }
         }
+        // The first launch of a same-size group whose pre-process stored no initial field (Instance::u0_bytes): it reads the members' destination
+        // bytes where that form exists for the step's facts; where it does not (nothing composed, level 1 in float, one pre-sweep), a
+        // small launch stores the float16 planes after all and the planes' form runs -- never on planes nobody wrote.
+        if (s.kind == FUSED_FIRST && s.u_half) {
+            int reader = 1;
+            if (I->u0_bytes) {
+                const SolveTarget &to = I->spec_post.to;
+                Cycle0Launch d3 = d;
+                d3.u_half = false; d3.in_bytes = true; d3.jobs = to.group ? to.group->data() : nullptr; d3.njobs = to.group ? (int)to.group->size() : 0;
+                int T3, TAG3;
+                bool PRO3;
+                if (d3.jobs && cycle0_form(d3, T3, PRO3, TAG3)) { d = d3; reader = 2; }
+                else if (!to.group) { I->err = "internal: no initial field stored for a solve without members"; return SC_ERR_BAD_ARG; }
+                else { launch_u0_half_group(to.group->data(), (int)to.group->size(), I->U0, I->stream); reader = 4; }
+            }
+            I->u0_reader |= reader;
+        }
         const int nb = launch_cycle0(d);
         if (s.out_bytes && nb <= 0) { verdict = VERDICT_NO_FORM; continue; }
         if (s.prolong ? nb <= 0 : nb < 0) { I->err = "cycle0: unsupported depth"; return SC_ERR_BAD_ARG; }
@@ -483,7 +500,7 @@ static int mg_solve_fused(Instance *I, int pre, int post, float utol, int budget
                 SC_HIP(I, hipStreamWaitEvent(I->stream, I->rag.ev_ready, 0));      // (the matrices: run_tail waits for them)
                 I->rag.ready_pending = false;
             }
-            I->u_half = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
+            I->u_half = I->u0_bytes = false;             // consumed: both U buffers hold float (or 16-bit fixed point: u_q16) from here on
             I->mg_q16_last = q16;
         } else if (!s.out_bytes) {
             lowmode_bands_written(I, d.bands ? result(I).p : nullptr);

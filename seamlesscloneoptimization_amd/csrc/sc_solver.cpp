@@ -188,11 +188,21 @@ int solve(Instance *I)
 
 // the fused multigrid path reads a float16 right-hand side and initial field; an edit (edit_call) and a Poisson call (FLOAT_RHS |
 // FLOAT_U0) never do
-void solve_prepare(Instance *I)
+// u0_bytes: the float16 initial field is not stored at all -- a same-size group of up to ImageJobs::MAX members (no size class), large
+// enough to pay for workgroups of three-fold length (SC_IN3_MIN_TILES) or forced, reads it from the destinations in its first launch
+void solve_prepare(Instance *I, const SolveTarget &t)
 {
     I->result_in_U1 = false;
     I->f_half = mg_reads_half_rhs(I);
     I->u_half = I->f_half && !(I->opts.flags & SC_FLAG_FLOAT_U0);
+    I->u0_bytes = false;
+    if (I->u_half && t.group && !t.group->empty() && t.group->size() <= (size_t)ImageJobs::MAX && t.group->size() * 3 == (size_t)I->F.C &&
+        !legacy_path(I->opts, SC_LEGACY_U0_PLANES)) {
+        bool one_size = true;
+        for (const ImageJob &j : *t.group) one_size = one_size && j.W == 0;
+        const long tiles = (long)cycle0_blocks(I->F.W, I->F.H, (int)t.group->size(), 2);
+        I->u0_bytes = one_size && (tiles >= SC_IN3_MIN_TILES || legacy_path(I->opts, SC_FORCE_U0_BYTES));
+    }
 }
 
 int solve_attempt(Instance *I, const SolveTarget &t)

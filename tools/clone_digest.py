@@ -110,6 +110,12 @@ def main():
                 continue
             configure(inst, dict(legacy_paths=bit), F.SC_FLAG_LEGACY_PATHS if bit else 0)
             batch(inst, "batch 16 x 470x300 %s" % oname, [(470, 300)] * 16, 70)
+        # ... and whose first launch may read the destinations' bytes itself (C0_IN3): by the default rule, forced, and from float16 planes
+        for oname, bit in (("u0_defaults", 0), ("u0_forced_bytes", getattr(F, "SC_FORCE_U0_BYTES", None)), ("u0_legacy_planes", getattr(F, "SC_LEGACY_U0_PLANES", None))):
+            if bit is None:
+                continue
+            configure(inst, dict(legacy_paths=bit), F.SC_FLAG_LEGACY_PATHS if bit else 0)
+            batch(inst, "batch 16 x 470x300 %s" % oname, [(470, 300)] * 16, 70)
     finally:
         inst.destroy()
 
