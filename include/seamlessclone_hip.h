@@ -803,7 +803,7 @@ SC_API int sc_hip_robust_device(void *instance, const sc_robust_params *p, const
 SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
                          float *out);
-/* The last robust call's last chunk, round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+/* The last robust call's last chunk (sc_hip_robust* or sc_hip_volume_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
@@ -856,7 +856,8 @@ SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int c
  * NOT detected, the caller's responsibility: a connected component of UNKNOWN pixels that nothing pins (no KNOWN neighbour, no Dirichlet
  * line, no weight) while other components are pinned.  In the guidance form the system stays consistent and the call returns some
  * constant offset on that component; with SC_POISSON_LAPLACIAN it need not converge.
- * Not offered: region states in the robust call or through the 8-bit clone and edit entry points. */
+ * Not offered: robust region solves on single images (sc_hip_volume_robust takes states, on frames >= 2), region states through the
+ * 8-bit clone and edit entry points. */
 #define SC_REGION_UNKNOWN 0
 #define SC_REGION_KNOWN   1
 #define SC_REGION_OUTSIDE 2
@@ -935,8 +936,8 @@ SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poi
  * when the call has no Dirichlet line, the channel has UNKNOWN pixels, and the volume has no UNKNOWN - KNOWN link of either kind and
  * no positive weight.  Not detected, as in the region call: a connected component (through spatial and temporal links) that nothing
  * pins while others are pinned.
- * Not offered here: per-link spatial or temporal weights and periodic time (sc_hip_volume_wls has both); anywhere: robust penalties on
- * volumes, the 8-bit entry points. */
+ * Not offered here: per-link spatial or temporal weights and periodic time (sc_hip_volume_wls has both), robust penalties
+ * (sc_hip_volume_robust); anywhere: the 8-bit entry points. */
 typedef struct sc_volume_params {
     int       kind;            /* as sc_region_params.kind */
     int       frames;          /* >= 2; frames * channels <= SC_POISSON_MAX_PLANES */
@@ -1011,7 +1012,7 @@ SC_API int sc_hip_volume(void *instance, const sc_volume_params *p, const sc_poi
  * run -- for every per-job refusal of sc_hip_volume; exactly one of smooth_x / smooth_y; link arrays where the first volume has none, or
  * the reverse; a link array overlapping out; a live link that is not finite or not > 0 (smooth_t as well as its product with tau),
  * judged only where it is read.  The pin check is sc_hip_volume's; an UNKNOWN - KNOWN link counts its own weight.
- * Not offered: robust penalties on volumes, motion-compensated temporal links, the 8-bit entry points. */
+ * Not offered: motion-compensated temporal links, the 8-bit entry points. */
 typedef struct sc_volume_wls_params {
     int       kind;            /* as sc_volume_params.kind */
     int       frames;          /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
@@ -1047,6 +1048,74 @@ SC_API int sc_hip_volume_wls_device(void *instance, const sc_volume_wls_params *
 SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                              const float *gt, const float *lap, const float *data, const float *state, const float *weight,
                              const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
+/* ---- robust volume solves: Lp penalties in space, time and data on frame stacks ---------------------------------------------------------
+ * sc_hip_volume_wls's problem with sc_hip_robust's penalties in place of the squares.  Per channel, with exponents 0 < p, r, q <= 2, the
+ * call minimises over the UNKNOWN pixels of all frames
+ *     sum w phi_q(u - d; eps_d)  +  sum_live x-links c_x phi_p(dx u - gx; eps_g)  +  sum_live y-links c_y phi_p(dy u - gy; eps_g)
+ *                                +  sum_live t-links c_t phi_r(u_{t+1} - u_t - gt; eps_t),
+ * phi the robust call's penalty; c_x, c_y are smooth_x, smooth_y (NULL: 1) and c_t = lt, the float32 product tau * smooth_t rounded once
+ * (NULL: tau), exactly as in sc_hip_volume_wls.  The value of u at a KNOWN pixel is data's, on a Dirichlet line of the border kind
+ * boundary's.  Total-variation denoising of video that does not flicker (p = 1, r = 1 or 2, q = 2), integrating a video's gradient field
+ * or a stack of edited gradients when some of them are grossly wrong (a bad flow vector, a shot cut, a specular frame), TV inpainting of
+ * a moving hole, robust propagation from keyframes -- each on a domain of any shape.
+ * States, the liveness of spatial and temporal links, periodic time, the arrays' lengths, what is read and what is written:
+ * sc_hip_volume_wls's, word for word.  gt NULL means zeros: it is not read and the residual of a temporal link is the plain difference.
+ * weight NULL means no data term: p_data and eps_data are validated and unused.  There is no lap: the residual of a link needs g itself
+ * (the base kind must be SC_POISSON_GUIDANCE).
+ * Solved by iteratively reweighted least squares, as sc_hip_robust.  Round 0 is sc_hip_volume_wls's system with the caller's arrays, set
+ * up and cold-started as that call does.  Round k >= 1 is the same system with s = c rho(link residual) on every live link (rho_p on
+ * the spatial, rho_r on the temporal ones) and w' = w rho_q(u - d), taken at round k - 1's iterate: each a rounded float32 product, and
+ * with exponent 2 the base value passes through without a multiply (rho in float32: sc_hip_robust's).  Both ends of a link take its
+ * residual as t = (u_hi - u_lo) - g with the same bits.  The right-hand side of round k is the seven steps of the WLS volume section in
+ * that order with those links, its diagonal (((lw + le) + (ln + ls)) + (lb + lf)) + w'; its solve starts warm from the iterate.  The
+ * preconditioner's means are each round's own: s-bar the mean of the live spatial s, tau-bar the mean of the live temporal s, w-bar =
+ * (the sum of w' + the sum of the UNKNOWN - KNOWN links' s) / (the UNKNOWN pixels); the table along the frames and the modes' shifts
+ * are rebuilt per round.  One launch (k_volume_robust_setup) and one host read per round, as in the robust call.
+ * Rounds, max_rounds, round_tol (judged per plane: a channel's whole volume), SC_ERR_NOT_CONVERGED, sc_run_info and the trace
+ * (sc_hip_robust_trace): sc_hip_robust's.  Size, chunks, methods, SC_FLAG_FFT_FP64 limits: sc_hip_volume's.
+ * Ties: with p_grad = p_time = p_data = 2 no round runs and the call writes the bytes of sc_hip_volume_wls with default precond_* and the
+ * same tol and max_iters.  Link arrays of 1.0f give the bytes of NULL arrays.  Two runs of one call give the same bytes.
+ * Codes: everything sc_hip_volume_wls_check refuses; everything sc_hip_robust_check refuses for exponents, eps, tol, round_tol and a
+ * Laplacian base; SC_ERR_BAD_ARG for SC_ROBUST_ISOTROPIC / SC_ROBUST_JOINT_CHANNELS in kind.  Per job: the WLS volume call's refusals;
+ * the first volume decides for weight and for the link arrays.
+ * Not offered: coupled forms on volumes, robust region solves on single images (frames >= 2), motion-compensated temporal links, the
+ * 8-bit entry points. */
+typedef struct sc_volume_robust_params {
+    int       kind;              /* as sc_volume_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
+    int       frames;            /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
+    long long frame_stride;      /* floats from a frame to the next in every array; at least the span of one frame under the layout */
+    float     tau;               /* multiplies every temporal base link; finite, > 0 */
+    int       time_periodic;     /* 0: the ends of time are free; 1: frame frames - 1 is linked to frame 0 */
+    float     p_grad, eps_grad;  /* spatial links:  0 < p <= 2; eps finite, > 0 (unused when p == 2) */
+    float     p_time, eps_time;  /* temporal links: likewise */
+    float     p_data, eps_data;  /* data term:      likewise */
+    int       max_rounds;        /* reweighting rounds after the quadratic solve; <= 0: 15 */
+    float     round_tol;         /* stop when no plane's energy fell by more than round_tol * its energy in the last round; 0: 1e-4; < 0: never stop early */
+    float     tol;               /* inner solves: ||r||_2 <= tol * ||b||_2 on every (volume, channel); <= 0: 1e-5 */
+    int       max_iters;         /* per inner solve; <= 0: 400 */
+} sc_volume_robust_params;
+typedef struct sc_volume_robust_job {   /* sc_volume_wls_job without lap */
+    const float *gx, *gy;    /* `frames` frames, read at links live in the region: required */
+    const float *gt;         /* frames - 1 frames (time_periodic: frames), read at live temporal links; NULL: zeros */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* the base links c > 0 at links live in the region; both NULL: every spatial base link 1 */
+    const float *smooth_y;
+    const float *smooth_t;   /* > 0 at live temporal links; NULL: every temporal base link tau */
+    const float *boundary;   /* its Dirichlet lines in every frame (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names in every frame is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_volume_robust_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_robust_device(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, sc_volume_robust_job *jobs,
+                                       int n, bool bSync);
+/* One volume on host arrays, as sc_hip_volume_wls: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                                const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x,
+                                const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

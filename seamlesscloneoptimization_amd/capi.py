@@ -297,6 +297,20 @@ class RobustJob(C.Structure):
                 ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# robust volume solves (sc_hip_volume_robust*): Instance.volume_robust / volume_robust_device -- Lp penalties in space, time and data on
+# frame stacks; robust_trace() reports the rounds
+class VolumeRobustParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("frames", C.c_int), ("frame_stride", C.c_longlong), ("tau", C.c_float), ("time_periodic", C.c_int),
+                ("p_grad", C.c_float), ("eps_grad", C.c_float), ("p_time", C.c_float), ("eps_time", C.c_float), ("p_data", C.c_float),
+                ("eps_data", C.c_float), ("max_rounds", C.c_int), ("round_tol", C.c_float), ("tol", C.c_float), ("max_iters", C.c_int)]
+
+
+class VolumeRobustJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("gt", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p), ("weight", C.c_void_p),
+                ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("smooth_t", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p),
+                ("rc", C.c_int)]
+
+
 class SeamlessCloneError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -520,6 +534,13 @@ def load():
     L.sc_hip_volume_wls_device.restype = C.c_int
     L.sc_hip_volume_wls.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 12
     L.sc_hip_volume_wls.restype = C.c_int
+    L.sc_hip_volume_robust_check.argtypes = [C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_robust_check.restype = C.c_int
+    L.sc_hip_volume_robust_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout), C.POINTER(VolumeRobustJob),
+                                              C.c_int, C.c_bool]
+    L.sc_hip_volume_robust_device.restype = C.c_int
+    L.sc_hip_volume_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 11
+    L.sc_hip_volume_robust.restype = C.c_int
     L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_robust_check.restype = C.c_int
     L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
@@ -977,6 +998,42 @@ def volume_wls_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, sm
     return kind, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, lap, boundary
 
 
+def volume_robust_params(kind, frames, frame_stride, tau=1.0, loop=False, p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
+                         eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0) -> VolumeRobustParams:
+    return VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), 1 if loop else 0, float(p_grad), float(eps_grad), float(p_time),
+                              float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
+
+
+def volume_robust_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                        p_grad: float = 1.0, eps_grad: float = 1e-3, p_time: float = 1.0, eps_time: float = 1e-3, p_data: float = 2.0,
+                        eps_data: float = 1e-3, max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0,
+                        layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                        channel_stride=None) -> int:
+    """Host-only sc_hip_volume_robust_check: SC_OK or the code a robust volume call with these parameters and this layout returns before
+    it runs anything.  The layout (of one frame) as a PoissonLayout or as keyword fields."""
+    p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
+                           float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    return _check_call("sc_hip_volume_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_robust_arrays(gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0, loop=False,
+                         neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0, eps_data=1e-3):
+    """Checks a robust volume problem's numpy arrays and penalties before any device is touched: (kind, data, state, weight, smooth_x,
+    smooth_y, smooth_t, gx, gy, gt, boundary), volume_wls_arrays' rules.  gx and gy are required: the residual of a link needs the
+    guidance itself (there is no lap).  Exponents in (0, 2]; an eps finite and > 0 wherever its exponent is not 2."""
+    if gx is None or gy is None:
+        raise ValueError("a robust volume solve needs the guidance gx and gy (there is no Laplacian form)")
+    for name, r, eps in (("grad", p_grad, eps_grad), ("time", p_time, eps_time), ("data", p_data, eps_data)):
+        if not (np.isfinite(r) and 0 < r <= 2):
+            raise ValueError(f"p_{name} must lie in (0, 2]")
+        if r != 2 and not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps_{name} must be finite and > 0")
+    kind, data, state, weight, sx, sy, smt, gx, gy, gt, _, boundary = volume_wls_arrays(data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt,
+                                                                                       None, boundary, tau, loop, neumann, free_sides, periodic)
+    return kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary
+
+
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
                  max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
                  cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None, isotropic=False,
@@ -1366,6 +1423,38 @@ class Instance:
         SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_volume_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
+    # ---- robust volume solves on float32 arrays
+    def volume_robust(self, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,
+                      loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
+                      eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0, allow_not_converged=False):
+        """sc_hip_volume_robust on numpy float32 arrays of shape T x H x W or T x H x W x C (volume_robust_arrays' rules): volume_wls()'s
+        problem with the penalties of robust() in place of the squares -- phi_p (p_grad, eps_grad) on the spatial links, phi_r (p_time,
+        eps_time) on the temporal ones, phi_q (p_data, eps_data) on the data term -- by reweighted WLS volume solves on the device.
+        max_rounds, round_tol, tol, max_iters: sc_volume_robust_params' (0: the defaults; round_tol < 0: never stop early).  Returns a
+        NEW array composed as volume()'s; info() has the total of the inner iterations and whether the round rule was met,
+        robust_trace() the rounds."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary = volume_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                            gt, boundary, tau, loop, neumann, free_sides, periodic,
+                                                                                            p_grad, eps_grad, p_time, eps_time, p_data, eps_data)
+        layout = poisson_layout_of(data[0])
+        p = volume_robust_params(kind, data.shape[0], data[0].size, tau, loop, p_grad, eps_grad, p_time, eps_time, p_data, eps_data, max_rounds,
+                                 round_tol, tol, max_iters)
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_robust(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                         (gx, gy, gt, data, state, weight, sx, sy, smt, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    @staticmethod
+    def make_volume_robust_jobs(n: int):
+        return (VolumeRobustJob * n)()
+
+    def volume_robust_device(self, params: VolumeRobustParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_robust_device: jobs is a VolumeRobustJob array (make_volume_robust_jobs) of device pointers, one frame layout and
+        one frame stride for all.  sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code:
+        SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_volume_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
                p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0,
@@ -1395,7 +1484,7 @@ class Instance:
         return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     def robust_trace(self):
-        """(energy, iters) of the last robust call's last chunk: float64 and int32 arrays with one entry per round, the quadratic one
+        """(energy, iters) of the last robust call's last chunk (robust or volume_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
         included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
         n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
         energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)

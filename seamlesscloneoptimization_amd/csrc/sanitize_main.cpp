@@ -19,6 +19,8 @@
 //      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check;
 //      sc_hip_volume_check: the same verdicts for two frames a frame's span apart, then frames, the plane limit, frame_stride and tau.
 //      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
+//      sc_hip_volume_robust_check: the WLS volume call's verdicts on a guidance base, then every exponent, every eps, round_tol, the coupling
+//      bits, a Laplacian base and the WLS volume call's own refusals.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 //  10. a job's side arrays (SideArrays; sc_instance.h, sc_pcg.h): for_side_tables fills every family's table, 20 jobs as 16 + 4, each
@@ -500,8 +502,56 @@ int main()
                     if (sc_hip_volume_wls_check(&wp, &l) != SC_ERR_BAD_ARG) return fail("volume_wls_check (time_periodic)");
                 }
             }
-            // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
             const bool lap_base = (k.kind & 3) == SC_POISSON_LAPLACIAN;
+            // the robust volume call: the WLS volume call's verdict on a guidance base under either kind of time, a refusal on a Laplacian
+            // one; then the robust call's refusals -- every exponent, every eps, round_tol --, the coupling bits and the WLS volume call's own
+            for (int tp = 0; tp < 2; ++tp) {
+                const int fr = tp ? 3 : 2;
+                const sc_volume_robust_params good{ k.kind, fr, span, 1.f, tp, 1.f, 1e-3f, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
+                sc_volume_robust_params vr = good;
+                const int verdict = sc_hip_volume_robust_check(&vr, &l);
+                if (lap_base ? verdict == SC_OK : verdict != k.want) return fail("volume_robust_check");
+                if (lap_base || k.want != SC_OK) continue;
+                for (float bad : { 0.f, -1.f, 2.5f, nan }) {
+                    vr = good; vr.p_grad = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_grad)");
+                    vr = good; vr.p_time = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_time)");
+                    vr = good; vr.p_data = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_data)");
+                }
+                for (float bad : { 0.f, -1.f, nan, inf }) {
+                    vr = good; vr.eps_grad = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_grad)");
+                    vr = good; vr.eps_time = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_time)");
+                    vr = good; vr.p_data = 1.f; vr.eps_data = bad;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_data)");
+                    vr = good; vr.eps_data = bad;          // (an exponent of 2 does not look at its eps)
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_OK) return fail("volume_robust_check (eps_data unused)");
+                }
+                vr = good; vr.round_tol = nan;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (round_tol)");
+                vr = good; vr.round_tol = -1.f;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_OK) return fail("volume_robust_check (round_tol < 0)");
+                for (int bits : { SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS, SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS }) {
+                    vr = good; vr.kind = k.kind | bits;
+                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (coupling bits)");
+                }
+                vr = good; vr.frames = tp ? 2 : 1;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (too few frames)");
+                vr = good; vr.frames = SC_POISSON_MAX_PLANES / k.c + 1;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_SIZE) return fail("volume_robust_check (beyond the plane limit)");
+                vr = good; vr.frame_stride = span - 1;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (frame_stride)");
+                vr = good; vr.tau = nan;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tau)");
+                vr = good; vr.time_periodic = 2;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (time_periodic)");
+                vr = good; vr.tol = inf;
+                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tol)");
+            }
+            // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
             sc_robust_params r{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
             const int got = sc_hip_robust_check(&r, &l);
             if (lap_base ? got != SC_ERR_BAD_ARG : got != k.want) return fail("robust_check");

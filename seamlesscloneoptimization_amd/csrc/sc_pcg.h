@@ -1,8 +1,9 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_volume.hip: a family's statistics, set-up and operator) and the link operator of the WLS and the robust call
-// (WlsOperator, sc_wls_api.cpp).
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
+// of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the two
+// robust calls' rounds share (RobustRounds, robust_chunk; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
 // Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
 // float4 access); plane p = member C + channel.  Tiling of the launches that walk a plane in 2-D (statistics, set-up, operator): column
@@ -47,6 +48,7 @@ void pcg_release(Instance *I);             // frees Instance::pcg and all it hol
 // defaults of precond (direct_jobs_solve with precond_constant's lam), out, work_geo and chunk_planes, which only the volume family
 // replaces.
 struct PcgChunk;
+struct RobustRounds;
 struct PcgOperator {
     const int nstat;                       // doubles per part of the statistics launch
     const int nround;                      // doubles per part a family's own later launches sum (PcgChunk::d_round; the robust call's rounds)
@@ -73,6 +75,8 @@ struct PcgOperator {
     // the preconditioner: out = M^-1 in on the chunk's work planes.  The default: (A - lam) out = in through direct_jobs_solve, plane
     // by plane (lam: precond_constant's)
     virtual int precond(const PcgChunk &c, float lam, bool fp64, const float *in, float *out);
+    // the reweighting rounds of an operator that robust_chunk may drive (the robust call's, the robust volume call's); NULL: it has none
+    virtual RobustRounds *rounds() { return nullptr; }
     // the sum of field f of one plane's statistics over its first `parts` parts
     double stat_sum(const double *plane, int parts, int f) const
     {
@@ -286,8 +290,9 @@ constexpr int VOLUME_STATS = 11, VOLUME_STATS_PLAIN = 5;
 // its live temporal links lt (the earlier frame owns a link, frame T - 1 the wrapping one) | how many there are | how many are invalid.
 // A call without any link array under free time (the first record's sx and smt NULL, vg.periodic 0) has parts of the first VOLUME_STATS_PLAIN
 // fields alone, as sc_hip_volume always had: stats[(plane * PCG_PARTS + i) * VOLUME_STATS_PLAIN + ..].
+// full: VOLUME_STATS fields per part whatever the call carries (the robust volume call: its rounds need the links' counts).
 void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
-                         double *stats, hipStream_t s);
+                         double *stats, hipStream_t s, bool full = false);
 // R = b (the order: seamlessclone_hip.h, the volume sections); E / S / F = the link to the next column / row / frame where both ends are
 // UNKNOWN (F in the last frame's rows: the wrapping link, 0 with free time); Dg = the sum of the incident live links plus w; all five 0
 // at every pixel that is not UNKNOWN; bb = the parts of b . b
@@ -305,12 +310,81 @@ void launch_volume_dct(const PcgGeo &wg, const VolumeGeo &vg, int planes, bool t
 // the jobs' out, frame by frame: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
 void launch_volume_out(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                        const float *U, hipStream_t s);
+// The operator of the volume families (sc_volume_api.cpp; its head comment says what it tells the iteration): sc_hip_volume's and
+// sc_hip_volume_wls's, and through VolumeRobustOperator every round's of the robust volume call.  links, tlinks: the call's volumes
+// carry smooth_x / smooth_y, smooth_t (a robust round: its own links, always); full_stats: the statistics in their VOLUME_STATS form
+// whatever the call carries.
+struct VolumeOperator : PcgOperator {
+    Instance *const I;
+    const int T;
+    const long long fs;
+    const float tau, plam, psmooth, ptau;
+    const bool periodic;
+    bool links, tlinks;
+    // of the volumes that stay: the sums of w and of the UNKNOWN - KNOWN links, the UNKNOWN pixels, the sum and the number of the spatial
+    // links live in the region and of the live temporal links
+    double wsum = 0.0, unknowns = 0.0, uksum = 0.0, ssum = 0.0, scount = 0.0, tsum = 0.0, tcount = 0.0;
+    float u0_scale = 1.f;                                          // 1 / s-bar
+    VolumeOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_, int nround_ = 0, bool full_stats = false)
+        : PcgOperator(full_stats || links_ || tlinks_ || p->time_periodic ? VOLUME_STATS : VOLUME_STATS_PLAIN, nround_), I(I_), T(p->frames),
+          fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda), psmooth(p->precond_smooth), ptau(p->precond_tau),
+          periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
+    VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau, periodic ? 1 : 0 }; }
+    int chunk_planes(int C) const override { return C * T; }
+    PcgGeo work_geo(const MixedGeo &mg) const override { return volume_work_geo(mg, T); }
+    void begin() override;
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override;
+    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override;
+    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override;      // w-bar; the table along the frames and the modes' shifts go to the device here
+    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override;
+    // PcgState::tab: the shifts (double, planes * T of them at most SC_POISSON_MAX_PLANES) | the T x T table (float)
+    double *shifts() const { return (double *)I->pcg->tab.p; }
+    float *table() const { return (float *)(shifts() + SC_POISSON_MAX_PLANES); }
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override;
+    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override;
+    int precond(const PcgChunk &c, float, bool fp64, const float *in, float *out) override;
+    void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override;
+};
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;
 // eps2 = eps * eps rounded to float32, half_exp = (r - 2) / 2, scale = 2 / r
 struct RobustTerm { int mode; float eps2, half_exp, scale; };
+inline RobustTerm robust_term(float r, float eps)
+{
+    RobustTerm t;
+    t.mode = r == 2.f ? 0 : r == 1.f ? 1 : 2;
+    t.eps2 = t.mode ? eps * eps : 0.f;
+    t.half_exp = (r - 2.f) * 0.5f;
+    t.scale = 2.f / r;
+    return t;
+}
+// what the robust calls' checks refuse of an exponent and of its eps
+inline bool robust_bad_exponent(float r) { return !(r > 0.f && r <= 2.f); }
+inline bool robust_bad_eps(float r, float eps) { return r != 2.f && !(std::isfinite(eps) && eps > 0.f); }
+// What robust_chunk asks of an operator beyond PcgOperator (PcgOperator::rounds): whether every exponent is 2 (no round runs), the
+// call's max_rounds and round_tol as the caller gave them, and reweigh -- a later round: the system at the chunk's iterate c.U put in
+// place of the operator's, its means, and that iterate's energy per unit of the round rule (one host wait).
+struct RobustRounds {
+    virtual ~RobustRounds() = default;
+    virtual bool quadratic() const = 0;
+    virtual int max_rounds() const = 0;
+    virtual float round_tol() const = 0;
+    virtual int reweigh(PcgChunk &c, std::vector<double> &energy) = 0;
+};
+// One chunk of a robust call (sc_robust_api.cpp; a PcgChunkFn): the quadratic round, the reweighting rounds of op.rounds(), the output,
+// PcgState's trace
+int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res, int &job_errors);
 constexpr int ROBUST_SUMS = 3;
+// the robust volume call's launch (sc_volume_robust.hip): launch_volume_setup in its guidance form with s = c rho(link residual of U)
+// on every live link -- c: sx, sy (NULL: 1) with `grad`, lt = tau * smt (NULL: tau) with `time` -- and w' = w rho(U - d) with `data`;
+// the value of u across a link is data's at a KNOWN pixel, boundary's on a Dirichlet line, U's at an UNKNOWN one.  sums[(plane *
+// PCG_PARTS + i) * VOLUME_ROBUST_SUMS + ..] = the part's sum of w' | of its live spatial links s | of its live temporal links | of its
+// UNKNOWN - KNOWN links | the energy of U; every live link once, by launch_volume_stats' owner rule
+constexpr int VOLUME_ROBUST_SUMS = 5;
+void launch_volume_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const float *U, float *R, float *E, float *S,
+                                float *F, float *Dg, double *bb, double *sums, hipStream_t s);
 // k_wls_setup with s = c rho_p(link residual of U), w' = w rho_q(U - d) (c = sx, sy; NULL for every job: 1): R = b, E, S, Dg as
 // launch_wls_setup in its guidance form, bb = the parts of b . b, sums[(plane * PCG_PARTS + i) * ROBUST_SUMS + ..] = the part's sum of
 // w' | the sum of its live links s, each counted once as launch_wls_stats counts them | the energy of U

@@ -1,6 +1,7 @@
 // sc_pcg_device.h -- what the kernels of the conjugate-gradient families share (sc_pcg.hip, sc_weighted.hip, sc_wls.hip): the workgroup's
 // size and its sum in one fixed order, and one walk of each kind over the work planes (sc_pcg.h, PcgGeo) -- the element-wise walk of a
-// segment's float4 groups, the band of a statistics or set-up launch, and the operator's walk with a family's coefficients as a policy.
+// segment's float4 groups, the band of a statistics or set-up launch, and the operator's walk with a family's coefficients as a policy,
+// and the robust penalties' arithmetic (sc_robust.hip, sc_volume_robust.hip).
 #pragma once
 #include "sc_pcg.h"
 #include "sc_wave.h"
@@ -70,6 +71,32 @@ __device__ __forceinline__ void part_store(double v, double *ws, const PcgGeo &w
 {
     v = block_sum(v, ws);
     if (threadIdx.x == 0) parts[((size_t)blockIdx.z * PCG_PARTS + blockIdx.y * wg.cg + blockIdx.x) * per + f] = v;
+}
+
+// ---- the robust penalties (sc_robust.hip, sc_volume_robust.hip): one term as RobustTerm states it (sc_pcg.h)
+// rho_r(t), and q = t t + eps eps (r = 2: t t; eps is unused there)
+__device__ __forceinline__ float robust_rho(const RobustTerm &r, float t, float &q)
+{
+    q = rounded_product(t, t);
+    if (r.mode == 0) return 1.f;
+    q = q + r.eps2;
+    return r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
+}
+// one term of the energy, base phi_r(t), in double from rho's float32 values: (2 / r) q rho = (2 / r) q^(r/2)
+__device__ __forceinline__ double robust_phi(const RobustTerm &r, float base, float q, float rho)
+{
+    return (double)base * ((double)r.scale * ((double)q * (double)rho));
+}
+// a link: its weight s = base rho_p(t), t = (hi - lo) - g, and its energy
+struct RobustLink { float s; double e; };
+__device__ __forceinline__ RobustLink robust_link(const RobustTerm &r, float base, float hi, float lo, float g)
+{
+    float q;
+    const float t = (hi - lo) - g, rho = robust_rho(r, t, q);
+    RobustLink k;
+    k.s = r.mode == 0 ? base : rounded_product(base, rho);
+    k.e = robust_phi(r, base, q, rho);
+    return k;
 }
 
 // The operator's launch (grid: cg x bands x planes), one kernel for every family.  RES false: Q = L P and the parts of P . Q;  true:

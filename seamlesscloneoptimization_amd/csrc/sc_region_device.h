@@ -1,5 +1,6 @@
-// sc_region_device.h -- what the kernels of the region and the volume family share (sc_region.hip, sc_volume.hip): a state element's
-// meaning and the four spatial neighbours of a pixel as the region call sees them.
+// sc_region_device.h -- what the kernels of the region and the volume families share (sc_region.hip, sc_volume.hip, sc_volume_robust.hip):
+// a state element's meaning, the four spatial neighbours of a pixel as the region call sees them, and a volume's frames: the row of a
+// work plane of stacked frames, the two temporal neighbours, a temporal link's weight.
 #pragma once
 #include "sc_pcg_device.h"
 
@@ -26,5 +27,38 @@ struct Around {
         ks = !(Y < g.H - 1 || py) ? NB_NONE : (Y == g.H - 2 && mixed_high_d(wg.ay)) ? NB_DIRICHLET : state_kind(st[os]);
     }
 };
+
+// ---- the volume family (sc_volume.hip, sc_volume_robust.hip): frames stacked along y, temporal neighbours
+// row y of a work plane: its frame, its row of unknowns inside the frame
+struct FrameRow {
+    int t, yy;
+    __device__ __forceinline__ FrameRow(const VolumeGeo &vg, int y) { t = y / vg.ny; yy = y - t * vg.ny; }
+};
+
+// the pixel across a temporal link: NB_NONE beyond either end of time
+__device__ __forceinline__ int time_kind(const float *__restrict__ st, long long o, bool exists) { return exists ? state_kind(st[o]) : NB_NONE; }
+
+// The two temporal neighbours of frame t's element at offset o: where they lie -- the wrap of periodic time included -- and whether
+// they exist.  The link to the previous frame, its weight and its guidance value are stored at ob, those to the next frame at o.
+struct TimeAround {
+    long long ob, of;
+    bool hb, hf;
+    // wraps false (a launch under free time, known at compile time): one frame before and behind, nothing else is computed
+    __device__ __forceinline__ TimeAround(const VolumeGeo &vg, int t, long long o, bool wraps)
+    {
+        if (!wraps) {
+            ob = o - vg.fs; of = o + vg.fs;
+            hb = t > 0; hf = t < vg.T - 1;
+            return;
+        }
+        const long long wrap = (long long)(vg.T - 1) * vg.fs;
+        ob = t > 0 ? o - vg.fs : o + wrap;
+        of = t < vg.T - 1 ? o + vg.fs : o - wrap;
+        hb = t > 0 || vg.periodic;
+        hf = t < vg.T - 1 || vg.periodic;
+    }
+};
+// the weight of the temporal link stored at element e: tau * smooth_t, one rounded product (no array: tau)
+__device__ __forceinline__ float time_link(const float *__restrict__ smt, long long e, float tau) { return smt ? rounded_product(tau, smt[e]) : tau; }
 
 } // namespace sc

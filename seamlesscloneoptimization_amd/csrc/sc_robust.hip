@@ -18,31 +18,6 @@ namespace sc {
 
 namespace {
 
-// rho_r(t), and q = t t + eps eps (r = 2: t t; eps is unused there)
-__device__ __forceinline__ float robust_rho(const RobustTerm &r, float t, float &q)
-{
-    q = rounded_product(t, t);
-    if (r.mode == 0) return 1.f;
-    q = q + r.eps2;
-    return r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
-}
-// one term of the energy, base phi_r(t), in double from rho's float32 values: (2 / r) q rho = (2 / r) q^(r/2)
-__device__ __forceinline__ double robust_phi(const RobustTerm &r, float base, float q, float rho)
-{
-    return (double)base * ((double)r.scale * ((double)q * (double)rho));
-}
-// a link: its weight s = base rho_p(t), t = (hi - lo) - g, and its energy
-struct RobustLink { float s; double e; };
-__device__ __forceinline__ RobustLink robust_link(const RobustTerm &r, float base, float hi, float lo, float g)
-{
-    float q;
-    const float t = (hi - lo) - g, rho = robust_rho(r, t, q);
-    RobustLink k;
-    k.s = r.mode == 0 ? base : rounded_product(base, rho);
-    k.e = robust_phi(r, base, q, rho);
-    return k;
-}
-
 // BASE: the caller's base links c (t.sx, t.sy); false: all 1
 template <bool BASE>
 __global__ __launch_bounds__(WL) void k_robust_setup(PoissonGeo g, PcgGeo wg, WlsJobs t, RobustTerm tg, RobustTerm td, const float *__restrict__ U,

@@ -28,17 +28,14 @@ using namespace sc;
 
 namespace {
 
-bool bad_exponent(float r) { return !(r > 0.f && r <= 2.f); }
-bool bad_eps(float r, float eps) { return r != 2.f && !(std::isfinite(eps) && eps > 0.f); }
-
 constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
 
 int robust_validate(const sc_robust_params *p, const sc_poisson_layout *l, const char **why)
 {
     const int kind = p ? p->kind & ~COUPLING_BITS : 0;          // the two bits are this call's own: the family's kinds know nothing of them
     const char *own = !p ? nullptr
-                    : bad_exponent(p->p_grad) || bad_exponent(p->p_data) ? "p_grad and p_data must lie in (0, 2]"
-                    : bad_eps(p->p_grad, p->eps_grad) || bad_eps(p->p_data, p->eps_data) ? "eps_grad and eps_data must be finite and > 0 where their exponent is not 2"
+                    : robust_bad_exponent(p->p_grad) || robust_bad_exponent(p->p_data) ? "p_grad and p_data must lie in (0, 2]"
+                    : robust_bad_eps(p->p_grad, p->eps_grad) || robust_bad_eps(p->p_data, p->eps_data) ? "eps_grad and eps_data must be finite and > 0 where their exponent is not 2"
                     : !std::isfinite(p->tol) ? "tol must be finite"
                     : !std::isfinite(p->round_tol) ? "round_tol must be finite"
                     : poisson_base(kind) == SC_POISSON_LAPLACIAN ? "a robust solve needs the guidance itself: the base kind must be SC_POISSON_GUIDANCE" : nullptr;
@@ -49,20 +46,10 @@ int robust_validate(const sc_robust_params *p, const sc_poisson_layout *l, const
 constexpr const char *METHOD_WHY = "a robust solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
 constexpr const char *FP64_WHY = "a robust solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
 
-RobustTerm robust_term(float r, float eps)
-{
-    RobustTerm t;
-    t.mode = r == 2.f ? 0 : r == 1.f ? 1 : 2;
-    t.eps2 = t.mode ? eps * eps : 0.f;
-    t.half_exp = (r - 2.f) * 0.5f;
-    t.scale = 2.f / r;
-    return t;
-}
-
 int carries_of(bool base_links) { return FLOAT_DATA | FLOAT_WEIGHT | (base_links ? FLOAT_SMOOTH : 0); }
 
 // The WLS operator with the links of the current round: round 0 from the caller's arrays, later rounds from the iterate.
-struct RobustOperator final : WlsOperator {
+struct RobustOperator final : WlsOperator, RobustRounds {
     const sc_robust_params prm;
     const RobustTerm grad, data;
     const int bits;          // ROBUST_ISO | ROBUST_JOINT as the caller set them
@@ -70,12 +57,15 @@ struct RobustOperator final : WlsOperator {
         : WlsOperator(I_, base_links, 0.f, 0.f, ROBUST_SUMS + 1), prm(*p), grad(robust_term(p->p_grad, p->eps_grad)),
           data(robust_term(p->p_data, p->eps_data)),
           bits(((p->kind & SC_ROBUST_ISOTROPIC) ? ROBUST_ISO : 0) | ((p->kind & SC_ROBUST_JOINT_CHANNELS) ? ROBUST_JOINT : 0)) {}
-    bool quadratic() const { return grad.mode == 0 && data.mode == 0; }
+    RobustRounds *rounds() override { return this; }
+    bool quadratic() const override { return grad.mode == 0 && data.mode == 0; }
+    int max_rounds() const override { return prm.max_rounds; }
+    float round_tol() const override { return prm.round_tol; }
     // the coupling that changes anything: none with p_grad = 2 (every form is sum c t^2), no joint form of one channel
     int coupling(int C) const { return grad.mode == 0 ? 0 : C == 1 ? bits & ~ROBUST_JOINT : bits; }
     // A later round: the system at the chunk's iterate, its means, and that iterate's energy (one wait) -- per plane, or per job where
     // the channels are coupled (the round rule's units)
-    int reweigh(PcgChunk &c, std::vector<double> &energy)
+    int reweigh(PcgChunk &c, std::vector<double> &energy) override
     {
         PcgState &S = *I->pcg;
         const int cpl = coupling(c.g.C), per = (cpl & ROBUST_JOINT) ? c.g.C : 1;
@@ -109,12 +99,17 @@ struct RobustOperator final : WlsOperator {
     }
 };
 
-// One chunk: the quadratic round, the reweighting rounds, the output.  res: the total of the inner iterations, whether the round rule
+PcgCall robust_call(int kind, const sc_robust_params *p) { return PcgCall{ kind, p->tol, p->max_iters, 400 }; }
+
+} // namespace
+
+// One chunk of either robust call (the operator's rounds(): RobustOperator's here, VolumeRobustOperator's in sc_volume_api.cpp): the
+// quadratic round, the reweighting rounds, the output.  res: the total of the inner iterations, whether the round rule
 // was met (always, when p = q = 2), the last inner solve's residual.  The code: SC_ERR_NOT_CONVERGED when an inner solve ran out of
 // max_iters (the rounds go on from its last iterate), else SC_OK -- running out of rounds included.
-int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &base, int *const *rcs, int m, PcgChunkResult &res, int &job_errors)
+int sc::robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res, int &job_errors)
 {
-    RobustOperator &op = static_cast<RobustOperator &>(base);
+    RobustRounds &rounds = *op.rounds();
     PcgState &S = *I->pcg;
     S.trace_energy.clear();
     S.trace_iters.clear();
@@ -127,13 +122,13 @@ int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOpera
     PcgChunkResult one;
     if ((rc = pcg_chunk_iterate(c, op, false, one))) return rc;
     int total = one.iters;
-    bool inner = one.converged, met = op.quadratic();
+    bool inner = one.converged, met = rounds.quadratic();
     S.trace_iters.push_back(one.iters);
-    const int max_rounds = op.quadratic() ? 0 : op.prm.max_rounds > 0 ? op.prm.max_rounds : 15;
-    const double round_tol = op.prm.round_tol == 0.f ? 1e-4 : (double)op.prm.round_tol;
+    const int max_rounds = rounds.quadratic() ? 0 : rounds.max_rounds() > 0 ? rounds.max_rounds() : 15;
+    const double round_tol = rounds.round_tol() == 0.f ? 1e-4 : (double)rounds.round_tol();
     std::vector<double> prev, cur;
     for (int k = 1;; ++k) {
-        if ((rc = op.reweigh(c, cur))) return rc;          // the energy of round k - 1's iterate, and round k's system
+        if ((rc = rounds.reweigh(c, cur))) return rc;          // the energy of round k - 1's iterate, and round k's system
         double sum = 0.0;
         for (double e : cur) sum += e;
         S.trace_energy.push_back(sum);
@@ -154,10 +149,6 @@ int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOpera
     res.rel = one.rel;
     return pcg_chunk_finish(c, op, inner ? SC_OK : SC_ERR_NOT_CONVERGED);
 }
-
-PcgCall robust_call(int kind, const sc_robust_params *p) { return PcgCall{ kind, p->tol, p->max_iters, 400 }; }
-
-} // namespace
 
 extern "C" {
 

@@ -25,39 +25,7 @@ namespace sc {
 
 namespace {
 
-// row y of a work plane: its frame, its row of unknowns inside the frame
-struct FrameRow {
-    int t, yy;
-    __device__ __forceinline__ FrameRow(const VolumeGeo &vg, int y) { t = y / vg.ny; yy = y - t * vg.ny; }
-};
-
-// the pixel across a temporal link: NB_NONE beyond either end of time
-__device__ __forceinline__ int time_kind(const float *__restrict__ st, long long o, bool exists) { return exists ? state_kind(st[o]) : NB_NONE; }
-
 __device__ __forceinline__ bool bad_link(float v) { return !(v > 0.f) || v > 3.4028234e38f; }
-
-// The two temporal neighbours of frame t's element at offset o: where they lie -- the wrap of periodic time included -- and whether
-// they exist.  The link to the previous frame, its weight and its guidance value are stored at ob, those to the next frame at o.
-struct TimeAround {
-    long long ob, of;
-    bool hb, hf;
-    // wraps false (a launch under free time, known at compile time): one frame before and behind, nothing else is computed
-    __device__ __forceinline__ TimeAround(const VolumeGeo &vg, int t, long long o, bool wraps)
-    {
-        if (!wraps) {
-            ob = o - vg.fs; of = o + vg.fs;
-            hb = t > 0; hf = t < vg.T - 1;
-            return;
-        }
-        const long long wrap = (long long)(vg.T - 1) * vg.fs;
-        ob = t > 0 ? o - vg.fs : o + wrap;
-        of = t < vg.T - 1 ? o + vg.fs : o - wrap;
-        hb = t > 0 || vg.periodic;
-        hf = t < vg.T - 1 || vg.periodic;
-    }
-};
-// the weight of the temporal link stored at element e: tau * smooth_t, one rounded product (no array: tau)
-__device__ __forceinline__ float time_link(const float *__restrict__ smt, long long e, float tau) { return smt ? rounded_product(tau, smt[e]) : tau; }
 
 // Per plane and part (VOLUME_STATS doubles): the sum of w over the UNKNOWN pixels | how many of those w are invalid | the UNKNOWN
 // pixels | the sum of the UNKNOWN - KNOWN links' weights, each counted once by its low end (k_region_stats' rule; the earlier frame owns
@@ -343,11 +311,11 @@ template <bool LNK> void setup_form(bool lap, bool now, dim3 grid, hipStream_t s
 } // namespace
 
 void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
-                         double *stats, hipStream_t s)
+                         double *stats, hipStream_t s, bool full)
 {
     for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
-        const bool general = t.sx[0] || t.smt[0] || vg.periodic;
+        const bool general = full || t.sx[0] || t.smt[0] || vg.periodic;
         double *st = stats + (size_t)g.C * i0 * PCG_PARTS * (general ? VOLUME_STATS : VOLUME_STATS_PLAIN);
         if (general) hipLaunchKernelGGL(k_volume_stats<true>, grid, dim3(WL), 0, s, g, wg, vg, t, st);
         else hipLaunchKernelGGL(k_volume_stats<false>, grid, dim3(WL), 0, s, g, wg, vg, t, st);

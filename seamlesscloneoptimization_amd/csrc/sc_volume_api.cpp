@@ -1,5 +1,5 @@
 // sc_volume_api.cpp -- the volume solves on float32 frame stacks (sc_hip_volume_check, sc_hip_volume_device, sc_hip_volume, and the
-// same three of sc_hip_volume_wls): the region call's problem on every one of `frames` images that share a layout, coupled by temporal
+// same three of sc_hip_volume_wls and of sc_hip_volume_robust): the region call's problem on every one of `frames` images that share a layout, coupled by temporal
 // links (sc_volume.hip: the system and its work planes).  sc_hip_volume has unit spatial links, temporal links of the constant weight
 // tau and free ends of time; sc_hip_volume_wls takes per-link weights smooth_x, smooth_y, smooth_t and, if asked, periodic time.  One
 // operator serves both: sc_hip_volume is the call without link arrays under free time.  The entry code and the iteration are the
@@ -19,6 +19,10 @@
 //               direct_jobs_solve over all frames * channels * volumes planes with the shift (w-bar + tau-bar mu_k) / s-bar of mode k,
 //               k_volume_dct transposed: exact for constant coefficients.  The factor 1 / s-bar goes once on u0 (scale_start).
 // All six side arrays of a volume come in PcgOperator::ds beside the job (NULL where the call carries none: the front end's word).
+// sc_hip_volume_robust (its own three entries, below): Lp penalties on the spatial links, the temporal links and the data term.  Round 0
+// is sc_hip_volume_wls's chunk with default precond_*; VolumeRobustOperator::reweigh puts the system at the iterate in its place
+// (k_volume_robust_setup, sc_volume_robust.hip) and the round's sums in place of the statistics'; the rounds are robust_chunk's
+// (sc_robust_api.cpp), which drives this operator and the robust call's through RobustRounds.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -74,142 +78,223 @@ int carries_of(bool weight, bool links, bool tlinks)
     return FLOAT_DATA | FLOAT_STATE | FLOAT_GT | (weight ? FLOAT_WEIGHT : 0) | (links ? FLOAT_SMOOTH : 0) | (tlinks ? FLOAT_SMOOTH_T : 0);
 }
 
-// links, tlinks: the call's volumes carry smooth_x / smooth_y, smooth_t
-struct VolumeOperator : PcgOperator {
-    Instance *const I;
-    const int T;
-    const long long fs;
-    const float tau, plam, psmooth, ptau;
-    const bool periodic, links, tlinks;
-    // of the volumes that stay: the sums of w and of the UNKNOWN - KNOWN links, the UNKNOWN pixels, the sum and the number of the spatial
-    // links live in the region and of the live temporal links
-    double wsum = 0.0, unknowns = 0.0, uksum = 0.0, ssum = 0.0, scount = 0.0, tsum = 0.0, tcount = 0.0;
-    float u0_scale = 1.f;                                          // 1 / s-bar
-    VolumeOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_)
-        : PcgOperator(links_ || tlinks_ || p->time_periodic ? VOLUME_STATS : VOLUME_STATS_PLAIN), I(I_), T(p->frames), fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda), psmooth(p->precond_smooth),
-          ptau(p->precond_tau), periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
-    VolumeGeo geo(const PcgGeo &wg) const { return VolumeGeo{ T, wg.ny / T, fs, tau, periodic ? 1 : 0 }; }
-    int chunk_planes(int C) const override { return C * T; }
-    PcgGeo work_geo(const MixedGeo &mg) const override { return volume_work_geo(mg, T); }
-    void begin() override { wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0; }
-    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
-    {
-        launch_volume_stats(g, wg, geo(wg), dj.data(), ds.data(), m, d_stats, s);
+} // namespace
+
+namespace sc {
+
+void VolumeOperator::begin() { wsum = unknowns = uksum = ssum = scount = tsum = tcount = 0.0; }
+
+void VolumeOperator::stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s)
+{
+    launch_volume_stats(g, wg, geo(wg), dj.data(), ds.data(), m, d_stats, s, nstat == VOLUME_STATS);
+}
+
+const char *VolumeOperator::judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet)
+{
+    double job[VOLUME_STATS] = {};
+    const int nf = nstat;      // (a call without link arrays under free time: the link fields do not exist)
+    bool loose = false;
+    for (int c = 0; c < g.C; ++c) {      // a plane is the channel's whole volume: the pin check is the volume's, not a frame's
+        const double *plane = st + (size_t)c * PCG_PARTS * nstat;
+        double f[VOLUME_STATS] = {};
+        for (int i = 0; i < nf; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
+        loose = loose || (no_dirichlet && f[2] > 0.0 && !(f[3] > 0.0) && !(f[0] > 0.0));
     }
-    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
-    {
-        double job[VOLUME_STATS] = {};
-        const int nf = nstat;      // (a call without link arrays under free time: the link fields do not exist)
-        bool loose = false;
-        for (int c = 0; c < g.C; ++c) {      // a plane is the channel's whole volume: the pin check is the volume's, not a frame's
-            const double *plane = st + (size_t)c * PCG_PARTS * nstat;
-            double f[VOLUME_STATS] = {};
-            for (int i = 0; i < nf; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
-            loose = loose || (no_dirichlet && f[2] > 0.0 && !(f[3] > 0.0) && !(f[0] > 0.0));
-        }
-        if (job[4] != 0.0) return "a state element is not 0, 1 or 2";
-        if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
-        if (job[7] != 0.0 || !std::isfinite(job[5])) return "a spatial link weight live in the region is not finite or not > 0";
-        if (job[10] != 0.0 || !std::isfinite(job[8])) return "a live temporal link weight is not finite or not > 0";
-        if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link in space or time and no data weight";
-        wsum += job[0];
-        unknowns += job[2];
-        uksum += job[3];
-        ssum += job[5];
-        scount += job[6];
-        tsum += job[8];
-        tcount += job[9];
-        return nullptr;
+    if (job[4] != 0.0) return "a state element is not 0, 1 or 2";
+    if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
+    if (job[7] != 0.0 || !std::isfinite(job[5])) return "a spatial link weight live in the region is not finite or not > 0";
+    if (job[10] != 0.0 || !std::isfinite(job[8])) return "a live temporal link weight is not finite or not > 0";
+    if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link in space or time and no data weight";
+    wsum += job[0];
+    unknowns += job[2];
+    uksum += job[3];
+    ssum += job[5];
+    scount += job[6];
+    tsum += job[8];
+    tcount += job[9];
+    return nullptr;
+}
+
+float VolumeOperator::precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv)
+{
+    const double sbar = psmooth > 0.f ? (double)psmooth : !links || !(scount > 0.0) ? 1.0 : ssum / scount;
+    const double tbar = ptau > 0.f ? (double)ptau : !tlinks || !(tcount > 0.0) ? (double)tau : tsum / tcount;
+    // (a chunk without any UNKNOWN pixel: b = 0 on every plane, any regular M serves)
+    const double wbar = plam > 0.f ? (double)plam : unknowns > 0.0 ? (wsum + uksum) / unknowns : 1.0;
+    // without a Dirichlet line the rectangle's A is singular: judge kept only volumes whose every channel is pinned
+    assert(!(mixed_zero_eig(wg.ax) && mixed_zero_eig(wg.ay)) || wbar > 0.0);
+    u0_scale = (float)(1.0 / sbar);
+    launch_volume_tables(T, g.C * mv, periodic, wbar, tbar, sbar, table(), shifts(), I->stream);
+    return (float)wbar;
+}
+
+// the factor 1 / s-bar that the modes' solves leave out (1: no launch)
+void VolumeOperator::scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s)
+{
+    if (u0_scale != 1.f) launch_pcg_scale(wg, planes, U, u0_scale, s);
+}
+
+int VolumeOperator::setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb)
+{
+    PcgState &S = *I->pcg;
+    int rc;
+    for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
+        if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
+    if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
+    launch_volume_setup(g, wg, geo(wg), lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, bb,
+                        I->stream);
+    return SC_OK;
+}
+
+void VolumeOperator::apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s)
+{
+    PcgState &S = *I->pcg;
+    launch_volume_op(wg, geo(wg), planes, residual, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.f.p, (const float *)S.dg.p, Q,
+                     parts, s);
+}
+
+// out = M^-1 in: forward along the frames into PcgState::dct, every mode's screened solve there in place (the first transform launch
+// has read a plane before the last one writes it), back into out.  A work plane is one job of T channels, a frame apart.
+int VolumeOperator::precond(const PcgChunk &c, float, bool fp64, const float *in, float *out)
+{
+    const PcgGeo &wg = c.wg;
+    const VolumeGeo vg = geo(wg);
+    float *X = (float *)I->pcg->dct.p;
+    launch_volume_dct(wg, vg, c.planes, false, table(), in, X, I->stream);
+    const PoissonGeo pg{ c.g.W, c.g.H, T, 1, (long long)wg.nx, (long long)wg.nx * vg.ny };
+    const long long shift = (long long)wg.x0 + (long long)wg.y0 * wg.nx;
+    std::vector<PoissonJobDev> pj(c.planes);
+    for (int k = 0; k < c.planes; ++k) {
+        float *x = X + (long long)k * wg.stride - shift;
+        pj[k] = PoissonJobDev{ nullptr, nullptr, x, nullptr, x };
     }
-    // w-bar; the table along the frames and the modes' shifts of this chunk go to the device here
-    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
-    {
-        const double sbar = psmooth > 0.f ? (double)psmooth : !links || !(scount > 0.0) ? 1.0 : ssum / scount;
-        const double tbar = ptau > 0.f ? (double)ptau : !tlinks || !(tcount > 0.0) ? (double)tau : tsum / tcount;
-        // (a chunk without any UNKNOWN pixel: b = 0 on every plane, any regular M serves)
-        const double wbar = plam > 0.f ? (double)plam : unknowns > 0.0 ? (wsum + uksum) / unknowns : 1.0;
-        // without a Dirichlet line the rectangle's A is singular: judge kept only volumes whose every channel is pinned
-        assert(!(mixed_zero_eig(wg.ax) && mixed_zero_eig(wg.ay)) || wbar > 0.0);
-        u0_scale = (float)(1.0 / sbar);
-        launch_volume_tables(T, g.C * mv, periodic, wbar, tbar, sbar, table(), shifts(), I->stream);
-        return (float)wbar;
-    }
-    // the factor 1 / s-bar that the modes' solves leave out (1: no launch)
-    void scale_start(const PcgGeo &wg, int planes, float *U, hipStream_t s) override
-    {
-        if (u0_scale != 1.f) launch_pcg_scale(wg, planes, U, u0_scale, s);
-    }
-    // PcgState::tab: the shifts (double, planes * T of them at most SC_POISSON_MAX_PLANES) | the T x T table (float)
-    double *shifts() const { return (double *)I->pcg->tab.p; }
-    float *table() const { return (float *)(shifts() + SC_POISSON_MAX_PLANES); }
-    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
-    {
-        PcgState &S = *I->pcg;
-        int rc;
-        for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
-            if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
-        if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
-        launch_volume_setup(g, wg, geo(wg), lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, bb,
-                            I->stream);
-        return SC_OK;
-    }
-    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
-    {
-        PcgState &S = *I->pcg;
-        launch_volume_op(wg, geo(wg), planes, residual, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.f.p, (const float *)S.dg.p, Q,
-                         parts, s);
-    }
-    // out = M^-1 in: forward along the frames into PcgState::dct, every mode's screened solve there in place (the first transform launch
-    // has read a plane before the last one writes it), back into out.  A work plane is one job of T channels, a frame apart.
-    int precond(const PcgChunk &c, float, bool fp64, const float *in, float *out) override
-    {
-        const PcgGeo &wg = c.wg;
-        const VolumeGeo vg = geo(wg);
-        float *X = (float *)I->pcg->dct.p;
-        launch_volume_dct(wg, vg, c.planes, false, table(), in, X, I->stream);
-        const PoissonGeo pg{ c.g.W, c.g.H, T, 1, (long long)wg.nx, (long long)wg.nx * vg.ny };
-        const long long shift = (long long)wg.x0 + (long long)wg.y0 * wg.nx;
-        std::vector<PoissonJobDev> pj(c.planes);
-        for (int k = 0; k < c.planes; ++k) {
-            float *x = X + (long long)k * wg.stride - shift;
-            pj[k] = PoissonJobDev{ nullptr, nullptr, x, nullptr, x };
-        }
-        const int rc = direct_jobs_solve(I, pg, c.mg, true, pj.data(), c.planes, fp64, 0.f, shifts());
-        if (rc) return rc;
-        launch_volume_dct(wg, vg, c.planes, true, table(), X, out, I->stream);
-        return SC_OK;
-    }
-    void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override
-    {
-        launch_volume_out(g, wg, geo(wg), dj.data(), ds.data(), mv, U, s);
-    }
-};
+    const int rc = direct_jobs_solve(I, pg, c.mg, true, pj.data(), c.planes, fp64, 0.f, shifts());
+    if (rc) return rc;
+    launch_volume_dct(wg, vg, c.planes, true, table(), X, out, I->stream);
+    return SC_OK;
+}
+
+void VolumeOperator::out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s)
+{
+    launch_volume_out(g, wg, geo(wg), dj.data(), ds.data(), mv, U, s);
+}
+
+} // namespace sc
+
+namespace {
 
 PcgCall volume_call(int kind, const sc_volume_wls_params *p)
 {
     return PcgCall{ kind, p->tol, p->max_iters, 400, p->frames, p->frame_stride, p->time_periodic ? p->frames : p->frames - 1 };
 }
 
-// the device call of both families, on either's jobs (links_of(job): its three link arrays, NULLs for sc_hip_volume's); the data term
-// and the link arrays: all volumes or none, as the first one has them -- smooth_x / smooth_y and smooth_t judged separately; a volume
-// that differs is refused with a reason of its own (as one with exactly one of smooth_x / smooth_y is by the front end)
-struct VolumeLinks { const float *sx, *sy, *smt; };
-template <class Job, class LinksOf>
-int volume_device_call(Instance *I, int kind, const sc_volume_wls_params *p, const sc_poisson_layout *l, Job *jobs, int n, bool bSync, LinksOf links_of)
+// the device call of the three families, on any one's jobs (links_of(job): its three link arrays and lap, NULLs where its job has none;
+// Op: the family's operator, made from the call's parameters and what its volumes carry); the data term and the link arrays: all
+// volumes or none, as the first one has them -- smooth_x / smooth_y and smooth_t judged separately; a volume that differs is refused
+// with a reason of its own (as one with exactly one of smooth_x / smooth_y is by the front end)
+struct VolumeLinks { const float *sx, *sy, *smt, *lap; };
+template <class Op, class Params, class Job, class LinksOf>
+int volume_device_call(Instance *I, const PcgCall &call, const Params *p, const sc_poisson_layout *l, Job *jobs, int n, bool bSync, LinksOf links_of,
+                       PcgChunkFn chunk = nullptr)
 {
-    const VolumeLinks first = jobs && n > 0 ? links_of(jobs[0]) : VolumeLinks{ nullptr, nullptr, nullptr };
+    const VolumeLinks first = jobs && n > 0 ? links_of(jobs[0]) : VolumeLinks{ nullptr, nullptr, nullptr, nullptr };
     const bool weight = jobs && n > 0 && jobs[0].weight, links = first.sx || first.sy, tlinks = first.smt != nullptr;
-    VolumeOperator op(I, p, links, tlinks);
-    return pcg_device_call(I, volume_call(kind, p), l, carries_of(weight, links, tlinks), jobs, n, [=](const Job &j) {
+    Op op(I, p, links, tlinks);
+    return pcg_device_call(I, call, l, carries_of(weight, links, tlinks), jobs, n, [=](const Job &j) {
         const VolumeLinks k = links_of(j);
-        FloatArrays a{ j.gx, j.gy, j.lap, j.data, j.weight, j.boundary, j.out, k.sx, k.sy, j.state };
+        FloatArrays a{ j.gx, j.gy, k.lap, j.data, j.weight, j.boundary, j.out, k.sx, k.sy, j.state };
         a.gt = j.gt;
         a.smooth_t = k.smt;
         a.refuse = !weight && j.weight ? "a volume has a weight where the first volume of the call has none"
                  : !links && (k.sx || k.sy) ? "a volume has smooth_x / smooth_y where the first volume of the call has none"
                  : !tlinks && k.smt ? "a volume has smooth_t where the first volume of the call has none" : nullptr;
-        return a; }, op, bSync);
+        return a; }, op, bSync, chunk);
 }
+
+// ---- the robust volume call: the volume operator with the links of the current round -- round 0 from the caller's arrays (the WLS
+// volume call's system, default precond_*), later rounds from the iterate (k_volume_robust_setup).  Its statistics are always the full
+// form: a round's means divide by the counts of live links.
+constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
+
+sc_volume_wls_params wls_params_of(const sc_volume_robust_params *p)
+{
+    return sc_volume_wls_params{ p->kind, p->frames, p->frame_stride, p->tau, p->time_periodic, p->tol, p->max_iters, 0.f, 0.f, 0.f };
+}
+
+int volume_robust_validate(const sc_volume_robust_params *p, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    if (!p) return volume_wls_validate(nullptr, l, why);
+    const sc_volume_wls_params q = wls_params_of(p);          // (the coupling bits stay in kind: the family's kinds refuse them)
+    const int rc = volume_wls_validate(&q, l, why);
+    if (rc) return rc;
+    const char *own = robust_bad_exponent(p->p_grad) || robust_bad_exponent(p->p_time) || robust_bad_exponent(p->p_data)
+                        ? "p_grad, p_time and p_data must lie in (0, 2]"
+                    : robust_bad_eps(p->p_grad, p->eps_grad) || robust_bad_eps(p->p_time, p->eps_time) || robust_bad_eps(p->p_data, p->eps_data)
+                        ? "eps_grad, eps_time and eps_data must be finite and > 0 where their exponent is not 2"
+                    : !std::isfinite(p->round_tol) ? "round_tol must be finite"
+                    : poisson_base(p->kind) == SC_POISSON_LAPLACIAN ? "a robust solve needs the guidance itself: the base kind must be SC_POISSON_GUIDANCE"
+                    : (p->kind & COUPLING_BITS) ? "the coupled forms are not offered on volumes" : nullptr;
+    if (own) { *why = own; return SC_ERR_BAD_ARG; }
+    return SC_OK;
+}
+
+struct VolumeRobustOperator final : VolumeOperator, RobustRounds {
+    const sc_volume_robust_params prm;
+    const sc_volume_wls_params base;
+    const RobustTerm grad, time, data;
+    const bool base_links, base_tlinks;
+    VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, bool links_, bool tlinks_)
+        : VolumeRobustOperator(I_, p, wls_params_of(p), links_, tlinks_) {}
+    VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_)
+        : VolumeOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS, true), prm(*p), base(q), grad(robust_term(p->p_grad, p->eps_grad)),
+          time(robust_term(p->p_time, p->eps_time)), data(robust_term(p->p_data, p->eps_data)), base_links(links_), base_tlinks(tlinks_) {}
+    RobustRounds *rounds() override { return this; }
+    bool quadratic() const override { return grad.mode == 0 && time.mode == 0 && data.mode == 0; }
+    int max_rounds() const override { return prm.max_rounds; }
+    float round_tol() const override { return prm.round_tol; }
+    void begin() override
+    {
+        VolumeOperator::begin();
+        links = base_links;          // round 0 of a new chunk: the caller's arrays again
+        tlinks = base_tlinks;
+    }
+    // A later round: the system at the chunk's iterate in place of the operator's, the round's sums in place of the statistics' (the
+    // counts of live links and of UNKNOWN pixels stay: the states do not change), and that iterate's energy per plane (one wait)
+    int reweigh(PcgChunk &c, std::vector<double> &energy) override
+    {
+        PcgState &S = *I->pcg;
+        const size_t parts = (size_t)c.planes * PCG_PARTS;
+        launch_volume_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
+                                   (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
+        SC_HIP(I, hipGetLastError());
+        SC_HIP(I, hipMemcpyAsync(c.h_round, c.d_round, sizeof(double) * parts * VOLUME_ROBUST_SUMS, hipMemcpyDeviceToHost, I->stream));
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        energy.assign(c.planes, 0.0);
+        wsum = ssum = tsum = uksum = 0.0;
+        links = tlinks = true;
+        for (int p = 0; p < c.planes; ++p) {
+            const double *plane = c.h_round + (size_t)p * PCG_PARTS * VOLUME_ROBUST_SUMS;
+            for (int i = 0; i < c.nop; ++i) {
+                const double *part = plane + (size_t)i * VOLUME_ROBUST_SUMS;
+                wsum += part[0];
+                ssum += part[1];
+                tsum += part[2];
+                uksum += part[3];
+                energy[p] += part[4];
+            }
+        }
+        return SC_OK;
+    }
+};
+
+PcgCall volume_robust_call(int kind, const sc_volume_robust_params *p)
+{
+    return PcgCall{ kind, p->tol, p->max_iters, 400, p->frames, p->frame_stride, p->time_periodic ? p->frames : p->frames - 1 };
+}
+
+constexpr const char *ROBUST_METHOD_WHY = "a robust volume solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
 
 } // namespace
 
@@ -226,7 +311,8 @@ int sc_hip_volume_device(void *inst, const sc_volume_params *p, const sc_poisson
     int kind, rc = pcg_begin(inst, p, l, volume_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
     const sc_volume_wls_params q = wls_params_of(p);
-    return volume_device_call(I, kind, &q, l, jobs, n, bSync, [](const sc_volume_job &) { return VolumeLinks{ nullptr, nullptr, nullptr }; });
+    return volume_device_call<VolumeOperator>(I, volume_call(kind, &q), &q, l, jobs, n, bSync,
+                                              [](const sc_volume_job &j) { return VolumeLinks{ nullptr, nullptr, nullptr, j.lap }; });
 }
 
 int sc_hip_volume(void *inst, const sc_volume_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
@@ -252,7 +338,8 @@ int sc_hip_volume_wls_device(void *inst, const sc_volume_wls_params *p, const sc
     Instance *I;
     int kind, rc = pcg_begin(inst, p, l, volume_wls_validate, METHOD_WHY, FP64_WHY, I, kind);
     if (rc) return rc;
-    return volume_device_call(I, kind, p, l, jobs, n, bSync, [](const sc_volume_wls_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t }; });
+    return volume_device_call<VolumeOperator>(I, volume_call(kind, p), p, l, jobs, n, bSync,
+                                              [](const sc_volume_wls_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, j.lap }; });
 }
 
 int sc_hip_volume_wls(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
@@ -269,6 +356,36 @@ int sc_hip_volume_wls(void *inst, const sc_volume_wls_params *p, const sc_poisso
     a.gt = gt;
     a.smooth_t = smooth_t;
     return pcg_host_call(I, volume_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op);
+}
+
+int sc_hip_volume_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l)
+{
+    return volume_robust_validate(p, l, nullptr);
+}
+
+int sc_hip_volume_robust_device(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, sc_volume_robust_job *jobs, int n, bool bSync)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    return volume_device_call<VolumeRobustOperator>(I, volume_robust_call(kind, p), p, l, jobs, n, bSync, [](const sc_volume_robust_job &j) {
+        return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, nullptr }; }, robust_chunk);
+}
+
+int sc_hip_volume_robust(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
+                         const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                         const float *smooth_t, const float *boundary, float *out)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    VolumeRobustOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    return pcg_host_call(I, volume_robust_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op, robust_chunk);
 }
 
 } // extern "C"

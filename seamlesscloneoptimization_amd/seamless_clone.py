@@ -1006,3 +1006,61 @@ def make_loop(frames, lam=1e-2, tau=1.0, gpu_id=0, **solver):
     gt[:-1] = frames[1:] - frames[:-1]          # (the wrapping link's stays 0)
     return volume_wls_solve(frames, np.zeros(frames.shape[:3], np.uint8), gx=gx, gy=gy, gt=gt, weight=np.full(frames.shape[:3], lam, np.float32),
                             tau=tau, loop=True, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0, loop=False,
+                        p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None, periodic="",
+                        max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, **solver):
+    """volume_wls_solve with robust_solve's penalties in place of the squares: per channel it minimises over the UNKNOWN pixels
+        sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy) + sum tau smooth_t phi_r(u_{t+1} - u_t - gt),
+        phi_e(t) = (2 / e) (t^2 + eps^2)^(e/2),      0 < p, r = p_time, q <= 2,
+    by iteratively reweighted least squares on the GPU: the quadratic problem (volume_wls_solve's) and then up to max_rounds (default
+    15) WLS volume solves whose links and weights come from the previous iterate, each started from it.  state, the link arrays, gt,
+    loop and the borders as volume_wls_solve's; gx and gy are required (there is no laplacian form), weight None: no data term.
+    round_tol (default 1e-4): stop when no channel's energy fell by more than that fraction in the last round; negative: run every
+    round.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    with _instance(gpu_id, solver) as inst:
+        return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, tau=tau, loop=bool(loop), neumann=neumann,
+                                  free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_time=p_time, eps_time=eps_time, p_data=q,
+                                  eps_data=eps_data, max_rounds=max_rounds or 0, round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0)
+
+
+def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """Total-variation denoising of a float32 video (T x H x W or T x H x W x C) that does not flicker: the video u that minimises
+        lam sum phi_q(u - frames) + sum phi_p(forward differences of u within a frame) + tau sum phi_r(u_{t+1} - u_t),      r = p_time,
+    under reflecting borders -- volume_robust_solve with zero guidance, every state unknown, data = frames and weight = lam.  p = 1 is
+    the anisotropic total variation in space; p_time = 1 lets the video jump at cuts and moving edges, p_time = 2 smooths along time.
+    eps (in the frames' units) rounds all three penalties off near 0.  loop: the last frame is joined to the first.  Returns a NEW array."""
+    frames = _video_of("frames", frames)
+    if not (np.isfinite(lam) and lam > 0):
+        raise ValueError("lam must be finite and > 0")
+    zero = np.zeros_like(frames)
+    return volume_robust_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), weight=np.full(frames.shape[:3], lam, np.float32), tau=tau,
+                               loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True, max_rounds=max_rounds,
+                               round_tol=round_tol, gpu_id=gpu_id, **solver)
+
+
+def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time=1.0, eps=1e-3, anchor=1e-3, loop=False, tau=1.0, max_rounds=None,
+                              round_tol=None, gpu_id=0, **solver):
+    """Integrates a float32 video's gradient field -- gx, gy: forward differences within a frame, T x H x W (x C); gt: from a frame to
+    the next, T - 1 frames (loop: T, the last one from frame T - 1 to frame 0) -- into a video with an Lp penalty on the residual of
+    every link: p = p_time = 1 (the default) ignores gross outliers in the field (a bad flow vector, a shot cut, a specular frame) that
+    a least-squares integration would smear over the video.  known (T x H x W, bool) and values: the pixels that hold exactly (keyframes,
+    a lattice of samples).  Neither: the free constant is held by a data term of weight `anchor` towards 0, small enough to leave the
+    shape alone.  Reflecting borders.  eps rounds the penalties off near 0, in the field's units.  Returns a NEW array."""
+    gx = _video_of("gx", gx)
+    if (known is None) != (values is None):
+        raise ValueError("known and values go together")
+    if known is None:
+        if not (np.isfinite(anchor) and anchor > 0):
+            raise ValueError("anchor must be finite and > 0")
+        return volume_robust_solve(gx, gy, np.zeros_like(gx), np.zeros(gx.shape[:3], np.uint8), gt=gt, weight=np.full(gx.shape[:3], anchor, np.float32),
+                                   tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps, neumann=True, max_rounds=max_rounds,
+                                   round_tol=round_tol, gpu_id=gpu_id, **solver)
+    m = _video_masks("known", known, gx)
+    if not m.any():
+        raise ValueError("known is empty: nothing holds the video")
+    state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
+    return volume_robust_solve(gx, gy, _video_of("values", values), state, gt=gt, tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps,
+                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
