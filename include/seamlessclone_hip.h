@@ -803,7 +803,7 @@ SC_API int sc_hip_robust_device(void *instance, const sc_robust_params *p, const
 SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
                          float *out);
-/* The last robust call's last chunk (sc_hip_robust* or sc_hip_volume_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+/* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust* or sc_hip_volume_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
@@ -856,8 +856,7 @@ SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int c
  * NOT detected, the caller's responsibility: a connected component of UNKNOWN pixels that nothing pins (no KNOWN neighbour, no Dirichlet
  * line, no weight) while other components are pinned.  In the guidance form the system stays consistent and the call returns some
  * constant offset on that component; with SC_POISSON_LAPLACIAN it need not converge.
- * Not offered: robust region solves on single images (sc_hip_volume_robust takes states, on frames >= 2), region states through the
- * 8-bit clone and edit entry points. */
+ * Not offered: region states through the 8-bit clone and edit entry points (robust penalties on a region: sc_hip_region_robust below). */
 #define SC_REGION_UNKNOWN 0
 #define SC_REGION_KNOWN   1
 #define SC_REGION_OUTSIDE 2
@@ -888,6 +887,64 @@ SC_API int sc_hip_region_device(void *instance, const sc_region_params *p, const
 SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x,
                          const float *smooth_y, const float *boundary, float *out);
+/* ---- robust region solves: Lp and TV penalties on a domain of any shape ------------------------------------------------------------------
+ * sc_hip_region's domain with sc_hip_robust's penalties in place of the squares.  Per channel, with exponents 0 < p, q <= 2, the call
+ * minimises over the UNKNOWN pixels
+ *     sum w phi_q(u - d; eps_d)  +  sum_live x-links c_x phi_p(dx u - gx; eps_g)  +  sum_live y-links c_y phi_p(dy u - gy; eps_g),
+ * phi, eps and the float32 forms of rho sc_hip_robust's; "live in the region", the three states, what is read and what is written
+ * sc_hip_region's, word for word.  The value of u across a link is data's at a KNOWN pixel, boundary's on a Dirichlet line of the border
+ * kind and the work plane's only at an UNKNOWN pixel.  Total-variation inpainting (the hole is filled so that edges run through it,
+ * where sc_hip_region gives a membrane), robust integration of a gradient field on a valid-pixel mask (photometric-stereo normals,
+ * depth from gradients: invalid pixels and outliers at once), robust interpolation from scattered hard samples, Poisson clones in the
+ * exact mask shape that ignore a few wrong gradients.
+ * The parameters are sc_robust_params themselves: exponents, eps, max_rounds, round_tol, tol and max_iters as in sc_hip_robust;
+ * SC_ROBUST_ISOTROPIC and SC_ROBUST_JOINT_CHANNELS are accepted.  There is no lap (the base kind must be SC_POISSON_GUIDANCE).
+ * weight NULL means no data term: p_data and eps_data are validated and unused, and data is not read at UNKNOWN pixels.  smooth_x,
+ * smooth_y: the base links c, both or neither; NULL: every link is 1.  In a device call the first job decides for weight and for the
+ * link arrays; a job that differs gets SC_ERR_BAD_ARG.
+ * Coupled forms: sc_hip_robust's definitions restricted to the links live in the region.  The owner of a link is its low end, which may
+ * be UNKNOWN, KNOWN or a pixel of a low Dirichlet line.  A dead link contributes nothing to a magnitude, and an owner without a live
+ * link nothing to the energy.  Under SC_ROBUST_JOINT_CHANNELS the magnitude of a link sums the channels in which that link is live
+ * (state is per channel).  The coupling changes nothing with p_grad = 2, or with the joint bit on one channel.
+ * Rounds: round 0 is sc_hip_region's system with default precond_*, set up and cold-started as that call does.  Round k >= 1 is the
+ * region system with s = c rho and w' = w rho_q taken at round k - 1's iterate, started warm from it.  Its right-hand side follows the
+ * region section's order: the guidance products (a - b) + (c - d), then - w' d, then the Dirichlet lines' terms west, north, east,
+ * south, then the KNOWN neighbours' terms west, north, east, south, each a rounded product.  Its diagonal is ((lw + le) + (ln + ls)) + w'.
+ * Both ends of a link compute its weight with the same bits: t = (u_hi - u_lo) - g, then sc_hip_robust's rho and one rounded product
+ * (the coupled forms: both ends read one rho).  The region section's zero condition -- right-hand side and coefficients 0 at every
+ * pixel that is not UNKNOWN -- holds after every round.  The preconditioner's means are each round's own: s-bar the mean of the live s,
+ * w-bar = (the sum of w' + the sum of the UNKNOWN - KNOWN links' s) / (the UNKNOWN pixels).  "Nothing pins the channel" and all other
+ * per-job refusals are the region call's, made in round 0.  One launch (k_region_robust_setup; coupled forms: k_region_robust_rho and
+ * k_region_robust_setup_rho) and one host read per round.
+ * max_rounds, round_tol (a plane's energy; under SC_ROBUST_JOINT_CHANNELS a job's), SC_ERR_NOT_CONVERGED, methods, sizes (8192 unknowns
+ * per side, 4096 with SC_FLAG_FFT_FP64), chunks, sc_run_info and the trace (sc_hip_robust_trace): sc_hip_robust's.
+ * Ties, byte for byte on out with equal sweeps: (a) every state 0 with a weight array: the bytes of sc_hip_robust with the same
+ * parameters, coupled bits included; (b) p_grad = p_data = 2: no round runs, the bytes of sc_hip_region (guidance base, default
+ * precond_*, the same tol and max_iters); (c) link arrays of 1.0f: the bytes of NULL arrays; (d) every state 0 with weight NULL: the
+ * bytes of the same call with a weight array of 0.0f; (e) two runs of one call give the same bytes.
+ * Codes: everything sc_hip_region_check refuses for layout and kind; everything sc_hip_robust_check refuses for exponents, eps, tol,
+ * round_tol and a Laplacian base.  Per job: the region call's refusals.
+ * Not offered: the 8-bit clone and edit entry points, a joint or isotropic data term, continuation in p or eps. */
+typedef struct sc_region_robust_job {   /* sc_region_job without lap */
+    const float *gx, *gy;    /* read at links live in the region: required */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* the base links c > 0 where live in the region; both NULL: every base link 1 */
+    const float *smooth_y;
+    const float *boundary;   /* its Dirichlet lines (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_region_robust_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_region_robust_check(const sc_robust_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_region_robust_device(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, sc_region_robust_job *jobs,
+                                       int n, bool bSync);
+/* One problem on host arrays, as sc_hip_region: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_region_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                                const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                                const float *boundary, float *out);
 /* ---- volume solves: region solves on frame stacks with temporal links ------------------------------------------------------------------
  * A stack of `frames` >= 2 images (video frames, CT or MRI slices, a depth stack) shares one sc_poisson_layout; in every array of a job
  * frame t begins frame_stride floats behind frame t - 1.  The unknown is u_t(q).  Per channel the call minimises
@@ -1078,8 +1135,8 @@ SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, cons
  * Codes: everything sc_hip_volume_wls_check refuses; everything sc_hip_robust_check refuses for exponents, eps, tol, round_tol and a
  * Laplacian base; SC_ERR_BAD_ARG for SC_ROBUST_ISOTROPIC / SC_ROBUST_JOINT_CHANNELS in kind.  Per job: the WLS volume call's refusals;
  * the first volume decides for weight and for the link arrays.
- * Not offered: coupled forms on volumes, robust region solves on single images (frames >= 2), motion-compensated temporal links, the
- * 8-bit entry points. */
+ * Not offered: coupled forms on volumes, motion-compensated temporal links, the 8-bit entry points.  A single image with states and
+ * robust penalties is sc_hip_region_robust's, which also takes the coupled forms. */
 typedef struct sc_volume_robust_params {
     int       kind;              /* as sc_volume_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
     int       frames;            /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */

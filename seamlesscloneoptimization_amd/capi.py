@@ -297,6 +297,13 @@ class RobustJob(C.Structure):
                 ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# robust region solves (sc_hip_region_robust*): Instance.region_robust / region_robust_device -- RobustParams themselves (the coupling bits
+# included) on a RegionJob without lap; robust_trace() reports the rounds
+class RegionRobustJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p), ("weight", C.c_void_p),
+                ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # robust volume solves (sc_hip_volume_robust*): Instance.volume_robust / volume_robust_device -- Lp penalties in space, time and data on
 # frame stacks; robust_trace() reports the rounds
 class VolumeRobustParams(C.Structure):
@@ -541,6 +548,13 @@ def load():
     L.sc_hip_volume_robust_device.restype = C.c_int
     L.sc_hip_volume_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 11
     L.sc_hip_volume_robust.restype = C.c_int
+    L.sc_hip_region_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_region_robust_check.restype = C.c_int
+    L.sc_hip_region_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RegionRobustJob), C.c_int,
+                                              C.c_bool]
+    L.sc_hip_region_robust_device.restype = C.c_int
+    L.sc_hip_region_robust.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 9
+    L.sc_hip_region_robust.restype = C.c_int
     L.sc_hip_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_robust_check.restype = C.c_int
     L.sc_hip_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RobustJob), C.c_int, C.c_bool]
@@ -1070,6 +1084,37 @@ def robust_arrays(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=N
     return kind | robust_coupling_bits(isotropic, joint_channels), gx, gy, data, weight, smooth_x, smooth_y, boundary, out
 
 
+def region_robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
+                        max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
+                        cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None, isotropic=False,
+                        joint_channels=False) -> int:
+    """Host-only sc_hip_region_robust_check: SC_OK or the code a robust region call with these parameters and this layout returns before
+    it runs anything.  The layout as a PoissonLayout or as keyword fields.  isotropic, joint_channels: SC_ROBUST_ISOTROPIC and
+    SC_ROBUST_JOINT_CHANNELS or'ed into kind (which may carry them itself)."""
+    p = RobustParams(int(kind) | robust_coupling_bits(isotropic, joint_channels), float(p_grad), float(eps_grad), float(p_data), float(eps_data),
+                     int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    return _check_call("sc_hip_region_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def region_robust_arrays(gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, out=None, neumann=False, free_sides="",
+                         periodic="", p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, isotropic=False, joint_channels=False):
+    """Checks a robust region problem's numpy arrays and penalties before any device is touched: (kind, gx, gy, data, state, weight,
+    smooth_x, smooth_y, boundary, out), region_arrays' rules.  gx and gy are required: the residual of a link needs the guidance itself
+    (there is no lap).  Exponents in (0, 2]; an eps finite and > 0 wherever its exponent is not 2 (p_data and eps_data are checked with
+    weight None as well, and then unused).  isotropic, joint_channels: kind carries SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS."""
+    if gx is None or gy is None:
+        raise ValueError("a robust region solve needs the guidance gx and gy (there is no Laplacian form)")
+    for name, r, eps in (("grad", p_grad, eps_grad), ("data", p_data, eps_data)):
+        if not (np.isfinite(r) and 0 < r <= 2):
+            raise ValueError(f"p_{name} must lie in (0, 2]")
+        if r != 2 and not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps_{name} must be finite and > 0")
+    kind, data, state, weight, sx, sy, gx, gy, _, boundary, out = region_arrays(data, state, weight, smooth_x, smooth_y, gx, gy, None, boundary, out,
+                                                                                neumann, free_sides, periodic)
+    return kind | robust_coupling_bits(isotropic, joint_channels), gx, gy, data, state, weight, sx, sy, boundary, out
+
+
 class Instance:
     """Thin RAII wrapper over one library instance (one GPU, one stream)."""
 
@@ -1366,6 +1411,35 @@ class Instance:
         raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_region_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
+    # ---- robust region solves on float32 arrays
+    def region_robust(self, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="",
+                      periodic="", p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0,
+                      allow_not_converged=False, isotropic=False, joint_channels=False):
+        """sc_hip_region_robust on numpy float32 arrays of shape H x W or H x W x C (C 1..4): region()'s problem with the penalties of
+        robust() in place of the squares -- over the UNKNOWN pixels minimise sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) +
+        sum smooth_y phi_p(d_y u - gy) over the links live in the region, p = p_grad, q = p_data -- by reweighted region solves on the
+        device.  state as region()'s; weight None: no data term; smooth_x, smooth_y None: every base link 1.  isotropic, joint_channels:
+        robust()'s coupled forms on the live links.  max_rounds, round_tol, tol, max_iters: sc_robust_params' (0: the defaults; round_tol
+        < 0: never stop early).  Returns out as region() composes it; info() has the total of the inner iterations and whether the round
+        rule was met, robust_trace() the rounds."""
+        kind, gx, gy, data, state, weight, sx, sy, boundary, out = region_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, boundary, out,
+                                                                                        neumann, free_sides, periodic, p_grad, eps_grad, p_data,
+                                                                                        eps_data, isotropic, joint_channels)
+        p = RobustParams(kind, float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
+                         int(max_iters))
+        return self._host_call("sc_hip_region_robust", p, (gx, gy, data, state, weight, sx, sy, boundary), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_region_robust_jobs(n: int):
+        return (RegionRobustJob * n)()
+
+    def region_robust_device(self, params: RobustParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_region_robust_device: jobs is a RegionRobustJob array (make_region_robust_jobs) of device pointers, one layout for all.
+        sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned,
+        other failures raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_region_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
     # ---- volume solves on float32 arrays
     def volume(self, data, state, weight=None, gx=None, gy=None, gt=None, lap=None, boundary=None, tau=1.0, neumann=False, free_sides="",
                periodic="", tol=0.0, max_iters=0, precond_lambda=0.0, allow_not_converged=False):
@@ -1484,7 +1558,7 @@ class Instance:
         return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     def robust_trace(self):
-        """(energy, iters) of the last robust call's last chunk (robust or volume_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
+        """(energy, iters) of the last robust call's last chunk (robust, region_robust or volume_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
         included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
         n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
         energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)

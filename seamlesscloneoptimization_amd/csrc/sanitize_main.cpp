@@ -19,6 +19,8 @@
 //      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check;
 //      sc_hip_volume_check: the same verdicts for two frames a frame's span apart, then frames, the plane limit, frame_stride and tau.
 //      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
+//      sc_hip_region_robust_check: the robust call's verdicts (the region call's on a guidance base), the coupling bits accepted, then every
+//      exponent, every eps, round_tol and tol.
 //      sc_hip_volume_robust_check: the WLS volume call's verdicts on a guidance base, then every exponent, every eps, round_tol, the coupling
 //      bits, a Laplacian base and the WLS volume call's own refusals.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
@@ -559,11 +561,45 @@ int main()
             if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (p_grad)");
             r.p_grad = 1.f; r.eps_grad = 0.f;
             if (sc_hip_robust_check(&r, &l) != SC_ERR_BAD_ARG) return fail("robust_check (eps_grad)");
-            // the coupling bits: the robust call's verdict does not change with them, every other family refuses them
+            // the robust region call: the robust call's verdicts -- the region call's on a guidance base --, then every exponent, every eps,
+            // round_tol and tol
+            {
+                const sc_robust_params good{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
+                sc_robust_params rr = good;
+                if (sc_hip_region_robust_check(&rr, &l) != got) return fail("region_robust_check");
+                rg.kind = k.kind;
+                if (!lap_base && sc_hip_region_check(&rg, &l) != got) return fail("region_robust_check (the region call's verdict)");
+                if (!lap_base && got == SC_OK) {
+                    for (float bad : { 0.f, -1.f, 2.5f, nan }) {
+                        rr = good; rr.p_grad = bad;
+                        if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (p_grad)");
+                        rr = good; rr.p_data = bad;
+                        if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (p_data)");
+                    }
+                    for (float bad : { 0.f, -1.f, nan, inf }) {
+                        rr = good; rr.eps_grad = bad;
+                        if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (eps_grad)");
+                        rr = good; rr.p_data = 1.f; rr.eps_data = bad;
+                        if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (eps_data)");
+                        rr = good; rr.eps_data = bad;          // (an exponent of 2 does not look at its eps)
+                        if (sc_hip_region_robust_check(&rr, &l) != SC_OK) return fail("region_robust_check (eps_data unused)");
+                    }
+                    rr = good; rr.round_tol = nan;
+                    if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (round_tol)");
+                    rr = good; rr.round_tol = -1.f;
+                    if (sc_hip_region_robust_check(&rr, &l) != SC_OK) return fail("region_robust_check (round_tol < 0)");
+                    rr = good; rr.tol = inf;
+                    if (sc_hip_region_robust_check(&rr, &l) != SC_ERR_BAD_ARG) return fail("region_robust_check (tol)");
+                }
+                if (sc_hip_region_robust_check(nullptr, &l) != SC_ERR_BAD_ARG || sc_hip_region_robust_check(&good, nullptr) != SC_ERR_BAD_ARG)
+                    return fail("region_robust_check (null)");
+            }
+            // the coupling bits: the robust calls' verdicts do not change with them, every other family refuses them
             r.eps_grad = 1e-3f;
             for (int bits : { SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS, SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS }) {
                 r.kind = k.kind | bits;
                 if (sc_hip_robust_check(&r, &l) != got) return fail("robust_check (coupling bits)");
+                if (sc_hip_region_robust_check(&r, &l) != got) return fail("region_robust_check (coupling bits)");
                 p.kind = q.kind = k.kind | bits;
                 if (sc_hip_weighted_check(&p, &l) != SC_ERR_BAD_ARG || sc_hip_wls_check(&q, &l) != SC_ERR_BAD_ARG) return fail("weighted_check / wls_check (coupling bits)");
                 rg.kind = k.kind | bits;

@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
 // of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the two
 // robust calls' rounds share (RobustRounds, robust_chunk; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
@@ -13,6 +13,7 @@
 // shuffles): no atomics, no host round trip.
 #pragma once
 #include "sc_instance.h"
+#include <cassert>
 #include <cmath>
 
 namespace sc {
@@ -262,6 +263,69 @@ void launch_region_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const 
                          float *S, float *Dg, double *bb, hipStream_t s);
 // the jobs' out: U at UNKNOWN pixels, data's bits at KNOWN and OUTSIDE pixels, boundary's bits on the Dirichlet lines
 void launch_region_out(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const float *U, hipStream_t s);
+// The operator of the region families (sc_region_api.cpp: its head comment says what it tells the iteration): sc_hip_region's, and through
+// RegionRobustOperator (sc_region_robust_api.cpp) every round's of the robust region call.
+struct RegionOperator : WlsOperator {
+    const bool has_w;
+    double unknowns = 0.0, uksum = 0.0, lcount = 0.0;      // of the jobs that stay: UNKNOWN pixels, the sum of UNKNOWN - KNOWN links, links live in the region
+    RegionOperator(Instance *I_, bool weight, bool links_, float plam_, float psmooth_, int nround_ = 0)      // nround_: a subclass's round sums
+        : WlsOperator(I_, links_, plam_, psmooth_, nround_, REGION_STATS), has_w(weight) {}
+    void begin() override
+    {
+        WlsOperator::begin();
+        unknowns = uksum = lcount = 0.0;
+    }
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
+    {
+        launch_region_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
+    }
+    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
+    {
+        double job[REGION_STATS] = {};
+        bool loose = false;
+        for (int c = 0; c < g.C; ++c) {
+            const double *plane = st + (size_t)c * PCG_PARTS * REGION_STATS;
+            double f[REGION_STATS];
+            for (int i = 0; i < REGION_STATS; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
+            // (a plane without an UNKNOWN pixel has nothing to pin: b = 0, data and boundary are copied)
+            loose = loose || (no_dirichlet && f[4] > 0.0 && !(f[5] > 0.0) && !(f[0] > 0.0));
+        }
+        if (job[6] != 0.0) return "a state element is not 0, 1 or 2";
+        if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
+        if (job[3] != 0.0 || !std::isfinite(job[2])) return "a link weight live in the region is not finite or not > 0";
+        if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link and no data weight";
+        wsum += job[0];
+        ssum += job[2];
+        unknowns += job[4];
+        uksum += job[5];
+        lcount += job[7];
+        return nullptr;
+    }
+    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
+    {
+        const double sbar = psmooth > 0.f ? (double)psmooth : unit_links || !(lcount > 0.0) ? 1.0 : ssum / lcount;
+        // (a chunk without any UNKNOWN pixel: b = 0 on every plane, any regular M serves)
+        const double wbar = plam > 0.f ? (double)plam : unknowns > 0.0 ? (wsum + uksum) / unknowns : sbar;
+        // without a Dirichlet line the rectangle's A is singular: judge kept only jobs whose every channel has a KNOWN neighbour or weight
+        assert(!(mixed_zero_eig(wg.ax) && mixed_zero_eig(wg.ay)) || wbar > 0.0);
+        u0_scale = (float)(1.0 / sbar);
+        return (float)(wbar / sbar);
+    }
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
+    {
+        PcgState &S = *I->pcg;
+        for (DevBuf *b : { &S.e, &S.s, &S.dg }) {
+            const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
+            if (rc) return rc;
+        }
+        launch_region_setup(g, wg, lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb, I->stream);
+        return SC_OK;
+    }
+    void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override
+    {
+        launch_region_out(g, wg, dj.data(), ds.data(), mv, U, s);
+    }
+};
 
 // ---- the volume family (sc_volume.hip): the region system on a stack of T frames, plus temporal links between (q, t) and (q, t + 1)
 // -- and, under periodic time, between (q, T - 1) and (q, 0).  A spatial link weighs sx / sy (NULL: 1), a temporal one lt = tau * smt
@@ -404,5 +468,21 @@ inline size_t robust_rho_floats(const PcgGeo &wg, int C, int m, int coupling)
 }
 void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
                            float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
+// the robust region call's launches (sc_region_robust.hip): launch_region_setup in its guidance form with s = c rho_p(link residual of U)
+// on every link live in the region (c = sx, sy; NULL: 1) and w' = w rho_q(U - d) (w NULL: no data term); the value of u across a link is
+// data's at a KNOWN pixel, boundary's on a Dirichlet line, U's at an UNKNOWN one.  sums[(plane * PCG_PARTS + i) * REGION_ROBUST_SUMS + ..]
+// = the part's sum of w' | of its live links s | of its UNKNOWN - KNOWN links s | the energy of U; every live link once, by
+// launch_region_stats' owner rule.  No allocation, no synchronise.
+constexpr int REGION_ROBUST_SUMS = 4;
+void launch_region_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                const RobustTerm &grad, const RobustTerm &data, const float *U, float *R, float *E, float *S, float *Dg,
+                                double *bb, double *sums, hipStream_t s);
+// its coupled forms (coupling: ROBUST_ISO | ROBUST_JOINT, not 0; p_grad < 2): launch_robust_coupled's two launches restricted to the
+// links live in the region -- k_region_robust_rho writes rho of every owner with a live link to the rho planes (robust_rho_stride,
+// robust_rho_floats) and esum as launch_robust_coupled, k_region_robust_setup_rho is launch_region_robust_setup with s read from them,
+// field 3 of its sums the data term's energy alone
+void launch_region_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                  const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho, float *R, float *E,
+                                  float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
 
 } // namespace sc

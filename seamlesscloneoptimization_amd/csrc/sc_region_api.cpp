@@ -3,7 +3,7 @@
 // (SC_REGION_UNKNOWN), fixed at data's value (SC_REGION_KNOWN) or not part of the domain (SC_REGION_OUTSIDE: its links do not exist).
 // The call is the WLS call with another folding of the caller's arrays into the coefficient planes E, S, Dg (sc_region.hip: why the
 // unchanged operator launch is exact): the same entry code (sc_pcg.h; the front end with FLOAT_STATE), the same iteration, and
-// RegionOperator, a WlsOperator with its own
+// RegionOperator (sc_pcg.h), a WlsOperator with its own
 //   statistics  k_region_stats; a job with a state that is not 0, 1 or 2, an invalid weight or link where one is read, or -- without any
 //               Dirichlet line -- a channel with UNKNOWN pixels that no KNOWN neighbour and no weight pins gets SC_ERR_BAD_ARG and leaves.
 //   constants   s-bar = precond_smooth, or the mean of the links live in the region over the chunk's remaining jobs (1 without link
@@ -34,68 +34,6 @@ constexpr const char *METHOD_WHY = "a region solve is solved by SC_METHOD_AUTO a
 constexpr const char *FP64_WHY = "a region solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
 
 int carries_of(bool weight, bool links) { return FLOAT_DATA | FLOAT_STATE | (weight ? FLOAT_WEIGHT : 0) | (links ? FLOAT_SMOOTH : 0); }
-
-struct RegionOperator : WlsOperator {
-    const bool has_w;
-    double unknowns = 0.0, uksum = 0.0, lcount = 0.0;      // of the jobs that stay: UNKNOWN pixels, the sum of UNKNOWN - KNOWN links, links live in the region
-    RegionOperator(Instance *I_, bool weight, bool links_, float plam_, float psmooth_)
-        : WlsOperator(I_, links_, plam_, psmooth_, 0, REGION_STATS), has_w(weight) {}
-    void begin() override
-    {
-        WlsOperator::begin();
-        unknowns = uksum = lcount = 0.0;
-    }
-    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
-    {
-        launch_region_stats(g, wg, dj.data(), ds.data(), m, d_stats, s);
-    }
-    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
-    {
-        double job[REGION_STATS] = {};
-        bool loose = false;
-        for (int c = 0; c < g.C; ++c) {
-            const double *plane = st + (size_t)c * PCG_PARTS * REGION_STATS;
-            double f[REGION_STATS];
-            for (int i = 0; i < REGION_STATS; ++i) job[i] += f[i] = stat_sum(plane, parts, i);
-            // (a plane without an UNKNOWN pixel has nothing to pin: b = 0, data and boundary are copied)
-            loose = loose || (no_dirichlet && f[4] > 0.0 && !(f[5] > 0.0) && !(f[0] > 0.0));
-        }
-        if (job[6] != 0.0) return "a state element is not 0, 1 or 2";
-        if (job[1] != 0.0 || !std::isfinite(job[0])) return "a weight is negative or not finite";
-        if (job[3] != 0.0 || !std::isfinite(job[2])) return "a link weight live in the region is not finite or not > 0";
-        if (loose) return "nothing pins the channel: no Dirichlet line, no UNKNOWN - KNOWN link and no data weight";
-        wsum += job[0];
-        ssum += job[2];
-        unknowns += job[4];
-        uksum += job[5];
-        lcount += job[7];
-        return nullptr;
-    }
-    float precond_constant(const PoissonGeo &g, const PcgGeo &wg, int mv) override
-    {
-        const double sbar = psmooth > 0.f ? (double)psmooth : unit_links || !(lcount > 0.0) ? 1.0 : ssum / lcount;
-        // (a chunk without any UNKNOWN pixel: b = 0 on every plane, any regular M serves)
-        const double wbar = plam > 0.f ? (double)plam : unknowns > 0.0 ? (wsum + uksum) / unknowns : sbar;
-        // without a Dirichlet line the rectangle's A is singular: judge kept only jobs whose every channel has a KNOWN neighbour or weight
-        assert(!(mixed_zero_eig(wg.ax) && mixed_zero_eig(wg.ay)) || wbar > 0.0);
-        u0_scale = (float)(1.0 / sbar);
-        return (float)(wbar / sbar);
-    }
-    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
-    {
-        PcgState &S = *I->pcg;
-        for (DevBuf *b : { &S.e, &S.s, &S.dg }) {
-            const int rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false);
-            if (rc) return rc;
-        }
-        launch_region_setup(g, wg, lap, dj.data(), ds.data(), mv, R, (float *)S.e.p, (float *)S.s.p, (float *)S.dg.p, bb, I->stream);
-        return SC_OK;
-    }
-    void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override
-    {
-        launch_region_out(g, wg, dj.data(), ds.data(), mv, U, s);
-    }
-};
 
 PcgCall region_call(int kind, const sc_region_params *p) { return PcgCall{ kind, p->tol, p->max_iters, 400 }; }
 

@@ -1064,3 +1064,101 @@ def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time
     state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
     return volume_robust_solve(gx, gy, _video_of("values", values), state, gt=gt, tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps,
                                neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+
+
+def region_robust_solve(gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
+                        neumann=True, free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, validate=False,
+                        gpu_id=0, isotropic=False, joint_channels=False, **solver):
+    """region_solve with robust_solve's penalties in place of the squares, on a float32 image of shape H x W or H x W x C (C 1..4): per
+    channel it minimises over the unknown pixels
+        sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy),      phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),
+    the sums over the links that do not touch an outside pixel and have an unknown end; u is data at known pixels and boundary on the
+    Dirichlet lines.  By iteratively reweighted least squares on the GPU: the quadratic problem (region_solve's) and then up to max_rounds
+    (default 15) region solves whose links and weights come from the previous iterate, each started from it.  state as region_solve's;
+    gx and gy are required (there is no laplacian form); weight None: no data term; smooth_x, smooth_y None: every base link 1.
+    isotropic, joint_channels: robust_solve's coupled forms over the live links.  round_tol, tol, max_iters: robust_solve's.
+    validate=True checks first that every component of unknown pixels is pinned (region_solve's).  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    if validate:
+        kind, _, _, d, st, w, _, _, _, _ = capi.region_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, boundary, neumann=neumann,
+                                                                     free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q,
+                                                                     eps_data=eps_data)
+        _region_validate(kind, st, w)
+    with _instance(gpu_id, solver) as inst:
+        return inst.region_robust(gx, gy, data, state, weight, smooth_x, smooth_y, boundary=boundary, neumann=neumann, free_sides=free_sides,
+                                  periodic=periodic, p_grad=p, eps_grad=eps_grad, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0,
+                                  round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0, isotropic=isotropic,
+                                  joint_channels=joint_channels)
+
+
+def region_robust_solve_batch(gxs, gys, datas, states, weights=None, smooth_xs=None, smooth_ys=None, boundaries=None, p=1.0, q=2.0, eps_grad=1e-3,
+                              eps_data=1e-3, neumann=True, free_sides=None, periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None,
+                              gpu_id=0, isotropic=False, joint_channels=False, **solver):
+    """region_robust_solve over a list of same-shape problems through ONE device-resident call (sc_hip_region_robust_device), as
+    robust_solve_batch: the rounds, the inner stops and the preconditioner's constants are joint, so a member agrees with its solo solve
+    to the inner solves' error as the rounds carry it, not bit for bit.  weights, smooth_xs and smooth_ys: for every problem or None.
+    Returns a list of NEW arrays."""
+    def arrays_of(d, a, borders):
+        kind, gx, gy, d, st, w, sx, sy, b, _ = capi.region_robust_arrays(a["gx"], a["gy"], d, a["state"], a.get("weight"), a.get("smooth_x"),
+                                                                         a.get("smooth_y"), a.get("boundary"), **borders, p_grad=p, eps_grad=eps_grad,
+                                                                         p_data=q, eps_data=eps_data, isotropic=isotropic, joint_channels=joint_channels)
+        return kind, dict(gx=gx, gy=gy, data=d, state=st, weight=w, smooth_x=sx, smooth_y=sy, boundary=b)
+    return _pcg_batch("robust region", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(state=states, gx=gxs, gy=gys), optional=dict(weight=weights, smooth_x=smooth_xs, smooth_y=smooth_ys),
+                      refusal="smooth_xs and smooth_ys go together" if (smooth_xs is None) != (smooth_ys is None) else None,
+                      length_why="one state, one guidance field and, where given, one weight, one pair of base links and, with a Dirichlet line, "
+                                 "one boundary per data term",
+                      arrays_of=arrays_of, slots=("gx", "gy", "data", "state", "weight", "smooth_x", "smooth_y", "boundary"),
+                      params_of=lambda kind: _robust_params(kind, p, q, eps_grad, eps_data, max_rounds, round_tol, tol, max_iters),
+                      make_jobs=capi.Instance.make_region_robust_jobs, device_call=capi.Instance.region_robust_device)
+
+
+def tv_inpaint(image, hole, p=1.0, eps=1e-2, isotropic=True, joint_channels=False, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """Total-variation fill of a float32 image (H x W or H x W x C): the pixels where hole (H x W, anything truthy) is set are replaced
+    by the u that minimises sum phi_p(forward differences of u) over the links that touch the hole, the pixels around it held -- edges
+    run through the hole where inpaint's membrane blurs them.  region_robust_solve with zero guidance, every pixel outside the hole
+    known, reflecting borders where the hole touches the image's edge.  p = 1 with isotropic=True (the default) is the total variation
+    of the gradient's magnitude; joint_channels=True takes it over all channels.  eps (in the image's units) rounds the penalty off
+    near 0.  Returns a NEW array; pixels outside the hole keep their bits."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+        raise TypeError("image must be a float32 numpy array")
+    h = _mask_of("hole", hole, image)
+    if h.all():
+        raise ValueError("the hole covers the whole image: nothing to fill it from")
+    state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    zero = np.zeros_like(image)
+    return region_robust_solve(zero, zero, image, state, p=p, eps_grad=eps, neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id,
+                               isotropic=isotropic, joint_channels=joint_channels, **solver)
+
+
+def integrate_gradients_masked(gx, gy, valid, known=None, values=None, p=1.0, eps=1e-3, anchor=1e-3, max_rounds=None, round_tol=None, gpu_id=0,
+                               isotropic=False, joint_channels=False, **solver):
+    """integrate_gradients on a mask of valid pixels: integrates a float32 gradient field (gx, gy: forward differences, H x W or
+    H x W x C) over the pixels where valid (H x W, anything truthy) is set, with an Lp penalty on the residual of every link between two
+    valid pixels -- photometric-stereo normals or depth from gradients with invalid pixels and gross outliers at once.  Pixels outside
+    valid are outside the domain: no link reaches them and the result holds 0 there.  known (H x W) and values: hard anchors, the
+    pixels that hold exactly.  Neither: the free constant is held by a data term of weight `anchor` towards 0, as in
+    integrate_gradients.  Reflecting borders.  Returns a NEW array."""
+    if not isinstance(gx, np.ndarray) or gx.dtype != np.float32:
+        raise TypeError("gx and gy must be float32 numpy arrays")
+    v = _mask_of("valid", valid, gx)
+    if not v.any():
+        raise ValueError("valid is empty: nothing to integrate over")
+    if (known is None) != (values is None):
+        raise ValueError("known and values go together")
+    state = np.where(v, capi.SC_REGION_UNKNOWN, capi.SC_REGION_OUTSIDE).astype(np.uint8)
+    if known is None:
+        if not (np.isfinite(anchor) and anchor > 0):
+            raise ValueError("anchor must be finite and > 0")
+        return region_robust_solve(gx, gy, np.zeros_like(gx), state, weight=np.full(gx.shape, anchor, np.float32), p=p, eps_grad=eps, neumann=True,
+                                   max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, joint_channels=joint_channels,
+                                   **solver)
+    k = _mask_of("known", known, gx) & v
+    if not k.any():
+        raise ValueError("known is empty inside valid: nothing holds the image")
+    if not isinstance(values, np.ndarray) or values.dtype != np.float32 or values.shape != gx.shape:
+        raise TypeError("values must be a float32 numpy array of gx's shape")
+    state[k] = capi.SC_REGION_KNOWN
+    data = np.where((v if gx.ndim == 2 else v[:, :, None]), values, np.float32(0)).astype(np.float32)
+    return region_robust_solve(gx, gy, data, state, p=p, eps_grad=eps, neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id,
+                               isotropic=isotropic, joint_channels=joint_channels, **solver)
