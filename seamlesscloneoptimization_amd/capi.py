@@ -287,9 +287,24 @@ def robust_coupling_bits(isotropic=False, joint_channels=False) -> int:
     return (SC_ROBUST_ISOTROPIC if isotropic else 0) | (SC_ROBUST_JOINT_CHANNELS if joint_channels else 0)
 
 
+def robust_penalties(**terms):
+    """What every robust call asks of its penalties, name=(exponent, eps): an exponent in (0, 2], an eps finite and > 0 wherever its
+    exponent is not 2."""
+    for name, (r, eps) in terms.items():
+        if not (np.isfinite(r) and 0 < r <= 2):
+            raise ValueError(f"p_{name} must lie in (0, 2]")
+        if r != 2 and not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"eps_{name} must be finite and > 0")
+
+
 class RobustParams(C.Structure):
     _fields_ = [("kind", C.c_int), ("p_grad", C.c_float), ("eps_grad", C.c_float), ("p_data", C.c_float), ("eps_data", C.c_float),
                 ("max_rounds", C.c_int), ("round_tol", C.c_float), ("tol", C.c_float), ("max_iters", C.c_int)]
+
+
+def robust_params(kind, p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0) -> RobustParams:
+    return RobustParams(int(kind), float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
+                        int(max_iters))
 
 
 class RobustJob(C.Structure):
@@ -1038,11 +1053,7 @@ def volume_robust_arrays(gx, gy, data, state, weight=None, smooth_x=None, smooth
     guidance itself (there is no lap).  Exponents in (0, 2]; an eps finite and > 0 wherever its exponent is not 2."""
     if gx is None or gy is None:
         raise ValueError("a robust volume solve needs the guidance gx and gy (there is no Laplacian form)")
-    for name, r, eps in (("grad", p_grad, eps_grad), ("time", p_time, eps_time), ("data", p_data, eps_data)):
-        if not (np.isfinite(r) and 0 < r <= 2):
-            raise ValueError(f"p_{name} must lie in (0, 2]")
-        if r != 2 and not (np.isfinite(eps) and eps > 0):
-            raise ValueError(f"eps_{name} must be finite and > 0")
+    robust_penalties(grad=(p_grad, eps_grad), time=(p_time, eps_time), data=(p_data, eps_data))
     kind, data, state, weight, sx, sy, smt, gx, gy, gt, _, boundary = volume_wls_arrays(data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt,
                                                                                        None, boundary, tau, loop, neumann, free_sides, periodic)
     return kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary
@@ -1055,8 +1066,7 @@ def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad:
     """Host-only sc_hip_robust_check: SC_OK or the code a robust call with these parameters and this layout returns before it runs
     anything.  The layout as a PoissonLayout or as keyword fields.  isotropic, joint_channels: SC_ROBUST_ISOTROPIC and
     SC_ROBUST_JOINT_CHANNELS or'ed into kind (which may carry them itself)."""
-    p = RobustParams(int(kind) | robust_coupling_bits(isotropic, joint_channels), float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
-                     int(max_iters))
+    p = robust_params(int(kind) | robust_coupling_bits(isotropic, joint_channels), p_grad, eps_grad, p_data, eps_data, max_rounds, round_tol, tol, max_iters)
     return _check_call("sc_hip_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
                        row_stride=row_stride, channel_stride=channel_stride)
 
@@ -1071,11 +1081,7 @@ def robust_arrays(gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=N
         raise ValueError("a robust solve needs the guidance gx and gy (there is no Laplacian form)")
     if (smooth_x is None) != (smooth_y is None):
         raise ValueError("smooth_x and smooth_y go together (both None: all base links 1)")
-    for name, r, eps in (("grad", p_grad, eps_grad), ("data", p_data, eps_data)):
-        if not (np.isfinite(r) and 0 < r <= 2):
-            raise ValueError(f"p_{name} must lie in (0, 2]")
-        if r != 2 and not (np.isfinite(eps) and eps > 0):
-            raise ValueError(f"eps_{name} must be finite and > 0")
+    robust_penalties(grad=(p_grad, eps_grad), data=(p_data, eps_data))
     if smooth_x is None:
         kind, data, weight, gx, gy, _, boundary, out = weighted_arrays(data, weight, gx, gy, None, boundary, out, neumann, free_sides, periodic)
     else:
@@ -1091,8 +1097,7 @@ def region_robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, ep
     """Host-only sc_hip_region_robust_check: SC_OK or the code a robust region call with these parameters and this layout returns before
     it runs anything.  The layout as a PoissonLayout or as keyword fields.  isotropic, joint_channels: SC_ROBUST_ISOTROPIC and
     SC_ROBUST_JOINT_CHANNELS or'ed into kind (which may carry them itself)."""
-    p = RobustParams(int(kind) | robust_coupling_bits(isotropic, joint_channels), float(p_grad), float(eps_grad), float(p_data), float(eps_data),
-                     int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    p = robust_params(int(kind) | robust_coupling_bits(isotropic, joint_channels), p_grad, eps_grad, p_data, eps_data, max_rounds, round_tol, tol, max_iters)
     return _check_call("sc_hip_region_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
                        row_stride=row_stride, channel_stride=channel_stride)
 
@@ -1105,11 +1110,7 @@ def region_robust_arrays(gx, gy, data, state, weight=None, smooth_x=None, smooth
     weight None as well, and then unused).  isotropic, joint_channels: kind carries SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS."""
     if gx is None or gy is None:
         raise ValueError("a robust region solve needs the guidance gx and gy (there is no Laplacian form)")
-    for name, r, eps in (("grad", p_grad, eps_grad), ("data", p_data, eps_data)):
-        if not (np.isfinite(r) and 0 < r <= 2):
-            raise ValueError(f"p_{name} must lie in (0, 2]")
-        if r != 2 and not (np.isfinite(eps) and eps > 0):
-            raise ValueError(f"eps_{name} must be finite and > 0")
+    robust_penalties(grad=(p_grad, eps_grad), data=(p_data, eps_data))
     kind, data, state, weight, sx, sy, gx, gy, _, boundary, out = region_arrays(data, state, weight, smooth_x, smooth_y, gx, gy, None, boundary, out,
                                                                                 neumann, free_sides, periodic)
     return kind | robust_coupling_bits(isotropic, joint_channels), gx, gy, data, state, weight, sx, sy, boundary, out
@@ -1425,8 +1426,7 @@ class Instance:
         kind, gx, gy, data, state, weight, sx, sy, boundary, out = region_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, boundary, out,
                                                                                         neumann, free_sides, periodic, p_grad, eps_grad, p_data,
                                                                                         eps_data, isotropic, joint_channels)
-        p = RobustParams(kind, float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
-                         int(max_iters))
+        p = robust_params(kind, p_grad, eps_grad, p_data, eps_data, max_rounds, round_tol, tol, max_iters)
         return self._host_call("sc_hip_region_robust", p, (gx, gy, data, state, weight, sx, sy, boundary), out, data,
                                (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
 
@@ -1542,8 +1542,7 @@ class Instance:
         kind, gx, gy, data, weight, sx, sy, boundary, out = robust_arrays(gx, gy, data, weight, smooth_x, smooth_y, boundary, out, neumann,
                                                                           free_sides, periodic, p_grad, eps_grad, p_data, eps_data, isotropic,
                                                                           joint_channels)
-        p = RobustParams(kind, float(p_grad), float(eps_grad), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol),
-                         int(max_iters))
+        p = robust_params(kind, p_grad, eps_grad, p_data, eps_data, max_rounds, round_tol, tol, max_iters)
         return self._host_call("sc_hip_robust", p, (gx, gy, data, weight, sx, sy, boundary), out, data,
                                (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
 

@@ -2,8 +2,8 @@
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
 // sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
-// of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the two
-// robust calls' rounds share (RobustRounds, robust_chunk; sc_robust_api.cpp).
+// of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the three
+// robust calls share: their rounds, their check and their entry preamble (RobustRounds, robust_chunk, robust_begin; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
 // Work planes are compact float32: only the nx x ny unknowns of MixedGeo, row after row, planes `stride` floats apart (a multiple of 4:
 // float4 access); plane p = member C + channel.  Tiling of the launches that walk a plane in 2-D (statistics, set-up, operator): column
@@ -15,6 +15,7 @@
 #include "sc_instance.h"
 #include <cassert>
 #include <cmath>
+#include <initializer_list>
 
 namespace sc {
 
@@ -147,9 +148,8 @@ int pcg_run(Instance *I, const PcgCall &call, const sc_poisson_layout *l, PcgOpe
             int nv, bool timed, PcgChunkFn chunk = nullptr);
 // What every entry of the three families starts with: the instance, the family's validation of the call (its sc_hip_*_check) and the
 // instance's word on a direct solve, with the family's two reasons; kind: poisson_norm_kind's
-template <class Params> int pcg_begin(void *inst, const Params *p, const sc_poisson_layout *l,
-                                      int (*validate)(const Params *, const sc_poisson_layout *, const char **), const char *method_why,
-                                      const char *fp64_why, Instance *&I, int &kind)
+template <class Params, class Validate> int pcg_begin(void *inst, const Params *p, const sc_poisson_layout *l, Validate validate,
+                                                      const char *method_why, const char *fp64_why, Instance *&I, int &kind)
 {
     int rc = begin_call(inst, I);
     if (rc) return rc;
@@ -426,19 +426,52 @@ inline RobustTerm robust_term(float r, float eps)
 // what the robust calls' checks refuse of an exponent and of its eps
 inline bool robust_bad_exponent(float r) { return !(r > 0.f && r <= 2.f); }
 inline bool robust_bad_eps(float r, float eps) { return r != 2.f && !(std::isfinite(eps) && eps > 0.f); }
-// What robust_chunk asks of an operator beyond PcgOperator (PcgOperator::rounds): whether every exponent is 2 (no round runs), the
-// call's max_rounds and round_tol as the caller gave them, and reweigh -- a later round: the system at the chunk's iterate c.U put in
-// place of the operator's, its means, and that iterate's energy per unit of the round rule (one host wait).
+// the two bits of sc_robust_params::kind that are the robust calls' own (the families' kinds know nothing of them), and the launches' word for them
+constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
+constexpr int ROBUST_ISO = 1, ROBUST_JOINT = 2;
+// The reweighting rounds of a robust call: what robust_chunk (sc_robust_api.cpp) asks of an operator beyond PcgOperator
+// (PcgOperator::rounds).  The penalties (time: the volume call's; elsewhere exponent 2), max_rounds and round_tol as the caller gave
+// them, the caller's coupling bits as ROBUST_ISO | ROBUST_JOINT.  A later round is reweigh() -- the one place that says what a round
+// does --, of which an operator provides three things:
+//   nsums   the doubles per part its round launch sums, the energy last (ROBUST_SUMS, REGION_ROBUST_SUMS, VOLUME_ROBUST_SUMS);
+//   launch  the set-up at the iterate c.U in place of the operator's system: b into c.R, the coefficient planes, the parts of b . b into
+//           c.d_bb, the sums into c.d_round; under a coupling (coupling(C), not 0) the two launches of the coupled forms, PcgState::rho
+//           ensured, the gradient energy's parts behind the sums at `esum`;
+//   take    the folded sums (nsums - 1 totals, in the launch's order) in place of the statistics' sums, and the operator's flag that
+//           later rounds' links are the iterate's (the counts of links and of UNKNOWN pixels stay round 0's: states do not change).
 struct RobustRounds {
+    const RobustTerm grad, data, time;
+    const int max_rounds;
+    const float round_tol;
+    const int bits, nsums;
+    RobustRounds(const RobustTerm &grad_, const RobustTerm &data_, const RobustTerm &time_, int max_rounds_, float round_tol_, int kind, int nsums_)
+        : grad(grad_), data(data_), time(time_), max_rounds(max_rounds_), round_tol(round_tol_),
+          bits(((kind & SC_ROBUST_ISOTROPIC) ? ROBUST_ISO : 0) | ((kind & SC_ROBUST_JOINT_CHANNELS) ? ROBUST_JOINT : 0)), nsums(nsums_) {}
+    RobustRounds(const sc_robust_params &p, int nsums_)
+        : RobustRounds(robust_term(p.p_grad, p.eps_grad), robust_term(p.p_data, p.eps_data), robust_term(2.f, 0.f), p.max_rounds, p.round_tol, p.kind,
+                       nsums_) {}
     virtual ~RobustRounds() = default;
-    virtual bool quadratic() const = 0;
-    virtual int max_rounds() const = 0;
-    virtual float round_tol() const = 0;
-    virtual int reweigh(PcgChunk &c, std::vector<double> &energy) = 0;
+    bool quadratic() const { return grad.mode == 0 && data.mode == 0 && time.mode == 0; }      // every exponent is 2: no round runs
+    // the coupling that changes anything: none with p_grad = 2 (every form is sum c t^2), no joint form of one channel
+    int coupling(int C) const { return grad.mode == 0 ? 0 : C == 1 ? bits & ~ROBUST_JOINT : bits; }
+    virtual int launch(PcgChunk &c, int coupling, double *esum) = 0;
+    virtual void take(const double *totals) = 0;
+    // One round's system, its means and the energy of the chunk's iterate per unit of the round rule -- a plane, or a job where the
+    // channels are coupled (one host wait)
+    int reweigh(PcgChunk &c, std::vector<double> &energy);
 };
 // One chunk of a robust call (sc_robust_api.cpp; a PcgChunkFn): the quadratic round, the reweighting rounds of op.rounds(), the output,
 // PcgState's trace
 int robust_chunk(Instance *I, const PcgCall &call, const PoissonGeo &g, PcgOperator &op, int *const *rcs, int m, PcgChunkResult &res, int &job_errors);
+// What the image and the region call's entries share (sc_robust_api.cpp).  robust_validate: the check of either, `size_why` the family's
+// reason against more than 8192 unknowns per side.  robust_penalties_why: the penalties' own reason against a call, NULL: none -- the
+// exponents (p_why), their eps (eps_why), tol, round_tol, the base kind; the volume call's check has it too.  robust_begin: pcg_begin
+// with robust_validate, and the call without the coupling bits (poisson_norm_kind passes them through; RobustRounds has them from p).
+struct RobustPenalty { float p, eps; };
+struct RobustFamily { const char *size_why, *method_why, *fp64_why; };
+const char *robust_penalties_why(std::initializer_list<RobustPenalty> terms, const char *p_why, const char *eps_why, float tol, float round_tol, int kind);
+int robust_validate(const sc_robust_params *p, const sc_poisson_layout *l, const char *size_why, const char **why);
+int robust_begin(void *inst, const sc_robust_params *p, const sc_poisson_layout *l, const RobustFamily &f, Instance *&I, PcgCall &call);
 constexpr int ROBUST_SUMS = 3;
 // the robust volume call's launch (sc_volume_robust.hip): launch_volume_setup in its guidance form with s = c rho(link residual of U)
 // on every live link -- c: sx, sy (NULL: 1) with `grad`, lt = tau * smt (NULL: tau) with `time` -- and w' = w rho(U - d) with `data`;
@@ -460,7 +493,6 @@ void launch_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const PoissonJob
 // (ROBUST_ISO) or two (x-links, y-links) -- and esum[plane * PCG_PARTS + i] = the part's gradient energy, under ROBUST_JOINT on the
 // job's channel-0 plane only (the others' are not written); k_robust_setup_rho is launch_robust_setup with s read from those planes,
 // field 2 of its sums the data term's energy alone.
-constexpr int ROBUST_ISO = 1, ROBUST_JOINT = 2;
 inline long long robust_rho_stride(const PcgGeo &wg) { return ((long long)(wg.x0 + wg.nx) * (wg.y0 + wg.ny) + 63) / 64 * 64; }
 inline size_t robust_rho_floats(const PcgGeo &wg, int C, int m, int coupling)
 {

@@ -1,11 +1,12 @@
 // sc_pcg_device.h -- what the kernels of the conjugate-gradient families share (sc_pcg.hip, sc_weighted.hip, sc_wls.hip): the workgroup's
 // size and its sum in one fixed order, and one walk of each kind over the work planes (sc_pcg.h, PcgGeo) -- the element-wise walk of a
 // segment's float4 groups, the band of a statistics or set-up launch, and the operator's walk with a family's coefficients as a policy,
-// and the robust penalties' arithmetic (sc_robust.hip, sc_volume_robust.hip).
+// and the robust penalties' arithmetic with the coupled forms' side tables (sc_robust.hip, sc_region_robust.hip, sc_volume_robust.hip).
 #pragma once
 #include "sc_pcg.h"
 #include "sc_wave.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace sc {
 
@@ -73,7 +74,7 @@ __device__ __forceinline__ void part_store(double v, double *ws, const PcgGeo &w
     if (threadIdx.x == 0) parts[((size_t)blockIdx.z * PCG_PARTS + blockIdx.y * wg.cg + blockIdx.x) * per + f] = v;
 }
 
-// ---- the robust penalties (sc_robust.hip, sc_volume_robust.hip): one term as RobustTerm states it (sc_pcg.h)
+// ---- the robust penalties (sc_robust.hip, sc_region_robust.hip, sc_volume_robust.hip): one term as RobustTerm states it (sc_pcg.h)
 // rho_r(t), and q = t t + eps eps (r = 2: t t; eps is unused there)
 __device__ __forceinline__ float robust_rho(const RobustTerm &r, float t, float &q)
 {
@@ -97,6 +98,55 @@ __device__ __forceinline__ RobustLink robust_link(const RobustTerm &r, float bas
     k.s = r.mode == 0 ? base : rounded_product(base, rho);
     k.e = robust_phi(r, base, q, rho);
     return k;
+}
+
+// the penalties' constants in vector registers: the region and volume walks are short of scalar ones
+__device__ __forceinline__ void lane_term(RobustTerm &r)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(r.eps2), "+v"(r.half_exp), "+v"(r.scale));
+#endif
+}
+// The data term at the iterate: w' = w rho_q(u - d) (the return value), rhs = screened_rhs(rhs, w', d), e = the term's energy
+__device__ __forceinline__ float robust_data(const RobustTerm &r, float wv, float dv, float uc, float &rhs, double &e)
+{
+    float q;
+    const float rho = robust_rho(r, uc - dv, q), wr = r.mode == 0 ? wv : rounded_product(wv, rho);
+    rhs = screened_rhs(rhs, wr, dv);
+    e = robust_phi(r, wv, q, rho);
+    return wr;
+}
+
+// ---- the coupled forms (sc_robust.hip: their definitions): the rho planes' geometry, a link's share c t^2 of a magnitude (BASE: with
+// the base link c[o]; false: 1, no multiply), rho_p(M) with the magnitude's energy (2 / p) Q rho in double from the float32 Q and rho
+struct RhoGeo { int rw, ncomp; long long rstride; };
+template <bool BASE>
+__device__ __forceinline__ float robust_sq(const float *__restrict__ c, long long o, float t)
+{
+    const float q = rounded_product(t, t);
+    return BASE ? rounded_product(c[o], q) : q;
+}
+__device__ __forceinline__ float coupled_rho(const RobustTerm &r, float m, double &e)
+{
+    const float q = m + r.eps2, rho = r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
+    e = (double)r.scale * ((double)q * (double)rho);
+    return rho;
+}
+// The coupled forms' launches of every side table (host): fn(iso, joint, t, cnt, rg, o, po, ro) -- iso, joint: the form as
+// std::bool_constant, for the kernels' template arguments; o, po, ro: the first job's offset into the work planes, into the parts (per
+// double of a part) and into the rho planes
+template <class Table, class Fn>
+void for_coupled_tables(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, int coupling, Fn fn)
+{
+    const bool iso = (coupling & ROBUST_ISO) != 0, joint = (coupling & ROBUST_JOINT) != 0;
+    const RhoGeo rg{ wg.x0 + wg.nx, iso ? 1 : 2, robust_rho_stride(wg) };
+    for_side_tables<Table>(jobs, sides, m, [&](const Table &t, int i0, int cnt) {
+        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
+        const size_t ro = (size_t)(joint ? i0 : g.C * i0) * rg.ncomp * rg.rstride;
+        if (iso && joint) fn(std::true_type(), std::true_type(), t, cnt, rg, o, po, ro);
+        else if (iso) fn(std::true_type(), std::false_type(), t, cnt, rg, o, po, ro);
+        else fn(std::false_type(), std::true_type(), t, cnt, rg, o, po, ro);
+    });
 }
 
 // The operator's launch (grid: cg x bands x planes), one kernel for every family.  RES false: Q = L P and the parts of P . Q;  true:

@@ -1,11 +1,13 @@
-// sc_region_robust.hip -- the robust region call's kernels (sc_hip_region_robust*, sc_region_robust_api.cpp): one reweighting round of
+// sc_region_robust.hip -- the robust region call's kernels (sc_hip_region_robust*, sc_region_robust_api.cpp: RegionRobustOperator's
+// launches in a reweighting round, which RobustRounds::reweigh in sc_robust_api.cpp describes).  The system of a round of
 //     minimise  sum w phi_q(u - d) + sum_live x-links c_x phi_p(dx u - gx) + sum_live y-links c_y phi_p(dy u - gy)
 // over the UNKNOWN pixels of one image under region states is the region system (sc_region.hip) with s = c rho_p(link residual) on every
 // link live in the region and w' = w rho_q(u - d), all at the iterate U on the compact work plane.  k_region_robust_setup is
 // k_robust_setup's walk (sc_robust.hip: column groups of 256, bands of rows, a lane owns one column of its band) with k_region_setup's
 // state logic (Around, state_kind) and every link computed where it is used, as k_volume_robust_setup does (sc_volume_robust.hip)
 // without the time axis; behind it the two launches of the coupled forms (k_region_robust_rho, k_region_robust_setup_rho), k_robust_rho
-// and k_robust_setup_rho restricted to the links live in the region.
+// and k_robust_setup_rho restricted to the links live in the region.  The penalties' arithmetic, the data term (robust_data), lane_term
+// and the coupled forms' helpers are sc_pcg_device.h's.
 // The value of u across a link is NOT the work plane's wherever the neighbour is not UNKNOWN -- u0 = M^-1 b and z = M^-1 r fill the
 // whole rectangle (sc_region.hip) --: it is data's at a KNOWN pixel, boundary's on a Dirichlet line and U's only at an UNKNOWN one.
 // Both ends of a link compute its weight by one expression on the same operands -- t = (u_hi - u_lo) - g, hi / lo by the link's
@@ -23,14 +25,6 @@
 namespace sc {
 
 namespace {
-
-// the penalties' constants in vector registers: the walk is short of scalar ones
-__device__ __forceinline__ void lane_term(RobustTerm &r)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(r.eps2), "+v"(r.half_exp), "+v"(r.scale));
-#endif
-}
 
 // NOW: no weight (w and data at UNKNOWN pixels are not read);  LNK: the call has base link arrays (false: every base link is 1).
 // sums[(plane * PCG_PARTS + part) * REGION_ROBUST_SUMS + ..] = the sum of w' | of the live links s | of the UNKNOWN - KNOWN links s |
@@ -107,14 +101,8 @@ __global__ __launch_bounds__(WL) void k_region_robust_setup(PoissonGeo g, PcgGeo
                     v = (pa - pb) + (pc - pd);
                     float wr = 0.f;
                     if (!NOW) {
-                        // the data term at the iterate: w' = w rho_q(u - d)
-                        const float wv = w[o], dv = j.d[o];
-                        float q;
-                        const float rho = robust_rho(td, uc - dv, q);
-                        wr = td.mode == 0 ? wv : rounded_product(wv, rho);
-                        v = screened_rhs(v, wr, dv);
+                        wr = robust_data(td, w[o], j.d[o], uc, v, e_d);
                         s_w += (double)wr;
-                        e_d = robust_phi(td, wv, q, rho);
                     }
                     if (a.kw == NB_DIRICHLET) v -= rounded_product(lw, u_w);
                     if (a.kn == NB_DIRICHLET) v -= rounded_product(ln, u_n);
@@ -156,22 +144,6 @@ __global__ __launch_bounds__(WL) void k_region_robust_setup(PoissonGeo g, PcgGeo
 //                              gradient energy, every such owner once; under JOINT the job's, booked on its channel-0 plane.
 //   k_region_robust_setup_rho  k_region_robust_setup with s = c rho read at the pixel (east, south), at its west owner and at its north
 //                              owner, only where that link is live in the region: then its owner wrote it.  Its energy is the data term's.
-struct RhoGeo { int rw, ncomp; long long rstride; };
-
-template <bool LNK>
-__device__ __forceinline__ float region_sq(const float *__restrict__ c, long long o, float t)
-{
-    const float q = rounded_product(t, t);
-    return LNK ? rounded_product(c[o], q) : q;
-}
-// rho_p(M) and the magnitude's energy (2 / p) Q rho in double from the float32 Q and rho
-__device__ __forceinline__ float region_coupled_rho(const RobustTerm &r, float m, double &e)
-{
-    const float q = m + r.eps2, rho = r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
-    e = (double)r.scale * ((double)q * (double)rho);
-    return rho;
-}
-
 // grid: cg x bands x units; esum[(the unit's first plane * PCG_PARTS + part)] = the part's gradient energy
 template <bool LNK, bool ISO, bool JOINT>
 __global__ __launch_bounds__(WL) void k_region_robust_rho(PoissonGeo g, PcgGeo wg, RegionJobs t, RobustTerm tg, RhoGeo rg, const float *__restrict__ U,
@@ -210,24 +182,24 @@ __global__ __launch_bounds__(WL) void k_region_robust_rho(PoissonGeo g, PcgGeo w
                 const float uc = value(kp, o, li);
                 float ax = 0.f, ay = 0.f;
                 if (live(a.ke)) {
-                    ax = region_sq<LNK>(sx, o, (value(a.ke, a.oe, ro + xe) - uc) - j.gx[o]);
+                    ax = robust_sq<LNK>(sx, o, (value(a.ke, a.oe, ro + xe) - uc) - j.gx[o]);
                     has_x = true;
                 }
                 if (live(a.ks)) {
-                    ay = region_sq<LNK>(sy, o, (value(a.ks, a.os, y < ny - 1 ? li + nx : (size_t)x) - uc) - j.gy[o]);
+                    ay = robust_sq<LNK>(sy, o, (value(a.ks, a.os, y < ny - 1 ? li + nx : (size_t)x) - uc) - j.gy[o]);
                     has_y = true;
                 }
                 if (ISO) mx += ax + ay;
                 else { mx += ax; my += ay; }
-                if (unk && a.kw == NB_DIRICHLET) { mw += region_sq<LNK>(sx, a.ow, (uc - j.b[a.ow]) - j.gx[a.ow]); has_w = true; }
-                if (unk && a.kn == NB_DIRICHLET) { mn += region_sq<LNK>(sy, a.on, (uc - j.b[a.on]) - j.gy[a.on]); has_n = true; }
+                if (unk && a.kw == NB_DIRICHLET) { mw += robust_sq<LNK>(sx, a.ow, (uc - j.b[a.ow]) - j.gx[a.ow]); has_w = true; }
+                if (unk && a.kn == NB_DIRICHLET) { mn += robust_sq<LNK>(sy, a.on, (uc - j.b[a.on]) - j.gy[a.on]); has_n = true; }
             }
             const size_t i = (size_t)Y * rg.rw + X;
             double e_x = 0.0, e_y = 0.0, e_w = 0.0, e_n = 0.0;
-            if (ISO ? (has_x || has_y) : has_x) rx[i] = region_coupled_rho(tg, mx, e_x);
-            if (!ISO && has_y) ry[i] = region_coupled_rho(tg, my, e_y);
-            if (has_w) rx[i - 1] = region_coupled_rho(tg, mw, e_w);              // (a low Dirichlet line: X == 1)
-            if (has_n) ry[i - rg.rw] = region_coupled_rho(tg, mn, e_n);          // (Y == 1)
+            if (ISO ? (has_x || has_y) : has_x) rx[i] = coupled_rho(tg, mx, e_x);
+            if (!ISO && has_y) ry[i] = coupled_rho(tg, my, e_y);
+            if (has_w) rx[i - 1] = coupled_rho(tg, mw, e_w);              // (a low Dirichlet line: X == 1)
+            if (has_n) ry[i - rg.rw] = coupled_rho(tg, mn, e_n);          // (Y == 1)
             s_e += (e_x + e_y) + (e_w + e_n);
         }
     }
@@ -292,13 +264,8 @@ __global__ __launch_bounds__(WL) void k_region_robust_setup_rho(PoissonGeo g, Pc
                     v = (pa - pb) + (pc - pd);
                     float wr = 0.f;
                     if (!NOW) {
-                        const float wv = w[o], dv = j.d[o];
-                        float q;
-                        const float rho = robust_rho(td, uc - dv, q);
-                        wr = td.mode == 0 ? wv : rounded_product(wv, rho);
-                        v = screened_rhs(v, wr, dv);
+                        wr = robust_data(td, w[o], j.d[o], uc, v, e_d);
                         s_w += (double)wr;
-                        e_d = robust_phi(td, wv, q, rho);
                     }
                     if (a.kw == NB_DIRICHLET) v -= rounded_product(lw, j.b[a.ow]);
                     if (a.kn == NB_DIRICHLET) v -= rounded_product(ln, j.b[a.on]);
@@ -342,32 +309,18 @@ void coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const RegionJobs &t
                        data, rg, Rho, U, R, E, S, Dg, bb, sums);
 }
 
-template <bool NOW, bool LNK, class... A> void coupled_form(bool iso, bool joint, A... a)
-{
-    if (iso && joint) coupled_launches<NOW, LNK, true, true>(a...);
-    else if (iso) coupled_launches<NOW, LNK, true, false>(a...);
-    else coupled_launches<NOW, LNK, false, true>(a...);
-}
-
 } // namespace
 
 void launch_region_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                   const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho, float *R, float *E,
                                   float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s)
 {
-    const bool iso = (coupling & ROBUST_ISO) != 0, joint = (coupling & ROBUST_JOINT) != 0;
-    RhoGeo rg;
-    rg.rw = wg.x0 + wg.nx;
-    rg.ncomp = iso ? 1 : 2;
-    rg.rstride = robust_rho_stride(wg);
-    for_side_tables<RegionJobs>(jobs, sides, m, [&](const RegionJobs &t, int i0, int cnt) {
-        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
-        float *rho = Rho + (size_t)(joint ? i0 : g.C * i0) * rg.ncomp * rg.rstride;
-        const bool now = !t.w[0], lnk = t.sx[0] != nullptr;
-#define SC_COUPLED(N, L) coupled_form<N, L>(iso, joint, g, wg, t, cnt, grad, data, rg, U + o, rho, R + o, E + o, S + o, Dg + o, bb + po, sums + po * REGION_ROBUST_SUMS, esum + po, s)
-        if (now) { if (lnk) SC_COUPLED(true, true); else SC_COUPLED(true, false); }
-        else { if (lnk) SC_COUPLED(false, true); else SC_COUPLED(false, false); }
-#undef SC_COUPLED
+    for_coupled_tables<RegionJobs>(g, wg, jobs, sides, m, coupling, [&](auto iso, auto joint, const RegionJobs &t, int cnt, const RhoGeo &rg, size_t o, size_t po, size_t ro) {
+        constexpr bool ISO = decltype(iso)::value, JOINT = decltype(joint)::value;
+        const bool lnk = t.sx[0] != nullptr;
+        auto go = !t.w[0] ? (lnk ? coupled_launches<true, true, ISO, JOINT> : coupled_launches<true, false, ISO, JOINT>)
+                          : (lnk ? coupled_launches<false, true, ISO, JOINT> : coupled_launches<false, false, ISO, JOINT>);
+        go(g, wg, t, cnt, grad, data, rg, U + o, Rho + ro, R + o, E + o, S + o, Dg + o, bb + po, sums + po * REGION_ROBUST_SUMS, esum + po, s);
     });
 }
 

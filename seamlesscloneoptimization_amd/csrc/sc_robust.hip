@@ -1,6 +1,7 @@
-// sc_robust.hip -- the robust call's kernels of its own (sc_hip_robust*, sc_robust_api.cpp): k_robust_setup, k_wls_setup (sc_wls.hip) with
-// the links computed from the current iterate instead of read from the caller, and behind it the two launches of the coupled forms
-// (isotropic, joint channels: k_robust_rho, k_robust_setup_rho).  One reweighting round of
+// sc_robust.hip -- the robust call's kernels of its own (sc_hip_robust*, sc_robust_api.cpp: RobustOperator's launches in a reweighting
+// round, which RobustRounds::reweigh there describes): k_robust_setup, k_wls_setup (sc_wls.hip) with the links computed from the
+// current iterate instead of read from the caller, and behind it the two launches of the coupled forms (isotropic, joint channels:
+// k_robust_rho, k_robust_setup_rho).  The system of a round of
 //     minimise  sum w phi_q(u - d) + sum_x-links c_x phi_p(u(x+1,y) - u(x,y) - gx) + sum_y-links c_y phi_p(u(x,y+1) - u(x,y) - gy),
 //     phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2),
 // is the WLS system with s = c rho_p(link residual), w' = w rho_q(u - d), rho_r(t) = (t^2 + eps^2)^((r-2)/2), all at the iterate U on
@@ -9,8 +10,8 @@
 // The link to the north is the link to the south of the row above, carried in a register (computed once at the band's first row); the
 // link to the west is computed again from the west neighbour's u -- by the same expression on the same operands as that neighbour's east
 // link, hence with the same bits: E of the neighbour and this pixel's share of Dg agree and L stays symmetric.
-// rho in float32: r = 2: 1, and the base value passes through without a multiply; r = 1: 1 / sqrt(t t + eps eps), square and sum rounded
-// separately; else powf(t t + eps eps, (r - 2) / 2).
+// rho in float32 (sc_pcg_device.h: robust_rho, robust_link, robust_data): r = 2: 1, and the base value passes through without a
+// multiply; r = 1: 1 / sqrt(t t + eps eps), square and sum rounded separately; else powf(t t + eps eps, (r - 2) / 2).
 #include "sc_pcg_device.h"
 #include <cmath>
 
@@ -76,11 +77,8 @@ __global__ __launch_bounds__(WL) void k_robust_setup(PoissonGeo g, PcgGeo wg, Wl
                 d = rounded_product(north.s, gv);
             } else north = RobustLink{ 0.f, 0.0 };
             float v = (a - b) + (cc - d);
-            // the data term at the iterate: w' = w rho_q(u - d)
-            const float wv = w[o], dv = j.d[o];
-            float q;
-            const float rho = robust_rho(td, uc - dv, q), wr = td.mode == 0 ? wv : rounded_product(wv, rho);
-            v = screened_rhs(v, wr, dv);
+            double e_d;
+            const float wr = robust_data(td, w[o], j.d[o], uc, v, e_d);
             if (dir_w) v -= rounded_product(westl.s, b_w);
             if (dir_n) v -= rounded_product(north.s, b_n);
             if (dir_e) v -= rounded_product(east.s, b_e);
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(WL) void k_robust_setup(PoissonGeo g, PcgGeo wg, Wl
             s_w += (double)wr;
             // every live link once, as k_wls_stats counts them: by its low end, a link to a Dirichlet pixel by its unknown end
             s_l += ((double)east.s + (double)south.s) + ((dir_w ? (double)westl.s : 0.0) + (dir_n ? (double)north.s : 0.0));
-            s_e += robust_phi(td, wv, q, rho) + ((east.e + south.e) + ((dir_w ? westl.e : 0.0) + (dir_n ? north.e : 0.0)));
+            s_e += e_d + ((east.e + south.e) + ((dir_w ? westl.e : 0.0) + (dir_n ? north.e : 0.0)));
             north = south;
         }
     }
@@ -115,23 +113,8 @@ __global__ __launch_bounds__(WL) void k_robust_setup(PoissonGeo g, PcgGeo wg, Wl
 //   k_robust_setup_rho  k_robust_setup with s = c rho read at the pixel, its west and its north neighbour; its energy is the data term's.
 // float32: t t rounded, times c rounded (no base links: no multiply), a_x + a_y within a pixel, then the running sum over the channels
 // 0 .. C - 1, Q = M + eps eps, rho = 1 / sqrtf(Q) (p = 1) or powf(Q, (p - 2) / 2), s = c rho rounded.  Both ends of a link read the same
-// rho and the same c: the same bits, L stays symmetric.  p = 2 never comes here (launch_robust_coupled: the bits change nothing then).
-struct RhoGeo { int rw, ncomp; long long rstride; };
-
-template <bool BASE>
-__device__ __forceinline__ float robust_sq(const float *__restrict__ c, long long o, float t)
-{
-    const float q = rounded_product(t, t);
-    return BASE ? rounded_product(c[o], q) : q;
-}
-// rho_p(M) and the magnitude's energy (2 / p) Q rho in double from the float32 Q and rho
-__device__ __forceinline__ float coupled_rho(const RobustTerm &r, float m, double &e)
-{
-    const float q = m + r.eps2, rho = r.mode == 1 ? 1.0f / sqrtf(q) : powf(q, r.half_exp);
-    e = (double)r.scale * ((double)q * (double)rho);
-    return rho;
-}
-
+// rho and the same c: the same bits, L stays symmetric.  p = 2 never comes here (RobustRounds::coupling: the bits change nothing then).
+// RhoGeo, robust_sq, coupled_rho and the side tables' offsets (for_coupled_tables) are sc_pcg_device.h's: the region call's forms use them too.
 // grid: cg x bands x units; esum[(the unit's first plane * PCG_PARTS + part)] = the part's gradient energy
 template <bool BASE, bool ISO, bool JOINT>
 __global__ __launch_bounds__(WL) void k_robust_rho(PoissonGeo g, PcgGeo wg, WlsJobs t, RobustTerm tg, RhoGeo rg, const float *__restrict__ U,
@@ -247,11 +230,8 @@ __global__ __launch_bounds__(WL) void k_robust_setup_rho(PoissonGeo g, PcgGeo wg
                 d = rounded_product(north, j.gy[on]);
             } else north = 0.f;
             float v = (a - b) + (cc - d);
-            // the data term at the iterate: w' = w rho_q(u - d)
-            const float wv = w[o], dv = j.d[o];
-            float q;
-            const float rho = robust_rho(td, uc - dv, q), wr = td.mode == 0 ? wv : rounded_product(wv, rho);
-            v = screened_rhs(v, wr, dv);
+            double e_d;
+            const float wr = robust_data(td, w[o], j.d[o], uc, v, e_d);
             if (dir_w) v -= rounded_product(westl, b_w);
             if (dir_n) v -= rounded_product(north, b_n);
             if (dir_e) v -= rounded_product(east, b_e);
@@ -264,7 +244,7 @@ __global__ __launch_bounds__(WL) void k_robust_setup_rho(PoissonGeo g, PcgGeo wg
             s_bb += (double)v * (double)v;
             s_w += (double)wr;
             s_l += ((double)east + (double)south) + ((dir_w ? (double)westl : 0.0) + (dir_n ? (double)north : 0.0));
-            s_e += robust_phi(td, wv, q, rho);
+            s_e += e_d;
             north = south;
         }
     }
@@ -291,19 +271,10 @@ void coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const WlsJobs &t, i
 void launch_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m, const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho,
                            float *R, float *E, float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s)
 {
-    const bool iso = (coupling & ROBUST_ISO) != 0, joint = (coupling & ROBUST_JOINT) != 0;
-    RhoGeo rg;
-    rg.rw = wg.x0 + wg.nx;
-    rg.ncomp = iso ? 1 : 2;
-    rg.rstride = robust_rho_stride(wg);
-    for_side_tables<WlsJobs>(jobs, sides, m, [&](const WlsJobs &t, int i0, int cnt) {
-        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
-        float *rho = Rho + (size_t)(joint ? i0 : g.C * i0) * rg.ncomp * rg.rstride;
-        const bool base = t.sx[0] != nullptr;
-#define SC_COUPLED(B, I, J) coupled_launches<B, I, J>(g, wg, t, cnt, grad, data, rg, U + o, rho, R + o, E + o, S + o, Dg + o, bb + po, sums + po * ROBUST_SUMS, esum + po, s)
-        if (base) { if (iso) { if (joint) SC_COUPLED(true, true, true); else SC_COUPLED(true, true, false); } else SC_COUPLED(true, false, true); }
-        else { if (iso) { if (joint) SC_COUPLED(false, true, true); else SC_COUPLED(false, true, false); } else SC_COUPLED(false, false, true); }
-#undef SC_COUPLED
+    for_coupled_tables<WlsJobs>(g, wg, jobs, sides, m, coupling, [&](auto iso, auto joint, const WlsJobs &t, int cnt, const RhoGeo &rg, size_t o, size_t po, size_t ro) {
+        constexpr bool ISO = decltype(iso)::value, JOINT = decltype(joint)::value;
+        auto go = t.sx[0] ? coupled_launches<true, ISO, JOINT> : coupled_launches<false, ISO, JOINT>;
+        go(g, wg, t, cnt, grad, data, rg, U + o, Rho + ro, R + o, E + o, S + o, Dg + o, bb + po, sums + po * ROBUST_SUMS, esum + po, s);
     });
 }
 

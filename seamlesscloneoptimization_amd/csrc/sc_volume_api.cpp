@@ -20,9 +20,9 @@
 //               k_volume_dct transposed: exact for constant coefficients.  The factor 1 / s-bar goes once on u0 (scale_start).
 // All six side arrays of a volume come in PcgOperator::ds beside the job (NULL where the call carries none: the front end's word).
 // sc_hip_volume_robust (its own three entries, below): Lp penalties on the spatial links, the temporal links and the data term.  Round 0
-// is sc_hip_volume_wls's chunk with default precond_*; VolumeRobustOperator::reweigh puts the system at the iterate in its place
-// (k_volume_robust_setup, sc_volume_robust.hip) and the round's sums in place of the statistics'; the rounds are robust_chunk's
-// (sc_robust_api.cpp), which drives this operator and the robust call's through RobustRounds.
+// is sc_hip_volume_wls's chunk with default precond_*; the chunk, its rounds and the round itself are sc_robust_api.cpp's (robust_chunk,
+// RobustRounds::reweigh), for which VolumeRobustOperator provides the launch (k_volume_robust_setup, sc_volume_robust.hip) and takes
+// the round's sums in place of the statistics'.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -214,8 +214,6 @@ int volume_device_call(Instance *I, const PcgCall &call, const Params *p, const 
 // ---- the robust volume call: the volume operator with the links of the current round -- round 0 from the caller's arrays (the WLS
 // volume call's system, default precond_*), later rounds from the iterate (k_volume_robust_setup).  Its statistics are always the full
 // form: a round's means divide by the counts of live links.
-constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
-
 sc_volume_wls_params wls_params_of(const sc_volume_robust_params *p)
 {
     return sc_volume_wls_params{ p->kind, p->frames, p->frame_stride, p->tau, p->time_periodic, p->tol, p->max_iters, 0.f, 0.f, 0.f };
@@ -229,64 +227,40 @@ int volume_robust_validate(const sc_volume_robust_params *p, const sc_poisson_la
     const sc_volume_wls_params q = wls_params_of(p);          // (the coupling bits stay in kind: the family's kinds refuse them)
     const int rc = volume_wls_validate(&q, l, why);
     if (rc) return rc;
-    const char *own = robust_bad_exponent(p->p_grad) || robust_bad_exponent(p->p_time) || robust_bad_exponent(p->p_data)
-                        ? "p_grad, p_time and p_data must lie in (0, 2]"
-                    : robust_bad_eps(p->p_grad, p->eps_grad) || robust_bad_eps(p->p_time, p->eps_time) || robust_bad_eps(p->p_data, p->eps_data)
-                        ? "eps_grad, eps_time and eps_data must be finite and > 0 where their exponent is not 2"
-                    : !std::isfinite(p->round_tol) ? "round_tol must be finite"
-                    : poisson_base(p->kind) == SC_POISSON_LAPLACIAN ? "a robust solve needs the guidance itself: the base kind must be SC_POISSON_GUIDANCE"
-                    : (p->kind & COUPLING_BITS) ? "the coupled forms are not offered on volumes" : nullptr;
+    const char *own = robust_penalties_why({ { p->p_grad, p->eps_grad }, { p->p_time, p->eps_time }, { p->p_data, p->eps_data } },
+                                           "p_grad, p_time and p_data must lie in (0, 2]",
+                                           "eps_grad, eps_time and eps_data must be finite and > 0 where their exponent is not 2", p->tol, p->round_tol,
+                                           p->kind);
+    if (!own && (p->kind & COUPLING_BITS)) own = "the coupled forms are not offered on volumes";
     if (own) { *why = own; return SC_ERR_BAD_ARG; }
     return SC_OK;
 }
 
+// Sums: w' | spatial links | temporal links | UNKNOWN - KNOWN | energy.  (No coupled form: the check refuses the bits.)
 struct VolumeRobustOperator final : VolumeOperator, RobustRounds {
-    const sc_volume_robust_params prm;
-    const sc_volume_wls_params base;
-    const RobustTerm grad, time, data;
     const bool base_links, base_tlinks;
     VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, bool links_, bool tlinks_)
         : VolumeRobustOperator(I_, p, wls_params_of(p), links_, tlinks_) {}
     VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_)
-        : VolumeOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS, true), prm(*p), base(q), grad(robust_term(p->p_grad, p->eps_grad)),
-          time(robust_term(p->p_time, p->eps_time)), data(robust_term(p->p_data, p->eps_data)), base_links(links_), base_tlinks(tlinks_) {}
+        : VolumeOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS, true),
+          RobustRounds(robust_term(p->p_grad, p->eps_grad), robust_term(p->p_data, p->eps_data), robust_term(p->p_time, p->eps_time), p->max_rounds,
+                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS),
+          base_links(links_), base_tlinks(tlinks_) {}
     RobustRounds *rounds() override { return this; }
-    bool quadratic() const override { return grad.mode == 0 && time.mode == 0 && data.mode == 0; }
-    int max_rounds() const override { return prm.max_rounds; }
-    float round_tol() const override { return prm.round_tol; }
     void begin() override
     {
         VolumeOperator::begin();
         links = base_links;          // round 0 of a new chunk: the caller's arrays again
         tlinks = base_tlinks;
     }
-    // A later round: the system at the chunk's iterate in place of the operator's, the round's sums in place of the statistics' (the
-    // counts of live links and of UNKNOWN pixels stay: the states do not change), and that iterate's energy per plane (one wait)
-    int reweigh(PcgChunk &c, std::vector<double> &energy) override
+    int launch(PcgChunk &c, int, double *) override
     {
         PcgState &S = *I->pcg;
-        const size_t parts = (size_t)c.planes * PCG_PARTS;
         launch_volume_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
                                    (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
-        SC_HIP(I, hipGetLastError());
-        SC_HIP(I, hipMemcpyAsync(c.h_round, c.d_round, sizeof(double) * parts * VOLUME_ROBUST_SUMS, hipMemcpyDeviceToHost, I->stream));
-        SC_HIP(I, hipStreamSynchronize(I->stream));
-        energy.assign(c.planes, 0.0);
-        wsum = ssum = tsum = uksum = 0.0;
-        links = tlinks = true;
-        for (int p = 0; p < c.planes; ++p) {
-            const double *plane = c.h_round + (size_t)p * PCG_PARTS * VOLUME_ROBUST_SUMS;
-            for (int i = 0; i < c.nop; ++i) {
-                const double *part = plane + (size_t)i * VOLUME_ROBUST_SUMS;
-                wsum += part[0];
-                ssum += part[1];
-                tsum += part[2];
-                uksum += part[3];
-                energy[p] += part[4];
-            }
-        }
         return SC_OK;
     }
+    void take(const double *t) override { wsum = t[0]; ssum = t[1]; tsum = t[2]; uksum = t[3]; links = tlinks = true; }
 };
 
 PcgCall volume_robust_call(int kind, const sc_volume_robust_params *p)

@@ -1,6 +1,7 @@
-// sc_volume_robust.hip -- the robust volume call's one kernel of its own (sc_hip_volume_robust*, sc_volume_api.cpp): k_volume_robust_setup,
-// k_volume_setup (sc_volume.hip) with every link computed from the current iterate as k_robust_setup (sc_robust.hip) computes them.  One
-// reweighting round of
+// sc_volume_robust.hip -- the robust volume call's one kernel of its own (sc_hip_volume_robust*, sc_volume_api.cpp: VolumeRobustOperator's
+// launch in a reweighting round, which RobustRounds::reweigh in sc_robust_api.cpp describes): k_volume_robust_setup, k_volume_setup
+// (sc_volume.hip) with every link computed from the current iterate as k_robust_setup (sc_robust.hip) computes them.  The system of a
+// round of
 //     minimise  sum w phi_q(u - d) + sum c_x phi_p(dx u - gx) + sum c_y phi_p(dy u - gy) + sum c_t phi_r(u_(t+1) - u_t - gt)
 // over the UNKNOWN pixels of a stack of frames is the WLS volume system with s = c rho(link residual) on every live link and w' = w
 // rho_q(u - d), all at the iterate U on the work plane of stacked frames (sc_volume.hip: its layout).  c_x, c_y: smooth_x, smooth_y
@@ -29,13 +30,6 @@ namespace {
 // Every live link is counted once, under k_volume_stats' owner rule: by its low end (the last pixel of a periodic axis owns the
 // wrapping link, the earlier frame a temporal link, frame T - 1 the wrapping one) whether that end is UNKNOWN or KNOWN, and by its
 // UNKNOWN end where the other lies on a low Dirichlet line.
-__device__ __forceinline__ void lane_term(RobustTerm &r)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(r.eps2), "+v"(r.half_exp), "+v"(r.scale));
-#endif
-}
-
 template <bool NOW, bool LNK, bool PER>
 __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, RobustTerm tg, RobustTerm tt, RobustTerm td,
                                                              const float *__restrict__ U, float *__restrict__ R, float *__restrict__ E,
@@ -43,7 +37,6 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
                                                              double *__restrict__ bb, double *__restrict__ sums)
 {
     __shared__ double ws[VOLUME_ROBUST_SUMS + 1][4];
-    // the penalties' constants in vector registers: the walk is short of scalar ones
     lane_term(tg); lane_term(tt); lane_term(td);
     const PcgBand bd(g, wg);
     const PoissonJobDev &j = t.j[bd.member];
@@ -132,14 +125,10 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
                     v = ((pa - pb) + (pc - pd)) + (pe - pf);
                     float wr = 0.f;
                     if (!NOW) {
-                        // the data term at the iterate: w' = w rho_q(u - d)
-                        const float wv = w[o], dv = j.d[o];
-                        float q;
-                        const float rho = robust_rho(td, uc - dv, q);
-                        wr = td.mode == 0 ? wv : rounded_product(wv, rho);
-                        v = screened_rhs(v, wr, dv);
+                        double e_d;
+                        wr = robust_data(td, w[o], j.d[o], uc, v, e_d);
                         s_w += (double)wr;
-                        s_e += robust_phi(td, wv, q, rho);
+                        s_e += e_d;
                     }
                     if (a.kw == NB_DIRICHLET) v -= rounded_product(lw, u_w);
                     if (a.kn == NB_DIRICHLET) v -= rounded_product(ln, u_n);

@@ -256,7 +256,8 @@ def test_out_may_be_data(inst):
 
 
 # ---- 5. a device batch -----------------------------------------------------------------------------------------------------------------
-def test_a_batch_of_seventeen_jobs(inst):
+@pytest.mark.parametrize("coupling", [0, rr.ISO | rr.JOINT, rr.ISO])      # (coupled: the second job table's rho planes)
+def test_a_batch_of_seventeen_jobs(inst, coupling):
     configure(inst)
     n, bad_state, stray = 17, 5, 16
     case = ("free_lt", 9, 11, 3, "scatter", "sparse", None)
@@ -280,7 +281,7 @@ def test_a_batch_of_seventeen_jobs(inst):
         dev.append(inst.to_device(np.full((H, W, C), SENTINEL, np.float32)))
         jobs[k].out = dev[-1]
     try:
-        kind = G | capi.border_bits(probs[0]["sides"], False, probs[0]["periodic"])
+        kind = G | capi.border_bits(probs[0]["sides"], False, probs[0]["periodic"]) | capi.robust_coupling_bits(bool(coupling & rr.ISO), bool(coupling & rr.JOINT))
         params = capi.RobustParams(kind, pen[0], pen[2], pen[1], pen[3], rb.ROUNDS, -1.0, 0.0, 0)
         rc = inst.region_robust_device(params, capi.poisson_layout_of(probs[0]["data"]), jobs, allow_job_errors=True)
         codes = [j.rc for j in jobs]
@@ -293,17 +294,17 @@ def test_a_batch_of_seventeen_jobs(inst):
     for k in refused:
         assert (outs[k] == np.float32(SENTINEL)).all(), "a refused job's out was written"
     stay = [k for k in range(n) if k not in refused]
-    chunk = rr.irls_f32([probs[k] for k in stay], pen, rb.ROUNDS)
+    chunk = rr.irls_f32([probs[k] for k in stay], pen, rb.ROUNDS, coupling)
     for k, (u32, its) in zip(stay, chunk):
-        y = rb.Yardstick(probs[k], pen, u32=u32, iters32=its)
+        y = rb.Yardstick(probs[k], pen, coupling, u32=u32, iters32=its)
         err, res = y.measure(u32[-2], outs[k])          # (the iterate before the last: the restatement's, the library's own stays on the device)
         eb, _ = y.bounds()
         assert err <= eb, (k, err, eb)
         assert_copied_bits(probs[k], outs[k])
     # one member against its solo run: they differ by no more than both bounds
     k = stay[-1]
-    y = rb.Yardstick(probs[k], pen)
-    solo = solve(inst, probs[k], pen, rb.ROUNDS)
+    y = rb.Yardstick(probs[k], pen, coupling)
+    solo = solve(inst, probs[k], pen, rb.ROUNDS, coupling)
     assert float(np.abs(outs[k] - solo).max()) / probs[k]["range"] <= 2 * max(rb.ERR_FACTOR * y.err32, rb.ERR_FLOOR)
 
 

@@ -16,6 +16,9 @@ Behind them the families whose jobs carry a state array (region, volume, WLS vol
 and 16 x 5 of one (under a frame 14 unknown columns, no multiple of a float4), guidance and Laplacian forms, with and without weight
 and link arrays, free and periodic time, and per family two device batches -- three jobs of which job 0 has a bad state element (the
 two that stay and every array of theirs move to the front) and 17 one-channel jobs (two job tables).  --sides: these lines alone.
+Last the robust rounds (--rounds: these lines alone): the image call under the coupled forms, the region call on scattered states and
+the volume call of four frames, at 17 x 23 and at 300 x 17 pixels (two column groups, three bands) of three channels, and 17-job
+device batches of the image and region calls under the coupled forms (two side tables).
 
     python tools/solve_digest.py --pcg [--root DIR] > profiles/pcg_digest_<build>.txt
 """
@@ -31,6 +34,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--pcg", action="store_true")
 ap.add_argument("--sides", action="store_true")
+ap.add_argument("--rounds", action="store_true")
 ARGS = ap.parse_args()
 sys.path.insert(0, os.path.abspath(ARGS.root))
 
@@ -330,6 +334,94 @@ def side_batch(inst, name, sides, periodic, W, H, C, m, refuse=None):
             pcg_emit(inst, name, sides, periodic, "x%d %s" % (m, tag), got[:, nf, :n].tobytes() + np.array([j.rc for j in jobs], np.int32).tobytes())
 
 
+# ---- the robust rounds (--rounds: these lines alone): what the image, region and volume robust calls share -- the fold over parts and
+# planes, the coupled forms' rho planes and gradient energy, the second side table's offsets.  Three rounds, every one run; out and
+# robust_trace() hashed; the tiling (capi.pcg_plan) on the line.
+COUPLINGS = [(False, False, "aniso"), (True, False, "iso"), (False, True, "joint"), (True, True, "iso+joint")]
+PQ = ((1.0, 2.0), (0.8, 1.0))
+# (name, W, H, C, free sides); the second: two column groups, three bands of the 17 unknown rows between free ends
+ROUND_SHAPES = (("rounds 17x23 C3", 17, 23, 3, ""), ("rounds 300x17 C3", 300, 17, 3, "tb"))
+
+
+def rounds_emit(inst, name, W, H, sides, frames, tag, call):
+    plan = capi.pcg_plan(W, H, capi.SC_POISSON_GUIDANCE | capi.free_side_bits(sides), frames)
+    if W == 300 and frames == 1:
+        assert plan["cg"] == 2 and plan["bands"] == 3, plan
+    try:
+        digest = hashlib.sha256(np.ascontiguousarray(call()).tobytes() + robust_trace_bytes(inst)).hexdigest() + " %d" % inst.info().sweeps
+    except capi.SeamlessCloneError as e:
+        digest = hashlib.sha256(str(e).encode()).hexdigest() + " refused"
+    print("%s [%s|-] [cg=%d bands=%d] %s" % (name, sides or "-", plan["cg"], plan["bands"], tag), digest, flush=True)
+
+
+def rounds_single(inst):
+    for name, W, H, C, sides in ROUND_SHAPES:
+        a = side_arrays(name, 1, SIDE_T, H, W, C)                    # (k odd: the three states scattered)
+        f0 = {k: v[0] for k, v in a.items()}
+        for p, q in PQ:
+            kw = dict(p_grad=p, p_data=q, allow_not_converged=True, **ROBUST)
+            for iso, joint, ctag in COUPLINGS[1:]:                   # the image call under the coupled forms
+                for prec in ("f32", "f64"):
+                    configure(inst, capi.SC_FLAG_FFT_FP64 if prec == "f64" else 0)
+                    for links in (False, True):
+                        base = (f0["sx"], f0["sy"]) if links else ()
+                        rounds_emit(inst, name, W, H, sides, 1, "robust %s %s %s p=%g q=%g" % (prec, "links" if links else "unit", ctag, p, q),
+                                    lambda: inst.robust(f0["gx"], f0["gy"], f0["data"], f0["weight"], *base, boundary=f0["boundary"], free_sides=sides,
+                                                        isotropic=iso, joint_channels=joint, **kw))
+            configure(inst, 0)
+            for iso, joint, ctag in COUPLINGS:                       # the region call on the scattered states
+                for w in (False, True):
+                    for links in (False, True):
+                        lk = dict(smooth_x=f0["sx"], smooth_y=f0["sy"]) if links else {}
+                        rounds_emit(inst, name, W, H, sides, 1, "region_robust %s %s %s p=%g q=%g" % ("w" if w else "-", "xy" if links else "--", ctag, p, q),
+                                    lambda: inst.region_robust(f0["gx"], f0["gy"], f0["data"], f0["state"], f0["weight"] if w else None,
+                                                               boundary=f0["boundary"], free_sides=sides, isotropic=iso, joint_channels=joint, **lk, **kw))
+            for loop in (False, True):                               # the volume call: four frames
+                n = SIDE_T if loop else SIDE_T - 1
+                for t in (False, True):
+                    lk = dict(smooth_t=a["smt"][:n]) if t else {}
+                    rounds_emit(inst, name, W, H, sides, SIDE_T, "volume_robust %s %s p=%g q=%g" % ("t" if t else "-", "loop" if loop else "free", p, q),
+                                lambda: inst.volume_robust(a["gx"], a["gy"], a["data"], a["state"], a["weight"], a["sx"], a["sy"], gt=a["gt"][:n],
+                                                           boundary=a["boundary"], tau=0.7, loop=loop, free_sides=sides, p_time=p, eps_time=0.5, **lk, **kw))
+
+
+def rounds_batch(inst, name, W, H, C, m):
+    """m jobs in one device call of the image and of the region call under ISO | JOINT and under ISO: two side tables.  The digest covers
+    every job's out, the trace and the jobs' codes."""
+    configure(inst, 0)
+    nf, n, slot = len(SIDE_FIELDS), W * H * C, (W * H * C + 63) // 64 * 64
+    layout = capi.PoissonLayout(W, H, C, C, W * C, 1)
+    host = np.zeros((m, nf + 1, slot), np.float32)                   # SIDE_FIELDS, out
+    for k in range(m):
+        a = side_arrays(name, k, 1, H, W, C)
+        host[k, :nf, :n] = [a[f].reshape(-1) for f in SIDE_FIELDS]
+    for family in ("robust", "region_robust"):
+        for iso, joint, ctag in (COUPLINGS[3], COUPLINGS[1]):
+            dev = inst.malloc(host.nbytes)
+            try:
+                inst._check(inst.L.sc_hip_memcpy_h2d(inst.h, dev, host.ctypes.data, host.nbytes))
+                at = lambda k, f: dev + 4 * slot * ((nf + 1) * k + (SIDE_FIELDS + ("out",)).index(f))      # noqa: E731
+                jobs = getattr(capi.Instance, "make_%s_jobs" % family)(m)
+                for k, j in enumerate(jobs):
+                    j.gx, j.gy, j.data, j.weight, j.boundary, j.out = (at(k, f) for f in ("gx", "gy", "data", "weight", "boundary", "out"))
+                    j.smooth_x, j.smooth_y = at(k, "sx"), at(k, "sy")
+                    if family == "region_robust":
+                        j.state = at(k, "state")
+                params = capi.RobustParams(capi.SC_POISSON_GUIDANCE | capi.robust_coupling_bits(iso, joint), 0.8, ROBUST["eps_grad"], 1.0,
+                                           ROBUST["eps_data"], ROBUST["max_rounds"], ROBUST["round_tol"], 0.0, 0)
+                getattr(inst, family + "_device")(params, layout, jobs, allow_job_errors=True)
+                got = inst.from_device(dev, host.shape, np.float32)
+            finally:
+                inst.free(dev)
+            pcg_emit(inst, name, "", "", "x%d %s %s" % (m, family, ctag), got[:, nf, :n].tobytes() + robust_trace_bytes(inst) +
+                     np.array([j.rc for j in jobs], np.int32).tobytes())
+
+
+def rounds_main(inst):
+    rounds_single(inst)
+    rounds_batch(inst, "rounds tables 17x23 C3", 17, 23, 3, 17)
+
+
 def side_main(inst):
     for sides in ("", "lt"):
         side_single(inst, "sides 17x23 C3", sides, "", 17, 23, 3)
@@ -360,6 +452,7 @@ def pcg_main(inst):
     for sides, periodic in (("", ""), ("lrtb", "")):
         pcg_single(inst, "budget 40x130 C3", sides, periodic, 40, 130, 3, max_iters=3, allow_not_converged=True)
     side_main(inst)
+    rounds_main(inst)
 
 
 def main():
@@ -367,6 +460,8 @@ def main():
     try:
         if ARGS.sides:
             return side_main(inst)
+        if ARGS.rounds:
+            return rounds_main(inst)
         if ARGS.pcg:
             return pcg_main(inst)
         for f in range(16):                                          # every border combination; all-Dirichlet is the untouched control
