@@ -887,6 +887,95 @@ SC_API int sc_hip_region_device(void *instance, const sc_region_params *p, const
 SC_API int sc_hip_region(void *instance, const sc_region_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x,
                          const float *smooth_y, const float *boundary, float *out);
+/* ---- bounded solves: box constraints lower <= u <= upper on a region solve ---------------------------------------------------------------
+ * The problem: sc_hip_region's, per channel, word for word -- the three states, the links live in the region, the data term, both forms
+ * of the right-hand side, every border kind -- minimised under the constraint
+ *     lower <= u <= upper   at every UNKNOWN pixel.
+ * The bounds say nothing about KNOWN pixels, OUTSIDE pixels or Dirichlet lines.  A Poisson clone that stays inside the displayable
+ * range, a height or depth field integrated from gradients that never goes negative, a matte or confidence map interpolated from
+ * scribbles that stays in [0, 1], a membrane over an obstacle.  Clamping an unconstrained answer is not this: the constrained minimiser
+ * spreads what the bound cuts off over the free pixels and differs from the clamped one everywhere.
+ * Bounds: sc_bounded_params.lower / .upper are scalars; -INFINITY / +INFINITY mean no bound on that side.  sc_bounded_job.lower /
+ * .upper, where not NULL, are arrays under the call's layout that replace the scalar for that job; they are read at UNKNOWN pixels
+ * only.  In a device call the first job decides for each of the two arrays (as for weight); a job that differs gets SC_ERR_BAD_ARG.
+ * The arrays fall under the span rule against out, as state does.
+ * The method: the primal-dual active set method (Hintermueller, Ito, Kunisch 2002).  The region system is a symmetric M-matrix (links
+ * > 0, weights >= 0), for which the method is monotone with one-sided bounds and ends after finitely many rounds.
+ *   round 0   sc_hip_region's system, set-up and cold start, unchanged.
+ *   the mark  after every solve one launch (k_bounded_mark) forms r = L u - b of the ORIGINAL system at every active pixel (the rule asks
+ *             for it nowhere else), in float32:
+ *             ((lw (uw - u) + le (ue - u)) + (ln (un - u) + ls (us - u))) - w (u - d) - the guidance term (lap, or (a - b) + (c - d)).
+ *             Across a link it reads the bound at an active pixel, data at a KNOWN pixel, boundary on a Dirichlet line, and the iterate
+ *             anywhere else; u of an active pixel is its bound.  r = - dE/du: at a minimiser r >= 0 on the upper bound, <= 0 on the lower.
+ *   the rule  a free pixel with u > upper becomes upper-active, one with u < lower lower-active; an upper-active pixel stays while
+ *             r > 0, a lower-active one while r < 0; every other pixel is free.  The launch writes the new set to the second of two
+ *             set planes (the neighbours read the first) and per part the number of pixels whose set changed: doubles, no atomics,
+ *             one host read.
+ *   set-up    if any pixel of the chunk changed, a second launch (k_bounded_setup) builds the round's system: k_region_setup's planes
+ *             with an active pixel treated as a KNOWN one whose value is its bound (its terms follow the KNOWN neighbours' in the
+ *             right-hand side's order: west, north, east, south).  It puts the bound into the iterate at every pixel that is or was
+ *             active, so a pixel released later starts from its bound, and sums what the preconditioner's w-bar is refreshed from: w
+ *             over the free pixels, the links from a free pixel to a KNOWN or active one, the free pixels (a second host read; s-bar
+ *             stays round 0's).  The conjugate gradients then start warm from the iterate.
+ *   the end   no pixel of any job of the chunk changed: the iterate satisfies the KKT conditions to the inner tolerance.  When
+ *             max_rounds solves have run and the set still changes, the last iterate is returned with sc_run_info.converged = 0 and
+ *             SC_OK (the robust call's convention for rounds); SC_ERR_NOT_CONVERGED is kept for an inner solve that ran out of
+ *             max_iters.  sc_run_info.sweeps is the total of the inner iterations.
+ * Rounds: the contact set of a smooth obstacle problem (constant load, one bound) grows by one layer of pixels per round, so the
+ * rounds grow with the side length there: 8 at 32 x 32, 13 at 64 x 64, 22 at 128 x 128 in float64, 94 at 512 x 512 on the device.
+ * Bounds at the quartiles of a rough unconstrained answer take 3 to 8 rounds on the tests' inputs (up to 300 pixels a side), the same
+ * as the float64 method.  Raise max_rounds for large smooth contact sets.  On megapixel inputs the set settles to a handful of
+ * changing pixels within some 15 rounds and then a last pixel may alternate for long -- a 1024 x 1024 x 3 clone that overshoots by a
+ * quarter of the range ended after 72 rounds, the same at 2048 x 2048 x 1 had one pixel alternating after 200:
+ * with max_rounds = 30 such a call returns converged = 0, its answer in range and within the inner tolerance of the KKT conditions.
+ * What is written: every element the layout names -- the bound's bits at active pixels; the iterate clamped into [lower, upper] at free
+ * UNKNOWN pixels (after a converged stop the clamp changes nothing; after running out of rounds it still guarantees the range);
+ * data's bits at KNOWN and OUTSIDE pixels; boundary's bits on the Dirichlet lines.  out may equal data or boundary.
+ * Exact ties: (a) no finite bound anywhere (both scalars infinite, no arrays): the bytes of sc_hip_region, no extra launch, no extra
+ * wait; (b) bounds that round 0's iterate already satisfies: the bytes of sc_hip_region after one mark launch, a trace of one entry;
+ * (c) lower == upper: the bound's bits at every UNKNOWN pixel; (d) two runs of one call give the same bytes.
+ * Codes: sc_hip_region_check's for parameters and layout, and SC_ERR_BAD_ARG for a scalar bound that is NaN or scalars with lower >
+ * upper.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others run -- for everything sc_hip_region refuses; a bound that
+ * is NaN or lower > upper at an UNKNOWN pixel (at other pixels the bounds are not read); a bound array where the first job has none
+ * (or the reverse), misaligned, or overlapping out.
+ * Not offered: bounds together with robust penalties, on volumes, or through the 8-bit entry points; a tolerance rule for degenerate
+ * pixels (u on its bound with r = 0) that alternate between the sets under inexact inner solves -- they show as converged = 0 with a
+ * KKT violation at the inner tolerance's scale. */
+typedef struct sc_bounded_params {
+    int   kind;              /* as sc_region_params */
+    float tol;
+    int   max_iters;
+    float precond_lambda;
+    float precond_smooth;
+    float lower, upper;      /* the bounds where a job gives no array; -INFINITY / +INFINITY: none on that side */
+    int   max_rounds;        /* solves per chunk at the most; <= 0: 30 */
+} sc_bounded_params;
+typedef struct sc_bounded_job {
+    const float *gx, *gy;    /* as sc_region_job */
+    const float *lap;
+    const float *data;
+    const float *state;
+    const float *weight;
+    const float *smooth_x;
+    const float *smooth_y;
+    const float *boundary;
+    const float *lower;      /* per-pixel bounds under the layout, read at UNKNOWN pixels; NULL: the scalar */
+    const float *upper;
+    float *out;              /* every element the layout names is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_bounded_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_bounded_check(const sc_bounded_params *p, const sc_poisson_layout *l);
+/* Device pointers.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_bounded_device(void *instance, const sc_bounded_params *p, const sc_poisson_layout *l, sc_bounded_job *jobs, int n, bool bSync);
+/* One problem on host arrays, as sc_hip_region: spans in and out through pinned staging, only the named elements of out written.
+ * lower, upper: arrays, or NULL for the scalars. */
+SC_API int sc_hip_bounded(void *instance, const sc_bounded_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                          const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x,
+                          const float *smooth_y, const float *boundary, const float *lower, const float *upper, float *out);
+/* The last bounded call's last chunk, round by round: entry k holds the pixels whose set changed in the mark behind solve k, the
+ * pixels active after it, and solve k's inner iterations.  Returns the number of entries (fills at most cap); any pointer may be NULL. */
+SC_API int sc_hip_bounded_trace(void *instance, int *changed, int *active, int *iters, int cap);
 /* ---- robust region solves: Lp and TV penalties on a domain of any shape ------------------------------------------------------------------
  * sc_hip_region's domain with sc_hip_robust's penalties in place of the squares.  Per channel, with exponents 0 < p, q <= 2, the call
  * minimises over the UNKNOWN pixels

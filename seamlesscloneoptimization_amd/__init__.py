@@ -11,7 +11,8 @@ from .seamless_clone import (SeamlessClone, colorChange, edit_batch, gradient_fi
                              robust_solve_batch, tv_denoise, integrate_gradients, region_solve, region_solve_batch, inpaint, poisson_clone, volume_solve, inpaint_video,
                              poisson_clone_video, volume_wls_solve, wls_filter_video, interpolate_constraints_video, make_loop,
                              volume_robust_solve, tv_denoise_video, integrate_gradients_video, region_robust_solve, region_robust_solve_batch,
-                             tv_inpaint, integrate_gradients_masked)
+                             tv_inpaint, integrate_gradients_masked, bounded_solve, bounded_solve_batch, poisson_clone_in_range,
+                             interpolate_in_range)
 
 __all__ = ["capi", "compare", "ymlio", "SeamlessClone", "seamlessClone", "colorChange", "illuminationChange", "textureFlattening",
            "edit_batch", "poisson_solve", "poisson_solve_batch", "screened_solve", "screened_solve_batch", "gradient_filter",
@@ -20,4 +21,5 @@ __all__ = ["capi", "compare", "ymlio", "SeamlessClone", "seamlessClone", "colorC
            "region_solve", "region_solve_batch", "inpaint", "poisson_clone", "volume_solve", "inpaint_video", "poisson_clone_video",
            "volume_wls_solve", "wls_filter_video", "interpolate_constraints_video", "make_loop",
            "volume_robust_solve", "tv_denoise_video", "integrate_gradients_video", "region_robust_solve", "region_robust_solve_batch",
-           "tv_inpaint", "integrate_gradients_masked"]
+           "tv_inpaint", "integrate_gradients_masked", "bounded_solve", "bounded_solve_batch", "poisson_clone_in_range",
+           "interpolate_in_range"]

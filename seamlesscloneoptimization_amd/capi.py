@@ -254,6 +254,19 @@ class RegionJob(C.Structure):
                 ("rc", C.c_int)]
 
 
+# bounded solves (sc_hip_bounded*): Instance.bounded / bounded_device -- region solves under lower <= u <= upper at the UNKNOWN pixels;
+# bounded_trace() reports the rounds
+class BoundedParams(C.Structure):
+    _fields_ = [("kind", C.c_int), ("tol", C.c_float), ("max_iters", C.c_int), ("precond_lambda", C.c_float), ("precond_smooth", C.c_float),
+                ("lower", C.c_float), ("upper", C.c_float), ("max_rounds", C.c_int)]
+
+
+class BoundedJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p),
+                ("weight", C.c_void_p), ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("boundary", C.c_void_p), ("lower", C.c_void_p),
+                ("upper", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # volume solves (sc_hip_volume*): Instance.volume / volume_device -- region solves on frame stacks with temporal links
 class VolumeParams(C.Structure):
     _fields_ = [("kind", C.c_int), ("frames", C.c_int), ("frame_stride", C.c_longlong), ("tau", C.c_float), ("tol", C.c_float),
@@ -578,6 +591,14 @@ def load():
     L.sc_hip_robust.restype = C.c_int
     L.sc_hip_robust_trace.argtypes = [C.c_void_p, f64p, i32p, C.c_int]
     L.sc_hip_robust_trace.restype = C.c_int
+    L.sc_hip_bounded_check.argtypes = [C.POINTER(BoundedParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_bounded_check.restype = C.c_int
+    L.sc_hip_bounded_device.argtypes = [C.c_void_p, C.POINTER(BoundedParams), C.POINTER(PoissonLayout), C.POINTER(BoundedJob), C.c_int, C.c_bool]
+    L.sc_hip_bounded_device.restype = C.c_int
+    L.sc_hip_bounded.argtypes = [C.c_void_p, C.POINTER(BoundedParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 12
+    L.sc_hip_bounded.restype = C.c_int
+    L.sc_hip_bounded_trace.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int]
+    L.sc_hip_bounded_trace.restype = C.c_int
     _lib = L
     return L
 
@@ -895,6 +916,51 @@ def region_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, gx=Non
             links.append(a)
         smooth_x, smooth_y = links
     return kind, data, state, weight, smooth_x, smooth_y, gx, gy, lap, boundary, out
+
+
+def bounded_check(kind: int = SC_POISSON_GUIDANCE, lower: float = -np.inf, upper: float = np.inf, max_rounds: int = 0, tol: float = 0.0,
+                  max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0, layout: "PoissonLayout | None" = None, *,
+                  cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_bounded_check: SC_OK or the code a bounded call with these parameters and this layout returns before it runs
+    anything.  The layout as a PoissonLayout or as keyword fields."""
+    p = BoundedParams(int(kind), float(tol), int(max_iters), float(precond_lambda), float(precond_smooth), float(lower), float(upper),
+                      int(max_rounds))
+    return _check_call("sc_hip_bounded_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def bounded_arrays(data, state, lower=None, upper=None, weight=None, smooth_x=None, smooth_y=None, gx=None, gy=None, lap=None, boundary=None,
+                   out=None, neumann=False, free_sides="", periodic=""):
+    """Checks a bounded problem's numpy arrays and bounds before any device is touched: (kind, data, state, weight, smooth_x, smooth_y,
+    gx, gy, lap, boundary, out, lower scalar, upper scalar, lower array, upper array), region_arrays' rules for all but the bounds.
+    lower, upper: None (no bound on that side), a number, or a float32 array of data's shape or H x W (broadcast over the channels);
+    an array stands in for the scalar, which then reads -inf / +inf.  No bound may be NaN, and lower <= upper must hold at every
+    UNKNOWN pixel the borders call an unknown (elsewhere the bounds are not read)."""
+    kind, data, state, weight, sx, sy, gx, gy, lap, boundary, out = region_arrays(data, state, weight, smooth_x, smooth_y, gx, gy, lap, boundary,
+                                                                                  out, neumann, free_sides, periodic)
+    read = border_unknowns(kind, *data.shape[:2])
+    read = (read if data.ndim == 2 else read[:, :, None]) & (state == SC_REGION_UNKNOWN)
+    scalars, arrays = [], []
+    for name, b, none in (("lower", lower, -np.inf), ("upper", upper, np.inf)):
+        if isinstance(b, np.ndarray) and b.ndim:
+            if b.ndim == 2 and data.ndim == 3 and b.shape == data.shape[:2]:
+                b = np.ascontiguousarray(np.broadcast_to(b[:, :, None], data.shape))
+            _same_shape_f32(name, b, data)
+            if np.isnan(b[read]).any():
+                raise ValueError(f"{name} must not be NaN at an UNKNOWN pixel")
+            scalars.append(none)
+            arrays.append(b)
+        else:
+            b = none if b is None else float(b)
+            if b != b:
+                raise ValueError(f"{name} must not be NaN")
+            scalars.append(float(np.float32(b)))
+            arrays.append(None)
+    lo = arrays[0][read] if arrays[0] is not None else scalars[0]
+    hi = arrays[1][read] if arrays[1] is not None else scalars[1]
+    if np.any(np.asarray(lo) > np.asarray(hi)):
+        raise ValueError("lower must not exceed upper at an UNKNOWN pixel")
+    return (kind, data, state, weight, sx, sy, gx, gy, lap, boundary, out, *scalars, *arrays)
 
 
 def volume_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, tol: float = 0.0, max_iters: int = 0,
@@ -1411,6 +1477,40 @@ class Instance:
         wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures
         raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_region_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- bounded solves on float32 arrays
+    def bounded(self, data, state, lower=None, upper=None, weight=None, smooth_x=None, smooth_y=None, gx=None, gy=None, lap=None, boundary=None,
+                neumann=False, out=None, free_sides="", periodic="", max_rounds=0, tol=0.0, max_iters=0, precond_lambda=0.0,
+                precond_smooth=0.0, allow_not_converged=False):
+        """sc_hip_bounded on numpy float32 arrays of shape H x W or H x W x C (C 1..4): region()'s problem under lower <= u <= upper at
+        every UNKNOWN pixel, by the primal-dual active set method on the device.  lower, upper: None (no bound on that side), a number,
+        or a float32 array of data's shape or H x W (bounded_arrays).  Returns out as region() composes it, the UNKNOWN pixels inside
+        their bounds; info() has the total of the inner iterations and whether the active set stopped changing within max_rounds
+        (0: 30), bounded_trace() the rounds."""
+        kind, data, state, weight, sx, sy, gx, gy, lap, boundary, out, lo, hi, lo_a, hi_a = bounded_arrays(
+            data, state, lower, upper, weight, smooth_x, smooth_y, gx, gy, lap, boundary, out, neumann, free_sides, periodic)
+        p = BoundedParams(kind, float(tol), int(max_iters), float(precond_lambda), float(precond_smooth), lo, hi, int(max_rounds))
+        return self._host_call("sc_hip_bounded", p, (gx, gy, lap, data, state, weight, sx, sy, boundary, lo_a, hi_a), out, data,
+                               (SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+
+    @staticmethod
+    def make_bounded_jobs(n: int):
+        return (BoundedJob * n)()
+
+    def bounded_device(self, params: BoundedParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_bounded_device: jobs is a BoundedJob array (make_bounded_jobs) of device pointers, one layout for all.  sync: bSync and
+        a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code: SC_ERR_NOT_CONVERGED is returned, other failures
+        raise unless allow_job_errors (then they are returned as well)."""
+        return self._device_call("sc_hip_bounded_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    def bounded_trace(self):
+        """(changed, active, iters) of the last bounded call's last chunk: int32 arrays with one entry per round -- the pixels whose set
+        changed in the mark behind that round's solve, the pixels active after it, the solve's inner iterations."""
+        n = int(self.L.sc_hip_bounded_trace(self.h, None, None, None, 0))
+        changed, active, iters = (np.zeros(n, np.int32) for _ in range(3))
+        if n:
+            self.L.sc_hip_bounded_trace(self.h, changed.ctypes.data_as(i32p), active.ctypes.data_as(i32p), iters.ctypes.data_as(i32p), n)
+        return changed, active, iters
 
     # ---- robust region solves on float32 arrays
     def region_robust(self, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="",

@@ -21,6 +21,7 @@
 //      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
 //      sc_hip_region_robust_check: the robust call's verdicts (the region call's on a guidance base), the coupling bits accepted, then every
 //      exponent, every eps, round_tol and tol.
+//      sc_hip_bounded_check: the region call's verdicts under any valid pair of scalar bounds, then lower > upper and a NaN bound.
 //      sc_hip_volume_robust_check: the WLS volume call's verdicts on a guidance base, then every exponent, every eps, round_tol, the coupling
 //      bits, a Laplacian base and the WLS volume call's own refusals.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
@@ -444,6 +445,20 @@ int main()
             if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check");
             rg.precond_smooth = k.plam;
             if (sc_hip_region_check(&rg, &l) != k.want) return fail("region_check (precond_smooth)");
+            // the bounded call: the region call's verdicts whatever valid bounds it carries, then its own refusals of the scalars
+            struct Pair { float lo, hi; };
+            for (const Pair b : { Pair{ -inf, inf }, Pair{ 0.f, 1.f }, Pair{ 0.25f, 0.25f }, Pair{ -inf, 0.f } }) {
+                sc_bounded_params bp{ k.kind, k.tol, k.iters, k.plam, 0.f, b.lo, b.hi, 7 };
+                if (sc_hip_bounded_check(&bp, &l) != k.want) return fail("bounded_check");
+            }
+            if (k.want == SC_OK) {
+                for (const Pair b : { Pair{ 1.f, 0.f }, Pair{ nan, 1.f }, Pair{ 0.f, nan }, Pair{ inf, -inf } }) {
+                    sc_bounded_params bp{ k.kind, k.tol, k.iters, k.plam, 0.f, b.lo, b.hi, 0 };
+                    if (sc_hip_bounded_check(&bp, &l) != SC_ERR_BAD_ARG) return fail("bounded_check (bounds)");
+                }
+                sc_bounded_params bp{ k.kind, k.tol, k.iters, k.plam, 0.f, 0.f, 1.f, 0 };
+                if (sc_hip_bounded_check(nullptr, &l) != SC_ERR_BAD_ARG || sc_hip_bounded_check(&bp, nullptr) != SC_ERR_BAD_ARG) return fail("bounded_check (null)");
+            }
             // the volume call: the region call's verdicts for two frames a frame's span apart, then its own refusals
             const long long span = k.want == SC_OK ? (k.w - 1) * k.cs + (k.h - 1) * k.rs + (k.c - 1) * k.chs + 1 : 1LL << 40;
             sc_volume_params vp{ k.kind, 2, span, 1.f, k.tol, k.iters, k.plam };

@@ -165,6 +165,7 @@ struct Instance {
     DevBuf h_sx, h_sy;                             // a WLS host call's two link arrays (float_stage)
     DevBuf h_state;                                // a region host call's state array (float_stage)
     DevBuf h_gt, h_smt;                            // a volume host call's temporal guidance and temporal link weights (float_stage)
+    DevBuf h_lo, h_hi;                             // a bounded host call's bound arrays (float_stage)
     std::unique_ptr<RowCopier> copier;   // helper threads for the packing / splicing copies (created on first use)
     hipEvent_t ev_chunk[8]{};            // D2H chunk completions (host path): splice chunk k while k+1 is in flight
     // ROI mask after 3x erode
@@ -381,13 +382,14 @@ inline bool poisson_no_dirichlet(int kind)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 // What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
-enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16, FLOAT_SMOOTH_T = 32 };
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16, FLOAT_SMOOTH_T = 32, FLOAT_LOWER = 64, FLOAT_UPPER = 128 };
 struct FloatArrays {
     const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; const float *smooth_x = nullptr, *smooth_y = nullptr;
     const float *state = nullptr;      // FLOAT_STATE: the region call's state array
     const float *gt = nullptr;         // FLOAT_GT: the volume call's temporal guidance (may be NULL: zeros)
     const float *smooth_t = nullptr;   // FLOAT_SMOOTH_T: the WLS volume call's temporal link weights
     const char *refuse = nullptr;      // the family's own reason against this job (float_job_validate: SC_ERR_BAD_ARG with it)
+    const float *lower = nullptr, *upper = nullptr;      // FLOAT_LOWER, FLOAT_UPPER: the bounded call's per-pixel bounds
 };
 // A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
 // family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
@@ -400,14 +402,15 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 // FLOAT_SMOOTH: the two link arrays as well, and -- span > 0, the floats an array occupies under the call's layout (poisson_span) --
 // neither they nor weight may share a float of their span with out's.  FLOAT_STATE: the state array as well, under the same span rule
 // (which then holds for whichever of weight and the link arrays the call carries).  FLOAT_SMOOTH_T: the temporal link array as well; it
-// occupies tspan floats (the call's temporal frames) and may share none of them with out's span.
+// occupies tspan floats (the call's temporal frames) and may share none of them with out's span.  FLOAT_LOWER, FLOAT_UPPER: that bound
+// array as well, under state's span rule.
 int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0, size_t tspan = 0);
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
 // A job's side arrays: what a family's set-up reads beside the job's PoissonJobDev -- data weights, spatial link weights, the region
-// and volume calls' state, the volume calls' temporal guidance and temporal link weights.  Device pointers; an array the call does not
+// and volume calls' state, the volume calls' temporal guidance and temporal link weights, the bounded call's bound arrays.  Device pointers; an array the call does not
 // carry (its FLOAT_* bit is not in `carries`) is NULL: float_intake and float_stage say so, nobody behind them asks again.  One record
 // per job, beside its PoissonJobDev from there to the kernels' tables (sc_pcg.h: PcgOperator::ds, for_side_tables).
-struct SideArrays { const float *w = nullptr, *sx = nullptr, *sy = nullptr, *st = nullptr, *gt = nullptr, *smt = nullptr; };
+struct SideArrays { const float *w = nullptr, *sx = nullptr, *sy = nullptr, *st = nullptr, *gt = nullptr, *smt = nullptr, *lo = nullptr, *hi = nullptr; };
 // The validated jobs of a device call: their device forms (contiguous: the Poisson and the screened call hand dj.data() to the solve),
 // their side arrays and where each one's code goes.
 struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<SideArrays> side; std::vector<int *> rcs; };
@@ -434,13 +437,14 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
         const bool smooth = (carries & FLOAT_SMOOTH) != 0;
         v.side.push_back(SideArrays{ carries & FLOAT_WEIGHT ? a.weight : nullptr, smooth ? a.smooth_x : nullptr, smooth ? a.smooth_y : nullptr,
                                      carries & FLOAT_STATE ? a.state : nullptr, carries & FLOAT_GT ? a.gt : nullptr,
-                                     carries & FLOAT_SMOOTH_T ? a.smooth_t : nullptr });
+                                     carries & FLOAT_SMOOTH_T ? a.smooth_t : nullptr, carries & FLOAT_LOWER ? a.lower : nullptr,
+                                     carries & FLOAT_UPPER ? a.upper : nullptr });
         v.rcs.push_back(&j.rc);
     }
     return worst;
 }
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
-// boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state --, uploaded in that order.  job: the
+// boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state | lower | upper --, uploaded in that order.  job: the
 // device job (float_dev_job's rules; job.out is what poisson_download reads), side: the staged side arrays (NULL where the call carries none).
 // frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; the
 // temporal arrays -- gt, FLOAT_GT and not NULL, and smooth_t, FLOAT_SMOOTH_T -- hold tframes of them (0: frames - 1) and go behind

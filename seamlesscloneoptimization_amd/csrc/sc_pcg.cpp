@@ -272,8 +272,9 @@ void pcg_release(Instance *I)
 {
     if (!I->pcg) return;
     PcgState &S = *I->pcg;
-    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.f, &S.dct, &S.tab, &S.rho, &S.red }) dev_release(*b);
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.f, &S.dct, &S.tab, &S.rho, &S.act, &S.bad, &S.red }) dev_release(*b);
     if (S.h_red.p) (void)hipHostFree(S.h_red.p);
+    if (S.h_bad.p) (void)hipHostFree(S.h_bad.p);
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);
     delete I->pcg;
 }

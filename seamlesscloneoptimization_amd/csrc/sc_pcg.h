@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
 // of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the three
 // robust calls share: their rounds, their check and their entry preamble (RobustRounds, robust_chunk, robust_begin; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
@@ -34,11 +34,15 @@ struct PcgState {
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
     DevBuf f, dct, tab;                    // the volume solve's (sc_volume.hip): links to the next frame; the transformed planes; the DCT table (float) and the modes' shifts (double)
     DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude
+    DevBuf act;                            // the bounded solve's two set planes (sc_bounded.hip): 0 free, +1 upper-active, -1 lower-active
+    DevBuf bad, h_bad;                     // ... and its judgement of bound arrays: per part the UNKNOWN pixels with an invalid bound (double; device, pinned)
     DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane | a family's round sums
     DevBuf h_red;                          // pinned: the statistics' copy | b.b parts | RING slots of ||r||^2 per plane | a family's round sums
     hipEvent_t ev[RING]{};
     std::vector<double> trace_energy;      // the last robust call's last chunk (sc_hip_robust_trace): per round the energy of its iterate
     std::vector<int> trace_iters;          // ... and its inner iterations
+    // the last bounded call's last chunk (sc_hip_bounded_trace), its own three: per round the pixels that changed set, the active ones, the inner iterations
+    std::vector<int> trace_changed, trace_active, trace_bounded_iters;
 };
 void pcg_release(Instance *I);             // frees Instance::pcg and all it holds
 
@@ -516,5 +520,35 @@ void launch_region_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const Poi
 void launch_region_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                   const RobustTerm &grad, const RobustTerm &data, int coupling, const float *U, float *Rho, float *R, float *E,
                                   float *S, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
+
+// ---- the bounded family (sc_bounded.hip): the region system under lower <= u <= upper at the UNKNOWN pixels, by the primal-dual active
+// set method -- every round the region system with the active pixels held at their bound (seamlessclone_hip.h, the bounded section).  A
+// set plane lies beside the work planes (PcgGeo::stride apart): 0 free, +1 upper-active, -1 lower-active, 0 at a pixel that is not UNKNOWN.
+struct BoundedJobs {
+    enum { MAX = 16 }; PoissonJobDev j[MAX]; const float *w[MAX], *sx[MAX], *sy[MAX], *st[MAX], *lo[MAX], *hi[MAX];
+    void set(int i, const PoissonJobDev &job, const SideArrays &a)
+    {
+        j[i] = job; w[i] = a.w; sx[i] = a.sx; sy[i] = a.sy; st[i] = a.st; lo[i] = a.lo; hi[i] = a.hi;
+    }
+};
+struct BoundScalars { float lo, hi; };      // the bounds of a job without the array
+constexpr int BOUNDED_SUMS = 3;
+// bad[plane * PCG_PARTS + i] = the part's UNKNOWN pixels whose bound is NaN or whose lower > upper
+void launch_bounded_stats(const PoissonGeo &g, const PcgGeo &wg, const BoundScalars &bs, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                          double *bad, hipStream_t s);
+// r = L u - b of the original system at every pixel active in `cur` (the rule asks for it nowhere else), u read through that set (an
+// active pixel: its bound), and the set rule: the next set into `next`; sums[(plane * PCG_PARTS + i) * BOUNDED_SUMS + ..] = the part's pixels whose set changed | its active pixels
+void launch_bounded_mark(const PoissonGeo &g, const PcgGeo &wg, bool lap, const BoundScalars &bs, const PoissonJobDev *jobs, const SideArrays *sides,
+                         int m, const float *U, const float *cur, float *next, double *sums, hipStream_t s);
+// launch_region_setup with the pixels active in `set` treated as KNOWN at their bound; U = the bound wherever `set` or `prev` (the set
+// of the solve before) is active; sums[..] = the part's sum of w over the free pixels | of its links from a free pixel to a KNOWN or
+// active one | its free pixels
+void launch_bounded_setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, const BoundScalars &bs, const PoissonJobDev *jobs, const SideArrays *sides,
+                          int m, const float *set, const float *prev, float *U, float *R, float *E, float *S, float *Dg, double *bb, double *sums,
+                          hipStream_t s);
+// the jobs' out: the bound's bits at the pixels active in `set`, U clamped into its bounds at the free ones, data's bits at KNOWN and
+// OUTSIDE pixels, boundary's bits on the Dirichlet lines
+void launch_bounded_out(const PoissonGeo &g, const PcgGeo &wg, const BoundScalars &bs, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                        const float *U, const float *set, hipStream_t s);
 
 } // namespace sc

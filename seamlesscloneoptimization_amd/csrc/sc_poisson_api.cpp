@@ -146,6 +146,14 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
         if (!a.smooth_t) { *why = "null smooth_t pointer"; return SC_ERR_BAD_ARG; }
         if (!aligned4(a.smooth_t)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
     }
+    if (carries & FLOAT_LOWER) {
+        if (!a.lower) { *why = "null lower pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(a.lower)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
+    if (carries & FLOAT_UPPER) {
+        if (!a.upper) { *why = "null upper pointer"; return SC_ERR_BAD_ARG; }
+        if (!aligned4(a.upper)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+    }
     if (span && (carries & (FLOAT_SMOOTH | FLOAT_STATE))) {
         const uintptr_t o = (uintptr_t)a.out, bytes = span * sizeof(float);
         auto overlaps = [&](const float *q) { return (uintptr_t)q < o + bytes && o < (uintptr_t)q + bytes; };
@@ -153,6 +161,8 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
                                 carries & FLOAT_SMOOTH ? a.smooth_y : nullptr })
             if (q && overlaps(q)) { *why = "weight, smooth_x or smooth_y overlaps out"; return SC_ERR_BAD_ARG; }
         if ((carries & FLOAT_STATE) && overlaps(a.state)) { *why = "state overlaps out"; return SC_ERR_BAD_ARG; }
+        for (const float *q : { carries & FLOAT_LOWER ? a.lower : nullptr, carries & FLOAT_UPPER ? a.upper : nullptr })
+            if (q && overlaps(q)) { *why = "lower or upper overlaps out"; return SC_ERR_BAD_ARG; }
     }
     if (span && tspan && (carries & FLOAT_SMOOTH_T)) {          // (its own length: the call's temporal frames)
         const uintptr_t o = (uintptr_t)a.out, q = (uintptr_t)a.smooth_t;
@@ -178,9 +188,9 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     const float *boundary = carries && poisson_no_dirichlet(kind) ? nullptr : a.boundary;
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
     const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0, gt = (carries & FLOAT_GT) && guidance && a.gt;
-    const bool smooth_t = (carries & FLOAT_SMOOTH_T) != 0;
+    const bool smooth_t = (carries & FLOAT_SMOOTH_T) != 0, lower = (carries & FLOAT_LOWER) != 0, upper = (carries & FLOAT_UPPER) != 0;
     const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0) + (gt ? 1 : 0) +
-                      (smooth_t ? 1 : 0);
+                      (smooth_t ? 1 : 0) + (lower ? 1 : 0) + (upper ? 1 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -191,6 +201,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
     float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state), *d_gt = next(gt), *d_smt = next(smooth_t);
+    float *d_lo = next(lower), *d_hi = next(upper);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -205,7 +216,9 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     const size_t tbytes = (poisson_span(l) + (size_t)((tframes > 0 ? tframes : frames - 1) - 1) * (size_t)frame_stride) * sizeof(float);
     if (d_gt && (rc = upload_rows(I, I->h_gt, d_gt, tbytes, (const uint8_t *)a.gt, tbytes, tbytes, 1))) return rc;
     if (d_smt && (rc = upload_rows(I, I->h_smt, d_smt, tbytes, (const uint8_t *)a.smooth_t, tbytes, tbytes, 1))) return rc;
-    s.side = SideArrays{ d_w, d_sx, d_sy, d_state, d_gt, d_smt };      // (an array the call does not carry has no slot: NULL)
+    if ((rc = upload(I->h_lo, d_lo, a.lower))) return rc;
+    if ((rc = upload(I->h_hi, d_hi, a.upper))) return rc;
+    s.side = SideArrays{ d_w, d_sx, d_sy, d_state, d_gt, d_smt, d_lo, d_hi };      // (an array the call does not carry has no slot: NULL)
     return SC_OK;
 }
 

@@ -1162,3 +1162,103 @@ def integrate_gradients_masked(gx, gy, valid, known=None, values=None, p=1.0, ep
     data = np.where((v if gx.ndim == 2 else v[:, :, None]), values, np.float32(0)).astype(np.float32)
     return region_robust_solve(gx, gy, data, state, p=p, eps_grad=eps, neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id,
                                isotropic=isotropic, joint_channels=joint_channels, **solver)
+
+
+def bounded_solve(data, state, lower=None, upper=None, gx=None, gy=None, laplacian=None, weight=None, smooth_x=None, smooth_y=None, boundary=None,
+                  neumann=True, free_sides=None, periodic="", max_rounds=None, tol=None, validate=False, max_iters=None, precond_lambda=None,
+                  precond_smooth=None, gpu_id=0, **solver):
+    """region_solve under the box constraint lower <= u <= upper at every unknown pixel, on a float32 image of shape H x W or H x W x C
+    (C 1..4): the minimiser of region_solve's energy among the images inside the bounds -- not the clamped unconstrained answer, which
+    it differs from everywhere.  lower, upper: None (no bound on that side), a number, or a float32 array of data's shape or H x W;
+    known and outside pixels and the Dirichlet lines are not constrained.  By the primal-dual active set method on the GPU: the
+    unconstrained solve, then up to max_rounds (default 30) region solves with the pixels on a bound held there, each started from the
+    last; it ends when the set of held pixels stops changing.  Everything else is region_solve's.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    kind, data, state, weight, smooth_x, smooth_y, gx, gy, laplacian, boundary = capi.bounded_arrays(
+        data, state, lower, upper, weight, smooth_x, smooth_y, gx, gy, laplacian, boundary, neumann=neumann, free_sides=free_sides,
+        periodic=periodic)[:10]
+    if validate:
+        _region_validate(kind, state, weight)
+    with _instance(gpu_id, solver) as inst:
+        return inst.bounded(data, state, lower, upper, weight, smooth_x, smooth_y, gx=gx, gy=gy, lap=laplacian, boundary=boundary, neumann=neumann,
+                            free_sides=free_sides, periodic=periodic, max_rounds=max_rounds or 0, tol=tol or 0.0, max_iters=max_iters or 0,
+                            precond_lambda=precond_lambda or 0.0, precond_smooth=precond_smooth or 0.0)
+
+
+def bounded_solve_batch(datas, states, lower=None, upper=None, gxs=None, gys=None, laplacians=None, weights=None, smooth_xs=None, smooth_ys=None,
+                        boundaries=None, neumann=True, free_sides=None, periodic="", max_rounds=None, tol=None, validate=False, max_iters=None,
+                        precond_lambda=None, precond_smooth=None, gpu_id=0, **solver):
+    """bounded_solve over a list of same-shape problems through ONE device-resident call (sc_hip_bounded_device), as region_solve_batch:
+    the rounds, the inner stops and the preconditioner's constants are joint, so a member agrees with its solo solve to the stop rule's
+    error.  lower, upper: None or a number for every problem, or a list of arrays, one per problem.  Returns a list of NEW arrays."""
+    per_problem = {f: v for f, v in (("lower", lower), ("upper", upper)) if isinstance(v, (list, tuple))}
+    scalar = {f: None if f in per_problem else v for f, v in (("lower", lower), ("upper", upper))}
+    bounds = {}
+
+    def arrays_of(d, a, borders):
+        kind, d, st, w, sx, sy, gx, gy, lap, b, _, lo, hi, lo_a, hi_a = capi.bounded_arrays(
+            d, a["state"], a.get("lower", scalar["lower"]), a.get("upper", scalar["upper"]), a.get("weight"), a.get("smooth_x"), a.get("smooth_y"),
+            a.get("gx"), a.get("gy"), a.get("lap"), a.get("boundary"), **borders)
+        if validate:
+            _region_validate(kind, st, w)
+        bounds["lower"], bounds["upper"] = lo, hi
+        return kind, dict(gx=gx, gy=gy, lap=lap, data=d, state=st, weight=w, smooth_x=sx, smooth_y=sy, boundary=b, lower=lo_a, upper=hi_a)
+    refusal = _GUIDANCE_WHY if (gxs is None) != (gys is None) or (gxs is not None and laplacians is not None) else \
+        "smooth_xs and smooth_ys go together" if (smooth_xs is None) != (smooth_ys is None) else None
+    return _pcg_batch("bounded", datas, boundaries, neumann, free_sides, periodic, gpu_id, solver,
+                      required=dict(state=states),
+                      optional=dict(gx=gxs, gy=gys, lap=laplacians, weight=weights, smooth_x=smooth_xs, smooth_y=smooth_ys, **per_problem),
+                      refusal=refusal,
+                      length_why="one state and, where given, one weight, one pair of link weights, one guidance field (or laplacian), one array "
+                                 "per bound and, with a Dirichlet line, one boundary per data term",
+                      arrays_of=arrays_of,
+                      slots=("gx", "gy", "lap", "data", "state", "weight", "smooth_x", "smooth_y", "boundary", "lower", "upper"),
+                      params_of=lambda kind: capi.BoundedParams(kind, float(tol or 0.0), int(max_iters or 0), float(precond_lambda or 0.0),
+                                                                float(precond_smooth or 0.0), bounds["lower"], bounds["upper"],
+                                                                int(max_rounds or 0)),
+                      make_jobs=capi.Instance.make_bounded_jobs, device_call=capi.Instance.bounded_device)
+
+
+def poisson_clone_in_range(src, dst, mask, lo=0.0, hi=1.0, mixed=False, gpu_id=0, **solver):
+    """poisson_clone with the result kept inside [lo, hi] (the displayable range) wherever it is solved for: a bright patch cloned into a
+    dark scene overshoots, and clamping the overshoot flattens it while the rest of the patch stays as if nothing had been cut off --
+    here the excess is spread over the whole patch (bounded_solve).  Outside the mask the result is dst, bit for bit, whatever its
+    range.  With bounds the unconstrained clone already satisfies, the bytes of poisson_clone.  Returns a NEW array."""
+    for name, a in (("src", src), ("dst", dst)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+            raise TypeError(f"{name} must be a float32 numpy array")
+    if src.shape != dst.shape:
+        raise ValueError(f"src has shape {src.shape}, dst {dst.shape}")
+    m = _mask_of("mask", mask, dst)
+    if m.all():
+        raise ValueError("the mask covers the whole image: nothing of dst is left to join")
+    gx, gy = _forward_differences(src)
+    if mixed:
+        dx, dy = _forward_differences(dst)
+        gx, gy = np.where(np.abs(dx) > np.abs(gx), dx, gx), np.where(np.abs(dy) > np.abs(gy), dy, gy)
+    state = np.where(m, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    return bounded_solve(dst, state, lo, hi, gx=gx, gy=gy, neumann=True, gpu_id=gpu_id, **solver)
+
+
+def interpolate_in_range(values, known_mask, lo, hi, guide=None, edge_sigma=None, image_gradients=None, gpu_id=0, **solver):
+    """interpolate_constraints with hard samples and the answer kept inside [lo, hi]: the pixels where known_mask (H x W, anything
+    truthy) is set hold their values exactly, the others are filled from them -- a membrane, or along image_gradients = (gx, gy), whose
+    integration may leave the range -- and stay inside the bounds (an alpha matte or a confidence map in [0, 1], a depth that is not
+    negative).  guide, edge_sigma: interpolate_constraints' edge-stopping link weights.  lo, hi: numbers or arrays, bounded_solve's.
+    Returns a NEW array."""
+    if not isinstance(values, np.ndarray) or values.dtype != np.float32:
+        raise TypeError("values must be a float32 numpy array")
+    m = _mask_of("known_mask", known_mask, values)
+    gx, gy = (None, None) if image_gradients is None else image_gradients
+    if guide is None and edge_sigma is not None:
+        raise ValueError("edge_sigma needs a guide")
+    sx = sy = None
+    if guide is not None:
+        g = np.asarray(guide, np.float64)
+        if g.shape[:2] != values.shape[:2]:
+            raise ValueError(f"guide has shape {g.shape[:2]}, the image {values.shape[:2]}")
+        sigma = 0.1 * float(g.max() - g.min()) if edge_sigma is None else float(edge_sigma)
+        if not np.isfinite(sigma) or not sigma > 0:
+            raise ValueError("edge_sigma must be finite and > 0 (None: a tenth of the guide's range, which must not be flat)")
+        sx, sy = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in _forward_abs_differences(g))
+    return bounded_solve(values, m, lo, hi, gx=gx, gy=gy, smooth_x=sx, smooth_y=sy, neumann=True, gpu_id=gpu_id, **solver)
