@@ -1224,8 +1224,9 @@ SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, cons
  * Codes: everything sc_hip_volume_wls_check refuses; everything sc_hip_robust_check refuses for exponents, eps, tol, round_tol and a
  * Laplacian base; SC_ERR_BAD_ARG for SC_ROBUST_ISOTROPIC / SC_ROBUST_JOINT_CHANNELS in kind.  Per job: the WLS volume call's refusals;
  * the first volume decides for weight and for the link arrays.
- * Not offered: coupled forms on volumes, motion-compensated temporal links, the 8-bit entry points.  A single image with states and
- * robust penalties is sc_hip_region_robust's, which also takes the coupled forms. */
+ * Not offered here: the coupled forms -- kind refuses their bits; sc_hip_volume_coupled below takes a coupling of its own, time
+ * included --; anywhere: motion-compensated temporal links, the 8-bit entry points.  A single image with states and robust penalties
+ * is sc_hip_region_robust's, which also takes the coupled forms. */
 typedef struct sc_volume_robust_params {
     int       kind;              /* as sc_volume_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
     int       frames;            /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
@@ -1262,6 +1263,62 @@ SC_API int sc_hip_volume_robust_device(void *instance, const sc_volume_robust_pa
 SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                                 const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x,
                                 const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
+/* ---- coupled volume solves: isotropic, space-time and joint-channel total variation on frame stacks ---------------------------------------
+ * sc_hip_volume_robust with one penalty over several links, as SC_ROBUST_ISOTROPIC and SC_ROBUST_JOINT_CHANNELS couple them on single
+ * images (sc_hip_robust, sc_hip_region_robust) -- and a volume's third axis, which those two bits cannot describe.  The parameters and
+ * the jobs are sc_hip_volume_robust's, unchanged; the coupling comes beside them (p->kind carries no coupling bits here either):
+ *     SC_VOLUME_COUPLE_SPACE     one penalty per pixel over its x- and its y-link: per frame the isotropic total variation (p_grad = 1),
+ *                                ROF as usually meant -- discs stay discs where the anisotropic form makes them diamonds;
+ *     SC_VOLUME_COUPLE_TIME      ... and its forward temporal link in the same magnitude: the space-time total variation, which
+ *                                penalises a moving edge once, as one surface.  Comes with SPACE; p_time = p_grad, eps_time = eps_grad;
+ *     SC_VOLUME_COUPLE_CHANNELS  every magnitude sums over the channels of a volume: the vectorial total variation, no colour fringes.
+ * Owners and magnitudes.  The owner of a link is its low end, as in sc_hip_region_robust: the last pixel of a periodic axis owns the
+ * wrapping link, the earlier frame a temporal link, frame frames - 1 the wrapping temporal link.  A pixel of a low Dirichlet line owns
+ * only its one spatial link into the domain, which forms a magnitude of its own; it owns no temporal link (a Dirichlet pixel's temporal
+ * neighbour is a Dirichlet pixel: the link is never live).  For a live link t = (u_hi - u_lo) - g and a = c t^2, c = smooth_x or smooth_y
+ * (NULL: 1, no multiply) or lt = tau * smooth_t rounded once (NULL: tau).  A dead link adds nothing to a magnitude; an owner with no
+ * live link adds nothing to the energy.  With psi_e(M; eps) = (2 / e) (M + eps^2)^(e/2), the gradient-plus-time term of the energy is
+ *     0                         sc_hip_volume_robust's, to the byte
+ *     SPACE                     sum_k sum_pixels psi_p(a_x + a_y; eps_g)  +  sum_k sum_t-links c_t phi_r(t_t; eps_t)
+ *     SPACE | TIME              sum_k sum_pixels psi_p((a_x + a_y) + a_t; eps_g)
+ *     CHANNELS                  sum_x-links psi_p(sum_k a_x)  +  sum_y-links psi_p(sum_k a_y)  +  sum_t-links psi_r(sum_k a_t; eps_t)
+ *     SPACE | CHANNELS          sum_pixels psi_p(sum_k (a_x + a_y))  +  sum_t-links psi_r(sum_k a_t; eps_t)
+ *     SPACE | TIME | CHANNELS   sum_pixels psi_p(sum_k ((a_x + a_y) + a_t))
+ * The data term stays per pixel and per channel.  Under CHANNELS a magnitude sums only the channels in which that link is live (state
+ * is per channel).  TIME without SPACE is SC_ERR_BAD_ARG, and so are unknown bits; TIME with p_time != p_grad or eps_time != eps_grad
+ * (compared as floats) is SC_ERR_BAD_ARG: there is one penalty.
+ * Float32 order, as in the robust sections: t t is rounded, then multiplied by c and rounded; within a pixel the sum is (a_x + a_y) + a_t;
+ * then the running sum over channels 0 .. C - 1; Q = M + eps eps; rho = 1.0f / sqrtf(Q) for exponent 1, powf(Q, (e - 2) / 2) otherwise;
+ * s = c rho, one rounded product.  A magnitude whose exponent is 2 gives rho exactly 1: the base value passes through without a
+ * multiply, and its links' energy is booked link by link, c t^2.  Both ends of a link read the same rho bits.
+ * Rounds.  Round 0 is sc_hip_volume_wls's system, untouched.  Round k >= 1 is the WLS volume system with s = c rho(M) on every link
+ * that shares M and w' = w rho_q(u - d).  The right-hand side, the diagonal, the warm start and each round's means (s-bar, tau-bar,
+ * w-bar) follow sc_hip_volume_robust word for word, and the region family's zero condition holds after every round.  Two launches per
+ * coupled round (k_volume_robust_rho: rho of every owner's magnitudes and the gradient-and-time energy; k_volume_robust_setup_rho: the
+ * system with s read from them) and still one host read.  The rho planes live in the instance's arena: per volume and channel (under
+ * CHANNELS: per volume) frames * (the frame's pixels, rounded up to 64) floats for each component -- one under SPACE | TIME, two under
+ * SPACE, three otherwise, a component whose exponent is 2 not stored; where the arena cannot grow the call returns SC_ERR_HIP.
+ * Effective coupling.  SPACE and TIME change nothing when p_grad = 2; CHANNELS changes nothing on one channel or when p_grad = p_time = 2.
+ * A call whose effective coupling is 0 runs the uncoupled launch and writes the bytes of sc_hip_volume_robust.
+ * Under CHANNELS the round rule judges a volume's energy, the sum over its channels; otherwise a plane's.  sc_hip_robust_trace reports
+ * this call too.  max_rounds, round_tol, SC_ERR_NOT_CONVERGED, sc_run_info, sizes, chunks (a chunk holds whole volumes), methods and
+ * SC_FLAG_FFT_FP64 limits: sc_hip_volume_robust's.
+ * Codes: everything sc_hip_volume_robust_check refuses, coupling bits in kind included; the two refusals of a coupling above.  Per
+ * job: the robust volume call's refusals.
+ * Not offered: a coupled data term, motion-compensated temporal links, a separate s-bar for x and y, bounds on volumes, the 8-bit entry
+ * points. */
+#define SC_VOLUME_COUPLE_SPACE    1   /* one penalty per pixel over its x- and y-link (per frame isotropic TV)          */
+#define SC_VOLUME_COUPLE_TIME     2   /* ... and its forward temporal link in the same magnitude (space-time TV)       */
+#define SC_VOLUME_COUPLE_CHANNELS 4   /* every magnitude sums over the channels of a volume (vectorial TV)            */
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters, this coupling and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_coupled_check(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_coupled_device(void *instance, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l,
+                                        sc_volume_robust_job *jobs, int n, bool bSync);
+/* One volume on host arrays, the arrays of sc_hip_volume_robust in its order. */
+SC_API int sc_hip_volume_coupled(void *instance, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const float *gx,
+                                 const float *gy, const float *gt, const float *data, const float *state, const float *weight,
+                                 const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

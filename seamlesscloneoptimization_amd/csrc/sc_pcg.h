@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_robust.hip: a family's statistics, set-up and operator), the link operator
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_robust.hip, sc_volume_coupled.hip: a family's statistics, set-up and operator), the link operator
 // of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the three
 // robust calls share: their rounds, their check and their entry preamble (RobustRounds, robust_chunk, robust_begin; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
@@ -432,10 +432,12 @@ inline bool robust_bad_exponent(float r) { return !(r > 0.f && r <= 2.f); }
 inline bool robust_bad_eps(float r, float eps) { return r != 2.f && !(std::isfinite(eps) && eps > 0.f); }
 // the two bits of sc_robust_params::kind that are the robust calls' own (the families' kinds know nothing of them), and the launches' word for them
 constexpr int COUPLING_BITS = SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS;
-constexpr int ROBUST_ISO = 1, ROBUST_JOINT = 2;
+// (ROBUST_TIME: the coupled volume call's third word -- the forward temporal link shares the pixel's magnitude; it comes with ROBUST_ISO)
+constexpr int ROBUST_ISO = 1, ROBUST_JOINT = 2, ROBUST_TIME = 4;
 // The reweighting rounds of a robust call: what robust_chunk (sc_robust_api.cpp) asks of an operator beyond PcgOperator
 // (PcgOperator::rounds).  The penalties (time: the volume call's; elsewhere exponent 2), max_rounds and round_tol as the caller gave
-// them, the caller's coupling bits as ROBUST_ISO | ROBUST_JOINT.  A later round is reweigh() -- the one place that says what a round
+// them, the caller's coupling bits as ROBUST_ISO | ROBUST_JOINT (from kind; the coupled volume call's come as launch words of their
+// own, `launch_bits`, ROBUST_TIME among them).  A later round is reweigh() -- the one place that says what a round
 // does --, of which an operator provides three things:
 //   nsums   the doubles per part its round launch sums, the energy last (ROBUST_SUMS, REGION_ROBUST_SUMS, VOLUME_ROBUST_SUMS);
 //   launch  the set-up at the iterate c.U in place of the operator's system: b into c.R, the coefficient planes, the parts of b . b into
@@ -448,16 +450,18 @@ struct RobustRounds {
     const int max_rounds;
     const float round_tol;
     const int bits, nsums;
-    RobustRounds(const RobustTerm &grad_, const RobustTerm &data_, const RobustTerm &time_, int max_rounds_, float round_tol_, int kind, int nsums_)
+    RobustRounds(const RobustTerm &grad_, const RobustTerm &data_, const RobustTerm &time_, int max_rounds_, float round_tol_, int kind, int nsums_,
+                 int launch_bits = 0)
         : grad(grad_), data(data_), time(time_), max_rounds(max_rounds_), round_tol(round_tol_),
-          bits(((kind & SC_ROBUST_ISOTROPIC) ? ROBUST_ISO : 0) | ((kind & SC_ROBUST_JOINT_CHANNELS) ? ROBUST_JOINT : 0)), nsums(nsums_) {}
+          bits(((kind & SC_ROBUST_ISOTROPIC) ? ROBUST_ISO : 0) | ((kind & SC_ROBUST_JOINT_CHANNELS) ? ROBUST_JOINT : 0) | launch_bits), nsums(nsums_) {}
     RobustRounds(const sc_robust_params &p, int nsums_)
         : RobustRounds(robust_term(p.p_grad, p.eps_grad), robust_term(p.p_data, p.eps_data), robust_term(2.f, 0.f), p.max_rounds, p.round_tol, p.kind,
                        nsums_) {}
     virtual ~RobustRounds() = default;
     bool quadratic() const { return grad.mode == 0 && data.mode == 0 && time.mode == 0; }      // every exponent is 2: no round runs
-    // the coupling that changes anything: none with p_grad = 2 (every form is sum c t^2), no joint form of one channel
-    int coupling(int C) const { return grad.mode == 0 ? 0 : C == 1 ? bits & ~ROBUST_JOINT : bits; }
+    // the coupling that changes anything: none with p_grad = 2 (every form is sum c t^2), no joint form of one channel (the volume
+    // call has a rule of its own: its temporal penalty counts too)
+    virtual int coupling(int C) const { return grad.mode == 0 ? 0 : C == 1 ? bits & ~ROBUST_JOINT : bits; }
     virtual int launch(PcgChunk &c, int coupling, double *esum) = 0;
     virtual void take(const double *totals) = 0;
     // One round's system, its means and the energy of the chunk's iterate per unit of the round rule -- a plane, or a job where the
@@ -486,6 +490,32 @@ constexpr int VOLUME_ROBUST_SUMS = 5;
 void launch_volume_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                 const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                                 float *F, float *Dg, double *bb, double *sums, hipStream_t s);
+// the coupled volume call's two launches (sc_volume_coupled.hip; coupling: ROBUST_ISO | ROBUST_TIME | ROBUST_JOINT, not 0 and effective):
+// k_volume_robust_rho writes rho of every owner's magnitudes to the rho planes and esum as launch_robust_coupled (the gradient-and-time
+// energy's parts; under ROBUST_JOINT on the volume's channel-0 plane only), k_volume_robust_setup_rho is launch_volume_robust_setup with
+// s read from them, field 4 of its sums the data term's energy alone.  The rho planes: per unit (a volume under ROBUST_JOINT, else a
+// work plane) `unit` floats, its components at ox, oy, ot -- one under ROBUST_ISO | ROBUST_TIME, xy | t under ROBUST_ISO, else x | y |
+// t; a component whose penalty has exponent 2 is not stored -- of T frames `fstride` floats apart, rows of rw = x0 + nx floats.
+struct VolumeRhoGeo { int rw; long long fstride, ox, oy, ot, unit; };
+inline VolumeRhoGeo volume_rho_geo(const PcgGeo &wg, const VolumeGeo &vg, const RobustTerm &grad, const RobustTerm &time, int coupling)
+{
+    VolumeRhoGeo r{ wg.x0 + wg.nx, ((long long)(wg.x0 + wg.nx) * (wg.y0 + vg.ny) + 63) / 64 * 64, 0, 0, 0, 0 };
+    const long long comp = r.fstride * vg.T;
+    long long n = 0;
+    if (grad.mode != 0) {
+        r.ox = n; n += comp;
+        r.oy = (coupling & ROBUST_ISO) ? r.ox : n;
+        if (!(coupling & ROBUST_ISO)) n += comp;
+    }
+    if (coupling & ROBUST_TIME) r.ot = r.ox;
+    else if (time.mode != 0) { r.ot = n; n += comp; }
+    r.unit = n;
+    return r;
+}
+inline size_t volume_rho_floats(const VolumeRhoGeo &rg, int C, int m, int coupling) { return (size_t)rg.unit * ((coupling & ROBUST_JOINT) ? m : C * m); }
+void launch_volume_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                  const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, int coupling, const float *U, float *Rho,
+                                  float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
 // k_wls_setup with s = c rho_p(link residual of U), w' = w rho_q(U - d) (c = sx, sy; NULL for every job: 1): R = b, E, S, Dg as
 // launch_wls_setup in its guidance form, bb = the parts of b . b, sums[(plane * PCG_PARTS + i) * ROBUST_SUMS + ..] = the part's sum of
 // w' | the sum of its live links s, each counted once as launch_wls_stats counts them | the energy of U

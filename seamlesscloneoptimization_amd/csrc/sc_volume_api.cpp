@@ -23,6 +23,9 @@
 // is sc_hip_volume_wls's chunk with default precond_*; the chunk, its rounds and the round itself are sc_robust_api.cpp's (robust_chunk,
 // RobustRounds::reweigh), for which VolumeRobustOperator provides the launch (k_volume_robust_setup, sc_volume_robust.hip) and takes
 // the round's sums in place of the statistics'.
+// sc_hip_volume_coupled (its own three entries, last): the robust volume call with a coupling -- SC_VOLUME_COUPLE_SPACE, _TIME, _CHANNELS
+// -- beside the parameters, which the operator takes as launch words (ROBUST_ISO, ROBUST_TIME, ROBUST_JOINT); a round under an effective
+// coupling is two launches (k_volume_robust_rho, k_volume_robust_setup_rho, sc_volume_coupled.hip) with PcgState::rho between them.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -236,26 +239,54 @@ int volume_robust_validate(const sc_volume_robust_params *p, const sc_poisson_la
     return SC_OK;
 }
 
-// Sums: w' | spatial links | temporal links | UNKNOWN - KNOWN | energy.  (No coupled form: the check refuses the bits.)
+// the coupled volume call's parameters: the robust volume call's and the coupling as the launches' words
+struct VolumeCoupledParams { const sc_volume_robust_params *p; int bits; };
+int coupling_words(int coupling)
+{
+    return ((coupling & SC_VOLUME_COUPLE_SPACE) ? ROBUST_ISO : 0) | ((coupling & SC_VOLUME_COUPLE_TIME) ? ROBUST_TIME : 0) |
+           ((coupling & SC_VOLUME_COUPLE_CHANNELS) ? ROBUST_JOINT : 0);
+}
+
+// Sums: w' | spatial links | temporal links | UNKNOWN - KNOWN | energy.  (kind carries no coupling bits: the check refuses them; the
+// coupled call's come beside the parameters.)
 struct VolumeRobustOperator final : VolumeOperator, RobustRounds {
     const bool base_links, base_tlinks;
     VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, bool links_, bool tlinks_)
-        : VolumeRobustOperator(I_, p, wls_params_of(p), links_, tlinks_) {}
-    VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_)
-        : VolumeOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS, true),
+        : VolumeRobustOperator(I_, p, wls_params_of(p), links_, tlinks_, 0) {}
+    VolumeRobustOperator(Instance *I_, const VolumeCoupledParams *c, bool links_, bool tlinks_)
+        : VolumeRobustOperator(I_, c->p, wls_params_of(c->p), links_, tlinks_, c->bits) {}
+    VolumeRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_, int words)
+        : VolumeOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS + (words ? 1 : 0), true),
           RobustRounds(robust_term(p->p_grad, p->eps_grad), robust_term(p->p_data, p->eps_data), robust_term(p->p_time, p->eps_time), p->max_rounds,
-                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS),
+                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS, words),
           base_links(links_), base_tlinks(tlinks_) {}
     RobustRounds *rounds() override { return this; }
+    // the coupling that changes anything: SPACE and TIME not with p_grad = 2 (TIME: p_time = p_grad), CHANNELS not on one channel and
+    // not with p_grad = p_time = 2
+    int coupling(int C) const override
+    {
+        int b = bits;
+        if (grad.mode == 0) b &= ~(ROBUST_ISO | ROBUST_TIME);
+        if (C == 1 || (grad.mode == 0 && time.mode == 0)) b &= ~ROBUST_JOINT;
+        return b;
+    }
     void begin() override
     {
         VolumeOperator::begin();
         links = base_links;          // round 0 of a new chunk: the caller's arrays again
         tlinks = base_tlinks;
     }
-    int launch(PcgChunk &c, int, double *) override
+    int launch(PcgChunk &c, int cpl, double *esum) override
     {
         PcgState &S = *I->pcg;
+        if (cpl) {
+            const VolumeGeo vg = geo(c.wg);
+            const int rc = ensure(I, S.rho, sizeof(float) * volume_rho_floats(volume_rho_geo(c.wg, vg, grad, time, cpl), c.g.C, c.mv, cpl), false);
+            if (rc) return rc;
+            launch_volume_robust_coupled(c.g, c.wg, vg, dj.data(), ds.data(), c.mv, grad, time, data, cpl, c.U, (float *)S.rho.p, c.R, (float *)S.e.p,
+                                         (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, esum, I->stream);
+            return SC_OK;
+        }
         launch_volume_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, c.U, c.R, (float *)S.e.p, (float *)S.s.p,
                                    (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
         return SC_OK;
@@ -269,6 +300,21 @@ PcgCall volume_robust_call(int kind, const sc_volume_robust_params *p)
 }
 
 constexpr const char *ROBUST_METHOD_WHY = "a robust volume solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
+
+// the coupled call's check: the robust volume call's (coupling bits in kind included), then the coupling's own two refusals
+int volume_coupled_validate(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    const int rc = volume_robust_validate(p, l, why);
+    if (rc) return rc;
+    const char *own = (coupling & ~(SC_VOLUME_COUPLE_SPACE | SC_VOLUME_COUPLE_TIME | SC_VOLUME_COUPLE_CHANNELS)) ? "coupling has bits that are not SC_VOLUME_COUPLE_*"
+                    : ((coupling & SC_VOLUME_COUPLE_TIME) && !(coupling & SC_VOLUME_COUPLE_SPACE)) ? "SC_VOLUME_COUPLE_TIME comes with SC_VOLUME_COUPLE_SPACE"
+                    : ((coupling & SC_VOLUME_COUPLE_TIME) && (p->p_time != p->p_grad || p->eps_time != p->eps_grad))
+                        ? "SC_VOLUME_COUPLE_TIME is one penalty: p_time must equal p_grad and eps_time eps_grad" : nullptr;
+    if (own) { *why = own; return SC_ERR_BAD_ARG; }
+    return SC_OK;
+}
 
 } // namespace
 
@@ -356,6 +402,41 @@ int sc_hip_volume_robust(void *inst, const sc_volume_robust_params *p, const sc_
     if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
     const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
     VolumeRobustOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    return pcg_host_call(I, volume_robust_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op, robust_chunk);
+}
+
+int sc_hip_volume_coupled_check(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l)
+{
+    return volume_coupled_validate(p, coupling, l, nullptr);
+}
+
+int sc_hip_volume_coupled_device(void *inst, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, sc_volume_robust_job *jobs, int n,
+                                 bool bSync)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, [coupling](const sc_volume_robust_params *q, const sc_poisson_layout *m, const char **why) {
+        return volume_coupled_validate(q, coupling, m, why); }, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    const VolumeCoupledParams cp{ p, coupling_words(coupling) };
+    return volume_device_call<VolumeRobustOperator>(I, volume_robust_call(kind, p), &cp, l, jobs, n, bSync, [](const sc_volume_robust_job &j) {
+        return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, nullptr }; }, robust_chunk);
+}
+
+int sc_hip_volume_coupled(void *inst, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const float *gx, const float *gy,
+                          const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                          const float *smooth_t, const float *boundary, float *out)
+{
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, [coupling](const sc_volume_robust_params *q, const sc_poisson_layout *m, const char **why) {
+        return volume_coupled_validate(q, coupling, m, why); }, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    const VolumeCoupledParams cp{ p, coupling_words(coupling) };
+    VolumeRobustOperator op(I, &cp, links, tlinks);
     FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
     a.gt = gt;
     a.smooth_t = smooth_t;

@@ -1010,7 +1010,8 @@ def make_loop(frames, lam=1e-2, tau=1.0, gpu_id=0, **solver):
 
 def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0, loop=False,
                         p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None, periodic="",
-                        max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, **solver):
+                        max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False, spacetime=False, joint_channels=False,
+                        **solver):
     """volume_wls_solve with robust_solve's penalties in place of the squares: per channel it minimises over the UNKNOWN pixels
         sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy) + sum tau smooth_t phi_r(u_{t+1} - u_t - gt),
         phi_e(t) = (2 / e) (t^2 + eps^2)^(e/2),      0 < p, r = p_time, q <= 2,
@@ -1018,27 +1019,60 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     15) WLS volume solves whose links and weights come from the previous iterate, each started from it.  state, the link arrays, gt,
     loop and the borders as volume_wls_solve's; gx and gy are required (there is no laplacian form), weight None: no data term.
     round_tol (default 1e-4): stop when no channel's energy fell by more than that fraction in the last round; negative: run every
-    round.  Returns a NEW array."""
+    round.  isotropic: one penalty per pixel over its x- and y-link (per frame the isotropic total variation); spacetime: ... and over
+    its forward temporal link too (the space-time total variation; implies isotropic and needs p_time == p and eps_time == eps_grad);
+    joint_channels: every penalty over the channels of the volume (the vectorial total variation).  With any of the three the call is
+    sc_hip_volume_coupled's.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
+    if spacetime and (p_time != p or eps_time != eps_grad):
+        raise ValueError("spacetime=True is one penalty over space and time: p_time must equal p and eps_time eps_grad")
+    args = dict(tau=tau, loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_time=p_time,
+                eps_time=eps_time, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0, round_tol=round_tol or 0.0, tol=tol or 0.0,
+                max_iters=max_iters or 0)
     with _instance(gpu_id, solver) as inst:
-        return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, tau=tau, loop=bool(loop), neumann=neumann,
-                                  free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_time=p_time, eps_time=eps_time, p_data=q,
-                                  eps_data=eps_data, max_rounds=max_rounds or 0, round_tol=round_tol or 0.0, tol=tol or 0.0, max_iters=max_iters or 0)
+        if coupling:
+            return inst.volume_coupled(coupling, gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
+        return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
 
 
-def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False,
+                     spacetime=False, joint_channels=False, **solver):
     """Total-variation denoising of a float32 video (T x H x W or T x H x W x C) that does not flicker: the video u that minimises
         lam sum phi_q(u - frames) + sum phi_p(forward differences of u within a frame) + tau sum phi_r(u_{t+1} - u_t),      r = p_time,
     under reflecting borders -- volume_robust_solve with zero guidance, every state unknown, data = frames and weight = lam.  p = 1 is
     the anisotropic total variation in space; p_time = 1 lets the video jump at cuts and moving edges, p_time = 2 smooths along time.
-    eps (in the frames' units) rounds all three penalties off near 0.  loop: the last frame is joined to the first.  Returns a NEW array."""
+    eps (in the frames' units) rounds all three penalties off near 0.  loop: the last frame is joined to the first.  isotropic,
+    spacetime, joint_channels: volume_robust_solve's coupled forms -- the total variation of the gradient's magnitude per frame (discs
+    stay discs), of the space-time gradient's (a moving edge is one surface; needs p_time == p), and over all channels (no colour
+    fringes).  Returns a NEW array."""
     frames = _video_of("frames", frames)
     if not (np.isfinite(lam) and lam > 0):
         raise ValueError("lam must be finite and > 0")
     zero = np.zeros_like(frames)
     return volume_robust_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), weight=np.full(frames.shape[:3], lam, np.float32), tau=tau,
                                loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True, max_rounds=max_rounds,
-                               round_tol=round_tol, gpu_id=gpu_id, **solver)
+                               round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime, joint_channels=joint_channels, **solver)
+
+
+def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=False, joint_channels=False, tau=1.0, loop=False, p_time=None,
+                     max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """Total-variation fill of a float32 video (T x H x W or T x H x W x C), the volume partner of tv_inpaint: the pixels where hole
+    (T x H x W, anything truthy: a hole per frame, which may move) is set are replaced by the u that minimises
+        sum phi_p(forward differences of u within a frame) + tau sum phi_r(u_{t+1} - u_t),      r = p_time (default: p),
+    over the links that touch the hole, every pixel outside it held -- volume_robust_solve with zero guidance, every pixel outside the
+    hole known and reflecting borders.  isotropic (the default), spacetime, joint_channels: its coupled forms.  eps (in the frames'
+    units) rounds the penalties off near 0.  loop: the last frame is joined to the first.  Returns a NEW array; pixels outside the hole
+    keep their bits."""
+    frames = _video_of("frames", frames)
+    h = _video_masks("hole", hole, frames)
+    if h.all():
+        raise ValueError("the hole covers the whole video: nothing to fill it from")
+    state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    zero = np.zeros_like(frames)
+    return volume_robust_solve(zero, zero, frames, state, tau=tau, loop=loop, p=p, p_time=p if p_time is None else p_time, eps_grad=eps, eps_time=eps,
+                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime,
+                               joint_channels=joint_channels, **solver)
 
 
 def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time=1.0, eps=1e-3, anchor=1e-3, loop=False, tau=1.0, max_rounds=None,
