@@ -76,6 +76,26 @@ SC_API int sc_hip_build_rhs(void *instance,
                      const uint8_t *mask, int mask_cols, int mask_rows, int mask_step,
                      int centerX, int centerY, int geo[6], float *B_out, float *lap_out, size_t plane_capacity);
 
+/* The front end of n device-resident clones WHERE THE CALLER'S BYTES LIE: face / body / mask of every job are device pointers with the
+ * caller's own base and step, handed to the launches as the clone calls hand them.  Runs the scan, the erode and the pre-process and
+ * nothing else -- no solve, no output launch, nothing is written to body -- through the functions the clone calls run:
+ *   form 0  solo: the scan, the erode (grey: the minimum filter), the pre-process without a scan, one member after the other
+ *   form 1  predicted: member i is launched on the rectangle guess[4 i ..] = {x0, x1, y0, y1}; no erode launch, the scan rides in the
+ *           pre-process launch as extra workgroup rows and its tiles erode the mask themselves.  M, B and lap belong to the guessed box,
+ *           the rectangle to the true one
+ *   form 2  group: the scans, the erodes and the tiles of all members as one launch each; every member has the fields' size
+ *   form 3  size class: as form 2, the fields take the largest W and H and every member carries its own
+ * storage: bit 0 the right-hand side as float16, bit 1 the initial field as float16, bit 2 no initial field stored (groups; B stays
+ * untouched); SC_ERR_BAD_ARG for a word no launcher instantiates (0, 1, 3; 7 for groups).  The instance's clone mode and
+ * SC_FLAG_OPENCV_GREY_MASK (form 0, storage 0) apply as in a run.
+ * Per member i: rect_dev / rect_host [4 i ..] the raw rectangle the scan left in device memory / in the pinned mailbox, geo[6 i ..] =
+ * {x0, y0, W, H, ltx, lty} (zeros where jobs[i].rc says the rectangle gives no usable ROI -- the rectangle is still returned), and at
+ * member strides of `capacity` pixels: M_out the eroded mask, dense W x H bytes, B_out / lap_out dense [3][H][W] float32 (float16
+ * expanded).  M_out, B_out and lap_out may be NULL; all three NULL in forms 0, 2 and 3: the scan alone (a group's masks may then differ
+ * in size). */
+SC_API int sc_hip_front_end_device(void *instance, sc_batch_job *jobs, int n, int form, int storage, const int *guess, int *rect_dev,
+                                   int *rect_host, int *geo, uint8_t *M_out, float *B_out, float *lap_out, size_t capacity);
+
 /* whole-image edit (sc_hip_edit) up to its right-hand side: M_out receives the eroded mask (dense cols * rows bytes), lap_out the
  * un-folded right-hand side, planar [3][rows][cols] float32 (0 on the frame).  Either may be NULL. */
 SC_API int sc_hip_edit_rhs(void *instance, const sc_edit_params *p, const uint8_t *src, int cols, int rows, int src_step,

@@ -446,6 +446,8 @@ def load():
     L.sc_hip_mask_stage.restype = C.c_int
     L.sc_hip_build_rhs.argtypes = [C.c_void_p] + _IMG * 3 + [C.c_int, C.c_int, i32p, f32p, f32p, C.c_size_t]
     L.sc_hip_build_rhs.restype = C.c_int
+    L.sc_hip_front_end_device.argtypes = [C.c_void_p, C.POINTER(BatchJob), C.c_int, C.c_int, C.c_int, i32p, i32p, i32p, i32p, u8p, f32p, f32p, C.c_size_t]
+    L.sc_hip_front_end_device.restype = C.c_int
     L.sc_hip_field_load.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, f32p]
     L.sc_hip_field_load.restype = C.c_int
     L.sc_hip_field_sweep.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]
@@ -1766,11 +1768,11 @@ class Instance:
         self._check(self.L.sc_hip_memcpy_d2d_async(self.h, dst, src, nbytes))
 
     def run_device(self, d_face, fshape, d_body, bshape, d_mask, mshape, cx, cy, sync=True,
-                   allow_not_converged=False):
-        """shapes are (rows, cols); rows are dense (step = cols * channels)."""
-        rc = self.L.sc_hip_run_device(self.h, d_face, fshape[1], fshape[0], 3 * fshape[1],
-                                      d_body, bshape[1], bshape[0], 3 * bshape[1],
-                                      d_mask, mshape[1], mshape[0], mshape[1], int(cx), int(cy), bool(sync))
+                   allow_not_converged=False, face_step=None, body_step=None, mask_step=None):
+        """shapes are (rows, cols); rows are dense (step = cols * channels) unless a step is given."""
+        rc = self.L.sc_hip_run_device(self.h, d_face, fshape[1], fshape[0], face_step or 3 * fshape[1],
+                                      d_body, bshape[1], bshape[0], body_step or 3 * bshape[1],
+                                      d_mask, mshape[1], mshape[0], mask_step or mshape[1], int(cx), int(cy), bool(sync))
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
 
     def run_device_batch(self, jobs, sync=True):
@@ -1801,6 +1803,34 @@ class Instance:
                                             B.ctypes.data_as(f32p), lap.ctypes.data_as(f32p), cap))
         W, H = int(geo[2]), int(geo[3])
         return geo, B[:3 * W * H].reshape(3, H, W).copy(), lap[:3 * W * H].reshape(3, H, W).copy()
+
+    def front_end_device(self, jobs, form, storage=0, guess=None, fields=True, allow=()):
+        """sc_hip_front_end_device on a BatchJob array of device-resident images at the caller's bases and steps.  Returns one dict per
+        member: rect_dev, rect_host (the raw rectangle, device copy and pinned mailbox), rc, geo, and with `fields` M, B (None when
+        storage bit 2 is set), lap of the ROI the launches ran on.  allow: codes of the call that do not raise."""
+        n = len(jobs)
+        cap = max(int(j.mask_cols) for j in jobs) * max(int(j.mask_rows) for j in jobs) if fields else 0
+        rd, rh, geo = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32), np.zeros((n, 6), np.int32)
+        M = np.zeros((n, cap), np.uint8) if fields else None
+        B = np.zeros((n, 3 * cap), np.float32) if fields else None
+        lap = np.zeros((n, 3 * cap), np.float32) if fields else None
+        g = None if guess is None else np.ascontiguousarray(guess, np.int32).reshape(n, 4)
+        rc = self.L.sc_hip_front_end_device(self.h, jobs, n, int(form), int(storage), None if g is None else g.ctypes.data_as(i32p),
+                                            rd.ctypes.data_as(i32p), rh.ctypes.data_as(i32p), geo.ctypes.data_as(i32p),
+                                            M.ctypes.data_as(u8p) if fields else None, B.ctypes.data_as(f32p) if fields else None,
+                                            lap.ctypes.data_as(f32p) if fields else None, cap)
+        self._check(rc, allow=allow)
+        out = []
+        for i in range(n):
+            W, H = int(geo[i, 2]), int(geo[i, 3])
+            d = dict(rect_dev=tuple(int(v) for v in rd[i]), rect_host=tuple(int(v) for v in rh[i]), rc=int(jobs[i].rc), geo=geo[i].copy(), M=None, B=None, lap=None)
+            if fields and rc == SC_OK and W > 0 and jobs[i].rc == SC_OK:
+                d["M"] = M[i, :W * H].reshape(H, W).copy()
+                d["lap"] = lap[i, :3 * W * H].reshape(3, H, W).copy()
+                if not storage & 4:
+                    d["B"] = B[i, :3 * W * H].reshape(3, H, W).copy()
+            out.append(d)
+        return out
 
     def field_load(self, U, lap):
         U = np.ascontiguousarray(U, np.float32)

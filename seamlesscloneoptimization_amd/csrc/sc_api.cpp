@@ -67,7 +67,7 @@ static int tmark(Instance *I, int k, bool empty_stage = false)
 
 // With `predicted` the same launch also erodes that ROI (the whole mask stage in one kernel: the erode of a predicted box
 // does not depend on the box being computed); device_clone then skips its own erode launch.
-static int bbox_enqueue(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, const Geo *predicted = nullptr)
+int bbox_enqueue(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, const Geo *predicted)
 {
     // The scan's workgroups leave their extrema as parts, the last one to finish folds them into the rectangle (seeded like the
     // reference's, seamlessClone_imp.cpp:1006) and stores it in device memory AND in the pinned mailbox h_rect[4..7]: no seed
@@ -167,6 +167,17 @@ void erode_mask(Instance *I, const uint8_t *d_mask, int ms, int mr, const Geo &g
     else launch_mask_erode3(d_mask, ms, mr, g, (uint8_t *)I->d_M.p, I->mpitch, I->stream);
 }
 
+bool launch_clone_preprocess(Instance *I, const uint8_t *body_org, int bstep, const uint8_t *face_org, int fstep)
+{
+    const bool grey = (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0;
+    if (I->scan_pending) I->pending_scan.M_out = (uint8_t *)I->d_M.p;      // the launch's tiles erode the mask themselves and leave it here
+    const bool had_scan = I->scan_pending;
+    launch_preprocess(body_org, bstep, face_org, fstep, (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F,
+                      I->stream, I->f_half, I->u_half, grey, I->scan_pending ? &I->pending_scan : nullptr, I->clone_mode);
+    I->scan_pending = false;
+    return had_scan;
+}
+
 // erode -> pre-process -> solve -> post-process on device-resident ROI origins
 // out_org / ostep: where the output bytes go (ROI origin, row step): the destination itself for device-resident images; the
 // host path hands a compact buffer of its own so that what comes back across PCIe is the ROI and nothing else
@@ -186,7 +197,6 @@ static int device_clone(Instance *I, const uint8_t *d_mask, int ms, int mr, cons
     if ((rc = ensure(I, I->d_M, (size_t)I->mpitch * g.H, false))) return rc;
     if ((rc = setup_fields(I, g.W, g.H, 3))) return rc;
     const bool eroded = I->erode_done;
-    const bool grey = (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0;
     if (!eroded) erode_mask(I, d_mask, ms, mr, g);
     I->erode_done = false;
     if ((rc = tmark(I, 4, eroded))) return rc;
@@ -195,11 +205,7 @@ static int device_clone(Instance *I, const uint8_t *d_mask, int ms, int mr, cons
     for (int pass = 0; pass < passes; ++pass) {
         const bool last = pass == passes - 1;
         solve_rc = solve_step(I, to, [&]() -> int {
-            if (I->scan_pending) I->pending_scan.M_out = (uint8_t *)I->d_M.p;      // the launch's tiles erode the mask themselves and leave it here
-            const bool had_scan = I->scan_pending;
-            launch_preprocess(body_org, bstep, face_org, fstep, (const uint8_t *)I->d_M.p, I->mpitch, I->U0, I->U1, I->F,
-                              I->stream, I->f_half, I->u_half, grey, I->scan_pending ? &I->pending_scan : nullptr, I->clone_mode);
-            I->scan_pending = false;
+            const bool had_scan = launch_clone_preprocess(I, body_org, bstep, face_org, fstep);
             if (last && (rc = tmark(I, 5))) return rc;
             if (had_scan) {
                 // the host compares the scan's rectangle (pinned mailbox) with its guess once THIS point of the stream has passed: mark 5
@@ -787,8 +793,7 @@ int sc_hip_run_device(void *p, const uint8_t *d_face, int fc, int fr, int fs, ui
     auto attempt = [&](const Geo &g) -> int {
         int r = tmark(I, 3, true);
         if (r) return r;
-        r = device_clone(I, d_mask, ms, mr, d_face + (size_t)g.y0 * fs + 3 * g.x0, fs,
-                             d_body + (size_t)g.lty * bs + 3 * g.ltx, bs, g, passes);
+        r = device_clone(I, d_mask, ms, mr, roi_at(d_face, fs, g.x0, g.y0), fs, roi_at(d_body, bs, g.ltx, g.lty), bs, g, passes);
         if (r != SC_OK && r != SC_ERR_NOT_CONVERGED) return r;
         SC_HIP(I, hipEventRecord(I->ev_k1, I->stream));
         return r;

@@ -28,6 +28,42 @@ FrameSpans frame_spans(size_t step, int rows, int ltx, int lty, int W, int H)
     return f;
 }
 
+std::vector<MaskJob> group_scan_jobs(const sc_batch_job *jobs, int n, const std::vector<char> &usable, int *d_r, int *h_out)
+{
+    std::vector<MaskJob> mj;
+    mj.reserve(n);
+    for (int i = 0; i < n; ++i) {
+        if (!usable[i]) continue;
+        MaskJob m{};
+        m.mask = jobs[i].mask; m.mw = jobs[i].mask_cols; m.mh = jobs[i].mask_rows; m.mstep = jobs[i].mask_step;
+        m.rect = d_r + GROUP_RS * i; m.rect_host = h_out + GROUP_RS * i;
+        mj.push_back(m);
+    }
+    return mj;
+}
+
+void group_member_jobs(Instance *I, const sc_batch_job *jobs, const std::vector<int> &idx, const std::vector<Geo> &geo, const int *guess, int *d_r,
+                       bool size_class, const std::vector<char> &frame, size_t mplane, std::vector<MaskJob> &mj, std::vector<ImageJob> &ij)
+{
+    const int n = (int)idx.size();
+    mj.assign(n, MaskJob{});
+    ij.assign(n, ImageJob{});
+    for (int k = 0; k < n; ++k) {
+        const int i = idx[k];
+        const sc_batch_job &j = jobs[i];
+        mj[k].mask = j.mask; mj[k].mw = j.mask_cols; mj[k].mh = j.mask_rows; mj[k].mstep = j.mask_step;
+        mj[k].rect = d_r + GROUP_RS * i;
+        mj[k].g = geo[i]; mj[k].M = (uint8_t *)I->d_M.p + mplane * k; mj[k].mpitch = I->mpitch;
+        ij[k].face_org = roi_at(j.face, j.face_step, geo[i].x0, geo[i].y0); ij[k].fstep = j.face_step;
+        ij[k].body_org = roi_at(j.body, j.body_step, geo[i].ltx, geo[i].lty);
+        ij[k].body_src = frame[i] ? roi_at(j.body_restore, j.body_step, geo[i].ltx, geo[i].lty) : ij[k].body_org; ij[k].bstep = j.body_step;
+        ij[k].M = (const uint8_t *)I->d_M.p + mplane * k;
+        ij[k].d_rect = guess ? d_r + GROUP_RS * i : nullptr;
+        if (guess) { ij[k].rx0 = guess[4 * i]; ij[k].rx1 = guess[4 * i + 1]; ij[k].ry0 = guess[4 * i + 2]; ij[k].ry1 = guess[4 * i + 3]; }
+        if (size_class) { ij[k].W = geo[i].W; ij[k].H = geo[i].H; }
+    }
+}
+
 } // namespace sc
 
 // ---- n device-resident clones through ONE set of launches ------------------------------------------------------
@@ -41,8 +77,6 @@ FrameSpans frame_spans(size_t step, int rows, int ltx, int lty, int W, int H)
 // differs (a batch of real clones has a mask box per face / frame).  A failing member, the reference's warm-up option and
 // OpenCV's grey-mask semantics still run one after the other through sc_hip_run_device.
 namespace {
-
-constexpr int GROUP_RS = 32;      // ints between the rectangles of a group's scans: one 128-byte line each (eight rectangles in one line: 162 us for the group's scan instead of 20)
 
 struct RagScope {      // leaves the size-class mode on every way out
     Instance *I;
@@ -76,23 +110,9 @@ int run_group_members(Instance *I, sc_batch_job *jobs, const std::vector<int> &i
     if ((rc = setup_fields(I, g0.W, g0.H, 3 * n))) return rc;
     RagScope scope{ I };
     CallScope call{ I };
-    std::vector<MaskJob> mj(n);
-    std::vector<ImageJob> ij(n);
-    for (int k = 0; k < n; ++k) {
-        const int i = idx[k];
-        const sc_batch_job &j = jobs[i];
-        mj[k] = MaskJob{};
-        mj[k].mask = j.mask; mj[k].mw = j.mask_cols; mj[k].mh = j.mask_rows; mj[k].mstep = j.mask_step;
-        mj[k].rect = d_r + GROUP_RS * i;
-        mj[k].g = geo[i]; mj[k].M = (uint8_t *)I->d_M.p + mplane * k; mj[k].mpitch = I->mpitch;
-        ij[k].face_org = j.face + (size_t)geo[i].y0 * j.face_step + 3 * geo[i].x0; ij[k].fstep = j.face_step;
-        const size_t roi = (size_t)geo[i].lty * j.body_step + 3 * geo[i].ltx;
-        ij[k].body_org = j.body + roi; ij[k].body_src = frame[i] ? j.body_restore + roi : j.body + roi; ij[k].bstep = j.body_step;
-        ij[k].M = (const uint8_t *)I->d_M.p + mplane * k;
-        ij[k].d_rect = guess ? d_r + GROUP_RS * i : nullptr;
-        if (guess) { ij[k].rx0 = guess[4 * i]; ij[k].rx1 = guess[4 * i + 1]; ij[k].ry0 = guess[4 * i + 2]; ij[k].ry1 = guess[4 * i + 3]; }
-        if (plans) { ij[k].W = geo[i].W; ij[k].H = geo[i].H; }
-    }
+    std::vector<MaskJob> mj;
+    std::vector<ImageJob> ij;
+    group_member_jobs(I, jobs, idx, geo, guess, d_r, plans != nullptr, frame, mplane, mj, ij);
     // (a size class: the members' table goes up FIRST -- 9 us of host time, a 3-us copy in front of the erode -- so that the other
     //  streams' builds, which wait for it, run beside the erode and the pre-process)
     if (plans && (rc = rag_begin_table(I, *plans))) return rc;
@@ -215,15 +235,7 @@ int sc_hip_run_device_batch(void *p, sc_batch_job *jobs, int n)
     // (the fold launch writes every usable member's rectangle to d_r AND into the pinned h_out: no seeds to upload, nothing to read back)
     int *h_out = (int *)I->h_rects.p + RS * n, *d_r = (int *)I->d_rects.p;
     {
-        std::vector<MaskJob> mj;
-        mj.reserve(n);
-        for (int i = 0; i < n; ++i) {
-            if (!usable[i]) continue;
-            MaskJob m{};
-            m.mask = jobs[i].mask; m.mw = jobs[i].mask_cols; m.mh = jobs[i].mask_rows; m.mstep = jobs[i].mask_step;
-            m.rect = d_r + RS * i; m.rect_host = h_out + RS * i;
-            mj.push_back(m);
-        }
+        std::vector<MaskJob> mj = group_scan_jobs(jobs, n, usable, d_r, h_out);
         if ((rc = ensure(I, I->d_bbox_parts, sizeof(int) * mask_bbox_group_parts(mj.data(), (int)mj.size())))) {
             restore();
             return rc;

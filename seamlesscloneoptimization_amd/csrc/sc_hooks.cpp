@@ -98,6 +98,47 @@ static FusedStep default_step(int kind, bool q16, bool composed)
     }
 }
 
+// ---- the front end where the caller's bytes lie (sc_hip_front_end_device)
+namespace {
+
+struct FrontOut { uint8_t *M; float *B, *lap; size_t cap; };
+
+// W x H of plane c of `src` (the fields' pitch and plane size) into plane c of member k's dense [3][H][W] block of `out`
+int front_planes(Instance *I, const Field &f, const float *src, int k, int W, int H, float *out, size_t cap)
+{
+    int rc;
+    for (int c = 0; c < 3; ++c)
+        if ((rc = download_rows(I, I->h_out, (uint8_t *)(out + 3 * cap * k + (size_t)c * W * H), (size_t)W * sizeof(float),
+                                src + (size_t)(3 * k + c) * f.plane, (size_t)f.pitch * sizeof(float), (size_t)W * sizeof(float), H))) return rc;
+    return SC_OK;
+}
+
+// what the launches left for members 0 .. n-1 (first: the caller's index of member 0) of the instance's fields and d_M (mplane bytes per
+// member), to the host: float16 fields are expanded through U1, which no front-end launch writes
+int front_download(Instance *I, int first, int n, const Geo *geo, size_t mplane, bool f_half, bool u_half, bool no_u0, const FrontOut &o)
+{
+    int rc;
+    const size_t elems = I->F.plane * (size_t)I->F.C;
+    if (o.M)
+        for (int k = 0; k < n; ++k)
+            if ((rc = download_rows(I, I->h_out, o.M + o.cap * (first + k), geo[k].W, (const uint8_t *)I->d_M.p + mplane * k, I->mpitch, geo[k].W, geo[k].H))) return rc;
+    if (o.lap) {
+        if (f_half) { launch_half_to_float(I->F.p, I->U1.p, elems, I->stream); SC_HIP(I, hipGetLastError()); }
+        for (int k = 0; k < n; ++k)
+            if ((rc = front_planes(I, I->F, f_half ? I->U1.p : I->F.p, k, geo[k].W, geo[k].H, o.lap + 3 * o.cap * first, o.cap))) return rc;
+    }
+    if (o.B && !no_u0) {
+        if (u_half) { launch_half_to_float(I->U0.p, I->U1.p, elems, I->stream); SC_HIP(I, hipGetLastError()); }
+        for (int k = 0; k < n; ++k)
+            if ((rc = front_planes(I, I->U0, u_half ? I->U1.p : I->U0.p, k, geo[k].W, geo[k].H, o.B + 3 * o.cap * first, o.cap))) return rc;
+    }
+    return SC_OK;
+}
+
+void front_geo(const Geo &g, int *out) { out[0] = g.x0; out[1] = g.y0; out[2] = g.W; out[3] = g.H; out[4] = g.ltx; out[5] = g.lty; }
+
+} // namespace
+
 extern "C" {
 
 int sc_hip_selftest_host(void)
@@ -213,6 +254,113 @@ int sc_hip_build_rhs(void *p, const uint8_t *face, int fc, int fr, int fs, const
     if (B_out && (rc = download_field(I, I->U0, B_out))) return rc;
     if (lap_out && (rc = download_field(I, I->F, lap_out))) return rc;
     SC_HIP(I, hipStreamSynchronize(I->stream));
+    return SC_OK;
+}
+
+int sc_hip_front_end_device(void *p, sc_batch_job *jobs, int n, int form, int storage, const int *guess, int *rect_dev, int *rect_host,
+                                       int *geo_out, uint8_t *M_out, float *B_out, float *lap_out, size_t capacity)
+{
+    Instance *I = get(p);
+    if (!I || !jobs || n < 1 || form < 0 || form > 3 || !rect_dev || !rect_host || !geo_out || (form == 1 && !guess)) return SC_ERR_BAD_ARG;
+    I->err.clear();
+    SC_HIP(I, hipSetDevice(I->gpu));
+    const bool f_half = (storage & 1) != 0, u_half = (storage & 2) != 0, no_u0 = (storage & 4) != 0;
+    const bool grey = (I->opts.flags & SC_FLAG_OPENCV_GREY_MASK) != 0;
+    // the storage words the launchers instantiate: float, float16 right-hand side, both float16, and for a group both without the initial field
+    if (storage != 0 && storage != 1 && storage != 3 && !(storage == 7 && form >= 2)) { I->err = "front_end: no launch form stores the fields that way"; return SC_ERR_BAD_ARG; }
+    if (grey && (form != 0 || storage != 0)) { I->err = "front_end: grey masks run solo on float fields"; return SC_ERR_BAD_ARG; }
+    const bool fields = M_out || B_out || lap_out;
+    const FrontOut out{ M_out, B_out, lap_out, capacity };
+    int rc;
+    for (int i = 0; i < n; ++i) {
+        sc_batch_job &j = jobs[i];
+        if ((rc = validate_images(I, j.face, j.face_cols, j.face_rows, j.face_step, j.body, j.body_cols, j.body_rows, j.body_step, j.mask, j.mask_cols,
+                                  j.mask_rows, j.mask_step))) return rc;
+        j.rc = SC_OK;
+    }
+    std::fill(geo_out, geo_out + 6 * (size_t)n, 0);
+    I->stage_marks = false;
+    I->guard = RectGuard();
+    if (form <= 1) {
+        for (int i = 0; i < n; ++i) {
+            sc_batch_job &j = jobs[i];
+            Geo g{};
+            auto rects = [&]() -> int {      // behind the scan: the rectangle it left, device copy and pinned mailbox
+                SC_HIP(I, hipMemcpyAsync(rect_dev + 4 * i, I->d_rect, 4 * sizeof(int), hipMemcpyDeviceToHost, I->stream));
+                SC_HIP(I, hipStreamSynchronize(I->stream));
+                memcpy(rect_host + 4 * i, I->h_rect + 4, 4 * sizeof(int));
+                return SC_OK;
+            };
+            if (form == 1) {
+                if ((rc = geo_from_rect(I, guess + 4 * i, j.centerX, j.centerY, g)) || (rc = check_roi(I, g, j.body_cols, j.body_rows))) return rc;
+                if ((rc = bbox_enqueue(I, j.mask, j.mask_cols, j.mask_rows, j.mask_step, &g))) return rc;
+            } else {
+                if ((rc = bbox_enqueue(I, j.mask, j.mask_cols, j.mask_rows, j.mask_step))) return rc;
+                if ((rc = rects())) return rc;
+                if (!(j.rc = geo_from_rect(I, I->h_rect + 4, j.centerX, j.centerY, g))) j.rc = check_roi(I, g, j.body_cols, j.body_rows);
+                if (j.rc || !fields) { if (!j.rc) front_geo(g, geo_out + 6 * i); continue; }
+            }
+            if (capacity < (size_t)g.W * g.H) return SC_ERR_BAD_SIZE;
+            I->mpitch = round_up(g.W, 64);
+            if ((rc = ensure(I, I->d_M, (size_t)I->mpitch * g.H, false))) return rc;
+            if ((rc = setup_fields(I, g.W, g.H, 3))) return rc;
+            if (!I->erode_done) erode_mask(I, j.mask, j.mask_step, j.mask_rows, g);
+            I->erode_done = false;
+            I->f_half = f_half; I->u_half = u_half;
+            launch_clone_preprocess(I, roi_at(j.body, j.body_step, g.ltx, g.lty), j.body_step, roi_at(j.face, j.face_step, g.x0, g.y0), j.face_step);
+            SC_HIP(I, hipGetLastError());
+            if (form == 1 && (rc = rects())) return rc;
+            front_geo(g, geo_out + 6 * i);
+            if ((rc = front_download(I, i, 1, &g, 0, f_half, u_half, false, out))) return rc;
+        }
+        SC_HIP(I, hipStreamSynchronize(I->stream));
+        return SC_OK;
+    }
+    // --- a group: the scans of all members, then their erodes and tiles as one launch each
+    if ((rc = ensure(I, I->d_rects, (size_t)n * GROUP_RS * sizeof(int))) || (rc = ensure_pinned(I, I->h_rects, (size_t)n * 2 * GROUP_RS * sizeof(int)))) return rc;
+    int *h_dev = (int *)I->h_rects.p, *h_out = h_dev + GROUP_RS * n, *d_r = (int *)I->d_rects.p;
+    {
+        const std::vector<MaskJob> mj = group_scan_jobs(jobs, n, std::vector<char>(n, 1), d_r, h_out);
+        if ((rc = ensure(I, I->d_bbox_parts, sizeof(int) * mask_bbox_group_parts(mj.data(), n)))) return rc;
+        launch_mask_bbox_group(mj.data(), n, I->stream, (int *)I->d_bbox_parts.p);
+    }
+    SC_HIP(I, hipGetLastError());
+    SC_HIP(I, hipMemcpyAsync(h_dev, d_r, (size_t)n * GROUP_RS * sizeof(int), hipMemcpyDeviceToHost, I->stream));
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    std::vector<Geo> geo(n);
+    int worst = SC_OK;
+    Geo g0{};
+    for (int i = 0; i < n; ++i) {
+        sc_batch_job &j = jobs[i];
+        memcpy(rect_dev + 4 * i, h_dev + GROUP_RS * i, 4 * sizeof(int));
+        memcpy(rect_host + 4 * i, h_out + GROUP_RS * i, 4 * sizeof(int));
+        if (!(j.rc = geo_from_rect(I, h_out + GROUP_RS * i, j.centerX, j.centerY, geo[i]))) j.rc = check_roi(I, geo[i], j.body_cols, j.body_rows);
+        worst = worse(worst, j.rc);
+        if (j.rc) continue;
+        front_geo(geo[i], geo_out + 6 * i);
+        if (form == 2 && i > 0 && (geo[i].W != geo[0].W || geo[i].H != geo[0].H)) worst = worse(worst, SC_ERR_BAD_SIZE);
+        g0.W = std::max(g0.W, geo[i].W); g0.H = std::max(g0.H, geo[i].H);
+    }
+    if (!fields) return SC_OK;
+    if (worst) return worst;
+    if (capacity < (size_t)g0.W * g0.H) return SC_ERR_BAD_SIZE;
+    I->mpitch = round_up(g0.W, 64);
+    const size_t mplane = (size_t)I->mpitch * g0.H;
+    if ((rc = ensure(I, I->d_M, mplane * n, false))) return rc;
+    if ((rc = setup_fields(I, g0.W, g0.H, 3 * n))) return rc;
+    std::vector<int> idx(n);
+    for (int i = 0; i < n; ++i) idx[i] = i;
+    std::vector<MaskJob> mj;
+    std::vector<ImageJob> ij;
+    group_member_jobs(I, jobs, idx, geo, nullptr, d_r, form == 3, std::vector<char>(n, 0), mplane, mj, ij);
+    launch_mask_erode3_group(mj.data(), n, I->stream);
+    I->erode_done = false;
+    I->f_half = f_half; I->u_half = u_half; I->u0_bytes = no_u0;
+    launch_preprocess_group(ij.data(), n, I->mpitch, I->U0, I->F, I->stream, I->f_half, I->u_half, I->clone_mode, !I->u0_bytes);
+    SC_HIP(I, hipGetLastError());
+    if ((rc = front_download(I, 0, n, geo.data(), mplane, f_half, u_half, no_u0, out))) return rc;
+    SC_HIP(I, hipStreamSynchronize(I->stream));
+    I->u0_bytes = false;
     return SC_OK;
 }
 

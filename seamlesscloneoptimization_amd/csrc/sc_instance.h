@@ -322,6 +322,22 @@ int geo_from_rect(Instance *I, const int r[4], int cx, int cy, Geo &g);
 int check_roi(Instance *I, const Geo &g, int bc, int br);
 int device_bbox(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, int cx, int cy, Geo &g);   // waits for the device's rectangle
 void erode_mask(Instance *I, const uint8_t *d_mask, int ms, int mr, const Geo &g);                    // ROI g of the mask into I->d_M
+// the scan of a device mask into the instance's rectangle (d_rect, pinned mailbox h_rect[4..7]), enqueue only.  predicted: the scan does not
+// go out -- it is left in pending_scan (with the erode's geometry and byte count) to ride in the clone's pre-process launch
+int bbox_enqueue(Instance *I, const uint8_t *d_mask, int mc, int mr, int ms, const Geo *predicted = nullptr);
+// the pre-process launch of a single clone on its ROI origins, into the instance's fields in the formats f_half / u_half name; a pending
+// scan rides in it, its tiles then erode the mask themselves into d_M.  Returns whether it carried the scan.
+bool launch_clone_preprocess(Instance *I, const uint8_t *body_org, int bstep, const uint8_t *face_org, int fstep);
+// pixel (x, y) of an interleaved 8-bit BGR image: where a ROI's origin lies
+template <class T> inline T *roi_at(T *img, int step, int x, int y) { return img + (size_t)y * step + 3 * x; }
+// sc_batch.cpp: the jobs of a group's launches.  GROUP_RS: ints between the rectangles of a group's scans, one 128-byte line each (eight
+// rectangles in one line: 162 us for the group's scan instead of 20)
+constexpr int GROUP_RS = 32;
+// the scans of the usable members of a call: rectangles to d_r and to the pinned h_out, GROUP_RS ints apart, at the member's index
+std::vector<MaskJob> group_scan_jobs(const sc_batch_job *jobs, int n, const std::vector<char> &usable, int *d_r, int *h_out);
+// erode and image jobs of members idx[0..) as one field (run_group_members): member k's eroded mask is plane k (mplane bytes) of d_M
+void group_member_jobs(Instance *I, const sc_batch_job *jobs, const std::vector<int> &idx, const std::vector<Geo> &geo, const int *guess, int *d_r,
+                       bool size_class, const std::vector<char> &frame, size_t mplane, std::vector<MaskJob> &mj, std::vector<ImageJob> &ij);
 void fill_info_geo(Instance *I, const Geo &g);
 float ev_ms(hipEvent_t a, hipEvent_t b);
 // stage mark k of an edit or a Poisson call (synchronous calls only; a failed record leaves the mark's time unread)
