@@ -187,6 +187,22 @@ SC_API int sc_hip_u0_bytes_fetch(const uint8_t *row, int W, int xw, int *out);
  * ranges. */
 SC_API int sc_hip_coarse_tile_plan(const int *facts, int *plan);
 
+/* Host only, nothing is launched: the tiling of a level-0 multigrid launch (csrc/sc_cycle0.hip: k_cycle0) on a W x H field (ring
+ * included) by the functions its launcher evaluates and, per wave, what the kernel's wave-uniform `inner` test answers -- a restatement of
+ * the kernel's lines beside them (csrc/sc_cycle0.hip: cycle0_inner_fail), on the level sizes of the library's own ladder.
+ * facts = { W, H, sweeps of the launch (2: first launch, judged cycle; 4: full cycle), prolong (0 / 1), composed (0 / 1: it prolongs from
+ * the composed level 1) }.
+ * plan = { column tiles nbx, row tiles nby, columns a tile owns, rows a tile owns, halo columns hx, halo rows hy, waves per tile, rows
+ * per wave, levels of the ladder, first level of the bottom under the default options, the default tail level (0: none), 1: the default
+ * schedule composes level 1, unknowns of level 1 in x and y, unknowns of level 2 in x and y (0: no such level) }, then -- where
+ * capacity allows more than these SC_CYCLE0_PLAN_HEAD ints -- one int per wave, (row tile * nbx + column tile) * waves per tile + wave:
+ * 0 the wave takes the mask-free forms, else the first condition that fails: 1 xw >= 4, 2 xw + 255 <= W - 2, 3 y0 >= 1,
+ * 4 y0 + R - 1 <= H - 2, and of a launch that prolongs 5 level 1's last column, 6 its first row, 7 its last row, composed 8 level 2's
+ * last column, 9 its last row (xw = column tile * columns owned - hx, y0 = row tile * rows owned - hy + wave * R).
+ * Returns 0; SC_ERR_BAD_ARG for facts outside their ranges, a ladder without the levels asked of it, or too little capacity for the waves. */
+#define SC_CYCLE0_PLAN_HEAD 16
+SC_API int sc_hip_cycle0_plan(const int *facts, int *plan, int capacity);
+
 /* Host only, nothing is launched: the tiling of the work planes a conjugate-gradient call (sc_hip_weighted, _wls, _robust, _region,
  * _volume, _volume_wls) would run with on images of cols x rows pixels under the border word `kind` (a base kind with its SC_POISSON_NEUMANN,
  * SC_POISSON_FREE_* or SC_POISSON_PERIODIC_* bits, as the calls take it); frames: a volume call's (its frames' unknowns stacked along

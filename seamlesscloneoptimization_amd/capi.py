@@ -504,6 +504,8 @@ def load():
     L.sc_hip_cycle0_form.restype = C.c_int
     L.sc_hip_coarse_tile_plan.argtypes = [i32p, i32p]
     L.sc_hip_coarse_tile_plan.restype = C.c_int
+    L.sc_hip_cycle0_plan.argtypes = [i32p, i32p, C.c_int]
+    L.sc_hip_cycle0_plan.restype = C.c_int
     L.sc_hip_pcg_plan.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_longlong)]
     L.sc_hip_pcg_plan.restype = C.c_int
     L.sc_hip_fused_schedule.argtypes = [i32p, i32p, C.c_int, i32p, C.c_int]
@@ -2106,6 +2108,30 @@ def coarse_tile_plan(W, H, C_, useful, halo, rows, size_class=False, unpacked=Fa
         raise SeamlessCloneError(rc, "coarse_tile_plan")
     t = out[4:].reshape(n, 130)
     return tuple(int(v) for v in head), (t[:, 0], t[:, 1], t[:, 2::2], t[:, 3::2])
+
+
+CYCLE0_PLAN = ("nbx", "nby", "xstep", "ystep", "hx", "hy", "waves", "rows", "levels", "bottom", "tail", "composes", "n1x", "n1y", "n2x", "n2y")
+CYCLE0_INNER = ("inner", "x_first", "x_last", "y_first", "y_last", "l1_x", "l1_y_first", "l1_y_last", "l2_x", "l2_y")
+
+
+def cycle0_plan(W, H, sweeps, prolong=False, composed=False):
+    """Host-only: the tiling of a level-0 multigrid launch with `sweeps` sweeps on a W x H field (ring included) and what the kernel's
+    wave-uniform `inner` test answers for each of its waves (sc_hip_cycle0_plan): a dict of CYCLE0_PLAN (the last eight: the library's
+    own ladder for the size) plus "inner": int array [nby, nbx, waves], an index into CYCLE0_INNER (0: the mask-free forms)."""
+    f = (C.c_int * 5)(int(W), int(H), int(sweeps), int(bool(prolong)), int(bool(composed)))
+    n = len(CYCLE0_PLAN)
+    head = np.zeros(n, np.int32)
+    rc = load().sc_hip_cycle0_plan(f, head.ctypes.data_as(i32p), n)
+    if rc != 0:
+        raise SeamlessCloneError(rc, "cycle0_plan")
+    waves = int(head[0]) * int(head[1]) * int(head[6])
+    out = np.zeros(n + waves, np.int32)
+    rc = load().sc_hip_cycle0_plan(f, out.ctypes.data_as(i32p), n + waves)
+    if rc != 0:
+        raise SeamlessCloneError(rc, "cycle0_plan")
+    plan = dict(zip(CYCLE0_PLAN, (int(v) for v in out[:n])))
+    plan["inner"] = out[n:].reshape(int(head[1]), int(head[0]), int(head[6])).copy()
+    return plan
 
 
 PCG_PLAN = ("nx", "ny", "x0", "y0", "cg", "bands", "rows", "eparts", "egroups", "stride")

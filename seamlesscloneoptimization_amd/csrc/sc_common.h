@@ -292,6 +292,9 @@ void launch_max_final2(const float *d_a, int na, const float *d_b, int nb, unsig
 // tiling of a level-0 launch (sc_cycle0.hip, launch_cycle0 below)
 void cycle0_row_geometry(int H, int sweeps, int &nby, int &step, int &hy);
 int  cycle0_blocks(int W, int H, int C, int sweeps);
+// host only (sc_hip_cycle0_plan): head[8] = nbx, nby, column step, row step, hx, hy, waves per tile, rows per wave; verdicts[(by nbx + bx) waves + wave] =
+// what k_cycle0's `inner` test answers there (restated beside cycle0_plan, sc_cycle0.hip); ncx .. n2y: coarse unknowns of levels 1 and 2.  -1: no such launch.
+int  cycle0_plan(int W, int H, int sweeps, bool prolong, bool composed, int ncx, int ncy, int n2x, int n2y, int head[8], int *verdicts, int capacity);
 // coarse level: zero-guess pre-smoothing + residual + restriction fused (Uout = smoothed correction, Fc = next RHS)
 bool launch_cycle_coarse(Field Uout, Field F, Field Fc, const MGGeom &g, int sweeps, hipStream_t s, bool half_io = false,
                          const RagMember *rag = nullptr, int lev = 0, bool pack = true);

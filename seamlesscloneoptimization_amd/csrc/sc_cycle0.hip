@@ -1018,6 +1018,52 @@ void cycle0_row_geometry(int H, int sweeps, int &nby, int &step, int &hy)
     hy = 2 * sweeps + 2; step = RH - 2 * hy; nby = (H + step - 1) / step;
 }
 
+// k_cycle0's wave-uniform `inner` test (the lines from `const int xw = bx * (256 - 2 * C0_HX) - C0_HX` to the end of `if (PRO) { ... }`
+// above its prolongation), RESTATED for the host: 0 where the wave takes the mask-free forms, else the first condition that fails, in the
+// kernel's order (seamlessclone_hip_testing.h: sc_hip_cycle0_plan).  A copy, not the kernel's own text: with the test moved into a function
+// both sides call, every PRO instantiation kept its registers and scratch but changed its code size by 4 .. 12 bytes, and the kernel is not
+// to change for a test hook.  Whoever edits the test up there edits this (tests/test_mg_cycles_host.py holds the equalities of both).
+static int cycle0_inner_fail(int R, bool PRO, bool COMP, int xw, int y0, int W, int H, int ncx, int ncy, int n2x, int n2y)
+{
+    const int NE = R / 2 + 2, NQ = R / 4 + 3;      // rows of the level-1 and level-2 windows
+    if (!(xw >= 4)) return 1;
+    if (!(xw + 255 <= W - 2)) return 2;
+    if (!(y0 >= 1)) return 3;
+    if (!(y0 + R - 1 <= H - 2)) return 4;
+    if (PRO) {
+        const int Jb = (y0 >> 1) - 1;
+        if (!(((xw + 252) >> 1) + 2 <= ncx)) return 5;
+        if (!(Jb >= 1)) return 6;
+        if (!(Jb + NE - 1 <= ncy)) return 7;
+        if (COMP) {
+            if (!(((xw + 252) >> 2) + 1 <= n2x)) return 8;
+            if (!((Jb >> 1) + NQ - 1 <= n2y)) return 9;
+        }
+    }
+    return 0;
+}
+
+// The tiling of a level-0 launch by the functions its launcher evaluates, and the `inner` verdict of each of its waves (host arithmetic;
+// nothing is launched).  verdicts == nullptr: the head only.
+int cycle0_plan(int W, int H, int sweeps, bool prolong, bool composed, int ncx, int ncy, int n2x, int n2y, int head[8], int *verdicts, int capacity)
+{
+    if (W < 3 || H < 3 || sweeps < 1 || 2 * sweeps + 2 > C0_HX || (composed && !prolong)) return -1;
+    const int xstep = 256 - 2 * C0_HX, nbx = (W + xstep - 1) / xstep;
+    int nby, ystep, hy;
+    cycle0_row_geometry(H, sweeps, nby, ystep, hy);
+    const int out[8] = { nbx, nby, xstep, ystep, C0_HX, hy, C0_NW, C0_R };
+    for (int k = 0; k < 8; ++k) head[k] = out[k];
+    if (!verdicts) return 0;
+    if ((long)nbx * nby * C0_NW > capacity) return -1;
+    for (int by = 0; by < nby; ++by)
+        for (int bx = 0; bx < nbx; ++bx)
+            for (int wv = 0; wv < C0_NW; ++wv) {
+                const int xw = bx * xstep - C0_HX, y0 = by * ystep - hy + wv * C0_R;      // k_cycle0's
+                verdicts[(by * nbx + bx) * C0_NW + wv] = cycle0_inner_fail(C0_R, prolong, composed, xw, y0, W, H, ncx, ncy, n2x, n2y);
+            }
+    return 0;
+}
+
 int cycle0_blocks(int W, int H, int C, int sweeps)
 {
     const int RH = C0_NW * C0_R, HY = 2 * sweeps + 2;

@@ -700,6 +700,26 @@ int sc_hip_coarse_tile_plan(const int *facts, int *plan)
     return SC_OK;
 }
 
+int sc_hip_cycle0_plan(const int *facts, int *plan, int capacity)
+{
+    if (!facts || !plan || capacity < SC_CYCLE0_PLAN_HEAD) return SC_ERR_BAD_ARG;
+    const int W = facts[0], H = facts[1], sweeps = facts[2];
+    const bool prolong = facts[3] != 0, composed = facts[4] != 0;
+    if (W < 3 || H < 3 || W > 65536 || H > 65536) return SC_ERR_BAD_ARG;
+    std::vector<MGGeom> g;
+    mg_plan_levels(W, H, g);                                  // build_levels' ladder
+    const int nl = (int)g.size();
+    if ((prolong && nl < 2) || (composed && nl < 3)) return SC_ERR_BAD_ARG;
+    const size_t bottom = mg_plan_bottom(g, true);            // ... and its default bottom
+    int *const verdicts = capacity > SC_CYCLE0_PLAN_HEAD ? plan + SC_CYCLE0_PLAN_HEAD : nullptr;
+    if (cycle0_plan(W, H, sweeps, prolong, composed, g[0].x.nc, g[0].y.nc, nl > 1 ? g[1].x.nc : 0, nl > 1 ? g[1].y.nc : 0, plan, verdicts,
+                    capacity - SC_CYCLE0_PLAN_HEAD) < 0) return SC_ERR_BAD_ARG;
+    plan[8] = nl; plan[9] = (int)bottom; plan[10] = (int)mg_default_tail_level(g);
+    plan[11] = mg_ladder_composes((size_t)nl, bottom);         // mg_composes_level1 under the default options
+    plan[12] = g[0].x.nc; plan[13] = g[0].y.nc; plan[14] = nl > 1 ? g[1].x.nc : 0; plan[15] = nl > 1 ? g[1].y.nc : 0;
+    return SC_OK;
+}
+
 int sc_hip_pcg_plan(int cols, int rows, int kind, int frames, long long plan[10])
 {
     if (!plan || frames < 1 || frames > SC_POISSON_MAX_PLANES) return SC_ERR_BAD_ARG;

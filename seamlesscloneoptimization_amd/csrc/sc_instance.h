@@ -596,6 +596,8 @@ int lowmode_projection_splits(int nxt, int nkb);                      // row spl
 void launch_lm_tables_rag(const RagMember *rag, int members, int max_rows, int Kxp, int Kyp, hipStream_t s);
 void mg_plan_levels(int W, int H, std::vector<MGGeom> &g);           // sc_mg_levels.cpp
 size_t mg_default_tail_level(const std::vector<MGGeom> &g);
+size_t mg_plan_bottom(const std::vector<MGGeom> &g, bool default_rule);      // first level of the cycle's bottom (g.size(): none)
+bool mg_ladder_composes(size_t levels, size_t bottom);                       // the ladder allows the composed level 1 (mg_composes_level1)
 MGDim make_dim(int n, double a, int nc);                             // one direction of a level: n unknowns, last interval a, nc coarse unknowns
 int bottom_pitch(const MGLevel &L);                                  // row pitch of a level inside the bottom kernel's LDS
 int build_levels(Instance *I);                                       // the hierarchy of the fields bound to I (kept while their size stays)

@@ -41,19 +41,20 @@ static Field level_field(void *p, int W, int H, int C)
 
 // LDS floats level l needs inside the bottom kernel: U and F planes, odd row pitch
 int bottom_pitch(const MGLevel &L) { return (L.g.x.n + 2) | 1; }
-static long bottom_floats(const MGLevel &L) { return 2L * bottom_pitch(L) * (L.g.y.n + 2); }
+static long bottom_floats(const MGGeom &g) { return 2L * ((g.x.n + 2) | 1) * (g.y.n + 2); }
+static long bottom_floats(const MGLevel &L) { return bottom_floats(L.g); }
 
 // first level handled by the fused bottom kernel: the first l >= 1 from which all remaining
 // levels fit the LDS budget together (never level 0: it runs the exact kernels)
-static size_t bottom_start(Instance *I)
+static size_t bottom_start(const std::vector<MGGeom> &g)
 {
-    for (size_t l = 1; l < I->mg.size(); ++l) {
-        if (I->mg.size() - l > (size_t)MG_BOTTOM_MAX_LEVELS) continue;
+    for (size_t l = 1; l < g.size(); ++l) {
+        if (g.size() - l > (size_t)MG_BOTTOM_MAX_LEVELS) continue;
         long tot = 0;
-        for (size_t k = l; k < I->mg.size(); ++k) tot += bottom_floats(I->mg[k]);
+        for (size_t k = l; k < g.size(); ++k) tot += bottom_floats(g[k]);
         if (tot * (long)sizeof(float) <= (long)MG_BOTTOM_LDS_BYTES) return l;
     }
-    return I->mg.size();
+    return g.size();
 }
 
 // Chooses the bottom level solved directly and has its matrices built ON THE DEVICE from the closed-form eigenpairs of the
@@ -137,6 +138,26 @@ size_t mg_default_tail_level(const std::vector<MGGeom> &g)
     return (a && !(a == 2 && level1_direct)) ? a : 0;
 }
 
+// The first level the bottom of the cycle handles on the ladder g: the LDS-fit rule (bottom_start), and under the default rule (see
+// build_levels) the level below the tail level, or the first level the matrix-core solve fits where level 1 does not fit it already.
+size_t mg_plan_bottom(const std::vector<MGGeom> &g, bool default_rule)
+{
+    const size_t nl = g.size();
+    size_t b = bottom_start(g);
+    if (default_rule) {
+        const size_t a = mg_default_tail_level(g);
+        const bool level1_direct = nl > 1 && g[1].x.n <= 96 && g[1].y.n <= 96;
+        if (a) b = a + 1;
+        else if (!level1_direct)
+            for (size_t l = 1; l < nl; ++l)
+                if (g[l].x.n <= 96 && g[l].y.n <= 96) { b = l; break; }
+    }
+    return b;
+}
+
+// The ladder's part of mg_composes_level1 (sc_multigrid.cpp): a launched level 1 with a level 2 below it.
+bool mg_ladder_composes(size_t levels, size_t bottom) { return levels >= 3 && bottom >= 2; }
+
 // The three planes of level l (>= 1, geometry in I->mg[l].g) for C channels: their buffers, the Fields over them, and those of
 // U, F, T (bits 0, 1, 2 of `zero`) queued in zj to be zeroed by the launch that zeroes every plane (a full queue goes out on
 // `zero_on`; the caller launches what is left).
@@ -193,7 +214,8 @@ int build_levels(Instance *I)
     launch_zero_multi(zj, I->stream);
     SC_HIP(I, hipGetLastError());
     I->mg[0].F = I->F;
-    I->mg_bottom = bottom_start(I);
+    const bool default_rule = !(I->opts.flags & SC_FLAG_VCYCLE_BOTTOM) && !legacy_path(I->opts, SC_LEGACY_BOTTOM_F32) && I->opts.mg_direct_max <= 0;
+    I->mg_bottom = mg_plan_bottom(plan, default_rule);
     // Default hierarchy since round 4: the deepest launched level ("A") is the first one (>= 2) with at most 127 unknowns per side --
     // k_mg_tail holds it in registers -- and the level below it ("B", at most 63 per side) is the one solved directly, on the matrix
     // cores, inside the same launch.  The LDS-fit rule above chose the bottom in rounds 1-3; where it landed on a level with 97 .. ~190
@@ -201,14 +223,7 @@ int build_levels(Instance *I)
     // k_mg_bottom instead) a cycle cost 60 us more than at the sizes next to it (0.55 against 0.38 ms for one clone).  Kept: a ROI
     // whose level 1 fits the matrix-core solve at 64 (solved there; at 65..96 only where the ladder has no level for k_mg_tail),
     // the flags that ask for the older bottoms.
-    if (!(I->opts.flags & SC_FLAG_VCYCLE_BOTTOM) && !legacy_path(I->opts, SC_LEGACY_BOTTOM_F32) && I->opts.mg_direct_max <= 0) {
-        const size_t a = mg_default_tail_level(plan);
-        const bool level1_direct = nl > 1 && I->mg[1].g.x.n <= 96 && I->mg[1].g.y.n <= 96;
-        if (a) I->mg_bottom = a + 1;
-        else if (!level1_direct)
-            for (size_t l = 1; l < nl; ++l)
-                if (I->mg[l].g.x.n <= 96 && I->mg[l].g.y.n <= 96) { I->mg_bottom = l; break; }
-    }
+    // (mg_plan_bottom above: the rule itself, which sc_hip_cycle0_plan answers from as well)
     I->mg_l1_half = false;        // fresh planes: all zero in either format
     return build_fd(I);
 }

@@ -197,7 +197,7 @@ bool mg_composes_level1(const Instance *I)
 {
     const sc_solver_opts &o = I->opts;
     const int pre = mg_params(o).pre, post = mg_params(o).post;
-    return !(o.flags & SC_FLAG_NO_COMPOSE_L1) && I->mg.size() >= 3 && I->mg_bottom >= 2 && pre == 2 && post == 2;
+    return !(o.flags & SC_FLAG_NO_COMPOSE_L1) && mg_ladder_composes(I->mg.size(), I->mg_bottom) && pre == 2 && post == 2;
 }
 
 // Level 1 with float16 fields (sc_cycle0.hip, TAG bit 7): the composed schedule on the float16 right-hand side -- the default

@@ -78,8 +78,8 @@ def test_testing_surface_is_a_header_of_its_own(tmp_path):
     hooks = {"sc_hip_mask_stage", "sc_hip_build_rhs", "sc_hip_selftest_host"}
     hooks |= {"sc_hip_field_" + n for n in ("load", "sweep", "residual", "solve", "shape", "store", "finish", "lowmode", "time_sweeps")}
     hooks |= {"sc_hip_time_" + n for n in ("cycle0", "cycle0_form", "coarse_chain", "tail_phases")}
-    hooks |= {"sc_hip_cycle0_form", "sc_hip_fused_schedule"}
-    assert len(hooks) == 18 and hooks <= testing, hooks - testing
+    hooks |= {"sc_hip_cycle0_form", "sc_hip_fused_schedule", "sc_hip_cycle0_plan"}
+    assert len(hooks) == 19 and hooks <= testing, hooks - testing
     nm = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], check=True, capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in nm.splitlines() if re.fullmatch(r"(?:my_seamlessclone_api_imp_|sc_hip_)\w+", l.split()[-1])}
     assert exported == public | testing, (exported - (public | testing), (public | testing) - exported)
