@@ -1158,7 +1158,7 @@ SC_API int sc_hip_volume(void *instance, const sc_volume_params *p, const sc_poi
  * run -- for every per-job refusal of sc_hip_volume; exactly one of smooth_x / smooth_y; link arrays where the first volume has none, or
  * the reverse; a link array overlapping out; a live link that is not finite or not > 0 (smooth_t as well as its product with tau),
  * judged only where it is read.  The pin check is sc_hip_volume's; an UNKNOWN - KNOWN link counts its own weight.
- * Not offered: motion-compensated temporal links, the 8-bit entry points. */
+ * Not offered: the 8-bit entry points.  Motion-compensated temporal links: sc_hip_volume_flow below, with these parameters. */
 typedef struct sc_volume_wls_params {
     int       kind;            /* as sc_volume_params.kind */
     int       frames;          /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
@@ -1194,6 +1194,77 @@ SC_API int sc_hip_volume_wls_device(void *instance, const sc_volume_wls_params *
 SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                              const float *gt, const float *lap, const float *data, const float *state, const float *weight,
                              const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
+/* ---- flow volume solves: temporal links along a caller's motion field ----------------------------------------------------------------------
+ * sc_hip_volume_wls's problem, word for word, except that a temporal link joins pixel p of frame t to pixel m_t(p) of frame t + 1, where
+ * m_t follows a flow the caller supplies; the temporal term is
+ *     sum_t sum_p lt(p) (u_{t+1}(m_t(p)) - u_t(p) - gt_t(p))^2
+ * over the pixels p that hold a link.  On footage in which anything moves the straight link of sc_hip_volume_wls ties a pixel to another
+ * surface point of the next frame and the solve smears along the motion; with the scene's flow the links follow the surface.  Cloning,
+ * inpainting, propagation and smoothing of video with a moving camera or moving objects.  The parameters are sc_volume_wls_params,
+ * unchanged.  smooth_t and gt stay stored at the link's source element (p, t).
+ * flow_x, flow_y: float32, dense and without channel axis whatever the layout: element (x, y, t) at (t * rows + y) * cols + x; frames - 1
+ * frames, with time_periodic `frames` of them, the last from frame frames - 1 onto frame 0.  Element (x, y, t) says that pixel (x, y) of
+ * frame t is pixel (x + flow_x, y + flow_y) of frame t + 1.  Values are whole numbers (-0.0 is 0); a component that is not finite means
+ * "no link": that is how a caller marks an occlusion.  A volume's channels share its flow.
+ * The matching, per volume and pair of frames, without regard to state.  A pixel p of the work rectangle -- the border kind's unknowns:
+ * a Dirichlet line is outside, it has no temporal links -- is a candidate when both components are finite, both have magnitude <= 1e6 (a
+ * finite value beyond counts as leaving the rectangle) and its target lies inside the work rectangle; on a periodic axis the target wraps.
+ * Among the candidates with the same target the one with the smallest y * nx + x in work-rectangle coordinates holds the link, the others
+ * hold none.  So every pixel holds at most one link and at most one arrives at it, the system stays symmetric, and nothing depends on
+ * the order in which anything ran.
+ * Liveness, right-hand side, diagonal, pin check: sc_hip_volume_wls's rules on matched pairs.  A matched link is live when neither end
+ * is OUTSIDE and at least one end is UNKNOWN.  In the seven steps "the link to the next frame" is the link this pixel holds and "the
+ * link to the previous frame" the link that arrives at it, whose lt and gt are read at its source's element; a KNOWN temporal
+ * neighbour's data is read at the partner pixel; the diagonal is (((lw + le) + (ln + ls)) + (lb + lf)) + w with lb the arriving link.
+ * What is read: sc_hip_volume_wls's elements, with gt and smooth_t only at live matched links (a NaN at an unmatched or dead link is
+ * fine), and the flow at every pixel of the work rectangle of every frame it holds, nowhere else.  The flow arrays must not overlap out.
+ * Ties: flow arrays of zeros give the bytes and the iteration count of sc_hip_volume_wls; both arrays NULL runs sc_hip_volume_wls's
+ * launches.  Two runs of one call give the same bytes: the matching's one atomic is an integer minimum.
+ * Solved as sc_hip_volume_wls, with its preconditioner unchanged: M = s-bar A - w-bar + tau-bar A_t with straight time links and the
+ * same means (tau-bar is exactly tau without smooth_t).  M is positive definite, so the iteration converges, but it is no longer exact
+ * for constant coefficients: strong temporal coupling together with several pixels of motion is expensive.  Iterations of a float64
+ * model at tol 1e-5 (all UNKNOWN, a data weight at 3 % of the pixels, free sides, 47 x 33 x 5 and 64 x 64 x 8):
+ *     tau    zero flow   halves moving +-1 px   halves moving +-3 px   random +-3 px
+ *     0.1       10            10 - 12                10 - 12              10 - 12
+ *     1          8            17 - 18                43 - 46              25 - 26
+ *     10         7           100 - 106              335 - 371            163 - 171
+ * Raise max_iters there.  Size, chunks, stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, methods, SC_FLAG_FFT_FP64 limits, host waits,
+ * sc_run_info: sc_hip_volume_wls's.
+ * Size: the link planes index a volume's unknowns with 32 bits, so (unknowns per frame) * frames must be below 2^31 - 1: a larger
+ * volume -- 8192 x 8192 free-sided pixels take 31 frames, not 32 -- gets SC_ERR_BAD_SIZE from sc_hip_volume_flow_check and from a call
+ * that carries a flow, before anything runs (without flow arrays the call is sc_hip_volume_wls and takes what that call takes).
+ * Codes: everything sc_hip_volume_wls_check refuses, and SC_ERR_BAD_SIZE as above.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others run -- for
+ * every per-job refusal of sc_hip_volume_wls; exactly one of flow_x / flow_y; a flow where the first volume has none, or the reverse; a
+ * flow array overlapping out; a finite flow value, where the flow is read, that is not a whole number.
+ * Not offered: flow through sc_hip_volume, sc_hip_volume_robust, sc_hip_volume_coupled or the 8-bit entry points; sub-pixel flow (a link
+ * would become a stencil of several points and the matching would not apply); a preconditioner that transforms along the trajectories;
+ * links of several pixels onto one; an estimator of the flow. */
+typedef struct sc_volume_flow_job {     /* sc_volume_wls_job and the two flow arrays */
+    const float *gx, *gy;    /* SC_POISSON_GUIDANCE: `frames` frames, read at links live in the region */
+    const float *gt;         /* SC_POISSON_GUIDANCE: frames - 1 frames (time_periodic: frames), read at live matched links; NULL: zeros */
+    const float *lap;        /* SC_POISSON_LAPLACIAN: read at UNKNOWN pixels */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* `frames` frames, > 0 at links live in the region; both NULL: every spatial link 1 */
+    const float *smooth_y;
+    const float *smooth_t;   /* frames - 1 frames (time_periodic: frames), > 0 at live matched links; NULL: every temporal link tau */
+    const float *flow_x;     /* dense cols x rows x (frames - 1; time_periodic: frames), whole numbers; both NULL: straight links */
+    const float *flow_y;
+    const float *boundary;   /* its Dirichlet lines in every frame (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names in every frame is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_volume_flow_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_flow_check(const sc_volume_wls_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_flow_device(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_flow_job *jobs, int n,
+                                     bool bSync);
+/* One volume on host arrays, as sc_hip_volume_wls: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_volume_flow(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                              const float *gt, const float *lap, const float *data, const float *state, const float *weight,
+                              const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x, const float *flow_y,
+                              const float *boundary, float *out);
 /* ---- robust volume solves: Lp penalties in space, time and data on frame stacks ---------------------------------------------------------
  * sc_hip_volume_wls's problem with sc_hip_robust's penalties in place of the squares.  Per channel, with exponents 0 < p, r, q <= 2, the
  * call minimises over the UNKNOWN pixels of all frames
@@ -1305,8 +1376,8 @@ SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p
  * SC_FLAG_FFT_FP64 limits: sc_hip_volume_robust's.
  * Codes: everything sc_hip_volume_robust_check refuses, coupling bits in kind included; the two refusals of a coupling above.  Per
  * job: the robust volume call's refusals.
- * Not offered: a coupled data term, motion-compensated temporal links, a separate s-bar for x and y, bounds on volumes, the 8-bit entry
- * points. */
+ * Not offered: a coupled data term, motion-compensated temporal links (sc_hip_volume_flow has them, without penalties), a separate
+ * s-bar for x and y, bounds on volumes, the 8-bit entry points. */
 #define SC_VOLUME_COUPLE_SPACE    1   /* one penalty per pixel over its x- and y-link (per frame isotropic TV)          */
 #define SC_VOLUME_COUPLE_TIME     2   /* ... and its forward temporal link in the same magnitude (space-time TV)       */
 #define SC_VOLUME_COUPLE_CHANNELS 4   /* every magnitude sums over the channels of a volume (vectorial TV)            */

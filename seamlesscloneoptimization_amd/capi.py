@@ -291,6 +291,13 @@ class VolumeWlsJob(C.Structure):
                 ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# flow volume solves (sc_hip_volume_flow*): Instance.volume_flow / volume_flow_device -- VolumeWlsParams themselves; temporal links along a flow
+class VolumeFlowJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("gt", C.c_void_p), ("lap", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p),
+                ("weight", C.c_void_p), ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("smooth_t", C.c_void_p), ("flow_x", C.c_void_p),
+                ("flow_y", C.c_void_p), ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # robust solves (sc_hip_robust*): Instance.robust / robust_device / robust_trace
 SC_ROBUST_ISOTROPIC = 1 << 20        # or'ed into RobustParams.kind only: one penalty per pixel over its two forward links
 SC_ROBUST_JOINT_CHANNELS = 1 << 21   # ... one penalty over all channels of a job (both: vectorial TV)
@@ -586,6 +593,13 @@ def load():
     L.sc_hip_volume_wls_device.restype = C.c_int
     L.sc_hip_volume_wls.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 12
     L.sc_hip_volume_wls.restype = C.c_int
+    L.sc_hip_volume_flow_check.argtypes = [C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_flow_check.restype = C.c_int
+    L.sc_hip_volume_flow_device.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout), C.POINTER(VolumeFlowJob), C.c_int,
+                                            C.c_bool]
+    L.sc_hip_volume_flow_device.restype = C.c_int
+    L.sc_hip_volume_flow.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 14
+    L.sc_hip_volume_flow.restype = C.c_int
     L.sc_hip_volume_robust_check.argtypes = [C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_volume_robust_check.restype = C.c_int
     L.sc_hip_volume_robust_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout), C.POINTER(VolumeRobustJob),
@@ -1117,6 +1131,31 @@ def volume_wls_arrays(data, state, weight=None, smooth_x=None, smooth_y=None, sm
     return kind, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, lap, boundary
 
 
+def volume_flow_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                      tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0, precond_tau: float = 0.0,
+                      layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                      channel_stride=None) -> int:
+    """Host-only sc_hip_volume_flow_check: volume_wls_check's codes -- the flow call takes the WLS volume call's parameters unchanged."""
+    p = VolumeWlsParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(tol), int(max_iters),
+                        float(precond_lambda), float(precond_smooth), float(precond_tau))
+    return _check_call("sc_hip_volume_flow_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_flow_planes(flow, frames: int, rows: int, cols: int, loop: bool = False):
+    """A flow for a volume of `frames` frames of rows x cols pixels as the C layer wants it: (flow_x, flow_y), two C-contiguous float32
+    arrays of shape (frames - 1) x rows x cols -- with loop `frames` of them, the last from the last frame onto frame 0.  flow: a real
+    array of that shape x 2 holding (dx, dy): pixel (x, y) of frame t is pixel (x + dx, y + dy) of frame t + 1.  Values are rounded to
+    whole numbers (np.rint); NaN and the infinities are kept: "no link here" (an occlusion)."""
+    if not isinstance(flow, np.ndarray) or not (np.issubdtype(flow.dtype, np.floating) or np.issubdtype(flow.dtype, np.integer)):
+        raise TypeError("flow must be a numpy array of real numbers")
+    want = ((frames if loop else frames - 1), rows, cols, 2)
+    if flow.shape != want:
+        raise ValueError(f"flow has shape {flow.shape}, the problem {want}: (dx, dy) per pixel of every frame that has a next one")
+    f = np.rint(flow.astype(np.float32))
+    return np.ascontiguousarray(f[..., 0]), np.ascontiguousarray(f[..., 1])
+
+
 def volume_robust_params(kind, frames, frame_stride, tau=1.0, loop=False, p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
                          eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0) -> VolumeRobustParams:
     return VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), 1 if loop else 0, float(p_grad), float(eps_grad), float(p_time),
@@ -1634,6 +1673,35 @@ class Instance:
         frame stride for all.  sync: bSync and a wait for the stream.  Per-job codes in jobs[i].rc; returns the worst code:
         SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_volume_wls_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- flow volume solves on float32 arrays
+    def volume_flow(self, data, state, flow, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gx=None, gy=None, gt=None, lap=None,
+                    boundary=None, tau=1.0, loop=False, neumann=False, free_sides="", periodic="", tol=0.0, max_iters=0, precond_lambda=0.0,
+                    precond_smooth=0.0, precond_tau=0.0, allow_not_converged=False):
+        """sc_hip_volume_flow on numpy float32 arrays (volume_wls_arrays' rules): volume_wls()'s problem with every temporal link along
+        `flow` ((T - 1) x H x W x 2, with loop T x H x W x 2, holding (dx, dy); volume_flow_planes' rules: rounded, NaN = no link).  gt and
+        smooth_t stay stored at a link's source pixel.  flow None: volume_wls() itself.  Returns a NEW array composed as volume()'s."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, lap, boundary = volume_wls_arrays(data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                              gx, gy, gt, lap, boundary, tau, loop, neumann,
+                                                                                              free_sides, periodic)
+        fx, fy = (None, None) if flow is None else volume_flow_planes(flow, data.shape[0], data.shape[1], data.shape[2], loop)
+        layout = poisson_layout_of(data[0])
+        p = VolumeWlsParams(kind, data.shape[0], data[0].size, float(tau), 1 if loop else 0, float(tol), int(max_iters), float(precond_lambda),
+                            float(precond_smooth), float(precond_tau))
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_flow(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                       (gx, gy, gt, lap, data, state, weight, sx, sy, smt, fx, fy, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    @staticmethod
+    def make_volume_flow_jobs(n: int):
+        return (VolumeFlowJob * n)()
+
+    def volume_flow_device(self, params: VolumeWlsParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_flow_device: jobs is a VolumeFlowJob array (make_volume_flow_jobs) of device pointers; flow_x, flow_y are dense
+        W x H x (T - 1; periodic time: T) float32 whatever the layout.  Codes as volume_wls_device."""
+        return self._device_call("sc_hip_volume_flow_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- robust volume solves on float32 arrays
     def volume_robust(self, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,

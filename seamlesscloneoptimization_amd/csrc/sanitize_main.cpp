@@ -18,7 +18,8 @@
 //      sc_hip_robust_check: the same verdicts on a guidance base, its own on a Laplacian base, a bad exponent, a bad eps; the coupling
 //      bits (SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS) change none of its verdicts and are refused by every other check;
 //      sc_hip_volume_check: the same verdicts for two frames a frame's span apart, then frames, the plane limit, frame_stride and tau.
-//      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau.
+//      sc_hip_volume_wls_check: the volume call's verdicts under free and periodic time, then time_periodic, precond_smooth, precond_tau;
+//      sc_hip_volume_flow_check beside it: the flow call takes the same parameters and gives the same verdicts.
 //      sc_hip_region_robust_check: the robust call's verdicts (the region call's on a guidance base), the coupling bits accepted, then every
 //      exponent, every eps, round_tol and tol.
 //      sc_hip_bounded_check: the region call's verdicts under any valid pair of scalar bounds, then lower > upper and a NaN bound.
@@ -488,6 +489,7 @@ int main()
                 const int fr = tp ? 3 : 2;
                 sc_volume_wls_params wp{ k.kind, fr, span, 1.f, tp, k.tol, k.iters, k.plam, 0.f, 0.f };
                 if (sc_hip_volume_wls_check(&wp, &l) != k.want) return fail("volume_wls_check");
+                if (sc_hip_volume_flow_check(&wp, &l) != k.want) return fail("volume_flow_check");          // (the same parameters, the same verdicts)
                 wp.precond_smooth = wp.precond_tau = k.plam;          // (the same values make the same verdicts)
                 if (sc_hip_volume_wls_check(&wp, &l) != k.want) return fail("volume_wls_check (precond_smooth, precond_tau)");
                 wp.precond_smooth = wp.precond_tau = 0.f;

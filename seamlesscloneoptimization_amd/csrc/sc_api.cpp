@@ -379,7 +379,7 @@ void my_seamlessclone_api_imp_destroy(void *p)
     if (I->h_maxcorr) (void)hipHostFree(I->h_maxcorr);
     if (I->h_rect) (void)hipHostFree(I->h_rect);
     if (I->h_red) (void)hipHostFree(I->h_red);
-    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in, &I->h_hyst, &I->h_sx, &I->h_sy, &I->h_state, &I->h_gt, &I->h_smt, &I->h_lo, &I->h_hi }) if (b->p) (void)hipHostFree(b->p);
+    for (DevBuf *b : { &I->h_face, &I->h_body, &I->h_mask, &I->h_out, &I->h_in, &I->h_hyst, &I->h_sx, &I->h_sy, &I->h_state, &I->h_gt, &I->h_smt, &I->h_lo, &I->h_hi, &I->h_fx, &I->h_fy }) if (b->p) (void)hipHostFree(b->p);
     for (int i = 0; i < 8; ++i) if (I->ev[i]) (void)hipEventDestroy(I->ev[i]);
     for (int i = 0; i < 8; ++i) if (I->ev_chunk[i]) (void)hipEventDestroy(I->ev_chunk[i]);
     if (I->ev_k0) (void)hipEventDestroy(I->ev_k0);

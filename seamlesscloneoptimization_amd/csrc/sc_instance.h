@@ -166,6 +166,7 @@ struct Instance {
     DevBuf h_state;                                // a region host call's state array (float_stage)
     DevBuf h_gt, h_smt;                            // a volume host call's temporal guidance and temporal link weights (float_stage)
     DevBuf h_lo, h_hi;                             // a bounded host call's bound arrays (float_stage)
+    DevBuf h_fx, h_fy;                             // a flow volume host call's two flow arrays (sc_hip_volume_flow)
     std::unique_ptr<RowCopier> copier;   // helper threads for the packing / splicing copies (created on first use)
     hipEvent_t ev_chunk[8]{};            // D2H chunk completions (host path): splice chunk k while k+1 is in flight
     // ROI mask after 3x erode
@@ -398,7 +399,7 @@ inline bool poisson_no_dirichlet(int kind)
 struct PoissonCall { int kind; float tol, lam; };      // kind: poisson_norm_kind's
 size_t poisson_span(const sc_poisson_layout *l);          // floats from an array's pointer to one past its last element
 // What a family's jobs carry beyond the Poisson call's arrays, and one job's arrays (host or device pointers; absent ones NULL).
-enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16, FLOAT_SMOOTH_T = 32, FLOAT_LOWER = 64, FLOAT_UPPER = 128 };
+enum { FLOAT_DATA = 1, FLOAT_WEIGHT = 2, FLOAT_SMOOTH = 4, FLOAT_STATE = 8, FLOAT_GT = 16, FLOAT_SMOOTH_T = 32, FLOAT_LOWER = 64, FLOAT_UPPER = 128, FLOAT_FLOW = 256 };
 struct FloatArrays {
     const float *gx, *gy, *lap, *data, *weight, *boundary; float *out; const float *smooth_x = nullptr, *smooth_y = nullptr;
     const float *state = nullptr;      // FLOAT_STATE: the region call's state array
@@ -406,6 +407,7 @@ struct FloatArrays {
     const float *smooth_t = nullptr;   // FLOAT_SMOOTH_T: the WLS volume call's temporal link weights
     const char *refuse = nullptr;      // the family's own reason against this job (float_job_validate: SC_ERR_BAD_ARG with it)
     const float *lower = nullptr, *upper = nullptr;      // FLOAT_LOWER, FLOAT_UPPER: the bounded call's per-pixel bounds
+    const float *flow_x = nullptr, *flow_y = nullptr;    // FLOAT_FLOW: the flow volume call's two dense flow arrays (no channel axis, their own length)
 };
 // A screened or weighted family's validation around poisson_validate: params (their kind) and layout non-null, `own` (the reason the
 // family's own parameters fail, or NULL), the Poisson call's checks, then the direct solve's side limit under a frame with `limit_why`.
@@ -419,14 +421,18 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 // neither they nor weight may share a float of their span with out's.  FLOAT_STATE: the state array as well, under the same span rule
 // (which then holds for whichever of weight and the link arrays the call carries).  FLOAT_SMOOTH_T: the temporal link array as well; it
 // occupies tspan floats (the call's temporal frames) and may share none of them with out's span.  FLOAT_LOWER, FLOAT_UPPER: that bound
-// array as well, under state's span rule.
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0, size_t tspan = 0);
+// array as well, under state's span rule.  FLOAT_FLOW: the two flow arrays as well; each occupies fspan floats (dense: the call's temporal
+// frames of cols x rows) and may share none of them with out's span.
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span = 0, size_t tspan = 0, size_t fspan = 0);
 PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a);
 // A job's side arrays: what a family's set-up reads beside the job's PoissonJobDev -- data weights, spatial link weights, the region
 // and volume calls' state, the volume calls' temporal guidance and temporal link weights, the bounded call's bound arrays.  Device pointers; an array the call does not
 // carry (its FLOAT_* bit is not in `carries`) is NULL: float_intake and float_stage say so, nobody behind them asks again.  One record
 // per job, beside its PoissonJobDev from there to the kernels' tables (sc_pcg.h: PcgOperator::ds, for_side_tables).
-struct SideArrays { const float *w = nullptr, *sx = nullptr, *sy = nullptr, *st = nullptr, *gt = nullptr, *smt = nullptr, *lo = nullptr, *hi = nullptr; };
+struct SideArrays {
+    const float *w = nullptr, *sx = nullptr, *sy = nullptr, *st = nullptr, *gt = nullptr, *smt = nullptr, *lo = nullptr, *hi = nullptr;
+    const float *fx = nullptr, *fy = nullptr;      // the flow volume call's two dense flow arrays
+};
 // The validated jobs of a device call: their device forms (contiguous: the Poisson and the screened call hand dj.data() to the solve),
 // their side arrays and where each one's code goes.
 struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<SideArrays> side; std::vector<int *> rcs; };
@@ -434,7 +440,7 @@ struct FloatJobs { std::vector<PoissonJobDev> dj; std::vector<SideArrays> side; 
 // others go into v with SC_ERR_HIP until their chunk has run.  Returns the worst validation code, I->err the first reason (v.rcs
 // empty: nothing to run).
 template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int carries, Job *jobs, int n, ArraysOf arrays_of, FloatJobs &v,
-                                                      size_t span = 0, size_t tspan = 0)
+                                                      size_t span = 0, size_t tspan = 0, size_t fspan = 0)
 {
     if (!jobs || n <= 0) { I->err = "no jobs"; return SC_ERR_BAD_ARG; }
     int worst = SC_OK;
@@ -442,7 +448,7 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
     for (int i = 0; i < n; ++i) {
         Job &j = jobs[i];
         const FloatArrays a = arrays_of(j);
-        const int vrc = float_job_validate(kind, carries, a, &why, span, tspan);
+        const int vrc = float_job_validate(kind, carries, a, &why, span, tspan, fspan);
         if (vrc != SC_OK) {
             j.rc = vrc;
             if (worst == SC_OK) { worst = vrc; I->err = why; }
@@ -455,19 +461,21 @@ template <class Job, class ArraysOf> int float_intake(Instance *I, int kind, int
                                      carries & FLOAT_STATE ? a.state : nullptr, carries & FLOAT_GT ? a.gt : nullptr,
                                      carries & FLOAT_SMOOTH_T ? a.smooth_t : nullptr, carries & FLOAT_LOWER ? a.lower : nullptr,
                                      carries & FLOAT_UPPER ? a.upper : nullptr });
+        if (carries & FLOAT_FLOW) { v.side.back().fx = a.flow_x; v.side.back().fy = a.flow_y; }
         v.rcs.push_back(&j.rc);
     }
     return worst;
 }
 // A host call's staging: the arrays' spans into one block of I->d_pois, each at a 256-byte boundary -- gx, gy or lap | data | weight |
-// boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state | lower | upper --, uploaded in that order.  job: the
+// boundary unless it is data | out unless it is data or boundary (in place) | smooth_x | smooth_y | state | lower | upper | flow_x | flow_y --, uploaded in that order.  job: the
 // device job (float_dev_job's rules; job.out is what poisson_download reads), side: the staged side arrays (NULL where the call carries none).
 // frames > 1 (the volume call): every array is `frames` images frame_stride floats apart -- one span of all of them is staged; the
 // temporal arrays -- gt, FLOAT_GT and not NULL, and smooth_t, FLOAT_SMOOTH_T -- hold tframes of them (0: frames - 1) and go behind
-// state, each through a pinned block of its own.
+// state, each through a pinned block of its own.  FLOAT_FLOW: the two flow arrays, flow_floats floats each (at most a slot: they
+// have no channel axis), in the last two slots, through h_fx and h_fy.
 struct FloatStaged { PoissonJobDev job; SideArrays side; };
 int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames = 1,
-                long long frame_stride = 0, int tframes = 0);
+                long long frame_stride = 0, int tframes = 0, size_t flow_floats = 0);
 // nv validated jobs of C channels through chunks of at most SC_POISSON_MAX_PLANES planes: chunk(i0, m) runs jobs i0 .. i0 + m - 1 and
 // sets their codes.  SC_OK and SC_ERR_NOT_CONVERGED let the call go on; any other code ends it: that chunk's jobs and every one not
 // yet run read it, after SC_ERR_HIP the ones already run too.  Returns that code, else the worst.

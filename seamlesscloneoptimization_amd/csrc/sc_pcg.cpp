@@ -258,9 +258,9 @@ int pcg_host_call(Instance *I, const PcgCall &call, const sc_poisson_layout *l, 
 {
     const char *why = "";
     int rc;
-    if ((rc = float_job_validate(call.kind, carries, a, &why, pcg_call_span(call, l), pcg_call_tspan(call, l)))) { I->err = why; return rc; }
+    if ((rc = float_job_validate(call.kind, carries, a, &why, pcg_call_span(call, l), pcg_call_tspan(call, l), call.flow_floats))) { I->err = why; return rc; }
     FloatStaged s;
-    if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride, call.tframes))) return rc;
+    if ((rc = float_stage(I, l, call.kind, carries, a, s, call.frames, call.frame_stride, call.tframes, call.flow_floats))) return rc;
     int job_rc = SC_ERR_HIP, *const job_rcs[1] = { &job_rc };
     rc = pcg_run(I, call, l, op, &s.job, &s.side, job_rcs, 1, true, chunk);
     if (rc != SC_OK && rc != SC_ERR_NOT_CONVERGED) return rc;
@@ -272,7 +272,7 @@ void pcg_release(Instance *I)
 {
     if (!I->pcg) return;
     PcgState &S = *I->pcg;
-    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.f, &S.dct, &S.tab, &S.rho, &S.act, &S.bad, &S.red }) dev_release(*b);
+    for (DevBuf *b : { &S.u, &S.r, &S.p, &S.q, &S.w, &S.e, &S.s, &S.dg, &S.f, &S.dct, &S.tab, &S.lnk, &S.rho, &S.act, &S.bad, &S.red }) dev_release(*b);
     if (S.h_red.p) (void)hipHostFree(S.h_red.p);
     if (S.h_bad.p) (void)hipHostFree(S.h_bad.p);
     for (hipEvent_t e : S.ev) if (e) (void)hipEventDestroy(e);

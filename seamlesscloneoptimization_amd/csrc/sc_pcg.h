@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_robust.hip, sc_volume_coupled.hip: a family's statistics, set-up and operator), the link operator
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_flow.hip, sc_volume_robust.hip, sc_volume_coupled.hip: a family's statistics, set-up and operator), the link operator
 // of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the three
 // robust calls share: their rounds, their check and their entry preamble (RobustRounds, robust_chunk, robust_begin; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
@@ -14,6 +14,7 @@
 #pragma once
 #include "sc_instance.h"
 #include <cassert>
+#include <climits>
 #include <cmath>
 #include <initializer_list>
 
@@ -33,6 +34,7 @@ struct PcgState {
     DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
     DevBuf f, dct, tab;                    // the volume solve's (sc_volume.hip): links to the next frame; the transformed planes; the DCT table (float) and the modes' shifts (double)
+    DevBuf lnk;                            // the flow volume solve's (sc_volume_flow.hip): the int32 link planes fwd | bwd per volume
     DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude
     DevBuf act;                            // the bounded solve's two set planes (sc_bounded.hip): 0 free, +1 upper-active, -1 lower-active
     DevBuf bad, h_bad;                     // ... and its judgement of bound arrays: per part the UNKNOWN pixels with an invalid bound (double; device, pinned)
@@ -111,7 +113,8 @@ struct PcgOperator {
 };
 // kind: poisson_norm_kind's; frames, frame_stride: the volume call's -- a job's arrays are `frames` images under the layout, frame_stride
 // floats apart; tframes: how many of them the temporal arrays hold (gt, smooth_t: frames - 1 with free time, frames with periodic time)
-struct PcgCall { int kind; float tol; int max_iters; int default_iters; int frames = 1; long long frame_stride = 0; int tframes = 0; };
+// flow_floats: the floats of one of the flow volume call's dense flow arrays (0: the call has none)
+struct PcgCall { int kind; float tol; int max_iters; int default_iters; int frames = 1; long long frame_stride = 0; int tframes = 0; size_t flow_floats = 0; };
 // the floats from an array's pointer to one past its last element, all frames of the call (pcg_call_tspan: of a temporal array)
 inline size_t pcg_call_span(const PcgCall &call, const sc_poisson_layout *l) { return poisson_span(l) + (size_t)(call.frames - 1) * (size_t)call.frame_stride; }
 inline size_t pcg_call_tspan(const PcgCall &call, const sc_poisson_layout *l)
@@ -170,7 +173,7 @@ template <class Job, class ArraysOf> int pcg_device_call(Instance *I, const PcgC
                                                          ArraysOf arrays_of, PcgOperator &op, bool timed, PcgChunkFn chunk = nullptr)
 {
     FloatJobs v;
-    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l), pcg_call_tspan(call, l));
+    const int worst = float_intake(I, call.kind, carries, jobs, n, arrays_of, v, pcg_call_span(call, l), pcg_call_tspan(call, l), call.flow_floats);
     if (v.rcs.empty()) return worst;
     I->info.ms_h2d = I->info.ms_d2h = 0.f;
     return worse(worst, pcg_run(I, call, l, op, v.dj.data(), v.side.data(), v.rcs.data(), (int)v.rcs.size(), timed, chunk));
@@ -412,7 +415,41 @@ struct VolumeOperator : PcgOperator {
     void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override;
     int precond(const PcgChunk &c, float, bool fp64, const float *in, float *out) override;
     void out(const PoissonGeo &g, const PcgGeo &wg, int mv, const float *U, hipStream_t s) override;
+protected:
+    // a subclass with statistics of its own length (the flow call's: VOLUME_FLOW_STATS)
+    struct OwnStats { int nstat; };
+    VolumeOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_, int nround_, OwnStats own)
+        : PcgOperator(own.nstat, nround_), I(I_), T(p->frames), fs(p->frame_stride), tau(p->tau), plam(p->precond_lambda), psmooth(p->precond_smooth),
+          ptau(p->precond_tau), periodic(p->time_periodic != 0), links(links_), tlinks(tlinks_) {}
 };
+
+// ---- the flow volume call (sc_volume_flow.hip, and the flow forms of sc_volume.hip's statistics and set-up): sc_hip_volume_wls's system
+// with every temporal link along a whole-numbered flow.  Per volume two dense float32 arrays fx, fy without channel axis -- element
+// (X, Y, t) at (t H + Y) W + X, T - 1 frames, with periodic time T -- say that pixel (X, Y) of frame t is pixel (X + fx, Y + fy) of the
+// next frame.  The link planes: per volume (shared by its channels) two int32 planes of nx * T ny work-plane indices (t ny + y) nx + x,
+// `stride` ints apart: fwd[i] = the element that i's link leads to, bwd[i] = the element whose link arrives at i, -1: none.  Matching
+// (seamlessclone_hip.h, the flow section): a pixel is a candidate when both components are finite, whole, at most 1e6 in magnitude and
+// its target lies in the work rectangle (a periodic axis wraps); of the candidates of one target the smallest index holds the link.
+struct FlowLinks { const int *fwd, *bwd; long long stride; };      // of the launch's first volume
+struct FlowArrays {                                                 // the flow arrays of a launch's volumes (the matching; the statistics count their fractional elements)
+    enum { MAX = 16 }; const float *fx[MAX], *fy[MAX];
+    void set(int i, const SideArrays &a) { fx[i] = a.fx; fy[i] = a.fy; }
+};
+// what the link planes index: a volume's work-plane elements nx * T ny.  A flow call needs them below INT_MAX (the planes' empty mark)
+inline bool flow_indexable(const PcgGeo &wg) { return (long long)wg.nx * wg.ny < (long long)INT_MAX; }
+constexpr int VOLUME_FLOW_STATS = VOLUME_STATS + 1;      // VOLUME_STATS' fields | the flow elements of the work rectangle that are finite and not whole
+inline long long flow_link_stride(const PcgGeo &wg) { return ((long long)wg.nx * wg.ny + 3) / 4 * 4; }
+// fwd and bwd of m volumes from their flow arrays (sides[k].fx, .fy): bwd = INT_MAX, every candidate's integer atomicMin(bwd[target],
+// own index) -- the one atomic, its outcome independent of order --, then fwd[p] = target where bwd[target] == p and INT_MAX -> -1
+void launch_flow_links(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const SideArrays *sides, int m, int *fwd, int *bwd, hipStream_t s);
+// launch_volume_stats in its VOLUME_FLOW_STATS form and launch_volume_setup with the temporal neighbours read through the link planes
+void launch_volume_flow_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                              const int *fwd, const int *bwd, double *stats, hipStream_t s);
+void launch_volume_flow_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides,
+                              int m, const int *fwd, const int *bwd, float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s);
+// launch_volume_op with tb = F[bwd[i]] P[bwd[i]] and tf = F[i] P[fwd[i]] (0 where there is none); C: the planes per volume
+void launch_volume_flow_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, int C, bool residual, const float *P, const float *E, const float *S,
+                           const float *F, const float *Dg, const int *fwd, const int *bwd, float *Q, double *parts, hipStream_t s);
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;

@@ -117,7 +117,7 @@ int direct_instance_check(Instance *I, int kind, const sc_poisson_layout *l, con
 
 // (a job without a Dirichlet line on any side -- the Neumann call, a periodic axis beside a periodic or free-free one -- needs no
 // boundary: out is then checked in its place)
-int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span, size_t tspan)
+int float_job_validate(int kind, int carries, const FloatArrays &a, const char **why, size_t span, size_t tspan, size_t fspan)
 {
     if (a.refuse) { *why = a.refuse; return SC_ERR_BAD_ARG; }
     if ((carries & FLOAT_DATA) && !a.data) { *why = "null data pointer"; return SC_ERR_BAD_ARG; }
@@ -164,6 +164,14 @@ int float_job_validate(int kind, int carries, const FloatArrays &a, const char *
         for (const float *q : { carries & FLOAT_LOWER ? a.lower : nullptr, carries & FLOAT_UPPER ? a.upper : nullptr })
             if (q && overlaps(q)) { *why = "lower or upper overlaps out"; return SC_ERR_BAD_ARG; }
     }
+    if (carries & FLOAT_FLOW) {
+        for (const float *q : { a.flow_x, a.flow_y }) {
+            if (!q) { *why = "null flow_x or flow_y pointer"; return SC_ERR_BAD_ARG; }
+            if (!aligned4(q)) { *why = "array pointer not 4-byte aligned"; return SC_ERR_BAD_ARG; }
+            const uintptr_t o = (uintptr_t)a.out, f = (uintptr_t)q;          // (their own length: dense, no channel axis)
+            if (span && fspan && f < o + span * sizeof(float) && o < f + fspan * sizeof(float)) { *why = "flow_x or flow_y overlaps out"; return SC_ERR_BAD_ARG; }
+        }
+    }
     if (span && tspan && (carries & FLOAT_SMOOTH_T)) {          // (its own length: the call's temporal frames)
         const uintptr_t o = (uintptr_t)a.out, q = (uintptr_t)a.smooth_t;
         if (q < o + span * sizeof(float) && o < q + tspan * sizeof(float)) { *why = "smooth_t overlaps out"; return SC_ERR_BAD_ARG; }
@@ -179,7 +187,7 @@ PoissonJobDev float_dev_job(int kind, int carries, const FloatArrays &a)
 }
 
 int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, const FloatArrays &a, FloatStaged &s, int frames, long long frame_stride,
-                int tframes)
+                int tframes, size_t flow_floats)
 {
     const size_t bytes = (poisson_span(l) + (size_t)(frames - 1) * (size_t)frame_stride) * sizeof(float), slot = (bytes + 255) / 256 * 256;
     const bool guidance = poisson_base(kind) == SC_POISSON_GUIDANCE;
@@ -189,8 +197,9 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     const bool own_b = boundary && boundary != data, in_place = (data && a.out == data) || (boundary && a.out == boundary);
     const bool smooth = (carries & FLOAT_SMOOTH) != 0, state = (carries & FLOAT_STATE) != 0, gt = (carries & FLOAT_GT) && guidance && a.gt;
     const bool smooth_t = (carries & FLOAT_SMOOTH_T) != 0, lower = (carries & FLOAT_LOWER) != 0, upper = (carries & FLOAT_UPPER) != 0;
+    const bool flow = (carries & FLOAT_FLOW) != 0;
     const int slots = (guidance ? 2 : 1) + (data ? 1 : 0) + (weight ? 1 : 0) + (own_b ? 1 : 0) + (in_place ? 0 : 1) + (smooth ? 2 : 0) + (state ? 1 : 0) + (gt ? 1 : 0) +
-                      (smooth_t ? 1 : 0) + (lower ? 1 : 0) + (upper ? 1 : 0);
+                      (smooth_t ? 1 : 0) + (lower ? 1 : 0) + (upper ? 1 : 0) + (flow ? 2 : 0);
     int rc, at = 0;
     if ((rc = ensure(I, I->d_pois, slot * slots, false))) return rc;
     auto next = [&](bool wanted) { return wanted ? (float *)((uint8_t *)I->d_pois.p + slot * at++) : nullptr; };
@@ -201,7 +210,7 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     float *d_b = own_b ? next(true) : (boundary ? d_d : nullptr);
     float *d_out = !in_place ? next(true) : (data && a.out == data ? d_d : d_b);
     float *d_sx = next(smooth), *d_sy = next(smooth), *d_state = next(state), *d_gt = next(gt), *d_smt = next(smooth_t);
-    float *d_lo = next(lower), *d_hi = next(upper);
+    float *d_lo = next(lower), *d_hi = next(upper), *d_fx = next(flow), *d_fy = next(flow);
     SC_HIP(I, hipEventRecord(I->ev_k0, I->stream));
     if ((rc = upload(I->h_face, d_in0, guidance ? a.gx : a.lap))) return rc;
     if ((rc = upload(I->h_body, d_in1, a.gy))) return rc;
@@ -218,7 +227,13 @@ int float_stage(Instance *I, const sc_poisson_layout *l, int kind, int carries, 
     if (d_smt && (rc = upload_rows(I, I->h_smt, d_smt, tbytes, (const uint8_t *)a.smooth_t, tbytes, tbytes, 1))) return rc;
     if ((rc = upload(I->h_lo, d_lo, a.lower))) return rc;
     if ((rc = upload(I->h_hi, d_hi, a.upper))) return rc;
+    const size_t fbytes = flow_floats * sizeof(float);
+    if (flow && fbytes > slot) { I->err = "a flow array is longer than the call's arrays"; return SC_ERR_BAD_ARG; }
+    if (d_fx && (rc = upload_rows(I, I->h_fx, d_fx, fbytes, (const uint8_t *)a.flow_x, fbytes, fbytes, 1))) return rc;
+    if (d_fy && (rc = upload_rows(I, I->h_fy, d_fy, fbytes, (const uint8_t *)a.flow_y, fbytes, fbytes, 1))) return rc;
     s.side = SideArrays{ d_w, d_sx, d_sy, d_state, d_gt, d_smt, d_lo, d_hi };      // (an array the call does not carry has no slot: NULL)
+    s.side.fx = d_fx;
+    s.side.fy = d_fy;
     return SC_OK;
 }
 

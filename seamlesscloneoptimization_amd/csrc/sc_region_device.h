@@ -1,6 +1,6 @@
 // sc_region_device.h -- what the kernels of the region and the volume families share (sc_region.hip, sc_volume.hip, sc_volume_robust.hip):
 // a state element's meaning, the four spatial neighbours of a pixel as the region call sees them, and a volume's frames: the row of a
-// work plane of stacked frames, the two temporal neighbours, a temporal link's weight.
+// work plane of stacked frames, the two temporal neighbours -- one frame away, or at the ends of the flow call's links --, a temporal link's weight.
 #pragma once
 #include "sc_pcg_device.h"
 
@@ -57,7 +57,29 @@ struct TimeAround {
         hb = t > 0 || vg.periodic;
         hf = t < vg.T - 1 || vg.periodic;
     }
+    // the flow form: the neighbours are the ends of the two links of work-plane element (x, y) of volume `member` of the launch (FlowLinks:
+    // fwd, bwd), turned back into offsets of channel c under the call's layout; the wrap of time is in the indices
+    __device__ __forceinline__ TimeAround(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const FlowLinks &fl, int member, int c, int y, int x)
+    {
+        const long long lo = (long long)member * fl.stride + ((long long)y * wg.nx + x);
+        const int jb = fl.bwd[lo], jf = fl.fwd[lo], n2 = wg.nx * vg.ny;
+        auto offset = [&](int j) {
+            const int t = j / n2, r = j - t * n2, y = r / wg.nx, x = r - y * wg.nx;
+            return (long long)(wg.x0 + x) * g.cs + (long long)(wg.y0 + y) * g.rs + (long long)c * g.chs + (long long)t * vg.fs;
+        };
+        hb = jb >= 0; hf = jf >= 0;
+        ob = hb ? offset(jb) : 0; of = hf ? offset(jf) : 0;
+    }
 };
+// the temporal neighbours of a launch's form: FLW through the link planes, else one frame before and behind
+template <bool FLW, class Flow>
+__device__ __forceinline__ TimeAround time_around(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const Flow &fl, int member, int c, int y, int x,
+                                                  int t, long long o, bool wraps)
+{
+    if constexpr (FLW) return TimeAround(g, wg, vg, fl, member, c, y, x);
+    else return TimeAround(vg, t, o, wraps);
+}
+struct NoFlow {};      // the trailing argument of a launch form without link planes
 // the weight of the temporal link stored at element e: tau * smooth_t, one rounded product (no array: tau)
 __device__ __forceinline__ float time_link(const float *__restrict__ smt, long long e, float tau) { return smt ? rounded_product(tau, smt[e]) : tau; }
 

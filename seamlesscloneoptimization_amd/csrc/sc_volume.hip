@@ -35,21 +35,32 @@ __device__ __forceinline__ bool bad_link(float v) { return !(v > 0.f) || v > 3.4
 // t.w NULL: no data term; t.sx NULL: every spatial link 1; t.smt NULL: every temporal link tau.  LNK false (a call without any link
 // array under free time -- sc_hip_volume's): the links are not looked at, an UNKNOWN - KNOWN link counts 1 or tau, time does not wrap,
 // and a part is the first VOLUME_STATS_PLAIN fields alone; true: every other call, VOLUME_STATS fields per part.
-template <bool LNK>
-__global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, double *__restrict__ stats)
+// FLW (the flow call; LNK with it): the temporal neighbours come from the link planes fl.fwd / fl.bwd, a part is VOLUME_FLOW_STATS fields,
+// the last one the pixel's flow components that are finite and not whole numbers (fa.fx, fa.fy; frames that have a flow only).
+template <bool LNK, bool FLW = false>
+__global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, double *__restrict__ stats,
+                                                      std::conditional_t<FLW, FlowLinks, NoFlow> fl, std::conditional_t<FLW, FlowArrays, NoFlow> fa)
 {
-    constexpr int NS = LNK ? VOLUME_STATS : VOLUME_STATS_PLAIN;
+    constexpr int NS = FLW ? VOLUME_FLOW_STATS : LNK ? VOLUME_STATS : VOLUME_STATS_PLAIN;
     __shared__ double ws[NS][4];
     const PcgBand b(g, wg);
     const float *__restrict__ w = t.w[b.member], *__restrict__ st = t.st[b.member];
     const float *__restrict__ sx = t.sx[b.member], *__restrict__ sy = t.sy[b.member], *__restrict__ smt = t.smt[b.member];
     const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
-    double sw = 0.0, bw = 0.0, nu = 0.0, uk = 0.0, bst = 0.0, ss = 0.0, ns = 0.0, bs = 0.0, sl = 0.0, nt = 0.0, bt = 0.0;
+    double sw = 0.0, bw = 0.0, nu = 0.0, uk = 0.0, bst = 0.0, ss = 0.0, ns = 0.0, bs = 0.0, sl = 0.0, nt = 0.0, bt = 0.0, bfl = 0.0;
     if (b.x < wg.nx)
         for (int y = b.y0; y < b.y1; ++y) {
             const FrameRow fr(vg, y);
             const int X = wg.x0 + b.x, Y = wg.y0 + fr.yy;
             const long long o = b.pixel(g, X, Y) + (long long)fr.t * vg.fs;
+            if constexpr (FLW) {
+                if (fr.t < vg.T - 1 || vg.periodic) {
+                    const size_t e = ((size_t)fr.t * g.H + Y) * g.W + X;
+                    const float vx = fa.fx[b.member][e], vy = fa.fy[b.member][e];
+                    if (vx - vx == 0.f && vx != rintf(vx)) bfl += 1.0;
+                    if (vy - vy == 0.f && vy != rintf(vy)) bfl += 1.0;
+                }
+            }
             const float sv = st[o];
             if (!(sv == 0.f || sv == 1.f || sv == 2.f)) { bst += 1.0; continue; }
             const int kp = state_kind(sv);
@@ -72,7 +83,7 @@ __global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, Vo
                 ns += 1.0;
                 if (kp + kq == NB_KNOWN) uk += (double)s;      // one end UNKNOWN (0), the other KNOWN (1)
             };
-            const TimeAround ta(vg, fr.t, o, LNK);
+            const TimeAround ta = time_around<FLW>(g, wg, vg, fl, b.member, b.c, y, b.x, fr.t, o, LNK);
             const int kf = time_kind(st, ta.of, ta.hf);
             if (!LNK) {
                 if (kp + a.ke == NB_KNOWN) uk += 1.0;
@@ -105,6 +116,7 @@ __global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, Vo
         part_store(nt, ws[9], wg, stats, NS, 9);
         part_store(bt, ws[10], wg, stats, NS, 10);
     }
+    if constexpr (FLW) part_store(bfl, ws[11], wg, stats, NS, 11);
 }
 
 // k_region_setup's walk, frame by frame, and the temporal part.  b in the order the header states: the region call's guidance sum
@@ -115,9 +127,12 @@ __global__ __launch_bounds__(WL) void k_volume_stats(PoissonGeo g, PcgGeo wg, Vo
 // before the folded terms, gx, gy, gt are not read.  LNK false (a call without any link array under free time): every spatial link is 1, every
 // temporal one tau, no link array is looked at and time does not wrap -- the set-up sc_hip_volume always had; true: each array is a uniform pointer test.  1 * g = g and tau * 1 = tau exactly, so arrays of
 // 1.0f give the bytes of no arrays.
-template <bool LAP, bool NOW, bool LNK>
+// FLW (the flow call; LNK with it): "the next frame" is the end of the link this pixel holds, "the previous frame" the source of the link
+// that arrives at it (fl.fwd, fl.bwd) -- whose lt and gt are stored at that source --, F the held link where both ends are UNKNOWN.
+template <bool LAP, bool NOW, bool LNK, bool FLW = false>
 __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, float *__restrict__ R, float *__restrict__ E,
-                                                      float *__restrict__ S, float *__restrict__ F, float *__restrict__ Dg, double *__restrict__ bb)
+                                                      float *__restrict__ S, float *__restrict__ F, float *__restrict__ Dg, double *__restrict__ bb,
+                                                      std::conditional_t<FLW, FlowLinks, NoFlow> fl)
 {
     __shared__ double ws[4];
     const PcgBand bd(g, wg);
@@ -135,7 +150,7 @@ __global__ __launch_bounds__(WL) void k_volume_setup(PoissonGeo g, PcgGeo wg, Vo
             float v = 0.f, e = 0.f, so = 0.f, f = 0.f, dg = 0.f;
             if (st[o] == 0.f) {
                 const Around a(g, wg, st, X, Y, o, px, py);
-                const TimeAround ta(vg, fr.t, o, LNK);
+                const TimeAround ta = time_around<FLW>(g, wg, vg, fl, bd.member, bd.c, y, bd.x, fr.t, o, LNK);
                 const int kb = time_kind(st, ta.ob, ta.hb), kf = time_kind(st, ta.of, ta.hf);
                 const float lw = a.kw == NB_NONE ? 0.f : LNK && sx ? sx[a.ow] : 1.f, le = a.ke == NB_NONE ? 0.f : LNK && sx ? sx[o] : 1.f;
                 const float ln = a.kn == NB_NONE ? 0.f : LNK && sy ? sy[a.on] : 1.f, ls = a.ks == NB_NONE ? 0.f : LNK && sy ? sy[o] : 1.f;
@@ -299,13 +314,21 @@ __global__ __launch_bounds__(WL) void k_volume_out(PoissonGeo g, PcgGeo wg, Volu
     else j.out[o] = j.b[o];
 }
 
-template <bool LNK> void setup_form(bool lap, bool now, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg,
-                                    const VolumeJobs &t, float *R, float *E, float *S, float *F, float *Dg, double *b)
+template <bool LNK, bool FLW = false, class Flow = NoFlow>
+void setup_form(bool lap, bool now, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t, float *R,
+                float *E, float *S, float *F, float *Dg, double *b, const Flow &fl = Flow())
 {
-    if (lap && now) hipLaunchKernelGGL((k_volume_setup<true, true, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
-    else if (lap) hipLaunchKernelGGL((k_volume_setup<true, false, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
-    else if (now) hipLaunchKernelGGL((k_volume_setup<false, true, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
-    else hipLaunchKernelGGL((k_volume_setup<false, false, LNK>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b);
+    if (lap && now) hipLaunchKernelGGL((k_volume_setup<true, true, LNK, FLW>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b, fl);
+    else if (lap) hipLaunchKernelGGL((k_volume_setup<true, false, LNK, FLW>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b, fl);
+    else if (now) hipLaunchKernelGGL((k_volume_setup<false, true, LNK, FLW>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b, fl);
+    else hipLaunchKernelGGL((k_volume_setup<false, false, LNK, FLW>), grid, dim3(WL), 0, s, g, wg, vg, t, R, E, S, F, Dg, b, fl);
+}
+
+// the link planes of volumes i0 .. of a launch
+FlowLinks flow_links_of(const PcgGeo &wg, int i0, const int *fwd, const int *bwd)
+{
+    const long long stride = flow_link_stride(wg);
+    return FlowLinks{ fwd + stride * i0, bwd + stride * i0, stride };
 }
 
 } // namespace
@@ -317,8 +340,32 @@ void launch_volume_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo 
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const bool general = full || t.sx[0] || t.smt[0] || vg.periodic;
         double *st = stats + (size_t)g.C * i0 * PCG_PARTS * (general ? VOLUME_STATS : VOLUME_STATS_PLAIN);
-        if (general) hipLaunchKernelGGL(k_volume_stats<true>, grid, dim3(WL), 0, s, g, wg, vg, t, st);
-        else hipLaunchKernelGGL(k_volume_stats<false>, grid, dim3(WL), 0, s, g, wg, vg, t, st);
+        if (general) hipLaunchKernelGGL(k_volume_stats<true>, grid, dim3(WL), 0, s, g, wg, vg, t, st, NoFlow(), NoFlow());
+        else hipLaunchKernelGGL(k_volume_stats<false>, grid, dim3(WL), 0, s, g, wg, vg, t, st, NoFlow(), NoFlow());
+    });
+}
+
+void launch_volume_flow_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                              const int *fwd, const int *bwd, double *stats, hipStream_t s)
+{
+    static_assert((int)FlowArrays::MAX == (int)VolumeJobs::MAX, "one record of either per volume of a launch");
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
+        const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
+        FlowArrays fa{};
+        for (int i = 0; i < cnt; ++i) fa.set(i, sides[i0 + i]);
+        hipLaunchKernelGGL((k_volume_stats<true, true>), grid, dim3(WL), 0, s, g, wg, vg, t, stats + (size_t)g.C * i0 * PCG_PARTS * VOLUME_FLOW_STATS,
+                           flow_links_of(wg, i0, fwd, bwd), fa);
+    });
+}
+
+void launch_volume_flow_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides,
+                              int m, const int *fwd, const int *bwd, float *R, float *E, float *S, float *F, float *Dg, double *bb, hipStream_t s)
+{
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
+        const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
+        const size_t o = (size_t)g.C * i0 * wg.stride;
+        setup_form<true, true>(lap, !t.w[0], grid, s, g, wg, vg, t, R + o, E + o, S + o, F + o, Dg + o, bb + (size_t)g.C * i0 * PCG_PARTS,
+                               flow_links_of(wg, i0, fwd, bwd));
     });
 }
 

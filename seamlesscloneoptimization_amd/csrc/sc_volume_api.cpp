@@ -26,6 +26,13 @@
 // sc_hip_volume_coupled (its own three entries, last): the robust volume call with a coupling -- SC_VOLUME_COUPLE_SPACE, _TIME, _CHANNELS
 // -- beside the parameters, which the operator takes as launch words (ROBUST_ISO, ROBUST_TIME, ROBUST_JOINT); a round under an effective
 // coupling is two launches (k_volume_robust_rho, k_volume_robust_setup_rho, sc_volume_coupled.hip) with PcgState::rho between them.
+// sc_hip_volume_flow (its own three entries, behind sc_hip_volume_wls's): sc_hip_volume_wls with every temporal link along a flow.
+// VolumeFlowOperator is VolumeOperator with the volumes' link planes (PcgState::lnk; sc_volume_flow.hip: the matching) built in front
+// of the statistics -- and again in front of the set-up where a volume has left, since the planes lie in the order of the volumes that
+// stay --, the statistics and the set-up in their flow forms, k_volume_flow_op, and M^-1 untouched: straight time links.  The two flow
+// arrays come through the front end like every side array (FLOAT_FLOW, PcgCall::flow_floats: dense, no channel axis, their own
+// length) and the call through volume_device_call and pcg_host_call; a volume whose unknowns the link planes' 32 bits cannot index is
+// refused before anything runs (SC_ERR_BAD_SIZE), by sc_hip_volume_flow_check and by a call that carries a flow.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -74,6 +81,8 @@ int volume_validate(const sc_volume_params *p, const sc_poisson_layout *l, const
 }
 
 constexpr const char *METHOD_WHY = "a volume solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
+constexpr const char *FLOW_PAIR_WHY = "flow_x and flow_y go together (both NULL: straight temporal links)";
+constexpr const char *FLOW_SIZE_WHY = "a flow volume solve indexes a volume's unknowns with 32 bits: unknowns per frame * frames must be below 2^31 - 1";
 constexpr const char *FP64_WHY = "a volume solve with SC_FLAG_FFT_FP64: at most 4096 unknowns per axis";
 
 int carries_of(bool weight, bool links, bool tlinks)
@@ -95,7 +104,7 @@ void VolumeOperator::stats(const PoissonGeo &g, const PcgGeo &wg, int m, double 
 const char *VolumeOperator::judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet)
 {
     double job[VOLUME_STATS] = {};
-    const int nf = nstat;      // (a call without link arrays under free time: the link fields do not exist)
+    const int nf = std::min(nstat, (int)VOLUME_STATS);      // (a call without link arrays under free time: the link fields do not exist)
     bool loose = false;
     for (int c = 0; c < g.C; ++c) {      // a plane is the channel's whole volume: the pin check is the volume's, not a frame's
         const double *plane = st + (size_t)c * PCG_PARTS * nstat;
@@ -194,24 +203,107 @@ PcgCall volume_call(int kind, const sc_volume_wls_params *p)
 // the device call of the three families, on any one's jobs (links_of(job): its three link arrays and lap, NULLs where its job has none;
 // Op: the family's operator, made from the call's parameters and what its volumes carry); the data term and the link arrays: all
 // volumes or none, as the first one has them -- smooth_x / smooth_y and smooth_t judged separately; a volume that differs is refused
-// with a reason of its own (as one with exactly one of smooth_x / smooth_y is by the front end)
-struct VolumeLinks { const float *sx, *sy, *smt, *lap; };
+// with a reason of its own (as one with exactly one of smooth_x / smooth_y is by the front end).  The flow call's two flow arrays
+// likewise (call.flow_floats > 0: the first volume has them); exactly one of the two is refused whatever the first volume has.
+struct VolumeLinks { const float *sx, *sy, *smt, *lap, *fx = nullptr, *fy = nullptr; };
 template <class Op, class Params, class Job, class LinksOf>
 int volume_device_call(Instance *I, const PcgCall &call, const Params *p, const sc_poisson_layout *l, Job *jobs, int n, bool bSync, LinksOf links_of,
                        PcgChunkFn chunk = nullptr)
 {
     const VolumeLinks first = jobs && n > 0 ? links_of(jobs[0]) : VolumeLinks{ nullptr, nullptr, nullptr, nullptr };
     const bool weight = jobs && n > 0 && jobs[0].weight, links = first.sx || first.sy, tlinks = first.smt != nullptr;
+    const bool flow = call.flow_floats > 0;
     Op op(I, p, links, tlinks);
-    return pcg_device_call(I, call, l, carries_of(weight, links, tlinks), jobs, n, [=](const Job &j) {
+    return pcg_device_call(I, call, l, carries_of(weight, links, tlinks) | (flow ? FLOAT_FLOW : 0), jobs, n, [=](const Job &j) {
         const VolumeLinks k = links_of(j);
         FloatArrays a{ j.gx, j.gy, k.lap, j.data, j.weight, j.boundary, j.out, k.sx, k.sy, j.state };
         a.gt = j.gt;
         a.smooth_t = k.smt;
+        a.flow_x = k.fx;
+        a.flow_y = k.fy;
         a.refuse = !weight && j.weight ? "a volume has a weight where the first volume of the call has none"
                  : !links && (k.sx || k.sy) ? "a volume has smooth_x / smooth_y where the first volume of the call has none"
-                 : !tlinks && k.smt ? "a volume has smooth_t where the first volume of the call has none" : nullptr;
+                 : !tlinks && k.smt ? "a volume has smooth_t where the first volume of the call has none"
+                 : !k.fx != !k.fy ? FLOW_PAIR_WHY
+                 : !flow && k.fx ? "a volume has a flow where the first volume of the call has none"
+                 : flow && !k.fx ? "a volume has no flow where the first volume of the call has one" : nullptr;
         return a; }, op, bSync, chunk);
+}
+
+// ---- the flow volume call
+struct VolumeFlowOperator final : VolumeOperator {
+    int built = -1;      // the volumes whose link planes stand, in dj's order
+    VolumeFlowOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_)
+        : VolumeOperator(I_, p, links_, tlinks_, 0, OwnStats{ VOLUME_FLOW_STATS }) {}
+    // (the entries have made PcgState::lnk large enough for a chunk: flow_links_ensure)
+    int *fwd() const { return (int *)I->pcg->lnk.p; }
+    int *bwd(const PcgGeo &wg) const { return fwd() + flow_link_stride(wg) * std::max(1, SC_POISSON_MAX_PLANES / (chan * T)); }
+    int chan = 1;        // the call's channels: the planes that share a volume's link planes
+    void begin() override { VolumeOperator::begin(); built = -1; }
+    void match(const PoissonGeo &g, const PcgGeo &wg, int m, hipStream_t s)
+    {
+        chan = g.C;
+        launch_flow_links(g, wg, geo(wg), ds.data(), m, fwd(), bwd(wg), s);
+        built = m;
+    }
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
+    {
+        match(g, wg, m, s);
+        launch_volume_flow_stats(g, wg, geo(wg), dj.data(), ds.data(), m, fwd(), bwd(wg), d_stats, s);
+    }
+    const char *judge(const PoissonGeo &g, int k, const double *st, int parts, bool no_dirichlet) override
+    {
+        double frac = 0.0;
+        for (int c = 0; c < g.C; ++c) frac += stat_sum(st + (size_t)c * PCG_PARTS * nstat, parts, VOLUME_STATS);
+        if (frac != 0.0) return "a flow value is finite and not a whole number";
+        return VolumeOperator::judge(g, k, st, parts, no_dirichlet);
+    }
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
+    {
+        PcgState &S = *I->pcg;
+        int rc;
+        for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
+            if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
+        if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
+        if (mv != built) match(g, wg, mv, I->stream);      // a volume left: dj and ds moved up, the planes follow
+        launch_volume_flow_setup(g, wg, geo(wg), lap, dj.data(), ds.data(), mv, fwd(), bwd(wg), R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p,
+                                 (float *)S.dg.p, bb, I->stream);
+        return SC_OK;
+    }
+    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
+    {
+        PcgState &S = *I->pcg;
+        launch_volume_flow_op(wg, geo(wg), planes, chan, residual, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.f.p,
+                              (const float *)S.dg.p, fwd(), bwd(wg), Q, parts, s);
+    }
+};
+
+// the work planes of a flow call's volume, and the call's own refusal of a size (SC_ERR_BAD_SIZE; SC_OK: none)
+PcgGeo flow_work_geo(const sc_volume_wls_params *p, const sc_poisson_layout *l, int kind)
+{
+    return volume_work_geo(poisson_mixed_geo(poisson_free_sides(kind), l->cols, l->rows, poisson_periodic(kind)), p->frames);
+}
+int volume_flow_validate(const sc_volume_wls_params *p, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    const int rc = volume_wls_validate(p, l, why);
+    if (rc) return rc;
+    if (!flow_indexable(flow_work_geo(p, l, poisson_norm_kind(p->kind)))) { *why = FLOW_SIZE_WHY; return SC_ERR_BAD_SIZE; }
+    return SC_OK;
+}
+// the link planes of one chunk: fwd | bwd, each of as many volumes as a chunk holds at most
+int flow_links_ensure(Instance *I, const sc_volume_wls_params *p, const sc_poisson_layout *l, int kind)
+{
+    const int per = std::max(1, SC_POISSON_MAX_PLANES / (l->channels * p->frames));
+    return ensure(I, I->pcg->lnk, sizeof(int) * 2 * (size_t)flow_link_stride(flow_work_geo(p, l, kind)) * per, false);
+}
+// the call of a volume with a flow: volume_call and the floats of one of its dense flow arrays
+PcgCall volume_flow_call(int kind, const sc_volume_wls_params *p, const sc_poisson_layout *l)
+{
+    PcgCall call = volume_call(kind, p);
+    call.flow_floats = (size_t)call.tframes * (size_t)l->rows * (size_t)l->cols;
+    return call;
 }
 
 // ---- the robust volume call: the volume operator with the links of the current round -- round 0 from the caller's arrays (the WLS
@@ -376,6 +468,47 @@ int sc_hip_volume_wls(void *inst, const sc_volume_wls_params *p, const sc_poisso
     a.gt = gt;
     a.smooth_t = smooth_t;
     return pcg_host_call(I, volume_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op);
+}
+
+int sc_hip_volume_flow_check(const sc_volume_wls_params *p, const sc_poisson_layout *l)
+{
+    return volume_flow_validate(p, l, nullptr);
+}
+
+// (without flow arrays the call is sc_hip_volume_wls: its validation, its operator, its launches)
+int sc_hip_volume_flow_device(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_flow_job *jobs, int n, bool bSync)
+{
+    const bool flow = jobs && n > 0 && (jobs[0].flow_x || jobs[0].flow_y);
+    Instance *I;
+    int kind, rc = flow ? pcg_begin(inst, p, l, volume_flow_validate, METHOD_WHY, FP64_WHY, I, kind)
+                        : pcg_begin(inst, p, l, volume_wls_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    auto links_of = [](const sc_volume_flow_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, j.lap, j.flow_x, j.flow_y }; };
+    if (!flow) return volume_device_call<VolumeOperator>(I, volume_call(kind, p), p, l, jobs, n, bSync, links_of);
+    if ((rc = flow_links_ensure(I, p, l, kind))) return rc;
+    return volume_device_call<VolumeFlowOperator>(I, volume_flow_call(kind, p, l), p, l, jobs, n, bSync, links_of);
+}
+
+int sc_hip_volume_flow(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
+                       const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                       const float *smooth_t, const float *flow_x, const float *flow_y, const float *boundary, float *out)
+{
+    if (!flow_x && !flow_y)
+        return sc_hip_volume_wls(inst, p, l, gx, gy, gt, lap, data, state, weight, smooth_x, smooth_y, smooth_t, boundary, out);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_flow_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial link 1)"; return SC_ERR_BAD_ARG; }
+    if (!flow_x != !flow_y) { I->err = FLOW_PAIR_WHY; return SC_ERR_BAD_ARG; }
+    if ((rc = flow_links_ensure(I, p, l, kind))) return rc;
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    VolumeFlowOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, lap, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    a.flow_x = flow_x;
+    a.flow_y = flow_y;
+    return pcg_host_call(I, volume_flow_call(kind, p, l), l, carries_of(weight != nullptr, links, tlinks) | FLOAT_FLOW, a, op);
 }
 
 int sc_hip_volume_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l)

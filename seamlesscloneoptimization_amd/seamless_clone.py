@@ -645,10 +645,39 @@ def _video_masks(name, masks, frames):
     return m.astype(bool)
 
 
-def inpaint_video(frames, holes, tau=1.0, gpu_id=0, **solver):
+def _flow_of(flow, frames, loop=False):
+    """the rounded flow of a video as volume_flow_planes checks it ((T - 1) x H x W x 2, with loop T; (dx, dy); NaN: no link): float32"""
+    fx, fy = capi.volume_flow_planes(flow, frames.shape[0], frames.shape[1], frames.shape[2], loop)
+    return np.stack([fx, fy], -1)
+
+
+def _along_flow(a, flow, loop=False, wrap=""):
+    """(partner, inside): partner[t][p] = a[t + 1][m_t(p)], the element of the next frame (with loop: of frame 0 behind the last) that
+    the rounded flow leads to from p, and where that target exists -- both components finite and the target inside the frame (an axis
+    named in wrap wraps).  partner is a[t][p] itself where it does not."""
+    T, H, W = a.shape[:3]
+    nxt = np.roll(a, -1, 0) if loop else a[1:]
+    fin = np.isfinite(flow).all(-1) & (np.abs(np.nan_to_num(flow, nan=0.0, posinf=2e6, neginf=-2e6)) <= 1e6).all(-1)
+    f = np.where(fin[..., None], flow, 0).astype(np.int64)
+    yy, xx = np.mgrid[0:H, 0:W]
+    tx, ty = xx[None] + f[..., 0], yy[None] + f[..., 1]
+    if "x" in wrap:
+        tx %= W
+    if "y" in wrap:
+        ty %= H
+    inside = fin & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
+    tt = np.arange(nxt.shape[0])[:, None, None]
+    partner = nxt[tt, np.clip(ty, 0, H - 1), np.clip(tx, 0, W - 1)]
+    sel = inside.reshape(inside.shape + (1,) * (a.ndim - 3))
+    return np.where(sel, partner, a[:nxt.shape[0]]), inside
+
+
+def inpaint_video(frames, holes, tau=1.0, flow=None, gpu_id=0, **solver):
     """Membrane fill of a float32 video (T x H x W or T x H x W x C): inpaint() with temporal links of weight tau.  The pixels where
     holes (T x H x W, anything truthy) is set are filled from the pixels around them in space and time, so a place hidden in one frame is
-    filled from the frames where it is visible, and the fill does not flicker.  Returns a NEW array; pixels outside the holes keep their
+    filled from the frames where it is visible, and the fill does not flicker.  flow ((T - 1) x H x W x 2 of (dx, dy), rounded; NaN: no
+    link): the temporal links follow it -- pixel (x, y) of frame t is joined to pixel (x + dx, y + dy) of frame t + 1 --, so a hole is
+    filled from where its surface point is visible, also when the scene moves.  Returns a NEW array; pixels outside the holes keep their
     bits."""
     if not isinstance(frames, np.ndarray) or frames.dtype != np.float32:
         raise TypeError("frames must be a float32 numpy array")
@@ -658,13 +687,17 @@ def inpaint_video(frames, holes, tau=1.0, gpu_id=0, **solver):
     if h.all():
         raise ValueError("the holes cover every frame: nothing to fill them from")
     state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    if flow is not None:
+        return volume_wls_solve(frames, state, tau=tau, neumann=True, flow=flow, gpu_id=gpu_id, **solver)
     return volume_solve(frames, state, tau=tau, neumann=True, gpu_id=gpu_id, **solver)
 
 
-def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, gpu_id=0, **solver):
+def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, flow=None, gpu_id=0, **solver):
     """poisson_clone on every frame of float32 videos of one shape (T x H x W or T x H x W x C), the frames joined by temporal links of
     weight tau whose guidance is srcs' difference from frame to frame where both frames' masks (T x H x W) are set, 0 elsewhere: the
-    clone follows the source's change over time and does not flicker.  mixed: poisson_clone's, per frame.  Returns a NEW array."""
+    clone follows the source's change over time and does not flicker.  mixed: poisson_clone's, per frame.  flow (inpaint_video's): the
+    links follow it and their guidance is srcs' difference along it, srcs[t + 1][m(p)] - srcs[t][p], where both ends are masked.
+    Returns a NEW array."""
     for name, a in (("srcs", srcs), ("dsts", dsts)):
         if not isinstance(a, np.ndarray) or a.dtype != np.float32:
             raise TypeError(f"{name} must be a float32 numpy array")
@@ -684,6 +717,12 @@ def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, gpu_id=0, **sol
     both = (m[1:] & m[:-1]).reshape(m[1:].shape + (1,) * (srcs.ndim - 3))
     gt = np.where(both, srcs[1:] - srcs[:-1], np.float32(0)).astype(np.float32)
     state = np.where(m, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    if flow is not None:
+        f = _flow_of(flow, dsts)
+        partner, inside = _along_flow(srcs, f)
+        both = (m[:-1] & inside & _along_flow(m, f)[0]).reshape(m[1:].shape + (1,) * (srcs.ndim - 3))
+        gt = np.where(both, partner - srcs[:-1], np.float32(0)).astype(np.float32)
+        return volume_wls_solve(dsts, state, gx=gx, gy=gy, gt=gt, tau=tau, neumann=True, flow=f, gpu_id=gpu_id, **solver)
     return volume_solve(dsts, state, gx=gx, gy=gy, gt=gt, tau=tau, neumann=True, gpu_id=gpu_id, **solver)
 
 
@@ -908,17 +947,27 @@ def make_tileable(image, lam=0.0, axes="xy", gpu_id=0, **solver):
 
 
 def volume_wls_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None,
-                     tau=1.0, loop=False, neumann=True, free_sides=None, periodic="", tol=None, max_iters=None, gpu_id=0, **solver):
+                     tau=1.0, loop=False, neumann=True, free_sides=None, periodic="", tol=None, max_iters=None, flow=None, gpu_id=0, **solver):
     """volume_solve with a weight on every link: per channel it minimises sum_t [sum w (u_t - d_t)^2 + sum smooth_x (d_x u_t - gx_t)^2 +
     sum smooth_y (d_y u_t - gy_t)^2] + sum_t sum tau smooth_t (u_{t+1} - u_t - gt_t)^2.  smooth_x, smooth_y (together; None: 1): T x H x
     W (x C), each at its link's low end as in region_solve.  smooth_t (None: 1) and gt: element [t] belongs to the link from frame t to
     frame t + 1, T - 1 frames.  loop: time is periodic -- frame T - 1 is linked to frame 0 (T >= 3), and smooth_t and gt hold T frames,
-    the last one that link's.  Links must be finite and > 0 where they are live.  Returns a NEW array."""
+    the last one that link's.  Links must be finite and > 0 where they are live.  flow ((T - 1) x H x W x 2, with loop T x H x W x 2, of
+    (dx, dy); rounded with np.rint, NaN kept: no link, an occlusion): the temporal link of pixel (x, y) of frame t leads to pixel (x + dx,
+    y + dy) of frame t + 1 in place of (x, y) -- sc_hip_volume_flow; of several pixels with one target the first in row-major order holds
+    the link; smooth_t and gt stay stored at the link's source.  Strong tau with several pixels of motion needs more iterations: raise
+    max_iters.  None: straight links.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     _, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary = capi.volume_wls_arrays(
         data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau, bool(loop), neumann=neumann, free_sides=free_sides,
         periodic=periodic)
+    if flow is not None:
+        capi.volume_flow_planes(flow, data.shape[0], data.shape[1], data.shape[2], bool(loop))      # (its shape, before a device is touched)
     with _instance(gpu_id, solver) as inst:
+        if flow is not None:
+            return inst.volume_flow(data, state, flow, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau=tau,
+                                    loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, tol=tol or 0.0,
+                                    max_iters=max_iters or 0)
         return inst.volume_wls(data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau=tau, loop=bool(loop),
                                neumann=neumann, free_sides=free_sides, periodic=periodic, tol=tol or 0.0, max_iters=max_iters or 0)
 
@@ -959,12 +1008,14 @@ def wls_filter_video(frames, lam=1.0, alpha=1.2, eps=1e-4, tau=1.0, guide=None, 
                             smooth_t=st, tau=tau, loop=loop, neumann=True, gpu_id=gpu_id, **solver)
 
 
-def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, tau=1.0, hard=True, loop=False, strength=1.0, gpu_id=0, **solver):
+def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, tau=1.0, hard=True, loop=False, strength=1.0, flow=None, gpu_id=0,
+                                  **solver):
     """interpolate_constraints with a guide on a float32 video (T x H x W or T x H x W x C): the values at the pixels where known_mask
     (T x H x W) is set spread through space and time and stop at the guide's edges in both -- every link exp(-d^2 / (2 edge_sigma^2)) +
     1e-3, d the guide's forward difference in x, y or t (edge_sigma None: a tenth of the guide's range).  Scribble, colour or depth
     propagation from a few frames or a few pixels.  hard: the known pixels hold exactly; else they carry the weight `strength`.
-    loop: the last frame is joined to the first.  Returns a NEW array."""
+    loop: the last frame is joined to the first.  flow (volume_wls_solve's): the temporal links follow it, and a link's d is the guide's
+    difference along it, so the values travel with the scene.  Returns a NEW array."""
     values = _video_of("values", values)
     m = _video_masks("known_mask", known_mask, values)
     if guide is None:
@@ -979,7 +1030,13 @@ def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, ta
         raise ValueError("edge_sigma must be finite and > 0 (None: a tenth of the guide's range, which must not be flat)")
     if not m.any():
         raise ValueError("known_mask is empty: nothing to spread")
-    sx, sy, st = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in _video_abs_differences(g, loop))
+    dx, dy, dt = _video_abs_differences(g, loop)
+    if flow is not None:
+        flow = _flow_of(flow, values, loop)
+        g4 = g[:, :, :, None] if g.ndim == 3 else g
+        dt = np.sqrt(((_along_flow(g4, flow, loop)[0] - g4[:flow.shape[0]]) ** 2).sum(3))
+        solver = dict(solver, flow=flow)
+    sx, sy, st = ((np.exp(-d * d / (2.0 * sigma * sigma)) + 1e-3).astype(np.float32) for d in (dx, dy, dt))
     if hard:
         state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
         return volume_wls_solve(values, state, smooth_x=sx, smooth_y=sy, smooth_t=st, tau=tau, loop=loop, neumann=True, gpu_id=gpu_id, **solver)
