@@ -803,7 +803,8 @@ SC_API int sc_hip_robust_device(void *instance, const sc_robust_params *p, const
 SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
                          float *out);
-/* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust* or sc_hip_volume_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+/* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust*, sc_hip_volume_robust*, sc_hip_volume_coupled* or
+ * sc_hip_volume_flow_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
@@ -1236,7 +1237,8 @@ SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, cons
  * Codes: everything sc_hip_volume_wls_check refuses, and SC_ERR_BAD_SIZE as above.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others run -- for
  * every per-job refusal of sc_hip_volume_wls; exactly one of flow_x / flow_y; a flow where the first volume has none, or the reverse; a
  * flow array overlapping out; a finite flow value, where the flow is read, that is not a whole number.
- * Not offered: flow through sc_hip_volume, sc_hip_volume_robust, sc_hip_volume_coupled or the 8-bit entry points; sub-pixel flow (a link
+ * Not offered: flow through sc_hip_volume, sc_hip_volume_coupled or the 8-bit entry points (robust penalties along a flow:
+ * sc_hip_volume_flow_robust below); sub-pixel flow (a link
  * would become a stencil of several points and the matching would not apply); a preconditioner that transforms along the trajectories;
  * links of several pixels onto one; an estimator of the flow. */
 typedef struct sc_volume_flow_job {     /* sc_volume_wls_job and the two flow arrays */
@@ -1296,8 +1298,8 @@ SC_API int sc_hip_volume_flow(void *instance, const sc_volume_wls_params *p, con
  * Laplacian base; SC_ERR_BAD_ARG for SC_ROBUST_ISOTROPIC / SC_ROBUST_JOINT_CHANNELS in kind.  Per job: the WLS volume call's refusals;
  * the first volume decides for weight and for the link arrays.
  * Not offered here: the coupled forms -- kind refuses their bits; sc_hip_volume_coupled below takes a coupling of its own, time
- * included --; anywhere: motion-compensated temporal links, the 8-bit entry points.  A single image with states and robust penalties
- * is sc_hip_region_robust's, which also takes the coupled forms. */
+ * included --, motion-compensated temporal links (sc_hip_volume_flow_robust below); anywhere: the 8-bit entry points.  A single image
+ * with states and robust penalties is sc_hip_region_robust's, which also takes the coupled forms. */
 typedef struct sc_volume_robust_params {
     int       kind;              /* as sc_volume_wls_params.kind; the base must be SC_POISSON_GUIDANCE */
     int       frames;            /* >= 2 (>= 3 with time_periodic); frames * channels <= SC_POISSON_MAX_PLANES */
@@ -1334,6 +1336,60 @@ SC_API int sc_hip_volume_robust_device(void *instance, const sc_volume_robust_pa
 SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                                 const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x,
                                 const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
+/* ---- robust flow volume solves: Lp penalties along a caller's motion field ------------------------------------------------------------------
+ * sc_hip_volume_robust's problem, parameters and rounds, word for word, with every temporal link -- its weight lt = tau * smooth_t, its
+ * guidance gt, its penalty phi_r -- on the matched link of sc_hip_volume_flow.  Per channel the call minimises over the UNKNOWN pixels
+ *     sum w phi_q(u - d; eps_d)  +  sum_live x-links c_x phi_p(dx u - gx; eps_g)  +  sum_live y-links c_y phi_p(dy u - gy; eps_g)
+ *                                +  sum_(matched live links i -> m(i)) c_t(i) phi_r(u(m(i)) - u(i) - gt(i); eps_t).
+ * A wrong flow vector ties two surface points that disagree; under p_time = 1 such a link is down-weighted round by round where the
+ * quadratic link of sc_hip_volume_flow smears across it.  Total-variation denoising of a panning shot that neither blurs along the
+ * motion nor flickers, integrating a video's gradients with gt taken along the flow, robust propagation from keyframes.
+ * The parameters are sc_volume_robust_params, unchanged; coupling bits in kind are refused as there.  flow_x, flow_y, the matching, the
+ * liveness of a matched link, where lt and gt of a link are stored (at its source) and what is read: sc_hip_volume_flow's, word for
+ * word -- gt and smooth_t only where a live matched link has its source, the flow at every pixel of the work rectangle of every frame
+ * it holds and nowhere else.  The matching is built once per chunk and again when a volume leaves the chunk.
+ * Rounds.  Round 0 is sc_hip_volume_flow's system with the caller's arrays and default precond_*, cold-started.  Round k >= 1 is that
+ * system with s = c rho(link residual) on every live link and w' = w rho_q(u - d) at round k - 1's iterate, as in sc_hip_volume_robust;
+ * the residual of a temporal link is t = (u(m(i)) - u(i)) - gt(i), computed by both of its ends with the same bits, so the system stays
+ * symmetric.  One launch (k_volume_flow_robust_setup) and one host read per round.  The means are each round's own and a temporal link
+ * is counted once, at its source.  The preconditioner keeps straight time links (sc_hip_volume_flow: what that costs): a temporal L1
+ * penalty with a small eps_time raises the temporal weights by up to 1 / eps_time where the iterate is flat along the flow, which
+ * together with several pixels of motion is the expensive regime of that section's table.  Raise eps_time or max_iters there.
+ * Ties: flow arrays of zeros give the bytes, the rounds and the inner iteration counts of sc_hip_volume_robust; both arrays NULL (in
+ * every volume) runs sc_hip_volume_robust's launches; p_grad = p_time = p_data = 2 gives the bytes of sc_hip_volume_flow with default
+ * precond_*; link arrays of 1.0f give the bytes of NULL arrays.  Two runs of one call give the same bytes.
+ * Trace, rounds, max_rounds, round_tol, SC_ERR_NOT_CONVERGED, sc_run_info: sc_hip_volume_robust's.  Size: sc_hip_volume_flow's 32-bit rule.
+ * Codes: everything sc_hip_volume_robust_check refuses, then SC_ERR_BAD_SIZE as sc_hip_volume_flow_check.  Per job SC_ERR_BAD_ARG --
+ * nothing of the job is written, the others run -- for every per-job refusal of sc_hip_volume_robust; exactly one of flow_x / flow_y; a
+ * flow where the first volume has none, or the reverse; a flow array overlapping out; a finite flow value, where the flow is read,
+ * that is not a whole number.
+ * Not offered: the coupled forms along a flow, sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points. */
+typedef struct sc_volume_flow_robust_job {   /* sc_volume_robust_job and the two flow arrays, as sc_volume_flow_job has them */
+    const float *gx, *gy;    /* `frames` frames, read at links live in the region: required */
+    const float *gt;         /* frames - 1 frames (time_periodic: frames), read at live matched links; NULL: zeros */
+    const float *data;       /* the values at KNOWN pixels, copied at OUTSIDE ones; d of the data term at UNKNOWN ones when weight is given */
+    const float *state;      /* SC_REGION_UNKNOWN / _KNOWN / _OUTSIDE as 0.0f / 1.0f / 2.0f */
+    const float *weight;     /* w >= 0 at UNKNOWN pixels; NULL: no data term */
+    const float *smooth_x;   /* the base links c > 0 at links live in the region; both NULL: every spatial base link 1 */
+    const float *smooth_y;
+    const float *smooth_t;   /* > 0 at live matched links; NULL: every temporal base link tau */
+    const float *flow_x;     /* dense cols x rows x (frames - 1; time_periodic: frames), whole numbers; both NULL: straight links */
+    const float *flow_y;
+    const float *boundary;   /* its Dirichlet lines in every frame (no Dirichlet line on any side: unused, may be NULL) */
+    float *out;              /* every element the layout names in every frame is written; may equal data or boundary */
+    int rc;                  /* out: SC_OK or SC_ERR_* of this job */
+} sc_volume_flow_robust_job;
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_flow_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_flow_robust_device(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l,
+                                            sc_volume_flow_robust_job *jobs, int n, bool bSync);
+/* One volume on host arrays, the arrays of sc_hip_volume_robust in its order with flow_x, flow_y behind smooth_t -- before boundary
+ * and out, the place sc_hip_volume_flow and both flow job structs give them, not directly in front of out. */
+SC_API int sc_hip_volume_flow_robust(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx,
+                                     const float *gy, const float *gt, const float *data, const float *state, const float *weight,
+                                     const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x,
+                                     const float *flow_y, const float *boundary, float *out);
 /* ---- coupled volume solves: isotropic, space-time and joint-channel total variation on frame stacks ---------------------------------------
  * sc_hip_volume_robust with one penalty over several links, as SC_ROBUST_ISOTROPIC and SC_ROBUST_JOINT_CHANNELS couple them on single
  * images (sc_hip_robust, sc_hip_region_robust) -- and a volume's third axis, which those two bits cannot describe.  The parameters and

@@ -353,6 +353,14 @@ class VolumeRobustJob(C.Structure):
                 ("rc", C.c_int)]
 
 
+# robust flow volume solves (sc_hip_volume_flow_robust*): Instance.volume_flow_robust / volume_flow_robust_device -- VolumeRobustParams
+# themselves; every temporal link, its penalty included, along a flow
+class VolumeFlowRobustJob(C.Structure):
+    _fields_ = [("gx", C.c_void_p), ("gy", C.c_void_p), ("gt", C.c_void_p), ("data", C.c_void_p), ("state", C.c_void_p), ("weight", C.c_void_p),
+                ("smooth_x", C.c_void_p), ("smooth_y", C.c_void_p), ("smooth_t", C.c_void_p), ("flow_x", C.c_void_p), ("flow_y", C.c_void_p),
+                ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
+
+
 # coupled volume solves (sc_hip_volume_coupled*): Instance.volume_coupled / volume_coupled_device -- VolumeRobustParams and VolumeRobustJob
 # themselves, the coupling beside them
 SC_VOLUME_COUPLE_SPACE = 1           # one penalty per pixel over its x- and y-link (per frame isotropic TV)
@@ -607,6 +615,13 @@ def load():
     L.sc_hip_volume_robust_device.restype = C.c_int
     L.sc_hip_volume_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 11
     L.sc_hip_volume_robust.restype = C.c_int
+    L.sc_hip_volume_flow_robust_check.argtypes = [C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_flow_robust_check.restype = C.c_int
+    L.sc_hip_volume_flow_robust_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout),
+                                                   C.POINTER(VolumeFlowRobustJob), C.c_int, C.c_bool]
+    L.sc_hip_volume_flow_robust_device.restype = C.c_int
+    L.sc_hip_volume_flow_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 13
+    L.sc_hip_volume_flow_robust.restype = C.c_int
     L.sc_hip_volume_coupled_check.argtypes = [C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout)]
     L.sc_hip_volume_coupled_check.restype = C.c_int
     L.sc_hip_volume_coupled_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout),
@@ -1142,16 +1157,21 @@ def volume_flow_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_st
                        row_stride=row_stride, channel_stride=channel_stride)
 
 
-def volume_flow_planes(flow, frames: int, rows: int, cols: int, loop: bool = False):
-    """A flow for a volume of `frames` frames of rows x cols pixels as the C layer wants it: (flow_x, flow_y), two C-contiguous float32
-    arrays of shape (frames - 1) x rows x cols -- with loop `frames` of them, the last from the last frame onto frame 0.  flow: a real
-    array of that shape x 2 holding (dx, dy): pixel (x, y) of frame t is pixel (x + dx, y + dy) of frame t + 1.  Values are rounded to
-    whole numbers (np.rint); NaN and the infinities are kept: "no link here" (an occlusion)."""
+def volume_flow_shape(flow, frames: int, rows: int, cols: int, loop: bool = False) -> None:
+    """volume_flow_planes' refusals of a flow's type and shape alone: nothing is converted"""
     if not isinstance(flow, np.ndarray) or not (np.issubdtype(flow.dtype, np.floating) or np.issubdtype(flow.dtype, np.integer)):
         raise TypeError("flow must be a numpy array of real numbers")
     want = ((frames if loop else frames - 1), rows, cols, 2)
     if flow.shape != want:
         raise ValueError(f"flow has shape {flow.shape}, the problem {want}: (dx, dy) per pixel of every frame that has a next one")
+
+
+def volume_flow_planes(flow, frames: int, rows: int, cols: int, loop: bool = False):
+    """A flow for a volume of `frames` frames of rows x cols pixels as the C layer wants it: (flow_x, flow_y), two C-contiguous float32
+    arrays of shape (frames - 1) x rows x cols -- with loop `frames` of them, the last from the last frame onto frame 0.  flow: a real
+    array of that shape x 2 holding (dx, dy): pixel (x, y) of frame t is pixel (x + dx, y + dy) of frame t + 1.  Values are rounded to
+    whole numbers (np.rint); NaN and the infinities are kept: "no link here" (an occlusion)."""
+    volume_flow_shape(flow, frames, rows, cols, loop)
     f = np.rint(flow.astype(np.float32))
     return np.ascontiguousarray(f[..., 0]), np.ascontiguousarray(f[..., 1])
 
@@ -1172,6 +1192,19 @@ def volume_robust_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_
     p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
                            float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
     return _check_call("sc_hip_volume_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_flow_robust_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                             p_grad: float = 1.0, eps_grad: float = 1e-3, p_time: float = 1.0, eps_time: float = 1e-3, p_data: float = 2.0,
+                             eps_data: float = 1e-3, max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0,
+                             layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                             channel_stride=None) -> int:
+    """Host-only sc_hip_volume_flow_robust_check: volume_robust_check's codes, then the flow call's refusal of a volume whose unknowns
+    32 bits cannot index (SC_ERR_BAD_SIZE)."""
+    p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
+                           float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    return _check_call("sc_hip_volume_flow_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
                        row_stride=row_stride, channel_stride=channel_stride)
 
 
@@ -1735,6 +1768,36 @@ class Instance:
         SC_ERR_NOT_CONVERGED is returned, other failures raise unless allow_job_errors (then they are returned as well)."""
         return self._device_call("sc_hip_volume_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
+    # ---- robust flow volume solves on float32 arrays
+    def volume_flow_robust(self, gx, gy, data, state, flow, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,
+                           loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
+                           eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0, allow_not_converged=False):
+        """sc_hip_volume_flow_robust on numpy float32 arrays: volume_robust()'s problem, keywords and result with every temporal link --
+        its weight, its gt, its penalty phi_r -- along `flow` ((T - 1) x H x W x 2, with loop T x H x W x 2, holding (dx, dy);
+        volume_flow_planes' rules: rounded, NaN = no link).  gt and smooth_t stay stored at a link's source pixel.  flow None:
+        volume_robust() itself."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary = volume_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                            gt, boundary, tau, loop, neumann, free_sides, periodic,
+                                                                                            p_grad, eps_grad, p_time, eps_time, p_data, eps_data)
+        fx, fy = (None, None) if flow is None else volume_flow_planes(flow, data.shape[0], data.shape[1], data.shape[2], loop)
+        layout = poisson_layout_of(data[0])
+        p = volume_robust_params(kind, data.shape[0], data[0].size, tau, loop, p_grad, eps_grad, p_time, eps_time, p_data, eps_data, max_rounds,
+                                 round_tol, tol, max_iters)
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_flow_robust(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                              (gx, gy, gt, data, state, weight, sx, sy, smt, fx, fy, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    @staticmethod
+    def make_volume_flow_robust_jobs(n: int):
+        return (VolumeFlowRobustJob * n)()
+
+    def volume_flow_robust_device(self, params: VolumeRobustParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_flow_robust_device: jobs is a VolumeFlowRobustJob array (make_volume_flow_robust_jobs) of device pointers; flow_x,
+        flow_y are dense W x H x (T - 1; periodic time: T) float32 whatever the layout.  Codes as volume_robust_device."""
+        return self._device_call("sc_hip_volume_flow_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
     # ---- coupled volume solves on float32 arrays
     def volume_coupled(self, coupling, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,
                        loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
@@ -1792,7 +1855,7 @@ class Instance:
         return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     def robust_trace(self):
-        """(energy, iters) of the last robust call's last chunk (robust, region_robust or volume_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
+        """(energy, iters) of the last robust call's last chunk (robust, region_robust, volume_robust, volume_coupled or volume_flow_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
         included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
         n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
         energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)

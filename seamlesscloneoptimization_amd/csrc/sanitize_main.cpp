@@ -24,7 +24,8 @@
 //      exponent, every eps, round_tol and tol.
 //      sc_hip_bounded_check: the region call's verdicts under any valid pair of scalar bounds, then lower > upper and a NaN bound.
 //      sc_hip_volume_robust_check: the WLS volume call's verdicts on a guidance base, then every exponent, every eps, round_tol, the coupling
-//      bits, a Laplacian base and the WLS volume call's own refusals.
+//      bits, a Laplacian base and the WLS volume call's own refusals; sc_hip_volume_flow_robust_check beside every one of these calls: the
+//      same parameters, the same verdicts.
 //      sc_hip_volume_coupled_check: every legal coupling accepted, TIME alone and unknown bits refused, unequal p or eps under TIME
 //      refused, the coupling bits in kind still refused.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
@@ -530,47 +531,53 @@ int main()
                 const int fr = tp ? 3 : 2;
                 const sc_volume_robust_params good{ k.kind, fr, span, 1.f, tp, 1.f, 1e-3f, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
                 sc_volume_robust_params vr = good;
-                const int verdict = sc_hip_volume_robust_check(&vr, &l);
+                // sc_hip_volume_flow_robust_check beside every call: the same parameters, the same verdicts (these sizes lie far below the
+                // link planes' 32-bit limit); a verdict that differs is no code at all
+                auto robust_checks = [](const sc_volume_robust_params *vp, const sc_poisson_layout *vl) {
+                    const int v = sc_hip_volume_robust_check(vp, vl);
+                    return sc_hip_volume_flow_robust_check(vp, vl) == v ? v : -1000;
+                };
+                const int verdict = robust_checks(&vr, &l);
                 if (lap_base ? verdict == SC_OK : verdict != k.want) return fail("volume_robust_check");
                 if (lap_base || k.want != SC_OK) continue;
                 for (float bad : { 0.f, -1.f, 2.5f, nan }) {
                     vr = good; vr.p_grad = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_grad)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_grad)");
                     vr = good; vr.p_time = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_time)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_time)");
                     vr = good; vr.p_data = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_data)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (p_data)");
                 }
                 for (float bad : { 0.f, -1.f, nan, inf }) {
                     vr = good; vr.eps_grad = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_grad)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_grad)");
                     vr = good; vr.eps_time = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_time)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_time)");
                     vr = good; vr.p_data = 1.f; vr.eps_data = bad;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_data)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (eps_data)");
                     vr = good; vr.eps_data = bad;          // (an exponent of 2 does not look at its eps)
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_OK) return fail("volume_robust_check (eps_data unused)");
+                    if (robust_checks(&vr, &l) != SC_OK) return fail("volume_robust_check (eps_data unused)");
                 }
                 vr = good; vr.round_tol = nan;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (round_tol)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (round_tol)");
                 vr = good; vr.round_tol = -1.f;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_OK) return fail("volume_robust_check (round_tol < 0)");
+                if (robust_checks(&vr, &l) != SC_OK) return fail("volume_robust_check (round_tol < 0)");
                 for (int bits : { SC_ROBUST_ISOTROPIC, SC_ROBUST_JOINT_CHANNELS, SC_ROBUST_ISOTROPIC | SC_ROBUST_JOINT_CHANNELS }) {
                     vr = good; vr.kind = k.kind | bits;
-                    if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (coupling bits)");
+                    if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (coupling bits)");
                 }
                 vr = good; vr.frames = tp ? 2 : 1;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (too few frames)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (too few frames)");
                 vr = good; vr.frames = SC_POISSON_MAX_PLANES / k.c + 1;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_SIZE) return fail("volume_robust_check (beyond the plane limit)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_SIZE) return fail("volume_robust_check (beyond the plane limit)");
                 vr = good; vr.frame_stride = span - 1;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (frame_stride)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (frame_stride)");
                 vr = good; vr.tau = nan;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tau)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tau)");
                 vr = good; vr.time_periodic = 2;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (time_periodic)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (time_periodic)");
                 vr = good; vr.tol = inf;
-                if (sc_hip_volume_robust_check(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tol)");
+                if (robust_checks(&vr, &l) != SC_ERR_BAD_ARG) return fail("volume_robust_check (tol)");
                 // the coupled volume call: every legal coupling (and none) accepted, TIME alone and unknown bits refused, unequal p or eps
                 // under TIME refused (not without it), the coupling bits in kind still refused, the robust volume call's own refusals kept
                 const int S = SC_VOLUME_COUPLE_SPACE, T = SC_VOLUME_COUPLE_TIME, J = SC_VOLUME_COUPLE_CHANNELS;

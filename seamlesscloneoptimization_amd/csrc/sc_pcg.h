@@ -527,6 +527,13 @@ constexpr int VOLUME_ROBUST_SUMS = 5;
 void launch_volume_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                 const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const float *U, float *R, float *E, float *S,
                                 float *F, float *Dg, double *bb, double *sums, hipStream_t s);
+// the robust flow volume call's launch (sc_volume_flow_robust.hip): launch_volume_robust_setup with the two temporal neighbours of an
+// element read through the volumes' link planes (fwd, bwd as launch_flow_links left them, in the jobs' order) -- the held link's lt and
+// gt at the element itself, the arriving link's at its source, the neighbour's value U[fwd[i]] / U[bwd[i]] where it is UNKNOWN; the
+// same sums, a temporal link counted once at its source
+void launch_volume_flow_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                     const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const int *fwd, const int *bwd,
+                                     const float *U, float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, hipStream_t s);
 // the coupled volume call's two launches (sc_volume_coupled.hip; coupling: ROBUST_ISO | ROBUST_TIME | ROBUST_JOINT, not 0 and effective):
 // k_volume_robust_rho writes rho of every owner's magnitudes to the rho planes and esum as launch_robust_coupled (the gradient-and-time
 // energy's parts; under ROBUST_JOINT on the volume's channel-0 plane only), k_volume_robust_setup_rho is launch_volume_robust_setup with

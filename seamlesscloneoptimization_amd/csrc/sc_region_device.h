@@ -43,6 +43,7 @@ __device__ __forceinline__ int time_kind(const float *__restrict__ st, long long
 struct TimeAround {
     long long ob, of;
     bool hb, hf;
+    int jb = -1, jf = -1;      // the flow form: the two ends as work-plane indices (the links' own words), -1: none
     // wraps false (a launch under free time, known at compile time): one frame before and behind, nothing else is computed
     __device__ __forceinline__ TimeAround(const VolumeGeo &vg, int t, long long o, bool wraps)
     {
@@ -62,7 +63,8 @@ struct TimeAround {
     __device__ __forceinline__ TimeAround(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const FlowLinks &fl, int member, int c, int y, int x)
     {
         const long long lo = (long long)member * fl.stride + ((long long)y * wg.nx + x);
-        const int jb = fl.bwd[lo], jf = fl.fwd[lo], n2 = wg.nx * vg.ny;
+        const int n2 = wg.nx * vg.ny;
+        jb = fl.bwd[lo]; jf = fl.fwd[lo];
         auto offset = [&](int j) {
             const int t = j / n2, r = j - t * n2, y = r / wg.nx, x = r - y * wg.nx;
             return (long long)(wg.x0 + x) * g.cs + (long long)(wg.y0 + y) * g.rs + (long long)c * g.chs + (long long)t * vg.fs;

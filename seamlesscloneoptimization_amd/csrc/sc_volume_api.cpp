@@ -33,6 +33,10 @@
 // arrays come through the front end like every side array (FLOAT_FLOW, PcgCall::flow_floats: dense, no channel axis, their own
 // length) and the call through volume_device_call and pcg_host_call; a volume whose unknowns the link planes' 32 bits cannot index is
 // refused before anything runs (SC_ERR_BAD_SIZE), by sc_hip_volume_flow_check and by a call that carries a flow.
+// sc_hip_volume_flow_robust (its own three entries, behind sc_hip_volume_robust's): the robust volume call with every temporal link --
+// its base weight, its gt, its penalty -- on the flow call's matched link.  VolumeFlowRobustOperator is VolumeFlowOperator (the matching,
+// the statistics and their judgement, round 0's set-up, k_volume_flow_op) with the robust volume operator's rounds, whose launch is
+// k_volume_flow_robust_setup (sc_volume_flow_robust.hip) through the same link planes, re-matched where a volume has left.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -230,11 +234,11 @@ int volume_device_call(Instance *I, const PcgCall &call, const Params *p, const 
         return a; }, op, bSync, chunk);
 }
 
-// ---- the flow volume call
-struct VolumeFlowOperator final : VolumeOperator {
+// ---- the flow volume call (nround_: the sums of a round, for the robust flow call that stands on this operator)
+struct VolumeFlowOperator : VolumeOperator {
     int built = -1;      // the volumes whose link planes stand, in dj's order
-    VolumeFlowOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_)
-        : VolumeOperator(I_, p, links_, tlinks_, 0, OwnStats{ VOLUME_FLOW_STATS }) {}
+    VolumeFlowOperator(Instance *I_, const sc_volume_wls_params *p, bool links_, bool tlinks_, int nround_ = 0)
+        : VolumeOperator(I_, p, links_, tlinks_, nround_, OwnStats{ VOLUME_FLOW_STATS }) {}
     // (the entries have made PcgState::lnk large enough for a chunk: flow_links_ensure)
     int *fwd() const { return (int *)I->pcg->lnk.p; }
     int *bwd(const PcgGeo &wg) const { return fwd() + flow_link_stride(wg) * std::max(1, SC_POISSON_MAX_PLANES / (chan * T)); }
@@ -386,12 +390,62 @@ struct VolumeRobustOperator final : VolumeOperator, RobustRounds {
     void take(const double *t) override { wsum = t[0]; ssum = t[1]; tsum = t[2]; uksum = t[3]; links = tlinks = true; }
 };
 
+// ---- the robust flow volume call: the flow operator -- its matching, statistics, judgement, round 0's set-up and k_volume_flow_op --
+// with the robust volume operator's rounds: a later round's system from the iterate through the link planes
+// (k_volume_flow_robust_setup, sc_volume_flow_robust.hip).  No coupling: the check refuses the bits.
+struct VolumeFlowRobustOperator final : VolumeFlowOperator, RobustRounds {
+    const bool base_links, base_tlinks;
+    VolumeFlowRobustOperator(Instance *I_, const sc_volume_robust_params *p, bool links_, bool tlinks_)
+        : VolumeFlowRobustOperator(I_, p, wls_params_of(p), links_, tlinks_) {}
+    VolumeFlowRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_)
+        : VolumeFlowOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS),
+          RobustRounds(robust_term(p->p_grad, p->eps_grad), robust_term(p->p_data, p->eps_data), robust_term(p->p_time, p->eps_time), p->max_rounds,
+                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS),
+          base_links(links_), base_tlinks(tlinks_) {}
+    RobustRounds *rounds() override { return this; }
+    int coupling(int) const override { return 0; }
+    void begin() override
+    {
+        VolumeFlowOperator::begin();
+        links = base_links;          // round 0 of a new chunk: the caller's arrays again
+        tlinks = base_tlinks;
+    }
+    int launch(PcgChunk &c, int, double *) override
+    {
+        PcgState &S = *I->pcg;
+        if (c.mv != built) match(c.g, c.wg, c.mv, I->stream);      // the planes lie in the order of the volumes that stay
+        launch_volume_flow_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, fwd(), bwd(c.wg), c.U, c.R, (float *)S.e.p,
+                                        (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
+        return SC_OK;
+    }
+    void take(const double *t) override { wsum = t[0]; ssum = t[1]; tsum = t[2]; uksum = t[3]; links = tlinks = true; }
+};
+
 PcgCall volume_robust_call(int kind, const sc_volume_robust_params *p)
 {
     return PcgCall{ kind, p->tol, p->max_iters, 400, p->frames, p->frame_stride, p->time_periodic ? p->frames : p->frames - 1 };
 }
 
 constexpr const char *ROBUST_METHOD_WHY = "a robust volume solve is solved by SC_METHOD_AUTO and SC_METHOD_FFT only (conjugate gradients preconditioned by the direct solve)";
+
+// the robust flow call's check: the robust volume call's, then the flow call's refusal of a size
+int volume_flow_robust_validate(const sc_volume_robust_params *p, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    const int rc = volume_robust_validate(p, l, why);
+    if (rc) return rc;
+    const sc_volume_wls_params q = wls_params_of(p);
+    if (!flow_indexable(flow_work_geo(&q, l, poisson_norm_kind(p->kind)))) { *why = FLOW_SIZE_WHY; return SC_ERR_BAD_SIZE; }
+    return SC_OK;
+}
+// the call of a robust volume with a flow: volume_robust_call and the floats of one of its dense flow arrays
+PcgCall volume_flow_robust_call(int kind, const sc_volume_robust_params *p, const sc_poisson_layout *l)
+{
+    PcgCall call = volume_robust_call(kind, p);
+    call.flow_floats = (size_t)call.tframes * (size_t)l->rows * (size_t)l->cols;
+    return call;
+}
 
 // the coupled call's check: the robust volume call's (coupling bits in kind included), then the coupling's own two refusals
 int volume_coupled_validate(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const char **why)
@@ -539,6 +593,49 @@ int sc_hip_volume_robust(void *inst, const sc_volume_robust_params *p, const sc_
     a.gt = gt;
     a.smooth_t = smooth_t;
     return pcg_host_call(I, volume_robust_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op, robust_chunk);
+}
+
+int sc_hip_volume_flow_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l)
+{
+    return volume_flow_robust_validate(p, l, nullptr);
+}
+
+// (without flow arrays the call is sc_hip_volume_robust: its validation, its operator, its launches)
+int sc_hip_volume_flow_robust_device(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, sc_volume_flow_robust_job *jobs, int n,
+                                     bool bSync)
+{
+    const bool flow = jobs && n > 0 && (jobs[0].flow_x || jobs[0].flow_y);
+    Instance *I;
+    int kind, rc = flow ? pcg_begin(inst, p, l, volume_flow_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind)
+                        : pcg_begin(inst, p, l, volume_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    auto links_of = [](const sc_volume_flow_robust_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, nullptr, j.flow_x, j.flow_y }; };
+    if (!flow) return volume_device_call<VolumeRobustOperator>(I, volume_robust_call(kind, p), p, l, jobs, n, bSync, links_of, robust_chunk);
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = flow_links_ensure(I, &q, l, kind))) return rc;
+    return volume_device_call<VolumeFlowRobustOperator>(I, volume_flow_robust_call(kind, p, l), p, l, jobs, n, bSync, links_of, robust_chunk);
+}
+
+int sc_hip_volume_flow_robust(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
+                              const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                              const float *smooth_t, const float *flow_x, const float *flow_y, const float *boundary, float *out)
+{
+    if (!flow_x && !flow_y) return sc_hip_volume_robust(inst, p, l, gx, gy, gt, data, state, weight, smooth_x, smooth_y, smooth_t, boundary, out);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_flow_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
+    if (!flow_x != !flow_y) { I->err = FLOW_PAIR_WHY; return SC_ERR_BAD_ARG; }
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = flow_links_ensure(I, &q, l, kind))) return rc;
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    VolumeFlowRobustOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    a.flow_x = flow_x;
+    a.flow_y = flow_y;
+    return pcg_host_call(I, volume_flow_robust_call(kind, p, l), l, carries_of(weight != nullptr, links, tlinks) | FLOAT_FLOW, a, op, robust_chunk);
 }
 
 int sc_hip_volume_coupled_check(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l)

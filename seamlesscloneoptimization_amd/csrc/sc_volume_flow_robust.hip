@@ -1,23 +1,20 @@
-// sc_volume_robust.hip -- the robust volume call's one kernel of its own (sc_hip_volume_robust*, sc_volume_api.cpp: VolumeRobustOperator's
-// launch in a reweighting round, which RobustRounds::reweigh in sc_robust_api.cpp describes): k_volume_robust_setup, k_volume_setup
-// (sc_volume.hip) with every link computed from the current iterate as k_robust_setup (sc_robust.hip) computes them.  The system of a
-// round of
-//     minimise  sum w phi_q(u - d) + sum c_x phi_p(dx u - gx) + sum c_y phi_p(dy u - gy) + sum c_t phi_r(u_(t+1) - u_t - gt)
-// over the UNKNOWN pixels of a stack of frames is the WLS volume system with s = c rho(link residual) on every live link and w' = w
-// rho_q(u - d), all at the iterate U on the work plane of stacked frames (sc_volume.hip: its layout).  c_x, c_y: smooth_x, smooth_y
-// (NULL: 1); c_t = lt = tau * smooth_t, one rounded product (NULL: tau).
-// The value of u across a link is NOT the work plane's wherever the neighbour is not UNKNOWN -- u0 = M^-1 b and z = M^-1 r fill the
-// whole rectangle (sc_region.hip) --: it is data's at a KNOWN pixel, boundary's on a Dirichlet line and U's only at an UNKNOWN one.
-// Both ends of a link compute its weight by one expression on the same operands -- t = (u_hi - u_lo) - g, hi / lo by the link's
-// direction, then robust_link -- whichever end evaluates it: the same bits, so E / S / F of one end and the other end's share of Dg
-// agree and L stays symmetric.  Nothing is carried from row to row: every link is computed where it is used (a launch per round
-// against tens of operator launches), so a band may start anywhere inside a frame.
-// The zero condition of the region family holds after every round: R = E = S = F = Dg = 0 at every pixel that is not UNKNOWN, and E,
-// S, F are 0 on a link whose other end is not UNKNOWN.
-// sc_volume_flow_robust.hip holds this kernel's sibling for the robust flow call, k_volume_flow_robust_setup: the same walk, sums and
-// owner rule with the temporal neighbours read through link planes.  A change to either belongs in both.
-// What is read: the header's elements of the WLS volume call -- a link weight and its g only where the link is live, data at UNKNOWN
-// pixels only with a weight -- and U at UNKNOWN pixels.
+// sc_volume_flow_robust.hip -- the robust flow volume call's one kernel of its own (sc_hip_volume_flow_robust*, sc_volume_api.cpp:
+// VolumeFlowRobustOperator's launch in a reweighting round): k_volume_flow_robust_setup, k_volume_robust_setup (sc_volume_robust.hip:
+// the round's system, the value of u across a link, the sums and their owner rule, the zero condition) with the two temporal
+// neighbours of an element taken from the volume's link planes (sc_pcg.h: what they hold; sc_volume_flow.hip: the matching) as
+// k_volume_setup's flow form takes them.  The round's system of
+//     minimise  sum w phi_q(u - d) + sum c_x phi_p(dx u - gx) + sum c_y phi_p(dy u - gy)
+//                                  + sum_(matched live links i -> fwd[i]) c_t(i) phi_r(u[fwd[i]] - u[i] - gt(i))
+// is the flow volume system with s = c rho(link residual) on every live link and w' = w rho_q(u - d) at the iterate U.
+// A temporal link lives at its source: the link element i holds leads to jf = fwd[i], its base weight lt = tau * smooth_t and its gt
+// are stored at i's own offset o; the link that arrives at i comes from jb = bwd[i] and its lt and gt are stored at jb's offset.  A
+// neighbour's kind is state's at the offset TimeAround's flow constructor gives; its value is U[j] where it is UNKNOWN -- a link
+// plane's index IS the work-plane index -- and data's where it is KNOWN.  Both ends compute the link's weight as robust_link(time,
+// base, u_target, u_source, gt_source) on the same operands: F at the source and the target's share of Dg carry the same bits.  The
+// wrap of periodic time is in the indices, so there is no periodic form.
+// Per element beyond k_volume_robust_setup: two int32 loads (the link planes), and in place of the two neighbours one frame away a
+// gather of state, and of U or data, smooth_t and gt, at the two ends -- as coalesced as the flow is smooth.  No atomics, no LDS but
+// the block sums'.
 #include "sc_region_device.h"
 #include <cmath>
 
@@ -25,18 +22,13 @@ namespace sc {
 
 namespace {
 
-// NOW: no weight (w and data at UNKNOWN pixels are not read);  LNK: the call has a base link array (each array then is a uniform
-// pointer test; false: every spatial base link is 1, every temporal one tau, no array is looked at);  PER: periodic time.
-// sums[(plane * PCG_PARTS + part) * VOLUME_ROBUST_SUMS + ..] = the sum of w' | of the live spatial links s | of the live temporal
-// links | of the UNKNOWN - KNOWN links of either kind | the energy of U, in double from the float32 values as robust_phi gives it.
-// Every live link is counted once, under k_volume_stats' owner rule: by its low end (the last pixel of a periodic axis owns the
-// wrapping link, the earlier frame a temporal link, frame T - 1 the wrapping one) whether that end is UNKNOWN or KNOWN, and by its
-// UNKNOWN end where the other lies on a low Dirichlet line.
-template <bool NOW, bool LNK, bool PER>
-__global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, RobustTerm tg, RobustTerm tt, RobustTerm td,
-                                                             const float *__restrict__ U, float *__restrict__ R, float *__restrict__ E,
-                                                             float *__restrict__ S, float *__restrict__ F, float *__restrict__ Dg,
-                                                             double *__restrict__ bb, double *__restrict__ sums)
+// NOW, LNK: k_volume_robust_setup's.  sums: VOLUME_ROBUST_SUMS' fields under its owner rule -- a temporal link is counted once, at
+// its source, whether that end is UNKNOWN or KNOWN.
+template <bool NOW, bool LNK>
+__global__ __launch_bounds__(WL) void k_volume_flow_robust_setup(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, RobustTerm tg, RobustTerm tt,
+                                                                  RobustTerm td, FlowLinks fl, const float *__restrict__ U, float *__restrict__ R,
+                                                                  float *__restrict__ E, float *__restrict__ S, float *__restrict__ F,
+                                                                  float *__restrict__ Dg, double *__restrict__ bb, double *__restrict__ sums)
 {
     __shared__ double ws[VOLUME_ROBUST_SUMS + 1][4];
     lane_term(tg); lane_term(tt); lane_term(td);
@@ -47,7 +39,6 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
     const float *__restrict__ smt = LNK ? t.smt[bd.member] : nullptr;
     const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
     const int nx = wg.nx, fny = vg.ny, x = bd.x;
-    const size_t n2 = (size_t)nx * fny;
     const float *__restrict__ ul = U + (size_t)bd.p * wg.stride;
     const float tau = vg.tau;
     // this lane's column of the five planes it writes: per-lane pointers, so that the planes' bases need no scalar registers inside the walk
@@ -66,13 +57,15 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
             if (kp != NB_NONE) {
                 const bool unk = kp == NB_UNKNOWN;
                 const Around a(g, wg, st, X, Y, o, px, py);
-                const TimeAround ta(vg, fr.t, o, PER);
+                // the ends of the two links of element li: their offsets under the layout, and their work-plane indices (>= 0 where the link exists)
+                const TimeAround ta(g, wg, vg, fl, bd.member, bd.c, y, x);
+                const int jb = ta.jb, jf = ta.jf;
                 const int kb = time_kind(st, ta.ob, ta.hb), kf = time_kind(st, ta.of, ta.hf);
-                // u at this pixel and across a link: U at an UNKNOWN pixel (li: its element of the plane), data at a KNOWN one, boundary on a Dirichlet line
+                // u at this pixel and across a link: U at an UNKNOWN pixel (i: its element of the plane), data at a KNOWN one, boundary on a Dirichlet line
                 auto value = [&](int k, long long off, size_t i) { return k == NB_UNKNOWN ? ul[i] : k == NB_KNOWN ? j.d[off] : j.b[off]; };
                 auto live = [&](int kq) { return kq != NB_NONE && (unk || kq == NB_UNKNOWN); };
                 const float uc = value(kp, o, li);
-                // the links this pixel owns: east, south, forward -- evaluated at a KNOWN low end as well, for the sums
+                // the links this pixel owns: east, south, the held one -- evaluated at a KNOWN low end or source as well, for the sums
                 RobustLink east{ 0.f, 0.0 }, south{ 0.f, 0.0 }, fwd{ 0.f, 0.0 }, west{ 0.f, 0.0 }, north{ 0.f, 0.0 }, back{ 0.f, 0.0 };
                 float g_e = 0.f, g_s = 0.f, g_f = 0.f, g_w = 0.f, g_n = 0.f, g_b = 0.f, u_e = 0.f, u_s = 0.f, u_f = 0.f, u_w = 0.f, u_n = 0.f, u_b = 0.f;
                 if (live(a.ke)) {
@@ -87,9 +80,8 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
                     south = robust_link(tg, sy ? sy[o] : 1.f, u_s, uc, g_s);
                     if (kp + a.ks == NB_KNOWN) s_uk += (double)south.s;
                 }
-                if (live(kf)) {
-                    const size_t i_f = !PER || fr.t < vg.T - 1 ? li + n2 : li - (size_t)(vg.T - 1) * n2;
-                    u_f = value(kf, ta.of, i_f);
+                if (live(kf)) {          // (kf is NB_NONE without a held link: jf >= 0 here)
+                    u_f = value(kf, ta.of, (size_t)jf);
                     g_f = gt ? gt[o] : 0.f;
                     fwd = robust_link(tt, time_link(smt, o, tau), u_f, uc, g_f);
                     if (kp + kf == NB_KNOWN) s_uk += (double)fwd.s;
@@ -108,9 +100,8 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
                         g_n = j.gy[a.on];
                         north = robust_link(tg, sy ? sy[a.on] : 1.f, uc, u_n, g_n);
                     }
-                    if (kb != NB_NONE) {
-                        const size_t i_b = !PER || fr.t > 0 ? li - n2 : li + (size_t)(vg.T - 1) * n2;
-                        u_b = value(kb, ta.ob, i_b);
+                    if (kb != NB_NONE) {     // (an arriving link: jb >= 0; its base weight and gt at its source)
+                        u_b = value(kb, ta.ob, (size_t)jb);
                         g_b = gt ? gt[ta.ob] : 0.f;
                         back = robust_link(tt, time_link(smt, ta.ob, tau), uc, u_b, g_b);
                     }
@@ -164,29 +155,26 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup(PoissonGeo g, PcgGeo
     part_store(s_e, ws[5], wg, sums, VOLUME_ROBUST_SUMS, 4);
 }
 
-template <bool NOW, bool LNK> void robust_form(bool per, dim3 grid, hipStream_t s, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t,
-                                               const RobustTerm &tg, const RobustTerm &tt, const RobustTerm &td, const float *U, float *R, float *E, float *S,
-                                               float *F, float *Dg, double *bb, double *sums)
-{
-    if (per) hipLaunchKernelGGL((k_volume_robust_setup<NOW, LNK, true>), grid, dim3(WL), 0, s, g, wg, vg, t, tg, tt, td, U, R, E, S, F, Dg, bb, sums);
-    else hipLaunchKernelGGL((k_volume_robust_setup<NOW, LNK, false>), grid, dim3(WL), 0, s, g, wg, vg, t, tg, tt, td, U, R, E, S, F, Dg, bb, sums);
-}
-
 } // namespace
 
-void launch_volume_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
-                                const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const float *U, float *R, float *E, float *S,
-                                float *F, float *Dg, double *bb, double *sums, hipStream_t s)
+void launch_volume_flow_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                     const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const int *fwd, const int *bwd,
+                                     const float *U, float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, hipStream_t s)
 {
+    const long long ls = flow_link_stride(wg);
     for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
         const dim3 grid((unsigned)wg.cg, (unsigned)wg.bands, (unsigned)(g.C * cnt));
         const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
-        const bool now = !t.w[0], lnk = t.sx[0] || t.smt[0], per = vg.periodic != 0;
+        const bool now = !t.w[0], lnk = t.sx[0] || t.smt[0];
+        const FlowLinks fl{ fwd + ls * i0, bwd + ls * i0, ls };
         double *b = bb + po, *sm = sums + po * VOLUME_ROBUST_SUMS;
-        if (now && lnk) robust_form<true, true>(per, grid, s, g, wg, vg, t, grad, time, data, U + o, R + o, E + o, S + o, F + o, Dg + o, b, sm);
-        else if (now) robust_form<true, false>(per, grid, s, g, wg, vg, t, grad, time, data, U + o, R + o, E + o, S + o, F + o, Dg + o, b, sm);
-        else if (lnk) robust_form<false, true>(per, grid, s, g, wg, vg, t, grad, time, data, U + o, R + o, E + o, S + o, F + o, Dg + o, b, sm);
-        else robust_form<false, false>(per, grid, s, g, wg, vg, t, grad, time, data, U + o, R + o, E + o, S + o, F + o, Dg + o, b, sm);
+        auto form = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(WL), 0, s, g, wg, vg, t, grad, time, data, fl, U + o, R + o, E + o, S + o, F + o, Dg + o, b, sm);
+        };
+        if (now && lnk) form(k_volume_flow_robust_setup<true, true>);
+        else if (now) form(k_volume_flow_robust_setup<true, false>);
+        else if (lnk) form(k_volume_flow_robust_setup<false, true>);
+        else form(k_volume_flow_robust_setup<false, false>);
     });
 }
 

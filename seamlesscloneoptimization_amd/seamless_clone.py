@@ -1068,7 +1068,7 @@ def make_loop(frames, lam=1e-2, tau=1.0, gpu_id=0, **solver):
 def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0, loop=False,
                         p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None, periodic="",
                         max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False, spacetime=False, joint_channels=False,
-                        **solver):
+                        flow=None, **solver):
     """volume_wls_solve with robust_solve's penalties in place of the squares: per channel it minimises over the UNKNOWN pixels
         sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy) + sum tau smooth_t phi_r(u_{t+1} - u_t - gt),
         phi_e(t) = (2 / e) (t^2 + eps^2)^(e/2),      0 < p, r = p_time, q <= 2,
@@ -1079,9 +1079,16 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     round.  isotropic: one penalty per pixel over its x- and y-link (per frame the isotropic total variation); spacetime: ... and over
     its forward temporal link too (the space-time total variation; implies isotropic and needs p_time == p and eps_time == eps_grad);
     joint_channels: every penalty over the channels of the volume (the vectorial total variation).  With any of the three the call is
-    sc_hip_volume_coupled's.  Returns a NEW array."""
+    sc_hip_volume_coupled's.  flow (volume_wls_solve's: (T - 1) x H x W x 2, with loop T, of (dx, dy), rounded; NaN: no link): every
+    temporal link -- its weight, its gt, its penalty -- joins pixel (x, y) of frame t to pixel (x + dx, y + dy) of frame t + 1, and
+    smooth_t and gt stay stored at the link's source; sc_hip_volume_flow_robust.  A flow goes with none of the three coupled forms: the
+    library has no coupled penalties along a flow.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
+    if flow is not None:
+        if coupling:
+            raise ValueError("flow= goes with none of isotropic, spacetime and joint_channels: coupled penalties along a flow are not offered")
+        capi.volume_flow_shape(flow, np.shape(data)[0], np.shape(data)[1], np.shape(data)[2], bool(loop))       # (before a device is touched)
     if spacetime and (p_time != p or eps_time != eps_grad):
         raise ValueError("spacetime=True is one penalty over space and time: p_time must equal p and eps_time eps_grad")
     args = dict(tau=tau, loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_time=p_time,
@@ -1090,11 +1097,13 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     with _instance(gpu_id, solver) as inst:
         if coupling:
             return inst.volume_coupled(coupling, gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
+        if flow is not None:
+            return inst.volume_flow_robust(gx, gy, data, state, flow, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
         return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
 
 
 def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False,
-                     spacetime=False, joint_channels=False, **solver):
+                     spacetime=False, joint_channels=False, flow=None, **solver):
     """Total-variation denoising of a float32 video (T x H x W or T x H x W x C) that does not flicker: the video u that minimises
         lam sum phi_q(u - frames) + sum phi_p(forward differences of u within a frame) + tau sum phi_r(u_{t+1} - u_t),      r = p_time,
     under reflecting borders -- volume_robust_solve with zero guidance, every state unknown, data = frames and weight = lam.  p = 1 is
@@ -1102,14 +1111,17 @@ def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, l
     eps (in the frames' units) rounds all three penalties off near 0.  loop: the last frame is joined to the first.  isotropic,
     spacetime, joint_channels: volume_robust_solve's coupled forms -- the total variation of the gradient's magnitude per frame (discs
     stay discs), of the space-time gradient's (a moving edge is one surface; needs p_time == p), and over all channels (no colour
-    fringes).  Returns a NEW array."""
+    fringes).  flow (volume_robust_solve's; with none of the three coupled forms): the temporal term is tau sum phi_r(u_{t+1}(x + dx,
+    y + dy) - u_t(x, y)) over the matched pixels, so a panning shot is neither blurred along its motion nor left to flicker.  Returns a
+    NEW array."""
     frames = _video_of("frames", frames)
     if not (np.isfinite(lam) and lam > 0):
         raise ValueError("lam must be finite and > 0")
     zero = np.zeros_like(frames)
     return volume_robust_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), weight=np.full(frames.shape[:3], lam, np.float32), tau=tau,
                                loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True, max_rounds=max_rounds,
-                               round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime, joint_channels=joint_channels, **solver)
+                               round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime, joint_channels=joint_channels, flow=flow,
+                               **solver)
 
 
 def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=False, joint_channels=False, tau=1.0, loop=False, p_time=None,
@@ -1133,13 +1145,15 @@ def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=Fa
 
 
 def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time=1.0, eps=1e-3, anchor=1e-3, loop=False, tau=1.0, max_rounds=None,
-                              round_tol=None, gpu_id=0, **solver):
+                              round_tol=None, gpu_id=0, flow=None, **solver):
     """Integrates a float32 video's gradient field -- gx, gy: forward differences within a frame, T x H x W (x C); gt: from a frame to
     the next, T - 1 frames (loop: T, the last one from frame T - 1 to frame 0) -- into a video with an Lp penalty on the residual of
     every link: p = p_time = 1 (the default) ignores gross outliers in the field (a bad flow vector, a shot cut, a specular frame) that
     a least-squares integration would smear over the video.  known (T x H x W, bool) and values: the pixels that hold exactly (keyframes,
     a lattice of samples).  Neither: the free constant is held by a data term of weight `anchor` towards 0, small enough to leave the
-    shape alone.  Reflecting borders.  eps rounds the penalties off near 0, in the field's units.  Returns a NEW array."""
+    shape alone.  Reflecting borders.  eps rounds the penalties off near 0, in the field's units.  flow (volume_robust_solve's): gt is a
+    difference along the flow -- element (x, y, t) is u_{t+1}(x + dx, y + dy) - u_t(x, y), stored at the link's source.  Returns a NEW
+    array."""
     gx = _video_of("gx", gx)
     if (known is None) != (values is None):
         raise ValueError("known and values go together")
@@ -1148,13 +1162,13 @@ def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time
             raise ValueError("anchor must be finite and > 0")
         return volume_robust_solve(gx, gy, np.zeros_like(gx), np.zeros(gx.shape[:3], np.uint8), gt=gt, weight=np.full(gx.shape[:3], anchor, np.float32),
                                    tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps, neumann=True, max_rounds=max_rounds,
-                                   round_tol=round_tol, gpu_id=gpu_id, **solver)
+                                   round_tol=round_tol, gpu_id=gpu_id, flow=flow, **solver)
     m = _video_masks("known", known, gx)
     if not m.any():
         raise ValueError("known is empty: nothing holds the video")
     state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
     return volume_robust_solve(gx, gy, _video_of("values", values), state, gt=gt, tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps,
-                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, **solver)
+                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, flow=flow, **solver)
 
 
 def region_robust_solve(gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
