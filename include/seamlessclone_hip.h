@@ -803,8 +803,8 @@ SC_API int sc_hip_robust_device(void *instance, const sc_robust_params *p, const
 SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
                          const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
                          float *out);
-/* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust*, sc_hip_volume_robust*, sc_hip_volume_coupled* or
- * sc_hip_volume_flow_robust*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+/* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust*, sc_hip_volume_robust*, sc_hip_volume_coupled*,
+ * sc_hip_volume_flow_robust* or sc_hip_volume_flow_coupled*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
@@ -1237,8 +1237,8 @@ SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, cons
  * Codes: everything sc_hip_volume_wls_check refuses, and SC_ERR_BAD_SIZE as above.  Per job SC_ERR_BAD_ARG -- nothing of the job is written, the others run -- for
  * every per-job refusal of sc_hip_volume_wls; exactly one of flow_x / flow_y; a flow where the first volume has none, or the reverse; a
  * flow array overlapping out; a finite flow value, where the flow is read, that is not a whole number.
- * Not offered: flow through sc_hip_volume, sc_hip_volume_coupled or the 8-bit entry points (robust penalties along a flow:
- * sc_hip_volume_flow_robust below); sub-pixel flow (a link
+ * Not offered: flow through sc_hip_volume or the 8-bit entry points (robust penalties along a flow: sc_hip_volume_flow_robust
+ * below; the coupled forms along a flow: sc_hip_volume_flow_coupled); sub-pixel flow (a link
  * would become a stencil of several points and the matching would not apply); a preconditioner that transforms along the trajectories;
  * links of several pixels onto one; an estimator of the flow. */
 typedef struct sc_volume_flow_job {     /* sc_volume_wls_job and the two flow arrays */
@@ -1363,7 +1363,8 @@ SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p
  * nothing of the job is written, the others run -- for every per-job refusal of sc_hip_volume_robust; exactly one of flow_x / flow_y; a
  * flow where the first volume has none, or the reverse; a flow array overlapping out; a finite flow value, where the flow is read,
  * that is not a whole number.
- * Not offered: the coupled forms along a flow, sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points. */
+ * Not offered: sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points.  The coupled forms along a flow:
+ * sc_hip_volume_flow_coupled below, with these jobs. */
 typedef struct sc_volume_flow_robust_job {   /* sc_volume_robust_job and the two flow arrays, as sc_volume_flow_job has them */
     const float *gx, *gy;    /* `frames` frames, read at links live in the region: required */
     const float *gt;         /* frames - 1 frames (time_periodic: frames), read at live matched links; NULL: zeros */
@@ -1432,8 +1433,8 @@ SC_API int sc_hip_volume_flow_robust(void *instance, const sc_volume_robust_para
  * SC_FLAG_FFT_FP64 limits: sc_hip_volume_robust's.
  * Codes: everything sc_hip_volume_robust_check refuses, coupling bits in kind included; the two refusals of a coupling above.  Per
  * job: the robust volume call's refusals.
- * Not offered: a coupled data term, motion-compensated temporal links (sc_hip_volume_flow has them, without penalties), a separate
- * s-bar for x and y, bounds on volumes, the 8-bit entry points. */
+ * Not offered: a coupled data term, a separate s-bar for x and y, bounds on volumes, the 8-bit entry points.  Motion-compensated
+ * temporal links under a coupling: sc_hip_volume_flow_coupled below, with these parameters and this coupling. */
 #define SC_VOLUME_COUPLE_SPACE    1   /* one penalty per pixel over its x- and y-link (per frame isotropic TV)          */
 #define SC_VOLUME_COUPLE_TIME     2   /* ... and its forward temporal link in the same magnitude (space-time TV)       */
 #define SC_VOLUME_COUPLE_CHANNELS 4   /* every magnitude sums over the channels of a volume (vectorial TV)            */
@@ -1446,6 +1447,53 @@ SC_API int sc_hip_volume_coupled_device(void *instance, const sc_volume_robust_p
 SC_API int sc_hip_volume_coupled(void *instance, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const float *gx,
                                  const float *gy, const float *gt, const float *data, const float *state, const float *weight,
                                  const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *boundary, float *out);
+/* ---- coupled flow volume solves: isotropic, space-time and joint-channel total variation along a caller's motion field --------------------
+ * sc_hip_volume_coupled with every temporal link along a flow: the video total-variation solve when something moves -- isotropic in
+ * space, so that discs stay discs; vectorial, so that there are no colour fringes; and its temporal term compares a surface point
+ * with itself in the next frame.  The parameters are sc_volume_robust_params, the coupling SC_VOLUME_COUPLE_*, the job
+ * sc_volume_flow_robust_job, all unchanged.
+ * Problem.  sc_hip_volume_coupled's energy table, word for word, in which every temporal link is the matched live link i -> m(i) of
+ * sc_hip_volume_flow; its base weight lt = tau * smooth_t and its gt are stored at its source i.  flow_x, flow_y, the matching, the
+ * liveness of a matched link and what is read: sc_hip_volume_flow's, word for word.
+ * Owners and magnitudes.  The owner of a temporal link is its source, the pixel that holds it (not "the earlier frame": under periodic
+ * time and under a flow the target's frame is in the link); spatial owners are sc_hip_volume_coupled's.  Under SPACE | TIME a pixel's
+ * magnitude is (a_x + a_y) + a_t with a_t that of the link the pixel holds; a pixel that holds no live link -- occluded (NaN), the
+ * loser of a collision's claim, its target off the rectangle, or a dead end -- has a_t add nothing.  A link that arrives at a pixel
+ * plays no part in that pixel's magnitude.  Under CHANNELS a magnitude sums the channels in which that link is live: the matching is
+ * per volume, liveness per channel.  TIME without CHANNELS or SPACE | TIME leaves the temporal link its uncoupled penalty c_t phi_r,
+ * exactly as in sc_hip_volume_coupled.
+ * Float32 order: sc_hip_volume_coupled's -- t t rounded, then times c rounded; (a_x + a_y) + a_t; then the running sum over channels
+ * 0 .. C - 1.  The residual of a temporal link is t = (u(m(i)) - u(i)) - gt(i), computed on the same operands by whoever needs it.  Both
+ * ends of every link read the same rho bits from the rho planes, so the system stays symmetric: a temporal link's rho is written once,
+ * by its source, at the source's element, and the pixel it arrives at reads it there, through the matching's backward index.
+ * Rounds.  Round 0 is sc_hip_volume_flow's system with the caller's arrays and default precond_*, cold-started.  Round k >= 1 is as in
+ * sc_hip_volume_coupled, with the means counted as sc_hip_volume_flow_robust counts them: a temporal link once, at its source.  Two
+ * launches (k_volume_flow_robust_rho, k_volume_flow_robust_setup_rho) and one host read per coupled round; the matching is built once
+ * per chunk and again when a volume leaves the chunk.  The rho planes: sc_hip_volume_coupled's.
+ * Effective coupling: sc_hip_volume_coupled's rule.  A call whose effective coupling is 0 runs k_volume_flow_robust_setup and writes the
+ * bytes of sc_hip_volume_flow_robust.
+ * The preconditioner keeps straight time links (sc_hip_volume_flow: what that costs): a temporal or space-time L1 penalty with a small
+ * eps raises the temporal weights by up to 1 / eps where the iterate is flat along the flow, which together with several pixels of
+ * motion is the expensive regime of that section's table.  Raise eps or max_iters there.
+ * Ties, to the byte (the first two also in the trace's rounds and inner iteration counts): flow arrays of zeros (-0.0f among them)
+ * give sc_hip_volume_coupled's result; both flow arrays NULL in every volume runs sc_hip_volume_coupled's launches; every exponent 2
+ * gives the bytes of sc_hip_volume_flow with default precond_*; link arrays of 1.0f give the bytes of NULL arrays; two runs give the
+ * same bytes.
+ * Trace (sc_hip_robust_trace reports this call too), round rule, max_rounds, round_tol, SC_ERR_NOT_CONVERGED, sc_run_info, chunks,
+ * methods, SC_FLAG_FFT_FP64 limits: sc_hip_volume_coupled's.  Size: sc_hip_volume_flow's 32-bit rule.
+ * Codes: everything sc_hip_volume_coupled_check refuses, then SC_ERR_BAD_SIZE as sc_hip_volume_flow_check gives it.  Per job:
+ * sc_hip_volume_flow_robust's refusals.
+ * Not offered: a coupled data term, sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points. */
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters, this coupling and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_flow_coupled_check(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_flow_coupled_device(void *instance, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l,
+                                             sc_volume_flow_robust_job *jobs, int n, bool bSync);
+/* One volume on host arrays, the arrays of sc_hip_volume_flow_robust in its order. */
+SC_API int sc_hip_volume_flow_coupled(void *instance, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const float *gx,
+                                      const float *gy, const float *gt, const float *data, const float *state, const float *weight,
+                                      const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x,
+                                      const float *flow_y, const float *boundary, float *out);
 /* Host-only: what decides a ROI size's class: out = { eligible, levels, level held by k_mg_tail (THE class key, beside the 2x spread),
  * operand padding x, y of the level solved directly, mode-block padding x, y of the correction, its column tiles, its row splits,
  * 1000 * nx + ny of the level solved directly, solo_differs (1: a small ROI whose level 1 a solo clone solves directly -- inside a

@@ -10,7 +10,7 @@ from .seamless_clone import (SeamlessClone, colorChange, edit_batch, gradient_fi
                              textureFlattening, weighted_solve, weighted_solve_batch, wls_filter, wls_solve, wls_solve_batch, robust_solve,
                              robust_solve_batch, tv_denoise, integrate_gradients, region_solve, region_solve_batch, inpaint, poisson_clone, volume_solve, inpaint_video,
                              poisson_clone_video, volume_wls_solve, wls_filter_video, interpolate_constraints_video, make_loop,
-                             volume_robust_solve, tv_denoise_video, tv_inpaint_video, integrate_gradients_video, region_robust_solve, region_robust_solve_batch,
+                             volume_robust_solve, volume_flow_coupled_solve, tv_denoise_video, tv_denoise_video_along_flow, tv_inpaint_video, integrate_gradients_video, region_robust_solve, region_robust_solve_batch,
                              tv_inpaint, integrate_gradients_masked, bounded_solve, bounded_solve_batch, poisson_clone_in_range,
                              interpolate_in_range)
 
@@ -20,6 +20,6 @@ __all__ = ["capi", "compare", "ymlio", "SeamlessClone", "seamlessClone", "colorC
            "wls_solve_batch", "wls_filter", "robust_solve", "robust_solve_batch", "tv_denoise", "integrate_gradients",
            "region_solve", "region_solve_batch", "inpaint", "poisson_clone", "volume_solve", "inpaint_video", "poisson_clone_video",
            "volume_wls_solve", "wls_filter_video", "interpolate_constraints_video", "make_loop",
-           "volume_robust_solve", "tv_denoise_video", "tv_inpaint_video", "integrate_gradients_video", "region_robust_solve", "region_robust_solve_batch",
+           "volume_robust_solve", "volume_flow_coupled_solve", "tv_denoise_video", "tv_denoise_video_along_flow", "tv_inpaint_video", "integrate_gradients_video", "region_robust_solve", "region_robust_solve_batch",
            "tv_inpaint", "integrate_gradients_masked", "bounded_solve", "bounded_solve_batch", "poisson_clone_in_range",
            "interpolate_in_range"]

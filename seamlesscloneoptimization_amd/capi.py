@@ -362,7 +362,8 @@ class VolumeFlowRobustJob(C.Structure):
 
 
 # coupled volume solves (sc_hip_volume_coupled*): Instance.volume_coupled / volume_coupled_device -- VolumeRobustParams and VolumeRobustJob
-# themselves, the coupling beside them
+# themselves, the coupling beside them; along a flow (sc_hip_volume_flow_coupled*): Instance.volume_flow_coupled /
+# volume_flow_coupled_device, with VolumeFlowRobustJob
 SC_VOLUME_COUPLE_SPACE = 1           # one penalty per pixel over its x- and y-link (per frame isotropic TV)
 SC_VOLUME_COUPLE_TIME = 2            # ... and its forward temporal link in the same magnitude (space-time TV); comes with SPACE
 SC_VOLUME_COUPLE_CHANNELS = 4        # every magnitude sums over the channels of a volume (vectorial TV)
@@ -629,6 +630,13 @@ def load():
     L.sc_hip_volume_coupled_device.restype = C.c_int
     L.sc_hip_volume_coupled.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout)] + [C.c_void_p] * 11
     L.sc_hip_volume_coupled.restype = C.c_int
+    L.sc_hip_volume_flow_coupled_check.argtypes = [C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_flow_coupled_check.restype = C.c_int
+    L.sc_hip_volume_flow_coupled_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout),
+                                                    C.POINTER(VolumeFlowRobustJob), C.c_int, C.c_bool]
+    L.sc_hip_volume_flow_coupled_device.restype = C.c_int
+    L.sc_hip_volume_flow_coupled.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout)] + [C.c_void_p] * 13
+    L.sc_hip_volume_flow_coupled.restype = C.c_int
     L.sc_hip_region_robust_check.argtypes = [C.POINTER(RobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_region_robust_check.restype = C.c_int
     L.sc_hip_region_robust_device.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.POINTER(PoissonLayout), C.POINTER(RegionRobustJob), C.c_int,
@@ -1235,6 +1243,20 @@ def volume_coupled_check(coupling: int, kind: int = SC_POISSON_GUIDANCE, frames:
     return int(load().sc_hip_volume_coupled_check(C.byref(p), int(coupling), C.byref(layout)))
 
 
+def volume_flow_coupled_check(coupling: int, kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0,
+                              time_periodic: int = 0, p_grad: float = 1.0, eps_grad: float = 1e-3, p_time: float = 1.0, eps_time: float = 1e-3,
+                              p_data: float = 2.0, eps_data: float = 1e-3, max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0,
+                              max_iters: int = 0, layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None,
+                              row_stride=None, channel_stride=None) -> int:
+    """Host-only sc_hip_volume_flow_coupled_check: volume_coupled_check's codes, then the flow call's refusal of a volume whose unknowns
+    32 bits cannot index (SC_ERR_BAD_SIZE)."""
+    p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
+                           float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    if layout is None:
+        layout = PoissonLayout(*(int(v) for v in (cols, rows, channels, col_stride, row_stride, channel_stride)))
+    return int(load().sc_hip_volume_flow_coupled_check(C.byref(p), int(coupling), C.byref(layout)))
+
+
 def robust_check(kind: int = SC_POISSON_GUIDANCE, p_grad: float = 1.0, eps_grad: float = 1e-3, p_data: float = 2.0, eps_data: float = 1e-3,
                  max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0, layout: "PoissonLayout | None" = None, *,
                  cols=None, rows=None, channels=None, col_stride=None, row_stride=None, channel_stride=None, isotropic=False,
@@ -1827,6 +1849,41 @@ class Instance:
             return rc
         return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
 
+    # ---- coupled flow volume solves on float32 arrays
+    def volume_flow_coupled(self, coupling, gx, gy, data, state, flow, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None,
+                            boundary=None, tau=1.0, loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0,
+                            eps_time=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0, allow_not_converged=False):
+        """sc_hip_volume_flow_coupled on numpy float32 arrays: volume_coupled()'s problem, coupling, keywords and result with every temporal
+        link -- its weight, its gt, its share of a magnitude -- along `flow` ((T - 1) x H x W x 2, with loop T x H x W x 2, holding (dx,
+        dy); volume_flow_planes' rules: rounded, NaN = no link).  A temporal link belongs to its source pixel: gt, smooth_t and, under
+        SC_VOLUME_COUPLE_TIME, its place in a magnitude.  flow None: volume_coupled() itself; coupling 0: volume_flow_robust()'s bytes."""
+        if flow is None:
+            return self.volume_coupled(coupling, gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, tau, loop, neumann,
+                                       free_sides, periodic, p_grad, eps_grad, p_time, eps_time, p_data, eps_data, max_rounds, round_tol, tol,
+                                       max_iters, allow_not_converged)
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary = volume_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                            gt, boundary, tau, loop, neumann, free_sides, periodic,
+                                                                                            p_grad, eps_grad, p_time, eps_time, p_data, eps_data)
+        fx, fy = volume_flow_planes(flow, data.shape[0], data.shape[1], data.shape[2], loop)
+        layout = poisson_layout_of(data[0])
+        p = volume_robust_params(kind, data.shape[0], data[0].size, tau, loop, p_grad, eps_grad, p_time, eps_time, p_data, eps_data, max_rounds,
+                                 round_tol, tol, max_iters)
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_flow_coupled(self.h, C.byref(p), int(coupling), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                               (gx, gy, gt, data, state, weight, sx, sy, smt, fx, fy, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    def volume_flow_coupled_device(self, params: VolumeRobustParams, coupling: int, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_flow_coupled_device: volume_flow_robust_device() with a coupling (SC_VOLUME_COUPLE_*); jobs from
+        make_volume_flow_robust_jobs."""
+        rc = self.L.sc_hip_volume_flow_coupled_device(self.h, C.byref(params), int(coupling), C.byref(layout), jobs, len(jobs), bool(sync))
+        if sync:
+            self.sync()
+        if allow_job_errors and rc != SC_ERR_HIP:
+            return rc
+        return self._check(rc, allow=(SC_ERR_NOT_CONVERGED,))
+
     # ---- robust solves on float32 arrays
     def robust(self, gx, gy, data, weight, smooth_x=None, smooth_y=None, boundary=None, neumann=False, out=None, free_sides="", periodic="",
                p_grad=1.0, eps_grad=1e-3, p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0,
@@ -1855,7 +1912,7 @@ class Instance:
         return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     def robust_trace(self):
-        """(energy, iters) of the last robust call's last chunk (robust, region_robust, volume_robust, volume_coupled or volume_flow_robust, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
+        """(energy, iters) of the last robust call's last chunk (robust, region_robust, volume_robust, volume_coupled, volume_flow_robust or volume_flow_coupled, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
         included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
         n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
         energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)

@@ -27,7 +27,8 @@
 //      bits, a Laplacian base and the WLS volume call's own refusals; sc_hip_volume_flow_robust_check beside every one of these calls: the
 //      same parameters, the same verdicts.
 //      sc_hip_volume_coupled_check: every legal coupling accepted, TIME alone and unknown bits refused, unequal p or eps under TIME
-//      refused, the coupling bits in kind still refused.
+//      refused, the coupling bits in kind still refused; sc_hip_volume_flow_coupled_check beside every one of these calls: the same
+//      parameters and coupling, the same verdicts.
 //   8. sc_hip_fused_schedule: the schedule of a fused multigrid solve's level-0 launches over a few hundred facts and verdict lists.
 //   9. sc_hip_restore_spans: a frame-only restore's byte spans applied to heap buffers of exactly the image's size.
 //  10. a job's side arrays (SideArrays; sc_instance.h, sc_pcg.h): for_side_tables fills every family's table, 20 jobs as 16 + 4, each
@@ -581,23 +582,28 @@ int main()
                 // the coupled volume call: every legal coupling (and none) accepted, TIME alone and unknown bits refused, unequal p or eps
                 // under TIME refused (not without it), the coupling bits in kind still refused, the robust volume call's own refusals kept
                 const int S = SC_VOLUME_COUPLE_SPACE, T = SC_VOLUME_COUPLE_TIME, J = SC_VOLUME_COUPLE_CHANNELS;
+                // sc_hip_volume_flow_coupled_check beside every call, as above: the same parameters and coupling, the same verdicts
+                auto coupled_checks = [](const sc_volume_robust_params *vp, int cpl, const sc_poisson_layout *vl) {
+                    const int v = sc_hip_volume_coupled_check(vp, cpl, vl);
+                    return sc_hip_volume_flow_coupled_check(vp, cpl, vl) == v ? v : -1000;
+                };
                 for (int cpl : { 0, S, S | T, J, S | J, S | T | J }) {
                     vr = good;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != SC_OK) return fail("volume_coupled_check (a legal coupling)");
+                    if (coupled_checks(&vr, cpl, &l) != SC_OK) return fail("volume_coupled_check (a legal coupling)");
                     vr.kind = k.kind | SC_ROBUST_ISOTROPIC;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (coupling bits in kind)");
+                    if (coupled_checks(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (coupling bits in kind)");
                     vr = good; vr.p_data = 2.5f;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (p_data)");
+                    if (coupled_checks(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (p_data)");
                     vr = good; vr.frame_stride = span - 1;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (frame_stride)");
+                    if (coupled_checks(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (frame_stride)");
                     vr = good; vr.p_time = 1.5f;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != ((cpl & T) ? SC_ERR_BAD_ARG : SC_OK)) return fail("volume_coupled_check (p_time != p_grad)");
+                    if (coupled_checks(&vr, cpl, &l) != ((cpl & T) ? SC_ERR_BAD_ARG : SC_OK)) return fail("volume_coupled_check (p_time != p_grad)");
                     vr = good; vr.eps_time = 2e-3f;
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != ((cpl & T) ? SC_ERR_BAD_ARG : SC_OK)) return fail("volume_coupled_check (eps_time != eps_grad)");
+                    if (coupled_checks(&vr, cpl, &l) != ((cpl & T) ? SC_ERR_BAD_ARG : SC_OK)) return fail("volume_coupled_check (eps_time != eps_grad)");
                 }
                 vr = good;
                 for (int cpl : { T, T | J, 8, S | 8, -1, 1 << 20 })
-                    if (sc_hip_volume_coupled_check(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (an illegal coupling)");
+                    if (coupled_checks(&vr, cpl, &l) != SC_ERR_BAD_ARG) return fail("volume_coupled_check (an illegal coupling)");
             }
             // the robust call: the WLS call's verdict on a guidance base, SC_ERR_BAD_ARG on a Laplacian one and on a bad exponent or eps
             sc_robust_params r{ k.kind, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };

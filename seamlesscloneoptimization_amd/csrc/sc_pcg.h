@@ -560,6 +560,15 @@ inline size_t volume_rho_floats(const VolumeRhoGeo &rg, int C, int m, int coupli
 void launch_volume_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                   const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, int coupling, const float *U, float *Rho,
                                   float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, double *esum, hipStream_t s);
+// the coupled flow volume call's two launches (sc_volume_flow_coupled.hip): launch_volume_robust_coupled with the temporal neighbours of
+// an element read through the volumes' link planes (fwd, bwd as launch_flow_links left them, in the jobs' order).  The owner of a
+// temporal link is its source: its rho is written at the source's own [frame][Y][X] element of the t-component (under ROBUST_TIME: of
+// the one component, with the source's spatial links in the magnitude) and read there by the pixel it arrives at, through bwd.  The
+// same rho planes, sums and esum; a temporal link is counted once, at its source.
+void launch_volume_flow_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides,
+                                       int m, const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, int coupling, const int *fwd,
+                                       const int *bwd, const float *U, float *Rho, float *R, float *E, float *S, float *F, float *Dg, double *bb,
+                                       double *sums, double *esum, hipStream_t s);
 // k_wls_setup with s = c rho_p(link residual of U), w' = w rho_q(U - d) (c = sx, sy; NULL for every job: 1): R = b, E, S, Dg as
 // launch_wls_setup in its guidance form, bb = the parts of b . b, sums[(plane * PCG_PARTS + i) * ROBUST_SUMS + ..] = the part's sum of
 // w' | the sum of its live links s, each counted once as launch_wls_stats counts them | the energy of U

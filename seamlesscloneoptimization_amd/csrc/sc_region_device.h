@@ -85,4 +85,11 @@ struct NoFlow {};      // the trailing argument of a launch form without link pl
 // the weight of the temporal link stored at element e: tau * smooth_t, one rounded product (no array: tau)
 __device__ __forceinline__ float time_link(const float *__restrict__ smt, long long e, float tau) { return smt ? rounded_product(tau, smt[e]) : tau; }
 
+// a link's share of a magnitude: c t^2, the square rounded, then the product (c NULL: no multiply)
+__device__ __forceinline__ float coupled_sq(const float *__restrict__ c, long long o, float t)
+{
+    const float q = rounded_product(t, t);
+    return c ? rounded_product(c[o], q) : q;
+}
+
 } // namespace sc

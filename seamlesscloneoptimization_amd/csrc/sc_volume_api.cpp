@@ -392,28 +392,47 @@ struct VolumeRobustOperator final : VolumeOperator, RobustRounds {
 
 // ---- the robust flow volume call: the flow operator -- its matching, statistics, judgement, round 0's set-up and k_volume_flow_op --
 // with the robust volume operator's rounds: a later round's system from the iterate through the link planes
-// (k_volume_flow_robust_setup, sc_volume_flow_robust.hip).  No coupling: the check refuses the bits.
+// (k_volume_flow_robust_setup, sc_volume_flow_robust.hip).  The robust flow call has no coupling: its check refuses the bits; the
+// coupled flow call's words come beside the parameters as the coupled call's do (VolumeCoupledParams), and a round under an effective
+// coupling is the two launches of sc_volume_flow_coupled.hip.
 struct VolumeFlowRobustOperator final : VolumeFlowOperator, RobustRounds {
     const bool base_links, base_tlinks;
     VolumeFlowRobustOperator(Instance *I_, const sc_volume_robust_params *p, bool links_, bool tlinks_)
-        : VolumeFlowRobustOperator(I_, p, wls_params_of(p), links_, tlinks_) {}
-    VolumeFlowRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_)
-        : VolumeFlowOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS),
+        : VolumeFlowRobustOperator(I_, p, wls_params_of(p), links_, tlinks_, 0) {}
+    VolumeFlowRobustOperator(Instance *I_, const VolumeCoupledParams *c, bool links_, bool tlinks_)
+        : VolumeFlowRobustOperator(I_, c->p, wls_params_of(c->p), links_, tlinks_, c->bits) {}
+    VolumeFlowRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, bool links_, bool tlinks_, int words)
+        : VolumeFlowOperator(I_, &q, links_, tlinks_, VOLUME_ROBUST_SUMS + (words ? 1 : 0)),
           RobustRounds(robust_term(p->p_grad, p->eps_grad), robust_term(p->p_data, p->eps_data), robust_term(p->p_time, p->eps_time), p->max_rounds,
-                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS),
+                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS, words),
           base_links(links_), base_tlinks(tlinks_) {}
     RobustRounds *rounds() override { return this; }
-    int coupling(int) const override { return 0; }
+    // VolumeRobustOperator::coupling's rule
+    int coupling(int C) const override
+    {
+        int b = bits;
+        if (grad.mode == 0) b &= ~(ROBUST_ISO | ROBUST_TIME);
+        if (C == 1 || (grad.mode == 0 && time.mode == 0)) b &= ~ROBUST_JOINT;
+        return b;
+    }
     void begin() override
     {
         VolumeFlowOperator::begin();
         links = base_links;          // round 0 of a new chunk: the caller's arrays again
         tlinks = base_tlinks;
     }
-    int launch(PcgChunk &c, int, double *) override
+    int launch(PcgChunk &c, int cpl, double *esum) override
     {
         PcgState &S = *I->pcg;
         if (c.mv != built) match(c.g, c.wg, c.mv, I->stream);      // the planes lie in the order of the volumes that stay
+        if (cpl) {
+            const VolumeGeo vg = geo(c.wg);
+            const int rc = ensure(I, S.rho, sizeof(float) * volume_rho_floats(volume_rho_geo(c.wg, vg, grad, time, cpl), c.g.C, c.mv, cpl), false);
+            if (rc) return rc;
+            launch_volume_flow_robust_coupled(c.g, c.wg, vg, dj.data(), ds.data(), c.mv, grad, time, data, cpl, fwd(), bwd(c.wg), c.U, (float *)S.rho.p,
+                                              c.R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, esum, I->stream);
+            return SC_OK;
+        }
         launch_volume_flow_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, fwd(), bwd(c.wg), c.U, c.R, (float *)S.e.p,
                                         (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
         return SC_OK;
@@ -459,6 +478,18 @@ int volume_coupled_validate(const sc_volume_robust_params *p, int coupling, cons
                     : ((coupling & SC_VOLUME_COUPLE_TIME) && (p->p_time != p->p_grad || p->eps_time != p->eps_grad))
                         ? "SC_VOLUME_COUPLE_TIME is one penalty: p_time must equal p_grad and eps_time eps_grad" : nullptr;
     if (own) { *why = own; return SC_ERR_BAD_ARG; }
+    return SC_OK;
+}
+
+// the coupled flow call's check: the coupled call's, then the flow call's refusal of a size
+int volume_flow_coupled_validate(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const char **why)
+{
+    const char *dummy;
+    if (!why) why = &dummy;
+    const int rc = volume_coupled_validate(p, coupling, l, why);
+    if (rc) return rc;
+    const sc_volume_wls_params q = wls_params_of(p);
+    if (!flow_indexable(flow_work_geo(&q, l, poisson_norm_kind(p->kind)))) { *why = FLOW_SIZE_WHY; return SC_ERR_BAD_SIZE; }
     return SC_OK;
 }
 
@@ -671,6 +702,53 @@ int sc_hip_volume_coupled(void *inst, const sc_volume_robust_params *p, int coup
     a.gt = gt;
     a.smooth_t = smooth_t;
     return pcg_host_call(I, volume_robust_call(kind, p), l, carries_of(weight != nullptr, links, tlinks), a, op, robust_chunk);
+}
+
+int sc_hip_volume_flow_coupled_check(const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l)
+{
+    return volume_flow_coupled_validate(p, coupling, l, nullptr);
+}
+
+// (without flow arrays the call is sc_hip_volume_coupled: its validation, its operator, its launches)
+int sc_hip_volume_flow_coupled_device(void *inst, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l,
+                                      sc_volume_flow_robust_job *jobs, int n, bool bSync)
+{
+    const bool flow = jobs && n > 0 && (jobs[0].flow_x || jobs[0].flow_y);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, [coupling, flow](const sc_volume_robust_params *q, const sc_poisson_layout *m, const char **why) {
+        return flow ? volume_flow_coupled_validate(q, coupling, m, why) : volume_coupled_validate(q, coupling, m, why); }, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    const VolumeCoupledParams cp{ p, coupling_words(coupling) };
+    auto links_of = [](const sc_volume_flow_robust_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, nullptr, j.flow_x, j.flow_y }; };
+    if (!flow) return volume_device_call<VolumeRobustOperator>(I, volume_robust_call(kind, p), &cp, l, jobs, n, bSync, links_of, robust_chunk);
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = flow_links_ensure(I, &q, l, kind))) return rc;
+    return volume_device_call<VolumeFlowRobustOperator>(I, volume_flow_robust_call(kind, p, l), &cp, l, jobs, n, bSync, links_of, robust_chunk);
+}
+
+int sc_hip_volume_flow_coupled(void *inst, const sc_volume_robust_params *p, int coupling, const sc_poisson_layout *l, const float *gx, const float *gy,
+                               const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x,
+                               const float *smooth_y, const float *smooth_t, const float *flow_x, const float *flow_y, const float *boundary, float *out)
+{
+    if (!flow_x && !flow_y)
+        return sc_hip_volume_coupled(inst, p, coupling, l, gx, gy, gt, data, state, weight, smooth_x, smooth_y, smooth_t, boundary, out);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, [coupling](const sc_volume_robust_params *q, const sc_poisson_layout *m, const char **why) {
+        return volume_flow_coupled_validate(q, coupling, m, why); }, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
+    if (!flow_x != !flow_y) { I->err = FLOW_PAIR_WHY; return SC_ERR_BAD_ARG; }
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = flow_links_ensure(I, &q, l, kind))) return rc;
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    const VolumeCoupledParams cp{ p, coupling_words(coupling) };
+    VolumeFlowRobustOperator op(I, &cp, links, tlinks);
+    FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    a.flow_x = flow_x;
+    a.flow_y = flow_y;
+    return pcg_host_call(I, volume_flow_robust_call(kind, p, l), l, carries_of(weight != nullptr, links, tlinks) | FLOAT_FLOW, a, op, robust_chunk);
 }
 
 } // extern "C"

@@ -1,34 +1,31 @@
-// sc_volume_coupled.hip -- the coupled volume call's two kernels (sc_hip_volume_coupled*, sc_volume_api.cpp: VolumeRobustOperator's
-// launches in a reweighting round under a coupling, which RobustRounds::reweigh in sc_robust_api.cpp describes): k_volume_robust_rho
-// and k_volume_robust_setup_rho, k_region_robust_rho and k_region_robust_setup_rho (sc_region_robust.hip) on k_volume_robust_setup's
-// walk (sc_volume_robust.hip: frames stacked along y, FrameRow, TimeAround, every link computed where it is used, so a band may start
-// anywhere inside a frame).  The system of a round is the WLS volume system with s = c rho(M) on every link that shares the magnitude
-// M and w' = w rho_q(u - d); a link's share of a magnitude is a = c t^2, t = (u_hi - u_lo) - g, c = smooth_x, smooth_y (NULL: 1, no
-// multiply) or lt = tau * smooth_t rounded once (NULL: tau).  The forms (seamlessclone_hip.h, the coupled volume section):
-//   SPACE           one magnitude per pixel over its x- and y-link: (a_x + a_y), penalty (p_grad, eps_grad);
-//   SPACE | TIME    ... and its forward temporal link: (a_x + a_y) + a_t, the one penalty (p_time = p_grad, eps_time = eps_grad);
-//   JOINT           every magnitude is the running sum over channels 0 .. C - 1, only the channels in which the link is live; the
-//                   temporal links' is then sum_k a_t under (p_time, eps_time).  Without JOINT and without TIME a temporal link keeps
-//                   the uncoupled penalty c_t phi_r(t): its rho is rho_r(t), robust_rho's bits.
-// The owner of a link is its low end: the last pixel of a periodic axis owns the wrapping link, the earlier frame a temporal link,
-// frame T - 1 the wrapping one; a pixel of a low Dirichlet line owns only its one spatial link into the domain, which forms a magnitude
-// of its own and is written by its UNKNOWN end.  A dead link adds nothing to a magnitude; an owner with no live link writes no rho and
-// books no energy.  A penalty of exponent 2 has rho 1: its component of the rho planes is neither written nor read, the base value
-// passes through without a multiply and its energy is booked link by link, c t^2 in double.
-// The rho planes: per unit (a volume under JOINT, else a work plane) up to three components -- xy | t under SPACE, one under SPACE |
-// TIME, x | y | t otherwise -- of T frames each, a frame robust_rho_stride of the frame's rectangle apart, addressed [frame][Y][X].
-// Every element is written by its owner only: no atomics.  What is read: the robust volume call's elements, and U at UNKNOWN pixels.
+// sc_volume_flow_coupled.hip -- the coupled flow volume call's two kernels (sc_hip_volume_flow_coupled*, sc_volume_api.cpp:
+// VolumeFlowRobustOperator's launches in a reweighting round under a coupling): k_volume_flow_robust_rho and
+// k_volume_flow_robust_setup_rho, k_volume_robust_rho and k_volume_robust_setup_rho (sc_volume_coupled.hip: the forms, the magnitudes,
+// the float32 order, the rho planes) with the temporal neighbours of an element taken from the volume's link planes (sc_pcg.h: what they
+// hold; sc_volume_flow.hip: the matching) as k_volume_flow_robust_setup takes them (sc_volume_flow_robust.hip).
+// The owner of a temporal link is its source, the element i that holds it: lt = tau * smooth_t, gt and -- new here -- the link's rho are
+// stored at i; under SPACE | TIME the pixel's magnitude is (a_x + a_y) + a_t with a_t of the held link, nothing where it holds none; a
+// link that arrives at a pixel plays no part in that pixel's magnitude.  The matching is per volume, liveness per channel: under JOINT a
+// magnitude sums the channels in which the link is live.  The wrap of periodic time is in the indices, so there is no periodic form.
+// The t-component of rho is written at the owner's own [frame][Y][X] element only -- no atomics; the pixel a link arrives at reads it at
+// the source jb = bwd[i], whose frame, row and column come from the work-plane index: the source may lie in another band, another column
+// group or (periodic time) a frame other than t - 1.  The rho launch and the set-up launch are ordered by the stream.
+// Per element beyond the straight pair: one int32 load per channel in the rho kernel (under JOINT the same word again: looked up once
+// per pixel the forms need up to 24 VGPRs more), two in the set-up, and in place of the neighbours one frame away a gather of state, of
+// U or data, and in the set-up of rho, smooth_t and gt at the back link's source -- as coalesced as the flow is smooth.
 #include "sc_region_device.h"
 #include <cmath>
+#include <type_traits>
 
 namespace sc {
 
 namespace {
 
 // grid: cg x bands x units; esum[(the unit's first plane * PCG_PARTS + part)] = the part's gradient-and-time energy
-template <bool LNK, bool PER, bool SPACE, bool TIME, bool JOINT>
-__global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, RobustTerm tg, RobustTerm tt, VolumeRhoGeo rg,
-                                                           const float *__restrict__ U, float *__restrict__ Rho, double *__restrict__ esum)
+template <bool LNK, bool SPACE, bool TIME, bool JOINT>
+__global__ __launch_bounds__(WL) void k_volume_flow_robust_rho(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, RobustTerm tg, RobustTerm tt,
+                                                                VolumeRhoGeo rg, FlowLinks fl, const float *__restrict__ U, float *__restrict__ Rho,
+                                                                double *__restrict__ esum)
 {
     __shared__ double ws[4];
     lane_term(tg); lane_term(tt);
@@ -42,7 +39,6 @@ __global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo w
     const bool rho_g = tg.mode != 0, rho_t = TIME || tt.mode != 0;      // the penalty has a rho to store (exponent 2: none)
     const int nx = wg.nx, fny = vg.ny, x = (int)blockIdx.x * WL + (int)threadIdx.x;
     const int y0 = (int)blockIdx.y * wg.rows, y1 = min(y0 + wg.rows, wg.ny);
-    const size_t n2 = (size_t)nx * fny;
     const float tau = vg.tau;
     float *__restrict__ ru = Rho + (size_t)unit * rg.unit;
     float *__restrict__ rx = ru + rg.ox, *__restrict__ ry = ru + rg.oy, *__restrict__ rt = ru + rg.ot;
@@ -53,9 +49,7 @@ __global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo w
             const FrameRow fr(vg, y);
             const int Y = wg.y0 + fr.yy;
             const size_t ro = (size_t)y * nx, li = ro + x;
-            // the magnitudes: this pixel's (mx: its x-link's, or under SPACE both spatial links' and under TIME the forward link's too;
-            // my: its y-link's; mt: its forward link's), the west Dirichlet pixel's x-link (mw), the north Dirichlet pixel's y-link (mn);
-            // has_*: live in a channel;  e2: the energy of the links without a magnitude, link by link
+            // the magnitudes, has_*, e2: k_volume_robust_rho's; mt and the t-share of mx: the held link's
             float mx = 0.f, my = 0.f, mt = 0.f, mw = 0.f, mn = 0.f;
             bool has_x = false, has_y = false, has_t = false, has_w = false, has_n = false;
             double e2 = 0.0;
@@ -65,8 +59,11 @@ __global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo w
                 if (kp == NB_NONE) continue;
                 const bool unk = kp == NB_UNKNOWN;
                 const Around a(g, wg, st, X, Y, o, px, py);
-                const TimeAround ta(vg, fr.t, o, PER);
-                const int kf = time_kind(st, ta.of, ta.hf);
+                // the link this element holds: the volume's, its target's offset in this channel
+                const TimeAround ta(g, wg, vg, fl, member, k, y, x);
+                const int jf = ta.jf;
+                const long long of = ta.of;
+                const int kf = time_kind(st, of, ta.hf);
                 const float *__restrict__ ul = U + (size_t)(member * g.C + k) * wg.stride;
                 auto value = [&](int kq, long long off, size_t i) { return kq == NB_UNKNOWN ? ul[i] : kq == NB_KNOWN ? j.d[off] : j.b[off]; };
                 auto live = [&](int kq) { return kq != NB_NONE && (unk || kq == NB_UNKNOWN); };
@@ -82,9 +79,8 @@ __global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo w
                     if (rho_g) { ay = coupled_sq(sy, o, tr); has_y = true; }
                     else e2 += (double)(sy ? sy[o] : 1.f) * (double)rounded_product(tr, tr);
                 }
-                if (live(kf)) {
-                    const size_t i_f = !PER || fr.t < vg.T - 1 ? li + n2 : li - (size_t)(vg.T - 1) * n2;
-                    const float tr = (value(kf, ta.of, i_f) - uc) - (gt ? gt[o] : 0.f), lt = time_link(smt, o, tau);
+                if (live(kf)) {          // (kf is NB_NONE without a held link: jf >= 0 here)
+                    const float tr = (value(kf, of, (size_t)jf) - uc) - (gt ? gt[o] : 0.f), lt = time_link(smt, o, tau);
                     if (TIME || (JOINT && rho_t)) {
                         at = rounded_product(lt, rounded_product(tr, tr));
                         has_t = true;
@@ -123,15 +119,16 @@ __global__ __launch_bounds__(WL) void k_volume_robust_rho(PoissonGeo g, PcgGeo w
     if (threadIdx.x == 0) esum[(size_t)(JOINT ? unit * g.C : unit) * PCG_PARTS + blockIdx.y * wg.cg + blockIdx.x] = s_e;
 }
 
-// k_volume_robust_setup (its walk, its order, its five sums) with every link's rho read from the rho planes -- at the pixel (east,
-// south, forward), at its west, north and back owner, only where that link is live: then its owner wrote it.  Field 4 of the sums: the
-// data term's energy alone.  gmode, tmode: the modes of the spatial and of the temporal penalty (0: no rho, the base link itself).
-template <bool NOW, bool LNK, bool PER, bool SPACE, bool TIME, bool JOINT>
-__global__ __launch_bounds__(WL) void k_volume_robust_setup_rho(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, int gmode, int tmode, RobustTerm td,
-                                                                 VolumeRhoGeo rg, const float *__restrict__ Rho, const float *__restrict__ U,
-                                                                 float *__restrict__ R, float *__restrict__ E, float *__restrict__ S,
-                                                                 float *__restrict__ F, float *__restrict__ Dg, double *__restrict__ bb,
-                                                                 double *__restrict__ sums)
+// k_volume_robust_setup_rho (its walk, its order, its five sums) with the temporal neighbours through the link planes: the held link's
+// rho, lt and gt at the pixel's own element, the arriving link's at its source jb = bwd[i] -- the rho element [jb's frame][row][column]
+// of the work-plane index; the values across a link as k_volume_flow_robust_setup takes them.  Field 4 of the sums: the data term's
+// energy alone.  gmode, tmode: the modes of the spatial and of the temporal penalty (0: no rho, the base link itself).
+template <bool NOW, bool LNK, bool SPACE, bool TIME, bool JOINT>
+__global__ __launch_bounds__(WL) void k_volume_flow_robust_setup_rho(PoissonGeo g, PcgGeo wg, VolumeGeo vg, VolumeJobs t, int gmode, int tmode,
+                                                                      RobustTerm td, VolumeRhoGeo rg, FlowLinks fl, const float *__restrict__ Rho,
+                                                                      const float *__restrict__ U, float *__restrict__ R, float *__restrict__ E,
+                                                                      float *__restrict__ S, float *__restrict__ F, float *__restrict__ Dg,
+                                                                      double *__restrict__ bb, double *__restrict__ sums)
 {
     __shared__ double ws[VOLUME_ROBUST_SUMS + 1][4];
     lane_term(td);
@@ -142,7 +139,7 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup_rho(PoissonGeo g, Pc
     const float *__restrict__ smt = LNK ? t.smt[bd.member] : nullptr;
     const bool px = wg.ax == MIXED_PERIODIC, py = wg.ay == MIXED_PERIODIC;
     const bool rho_g = gmode != 0, rho_t = TIME || tmode != 0;
-    const int nx = wg.nx, x = bd.x;
+    const int nx = wg.nx, x = bd.x, n2 = wg.nx * vg.ny;
     const float *__restrict__ ul = U + (size_t)bd.p * wg.stride;
     const float tau = vg.tau;
     const float *__restrict__ ru = Rho + (size_t)(JOINT ? bd.member : bd.p) * rg.unit;
@@ -172,7 +169,8 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup_rho(PoissonGeo g, Pc
             if (kp != NB_NONE) {
                 const bool unk = kp == NB_UNKNOWN;
                 const Around a(g, wg, st, X, Y, o, px, py);
-                const TimeAround ta(vg, fr.t, o, PER);
+                const TimeAround ta(g, wg, vg, fl, bd.member, bd.c, y, x);
+                const int jb = ta.jb;
                 const int kb = time_kind(st, ta.ob, ta.hb), kf = time_kind(st, ta.of, ta.hf);
                 auto live = [&](int kq) { return kq != NB_NONE && (unk || kq == NB_UNKNOWN); };
                 float le = 0.f, ls = 0.f, lf = 0.f, lw = 0.f, ln = 0.f, lb = 0.f;
@@ -194,9 +192,9 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup_rho(PoissonGeo g, Pc
                     const float uc = ul[li];
                     if (a.kw != NB_NONE) lw = space_link(sx, a.ow, rx, rr + Xw);
                     if (a.kn != NB_NONE) ln = space_link(sy, a.on, ry, rf + (size_t)(Y > 0 ? Y - 1 : g.H - 1) * rg.rw + X);
-                    if (kb != NB_NONE) {
-                        const int tb = fr.t > 0 ? fr.t - 1 : vg.T - 1;              // the owner of the back link
-                        lb = time_s(ta.ob, (size_t)tb * rg.fstride + (size_t)Y * rg.rw + X);
+                    if (kb != NB_NONE) {     // (an arriving link: jb >= 0; its rho where its source wrote it)
+                        const int tb = jb / n2, rb = jb - tb * n2, yb = rb / nx, xb = rb - yb * nx;
+                        lb = time_s(ta.ob, (size_t)tb * rg.fstride + (size_t)(wg.y0 + yb) * rg.rw + (size_t)(wg.x0 + xb));
                     }
                     // the links to a low Dirichlet line have no other owner
                     if (a.kw == NB_DIRICHLET) s_l += (double)lw;
@@ -247,67 +245,57 @@ __global__ __launch_bounds__(WL) void k_volume_robust_setup_rho(PoissonGeo g, Pc
     part_store(s_e, ws[5], wg, sums, VOLUME_ROBUST_SUMS, 4);
 }
 
-struct CoupledArgs {
+struct FlowCoupledArgs {
     const RobustTerm &grad, &time, &data;
+    FlowLinks fl;
     const float *U;
     float *Rho, *R, *E, *S, *F, *Dg;
     double *bb, *sums, *esum;
     hipStream_t s;
 };
 
-template <bool NOW, bool LNK, bool PER, bool SPACE, bool TIME, bool JOINT>
-void coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t, int cnt, const VolumeRhoGeo &rg, const CoupledArgs &a)
+template <bool NOW, bool LNK, bool SPACE, bool TIME, bool JOINT>
+void flow_coupled_launches(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t, int cnt, const VolumeRhoGeo &rg,
+                           const FlowCoupledArgs &a)
 {
     const unsigned planes = (unsigned)(g.C * cnt);
-    hipLaunchKernelGGL((k_volume_robust_rho<LNK, PER, SPACE, TIME, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, JOINT ? (unsigned)cnt : planes),
-                       dim3(WL), 0, a.s, g, wg, vg, t, a.grad, a.time, rg, a.U, a.Rho, a.esum);
-    hipLaunchKernelGGL((k_volume_robust_setup_rho<NOW, LNK, PER, SPACE, TIME, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, planes), dim3(WL), 0,
-                       a.s, g, wg, vg, t, a.grad.mode, a.time.mode, a.data, rg, a.Rho, a.U, a.R, a.E, a.S, a.F, a.Dg, a.bb, a.sums);
+    hipLaunchKernelGGL((k_volume_flow_robust_rho<LNK, SPACE, TIME, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, JOINT ? (unsigned)cnt : planes),
+                       dim3(WL), 0, a.s, g, wg, vg, t, a.grad, a.time, rg, a.fl, a.U, a.Rho, a.esum);
+    hipLaunchKernelGGL((k_volume_flow_robust_setup_rho<NOW, LNK, SPACE, TIME, JOINT>), dim3((unsigned)wg.cg, (unsigned)wg.bands, planes), dim3(WL), 0,
+                       a.s, g, wg, vg, t, a.grad.mode, a.time.mode, a.data, rg, a.fl, a.Rho, a.U, a.R, a.E, a.S, a.F, a.Dg, a.bb, a.sums);
 }
 
 template <bool SPACE, bool TIME, bool JOINT>
-void coupled_form(bool now, bool lnk, bool per, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t, int cnt,
-                  const VolumeRhoGeo &rg, const CoupledArgs &a)
+void flow_coupled_form(bool now, bool lnk, const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const VolumeJobs &t, int cnt,
+                       const VolumeRhoGeo &rg, const FlowCoupledArgs &a)
 {
-    auto go = now ? (lnk ? (per ? coupled_launches<true, true, true, SPACE, TIME, JOINT> : coupled_launches<true, true, false, SPACE, TIME, JOINT>)
-                         : (per ? coupled_launches<true, false, true, SPACE, TIME, JOINT> : coupled_launches<true, false, false, SPACE, TIME, JOINT>))
-                  : (lnk ? (per ? coupled_launches<false, true, true, SPACE, TIME, JOINT> : coupled_launches<false, true, false, SPACE, TIME, JOINT>)
-                         : (per ? coupled_launches<false, false, true, SPACE, TIME, JOINT> : coupled_launches<false, false, false, SPACE, TIME, JOINT>));
+    auto go = now ? (lnk ? flow_coupled_launches<true, true, SPACE, TIME, JOINT> : flow_coupled_launches<true, false, SPACE, TIME, JOINT>)
+                  : (lnk ? flow_coupled_launches<false, true, SPACE, TIME, JOINT> : flow_coupled_launches<false, false, SPACE, TIME, JOINT>);
     go(g, wg, vg, t, cnt, rg, a);
-}
-
-// The coupled volume forms' launches of every side table: fn(space, time, joint, t, cnt, o, po, ro) -- the form as std::bool_constant,
-// for the kernels' template arguments; o, po, ro: the first volume's offset into the work planes, into the parts (per double of a part)
-// and into the rho planes
-template <class Fn>
-void for_volume_coupled_tables(const PoissonGeo &g, const PcgGeo &wg, const VolumeRhoGeo &rg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
-                               int coupling, Fn fn)
-{
-    const bool space = (coupling & ROBUST_ISO) != 0, time = (coupling & ROBUST_TIME) != 0, joint = (coupling & ROBUST_JOINT) != 0;
-    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
-        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
-        const size_t ro = (size_t)(joint ? i0 : g.C * i0) * rg.unit;
-        using T = std::true_type;
-        using F = std::false_type;
-        if (space && time && joint) fn(T(), T(), T(), t, cnt, o, po, ro);
-        else if (space && time) fn(T(), T(), F(), t, cnt, o, po, ro);
-        else if (space && joint) fn(T(), F(), T(), t, cnt, o, po, ro);
-        else if (space) fn(T(), F(), F(), t, cnt, o, po, ro);
-        else fn(F(), F(), T(), t, cnt, o, po, ro);
-    });
 }
 
 } // namespace
 
-void launch_volume_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
-                                  const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, int coupling, const float *U, float *Rho,
-                                  float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, double *esum, hipStream_t s)
+void launch_volume_flow_robust_coupled(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides,
+                                       int m, const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, int coupling, const int *fwd,
+                                       const int *bwd, const float *U, float *Rho, float *R, float *E, float *S, float *F, float *Dg, double *bb,
+                                       double *sums, double *esum, hipStream_t s)
 {
     const VolumeRhoGeo rg = volume_rho_geo(wg, vg, grad, time, coupling);
-    for_volume_coupled_tables(g, wg, rg, jobs, sides, m, coupling, [&](auto space, auto tm, auto joint, const VolumeJobs &t, int cnt, size_t o, size_t po, size_t ro) {
-        const bool now = !t.w[0], lnk = t.sx[0] || t.smt[0], per = vg.periodic != 0;
-        const CoupledArgs a{ grad, time, data, U + o, Rho + ro, R + o, E + o, S + o, F + o, Dg + o, bb + po, sums + po * VOLUME_ROBUST_SUMS, esum + po, s };
-        coupled_form<decltype(space)::value, decltype(tm)::value, decltype(joint)::value>(now, lnk, per, g, wg, vg, t, cnt, rg, a);
+    const long long ls = flow_link_stride(wg);
+    const bool space = (coupling & ROBUST_ISO) != 0, tm = (coupling & ROBUST_TIME) != 0, joint = (coupling & ROBUST_JOINT) != 0;
+    for_side_tables<VolumeJobs>(jobs, sides, m, [&](const VolumeJobs &t, int i0, int cnt) {
+        const size_t o = (size_t)g.C * i0 * wg.stride, po = (size_t)g.C * i0 * PCG_PARTS;
+        const size_t ro = (size_t)(joint ? i0 : g.C * i0) * rg.unit;
+        const bool now = !t.w[0], lnk = t.sx[0] || t.smt[0];
+        const FlowCoupledArgs a{ grad, time, data, FlowLinks{ fwd + ls * i0, bwd + ls * i0, ls }, U + o, Rho + ro, R + o, E + o, S + o, F + o, Dg + o,
+                                 bb + po, sums + po * VOLUME_ROBUST_SUMS, esum + po, s };
+        // the five legal forms, as for_volume_coupled_tables (sc_volume_coupled.hip) deals them
+        if (space && tm && joint) flow_coupled_form<true, true, true>(now, lnk, g, wg, vg, t, cnt, rg, a);
+        else if (space && tm) flow_coupled_form<true, true, false>(now, lnk, g, wg, vg, t, cnt, rg, a);
+        else if (space && joint) flow_coupled_form<true, false, true>(now, lnk, g, wg, vg, t, cnt, rg, a);
+        else if (space) flow_coupled_form<true, false, false>(now, lnk, g, wg, vg, t, cnt, rg, a);
+        else flow_coupled_form<false, false, true>(now, lnk, g, wg, vg, t, cnt, rg, a);
     });
 }
 

@@ -1081,13 +1081,14 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     joint_channels: every penalty over the channels of the volume (the vectorial total variation).  With any of the three the call is
     sc_hip_volume_coupled's.  flow (volume_wls_solve's: (T - 1) x H x W x 2, with loop T, of (dx, dy), rounded; NaN: no link): every
     temporal link -- its weight, its gt, its penalty -- joins pixel (x, y) of frame t to pixel (x + dx, y + dy) of frame t + 1, and
-    smooth_t and gt stay stored at the link's source; sc_hip_volume_flow_robust.  A flow goes with none of the three coupled forms: the
-    library has no coupled penalties along a flow.  Returns a NEW array."""
+    smooth_t and gt stay stored at the link's source; sc_hip_volume_flow_robust.  A flow goes with none of the three coupled forms here:
+    volume_flow_coupled_solve has the coupled penalties along a flow.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
     if flow is not None:
         if coupling:
-            raise ValueError("flow= goes with none of isotropic, spacetime and joint_channels: coupled penalties along a flow are not offered")
+            raise ValueError("flow= goes with none of isotropic, spacetime and joint_channels: coupled penalties along a flow are not offered here "
+                             "(volume_flow_coupled_solve and tv_denoise_video_along_flow have them)")
         capi.volume_flow_shape(flow, np.shape(data)[0], np.shape(data)[1], np.shape(data)[2], bool(loop))       # (before a device is touched)
     if spacetime and (p_time != p or eps_time != eps_grad):
         raise ValueError("spacetime=True is one penalty over space and time: p_time must equal p and eps_time eps_grad")
@@ -1102,6 +1103,53 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
         return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
 
 
+def volume_flow_coupled_solve(gx, gy, data, state, flow, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0,
+                              loop=False, p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None,
+                              periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False, spacetime=False,
+                              joint_channels=False, **solver):
+    """volume_robust_solve's coupled forms with every temporal link along `flow` ((T - 1) x H x W x 2, with loop T, of (dx, dy),
+    rounded; NaN: no link): isotropic -- one penalty per pixel over its x- and y-link --, spacetime -- ... and over the temporal link
+    the pixel holds, the one that leads from it to pixel (x + dx, y + dy) of frame t + 1 (implies isotropic and needs p_time == p and
+    eps_time == eps_grad); a pixel that holds no link has a spatial magnitude alone, and a link that arrives at a pixel plays no part in
+    that pixel's magnitude --, joint_channels -- every penalty over the channels in which its link is live.  smooth_t and gt stay stored
+    at a link's source.  volume_robust_solve's other arguments and defaults.  The call is
+        Instance.volume_flow_coupled(capi.volume_coupling(isotropic, spacetime, joint_channels), gx, gy, data, state, flow, weight,
+                                     smooth_x, smooth_y, smooth_t, gt, boundary, ...)
+    (sc_hip_volume_flow_coupled); flow None: volume_robust_solve's coupled call, none of the three: volume_robust_solve(flow=flow)'s
+    bytes.  Returns a NEW array."""
+    neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
+    coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
+    if flow is not None:
+        capi.volume_flow_shape(flow, np.shape(data)[0], np.shape(data)[1], np.shape(data)[2], bool(loop))       # (before a device is touched)
+    if spacetime and (p_time != p or eps_time != eps_grad):
+        raise ValueError("spacetime=True is one penalty over space and time: p_time must equal p and eps_time eps_grad")
+    args = dict(tau=tau, loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, p_grad=p, eps_grad=eps_grad, p_time=p_time,
+                eps_time=eps_time, p_data=q, eps_data=eps_data, max_rounds=max_rounds or 0, round_tol=round_tol or 0.0, tol=tol or 0.0,
+                max_iters=max_iters or 0)
+    with _instance(gpu_id, solver) as inst:
+        return inst.volume_flow_coupled(coupling, gx, gy, data, state, flow, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
+
+
+def tv_denoise_video_along_flow(frames, lam, flow, isotropic=True, spacetime=False, joint_channels=False, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2,
+                                loop=False, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+    """tv_denoise_video with its coupled forms along a flow: the video u that minimises
+        lam sum phi_q(u - frames) + (the isotropic / space-time / vectorial total variation of u) with the temporal differences
+        u_{t+1}(x + dx, y + dy) - u_t(x, y) over the matched pixels of `flow` (volume_flow_coupled_solve's),
+    so that on a moving shot discs stay discs, colours do not fringe and the temporal term compares a surface point with itself.
+    tv_denoise_video's other arguments.  The call is
+        Instance.volume_flow_coupled(capi.volume_coupling(isotropic, spacetime, joint_channels), 0, 0, frames, all UNKNOWN, flow,
+                                     weight=lam, p_grad=p, p_time=p_time, p_data=q, eps_grad=eps_time=eps_data=eps, neumann=True, ...)
+    through volume_flow_coupled_solve.  Returns a NEW array."""
+    frames = _video_of("frames", frames)
+    if not (np.isfinite(lam) and lam > 0):
+        raise ValueError("lam must be finite and > 0")
+    zero = np.zeros_like(frames)
+    return volume_flow_coupled_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), flow, weight=np.full(frames.shape[:3], lam, np.float32),
+                                     tau=tau, loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True,
+                                     max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime,
+                                     joint_channels=joint_channels, **solver)
+
+
 def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False,
                      spacetime=False, joint_channels=False, flow=None, **solver):
     """Total-variation denoising of a float32 video (T x H x W or T x H x W x C) that does not flicker: the video u that minimises
@@ -1111,7 +1159,8 @@ def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, l
     eps (in the frames' units) rounds all three penalties off near 0.  loop: the last frame is joined to the first.  isotropic,
     spacetime, joint_channels: volume_robust_solve's coupled forms -- the total variation of the gradient's magnitude per frame (discs
     stay discs), of the space-time gradient's (a moving edge is one surface; needs p_time == p), and over all channels (no colour
-    fringes).  flow (volume_robust_solve's; with none of the three coupled forms): the temporal term is tau sum phi_r(u_{t+1}(x + dx,
+    fringes).  flow (volume_robust_solve's; with none of the three coupled forms -- those along a flow:
+    tv_denoise_video_along_flow): the temporal term is tau sum phi_r(u_{t+1}(x + dx,
     y + dy) - u_t(x, y)) over the matched pixels, so a panning shot is neither blurred along its motion nor left to flicker.  Returns a
     NEW array."""
     frames = _video_of("frames", frames)
@@ -1132,7 +1181,7 @@ def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=Fa
     over the links that touch the hole, every pixel outside it held -- volume_robust_solve with zero guidance, every pixel outside the
     hole known and reflecting borders.  isotropic (the default), spacetime, joint_channels: its coupled forms.  eps (in the frames'
     units) rounds the penalties off near 0.  loop: the last frame is joined to the first.  Returns a NEW array; pixels outside the hole
-    keep their bits."""
+    keep their bits.  (Along a flow: volume_flow_coupled_solve with zero guidance, these states and the same coupling.)"""
     frames = _video_of("frames", frames)
     h = _video_masks("hole", hole, frames)
     if h.all():
