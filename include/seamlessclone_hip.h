@@ -1238,9 +1238,9 @@ SC_API int sc_hip_volume_wls(void *instance, const sc_volume_wls_params *p, cons
  * every per-job refusal of sc_hip_volume_wls; exactly one of flow_x / flow_y; a flow where the first volume has none, or the reverse; a
  * flow array overlapping out; a finite flow value, where the flow is read, that is not a whole number.
  * Not offered: flow through sc_hip_volume or the 8-bit entry points (robust penalties along a flow: sc_hip_volume_flow_robust
- * below; the coupled forms along a flow: sc_hip_volume_flow_coupled); sub-pixel flow (a link
- * would become a stencil of several points and the matching would not apply); a preconditioner that transforms along the trajectories;
- * links of several pixels onto one; an estimator of the flow. */
+ * below; the coupled forms along a flow: sc_hip_volume_flow_coupled); a preconditioner that transforms along the trajectories; an
+ * estimator of the flow.  Sub-pixel flow and links of several pixels onto one: sc_hip_volume_subflow below, with these parameters and
+ * jobs -- there a link is a bilinear stencil and no matching applies. */
 typedef struct sc_volume_flow_job {     /* sc_volume_wls_job and the two flow arrays */
     const float *gx, *gy;    /* SC_POISSON_GUIDANCE: `frames` frames, read at links live in the region */
     const float *gt;         /* SC_POISSON_GUIDANCE: frames - 1 frames (time_periodic: frames), read at live matched links; NULL: zeros */
@@ -1267,6 +1267,59 @@ SC_API int sc_hip_volume_flow(void *instance, const sc_volume_wls_params *p, con
                               const float *gt, const float *lap, const float *data, const float *state, const float *weight,
                               const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x, const float *flow_y,
                               const float *boundary, float *out);
+/* ---- sub-pixel flow volume solves: bilinear temporal links along a real-valued flow ----------------------------------------------------------
+ * sc_hip_volume_flow's call with the flow's values taken as they are: every optical-flow estimator returns real-valued vectors, and on
+ * a slow pan or a zoom a rounded flow is the straight link again for half the pixels.  A temporal link joins pixel p of frame t to the
+ * bilinear interpolation of frame t + 1 at p + flow(p); the temporal term is
+ *     sum_t sum_p lt(p) (sum_k b_k(p) u_{t+1}(q_k(p)) - u_t(p) - gt_t(p))^2
+ * over the pixels p that hold a link.  The parameters are sc_volume_wls_params, the jobs sc_volume_flow_job, both unchanged; flow_x and
+ * flow_y have sc_hip_volume_flow's layout, and smooth_t and gt stay stored at the link's source element (p, t).  Everything but the
+ * temporal term is sc_hip_volume_wls's problem, word for word.
+ * Taps.  Per component in float32: x0 = floorf(dx), ax = dx - x0 (one float32 subtraction: exact unless dx is a negative value within
+ * 2^-25 of a whole number, where it rounds to 1 and the link is the whole-numbered one), y0 and ay likewise.  The tap columns are
+ * x + (int)x0 and one more, the tap rows y + (int)y0 and one more, the four weights the float32 products (1 - ax)(1 - ay), ax (1 - ay),
+ * (1 - ax) ay and ax ay, the taps in that order.  A tap whose weight is exactly 0 is no part of the link: a whole-numbered flow has one
+ * tap, a flow that is fractional along one axis two; -0.0 is 0.
+ * Candidates.  A pixel of the work rectangle (sc_hip_volume_flow's: a Dirichlet line is outside and carries no temporal links) whose
+ * frame has a next frame -- or time is periodic -- is a candidate when both components are finite and at most 1e6 in magnitude.  A
+ * periodic axis wraps each tap; elsewhere a link with any remaining tap outside the work rectangle is no link.  There is no matching:
+ * every candidate holds its link, and any number of links may arrive at a pixel.  With B the matrix whose row p holds b_k(p) at the
+ * taps and -1 at p, the temporal term of the system is B^T S B, S = diag(lt): symmetric by construction.
+ * Liveness.  A link is dead when its source or any tap is OUTSIDE; it is live when it is not dead and at least one of its up to five
+ * points is UNKNOWN.  KNOWN points enter the right-hand side with data's value times their coefficient (b_k at a tap, -1 at the
+ * source).  The guidance form's temporal divergence is B^T S gt; the Laplacian form takes lap as it is and does not read gt.
+ * What is read: sc_hip_volume_wls's elements, with gt and smooth_t only at the source of a live link (a NaN elsewhere is fine), and the
+ * flow at every pixel of the work rectangle of every frame it holds, nowhere else.  The flow arrays must not overlap out.
+ * Preconditioner: sc_hip_volume_wls's, unchanged, with straight time links.  tau-bar is the mean of lt over the live links (exactly tau
+ * without smooth_t); in w-bar a temporal link's share is lt * (1 where its source is KNOWN, else the sum of b over its KNOWN taps) --
+ * for a link of one tap sc_hip_volume_flow's "an UNKNOWN - KNOWN link counts its own weight".  The pin check is the volume call's over
+ * these sums.  sc_hip_volume_flow's warning carries over: strong temporal coupling under motion costs iterations (a float64 model, all
+ * UNKNOWN, a weight at 3 % of the pixels, 47 x 33 x 5, tol 1e-5: tau 0.1 / 1 / 10 take 11 / 16 / 65 iterations on a pan of (0.5, 0.5)
+ * and 13 / 35 / 238 on one of (2.25, -0.75), against 10 / 9 / 8 on a zero flow).  Raise max_iters there.
+ * Cost.  The arrivals at a pixel are summed by one lane in their fixed order, so an application of the operator takes time in proportion
+ * to the longest row: about four arrivals per pixel under a smooth flow, but a flow that sends L pixels onto one point makes every
+ * iteration wait for L dependent loads.  Mark such pixels as occluded (a component that is not finite) where that is what they are.
+ * Determinism.  Two runs of one call give the same bytes: the operator and the right-hand side use no float atomics, and wherever the
+ * arrivals at a pixel are summed the order is ascending (source index, tap).
+ * Ties.  Both flow arrays NULL runs sc_hip_volume_wls's launches and gives its bytes.  No byte tie holds with sc_hip_volume_wls on a
+ * flow of zeros, nor with sc_hip_volume_flow on a whole-numbered flow: the temporal operator is applied in product form, B^T (S (B u)),
+ * which rounds differently from the assembled diagonal of those calls.  On a whole-numbered flow without collisions the two calls solve
+ * the same system.
+ * Size, chunks, stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, methods, SC_FLAG_FFT_FP64 limits, host waits, sc_run_info:
+ * sc_hip_volume_flow's, its 32-bit size rule included ((unknowns per frame) * frames below 2^31 - 1, else SC_ERR_BAD_SIZE).
+ * Codes: sc_hip_volume_flow's without the refusal of a value that is not a whole number.
+ * Not offered: robust or coupled penalties along a sub-pixel flow; a preconditioner that transforms along the trajectories; the 8-bit
+ * entry points; an estimator of the flow. */
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_subflow_check(const sc_volume_wls_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_subflow_device(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_flow_job *jobs, int n,
+                                        bool bSync);
+/* One volume on host arrays, as sc_hip_volume_flow: spans in and out through pinned staging, only the named elements of out written. */
+SC_API int sc_hip_volume_subflow(void *instance, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                                 const float *gt, const float *lap, const float *data, const float *state, const float *weight,
+                                 const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x, const float *flow_y,
+                                 const float *boundary, float *out);
 /* ---- robust volume solves: Lp penalties in space, time and data on frame stacks ---------------------------------------------------------
  * sc_hip_volume_wls's problem with sc_hip_robust's penalties in place of the squares.  Per channel, with exponents 0 < p, r, q <= 2, the
  * call minimises over the UNKNOWN pixels of all frames

@@ -609,6 +609,13 @@ def load():
     L.sc_hip_volume_flow_device.restype = C.c_int
     L.sc_hip_volume_flow.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 14
     L.sc_hip_volume_flow.restype = C.c_int
+    L.sc_hip_volume_subflow_check.argtypes = [C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_subflow_check.restype = C.c_int
+    L.sc_hip_volume_subflow_device.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout), C.POINTER(VolumeFlowJob), C.c_int,
+                                               C.c_bool]
+    L.sc_hip_volume_subflow_device.restype = C.c_int
+    L.sc_hip_volume_subflow.argtypes = [C.c_void_p, C.POINTER(VolumeWlsParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 14
+    L.sc_hip_volume_subflow.restype = C.c_int
     L.sc_hip_volume_robust_check.argtypes = [C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)]
     L.sc_hip_volume_robust_check.restype = C.c_int
     L.sc_hip_volume_robust_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout), C.POINTER(VolumeRobustJob),
@@ -1181,6 +1188,25 @@ def volume_flow_planes(flow, frames: int, rows: int, cols: int, loop: bool = Fal
     whole numbers (np.rint); NaN and the infinities are kept: "no link here" (an occlusion)."""
     volume_flow_shape(flow, frames, rows, cols, loop)
     f = np.rint(flow.astype(np.float32))
+    return np.ascontiguousarray(f[..., 0]), np.ascontiguousarray(f[..., 1])
+
+
+def volume_subflow_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                         tol: float = 0.0, max_iters: int = 0, precond_lambda: float = 0.0, precond_smooth: float = 0.0, precond_tau: float = 0.0,
+                         layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                         channel_stride=None) -> int:
+    """Host-only sc_hip_volume_subflow_check: volume_flow_check's codes -- the sub-pixel call takes the flow call's parameters unchanged."""
+    p = VolumeWlsParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(tol), int(max_iters),
+                        float(precond_lambda), float(precond_smooth), float(precond_tau))
+    return _check_call("sc_hip_volume_subflow_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_subflow_planes(flow, frames: int, rows: int, cols: int, loop: bool = False):
+    """volume_flow_planes without the rounding: (flow_x, flow_y) as float32, the values as they are (sc_hip_volume_subflow takes a
+    real-valued flow); NaN and the infinities are kept: "no link here"."""
+    volume_flow_shape(flow, frames, rows, cols, loop)
+    f = flow.astype(np.float32)
     return np.ascontiguousarray(f[..., 0]), np.ascontiguousarray(f[..., 1])
 
 
@@ -1757,6 +1783,31 @@ class Instance:
         """sc_hip_volume_flow_device: jobs is a VolumeFlowJob array (make_volume_flow_jobs) of device pointers; flow_x, flow_y are dense
         W x H x (T - 1; periodic time: T) float32 whatever the layout.  Codes as volume_wls_device."""
         return self._device_call("sc_hip_volume_flow_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
+    # ---- sub-pixel flow volume solves on float32 arrays
+    def volume_subflow(self, data, state, flow, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gx=None, gy=None, gt=None, lap=None,
+                       boundary=None, tau=1.0, loop=False, neumann=False, free_sides="", periodic="", tol=0.0, max_iters=0, precond_lambda=0.0,
+                       precond_smooth=0.0, precond_tau=0.0, allow_not_converged=False):
+        """sc_hip_volume_subflow on numpy float32 arrays: volume_flow()'s arguments and result with `flow` taken as it is -- a temporal link
+        joins a pixel to the bilinear interpolation of the next frame at (x + dx, y + dy) (volume_subflow_planes' rules: float32, not
+        rounded, NaN = no link).  gt and smooth_t stay stored at a link's source pixel.  flow None: volume_wls() itself."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, lap, boundary = volume_wls_arrays(data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                              gx, gy, gt, lap, boundary, tau, loop, neumann,
+                                                                                              free_sides, periodic)
+        fx, fy = (None, None) if flow is None else volume_subflow_planes(flow, data.shape[0], data.shape[1], data.shape[2], loop)
+        layout = poisson_layout_of(data[0])
+        p = VolumeWlsParams(kind, data.shape[0], data[0].size, float(tau), 1 if loop else 0, float(tol), int(max_iters), float(precond_lambda),
+                            float(precond_smooth), float(precond_tau))
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_subflow(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                          (gx, gy, gt, lap, data, state, weight, sx, sy, smt, fx, fy, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    def volume_subflow_device(self, params: VolumeWlsParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_subflow_device: volume_flow_device()'s jobs (make_volume_flow_jobs) with flow_x, flow_y real-valued.  Codes as
+        volume_wls_device."""
+        return self._device_call("sc_hip_volume_subflow_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     # ---- robust volume solves on float32 arrays
     def volume_robust(self, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,

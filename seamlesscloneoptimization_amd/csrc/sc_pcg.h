@@ -1,7 +1,7 @@
 // sc_pcg.h -- the preconditioned conjugate gradients that the weighted, the WLS and the robust call share: the work planes' geometry and
 // tiling, the instance's state, what a family tells the iteration about its operator (PcgOperator), the driver and the entry code around
 // it (pcg_run, pcg_begin, pcg_host_call, pcg_device_call; sc_pcg.cpp), the launches (sc_pcg.hip: the shared ones; sc_weighted.hip,
-// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_flow.hip, sc_volume_robust.hip, sc_volume_coupled.hip: a family's statistics, set-up and operator), the link operator
+// sc_wls.hip, sc_robust.hip, sc_region.hip, sc_region_robust.hip, sc_bounded.hip, sc_volume.hip, sc_volume_flow.hip, sc_volume_subflow.hip, sc_volume_robust.hip, sc_volume_coupled.hip: a family's statistics, set-up and operator), the link operator
 // of the WLS and the robust call (WlsOperator, sc_wls_api.cpp), the volume families' (VolumeOperator, sc_volume_api.cpp) and what the three
 // robust calls share: their rounds, their check and their entry preamble (RobustRounds, robust_chunk, robust_begin; sc_robust_api.cpp).
 //     L u = b,  L negative definite,  preconditioned by direct_jobs_solve with a constant: M = A - lam.
@@ -33,9 +33,9 @@ struct PcgState {
     DevBuf u, r, p, q;
     DevBuf w;                              // the weighted solve's coefficient plane (sc_weighted.hip): the weights
     DevBuf e, s, dg;                       // the WLS solve's (sc_wls.hip): links east, links south, the diagonal
-    DevBuf f, dct, tab;                    // the volume solve's (sc_volume.hip): links to the next frame; the transformed planes; the DCT table (float) and the modes' shifts (double)
-    DevBuf lnk;                            // the flow volume solve's (sc_volume_flow.hip): the int32 link planes fwd | bwd per volume
-    DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude
+    DevBuf f, dct, tab;                    // the volume solve's (sc_volume.hip): links to the next frame (the sub-pixel flow call: 1 at UNKNOWN pixels, else 0); the transformed planes; the DCT table (float) and the modes' shifts (double)
+    DevBuf lnk;                            // the flow volume solve's (sc_volume_flow.hip): the int32 link planes fwd | bwd per volume; the sub-pixel flow call's (sc_volume_subflow.hip): off | ent | fw of a chunk's volumes and the build's scratch (SubflowStore)
+    DevBuf rho;                            // the robust solve's coupled forms (sc_robust.hip): rho of every owner's magnitude; the sub-pixel flow call's: rho | LT, a work plane each per (volume, channel)
     DevBuf act;                            // the bounded solve's two set planes (sc_bounded.hip): 0 free, +1 upper-active, -1 lower-active
     DevBuf bad, h_bad;                     // ... and its judgement of bound arrays: per part the UNKNOWN pixels with an invalid bound (double; device, pinned)
     DevBuf red;                            // double: the family's statistics | b.b | p.q | r.r | r.z of even / odd iterations (PCG_PARTS per plane each) | ||r||^2 per plane | a family's round sums
@@ -450,6 +450,39 @@ void launch_volume_flow_setup(const PoissonGeo &g, const PcgGeo &wg, const Volum
 // launch_volume_op with tb = F[bwd[i]] P[bwd[i]] and tf = F[i] P[fwd[i]] (0 where there is none); C: the planes per volume
 void launch_volume_flow_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, int C, bool residual, const float *P, const float *E, const float *S,
                            const float *F, const float *Dg, const int *fwd, const int *bwd, float *Q, double *parts, hipStream_t s);
+
+// ---- the sub-pixel flow volume call (sc_volume_subflow.hip): sc_hip_volume_wls's system with every temporal link a bilinear stencil
+// along a real-valued flow -- the flow call's two arrays, their values taken as they are.  The link p holds has up to four taps in the
+// next frame (seamlessclone_hip.h, the sub-pixel section: floorf, the float32 fractions and products, a tap of weight 0 left out); no
+// matching: every candidate holds its link.  Per volume (shared by its channels) PcgState::lnk holds, in the order of the volumes that
+// stay: off, n + 1 int64 row starts (n = nx * T ny work-plane elements; n + 2 apart), and ent, the rows' entries -- bits 0..31 the
+// source's work-plane index, bits 32..63 the tap's float32 weight --, for every target the taps that arrive at it in ascending (source,
+// tap) order (4 n apart; off[n] of them are set); fw, the flow cropped to the work rectangle, dx | dy (n floats each, 2 n apart), NaN
+// where a pixel holds no link.  Behind them the build's scratch for one volume: keys in and out, values in, a pass's counts.
+struct SubflowLinks { const long long *off; const unsigned long long *ent; const float *fw; long long n; };      // of the launch's first volume
+struct SubflowStore { long long n; int per; size_t off_b, ent_b, fw_b, kin_b, kout_b, vin_b, tmp_b, tmp_bytes, total; };      // byte offsets into lnk
+// the storage of a chunk of at most `per` volumes (the entries pass the call's own volumes where those are fewer than a chunk holds)
+SubflowStore subflow_store(const PcgGeo &wg, int per);
+// off, ent and fw of m volumes from their flow arrays (sides[k].fx, .fy), volume by volume: every tap slot's (target, (source, weight)),
+// a stable radix sort by target (one stable split per key bit), every row's start by bisection.  Linear in the volume whatever the
+// longest row; no atomics.
+void launch_subflow_links(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const SideArrays *sides, int m, const SubflowStore &st, void *lnk,
+                                hipStream_t s);
+// launch_volume_stats in its full form with the temporal fields of the bilinear links (a link counted once, at its source; in the
+// UNKNOWN - KNOWN sum lt * (1 where the source is KNOWN, else the sum of b over its KNOWN taps))
+void launch_volume_subflow_stats(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                 const SubflowStore &st, void *lnk, double *stats, hipStream_t s);
+// two launches: LT = the weight of the link every element holds where it is live (else 0) and SG = lt * (gt less the KNOWN taps' b * data,
+// plus data at a KNOWN source); then launch_volume_setup's planes with b's temporal part SG(i) - sum over the arrivals of b SG(source),
+// F = 1 at UNKNOWN pixels (else 0) and Dg = the spatial links and w alone.  SG may be the plane launch_volume_subflow_op overwrites.
+void launch_volume_subflow_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, bool lap, const PoissonJobDev *jobs, const SideArrays *sides,
+                                 int m, const SubflowStore &st, void *lnk, float *LT, float *SG, float *R, float *E, float *S, float *F, float *Dg,
+                                 double *bb, hipStream_t s);
+// two launches: RHO(p) = LT(p) (sum_k b_k F P at the taps - F(p) P(p)); then launch_volume_op with the temporal part F(i) (RHO(i) - sum
+// over the arrivals of b RHO(source)); C: the planes per volume
+void launch_volume_subflow_op(const PcgGeo &wg, const VolumeGeo &vg, int planes, int C, bool residual, const SubflowStore &st, const void *lnk, const float *P,
+                              const float *E, const float *S, const float *F, const float *Dg, const float *LT, float *RHO, float *Q, double *parts,
+                              hipStream_t s);
 
 // ---- the robust family (sc_robust.hip): the WLS system of one reweighting round, its links and weights taken at an iterate
 // one penalty phi_r(t) = (2 / r) (t^2 + eps^2)^(r/2) as the kernel takes it: mode 0: r = 2 (rho = 1), 1: r = 1 (rho = 1 / sqrt), 2: powf;

@@ -33,6 +33,10 @@
 // arrays come through the front end like every side array (FLOAT_FLOW, PcgCall::flow_floats: dense, no channel axis, their own
 // length) and the call through volume_device_call and pcg_host_call; a volume whose unknowns the link planes' 32 bits cannot index is
 // refused before anything runs (SC_ERR_BAD_SIZE), by sc_hip_volume_flow_check and by a call that carries a flow.
+// sc_hip_volume_subflow (its own three entries, behind sc_hip_volume_flow's): the flow call with a real-valued flow, every temporal link a
+// bilinear stencil.  VolumeSubflowOperator is VolumeOperator with the volumes' transposed links (PcgState::lnk; sc_volume_subflow.hip: no
+// matching, a stable sort by target) built where VolumeFlowOperator builds its planes, the statistics and the set-up in their sub-pixel
+// forms and the operator in product form (k_subflow_rho, k_subflow_op; PcgState::rho: rho | LT); the same front end, check and size rule.
 // sc_hip_volume_flow_robust (its own three entries, behind sc_hip_volume_robust's): the robust volume call with every temporal link --
 // its base weight, its gt, its penalty -- on the flow call's matched link.  VolumeFlowRobustOperator is VolumeFlowOperator (the matching,
 // the statistics and their judgement, round 0's set-up, k_volume_flow_op) with the robust volume operator's rounds, whose launch is
@@ -308,6 +312,69 @@ PcgCall volume_flow_call(int kind, const sc_volume_wls_params *p, const sc_poiss
     PcgCall call = volume_call(kind, p);
     call.flow_floats = (size_t)call.tframes * (size_t)l->rows * (size_t)l->cols;
     return call;
+}
+
+// ---- the sub-pixel flow volume call: VolumeOperator with the volumes' transposed bilinear links (PcgState::lnk; sc_volume_subflow.hip)
+// built in front of the statistics -- and again in front of the set-up where a volume has left --, the statistics and the set-up in
+// their sub-pixel forms and the operator in product form: PcgState::rho holds rho | LT per work plane, PcgState::f the mask of the
+// UNKNOWN pixels.  M^-1 untouched: straight time links.
+// the sub-pixel call's parameters: the WLS volume call's and the volumes the call holds (the link storage is sized by them)
+struct VolumeSubflowParams { const sc_volume_wls_params *p; int volumes; };
+// the volumes a chunk of the call holds at most: a chunk's share of SC_POISSON_MAX_PLANES, or the call's volumes where those are fewer
+int subflow_chunk_volumes(int volumes, int channels, int frames)
+{
+    return std::max(1, std::min(volumes, SC_POISSON_MAX_PLANES / (channels * frames)));
+}
+struct VolumeSubflowOperator final : VolumeOperator {
+    int built = -1;      // the volumes whose links stand, in dj's order
+    int chan = 1;        // the call's channels: the planes that share a volume's links
+    size_t lt_at = 0;    // where LT starts in PcgState::rho, in floats
+    const int volumes;   // of the call
+    VolumeSubflowOperator(Instance *I_, const VolumeSubflowParams *c, bool links_, bool tlinks_)
+        : VolumeOperator(I_, c->p, links_, tlinks_, 0, OwnStats{ VOLUME_STATS }), volumes(c->volumes) {}
+    // (the entries have made PcgState::lnk large enough for a chunk: subflow_links_ensure)
+    SubflowStore st{};   // where they lie in PcgState::lnk (build)
+    void begin() override { VolumeOperator::begin(); built = -1; }
+    void build(const PoissonGeo &g, const PcgGeo &wg, int m, hipStream_t s)
+    {
+        chan = g.C;
+        st = subflow_store(wg, subflow_chunk_volumes(volumes, chan, T));      // (subflow_links_ensure's count: ent and fw lie behind all its volumes' off)
+        launch_subflow_links(g, wg, geo(wg), ds.data(), m, st, I->pcg->lnk.p, s);
+        built = m;
+    }
+    void stats(const PoissonGeo &g, const PcgGeo &wg, int m, double *d_stats, hipStream_t s) override
+    {
+        build(g, wg, m, s);
+        launch_volume_subflow_stats(g, wg, geo(wg), dj.data(), ds.data(), m, st, I->pcg->lnk.p, d_stats, s);
+    }
+    int setup(const PoissonGeo &g, const PcgGeo &wg, bool lap, int mv, float *R, double *bb) override
+    {
+        PcgState &S = *I->pcg;
+        int rc;
+        for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
+            if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
+        lt_at = (size_t)wg.stride * g.C * mv;
+        if ((rc = ensure(I, S.rho, sizeof(float) * 2 * lt_at, false))) return rc;
+        if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
+        if (mv != built) build(g, wg, mv, I->stream);      // a volume left: dj and ds moved up, the links follow
+        float *rho = (float *)S.rho.p;
+        launch_volume_subflow_setup(g, wg, geo(wg), lap, dj.data(), ds.data(), mv, st, S.lnk.p, rho + lt_at, rho, R, (float *)S.e.p, (float *)S.s.p,
+                                    (float *)S.f.p, (float *)S.dg.p, bb, I->stream);
+        return SC_OK;
+    }
+    void apply(const PcgGeo &wg, int planes, bool residual, const float *P, float *Q, double *parts, hipStream_t s) override
+    {
+        PcgState &S = *I->pcg;
+        float *rho = (float *)S.rho.p;
+        launch_volume_subflow_op(wg, geo(wg), planes, chan, residual, st, S.lnk.p, P, (const float *)S.e.p, (const float *)S.s.p, (const float *)S.f.p,
+                                 (const float *)S.dg.p, rho + lt_at, rho, Q, parts, s);
+    }
+};
+
+// the links of one chunk and the build's scratch
+int subflow_links_ensure(Instance *I, const sc_volume_wls_params *p, const sc_poisson_layout *l, int kind, int volumes)
+{
+    return ensure(I, I->pcg->lnk, subflow_store(flow_work_geo(p, l, kind), subflow_chunk_volumes(volumes, l->channels, p->frames)).total, false);
 }
 
 // ---- the robust volume call: the volume operator with the links of the current round -- round 0 from the caller's arrays (the WLS
@@ -588,6 +655,49 @@ int sc_hip_volume_flow(void *inst, const sc_volume_wls_params *p, const sc_poiss
     if ((rc = flow_links_ensure(I, p, l, kind))) return rc;
     const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
     VolumeFlowOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, lap, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    a.flow_x = flow_x;
+    a.flow_y = flow_y;
+    return pcg_host_call(I, volume_flow_call(kind, p, l), l, carries_of(weight != nullptr, links, tlinks) | FLOAT_FLOW, a, op);
+}
+
+int sc_hip_volume_subflow_check(const sc_volume_wls_params *p, const sc_poisson_layout *l)
+{
+    return volume_flow_validate(p, l, nullptr);
+}
+
+// (without flow arrays the call is sc_hip_volume_wls: its validation, its operator, its launches)
+int sc_hip_volume_subflow_device(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, sc_volume_flow_job *jobs, int n, bool bSync)
+{
+    const bool flow = jobs && n > 0 && (jobs[0].flow_x || jobs[0].flow_y);
+    Instance *I;
+    int kind, rc = flow ? pcg_begin(inst, p, l, volume_flow_validate, METHOD_WHY, FP64_WHY, I, kind)
+                        : pcg_begin(inst, p, l, volume_wls_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    auto links_of = [](const sc_volume_flow_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, j.lap, j.flow_x, j.flow_y }; };
+    if (!flow) return volume_device_call<VolumeOperator>(I, volume_call(kind, p), p, l, jobs, n, bSync, links_of);
+    if ((rc = subflow_links_ensure(I, p, l, kind, n))) return rc;
+    const VolumeSubflowParams sp{ p, n };
+    return volume_device_call<VolumeSubflowOperator>(I, volume_flow_call(kind, p, l), &sp, l, jobs, n, bSync, links_of);
+}
+
+int sc_hip_volume_subflow(void *inst, const sc_volume_wls_params *p, const sc_poisson_layout *l, const float *gx, const float *gy, const float *gt,
+                          const float *lap, const float *data, const float *state, const float *weight, const float *smooth_x, const float *smooth_y,
+                          const float *smooth_t, const float *flow_x, const float *flow_y, const float *boundary, float *out)
+{
+    if (!flow_x && !flow_y)
+        return sc_hip_volume_wls(inst, p, l, gx, gy, gt, lap, data, state, weight, smooth_x, smooth_y, smooth_t, boundary, out);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_flow_validate, METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial link 1)"; return SC_ERR_BAD_ARG; }
+    if (!flow_x != !flow_y) { I->err = FLOW_PAIR_WHY; return SC_ERR_BAD_ARG; }
+    if ((rc = subflow_links_ensure(I, p, l, kind, 1))) return rc;
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    const VolumeSubflowParams sp{ p, 1 };
+    VolumeSubflowOperator op(I, &sp, links, tlinks);
     FloatArrays a{ gx, gy, lap, data, weight, boundary, out, smooth_x, smooth_y, state };
     a.gt = gt;
     a.smooth_t = smooth_t;

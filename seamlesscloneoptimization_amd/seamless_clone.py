@@ -672,13 +672,60 @@ def _along_flow(a, flow, loop=False, wrap=""):
     return np.where(sel, partner, a[:nxt.shape[0]]), inside
 
 
-def inpaint_video(frames, holes, tau=1.0, flow=None, gpu_id=0, **solver):
+def _subpixel_flow_of(flow, frames, loop=False):
+    """the flow of a video as volume_subflow_planes checks it, values as they are: float32 (T - 1) x H x W x 2, with loop T"""
+    fx, fy = capi.volume_subflow_planes(flow, frames.shape[0], frames.shape[1], frames.shape[2], loop)
+    return np.stack([fx, fy], -1)
+
+
+def _subpixel_taps(flow, H, W, wrap=""):
+    """sc_hip_volume_subflow's taps of a float32 flow (Tf x H x W x 2) on the whole frame: (ty, tx, b, inside) -- per tap k of 4 its row,
+    its column (clipped into the frame) and its float32 weight (0: no part of the link), and where the pixel holds a link: both components
+    finite and at most 1e6, every tap of non-zero weight inside the frame (an axis named in wrap wraps)"""
+    flow = np.asarray(flow, np.float32)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(flow) <= np.float32(1e6)).all(-1)
+    f = np.where(ok[..., None], flow, np.float32(0))
+    f0 = np.floor(f)
+    a = f - f0
+    i0 = f0.astype(np.int64)
+    one = np.float32(1)
+    wx, wy = (one - a[..., 0], a[..., 0]), (one - a[..., 1], a[..., 1])
+    yy, xx = np.mgrid[0:H, 0:W]
+    tys, txs, bs = [], [], []
+    for k in range(4):
+        w = wx[k & 1] * wy[k >> 1]
+        tx, ty = xx[None] + i0[..., 0] + (k & 1), yy[None] + i0[..., 1] + (k >> 1)
+        if "x" in wrap:
+            tx %= W
+        if "y" in wrap:
+            ty %= H
+        part = w != 0
+        ok = ok & ~(part & ~((tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)))
+        tys.append(np.clip(ty, 0, H - 1)); txs.append(np.clip(tx, 0, W - 1)); bs.append(w)
+    return tys, txs, [np.where(ok, w, np.float32(0)) for w in bs], ok
+
+
+def _along_subpixel_flow(a, flow, loop=False, wrap=""):
+    """_along_flow for a real-valued flow: partner[t][p] = sum_k b_k a[t + 1][q_k(p)], the bilinear interpolation of the next frame at
+    p + flow(p) with sc_hip_volume_subflow's taps, in float64; inside: where p holds a link.  partner is a[t][p] itself where it does not."""
+    T, H, W = a.shape[:3]
+    nxt = np.asarray(np.roll(a, -1, 0) if loop else a[1:], np.float64)
+    tys, txs, bs, inside = _subpixel_taps(flow, H, W, wrap)
+    tt = np.arange(nxt.shape[0])[:, None, None]
+    ext = (1,) * (a.ndim - 3)
+    partner = sum(b.astype(np.float64).reshape(b.shape + ext) * nxt[tt, ty, tx] for ty, tx, b in zip(tys, txs, bs))
+    return np.where(inside.reshape(inside.shape + ext), partner, a[:nxt.shape[0]]), inside
+
+
+def inpaint_video(frames, holes, tau=1.0, flow=None, subpixel=False, gpu_id=0, **solver):
     """Membrane fill of a float32 video (T x H x W or T x H x W x C): inpaint() with temporal links of weight tau.  The pixels where
     holes (T x H x W, anything truthy) is set are filled from the pixels around them in space and time, so a place hidden in one frame is
     filled from the frames where it is visible, and the fill does not flicker.  flow ((T - 1) x H x W x 2 of (dx, dy), rounded; NaN: no
     link): the temporal links follow it -- pixel (x, y) of frame t is joined to pixel (x + dx, y + dy) of frame t + 1 --, so a hole is
-    filled from where its surface point is visible, also when the scene moves.  Returns a NEW array; pixels outside the holes keep their
-    bits."""
+    filled from where its surface point is visible, also when the scene moves.  subpixel: the flow is not rounded -- a link joins
+    (x, y) to the bilinear interpolation of frame t + 1 at (x + dx, y + dy) (volume_wls_solve's).  Returns a NEW array; pixels outside
+    the holes keep their bits."""
     if not isinstance(frames, np.ndarray) or frames.dtype != np.float32:
         raise TypeError("frames must be a float32 numpy array")
     if frames.ndim not in (3, 4):
@@ -688,16 +735,17 @@ def inpaint_video(frames, holes, tau=1.0, flow=None, gpu_id=0, **solver):
         raise ValueError("the holes cover every frame: nothing to fill them from")
     state = np.where(h, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
     if flow is not None:
-        return volume_wls_solve(frames, state, tau=tau, neumann=True, flow=flow, gpu_id=gpu_id, **solver)
+        return volume_wls_solve(frames, state, tau=tau, neumann=True, flow=flow, subpixel=subpixel, gpu_id=gpu_id, **solver)
     return volume_solve(frames, state, tau=tau, neumann=True, gpu_id=gpu_id, **solver)
 
 
-def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, flow=None, gpu_id=0, **solver):
+def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, flow=None, subpixel=False, gpu_id=0, **solver):
     """poisson_clone on every frame of float32 videos of one shape (T x H x W or T x H x W x C), the frames joined by temporal links of
     weight tau whose guidance is srcs' difference from frame to frame where both frames' masks (T x H x W) are set, 0 elsewhere: the
     clone follows the source's change over time and does not flicker.  mixed: poisson_clone's, per frame.  flow (inpaint_video's): the
     links follow it and their guidance is srcs' difference along it, srcs[t + 1][m(p)] - srcs[t][p], where both ends are masked.
-    Returns a NEW array."""
+    subpixel: the flow is not rounded and the guidance is srcs' difference along the bilinear link, where the source and all its taps
+    are masked.  Returns a NEW array."""
     for name, a in (("srcs", srcs), ("dsts", dsts)):
         if not isinstance(a, np.ndarray) or a.dtype != np.float32:
             raise TypeError(f"{name} must be a float32 numpy array")
@@ -717,6 +765,17 @@ def poisson_clone_video(srcs, dsts, masks, tau=1.0, mixed=False, flow=None, gpu_
     both = (m[1:] & m[:-1]).reshape(m[1:].shape + (1,) * (srcs.ndim - 3))
     gt = np.where(both, srcs[1:] - srcs[:-1], np.float32(0)).astype(np.float32)
     state = np.where(m, capi.SC_REGION_UNKNOWN, capi.SC_REGION_KNOWN).astype(np.uint8)
+    if flow is not None and subpixel:
+        f = _subpixel_flow_of(flow, dsts)
+        partner, inside = _along_subpixel_flow(srcs, f)
+        tys, txs, bs, _ = _subpixel_taps(f, dsts.shape[1], dsts.shape[2])
+        tt = np.arange(f.shape[0])[:, None, None]
+        both = m[:-1] & inside
+        for ty, tx, b in zip(tys, txs, bs):
+            both &= (b == 0) | m[1:][tt, ty, tx]
+        both = both.reshape(m[1:].shape + (1,) * (srcs.ndim - 3))
+        gt = np.where(both, partner - srcs[:-1], 0.0).astype(np.float32)
+        return volume_wls_solve(dsts, state, gx=gx, gy=gy, gt=gt, tau=tau, neumann=True, flow=f, subpixel=True, gpu_id=gpu_id, **solver)
     if flow is not None:
         f = _flow_of(flow, dsts)
         partner, inside = _along_flow(srcs, f)
@@ -947,7 +1006,8 @@ def make_tileable(image, lam=0.0, axes="xy", gpu_id=0, **solver):
 
 
 def volume_wls_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None,
-                     tau=1.0, loop=False, neumann=True, free_sides=None, periodic="", tol=None, max_iters=None, flow=None, gpu_id=0, **solver):
+                     tau=1.0, loop=False, neumann=True, free_sides=None, periodic="", tol=None, max_iters=None, flow=None, subpixel=False, gpu_id=0,
+                     **solver):
     """volume_solve with a weight on every link: per channel it minimises sum_t [sum w (u_t - d_t)^2 + sum smooth_x (d_x u_t - gx_t)^2 +
     sum smooth_y (d_y u_t - gy_t)^2] + sum_t sum tau smooth_t (u_{t+1} - u_t - gt_t)^2.  smooth_x, smooth_y (together; None: 1): T x H x
     W (x C), each at its link's low end as in region_solve.  smooth_t (None: 1) and gt: element [t] belongs to the link from frame t to
@@ -956,7 +1016,9 @@ def volume_wls_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, wei
     (dx, dy); rounded with np.rint, NaN kept: no link, an occlusion): the temporal link of pixel (x, y) of frame t leads to pixel (x + dx,
     y + dy) of frame t + 1 in place of (x, y) -- sc_hip_volume_flow; of several pixels with one target the first in row-major order holds
     the link; smooth_t and gt stay stored at the link's source.  Strong tau with several pixels of motion needs more iterations: raise
-    max_iters.  None: straight links.  Returns a NEW array."""
+    max_iters.  None: straight links.  subpixel: the flow is passed on as it is (float32, not rounded) and the temporal link of pixel
+    (x, y) leads to the bilinear interpolation of frame t + 1 at (x + dx, y + dy) -- sc_hip_volume_subflow: up to four taps, no matching,
+    any number of links may arrive at a pixel.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     _, data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary = capi.volume_wls_arrays(
         data, state, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau, bool(loop), neumann=neumann, free_sides=free_sides,
@@ -964,6 +1026,10 @@ def volume_wls_solve(data, state, gx=None, gy=None, gt=None, laplacian=None, wei
     if flow is not None:
         capi.volume_flow_planes(flow, data.shape[0], data.shape[1], data.shape[2], bool(loop))      # (its shape, before a device is touched)
     with _instance(gpu_id, solver) as inst:
+        if flow is not None and subpixel:
+            return inst.volume_subflow(data, state, flow, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau=tau,
+                                       loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, tol=tol or 0.0,
+                                       max_iters=max_iters or 0)
         if flow is not None:
             return inst.volume_flow(data, state, flow, weight, smooth_x, smooth_y, smooth_t, gx, gy, gt, laplacian, boundary, tau=tau,
                                     loop=bool(loop), neumann=neumann, free_sides=free_sides, periodic=periodic, tol=tol or 0.0,
@@ -1008,14 +1074,15 @@ def wls_filter_video(frames, lam=1.0, alpha=1.2, eps=1e-4, tau=1.0, guide=None, 
                             smooth_t=st, tau=tau, loop=loop, neumann=True, gpu_id=gpu_id, **solver)
 
 
-def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, tau=1.0, hard=True, loop=False, strength=1.0, flow=None, gpu_id=0,
-                                  **solver):
+def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, tau=1.0, hard=True, loop=False, strength=1.0, flow=None,
+                                  subpixel=False, gpu_id=0, **solver):
     """interpolate_constraints with a guide on a float32 video (T x H x W or T x H x W x C): the values at the pixels where known_mask
     (T x H x W) is set spread through space and time and stop at the guide's edges in both -- every link exp(-d^2 / (2 edge_sigma^2)) +
     1e-3, d the guide's forward difference in x, y or t (edge_sigma None: a tenth of the guide's range).  Scribble, colour or depth
     propagation from a few frames or a few pixels.  hard: the known pixels hold exactly; else they carry the weight `strength`.
     loop: the last frame is joined to the first.  flow (volume_wls_solve's): the temporal links follow it, and a link's d is the guide's
-    difference along it, so the values travel with the scene.  Returns a NEW array."""
+    difference along it, so the values travel with the scene.  subpixel (volume_wls_solve's): the flow is not rounded, and a link's d is
+    the guide's difference along the bilinear link.  Returns a NEW array."""
     values = _video_of("values", values)
     m = _video_masks("known_mask", known_mask, values)
     if guide is None:
@@ -1031,7 +1098,12 @@ def interpolate_constraints_video(values, known_mask, guide, edge_sigma=None, ta
     if not m.any():
         raise ValueError("known_mask is empty: nothing to spread")
     dx, dy, dt = _video_abs_differences(g, loop)
-    if flow is not None:
+    if flow is not None and subpixel:
+        flow = _subpixel_flow_of(flow, values, loop)
+        g4 = g[:, :, :, None] if g.ndim == 3 else g
+        dt = np.sqrt(((_along_subpixel_flow(g4, flow, loop)[0] - g4[:flow.shape[0]]) ** 2).sum(3))
+        solver = dict(solver, flow=flow, subpixel=True)
+    elif flow is not None:
         flow = _flow_of(flow, values, loop)
         g4 = g[:, :, :, None] if g.ndim == 3 else g
         dt = np.sqrt(((_along_flow(g4, flow, loop)[0] - g4[:flow.shape[0]]) ** 2).sum(3))
