@@ -804,7 +804,7 @@ SC_API int sc_hip_robust(void *instance, const sc_robust_params *p, const sc_poi
                          const float *data, const float *weight, const float *smooth_x, const float *smooth_y, const float *boundary,
                          float *out);
 /* The last robust call's last chunk (sc_hip_robust*, sc_hip_region_robust*, sc_hip_volume_robust*, sc_hip_volume_coupled*,
- * sc_hip_volume_flow_robust* or sc_hip_volume_flow_coupled*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
+ * sc_hip_volume_flow_robust*, sc_hip_volume_subflow_robust* or sc_hip_volume_flow_coupled*, whichever the instance ran last), round by round: returns the number of entries, rounds run + 1 (0: no robust call yet); fills the
  * first min(that, cap) of energy[k] = the energy, summed over the chunk's planes, of the iterate that round k produced, and iters[k] =
  * that round's inner iterations.  Either pointer may be NULL. */
 SC_API int sc_hip_robust_trace(void *instance, double *energy, int *iters, int cap);
@@ -1308,8 +1308,8 @@ SC_API int sc_hip_volume_flow(void *instance, const sc_volume_wls_params *p, con
  * Size, chunks, stop rule, SC_WEIGHTED_POLL, SC_ERR_NOT_CONVERGED, methods, SC_FLAG_FFT_FP64 limits, host waits, sc_run_info:
  * sc_hip_volume_flow's, its 32-bit size rule included ((unknowns per frame) * frames below 2^31 - 1, else SC_ERR_BAD_SIZE).
  * Codes: sc_hip_volume_flow's without the refusal of a value that is not a whole number.
- * Not offered: robust or coupled penalties along a sub-pixel flow; a preconditioner that transforms along the trajectories; the 8-bit
- * entry points; an estimator of the flow. */
+ * Robust penalties along a sub-pixel flow: sc_hip_volume_subflow_robust below.  Not offered: coupled penalties along a sub-pixel flow; a
+ * preconditioner that transforms along the trajectories; the 8-bit entry points; an estimator of the flow. */
 /* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
 SC_API int sc_hip_volume_subflow_check(const sc_volume_wls_params *p, const sc_poisson_layout *l);
 /* Device pointers, n volumes of the same shape.  bSync: waits for the stream and records the call's time. */
@@ -1416,8 +1416,8 @@ SC_API int sc_hip_volume_robust(void *instance, const sc_volume_robust_params *p
  * nothing of the job is written, the others run -- for every per-job refusal of sc_hip_volume_robust; exactly one of flow_x / flow_y; a
  * flow where the first volume has none, or the reverse; a flow array overlapping out; a finite flow value, where the flow is read,
  * that is not a whole number.
- * Not offered: sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points.  The coupled forms along a flow:
- * sc_hip_volume_flow_coupled below, with these jobs. */
+ * Not offered: a preconditioner along the trajectories, the 8-bit entry points.  A real-valued flow: sc_hip_volume_subflow_robust below,
+ * with these jobs.  The coupled forms along a flow: sc_hip_volume_flow_coupled below, with these jobs. */
 typedef struct sc_volume_flow_robust_job {   /* sc_volume_robust_job and the two flow arrays, as sc_volume_flow_job has them */
     const float *gx, *gy;    /* `frames` frames, read at links live in the region: required */
     const float *gt;         /* frames - 1 frames (time_periodic: frames), read at live matched links; NULL: zeros */
@@ -1444,6 +1444,46 @@ SC_API int sc_hip_volume_flow_robust(void *instance, const sc_volume_robust_para
                                      const float *gy, const float *gt, const float *data, const float *state, const float *weight,
                                      const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x,
                                      const float *flow_y, const float *boundary, float *out);
+/* ---- robust sub-pixel flow volume solves: Lp penalties on bilinear temporal links -----------------------------------------------------------
+ * sc_hip_volume_robust's problem, parameters and rounds with every temporal link -- its weight c_t = tau * smooth_t, its guidance gt, its
+ * penalty phi_r -- on the bilinear link of sc_hip_volume_subflow: the flow's values are taken as they are.  Per channel the call
+ * minimises over the UNKNOWN pixels of all frames
+ *     sum w phi_q(u - d; eps_d)  +  sum_live x-links c_x phi_p(dx u - gx; eps_g)  +  sum_live y-links c_y phi_p(dy u - gy; eps_g)
+ *                                +  sum_(live links p) c_t(p) phi_r(sum_k b_k(p) u~(q_k(p)) - u~(p) - gt(p); eps_t),
+ * u~ = u at an UNKNOWN pixel and data at a KNOWN one.  The call for a caller whose flow comes from an estimator -- real-valued, and
+ * wrong in places: the flow is not rounded, and under p_time = 1 a link along a wrong vector is down-weighted round by round.
+ * The parameters are sc_volume_robust_params, the jobs sc_volume_flow_robust_job, both unchanged; coupling bits in kind are refused.
+ * The taps (q_k, b_k), the candidates, the liveness of a link, where smooth_t and gt of a link are stored (at its source) and what is
+ * read: sc_hip_volume_subflow's, word for word -- no whole-number refusal, no matching, any number of links may arrive at a pixel.
+ * Rounds.  Round 0 is sc_hip_volume_subflow's system with the caller's arrays and default precond_*, cold-started.  Round k >= 1 is that
+ * system with three replacements at round k - 1's iterate: the weight of the link p holds is robust_link's s = c_t(p) rho_r(t), t =
+ * (hi - u~(p)) - gt(p) with hi = sum_k b_k u~(q_k) accumulated in float32 in tap order (r = 2: c_t(p) in every round); the spatial links
+ * and w' are sc_hip_volume_robust's; the right-hand side's temporal part is B^T S g' with that S.  A link's weight is stored once, at its
+ * source, and both the source's and the taps' rows of the operator read it there: symmetric by construction.  Two launches
+ * (k_subflow_robust_sigma, k_subflow_robust_setup) and one host read per round; the transposed links are built once per chunk and
+ * again when a volume leaves it.  The means are each round's own: tau-bar the mean of the links' weights, a link's share of w-bar its
+ * weight times (1 where its source is KNOWN, else the sum of b over its KNOWN taps).  The preconditioner keeps straight time links:
+ * sc_hip_volume_subflow's and sc_hip_volume_flow_robust's warnings both hold -- a temporal L1 penalty with a small eps_time under a flow
+ * that moves pixels is the expensive regime.  Raise eps_time or max_iters there.
+ * Ties: both arrays NULL (in every volume) runs sc_hip_volume_robust itself; p_grad = p_time = p_data = 2 gives the bytes of
+ * sc_hip_volume_subflow with default precond_*; link arrays of 1.0f give the bytes of NULL arrays; two runs of one call give the same
+ * bytes, whatever arrives where.  No byte tie holds with sc_hip_volume_flow_robust on a whole-numbered flow (the product form rounds
+ * differently); without collisions the two calls run the same rounds.
+ * Trace, rounds, max_rounds, round_tol, SC_ERR_NOT_CONVERGED, sc_run_info: sc_hip_volume_robust's.  Size: sc_hip_volume_flow's 32-bit rule.
+ * Codes: everything sc_hip_volume_robust_check refuses, then SC_ERR_BAD_SIZE as sc_hip_volume_subflow_check.  Per job SC_ERR_BAD_ARG --
+ * nothing of the job is written, the others run -- for every per-job refusal of sc_hip_volume_robust; exactly one of flow_x / flow_y; a
+ * flow where the first volume has none, or the reverse; a flow array overlapping out.
+ * Not offered: coupled penalties along a sub-pixel flow, a preconditioner along the trajectories, the 8-bit entry points. */
+/* Host-only (needs no GPU): SC_OK, or the code a call with these parameters and this layout returns before it runs anything. */
+SC_API int sc_hip_volume_subflow_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l);
+/* Device pointers, n volumes of the same shape (flow_x, flow_y: real values).  bSync: waits for the stream and records the call's time. */
+SC_API int sc_hip_volume_subflow_robust_device(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l,
+                                               sc_volume_flow_robust_job *jobs, int n, bool bSync);
+/* One volume on host arrays, the arrays of sc_hip_volume_flow_robust in its order. */
+SC_API int sc_hip_volume_subflow_robust(void *instance, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx,
+                                        const float *gy, const float *gt, const float *data, const float *state, const float *weight,
+                                        const float *smooth_x, const float *smooth_y, const float *smooth_t, const float *flow_x,
+                                        const float *flow_y, const float *boundary, float *out);
 /* ---- coupled volume solves: isotropic, space-time and joint-channel total variation on frame stacks ---------------------------------------
  * sc_hip_volume_robust with one penalty over several links, as SC_ROBUST_ISOTROPIC and SC_ROBUST_JOINT_CHANNELS couple them on single
  * images (sc_hip_robust, sc_hip_region_robust) -- and a volume's third axis, which those two bits cannot describe.  The parameters and

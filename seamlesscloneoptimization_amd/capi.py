@@ -361,6 +361,10 @@ class VolumeFlowRobustJob(C.Structure):
                 ("boundary", C.c_void_p), ("out", C.c_void_p), ("rc", C.c_int)]
 
 
+# robust sub-pixel flow volume solves (sc_hip_volume_subflow_robust*): Instance.volume_subflow_robust / volume_subflow_robust_device --
+# VolumeRobustParams and VolumeFlowRobustJob themselves; the flow's values as they are, every temporal link a bilinear stencil
+
+
 # coupled volume solves (sc_hip_volume_coupled*): Instance.volume_coupled / volume_coupled_device -- VolumeRobustParams and VolumeRobustJob
 # themselves, the coupling beside them; along a flow (sc_hip_volume_flow_coupled*): Instance.volume_flow_coupled /
 # volume_flow_coupled_device, with VolumeFlowRobustJob
@@ -630,6 +634,13 @@ def load():
     L.sc_hip_volume_flow_robust_device.restype = C.c_int
     L.sc_hip_volume_flow_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 13
     L.sc_hip_volume_flow_robust.restype = C.c_int
+    L.sc_hip_volume_subflow_robust_check.argtypes = [C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)]
+    L.sc_hip_volume_subflow_robust_check.restype = C.c_int
+    L.sc_hip_volume_subflow_robust_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout),
+                                                      C.POINTER(VolumeFlowRobustJob), C.c_int, C.c_bool]
+    L.sc_hip_volume_subflow_robust_device.restype = C.c_int
+    L.sc_hip_volume_subflow_robust.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.POINTER(PoissonLayout)] + [C.c_void_p] * 13
+    L.sc_hip_volume_subflow_robust.restype = C.c_int
     L.sc_hip_volume_coupled_check.argtypes = [C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout)]
     L.sc_hip_volume_coupled_check.restype = C.c_int
     L.sc_hip_volume_coupled_device.argtypes = [C.c_void_p, C.POINTER(VolumeRobustParams), C.c_int, C.POINTER(PoissonLayout),
@@ -1239,6 +1250,19 @@ def volume_flow_robust_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, f
     p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
                            float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
     return _check_call("sc_hip_volume_flow_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
+                       row_stride=row_stride, channel_stride=channel_stride)
+
+
+def volume_subflow_robust_check(kind: int = SC_POISSON_GUIDANCE, frames: int = 2, frame_stride: int = 0, tau: float = 1.0, time_periodic: int = 0,
+                                p_grad: float = 1.0, eps_grad: float = 1e-3, p_time: float = 1.0, eps_time: float = 1e-3, p_data: float = 2.0,
+                                eps_data: float = 1e-3, max_rounds: int = 0, round_tol: float = 0.0, tol: float = 0.0, max_iters: int = 0,
+                                layout: "PoissonLayout | None" = None, *, cols=None, rows=None, channels=None, col_stride=None, row_stride=None,
+                                channel_stride=None) -> int:
+    """Host-only sc_hip_volume_subflow_robust_check: volume_flow_robust_check's codes -- the robust sub-pixel call takes the robust flow
+    call's parameters unchanged."""
+    p = VolumeRobustParams(int(kind), int(frames), int(frame_stride), float(tau), int(time_periodic), float(p_grad), float(eps_grad), float(p_time),
+                           float(eps_time), float(p_data), float(eps_data), int(max_rounds), float(round_tol), float(tol), int(max_iters))
+    return _check_call("sc_hip_volume_subflow_robust_check", p, layout, cols=cols, rows=rows, channels=channels, col_stride=col_stride,
                        row_stride=row_stride, channel_stride=channel_stride)
 
 
@@ -1871,6 +1895,32 @@ class Instance:
         flow_y are dense W x H x (T - 1; periodic time: T) float32 whatever the layout.  Codes as volume_robust_device."""
         return self._device_call("sc_hip_volume_flow_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
+    # ---- robust sub-pixel flow volume solves on float32 arrays
+    def volume_subflow_robust(self, gx, gy, data, state, flow, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None,
+                              tau=1.0, loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3,
+                              p_data=2.0, eps_data=1e-3, max_rounds=0, round_tol=0.0, tol=0.0, max_iters=0, allow_not_converged=False):
+        """sc_hip_volume_subflow_robust on numpy float32 arrays: volume_flow_robust()'s problem, keywords and result with `flow` taken as it
+        is -- a temporal link, its penalty phi_r included, joins a pixel to the bilinear interpolation of the next frame at (x + dx,
+        y + dy) (volume_subflow_planes' rules: float32, not rounded, NaN = no link).  gt and smooth_t stay stored at a link's source
+        pixel.  flow None: volume_robust() itself."""
+        kind, data, state, weight, sx, sy, smt, gx, gy, gt, boundary = volume_robust_arrays(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t,
+                                                                                            gt, boundary, tau, loop, neumann, free_sides, periodic,
+                                                                                            p_grad, eps_grad, p_time, eps_time, p_data, eps_data)
+        fx, fy = (None, None) if flow is None else volume_subflow_planes(flow, data.shape[0], data.shape[1], data.shape[2], loop)
+        layout = poisson_layout_of(data[0])
+        p = volume_robust_params(kind, data.shape[0], data[0].size, tau, loop, p_grad, eps_grad, p_time, eps_time, p_data, eps_data, max_rounds,
+                                 round_tol, tol, max_iters)
+        out = np.empty_like(data)
+        rc = self.L.sc_hip_volume_subflow_robust(self.h, C.byref(p), C.byref(layout), *(None if a is None else a.ctypes.data for a in
+                                                 (gx, gy, gt, data, state, weight, sx, sy, smt, fx, fy, boundary)), out.ctypes.data)
+        self._check(rc, allow=(SC_ERR_NOT_CONVERGED,) if allow_not_converged else ())
+        return out
+
+    def volume_subflow_robust_device(self, params: VolumeRobustParams, layout: PoissonLayout, jobs, sync=True, allow_job_errors=False):
+        """sc_hip_volume_subflow_robust_device: volume_flow_robust_device()'s jobs (make_volume_flow_robust_jobs) with flow_x, flow_y
+        real-valued.  Codes as volume_robust_device."""
+        return self._device_call("sc_hip_volume_subflow_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
+
     # ---- coupled volume solves on float32 arrays
     def volume_coupled(self, coupling, gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, gt=None, boundary=None, tau=1.0,
                        loop=False, neumann=False, free_sides="", periodic="", p_grad=1.0, eps_grad=1e-3, p_time=1.0, eps_time=1e-3, p_data=2.0,
@@ -1963,7 +2013,7 @@ class Instance:
         return self._device_call("sc_hip_robust_device", params, layout, jobs, sync, allow_job_errors, (SC_ERR_NOT_CONVERGED,))
 
     def robust_trace(self):
-        """(energy, iters) of the last robust call's last chunk (robust, region_robust, volume_robust, volume_coupled, volume_flow_robust or volume_flow_coupled, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
+        """(energy, iters) of the last robust call's last chunk (robust, region_robust, volume_robust, volume_coupled, volume_flow_robust, volume_subflow_robust or volume_flow_coupled, whichever ran last): float64 and int32 arrays with one entry per round, the quadratic one
         included -- the energy (summed over the chunk's planes) of the iterate that round produced and its inner iterations."""
         n = int(self.L.sc_hip_robust_trace(self.h, None, None, 0))
         energy, iters = np.zeros(n, np.float64), np.zeros(n, np.int32)

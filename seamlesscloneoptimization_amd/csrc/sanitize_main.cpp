@@ -24,8 +24,8 @@
 //      exponent, every eps, round_tol and tol.
 //      sc_hip_bounded_check: the region call's verdicts under any valid pair of scalar bounds, then lower > upper and a NaN bound.
 //      sc_hip_volume_robust_check: the WLS volume call's verdicts on a guidance base, then every exponent, every eps, round_tol, the coupling
-//      bits, a Laplacian base and the WLS volume call's own refusals; sc_hip_volume_flow_robust_check beside every one of these calls: the
-//      same parameters, the same verdicts.
+//      bits, a Laplacian base and the WLS volume call's own refusals; sc_hip_volume_flow_robust_check and
+//      sc_hip_volume_subflow_robust_check beside every one of these calls: the same parameters, the same verdicts.
 //      sc_hip_volume_coupled_check: every legal coupling accepted, TIME alone and unknown bits refused, unequal p or eps under TIME
 //      refused, the coupling bits in kind still refused; sc_hip_volume_flow_coupled_check beside every one of these calls: the same
 //      parameters and coupling, the same verdicts.
@@ -532,11 +532,11 @@ int main()
                 const int fr = tp ? 3 : 2;
                 const sc_volume_robust_params good{ k.kind, fr, span, 1.f, tp, 1.f, 1e-3f, 1.f, 1e-3f, 2.f, 0.f, 0, 0.f, k.tol, k.iters };
                 sc_volume_robust_params vr = good;
-                // sc_hip_volume_flow_robust_check beside every call: the same parameters, the same verdicts (these sizes lie far below the
-                // link planes' 32-bit limit); a verdict that differs is no code at all
+                // sc_hip_volume_flow_robust_check and sc_hip_volume_subflow_robust_check beside every call: the same parameters, the same
+                // verdicts (these sizes lie far below the links' 32-bit limit); a verdict that differs is no code at all
                 auto robust_checks = [](const sc_volume_robust_params *vp, const sc_poisson_layout *vl) {
                     const int v = sc_hip_volume_robust_check(vp, vl);
-                    return sc_hip_volume_flow_robust_check(vp, vl) == v ? v : -1000;
+                    return sc_hip_volume_flow_robust_check(vp, vl) == v && sc_hip_volume_subflow_robust_check(vp, vl) == v ? v : -1000;
                 };
                 const int verdict = robust_checks(&vr, &l);
                 if (lap_base ? verdict == SC_OK : verdict != k.want) return fail("volume_robust_check");

@@ -567,6 +567,17 @@ void launch_volume_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const Vol
 void launch_volume_flow_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
                                      const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const int *fwd, const int *bwd,
                                      const float *U, float *R, float *E, float *S, float *F, float *Dg, double *bb, double *sums, hipStream_t s);
+// the robust sub-pixel flow volume call's launch (sc_volume_subflow_robust.hip), two kernels on one grid: k_subflow_robust_sigma writes
+// LT = robust_link(time, lt, sum_k b_k u~(q_k), u~(p), gt).s of every live bilinear link at its source and SG = LT * g' where
+// launch_volume_subflow_setup writes them (u~: U at an UNKNOWN pixel, data at a KNOWN one) and its block's temporal sums into tp
+// (subflow_robust_partials(planes) doubles); k_subflow_robust_setup is launch_volume_robust_setup's spatial walk with
+// launch_volume_subflow_setup's temporal part of b, F and Dg, and adds its block's tp into the sums: launch_volume_robust_setup's five
+// fields, a temporal link counted once, at its source, with launch_volume_subflow_stats' UNKNOWN - KNOWN share
+size_t subflow_robust_partials(int planes);
+void launch_volume_subflow_robust_setup(const PoissonGeo &g, const PcgGeo &wg, const VolumeGeo &vg, const PoissonJobDev *jobs, const SideArrays *sides, int m,
+                                        const RobustTerm &grad, const RobustTerm &time, const RobustTerm &data, const SubflowStore &st, void *lnk,
+                                        const float *U, float *LT, float *SG, double *tp, float *R, float *E, float *S, float *F, float *Dg, double *bb,
+                                        double *sums, hipStream_t s);
 // the coupled volume call's two launches (sc_volume_coupled.hip; coupling: ROBUST_ISO | ROBUST_TIME | ROBUST_JOINT, not 0 and effective):
 // k_volume_robust_rho writes rho of every owner's magnitudes to the rho planes and esum as launch_robust_coupled (the gradient-and-time
 // energy's parts; under ROBUST_JOINT on the volume's channel-0 plane only), k_volume_robust_setup_rho is launch_volume_robust_setup with

@@ -41,6 +41,11 @@
 // its base weight, its gt, its penalty -- on the flow call's matched link.  VolumeFlowRobustOperator is VolumeFlowOperator (the matching,
 // the statistics and their judgement, round 0's set-up, k_volume_flow_op) with the robust volume operator's rounds, whose launch is
 // k_volume_flow_robust_setup (sc_volume_flow_robust.hip) through the same link planes, re-matched where a volume has left.
+// sc_hip_volume_subflow_robust (its own three entries, behind sc_hip_volume_flow_robust's): the robust volume call with every temporal
+// link -- its base weight, its gt, its penalty -- on the sub-pixel call's bilinear link.  VolumeSubflowRobustOperator is
+// VolumeSubflowOperator (the transposed links, the statistics, round 0's set-up, k_subflow_rho and k_subflow_op) with the robust volume
+// operator's rounds, whose launch is sc_volume_subflow_robust.hip's two kernels: they rewrite LT and SG in PcgState::rho and the spatial
+// planes, the operator's launches stay as they are.
 #include "sc_pcg.h"
 #include <algorithm>
 #include <cassert>
@@ -325,13 +330,14 @@ int subflow_chunk_volumes(int volumes, int channels, int frames)
 {
     return std::max(1, std::min(volumes, SC_POISSON_MAX_PLANES / (channels * frames)));
 }
-struct VolumeSubflowOperator final : VolumeOperator {
+// (nround_: the sums of a round, for the robust sub-pixel call that stands on this operator)
+struct VolumeSubflowOperator : VolumeOperator {
     int built = -1;      // the volumes whose links stand, in dj's order
     int chan = 1;        // the call's channels: the planes that share a volume's links
     size_t lt_at = 0;    // where LT starts in PcgState::rho, in floats
     const int volumes;   // of the call
-    VolumeSubflowOperator(Instance *I_, const VolumeSubflowParams *c, bool links_, bool tlinks_)
-        : VolumeOperator(I_, c->p, links_, tlinks_, 0, OwnStats{ VOLUME_STATS }), volumes(c->volumes) {}
+    VolumeSubflowOperator(Instance *I_, const VolumeSubflowParams *c, bool links_, bool tlinks_, int nround_ = 0)
+        : VolumeOperator(I_, c->p, links_, tlinks_, nround_, OwnStats{ VOLUME_STATS }), volumes(c->volumes) {}
     // (the entries have made PcgState::lnk large enough for a chunk: subflow_links_ensure)
     SubflowStore st{};   // where they lie in PcgState::lnk (build)
     void begin() override { VolumeOperator::begin(); built = -1; }
@@ -354,7 +360,8 @@ struct VolumeSubflowOperator final : VolumeOperator {
         for (DevBuf *b : { &S.e, &S.s, &S.dg, &S.f, &S.dct })
             if ((rc = ensure(I, *b, sizeof(float) * (size_t)wg.stride * g.C * mv, false))) return rc;
         lt_at = (size_t)wg.stride * g.C * mv;
-        if ((rc = ensure(I, S.rho, sizeof(float) * 2 * lt_at, false))) return rc;
+        // (a call with rounds: a round's temporal partials lie behind rho | LT)
+        if ((rc = ensure(I, S.rho, sizeof(float) * 2 * lt_at + (nround ? sizeof(double) * subflow_robust_partials(g.C * mv) : 0), false))) return rc;
         if ((rc = ensure(I, S.tab, sizeof(double) * SC_POISSON_MAX_PLANES + sizeof(float) * (size_t)T * T, false))) return rc;
         if (mv != built) build(g, wg, mv, I->stream);      // a volume left: dj and ds moved up, the links follow
         float *rho = (float *)S.rho.p;
@@ -502,6 +509,42 @@ struct VolumeFlowRobustOperator final : VolumeFlowOperator, RobustRounds {
         }
         launch_volume_flow_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, fwd(), bwd(c.wg), c.U, c.R, (float *)S.e.p,
                                         (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb, c.d_round, I->stream);
+        return SC_OK;
+    }
+    void take(const double *t) override { wsum = t[0]; ssum = t[1]; tsum = t[2]; uksum = t[3]; links = tlinks = true; }
+};
+
+// ---- the robust sub-pixel flow volume call: the sub-pixel operator -- its transposed links, statistics, round 0's set-up, k_subflow_rho
+// and k_subflow_op -- with the robust volume operator's rounds: a later round's LT, SG and spatial planes from the iterate
+// (sc_volume_subflow_robust.hip).  The call has no coupling: its check refuses the bits.
+struct VolumeSubflowRobustParams { const sc_volume_robust_params *p; int volumes; };
+struct VolumeSubflowRobustOperator final : VolumeSubflowOperator, RobustRounds {
+    const bool base_links, base_tlinks;
+    VolumeSubflowRobustOperator(Instance *I_, const VolumeSubflowRobustParams *c, bool links_, bool tlinks_)
+        : VolumeSubflowRobustOperator(I_, c->p, wls_params_of(c->p), c->volumes, links_, tlinks_) {}
+    VolumeSubflowRobustOperator(Instance *I_, const sc_volume_robust_params *p, const sc_volume_wls_params &q, int volumes_, bool links_, bool tlinks_)
+        : VolumeSubflowRobustOperator(I_, p, VolumeSubflowParams{ &q, volumes_ }, links_, tlinks_) {}
+    VolumeSubflowRobustOperator(Instance *I_, const sc_volume_robust_params *p, const VolumeSubflowParams &sp, bool links_, bool tlinks_)
+        : VolumeSubflowOperator(I_, &sp, links_, tlinks_, VOLUME_ROBUST_SUMS),
+          RobustRounds(robust_term(p->p_grad, p->eps_grad), robust_term(p->p_data, p->eps_data), robust_term(p->p_time, p->eps_time), p->max_rounds,
+                       p->round_tol, p->kind, VOLUME_ROBUST_SUMS),
+          base_links(links_), base_tlinks(tlinks_) {}
+    RobustRounds *rounds() override { return this; }
+    int coupling(int) const override { return 0; }
+    void begin() override
+    {
+        VolumeSubflowOperator::begin();
+        links = base_links;          // round 0 of a new chunk: the caller's arrays again
+        tlinks = base_tlinks;
+    }
+    int launch(PcgChunk &c, int, double *) override
+    {
+        PcgState &S = *I->pcg;
+        if (c.mv != built) build(c.g, c.wg, c.mv, I->stream);      // the links lie in the order of the volumes that stay
+        float *rho = (float *)S.rho.p;
+        launch_volume_subflow_robust_setup(c.g, c.wg, geo(c.wg), dj.data(), ds.data(), c.mv, grad, time, data, st, S.lnk.p, c.U, rho + lt_at, rho,
+                                           (double *)(rho + 2 * lt_at), c.R, (float *)S.e.p, (float *)S.s.p, (float *)S.f.p, (float *)S.dg.p, c.d_bb,
+                                           c.d_round, I->stream);
         return SC_OK;
     }
     void take(const double *t) override { wsum = t[0]; ssum = t[1]; tsum = t[2]; uksum = t[3]; links = tlinks = true; }
@@ -771,6 +814,51 @@ int sc_hip_volume_flow_robust(void *inst, const sc_volume_robust_params *p, cons
     if ((rc = flow_links_ensure(I, &q, l, kind))) return rc;
     const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
     VolumeFlowRobustOperator op(I, p, links, tlinks);
+    FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
+    a.gt = gt;
+    a.smooth_t = smooth_t;
+    a.flow_x = flow_x;
+    a.flow_y = flow_y;
+    return pcg_host_call(I, volume_flow_robust_call(kind, p, l), l, carries_of(weight != nullptr, links, tlinks) | FLOAT_FLOW, a, op, robust_chunk);
+}
+
+int sc_hip_volume_subflow_robust_check(const sc_volume_robust_params *p, const sc_poisson_layout *l)
+{
+    return volume_flow_robust_validate(p, l, nullptr);
+}
+
+// (without flow arrays the call is sc_hip_volume_robust: its validation, its operator, its launches)
+int sc_hip_volume_subflow_robust_device(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, sc_volume_flow_robust_job *jobs, int n,
+                                        bool bSync)
+{
+    const bool flow = jobs && n > 0 && (jobs[0].flow_x || jobs[0].flow_y);
+    Instance *I;
+    int kind, rc = flow ? pcg_begin(inst, p, l, volume_flow_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind)
+                        : pcg_begin(inst, p, l, volume_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    auto links_of = [](const sc_volume_flow_robust_job &j) { return VolumeLinks{ j.smooth_x, j.smooth_y, j.smooth_t, nullptr, j.flow_x, j.flow_y }; };
+    if (!flow) return volume_device_call<VolumeRobustOperator>(I, volume_robust_call(kind, p), p, l, jobs, n, bSync, links_of, robust_chunk);
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = subflow_links_ensure(I, &q, l, kind, n))) return rc;
+    const VolumeSubflowRobustParams sp{ p, n };
+    return volume_device_call<VolumeSubflowRobustOperator>(I, volume_flow_robust_call(kind, p, l), &sp, l, jobs, n, bSync, links_of, robust_chunk);
+}
+
+int sc_hip_volume_subflow_robust(void *inst, const sc_volume_robust_params *p, const sc_poisson_layout *l, const float *gx, const float *gy,
+                                 const float *gt, const float *data, const float *state, const float *weight, const float *smooth_x,
+                                 const float *smooth_y, const float *smooth_t, const float *flow_x, const float *flow_y, const float *boundary, float *out)
+{
+    if (!flow_x && !flow_y) return sc_hip_volume_robust(inst, p, l, gx, gy, gt, data, state, weight, smooth_x, smooth_y, smooth_t, boundary, out);
+    Instance *I;
+    int kind, rc = pcg_begin(inst, p, l, volume_flow_robust_validate, ROBUST_METHOD_WHY, FP64_WHY, I, kind);
+    if (rc) return rc;
+    if (!smooth_x != !smooth_y) { I->err = "smooth_x and smooth_y go together (both NULL: every spatial base link 1)"; return SC_ERR_BAD_ARG; }
+    if (!flow_x != !flow_y) { I->err = FLOW_PAIR_WHY; return SC_ERR_BAD_ARG; }
+    const sc_volume_wls_params q = wls_params_of(p);
+    if ((rc = subflow_links_ensure(I, &q, l, kind, 1))) return rc;
+    const bool links = smooth_x != nullptr, tlinks = smooth_t != nullptr;
+    const VolumeSubflowRobustParams sp{ p, 1 };
+    VolumeSubflowRobustOperator op(I, &sp, links, tlinks);
     FloatArrays a{ gx, gy, nullptr, data, weight, boundary, out, smooth_x, smooth_y, state };
     a.gt = gt;
     a.smooth_t = smooth_t;

@@ -1140,7 +1140,7 @@ def make_loop(frames, lam=1e-2, tau=1.0, gpu_id=0, **solver):
 def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0, loop=False,
                         p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None, periodic="",
                         max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False, spacetime=False, joint_channels=False,
-                        flow=None, **solver):
+                        flow=None, subpixel=False, **solver):
     """volume_wls_solve with robust_solve's penalties in place of the squares: per channel it minimises over the UNKNOWN pixels
         sum weight phi_q(u - data) + sum smooth_x phi_p(d_x u - gx) + sum smooth_y phi_p(d_y u - gy) + sum tau smooth_t phi_r(u_{t+1} - u_t - gt),
         phi_e(t) = (2 / e) (t^2 + eps^2)^(e/2),      0 < p, r = p_time, q <= 2,
@@ -1154,9 +1154,18 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     sc_hip_volume_coupled's.  flow (volume_wls_solve's: (T - 1) x H x W x 2, with loop T, of (dx, dy), rounded; NaN: no link): every
     temporal link -- its weight, its gt, its penalty -- joins pixel (x, y) of frame t to pixel (x + dx, y + dy) of frame t + 1, and
     smooth_t and gt stay stored at the link's source; sc_hip_volume_flow_robust.  A flow goes with none of the three coupled forms here:
-    volume_flow_coupled_solve has the coupled penalties along a flow.  Returns a NEW array."""
+    volume_flow_coupled_solve has the coupled penalties along a flow.  subpixel (with a flow, and none of the coupled forms): the flow
+    is passed on as it is (float32, not rounded) and a temporal link joins pixel (x, y) of frame t to the bilinear interpolation of
+    frame t + 1 at (x + dx, y + dy): up to four taps, no matching, gt the wanted difference along that link;
+    sc_hip_volume_subflow_robust.  Returns a NEW array."""
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
+    if subpixel:
+        if flow is None:
+            raise ValueError("subpixel=True needs a flow")
+        if coupling:
+            raise ValueError("subpixel=True goes with none of isotropic, spacetime and joint_channels: coupled penalties along a sub-pixel flow "
+                             "are not offered")
     if flow is not None:
         if coupling:
             raise ValueError("flow= goes with none of isotropic, spacetime and joint_channels: coupled penalties along a flow are not offered here "
@@ -1170,6 +1179,8 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
     with _instance(gpu_id, solver) as inst:
         if coupling:
             return inst.volume_coupled(coupling, gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
+        if flow is not None and subpixel:
+            return inst.volume_subflow_robust(gx, gy, data, state, flow, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
         if flow is not None:
             return inst.volume_flow_robust(gx, gy, data, state, flow, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
         return inst.volume_robust(gx, gy, data, state, weight, smooth_x, smooth_y, smooth_t, gt, boundary, **args)
@@ -1178,7 +1189,7 @@ def volume_robust_solve(gx, gy, data, state, gt=None, weight=None, smooth_x=None
 def volume_flow_coupled_solve(gx, gy, data, state, flow, gt=None, weight=None, smooth_x=None, smooth_y=None, smooth_t=None, boundary=None, tau=1.0,
                               loop=False, p=1.0, p_time=1.0, q=2.0, eps_grad=1e-3, eps_time=1e-3, eps_data=1e-3, neumann=True, free_sides=None,
                               periodic="", max_rounds=None, round_tol=None, tol=None, max_iters=None, gpu_id=0, isotropic=False, spacetime=False,
-                              joint_channels=False, **solver):
+                              joint_channels=False, subpixel=False, **solver):
     """volume_robust_solve's coupled forms with every temporal link along `flow` ((T - 1) x H x W x 2, with loop T, of (dx, dy),
     rounded; NaN: no link): isotropic -- one penalty per pixel over its x- and y-link --, spacetime -- ... and over the temporal link
     the pixel holds, the one that leads from it to pixel (x + dx, y + dy) of frame t + 1 (implies isotropic and needs p_time == p and
@@ -1188,7 +1199,11 @@ def volume_flow_coupled_solve(gx, gy, data, state, flow, gt=None, weight=None, s
         Instance.volume_flow_coupled(capi.volume_coupling(isotropic, spacetime, joint_channels), gx, gy, data, state, flow, weight,
                                      smooth_x, smooth_y, smooth_t, gt, boundary, ...)
     (sc_hip_volume_flow_coupled); flow None: volume_robust_solve's coupled call, none of the three: volume_robust_solve(flow=flow)'s
-    bytes.  Returns a NEW array."""
+    bytes.  subpixel (volume_robust_solve's keyword, kept so that the two signatures stay one): True is refused -- the coupled calls
+    take whole-numbered flows only.  Returns a NEW array."""
+    if subpixel:
+        raise ValueError("subpixel=True: coupled penalties along a sub-pixel flow are not offered (volume_robust_solve and tv_denoise_video take "
+                         "subpixel=True without a coupling)")
     neumann, free_sides = _screened_borders(neumann, free_sides, periodic)
     coupling = capi.volume_coupling(isotropic, spacetime, joint_channels)
     if flow is not None:
@@ -1203,7 +1218,7 @@ def volume_flow_coupled_solve(gx, gy, data, state, flow, gt=None, weight=None, s
 
 
 def tv_denoise_video_along_flow(frames, lam, flow, isotropic=True, spacetime=False, joint_channels=False, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2,
-                                loop=False, max_rounds=None, round_tol=None, gpu_id=0, **solver):
+                                loop=False, max_rounds=None, round_tol=None, gpu_id=0, subpixel=False, **solver):
     """tv_denoise_video with its coupled forms along a flow: the video u that minimises
         lam sum phi_q(u - frames) + (the isotropic / space-time / vectorial total variation of u) with the temporal differences
         u_{t+1}(x + dx, y + dy) - u_t(x, y) over the matched pixels of `flow` (volume_flow_coupled_solve's),
@@ -1211,7 +1226,7 @@ def tv_denoise_video_along_flow(frames, lam, flow, isotropic=True, spacetime=Fal
     tv_denoise_video's other arguments.  The call is
         Instance.volume_flow_coupled(capi.volume_coupling(isotropic, spacetime, joint_channels), 0, 0, frames, all UNKNOWN, flow,
                                      weight=lam, p_grad=p, p_time=p_time, p_data=q, eps_grad=eps_time=eps_data=eps, neumann=True, ...)
-    through volume_flow_coupled_solve.  Returns a NEW array."""
+    through volume_flow_coupled_solve, which refuses subpixel=True.  Returns a NEW array."""
     frames = _video_of("frames", frames)
     if not (np.isfinite(lam) and lam > 0):
         raise ValueError("lam must be finite and > 0")
@@ -1219,11 +1234,11 @@ def tv_denoise_video_along_flow(frames, lam, flow, isotropic=True, spacetime=Fal
     return volume_flow_coupled_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), flow, weight=np.full(frames.shape[:3], lam, np.float32),
                                      tau=tau, loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True,
                                      max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime,
-                                     joint_channels=joint_channels, **solver)
+                                     joint_channels=joint_channels, subpixel=subpixel, **solver)
 
 
 def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, loop=False, max_rounds=None, round_tol=None, gpu_id=0, isotropic=False,
-                     spacetime=False, joint_channels=False, flow=None, **solver):
+                     spacetime=False, joint_channels=False, flow=None, subpixel=False, **solver):
     """Total-variation denoising of a float32 video (T x H x W or T x H x W x C) that does not flicker: the video u that minimises
         lam sum phi_q(u - frames) + sum phi_p(forward differences of u within a frame) + tau sum phi_r(u_{t+1} - u_t),      r = p_time,
     under reflecting borders -- volume_robust_solve with zero guidance, every state unknown, data = frames and weight = lam.  p = 1 is
@@ -1233,8 +1248,9 @@ def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, l
     stay discs), of the space-time gradient's (a moving edge is one surface; needs p_time == p), and over all channels (no colour
     fringes).  flow (volume_robust_solve's; with none of the three coupled forms -- those along a flow:
     tv_denoise_video_along_flow): the temporal term is tau sum phi_r(u_{t+1}(x + dx,
-    y + dy) - u_t(x, y)) over the matched pixels, so a panning shot is neither blurred along its motion nor left to flicker.  Returns a
-    NEW array."""
+    y + dy) - u_t(x, y)) over the matched pixels, so a panning shot is neither blurred along its motion nor left to flicker.  subpixel
+    (volume_robust_solve's): the flow is not rounded and u_{t+1} is interpolated bilinearly at (x + dx, y + dy) -- a slow pan or a zoom,
+    where rounding makes half the links straight again.  Returns a NEW array."""
     frames = _video_of("frames", frames)
     if not (np.isfinite(lam) and lam > 0):
         raise ValueError("lam must be finite and > 0")
@@ -1242,7 +1258,7 @@ def tv_denoise_video(frames, lam, tau=1.0, p=1.0, p_time=1.0, q=2.0, eps=1e-2, l
     return volume_robust_solve(zero, zero, frames, np.zeros(frames.shape[:3], np.uint8), weight=np.full(frames.shape[:3], lam, np.float32), tau=tau,
                                loop=loop, p=p, p_time=p_time, q=q, eps_grad=eps, eps_time=eps, eps_data=eps, neumann=True, max_rounds=max_rounds,
                                round_tol=round_tol, gpu_id=gpu_id, isotropic=isotropic, spacetime=spacetime, joint_channels=joint_channels, flow=flow,
-                               **solver)
+                               subpixel=subpixel, **solver)
 
 
 def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=False, joint_channels=False, tau=1.0, loop=False, p_time=None,
@@ -1266,16 +1282,19 @@ def tv_inpaint_video(frames, hole, p=1.0, eps=1e-2, isotropic=True, spacetime=Fa
 
 
 def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time=1.0, eps=1e-3, anchor=1e-3, loop=False, tau=1.0, max_rounds=None,
-                              round_tol=None, gpu_id=0, flow=None, **solver):
+                              round_tol=None, gpu_id=0, flow=None, subpixel=False, **solver):
     """Integrates a float32 video's gradient field -- gx, gy: forward differences within a frame, T x H x W (x C); gt: from a frame to
     the next, T - 1 frames (loop: T, the last one from frame T - 1 to frame 0) -- into a video with an Lp penalty on the residual of
     every link: p = p_time = 1 (the default) ignores gross outliers in the field (a bad flow vector, a shot cut, a specular frame) that
     a least-squares integration would smear over the video.  known (T x H x W, bool) and values: the pixels that hold exactly (keyframes,
     a lattice of samples).  Neither: the free constant is held by a data term of weight `anchor` towards 0, small enough to leave the
     shape alone.  Reflecting borders.  eps rounds the penalties off near 0, in the field's units.  flow (volume_robust_solve's): gt is a
-    difference along the flow -- element (x, y, t) is u_{t+1}(x + dx, y + dy) - u_t(x, y), stored at the link's source.  Returns a NEW
-    array."""
+    difference along the flow -- element (x, y, t) is u_{t+1}(x + dx, y + dy) - u_t(x, y), stored at the link's source.  subpixel
+    (volume_robust_solve's): the flow is not rounded and gt is the difference along the bilinear link, sum_k b_k u_{t+1}(q_k) - u_t(x, y)
+    (_along_subpixel_flow(u, flow)[0] - u[:-1] of a video u).  Returns a NEW array."""
     gx = _video_of("gx", gx)
+    if subpixel and flow is None:
+        raise ValueError("subpixel=True needs a flow")
     if (known is None) != (values is None):
         raise ValueError("known and values go together")
     if known is None:
@@ -1283,13 +1302,13 @@ def integrate_gradients_video(gx, gy, gt, known=None, values=None, p=1.0, p_time
             raise ValueError("anchor must be finite and > 0")
         return volume_robust_solve(gx, gy, np.zeros_like(gx), np.zeros(gx.shape[:3], np.uint8), gt=gt, weight=np.full(gx.shape[:3], anchor, np.float32),
                                    tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps, neumann=True, max_rounds=max_rounds,
-                                   round_tol=round_tol, gpu_id=gpu_id, flow=flow, **solver)
+                                   round_tol=round_tol, gpu_id=gpu_id, flow=flow, subpixel=subpixel, **solver)
     m = _video_masks("known", known, gx)
     if not m.any():
         raise ValueError("known is empty: nothing holds the video")
     state = np.where(m, capi.SC_REGION_KNOWN, capi.SC_REGION_UNKNOWN).astype(np.uint8)
     return volume_robust_solve(gx, gy, _video_of("values", values), state, gt=gt, tau=tau, loop=loop, p=p, p_time=p_time, eps_grad=eps, eps_time=eps,
-                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, flow=flow, **solver)
+                               neumann=True, max_rounds=max_rounds, round_tol=round_tol, gpu_id=gpu_id, flow=flow, subpixel=subpixel, **solver)
 
 
 def region_robust_solve(gx, gy, data, state, weight=None, smooth_x=None, smooth_y=None, boundary=None, p=1.0, q=2.0, eps_grad=1e-3, eps_data=1e-3,
